@@ -10,7 +10,14 @@ A "step" = one complete ILU(0) factorisation of the device-resident CSR matrix (
 i.e. exactly what `P = ilupp.ILU0Preconditioner(A); P.apply(x)` does, with A and x already in HBM
 when the timed region starts.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--grid G] [--no-cpu] [--no-extra] [--config C2COLD|C2H|C2HP|C3|C4|ILUC|S27|S9]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--grid G] [--dump-outputs DIR]
+                    [--full [--no-cpu] [--no-extra] [--config C2COLD|C2H|C2HP|C3|C4|ILUC|S27|S9]]
+
+A plain run sets up, warms up, times K steps (ms_per_step = wall clock of one), dumps the last step's outputs if asked, and
+prints the result line.  Everything that takes runs of its own (CPU baseline and parity, checksum, copy rate, plain entry,
+refactor loop, extra configs, N > 1 batch checks) runs only with --full.
+--dump-outputs DIR: the last step's applied vector and L, U factors (as ILU0Preconditioner.factors() gives them) as float64
+DIR/{x,L_data,L_indices,L_indptr,U_data,U_indices,U_indptr}.npy; an array longer than DUMP_SAMPLE is cut to a fixed seeded sample.
 
 N > 1: the path does not shard (a single factorisation is one dependency chain), so every rank
 factors its own matrix of a batch (weak scaling, no data-path collective; RCCL only for the barrier,
@@ -18,13 +25,13 @@ the max-over-ranks time and one gather of per-matrix records).  Launched by
 `python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...` (one rank per GPU);
 run without a launcher, `--gpus N` starts that launcher itself -- before anything touches the GPU.
 
-The default run (one GPU) also measures what a matrix that is NOT the benchmark's box gets (C2COLD: the headline step in a fresh process
+--full (one GPU) also measures what a matrix that is NOT the benchmark's box gets (C2COLD: the headline step in a fresh process
 through the plain entry; C2H: the 256^3 mesh with 3 % of its points removed; C2HP: the same under a random symmetric permutation), C3, C4,
 one ILUC config and the multilevel configs (C5: one level, C5M: with the matching, C5L: a 5-level object, C5P: config 5 as named, C5PB: 64
 of those side by side) after the headline one (about a minute; --no-extra skips them), the same step through the entry without the
 entry count ("plain_entry") and a re-factorisation with new values on the analysed pattern ("refactor").  Every extra carries path, roofline,
 the reference's CPU figure and construct_plus_first_apply_s.
---config C3 / C4 add the other BASELINE configs as extra keys of the same JSON line ("extra"):
+--full --config C3 / C4 add the other BASELINE configs as extra keys of the same JSON line ("extra"):
 ILUT(10, 1e-4) on the random diagonally dominant matrix with n = 1e6, ICholT(0, 0) on the 256^3 matrix
 (bytes = read A + write the factors actually produced).  --config S27 / S9: ILU(0) beyond 7-point rows (27-point box
 stencil 128^3, 9-point 2048^2: the level-ordered kernels), same keys.  first_apply_ms: the apply right after construction (it may
@@ -57,6 +64,30 @@ def algorithmic_bytes(n, nnz):
     factor = (12 * nnz + 4 * (n + 1)) + (12 * (nnz + n) + 8 * (n + 1))
     apply_ = 12 * (nnz + n) + 8 * (n + 1) + 32 * n
     return factor, apply_
+
+
+DUMP_SAMPLE = 1 << 20      # entries kept per dumped array (7 arrays x 8 MiB of float64 at most)
+DUMP_SEED = 20240611
+
+
+def _dump_sample(a):
+    """`a` as float64, or a fixed sample of it: DUMP_SAMPLE sorted positions that depend on its length only"""
+    a = np.asarray(a)
+    if a.shape[0] > DUMP_SAMPLE:
+        pos = np.sort(np.random.default_rng([DUMP_SEED, a.shape[0]]).choice(a.shape[0], DUMP_SAMPLE, replace=False))
+        a = a[pos]
+    return a.astype(np.float64)
+
+
+def dump_outputs(outdir, P, x):
+    """--dump-outputs: the last timed step's outputs -- the applied vector `x` (a device tensor) and the factors as
+    ILU0Preconditioner.factors() hands them out (L, U: data, indices, indptr) -- as outdir/<name>.npy"""
+    os.makedirs(outdir, exist_ok=True)
+    arrays = {"x": x.cpu().numpy()}
+    for name, f in zip(("L", "U"), P.factors_info()):
+        arrays.update({name + "_data": f[0], name + "_indices": f[1], name + "_indptr": f[2]})
+    for name, a in arrays.items():
+        np.save(os.path.join(outdir, name + ".npy"), _dump_sample(a))
 
 
 def _same_kernel(profiled, wanted):
@@ -478,13 +509,18 @@ def main():
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--grid", type=int, default=256, help="grid points per dimension (256 = BASELINE config C2)")
-    ap.add_argument("--no-cpu", action="store_true", help="skip the CPU baseline leg")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write the last timed step's outputs as DIR/<name>.npy (float64)")
+    ap.add_argument("--full", action="store_true", help="also run everything beyond the headline: CPU baseline and parity, checksum, copy rate, "
+                                                        "plain entry, refactor loop, extra configs, N > 1 batch checks")
+    ap.add_argument("--no-cpu", action="store_true", help="with --full: skip the CPU baseline leg")
     ap.add_argument("--nrhs", type=int, default=0, help="right-hand sides kept resident (default: one per step, at most 16)")
     ap.add_argument("--cpu-grid", type=int, default=0, help="grid of the CPU baseline sample (default: same as --grid)")
     ap.add_argument("--config", action="append", default=[], choices=["C2", "C2COLD", "C2H", "C2HP", "C3", "C4", "C5", "C5M", "C5P", "C5PB", "C5L", "ILUC", "S27", "S9"],
-                    help="extra configs measured after the headline one (C2 is always the bench line; default: C3, C4, C5, C5M, C5L, C5P, C5PB, ILUC)")
-    ap.add_argument("--no-extra", action="store_true", help="skip the default extra configs (C3, C4, C5, ILUC) and the refactor loop")
+                    help="with --full: extra configs measured after the headline one (C2 is always the bench line; default: C3, C4, C5, C5M, C5L, C5P, C5PB, ILUC)")
+    ap.add_argument("--no-extra", action="store_true", help="with --full: skip the default extra configs (C3, C4, C5, ILUC) and the refactor loop")
     args = ap.parse_args()
+    if args.config and not args.full:
+        ap.error("--config needs --full")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(spawn_ranks(args))
@@ -562,10 +598,12 @@ def main():
     path = P.path()
     analysis_path = P.analysis_path() if hasattr(P, "analysis_path") else "general"
     knames = P.kernel_names() if hasattr(P, "kernel_names") else ()
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, P, txs[(nstep - 1) % nrhs])
     # numeric re-factorisation with NEW values on the analysed pattern + one apply (what a time-stepping caller pays per step),
     # timed the same way: ilupp_hip_ilu0_refactor_device reads the new value array where it lies
     refac = None
-    if not args.no_extra and world == 1:
+    if args.full and not args.no_extra and world == 1:
         td2 = td * 1.0009765625
         torch.cuda.synchronize()
         rn, ra = [], []
@@ -590,7 +628,7 @@ def main():
     # the same step through the entry the reference's constructor maps to (ilupp_hip_ilu0_create_device: no nnz handed in, so the
     # construction reads indptr[n] back before it starts), beside the headline's
     plain = None
-    if world == 1:
+    if args.full and world == 1:
         k = max(3, min(args.steps, 10))
         for it in range(k + 2):
             if it == 2:
@@ -605,16 +643,18 @@ def main():
         plain = {"ms_per_step": 1e3 * pwall, "steps": k,
                  "what": "ILU0Preconditioner_device without nnz (ilupp_hip_ilu0_create_device, what ILU0Preconditioner(A) on device arrays maps to) + one apply, wall clock per step"}
     # apply(ones) with the last factorisation (untimed): compared, as an array, with the CPU leg's
-    tx = txs[0]
-    tx.fill_(1.0)
-    torch.cuda.synchronize()
-    P.apply_device(tx.data_ptr(), n, transpose=False, sync=True)
-    x_gpu = tx.cpu().numpy()
-    checksum = float(x_gpu.sum())
+    checksum = x_gpu = None
+    if args.full:
+        tx = txs[0]
+        tx.fill_(1.0)
+        torch.cuda.synchronize()
+        P.apply_device(tx.data_ptr(), n, transpose=False, sync=True)
+        x_gpu = tx.cpu().numpy()
+        checksum = float(x_gpu.sum())
 
     # what this box's HBM gives a plain device-to-device copy (read + written bytes), next to the 8 TB/s spec peak
     copy_gbs = None
-    if rank == 0:
+    if args.full and rank == 0:
         try:
             src = torch.empty(1 << 27, dtype=torch.float64, device=dev)      # 1 GiB
             dst = torch.empty_like(src)
@@ -638,7 +678,7 @@ def main():
     # the batch through the driver of the N > 1 path (ilupp_amd/batched.py): one record per matrix, gathered on
     # every rank; rank 0 then factors every matrix itself and demands byte-identical outputs
     batch = None
-    if world > 1:
+    if args.full and world > 1:
         def work(member):
             dm, im, pm = batch_matrix(g, member)
             a = [torch.from_numpy(v).to(dev) for v in (dm, im, pm)]
@@ -664,7 +704,7 @@ def main():
     # here -- at n = 1e6 one matrix takes tens of seconds, profiles/r03_c5p.txt), then with default_configuration(1) at n = 1e6
     batch_ml = None
     batch_ml10 = None
-    if world > 1:
+    if args.full and world > 1:
         for preset, nml in ((10, int(os.environ.get("BENCH_C5_N", "1000000"))), (1, int(os.environ.get("BENCH_C5_N", "1000000")))):
             def work_ml(member, preset=preset, nml=nml):
                 return ml_batch_member(dev, member, nml, preset)
@@ -775,7 +815,7 @@ def main():
             out["batch_ml_config10"] = batch_ml10          # BASELINE config 5 as named
         if batch_ml is not None:
             out["batch_ml"] = batch_ml
-        if not args.no_cpu and world == 1:
+        if args.full and not args.no_cpu and world == 1:
             cg = args.cpu_grid or g
             rec, x_cpu = cpu_baseline(cg)
             out["cpu_baseline"] = rec
@@ -788,7 +828,7 @@ def main():
             out["cpu_baseline"] = None
         extra = {}
         cfgs = list(args.config)
-        if not args.no_extra and world == 1:
+        if args.full and not args.no_extra and world == 1:
             cfgs = [c for c in ("C2COLD", "C2H", "C2HP", "C3", "C4", "C5", "C5M", "C5L", "C5P", "C5PB", "ILUC") if c not in cfgs] + cfgs
         for cfg in cfgs:
             if cfg == "C2COLD" and world == 1:

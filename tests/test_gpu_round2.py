@@ -447,7 +447,7 @@ def test_error_paths_of_the_reference():
 _BATCH_SCRIPT = r'''
 import json, os, subprocess, sys
 root = %(root)r
-r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--grid", "48", "--no-cpu"],
+r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--grid", "48", "--full", "--no-cpu"],
                    capture_output=True, text=True, timeout=600, cwd=root)
 line = [l for l in r.stdout.splitlines() if l.startswith("{")]
 assert r.returncode == 0 and line, r.stdout + r.stderr
@@ -468,12 +468,12 @@ def test_batched_two_gpus():
 
 
 def test_bench_two_ranks_on_one_gpu():
-    """bench.py's N > 1 code path where only one GPU is visible: two ranks share GPU 0 over gloo (BENCH_SHARE_GPU=1; the measured runs use
+    """bench.py --full's N > 1 code path where only one GPU is visible: two ranks share GPU 0 over gloo (BENCH_SHARE_GPU=1; the measured runs use
     one rank per GPU over RCCL): both batches -- ILU(0) on shifted meshes, the multilevel preconditioner on n = 10^6 matrices -- gathered
     through run_batch and byte-identical to rank 0's own single-rank run, one JSON line with the whole-job value"""
     import json
     e = dict(os.environ, BENCH_SHARE_GPU="1")
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--grid", "48", "--no-cpu"],
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--grid", "48", "--full", "--no-cpu"],
                        capture_output=True, text=True, timeout=900, cwd=ROOT, env=e)
     line = [l for l in r.stdout.splitlines() if l.startswith("{")]
     assert r.returncode == 0 and len(line) == 1, r.stdout[-2000:] + r.stderr[-2000:]
@@ -491,9 +491,9 @@ def test_bench_two_ranks_on_one_gpu():
 
 
 def test_bench_single_gpu_line():
-    """bench.py's contract on a small grid: one JSON line with roofline, cpu_baseline and an ARRAY parity verdict"""
+    """bench.py --full's contract on a small grid: one JSON line with roofline, cpu_baseline and an ARRAY parity verdict"""
     import json
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1", "--grid", "48", "--no-extra"],
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1", "--grid", "48", "--full", "--no-extra"],
                        capture_output=True, text=True, timeout=900, cwd=ROOT)
     line = [l for l in r.stdout.splitlines() if l.startswith("{")]
     assert r.returncode == 0 and line, r.stdout + r.stderr
@@ -505,11 +505,44 @@ def test_bench_single_gpu_line():
     assert out["cpu_baseline"]["kind"] in ("reference", "port") and out["cpu_baseline"]["apply_paths_agree"]
 
 
+def test_bench_plain_line_and_dumped_outputs(tmp_path):
+    """a plain bench.py run (no --full): the headline fields and none of the runs of their own; --dump-outputs writes the last timed
+    step's vector and factors as float64 arrays, the same in two runs and the oracle's ILU(0) and apply(ones) on the same matrix"""
+    import json
+    import matgen
+    from oracle import oracle as O
+    dd, ii, pp = matgen.poisson3d(48)
+    outs = []
+    for k in range(2):
+        d = str(tmp_path / ("out%d" % k))
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "3", "--warmup", "1", "--grid", "48", "--dump-outputs", d],
+                           capture_output=True, text=True, timeout=600, cwd=ROOT)
+        line = [l for l in r.stdout.splitlines() if l.startswith("{")]
+        assert r.returncode == 0 and len(line) == 1, r.stdout + r.stderr
+        out = json.loads(line[0])
+        assert (out["metric"], out["unit"], out["higher_is_better"], out["dtype"], out["steps"]) == (
+            "ILU(0) factor+apply nnz/s, 3-D 7-pt Poisson fp64", "nnz/s", True, "f64", 3)
+        assert out["ms_per_step"] > 0 and abs(out["value"] - int(pp[-1]) / (out["ms_per_step"] * 1e-3)) <= 1e-9 * out["value"]
+        assert out["cpu_baseline"] is None and out["checksum"] is None and out["roofline"]["copy_GBs_measured"] is None
+        assert not {"extra", "refactor", "plain_entry", "parity"} & set(out)
+        outs.append({f[:-4]: np.load(os.path.join(d, f)) for f in os.listdir(d)})
+    assert sorted(outs[0]) == ["L_data", "L_indices", "L_indptr", "U_data", "U_indices", "U_indptr", "x"]
+    for name, a in outs[0].items():
+        assert a.dtype == np.float64 and np.array_equal(a, outs[1][name]), name
+    Lo, Uo = O.orc().ilu0((dd, ii, pp, True))
+    xo = O.orc().apply_lu(Lo, Uo, np.ones(pp.shape[0] - 1), O.ID)       # (--steps 3 --warmup 1: every step applies to its own vector of ones)
+    got = outs[0]
+    for F, name in ((Lo, "L"), (Uo, "U")):
+        assert np.array_equal(got[name + "_indices"], F[1]) and np.array_equal(got[name + "_indptr"], F[2])
+        assert np.all(np.abs(got[name + "_data"] - F[0]) <= 1e-12 * np.abs(F[0]))
+    assert np.all(np.abs(got["x"] - xo) <= 1e-12 * np.abs(xo))
+
+
 def test_bench_extras_of_every_kind_of_object():
-    """the default run's extra configs build three kinds of objects (single-level ones with a path word, multilevel ones without, the
+    """the --full run's extra configs build three kinds of objects (single-level ones with a path word, multilevel ones without, the
     speculative ICholT path): one of each through bench.py, with their roofline and path fields"""
     import json
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1", "--grid", "48", "--no-extra", "--no-cpu",
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1", "--grid", "48", "--full", "--no-extra", "--no-cpu",
                         "--config", "C4", "--config", "C5", "--config", "ILUC"], capture_output=True, text=True, timeout=1800, cwd=ROOT)
     line = [l for l in r.stdout.splitlines() if l.startswith("{")]
     assert r.returncode == 0 and line, r.stdout + r.stderr

@@ -59,9 +59,8 @@ def test_edges():
 
 
 def test_restatement_vs_reference_live():
-    if not O.ref_available():
-        pytest.skip("oracle/_ref not built (no reference in this environment)")
-    ref = O.ref()
+    import ref_replay
+    ref = ref_replay.ref()            # (oracle/_ref where it is built, else its recorded answers)
     for seed in range(6):
         d, i, p = matgen.random_dd(400 + 37 * seed, k=5 + seed, diag=2.0 + seed, seed=100 + seed)
         n = p.shape[0] - 1
