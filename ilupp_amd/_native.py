@@ -101,6 +101,10 @@ def lib():
     L.ilupp_hip_apply.argtypes = [_VP, _VP, ctypes.c_int64]
     L.ilupp_hip_apply_trans.argtypes = [_VP, _VP, ctypes.c_int64]
     L.ilupp_hip_apply_device.argtypes = [_VP, _VP, ctypes.c_int64, ctypes.c_int, ctypes.c_int]
+    L.ilupp_hip_apply_block.argtypes = [_VP, _VP, ctypes.c_int64, ctypes.c_int64, ctypes.c_int]
+    L.ilupp_hip_apply_block_device.argtypes = [_VP, _VP, ctypes.c_int64, ctypes.c_int64, ctypes.c_int, ctypes.c_int]
+    L.ilupp_hip_block_path.argtypes = [_VP]
+    L.ilupp_hip_block_path.restype = ctypes.c_char_p
     L.ilupp_hip_sync.argtypes = [_VP]
     L.ilupp_hip_release_cached_memory.argtypes = []
     L.ilupp_hip_set_cache_limit.argtypes = [ctypes.c_ulonglong]
@@ -182,6 +186,7 @@ ABI_SYMBOLS = [
     "ilupp_hip_ml_level_copy", "ilupp_hip_ml_timings", "ilupp_hip_solve", "ilupp_hip_ml_create_batch",
     "ilupp_hip_ilucp_create", "ilupp_hip_ilucp_destroy", "ilupp_hip_ilucp_apply", "ilupp_hip_ilucp_total_nnz", "ilupp_hip_ilucp_zero_pivots",
     "ilupp_hip_ilucp_info", "ilupp_hip_ilucp_copy", "ilupp_hip_ilutp_create",
+    "ilupp_hip_apply_block", "ilupp_hip_apply_block_device", "ilupp_hip_block_path",
 ]
 
 
@@ -277,6 +282,37 @@ class Preconditioner:
         rc = lib().ilupp_hip_apply_device(self._h, dptr, n, 1 if transpose else 0, 1 if sync else 0)
         if rc:
             _raise(rc)
+
+    def apply_block(self, X, transpose=False):
+        """X <- M^-1 X (M^-T X with transpose) in place for a writable, C-contiguous 2-D float64 array of shape (n, k): every column
+        as apply / apply_trans gives it, all k in one call (no counterpart in the reference's binding)"""
+        mv = memoryview(X)
+        if mv.ndim != 2:
+            raise RuntimeError("Expected 2D array for b!")
+        if not mv.c_contiguous:
+            raise RuntimeError("Expected contiguous array for b!")
+        if mv.format != "d":
+            raise RuntimeError("Expected d (d) array for b, got %s!" % mv.format)
+        if mv.readonly:
+            raise RuntimeError("b must be writable")
+        n, k = mv.shape
+        a = np.frombuffer(mv, dtype=np.float64) if n * k else np.zeros(1)
+        rc = lib().ilupp_hip_apply_block(self._h, a.ctypes.data, n, k, 1 if transpose else 0)
+        if rc:
+            _raise(rc)
+
+    def apply_block_trans(self, X):
+        self.apply_block(X, transpose=True)
+
+    def apply_block_device(self, dptr, n, k, transpose=False, sync=True):
+        """the block apply on a row-major n x k array in HBM (int address); stream ordering as apply_device"""
+        rc = lib().ilupp_hip_apply_block_device(self._h, dptr, n, k, 1 if transpose else 0, 1 if sync else 0)
+        if rc:
+            _raise(rc)
+
+    def block_path(self):
+        """route of the last block apply: "block:level", "block:columns" or "" (measurement / test hook)"""
+        return lib().ilupp_hip_block_path(self._h).decode()
 
     def sync(self):
         rc = lib().ilupp_hip_sync(self._h)

@@ -229,6 +229,14 @@ struct ilupp_precond {
     bool verdict_clean = false;  // ctrl[8] (the verdict word of grid.hip's proof) is zero already
     bool ctrl_armed = false;     // the control words are zero and both exchange buffers all-sentinel already (arm_apply): the next plain apply starts with its first sweep
     bool borrowed_queue = false; // stream and events belong to another object (the levels of a multilevel preconditioner share one)
+    // block apply (ilupp_hip_apply_block*): buffers kept from one call to the next (grown, never shrunk), the route of the last one
+    double *bxp = nullptr, *by = nullptr;   // n x bkb each: the hand-over buffer and the intermediate chunk of the level route
+    int bkb = 0;
+    double *bcol = nullptr;                 // n: one column of the columns route
+    int32_t *btk = nullptr;                 // [0] a column's sweep timed out (columns route), [1 ..] two tickets per chunk (level route)
+    int64_t btk_cap = 0;
+    const char *block_path = "";
+    bool block_events = false;              // the last apply was a block apply: ev[3] .. ev[2] bracket all of it
 };
 
 namespace {
@@ -253,6 +261,7 @@ void destroy_obj(ilupp_precond *p)
     for (int32_t *d : {p->dL, p->dU, p->dUT, p->dLT}) if (d) (void)pool_free(d);
     if (p->work) (void)pool_free(p->work);
     if (p->xdev) (void)pool_free(p->xdev);
+    for (void *q : {(void *)p->bxp, (void *)p->by, (void *)p->bcol, (void *)p->btk}) if (q) (void)pool_free(q);
     if (p->done) (void)pool_free(p->done);
     if (p->ctrl) (void)pool_free(p->ctrl);
     // streams and events are recycled: creating them costs more than a small kernel
@@ -641,6 +650,24 @@ static const PackedSweep *packed(ilupp_precond *p, int which, SweepKind kind, co
     return ps->valid ? ps : nullptr;
 }
 
+// Rows too long for the level-major records (ILUT factors, ICholT with fill, ILU(0) of a long-row matrix) sweep one lane per row, in
+// level order when the factor has one (sptrsv_lvl.hip; renumbered copy of the factor, built at the first sweep and shared by the single
+// and the block apply: one level order per factor).  nullptr: the sweep of M is another kernel (the caller tells which).
+static bool long_rows(const ilupp_precond *p, const DevMat &M)
+{
+    return (M.nnz > 4 * (int64_t)M.n || (p->kind == KIND_LU && p->fperm != nullptr)) && M.n >= 1024;
+}
+static LevelSweep *level_sweep(ilupp_precond *p, SweepKind kind, const DevMat &M, const Schedule &sch)
+{
+    LevelSweep *ls = &M == &p->Lc ? &p->lvl[0] : &M == &p->Uc ? &p->lvl[1] : &M == &p->UcT ? &p->lvl[2] : &M == &p->LcT ? &p->lvl[3] : nullptr;
+    if (ls && !ls->tried) {
+        if (&M == &p->Lc || &M == &p->Uc) ensure_csr_values(p);
+        const bool reuse = &M == &p->Lc && p->fperm && kind == SWEEP_FWD_LAST_ASC;      // L's rows depend on each other as A's lower part does
+        lvl_build(p->stream, kind, M, sch, ls, reuse ? p->fperm : nullptr, reuse ? p->fperm_levels : 0);
+    }
+    return ls && ls->valid ? ls : nullptr;
+}
+
 static int sweep(ilupp_precond *p, SweepKind kind, const DevMat &M, const Schedule &sch, const int32_t *desc, int32_t maxlen,
                  const PackedSweep *ps, double *rhs, double *out, int32_t *ticket, int32_t *err,
                  double *ypk_out = nullptr, const double *ypk_in = nullptr, const int32_t *ysrc = nullptr)
@@ -664,16 +691,11 @@ static int sweep(ilupp_precond *p, SweepKind kind, const DevMat &M, const Schedu
     // block of consecutive rows.  With blocks, a row waits for everything its lane has to do before it, and the factors of
     // a random matrix have no chains that would make blocks pay: BASELINE config C3's apply took 70 + 186 ms, more than the
     // reference needs on one core.
-    if ((M.nnz > 4 * (int64_t)M.n || (p->kind == KIND_LU && p->fperm != nullptr)) && M.n >= 1024) {
-        // ... and the rows in level order (sptrsv_lvl.hip; renumbered copy of the factor, built at the first sweep): in natural
-        // order only the rows inside the window of resident tickets can run, on a mesh a few grid lines
-        LevelSweep *ls = &M == &p->Lc ? &p->lvl[0] : &M == &p->Uc ? &p->lvl[1] : &M == &p->UcT ? &p->lvl[2] : &M == &p->LcT ? &p->lvl[3] : nullptr;
-        if (ls && !ls->tried) {
-            if (&M == &p->Lc || &M == &p->Uc) ensure_csr_values(p);
-            const bool reuse = &M == &p->Lc && p->fperm && kind == SWEEP_FWD_LAST_ASC;      // L's rows depend on each other as A's lower part does
-            lvl_build(p->stream, kind, M, sch, ls, reuse ? p->fperm : nullptr, reuse ? p->fperm_levels : 0);
-        }
-        if (ls && ls->valid) return sptrsv_lvl(p->stream, *ls, rhs, out, ticket, err);
+    if (long_rows(p, M)) {
+        // ... and the rows in level order: in natural order only the rows inside the window of resident tickets can run, on a mesh a
+        // few grid lines
+        const LevelSweep *ls = level_sweep(p, kind, M, sch);
+        if (ls) return sptrsv_lvl(p->stream, *ls, rhs, out, ticket, err);
         return sptrsv_rows(p->stream, kind, M, rhs, out, ticket, err);
     }
     return sptrsv(p->stream, kind, M, sch, desc, maxlen, rhs, out, ticket, err);
@@ -694,6 +716,24 @@ static bool static_transposed_ready(ilupp_precond *p)
     return false;
 }
 
+// LL^T objects whose factor is stencil-like (IChol0, ICholT without fill on a mesh): the static sweep kernels on the factor's own values,
+// analysed on first use.  The pair (forward, backward) when it exists.
+static bool llt_static_pair(ilupp_precond *p, PackedSweep **pf_out, PackedSweep **pb_out)
+{
+    const bool dl = p->llt_diag_last;
+    PackedSweep *pf = dl ? &p->pkL : &p->pkLT, *pb = dl ? &p->pkLT : &p->pkL;
+    if (!p->pair_tried && !p->degenerate) {
+        p->pair_tried = true;
+        // IChol0: forward over L (row-major, diagonal last), backward over its transposed copy in DESCENDING column order (T4);
+        // ICholT: forward over the row-major copy of L, backward over L's own column-major arrays (T3)
+        const bool ok = dl ? st_analyse_pair(p->stream, p->n, p->Lc, p->LcT, p->sL, p->sLT, pf, pb, true)
+                           : st_analyse_pair(p->stream, p->n, p->LcT, p->Lc, p->sLT, p->sL, pf, pb, false);
+        if (ok) p->pack_tried[0] = p->pack_tried[3] = true;
+    }
+    *pf_out = pf; *pb_out = pb;
+    return pf->valid && pf->pair && pb->valid && pb->pair;
+}
+
 // apply on a device vector; `transpose` as in apply_preconditioner_only(use, y)
 #define SWEEP_OR_RETURN(...) do { const int rc_ = sweep(__VA_ARGS__); if (rc_) return rc_; } while (0)
 int apply_dev(ilupp_precond *p, double *x, int transpose)
@@ -704,6 +744,7 @@ int apply_dev(ilupp_precond *p, double *x, int transpose)
     else ILUPP_HIP(hipMemsetAsync(p->ctrl, 0, 64, st));
     int32_t *err = p->ctrl, *t1 = p->ctrl + 4, *t2 = p->ctrl + 5;
     double *y = p->work;
+    p->block_events = false;
     if (p->kind == KIND_LU) {
         // solve with M (= A for CSR input): fwd(Lc) then bwd(Uc)      [CSR/ID, CSC/TRANSPOSE]
         // solve with M^T:                   fwd(Uc^T) then bwd_desc(Lc^T)  [CSR/TRANSPOSE, CSC/ID]
@@ -764,16 +805,8 @@ int apply_dev(ilupp_precond *p, double *x, int transpose)
         // stencil-like factors (IChol0, ICholT without fill on a mesh): the static sweep kernels on the factor's own values
         {
             const bool dl = p->llt_diag_last;
-            PackedSweep *pf = dl ? &p->pkL : &p->pkLT, *pb = dl ? &p->pkLT : &p->pkL;
-            if (!p->pair_tried && !p->degenerate) {
-                p->pair_tried = true;
-                // IChol0: forward over L (row-major, diagonal last), backward over its transposed copy in DESCENDING column order (T4);
-                // ICholT: forward over the row-major copy of L, backward over L's own column-major arrays (T3)
-                const bool ok = dl ? st_analyse_pair(st, p->n, p->Lc, p->LcT, p->sL, p->sLT, pf, pb, true)
-                                   : st_analyse_pair(st, p->n, p->LcT, p->Lc, p->sLT, p->sL, pf, pb, false);
-                if (ok) p->pack_tried[0] = p->pack_tried[3] = true;
-            }
-            if (pf->valid && pf->pair && pb->valid && pb->pair) {
+            PackedSweep *pf = nullptr, *pb = nullptr;
+            if (llt_static_pair(p, &pf, &pb)) {
                 ILUPP_HIP(hipEventRecord(p->ev[0], st));
                 { const int rc_ = sptrsv_st(st, *pf, dl ? p->sL : p->sLT, p->n, x, y, t1, err, pf->ybuf, nullptr, nullptr); if (rc_) return rc_; }
                 ILUPP_HIP(hipEventRecord(p->ev[1], st));
@@ -821,7 +854,7 @@ int finish_apply(ilupp_precond *p)
     if (p->apply_events_valid) {
         ILUPP_HIP(hipEventElapsedTime(&p->tm.lsolve_kernel_ms, p->ev[0], p->ev[1]));
         ILUPP_HIP(hipEventElapsedTime(&p->tm.usolve_kernel_ms, p->ev[1], p->ev[2]));
-        ILUPP_HIP(hipEventElapsedTime(&p->tm.last_apply_ms, p->ev[0], p->ev[2]));
+        ILUPP_HIP(hipEventElapsedTime(&p->tm.last_apply_ms, p->block_events ? p->ev[3] : p->ev[0], p->ev[2]));
     }
     if (err) {
         // a sweep gave up: restore the all-sentinel invariant of the work vector
@@ -831,6 +864,146 @@ int finish_apply(ilupp_precond *p)
         return ILUPP_ERR_TIMEOUT;
     }
     if (!armed_here) arm_apply(p);
+    return ILUPP_OK;
+}
+
+// ---- block apply: k right-hand sides, X row-major n x k, in place; every column as apply_dev gives it -----------------------------
+// Two routes.  "block:level": both sweeps of the apply are the level-order kernel (sptrsv_lvl.hip) -- the same records walked once per
+// chunk of up to kSptrsmMaxKB columns (sptrsm_lvl.hip).  "block:columns": every other object (the static and packed sweeps of box grids,
+// factors the level order declines, degenerate ones, n < 1024) and k = 1: each column gathered into a vector, apply_dev, scattered back.
+__global__ void k_col_gather(const double *__restrict__ X, int64_t ld, int32_t n, double *__restrict__ col)
+{
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) col[i] = X[i * ld];
+}
+__global__ void k_col_scatter(const double *__restrict__ col, double *__restrict__ X, int64_t ld, int32_t n, const int32_t *__restrict__ err,
+                              int32_t *__restrict__ seen)
+{
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i == 0 && *err) *seen = 1;              // (the next column's apply clears the control words)
+    if (i < n) X[i * ld] = col[i];
+}
+
+// the two sweeps of an apply when both run on the level-order kernel: apply_dev's branches, the same factors, sweep kinds and caches
+static bool block_level_plan(ilupp_precond *p, int transpose, LevelSweep **first, LevelSweep **second)
+{
+    *first = *second = nullptr;
+    if (p->degenerate) return false;
+    auto lvl = [p](int which, SweepKind kind, const DevMat &M, const Schedule &sch, const int32_t *desc, PackedSweep *pk) -> LevelSweep * {
+        if (packed(p, which, kind, M, sch, desc, MAXLEN_OF(M), pk)) return nullptr;      // level-major or static records
+        return long_rows(p, M) ? level_sweep(p, kind, M, sch) : nullptr;
+    };
+    if (p->kind == KIND_LU) {
+        const bool with_MT = (transpose != 0) != p->input_csc;
+        if (!with_MT) {
+            const Schedule &sl = p->sL.start ? p->sL : p->sA;
+            *first = lvl(0, SWEEP_FWD_LAST_ASC, p->Lc, sl, p->dL, &p->pkL);
+            *second = lvl(1, SWEEP_BWD_FIRST_ASC, p->Uc, p->sU, p->dU, &p->pkU);
+        } else {
+            p->pkL.xch_armed = p->pkU.xch_armed = false;
+            if (static_transposed_ready(p)) return false;
+            ensure_transposed(p);
+            *first = lvl(2, SWEEP_FWD_LAST_ASC, p->UcT, p->sUT, p->dUT, &p->pkUT);
+            *second = lvl(3, SWEEP_BWD_FIRST_DESC, p->LcT, p->sLT, p->dLT, &p->pkLT);
+        }
+    } else if (p->kind == KIND_UTU) {
+        ensure_transposed(p);
+        const bool tr = transpose != 0;
+        *first = lvl(tr ? 2 : 3, SWEEP_FWD_LAST_ASC, tr ? p->UcT : p->LcT, tr ? p->sUT : p->sLT, tr ? p->dUT : p->dLT, tr ? &p->pkUT : &p->pkLT);
+        *second = lvl(tr ? 0 : 1, SWEEP_BWD_FIRST_ASC, tr ? p->Lc : p->Uc, tr ? p->sL : p->sU, tr ? p->dL : p->dU, tr ? &p->pkL : &p->pkU);
+    } else {
+        ensure_transposed(p);
+        PackedSweep *pf = nullptr, *pb = nullptr;
+        if (llt_static_pair(p, &pf, &pb)) return false;
+        if (p->llt_diag_last) {       // IChol0: T1(L) then T4(L)
+            *first = lvl(0, SWEEP_FWD_LAST_ASC, p->Lc, p->sL, p->dL, &p->pkL);
+            *second = lvl(3, SWEEP_BWD_FIRST_DESC, p->LcT, p->sLT, p->dLT, &p->pkLT);
+        } else {                      // ICholT: T2(L) then T3(L)
+            *first = lvl(3, SWEEP_FWD_LAST_ASC, p->LcT, p->sLT, p->dLT, &p->pkLT);
+            *second = lvl(0, SWEEP_BWD_FIRST_ASC, p->Lc, p->sL, p->dL, &p->pkL);
+        }
+    }
+    return *first && *second && !p->degenerate;
+}
+
+static int chunk_width(int64_t left) { return left >= kSptrsmMaxKB ? kSptrsmMaxKB : left >= 8 ? 8 : left >= 4 ? 4 : left >= 2 ? 2 : 1; }
+
+// the block buffers for chunks of kb columns and `words` control words (grown only; an earlier asynchronous block apply may still use the
+// old ones, and the pool knows nothing of streams)
+static void block_buffers(ilupp_precond *p, int kb, int64_t words)
+{
+    if (kb <= p->bkb && words <= p->btk_cap) return;
+    ILUPP_HIP(stream_sync(p->stream));
+    if (kb > p->bkb) {
+        for (double **q : {&p->bxp, &p->by}) { if (*q) (void)pool_free(*q); *q = nullptr; }
+        p->bkb = 0;
+        ILUPP_HIP(pool_malloc(&p->bxp, sizeof(double) * (size_t)p->n * (size_t)kb));
+        ILUPP_HIP(pool_malloc(&p->by, sizeof(double) * (size_t)p->n * (size_t)kb));
+        p->bkb = kb;
+    }
+    if (words > p->btk_cap) {
+        if (p->btk) (void)pool_free(p->btk);
+        p->btk = nullptr; p->btk_cap = 0;
+        ILUPP_HIP(pool_malloc(&p->btk, sizeof(int32_t) * (size_t)words));
+        p->btk_cap = words;
+    }
+}
+
+int apply_block_dev(ilupp_precond *p, double *X, int64_t k, int transpose)
+{
+    hipStream_t st = p->stream;
+    const int32_t n = p->n;
+    order_after_caller(st, p->sev[0]);
+    LevelSweep *l1 = nullptr, *l2 = nullptr;
+    const bool level = k > 1 && block_level_plan(p, transpose, &l1, &l2);
+    p->block_path = level ? "block:level" : "block:columns";
+    if (!level && k == 1) {                              // (one column of a row-major block is a contiguous vector)
+        ILUPP_HIP(hipEventRecord(p->ev[3], st));
+        const int rc = apply_dev(p, X, transpose);
+        p->block_events = true;
+        return rc;
+    }
+    if (!level) {
+        if (!p->bcol) ILUPP_HIP(pool_malloc(&p->bcol, sizeof(double) * (size_t)n));
+        block_buffers(p, 0, 1);
+        ILUPP_HIP(hipMemsetAsync(p->btk, 0, sizeof(int32_t), st));
+        ILUPP_HIP(hipEventRecord(p->ev[3], st));
+        const dim3 g((unsigned)(((int64_t)n + 255) / 256)), b(256);
+        for (int64_t j = 0; j < k; ++j) {
+            hipLaunchKernelGGL(k_col_gather, g, b, 0, st, X + j, k, n, p->bcol);
+            const int rc = apply_dev(p, p->bcol, transpose);
+            if (rc) return rc;
+            hipLaunchKernelGGL(k_col_scatter, g, b, 0, st, p->bcol, X + j, k, n, p->ctrl, p->btk);
+        }
+        ILUPP_HIP(hipGetLastError());
+        ILUPP_HIP(hipMemcpyAsync(p->ctrl, p->btk, sizeof(int32_t), hipMemcpyDeviceToDevice, st));     // (what finish_apply reads)
+        ILUPP_HIP(hipEventRecord(p->ev[2], st));
+        p->block_events = true;
+        return ILUPP_OK;
+    }
+    int64_t chunks = 0;
+    int kbmax = 0;
+    for (int64_t c0 = 0; c0 < k; c0 += chunk_width(k - c0)) { ++chunks; kbmax = chunk_width(k - c0) > kbmax ? chunk_width(k - c0) : kbmax; }
+    block_buffers(p, kbmax, 1 + 2 * chunks);
+    if (p->ctrl_armed) p->ctrl_armed = false;            // (zero already: arm_apply)
+    else ILUPP_HIP(hipMemsetAsync(p->ctrl, 0, 64, st));
+    ILUPP_HIP(hipMemsetAsync(p->btk, 0, sizeof(int32_t) * (size_t)(1 + 2 * chunks), st));
+    ILUPP_HIP(hipEventRecord(p->ev[3], st));
+    ILUPP_HIP(hipEventRecord(p->ev[0], st));
+    int64_t q = 0;
+    for (int64_t c0 = 0; c0 < k; ++q) {
+        const int kb = chunk_width(k - c0);
+        // X's columns [c0, c0 + kb) -> the intermediate chunk (leading dimension kb) -> back in place
+        int rc = sptrsm_lvl(st, *l1, kb, X + c0, k, p->by, kb, p->bxp, p->btk + 1 + 2 * q, p->ctrl);
+        if (rc) return rc;
+        if (q == 0) ILUPP_HIP(hipEventRecord(p->ev[1], st));
+        rc = sptrsm_lvl(st, *l2, kb, p->by, kb, X + c0, k, p->bxp, p->btk + 2 + 2 * q, p->ctrl);
+        if (rc) return rc;
+        c0 += kb;
+    }
+    ILUPP_HIP(hipEventRecord(p->ev[2], st));
+    p->apply_events_valid = true;
+    p->block_events = true;
     return ILUPP_OK;
 }
 
@@ -1494,6 +1667,69 @@ int ilupp_hip_apply_device(ilupp_precond *p, double *d_x, int64_t len, int trans
     return ILUPP_OK;
     API_CATCH
 }
+
+static int block_args(const ilupp_precond *p, int64_t n, int64_t k)
+{
+    if (!p) { set_error("null preconditioner"); return ILUPP_ERR_INVALID; }
+    if (n != p->n) { set_error("vector has wrong size for preconditioner!"); return ILUPP_ERR_WRONG_SIZE; }   // binding.cpp:241-242
+    if (k < 0) { set_error("number of right-hand sides must not be negative"); return ILUPP_ERR_INVALID; }
+    return ILUPP_OK;
+}
+
+int ilupp_hip_apply_block_device(ilupp_precond *p, double *d_X, int64_t n, int64_t k, int transpose, int sync)
+{
+    API_TRY
+    int rc = block_args(p, n, k);
+    if (rc || k == 0) return rc;
+    rc = apply_block_dev(p, d_X, k, transpose);
+    if (rc) return rc;
+    if (sync) return finish_apply(p);
+    order_caller_after(p->stream, p->sev[1]);
+    return ILUPP_OK;
+    API_CATCH
+}
+
+// host X: staged through the device in pieces of at most this many bytes (whole chunks of kSptrsmMaxKB columns where more than one fits)
+static constexpr int64_t kBlockStageBytes = (int64_t)256 << 20;
+
+int ilupp_hip_apply_block(ilupp_precond *p, double *X, int64_t n, int64_t k, int transpose)
+{
+    API_TRY
+    int rc = block_args(p, n, k);
+    if (rc || k == 0) return rc;
+    int64_t cb = kBlockStageBytes / (8 * n);
+    if (cb > kSptrsmMaxKB) cb -= cb % kSptrsmMaxKB;
+    cb = cb < 1 ? 1 : (cb > k ? k : cb);
+    hipStream_t st = p->stream;
+    struct Stage { hipStream_t st; double *d = nullptr; ~Stage() { if (d) { (void)stream_sync(st); (void)pool_free(d); } } } stage{st};
+    ILUPP_HIP(pool_malloc(&stage.d, sizeof(double) * (size_t)n * (size_t)cb));
+    std::vector<double> pack(cb < k ? (size_t)n * (size_t)cb : 0);
+    float total_ms = 0.0f;
+    for (int64_t c0 = 0; c0 < k; c0 += cb) {
+        const int64_t w = k - c0 < cb ? k - c0 : cb;
+        const size_t bytes = sizeof(double) * (size_t)n * (size_t)w;
+        if (w == k) {
+            ILUPP_HIP(hipMemcpyAsync(stage.d, X, bytes, hipMemcpyHostToDevice, st));
+        } else {
+            for (int64_t i = 0; i < n; ++i) memcpy(&pack[(size_t)(i * w)], X + i * k + c0, sizeof(double) * (size_t)w);
+            ILUPP_HIP(hipMemcpyAsync(stage.d, pack.data(), bytes, hipMemcpyHostToDevice, st));
+        }
+        rc = apply_block_dev(p, stage.d, w, transpose);
+        if (rc) return rc;
+        rc = finish_apply(p);
+        if (rc) return rc;
+        total_ms += p->tm.last_apply_ms;
+        ILUPP_HIP(hipMemcpyAsync(w == k ? X : pack.data(), stage.d, bytes, hipMemcpyDeviceToHost, st));
+        ILUPP_HIP(stream_sync(st));
+        if (w != k)
+            for (int64_t i = 0; i < n; ++i) memcpy(X + i * k + c0, &pack[(size_t)(i * w)], sizeof(double) * (size_t)w);
+    }
+    p->tm.last_apply_ms = total_ms;
+    return ILUPP_OK;
+    API_CATCH
+}
+
+const char *ilupp_hip_block_path(const ilupp_precond *p) { return p ? p->block_path : ""; }
 
 int ilupp_hip_set_caller_stream(void *hip_stream, int enable)
 {

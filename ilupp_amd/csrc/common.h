@@ -544,6 +544,11 @@ bool lvl_build(hipStream_t st, SweepKind kind, const DevMat &M, const Schedule &
 int ilu0_numeric_lvl(hipStream_t st, const DevMat &A, DevMat *L, DevMat *U, const int32_t *perm, int32_t *d_ctrl, float *kernel_ms);
 int sptrsv_lvl(hipStream_t st, const LevelSweep &ls, double *rhs_and_reset, double *out, int32_t *d_ticket, int32_t *d_err);
 
+// sptrsm_lvl.hip: kb (1, 2, 4, 8 or kSptrsmMaxKB) columns of a row-major block through the same records; rhs is left as it is
+static constexpr int kSptrsmMaxKB = 16;
+int sptrsm_lvl(hipStream_t st, const LevelSweep &ls, int kb, const double *rhs, int64_t ldr, double *out, int64_t ldo, double *xp,
+               int32_t *d_ticket, int32_t *d_err);
+
 // sptrsv_lm.hip
 bool lm_prepare(hipStream_t st, SweepKind kind, const DevMat &M, const Schedule &sch, const int32_t *desc,
                 int32_t max_row_len, PackedSweep *ps);

@@ -108,12 +108,31 @@ void solve_in_place(const Factorisation &f, const py::buffer &x, bool transposed
                   : ilupp_hip_apply(f.h, static_cast<double *>(v.ptr), v.shape[0]));       // GIL held, as binding.cpp:237-254
 }
 
+// the block apply (no counterpart in binding.cpp): a writable, C-contiguous (n, k) fp64 buffer, every column as solve_in_place gives it
+void solve_block_in_place(const Factorisation &f, const py::buffer &x, bool transposed)
+{
+    py::buffer_info v = x.request();
+    if (v.ndim != 2) throw std::runtime_error("Expected 2D array for b!");
+    if ((v.shape[1] > 1 && v.strides[1] != v.itemsize) || (v.shape[0] > 1 && v.shape[1] > 0 && v.strides[0] != v.itemsize * v.shape[1]))
+        throw std::runtime_error("Expected contiguous array for b!");
+    if (v.format != py::format_descriptor<double>::format()) throw std::runtime_error("Expected d (d) array for b, got " + v.format + "!");
+    if (v.readonly) throw std::runtime_error("b must be writable");
+    int rc;
+    {
+        py::gil_scoped_release release;
+        rc = ilupp_hip_apply_block(f.h, static_cast<double *>(v.ptr), v.shape[0], v.shape[1], transposed ? 1 : 0);
+    }
+    ok(rc);
+}
+
 template <class T>
 py::class_<T> members(py::module_ &m, const char *name)
 {
     return py::class_<T>(m, name)
         .def("apply", [](const T &f, py::buffer x) { solve_in_place(f, x, false); })
         .def("apply_trans", [](const T &f, py::buffer x) { solve_in_place(f, x, true); })
+        .def("apply_block", [](const T &f, py::buffer x) { solve_block_in_place(f, x, false); })
+        .def("apply_block_trans", [](const T &f, py::buffer x) { solve_block_in_place(f, x, true); })
         .def_property_readonly("total_nnz", [](const T &f) { return ilupp_hip_total_nnz(f.h); })
         .def("factors_info", [](const T &f) { return egress(f); })
         .def_property_readonly("memory_used_calculations", [](const T &f) { return ilupp_hip_memory_used_calculations(f.h); })

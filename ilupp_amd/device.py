@@ -70,11 +70,20 @@ class DevicePreconditioner:
         p.update(params)
         _on_current_stream()
         self.pr = make(A.data.data_ptr(), A.indices.data_ptr(), A.indptr.data_ptr(), A.n, True, *[p[k] for k in names])
+        self.kind = kind
         self.n = A.n
         self.shape = A.shape
 
     def apply_(self, x, transpose=False):
-        """in place on a contiguous fp64 device tensor; asynchronous, ordered on torch's current stream"""
+        """in place on a contiguous fp64 device tensor; asynchronous, ordered on torch's current stream.  A tensor of shape (n, k) is
+        k right-hand sides, solved in one block apply (every column as apply_ on that column gives it; not for the "ILUpp" kind)"""
+        if x.dim() == 2:
+            if self.kind == "ILUpp":
+                raise NotImplementedError("block apply of the multilevel preconditioner: apply_ one column at a time")
+            assert x.is_cuda and x.dtype == torch.float64 and x.is_contiguous() and x.shape[0] == self.n
+            _on_current_stream()
+            self.pr.apply_block_device(x.data_ptr(), self.n, x.shape[1], transpose=transpose, sync=False)
+            return x
         assert x.is_cuda and x.dtype == torch.float64 and x.is_contiguous() and x.numel() == self.n
         _on_current_stream()
         self.pr.apply_device(x.data_ptr(), self.n, transpose=transpose, sync=False)

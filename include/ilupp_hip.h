@@ -132,6 +132,19 @@ int ilupp_hip_apply_trans(ilupp_precond *p, double *x, int64_t len);
 /* the same on a vector that already lives in HBM (asynchronous on the object's stream unless sync!=0) */
 int ilupp_hip_apply_device(ilupp_precond *p, double *d_x, int64_t len, int transpose, int sync);
 
+/* Block apply: k right-hand sides at once, X row-major n x k (row i's k values contiguous), in place; transpose != 0 applies
+ * M^-T as ilupp_hip_apply_trans does.  Every column comes out bit-identical to an apply of that column alone.  Objects of the five
+ * single-factorisation kinds (ILU0, ILUT, ILUC, IChol0, ICholT).  Errors: ILUPP_ERR_WRONG_SIZE ("vector has wrong size for
+ * preconditioner!") for n != the dimension, ILUPP_ERR_INVALID for k < 0; k == 0 does nothing.  last_apply_ms of
+ * ilupp_hip_get_timings covers the whole block apply.  No counterpart in binding.cpp (the reference applies one vector at a time). */
+/* host X: staged through the device in pieces of a bounded size */
+int ilupp_hip_apply_block(ilupp_precond *p, double *X, int64_t n, int64_t k, int transpose);
+/* X in HBM: stream ordering and `sync` as for ilupp_hip_apply_device.  No counterpart in binding.cpp */
+int ilupp_hip_apply_block_device(ilupp_precond *p, double *d_X, int64_t n, int64_t k, int transpose, int sync);
+/* the route of the last block apply: "block:level" (both sweeps walk the level-ordered factors once per chunk of up to 16 columns),
+ * "block:columns" (one apply per column), "" before the first one.  Measurement / test hook, no counterpart in binding.cpp */
+const char *ilupp_hip_block_path(const ilupp_precond *p);
+
 /* Stream ordering of the device-pointer entry points (*_create_device, ilupp_hip_ilu0_refactor_device,
  * ilupp_hip_apply_device).  Every object works on a private non-blocking HIP stream.  By default the caller must
  * have synchronised the producer of the device buffers before the call, and a call with sync=0 must be followed by
