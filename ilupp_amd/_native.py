@@ -88,6 +88,12 @@ def lib():
     L.ilupp_hip_icholt_create_device.argtypes = mat_host + [ctypes.c_int32, ctypes.c_double, ctypes.POINTER(_VP)]
     L.ilupp_hip_set_caller_stream.argtypes = [_VP, ctypes.c_int]
     L.ilupp_hip_spmv_device.argtypes = [_VP, _VP, _VP, ctypes.c_int32, ctypes.c_int64, _VP, _VP, _VP]
+    L.ilupp_hip_spmm_device.argtypes = [_VP, _VP, _VP, ctypes.c_int32, ctypes.c_int64, _VP, ctypes.c_int64, _VP, ctypes.c_int64,
+                                        ctypes.c_int64, _VP]
+    L.ilupp_hip_block_dot_device.argtypes = [ctypes.c_int32, ctypes.c_int64, _VP, ctypes.c_int64, _VP, ctypes.c_int64, _VP, _VP]
+    L.ilupp_hip_cg_block_update_device.argtypes = [ctypes.c_int32, ctypes.c_int32, ctypes.c_int64, _VP, _VP, _VP, _VP, _VP, _VP, _VP]
+    L.ilupp_hip_bicgstab_block_update_device.argtypes = [ctypes.c_int32, ctypes.c_int32, ctypes.c_int64, _VP, _VP, _VP, _VP, _VP, _VP, _VP,
+                                                         _VP, _VP, _VP, _VP]
     L.ilupp_hip_path.argtypes = [_VP]
     L.ilupp_hip_path.restype = ctypes.c_char_p
     L.ilupp_hip_analysis_path.argtypes = [_VP]
@@ -187,6 +193,7 @@ ABI_SYMBOLS = [
     "ilupp_hip_ilucp_create", "ilupp_hip_ilucp_destroy", "ilupp_hip_ilucp_apply", "ilupp_hip_ilucp_total_nnz", "ilupp_hip_ilucp_zero_pivots",
     "ilupp_hip_ilucp_info", "ilupp_hip_ilucp_copy", "ilupp_hip_ilutp_create",
     "ilupp_hip_apply_block", "ilupp_hip_apply_block_device", "ilupp_hip_block_path",
+    "ilupp_hip_spmm_device", "ilupp_hip_block_dot_device", "ilupp_hip_cg_block_update_device", "ilupp_hip_bicgstab_block_update_device",
 ]
 
 

@@ -6,6 +6,14 @@ operator that work on torch tensors living in HBM, so that an iteration of CG / 
     M = ild.DevicePreconditioner("ICholT", A, add_fill_in=0, threshold=0.0)
     x = ild.cg(A, b, M, maxiter=50)                        # b, x: torch.float64 tensors on the GPU
 
+k right-hand sides at once: B of shape (n, k), row-major; the k recurrences advance in lockstep, each iteration one SpMM, one block
+apply and the block dot products, and column j of the result has the bits of the same solve of B[:, j:j+1] alone.
+
+    B = torch.randn(A.n, 8, dtype=torch.float64, device="cuda")
+    stats = {}
+    X = ild.cg(A, B, M, maxiter=500, rtol=1e-8, check_every=10, stats=stats)
+    stats["iterations"], stats["converged"], stats["relres"]        # (8,) each, on the CPU
+
 Everything is ordered on torch's current stream (ilupp_hip_set_caller_stream): no host synchronisation per call.
 The reference's counterpart is the loop of iterative_solvers_implementation.h:385-530 around
 matrix_sparse::matrix_vector_multiplication (sparse_implementation.h:2733-2760) and apply_preconditioner_only.
@@ -30,6 +38,44 @@ def _on_current_stream():
     _native.set_caller_stream(torch.cuda.current_stream().cuda_stream, True)
 
 
+def _check_block(X, n, name, contiguous=True):
+    """a row-major fp64 (n, k) device tensor (unit column stride; with contiguous=False a leading dimension >= k is allowed): its leading
+    dimension.  ValueError otherwise -- raised before any native call"""
+    if not isinstance(X, torch.Tensor) or X.dim() != 2 or X.shape[0] != n:
+        raise ValueError("%s: expected a 2-D tensor with %d rows, got shape %s" % (name, n, tuple(getattr(X, "shape", ()))))
+    if X.dtype != torch.float64:
+        raise ValueError("%s: expected torch.float64, got %s" % (name, X.dtype))
+    k = X.shape[1]
+    ld = X.stride(0) if n > 1 else max(k, 1)
+    if contiguous:
+        if not X.is_contiguous():
+            raise ValueError("%s: expected a contiguous (row-major) tensor" % name)
+        ld = k
+    elif (k > 1 and X.stride(1) != 1) or ld < max(k, 1):
+        raise ValueError("%s: expected row-major storage (unit column stride, leading dimension >= k)" % name)
+    if not X.is_cuda:
+        raise ValueError("%s: expected a CUDA tensor" % name)
+    return ld
+
+
+def _block_dot(A, B, out=None):
+    """(k,) device tensor: column j = the dot product of A[:, j] and B[:, j] (ilupp_hip_block_dot_device: the reduction shape depends on
+    n alone, so column j has the same bits whatever k is)"""
+    n, k = A.shape
+    out = torch.empty(k, dtype=torch.float64, device=A.device) if out is None else out
+    if k:
+        rc = _native.lib().ilupp_hip_block_dot_device(n, k, A.data_ptr(), k, B.data_ptr(), k, out.data_ptr(),
+                                                      torch.cuda.current_stream().cuda_stream)
+        if rc:
+            _native._raise(rc)
+    return out
+
+
+def _ok(v):
+    """the scalars a recurrence may divide by: non-zero and finite"""
+    return (v != 0) & torch.isfinite(v)
+
+
 class DeviceCSR:
     """a square CSR matrix in HBM (fp64 values, int32 indices) with a bit-exact matvec"""
 
@@ -51,12 +97,34 @@ class DeviceCSR:
                    torch.from_numpy(A.indices.astype(np.int32)).to(dev), torch.from_numpy(A.indptr.astype(np.int32)).to(dev))
 
     def matvec(self, x, out=None):
+        if x.dim() == 2:
+            return self.matmat(x, out=out)
         y = torch.empty_like(x) if out is None else out
         rc = _native.lib().ilupp_hip_spmv_device(self.data.data_ptr(), self.indices.data_ptr(), self.indptr.data_ptr(), self.n,
                                                  self.nnz, x.data_ptr(), y.data_ptr(), torch.cuda.current_stream().cuda_stream)
         if rc:
             _native._raise(rc)
         return y
+
+    def matmat(self, X, out=None):
+        """Y = A X for a row-major fp64 (n, k) CUDA tensor (contiguous, or a row-major view with a leading dimension >= k, such as
+        X[:, c0:c1] of a wider block), ordered on torch's current stream.  Column j of Y has the bits of matvec(X[:, j]).  `out`: a
+        row-major (n, k) tensor that does not overlap X.  ValueError for a wrong shape, dtype or layout, before any native call."""
+        ldx = _check_block(X, self.n, "X", contiguous=False)
+        k = X.shape[1]
+        if out is None:
+            Y, ldy = torch.empty((self.n, k), dtype=torch.float64, device=X.device), k
+        else:
+            if tuple(out.shape) != (self.n, k):
+                raise ValueError("out: expected shape %s, got %s" % ((self.n, k), tuple(out.shape)))
+            Y, ldy = out, _check_block(out, self.n, "out", contiguous=False)
+        if k == 0:
+            return Y
+        rc = _native.lib().ilupp_hip_spmm_device(self.data.data_ptr(), self.indices.data_ptr(), self.indptr.data_ptr(), self.n, self.nnz,
+                                                 X.data_ptr(), ldx, Y.data_ptr(), ldy, k, torch.cuda.current_stream().cuda_stream)
+        if rc:
+            _native._raise(rc)
+        return Y
 
     __matmul__ = matvec
 
@@ -105,9 +173,23 @@ class DevicePreconditioner:
         self.pr.sync()
 
 
-def cg(A, b, M=None, x0=None, maxiter=100, rtol=0.0, check_every=0):
+def cg(A, b, M=None, x0=None, maxiter=100, rtol=0.0, check_every=0, stats=None):
     """preconditioned conjugate gradients on device tensors.  No host round trip per iteration: the scalars stay 0-dim
-    device tensors; the residual is only looked at every `check_every` iterations (0 = never: run maxiter iterations)."""
+    device tensors; the residual is only looked at every `check_every` iterations (0 = never: run maxiter iterations).
+
+    b of shape (n, k): k right-hand sides, k independent recurrences in lockstep, each column statement for statement the loop
+    below (not a block Krylov space); one SpMM, one block apply and the block dot products per iteration.  Per column:
+      - every `check_every` iterations one (k,) vector of relative residuals ||r|| / ||b|| is copied to the host; columns at or below
+        `rtol` freeze (converged), and the loop ends when no column is active.  check_every = 0: every column runs maxiter iterations;
+      - a zero right-hand-side column (or one whose x0 leaves a zero residual) returns x0's column (zeros) and counts as converged at
+        iteration 0 -- the 1-D function gives NaN there;
+      - a breakdown, p^T A p zero or not finite, freezes the column as not converged, without any host read;
+      - a frozen column is bitwise untouched from then on, and a NaN in one column never reaches another;
+      - column j of the result has the bits of the same solve of b[:, j:j+1] alone.
+    `stats`, when a dict and b is 2-D, receives "iterations" (k,) int64, "converged" (k,) bool and "relres" (k,) float64 on the CPU.
+    M of the "ILUpp" kind with a 2-D b: NotImplementedError."""
+    if b.dim() == 2:
+        return _cg_block(A, b, M, x0, maxiter, rtol, check_every, stats)
     x = torch.zeros_like(b) if x0 is None else x0.clone()
     r = b - A.matvec(x) if x0 is not None else b.clone()
     z = M.matvec(r) if M is not None else r.clone()
@@ -132,12 +214,25 @@ def cg(A, b, M=None, x0=None, maxiter=100, rtol=0.0, check_every=0):
     return x
 
 
-def bicgstab(A, b, M=None, x0=None, maxiter=100, rtol=0.0, check_every=0, history=None):
+def bicgstab(A, b, M=None, x0=None, maxiter=100, rtol=0.0, check_every=0, history=None, stats=None):
     """left-preconditioned BiCGstab on device tensors, statement for statement the loop of the reference
     (iterative_solvers_implementation.h:385-530 with a LEFT preconditioner application): the residual recurrence runs on
     r = M^-1 (b - A x), Ap = M^-1 (A p), As = M^-1 (A s).  No host round trip per iteration (the scalars stay 0-dim device tensors;
     the residual norm is looked at every `check_every` iterations only); `history`, when a list, receives a copy of the iterate after
-    every iteration (tests)."""
+    every iteration (tests).
+
+    b of shape (n, k): k right-hand sides as in cg() -- k recurrences in lockstep, each column statement for statement this loop; the
+    relative residual of a column is ||r|| / ||r_0|| of the preconditioned residual, as here.  Per column:
+      - every `check_every` iterations one (k,) vector of relative residuals is copied to the host; columns at or below `rtol` freeze
+        (converged), and the loop ends when no column is active.  check_every = 0: every column runs maxiter iterations;
+      - a zero right-hand-side column (or a zero initial residual) returns x0's column (zeros) and counts as converged at iteration 0
+        -- the 1-D function gives NaN there;
+      - a breakdown, rho = (r, r0*), (Ap, r0*) or omega zero or not finite, freezes the column as not converged, without any host read;
+      - a frozen column is bitwise untouched from then on, and a NaN in one column never reaches another;
+      - column j of the result has the bits of the same solve of b[:, j:j+1] alone.
+    `stats` as in cg().  M of the "ILUpp" kind with a 2-D b: NotImplementedError."""
+    if b.dim() == 2:
+        return _bicgstab_block(A, b, M, x0, maxiter, rtol, check_every, history, stats)
     def prec(v):
         return M.matvec(v) if M is not None else v.clone()
     y = torch.zeros_like(b) if x0 is None else x0.clone()
@@ -169,6 +264,133 @@ def bicgstab(A, b, M=None, x0=None, maxiter=100, rtol=0.0, check_every=0, histor
     if M is not None:
         M.sync()
     return y
+
+
+# ---- k right-hand sides: the 2-D paths of cg() and bicgstab() ---------------------------------------------------------------------
+def _block_setup(A, B, M, x0):
+    """the checks of a 2-D solve, all before any native call"""
+    if M is not None and getattr(M, "kind", None) == "ILUpp":
+        raise NotImplementedError("k right-hand sides with the multilevel preconditioner: solve one column at a time")
+    n = A.n
+    _check_block(B, n, "b")
+    if x0 is not None:
+        _check_block(x0, n, "x0")
+        if x0.shape != B.shape:
+            raise ValueError("x0: expected shape %s, got %s" % (tuple(B.shape), tuple(x0.shape)))
+    if M is not None and M.n != n:
+        raise ValueError("M: dimension %d, the matrix has %d" % (M.n, n))
+    return n, B.shape[1]
+
+
+def _block_update(solver, stage, n, k, active, *ptrs):
+    lib = _native.lib()
+    fn = lib.ilupp_hip_cg_block_update_device if solver == "cg" else lib.ilupp_hip_bicgstab_block_update_device
+    rc = fn(stage, n, k, active.data_ptr(), *[0 if t is None else t.data_ptr() for t in ptrs], torch.cuda.current_stream().cuda_stream)
+    if rc:
+        _native._raise(rc)
+
+
+def _block_stats(stats, iters, converged, relres):
+    if isinstance(stats, dict):
+        stats["iterations"] = iters.cpu()
+        stats["converged"] = converged.cpu()
+        stats["relres"] = relres.cpu()
+
+
+def _check_point(R, den, active, converged, rtol):
+    """freeze the columns at or below rtol; the one host read: the (k,) relative residuals of the columns still active (-1 for the
+    others).  True when no column is active."""
+    rel = torch.sqrt(_block_dot(R, R)) / den
+    newly = active & (rel <= rtol)
+    converged |= newly
+    active &= ~newly
+    h = torch.where(active, rel, torch.full_like(rel, -1.0)).cpu()
+    return not bool((h != -1.0).any())
+
+
+def _cg_block(A, B, M, x0, maxiter, rtol, check_every, stats):
+    n, k = _block_setup(A, B, M, x0)
+    X = torch.zeros_like(B) if x0 is None else x0.clone()
+    R = B - A.matmat(X) if x0 is not None else B.clone()
+    Z = M.apply_(R.clone()) if M is not None else R.clone()
+    P = Z.clone()
+    rz = _block_dot(R, Z)
+    bnorm = torch.sqrt(_block_dot(B, B))
+    zero = (bnorm == 0) | (_block_dot(R, R) == 0)
+    active = ~zero
+    converged = zero.clone()
+    iters = torch.zeros(k, dtype=torch.int64, device=B.device)
+    AP = torch.empty_like(B)
+    for it in range(maxiter):
+        A.matmat(P, out=AP)
+        pap = _block_dot(P, AP)
+        alpha = rz / pap
+        active &= _ok(pap)                                               # breakdown: frozen, not converged
+        _block_update("cg", 0, n, k, active, alpha, X, R, P, AP)         # x = x + p alpha; r = r - Ap alpha
+        iters += active
+        if check_every and (it + 1) % check_every == 0 and rtol > 0.0:
+            if _check_point(R, bnorm, active, converged, rtol):
+                break
+        if M is not None:
+            Z.copy_(R)
+            M.apply_(Z)
+        else:
+            Z = R
+        rz_new = _block_dot(R, Z)
+        _block_update("cg", 1, n, k, active, rz_new / rz, None, None, P, Z)   # p = z + p (rz_new / rz)
+        rz = rz_new
+    if M is not None:
+        M.sync()
+    if isinstance(stats, dict):
+        rel = torch.sqrt(_block_dot(R, R)) / bnorm
+        _block_stats(stats, iters, converged, torch.where(bnorm == 0, torch.zeros_like(rel), rel))
+    return X
+
+
+def _bicgstab_block(A, B, M, x0, maxiter, rtol, check_every, history, stats):
+    n, k = _block_setup(A, B, M, x0)
+
+    def prec_(V):
+        return M.apply_(V) if M is not None else V
+    Y = torch.zeros_like(B) if x0 is None else x0.clone()
+    R0s = B.clone() if x0 is None else B - A.matmat(Y)
+    R = prec_(R0s)
+    R0s = R.clone()
+    P = R.clone()
+    init = torch.sqrt(_block_dot(R, R))
+    zero = (_block_dot(B, B) == 0) | (init == 0)
+    active = ~zero
+    converged = zero.clone()
+    iters = torch.zeros(k, dtype=torch.int64, device=B.device)
+    AP = torch.empty_like(B)
+    AS = torch.empty_like(B)
+    S = torch.zeros_like(B)
+    for it in range(maxiter):
+        prec_(A.matmat(P, out=AP))
+        rho = _block_dot(R, R0s)
+        apr = _block_dot(AP, R0s)
+        active &= _ok(rho) & _ok(apr)                                    # breakdown: frozen, not converged
+        alpha = rho / apr
+        _block_update("bicgstab", 0, n, k, active, alpha, None, None, None, R, None, S, AP, None)     # s = r - alpha Ap
+        prec_(A.matmat(S, out=AS))
+        omega = _block_dot(AS, S) / _block_dot(AS, AS)
+        active &= _ok(omega)
+        # y = y + alpha p; y = y + omega s; r = s - omega As
+        _block_update("bicgstab", 1, n, k, active, alpha, omega, None, Y, R, P, S, None, AS)
+        beta = (_block_dot(R, R0s) / rho) * (alpha / omega)
+        _block_update("bicgstab", 2, n, k, active, None, omega, beta, None, R, P, None, AP, None)        # p = p - omega Ap; p = beta p + r
+        iters += active
+        if history is not None:
+            history.append(Y.clone())
+        if check_every and (it + 1) % check_every == 0 and rtol > 0.0:
+            if _check_point(R, init, active, converged, rtol):
+                break
+    if M is not None:
+        M.sync()
+    if isinstance(stats, dict):
+        rel = torch.sqrt(_block_dot(R, R)) / init
+        _block_stats(stats, iters, converged, torch.where(zero, torch.zeros_like(rel), rel))
+    return Y
 
 
 def bicgstab_split(A, b, M, min_iter=1, max_iter=500, rtol=1e-4, atol=1e-4):

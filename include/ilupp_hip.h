@@ -159,6 +159,34 @@ int ilupp_hip_set_caller_stream(void *hip_stream, int enable);
 int ilupp_hip_spmv_device(const double *d_data, const int32_t *d_indices, const int32_t *d_indptr, int32_t n, int64_t nnz,
                           const double *d_x, double *d_y, void *hip_stream);
 
+/* Y = A X for a CSR matrix in HBM and a row-major block X of k columns (row i's columns at X[i * ldx .. i * ldx + k)), Y likewise
+ * with leading dimension ldy, on the caller's stream.  Column j of Y is, bit for bit, ilupp_hip_spmv_device applied to column j
+ * (accumulation in stored order from 0, separate multiply and add).  X and Y must not overlap (refused).  k == 0 does nothing.
+ * Errors: ILUPP_ERR_INVALID for a null pointer, n <= 0, nnz < 0, k < 0, ldx < k or ldy < k -- before any launch. */
+int ilupp_hip_spmm_device(const double *d_data, const int32_t *d_indices, const int32_t *d_indptr, int32_t n, int64_t nnz,
+                          const double *d_X, int64_t ldx, double *d_Y, int64_t ldy, int64_t k, void *hip_stream);
+
+/* out[j] = sum_i A[i, j] * B[i, j] for j < k over two row-major blocks (leading dimensions lda, ldb), into k doubles in device memory,
+ * on the caller's stream (no host read).  The reduction shape depends on n alone (min(1024, ceil(n / 256)) contiguous chunks, a fixed
+ * tree inside each, a fixed order across them): column j has the bits of the same column dotted alone, on every run.  k == 0 does
+ * nothing.  Errors: ILUPP_ERR_INVALID for a null pointer, n <= 0, k < 0, lda < k or ldb < k -- before any launch. */
+int ilupp_hip_block_dot_device(int32_t n, int64_t k, const double *d_A, int64_t lda, const double *d_B, int64_t ldb, double *d_out,
+                               void *hip_stream);
+
+/* The masked updates of the k-column CG (ilupp_amd/device.py): contiguous row-major n x k blocks, per-column coefficients in device
+ * memory, d_active[j] != 0 for the columns that move -- a column whose flag is 0 is neither read nor written.
+ *   stage 0: X = X + P * coef; R = R - V * coef (V = A P)        stage 1: P = V + P * coef (V = Z; X and R unused)
+ * Errors: ILUPP_ERR_INVALID for another stage, a null pointer the stage uses, n <= 0 or k < 0.  k == 0 does nothing. */
+int ilupp_hip_cg_block_update_device(int32_t stage, int32_t n, int64_t k, const uint8_t *d_active, const double *d_coef, double *d_X,
+                                     double *d_R, double *d_P, const double *d_V, void *hip_stream);
+
+/* The masked updates of the k-column BiCGstab, as ilupp_hip_cg_block_update_device:
+ *   stage 0: S = R - alpha AP     stage 1: Y = Y + alpha P; Y = Y + omega S; R = S - omega AS     stage 2: P = P - omega AP; P = beta P + R
+ * Errors: ILUPP_ERR_INVALID for another stage, a null pointer the stage uses, n <= 0 or k < 0.  k == 0 does nothing. */
+int ilupp_hip_bicgstab_block_update_device(int32_t stage, int32_t n, int64_t k, const uint8_t *d_active, const double *d_alpha,
+                                           const double *d_omega, const double *d_beta, double *d_Y, double *d_R, double *d_P,
+                                           double *d_S, const double *d_AP, const double *d_AS, void *hip_stream);
+
 /* binding.cpp:255  total_nnz  (conventions per class) */
 int64_t ilupp_hip_total_nnz(const ilupp_precond *p);
 /* binding.cpp:257-261 */
