@@ -264,8 +264,8 @@ void destroy_obj(ilupp_precond *p)
     for (void *q : {(void *)p->bxp, (void *)p->by, (void *)p->bcol, (void *)p->btk}) if (q) (void)pool_free(q);
     if (p->done) (void)pool_free(p->done);
     if (p->ctrl) (void)pool_free(p->ctrl);
-    // streams and events are recycled: creating them costs more than a small kernel
-    if (p->stream && !p->borrowed_queue) {
+    // streams and events are recycled: creating them costs more than a small kernel (not a pack new_obj could not finish: jev[1] comes last)
+    if (p->stream && !p->borrowed_queue && p->jev[1]) {
         std::lock_guard<std::mutex> lk(g_queues.mu);
         QueuePack q; q.stream = p->stream; q.device = p->device;
         for (int k = 0; k < 6; ++k) q.ev[k] = p->ev[k];
@@ -276,9 +276,21 @@ void destroy_obj(ilupp_precond *p)
     delete p;
 }
 
+// an object under construction: destroyed (its side stream synchronised, its pool blocks given back) when the construction unwinds --
+// a HIP error thrown from the middle of a factorisation or an analysis leaves nothing behind
+struct ObjGuard {
+    ilupp_precond *p;
+    explicit ObjGuard(ilupp_precond *q) : p(q) {}
+    ~ObjGuard() { if (p) { if (p->side) (void)stream_sync(p->side); destroy_obj(p); } }
+    ilupp_precond *release() { ilupp_precond *q = p; p = nullptr; return q; }
+    ObjGuard(const ObjGuard &) = delete;
+    ObjGuard &operator=(const ObjGuard &) = delete;
+};
+
 ilupp_precond *new_obj(int32_t n)
 {
-    ilupp_precond *p = new ilupp_precond();
+    ObjGuard g(new ilupp_precond());
+    ilupp_precond *p = g.p;
     p->n = n;
     ILUPP_HIP(hipGetDevice(&p->device));
     {
@@ -310,13 +322,87 @@ ilupp_precond *new_obj(int32_t n)
     // limit, a 288^3 mesh (82 944 lines) got blocks of 365 rows that straddled lines, every lane waited for its predecessor
     // to finish, and the sweeps ran into their spin limits.
     p->max_lanes = 1 << 24;
-    return p;
+    return g.release();
 }
 
 int validate(const int32_t *indptr, int32_t n)
 {
     if (n <= 0 || indptr == nullptr) { set_error("matrix has size 0!"); return ILUPP_ERR_INVALID; }   // binding.cpp:80-81
     return ILUPP_OK;
+}
+
+// a device matrix this scope owns: released when it unwinds (or earlier, by whoever calls m.release())
+struct MatGuard {
+    DevMat m;
+    MatGuard() = default;
+    ~MatGuard() { m.release(); }
+    MatGuard(const MatGuard &) = delete;
+    MatGuard &operator=(const MatGuard &) = delete;
+};
+
+// a host CSR/CSC triple copied to pooled device memory, into *A (owned by the caller: a MatGuard, the solve's Guard)
+int upload(const double *data, const int32_t *indices, const int32_t *indptr, int32_t n, bool is_csr, DevMat *A)
+{
+    const int rc = validate(indptr, n);
+    if (rc) return rc;
+    const int64_t nnz = indptr[n];
+    A->n = n; A->nnz = nnz; A->is_csr = is_csr; A->owns = true;
+    ILUPP_HIP(pool_malloc(&A->ptr, sizeof(int32_t) * (size_t)(n + 1)));
+    ILUPP_HIP(pool_malloc(&A->idx, sizeof(int32_t) * (size_t)(nnz > 0 ? nnz : 1)));
+    ILUPP_HIP(pool_malloc(&A->val, sizeof(double) * (size_t)(nnz > 0 ? nnz : 1)));
+    ILUPP_HIP(hipMemcpy(A->ptr, indptr, sizeof(int32_t) * (size_t)(n + 1), hipMemcpyHostToDevice));
+    ILUPP_HIP(hipMemcpy(A->idx, indices, sizeof(int32_t) * (size_t)nnz, hipMemcpyHostToDevice));
+    ILUPP_HIP(hipMemcpy(A->val, data, sizeof(double) * (size_t)nnz, hipMemcpyHostToDevice));
+    return ILUPP_OK;
+}
+
+// the caller's device arrays, borrowed for the call (never released)
+DevMat borrow_csr(const double *d_data, const int32_t *d_indices, const int32_t *d_indptr, int32_t n, int64_t nnz, bool is_csr)
+{
+    DevMat A;
+    A.n = n; A.nnz = nnz; A.is_csr = is_csr; A.owns = false;
+    A.ptr = const_cast<int32_t *>(d_indptr); A.idx = const_cast<int32_t *>(d_indices); A.val = const_cast<double *>(d_data);
+    return A;
+}
+
+// what read_device_head reads, from host arrays: {indptr[0], indptr[1], indices[0..7]} (-1 where the matrix has no such entry)
+void host_head(const int32_t *indptr, const int32_t *indices, int64_t nnz, int32_t head[10])
+{
+    head[0] = indptr[0]; head[1] = indptr[1];
+    for (int i = 0; i < 8; ++i) head[2 + i] = i < nnz ? indices[i] : -1;
+}
+
+// one sweep's lane tables: the factor it runs over, its direction, where its schedule and descriptors go
+struct SweepSpec { const DevMat *M; bool fwd; Schedule *s; int32_t **desc; };
+
+// the lane tables of one sweep, or of two (b.M != nullptr) stage by stage: cuts and schedules, tilings, slot tables, descriptors.
+// Descriptors need a compact schedule: joint = for both sweeps or for neither, else each sweep for itself.  *max_len = the longest
+// major slice of the factors; returns whether every schedule is compact.
+bool sweep_tables(hipStream_t st, const ilupp_precond *p, const SweepSpec &a, const SweepSpec &b, bool joint, int32_t *max_len)
+{
+    const SweepSpec *sw[2] = {&a, b.M ? &b : nullptr};
+    int32_t m[2] = {0, 0};
+    for (int k = 0; k < 2; ++k)
+        if (sw[k]) count_cuts_and_schedule(st, p->n, sw[k]->M->ptr, sw[k]->M->idx, p->max_lanes, sw[k]->fwd ? sw[k]->s : nullptr,
+                                           sw[k]->fwd ? nullptr : sw[k]->s, &m[k]);
+    *max_len = m[0] > m[1] ? m[0] : m[1];
+    for (const SweepSpec *w : sw) if (w) choose_tiling(st, p->n, w->M->ptr, w->M->idx, w->s, w->fwd, p->max_lanes / kThreads);
+    for (const SweepSpec *w : sw) if (w) build_slot_tables(st, w->s, w->fwd);
+    const bool c[2] = {schedule_is_compact(*a.s), !sw[1] || schedule_is_compact(*b.s)};
+    for (int k = 0; k < 2; ++k)
+        if (sw[k] && (joint ? c[0] && c[1] : c[k])) make_desc(st, *sw[k]->M, *sw[k]->s, sw[k]->desc);
+    return c[0] && c[1];
+}
+
+// the end of a construction: its last event, the wait for it, the times of its two phases -- [ev[0], ev[1]) is the numeric
+// factorisation and [ev[1], ev[2]) the analysis, or the other way round (IChol(0) analyses first)
+void finish_timing(ilupp_precond *p, float kernel_ms, bool analysis_first = false)
+{
+    ILUPP_HIP(hipEventRecord(p->ev[2], p->stream));
+    ILUPP_HIP(stream_sync(p->stream));
+    ILUPP_HIP(hipEventElapsedTime(analysis_first ? &p->tm.analysis_ms : &p->tm.numeric_ms, p->ev[0], p->ev[1]));
+    ILUPP_HIP(hipEventElapsedTime(analysis_first ? &p->tm.numeric_ms : &p->tm.analysis_ms, p->ev[1], p->ev[2]));
+    p->tm.numeric_kernel_ms = kernel_ms;
 }
 
 // What a plain apply of a static ILU(0) object needs before its first sweep -- control words zero, both exchange buffers all-sentinel --
@@ -590,43 +676,18 @@ void ensure_transposed(ilupp_precond *p)
     if (p->kind == KIND_LU) {
         transpose_storage(st, p->Uc, &p->UcT);      // lower, diagonal last
         transpose_storage(st, p->Lc, &p->LcT);      // upper, diagonal first
-        int32_t m1 = 0, m2 = 0;
-        count_cuts_and_schedule(st, p->n, p->UcT.ptr, p->UcT.idx, p->max_lanes, &p->sUT, nullptr, &m1);
-        count_cuts_and_schedule(st, p->n, p->LcT.ptr, p->LcT.idx, p->max_lanes, nullptr, &p->sLT, &m2);
-        p->max_len_T = m1 > m2 ? m1 : m2;
-        choose_tiling(st, p->n, p->UcT.ptr, p->UcT.idx, &p->sUT, true, p->max_lanes / kThreads);
-        choose_tiling(st, p->n, p->LcT.ptr, p->LcT.idx, &p->sLT, false, p->max_lanes / kThreads);
-        build_slot_tables(st, &p->sUT, true);
-        build_slot_tables(st, &p->sLT, false);
-        if (schedule_is_compact(p->sUT) && schedule_is_compact(p->sLT)) {
-            make_desc(st, p->UcT, p->sUT, &p->dUT);
-            make_desc(st, p->LcT, p->sLT, &p->dLT);
-        }
+        sweep_tables(st, p, {&p->UcT, true, &p->sUT, &p->dUT}, {&p->LcT, false, &p->sLT, &p->dLT}, true, &p->max_len_T);
     } else if (p->kind == KIND_UTU) {
         // both transposes are row-major lower matrices with the diagonal last: forward sweeps
         transpose_storage(st, p->Lc, &p->LcT);
         transpose_storage(st, p->Uc, &p->UcT);
-        int32_t m1 = 0, m2 = 0;
-        count_cuts_and_schedule(st, p->n, p->LcT.ptr, p->LcT.idx, p->max_lanes, &p->sLT, nullptr, &m1);
-        count_cuts_and_schedule(st, p->n, p->UcT.ptr, p->UcT.idx, p->max_lanes, &p->sUT, nullptr, &m2);
-        p->max_len_T = m1 > m2 ? m1 : m2;
-        choose_tiling(st, p->n, p->LcT.ptr, p->LcT.idx, &p->sLT, true, p->max_lanes / kThreads);
-        choose_tiling(st, p->n, p->UcT.ptr, p->UcT.idx, &p->sUT, true, p->max_lanes / kThreads);
-        build_slot_tables(st, &p->sLT, true);
-        build_slot_tables(st, &p->sUT, true);
-        if (schedule_is_compact(p->sLT)) make_desc(st, p->LcT, p->sLT, &p->dLT);
-        if (schedule_is_compact(p->sUT)) make_desc(st, p->UcT, p->sUT, &p->dUT);
+        sweep_tables(st, p, {&p->LcT, true, &p->sLT, &p->dLT}, {&p->UcT, true, &p->sUT, &p->dUT}, false, &p->max_len_T);
     } else {
         transpose_storage(st, p->Lc, &p->LcT, (p->icholt_grid && !p->llt_diag_last && p->llt_gd.nx > 0) ? &p->llt_gd : nullptr);
         if (min_row_len(st, p->n, p->LcT.ptr, p->LcT.idx, p->llt_diag_last ? 1 : 2) == 0) p->degenerate = true;
         // Lc row-major lower (IChol0): LcT is upper with the diagonal first -> backward sweep;
         // Lc column-major lower (ICholT): LcT is its row-major form with the diagonal last -> forward sweep
-        const bool t_fwd = !p->llt_diag_last;
-        if (t_fwd) count_cuts_and_schedule(st, p->n, p->LcT.ptr, p->LcT.idx, p->max_lanes, &p->sLT, nullptr, &p->max_len_T);
-        else       count_cuts_and_schedule(st, p->n, p->LcT.ptr, p->LcT.idx, p->max_lanes, nullptr, &p->sLT, &p->max_len_T);
-        choose_tiling(st, p->n, p->LcT.ptr, p->LcT.idx, &p->sLT, t_fwd, p->max_lanes / kThreads);
-        build_slot_tables(st, &p->sLT, t_fwd);
-        if (schedule_is_compact(p->sLT)) make_desc(st, p->LcT, p->sLT, &p->dLT);
+        sweep_tables(st, p, {&p->LcT, !p->llt_diag_last, &p->sLT, &p->dLT}, {}, true, &p->max_len_T);
     }
     p->haveT = true;
 }
@@ -1007,17 +1068,6 @@ int apply_block_dev(ilupp_precond *p, double *X, int64_t k, int transpose)
     return ILUPP_OK;
 }
 
-// an object under construction: destroyed (its side stream synchronised, its pool blocks given back) when the construction unwinds --
-// a HIP error thrown from the middle of ilu0_factor leaves nothing behind
-struct ObjGuard {
-    ilupp_precond *p;
-    explicit ObjGuard(ilupp_precond *q) : p(q) {}
-    ~ObjGuard() { if (p) { if (p->side) (void)stream_sync(p->side); destroy_obj(p); } }
-    ilupp_precond *release() { ilupp_precond *q = p; p = nullptr; return q; }
-    ObjGuard(const ObjGuard &) = delete;
-    ObjGuard &operator=(const ObjGuard &) = delete;
-};
-
 int ilu0_create_common(const DevMat &A, int is_csr, const int32_t *head, ilupp_precond **out, ilupp_precond *made = nullptr)
 {
     ObjGuard g(made ? made : new_obj(A.n));
@@ -1069,22 +1119,12 @@ int ilupp_hip_ilu0_create(const double *data, const int32_t *indices, const int3
     API_TRY_BUILD
     if (!out) { set_error("null output"); return ILUPP_ERR_INVALID; }
     *out = nullptr;
-    int rc = validate(indptr, n);
+    MatGuard A;
+    const int rc = upload(data, indices, indptr, n, true, &A.m);
     if (rc) return rc;
-    const int64_t nnz = indptr[n];
-    DevMat A;
-    A.n = n; A.nnz = nnz; A.is_csr = true; A.owns = true;
-    ILUPP_HIP(pool_malloc(&A.ptr, sizeof(int32_t) * (size_t)(n + 1)));
-    ILUPP_HIP(pool_malloc(&A.idx, sizeof(int32_t) * (size_t)(nnz > 0 ? nnz : 1)));
-    ILUPP_HIP(pool_malloc(&A.val, sizeof(double) * (size_t)(nnz > 0 ? nnz : 1)));
-    ILUPP_HIP(hipMemcpy(A.ptr, indptr, sizeof(int32_t) * (size_t)(n + 1), hipMemcpyHostToDevice));
-    ILUPP_HIP(hipMemcpy(A.idx, indices, sizeof(int32_t) * (size_t)nnz, hipMemcpyHostToDevice));
-    ILUPP_HIP(hipMemcpy(A.val, data, sizeof(double) * (size_t)nnz, hipMemcpyHostToDevice));
-    int32_t head[10] = {indptr[0], indptr[1], -1, -1, -1, -1, -1, -1, -1, -1};
-    for (int i = 0; i < 8 && i < nnz; ++i) head[2 + i] = indices[i];
-    rc = ilu0_create_common(A, is_csr, head, out);
-    A.release();
-    return rc;
+    int32_t head[10];
+    host_head(indptr, indices, A.m.nnz, head);
+    return ilu0_create_common(A.m, is_csr, head, out);
     API_CATCH
 }
 
@@ -1097,14 +1137,10 @@ int ilupp_hip_ilu0_create_device(const double *d_data, const int32_t *d_indices,
     if (n <= 0 || !d_indptr) { set_error("matrix has size 0!"); return ILUPP_ERR_INVALID; }
     // indptr[n], and the head of the matrix for grid.hip's guess: one read-back
     int32_t head[10];
-    ilupp_precond *p = new_obj(n);                 // (first: the read-back below also cleans the object's verdict word)
-    int32_t nnz32 = 0;
-    try { nnz32 = read_device_head(d_indptr, d_indices, n, head, p->ctrl + 8); } catch (...) { destroy_obj(p); throw; }
-    p->verdict_clean = true;
-    DevMat A;
-    A.n = n; A.nnz = nnz32; A.is_csr = true; A.owns = false;
-    A.ptr = const_cast<int32_t *>(d_indptr); A.idx = const_cast<int32_t *>(d_indices); A.val = const_cast<double *>(d_data);
-    return ilu0_create_common(A, is_csr, head, out, p);           // (owns p from here: ObjGuard)
+    ObjGuard g(new_obj(n));                        // (first: the read-back below also cleans the object's verdict word)
+    const int32_t nnz32 = read_device_head(d_indptr, d_indices, n, head, g.p->ctrl + 8);
+    g.p->verdict_clean = true;
+    return ilu0_create_common(borrow_csr(d_data, d_indices, d_indptr, n, nnz32, true), is_csr, head, out, g.release());
     API_CATCH
 }
 
@@ -1120,15 +1156,9 @@ int ilupp_hip_ilu0_create_device_nnz(const double *d_data, const int32_t *d_indi
         GridDims gd = {0, 0, 0};
         if (nnz > 0 && nnz < (1LL << 31) && grid_shape_recall(n, nnz, &gd, d_indices)) {
             int32_t head[10] = {0, gd.nz > 1 ? 4 : 3, 0, 1, gd.nx, gd.nz > 1 ? gd.nx * gd.ny : -1, -1, -1, -1, -1};
-            DevMat A;
-            A.n = n; A.nnz = nnz; A.is_csr = true; A.owns = false;
-            A.ptr = const_cast<int32_t *>(d_indptr); A.idx = const_cast<int32_t *>(d_indices); A.val = const_cast<double *>(d_data);
             ObjGuard g(new_obj(n));
-            ilupp_precond *p = g.p;
-            p->kind = KIND_LU; p->nnz_mode = NNZ_GENERIC_LU; p->input_csc = !is_csr;
-            p->no_general_retry = true;            // (a failed proof must not run the general pass with an nnz nobody has checked)
-            const int rc = ilu0_factor(p, A, head);
-            if (rc == ILUPP_OK) { *out = g.release(); return ILUPP_OK; }
+            g.p->no_general_retry = true;          // (a failed proof must not run the general pass with an nnz nobody has checked)
+            const int rc = ilu0_create_common(borrow_csr(d_data, d_indices, d_indptr, n, nnz, true), is_csr, head, out, g.release());
             if (rc != ILUPP_ERR_UNSUPPORTED) return rc;
         }
         API_CATCH
@@ -1155,9 +1185,7 @@ int ilupp_hip_ilu0_refactor_device(ilupp_precond *p, const double *d_data, const
         ILUPP_HIP(hipStreamSynchronize(p->stream));
         if ((int64_t)nnz32 != p->nnzA) { set_error("ILU0 refactor: the matrix does not have the analysed pattern"); return ILUPP_ERR_INVALID; }
     }
-    DevMat A;
-    A.n = p->n; A.is_csr = true; A.owns = false; A.nnz = p->nnzA;
-    A.ptr = const_cast<int32_t *>(d_indptr); A.idx = const_cast<int32_t *>(d_indices); A.val = const_cast<double *>(d_data);
+    const DevMat A = borrow_csr(d_data, d_indices, d_indptr, p->n, p->nnzA, true);
     hipStream_t st = p->stream;
     ILUPP_HIP(hipEventRecord(p->ev[1], st));
     float kms = 0.f;
@@ -1189,27 +1217,13 @@ int ilupp_hip_ilu0_refactor_device(ilupp_precond *p, const double *d_data, const
 // preconditioner): backward schedules and descriptors of the stored arrays (the forward sweeps run on transposed copies, built on first use)
 static void utu_analyse(ilupp_precond *p)
 {
-    hipStream_t st = p->stream;
-    const int32_t n = p->n;
-    int32_t m1 = 0, m2 = 0;
-    count_cuts_and_schedule(st, n, p->Lc.ptr, p->Lc.idx, p->max_lanes, nullptr, &p->sL, &m1);
-    count_cuts_and_schedule(st, n, p->Uc.ptr, p->Uc.idx, p->max_lanes, nullptr, &p->sU, &m2);
-    p->max_row_len = m1 > m2 ? m1 : m2;
-    choose_tiling(st, n, p->Lc.ptr, p->Lc.idx, &p->sL, false, p->max_lanes / kThreads);
-    choose_tiling(st, n, p->Uc.ptr, p->Uc.idx, &p->sU, false, p->max_lanes / kThreads);
-    build_slot_tables(st, &p->sL, false);
-    build_slot_tables(st, &p->sU, false);
-    p->compact = schedule_is_compact(p->sL) && schedule_is_compact(p->sU);
-    if (p->compact) {
-        make_desc(st, p->Lc, p->sL, &p->dL);
-        make_desc(st, p->Uc, p->sU, &p->dU);
-    }
+    p->compact = sweep_tables(p->stream, p, {&p->Lc, false, &p->sL, &p->dL}, {&p->Uc, false, &p->sU, &p->dU}, true, &p->max_row_len);
 }
 
 static int iluc_create_common(DevMat &A, int32_t n, int is_csr, int32_t max_fill_in, double threshold, ilupp_precond **out)
 {
     // (guards: an ILUPP_HIP that throws below must leave neither the object nor the factors behind)
-    struct ObjGuard { ilupp_precond *p; ~ObjGuard() { if (p) destroy_obj(p); } } og{new_obj(n)};
+    ObjGuard og(new_obj(n));
     ilupp_precond *p = og.p;
     p->kind = KIND_UTU;
     p->nnz_mode = NNZ_GENERIC_LU;
@@ -1218,7 +1232,7 @@ static int iluc_create_common(DevMat &A, int32_t n, int is_csr, int32_t max_fill
     ILUPP_HIP(hipEventRecord(p->ev[0], st));
     int32_t err_row = -1;
     float kms = 0.f;
-    struct MatGuard { DevMat m; ~MatGuard() { m.release(); } } gl, gu;
+    MatGuard gl, gu;
     DevMat &Lcol = gl.m, &Urow = gu.m;             // L by columns (unit diagonal first), U by rows (pivot first)
     int rc = iluc_factor(st, A, max_fill_in, threshold, &Lcol, &Urow, &err_row, &kms);
     ILUPP_HIP(hipEventRecord(p->ev[1], st));
@@ -1234,22 +1248,15 @@ static int iluc_create_common(DevMat &A, int32_t n, int is_csr, int32_t max_fill
     if (is_csr) { p->Lc = Lcol; p->Uc = Urow; } else { p->Lc = Urow; p->Uc = Lcol; }
     Lcol.ptr = Lcol.idx = nullptr; Lcol.val = nullptr; Urow.ptr = Urow.idx = nullptr; Urow.val = nullptr;      // (the object owns them now)
     utu_analyse(p);
-    ILUPP_HIP(hipEventRecord(p->ev[2], st));
-    ILUPP_HIP(stream_sync(st));
-    ILUPP_HIP(hipEventElapsedTime(&p->tm.numeric_ms, p->ev[0], p->ev[1]));
-    ILUPP_HIP(hipEventElapsedTime(&p->tm.analysis_ms, p->ev[1], p->ev[2]));
-    p->tm.numeric_kernel_ms = kms;
-    *out = p;
-    og.p = nullptr;
+    finish_timing(p, kms);
+    *out = og.release();
     return ILUPP_OK;
 }
 
 static int ilut_create_common(DevMat &A, int32_t n, int is_csr, int32_t max_fill_in, double threshold, ilupp_precond **out)
 {
-    int rc = ILUPP_OK;
-    const int64_t nnz = A.nnz;
-    (void)nnz; (void)is_csr;
-    ilupp_precond *p = new_obj(n);
+    ObjGuard g(new_obj(n));
+    ilupp_precond *p = g.p;
     p->kind = KIND_LU;
     p->nnz_mode = NNZ_ILUT;
     p->input_csc = !is_csr;      // CSC: factor the row-major view A^T, swap roles on egress (preconditioner_implementation.h:999-1001)
@@ -1257,37 +1264,19 @@ static int ilut_create_common(DevMat &A, int32_t n, int is_csr, int32_t max_fill
     ILUPP_HIP(hipEventRecord(p->ev[0], st));
     int32_t err_row = -1;
     float kms = 0.f;
-    rc = ilut_factor(st, A, max_fill_in, threshold, &p->Lc, &p->Uc, &err_row, &kms);
+    const int rc = ilut_factor(st, A, max_fill_in, threshold, &p->Lc, &p->Uc, &err_row, &kms);
     ILUPP_HIP(hipEventRecord(p->ev[1], st));
     A.release();
     if (rc) {
         if (rc == ILUPP_ERR_ZERO_PIVOT) set_error("ILUT_heap: encountered zero pivot in row " + std::to_string(err_row));   // ILUT.hpp:269-270
         else if (rc == ILUPP_ERR_TIMEOUT) set_error("ILUT: dependency wait timed out");
         else set_error("ILUT: working row overflow");
-        destroy_obj(p);
         return rc;
     }
     // solve schedules from the factors' own patterns
-    int32_t m1 = 0, m2 = 0;
-    count_cuts_and_schedule(st, n, p->Lc.ptr, p->Lc.idx, p->max_lanes, &p->sL, nullptr, &m1);
-    count_cuts_and_schedule(st, n, p->Uc.ptr, p->Uc.idx, p->max_lanes, nullptr, &p->sU, &m2);
-    p->max_row_len = m1 > m2 ? m1 : m2;
-    const int max_wgs = p->max_lanes / kThreads;
-    choose_tiling(st, n, p->Lc.ptr, p->Lc.idx, &p->sL, true, max_wgs);
-    choose_tiling(st, n, p->Uc.ptr, p->Uc.idx, &p->sU, false, max_wgs);
-    build_slot_tables(st, &p->sL, true);
-    build_slot_tables(st, &p->sU, false);
-    p->compact = schedule_is_compact(p->sL) && schedule_is_compact(p->sU);
-    if (p->compact) {
-        make_desc(st, p->Lc, p->sL, &p->dL);
-        make_desc(st, p->Uc, p->sU, &p->dU);
-    }
-    ILUPP_HIP(hipEventRecord(p->ev[2], st));
-    ILUPP_HIP(stream_sync(st));
-    ILUPP_HIP(hipEventElapsedTime(&p->tm.numeric_ms, p->ev[0], p->ev[1]));
-    ILUPP_HIP(hipEventElapsedTime(&p->tm.analysis_ms, p->ev[1], p->ev[2]));
-    p->tm.numeric_kernel_ms = kms;
-    *out = p;
+    p->compact = sweep_tables(st, p, {&p->Lc, true, &p->sL, &p->dL}, {&p->Uc, false, &p->sU, &p->dU}, true, &p->max_row_len);
+    finish_timing(p, kms);
+    *out = g.release();
     return ILUPP_OK;
 }
 
@@ -1299,20 +1288,10 @@ int ilupp_hip_ilut_create(const double *data, const int32_t *indices, const int3
     API_TRY_BUILD
     if (!out) { set_error("null output"); return ILUPP_ERR_INVALID; }
     *out = nullptr;
-    int rc = validate(indptr, n);
+    MatGuard A;
+    const int rc = upload(data, indices, indptr, n, true, &A.m);
     if (rc) return rc;
-    const int64_t nnz = indptr[n];
-    DevMat A;
-    A.n = n; A.nnz = nnz; A.is_csr = true; A.owns = true;
-    ILUPP_HIP(pool_malloc(&A.ptr, sizeof(int32_t) * (size_t)(n + 1)));
-    ILUPP_HIP(pool_malloc(&A.idx, sizeof(int32_t) * (size_t)(nnz > 0 ? nnz : 1)));
-    ILUPP_HIP(pool_malloc(&A.val, sizeof(double) * (size_t)(nnz > 0 ? nnz : 1)));
-    ILUPP_HIP(hipMemcpy(A.ptr, indptr, sizeof(int32_t) * (size_t)(n + 1), hipMemcpyHostToDevice));
-    ILUPP_HIP(hipMemcpy(A.idx, indices, sizeof(int32_t) * (size_t)nnz, hipMemcpyHostToDevice));
-    ILUPP_HIP(hipMemcpy(A.val, data, sizeof(double) * (size_t)nnz, hipMemcpyHostToDevice));
-    rc = ilut_create_common(A, n, is_csr, max_fill_in, threshold, out);
-    A.release();
-    return rc;
+    return ilut_create_common(A.m, n, is_csr, max_fill_in, threshold, out);
     API_CATCH
 }
 
@@ -1324,10 +1303,7 @@ int ilupp_hip_ilut_create_device(const double *d_data, const int32_t *d_indices,
     if (!out) { set_error("null output"); return ILUPP_ERR_INVALID; }
     *out = nullptr;
     if (n <= 0 || !d_indptr) { set_error("matrix has size 0!"); return ILUPP_ERR_INVALID; }
-    const int32_t nnz32 = read_device_nnz(d_indptr, n);
-    DevMat A;
-    A.n = n; A.nnz = nnz32; A.is_csr = true; A.owns = false;
-    A.ptr = const_cast<int32_t *>(d_indptr); A.idx = const_cast<int32_t *>(d_indices); A.val = const_cast<double *>(d_data);
+    DevMat A = borrow_csr(d_data, d_indices, d_indptr, n, read_device_nnz(d_indptr, n), true);
     return ilut_create_common(A, n, is_csr, max_fill_in, threshold, out);
     API_CATCH
 }
@@ -1339,20 +1315,10 @@ int ilupp_hip_iluc_create(const double *data, const int32_t *indices, const int3
     API_TRY_BUILD
     if (!out) { set_error("null output"); return ILUPP_ERR_INVALID; }
     *out = nullptr;
-    int rc = validate(indptr, n);
+    MatGuard A;
+    const int rc = upload(data, indices, indptr, n, true, &A.m);
     if (rc) return rc;
-    const int64_t nnz = indptr[n];
-    DevMat A;
-    A.n = n; A.nnz = nnz; A.is_csr = true; A.owns = true;
-    ILUPP_HIP(pool_malloc(&A.ptr, sizeof(int32_t) * (size_t)(n + 1)));
-    ILUPP_HIP(pool_malloc(&A.idx, sizeof(int32_t) * (size_t)(nnz > 0 ? nnz : 1)));
-    ILUPP_HIP(pool_malloc(&A.val, sizeof(double) * (size_t)(nnz > 0 ? nnz : 1)));
-    ILUPP_HIP(hipMemcpy(A.ptr, indptr, sizeof(int32_t) * (size_t)(n + 1), hipMemcpyHostToDevice));
-    ILUPP_HIP(hipMemcpy(A.idx, indices, sizeof(int32_t) * (size_t)nnz, hipMemcpyHostToDevice));
-    ILUPP_HIP(hipMemcpy(A.val, data, sizeof(double) * (size_t)nnz, hipMemcpyHostToDevice));
-    rc = iluc_create_common(A, n, is_csr, max_fill_in, threshold, out);
-    A.release();
-    return rc;
+    return iluc_create_common(A.m, n, is_csr, max_fill_in, threshold, out);
     API_CATCH
 }
 
@@ -1363,59 +1329,44 @@ int ilupp_hip_iluc_create_device(const double *d_data, const int32_t *d_indices,
     if (!out) { set_error("null output"); return ILUPP_ERR_INVALID; }
     *out = nullptr;
     if (n <= 0 || !d_indptr) { set_error("matrix has size 0!"); return ILUPP_ERR_INVALID; }
-    const int32_t nnz32 = read_device_nnz(d_indptr, n);
-    DevMat A;
-    A.n = n; A.nnz = nnz32; A.is_csr = true; A.owns = false;
-    A.ptr = const_cast<int32_t *>(d_indptr); A.idx = const_cast<int32_t *>(d_indices); A.val = const_cast<double *>(d_data);
+    DevMat A = borrow_csr(d_data, d_indices, d_indptr, n, read_device_nnz(d_indptr, n), true);
     return iluc_create_common(A, n, is_csr, max_fill_in, threshold, out);
     API_CATCH
 }
 
 }  // extern "C"
 
-static int ichol0_create_common(DevMat &A, int32_t n, int is_csr, ilupp_precond **out)
+static int ichol0_create_common(DevMat &A, int32_t n, ilupp_precond **out)
 {
-    int rc = ILUPP_OK;
-    const int64_t nnz = A.nnz;
-    (void)nnz; (void)is_csr;
-    ilupp_precond *p = new_obj(n);
+    ObjGuard g(new_obj(n));
+    ilupp_precond *p = g.p;
     p->kind = KIND_LLT;
     p->nnz_mode = NNZ_LLT;
     p->llt_diag_last = true;
     hipStream_t st = p->stream;
     ILUPP_HIP(hipEventRecord(p->ev[0], st));
     int32_t missing = -1;
-    rc = triangular_part(st, A, true, &p->Lc, &missing);
+    int rc = triangular_part(st, A, true, &p->Lc, &missing);
     ILUPP_HIP(stream_sync(st));
     A.release();
     if (rc == ILUPP_ERR_NO_DIAGONAL) {
         set_error("IChol0: structurally missing diagonal entry in row " + std::to_string(missing));
-        destroy_obj(p);
         return rc;
     }
     p->Lc.is_csr = true;
-    count_cuts_and_schedule(st, n, p->Lc.ptr, p->Lc.idx, p->max_lanes, &p->sL, nullptr, &p->max_row_len);
-    choose_tiling(st, n, p->Lc.ptr, p->Lc.idx, &p->sL, true, p->max_lanes / kThreads);
-    build_slot_tables(st, &p->sL, true);
-    p->compact = schedule_is_compact(p->sL);
-    if (p->compact) make_desc(st, p->Lc, p->sL, &p->dL);
+    p->compact = sweep_tables(st, p, {&p->Lc, true, &p->sL, &p->dL}, {}, true, &p->max_row_len);
     ILUPP_HIP(hipEventRecord(p->ev[1], st));
     float kms = 0.f;
     // stencil-like lower triangles whose rows are "simple" (5-/7-point): the static form (st.hip); everything else: the dataflow kernel over chains
     p->chol_static = ichol0_numeric_st(st, &p->Lc, p->sL, p->ctrl, &kms, &rc);
     if (!p->chol_static)
         rc = ichol0_numeric(st, &p->Lc, p->sL, p->max_row_len, p->done, p->ctrl, &kms);
-    ILUPP_HIP(hipEventRecord(p->ev[2], st));
-    ILUPP_HIP(stream_sync(st));
-    ILUPP_HIP(hipEventElapsedTime(&p->tm.analysis_ms, p->ev[0], p->ev[1]));
-    ILUPP_HIP(hipEventElapsedTime(&p->tm.numeric_ms, p->ev[1], p->ev[2]));
-    p->tm.numeric_kernel_ms = kms;
+    finish_timing(p, kms, true);
     if (rc) {
         if (rc == ILUPP_ERR_TIMEOUT) set_error("IChol0: dependency wait timed out");
-        destroy_obj(p);
         return rc;
     }
-    *out = p;
+    *out = g.release();
     return ILUPP_OK;
 }
 
@@ -1428,20 +1379,10 @@ int ilupp_hip_ichol0_create(const double *data, const int32_t *indices, const in
     (void)is_csr;     // IChol0 keeps idx <= major in either orientation and labels the result ROW (IChol.hpp:63-68)
     if (!out) { set_error("null output"); return ILUPP_ERR_INVALID; }
     *out = nullptr;
-    int rc = validate(indptr, n);
+    MatGuard A;
+    const int rc = upload(data, indices, indptr, n, true, &A.m);
     if (rc) return rc;
-    const int64_t nnz = indptr[n];
-    DevMat A;
-    A.n = n; A.nnz = nnz; A.is_csr = true; A.owns = true;
-    ILUPP_HIP(pool_malloc(&A.ptr, sizeof(int32_t) * (size_t)(n + 1)));
-    ILUPP_HIP(pool_malloc(&A.idx, sizeof(int32_t) * (size_t)(nnz > 0 ? nnz : 1)));
-    ILUPP_HIP(pool_malloc(&A.val, sizeof(double) * (size_t)(nnz > 0 ? nnz : 1)));
-    ILUPP_HIP(hipMemcpy(A.ptr, indptr, sizeof(int32_t) * (size_t)(n + 1), hipMemcpyHostToDevice));
-    ILUPP_HIP(hipMemcpy(A.idx, indices, sizeof(int32_t) * (size_t)nnz, hipMemcpyHostToDevice));
-    ILUPP_HIP(hipMemcpy(A.val, data, sizeof(double) * (size_t)nnz, hipMemcpyHostToDevice));
-    rc = ichol0_create_common(A, n, is_csr, out);
-    A.release();
-    return rc;
+    return ichol0_create_common(A.m, n, out);
     API_CATCH
 }
 
@@ -1452,22 +1393,17 @@ int ilupp_hip_ichol0_create_device(const double *d_data, const int32_t *d_indice
     if (!out) { set_error("null output"); return ILUPP_ERR_INVALID; }
     *out = nullptr;
     if (n <= 0 || !d_indptr) { set_error("matrix has size 0!"); return ILUPP_ERR_INVALID; }
-    const int32_t nnz32 = read_device_nnz(d_indptr, n);
-    DevMat A;
-    A.n = n; A.nnz = nnz32; A.is_csr = true; A.owns = false;
-    A.ptr = const_cast<int32_t *>(d_indptr); A.idx = const_cast<int32_t *>(d_indices); A.val = const_cast<double *>(d_data);
-    return ichol0_create_common(A, n, is_csr, out);
+    DevMat A = borrow_csr(d_data, d_indices, d_indptr, n, read_device_nnz(d_indptr, n), true);
+    return ichol0_create_common(A, n, out);
     API_CATCH
 }
 }  // extern "C"
 
-static int icholt_create_common(DevMat &A, int32_t n, int is_csr, int32_t add_fill_in, double threshold, ilupp_precond **out,
-                                const int32_t *head = nullptr)
+static int icholt_create_common(DevMat &A, int32_t n, int32_t add_fill_in, double threshold, ilupp_precond **out, const int32_t *head)
 {
     int rc = ILUPP_OK;
-    const int64_t nnz = A.nnz;
-    (void)nnz; (void)is_csr;
-    ilupp_precond *p = new_obj(n);
+    ObjGuard g(new_obj(n));
+    ilupp_precond *p = g.p;
     p->kind = KIND_LLT;
     p->nnz_mode = NNZ_LLT;
     p->llt_diag_last = false;
@@ -1477,13 +1413,7 @@ static int icholt_create_common(DevMat &A, int32_t n, int is_csr, int32_t add_fi
     // the schedule of the sweeps: Lc = CSC lower, diagonal first; its arrays read as CSR are L^T (upper, diagonal first): backward sweep
     auto sweep_schedule = [&](hipStream_t q) {
         p->degenerate = min_row_len(q, n, p->Lc.ptr, p->Lc.idx, 1) == 0;      // (column-major lower: diagonal first)
-        int32_t m1 = 0;
-        count_cuts_and_schedule(q, n, p->Lc.ptr, p->Lc.idx, p->max_lanes, nullptr, &p->sL, &m1);
-        p->max_row_len = m1;
-        choose_tiling(q, n, p->Lc.ptr, p->Lc.idx, &p->sL, false, p->max_lanes / kThreads);
-        build_slot_tables(q, &p->sL, false);
-        p->compact = schedule_is_compact(p->sL);
-        if (p->compact) make_desc(q, p->Lc, p->sL, &p->dL);
+        p->compact = sweep_tables(q, p, {&p->Lc, false, &p->sL, &p->dL}, {}, true, &p->max_row_len);
     };
     // no fill allowed, nothing dropped by size, on a box grid: every column keeps A's entries if they all outweigh the one-step fill --
     // assumed, computed on the wavefront x + 2y + 3z, verified column by column (icholt_grid.hip); anything else: the general way.
@@ -1575,14 +1505,14 @@ static int icholt_create_common(DevMat &A, int32_t n, int is_csr, int32_t add_fi
         }
     }
     if (!p->icholt_grid) {
-        DevMat T;
+        MatGuard T;
         int32_t missing = -1;
-        rc = triangular_part(st, A, false, &T, &missing);        // natural_triangular_part(false): keep idx >= major
+        rc = triangular_part(st, A, false, &T.m, &missing);      // natural_triangular_part(false): keep idx >= major
         ILUPP_HIP(stream_sync(st));
         A.release();
         // a missing diagonal is caught by the reference inside the column loop (IChol.hpp:105-107); same error here
-        rc = icholt_factor(st, T, add_fill_in, threshold, &p->Lc, &kms);
-        T.release();
+        rc = icholt_factor(st, T.m, add_fill_in, threshold, &p->Lc, &kms);
+        T.m.release();
     } else {
         A.release();
     }
@@ -1596,16 +1526,11 @@ static int icholt_create_common(DevMat &A, int32_t n, int is_csr, int32_t add_fi
                                                               "factor and divides by the column's first stored entry, this build does not support it");
         else if (rc == ILUPP_ERR_TIMEOUT) set_error("ICholT: dependency wait timed out");
         else set_error("append_row: insufficient memory reserved (or a working column beyond the kernel's largest capacity class)");
-        destroy_obj(p);
         return rc;
     }
     if (!p->icholt_grid) sweep_schedule(st);
-    ILUPP_HIP(hipEventRecord(p->ev[2], st));
-    ILUPP_HIP(stream_sync(st));
-    ILUPP_HIP(hipEventElapsedTime(&p->tm.numeric_ms, p->ev[0], p->ev[1]));
-    ILUPP_HIP(hipEventElapsedTime(&p->tm.analysis_ms, p->ev[1], p->ev[2]));
-    p->tm.numeric_kernel_ms = kms;
-    *out = p;
+    finish_timing(p, kms);
+    *out = g.release();
     return ILUPP_OK;
 }
 
@@ -1618,22 +1543,12 @@ int ilupp_hip_icholt_create(const double *data, const int32_t *indices, const in
     (void)is_csr;     // ICholT keeps idx >= major in either orientation and labels the result COLUMN (IChol.hpp:158-164)
     if (!out) { set_error("null output"); return ILUPP_ERR_INVALID; }
     *out = nullptr;
-    int rc = validate(indptr, n);
+    MatGuard A;
+    const int rc = upload(data, indices, indptr, n, true, &A.m);
     if (rc) return rc;
-    const int64_t nnz = indptr[n];
-    DevMat A;
-    A.n = n; A.nnz = nnz; A.is_csr = true; A.owns = true;
-    ILUPP_HIP(pool_malloc(&A.ptr, sizeof(int32_t) * (size_t)(n + 1)));
-    ILUPP_HIP(pool_malloc(&A.idx, sizeof(int32_t) * (size_t)(nnz > 0 ? nnz : 1)));
-    ILUPP_HIP(pool_malloc(&A.val, sizeof(double) * (size_t)(nnz > 0 ? nnz : 1)));
-    ILUPP_HIP(hipMemcpy(A.ptr, indptr, sizeof(int32_t) * (size_t)(n + 1), hipMemcpyHostToDevice));
-    ILUPP_HIP(hipMemcpy(A.idx, indices, sizeof(int32_t) * (size_t)nnz, hipMemcpyHostToDevice));
-    ILUPP_HIP(hipMemcpy(A.val, data, sizeof(double) * (size_t)nnz, hipMemcpyHostToDevice));
-    int32_t head[10] = {indptr[0], indptr[1], -1, -1, -1, -1, -1, -1, -1, -1};
-    for (int i = 0; i < 8 && i < nnz; ++i) head[2 + i] = indices[i];
-    rc = icholt_create_common(A, n, is_csr, add_fill_in, threshold, out, head);
-    A.release();
-    return rc;
+    int32_t head[10];
+    host_head(indptr, indices, A.m.nnz, head);
+    return icholt_create_common(A.m, n, add_fill_in, threshold, out, head);
     API_CATCH
 }
 
@@ -1645,11 +1560,8 @@ int ilupp_hip_icholt_create_device(const double *d_data, const int32_t *d_indice
     *out = nullptr;
     if (n <= 0 || !d_indptr) { set_error("matrix has size 0!"); return ILUPP_ERR_INVALID; }
     int32_t head[10];
-    const int32_t nnz32 = read_device_head(d_indptr, d_indices, n, head);
-    DevMat A;
-    A.n = n; A.nnz = nnz32; A.is_csr = true; A.owns = false;
-    A.ptr = const_cast<int32_t *>(d_indptr); A.idx = const_cast<int32_t *>(d_indices); A.val = const_cast<double *>(d_data);
-    return icholt_create_common(A, n, is_csr, add_fill_in, threshold, out, head);
+    DevMat A = borrow_csr(d_data, d_indices, d_indptr, n, read_device_head(d_indptr, d_indices, n, head), true);
+    return icholt_create_common(A, n, add_fill_in, threshold, out, head);
     API_CATCH
 }
 
@@ -2180,19 +2092,10 @@ int ilupp_hip_ml_create(const double *data, const int32_t *indices, const int32_
     API_TRY_BUILD
     if (!out || !params) { set_error("null argument"); return ILUPP_ERR_INVALID; }
     *out = nullptr;
-    int rc = validate(indptr, n);
+    MatGuard A;
+    const int rc = upload(data, indices, indptr, n, is_csr != 0, &A.m);
     if (rc) return rc;
-    const int64_t nnz = indptr[n];
-    struct MatGuard { DevMat m; ~MatGuard() { m.release(); } } ga;
-    DevMat &A = ga.m;
-    A.n = n; A.nnz = nnz; A.is_csr = is_csr != 0; A.owns = true;
-    ILUPP_HIP(pool_malloc(&A.ptr, sizeof(int32_t) * (size_t)(n + 1)));
-    ILUPP_HIP(pool_malloc(&A.idx, sizeof(int32_t) * (size_t)(nnz > 0 ? nnz : 1)));
-    ILUPP_HIP(pool_malloc(&A.val, sizeof(double) * (size_t)(nnz > 0 ? nnz : 1)));
-    ILUPP_HIP(hipMemcpy(A.ptr, indptr, sizeof(int32_t) * (size_t)(n + 1), hipMemcpyHostToDevice));
-    ILUPP_HIP(hipMemcpy(A.idx, indices, sizeof(int32_t) * (size_t)nnz, hipMemcpyHostToDevice));
-    ILUPP_HIP(hipMemcpy(A.val, data, sizeof(double) * (size_t)nnz, hipMemcpyHostToDevice));
-    return ml_create_common(A, params, out);
+    return ml_create_common(A.m, params, out);
     API_CATCH
 }
 
@@ -2234,20 +2137,9 @@ int ilupp_hip_ml_create_batch(int32_t count, const double *const *data, const in
             if (i >= count) break;
             int rc;
             try {
-                rc = validate(indptr[i], n[i]);
-                if (!rc) {
-                    const int64_t nnz = indptr[i][n[i]];
-                    struct MatGuard { DevMat m; ~MatGuard() { m.release(); } } ga;
-                    DevMat &A = ga.m;
-                    A.n = n[i]; A.nnz = nnz; A.is_csr = is_csr != 0; A.owns = true;
-                    ILUPP_HIP(pool_malloc(&A.ptr, sizeof(int32_t) * (size_t)(n[i] + 1)));
-                    ILUPP_HIP(pool_malloc(&A.idx, sizeof(int32_t) * (size_t)(nnz > 0 ? nnz : 1)));
-                    ILUPP_HIP(pool_malloc(&A.val, sizeof(double) * (size_t)(nnz > 0 ? nnz : 1)));
-                    ILUPP_HIP(hipMemcpy(A.ptr, indptr[i], sizeof(int32_t) * (size_t)(n[i] + 1), hipMemcpyHostToDevice));
-                    ILUPP_HIP(hipMemcpy(A.idx, indices[i], sizeof(int32_t) * (size_t)nnz, hipMemcpyHostToDevice));
-                    ILUPP_HIP(hipMemcpy(A.val, data[i], sizeof(double) * (size_t)nnz, hipMemcpyHostToDevice));
-                    rc = ml_create_common(A, params, &out[i]);
-                }
+                MatGuard A;
+                rc = upload(data[i], indices[i], indptr[i], n[i], is_csr != 0, &A.m);
+                if (!rc) rc = ml_create_common(A.m, params, &out[i]);
             } catch (const ilupp::HipError &e) { ilupp::d2h_cancel_all(); rc = ilupp::report(e); }
             catch (const std::bad_alloc &) { ilupp::set_error("out of host memory"); rc = ILUPP_ERR_MEMORY; }
             catch (...) { ilupp::set_error("unexpected exception in a batch worker"); rc = ILUPP_ERR_HIP; }     // (a worker must reach chain_batch_leave)
@@ -2291,10 +2183,7 @@ int ilupp_hip_ml_create_device(const double *d_data, const int32_t *d_indices, c
     if (!out || !params) { set_error("null argument"); return ILUPP_ERR_INVALID; }
     *out = nullptr;
     if (n <= 0 || !d_indptr) { set_error("matrix has size 0!"); return ILUPP_ERR_INVALID; }
-    DevMat A;
-    A.n = n; A.nnz = read_device_nnz(d_indptr, n); A.is_csr = is_csr != 0; A.owns = false;
-    A.ptr = const_cast<int32_t *>(d_indptr); A.idx = const_cast<int32_t *>(d_indices); A.val = const_cast<double *>(d_data);
-    return ml_create_common(A, params, out);
+    return ml_create_common(borrow_csr(d_data, d_indices, d_indptr, n, read_device_nnz(d_indptr, n), is_csr != 0), params, out);
     API_CATCH
 }
 
@@ -2353,16 +2242,8 @@ int solve_build(const double *data, const int32_t *indices, const int32_t *indpt
                 ilupp_ml **m)
 {
     API_TRY
-    int rc = validate(indptr, n);
+    const int rc = upload(data, indices, indptr, n, is_csr != 0, A);
     if (rc) return rc;
-    const int64_t nnz = indptr[n];
-    A->n = n; A->nnz = nnz; A->is_csr = is_csr != 0; A->owns = true;
-    ILUPP_HIP(pool_malloc(&A->ptr, sizeof(int32_t) * (size_t)(n + 1)));
-    ILUPP_HIP(pool_malloc(&A->idx, sizeof(int32_t) * (size_t)(nnz > 0 ? nnz : 1)));
-    ILUPP_HIP(pool_malloc(&A->val, sizeof(double) * (size_t)(nnz > 0 ? nnz : 1)));
-    ILUPP_HIP(hipMemcpy(A->ptr, indptr, sizeof(int32_t) * (size_t)(n + 1), hipMemcpyHostToDevice));
-    ILUPP_HIP(hipMemcpy(A->idx, indices, sizeof(int32_t) * (size_t)nnz, hipMemcpyHostToDevice));
-    ILUPP_HIP(hipMemcpy(A->val, data, sizeof(double) * (size_t)nnz, hipMemcpyHostToDevice));
     return ml_create_common(*A, params, m);
     API_CATCH
 }
@@ -2540,7 +2421,7 @@ int ilucp_create_common(DevMat &A, int32_t n, int is_csr, int32_t max_fill_in, d
     ILUPP_HIP(pool_malloc(&m->perm, sizeof(int32_t) * (size_t)n));
     ILUPP_HIP(pool_malloc(&m->tmp, sizeof(double) * (size_t)n));
     ILUPP_HIP(hipEventRecord(p->ev[0], st));
-    struct MatGuard { DevMat m; ~MatGuard() { m.release(); } } gl;
+    MatGuard gl;
     const int rc = ilucp_factor(st, A, max_fill_in, threshold, piv_tol, row_pos, mem_factor, &gl.m, &m->U, m->perm, &m->zero_pivots, &m->kernel_ms);
     ILUPP_HIP(hipEventRecord(p->ev[1], st));
     A.release();
@@ -2564,11 +2445,7 @@ int ilucp_create_common(DevMat &A, int32_t n, int is_csr, int32_t max_fill_in, d
     p->Lc = gl.m; p->Uc = Up;
     gl.m = DevMat();                                            // (the object owns the arrays now)
     utu_analyse(p);
-    ILUPP_HIP(hipEventRecord(p->ev[2], st));
-    ILUPP_HIP(stream_sync(st));
-    ILUPP_HIP(hipEventElapsedTime(&p->tm.numeric_ms, p->ev[0], p->ev[1]));
-    ILUPP_HIP(hipEventElapsedTime(&p->tm.analysis_ms, p->ev[1], p->ev[2]));
-    p->tm.numeric_kernel_ms = m->kernel_ms;
+    finish_timing(p, m->kernel_ms);
     *out = m;
     g.m = nullptr;
     return ILUPP_OK;
@@ -2584,19 +2461,10 @@ int ilupp_hip_ilucp_create(const double *data, const int32_t *indices, const int
     API_TRY_BUILD
     if (!out) { set_error("null output"); return ILUPP_ERR_INVALID; }
     *out = nullptr;
-    int rc = validate(indptr, n);
+    MatGuard A;
+    const int rc = upload(data, indices, indptr, n, true, &A.m);
     if (rc) return rc;
-    const int64_t nnz = indptr[n];
-    struct MatGuard { DevMat m; ~MatGuard() { m.release(); } } ga;           // (a failing copy must not leave the arrays behind)
-    DevMat &A = ga.m;
-    A.n = n; A.nnz = nnz; A.is_csr = true; A.owns = true;
-    ILUPP_HIP(pool_malloc(&A.ptr, sizeof(int32_t) * (size_t)(n + 1)));
-    ILUPP_HIP(pool_malloc(&A.idx, sizeof(int32_t) * (size_t)(nnz > 0 ? nnz : 1)));
-    ILUPP_HIP(pool_malloc(&A.val, sizeof(double) * (size_t)(nnz > 0 ? nnz : 1)));
-    ILUPP_HIP(hipMemcpy(A.ptr, indptr, sizeof(int32_t) * (size_t)(n + 1), hipMemcpyHostToDevice));
-    ILUPP_HIP(hipMemcpy(A.idx, indices, sizeof(int32_t) * (size_t)nnz, hipMemcpyHostToDevice));
-    ILUPP_HIP(hipMemcpy(A.val, data, sizeof(double) * (size_t)nnz, hipMemcpyHostToDevice));
-    return ilucp_create_common(A, n, is_csr, max_fill_in, threshold, piv_tol, row_pos, mem_factor, out);
+    return ilucp_create_common(A.m, n, is_csr, max_fill_in, threshold, piv_tol, row_pos, mem_factor, out);
     API_CATCH
 }
 
@@ -2686,25 +2554,8 @@ int ilutp_create_common(DevMat &A, int32_t n, int is_csr, int32_t max_fill_in, d
     if (rc) return rc;
     // an object of the ILUT kind: L by rows with its 1 last, U (permuted numbering) by rows with the pivot first
     p->kind = KIND_LU; p->nnz_mode = NNZ_ILUT; p->input_csc = false;
-    int32_t m1 = 0, m2 = 0;
-    count_cuts_and_schedule(st, n, p->Lc.ptr, p->Lc.idx, p->max_lanes, &p->sL, nullptr, &m1);
-    count_cuts_and_schedule(st, n, p->Uc.ptr, p->Uc.idx, p->max_lanes, nullptr, &p->sU, &m2);
-    p->max_row_len = m1 > m2 ? m1 : m2;
-    const int max_wgs = p->max_lanes / kThreads;
-    choose_tiling(st, n, p->Lc.ptr, p->Lc.idx, &p->sL, true, max_wgs);
-    choose_tiling(st, n, p->Uc.ptr, p->Uc.idx, &p->sU, false, max_wgs);
-    build_slot_tables(st, &p->sL, true);
-    build_slot_tables(st, &p->sU, false);
-    p->compact = schedule_is_compact(p->sL) && schedule_is_compact(p->sU);
-    if (p->compact) {
-        make_desc(st, p->Lc, p->sL, &p->dL);
-        make_desc(st, p->Uc, p->sU, &p->dU);
-    }
-    ILUPP_HIP(hipEventRecord(p->ev[2], st));
-    ILUPP_HIP(stream_sync(st));
-    ILUPP_HIP(hipEventElapsedTime(&p->tm.numeric_ms, p->ev[0], p->ev[1]));
-    ILUPP_HIP(hipEventElapsedTime(&p->tm.analysis_ms, p->ev[1], p->ev[2]));
-    p->tm.numeric_kernel_ms = m->kernel_ms;
+    p->compact = sweep_tables(st, p, {&p->Lc, true, &p->sL, &p->dL}, {&p->Uc, false, &p->sU, &p->dU}, true, &p->max_row_len);
+    finish_timing(p, m->kernel_ms);
     *out = m;
     g.m = nullptr;
     return ILUPP_OK;
@@ -2718,18 +2569,9 @@ extern "C" int ilupp_hip_ilutp_create(const double *data, const int32_t *indices
     API_TRY_BUILD
     if (!out) { set_error("null output"); return ILUPP_ERR_INVALID; }
     *out = nullptr;
-    int rc = validate(indptr, n);
+    MatGuard A;
+    const int rc = upload(data, indices, indptr, n, true, &A.m);
     if (rc) return rc;
-    const int64_t nnz = indptr[n];
-    struct MatGuard { DevMat m; ~MatGuard() { m.release(); } } ga;           // (a failing copy must not leave the arrays behind)
-    DevMat &A = ga.m;
-    A.n = n; A.nnz = nnz; A.is_csr = true; A.owns = true;
-    ILUPP_HIP(pool_malloc(&A.ptr, sizeof(int32_t) * (size_t)(n + 1)));
-    ILUPP_HIP(pool_malloc(&A.idx, sizeof(int32_t) * (size_t)(nnz > 0 ? nnz : 1)));
-    ILUPP_HIP(pool_malloc(&A.val, sizeof(double) * (size_t)(nnz > 0 ? nnz : 1)));
-    ILUPP_HIP(hipMemcpy(A.ptr, indptr, sizeof(int32_t) * (size_t)(n + 1), hipMemcpyHostToDevice));
-    ILUPP_HIP(hipMemcpy(A.idx, indices, sizeof(int32_t) * (size_t)nnz, hipMemcpyHostToDevice));
-    ILUPP_HIP(hipMemcpy(A.val, data, sizeof(double) * (size_t)nnz, hipMemcpyHostToDevice));
-    return ilutp_create_common(A, n, is_csr, max_fill_in, threshold, piv_tol, row_pos, mem_factor, out);
+    return ilutp_create_common(A.m, n, is_csr, max_fill_in, threshold, piv_tol, row_pos, mem_factor, out);
     API_CATCH
 }
