@@ -471,27 +471,20 @@ int ilu0_factor(ilupp_precond *p, const DevMat &A, const int32_t *head)
     int rc = ILUPP_OK;
     // A matrix whose row 0 and entry count are those of a lexicographic box-grid stencil (grid.hip): the row blocks follow from the
     // three dimensions, and ONE streaming kernel on the side stream proves the guess for every row while the lane tables are built.
+    // Its verdict comes home with the construction's last read-back.  (Measured at 256^3: k_grid_lanes only stores and the skew fixpoint
+    // lives in LDS, so they lose little next to the 4.6 TB/s stream of the proof; DESIGN.md section 4.0.2 has the other placements.)
     GridDims gd = {0, 0, 0};
     bool grid = head != nullptr && p->side != nullptr && grid_guess(A.n, A.nnz, head, &gd);
-    // where the proof runs: 0 (default) = on the side stream next to the lane-table kernels, 1 = on the object's stream before them, 2 = on
-    // the side stream next to the factor kernel.  Its verdict comes home with the construction's last read-back in every case.  (Measured
-    // at 256^3: k_grid_lanes only stores and the skew fixpoint lives in LDS, so they lose little next to the 4.6 TB/s stream of the proof --
-    // analysis 0.23 ms for 0, 0.26 for 1; the factor kernel lives on short hand-over latencies and loses more than the proof takes: 2)
-    static const int grid_mode = []() { const char *e = getenv("ILUPP_GRID_CHECK_AT"); const int v = e ? atoi(e) : 0; return (v >= 0 && v <= 2) ? v : 0; }();
     int32_t grid_bad = 0;
     bool lm = false;
     for (;;) {
         if (grid) {
             if (p->verdict_clean) p->verdict_clean = false;
             else ILUPP_HIP(hipMemsetAsync(p->ctrl + 8, 0, sizeof(int32_t), st));
-            if (grid_mode == 0) {
-                ILUPP_HIP(hipEventRecord(p->jev[0], st));
-                ILUPP_HIP(hipStreamWaitEvent(p->side, p->jev[0], 0));
-                grid_check_launch(p->side, A, gd, p->ctrl + 8);
-                ILUPP_HIP(hipEventRecord(p->jev[1], p->side));
-            } else if (grid_mode == 1) {
-                grid_check_launch(st, A, gd, p->ctrl + 8);
-            }
+            ILUPP_HIP(hipEventRecord(p->jev[0], st));
+            ILUPP_HIP(hipStreamWaitEvent(p->side, p->jev[0], 0));
+            grid_check_launch(p->side, A, gd, p->ctrl + 8);
+            ILUPP_HIP(hipEventRecord(p->jev[1], p->side));
             grid_schedules(st, A, gd, &p->Lc, &p->Uc, &p->sA, &p->sU, &p->max_row_len, max_wgs);
         } else {
             // one pass over A's pattern: row counts of L and U, diagonal check, and the factor-sweep schedules (L shares A's
@@ -514,14 +507,14 @@ int ilu0_factor(ilupp_precond *p, const DevMat &A, const int32_t *head)
         // of slots), then the record-decoding level-major form
         lm = st_analyse_ilu0(st, A, p->sA, p->sU, &p->pkL, &p->pkU, &p->flm, nullptr, (grid && grid_tables) ? &gd : nullptr);
         if (grid && !(lm && p->flm.stat && p->flm.direct) && p->no_general_retry) {
-            if (grid_mode == 0) ILUPP_HIP(hipStreamSynchronize(p->side));
+            ILUPP_HIP(hipStreamSynchronize(p->side));
             return ILUPP_ERR_UNSUPPORTED;
         }
         if (grid && !(lm && p->flm.stat && p->flm.direct)) {
             // a grid the static direct-feed form does not take (or not the guessed grid: the lane templates of sampled rows disagree):
             // nothing built on the guess survives; the general pass decides
             if (getenv("ILUPP_DEBUG")) fprintf(stderr, "[ilupp] grid guess %d x %d x %d dropped (static analysis declined)\n", gd.nx, gd.ny, gd.nz);
-            if (grid_mode == 0) ILUPP_HIP(hipStreamSynchronize(p->side));
+            ILUPP_HIP(hipStreamSynchronize(p->side));
             p->pkL.release(); p->pkU.release(); p->flm.release();
             p->sA.release(); p->sU.release();
             p->sA = Schedule(); p->sU = Schedule();
@@ -574,23 +567,15 @@ int ilu0_factor(ilupp_precond *p, const DevMat &A, const int32_t *head)
         }
         if (!(p->pkL.valid && p->pkU.valid)) { p->pkL.release(); p->pkU.release(); }
     }
-    // (the factor kernel lives on short hand-over latencies: next to the proof's 4.6 TB/s stream it loses more than waiting for the proof
-    // costs -- with the lane tables in closed form the proof is what the analysis phase lasts)
     ILUPP_HIP(hipEventRecord(a1, st));
-    if (grid && grid_mode == 2) {
-        ILUPP_HIP(hipEventRecord(p->jev[0], st));
-        ILUPP_HIP(hipStreamWaitEvent(p->side, p->jev[0], 0));
-        grid_check_launch(p->side, A, gd, p->ctrl + 8);
-        ILUPP_HIP(hipEventRecord(p->jev[1], p->side));
-    }
     float kms = 0.f;
     // (the factor kernel's own read-back waits for the proof and takes its verdict along: no round trip of its own)
     const bool wx_numeric = p->flm.built && p->flm.stat && p->flm.direct && p->flm.wxf;
-    // (mode 0: the factor kernel waits for the proof -- it lives on short hand-over latencies and loses more next to the proof's 4.6 TB/s
-    // stream than the wait costs --, but what is queued in front of it, the clearing of its control words and exchange, does not)
-    p->pkL.join_ev = (grid && grid_mode != 1 && wx_numeric) ? p->jev[1] : nullptr;
-    p->pkL.join_before = grid && grid_mode == 0 && wx_numeric;
-    if (grid && grid_mode == 0 && !wx_numeric) ILUPP_HIP(hipStreamWaitEvent(st, p->jev[1], 0));
+    // (the factor kernel waits for the proof -- it lives on short hand-over latencies and loses more next to the proof's 4.6 TB/s
+    // stream than the wait costs --, but what is queued in front of it, the clearing of its control words and exchange, does not;
+    // with the lane tables in closed form the proof is what the analysis phase lasts)
+    p->pkL.join_ev = (grid && wx_numeric) ? p->jev[1] : nullptr;
+    if (grid && !wx_numeric) ILUPP_HIP(hipStreamWaitEvent(st, p->jev[1], 0));
     p->pkL.join_verdict = -1;                       // (-1: nobody has read the verdict yet)
     // (... and queues the arming of the first apply behind that read-back; the speculation's leftovers -- pending read-backs of the lane
     // tables' flags -- lie in front of it too)
@@ -605,7 +590,7 @@ int ilu0_factor(ilupp_precond *p, const DevMat &A, const int32_t *head)
     if (grid && p->pkL.join_verdict >= 0) {
         grid_bad = p->pkL.join_verdict;
     } else if (grid) {
-        if (grid_mode != 1) ILUPP_HIP(hipStreamWaitEvent(st, p->jev[1], 0));
+        ILUPP_HIP(hipStreamWaitEvent(st, p->jev[1], 0));
         ILUPP_HIP(d2h_async(st, &grid_bad, p->ctrl + 8, sizeof(int32_t)));
     }
     if (!waited) ILUPP_HIP(stream_sync(st));
@@ -636,7 +621,7 @@ int ilu0_factor(ilupp_precond *p, const DevMat &A, const int32_t *head)
         return ilu0_factor(p, A, nullptr);
     }
     if (grid && rc == ILUPP_OK) grid_shape_remember(A.n, A.nnz, gd, A.idx);
-    if (grid && grid_mode == 0 && wx_numeric && rc == ILUPP_OK) {
+    if (grid && wx_numeric && rc == ILUPP_OK) {
         // (the proof ends in front of the factor kernel, behind the launches that clear its control words: the analysis phase lasts until
         // the event in front of that kernel, ev[4], not until a1)
         ILUPP_HIP(hipEventElapsedTime(&p->tm.analysis_ms, a0, p->ev[4]));

@@ -151,9 +151,8 @@ struct PackedSweep {
     // diagonal; the backward sweep accumulates in descending column order when `desc` (a row-stored lower factor used transposed)
     bool pair = false, desc = false;
     // (forward sweep of an ILU(0) whose row blocks were guessed, grid.hip) the proof's end on its side stream and its verdict word, ctrl[8]:
-    // the factor kernel's own read-back waits for the one and takes the other along
+    // the factor kernel waits for the one (behind the launches that prepare it) and its own read-back takes the other along
     hipEvent_t join_ev = nullptr;
-    bool join_before = false;           // wait for join_ev in front of the factor kernel (behind the launches that prepare it), not behind it
     int32_t join_verdict = 0;
     // (forward sweep of a static ILU(0)) what the factor kernel's launch is followed by, behind its read-back and in front of the wait for
     // it: the arming of the first apply (api.hip: arm_apply) -- `arm` runs with `arm_ctx`, the wait is for `arm_ev` instead of the stream
@@ -189,7 +188,7 @@ struct FactorLM {
     long long *xcount = nullptr;    // device: doubles of xch in use
     bool stat = false;              // static form (st.hip): pkA holds 4 KB chunks {a0..a6, mask}
     bool direct = false;            // static form fed from A's CSR values (st_direct.hip): no pkA at all
-    bool wxf = false;               // ... by the wave-exchange factor kernel (st_wave.hip: k_ilu0_wx), which writes format-1 records
+    bool wxf = false;               // ... by the wave-exchange factor kernel (st_wave.hip: k_ilu0_wa), which writes format-1 records
     // (box grids, grid.hip) the sizes the analysis used to wait for were PREDICTED from the dimensions and everything behind them launched
     // at once; what the device found (flags of both schedules, exchange totals) lands here with the construction's last read-back and
     // must equal the prediction, or the construction is redone the waiting way (api.hip: ilu0_factor)
@@ -312,7 +311,7 @@ int ilu0_symbolic_and_schedule(hipStream_t st, const DevMat &A, DevMat *L, DevMa
                                int max_lanes, Schedule *fwd, Schedule *bwd, int32_t *max_row_len);
 void ilu0_write_patterns(hipStream_t st, const DevMat &A, DevMat *L, DevMat *U);
 void finish_chains(Schedule *fwd, Schedule *bwd);
-const char *wx_factor_kernel_name();     // st_wave.hip: the factor kernel ilu0_numeric_wx launches, as a profiler names it
+const char *wx_factor_kernel_name();     // st_wave.hip: the factor kernel ilu0_numeric_wx launches (k_ilu0_wa<0, 4, 4>), as a profiler names it
 bool wx_vec_on();            // st_wave.hip: the sweeps move the caller's vector through their vector wave (no level-major copies, no k_st_vec)
 // grid.hip: the first analysis pass for lexicographic box-grid stencil matrices (guess from row 0, proof on a side stream)
 struct GridDims { int32_t nx, ny, nz; };

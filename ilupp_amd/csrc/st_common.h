@@ -324,7 +324,7 @@ __device__ __forceinline__ void st_number_pairs(const int32_t *T, const int t, c
 #endif
 
 #if defined(__HIPCC__)
-// may the wave-exchange factor kernel (st_wave.hip: k_ilu0_wx) run this forward lane?  On top of wx_lane_ok: the transposed entry of
+// may the wave-exchange factor kernel (st_wave.hip: k_ilu0_wa) run this forward lane?  On top of wx_lane_ok: the transposed entry of
 // every elimination exists and is an entry its owner hands on (a'B or a'C of the pivot row; the own chain's: a'A), and what comes
 // from the workgroup is at most kSdHist - 1 steps old.  (after sd_tab_lane: ST_Q is set)
 __device__ __forceinline__ bool wf_lane_ok(const int32_t *T, const int32_t *__restrict__ ltabB, const int32_t *__restrict__ uslot)

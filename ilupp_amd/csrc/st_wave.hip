@@ -40,12 +40,10 @@ static constexpr int kWxLds = 2 * kStH * kWxRow * 8;
 __device__ unsigned long long g_wx_stamp[16];
 // ... and per workgroup of the factor kernel (by ticket): entry, lane 0's first row, lane 0's last row, exit (100 MHz)
 __device__ unsigned long long g_wf_tl[4096 * 4];
-// ... and per workgroup and wave (16 slots): cycles spent waiting at the barriers of the main loop, [12..15]: loop cycles of wave 0, the
-// courier's spin cycles, the producers' cycles between barriers (wave 5), steps
+// ... and per workgroup (16 slots): [0..3] cycles consumer wave w waited for its counters, [4] the poller's repeated polls, [8] HW_ID and
+// XCC_ID of lane 0, [9..11] the prefetcher's blocks asked for, scans and summed lead, [12] consumer loop cycles of wave 0, [13] its
+// steps that waited, [14] the poller's values missing at the first look, [15] steps
 __device__ unsigned long long g_wf_wait[4096 * 16];
-#define WF_BARRIER(acc_) do { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); const unsigned long long b0_ = __builtin_amdgcn_s_memtime(); asm volatile("s_barrier" ::: "memory"); (acc_) += __builtin_amdgcn_s_memtime() - b0_; } while (0)
-#else
-#define WF_BARRIER(acc_) ST_BARRIER()
 #endif
 
 // ---------------------------------------------------------------------------------------------
@@ -256,9 +254,6 @@ __device__ __forceinline__ void wx_sweep_wave(const StSArgs &A, unsigned char *x
     typedef unsigned int v2u_ __attribute__((ext_vector_type(2)));
     v4u ra[kStRA][2];
     double rr[kStRA];
-#ifdef WX_X_NOMEM
-#define WXS_LOAD(u) do { } while (0)
-#else
 #define WXS_LOAD(u)                                                                                    \
     do {                                                                                               \
         ra[u][0] = __builtin_amdgcn_raw_buffer_load_b128(rrec, vrec, 0, 0);                            \
@@ -267,17 +262,10 @@ __device__ __forceinline__ void wx_sweep_wave(const StSArgs &A, unsigned char *x
         if (!(VEC && DR > 0)) rr[u] = __builtin_bit_cast(double, __builtin_amdgcn_raw_buffer_load_b64(rrhs, vrhs, 0, 0)); \
         vrec += dRec; vrhs += dRhs;                                                                    \
     } while (0)
-#endif
-#ifdef WX_X_NOMEM
-    for (int u = 0; u < kStRA; ++u) { ra[u][0] = __builtin_amdgcn_raw_buffer_load_b128(rrec, vrec, 0, 0); ra[u][1] = ra[u][0]; rr[u] = 1.0; }
-#endif
 #pragma unroll
     for (int u = 0; u < kStRA; ++u) { WXS_LOAD(u); asm volatile("" ::: "memory"); }
     // (the courier's values of the first two steps are in place)
     ST_BARRIER();
-#ifdef WX_PRIO
-    __builtin_amdgcn_s_setprio(WX_PRIO);
-#endif
     double xprev = 0.0;
     double bB = st_lds(xh, W.aB), bC = st_lds(xh, W.aC);               // the hand-off values of the first step
     int k = tlo - sk;
@@ -299,11 +287,7 @@ __device__ __forceinline__ void wx_sweep_wave(const StSArgs &A, unsigned char *x
             const v2dd c01 = __builtin_bit_cast(v2dd, ra[u][0]), c2d = __builtin_bit_cast(v2dd, ra[u][1]);
             // the exchange inside the wave
             const double sB = wx_dpp_shr1(bB, xprev);
-#ifdef WX_X_NOBPERM
-            const double pC = xprev + 1.0;
-#else
             const double pC = wx_from_lane(W.src16, xprev);
-#endif
             const double sC = W.ringC ? bC : pC;
             // (accumulation in ascending column order: C, B, A forward, A, B, C backward; DESC: a backward sweep in descending order)
             const double xs0 = (DR > 0 || DESC) ? sC : xprev, xs2 = (DR > 0 || DESC) ? xprev : sC;
@@ -316,24 +300,16 @@ __device__ __forceinline__ void wx_sweep_wave(const StSArgs &A, unsigned char *x
             // 16-byte load is a free register to the allocator, and what it puts there has to wait for that load, a load of a later step)
             if (!DIV && !CL) asm volatile("" :: "v"(c2d.y));
             x = (valid && x == x) ? x : alt;
-#ifndef WX_X_NOLDSW
             *reinterpret_cast<double *>(xh + (unsigned)t * 8 + (unsigned)(u % kStH) * (kWxRow * 8)) = x;
             *reinterpret_cast<double *>(xh + (unsigned)t * 8 + (unsigned)(u % kStH + kStH) * (kWxRow * 8)) = x;
-#endif
             xprev = x;
-#ifndef WX_X_NOMEM
             if (VEC && DR < 0) *reinterpret_cast<double *>(vr + vbase + (((unsigned)k & 31u) << 3)) = x;      // (the vector wave takes it from there)
             else __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(v2u_, x), rout, vout, 0, 2);
-#endif
             vout += 512u;
             WXS_LOAD(u);
             bB = nB; bC = nC; bR = nR;
             ++k;
-#ifdef WX_X_NOBAR
-            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-#else
             ST_BARRIER();
-#endif
         }
     }
 #undef WXS_LOAD
@@ -357,13 +333,6 @@ __device__ __forceinline__ void wx_courier(const unsigned long long *src, const 
 {
     constexpr int SH = 2;
     const int ln = threadIdx.x & 63;
-#if defined(WX_X_NOCOURIER) || defined(WX_X_NOBAR)
-#ifndef WX_X_NOBAR
-    ST_BARRIER();
-    for (int tb = tlo; tb < thi; ++tb) ST_BARRIER();
-#endif
-    return;
-#endif
     const unsigned span = (unsigned)(P.khi - P.klo);
     unsigned long long gq[NP];
     // exports: lane e stores the unknown of the exported lane with ordinal e -- ONE store instruction per step, issued by every lane
@@ -722,629 +691,20 @@ int sptrsv_wx(hipStream_t st, const PackedSweep &ps, int32_t n, const double *rh
 }
 
 // =============================================================================================
-// ILU(0), wave-exchange form: the direct-feed factor kernel (st_direct.hip: producer waves stream A's values into LDS, consumer
-// waves run the pivot recurrence u_rr = a_rr - sum_k (a_rk / u_kk) a_kr, ILU0.hpp:47-62 for rows whose eliminations meet them on
-// the diagonal only) rebuilt around a lean consumer:
-//   * the PRODUCERS put every entry of a row where its class says (a canonical record of eight doubles per lane and step --
-//     {aC, aB} {aA, d} {a'A, a'B} {a'C, -}: the entries left of the diagonal by forward class, the diagonal, the entries right of it
-//     by backward class; a place no entry goes to stays +0.0): each producer thread's two 8-byte stores of a block simply go to
-//     thread-constant places.  The consumer reads its row with four 16-byte LDS loads at a lane-constant address: nothing about a
-//     row is looked up or selected, only the own-chain entries of a chain's first and last row are masked;
+// ILU(0), wave-exchange form: k_ilu0_wa -- the pivot recurrence u_rr = a_rr - sum_k (a_rk / u_kk) a_kr (ILU0.hpp:47-62 for rows whose
+// eliminations meet them on the diagonal only) on the sweeps' schedule, fed by LDS-DMA, no barrier in its loop, other workgroups
+// reading ahead for it:
+//   * a consumer lane reads its row in canonical order -- {aC, aB} {aA, d} {a'A, a'B} {a'C}: the entries left of the diagonal by
+//     forward class, the diagonal, the entries right of it by backward class; a place no entry goes to reads +0.0 --: nothing about
+//     a row is looked up or selected, only the own-chain entries of a chain's first and last row are masked;
 //   * pivots travel as the sweeps' unknowns do (DPP / ds_bpermute inside the wave, the hand-off array two steps old otherwise, a
 //     cell of ONES for a class without an entry: 0 / 1 = +0.0); the transposed entries a(k, r) -- entries right of the diagonal of
-//     the pivot row -- are re-published by the lane that owns the pivot row when it pre-reads that row, one step before its pivot;
-//   * records leave in format 1 as they are computed: {lC, lB} {lA, 1} and {a'A, a'B} {a'C, u_rr}; no "absent" selects, stores
-//     through buffer resources (a step outside the wave's chunks is dropped);
-//   * the courier imports pivots (polled) and transposed entries (from A) of earlier workgroups two barriers early and exports.
+//     the pivot row -- are handed on by the lane that owns the pivot row when it pre-reads that row, one step before its pivot;
+//   * records leave in format 1 as they are computed: {lC, lB} {lA, 1} and {a'A, a'B} {a'C, u_rr} (flags bit 3: L's {lA} alone,
+//     format 2); stores through buffer resources (a step outside the wave's chunks is dropped).
 // Arithmetic and its order are st_direct.hip's (bit-identical results; ILUPP_NO_WR=1 runs the old kernels).
-// =============================================================================================
-static constexpr int kWfH = 4;                            // steps of hand-off history (kept twice: slot s and s + 4)
-#ifdef WF_HALF
-// experiment: a workgroup runs the first 128 lanes of its slots only (schedules made with ILUPP_TILE_TZ=8: patches of 16 x 8 lines), with
-// half the LDS, so that two workgroups share a CU
-static constexpr int kWfLanes = 128, kWfPairs = 32;
-#else
-static constexpr int kWfLanes = kThreads, kWfPairs = 64;
-#endif
-#ifndef WF_PSLEEP
-#define WF_PSLEEP 4
-#endif
-static constexpr int kWfProdNap = WF_PSLEEP;              // s_sleep units (64 cycles) a producer waits behind each barrier before it issues loads
-static constexpr int kWfRow = kWfLanes + kWfPairs + 16;   // doubles per slot: lanes, courier pairs, [320] a cell of ones / zeros (+ padding: 4 rows = 21 x 512 B)
-static constexpr int kWfCell = kWfLanes + kWfPairs;
-static constexpr int kWfArr = 2 * kWfH * kWfRow * 8;      // bytes of one hand-off array
-static constexpr int kWfPitch = 80;                       // bytes of a lane's record in the row ring: 8 doubles + 16 (a wave's 16-byte loads and the producers' 8-byte stores then spread over the banks)
-static constexpr int kWfSlot = kWfLanes * kWfPitch;       // bytes of a step of the row ring
-static constexpr int kWfRing = 4 * kWfSlot;               // two blocks of two steps
-static constexpr unsigned kWfX = kWfRing;                 // pivots
-static constexpr unsigned kWfTB = kWfRing + kWfArr;       // a'B of every row (and the courier's transposed entries)
-static constexpr unsigned kWfTC = kWfRing + 2 * kWfArr;   // a'C
-static constexpr int kWfLds = kWfRing + 3 * kWfArr + 64;
-#ifdef WF_HALF
-static constexpr int kWfProd = 3, kWfPer = 6, kWfRA = 4;
-#else
-#ifndef WF_RA
-#define WF_RA 4
-#endif
-static constexpr int kWfProd = 6, kWfPer = 6, kWfRA = WF_RA;  // producer waves, groups of 8 lanes per wave, blocks read ahead (1, 2 or 4)
-static_assert(WF_RA == 1 || WF_RA == 2 || WF_RA == 4, "the producers' ring of registers is walked with (bb + 2) % kWfRA inside trips of four blocks");
-#endif
-static constexpr int kWfThreads = kWfLanes + 64 + 64 * kWfProd;
-static_assert(kWfProd * kWfPer * 8 >= kWfLanes, "every lane needs a producer");
-static_assert((kWfH * kWfRow * 8) % 512 == 0, "the two copies of a hand-off value are stored with one ds_write2st64_b64");
-
-struct WfArgs {
-    const int32_t *ltab, *ltabB, *uslot, *wtab;   // forward lane table, backward lane table, forward -> backward slot, chunk table
-    const double *val;                            // A's values, the pointer rounded down to 16 bytes
-    uint32_t val_bytes;
-    int32_t val_shift;
-    unsigned char *pkL, *pkU;                     // format-1 records, both in the forward schedule's order
-    const int32_t *xe, *xw;
-    double *xch;
-    int64_t xch_len;                              // doubles of the exchange: a workgroup's export window never reaches past it
-    int32_t *ctrl;                                // [0] ticket, [1] error; k_ilu0_wa: [2], [3], [9] .. [14] tickets by XCD
-    int32_t flags;                                // k_ilu0_wa: 2 = every workgroup of the launch is resident at once; 1 = ... and tiles are handed out by XCD
-    int32_t *prog;                                // k_ilu0_wa: [tile] steps done, [nwg + tile] blocks of eight steps somebody has asked for, [2 nwg + tile] blocks somebody finishes (or null)
-};
-struct WfPair { int idx0, stride, sk, cnt; unsigned at0; int atm, klast, sh, hasT; int astart, pw; };    // (st_direct.hip: SdPair; k_ilu0_wa: astart, where the producer's workgroup exports its first step; pw, that workgroup)
-
-// what a consumer lane knows
-struct WfLane {
-    unsigned xB, xC;              // pivot hand-off: stand-in of class B / C (the cell of ones without an entry)
-    unsigned tB, tC;              // transposed entries of the class B / C elimination (the cell of zeros without one)
-    bool ringC;
-    int src16;
-    bool hasB, hasC, hasUB, hasUC;   // the lane's rows have an entry of class B / C left of the diagonal; of (backward) class B / C right of it
-};
-
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t wf_rsrc(const WfArgs &A)
-{
-    return __builtin_amdgcn_make_buffer_rsrc(const_cast<double *>(A.val), 0, (int)A.val_bytes, 0x00020000);
-}
-
-// ---------------------------------------------------------------------------------------------
-// the 256 lanes of the schedule
-// ---------------------------------------------------------------------------------------------
-__device__ __forceinline__ void wf_consumer(const WfArgs &A, unsigned char *lds, const int wg, const WfLane W, const int tlo, const int thi)
-{
-    typedef double v2dd __attribute__((ext_vector_type(2)));
-    const int t = threadIdx.x, wv = t >> 6, ln = t & 63;
-    const int slot = wg * kThreads + t;
-    const int32_t *T = A.ltab + (size_t)slot * kStTab;
-    const int cnt = T[ST_CNT], sk = T[ST_SKEW];
-    const int32_t *wt = A.wtab + (size_t)(wg * 4 + wv) * 4;
-    const int base = __builtin_amdgcn_readfirstlane(wt[0]), tminw = __builtin_amdgcn_readfirstlane(wt[1]),
-              nchw = __builtin_amdgcn_readfirstlane(wt[2]);
-    const __amdgpu_buffer_rsrc_t rL = __builtin_amdgcn_make_buffer_rsrc(A.pkL + (size_t)base * 2048, 0, nchw * 2048, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rU = __builtin_amdgcn_make_buffer_rsrc(A.pkU + (size_t)base * 2048, 0, nchw * 2048, 0x00020000);
-    unsigned vout = (unsigned)(tlo - tminw) * 2048u + (unsigned)ln * 16u;          // (a step outside the wave's chunks: out of range)
-    const unsigned rowa = (unsigned)t * kWfPitch;                                  // this lane's record in a step of the row ring
-    const unsigned xown = kWfX + (unsigned)t * 8u, tbown = kWfTB + (unsigned)t * 8u, tcown = kWfTC + (unsigned)t * 8u;
-
-    // the row of a step is read during the step BEFORE (and its entries right of the diagonal handed on at once)
-#define WF_ROW(s4_, r0_, r1_, r2_, r3_)                                                                           \
-    do {                                                                                                           \
-        r0_ = *reinterpret_cast<const v2dd *>(lds + rowa + (unsigned)(s4_) * kWfSlot);                             \
-        r1_ = *reinterpret_cast<const v2dd *>(lds + rowa + (unsigned)(s4_) * kWfSlot + 16u);                       \
-        r2_ = *reinterpret_cast<const v2dd *>(lds + rowa + (unsigned)(s4_) * kWfSlot + 32u);                       \
-        r3_ = *reinterpret_cast<const v2dd *>(lds + rowa + (unsigned)(s4_) * kWfSlot + 48u);                       \
-    } while (0)
-#define WF_HAND_T(h4_, r2_, r3_)                                                                                   \
-    do {                                                                                                           \
-        *reinterpret_cast<double *>(lds + tbown + (unsigned)(h4_) * (kWfRow * 8)) = (r2_).y;                       \
-        *reinterpret_cast<double *>(lds + tbown + (unsigned)((h4_) + kWfH) * (kWfRow * 8)) = (r2_).y;              \
-        *reinterpret_cast<double *>(lds + tcown + (unsigned)(h4_) * (kWfRow * 8)) = (r3_).x;                       \
-        *reinterpret_cast<double *>(lds + tcown + (unsigned)((h4_) + kWfH) * (kWfRow * 8)) = (r3_).x;              \
-    } while (0)
-
-    // The producers place a row's entries by their distance from the row's (virtual) start.  A chain's first row has no own-chain
-    // entry left of its diagonal and its last row none right of it: there the neighbours' entries sit one place nearer to the diagonal
-    // (and the place at the far end holds an entry of another row).  Put right once per row, when the row is handed on; only the two
-    // rows at the ends of a chain need it, so the selects sit behind a branch the whole wave takes or skips.
-    const int fl = T[ST_DFL];
-    const int kF = ((fl >> 2) & 1) ? 0 : -1, kL = ((fl >> 3) & 1) ? cnt - 1 : -1;
-    // first row: the entry of template position j lies at the place of position j + 1; last row: of position q at the place of q - 1
-    const bool fCB = W.hasC && W.hasB, fCA = W.hasC && !W.hasB, fBA = W.hasB;
-    const bool lCB = W.hasUC && W.hasUB, lCA = W.hasUC && !W.hasUB, lBA = W.hasUB;
-#define WF_ENDS(kk_, r0_, r1_, r2_, r3_)                                                                          \
-    do {                                                                                                           \
-        const bool f_ = (kk_) == kF, l_ = (kk_) == kL;                                                             \
-        if (__builtin_amdgcn_ballot_w64(f_ || l_) != 0) {                                                          \
-            const double c_ = (r0_).x, b_ = (r0_).y, a_ = (r1_).x, ua_ = (r2_).x, ub_ = (r2_).y, uc_ = (r3_).x;    \
-            (r0_).x = f_ ? (fCB ? b_ : (fCA ? a_ : c_)) : c_;                                                      \
-            (r0_).y = f_ ? (fBA ? a_ : b_) : b_;                                                                   \
-            (r1_).x = f_ ? 0.0 : a_;                                                                               \
-            (r2_).x = l_ ? 0.0 : ua_;                                                                              \
-            (r2_).y = l_ ? (lBA ? ua_ : ub_) : ub_;                                                                \
-            (r3_).x = l_ ? (lCB ? ub_ : (lCA ? ua_ : uc_)) : uc_;                                                  \
-        }                                                                                                          \
-    } while (0)
-    ST_BARRIER();                                           // (the producers' first two blocks and the courier's first entries are in place)
-#ifdef WF_PRIO
-    __builtin_amdgcn_s_setprio(WF_PRIO);                    // (experiment: the waves on the chain before the couriers and producers that share their SIMDs)
-#endif
-    v2dd c0_, c1_, c2_, c3_;                                // the row of the current step: {aC, aB} {aA, d} {a'A, a'B} {a'C, -}
-    v2dd n0_, n1_, n2_, n3_;                                // ... of the next step
-    WF_ROW(0, c0_, c1_, c2_, c3_);
-    WF_ROW(1, n0_, n1_, n2_, n3_);
-    WF_ENDS(tlo - sk, c0_, c1_, c2_, c3_);
-    WF_HAND_T(0, c2_, c3_);
-    double bB = st_lds(lds, W.xB), bC = st_lds(lds, W.xC);  // pivots of other waves / workgroups for the first step
-    ST_BARRIER();                                           // (everybody's transposed entries of the first step are handed on)
-    double tB = st_lds(lds, W.tB), tC = st_lds(lds, W.tC);
-    double w3prev = 1.0, upA = 0.0;                         // the pivot of the lane's previous row; that row's own-chain entry right of the diagonal
-    double qC = 1.0;                                        // the pivot of lane - 16 (asked for at the end of the step before)
-    int k = tlo - sk;
-    unsigned long long wacc_ = 0;
-#ifdef WX_STAMP
-    const unsigned long long wt0_ = __builtin_amdgcn_s_memtime();
-#endif
-    (void)wacc_;
-    for (int tb = tlo; tb < thi; tb += 8) {
-#pragma unroll
-        for (int u = 0; u < 8; ++u) {
-            // the pivots: inside the wave from registers
-            const double pC = W.ringC ? bC : qC;
-            const double pB = wx_dpp_shr1(bB, w3prev);
-            // for the steps to come (nothing of it is used before the next barrier): the row of the step after the next, the pivots and
-            // the transposed entries of the next step that do not come through the wave's registers
-            v2dd m0_, m1_, m2_, m3_;
-            WF_ROW((u + 2) & 3, m0_, m1_, m2_, m3_);
-            const double nB = st_lds(lds, W.xB + (unsigned)((u + 1) & 3) * (kWfRow * 8));
-            const double nC = st_lds(lds, W.xC + (unsigned)((u + 1) & 3) * (kWfRow * 8));
-            const double ntB = st_lds(lds, W.tB + (unsigned)((u + 1) & 3) * (kWfRow * 8));
-            const double ntC = st_lds(lds, W.tC + (unsigned)((u + 1) & 3) * (kWfRow * 8));
-            const bool valid = (unsigned)k < (unsigned)cnt;
-#ifdef WX_STAMP
-            if (t == 0 && wg < 4096 && k == 0) g_wf_tl[wg * 4 + 1] = __builtin_amdgcn_s_memrealtime();
-            if (t == 0 && wg < 4096 && k == cnt - 1) g_wf_tl[wg * 4 + 2] = __builtin_amdgcn_s_memrealtime();
-#endif
-            // (the lane's previous step had no row: what it left in upA is not an entry of the matrix)
-            const double aA = c1_.x, tA = k == 0 ? 0.0 : upA;
-            const double uA = c2_.x;
-            // u_rr = a_rr - sum (a_rk / u_kk) a_kr, eliminations in ascending k: classes C, B, A
-#ifdef WF_X_NODIV
-            const double lC = c0_.x * pC, lB = c0_.y * pB, lA = aA * w3prev;
-#else
-            const double lC = c0_.x / pC, lB = c0_.y / pB, lA = aA / w3prev;
-#endif
-            double w = c1_.y;
-            w = w - lC * tC;
-            w = w - lB * tB;
-            w = w - lA * tA;
-            {
-                // (a pivot must not look like the marker of the exchange; a lane without a row hands on 1)
-                const unsigned long long wb = st_bits(w);
-                if ((wb & ~3ull) == (kSentinel & ~3ull)) w = st_dbl(kCanonNaN);
-            }
-            const double w3 = valid ? w : 1.0;
-            *reinterpret_cast<double *>(lds + xown + (unsigned)(u & 3) * (kWfRow * 8)) = w3;
-            *reinterpret_cast<double *>(lds + xown + (unsigned)((u & 3) + kWfH) * (kWfRow * 8)) = w3;
-            qC = wx_from_lane(W.src16, w3);
-            w3prev = w3; upA = c2_.x;
-            {
-                typedef unsigned int v4u_ __attribute__((ext_vector_type(4)));
-                v2dd la, lb, ua, ub;
-                la.x = lC; la.y = lB; lb.x = lA; lb.y = 1.0;
-                ua.x = uA; ua.y = c2_.y; ub.x = c3_.x; ub.y = w3;
-#ifdef WF_X_NOSTORE
-                if (w3 == 1.2345e-300) {
-#endif
-                __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(v4u_, la), rL, vout, 0, 2);
-                __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(v4u_, lb), rL, vout + 1024u, 0, 2);
-                __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(v4u_, ua), rU, vout, 0, 2);
-                __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(v4u_, ub), rU, vout + 1024u, 0, 2);
-#ifdef WF_X_NOSTORE
-                }
-#endif
-                vout += 2048u;
-            }
-            // the next row (read a step ago): its ends put right, its entries right of the diagonal handed on -- a step before its pivot
-            WF_ENDS(k + 1, n0_, n1_, n2_, n3_);
-            WF_HAND_T((u + 1) & 3, n2_, n3_);
-            c0_ = n0_; c1_ = n1_; c2_ = n2_; c3_ = n3_;
-            n0_ = m0_; n1_ = m1_; n2_ = m2_; n3_ = m3_;
-            bB = nB; bC = nC; tB = ntB; tC = ntC;
-            ++k;
-            WF_BARRIER(wacc_);
-        }
-    }
-#ifdef WX_STAMP
-    if (ln == 0 && wg < 4096) { g_wf_wait[wg * 16 + wv] = wacc_; if (wv == 0) { g_wf_wait[wg * 16 + 12] = __builtin_amdgcn_s_memtime() - wt0_; g_wf_wait[wg * 16 + 15] = (unsigned long long)(thi - tlo); } }
-#endif
-#undef WF_ROW
-#undef WF_HAND_T
-#undef WF_ENDS
-}
-
-// ---------------------------------------------------------------------------------------------
-// the courier: lane p serves pair p.  Inbound, before the barrier that ends step s - 2: the pivot of step s from the exchange (polled
-// kStPF steps ahead) and the transposed entry of step s from A.  Outbound, behind the barrier that ends step s: the pivots of the
-// exported lanes.
-// ---------------------------------------------------------------------------------------------
-__device__ __forceinline__ void wf_courier(const WfArgs &A, const unsigned long long *idle, unsigned char *lds, const WfPair P,
-                                           const int tlo, const int thi, const int wg, const int *s_exp)
-{
-    // (the pivots are polled NP steps ahead -- a tile settles that many steps further behind the one it reads from --, the transposed
-    // entries, which are A's and wait for nobody, NA steps ahead)
-    constexpr int NP = kStPF, NA = 8, SH = 2;
-    typedef unsigned int v2u_ __attribute__((ext_vector_type(2)));
-    const int ln = threadIdx.x & 63;
-#ifdef WF_X_NOCOURIER
-    ST_BARRIER(); ST_BARRIER();
-    for (int tb = tlo; tb < thi; ++tb) ST_BARRIER();
-    return;
-#endif
-    const __amdgpu_buffer_rsrc_t rs = wf_rsrc(A);
-    const unsigned long long *src = reinterpret_cast<const unsigned long long *>(A.xch);
-    const unsigned span = (unsigned)P.cnt;
-    // (a courier lane beyond the pair slots delivers to a place of the padding nobody reads)
-    const unsigned hoX = kWfX + (unsigned)((kWfH * kWfRow + (ln < kWfPairs ? kWfLanes + ln : kWfCell + 8)) * 8);
-    const unsigned hoT = kWfTB + (unsigned)((kWfH * kWfRow + (ln < kWfPairs ? kWfLanes + ln : kWfCell + 8)) * 8);
-    // exports (wx_courier)
-    const int E = __builtin_amdgcn_readfirstlane(A.xw[wg * 4]);
-    const int xrow0 = A.xw[wg * 4 + 3] + (tlo - A.xw[wg * 4 + 1]) * E;
-    const int elane = (ln < E) ? s_exp[ln] : -1;
-    const unsigned ea = kWfX + (unsigned)((kWfH * kWfRow + (elane >= 0 ? elane : kWfCell)) * 8);
-    // (the window is clamped to the allocation: sizes predicted from a box grid's dimensions are only compared with what the device
-    // found after this kernel has run)
-    const long long xroom = (long long)A.xch_len - (long long)xrow0;
-    const long long xwant = (long long)(thi - tlo) * (long long)E;
-    const __amdgpu_buffer_rsrc_t rx = __builtin_amdgcn_make_buffer_rsrc(A.xch + (xroom > 0 ? xrow0 : 0), 0, (int)(8 * (xroom > 0 ? (xwant < xroom ? xwant : xroom) : 0)), 0x00020000);
-    unsigned vx = elane >= 0 ? (unsigned)ln * 8u : 0xfffffff0u;
-    const unsigned dvx = elane >= 0 ? (unsigned)E * 8u : 0u;
-    if (E > 64 && ln == 0) atomicExch(&A.ctrl[1], 1);                 // (the analysis does not let such a schedule through)
-    unsigned long long gq[NP];
-    double ga[NA];
-#define WFC_ADDR(k_) ((unsigned)(k_) < span ? src + (P.idx0 + ((k_) + P.sk) * P.stride) : idle)
-#define WFC_AT(k_) (((unsigned)(k_) < span && P.hasT) ? P.at0 + (unsigned)((k_) * P.atm) - ((k_) == P.klast ? (unsigned)P.sh : 0u) : 0xfffffff0u)
-#define WFC_LDAT(k_) __builtin_bit_cast(double, __builtin_amdgcn_raw_buffer_load_b64(rs, WFC_AT(k_), 0, 0))
-#pragma unroll
-    for (int g = 0; g < NA; ++g) {
-        if (g < NP) gq[g] = ld_agent_u64(WFC_ADDR(tlo + g - P.sk));
-        ga[g] = WFC_LDAT(tlo + g - P.sk);
-        __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(v2u_, 0.0), rx, 0xfffffff0u, 0, 16);      // (the way in looks like a pass of the loop)
-        asm volatile("" ::: "memory");
-    }
-    bool dead = false;
-#define WFC_DELIVER(i_)                                                                                              \
-    do {                                                                                                             \
-        const int k = tlo_ + (i_) - P.sk;                                                                            \
-        const bool need = (unsigned)k < span;                                                                        \
-        unsigned long long v = gq[(i_) % NP];                                                                        \
-        if (!dead) {                                                                                                 \
-            unsigned spins = 0;                                                                                      \
-            while (__builtin_amdgcn_ballot_w64(need && v == kSentinel) != 0) {                                       \
-                if (need && v == kSentinel) v = ld_agent_u64(WFC_ADDR(k));                                           \
-                __builtin_amdgcn_s_waitcnt(0x0F70);                                                                  \
-                __builtin_amdgcn_s_sleep(1);                                                                         \
-                if ((++spins & 255u) == 0) {                                                                         \
-                    if (spins > kStSpinLimit) atomicExch(&A.ctrl[1], 1);                                             \
-                    const int e = ld_agent_i32(&A.ctrl[1]);                                                          \
-                    __builtin_amdgcn_s_waitcnt(0x0F70);                                                              \
-                    if (spins > kStSpinLimit || e != 0) { dead = true; break; }                                      \
-                }                                                                                                    \
-            }                                                                                                        \
-        }                                                                                                            \
-        *reinterpret_cast<unsigned long long *>(lds + hoX + (unsigned)((i_) & 3) * (kWfRow * 8)) = v;                \
-        *reinterpret_cast<double *>(lds + hoT + (unsigned)((i_) & 3) * (kWfRow * 8)) = ga[(i_) % NA];                \
-        gq[(i_) % NP] = ld_agent_u64(WFC_ADDR(k + NP));                                                              \
-        ga[(i_) % NA] = WFC_LDAT(k + NA);                                                                            \
-    } while (0)
-    {
-        const int tlo_ = tlo;
-#pragma unroll
-        for (int i = 0; i < SH; ++i) WFC_DELIVER(i);
-    }
-    ST_BARRIER();
-    ST_BARRIER();
-    unsigned long long wacc_ = 0, sacc_ = 0;
-    (void)wacc_; (void)sacc_;
-    for (int tb = tlo; tb < thi; tb += 8) {
-        const int tlo_ = tb;
-#pragma unroll
-        for (int u = 0; u < 8; ++u) {
-#ifdef WX_STAMP
-            const unsigned long long d0_ = __builtin_amdgcn_s_memtime();
-#endif
-            WFC_DELIVER(u + SH);
-#ifdef WX_STAMP
-            sacc_ += __builtin_amdgcn_s_memtime() - d0_;
-#endif
-            WF_BARRIER(wacc_);
-            {
-                const double v = st_lds(lds, ea + (unsigned)(u & 3) * (kWfRow * 8));
-                __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(v2u_, v), rx, vx, 0, 16);          // sc1: write-through
-                vx += dvx;
-            }
-        }
-    }
-#undef WFC_DELIVER
-#undef WFC_ADDR
-#undef WFC_AT
-#undef WFC_LDAT
-#ifdef WX_STAMP
-    if (ln == 0 && wg < 4096) { g_wf_wait[wg * 16 + 4] = wacc_; g_wf_wait[wg * 16 + 13] = sacc_; }
-#endif
-    if (dead && ln == 0) atomicExch(&A.ctrl[1], 1);
-}
-
-// ---------------------------------------------------------------------------------------------
-// a producer wave: 8 threads per lane, 16 bytes of A.val each per block of two steps (st_direct.hip: sd_producer); every thread's two
-// entries of a block go to the places of the canonical records they belong to
-// ---------------------------------------------------------------------------------------------
-__device__ __forceinline__ void wf_producer(const WfArgs &A, unsigned char *lds, const int wg, const int pw, const int tlo, const int thi,
-                                            const int4 *s_lane, const unsigned char *s_place)
-{
-    const int ln = threadIdx.x & 63, sub = ln & 7, lg = ln >> 3;
-#ifdef WF_X_NOPROD
-    ST_BARRIER(); ST_BARRIER();
-    for (int tb = tlo; tb < thi; ++tb) ST_BARRIER();
-    return;
-#endif
-    const __amdgpu_buffer_rsrc_t rs = wf_rsrc(A);
-    unsigned g[kWfPer], S[kWfPer], d0[kWfPer], d1[kWfPer];
-    const int b0 = tlo >> 1;
-#pragma unroll
-    for (int i = 0; i < kWfPer; ++i) {
-        const int l = (pw * kWfPer + i) * 8 + lg;
-        const bool live = l < kWfLanes;
-        // (the lane's fields and the canonical places of its row's positions: put into LDS by the lane itself, k_ilu0_wx)
-        const int4 lp = s_lane[live ? l : 0];                      // cnt, skew, first entry, flags (ST_DFL)
-        const int cnt = lp.x, sk = lp.y, p0 = lp.z, fl = lp.w;
-        const int ownL = (fl >> 2) & 1, m = fl >> 4;
-        const unsigned Cu = 8u * (unsigned)(p0 - ownL - sk * m) + (unsigned)A.val_shift;
-        const bool on = live && cnt > 0 && (sub < 7 || (Cu & 15u) + 16u * (unsigned)m > 112u);
-        S[i] = on ? 16u * (unsigned)m : 0u;
-        g[i] = on ? (Cu & ~15u) + (unsigned)b0 * S[i] + 16u * (unsigned)sub : 0xfffffff0u;
-        // where the thread's two entries of a block belong
-        unsigned dd[2];
-#pragma unroll
-        for (int e = 0; e < 2; ++e) {
-            const int idx = 2 * sub + e - (int)((Cu & 15u) >> 3);          // entry of the block's two (virtual) rows
-            int place = -1, ui = 0;
-            if (on && idx >= 0 && idx < 2 * m) {
-                ui = idx >= m ? 1 : 0;
-                const int pos = idx - ui * m;
-                place = pos < 8 ? (int)s_place[(live ? l : 0) * 8 + pos] - 1 : -1;
-            }
-            // (a piece of no row goes to place 7 of the lane's record, which nobody reads)
-            if (place < 0) { place = 7; ui = 0; }
-            dd[e] = (unsigned)ui * kWfSlot + (unsigned)(live ? l : 0) * kWfPitch + (unsigned)place * 8u;
-        }
-        d0[i] = dd[0]; d1[i] = dd[1];
-    }
-    const unsigned lbase = (unsigned)reinterpret_cast<uintptr_t>(lds);
-    v4u ra[kWfRA][kWfPer];
-#define WFP_LOAD(rb)                                                                       \
-    do {                                                                                   \
-        _Pragma("unroll") for (int i = 0; i < kWfPer; ++i) {                               \
-            ra[rb][i] = __builtin_amdgcn_raw_buffer_load_b128(rs, g[i], 0, 0);             \
-            g[i] += S[i];                                                                  \
-        }                                                                                  \
-    } while (0)
-#define WFP_WRITE(rb, parity)                                                              \
-    do {                                                                                   \
-        _Pragma("unroll") for (int i = 0; i < kWfPer; ++i) {                               \
-            if ((pw * kWfPer + i) * 8 < kWfLanes) {                                        \
-                typedef unsigned long long u64_;                                           \
-                const v4u x_ = ra[rb][i];                                                  \
-                const u64_ lo_ = ((u64_)x_.y << 32) | x_.x, hi_ = ((u64_)x_.w << 32) | x_.z; \
-                asm volatile("ds_write_b64 %0, %1 offset:%2" :: "v"(lbase + d0[i]), "v"(lo_), "n"((parity) * 2 * kWfSlot) : "memory"); \
-                asm volatile("ds_write_b64 %0, %1 offset:%2" :: "v"(lbase + d1[i]), "v"(hi_), "n"((parity) * 2 * kWfSlot) : "memory"); \
-            }                                                                              \
-        }                                                                                  \
-    } while (0)
-    // the first kWfRA blocks; blocks b0 and b0 + 1 go to the ring at once (the lanes read the row of step s during step s - 2)
-#pragma unroll
-    for (int rb = 0; rb < kWfRA; ++rb) { WFP_LOAD(rb); asm volatile("" ::: "memory"); }
-    WFP_WRITE(0, 0);
-    WFP_LOAD(0);
-    WFP_WRITE(1, 1);
-    WFP_LOAD(1);
-    ST_BARRIER();                                           // (the lanes read their first two rows behind this one)
-    ST_BARRIER();
-    unsigned long long wacc_ = 0, pacc_ = 0;
-    (void)wacc_; (void)pacc_;
-    for (int tb = tlo; tb < thi; tb += 8) {
-#pragma unroll
-        for (int bb = 0; bb < 4; ++bb) {
-            // steps 2 bb and 2 bb + 1 of this trip: the lanes read the rows of steps 2 bb + 2 and 2 bb + 3 (block bb + 1); block bb + 2
-            // takes the place of block bb, whose rows were read two steps ago
-            WF_BARRIER(wacc_);
-#ifdef WX_STAMP
-            const unsigned long long p0_ = __builtin_amdgcn_s_memtime();
-#endif
-            WFP_WRITE((bb + 2) % kWfRA, bb & 1);
-            // (the producers, who have eight steps of slack, let the courier's export and poll of this step into the CU's memory queue first:
-            // measured -2 % on the kernel at 256^3 with 2..6, nothing with 8, +5 % with 16)
-            __builtin_amdgcn_s_sleep(kWfProdNap);
-            WFP_LOAD((bb + 2) % kWfRA);
-#ifdef WX_STAMP
-            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-            pacc_ += __builtin_amdgcn_s_memtime() - p0_;
-#endif
-            WF_BARRIER(wacc_);
-        }
-    }
-#ifdef WX_STAMP
-    if (ln == 0 && wg < 4096) { g_wf_wait[wg * 16 + 5 + pw] = wacc_; if (pw == 0) g_wf_wait[wg * 16 + 14] = pacc_; }
-#endif
-#undef WFP_LOAD
-#undef WFP_WRITE
-}
-
-__global__ void __launch_bounds__(kWfThreads)
-k_ilu0_wx(WfArgs A)
-{
-    extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
-    __shared__ WfPair s_pairs[64];
-    __shared__ int s_exp[kWfLanes];
-    __shared__ int4 s_lane[kWfLanes];                     // per lane: cnt, skew, first entry of A, ST_DFL -- for the producers
-    __shared__ unsigned char s_place[kWfLanes * 8];       // per lane and row position: canonical place + 1 (0: the lane has no such position)
-    __shared__ int s_cnt[4], s_total;
-    __shared__ unsigned s_ticket;
-    if (threadIdx.x == 0) s_ticket = (unsigned)atomicAdd(&A.ctrl[0], 1);
-    __syncthreads();
-    const int wg = (int)s_ticket;
-    const int t = threadIdx.x;
-    int tlo = 0x7fffffff, thi = -0x7fffffff;
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-        const int32_t *w4 = A.wtab + (size_t)(wg * 4 + q) * 4;
-        const int a = w4[1], b = w4[2];
-        if (b > 0) { tlo = min(tlo, a); thi = max(thi, a + b); }
-    }
-    tlo = __builtin_amdgcn_readfirstlane(tlo); thi = __builtin_amdgcn_readfirstlane(thi);
-    if (thi <= tlo) return;
-    tlo &= ~7;                                                        // step % 8 = position in the unrolled loops
-    // the row ring and the hand-off arrays start all +0.0 (what no producer piece goes to stays that way); the cells of ones
-    for (int i = t; i < kWfLds / 8; i += kWfThreads) reinterpret_cast<double *>(lds)[i] = 0.0;
-    if (t < 64) { WfPair z; z.idx0 = 0; z.stride = 0; z.sk = 0; z.cnt = 0; z.at0 = 0; z.atm = 0; z.klast = -1; z.sh = 0; z.hasT = 0; z.astart = -1; z.pw = -1; s_pairs[t] = z; }
-    if (t < kWfLanes) s_exp[t] = -1;
-    if (t < 4) s_cnt[t] = 0;
-    __syncthreads();
-    if (t < 2 * kWfH) *reinterpret_cast<double *>(lds + kWfX + (unsigned)((t * kWfRow + kWfCell) * 8)) = 1.0;
-    if (t < kWfLanes) {
-        const int slot = wg * kThreads + t;
-        const int32_t *T = A.ltab + (size_t)slot * kStTab;
-        const int nd = T[ST_ND], cnt = T[ST_CNT];
-        int cls[3]; bool ring[3];
-        bool ok = wx_lane_ok(T, t, false) && wf_lane_ok(T, A.ltabB, A.uslot);
-        (void)wr_classify(T, t, false, cls, ring);
-        WfLane W;
-        W.xB = W.xC = kWfX + (unsigned)((kWfH * kWfRow + kWfCell) * 8);
-        W.tB = W.tC = kWfTB + (unsigned)((kWfH * kWfRow + kWfCell) * 8);
-        W.ringC = true;
-        W.src16 = ((t - 16) & 63) * 4;
-        bool isg[3];
-        WfPair gp[3];
-        unsigned xg[3], tg[3];
-#pragma unroll
-        for (int j = 0; j < 3; ++j) {
-            const int sw = T[ST_SRC + j];
-            const int ty = (j < nd && cnt > 0) ? (sw & 3) : ST_NONE;
-            const int os = sw >> 2;
-            const int q = ty != ST_NONE ? T[ST_Q + j] : -1;
-            isg[j] = ty == ST_GHOST;
-            xg[j] = 0; tg[j] = 0;
-            WfPair d; d.idx0 = 0; d.stride = 0; d.sk = T[ST_SKEW]; d.cnt = cnt > 0 ? cnt : 0; d.at0 = 0; d.atm = 0; d.klast = -1; d.sh = 0; d.hasT = 0; d.astart = -1; d.pw = -1;
-            if (ty == ST_LOCAL || ty == ST_GHOST) {
-                // the transposed entry: which entry right of the diagonal of the pivot row, and where its owner hands it on
-                const int pu = A.uslot[os];
-                const int32_t *TPB = A.ltabB + (size_t)(pu < 0 ? 0 : pu) * kStTab;
-                int pc[3]; bool pr[3];
-                (void)wr_classify(TPB, pu & 255, true, pc, pr);
-                const int qs = (q >= 0 && pu >= 0) ? wr_slot_of(q == 0 ? pc[0] : (q == 1 ? pc[1] : pc[2]), true) : -1;
-                if (qs != 1 && qs != 2) ok = false;                  // (a'B or a'C of the pivot row: what the lanes hand on)
-                if (ty == ST_LOCAL) {
-                    const int lane = os & 255, dt = T[ST_DT + j];
-                    if (dt < 1 || dt > kWfH - 1) ok = false;
-                    xg[j] = kWfX + (unsigned)(((kWfH - dt) * kWfRow + lane) * 8);
-                    tg[j] = (qs == 2 ? kWfTC : kWfTB) + (unsigned)(((kWfH - dt) * kWfRow + lane) * 8);
-                } else {
-                    const int pw = os >> 8;
-                    const int32_t *TP = A.ltab + (size_t)os * kStTab;
-                    const int E = A.xw[pw * 4];
-                    const int kap = T[ST_KAP + j];
-                    d.stride = E;
-                    d.idx0 = A.xw[pw * 4 + 3] + (kap + TP[ST_SKEW] - T[ST_SKEW] - A.xw[pw * 4 + 1]) * E + A.xe[os];
-                    const int flp = TP[ST_DFL];
-                    const int mp = flp >> 4;
-                    d.hasT = q >= 0 ? 1 : 0;
-                    d.atm = 8 * mp;
-                    d.at0 = (unsigned)A.val_shift + 8u * (unsigned)(TP[ST_P0] - ((flp >> 2) & 1) + TP[ST_ND] + 1 + (q < 0 ? 0 : q) + kap * mp);
-                    d.klast = TP[ST_CNT] - 1 - kap;
-                    d.sh = 8 * ((flp >> 3) & 1);
-                }
-            } else if (ty == ST_OWN) {
-                if (q != 0) ok = false;                               // (the own chain: the pivot row's first entry right of its diagonal)
-            }
-            gp[j] = d;
-        }
-        // the pairs of the workgroup, numbered
-        {
-            const int wv = t >> 6;
-            unsigned long long bal[3];
-#pragma unroll
-            for (int j = 0; j < 3; ++j) bal[j] = __builtin_amdgcn_ballot_w64(isg[j]);
-            const int mine = __popcll(bal[0]) + __popcll(bal[1]) + __popcll(bal[2]);
-            if ((t & 63) == 0) s_cnt[wv] = mine;
-            __syncthreads();
-            int before = 0;
-            for (int q = 0; q < wv; ++q) before += s_cnt[q];
-            if (t == 0) s_total = s_cnt[0] + s_cnt[1] + s_cnt[2] + s_cnt[3];
-#pragma unroll
-            for (int j = 0; j < 3; ++j) {
-                if (isg[j]) {
-                    const int p = before + __builtin_amdgcn_mbcnt_hi((unsigned)(bal[j] >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)bal[j], 0));
-                    if (p < kWfPairs) s_pairs[p] = gp[j];
-                    xg[j] = kWfX + (unsigned)((kWfH * kWfRow + kWfLanes + min(p, kWfPairs - 1)) * 8);
-                    tg[j] = kWfTB + (unsigned)((kWfH * kWfRow + kWfLanes + min(p, kWfPairs - 1)) * 8);
-                }
-                before += __popcll(bal[j]);
-            }
-        }
-        W.hasB = W.hasC = W.hasUB = W.hasUC = false;
-#pragma unroll
-        for (int j = 0; j < 3; ++j) {
-            if (cls[j] == WR_B) { W.hasB = true; W.tB = tg[j]; if (ring[j]) W.xB = xg[j]; }
-            if (cls[j] == WR_C) { W.hasC = true; W.tC = tg[j]; if (ring[j]) W.xC = xg[j]; else W.ringC = false; }
-        }
-        {
-            const int su = cnt > 0 ? A.uslot[slot] : -1;
-            int bc[3] = {WR_NONE, WR_NONE, WR_NONE};
-            if (su >= 0) {
-                bool br[3];
-                (void)wr_classify(A.ltabB + (size_t)su * kStTab, su & 255, true, bc, br);
-#pragma unroll
-                for (int q = 0; q < 3; ++q) { if (bc[q] == WR_B) W.hasUB = true; if (bc[q] == WR_C) W.hasUC = true; }
-            } else if (cnt > 0) {
-                ok = false;
-            }
-            // for the producers: the lane's fields, and where each position of its rows goes in the canonical record
-            const int fld = T[ST_DFL], ndU = fld & 3;
-            s_lane[t] = make_int4(cnt, T[ST_SKEW], T[ST_P0], fld);
-#pragma unroll
-            for (int pos = 0; pos < 8; ++pos) {
-                int place = -1;
-                if (pos < nd) { const int c = pos == 0 ? cls[0] : (pos == 1 ? cls[1] : cls[2]); place = c == WR_NONE ? -1 : wr_slot_of(c, false); }
-                else if (pos == nd) place = 3;
-                else if (pos <= nd + ndU && pos - nd - 1 < 3) { const int q = pos - nd - 1; const int c = q == 0 ? bc[0] : (q == 1 ? bc[1] : bc[2]); place = c == WR_NONE ? -1 : 4 + wr_slot_of(c, true); }
-                s_place[t * 8 + pos] = (unsigned char)(place + 1);
-            }
-        }
-        {
-            const int xe = A.xe[slot];
-            if (cnt > 0 && xe >= 0 && xe < kWfLanes) s_exp[xe] = t;
-        }
-        __syncthreads();
-        if ((t == 0 && s_total > kWfPairs) || !ok) atomicExch(&A.ctrl[1], 1);  // (the analysis does not let such a schedule through)
-#ifdef WX_STAMP
-        if (t == 0 && wg < 4096) g_wf_tl[wg * 4] = __builtin_amdgcn_s_memrealtime();
-#endif
-        wf_consumer(A, lds, wg, W, tlo, thi);
-#ifdef WX_STAMP
-        if (t == 0 && wg < 4096) g_wf_tl[wg * 4 + 3] = __builtin_amdgcn_s_memrealtime();
-#endif
-    } else if (t < kWfLanes + 64) {
-        __syncthreads();
-        __syncthreads();
-        const WfPair P = s_pairs[t - kWfLanes];
-        const unsigned long long *idle = reinterpret_cast<const unsigned long long *>(A.ltab + (size_t)wg * kThreads * kStTab);
-        wf_courier(A, idle, lds, P, tlo, thi, wg, s_exp);
-    } else {
-        __syncthreads();
-        __syncthreads();
-        wf_producer(A, lds, wg, (t - kWfLanes - 64) >> 6, tlo, thi, s_lane, s_place);
-    }
-}
-
-
-// =============================================================================================
-// ILU(0), wave-exchange form, round 6: k_ilu0_wa -- fed by LDS-DMA, no barrier in its loop, other workgroups reading ahead for it.
 //
-// k_ilu0_wx (above) took 1.0 ms at 256^3 for three rounds.  What this round's stamps and experiments found about it:
+// What bounds it (stamps at 256^3):
 //   (1) a tile at work is bounded by what ONE CU can have in flight at HBM latency: 25-30 GB/s of loads + stores, whether 4 tiles
 //       work on an otherwise idle chip or 120 (4096 x 32 x 32: four tiles, 0.73 us per step; 8192 x 16 x 16, one tile whose data the
 //       Infinity Cache still holds from the run before: 0.44).  A tile moves 30 KB per step, so a step takes about 1.1 us, and the
@@ -1353,7 +713,7 @@ k_ilu0_wx(WfArgs A)
 //   (2) the same tile reads A at nearly twice that pace when A's values come from the Infinity Cache (256 x 96 x 96, A touched just
 //       before: 0.49 -> 0.31 ms) -- and at any time most CUs are idle: their tile has not begun or has ended;
 //   (3) s_barrier counts every wave of the workgroup: with helper waves that touch memory at the step's barrier, the waves on the
-//       chain stood there for whichever of them was late (0.2 of 0.6 us per step).
+//       chain stand there for whichever of them is late (0.2 of 0.6 us per step).
 // So:
 //   * four LOADER waves (one per consumer wave) issue buffer_load_dwordx4 ... lds: A's values go from HBM into LDS as they lie, a
 //     128-byte window per lane and block of two steps (eight threads x 16 bytes = one memory burst per lane; the window of block b
@@ -1362,8 +722,7 @@ k_ilu0_wx(WfArgs A)
 //   * a window's eight 16-byte pieces are ROTATED by the lane ((lane >> 1) & 7; the source address of a DMA thread is per thread, its
 //     LDS destination is not: thread order), so that the 16 lanes the LDS serves at a time read 16 different bank groups;
 //   * the consumers read their row's seven entries where the window holds them: seven ds_read_b64 at lane-constant addresses (by step
-//     parity; an entry the lane's rows do not have is read from a cell of zeros) straight into the canonical order {aC, aB} {aA, d}
-//     {a'A, a'B} {a'C} -- from there on a step is k_ilu0_wx's, bit for bit;
+//     parity; an entry the lane's rows do not have is read from a cell of zeros) straight into the canonical order;
 //   * the courier is three waves, one per kind of traffic (a wave's memory operations retire in issue order: behind a write-through
 //     store or a load of A, a poll is late): the POLLER only polls, the EXPORTER stores the border pivots and fetches the imports'
 //     transposed entries eight steps ahead, the PREFETCHER (below) reads ahead for other tiles;
@@ -1381,15 +740,27 @@ k_ilu0_wx(WfArgs A)
 //     then the wave reads again until it is;
 //   * the hand-off arrays are kept once (a lane's source of `dt` steps ago is one of four precomputed addresses), which is what
 //     lets 128 KB of ring fit beside them.
-// MODE 1 (experiment, ILUPP_WD_MODE=1): the pivot recurrence alone -- of the records only {a'C, u_rr} is stored (results are wrong by
-// design; what VERDICT r5 asked to be measured: the chain without the record stream).
 // =============================================================================================
-#ifndef WD_NP
-#define WD_NP 2
-#endif
-#ifndef WA_DMA_AUX
-#define WA_DMA_AUX 0
-#endif
+struct WfArgs {
+    const int32_t *ltab, *ltabB, *uslot, *wtab;   // forward lane table, backward lane table, forward -> backward slot, chunk table
+    const double *val;                            // A's values, the pointer rounded down to 16 bytes
+    uint32_t val_bytes;
+    int32_t val_shift;
+    unsigned char *pkL, *pkU;                     // format-1 records, both in the forward schedule's order
+    const int32_t *xe, *xw;
+    double *xch;
+    int64_t xch_len;                              // doubles of the exchange: a workgroup's export window never reaches past it
+    int32_t *ctrl;                                // [0] ticket, [1] error
+    int32_t flags;                                // 2 = every workgroup of the launch is resident at once; 8 = compact L records (format 2)
+    int32_t *prog;                                // [tile] steps done, [nwg + tile] blocks of eight steps somebody has asked for
+};
+struct WfPair { int idx0, stride, sk, cnt; unsigned at0; int atm, klast, sh, hasT; int astart, pw; };    // (st_direct.hip: SdPair; astart: where the producer's workgroup exports its first step; pw: that workgroup)
+
+__device__ __forceinline__ __amdgpu_buffer_rsrc_t wf_rsrc(const WfArgs &A)
+{
+    return __builtin_amdgcn_make_buffer_rsrc(const_cast<double *>(A.val), 0, (int)A.val_bytes, 0x00020000);
+}
+
 static constexpr int kWdSH = 2;                            // steps a delivery is ahead of the step that uses it
 static constexpr int kWdWaveBlk = 64 * 128 + 16;           // a wave's windows of one block, and 16 bytes of zeros (what a row position the lane does not have reads)
 // the value of step (v - dt) of `src` in a hand-off array whose slots are `row` doubles long, as read for step v (mod 4)
@@ -1424,8 +795,8 @@ struct WaCfg {
     static_assert(U % (2 * D) == 0 && U % 4 == 0 && U % NP == 0, "slots are immediates of the unrolled loops");
     static_assert(Lds * (4 / NCW) <= 160 * 1024 - 256 * (4 / NCW), "the LDS of a CU");
 };
-enum { WA_CP = 0, WA_LF = 4, WA_IP = 8, WA_TP = 9, WA_EP = 10, WA_DEAD = 11, WA_BIG = 12, WA_WARM = 13,          // (set anew for every unit)
-       WA_CHAIN = 14, WA_UM = 16, WA_UA = 17, WA_UB = 18, WA_BARC = 20, WA_BARG = 21 };
+enum { WA_CP = 0, WA_LF = 4, WA_IP = 8, WA_TP = 9, WA_EP = 10, WA_DEAD = 11, WA_BIG = 12, WA_WARM = 13,          // (set by the set-up)
+       WA_BARC = 20, WA_BARG = 21 };
 static constexpr unsigned kWaSpinLimit = 1u << 24;
 
 // (LDS words other waves write: ordered with compiler barriers -- `volatile` would turn them into flat, system-scope accesses)
@@ -1490,9 +861,7 @@ struct WaLane {
     bool hasB, hasC, hasUB, hasUC;
 };
 
-// RP: a REPLAY of steps [tlo, thi) of tile `wg` (MODE 2): the pivots are read, not computed -- the chain has stored them --, and the
-// three quarters of the records the chain left out are written: {lC, lB} {lA, 1} and {a'A, a'B}
-template <int MODE, int NCW, int D, bool RP>
+template <int NCW, int D>
 __device__ __forceinline__ void wa_consumer(const WfArgs &A, unsigned char *lds, const int wg, const WaLane<WaCfg<NCW, D>::U> W, const int tlo, const int thi)
 {
     typedef WaCfg<NCW, D> C;
@@ -1512,10 +881,6 @@ __device__ __forceinline__ void wa_consumer(const WfArgs &A, unsigned char *lds,
     const unsigned cl2 = 1024u - (unsigned)ln * 8u;
     typedef unsigned int v2w2_ __attribute__((ext_vector_type(2)));
     const unsigned xown = C::X + (unsigned)t * 8u, tbown = C::TB + (unsigned)t * 8u, tcown = C::TC + (unsigned)t * 8u;
-    // (RP) the lane's stored pivot of step s_: write-through by the chain, 1 where the lane had no row or the wave no chunk
-    typedef unsigned int v4w_ __attribute__((ext_vector_type(4)));
-#define WA_LDW(s_) __builtin_amdgcn_raw_buffer_load_b128(rU, (unsigned)((s_) - tminw) * 2048u + 1024u + (unsigned)ln * 16u, 0, 16)
-#define WA_W(r_, s_) (((unsigned)((s_) - tminw) < (unsigned)nchw) ? __builtin_bit_cast(v2dd, r_).y : 1.0)
 #define WA_ROW(blk_, par_, r0_, r1_, r2_, r3_)                                                                     \
     do {                                                                                                           \
         const unsigned o_ = (unsigned)(blk_) * kWdWaveBlk;                                                         \
@@ -1574,38 +939,8 @@ __device__ __forceinline__ void wa_consumer(const WfArgs &A, unsigned char *lds,
     double tB = st_lds(lds, W.tB[0]), tC = st_lds(lds, W.tC[0]);
     double w3prev = 1.0, upA = 0.0;
     double qC = 1.0;
-    v4w_ wq[2];                                             // (RP) the stored pivots of the next two steps
-    if (RP) {
-        // the two steps before: what the other waves' lanes read of them (two steps old), this lane's own last pivot
-        const v4w_ r1 = WA_LDW(tlo - 1), r2 = WA_LDW(tlo - 2);
-#pragma unroll
-        for (int i = 0; i < 2; ++i) wq[i] = WA_LDW(tlo + i);
-        const double w1 = WA_W(r1, tlo - 1), w2 = WA_W(r2, tlo - 2);
-        *reinterpret_cast<double *>(lds + xown + (unsigned)((tlo - 1) & 3) * (C::RowL * 8)) = w1;
-        *reinterpret_cast<double *>(lds + xown + (unsigned)((tlo - 2) & 3) * (C::RowL * 8)) = w2;
-        w3prev = w1;
-        qC = wx_from_lane(W.src16, w1);
-    }
     asm volatile("" ::: "memory");
     if (ln == 0) wa_set<C>(lds, WA_CP + wv, tlo - 1);
-    if (RP) {
-        // (bB, bC above were read before the wave below had put its two steps in: again, behind the first step's check)
-        unsigned spins = 0;
-        for (;;) {
-            const int c0 = wa_ld32(lds, W.ca);
-            if (__builtin_amdgcn_ballot_w64(c0 - W.coff < tlo) == 0) break;
-            __builtin_amdgcn_s_sleep(1);
-            if ((++spins & 1023u) == 0) {
-                if (spins > kWaSpinLimit) { atomicExch(&A.ctrl[1], 1); wa_set<C>(lds, WA_DEAD, 1); }
-                if (wa_cnt<C>(lds, WA_DEAD) != 0) { dead = true; break; }
-            }
-        }
-        asm volatile("" ::: "memory");
-        // (only what another wave of the tile has put there: an import was read above, before this wave said so -- the poller takes
-        // the slot back once every wave has)
-        if (W.xB[0] < C::XI) bB = st_lds(lds, W.xB[0]);
-        if (W.xC[0] < C::XI) bC = st_lds(lds, W.xC[0]);
-    }
     int k = tlo - sk;
     int cv = wa_ld32(lds, W.ca);
 #ifdef WX_STAMP
@@ -1641,12 +976,12 @@ __device__ __forceinline__ void wa_consumer(const WfArgs &A, unsigned char *lds,
             WA_ROW(((u + 2) >> 1) % D, u & 1, m0_, m1_, m2_, m3_);
             const double nB = st_lds(lds, W.xB[(u + 1) & 3]);
             const double nC = st_lds(lds, W.xC[(u + 1) & 3]);
-            const double ntB = RP ? 0.0 : st_lds(lds, W.tB[(u + 1) & 3]);
-            const double ntC = RP ? 0.0 : st_lds(lds, W.tC[(u + 1) & 3]);
+            const double ntB = st_lds(lds, W.tB[(u + 1) & 3]);
+            const double ntC = st_lds(lds, W.tC[(u + 1) & 3]);
             const bool valid = (unsigned)k < (unsigned)cnt;
 #ifdef WX_STAMP
-            if (!RP && t == 0 && wg < 4096 && k == 0) g_wf_tl[wg * 4 + 1] = __builtin_amdgcn_s_memrealtime();
-            if (!RP && t == 0 && wg < 4096 && k == cnt - 1) g_wf_tl[wg * 4 + 2] = __builtin_amdgcn_s_memrealtime();
+            if (t == 0 && wg < 4096 && k == 0) g_wf_tl[wg * 4 + 1] = __builtin_amdgcn_s_memrealtime();
+            if (t == 0 && wg < 4096 && k == cnt - 1) g_wf_tl[wg * 4 + 2] = __builtin_amdgcn_s_memrealtime();
 #endif
             const double aA = c1_.x, tA = k == 0 ? 0.0 : upA;
             const double uA = c2_.x;
@@ -1656,18 +991,12 @@ __device__ __forceinline__ void wa_consumer(const WfArgs &A, unsigned char *lds,
             cv = wa_ld32(lds, W.ca);
             const double lA = aA / w3prev;
             double w = c1_.y;
-            if (!RP) {
-                w = w - lC * tC;
-                w = w - lB * tB;
-                w = w - lA * tA;
-                const unsigned long long wb = st_bits(w);
-                if ((wb & ~3ull) == (kSentinel & ~3ull)) w = st_dbl(kCanonNaN);
-            }
-            double w3 = valid ? w : 1.0;
-            if (RP) {
-                w3 = WA_W(wq[u & 1], s);
-                wq[u & 1] = WA_LDW(s + 2);
-            }
+            w = w - lC * tC;
+            w = w - lB * tB;
+            w = w - lA * tA;
+            const unsigned long long wb = st_bits(w);
+            if ((wb & ~3ull) == (kSentinel & ~3ull)) w = st_dbl(kCanonNaN);
+            const double w3 = valid ? w : 1.0;
             *reinterpret_cast<double *>(lds + xown + (unsigned)(u & 3) * (C::RowL * 8)) = w3;
             qC = wx_from_lane(W.src16, w3);
             w3prev = w3; upA = c2_.x;
@@ -1676,25 +1005,16 @@ __device__ __forceinline__ void wa_consumer(const WfArgs &A, unsigned char *lds,
                 v2dd la, lb, ua, ub;
                 la.x = lC; la.y = lB; lb.x = lA; lb.y = 1.0;
                 ua.x = uA; ua.y = c2_.y; ub.x = c3_.x; ub.y = w3;
-                if (MODE == 0 || RP) {
-                    __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(v4u_, la), rL, vout, 0, 2);
-                    // (flags bit 3: compact L records -- lA alone, 8 bytes per lane: four memory lines of a step's sixteen less)
-                    if (compactL) __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(v2w2_, lA), rL, vout + cl2, 0, 2);
-                    else __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(v4u_, lb), rL, vout + 1024u, 0, 2);
-                    __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(v4u_, ua), rU, vout, 0, 2);
-                }
-                if (RP) {
-                } else if (MODE == 2) {
-                    // (write-through: the finishers on other CUs read it; at most 15 of this wave's stores are ever on their way)
-                    __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(v4u_, ub), rU, vout + 1024u, 0, 16);
-                    asm volatile("s_waitcnt vmcnt(15)" ::: "memory");
-                } else {
-                    __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(v4u_, ub), rU, vout + 1024u, 0, 2);
-                }
+                __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(v4u_, la), rL, vout, 0, 2);
+                // (flags bit 3: compact L records -- lA alone, 8 bytes per lane: four memory lines of a step's sixteen less)
+                if (compactL) __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(v2w2_, lA), rL, vout + cl2, 0, 2);
+                else __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(v4u_, lb), rL, vout + 1024u, 0, 2);
+                __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(v4u_, ua), rU, vout, 0, 2);
+                __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(v4u_, ub), rU, vout + 1024u, 0, 2);
                 vout += 2048u;
             }
             WA_ENDS(k + 1, n0_, n1_, n2_, n3_);
-            if (!RP) WA_HAND_T((u + 1) & 3, n2_, n3_);
+            WA_HAND_T((u + 1) & 3, n2_, n3_);
             // this wave's step is done: its LDS writes are in front of the counter's (a wave's LDS operations stay in order)
             asm volatile("" ::: "memory");
             if (ln == 0) wa_set<C>(lds, WA_CP + wv, s);
@@ -1705,23 +1025,21 @@ __device__ __forceinline__ void wa_consumer(const WfArgs &A, unsigned char *lds,
         }
     }
 #ifdef WX_STAMP
-    if (!RP && ln == 0 && wg < 4096) { g_wf_wait[wg * 16 + wv] = cslow_; if (wv == 0) g_wf_wait[wg * 16 + 13] = nslow_; }
+    if (ln == 0 && wg < 4096) { g_wf_wait[wg * 16 + wv] = cslow_; if (wv == 0) g_wf_wait[wg * 16 + 13] = nslow_; }
 #endif
-    // (every store of this wave has arrived: the word the exporter's last progress and the finishers of this tile's leftovers wait for)
+    // (every store of this wave has arrived: the word the exporter's last progress waits for)
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     if (ln == 0) wa_set<C>(lds, WA_CP + wv, 0x7ffffff8);
 #undef WA_ROW
 #undef WA_HAND_T
 #undef WA_ENDS
-#undef WA_LDW
-#undef WA_W
 }
 
 // the poller: the imported pivots of step j into slot j mod 8 of the import ring, as far ahead of the consumers as the earlier
 // workgroups (and the ring) allow
 template <int NCW, int D>
 __device__ __forceinline__ void wa_poller(const WfArgs &A, const unsigned long long *idle, unsigned char *lds, const WfPair P,
-                                          const int tlo, const int thi, const int wg, const bool publish)
+                                          const int tlo, const int thi, const int wg)
 {
     typedef WaCfg<NCW, D> C;
     constexpr int NP = C::NP, SH = kWdSH, U = C::U;
@@ -1752,7 +1070,7 @@ __device__ __forceinline__ void wa_poller(const WfArgs &A, const unsigned long l
                 if (spins > kStSpinLimit || e != 0) { dead = true; break; }
             }
         }
-        if (ln == 0) { wa_set<C>(lds, WA_WARM, 1); if (A.prog && publish) st_agent_i32(&A.prog[wg], 0); }
+        if (ln == 0) { wa_set<C>(lds, WA_WARM, 1); st_agent_i32(&A.prog[wg], 0); }
     }
     // the value of step tlo_ + i_: wait for it, put it into the ring, ask for the one eight steps on; a value that was not there at the
     // first look means this workgroup has caught up with the one it reads from: everything asked for meanwhile was asked too early,
@@ -1818,7 +1136,7 @@ __device__ __forceinline__ void wa_poller(const WfArgs &A, const unsigned long l
 // the exporter: the border pivots of step s behind the consumers' step s; the imports' transposed entries four steps ahead
 template <int NCW, int D>
 __device__ __forceinline__ void wa_exporter(const WfArgs &A, unsigned char *lds, const WfPair P, const int tlo, const int thi, const int wg,
-                                            const int elane, const bool publish)
+                                            const int elane)
 {
     typedef WaCfg<NCW, D> C;
     constexpr int NA = C::NP, U = C::U;
@@ -1831,7 +1149,7 @@ __device__ __forceinline__ void wa_exporter(const WfArgs &A, unsigned char *lds,
     const int xrow0 = A.xw[wg * 4 + 3] + (tlo - A.xw[wg * 4 + 1]) * E;
     const unsigned ea = C::X + (unsigned)((elane >= 0 ? elane : C::NL) * 8);
     const int thiR = tlo + (thi - tlo + U - 1) / U * U;
-    // (clamped to the allocation, as wf_courier's)
+    // (clamped to the allocation)
     const long long xroom = (long long)A.xch_len - (long long)xrow0;
     const long long xwant = (long long)(thi - tlo) * (long long)E;
     const __amdgpu_buffer_rsrc_t rx = __builtin_amdgcn_make_buffer_rsrc(A.xch + (xroom > 0 ? xrow0 : 0), 0, (int)(8 * (xroom > 0 ? (xwant < xroom ? xwant : xroom) : 0)), 0x00020000);
@@ -1870,10 +1188,11 @@ __device__ __forceinline__ void wa_exporter(const WfArgs &A, unsigned char *lds,
             ga[u % NA] = WAC_LDAT(s + 4 + NA - P.sk);
             if (ln == 0) { wa_set<C>(lds, WA_EP, s); wa_set<C>(lds, WA_TP, s + 4); }
             // (for the prefetchers of other workgroups: how far this tile is, in steps from its first)
-            if ((u & 7) == 0 && ln == 0 && A.prog && publish) st_agent_i32(&A.prog[wg], s - tlo);
+            if ((u & 7) == 0 && ln == 0) st_agent_i32(&A.prog[wg], s - tlo);
         }
     }
-    if (A.prog && publish) { (void)wa_wait_consumers<C, NCW>(lds, 0x7ffffff0, A.ctrl); if (ln == 0) st_agent_i32(&A.prog[wg], 0x3fffffff); }
+    (void)wa_wait_consumers<C, NCW>(lds, 0x7ffffff0, A.ctrl);
+    if (ln == 0) st_agent_i32(&A.prog[wg], 0x3fffffff);
 #undef WAC_AT
 #undef WAC_LDAT
 }
@@ -1904,7 +1223,7 @@ __device__ __forceinline__ void wa_loader(const WfArgs &A, unsigned char *lds, c
 #define WAL_ISSUE(slot_)                                                                                             \
     do {                                                                                                             \
         _Pragma("unroll") for (int q = 0; q < 8; ++q) {                                                              \
-            __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, (lds_void *)(lds + lw * C::WaveRing + (slot_) * kWdWaveBlk + q * 1024), 16, g[q], 0, 0, WA_DMA_AUX); \
+            __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, (lds_void *)(lds + lw * C::WaveRing + (slot_) * kWdWaveBlk + q * 1024), 16, g[q], 0, 0, 0); \
             g[q] += S[q];                                                                                            \
         }                                                                                                            \
         asm volatile("" ::: "memory");                                                                               \
@@ -1915,20 +1234,16 @@ __device__ __forceinline__ void wa_loader(const WfArgs &A, unsigned char *lds, c
     if (ln == 0) wa_set<C>(lds, WA_LF + lw, tlo + 3);
     const int thiR = tlo + (thi - tlo + U - 1) / U * U;
     bool dead = false;
-#ifdef WX_STAMP
-    unsigned long long iacc_ = 0, vacc_ = 0, sacc_ = 0;
-#endif
-#ifndef WA_NO_PAIR
     // Two blocks at a time, the two windows of a lane right behind each other: the memory line they share is asked for once (the
     // windows start where the rows start, so consecutive windows of a lane overlap in a line; profiles/r06_cu_stream.txt: 37 against
     // 30 GB/s of new bytes per CU).  The ring then has two blocks in flight and four steps of lead for the first of a pair instead of
-    // three and six -- and the kernel takes 0.84 ms instead of 0.90 at 256^3 (-DWA_NO_PAIR: one block every two steps).
+    // three and six -- and the kernel takes 0.84 ms instead of 0.90 at 256^3 with one block every two steps.
 #define WAL_ISSUE2(s0_, s1_)                                                                                         \
     do {                                                                                                             \
         _Pragma("unroll") for (int q = 0; q < 8; ++q) {                                                              \
-            __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, (lds_void *)(lds + lw * C::WaveRing + (s0_) * kWdWaveBlk + q * 1024), 16, g[q], 0, 0, WA_DMA_AUX); \
+            __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, (lds_void *)(lds + lw * C::WaveRing + (s0_) * kWdWaveBlk + q * 1024), 16, g[q], 0, 0, 0); \
             g[q] += S[q];                                                                                            \
-            __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, (lds_void *)(lds + lw * C::WaveRing + (s1_) * kWdWaveBlk + q * 1024), 16, g[q], 0, 0, WA_DMA_AUX); \
+            __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, (lds_void *)(lds + lw * C::WaveRing + (s1_) * kWdWaveBlk + q * 1024), 16, g[q], 0, 0, 0); \
             g[q] += S[q];                                                                                            \
         }                                                                                                            \
         asm volatile("" ::: "memory");                                                                               \
@@ -1956,47 +1271,7 @@ __device__ __forceinline__ void wa_loader(const WfArgs &A, unsigned char *lds, c
         }
     }
 #undef WAL_ISSUE2
-#else
-    for (int tb = tlo; tb < thiR; tb += U) {
-#pragma unroll
-        for (int bb = 0; bb < U / 2; ++bb) {
-            // block b (steps tb + 2 bb, + 1): its slot takes block b + D once the wave has read its rows (during the two steps before);
-            // block b + 2 is published when it has landed (the D - 2 blocks behind it may be on their way: eight instructions each)
-            const int need = tb + 2 * bb - 1;
-#ifdef WX_STAMP
-            const unsigned long long s0_ = __builtin_amdgcn_s_memtime();
-#endif
-            if (!dead) {
-                unsigned spins = 0;
-                while (wa_cnt<C>(lds, WA_CP + lw) < need) {
-                    __builtin_amdgcn_s_sleep(1);
-                    if ((++spins & 1023u) == 0) {
-                        if (spins > kWaSpinLimit) { atomicExch(&A.ctrl[1], 1); wa_set<C>(lds, WA_DEAD, 1); }
-                        if (wa_cnt<C>(lds, WA_DEAD) != 0) { dead = true; break; }
-                    }
-                }
-            }
-#ifdef WX_STAMP
-            const unsigned long long i0_ = __builtin_amdgcn_s_memtime();
-            sacc_ += i0_ - s0_;
-#endif
-            WAL_ISSUE(bb % D);
-#ifdef WX_STAMP
-            const unsigned long long v0_ = __builtin_amdgcn_s_memtime();
-            iacc_ += v0_ - i0_;
-#endif
-            if (D == 4) asm volatile("s_waitcnt vmcnt(16)" ::: "memory"); else asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
-#ifdef WX_STAMP
-            vacc_ += __builtin_amdgcn_s_memtime() - v0_;
-#endif
-            if (ln == 0) wa_set<C>(lds, WA_LF + lw, tb + 2 * bb + 5);
-        }
-    }
-#endif
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-#ifdef WX_STAMP
-    if (ln == 0 && wg < 4096 && lw == 0) { g_wf_wait[wg * 16 + 5] = sacc_; g_wf_wait[wg * 16 + 6] = iacc_; g_wf_wait[wg * 16 + 7] = vacc_; }
-#endif
 #undef WAL_ISSUE
 }
 
@@ -2009,10 +1284,7 @@ __device__ __forceinline__ void wa_loader(const WfArgs &A, unsigned char *lds, c
 // atomic add on claim[tile] (from -1; block 0 is what the tile's loaders bring before its first step); a tile counts as begun, for
 // this purpose, when its poller says that every workgroup it reads from has begun -- some twenty steps before its first.  While
 // its own tile works the wave sleeps (it would take from what its CU can have in flight).
-#ifndef WA_PF_LEAD
-#define WA_PF_LEAD 32
-#endif
-static constexpr int kPfLead = WA_PF_LEAD;                   // steps ahead of a tile's published progress that are asked for
+static constexpr int kPfLead = 32;                           // steps ahead of a tile's published progress that are asked for
 
 template <int NCW, int D>
 __device__ __forceinline__ unsigned wa_pf_block(const WfArgs &A, const __amdgpu_buffer_rsrc_t rs, const int tile, const int blk)
@@ -2047,94 +1319,13 @@ __device__ __forceinline__ unsigned wa_pf_block(const WfArgs &A, const __amdgpu_
     return acc;
 }
 
-// ---------------------------------------------------------------------------------------------
-// MODE 2: the chains store a quarter of the records, REPLAYS write the rest.  The waves on the chain of a tile store {a'C, u_rr} only
-// (write-through: other CUs read it); everything else of a row's records follows from A and the pivots without any recurrence --
-// l = a / u_kk, the strict upper part of U is A's (ILU0.hpp:47-62 for rows whose eliminations meet them on the diagonal only) -- and
-// is written by a workgroup whose own tile has ended: it takes a unit of kRpSteps steps of any tile that is kFinMargin steps past
-// them and runs the same waves over it once more (wa_unit<RP>) -- loaders, poller, the four waves -- with the pivots read instead
-// of computed: no hand-over to wait for, the rows mostly still in the Infinity Cache.  That takes 48 of the 64 record bytes per row
-// off the CU that is bounded by what it can have in flight while it is on the critical path, and puts them on CUs that would idle.
-// (The chain waves keep at most 15 of their stores unacknowledged: what a replay reads has arrived.  The arithmetic of a replay is
-// the chain's, the same divisions on the same operands: bit-identical records.)
-// ---------------------------------------------------------------------------------------------
-static constexpr int kFinMargin = 16;
-#ifndef WA_RP_STEPS
-#define WA_RP_STEPS 32
-#endif
-static constexpr int kRpSteps = WA_RP_STEPS;
-
-// the first step of a tile and the number of its blocks of eight steps (as its own workgroup computes them)
-template <int NCW, int D>
-__device__ __forceinline__ void wa_tile_span(const WfArgs &A, const int tile, int *tl_out, int *nblk_out)
-{
-    int tl = 0x7fffffff, th = -0x7fffffff;
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-        const int32_t *w4 = A.wtab + (size_t)(tile * 4 + q) * 4;
-        const int a = w4[1], b = w4[2];
-        if (b > 0) { tl = min(tl, a); th = max(th, a + b); }
-    }
-    constexpr int U = WaCfg<NCW, D>::U;
-    tl &= U == 8 ? ~7 : ~3;
-    *tl_out = tl;
-    *nblk_out = th > tl ? ((th - tl + U - 1) / U * U) / 8 : 0;
-}
-
-// (wave 0 of a workgroup between units) the next unit to replay -> WA_UM (the tile; -1: none is left anywhere), WA_UA, WA_UB
-template <int NCW, int D>
-__device__ __forceinline__ void wa_claim_unit(const WfArgs &A, unsigned char *lds, const int wg)
-{
-    typedef WaCfg<NCW, D> C;
-    const int ln = threadIdx.x & 63;
-    const int nwg = (int)gridDim.x;
-    int32_t *prog = A.prog, *claimR = A.prog + 2 * nwg;
-    unsigned spins = 0;
-    for (;;) {
-        bool open = false;
-        for (int t0 = 0; t0 < nwg; t0 += 64) {
-            const int tt = t0 + ((ln + wg) & 63);
-            bool ready = false;
-            int cr = 0, tl = 0, nb = 0;
-            if (tt < nwg) {
-                const int pr = ld_agent_i32(&prog[tt]);
-                cr = ld_agent_i32(&claimR[tt]);
-                wa_tile_span<NCW, D>(A, tt, &tl, &nb);
-                const int nunits = (nb * 8 + kRpSteps - 1) / kRpSteps;
-                if (cr + 1 < nunits) {
-                    open = true;
-                    ready = pr >= 0x3fffffff || pr >= kRpSteps * (cr + 2) + kFinMargin;
-                }
-            }
-            const unsigned long long bw = __builtin_amdgcn_ballot_w64(ready);
-            if (bw != 0) {
-                const int L = __builtin_ctzll(bw);
-                int got = 0;
-                if (ln == L) got = atomicCAS(&claimR[tt], cr, cr + 1) == cr ? 1 : 0;
-                got = __builtin_amdgcn_readlane(got, L);
-                if (got) {
-                    if (ln == L) {
-                        const int ua = tl + kRpSteps * (cr + 1);
-                        wa_set<C>(lds, WA_UM, tt); wa_set<C>(lds, WA_UA, ua); wa_set<C>(lds, WA_UB, min(ua + kRpSteps, tl + 8 * nb));
-                    }
-                    return;
-                }
-                open = true;
-            }
-        }
-        if (__builtin_amdgcn_ballot_w64(open) == 0 || wa_cnt<C>(lds, WA_DEAD) != 0 || ++spins > (1u << 20)) { if (ln == 0) wa_set<C>(lds, WA_UM, -1); return; }
-        __builtin_amdgcn_s_sleep(64);
-    }
-}
-
 // The prefetcher: one wave of a workgroup, on its own from the launch on.  Before its tile begins and after its chain has ended it reads
 // ahead for the tiles at work (asleep in between: it would take from what its CU can have in flight while that is on the critical path).
-template <int MODE, int NCW, int D, bool PF>
+template <int NCW, int D>
 __device__ __forceinline__ void wa_helper(const WfArgs &A, unsigned char *lds, const int wg)
 {
     typedef WaCfg<NCW, D> C;
     const int ln = threadIdx.x & 63;
-    if (!A.prog) return;
     const int nwg = (int)gridDim.x;
     int32_t *prog = A.prog, *claim = A.prog + nwg;
     const __amdgpu_buffer_rsrc_t rs = wf_rsrc(A);
@@ -2173,7 +1364,7 @@ __device__ __forceinline__ void wa_helper(const WfArgs &A, unsigned char *lds, c
             if (wa_cnt<C>(lds, WA_WARM) != 0) { own_warm = true; continue; }
         } else if (!own_done) {
             if (wa_cnt<C>(lds, WA_DEAD) != 0) break;
-            if (wa_cnt<C>(lds, WA_CHAIN) != 2 && !(MODE != 2 && wa_cnt<C>(lds, WA_CP) >= 0x7ffffff0)) { __builtin_amdgcn_s_sleep(127); continue; }
+            if (wa_cnt<C>(lds, WA_CP) < 0x7ffffff0) { __builtin_amdgcn_s_sleep(127); continue; }
             own_done = true;
             // (a launch of more workgroups than the chip holds: this one's CU is wanted by the next)
             if (!(A.flags & 2)) break;
@@ -2220,21 +1411,18 @@ __device__ __forceinline__ void wa_helper(const WfArgs &A, unsigned char *lds, c
     if (acc == 0x9e3779b9u && A.val_bytes == 0xfffffff3u) atomicExch(&A.ctrl[1], (int)acc);        // (the loads above are not dead code)
 }
 
-// (per-XCD ticket counters in the control words: [2], [3], [9] .. [14])
-__device__ __forceinline__ int wa_xcd_word(const int x) { return x < 2 ? 2 + x : 7 + x; }
-
-// one UNIT of a workgroup's work: the chain of its own tile (RP false: tile `wg`, all of its steps), or (RP, MODE 2) the replay of steps
-// [ua, ub) of some tile whose chain is past them.  The waves of the roles only (the prefetcher goes its own way): they meet at
-// wa_bar, not at s_barrier.
-template <int MODE, int NCW, int D, bool RP>
-__device__ __forceinline__ void wa_unit(const WfArgs &A, unsigned char *lds, int *s_cnt, int &s_total, const int wg, const int ua, const int ub)
+// The waves of the roles on the workgroup's tile.  They meet at wa_bar, not at s_barrier (which would count the prefetcher too).  (A
+// function of its own: folded into the kernel's body, the same code gets another register allocation.)
+template <int NCW, int D>
+__device__ __forceinline__ void wa_tile(const WfArgs &A, unsigned char *lds, int *s_cnt, int &s_total, const int wg)
 {
     typedef WaCfg<NCW, D> C;
     constexpr int U = C::U, NL = C::NL;
     constexpr int NROLE = NL + 128 + NCW * 64;
+    const int t = threadIdx.x;
+    // (the scratch at the ring's start is the set-up's)
     WfPair *s_pairs = reinterpret_cast<WfPair *>(lds);
     int *s_exp = reinterpret_cast<int *>(lds + 64 * sizeof(WfPair));
-    const int t = threadIdx.x;
     int tlo = 0x7fffffff, thi = -0x7fffffff;
 #pragma unroll
     for (int q = 0; q < 4; ++q) {
@@ -2245,17 +1433,13 @@ __device__ __forceinline__ void wa_unit(const WfArgs &A, unsigned char *lds, int
     tlo = __builtin_amdgcn_readfirstlane(tlo); thi = __builtin_amdgcn_readfirstlane(thi);
     if (thi <= tlo) return;
     tlo &= U == 8 ? ~7 : ~3;                                          // step % 4 (% 8) = position in the unrolled loops
-    if (RP) { tlo = ua; thi = min(thi, ub); }
-    // the hand-off arrays start all +0.0 (the windows are whatever they are: a lane reads its own rows or the cells of zeros behind
-    // them, which no DMA touches), the scratch at the ring's start is the set-up's
-    for (int i = (int)(C::X / 8) + t; i < (int)(C::Cnt / 8); i += NROLE) reinterpret_cast<double *>(lds)[i] = 0.0;
     if (t < 4) s_cnt[t] = 0;
     wa_bar<C>(lds, NROLE / 64);
     if (t < 64) { WfPair z; z.idx0 = 0; z.stride = 0; z.sk = 0; z.cnt = 0; z.at0 = 0; z.atm = 0; z.klast = -1; z.sh = 0; z.hasT = 0; z.astart = -1; z.pw = -1; s_pairs[t] = z; }
     if (t < NL) s_exp[t] = -1;
     if (t < 4) *reinterpret_cast<double *>(lds + C::X + (unsigned)((t * C::RowL + NL) * 8)) = 1.0;
     // (a consumer wave has "done step tlo - 1" when it has read what its first step starts from)
-    if (t < 14) wa_set<C>(lds, t, t == WA_BIG ? 0x7fffffff : ((t == WA_DEAD || t == WA_WARM) ? 0 : (t < WA_LF ? tlo - 2 : ((RP && (t == WA_TP || t == WA_EP)) ? 0x7ffffff0 : tlo - 1))));
+    if (t < 14) wa_set<C>(lds, t, t == WA_BIG ? 0x7fffffff : ((t == WA_DEAD || t == WA_WARM) ? 0 : (t < WA_LF ? tlo - 2 : tlo - 1)));
     wa_bar<C>(lds, NROLE / 64);
     if (t < NL) {
         const int slot = wg * kThreads + t;
@@ -2435,11 +1619,11 @@ __device__ __forceinline__ void wa_unit(const WfArgs &A, unsigned char *lds, int
         wa_bar<C>(lds, NROLE / 64);
 #ifdef WX_STAMP
         const unsigned long long cy0_ = __builtin_amdgcn_s_memtime();
-        if (!RP && t == 0 && wg < 4096) g_wf_tl[wg * 4] = __builtin_amdgcn_s_memrealtime();
+        if (t == 0 && wg < 4096) g_wf_tl[wg * 4] = __builtin_amdgcn_s_memrealtime();
 #endif
-        wa_consumer<MODE, NCW, D, RP>(A, lds, wg, W, tlo, thi);
+        wa_consumer<NCW, D>(A, lds, wg, W, tlo, thi);
 #ifdef WX_STAMP
-        if (!RP && t == 0 && wg < 4096) {
+        if (t == 0 && wg < 4096) {
             g_wf_tl[wg * 4 + 3] = __builtin_amdgcn_s_memrealtime(); g_wf_wait[wg * 16 + 12] = __builtin_amdgcn_s_memtime() - cy0_;
             // where the workgroup ran: HW_ID (wave, SIMD, pipe, CU, SH, SE ...) and XCC_ID
             g_wf_wait[wg * 16 + 8] = (unsigned long long)__builtin_amdgcn_s_getreg(0xF804) | ((unsigned long long)__builtin_amdgcn_s_getreg(0x1814) << 32);
@@ -2456,9 +1640,9 @@ __device__ __forceinline__ void wa_unit(const WfArgs &A, unsigned char *lds, int
         wa_bar<C>(lds, NROLE / 64);
         if (t < NL + 64) {
             const unsigned long long *idle = reinterpret_cast<const unsigned long long *>(A.ltab + (size_t)wg * kThreads * kStTab);
-            wa_poller<NCW, D>(A, idle, lds, P, tlo, thi, wg, !RP);
-        } else if (!RP) {
-            wa_exporter<NCW, D>(A, lds, P, tlo, thi, wg, elane, true);
+            wa_poller<NCW, D>(A, idle, lds, P, tlo, thi, wg);
+        } else {
+            wa_exporter<NCW, D>(A, lds, P, tlo, thi, wg, elane);
         }
     } else if (t < NL + 128 + NCW * 64) {
         wa_bar<C>(lds, NROLE / 64);
@@ -2469,77 +1653,38 @@ __device__ __forceinline__ void wa_unit(const WfArgs &A, unsigned char *lds, int
     }
 }
 
+// MODE is always 0: the kernel keeps its profiler name, k_ilu0_wa<0, 4, 4>, which committed counter data is looked up by.
 template <int MODE, int NCW, int D>
 __global__ void __launch_bounds__((WaCfg<NCW, D>::Threads), (NCW == 2 ? 4 : 3))
 k_ilu0_wa(WfArgs A)
 {
+    static_assert(MODE == 0, "one mode");
     typedef WaCfg<NCW, D> C;
-    constexpr int NL = C::NL;
+    constexpr int NROLE = C::NL + 128 + NCW * 64;
     extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
     __shared__ int s_cnt[4], s_total;
     __shared__ unsigned s_ticket;
-    if (threadIdx.x == 0) {
-        // Which tile: the next ticket -- or (experiment, flags bit 0; only when every workgroup of the launch is resident at once) the
-        // next tile of THIS XCD's class (tile mod 8 = XCD).  The hardware starts the workgroups of one XCD in a row, so plain tickets
-        // put a whole line of 16 neighbouring tiles -- which work at the same time -- behind one XCD's L2 and fabric port; by class
-        // every band of the wavefront is spread over all eight.  Measured at 256^3: no difference (1.005 ms either way).
-        int tile = -1;
-        if (A.flags & 1) {
-            const int x = (int)(__builtin_amdgcn_s_getreg(0x1814) & 7u);
-            for (int i = 0; i < 8 && tile < 0; ++i) {
-                const int xx = (x + i) & 7;
-                const int c = atomicAdd(&A.ctrl[wa_xcd_word(xx)], 1);
-                if (c * 8 + xx < (int)gridDim.x) tile = c * 8 + xx;
-            }
-        } else {
-            tile = atomicAdd(&A.ctrl[0], 1);
-        }
-        s_ticket = (unsigned)tile;
-    }
+    if (threadIdx.x == 0) s_ticket = (unsigned)atomicAdd(&A.ctrl[0], 1);
     __syncthreads();
     const int wg = (int)s_ticket;
-    if (wg < 0) return;
+    __builtin_assume(wg >= 0);                                        // (the tile indexes every table: no sign extension)
     const int t = threadIdx.x;
-    // all of LDS +0.0 once (the cells of zeros behind every wave's windows stay that way)
+    // all of LDS +0.0 once: the hand-off arrays start that way, and the cells of zeros behind every wave's windows stay that way (the
+    // windows are whatever they are: a lane reads its own rows or those cells, which no DMA touches)
     for (int i = t; i < C::Lds / 8; i += C::Threads) reinterpret_cast<double *>(lds)[i] = 0.0;
     __syncthreads();
-    constexpr int NROLE = NL + 128 + NCW * 64;
     if (t >= NROLE) {
         // the prefetcher: on its own from here
-        wa_helper<MODE, NCW, D, true>(A, lds, wg);
+        wa_helper<NCW, D>(A, lds, wg);
         return;
     }
-    wa_unit<MODE, NCW, D, false>(A, lds, s_cnt, s_total, wg, 0, 0);
-    if (MODE != 2 || !(A.flags & 2) || !A.prog) return;
-    // Replays: what the chains leave of the records, in units of kRpSteps steps of any tile that is far enough past them
-    wa_bar<C>(lds, NROLE / 64);
-    if (t == 0) wa_set<C>(lds, WA_CHAIN, 2);
-    for (;;) {
-        if (t < 64) wa_claim_unit<NCW, D>(A, lds, wg);
-        wa_bar<C>(lds, NROLE / 64);
-        const int um = wa_cnt<C>(lds, WA_UM), ua = wa_cnt<C>(lds, WA_UA), ub = wa_cnt<C>(lds, WA_UB);
-        if (um < 0) break;
-        wa_unit<MODE, NCW, D, true>(A, lds, s_cnt, s_total, um, ua, ub);
-        wa_bar<C>(lds, NROLE / 64);
-    }
+    wa_tile<NCW, D>(A, lds, s_cnt, s_total, wg);
 }
 
-static int wd_mode()
-{
-    static const int m = [] { const char *e = getenv("ILUPP_WD_MODE"); return e ? atoi(e) : 0; }();
-    return m;
-}
-bool wa_on()
-{
-    static const bool on = getenv("ILUPP_NO_WA") == nullptr;
-    return on;
-}
 // the factor kernel ilu0_numeric_wx launches, as a profiler names it (ilupp_hip_kernel_names)
 const char *wx_factor_kernel_name()
 {
-    if (!wa_on()) return "k_ilu0_wx";
-    if (wd_mode() == 1) return "k_ilu0_wa<1, 4, 4>";
-    return getenv("ILUPP_REPLAY") != nullptr ? "k_ilu0_wa<2, 4, 4>" : "k_ilu0_wa<0, 4, 4>";
+    return "k_ilu0_wa<0, 4, 4>";
 }
 
 // what the factor kernel finds prepared, in ONE launch (three small launches in a row cost their dispatch gaps, and this chain -- not the
@@ -2562,11 +1707,7 @@ int ilu0_numeric_wx(hipStream_t st, const DevMat &A, PackedSweep *pl, PackedSwee
         int dev = 0;
         ILUPP_HIP(hipGetDevice(&dev));
         std::call_once(once[dev & 63], [] {
-            ILUPP_HIP(hipFuncSetAttribute((const void *)k_ilu0_wx, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kWfLds));
-            typedef WaCfg<4, 4> C44;
-            ILUPP_HIP(hipFuncSetAttribute((const void *)k_ilu0_wa<0, 4, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, C44::Lds));
-            ILUPP_HIP(hipFuncSetAttribute((const void *)k_ilu0_wa<1, 4, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, C44::Lds));
-            ILUPP_HIP(hipFuncSetAttribute((const void *)k_ilu0_wa<2, 4, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, C44::Lds));
+            ILUPP_HIP(hipFuncSetAttribute((const void *)k_ilu0_wa<0, 4, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, WaCfg<4, 4>::Lds));
         });
     }
     WfArgs a;
@@ -2578,19 +1719,18 @@ int ilu0_numeric_wx(hipStream_t st, const DevMat &A, PackedSweep *pl, PackedSwee
     a.pkL = reinterpret_cast<unsigned char *>(pl->pk); a.pkU = reinterpret_cast<unsigned char *>(pu->pk);
     a.xe = pl->xe; a.xw = pl->xw; a.xch = pl->xch; a.xch_len = pl->xch_len; a.ctrl = d_ctrl;
     a.flags = 0;
-    a.prog = nullptr;
-    if (wa_on() && getenv("ILUPP_NO_PREFETCH") == nullptr) {
+    {
         // progress and claim words of the tiles, all -1 (one buffer per device, kept)
         static int32_t *buf[64];
         static int64_t cap[64];
         int dev = 0;
         ILUPP_HIP(hipGetDevice(&dev));
         const int d = dev & 63;
-        if (cap[d] < 3 * (int64_t)pl->nwg) {
+        if (cap[d] < 2 * (int64_t)pl->nwg) {
             if (buf[d]) ILUPP_HIP(pool_free(buf[d]));
             buf[d] = nullptr; cap[d] = 0;
-            ILUPP_HIP(pool_malloc(&buf[d], sizeof(int32_t) * 3 * (size_t)pl->nwg));
-            cap[d] = 3 * (int64_t)pl->nwg;
+            ILUPP_HIP(pool_malloc(&buf[d], sizeof(int32_t) * 2 * (size_t)pl->nwg));
+            cap[d] = 2 * (int64_t)pl->nwg;
         }
         a.prog = buf[d];
     }
@@ -2598,46 +1738,29 @@ int ilu0_numeric_wx(hipStream_t st, const DevMat &A, PackedSweep *pl, PackedSwee
         long long blocks = ((long long)pl->xch_len + 255) / 256;
         if (blocks > 4096) blocks = 4096;
         if (blocks < 1) blocks = 1;
-        hipLaunchKernelGGL(k_wa_prepare, dim3((unsigned)blocks), dim3(256), 0, st, d_ctrl, a.prog, a.prog ? 3 * (int)pl->nwg : 0,
+        hipLaunchKernelGGL(k_wa_prepare, dim3((unsigned)blocks), dim3(256), 0, st, d_ctrl, a.prog, 2 * (int)pl->nwg,
                            reinterpret_cast<unsigned long long *>(pl->xch), (long long)pl->xch_len);
     }
     {
         // does the chip hold every workgroup of the launch at once?  (Then the prefetchers stay behind their own tile's end, for the
-        // tiles that still work; and, an experiment that changed nothing -- ILUPP_XCD_TICKETS=1 --, tiles are handed out by XCD.)
+        // tiles that still work.)
         static int ncu[64];
         int dev = 0;
         ILUPP_HIP(hipGetDevice(&dev));
         if (ncu[dev & 63] == 0) { int v = 0; ILUPP_HIP(hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev)); ncu[dev & 63] = v > 0 ? v : -1; }
-        if (ncu[dev & 63] > 0 && (int64_t)pl->nwg <= (int64_t)ncu[dev & 63]) {
-            a.flags |= 2;
-            if (getenv("ILUPP_XCD_TICKETS") != nullptr) {
-                a.flags |= 1;
-                ILUPP_HIP(hipMemsetAsync(d_ctrl + 9, 0, 6 * sizeof(int32_t), st));
-            }
-        }
+        if (ncu[dev & 63] > 0 && (int64_t)pl->nwg <= (int64_t)ncu[dev & 63]) a.flags |= 2;
     }
-    if (pl->join_ev && pl->join_before) ILUPP_HIP(hipStreamWaitEvent(st, pl->join_ev, 0));       // (grid.hip's proof, on its side stream)
+    if (pl->join_ev) ILUPP_HIP(hipStreamWaitEvent(st, pl->join_ev, 0));       // (grid.hip's proof, on its side stream)
     ILUPP_HIP(hipEventRecord(e0, st));
     // compact L records when the L sweep that reads them will run (the vector-wave sweep: ILUPP_NO_COMPACT_L=1 for format 1)
     static const bool no_compact = getenv("ILUPP_NO_COMPACT_L") != nullptr;
-    const bool compact = wa_on() && wd_mode() != 1 && !no_compact && wx_vec_on() && pl->vec_ok && pu->vec_ok;
+    const bool compact = !no_compact && wx_vec_on() && pl->vec_ok && pu->vec_ok;
     if (compact) a.flags |= 8;
-    if (wa_on()) {
-        typedef WaCfg<4, 4> C;
-        // (MODE 2 -- the chains store a quarter of the records, replays by the workgroups whose tile has ended write the rest -- is an
-        // experiment, ILUPP_REPLAY=1, where every workgroup is resident and the progress words exist: bit-identical, and slower at
-        // 256^3 -- 1.07 ms against 0.93: a replay unit's set-up and its 30 KB per step cost the idle CUs more time than they have)
-        static const bool nofin = getenv("ILUPP_REPLAY") == nullptr;
-        if (wd_mode() == 1) hipLaunchKernelGGL((k_ilu0_wa<1, 4, 4>), dim3((unsigned)pl->nwg), dim3(C::Threads), C::Lds, st, a);
-        else if ((a.flags & 2) && a.prog && !nofin) hipLaunchKernelGGL((k_ilu0_wa<2, 4, 4>), dim3((unsigned)pl->nwg), dim3(C::Threads), C::Lds, st, a);
-        else hipLaunchKernelGGL((k_ilu0_wa<0, 4, 4>), dim3((unsigned)pl->nwg), dim3(C::Threads), C::Lds, st, a);
-    } else {
-        hipLaunchKernelGGL(k_ilu0_wx, dim3((unsigned)pl->nwg), dim3(kWfThreads), kWfLds, st, a);
-    }
+    typedef WaCfg<4, 4> C;
+    hipLaunchKernelGGL((k_ilu0_wa<0, 4, 4>), dim3((unsigned)pl->nwg), dim3(C::Threads), C::Lds, st, a);
     ILUPP_HIP(hipEventRecord(e1, st));
     ILUPP_HIP(hipGetLastError());
     int32_t ctrl[12];
-    if (pl->join_ev && !pl->join_before) ILUPP_HIP(hipStreamWaitEvent(st, pl->join_ev, 0));
     ILUPP_HIP(d2h_async(st, ctrl, d_ctrl, sizeof(ctrl)));
     if (pl->arm && pl->arm_ev) {
         // (the first apply's control words and exchange buffers are made ready behind the read-back, while the host is on its way back)

@@ -122,12 +122,12 @@ def _run_with(env):
 
 def test_every_switch_of_the_grid_path_gives_the_same_bits():
     """the general pass (ILUPP_NO_GRID), the general lane-table kernels on the grid's row blocks (ILUPP_GRID_TABLES=0, ILUPP_GRID_LINK=0), the
-    waiting construction (ILUPP_NO_SPEC), the proof at its three places (ILUPP_GRID_CHECK_AT), the sweeps through k_st_vec
+    waiting construction (ILUPP_NO_SPEC), the sweeps through k_st_vec
     (ILUPP_NO_VECWAVE) and an unarmed apply (ILUPP_NO_ARM): one digest over factors and applies"""
     info, ref = _run_with({})
     assert all(l.startswith("grid") and "k_sptrsv_wv<1, false>" in l for l in info), info
-    for env in ({"ILUPP_NO_GRID": "1"}, {"ILUPP_GRID_TABLES": "0"}, {"ILUPP_GRID_LINK": "0"}, {"ILUPP_NO_SPEC": "1"}, {"ILUPP_GRID_CHECK_AT": "1"},
-                {"ILUPP_GRID_CHECK_AT": "2"}, {"ILUPP_NO_VECWAVE": "1"}, {"ILUPP_NO_ARM": "1"}, {"ILUPP_NO_COMPACT_L": "1"}):
+    for env in ({"ILUPP_NO_GRID": "1"}, {"ILUPP_GRID_TABLES": "0"}, {"ILUPP_GRID_LINK": "0"}, {"ILUPP_NO_SPEC": "1"},
+                {"ILUPP_NO_VECWAVE": "1"}, {"ILUPP_NO_ARM": "1"}, {"ILUPP_NO_COMPACT_L": "1"}):
         info2, dig = _run_with(env)
         assert dig == ref, (env, info2)
         if "ILUPP_NO_GRID" in env:
