@@ -677,59 +677,112 @@ void ensure_transposed(ilupp_precond *p)
     p->haveT = true;
 }
 
-#define MAXLEN_OF(M) ((&(M) == &p->LcT || &(M) == &p->UcT) ? p->max_len_T : p->max_row_len)
+// ---- the sweeps of an apply -----------------------------------------------------------------------------------------------------------
+// One sweep of one object: the stored triangle it walks (slot 0 = Lc, 1 = Uc, 2 = UcT, 3 = LcT: the numbering of pack_tried[] and lvl[])
+// and the manner.  Whatever else a sweep needs follows from the slot: sweep_parts.
+struct SweepOp { int slot; SweepKind kind; };
+struct SweepParts {
+    const DevMat &M; const Schedule &sch; const int32_t *desc; int32_t maxlen;      // the triangle, its schedule, descriptors, longest major slice
+    PackedSweep *pk; bool *pack_tried;                                               // its level-major or static records
+    LevelSweep *lvl;                                                                 // its renumbered copy in level order
+};
+static SweepParts sweep_parts(ilupp_precond *p, SweepOp op)
+{
+    switch (op.slot) {
+    // (an LU object's L has A's strictly-lower pattern, hence A's forward cuts: the factor-sweep schedule serves it)
+    case 0: return {p->Lc, (p->kind == KIND_LU && !p->sL.start) ? p->sA : p->sL, p->dL, p->max_row_len, &p->pkL, &p->pack_tried[0], &p->lvl[0]};
+    case 1: return {p->Uc, p->sU, p->dU, p->max_row_len, &p->pkU, &p->pack_tried[1], &p->lvl[1]};
+    case 2: return {p->UcT, p->sUT, p->dUT, p->max_len_T, &p->pkUT, &p->pack_tried[2], &p->lvl[2]};
+    default: return {p->LcT, p->sLT, p->dLT, p->max_len_T, &p->pkLT, &p->pack_tried[3], &p->lvl[3]};
+    }
+}
+
+// The two sweeps of an apply, in the order they run: the one place that knows which factor and which loop of the reference
+// (sparse_implementation.h:4040-4087: T1 gather forward, T2 scatter forward, T3 gather backward, T4 scatter backward) every case takes.
+// A scatter loop is a gather sweep over the transposed storage, T4 with the off-diagonal entries last-to-first (BWD_FIRST_DESC).
+struct ApplyPlan {
+    SweepOp first, second;
+    // with the level-major factor path (every in-workgroup dependency one step back) the intermediate vector may travel level-major
+    // between the two sweeps (first's ybuf, second's ysrc); y then only carries the values other workgroups poll
+    bool ylm;
+    bool transposed() const { return first.slot >= 2 || second.slot >= 2; }      // reads UcT or LcT
+};
+static ApplyPlan apply_plan(int kind, bool transpose, bool input_csc, bool llt_diag_last)
+{
+    const SweepKind fwd = SWEEP_FWD_LAST_ASC, bwd = SWEEP_BWD_FIRST_ASC, bwd_desc = SWEEP_BWD_FIRST_DESC;
+    if (kind == KIND_LU) {
+        // solve with M (= A for CSR input): fwd(Lc) then bwd(Uc)           [CSR/ID, CSC/TRANSPOSE]
+        // solve with M^T:                   fwd(Uc^T) then bwd_desc(Lc^T)  [CSR/TRANSPOSE, CSC/ID]
+        if (transpose == input_csc) return {{0, fwd}, {1, bwd}, true};
+        return {{2, fwd}, {3, bwd_desc}, false};
+    }
+    if (kind == KIND_UTU) {
+        // ILUC (preconditioner_implementation.h:940-958 + :103-111): the left factor is stored column-wise, the right one row-wise,
+        // i.e. both array triples read as upper CSR matrices with the diagonal first (F1 = left^T in Lc, F2 = right in Uc).
+        //   ID:        T2(left)    = forward sweep over F1^T, then T3(right)  = backward sweep over F2
+        //   TRANSPOSE: T2(right^T) = forward sweep over F2^T, then T3(left^T) = backward sweep over F1
+        if (!transpose) return {{3, fwd}, {1, bwd}, false};
+        return {{2, fwd}, {0, bwd}, false};
+    }
+    // LL^T: apply == apply_trans (preconditioner_implementation.h:381-394)
+    if (llt_diag_last) return {{0, fwd}, {3, bwd_desc}, false};      // IChol0 (Lc row-major): T1(L) then T4(L)
+    return {{3, fwd}, {0, bwd}, false};                               // ICholT (Lc column-major): T2(L) then T3(L)
+}
+static ApplyPlan apply_plan(const ilupp_precond *p, int transpose) { return apply_plan(p->kind, transpose != 0, p->input_csc, p->llt_diag_last); }
+
+#define OR_RETURN(call) do { const int rc_ = (call); if (rc_) return rc_; } while (0)
 
 // one sweep: the packed kernel when the factor has a verified level-major form, else the CSR kernels.  Either way
 // the right-hand side buffer is all-sentinel afterwards (the CSR kernels reset it row by row).
 // level-major records of a sweep straight from its CSR arrays and descriptors (any object whose rows are short enough:
 // transposed ILU(0) factors, IChol(0)); tried once, on first use
-static const PackedSweep *packed(ilupp_precond *p, int which, SweepKind kind, const DevMat &M, const Schedule &sch,
-                                 const int32_t *desc, int32_t maxlen, PackedSweep *ps)
+static const PackedSweep *packed(ilupp_precond *p, SweepOp op)
 {
-    if (!ps->valid && !p->pack_tried[which] && desc && !p->degenerate) {
-        if (lm_prepare(p->stream, kind, M, sch, desc, maxlen, ps)) {
-            lm_pack(p->stream, kind, M, sch, desc, ps, 3);
-            lm_finish(p->stream, ps);
+    const SweepParts s = sweep_parts(p, op);
+    if (!s.pk->valid && !*s.pack_tried && s.desc && !p->degenerate) {
+        if (lm_prepare(p->stream, op.kind, s.M, s.sch, s.desc, s.maxlen, s.pk)) {
+            lm_pack(p->stream, op.kind, s.M, s.sch, s.desc, s.pk, 3);
+            lm_finish(p->stream, s.pk);
         }
     }
-    p->pack_tried[which] = true;
-    return ps->valid ? ps : nullptr;
+    *s.pack_tried = true;
+    return s.pk->valid ? s.pk : nullptr;
 }
 
 // Rows too long for the level-major records (ILUT factors, ICholT with fill, ILU(0) of a long-row matrix) sweep one lane per row, in
 // level order when the factor has one (sptrsv_lvl.hip; renumbered copy of the factor, built at the first sweep and shared by the single
-// and the block apply: one level order per factor).  nullptr: the sweep of M is another kernel (the caller tells which).
-static bool long_rows(const ilupp_precond *p, const DevMat &M)
+// and the block apply: one level order per factor).  nullptr: the sweep is another kernel (the caller tells which).
+static bool long_rows(ilupp_precond *p, SweepOp op)
 {
+    const DevMat &M = sweep_parts(p, op).M;
     return (M.nnz > 4 * (int64_t)M.n || (p->kind == KIND_LU && p->fperm != nullptr)) && M.n >= 1024;
 }
-static LevelSweep *level_sweep(ilupp_precond *p, SweepKind kind, const DevMat &M, const Schedule &sch)
+static LevelSweep *level_sweep(ilupp_precond *p, SweepOp op)
 {
-    LevelSweep *ls = &M == &p->Lc ? &p->lvl[0] : &M == &p->Uc ? &p->lvl[1] : &M == &p->UcT ? &p->lvl[2] : &M == &p->LcT ? &p->lvl[3] : nullptr;
-    if (ls && !ls->tried) {
-        if (&M == &p->Lc || &M == &p->Uc) ensure_csr_values(p);
-        const bool reuse = &M == &p->Lc && p->fperm && kind == SWEEP_FWD_LAST_ASC;      // L's rows depend on each other as A's lower part does
-        lvl_build(p->stream, kind, M, sch, ls, reuse ? p->fperm : nullptr, reuse ? p->fperm_levels : 0);
+    const SweepParts s = sweep_parts(p, op);
+    if (!s.lvl->tried) {
+        if (op.slot < 2) ensure_csr_values(p);
+        const bool reuse = op.slot == 0 && p->fperm && op.kind == SWEEP_FWD_LAST_ASC;      // L's rows depend on each other as A's lower part does
+        lvl_build(p->stream, op.kind, s.M, s.sch, s.lvl, reuse ? p->fperm : nullptr, reuse ? p->fperm_levels : 0);
     }
-    return ls && ls->valid ? ls : nullptr;
+    return s.lvl->valid ? s.lvl : nullptr;
 }
 
-static int sweep(ilupp_precond *p, SweepKind kind, const DevMat &M, const Schedule &sch, const int32_t *desc, int32_t maxlen,
-                 const PackedSweep *ps, double *rhs, double *out, int32_t *ticket, int32_t *err,
+static int sweep(ilupp_precond *p, SweepOp op, const PackedSweep *ps, double *rhs, double *out, int32_t *ticket, int32_t *err,
                  double *ypk_out = nullptr, const double *ypk_in = nullptr, const int32_t *ysrc = nullptr)
 {
+    const SweepParts s = sweep_parts(p, op);
     // every sweep but the static ones hands its unknowns over through `out` (the data is the flag): all-sentinel before it runs.
     // The static sweeps never touch the work vector, so an object that only ever runs them never pays for the fill.
     if (!(ps && ps->valid && ps->stat && !p->degenerate) && !p->work_clean) {
         fill_u64(p->stream, reinterpret_cast<unsigned long long *>(p->work), p->n, kSentinel);
         p->work_clean = true;
     }
-    if (p->degenerate) return sptrsv_rows(p->stream, kind, M, rhs, out, ticket, err);
+    if (p->degenerate) return sptrsv_rows(p->stream, op.kind, s.M, rhs, out, ticket, err);
     if (ps && ps->valid) {
         // (the static sweeps exchange through a buffer of their own: `out` needs no sentinels before and `rhs` none after)
-        if (ps->stat) return sptrsv_st(p->stream, *ps, sch, p->n, rhs, out, ticket, err, ypk_out, ypk_in, ysrc);
-        int rc = sptrsv_lm(p->stream, *ps, sch, p->n, rhs, out, ticket, err, ypk_out, ypk_in, ysrc);
-        if (rc) return rc;
+        if (ps->stat) return sptrsv_st(p->stream, *ps, s.sch, p->n, rhs, out, ticket, err, ypk_out, ypk_in, ysrc);
+        OR_RETURN(sptrsv_lm(p->stream, *ps, s.sch, p->n, rhs, out, ticket, err, ypk_out, ypk_in, ysrc));
         fill_u64(p->stream, reinterpret_cast<unsigned long long *>(rhs), p->n, kSentinel);
         return ILUPP_OK;
     }
@@ -737,14 +790,14 @@ static int sweep(ilupp_precond *p, SweepKind kind, const DevMat &M, const Schedu
     // block of consecutive rows.  With blocks, a row waits for everything its lane has to do before it, and the factors of
     // a random matrix have no chains that would make blocks pay: BASELINE config C3's apply took 70 + 186 ms, more than the
     // reference needs on one core.
-    if (long_rows(p, M)) {
+    if (long_rows(p, op)) {
         // ... and the rows in level order: in natural order only the rows inside the window of resident tickets can run, on a mesh a
         // few grid lines
-        const LevelSweep *ls = level_sweep(p, kind, M, sch);
+        const LevelSweep *ls = level_sweep(p, op);
         if (ls) return sptrsv_lvl(p->stream, *ls, rhs, out, ticket, err);
-        return sptrsv_rows(p->stream, kind, M, rhs, out, ticket, err);
+        return sptrsv_rows(p->stream, op.kind, s.M, rhs, out, ticket, err);
     }
-    return sptrsv(p->stream, kind, M, sch, desc, maxlen, rhs, out, ticket, err);
+    return sptrsv(p->stream, op.kind, s.M, s.sch, s.desc, s.maxlen, rhs, out, ticket, err);
 }
 // static form: records of U^T and L^T exist (built on first use; a pattern they cannot express is remembered)
 static bool static_transposed_ready(ilupp_precond *p)
@@ -780,8 +833,22 @@ static bool llt_static_pair(ilupp_precond *p, PackedSweep **pf_out, PackedSweep 
     return pf->valid && pf->pair && pb->valid && pb->pair;
 }
 
+// What an apply does before its sweeps, whichever route runs them then: the transposed storages when `plan` reads one, and the two static
+// forms that take the place of the plan's sweeps -- LU's transposed records (ROUTE_STATIC_T) and the LL^T pair (ROUTE_STATIC_PAIR: *pf, *pb).
+enum ApplyRoute { ROUTE_SWEEPS, ROUTE_STATIC_T, ROUTE_STATIC_PAIR };
+static ApplyRoute prepare_apply(ilupp_precond *p, const ApplyPlan &plan, PackedSweep **pf, PackedSweep **pb)
+{
+    if (!plan.transposed()) return ROUTE_SWEEPS;
+    if (p->kind == KIND_LU) {
+        p->pkL.xch_armed = p->pkU.xch_armed = false;
+        if (static_transposed_ready(p)) return ROUTE_STATIC_T;
+    }
+    ensure_transposed(p);
+    if (p->kind == KIND_LLT && llt_static_pair(p, pf, pb)) return ROUTE_STATIC_PAIR;
+    return ROUTE_SWEEPS;
+}
+
 // apply on a device vector; `transpose` as in apply_preconditioner_only(use, y)
-#define SWEEP_OR_RETURN(...) do { const int rc_ = sweep(__VA_ARGS__); if (rc_) return rc_; } while (0)
 int apply_dev(ilupp_precond *p, double *x, int transpose)
 {
     hipStream_t st = p->stream;
@@ -791,94 +858,33 @@ int apply_dev(ilupp_precond *p, double *x, int transpose)
     int32_t *err = p->ctrl, *t1 = p->ctrl + 4, *t2 = p->ctrl + 5;
     double *y = p->work;
     p->block_events = false;
-    if (p->kind == KIND_LU) {
-        // solve with M (= A for CSR input): fwd(Lc) then bwd(Uc)      [CSR/ID, CSC/TRANSPOSE]
-        // solve with M^T:                   fwd(Uc^T) then bwd_desc(Lc^T)  [CSR/TRANSPOSE, CSC/ID]
-        const bool with_MT = (transpose != 0) != p->input_csc;
-        if (!with_MT) {
-            // L has A's strictly-lower pattern, hence A's forward cuts: the factor-sweep schedule serves it
-            const Schedule &sl = p->sL.start ? p->sL : p->sA;
-            ILUPP_HIP(hipEventRecord(p->ev[0], st));
-            // with the level-major factor path (every in-workgroup dependency one step back) the intermediate vector
-            // travels level-major between the two sweeps; y then only carries the values other workgroups poll
-            const bool ylm = p->flm.built && p->pkL.valid && p->pkU.valid && p->pkL.ybuf && p->pkU.ysrc;
-            const PackedSweep *p1 = packed(p, 0, SWEEP_FWD_LAST_ASC, p->Lc, sl, p->dL, MAXLEN_OF(p->Lc), &p->pkL);
-            const PackedSweep *p2 = packed(p, 1, SWEEP_BWD_FIRST_ASC, p->Uc, p->sU, p->dU, MAXLEN_OF(p->Uc), &p->pkU);
-            ILUPP_HIP(hipEventRecord(p->ev[0], st));
-            SWEEP_OR_RETURN(p, SWEEP_FWD_LAST_ASC, p->Lc, sl, p->dL, MAXLEN_OF(p->Lc), p1, x, y, t1, err, ylm ? p->pkL.ybuf : nullptr);
-            ILUPP_HIP(hipEventRecord(p->ev[1], st));
-            SWEEP_OR_RETURN(p, SWEEP_BWD_FIRST_ASC, p->Uc, p->sU, p->dU, MAXLEN_OF(p->Uc), p2, y, x, t2, err, nullptr,
-                  ylm ? p->pkL.ybuf : nullptr, ylm ? p->pkU.ysrc : nullptr);
-            ILUPP_HIP(hipEventRecord(p->ev[2], st));
-        } else if ((p->pkL.xch_armed = p->pkU.xch_armed = false, static_transposed_ready(p))) {
-            // static form: the same two sweep kernels on records of U^T and L^T
-            ILUPP_HIP(hipEventRecord(p->ev[0], st));
-            { const int rc_ = sptrsv_st_T(st, p->pkL, p->n, x, y, t1, err, p->pkL.ybuf, nullptr); if (rc_) return rc_; }
-            ILUPP_HIP(hipEventRecord(p->ev[1], st));
-            { const int rc_ = sptrsv_st_T(st, p->pkU, p->n, y, x, t2, err, p->pkL.ybuf, p->pkU.ysrc); if (rc_) return rc_; }
-            ILUPP_HIP(hipEventRecord(p->ev[2], st));
-        } else {
-            ensure_transposed(p);
-            const PackedSweep *p1 = packed(p, 2, SWEEP_FWD_LAST_ASC, p->UcT, p->sUT, p->dUT, MAXLEN_OF(p->UcT), &p->pkUT);
-            const PackedSweep *p2 = packed(p, 3, SWEEP_BWD_FIRST_DESC, p->LcT, p->sLT, p->dLT, MAXLEN_OF(p->LcT), &p->pkLT);
-            ILUPP_HIP(hipEventRecord(p->ev[0], st));
-            SWEEP_OR_RETURN(p, SWEEP_FWD_LAST_ASC, p->UcT, p->sUT, p->dUT, MAXLEN_OF(p->UcT), p1, x, y, t1, err);
-            ILUPP_HIP(hipEventRecord(p->ev[1], st));
-            SWEEP_OR_RETURN(p, SWEEP_BWD_FIRST_DESC, p->LcT, p->sLT, p->dLT, MAXLEN_OF(p->LcT), p2, y, x, t2, err);
-            ILUPP_HIP(hipEventRecord(p->ev[2], st));
-        }
-    } else if (p->kind == KIND_UTU) {
-        // ILUC (preconditioner_implementation.h:940-958 + :103-111): the left factor is stored column-wise, the right one row-wise,
-        // i.e. both array triples read as upper CSR matrices with the diagonal first (F1 = left^T, F2 = right).
-        //   ID:        T2(left)  = forward sweep over F1^T,  then T3(right) = backward sweep over F2
-        //   TRANSPOSE: T2(right^T) = forward sweep over F2^T, then T3(left^T) = backward sweep over F1
-        ensure_transposed(p);
-        const bool tr = transpose != 0;
-        const DevMat &Mf = tr ? p->UcT : p->LcT;
-        const DevMat &Mb = tr ? p->Lc : p->Uc;
-        const Schedule &sf = tr ? p->sUT : p->sLT, &sb = tr ? p->sL : p->sU;
-        const int32_t *df = tr ? p->dUT : p->dLT, *db = tr ? p->dL : p->dU;
-        const PackedSweep *p1 = packed(p, tr ? 2 : 3, SWEEP_FWD_LAST_ASC, Mf, sf, df, MAXLEN_OF(Mf), tr ? &p->pkUT : &p->pkLT);
-        const PackedSweep *p2 = packed(p, tr ? 0 : 1, SWEEP_BWD_FIRST_ASC, Mb, sb, db, MAXLEN_OF(Mb), tr ? &p->pkL : &p->pkU);
+    const ApplyPlan plan = apply_plan(p, transpose);
+    PackedSweep *pf = nullptr, *pb = nullptr;
+    const ApplyRoute route = prepare_apply(p, plan, &pf, &pb);
+    if (route == ROUTE_STATIC_T) {
+        // static form: the same two sweep kernels on records of U^T and L^T
         ILUPP_HIP(hipEventRecord(p->ev[0], st));
-        SWEEP_OR_RETURN(p, SWEEP_FWD_LAST_ASC, Mf, sf, df, MAXLEN_OF(Mf), p1, x, y, t1, err);
+        OR_RETURN(sptrsv_st_T(st, p->pkL, p->n, x, y, t1, err, p->pkL.ybuf, nullptr));
         ILUPP_HIP(hipEventRecord(p->ev[1], st));
-        SWEEP_OR_RETURN(p, SWEEP_BWD_FIRST_ASC, Mb, sb, db, MAXLEN_OF(Mb), p2, y, x, t2, err);
-        ILUPP_HIP(hipEventRecord(p->ev[2], st));
-    } else {
-        // LL^T: apply == apply_trans (preconditioner_implementation.h:381-394)
-        ensure_transposed(p);
+        OR_RETURN(sptrsv_st_T(st, p->pkU, p->n, y, x, t2, err, p->pkL.ybuf, p->pkU.ysrc));
+    } else if (route == ROUTE_STATIC_PAIR) {
         // stencil-like factors (IChol0, ICholT without fill on a mesh): the static sweep kernels on the factor's own values
-        {
-            const bool dl = p->llt_diag_last;
-            PackedSweep *pf = nullptr, *pb = nullptr;
-            if (llt_static_pair(p, &pf, &pb)) {
-                ILUPP_HIP(hipEventRecord(p->ev[0], st));
-                { const int rc_ = sptrsv_st(st, *pf, dl ? p->sL : p->sLT, p->n, x, y, t1, err, pf->ybuf, nullptr, nullptr); if (rc_) return rc_; }
-                ILUPP_HIP(hipEventRecord(p->ev[1], st));
-                { const int rc_ = sptrsv_st(st, *pb, dl ? p->sLT : p->sL, p->n, y, x, t2, err, nullptr, pf->ybuf, pb->ysrc); if (rc_) return rc_; }
-                ILUPP_HIP(hipEventRecord(p->ev[2], st));
-                p->apply_events_valid = true;
-                return ILUPP_OK;
-            }
-        }
-        if (p->llt_diag_last) {       // IChol0: T1(L) then T4(L)
-            const PackedSweep *p1 = packed(p, 0, SWEEP_FWD_LAST_ASC, p->Lc, p->sL, p->dL, MAXLEN_OF(p->Lc), &p->pkL);
-            const PackedSweep *p2 = packed(p, 3, SWEEP_BWD_FIRST_DESC, p->LcT, p->sLT, p->dLT, MAXLEN_OF(p->LcT), &p->pkLT);
-            ILUPP_HIP(hipEventRecord(p->ev[0], st));
-            SWEEP_OR_RETURN(p, SWEEP_FWD_LAST_ASC, p->Lc, p->sL, p->dL, MAXLEN_OF(p->Lc), p1, x, y, t1, err);
-            ILUPP_HIP(hipEventRecord(p->ev[1], st));
-            SWEEP_OR_RETURN(p, SWEEP_BWD_FIRST_DESC, p->LcT, p->sLT, p->dLT, MAXLEN_OF(p->LcT), p2, y, x, t2, err);
-        } else {                      // ICholT: T2(L) then T3(L)
-            const PackedSweep *p1 = packed(p, 3, SWEEP_FWD_LAST_ASC, p->LcT, p->sLT, p->dLT, MAXLEN_OF(p->LcT), &p->pkLT);
-            const PackedSweep *p2 = packed(p, 0, SWEEP_BWD_FIRST_ASC, p->Lc, p->sL, p->dL, MAXLEN_OF(p->Lc), &p->pkL);
-            ILUPP_HIP(hipEventRecord(p->ev[0], st));
-            SWEEP_OR_RETURN(p, SWEEP_FWD_LAST_ASC, p->LcT, p->sLT, p->dLT, MAXLEN_OF(p->LcT), p1, x, y, t1, err);
-            ILUPP_HIP(hipEventRecord(p->ev[1], st));
-            SWEEP_OR_RETURN(p, SWEEP_BWD_FIRST_ASC, p->Lc, p->sL, p->dL, MAXLEN_OF(p->Lc), p2, y, x, t2, err);
-        }
-        ILUPP_HIP(hipEventRecord(p->ev[2], st));
+        const bool dl = p->llt_diag_last;
+        ILUPP_HIP(hipEventRecord(p->ev[0], st));
+        OR_RETURN(sptrsv_st(st, *pf, dl ? p->sL : p->sLT, p->n, x, y, t1, err, pf->ybuf, nullptr, nullptr));
+        ILUPP_HIP(hipEventRecord(p->ev[1], st));
+        OR_RETURN(sptrsv_st(st, *pb, dl ? p->sLT : p->sL, p->n, y, x, t2, err, nullptr, pf->ybuf, pb->ysrc));
+    } else {
+        const PackedSweep *pk1 = sweep_parts(p, plan.first).pk, *pk2 = sweep_parts(p, plan.second).pk;
+        const bool ylm = plan.ylm && p->flm.built && pk1->valid && pk2->valid && pk1->ybuf && pk2->ysrc;
+        const PackedSweep *p1 = packed(p, plan.first);
+        const PackedSweep *p2 = packed(p, plan.second);
+        ILUPP_HIP(hipEventRecord(p->ev[0], st));
+        OR_RETURN(sweep(p, plan.first, p1, x, y, t1, err, ylm ? pk1->ybuf : nullptr));
+        ILUPP_HIP(hipEventRecord(p->ev[1], st));
+        OR_RETURN(sweep(p, plan.second, p2, y, x, t2, err, nullptr, ylm ? pk1->ybuf : nullptr, ylm ? pk2->ysrc : nullptr));
     }
+    ILUPP_HIP(hipEventRecord(p->ev[2], st));
     p->apply_events_valid = true;
     return ILUPP_OK;
 }
@@ -930,45 +936,20 @@ __global__ void k_col_scatter(const double *__restrict__ col, double *__restrict
     if (i < n) X[i * ld] = col[i];
 }
 
-// the two sweeps of an apply when both run on the level-order kernel: apply_dev's branches, the same factors, sweep kinds and caches
+// the two sweeps of an apply when both run on the level-order kernel (apply_dev's plan, the same caches)
 static bool block_level_plan(ilupp_precond *p, int transpose, LevelSweep **first, LevelSweep **second)
 {
     *first = *second = nullptr;
     if (p->degenerate) return false;
-    auto lvl = [p](int which, SweepKind kind, const DevMat &M, const Schedule &sch, const int32_t *desc, PackedSweep *pk) -> LevelSweep * {
-        if (packed(p, which, kind, M, sch, desc, MAXLEN_OF(M), pk)) return nullptr;      // level-major or static records
-        return long_rows(p, M) ? level_sweep(p, kind, M, sch) : nullptr;
+    const ApplyPlan plan = apply_plan(p, transpose);
+    PackedSweep *pf = nullptr, *pb = nullptr;
+    if (prepare_apply(p, plan, &pf, &pb) != ROUTE_SWEEPS) return false;
+    auto lvl = [p](SweepOp op) -> LevelSweep * {
+        if (packed(p, op)) return nullptr;      // level-major or static records
+        return long_rows(p, op) ? level_sweep(p, op) : nullptr;
     };
-    if (p->kind == KIND_LU) {
-        const bool with_MT = (transpose != 0) != p->input_csc;
-        if (!with_MT) {
-            const Schedule &sl = p->sL.start ? p->sL : p->sA;
-            *first = lvl(0, SWEEP_FWD_LAST_ASC, p->Lc, sl, p->dL, &p->pkL);
-            *second = lvl(1, SWEEP_BWD_FIRST_ASC, p->Uc, p->sU, p->dU, &p->pkU);
-        } else {
-            p->pkL.xch_armed = p->pkU.xch_armed = false;
-            if (static_transposed_ready(p)) return false;
-            ensure_transposed(p);
-            *first = lvl(2, SWEEP_FWD_LAST_ASC, p->UcT, p->sUT, p->dUT, &p->pkUT);
-            *second = lvl(3, SWEEP_BWD_FIRST_DESC, p->LcT, p->sLT, p->dLT, &p->pkLT);
-        }
-    } else if (p->kind == KIND_UTU) {
-        ensure_transposed(p);
-        const bool tr = transpose != 0;
-        *first = lvl(tr ? 2 : 3, SWEEP_FWD_LAST_ASC, tr ? p->UcT : p->LcT, tr ? p->sUT : p->sLT, tr ? p->dUT : p->dLT, tr ? &p->pkUT : &p->pkLT);
-        *second = lvl(tr ? 0 : 1, SWEEP_BWD_FIRST_ASC, tr ? p->Lc : p->Uc, tr ? p->sL : p->sU, tr ? p->dL : p->dU, tr ? &p->pkL : &p->pkU);
-    } else {
-        ensure_transposed(p);
-        PackedSweep *pf = nullptr, *pb = nullptr;
-        if (llt_static_pair(p, &pf, &pb)) return false;
-        if (p->llt_diag_last) {       // IChol0: T1(L) then T4(L)
-            *first = lvl(0, SWEEP_FWD_LAST_ASC, p->Lc, p->sL, p->dL, &p->pkL);
-            *second = lvl(3, SWEEP_BWD_FIRST_DESC, p->LcT, p->sLT, p->dLT, &p->pkLT);
-        } else {                      // ICholT: T2(L) then T3(L)
-            *first = lvl(3, SWEEP_FWD_LAST_ASC, p->LcT, p->sLT, p->dLT, &p->pkLT);
-            *second = lvl(0, SWEEP_BWD_FIRST_ASC, p->Lc, p->sL, p->dL, &p->pkL);
-        }
-    }
+    *first = lvl(plan.first);
+    *second = lvl(plan.second);
     return *first && *second && !p->degenerate;
 }
 
@@ -1883,33 +1864,22 @@ void ml_destroy(ilupp_ml *m)
 
 static bool getenv_small_off() { static const bool off = getenv("ILUPP_NO_SMALL_SWEEPS") != nullptr; return off; }
 
-// one half of the ILUC-kind apply (apply_dev, KIND_UTU): forward = the T2 loop (left factor, or right^T), backward = the T3 loop
+// one half of the ILUC-kind apply (apply_plan, KIND_UTU): forward = the T2 loop (left factor, or right^T), backward = the T3 loop
 int utu_half(ilupp_precond *p, bool forward, bool tr, double *rhs, double *out, int32_t *ticket)
 {
     ensure_transposed(p);
     int32_t *err = p->ctrl;
+    const ApplyPlan plan = apply_plan(KIND_UTU, tr, false, false);
+    const SweepOp op = forward ? plan.first : plan.second;
     // small levels (the later, denser ones): one workgroup with the unknowns in LDS instead of a chain of hops through memory
     // (not for a factor with an empty row: p->degenerate objects keep the row-by-row kernel, which reports what it meets)
     // (up to 1 024 rows always; up to kSmallSweepMax = 4 096 when the rows are long -- more than 32 entries on average: there the general
     //  kernels' hop through memory per link of the dependency chain costs most.  Measured, apply of a whole object: 26 levels from n = 2 000,
     //  177 entries per row: 65 against 176 ms; 3 375 rows with 6 entries per row: 0.82 against 0.68 ms -- hence the second condition)
-    const DevMat &Msmall = forward ? (tr ? p->UcT : p->LcT) : (tr ? p->Lc : p->Uc);
-    if ((p->n <= 1024 || (p->n <= kSmallSweepMax && Msmall.nnz > 32 * (int64_t)p->n)) && !p->degenerate && !getenv_small_off()) {
-        const DevMat &M = Msmall;
-        return sptrsv_small(p->stream, forward ? SWEEP_FWD_LAST_ASC : SWEEP_BWD_FIRST_ASC, M, rhs, out, err);
-    }
-    if (forward) {
-        const DevMat &Mf = tr ? p->UcT : p->LcT;
-        const Schedule &sf = tr ? p->sUT : p->sLT;
-        const int32_t *df = tr ? p->dUT : p->dLT;
-        const PackedSweep *p1 = packed(p, tr ? 2 : 3, SWEEP_FWD_LAST_ASC, Mf, sf, df, MAXLEN_OF(Mf), tr ? &p->pkUT : &p->pkLT);
-        return sweep(p, SWEEP_FWD_LAST_ASC, Mf, sf, df, MAXLEN_OF(Mf), p1, rhs, out, ticket, err);
-    }
-    const DevMat &Mb = tr ? p->Lc : p->Uc;
-    const Schedule &sb = tr ? p->sL : p->sU;
-    const int32_t *db = tr ? p->dL : p->dU;
-    const PackedSweep *p2 = packed(p, tr ? 0 : 1, SWEEP_BWD_FIRST_ASC, Mb, sb, db, MAXLEN_OF(Mb), tr ? &p->pkL : &p->pkU);
-    return sweep(p, SWEEP_BWD_FIRST_ASC, Mb, sb, db, MAXLEN_OF(Mb), p2, rhs, out, ticket, err);
+    const DevMat &M = sweep_parts(p, op).M;
+    if ((p->n <= 1024 || (p->n <= kSmallSweepMax && M.nnz > 32 * (int64_t)p->n)) && !p->degenerate && !getenv_small_off())
+        return sptrsv_small(p->stream, op.kind, M, rhs, out, err);
+    return sweep(p, op, packed(p, op), rhs, out, ticket, err);
 }
 
 int ml_apply_dev(ilupp_ml *m, double *x, int transpose, int part = 0)       // part: 0 = both passes, 1 = the first only, 2 = the second only
