@@ -436,7 +436,7 @@ static int ilu0_numeric_any(ilupp_precond *p, const DevMat &A, bool have_prog, f
     if (p->flm.built) {
         // (flm.built means the static form: round 1's record-decoding level-major FACTOR kernel, which only matrices the static form takes
         // ever reached -- and then only under ILUPP_NO_STATIC --, was removed in round 5)
-        rc = ilu0_numeric_st(st, A, p->sA, &p->pkL, &p->pkU, &p->flm, p->ctrl, kms, p->ev[4], p->ev[5]);
+        rc = ilu0_numeric_st(st, A, &p->pkL, &p->pkU, &p->flm, p->ctrl, kms, p->ev[4], p->ev[5]);
         p->csr_vals = false;
         return rc;
     }
@@ -645,8 +645,8 @@ void ensure_csr_values(ilupp_precond *p)
         const int fmt = p->pkL.fmt;
         wx_convert_records(p->stream, &p->pkL, &p->pkU, 0);
         if (!p->Lc.ptr) (void)st_make_csr(p->stream, p->n, p->pkL, p->pkU, &p->Lc, &p->Uc);      // (throws on a HIP error)
-        st_unpack(p->stream, p->Lc, p->sA, p->pkL);
-        st_unpack(p->stream, p->Uc, p->sU, p->pkU);
+        st_unpack(p->stream, p->Lc, p->pkL);
+        st_unpack(p->stream, p->Uc, p->pkU);
         wx_convert_records(p->stream, &p->pkL, &p->pkU, fmt);
     }
     ILUPP_HIP(stream_sync(p->stream));
@@ -781,7 +781,7 @@ static int sweep(ilupp_precond *p, SweepOp op, const PackedSweep *ps, double *rh
     if (p->degenerate) return sptrsv_rows(p->stream, op.kind, s.M, rhs, out, ticket, err);
     if (ps && ps->valid) {
         // (the static sweeps exchange through a buffer of their own: `out` needs no sentinels before and `rhs` none after)
-        if (ps->stat) return sptrsv_st(p->stream, *ps, s.sch, p->n, rhs, out, ticket, err, ypk_out, ypk_in, ysrc);
+        if (ps->stat) return sptrsv_st(p->stream, *ps, p->n, rhs, out, ticket, err, ypk_out, ypk_in, ysrc);
         OR_RETURN(sptrsv_lm(p->stream, *ps, s.sch, p->n, rhs, out, ticket, err, ypk_out, ypk_in, ysrc));
         fill_u64(p->stream, reinterpret_cast<unsigned long long *>(rhs), p->n, kSentinel);
         return ILUPP_OK;
@@ -869,11 +869,10 @@ int apply_dev(ilupp_precond *p, double *x, int transpose)
         OR_RETURN(sptrsv_st_T(st, p->pkU, p->n, y, x, t2, err, p->pkL.ybuf, p->pkU.ysrc));
     } else if (route == ROUTE_STATIC_PAIR) {
         // stencil-like factors (IChol0, ICholT without fill on a mesh): the static sweep kernels on the factor's own values
-        const bool dl = p->llt_diag_last;
         ILUPP_HIP(hipEventRecord(p->ev[0], st));
-        OR_RETURN(sptrsv_st(st, *pf, dl ? p->sL : p->sLT, p->n, x, y, t1, err, pf->ybuf, nullptr, nullptr));
+        OR_RETURN(sptrsv_st(st, *pf, p->n, x, y, t1, err, pf->ybuf, nullptr, nullptr));
         ILUPP_HIP(hipEventRecord(p->ev[1], st));
-        OR_RETURN(sptrsv_st(st, *pb, dl ? p->sLT : p->sL, p->n, y, x, t2, err, nullptr, pf->ybuf, pb->ysrc));
+        OR_RETURN(sptrsv_st(st, *pb, p->n, y, x, t2, err, nullptr, pf->ybuf, pb->ysrc));
     } else {
         const PackedSweep *pk1 = sweep_parts(p, plan.first).pk, *pk2 = sweep_parts(p, plan.second).pk;
         const bool ylm = plan.ylm && p->flm.built && pk1->valid && pk2->valid && pk1->ybuf && pk2->ysrc;

@@ -331,7 +331,7 @@ void grid_schedules(hipStream_t st, const DevMat &A, const GridDims &g, DevMat *
 bool grid_lane_tables(hipStream_t st, const GridDims &gd, const Schedule &fwd, const Schedule &bwd, int32_t *ltabF, int32_t *ltabB,
                       int32_t *flagsF, int32_t *flagsB, int32_t *uslot, int32_t *skewF, int32_t *skewB, int32_t *wtabF, int32_t *wtabB, bool wx);
 // chunks of a schedule (all waves), chunks of its longest wave, exchange entries before the last workgroup and of the last workgroup, for
-// a box grid placed in 16 x 16 patches with the wave-exchange skews (what k_st_link / k_st_scan / k_st_xch_pair find); false: not predictable
+// a box grid placed in 16 x 16 patches with the wave-exchange skews (what k_st_link_pair / k_st_scan_pair / k_st_xch_pair find); false: not predictable
 bool grid_predict_sizes(const GridDims &g, int ty, int tz, int64_t *nchunks, int32_t *maxch, int64_t *xoff_last, int32_t *xsz_last);
 // ... and everything the static analysis makes from them (first chunks of the waves, positions in the other schedule's records, direct-feed
 // fields, backward right-hand-side map, exchange layout) for 16 x 16 patches, in closed form: one launch instead of k_st_scan_pair,
@@ -562,12 +562,11 @@ void lm_link_y(hipStream_t st, const Schedule &fwd, PackedSweep *pl, PackedSweep
 // st.hip
 bool st_analyse_ilu0(hipStream_t st, const DevMat &A, const Schedule &fwd, const Schedule &bwd, PackedSweep *pl,
                      PackedSweep *pu, FactorLM *f, SideJoin *join = nullptr, const GridDims *grid = nullptr);
-int ilu0_numeric_st(hipStream_t st, const DevMat &A, const Schedule &fwd, PackedSweep *pl, PackedSweep *pu, FactorLM *f,
-                    int32_t *d_ctrl, float *kernel_ms, hipEvent_t e0, hipEvent_t e1);
-int sptrsv_st(hipStream_t st, const PackedSweep &ps, const Schedule &sch, int32_t n, const double *rhs, double *out,
-              int32_t *d_ticket, int32_t *d_err, double *ypk_out = nullptr, const double *ypk_in = nullptr,
-              const int32_t *ysrc = nullptr);
-void st_unpack(hipStream_t st, const DevMat &M, const Schedule &sch, const PackedSweep &ps);
+int ilu0_numeric_st(hipStream_t st, const DevMat &A, PackedSweep *pl, PackedSweep *pu, FactorLM *f, int32_t *d_ctrl, float *kernel_ms,
+                    hipEvent_t e0, hipEvent_t e1);
+int sptrsv_st(hipStream_t st, const PackedSweep &ps, int32_t n, const double *rhs, double *out, int32_t *d_ticket, int32_t *d_err,
+              double *ypk_out = nullptr, const double *ypk_in = nullptr, const int32_t *ysrc = nullptr);
+void st_unpack(hipStream_t st, const DevMat &M, const PackedSweep &ps);
 bool ichol0_numeric_st(hipStream_t st, DevMat *L, const Schedule &fwd, int32_t *d_ctrl, float *kernel_ms, int *rc_out);
 // static sweeps for a pair of stored factors: Lrow = row-major lower, diagonal last; Urow = row-major upper, diagonal first; both
 // with at most 3 entries per row besides the diagonal (false: the structure does not fit; pl, pu released)

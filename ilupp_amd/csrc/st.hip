@@ -1,8 +1,8 @@
 // ilupp_amd/csrc/st.hip -- static level-major ILU(0) and triangular sweeps for stencil-like matrices (gfx950).
 //
-// Same arithmetic as ilu0_lm.hip / sptrsv_lm.hip (reference ILU0.hpp:26-66: row-wise IKJ, eliminations in ascending k,
+// Same arithmetic as ilu0_lvl.hip / sptrsv_lm.hip (reference ILU0.hpp:26-66: row-wise IKJ, eliminations in ascending k,
 // separate multiply and subtract; sparse_implementation.h:4040-4087: sequential accumulation in stored order, division by
-// the diagonal found by position), same placement (a lane owns a chain of consecutive rows, a workgroup a 16x16 patch of
+// the diagonal found by position), same placement as sptrsv_lm.hip (a lane owns a chain of consecutive rows, a workgroup a 16x16 patch of
 // chains, row k of lane t is due at step k + skew(t)).  What is new is that NOTHING about the structure travels with the rows:
 //
 //   * the analysis proves, for EVERY row, that the lane's rows all look alike: the columns of row r are r + o for offsets o
@@ -28,13 +28,11 @@
 //     again, which makes the tile fall back behind its producers by just the latency it needs.
 //
 // A step is bound by instruction issue (one wave per SIMD): everything that can be a lane constant is one.
-// Everything the proof rejects runs on the record-decoding kernels (records_lm.hip) or the CSR kernels (any matrix).
+// Everything the proof rejects runs on the level-order kernels (ilu0_lvl.hip, sptrsv_lvl.hip) or the CSR kernels (any matrix).
 #include <stdio.h>
 #include <stdlib.h>
 
 #include <mutex>
-
-#include <hipcub/hipcub.hpp>
 
 #include "st_common.h"
 
@@ -140,23 +138,14 @@ st_template_body(const int32_t *__restrict__ ptr, const int32_t *__restrict__ id
     if (bad) atomicOr(&flags[0], 2);
 }
 
-template <int TRI>
+// both schedules with one launch (blockIdx.y: 0 forward, 1 backward, each on the matrix whose rows it sweeps; a launch of 256 small
+// workgroups is 25 us of dependent loads whatever it does).  A y-extent of 1: the forward schedule alone.
+struct StTplArgs { const int32_t *ptr, *idx; int32_t B, nb; const int32_t *start, *blk2slot, *sfirst, *scount; int32_t *exported, *ltab, *flags; };
 __global__ void __launch_bounds__(kThreads)
-k_st_template(const int32_t *__restrict__ ptr, const int32_t *__restrict__ idx, int32_t B, int32_t nb,
-              const int32_t *__restrict__ start, const int32_t *__restrict__ blk2slot, const int32_t *__restrict__ sfirst,
-              const int32_t *__restrict__ scount, int32_t *__restrict__ exported, int32_t *__restrict__ ltab,
-              int32_t *__restrict__ flags)
+k_st_template_pair(StTplArgs f, StTplArgs b)
 {
-    st_template_body<TRI>(ptr, idx, B, nb, start, blk2slot, sfirst, scount, exported, ltab, flags);
-}
-// both schedules of a matrix with one launch (blockIdx.y: 0 forward, 1 backward; a launch of 256 small workgroups is 25 us of
-// dependent loads whatever it does)
-struct StTplArgs { int32_t B, nb; const int32_t *start, *blk2slot, *sfirst, *scount; int32_t *exported, *ltab, *flags; };
-__global__ void __launch_bounds__(kThreads)
-k_st_template_pair(const int32_t *__restrict__ ptr, const int32_t *__restrict__ idx, StTplArgs f, StTplArgs b)
-{
-    if (blockIdx.y == 0) st_template_body<1>(ptr, idx, f.B, f.nb, f.start, f.blk2slot, f.sfirst, f.scount, f.exported, f.ltab, f.flags);
-    else st_template_body<-1>(ptr, idx, b.B, b.nb, b.start, b.blk2slot, b.sfirst, b.scount, b.exported, b.ltab, b.flags);
+    if (blockIdx.y == 0) st_template_body<1>(f.ptr, f.idx, f.B, f.nb, f.start, f.blk2slot, f.sfirst, f.scount, f.exported, f.ltab, f.flags);
+    else st_template_body<-1>(b.ptr, b.idx, b.B, b.nb, b.start, b.blk2slot, b.sfirst, b.scount, b.exported, b.ltab, b.flags);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -262,23 +251,18 @@ st_link_body(int32_t *__restrict__ ltab, const int32_t *__restrict__ ltab_u, con
     if (bad) atomicOr(&flags[0], 4);
 }
 
-template <bool FWD>
-__global__ void __launch_bounds__(kThreads)
-k_st_link(int32_t *__restrict__ ltab, const int32_t *__restrict__ ltab_u, const int32_t *__restrict__ uslot,
-          int32_t *__restrict__ skew, int32_t *__restrict__ wtab, int32_t *__restrict__ flags, int32_t wx)
-{
-    __shared__ int s[kThreads];
-    st_link_body<FWD>(ltab, ltab_u, uslot, skew, wtab, flags, s, (wx & 1) != 0, (wx & 2) != 0);
-}
-// both schedules of an ILU(0) with one launch (blockIdx.y: 0 forward with the proof about the eliminations, 1 backward)
+// both schedules with one launch (blockIdx.y: 0 forward -- PROVE: with the proof about the eliminations, an ILU(0) on A; stored factors
+// have none to prove --, 1 backward; a y-extent of 1: the forward schedule alone).  wx: 1 = the wave-exchange skews and lane check,
+// | 2 = the backward half's lane check reads its templates as a backward schedule's (st_link_body reads that only with bit 0 set)
+template <bool PROVE>
 __global__ void __launch_bounds__(kThreads)
 k_st_link_pair(int32_t *__restrict__ ltabF, int32_t *__restrict__ ltabB, const int32_t *__restrict__ uslot, int32_t *__restrict__ skewF,
                int32_t *__restrict__ skewB, int32_t *__restrict__ wtabF, int32_t *__restrict__ wtabB, int32_t *__restrict__ flagsF,
                int32_t *__restrict__ flagsB, int32_t wx)
 {
     __shared__ int s[kThreads];
-    if (blockIdx.y == 0) st_link_body<true>(ltabF, ltabB, uslot, skewF, wtabF, flagsF, s, wx != 0, false);
-    else st_link_body<false>(ltabB, nullptr, nullptr, skewB, wtabB, flagsB, s, wx != 0, true);
+    if (blockIdx.y == 0) st_link_body<PROVE>(ltabF, ltabB, uslot, skewF, wtabF, flagsF, s, (wx & 1) != 0, false);
+    else st_link_body<false>(ltabB, nullptr, nullptr, skewB, wtabB, flagsB, s, (wx & 1) != 0, (wx & 2) != 0);
 }
 
 // exclusive scan of the waves' chunk counts (one block); flags[1] = total, flags[2] = longest wave
@@ -299,14 +283,7 @@ __device__ __forceinline__ void st_scan_body(int32_t nwaves, int32_t *__restrict
     int run = part[t];
     for (int i = t * per; i < (t + 1) * per && i < nwaves; ++i) { wtab[(size_t)i * 4] = run; run += wtab[(size_t)i * 4 + 2]; }
 }
-__global__ void __launch_bounds__(kThreads)
-k_st_scan(int32_t nwaves, int32_t *__restrict__ wtab, int32_t *__restrict__ flags)
-{
-    __shared__ int part[kThreads];
-    __shared__ int pmax[kThreads];
-    st_scan_body(nwaves, wtab, flags, part, pmax);
-}
-// both chunk scans of an ILU(0) with one launch (block 0: forward, block 1: backward)
+// both chunk scans with one launch (block 0: forward, block 1: backward; one block: the forward schedule alone)
 __global__ void __launch_bounds__(kThreads)
 k_st_scan_pair(int32_t nwaves, int32_t *__restrict__ wtabF, int32_t *__restrict__ flagsF, int32_t *__restrict__ wtabB, int32_t *__restrict__ flagsB)
 {
@@ -1416,9 +1393,8 @@ int st_make_csr(hipStream_t st, int32_t n, const PackedSweep &pl, const PackedSw
     return ILUPP_OK;
 }
 
-void st_unpack(hipStream_t st, const DevMat &M, const Schedule &sch, const PackedSweep &ps)
+void st_unpack(hipStream_t st, const DevMat &M, const PackedSweep &ps)
 {
-    (void)sch;
     const dim3 grid((unsigned)(ps.nwg * 4), (unsigned)((ps.max_chunks + 7) / 8));
     if ((SweepKind)ps.kind == SWEEP_FWD_LAST_ASC)
         hipLaunchKernelGGL((k_st_unpack<SWEEP_FWD_LAST_ASC>), grid, dim3(512), 0, st, M.ptr, M.idx, M.val, ps.wtab, ps.ltab,
@@ -1434,52 +1410,12 @@ void st_unpack(hipStream_t st, const DevMat &M, const Schedule &sch, const Packe
 // ---------------------------------------------------------------------------------------------
 // the step-major exchange of a schedule: ordinals of the exported lanes of each workgroup, the workgroup's row length and steps
 static constexpr int kStXAlign = 16;          // first step of a workgroup's exchange rows: its first step rounded down to this
-__global__ void __launch_bounds__(kThreads)
-k_st_xch_layout(const int32_t *__restrict__ exported, const int32_t *__restrict__ ltab, const int32_t *__restrict__ wtab,
-                int32_t *__restrict__ xe, int32_t *__restrict__ xw, int32_t *__restrict__ xsz, int32_t *__restrict__ flags)
-{
-    __shared__ int s_cnt[4], s_pairs;
-    const int wg = blockIdx.x, t = threadIdx.x, wv = t >> 6;
-    const int slot = wg * kThreads + t;
-    const int32_t *T = ltab + (size_t)slot * kStTab;
-    const bool ex = T[ST_CNT] > 0 && exported[slot] != 0;
-    // the courier wave of the kernels serves at most 64 (lane, dependency) pairs that come from earlier workgroups
-    __shared__ int s_phase[16];
-    if (t == 0) s_pairs = 0;
-    if (t < 16) s_phase[t] = 0;
-    __syncthreads();
-    // (the vector wave of st_wave.hip serves at most 16 lanes per skew modulo 16: flags[9] & 8, as in k_st_xch_pair)
-    if (T[ST_CNT] > 0 && atomicAdd(&s_phase[T[ST_SKEW] & 15], 1) >= 16) atomicOr(&flags[9], 8);
-    int ng = 0;
-    for (int j = 0; j < 3; ++j) ng += (j < T[ST_ND] && T[ST_CNT] > 0 && (T[ST_SRC + j] & 3) == ST_GHOST) ? 1 : 0;
-    if (ng) atomicAdd(&s_pairs, ng);
-    const unsigned long long bal = __builtin_amdgcn_ballot_w64(ex);
-    if ((t & 63) == 0) s_cnt[wv] = __popcll(bal);
-    __syncthreads();
-    int before = 0;
-    for (int q = 0; q < wv; ++q) before += s_cnt[q];
-    xe[slot] = ex ? before + (int)__builtin_amdgcn_mbcnt_hi((unsigned)(bal >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)bal, 0)) : -1;
-    if (t == 0) {
-        const int total = s_cnt[0] + s_cnt[1] + s_cnt[2] + s_cnt[3];
-        const int E = (total + 15) & ~15;
-        int tlo = 0x7fffffff, thi = -0x7fffffff;
-        for (int q = 0; q < 4; ++q) {
-            const int a = wtab[(size_t)(wg * 4 + q) * 4 + 1], b = wtab[(size_t)(wg * 4 + q) * 4 + 2];
-            if (b > 0) { tlo = min(tlo, a); thi = max(thi, a + b); }
-        }
-        if (thi <= tlo) { tlo = 0; thi = 0; }
-        tlo &= ~(kStXAlign - 1);
-        xw[wg * 4 + 0] = E; xw[wg * 4 + 1] = tlo; xw[wg * 4 + 2] = thi - tlo; xw[wg * 4 + 3] = 0;
-        xsz[wg] = E * (thi - tlo);
-        if (s_pairs > 64) atomicOr(&flags[0], 32);
-        if (total > 64) atomicOr(&flags[9], 4);          // (st_wave.hip's courier exports with one store instruction per step)
-    }
-}
-// the exchange layouts of BOTH schedules of an ILU(0) and the offsets of their rows with one launch: block (w, d) lays out workgroup w
-// of direction d (k_st_xch_layout's job); the last block of a direction to finish scans that direction's sizes (an atomic ticket;
-// sizes through agent-scope stores and loads: the blocks sit on different XCDs) and writes the row offsets and tot[2 d] = the offset
-// of the last workgroup, tot[2 d + 1] = its size.  (Before: a launch for the layout, two for the scan, one for the offsets, per direction
-// -- 5 us each in an analysis of 450.)
+// the exchange layouts of the schedules of an analysis (grid (nwg, 2): both; (nwg, 1): the forward one, F, alone) and the offsets of
+// their rows with one launch: block (w, d) lays out workgroup w of direction d (flags[0] & 32: more than the 64 (lane, dependency) pairs
+// from earlier workgroups that the kernels' courier wave serves); the last block of a direction to finish scans that direction's sizes
+// (an atomic ticket, flags[11], which st_structure has cleared; sizes through agent-scope stores and loads: the blocks sit on different
+// XCDs) and writes the row offsets and tot[2 d] = the offset of the last workgroup, tot[2 d + 1] = its size.  (Before: a launch for the
+// layout, two for the scan, one for the offsets, per direction -- 5 us each in an analysis of 450.)
 struct StXchArgs { const int32_t *exported, *ltab, *wtab; int32_t *xe, *xw, *xsz, *flags; };
 __global__ void __launch_bounds__(kThreads)
 k_st_xch_pair(StXchArgs F, StXchArgs B, int32_t nwg, int32_t *__restrict__ tot)
@@ -1543,11 +1479,6 @@ k_st_xch_pair(StXchArgs F, StXchArgs B, int32_t nwg, int32_t *__restrict__ tot)
         run += c;
     }
 }
-__global__ void k_st_xch_rows(int32_t nwg, const int32_t *__restrict__ xoff, int32_t *__restrict__ xw)
-{
-    const int w = blockIdx.x * blockDim.x + threadIdx.x;
-    if (w < nwg) xw[w * 4 + 3] = xoff[w];
-}
 
 static void st_structure(hipStream_t st, const Schedule &sch, PackedSweep *ps, int kind)
 {
@@ -1569,16 +1500,135 @@ static void st_pack_values(hipStream_t st, const DevMat &A, PackedSweep *pl, Pac
                        pl->flags, groups);
 }
 
+// ---- the steps every static analysis takes, in this order (st_analyse_ilu0, st_analyse_pair, ichol0_analyse_st).  pu == nullptr: an
+// analysis of the forward schedule alone (IChol0's factor kernel); the launches then have an extent of 1 and read no backward argument
+static bool st_off()                 // ILUPP_NO_PACKED / ILUPP_NO_STATIC: no object gets the static form
+{
+    static const bool off = getenv("ILUPP_NO_PACKED") != nullptr || getenv("ILUPP_NO_STATIC") != nullptr;
+    return off;
+}
+static bool st_dbg()
+{
+    static const bool dbg = getenv("ILUPP_DEBUG") != nullptr;
+    return dbg;
+}
+
+static StTplArgs st_tpl_args(const DevMat &M, const Schedule &sch, const PackedSweep &ps)
+{
+    StTplArgs a;
+    a.ptr = M.ptr; a.idx = M.idx; a.B = sch.B; a.nb = sch.nb; a.start = sch.start; a.blk2slot = sch.blk2slot; a.sfirst = sch.sfirst;
+    a.scount = sch.scount; a.exported = sch.exported; a.ltab = ps.ltab; a.flags = ps.flags;
+    return a;
+}
+static void st_templates(hipStream_t st, const StTplArgs &f, const StTplArgs *b, int nwg)
+{
+    hipLaunchKernelGGL(k_st_template_pair, dim3((unsigned)nwg, b ? 2 : 1), dim3(kThreads), 0, st, f, b ? *b : f);
+}
+template <bool PROVE>
+static void st_link(hipStream_t st, PackedSweep *pl, PackedSweep *pu, int32_t wx)
+{
+    const PackedSweep &b = pu ? *pu : *pl;
+    hipLaunchKernelGGL(k_st_link_pair<PROVE>, dim3((unsigned)pl->nwg, pu ? 2 : 1), dim3(kThreads), 0, st, pl->ltab, b.ltab, b.uslot, pl->skew,
+                       b.skew, pl->wtab, b.wtab, pl->flags, b.flags, wx);
+}
+static void st_scan(hipStream_t st, PackedSweep *pl, PackedSweep *pu)
+{
+    const PackedSweep &b = pu ? *pu : *pl;
+    hipLaunchKernelGGL(k_st_scan_pair, dim3(pu ? 2 : 1), dim3(kThreads), 0, st, pl->nwg * 4, pl->wtab, pl->flags, b.wtab, b.flags);
+}
+// the exchange tables of the schedules and the layout kernel's work array: the workgroups' sizes of both directions, then tot[4]
+static int32_t *st_xch_alloc(PackedSweep *pl, PackedSweep *pu)
+{
+    const size_t nwg = (size_t)pl->nwg;
+    int32_t *xsz = nullptr;
+    ILUPP_HIP(pool_malloc(&xsz, sizeof(int32_t) * (nwg * 2 + 4)));
+    for (PackedSweep *p : {pl, pu}) {
+        if (!p) continue;
+        ILUPP_HIP(pool_malloc(&p->xe, sizeof(int32_t) * nwg * kThreads));
+        ILUPP_HIP(pool_malloc(&p->xw, sizeof(int32_t) * nwg * 4));
+    }
+    return xsz;
+}
+static void st_xch_layout(hipStream_t st, const Schedule &fwd, const Schedule *bwd, PackedSweep *pl, PackedSweep *pu, int32_t *xsz)
+{
+    const int nwg = pl->nwg;
+    const Schedule *ss[2] = {&fwd, bwd ? bwd : &fwd};
+    const PackedSweep *pp[2] = {pl, pu ? pu : pl};
+    StXchArgs xa[2];
+    for (int d = 0; d < 2; ++d) {
+        xa[d].exported = ss[d]->exported; xa[d].ltab = pp[d]->ltab; xa[d].wtab = pp[d]->wtab;
+        xa[d].xe = pp[d]->xe; xa[d].xw = pp[d]->xw; xa[d].xsz = xsz + (size_t)d * nwg; xa[d].flags = pp[d]->flags;
+    }
+    hipLaunchKernelGGL(k_st_xch_pair, dim3((unsigned)nwg, pu ? 2 : 1), dim3(kThreads), 0, st, xa[0], xa[1], (int32_t)nwg, xsz + (size_t)nwg * 2);
+}
+// what an analysis waits for: the flags of its schedules and the exchange totals (then the work array goes back)
+static void st_read_back(hipStream_t st, const PackedSweep *pl, const PackedSweep *pu, int32_t *xsz, int32_t hl[12], int32_t hu[12], int32_t xtot[4])
+{
+    ILUPP_HIP(d2h_async(st, xtot, xsz + (size_t)pl->nwg * 2, (pu ? 4 : 2) * sizeof(int32_t)));
+    ILUPP_HIP(d2h_async(st, hl, pl->flags, 12 * sizeof(int32_t)));
+    if (pu) ILUPP_HIP(d2h_async(st, hu, pu->flags, 12 * sizeof(int32_t)));
+    ILUPP_HIP(stream_sync(st));
+    ILUPP_HIP(pool_free(xsz));
+}
+// May the static kernels run what the analysis found?  hl, hu: the flags of the two schedules (hu == nullptr: one schedule);
+// `what`: who asks, for ILUPP_DEBUG
+static bool st_accept(const char *what, int64_t n, int nwg, const int32_t *hl, const int32_t *hu)
+{
+    // row slots of the chunks against rows: lines of 8 rows in a 16 x 16 patch (30 steps of skew) are 4.75 slots per row, and
+    // still 400 times faster than what the other generations make of 90 000 such lines
+    const int64_t lim = 6 * n + 64 * 4 * (int64_t)nwg;
+    const int32_t longest = hu && hu[2] > hl[2] ? hu[2] : hl[2];
+    bool ok = !hl[0] && hl[1] > 0 && (int64_t)hl[1] * 64 <= lim && hl[1] + 4 * nwg < kStMaxChunks;
+    if (hu) ok = ok && !hu[0] && !hu[3] && hu[1] > 0 && (int64_t)hu[1] * 64 <= lim && hu[1] + 4 * nwg < kStMaxChunks;
+    // (the exchange layout is indexed with 32 bits: at most 256 exported lanes x the steps of a workgroup, each)
+    ok = ok && (int64_t)nwg * kThreads * ((int64_t)longest + 2 * kStXAlign) <= 0x7fffffffLL;
+    if (!ok && st_dbg()) {
+        if (hu) fprintf(stderr, "[ilupp] %s: structure rejected (flags %d %d link %d, %d %d chunks)\n", what, hl[0], hu[0], hu[3], hl[1], hu[1]);
+        else fprintf(stderr, "[ilupp] %s: structure rejected (flags %d, %d chunks)\n", what, hl[0], hl[1]);
+    }
+    return ok;
+}
+// records, level-major vectors and exchange buffers for the sizes the analysis found (xtot: offset and size of each direction's last
+// workgroup).  One schedule: the records and the exchange buffer, which is all the factor kernel touches
+static void st_alloc(PackedSweep *pl, PackedSweep *pu, const int32_t *hl, const int32_t *hu, const int32_t *xtot)
+{
+    const size_t slots = (size_t)hl[1] + 4 * (size_t)pl->nwg;          // one spare chunk per wave: where waves / lanes without a row at a step store
+    pl->nchunks = hl[1]; pl->max_chunks = hl[2];
+    pl->xch_len = (int64_t)xtot[0] + xtot[1] + 64;
+    ILUPP_HIP(pool_malloc(&pl->pk, slots * 2048));
+    if (pu) {
+        pu->nchunks = hu[1]; pu->max_chunks = hu[2];
+        pu->xch_len = (int64_t)xtot[2] + xtot[3] + 64;
+        ILUPP_HIP(pool_malloc(&pu->pk, slots * 2048));                 // (the forward schedule's order: see k_sptrsv_st)
+        // vectors travel level-major: the right-hand side and the intermediate vector in the L sweep's order (pl->ybuf, in place), the
+        // result in the U sweep's (pu->xlm)
+        ILUPP_HIP(pool_malloc(&pl->ybuf, sizeof(double) * 64 * slots));
+        ILUPP_HIP(pool_malloc(&pu->xlm, sizeof(double) * 64 * ((size_t)pu->nchunks + 4 * (size_t)pl->nwg)));
+        pu->y_chunks = (int64_t)slots;
+    }
+    pl->built = true;
+    ILUPP_HIP(pool_malloc(&pl->xch, sizeof(double) * (size_t)pl->xch_len));
+    if (pu) ILUPP_HIP(pool_malloc(&pu->xch, sizeof(double) * (size_t)pu->xch_len));
+}
+// the two sweeps may run: which kernels (wave exchange: flags[9] clear but for its 8, which only declines the vector wave)
+static void st_close(PackedSweep *pl, PackedSweep *pu, const int32_t *hl, const int32_t *hu)
+{
+    pl->valid = pu->valid = true;
+    pl->stat = pu->stat = true;
+    pl->wx = (hl[9] & ~8) == 0; pu->wx = (hu[9] & ~8) == 0;
+    pl->vec_ok = pl->wx && (hl[9] & 8) == 0; pu->vec_ok = pu->wx && (hu[9] & 8) == 0;
+    pu->linked = true;
+}
+
 // The whole static analysis of an ILU(0): true when the factor kernel and both sweeps can run from lane tables
 // (pl, pu, f then complete, the values of A packed); false leaves the three objects released.
 bool st_analyse_ilu0(hipStream_t st, const DevMat &A, const Schedule &fwd, const Schedule &bwd, PackedSweep *pl,
                      PackedSweep *pu, FactorLM *f, SideJoin *join, const GridDims *grid)
 {
     pl->release(); pu->release(); f->release();
-    static const bool off = getenv("ILUPP_NO_PACKED") != nullptr ||
-                            getenv("ILUPP_CLASSIC_ANALYSIS") != nullptr || getenv("ILUPP_NO_STATIC") != nullptr;
-    static const bool dbg = getenv("ILUPP_DEBUG") != nullptr;
-    if (off || A.nnz > 7 * (int64_t)A.n || A.nnz < 16 || fwd.nslots < kThreads || fwd.nslots != bwd.nslots || !A.val) return false;
+    static const bool classic = getenv("ILUPP_CLASSIC_ANALYSIS") != nullptr;
+    const bool dbg = st_dbg();
+    if (st_off() || classic || A.nnz > 7 * (int64_t)A.n || A.nnz < 16 || fwd.nslots < kThreads || fwd.nslots != bwd.nslots || !A.val) return false;
     const int nwg = fwd.nslots / kThreads;
     const int nslots = fwd.nslots;
     st_structure(st, fwd, pl, (int)SWEEP_FWD_LAST_ASC);
@@ -1591,23 +1641,17 @@ bool st_analyse_ilu0(hipStream_t st, const DevMat &A, const Schedule &fwd, const
         linked_by_grid = grid_lane_tables(st, *grid, fwd, bwd, pl->ltab, pu->ltab, pl->flags, pu->flags, pu->uslot, pl->skew, pu->skew,
                                           pl->wtab, pu->wtab, st_wx_on());
     } else {
-        StTplArgs tf, tb;
-        tf.B = fwd.B; tf.nb = fwd.nb; tf.start = fwd.start; tf.blk2slot = fwd.blk2slot; tf.sfirst = fwd.sfirst; tf.scount = fwd.scount;
-        tf.exported = fwd.exported; tf.ltab = pl->ltab; tf.flags = pl->flags;
-        tb.B = bwd.B; tb.nb = bwd.nb; tb.start = bwd.start; tb.blk2slot = bwd.blk2slot; tb.sfirst = bwd.sfirst; tb.scount = bwd.scount;
-        tb.exported = bwd.exported; tb.ltab = pu->ltab; tb.flags = pu->flags;
-        hipLaunchKernelGGL(k_st_template_pair, dim3((unsigned)nwg, 2), dim3(kThreads), 0, st, A.ptr, A.idx, tf, tb);
+        const StTplArgs tf = st_tpl_args(A, fwd, *pl), tb = st_tpl_args(A, bwd, *pu);
+        st_templates(st, tf, &tb, nwg);
         pu->built = true;
         lm_link_factor(st, fwd, bwd, pu);               // forward slot -> backward slot of the same chain (flags[3] when there is none)
     }
-    if (!linked_by_grid)
-        hipLaunchKernelGGL(k_st_link_pair, dim3((unsigned)nwg, 2), dim3(kThreads), 0, st, pl->ltab, pu->ltab, pu->uslot, pl->skew, pu->skew,
-                           pl->wtab, pu->wtab, pl->flags, pu->flags, st_wx_on() ? 1 : 0);
+    if (!linked_by_grid) st_link<true>(st, pl, pu, st_wx_on() ? 3 : 2);
     // (a box grid in 16 x 16 patches: one closed-form launch below instead of the scan, the clears, the slot maps, k_st_scat and the
     // exchange layout -- grid.hip: k_grid_scat; ILUPP_GRID_SCAT=0: the general kernels on the grid's lane tables)
     static const bool grid_scat_on = []() { const char *e = getenv("ILUPP_GRID_SCAT"); return !(e && atoi(e) == 0); }();
     const bool scat_by_grid = linked_by_grid && grid_scat_on && getenv("ILUPP_SD_VERIFY") == nullptr;
-    if (!scat_by_grid) hipLaunchKernelGGL(k_st_scan_pair, dim3(2), dim3(kThreads), 0, st, nwg * 4, pl->wtab, pl->flags, pu->wtab, pu->flags);
+    if (!scat_by_grid) st_scan(st, pl, pu);
     int32_t *inv = nullptr;
     ILUPP_HIP(pool_malloc(&inv, sizeof(int32_t) * (size_t)nslots));
     ILUPP_HIP(pool_malloc(&pu->ysrc, sizeof(int32_t) * (size_t)nslots));
@@ -1633,26 +1677,16 @@ bool st_analyse_ilu0(hipStream_t st, const DevMat &A, const Schedule &fwd, const
         if (try_direct) st_direct_verify(st, A, fwd, pl, pu, pl->flags + 8);
     }
     // the exchange layouts of both schedules; their sizes come back with the flags (one wait for all)
-    int32_t xtot[2][2];
-    int32_t *xsz = nullptr;
+    int32_t xtot[4];
     int32_t hl[12], hu[12];
+    int32_t *xsz = st_xch_alloc(pl, pu);
     {
-        ILUPP_HIP(pool_malloc(&xsz, sizeof(int32_t) * ((size_t)nwg * 2 + 4)));
-        PackedSweep *pp[2] = {pl, pu};
-        const Schedule *ss[2] = {&fwd, &bwd};
-        StXchArgs xa[2];
-        for (int d = 0; d < 2; ++d) {
-            ILUPP_HIP(pool_malloc(&pp[d]->xe, sizeof(int32_t) * (size_t)nslots));
-            ILUPP_HIP(pool_malloc(&pp[d]->xw, sizeof(int32_t) * (size_t)nwg * 4));
-            xa[d].exported = ss[d]->exported; xa[d].ltab = pp[d]->ltab; xa[d].wtab = pp[d]->wtab;
-            xa[d].xe = pp[d]->xe; xa[d].xw = pp[d]->xw; xa[d].xsz = xsz + (size_t)d * nwg; xa[d].flags = pp[d]->flags;
-        }
         int32_t *tot = xsz + (size_t)nwg * 2;
         if (scat_by_grid)
             grid_scat_tables(st, *grid, fwd, pl->ltab, pu->ltab, pl->wtab, pu->wtab, pu->ysrc, f->xbase + nslots, pl->xe, pu->xe, pl->xw, pu->xw,
                              pl->flags, pu->flags, tot);
         else
-            hipLaunchKernelGGL(k_st_xch_pair, dim3((unsigned)nwg, 2), dim3(kThreads), 0, st, xa[0], xa[1], (int32_t)nwg, tot);
+            st_xch_layout(st, fwd, &bwd, pl, pu, xsz);
         D2HItem items[4];
         items[0] = {f->chk_xtot, tot, 4 * sizeof(int32_t)};
         items[1] = {f->chk_hl, pl->flags, sizeof(f->chk_hl)};
@@ -1677,41 +1711,20 @@ bool st_analyse_ilu0(hipStream_t st, const DevMat &A, const Schedule &fwd, const
         if (f->spec) {
             for (int i = 0; i < 12; ++i) hl[i] = hu[i] = 0;
             hl[1] = hu[1] = (int32_t)pn; hl[2] = hu[2] = pm;
-            xtot[0][0] = xtot[1][0] = (int32_t)px; xtot[0][1] = xtot[1][1] = pxl;
+            xtot[0] = xtot[2] = (int32_t)px; xtot[1] = xtot[3] = pxl;
             f->pred[0] = (int32_t)pn; f->pred[1] = pm; f->pred[2] = (int32_t)px; f->pred[3] = pxl;
         } else {
             ILUPP_HIP(stream_sync(st));
             for (int i = 0; i < 12; ++i) { hl[i] = f->chk_hl[i]; hu[i] = f->chk_hu[i]; }
-            for (int i = 0; i < 4; ++i) (&xtot[0][0])[i] = f->chk_xtot[i];
+            for (int i = 0; i < 4; ++i) xtot[i] = f->chk_xtot[i];
         }
     }
     ILUPP_HIP(pool_free(inv)); ILUPP_HIP(pool_free(xsz));
-    // row slots of the chunks against rows: lines of 8 rows in a 16 x 16 patch (30 steps of skew) are 4.75 slots per row, and
-    // still 400 times faster than what the other generations make of 90 000 such lines
-    const int64_t lim = 6 * (int64_t)A.n + 64 * 4 * (int64_t)nwg;
-    if (hl[0] || hu[0] || hu[3] || hl[1] <= 0 || hu[1] <= 0 || (int64_t)hl[1] * 64 > lim || (int64_t)hu[1] * 64 > lim ||
-        hl[1] + 4 * nwg >= kStMaxChunks || hu[1] + 4 * nwg >= kStMaxChunks ||
-        // (the exchange layout is indexed with 32 bits: at most 256 exported lanes x the steps of a workgroup, each)
-        (int64_t)nwg * kThreads * ((int64_t)(hl[2] > hu[2] ? hl[2] : hu[2]) + 2 * kStXAlign) > 0x7fffffffLL) {
-        if (dbg) fprintf(stderr, "[ilupp] static analysis: structure rejected (flags %d %d link %d, %d %d chunks)\n", hl[0], hu[0], hu[3], hl[1], hu[1]);
+    if (!st_accept("static analysis", A.n, nwg, hl, hu)) {
         pl->release(); pu->release(); f->release();
         return false;
     }
-    pl->nchunks = hl[1]; pl->max_chunks = hl[2];
-    pu->nchunks = hu[1]; pu->max_chunks = hu[2];
-    // one spare chunk per wave each: where waves / lanes without a row at a step store
-    ILUPP_HIP(pool_malloc(&pl->pk, (size_t)(pl->nchunks + 4 * nwg) * 2048));
-    ILUPP_HIP(pool_malloc(&pu->pk, (size_t)(pl->nchunks + 4 * nwg) * 2048));      // (the forward schedule's order: see k_sptrsv_st)
-    pl->built = true;
-    // vectors travel level-major: the right-hand side and the intermediate vector in the L sweep's order (pl->ybuf, in place), the
-    // result in the U sweep's (pu->xlm)
-    ILUPP_HIP(pool_malloc(&pl->ybuf, sizeof(double) * 64 * (size_t)(pl->nchunks + 4 * nwg)));
-    ILUPP_HIP(pool_malloc(&pu->xlm, sizeof(double) * 64 * (size_t)(pu->nchunks + 4 * nwg)));
-    pu->y_chunks = pl->nchunks + 4 * nwg;
-    pl->xch_len = (int64_t)xtot[0][0] + xtot[0][1] + 64;
-    pu->xch_len = (int64_t)xtot[1][0] + xtot[1][1] + 64;
-    ILUPP_HIP(pool_malloc(&pl->xch, sizeof(double) * (size_t)pl->xch_len));
-    ILUPP_HIP(pool_malloc(&pu->xch, sizeof(double) * (size_t)pu->xch_len));
+    st_alloc(pl, pu, hl, hu, xtot);
     f->direct = try_direct && hl[8] == 0;
     f->wxf = f->direct && (hl[9] & ~8) == 0 && (hu[9] & ~8) == 0 && hl[10] == 0 && st_wx_on() && getenv("ILUPP_NO_WXF") == nullptr;
     if (!f->direct) {
@@ -1727,22 +1740,17 @@ bool st_analyse_ilu0(hipStream_t st, const DevMat &A, const Schedule &fwd, const
     } else if (dbg) {
         fprintf(stderr, "[ilupp] static analysis: %d+%d chunks, direct feed\n", hl[1], hu[1]);
     }
-    pl->valid = pu->valid = true;
-    pl->stat = pu->stat = true;
-    pl->wx = (hl[9] & ~8) == 0; pu->wx = (hu[9] & ~8) == 0;
-    pl->vec_ok = pl->wx && (hl[9] & 8) == 0; pu->vec_ok = pu->wx && (hu[9] & 8) == 0;
+    st_close(pl, pu, hl, hu);
     if (dbg) fprintf(stderr, "[ilupp] static analysis: wave-exchange kernels: forward %s, backward %s\n", pl->wx ? "yes" : "no", pu->wx ? "yes" : "no");
-    pu->linked = true;
     f->built = true;
     f->stat = true;
     f->values_packed = !f->direct;
     return true;
 }
 
-int ilu0_numeric_st(hipStream_t st, const DevMat &A, const Schedule &fwd, PackedSweep *pl, PackedSweep *pu, FactorLM *f,
-                    int32_t *d_ctrl, float *kernel_ms, hipEvent_t e0, hipEvent_t e1)
+int ilu0_numeric_st(hipStream_t st, const DevMat &A, PackedSweep *pl, PackedSweep *pu, FactorLM *f, int32_t *d_ctrl, float *kernel_ms,
+                    hipEvent_t e0, hipEvent_t e1)
 {
-    (void)fwd;
     pl->fmt = pu->fmt = 0;                               // (the factor kernels below write records by template position)
     if (f->direct && f->wxf && (uint64_t)(pl->nchunks + 4 * (int64_t)pl->nwg) * 2048u < 0xfff00000ull)
         return ilu0_numeric_wx(st, A, pl, pu, d_ctrl, kernel_ms, e0, e1);
@@ -1782,14 +1790,18 @@ int ilu0_numeric_st(hipStream_t st, const DevMat &A, const Schedule &fwd, Packed
     return ILUPP_OK;
 }
 
-static void st_solo_attr_T()
+// one workgroup per CU: with 40 KB of LDS three would fit, and the dispatcher does put several on one CU while others stay
+// empty; the steps of two schedules on the same four SIMDs take turns.  The unused dynamic LDS makes the workgroup too big
+// for a neighbour.
+static void st_solo_attr()
 {
     static std::once_flag once[64];      // once per device
     int dev = 0;
     ILUPP_HIP(hipGetDevice(&dev));
     std::call_once(once[dev & 63], [] {
-        ILUPP_HIP(hipFuncSetAttribute((const void *)k_sptrsv_st<1, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kStSoloLds));
-        ILUPP_HIP(hipFuncSetAttribute((const void *)k_sptrsv_st<-1, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kStSoloLds));
+        for (const void *k : {(const void *)k_sptrsv_st<1, false>, (const void *)k_sptrsv_st<-1, false>, (const void *)k_sptrsv_st<1, true>,
+                              (const void *)k_sptrsv_st<-1, true>})
+            ILUPP_HIP(hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kStSoloLds));
     });
 }
 
@@ -1808,10 +1820,9 @@ void st_vec_from_lm(hipStream_t st, const PackedSweep &ps, double *nat)
 
 // One sweep of an apply.  Forward: `rhs` (natural order) -> the intermediate vector in `ypk_out` (the forward sweep's ybuf, in the
 // forward sweep's level-major order); backward: `ypk_in` (the same buffer) -> the result in `out` (natural order).
-int sptrsv_st(hipStream_t st, const PackedSweep &ps, const Schedule &sch, int32_t n, const double *rhs, double *out,
-              int32_t *d_ticket, int32_t *d_err, double *ypk_out, const double *ypk_in, const int32_t *ysrc)
+int sptrsv_st(hipStream_t st, const PackedSweep &ps, int32_t n, const double *rhs, double *out, int32_t *d_ticket, int32_t *d_err,
+              double *ypk_out, const double *ypk_in, const int32_t *ysrc)
 {
-    (void)sch;
     if (ps.fmt >= 1) return sptrsv_wx(st, ps, n, rhs, out, d_ticket, d_err, ypk_out, ypk_in, ysrc);
     const bool fwd = ps.kind == (int)SWEEP_FWD_LAST_ASC;
     double *lml = fwd ? ypk_out : const_cast<double *>(ypk_in);        // level-major, forward order
@@ -1824,30 +1835,16 @@ int sptrsv_st(hipStream_t st, const PackedSweep &ps, const Schedule &sch, int32_
     a.xe = ps.xe; a.xw = ps.xw; a.xch = ps.xch; a.ticket = d_ticket; a.err = d_err;
     fill_u64(st, reinterpret_cast<unsigned long long *>(ps.xch), ps.xch_len, kSentinel);
     const dim3 grid((unsigned)ps.nwg);
-    // one workgroup per CU: with 40 KB of LDS three would fit, and the dispatcher does put several on one CU while others stay
-    // empty; the steps of two schedules on the same four SIMDs take turns.  The unused dynamic LDS makes the workgroup too big
-    // for a neighbour.
-    {
-        static std::once_flag once[64];      // once per device
-        int dev = 0;
-        ILUPP_HIP(hipGetDevice(&dev));
-        std::call_once(once[dev & 63], [] {
-            ILUPP_HIP(hipFuncSetAttribute((const void *)k_sptrsv_st<1, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kStSoloLds));
-            ILUPP_HIP(hipFuncSetAttribute((const void *)k_sptrsv_st<-1, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kStSoloLds));
-        });
-    }
-    if (ps.pair) st_solo_attr_T();
+    st_solo_attr();
     if (fwd) {
-        hipLaunchKernelGGL((k_st_vec<1, true>), dim3((unsigned)(ps.nwg * 4), (unsigned)st_vec_groups(ps.max_chunks)), dim3(512), 0, st, ps.ltab, ps.wtab,
-                           const_cast<double *>(rhs), lml);
+        st_vec_to_lm(st, ps, rhs, lml);
         // (a pair of stored factors: the forward factor has a diagonal of its own)
         if (ps.pair) hipLaunchKernelGGL((k_sptrsv_st<1, true>), grid, dim3(kStWgThreads), kStSoloLds, st, a);
         else hipLaunchKernelGGL((k_sptrsv_st<1, false>), grid, dim3(kStWgThreads), kStSoloLds, st, a);
     } else {
         if (ps.pair && ps.desc) hipLaunchKernelGGL((k_sptrsv_st<-1, true>), grid, dim3(kStWgThreads), kStSoloLds, st, a);
         else hipLaunchKernelGGL((k_sptrsv_st<-1, false>), grid, dim3(kStWgThreads), kStSoloLds, st, a);
-        hipLaunchKernelGGL((k_st_vec<-1, false>), dim3((unsigned)(ps.nwg * 4), (unsigned)st_vec_groups(ps.max_chunks)), dim3(512), 0, st, ps.ltab, ps.wtab,
-                           out, ps.xlm);
+        st_vec_from_lm(st, ps, out);
     }
     ILUPP_HIP(hipGetLastError());
     return ILUPP_OK;
@@ -1979,79 +1976,34 @@ bool st_analyse_pair(hipStream_t st, int32_t n, const DevMat &Lrow, const DevMat
                      PackedSweep *pl, PackedSweep *pu, bool bwd_desc)
 {
     pl->release(); pu->release();
-    static const bool off = getenv("ILUPP_NO_PACKED") != nullptr || getenv("ILUPP_NO_STATIC") != nullptr;
-    static const bool dbg = getenv("ILUPP_DEBUG") != nullptr;
-    if (off || Lrow.nnz > 4 * (int64_t)n || Urow.nnz > 4 * (int64_t)n || n < 16 || fwd.nslots < kThreads || fwd.nslots != bwd.nslots ||
+    const bool dbg = st_dbg();
+    if (st_off() || Lrow.nnz > 4 * (int64_t)n || Urow.nnz > 4 * (int64_t)n || n < 16 || fwd.nslots < kThreads || fwd.nslots != bwd.nslots ||
         !Lrow.val || !Urow.val || !fwd.exported || !bwd.exported)
         return false;
     const int nwg = fwd.nslots / kThreads;
     const int nslots = fwd.nslots;
     st_structure(st, fwd, pl, (int)SWEEP_FWD_LAST_ASC);
     st_structure(st, bwd, pu, (int)SWEEP_BWD_FIRST_ASC);
-    hipLaunchKernelGGL((k_st_template<1>), dim3((unsigned)nwg), dim3(kThreads), 0, st, Lrow.ptr, Lrow.idx, fwd.B, fwd.nb, fwd.start,
-                       fwd.blk2slot, fwd.sfirst, fwd.scount, fwd.exported, pl->ltab, pl->flags);
-    hipLaunchKernelGGL((k_st_template<-1>), dim3((unsigned)nwg), dim3(kThreads), 0, st, Urow.ptr, Urow.idx, bwd.B, bwd.nb, bwd.start,
-                       bwd.blk2slot, bwd.sfirst, bwd.scount, bwd.exported, pu->ltab, pu->flags);
+    const StTplArgs tf = st_tpl_args(Lrow, fwd, *pl), tb = st_tpl_args(Urow, bwd, *pu);
+    st_templates(st, tf, &tb, nwg);
     pu->built = true;
     lm_link_factor(st, fwd, bwd, pu);
-    hipLaunchKernelGGL((k_st_link<false>), dim3((unsigned)nwg), dim3(kThreads), 0, st, pl->ltab, static_cast<const int32_t *>(nullptr),
-                       static_cast<const int32_t *>(nullptr), pl->skew, pl->wtab, pl->flags, st_wx_on() ? 1 : 0);
-    hipLaunchKernelGGL((k_st_link<false>), dim3((unsigned)nwg), dim3(kThreads), 0, st, pu->ltab, static_cast<const int32_t *>(nullptr),
-                       static_cast<const int32_t *>(nullptr), pu->skew, pu->wtab, pu->flags, st_wx_on() ? 3 : 0);
-    hipLaunchKernelGGL(k_st_scan, dim3(1), dim3(kThreads), 0, st, nwg * 4, pl->wtab, pl->flags);
-    hipLaunchKernelGGL(k_st_scan, dim3(1), dim3(kThreads), 0, st, nwg * 4, pu->wtab, pu->flags);
-    int32_t xtot[2][2];
-    int32_t *xsz = nullptr;
-    void *tmp2 = nullptr;
-    {
-        ILUPP_HIP(pool_malloc(&xsz, sizeof(int32_t) * (size_t)nwg * 4));
-        PackedSweep *pp[2] = {pl, pu};
-        const Schedule *ss[2] = {&fwd, &bwd};
-        size_t tb2 = 0;
-        ILUPP_HIP(hipcub::DeviceScan::ExclusiveSum(nullptr, tb2, xsz, xsz + nwg, nwg, st));
-        ILUPP_HIP(pool_malloc(&tmp2, tb2));
-        for (int d = 0; d < 2; ++d) {
-            int32_t *sz = xsz + 2 * d * nwg, *offp = sz + nwg;
-            ILUPP_HIP(pool_malloc(&pp[d]->xe, sizeof(int32_t) * (size_t)nslots));
-            ILUPP_HIP(pool_malloc(&pp[d]->xw, sizeof(int32_t) * (size_t)nwg * 4));
-            hipLaunchKernelGGL(k_st_xch_layout, dim3((unsigned)nwg), dim3(kThreads), 0, st, ss[d]->exported, pp[d]->ltab, pp[d]->wtab,
-                               pp[d]->xe, pp[d]->xw, sz, pp[d]->flags);
-            ILUPP_HIP(hipcub::DeviceScan::ExclusiveSum(tmp2, tb2, sz, offp, nwg, st));
-            hipLaunchKernelGGL(k_st_xch_rows, dim3((unsigned)((nwg + 255) / 256)), dim3(256), 0, st, nwg, offp, pp[d]->xw);
-            ILUPP_HIP(d2h_async(st, &xtot[d][0], offp + (nwg - 1), sizeof(int32_t)));
-            ILUPP_HIP(d2h_async(st, &xtot[d][1], sz + (nwg - 1), sizeof(int32_t)));
-        }
-    }
-    int32_t hl[12], hu[12];
-    ILUPP_HIP(d2h_async(st, hl, pl->flags, sizeof(hl)));
-    ILUPP_HIP(d2h_async(st, hu, pu->flags, sizeof(hu)));
-    ILUPP_HIP(stream_sync(st));
-    ILUPP_HIP(pool_free(xsz)); ILUPP_HIP(pool_free(tmp2));
-    const int64_t lim = 6 * (int64_t)n + 64 * 4 * (int64_t)nwg;
-    if (hl[0] || hu[0] || hu[3] || hl[1] <= 0 || hu[1] <= 0 || (int64_t)hl[1] * 64 > lim || (int64_t)hu[1] * 64 > lim ||
-        hl[1] + 4 * nwg >= kStMaxChunks || hu[1] + 4 * nwg >= kStMaxChunks ||
-        (int64_t)nwg * kThreads * ((int64_t)(hl[2] > hu[2] ? hl[2] : hu[2]) + 2 * kStXAlign) > 0x7fffffffLL) {
-        if (dbg) fprintf(stderr, "[ilupp] static sweeps of a factor pair: structure rejected (flags %d %d link %d, %d %d chunks)\n", hl[0], hu[0], hu[3], hl[1], hu[1]);
+    st_link<false>(st, pl, pu, st_wx_on() ? 3 : 0);
+    st_scan(st, pl, pu);
+    int32_t *xsz = st_xch_alloc(pl, pu);
+    st_xch_layout(st, fwd, &bwd, pl, pu, xsz);
+    int32_t hl[12], hu[12], xtot[4];
+    st_read_back(st, pl, pu, xsz, hl, hu, xtot);
+    if (!st_accept("static sweeps of a factor pair", n, nwg, hl, hu)) {
         pl->release(); pu->release();
         return false;
     }
-    pl->nchunks = hl[1]; pl->max_chunks = hl[2];
-    pu->nchunks = hu[1]; pu->max_chunks = hu[2];
-    ILUPP_HIP(pool_malloc(&pl->pk, (size_t)(pl->nchunks + 4 * nwg) * 2048));
-    ILUPP_HIP(pool_malloc(&pu->pk, (size_t)(pl->nchunks + 4 * nwg) * 2048));      // (both in the forward schedule's order)
-    pl->built = true;
+    st_alloc(pl, pu, hl, hu, xtot);
     // (a pair whose lanes fit the wave-exchange classes gets its records class-aligned at once: no second pass over 2 GB)
     const bool fmt1 = (hl[9] & ~8) == 0 && (hu[9] & ~8) == 0 && st_wx_on() && getenv("ILUPP_PACK_FMT0") == nullptr;
     hipLaunchKernelGGL(k_st_pack_pair, dim3((unsigned)(nwg * 4), (unsigned)((pl->max_chunks + 7) / 8)), dim3(512), 0, st, Lrow.ptr, Lrow.idx,
                        Lrow.val, Urow.ptr, Urow.idx, Urow.val, pl->ltab, pu->ltab, pu->uslot, pl->wtab, reinterpret_cast<v2d *>(pl->pk),
                        reinterpret_cast<v2d *>(pu->pk), pl->flags, fmt1 ? 1 : 0, bwd_desc ? 1 : 0);
-    ILUPP_HIP(pool_malloc(&pl->ybuf, sizeof(double) * 64 * (size_t)(pl->nchunks + 4 * nwg)));
-    ILUPP_HIP(pool_malloc(&pu->xlm, sizeof(double) * 64 * (size_t)(pu->nchunks + 4 * nwg)));
-    pu->y_chunks = pl->nchunks + 4 * nwg;
-    pl->xch_len = (int64_t)xtot[0][0] + xtot[0][1] + 64;
-    pu->xch_len = (int64_t)xtot[1][0] + xtot[1][1] + 64;
-    ILUPP_HIP(pool_malloc(&pl->xch, sizeof(double) * (size_t)pl->xch_len));
-    ILUPP_HIP(pool_malloc(&pu->xch, sizeof(double) * (size_t)pu->xch_len));
     ILUPP_HIP(pool_malloc(&pu->ysrc, sizeof(int32_t) * (size_t)nslots));
     ILUPP_HIP(hipMemsetAsync(pu->ysrc, 0, sizeof(int32_t) * (size_t)nslots, st));
     hipLaunchKernelGGL(k_lm_ysrc, dim3((unsigned)((nslots + 255) / 256)), dim3(256), 0, st, nslots, pu->uslot, fwd.scount, pl->wtab, pl->skew, pu->ysrc);
@@ -2060,13 +2012,9 @@ bool st_analyse_pair(hipStream_t st, int32_t n, const DevMat &Lrow, const DevMat
     ILUPP_HIP(stream_sync(st));
     if (dbg) fprintf(stderr, "[ilupp] static sweeps of a factor pair: row flags %d, %d+%d chunks\n", gl[0], hl[1], hu[1]);
     if (gl[0]) { pl->release(); pu->release(); return false; }
-    pl->valid = pu->valid = true;
-    pl->stat = pu->stat = true;
-    pl->wx = (hl[9] & ~8) == 0; pu->wx = (hu[9] & ~8) == 0;
-    pl->vec_ok = pl->wx && (hl[9] & 8) == 0; pu->vec_ok = pu->wx && (hu[9] & 8) == 0;
+    st_close(pl, pu, hl, hu);
     pl->pair = pu->pair = true;
     pu->desc = bwd_desc;
-    pu->linked = true;
     // a pair whose lanes fit the wave-exchange classes: class-aligned records, round 4's sweep kernels (neighbours in registers) with round
     // 5's vector wave; a backward sweep that accumulates in descending order (IChol0: T4) has its own instantiation (env ILUPP_NO_WR:
     // round 2's sweeps for every pair)
@@ -2079,62 +2027,50 @@ bool st_analyse_pair(hipStream_t st, int32_t n, const DevMat &Lrow, const DevMat
 // IChol(0), numeric phase on the static form.  L: on entry the lower triangle of A (rows, diagonal last), on exit the factor
 // (values in place, pattern unchanged).  false = this matrix is not one for the static form (nothing has been touched).
 // ---------------------------------------------------------------------------------------------
+// its analysis: the forward schedule alone, on L's pattern; true: ps has lane tables, records and an exchange buffer of the right sizes
+static bool ichol0_analyse_st(hipStream_t st, const DevMat &L, const Schedule &fwd, PackedSweep *ps)
+{
+    const int32_t n = L.n;
+    if (st_off() || L.nnz > 4 * (int64_t)n || n < 16 || fwd.nslots < kThreads || !L.val || !fwd.exported) return false;
+    const int nwg = fwd.nslots / kThreads;
+    st_structure(st, fwd, ps, (int)SWEEP_FWD_LAST_ASC);
+    st_templates(st, st_tpl_args(L, fwd, *ps), nullptr, nwg);
+    st_link<false>(st, ps, nullptr, 0);
+    hipLaunchKernelGGL(k_st_chol_check, dim3((unsigned)nwg), dim3(kThreads), 0, st, ps->ltab, ps->flags);
+    st_scan(st, ps, nullptr);
+    int32_t *xsz = st_xch_alloc(ps, nullptr);
+    st_xch_layout(st, fwd, nullptr, ps, nullptr, xsz);
+    int32_t hl[12], xtot[4];
+    st_read_back(st, ps, nullptr, xsz, hl, nullptr, xtot);
+    if (!st_accept("IChol0 static form", n, nwg, hl, nullptr)) return false;
+    st_alloc(ps, nullptr, hl, nullptr, xtot);
+    return true;
+}
+
+// (a PackedSweep has no destructor: the temporary one of the factorisation below is released on every way out, a thrown HipError included)
+struct SweepGuard {
+    PackedSweep ps;
+    SweepGuard() {}
+    ~SweepGuard() { ps.release(); }
+    SweepGuard(const SweepGuard &) = delete;
+    SweepGuard &operator=(const SweepGuard &) = delete;
+};
+
 bool ichol0_numeric_st(hipStream_t st, DevMat *L, const Schedule &fwd, int32_t *d_ctrl, float *kernel_ms, int *rc_out)
 {
-    static const bool off = getenv("ILUPP_NO_PACKED") != nullptr || getenv("ILUPP_NO_STATIC") != nullptr;
-    static const bool dbg = getenv("ILUPP_DEBUG") != nullptr;
-    const int32_t n = L->n;
+    const bool dbg = st_dbg();
     *rc_out = ILUPP_OK;
-    if (off || L->nnz > 4 * (int64_t)n || n < 16 || fwd.nslots < kThreads || !L->val || !fwd.exported) return false;
-    const int nwg = fwd.nslots / kThreads;
-    const int nslots = fwd.nslots;
-    PackedSweep ps;
-    st_structure(st, fwd, &ps, (int)SWEEP_FWD_LAST_ASC);
-    hipLaunchKernelGGL((k_st_template<1>), dim3((unsigned)nwg), dim3(kThreads), 0, st, L->ptr, L->idx, fwd.B, fwd.nb, fwd.start,
-                       fwd.blk2slot, fwd.sfirst, fwd.scount, fwd.exported, ps.ltab, ps.flags);
-    hipLaunchKernelGGL((k_st_link<false>), dim3((unsigned)nwg), dim3(kThreads), 0, st, ps.ltab, static_cast<const int32_t *>(nullptr),
-                       static_cast<const int32_t *>(nullptr), ps.skew, ps.wtab, ps.flags, 0);
-    hipLaunchKernelGGL(k_st_chol_check, dim3((unsigned)nwg), dim3(kThreads), 0, st, ps.ltab, ps.flags);
-    hipLaunchKernelGGL(k_st_scan, dim3(1), dim3(kThreads), 0, st, nwg * 4, ps.wtab, ps.flags);
-    int32_t *xsz = nullptr;
-    void *tmp2 = nullptr;
-    size_t tb2 = 0;
-    int32_t xtot[2] = {0, 0};
-    ILUPP_HIP(pool_malloc(&xsz, sizeof(int32_t) * (size_t)nwg * 2));
-    ILUPP_HIP(hipcub::DeviceScan::ExclusiveSum(nullptr, tb2, xsz, xsz + nwg, nwg, st));
-    ILUPP_HIP(pool_malloc(&tmp2, tb2));
-    ILUPP_HIP(pool_malloc(&ps.xe, sizeof(int32_t) * (size_t)nslots));
-    ILUPP_HIP(pool_malloc(&ps.xw, sizeof(int32_t) * (size_t)nwg * 4));
-    hipLaunchKernelGGL(k_st_xch_layout, dim3((unsigned)nwg), dim3(kThreads), 0, st, fwd.exported, ps.ltab, ps.wtab, ps.xe, ps.xw, xsz, ps.flags);
-    ILUPP_HIP(hipcub::DeviceScan::ExclusiveSum(tmp2, tb2, xsz, xsz + nwg, nwg, st));
-    hipLaunchKernelGGL(k_st_xch_rows, dim3((unsigned)((nwg + 255) / 256)), dim3(256), 0, st, nwg, xsz + nwg, ps.xw);
-    ILUPP_HIP(d2h_async(st, &xtot[0], xsz + nwg + (nwg - 1), sizeof(int32_t)));
-    ILUPP_HIP(d2h_async(st, &xtot[1], xsz + (nwg - 1), sizeof(int32_t)));
-    int32_t hl[4];
-    ILUPP_HIP(d2h_async(st, hl, ps.flags, sizeof(hl)));
-    ILUPP_HIP(stream_sync(st));
-    ILUPP_HIP(pool_free(xsz)); ILUPP_HIP(pool_free(tmp2));
-    const int64_t lim = 6 * (int64_t)n + 64 * 4 * (int64_t)nwg;
-    if (hl[0] || hl[1] <= 0 || (int64_t)hl[1] * 64 > lim || hl[1] + 4 * nwg >= kStMaxChunks ||
-        (int64_t)nwg * kThreads * ((int64_t)hl[2] + 2 * kStXAlign) > 0x7fffffffLL) {
-        if (dbg) fprintf(stderr, "[ilupp] IChol0 static form: structure rejected (flags %d, %d chunks)\n", hl[0], hl[1]);
-        ps.release();
-        return false;
-    }
-    ps.nchunks = hl[1]; ps.max_chunks = hl[2];
-    ILUPP_HIP(pool_malloc(&ps.pk, (size_t)(ps.nchunks + 4 * nwg) * 2048));
-    ps.built = true;
-    hipLaunchKernelGGL(k_st_pack_lower, dim3((unsigned)(nwg * 4), (unsigned)((ps.max_chunks + 7) / 8)), dim3(512), 0, st, L->ptr, L->idx, L->val,
+    SweepGuard g;
+    PackedSweep &ps = g.ps;
+    if (!ichol0_analyse_st(st, *L, fwd, &ps)) return false;
+    hipLaunchKernelGGL(k_st_pack_lower, dim3((unsigned)(ps.nwg * 4), (unsigned)((ps.max_chunks + 7) / 8)), dim3(512), 0, st, L->ptr, L->idx, L->val,
                        ps.ltab, ps.wtab, reinterpret_cast<v2d *>(ps.pk), ps.flags);
-    ps.xch_len = (int64_t)xtot[0] + xtot[1] + 64;
-    ILUPP_HIP(pool_malloc(&ps.xch, sizeof(double) * (size_t)ps.xch_len));
     fill_u64(st, reinterpret_cast<unsigned long long *>(ps.xch), ps.xch_len, kSentinel);
     int32_t gl[4];
     ILUPP_HIP(d2h_async(st, gl, ps.flags, sizeof(gl)));
     ILUPP_HIP(stream_sync(st));
     if (gl[0]) {
         if (dbg) fprintf(stderr, "[ilupp] IChol0 static form: row flags %d\n", gl[0]);
-        ps.release();
         return false;
     }
     ILUPP_HIP(hipMemsetAsync(d_ctrl, 0, 16, st));
@@ -2144,23 +2080,19 @@ bool ichol0_numeric_st(hipStream_t st, DevMat *L, const Schedule &fwd, int32_t *
     a.pkL = reinterpret_cast<v2d *>(ps.pk); a.pkU = nullptr;
     a.nchL = (int32_t)ps.nchunks;
     a.xe = ps.xe; a.xw = ps.xw; a.xch = ps.xch; a.ctrl = d_ctrl;
-    hipEvent_t e0, e1;
-    ILUPP_HIP(hipEventCreate(&e0));
-    ILUPP_HIP(hipEventCreate(&e1));
-    ILUPP_HIP(hipEventRecord(e0, st));
-    hipLaunchKernelGGL(k_ichol0_st, dim3((unsigned)nwg), dim3(kStWgThreads), 0, st, a);
-    ILUPP_HIP(hipEventRecord(e1, st));
+    EventPair ev;
+    ILUPP_HIP(ev.create());
+    ILUPP_HIP(hipEventRecord(ev.a, st));
+    hipLaunchKernelGGL(k_ichol0_st, dim3((unsigned)ps.nwg), dim3(kStWgThreads), 0, st, a);
+    ILUPP_HIP(hipEventRecord(ev.b, st));
     ILUPP_HIP(hipGetLastError());
     ps.valid = true; ps.stat = true;
-    st_unpack(st, *L, fwd, ps);
+    st_unpack(st, *L, ps);
     int32_t ctrl[4] = {0, 0, 0, 0};
     ILUPP_HIP(d2h_async(st, ctrl, d_ctrl, 16));
     ILUPP_HIP(stream_sync(st));
-    if (kernel_ms) ILUPP_HIP(hipEventElapsedTime(kernel_ms, e0, e1));
-    ILUPP_HIP(hipEventDestroy(e0));
-    ILUPP_HIP(hipEventDestroy(e1));
-    if (dbg) fprintf(stderr, "[ilupp] IChol0 static form: %d chunks, kernel %.3f ms, status %d\n", hl[1], kernel_ms ? *kernel_ms : 0.f, ctrl[1]);
-    ps.release();
+    if (kernel_ms) ILUPP_HIP(hipEventElapsedTime(kernel_ms, ev.a, ev.b));
+    if (dbg) fprintf(stderr, "[ilupp] IChol0 static form: %d chunks, kernel %.3f ms, status %d\n", (int)ps.nchunks, kernel_ms ? *kernel_ms : 0.f, ctrl[1]);
     if (ctrl[1] != 0) *rc_out = ILUPP_ERR_TIMEOUT;
     return true;
 }
@@ -2296,15 +2228,13 @@ int sptrsv_st_T(hipStream_t st, const PackedSweep &ps, int32_t n, const double *
     a.xe = ps.xe; a.xw = ps.xw; a.xch = ps.xch; a.ticket = d_ticket; a.err = d_err;
     fill_u64(st, reinterpret_cast<unsigned long long *>(ps.xch), ps.xch_len, kSentinel);
     const dim3 grid((unsigned)ps.nwg);
-    st_solo_attr_T();
+    st_solo_attr();
     if (fwd) {
-        hipLaunchKernelGGL((k_st_vec<1, true>), dim3((unsigned)(ps.nwg * 4), (unsigned)st_vec_groups(ps.max_chunks)), dim3(512), 0, st, ps.ltab, ps.wtab,
-                           const_cast<double *>(rhs), lml);
+        st_vec_to_lm(st, ps, rhs, lml);
         hipLaunchKernelGGL((k_sptrsv_st<1, true>), grid, dim3(kStWgThreads), kStSoloLds, st, a);
     } else {
         hipLaunchKernelGGL((k_sptrsv_st<-1, true>), grid, dim3(kStWgThreads), kStSoloLds, st, a);
-        hipLaunchKernelGGL((k_st_vec<-1, false>), dim3((unsigned)(ps.nwg * 4), (unsigned)st_vec_groups(ps.max_chunks)), dim3(512), 0, st, ps.ltab, ps.wtab,
-                           out, ps.xlm);
+        st_vec_from_lm(st, ps, out);
     }
     ILUPP_HIP(hipGetLastError());
     return ILUPP_OK;
