@@ -137,6 +137,25 @@ class _BlockApply:
         return self._block_copy(X, True)
 
 
+def _batch(cls, matrices, make):
+    """the instances of `cls` for `matrices` (all CSR or all CSC) from ONE native batched construction: `make` takes the list of
+    (data, indices, indptr) and the format, and returns the native objects in that order"""
+    matrices = list(matrices)
+    if not matrices:
+        return []
+    ms = [_borrow(A) for A in matrices]
+    if any(m.is_csr != ms[0].is_csr for m in ms):
+        raise TypeError("a batch holds matrices of one format")
+    natives = make([(m.data, m.indices, m.indptr) for m in ms], ms[0].is_csr)
+    out = []
+    for A, pr in zip(matrices, natives):
+        P = cls.__new__(cls)
+        P.pr = pr
+        _LinearOperator.__init__(P, dtype=A.dtype, shape=A.shape)
+        out.append(P)
+    return out
+
+
 def _ml_parameters(threshold, fill_in, params):
     """the parameter object of a multilevel construction: the caller's, or default-constructed ones carrying the two numbers"""
     if params is not None:
@@ -174,20 +193,7 @@ class ILUppPreconditioner(_HipPreconditioner):
         ``[ILUppPreconditioner(A, ...) for A in matrices]`` gives, bit for bit, in about the time of the slowest one -- the sequential
         chains of the factorisation with pivoting (one wave each) share one launch (``ilupp_hip_ml_create_batch``)."""
         params = _ml_parameters(threshold, fill_in, params)
-        matrices = list(matrices)
-        if not matrices:
-            return []
-        ms = [_borrow(A) for A in matrices]
-        if any(m.is_csr != ms[0].is_csr for m in ms):
-            raise TypeError("a batch holds matrices of one format")
-        natives = _backend.MultilevelILUCDPPreconditioner_batch([(m.data, m.indices, m.indptr) for m in ms], ms[0].is_csr, params)
-        out = []
-        for A, pr in zip(matrices, natives):
-            P = cls.__new__(cls)
-            P.pr = pr
-            _LinearOperator.__init__(P, dtype=A.dtype, shape=A.shape)
-            out.append(P)
-        return out
+        return _batch(cls, matrices, lambda ms, is_csr: _backend.MultilevelILUCDPPreconditioner_batch(ms, is_csr, params))
 
     # the three memory figures of the reference's object (binding.cpp:257-259), passed through from the native one
     memory = property(lambda self: self.pr.memory)
@@ -211,7 +217,8 @@ class ILUCPreconditioner(_BlockApply, _HipPreconditioner):
 
 class ILUTPPreconditioner(_HipPreconditioner):
     """ILUT with column pivoting -- on this engine a SEQUENTIAL chain that one wave walks: bit-identical to the reference and
-    10-30x slower than the reference on one host core for a single matrix (profiles/r04_chains.txt).  (Reference:
+    10-30x slower than the reference on one host core for a single matrix (profiles/r04_chains.txt); with many matrices use
+    :meth:`batch`, which walks their chains side by side (64 matrices in about 1.5x the time of one: profiles/r09_pivot_batch.txt).  (Reference:
     ilupp/__init__.py:218-236 over ILUTP2, ILUTP.hpp:13-140.)
 
     `A`: scipy CSR or CSC matrix; `fill_in`: entries kept per row of L and of U; `threshold`: relative size below which an entry is
@@ -223,6 +230,13 @@ class ILUTPPreconditioner(_HipPreconditioner):
     def __init__(self, A, fill_in=100, threshold=0.1, piv_tol=0.1, mem_factor=10.0):
         super().__init__(A, lambda m: _backend.ILUTPPreconditioner(*m, fill_in, threshold, piv_tol, -1, mem_factor))
 
+    @classmethod
+    def batch(cls, matrices, fill_in=100, threshold=0.1, piv_tol=0.1, mem_factor=10.0):
+        """One preconditioner per matrix of `matrices` (all CSR or all CSC; one parameter set), built side by side on the GPU: the objects
+        ``[ILUTPPreconditioner(A, ...) for A in matrices]`` gives, bit for bit -- the chains (one wave each) share one launch, one
+        workgroup per matrix (``ilupp_hip_ilutp_create_batch``)."""
+        return _batch(cls, matrices, lambda ms, is_csr: _backend.ILUTPPreconditioner_batch(ms, is_csr, fill_in, threshold, piv_tol, -1, mem_factor))
+
     def permutations(self):
         """(left, right): the two index arrays the pivoting produced (rows stay where they are for this factorisation)."""
         left, right = self.pr.permutations()
@@ -231,7 +245,8 @@ class ILUTPPreconditioner(_HipPreconditioner):
 
 class ILUCPPreconditioner(_HipPreconditioner):
     """Crout ILU with column pivoting (Mayer 2005) -- on this engine a SEQUENTIAL chain that one wave walks: bit-identical to the
-    reference and 10-30x slower than the reference on one host core for a single matrix (profiles/r04_chains.txt).  (Reference:
+    reference and 10-30x slower than the reference on one host core for a single matrix (profiles/r04_chains.txt); with many matrices use
+    :meth:`batch`, which walks their chains side by side (64 matrices in about 1.5x the time of one: profiles/r09_pivot_batch.txt).  (Reference:
     ilupp/__init__.py:252-270 over ILUCP4, ILUC.hpp:212-370.)
 
     `A`: scipy CSR or CSC matrix; `fill_in`: entries kept per column of L and per row of U; `threshold`, `piv_tol`, `mem_factor`: as
@@ -241,6 +256,13 @@ class ILUCPPreconditioner(_HipPreconditioner):
 
     def __init__(self, A, fill_in=100, threshold=0.1, piv_tol=0.1, mem_factor=10.0):
         super().__init__(A, lambda m: _backend.ILUCPPreconditioner(*m, fill_in, threshold, piv_tol, -1, mem_factor))
+
+    @classmethod
+    def batch(cls, matrices, fill_in=100, threshold=0.1, piv_tol=0.1, mem_factor=10.0):
+        """One preconditioner per matrix of `matrices` (all CSR or all CSC; one parameter set), built side by side on the GPU: the objects
+        ``[ILUCPPreconditioner(A, ...) for A in matrices]`` gives, bit for bit -- the chains (one wave each) share one launch, one
+        workgroup per matrix (``ilupp_hip_ilucp_create_batch``)."""
+        return _batch(cls, matrices, lambda ms, is_csr: _backend.ILUCPPreconditioner_batch(ms, is_csr, fill_in, threshold, piv_tol, -1, mem_factor))
 
     def permutations(self):
         """(left, right): the two index arrays the pivoting produced (rows stay where they are for this factorisation)."""

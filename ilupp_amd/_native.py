@@ -153,6 +153,10 @@ def lib():
     L.ilupp_hip_ilucp_create.argtypes = [_VP, _VP, _VP, ctypes.c_int32, ctypes.c_int, ctypes.c_int32, ctypes.c_double, ctypes.c_double, ctypes.c_int32,
                                          ctypes.c_double, ctypes.POINTER(_VP)]
     L.ilupp_hip_ilutp_create.argtypes = L.ilupp_hip_ilucp_create.argtypes
+    L.ilupp_hip_ilucp_create_batch.argtypes = [ctypes.c_int32, ctypes.POINTER(_VP), ctypes.POINTER(_VP), ctypes.POINTER(_VP), _I32P, ctypes.c_int,
+                                               ctypes.c_int32, ctypes.c_double, ctypes.c_double, ctypes.c_int32, ctypes.c_double,
+                                               ctypes.POINTER(_VP), _I32P]
+    L.ilupp_hip_ilutp_create_batch.argtypes = L.ilupp_hip_ilucp_create_batch.argtypes
     L.ilupp_hip_ilucp_destroy.argtypes = [_VP]
     L.ilupp_hip_ilucp_destroy.restype = None
     L.ilupp_hip_ilucp_apply.argtypes = [_VP, _VP, ctypes.c_int64, ctypes.c_int]
@@ -191,7 +195,7 @@ ABI_SYMBOLS = [
     "ilupp_hip_ml_apply_device", "ilupp_hip_ml_apply_part_device", "ilupp_hip_ml_sync", "ilupp_hip_ml_levels", "ilupp_hip_ml_total_nnz", "ilupp_hip_ml_level_info",
     "ilupp_hip_ml_level_copy", "ilupp_hip_ml_timings", "ilupp_hip_solve", "ilupp_hip_ml_create_batch",
     "ilupp_hip_ilucp_create", "ilupp_hip_ilucp_destroy", "ilupp_hip_ilucp_apply", "ilupp_hip_ilucp_total_nnz", "ilupp_hip_ilucp_zero_pivots",
-    "ilupp_hip_ilucp_info", "ilupp_hip_ilucp_copy", "ilupp_hip_ilutp_create",
+    "ilupp_hip_ilucp_info", "ilupp_hip_ilucp_copy", "ilupp_hip_ilutp_create", "ilupp_hip_ilucp_create_batch", "ilupp_hip_ilutp_create_batch",
     "ilupp_hip_apply_block", "ilupp_hip_apply_block_device", "ilupp_hip_block_path",
     "ilupp_hip_spmm_device", "ilupp_hip_block_dot_device", "ilupp_hip_cg_block_update_device", "ilupp_hip_bicgstab_block_update_device",
 ]
@@ -804,3 +808,42 @@ def ILUTPPreconditioner(A_data, A_indices, A_indptr, is_csr, max_fill_in, thresh
     if rc:
         _raise(rc)
     return PivotedPreconditioner(h, args[3], is_csr, rows=True)
+
+
+def _pivoted_batch(create_batch, rows, matrices, is_csr, max_fill_in, threshold, piv_tol, row_pos, mem_factor):
+    cnt = len(matrices)
+    if cnt == 0:
+        return []
+    keep, ns = [], []
+    D, I, P = (_VP * cnt)(), (_VP * cnt)(), (_VP * cnt)()
+    for k, (d, i, ptr) in enumerate(matrices):
+        args, arrays = _matrix_args(d, i, ptr, is_csr)
+        keep.append(arrays)
+        D[k], I[k], P[k] = args[0], args[1], args[2]
+        ns.append(args[3])
+    N = (ctypes.c_int32 * cnt)(*ns)
+    out = (_VP * cnt)()
+    status = (ctypes.c_int32 * cnt)()
+    rc = create_batch(cnt, D, I, P, N, 1 if is_csr else 0, int(max_fill_in), float(threshold), float(piv_tol), int(row_pos), float(mem_factor),
+                      out, status)
+    if rc:
+        first = next((k for k in range(cnt) if status[k] != 0), -1)
+        for k in range(cnt):
+            if out[k]:
+                lib().ilupp_hip_ilucp_destroy(out[k])
+        msg = lib().ilupp_hip_last_error().decode() + " (matrix %d of the batch, status %d)" % (first, status[first] if first >= 0 else rc)
+        if rc == ILUPP_ERR_UNSUPPORTED:
+            raise NotImplementedError(msg)
+        raise RuntimeError(msg)
+    return [PivotedPreconditioner(_VP(out[k]), ns[k], is_csr, rows=rows) for k in range(cnt)]
+
+
+def ILUCPPreconditioner_batch(matrices, is_csr, max_fill_in, threshold, piv_tol, row_pos, mem_factor):
+    """one ILUCP preconditioner per matrix of `matrices` (a list of (data, indices, indptr)), their chains side by side
+    (ilupp_hip_ilucp_create_batch): the same objects the constructor gives one at a time"""
+    return _pivoted_batch(lib().ilupp_hip_ilucp_create_batch, False, matrices, is_csr, max_fill_in, threshold, piv_tol, row_pos, mem_factor)
+
+
+def ILUTPPreconditioner_batch(matrices, is_csr, max_fill_in, threshold, piv_tol, row_pos, mem_factor):
+    """one ILUTP preconditioner per matrix of `matrices`, as ILUCPPreconditioner_batch (ilupp_hip_ilutp_create_batch)"""
+    return _pivoted_batch(lib().ilupp_hip_ilutp_create_batch, True, matrices, is_csr, max_fill_in, threshold, piv_tol, row_pos, mem_factor)

@@ -5,6 +5,7 @@
 #include <string.h>
 
 #include <atomic>
+#include <functional>
 #include <map>
 #include <chrono>
 #include <mutex>
@@ -2017,6 +2018,76 @@ int ml_create_common(const DevMat &A, const ilupp_ml_params *ip, ilupp_ml **out)
     return ILUPP_OK;
 }
 
+// The workers of a batched construction (ilupp_hip_ml_create_batch, ilupp_hip_ilucp_create_batch, ilupp_hip_ilutp_create_batch): `build(i)`
+// constructs member i on the calling worker's thread and returns its code; `worst_bytes` is the device memory the largest member holds
+// while it is built.  At most 64 workers (ILUPP_BATCH_WORKERS, read per call) and as many as the memory takes: 0.6 of the free bytes, the
+// pool's kept blocks counted as free.  Every worker is a member of one ChainBatch, so the sequential chains of the members it builds are
+// launched together with the other workers' (pilucdp.hip).  Members are independent: status[i] per member (may be null), the first
+// failure is returned and reported as "matrix i of the batch: ...".  The caller holds the build lock.
+int batch_build(int32_t count, double worst_bytes, int32_t *status, const std::function<int(int32_t)> &build)
+{
+    int workers = 64;
+    if (const char *e = getenv("ILUPP_BATCH_WORKERS")) { const int v = atoi(e); if (v > 0) workers = v; }
+    if (workers > count) workers = count;
+    int device = 0;
+    ILUPP_HIP(hipGetDevice(&device));
+    {
+        size_t free_b = 0, total_b = 0;
+        ILUPP_HIP(hipMemGetInfo(&free_b, &total_b));
+        free_b += pool_cached_bytes();
+        if (worst_bytes > 0.0) { const double fit = 0.6 * (double)free_b / worst_bytes; if (fit < (double)workers) workers = fit < 1.0 ? 1 : (int)fit; }
+    }
+    ChainBatch *cb = chain_batch_create(workers);
+    if (!cb) { set_error("batched construction: no stream"); return ILUPP_ERR_HIP; }
+    // (the batch and its stream go when this call unwinds, whatever throws below)
+    struct BatchGuard { ChainBatch *b; ~BatchGuard() { if (b) chain_batch_destroy(b); } } cbg{cb};
+    std::vector<int> rcs((size_t)count, ILUPP_OK);
+    std::vector<std::string> msgs((size_t)count);
+    std::atomic<int32_t> next(0);
+    auto work = [&](int w) {
+        (void)hipSetDevice(device);
+        pool_set_owner(w + 1);
+        chain_batch_enter(cb);
+        for (;;) {
+            const int32_t i = next.fetch_add(1);
+            if (i >= count) break;
+            int rc;
+            try { rc = build(i); }
+            catch (const ilupp::HipError &e) { ilupp::d2h_cancel_all(); rc = ilupp::report(e); }
+            catch (const std::bad_alloc &) { ilupp::set_error("out of host memory"); rc = ILUPP_ERR_MEMORY; }
+            catch (...) { ilupp::set_error("unexpected exception in a batch worker"); rc = ILUPP_ERR_HIP; }     // (a worker must reach chain_batch_leave)
+            rcs[(size_t)i] = rc;
+            if (rc) msgs[(size_t)i] = ilupp::g_last_error;
+        }
+        chain_batch_leave(cb);
+        (void)hipDeviceSynchronize();                          // (everything this worker queued is done: its kept blocks are everybody's)
+        pool_disown(w + 1);
+        pool_set_owner(0);
+    };
+    // Kept blocks of owner 0 may have been given back by calls on other objects' streams (apply temporaries, destroy) without a wait for
+    // those streams: nothing of that may still be queued when up to 64 fresh streams start to take such blocks (pool.h).
+    ILUPP_HIP(hipDeviceSynchronize());
+    {
+        // (threads that were started are joined whatever happens -- a joinable std::thread that is destroyed ends the process --, and
+        // workers that could not be started are taken out of the batch's count, or the others would wait for their launches for good)
+        struct Joiner { std::vector<std::thread> v; ~Joiner() { for (std::thread &t : v) if (t.joinable()) t.join(); } } pool_threads;
+        int started = 1;
+        try {
+            for (int w = 1; w < workers; ++w) { pool_threads.v.emplace_back(work, w); ++started; }
+        } catch (...) {
+            for (int w = started; w < workers; ++w) { chain_batch_enter(cb); chain_batch_leave(cb); }
+        }
+        work(0);
+    }
+    chain_batch_destroy(cbg.b); cbg.b = nullptr;
+    int first = ILUPP_OK;
+    for (int32_t i = 0; i < count; ++i) {
+        if (status) status[i] = rcs[(size_t)i];
+        if (rcs[(size_t)i] && !first) { first = rcs[(size_t)i]; set_error("matrix " + std::to_string(i) + " of the batch: " + msgs[(size_t)i]); }
+    }
+    return first;
+}
+
 }  // namespace
 
 extern "C" {
@@ -2060,73 +2131,16 @@ int ilupp_hip_ml_create_batch(int32_t count, const double *const *data, const in
     if (count < 0 || !data || !indices || !indptr || !n || !params || !out) { set_error("null argument"); return ILUPP_ERR_INVALID; }
     for (int32_t i = 0; i < count; ++i) { out[i] = nullptr; if (status) status[i] = ILUPP_OK; }
     if (count == 0) return ILUPP_OK;
-    int workers = 64;
-    if (const char *e = getenv("ILUPP_BATCH_WORKERS")) { const int v = atoi(e); if (v > 0) workers = v; }
-    if (workers > count) workers = count;
-    int device = 0;
-    ILUPP_HIP(hipGetDevice(&device));
-    {   // as many at a time as the memory takes: a construction with pivoting holds ~116 bytes per entry + 450 per row (two stores with
-        // their link arrays, the Schur store, both orientations of the level's matrix, the tables); the pool's kept blocks count as free
-        size_t free_b = 0, total_b = 0;
-        ILUPP_HIP(hipMemGetInfo(&free_b, &total_b));
-        free_b += pool_cached_bytes();
-        double worst = 0.0;
-        for (int32_t i = 0; i < count; ++i)
-            if (indptr[i] && n[i] > 0) { const double e = 116.0 * (double)indptr[i][n[i]] + 450.0 * (double)n[i] + (double)(64 << 20); if (e > worst) worst = e; }
-        if (worst > 0.0) { const double fit = 0.6 * (double)free_b / worst; if (fit < (double)workers) workers = fit < 1.0 ? 1 : (int)fit; }
-    }
-    ChainBatch *cb = chain_batch_create(workers);
-    if (!cb) { set_error("batched construction: no stream"); return ILUPP_ERR_HIP; }
-    // (the batch and its stream go when this call unwinds, whatever throws below)
-    struct BatchGuard { ChainBatch *b; ~BatchGuard() { if (b) chain_batch_destroy(b); } } cbg{cb};
-    std::vector<int> rcs((size_t)count, ILUPP_OK);
-    std::vector<std::string> msgs((size_t)count);
-    std::atomic<int32_t> next(0);
-    auto work = [&](int w) {
-        (void)hipSetDevice(device);
-        pool_set_owner(w + 1);
-        chain_batch_enter(cb);
-        for (;;) {
-            const int32_t i = next.fetch_add(1);
-            if (i >= count) break;
-            int rc;
-            try {
-                MatGuard A;
-                rc = upload(data[i], indices[i], indptr[i], n[i], is_csr != 0, &A.m);
-                if (!rc) rc = ml_create_common(A.m, params, &out[i]);
-            } catch (const ilupp::HipError &e) { ilupp::d2h_cancel_all(); rc = ilupp::report(e); }
-            catch (const std::bad_alloc &) { ilupp::set_error("out of host memory"); rc = ILUPP_ERR_MEMORY; }
-            catch (...) { ilupp::set_error("unexpected exception in a batch worker"); rc = ILUPP_ERR_HIP; }     // (a worker must reach chain_batch_leave)
-            rcs[(size_t)i] = rc;
-            if (rc) msgs[(size_t)i] = ilupp::g_last_error;
-        }
-        chain_batch_leave(cb);
-        (void)hipDeviceSynchronize();                          // (everything this worker queued is done: its kept blocks are everybody's)
-        pool_disown(w + 1);
-        pool_set_owner(0);
-    };
-    // Kept blocks of owner 0 may have been given back by calls on other objects' streams (apply temporaries, destroy) without a wait for
-    // those streams: nothing of that may still be queued when up to 64 fresh streams start to take such blocks (pool.h).
-    ILUPP_HIP(hipDeviceSynchronize());
-    {
-        // (threads that were started are joined whatever happens -- a joinable std::thread that is destroyed ends the process --, and
-        // workers that could not be started are taken out of the batch's count, or the others would wait for their launches for good)
-        struct Joiner { std::vector<std::thread> v; ~Joiner() { for (std::thread &t : v) if (t.joinable()) t.join(); } } pool_threads;
-        int started = 1;
-        try {
-            for (int w = 1; w < workers; ++w) { pool_threads.v.emplace_back(work, w); ++started; }
-        } catch (...) {
-            for (int w = started; w < workers; ++w) { chain_batch_enter(cb); chain_batch_leave(cb); }
-        }
-        work(0);
-    }
-    chain_batch_destroy(cbg.b); cbg.b = nullptr;
-    int first = ILUPP_OK;
-    for (int32_t i = 0; i < count; ++i) {
-        if (status) status[i] = rcs[(size_t)i];
-        if (rcs[(size_t)i] && !first) { first = rcs[(size_t)i]; set_error("matrix " + std::to_string(i) + " of the batch: " + msgs[(size_t)i]); }
-    }
-    return first;
+    // a construction with pivoting holds ~116 bytes per entry + 450 per row (two stores with their link arrays, the Schur store, both
+    // orientations of the level's matrix, the tables)
+    double worst = 0.0;
+    for (int32_t i = 0; i < count; ++i)
+        if (indptr[i] && n[i] > 0) { const double e = 116.0 * (double)indptr[i][n[i]] + 450.0 * (double)n[i] + (double)(64 << 20); if (e > worst) worst = e; }
+    return batch_build(count, worst, status, [&](int32_t i) {
+        MatGuard A;
+        const int rc = upload(data[i], indices[i], indptr[i], n[i], is_csr != 0, &A.m);
+        return rc ? rc : ml_create_common(A.m, params, &out[i]);
+    });
     API_CATCH
 }
 
@@ -2527,5 +2541,67 @@ extern "C" int ilupp_hip_ilutp_create(const double *data, const int32_t *indices
     const int rc = upload(data, indices, indptr, n, true, &A.m);
     if (rc) return rc;
     return ilutp_create_common(A.m, n, is_csr, max_fill_in, threshold, piv_tol, row_pos, mem_factor, out);
+    API_CATCH
+}
+
+// ---- many matrices at once: the chains of the members side by side, one workgroup each (k_ilucp_batch / k_ilutp_batch) ----
+namespace {
+
+// The device memory one construction holds (ilucp_factor / ilutp_factor and the object built from their result), R = the reserved entries
+// = min(max_fill_in * n, (Integer) mem_factor * nnz), slot = n + 64:
+//   the stores of R + 1 entries             ILUCP 32 bytes per entry (U: index, link, row, value; L: index, value), ILUTP 24 (U and L: index, value)
+//   the slot tables                         ILUCP 16 int32 + 5 double tables of `slot` = 104 slot; ILUTP 5 int32 of slot + (5 int32 + 3 double) of 4 slot = 196 slot
+//   the sort buffers                        ILUCP: two key arrays of n and the in-kernel sort's of up to 2 n, 8 bytes each = 32 n;
+//                                           ILUTP: the segmented sorts of the compress step, keys and values twice over = 24 R
+//   the compressed factors                  L, U and U in the other numbering, 12 bytes per entry, each at most R entries = 36 R
+//   the uploaded matrix                     12 nnz + 4 (n + 1)
+// + 64 MiB for what does not scale with the matrix (the sorts' and scans' temporaries, the sweeps' tables, the pool's rounding).
+double pivot_member_bytes(bool tp, int32_t n, int64_t nnz, int32_t max_fill_in, double mem_factor)
+{
+    int64_t mf = max_fill_in < 1 ? 1 : max_fill_in;
+    if (mf > n) mf = n;
+    const double a = (double)mf * (double)n, b = (double)((int32_t)mem_factor) * (double)nnz;
+    const double R = a < b ? (a > 0.0 ? a : 0.0) : (b > 0.0 ? b : 0.0);
+    const double slot = (double)n + 64.0;
+    const double stores = (tp ? 24.0 : 32.0) * (R + 1.0), tables = (tp ? 196.0 : 104.0) * slot, sorts = tp ? 24.0 * R : 32.0 * (double)n;
+    return stores + tables + sorts + 36.0 * R + 12.0 * (double)nnz + 4.0 * ((double)n + 1.0) + (double)(64 << 20);
+}
+
+int pivot_create_batch(bool tp, int32_t count, const double *const *data, const int32_t *const *indices, const int32_t *const *indptr, const int32_t *n,
+                       int is_csr, int32_t max_fill_in, double threshold, double piv_tol, int32_t row_pos, double mem_factor, ilupp_ilucp **out,
+                       int32_t *status)
+{
+    if (count < 0 || !data || !indices || !indptr || !n || !out) { set_error("null argument"); return ILUPP_ERR_INVALID; }
+    for (int32_t i = 0; i < count; ++i) { out[i] = nullptr; if (status) status[i] = ILUPP_OK; }
+    if (count == 0) return ILUPP_OK;
+    double worst = 0.0;
+    for (int32_t i = 0; i < count; ++i)
+        if (indptr[i] && n[i] > 0) { const double e = pivot_member_bytes(tp, n[i], indptr[i][n[i]], max_fill_in, mem_factor); if (e > worst) worst = e; }
+    return batch_build(count, worst, status, [&](int32_t i) {
+        MatGuard A;
+        const int rc = upload(data[i], indices[i], indptr[i], n[i], true, &A.m);
+        if (rc) return rc;
+        return tp ? ilutp_create_common(A.m, n[i], is_csr, max_fill_in, threshold, piv_tol, row_pos, mem_factor, &out[i])
+                  : ilucp_create_common(A.m, n[i], is_csr, max_fill_in, threshold, piv_tol, row_pos, mem_factor, &out[i]);
+    });
+}
+
+}  // namespace
+
+extern "C" int ilupp_hip_ilucp_create_batch(int32_t count, const double *const *data, const int32_t *const *indices, const int32_t *const *indptr,
+                                            const int32_t *n, int is_csr, int32_t max_fill_in, double threshold, double piv_tol, int32_t row_pos,
+                                            double mem_factor, ilupp_ilucp **out, int32_t *status)
+{
+    API_TRY_BUILD
+    return pivot_create_batch(false, count, data, indices, indptr, n, is_csr, max_fill_in, threshold, piv_tol, row_pos, mem_factor, out, status);
+    API_CATCH
+}
+
+extern "C" int ilupp_hip_ilutp_create_batch(int32_t count, const double *const *data, const int32_t *const *indices, const int32_t *const *indptr,
+                                            const int32_t *n, int is_csr, int32_t max_fill_in, double threshold, double piv_tol, int32_t row_pos,
+                                            double mem_factor, ilupp_ilucp **out, int32_t *status)
+{
+    API_TRY_BUILD
+    return pivot_create_batch(true, count, data, indices, indptr, n, is_csr, max_fill_in, threshold, piv_tol, row_pos, mem_factor, out, status);
     API_CATCH
 }

@@ -466,6 +466,16 @@ ChainBatch *chain_batch_create(int workers);
 void chain_batch_destroy(ChainBatch *b);
 void chain_batch_enter(ChainBatch *b);       // the calling thread is a worker of b from now on ...
 void chain_batch_leave(ChainBatch *b);       // ... until here (it will hand in no more launches)
+// the kinds of chain a batch combines: the chain with pivoting in LDS; partialILUC in LDS / with its vectors in memory (DpArgs, pilucdp.hip);
+// ILUCP's (CpArgs, ilucp.hip) and ILUTP's (TpArgs, ilutp.hip)
+enum { CHAIN_DP_LDS = 0, CHAIN_PC_LDS = 1, CHAIN_PC_MEM = 2, CHAIN_CP = 3, CHAIN_TP = 4, CHAIN_KINDS = 5 };
+// one chain launch on `st`, synchronised, timed in *ms: directly when the calling thread is no worker of a batch; else the chain is handed to
+// the batch, which launches it with the others' after everything queued on `st` so far.  args / size: the kind's argument record (host; it
+// is copied before the call returns)
+int chain_launch(hipStream_t st, const void *args, size_t size, int kind, float *ms);
+// a kind's kernels outside pilucdp.hip -- count == 0: the single kernel with the host record by value, > 0: the batched one over device records
+void ilucp_chain_kernel(hipStream_t st, const void *args, int count);
+void ilutp_chain_kernel(hipStream_t st, const void *args, int count);
 // pilucdp.hip: partialILUC as a sequential chain with its working vectors in LDS -- for what the dataflow kernel cannot run (dropping rules
 // that are recurrences over all steps) or runs badly (long working rows: its largest class).  +1: outside the chain kernel's capacity (LDS: working
 // rows of 2 048 entries; with mem_ok the chain goes on with its vectors in global memory: 32 768).

@@ -70,7 +70,8 @@ __device__ int cp_candidates(const CpArgs &A, const SpVec &v, int nnz, double th
     return cnt;
 }
 
-__global__ void __launch_bounds__(64) k_ilucp(CpArgs A)
+// the chain of one matrix, walked by one wave (the single and the batched kernel are this body)
+__device__ __forceinline__ void cp_chain(const CpArgs &A)
 {
     const int lane = threadIdx.x;
     const unsigned long long lt = (1ull << lane) - 1ull;
@@ -271,6 +272,21 @@ __global__ void __launch_bounds__(64) k_ilucp(CpArgs A)
 #undef CP_FAIL
 }
 
+__global__ void __launch_bounds__(64) k_ilucp(CpArgs A) { cp_chain(A); }
+// several chains, one workgroup each (ILUCPPreconditioner.batch): the member's record is read once, wave-uniformly, before its first step;
+// members share nothing -- one that gives up writes its own ctrl words and returns
+__global__ void __launch_bounds__(64) k_ilucp_batch(const CpArgs *__restrict__ args)
+{
+    const CpArgs A = args[blockIdx.x];
+    cp_chain(A);
+}
+// chain_launch's two forms of this kind (common.h)
+void ilucp_chain_kernel(hipStream_t st, const void *args, int count)
+{
+    if (count == 0) hipLaunchKernelGGL(k_ilucp, dim3(1), dim3(64), 0, st, *static_cast<const CpArgs *>(args));
+    else hipLaunchKernelGGL(k_ilucp_batch, dim3((unsigned)count), dim3(64), 0, st, static_cast<const CpArgs *>(args));
+}
+
 // ---------------------------------------------- set-up and the stores -> matrices ----------------------------------------------
 __global__ void k_cp_init(int32_t n, const int32_t *__restrict__ Cp, int32_t *perm, int32_t *iperm, int32_t *nonpiv, int32_t *listA, int32_t *headA,
                           int32_t *firstA, int32_t *listL, int32_t *startU, DpRec *zrec, DpRec *wrec)
@@ -398,16 +414,11 @@ int ilucp_factor(hipStream_t st, const DevMat &C, int32_t max_fill_in, double th
         ILUPP_HIP(hipcub::DeviceRadixSort::SortKeys(b_tmp.p, tb, b_k0.as<unsigned long long>(), b_k1.as<unsigned long long>(), n, 0, 64, st));
         hipLaunchKernelGGL(k_cp_chains, dim3((n + 255) / 256), dim3(256), 0, st, n, b_k1.as<unsigned long long>(), a.listA, a.headA);
     }
-    EventPair ev;
-    ILUPP_HIP(ev.create());
-    ILUPP_HIP(hipEventRecord(ev.a, st));
-    hipLaunchKernelGGL(k_ilucp, dim3(1), dim3(64), 0, st, a);
-    ILUPP_HIP(hipEventRecord(ev.b, st));
+    float ms = 0.f;
+    { const int rc = chain_launch(st, &a, sizeof(a), CHAIN_CP, &ms); if (rc) return rc; }       // (alone, or with the other chains of a batch)
     int32_t ctrl[8] = {0};
     ILUPP_HIP(hipMemcpyAsync(ctrl, a.ctrl, sizeof(ctrl), hipMemcpyDeviceToHost, st));
     ILUPP_HIP(hipStreamSynchronize(st));
-    float ms = 0.f;
-    ILUPP_HIP(hipEventElapsedTime(&ms, ev.a, ev.b));
     if (kernel_ms) *kernel_ms = ms;
     if (getenv("ILUPP_DEBUG")) fprintf(stderr, "[ilupp] ilucp: n %d, stores of %lld: status %d at step %d, %.2f ms\n", n, (long long)reserved, ctrl[0], ctrl[5], ms);
     if (ctrl[0] != 0) { set_error("ILUCP4: Insufficient memory reserved. Increase mem_factor"); return ILUPP_ERR_MEMORY; }

@@ -119,7 +119,8 @@ __device__ void tp_select(const TpArgs &A, int ns, int n_L, int n_U, double tau_
     DP_SYNC();
 }
 
-__global__ void __launch_bounds__(64) k_ilutp(TpArgs A)
+// the chain of one matrix, walked by one wave (the single and the batched kernel are this body)
+__device__ __forceinline__ void tp_chain(const TpArgs &A)
 {
     const int lane = threadIdx.x;
     const unsigned long long lt = (1ull << lane) - 1ull;
@@ -232,6 +233,21 @@ __global__ void __launch_bounds__(64) k_ilutp(TpArgs A)
 #undef TP_FAIL
 }
 
+__global__ void __launch_bounds__(64) k_ilutp(TpArgs A) { tp_chain(A); }
+// several chains, one workgroup each (ILUTPPreconditioner.batch): the member's record is read once, wave-uniformly, before its first row;
+// members share nothing -- one that gives up writes its own ctrl words and returns
+__global__ void __launch_bounds__(64) k_ilutp_batch(const TpArgs *__restrict__ args)
+{
+    const TpArgs A = args[blockIdx.x];
+    tp_chain(A);
+}
+// chain_launch's two forms of this kind (common.h)
+void ilutp_chain_kernel(hipStream_t st, const void *args, int count)
+{
+    if (count == 0) hipLaunchKernelGGL(k_ilutp, dim3(1), dim3(64), 0, st, *static_cast<const TpArgs *>(args));
+    else hipLaunchKernelGGL(k_ilutp_batch, dim3((unsigned)count), dim3(64), 0, st, static_cast<const TpArgs *>(args));
+}
+
 __global__ void k_tp_init(int32_t n, int32_t *perm, int32_t *iperm, int32_t *occ)
 {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -282,16 +298,11 @@ int ilutp_factor(hipStream_t st, const DevMat &A, int32_t max_fill_in, double th
     ILUPP_HIP(hipMemsetAsync(a.Uptr, 0, sizeof(int32_t), st));
     ILUPP_HIP(hipMemsetAsync(a.Lptr, 0, sizeof(int32_t), st));
     hipLaunchKernelGGL(k_tp_init, dim3((n + 255) / 256), dim3(256), 0, st, n, a.perm, a.iperm, a.occ);
-    EventPair ev;
-    ILUPP_HIP(ev.create());
-    ILUPP_HIP(hipEventRecord(ev.a, st));
-    hipLaunchKernelGGL(k_ilutp, dim3(1), dim3(64), 0, st, a);
-    ILUPP_HIP(hipEventRecord(ev.b, st));
+    float ms = 0.f;
+    { const int rc = chain_launch(st, &a, sizeof(a), CHAIN_TP, &ms); if (rc) return rc; }       // (alone, or with the other chains of a batch)
     int32_t ctrl[8] = {0};
     ILUPP_HIP(hipMemcpyAsync(ctrl, a.ctrl, sizeof(ctrl), hipMemcpyDeviceToHost, st));
     ILUPP_HIP(hipStreamSynchronize(st));
-    float ms = 0.f;
-    ILUPP_HIP(hipEventElapsedTime(&ms, ev.a, ev.b));
     if (kernel_ms) *kernel_ms = ms;
     if (getenv("ILUPP_DEBUG")) fprintf(stderr, "[ilupp] ilutp: n %d, stores of %lld: status %d at row %d, %.2f ms\n", n, (long long)reserved, ctrl[0], ctrl[5], ms);
     if (ctrl[0] == 3) { set_error("ILUTP2: memory reserved was insufficient."); return ILUPP_ERR_MEMORY; }

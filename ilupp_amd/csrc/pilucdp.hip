@@ -1344,7 +1344,7 @@ struct ChainBatch {
     std::mutex mu;
     std::condition_variable cv;
     int live = 0;                                   // workers that may still hand in a launch
-    struct Item { const DpArgs *args; hipEvent_t before; float ms; bool done; int rc; int kind; };
+    struct Item { const void *args; size_t size; hipEvent_t before; float ms; bool done; int rc; int kind; };       // args: the kind's argument record (host)
     std::vector<Item *> waiting;
     hipStream_t stream = nullptr;
     std::string fire_msg;                           // why the last combined launch failed (read by every worker it failed for; under `mu`)
@@ -1366,8 +1366,26 @@ void chain_batch_destroy(ChainBatch *b)
 }
 void chain_batch_enter(ChainBatch *b) { t_batch = b; }
 
-// the kinds of chain a batch combines (the chain with pivoting in LDS; partialILUC in LDS / with its vectors in memory)
-enum { CHAIN_DP_LDS = 0, CHAIN_PC_LDS = 1, CHAIN_PC_MEM = 2, CHAIN_KINDS = 3 };
+// the kinds of chain a batch combines (common.h: CHAIN_*): the size of a kind's argument record, and its kernel -- count == 0: the single
+// kernel with the host record `args` by value, count > 0: the batched kernel over `count` records in device memory
+static void dp_lds_kernel(hipStream_t st, const void *args, int count)
+{
+    if (count == 0) hipLaunchKernelGGL(k_pilucdp_lds, dim3(1), dim3(64), 0, st, *static_cast<const DpArgs *>(args));
+    else hipLaunchKernelGGL(k_pilucdp_lds_batch, dim3((unsigned)count), dim3(64), 0, st, static_cast<const DpArgs *>(args));
+}
+static void pc_lds_kernel(hipStream_t st, const void *args, int count)
+{
+    if (count == 0) hipLaunchKernelGGL(k_piluc_chain, dim3(1), dim3(64), 0, st, *static_cast<const DpArgs *>(args));
+    else hipLaunchKernelGGL(k_piluc_chain_batch, dim3((unsigned)count), dim3(64), 0, st, static_cast<const DpArgs *>(args));
+}
+static void pc_mem_kernel(hipStream_t st, const void *args, int count)
+{
+    if (count == 0) hipLaunchKernelGGL(k_piluc_chain_mem, dim3(1), dim3(64), 0, st, *static_cast<const DpArgs *>(args));
+    else hipLaunchKernelGGL(k_piluc_chain_mem_batch, dim3((unsigned)count), dim3(64), 0, st, static_cast<const DpArgs *>(args));
+}
+typedef void (*ChainKernel)(hipStream_t st, const void *args, int count);
+static const ChainKernel kChainKernel[CHAIN_KINDS] = {dp_lds_kernel, pc_lds_kernel, pc_mem_kernel, ilucp_chain_kernel, ilutp_chain_kernel};
+constexpr size_t kChainAlign = 16;                  // a kind's records start on a multiple of this in the combined buffer (they hold pointers and doubles)
 
 // (mu held) every live worker waits here: their chains as one launch per kind (all launches in the queue before the one wait)
 static void chain_batch_fire(ChainBatch *b)
@@ -1376,29 +1394,37 @@ static void chain_batch_fire(ChainBatch *b)
     int rc = ILUPP_OK;
     float ms = 0.f;
     try {
-        // the arguments sorted by kind; `off` = where a kind starts
-        std::vector<DpArgs> host;
-        host.reserve((size_t)cnt);
-        int off[CHAIN_KINDS + 1] = {0};
+        // the arguments sorted by kind in one buffer; `off` = the byte where a kind starts, `num` = its members (all records of a kind have one size)
+        std::vector<unsigned char> host;
+        size_t off[CHAIN_KINDS] = {0};
+        int num[CHAIN_KINDS] = {0};
         for (int kind = 0; kind < CHAIN_KINDS; ++kind) {
-            for (int i = 0; i < cnt; ++i) if (b->waiting[(size_t)i]->kind == kind) host.push_back(*b->waiting[(size_t)i]->args);
-            off[kind + 1] = (int)host.size();
+            host.resize((host.size() + kChainAlign - 1) / kChainAlign * kChainAlign);
+            off[kind] = host.size();
+            for (int i = 0; i < cnt; ++i) {
+                const ChainBatch::Item *it = b->waiting[(size_t)i];
+                if (it->kind != kind) continue;
+                const unsigned char *p = static_cast<const unsigned char *>(it->args);
+                host.insert(host.end(), p, p + it->size);
+                ++num[kind];
+            }
         }
-        DpArgs *dev = nullptr;
-        ILUPP_HIP(hipMalloc(reinterpret_cast<void **>(&dev), sizeof(DpArgs) * (size_t)cnt));
-        struct Free { DpArgs *p; ~Free() { (void)hipFree(p); } } guard{dev};
-        ILUPP_HIP(hipMemcpyAsync(dev, host.data(), sizeof(DpArgs) * (size_t)cnt, hipMemcpyHostToDevice, b->stream));
+        unsigned char *dev = nullptr;
+        ILUPP_HIP(hipMalloc(reinterpret_cast<void **>(&dev), host.size() > 0 ? host.size() : 1));
+        struct Free { unsigned char *p; ~Free() { (void)hipFree(p); } } guard{dev};
+        ILUPP_HIP(hipMemcpyAsync(dev, host.data(), host.size(), hipMemcpyHostToDevice, b->stream));
         for (int i = 0; i < cnt; ++i) ILUPP_HIP(hipStreamWaitEvent(b->stream, b->waiting[(size_t)i]->before, 0));
         EventPair ev;
         ILUPP_HIP(ev.create());
         ILUPP_HIP(hipEventRecord(ev.a, b->stream));
-        if (off[1] > off[0]) hipLaunchKernelGGL(k_pilucdp_lds_batch, dim3((unsigned)(off[1] - off[0])), dim3(64), 0, b->stream, (const DpArgs *)(dev + off[0]));
-        if (off[2] > off[1]) hipLaunchKernelGGL(k_piluc_chain_batch, dim3((unsigned)(off[2] - off[1])), dim3(64), 0, b->stream, (const DpArgs *)(dev + off[1]));
-        if (off[3] > off[2]) hipLaunchKernelGGL(k_piluc_chain_mem_batch, dim3((unsigned)(off[3] - off[2])), dim3(64), 0, b->stream, (const DpArgs *)(dev + off[2]));
+        for (int kind = 0; kind < CHAIN_KINDS; ++kind)
+            if (num[kind] > 0) kChainKernel[kind](b->stream, dev + off[kind], num[kind]);
         ILUPP_HIP(hipEventRecord(ev.b, b->stream));
         ILUPP_HIP(hipStreamSynchronize(b->stream));
         ILUPP_HIP(hipEventElapsedTime(&ms, ev.a, ev.b));
-        if (getenv("ILUPP_DEBUG")) fprintf(stderr, "[ilupp] chains of a batch: %d with pivoting, %d + %d of partialILUC (LDS / memory), %.2f ms\n", off[1] - off[0], off[2] - off[1], off[3] - off[2], ms);
+        if (getenv("ILUPP_DEBUG"))
+            fprintf(stderr, "[ilupp] chains of a batch: %d with pivoting, %d + %d of partialILUC (LDS / memory), %d of ILUCP, %d of ILUTP, %.2f ms\n", num[CHAIN_DP_LDS],
+                    num[CHAIN_PC_LDS], num[CHAIN_PC_MEM], num[CHAIN_CP], num[CHAIN_TP], ms);
     } catch (const HipError &e) { b->fire_msg = std::string("HIP error in the batched chain launch: ") + hipGetErrorString(e.code); rc = ILUPP_ERR_HIP; }
     catch (const std::bad_alloc &) { b->fire_msg = "out of host memory in the batched chain launch"; rc = ILUPP_ERR_MEMORY; }
     catch (...) { b->fire_msg = "unexpected exception in the batched chain launch"; rc = ILUPP_ERR_HIP; }
@@ -1416,7 +1442,7 @@ void chain_batch_leave(ChainBatch *b)
 }
 
 // one chain launch: directly, or together with the other chains of the batch this thread works for
-static int chain_launch(hipStream_t st, const DpArgs &a, int kind, float *ms)         // kind: CHAIN_*, or -1: the chain with pivoting on global memory (never combined)
+int chain_launch(hipStream_t st, const void *args, size_t size, int kind, float *ms)  // kind: CHAIN_*, or -1: the chain with pivoting on global memory (never combined)
 {
     ChainBatch *b = t_batch;
     *ms = 0.f;
@@ -1424,16 +1450,14 @@ static int chain_launch(hipStream_t st, const DpArgs &a, int kind, float *ms)   
         EventPair ev;
         ILUPP_HIP(ev.create());
         ILUPP_HIP(hipEventRecord(ev.a, st));
-        if (kind == CHAIN_DP_LDS) hipLaunchKernelGGL(k_pilucdp_lds, dim3(1), dim3(64), 0, st, a);
-        else if (kind == CHAIN_PC_LDS) hipLaunchKernelGGL(k_piluc_chain, dim3(1), dim3(64), 0, st, a);
-        else if (kind == CHAIN_PC_MEM) hipLaunchKernelGGL(k_piluc_chain_mem, dim3(1), dim3(64), 0, st, a);
-        else hipLaunchKernelGGL(k_pilucdp, dim3(1), dim3(64), 0, st, a);
+        if (kind >= 0) kChainKernel[kind](st, args, 0);
+        else hipLaunchKernelGGL(k_pilucdp, dim3(1), dim3(64), 0, st, *static_cast<const DpArgs *>(args));
         ILUPP_HIP(hipEventRecord(ev.b, st));
         ILUPP_HIP(hipStreamSynchronize(st));
         ILUPP_HIP(hipEventElapsedTime(ms, ev.a, ev.b));
         return ILUPP_OK;
     }
-    ChainBatch::Item it{&a, nullptr, 0.f, false, ILUPP_OK, kind};
+    ChainBatch::Item it{args, size, nullptr, 0.f, false, ILUPP_OK, kind};
     ILUPP_HIP(hipEventCreateWithFlags(&it.before, hipEventDisableTiming));
     struct DropEvent { hipEvent_t e; ~DropEvent() { (void)hipEventDestroy(e); } } drop{it.before};
     ILUPP_HIP(hipEventRecord(it.before, st));                  // (what this thread queued for the chain: initialisation, enlarged stores)
@@ -1447,6 +1471,7 @@ static int chain_launch(hipStream_t st, const DpArgs &a, int kind, float *ms)   
     if (it.rc != ILUPP_OK) set_error(b->fire_msg);             // (in THIS worker's thread: the message is thread-local, the launch may have been another worker's)
     return it.rc;                                              // (the batch's stream has been synchronised: the chain's results are there)
 }
+static int chain_launch(hipStream_t st, const DpArgs &a, int kind, float *ms) { return chain_launch(st, &a, sizeof(a), kind, ms); }
 
 
 // ---------------------------------------------- the stores -> matrices ----------------------------------------------

@@ -244,6 +244,44 @@ T make_pivoted(Create create, bool by_rows, py::buffer data, py::buffer indices,
     return f;
 }
 
+// many matrices side by side (include/ilupp_hip.h: ilupp_hip_ilucp_create_batch / ilupp_hip_ilutp_create_batch): the objects the constructor
+// gives one at a time.  On an error every object already built is destroyed; the message names the first failing matrix and its status.
+template <class T, class CreateBatch>
+py::list make_pivoted_batch(CreateBatch create_batch, bool by_rows, py::list matrices, bool is_csr, int32_t max_fill_in, double threshold,
+                            double piv_tol, int32_t row_pos, double mem_factor)
+{
+    const int32_t cnt = (int32_t)matrices.size();
+    std::vector<Csr> as;
+    std::vector<const double *> D; std::vector<const int32_t *> I, P; std::vector<int32_t> N;
+    for (py::handle h : matrices) {
+        py::tuple t = py::reinterpret_borrow<py::tuple>(h);
+        as.push_back(borrow(py::reinterpret_borrow<py::buffer>(t[0]), py::reinterpret_borrow<py::buffer>(t[1]), py::reinterpret_borrow<py::buffer>(t[2]), is_csr));
+    }
+    for (const Csr &a : as) { D.push_back(a.val); I.push_back(a.idx); P.push_back(a.ptr); N.push_back(a.n); }
+    std::vector<ilupp_ilucp *> out((size_t)cnt, nullptr);
+    std::vector<int32_t> status((size_t)cnt, 0);
+    int rc = ILUPP_OK;
+    if (cnt > 0) {
+        py::gil_scoped_release release;
+        rc = create_batch(cnt, D.data(), I.data(), P.data(), N.data(), is_csr ? 1 : 0, max_fill_in, threshold, piv_tol, row_pos, mem_factor, out.data(),
+                          status.data());
+    }
+    if (rc != ILUPP_OK) {
+        const std::string msg = ilupp_hip_last_error();
+        int first = -1;
+        for (int32_t k = 0; k < cnt; ++k) { if (status[(size_t)k] != 0 && first < 0) first = k; if (out[(size_t)k]) ilupp_hip_ilucp_destroy(out[(size_t)k]); }
+        const std::string full = msg + " (matrix " + std::to_string(first) + " of the batch, status " + std::to_string(first >= 0 ? status[(size_t)first] : rc) + ")";
+        if (rc == ILUPP_ERR_UNSUPPORTED) { PyErr_SetString(PyExc_NotImplementedError, full.c_str()); throw py::error_already_set(); }
+        throw std::runtime_error(full);
+    }
+    // (every handle has an owner before the list is built: nothing leaks if a cast or an append throws)
+    std::vector<T> owned((size_t)cnt);
+    for (int32_t k = 0; k < cnt; ++k) { T &f = owned[(size_t)k]; f.h = out[(size_t)k]; out[(size_t)k] = nullptr; f.n = N[(size_t)k]; f.csr = is_csr; f.by_rows = by_rows; }
+    py::list res;
+    for (T &f : owned) res.append(py::cast(std::move(f)));
+    return res;
+}
+
 template <class T>
 py::class_<T> pivoted_members(py::module_ &m, const char *name)
 {
@@ -262,6 +300,7 @@ py::class_<T> pivoted_members(py::module_ &m, const char *name)
         })
         .def_property_readonly("total_nnz", [](const T &f) { return ilupp_hip_ilucp_total_nnz(f.h); })
         .def_property_readonly("zero_pivots", [](const T &f) { return ilupp_hip_ilucp_zero_pivots(f.h); })
+        .def_property_readonly("kernel_ms", [](const T &f) { float ms = 0.f; ok(ilupp_hip_ilucp_info(f.h, nullptr, nullptr, nullptr, &ms)); return ms; })
         .def("factors_info", [](const T &f) { return pivoted_factors(f); })
         .def("permutations", [](const T &f) { return pivoted_permutations(f); })
         .def_property_readonly("memory_used_calculations", [](const T &) { return 0.0; })
@@ -306,6 +345,15 @@ PYBIND11_MODULE(_ilupp_hip, m)
                          double piv_tol, int32_t row_pos, double mem_factor) {
             return make_pivoted<ILUCP>(ilupp_hip_ilucp_create, false, data, indices, indptr, is_csr, max_fill_in, threshold, piv_tol, row_pos, mem_factor);
         }));
+
+    m.def("ILUTPPreconditioner_batch", [](py::list matrices, bool is_csr, int32_t max_fill_in, double threshold, double piv_tol, int32_t row_pos,
+                                          double mem_factor) {
+        return make_pivoted_batch<ILUTP>(ilupp_hip_ilutp_create_batch, true, matrices, is_csr, max_fill_in, threshold, piv_tol, row_pos, mem_factor);
+    });
+    m.def("ILUCPPreconditioner_batch", [](py::list matrices, bool is_csr, int32_t max_fill_in, double threshold, double piv_tol, int32_t row_pos,
+                                          double mem_factor) {
+        return make_pivoted_batch<ILUCP>(ilupp_hip_ilucp_create_batch, false, matrices, is_csr, max_fill_in, threshold, piv_tol, row_pos, mem_factor);
+    });
 
     py::class_<Multilevel>(m, "MultilevelILUCDPPreconditioner")
         .def(py::init([](py::buffer data, py::buffer indices, py::buffer indptr, bool is_csr, py::object param) {

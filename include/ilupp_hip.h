@@ -21,8 +21,8 @@
  * process-wide mutex, also across devices -- a process that drives two GPUs gets no overlap of its constructions.  The reason: their
  * work arrays come from one process-wide pool of device blocks that knows nothing of streams -- a block released while the releasing
  * object's stream still uses it is only safe to hand to work queued on that same stream or after that stream has been waited for,
- * which every construction does before it returns.  The ways to build several factorisations at once: ilupp_hip_ml_create_batch (one
- * call, many matrices, the pool's blocks partitioned per worker), or one process per GPU (bench.py --gpus N, batched.py).
+ * which every construction does before it returns.  The ways to build several factorisations at once: ilupp_hip_ml_create_batch and
+ * ilupp_hip_ilucp_create_batch / ilupp_hip_ilutp_create_batch (one call, many matrices, the pool's blocks partitioned per worker), or one process per GPU (bench.py --gpus N, batched.py).
  */
 #ifndef ILUPP_HIP_H
 #define ILUPP_HIP_H
@@ -334,7 +334,8 @@ int ilupp_hip_solve(const double *data, const int32_t *indices, const int32_t *i
 /* ---------------------------------------------------------------------------------------------
  * ILUCP: Crout ILU with column pivoting.  Replaces binding.cpp:343-356 (ILUCPPreconditioner.__init__ ->
  * preconditioner_implementation.h:1117-1147 -> ILUCP4, ILUC.hpp:212-370) and its apply (triangular_solve_perm,
- * sparse_implementation.h:4166-4253).  A chain of n data-dependent steps: one wave of the GPU walks it (ilucp.hip).
+ * sparse_implementation.h:4166-4253).  A chain of n data-dependent steps: one wave of the GPU walks it (ilucp.hip); many matrices at
+ * once: ilupp_hip_ilucp_create_batch.
  * Errors: ILUPP_ERR_MEMORY ("ILUCP4: Insufficient memory reserved. Increase mem_factor", ILUC.hpp:287-289, :344-346).
  * ------------------------------------------------------------------------------------------- */
 typedef struct ilupp_ilucp ilupp_ilucp;
@@ -359,6 +360,20 @@ int ilupp_hip_ilucp_copy(const ilupp_ilucp *p, double *l_data, int32_t *l_indice
  * ("matrix_sparse::ILUTP2: encountered zero pivot in row N") */
 int ilupp_hip_ilutp_create(const double *data, const int32_t *indices, const int32_t *indptr, int32_t n, int is_csr, int32_t max_fill_in,
                            double threshold, double piv_tol, int32_t row_pos, double mem_factor, ilupp_ilucp **out);
+/* Many matrices at once, with the contract of ilupp_hip_ml_create_batch: `count` independent matrices (host arrays, all CSR or all CSC),
+ * one parameter set, one preconditioner each.  The constructions run side by side (one host thread and HIP stream per matrix, at most
+ * ILUPP_BATCH_WORKERS = 64 at a time, fewer if the device memory takes fewer), and their chains -- one wave each -- are launched TOGETHER,
+ * one workgroup per matrix, so that a batch's chains cost about what its slowest member's costs (64 chains of n = 12000: 1.0 - 1.3 x one,
+ * profiles/r09_pivot_batch.txt); kernel_ms of a member is that combined launch's time.  out[i] is NULL and status[i] the code of a member that failed (status may be NULL); members are independent, one
+ * failing does not stop the others; returns the first error, whose message starts "matrix i of the batch: ".  count == 0 returns
+ * ILUPP_OK without touching the device.  Every result is identical to what ilupp_hip_ilucp_create / ilupp_hip_ilutp_create gives for
+ * that matrix. */
+int ilupp_hip_ilucp_create_batch(int32_t count, const double *const *data, const int32_t *const *indices, const int32_t *const *indptr,
+                                 const int32_t *n, int is_csr, int32_t max_fill_in, double threshold, double piv_tol, int32_t row_pos,
+                                 double mem_factor, ilupp_ilucp **out, int32_t *status);
+int ilupp_hip_ilutp_create_batch(int32_t count, const double *const *data, const int32_t *const *indices, const int32_t *const *indptr,
+                                 const int32_t *n, int is_csr, int32_t max_fill_in, double threshold, double piv_tol, int32_t row_pos,
+                                 double mem_factor, ilupp_ilucp **out, int32_t *status);
 
 /* ---------------------------------------------------------------------------------------------
  * Measurement hooks used by bench.py (not part of the reference's surface).
