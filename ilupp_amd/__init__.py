@@ -270,6 +270,35 @@ class ILUCPPreconditioner(_HipPreconditioner):
         return left, right
 
 
+def apply_batch(preconditioners, vectors, transpose=False):
+    """``[P @ b for P, b in zip(preconditioners, vectors)]`` (with ``transpose=True``: ``P.T @ b``) for :class:`ILUCPPreconditioner` /
+    :class:`ILUTPPreconditioner` instances, mixed at will, as ONE native call: one kernel launch applies all members side by side, one
+    workgroup each with the unknowns in LDS (``ilupp_hip_pivot_apply_batch``), where the loop applies them one after the other on one
+    CU.  Returns a list of new arrays, bit for bit what the loop gives; the inputs are not modified.  A member too large for the
+    kernel (n > 20 479 on an MI355X; a member of n > 4 096 that would have the launch to itself), or whose factors have an empty row, is
+    applied alone inside the same call.
+
+    TypeError for a member of any other class, ValueError for lists of unequal length or a vector of the wrong length -- all before any
+    native call; an empty list gives ``[]``.  Out of scope: the device classes (``ilupp_amd.device.DevicePreconditioner`` has no "ILUTP" /
+    "ILUCP" kind; device vectors go through ``ilupp_amd.device.pivot_apply_batch_``) and a batched apply of
+    :class:`ILUppPreconditioner` objects."""
+    preconditioners, vectors = list(preconditioners), list(vectors)
+    for P in preconditioners:
+        if not isinstance(P, (ILUCPPreconditioner, ILUTPPreconditioner)):
+            raise TypeError("apply_batch takes ILUCPPreconditioner / ILUTPPreconditioner instances, got %s" % type(P).__name__)
+    if len(preconditioners) != len(vectors):
+        raise ValueError("%d preconditioners but %d vectors" % (len(preconditioners), len(vectors)))
+    out = []
+    for P, b in zip(preconditioners, vectors):
+        y = np.array(b, dtype=np.float64, copy=True).ravel()
+        if y.shape[0] != P.shape[0]:
+            raise ValueError("vector of %d elements for a preconditioner of dimension %d" % (y.shape[0], P.shape[0]))
+        out.append(y)
+    if out:
+        _backend.pivot_apply_batch([P.pr for P in preconditioners], out, bool(transpose))
+    return out
+
+
 class ILU0Preconditioner(_BlockApply, _HipPreconditioner):
     """ILU(0): incomplete LU in the pattern of A."""
 

@@ -160,6 +160,13 @@ def lib():
     L.ilupp_hip_ilucp_destroy.argtypes = [_VP]
     L.ilupp_hip_ilucp_destroy.restype = None
     L.ilupp_hip_ilucp_apply.argtypes = [_VP, _VP, ctypes.c_int64, ctypes.c_int]
+    L.ilupp_hip_ilucp_apply_device.argtypes = [_VP, _VP, ctypes.c_int64, ctypes.c_int, ctypes.c_int]
+    L.ilupp_hip_pivot_apply_batch_device.argtypes = [ctypes.c_int32, ctypes.POINTER(_VP), _VP, ctypes.POINTER(ctypes.c_int64), ctypes.c_int,
+                                                     ctypes.c_int, _I32P]
+    L.ilupp_hip_pivot_apply_batch.argtypes = [ctypes.c_int32, ctypes.POINTER(_VP), ctypes.POINTER(_VP), ctypes.POINTER(ctypes.c_int64),
+                                              ctypes.c_int, _I32P]
+    L.ilupp_hip_pivot_apply_batch_max_n.argtypes = []
+    L.ilupp_hip_pivot_apply_batch_max_n.restype = ctypes.c_int64
     L.ilupp_hip_ilucp_total_nnz.argtypes = [_VP]
     L.ilupp_hip_ilucp_total_nnz.restype = ctypes.c_int64
     L.ilupp_hip_ilucp_zero_pivots.argtypes = [_VP]
@@ -196,6 +203,7 @@ ABI_SYMBOLS = [
     "ilupp_hip_ml_level_copy", "ilupp_hip_ml_timings", "ilupp_hip_solve", "ilupp_hip_ml_create_batch",
     "ilupp_hip_ilucp_create", "ilupp_hip_ilucp_destroy", "ilupp_hip_ilucp_apply", "ilupp_hip_ilucp_total_nnz", "ilupp_hip_ilucp_zero_pivots",
     "ilupp_hip_ilucp_info", "ilupp_hip_ilucp_copy", "ilupp_hip_ilutp_create", "ilupp_hip_ilucp_create_batch", "ilupp_hip_ilutp_create_batch",
+    "ilupp_hip_ilucp_apply_device", "ilupp_hip_pivot_apply_batch_device", "ilupp_hip_pivot_apply_batch", "ilupp_hip_pivot_apply_batch_max_n",
     "ilupp_hip_apply_block", "ilupp_hip_apply_block_device", "ilupp_hip_block_path",
     "ilupp_hip_spmm_device", "ilupp_hip_block_dot_device", "ilupp_hip_cg_block_update_device", "ilupp_hip_bicgstab_block_update_device",
 ]
@@ -735,6 +743,12 @@ class PivotedPreconditioner:
     def apply_trans(self, x):
         self._solve(x, 1)
 
+    def apply_device(self, dptr, n, transpose=False, sync=True):
+        """in place on a device vector of n doubles (ilupp_hip_ilucp_apply_device), ordered on the caller's stream (set_caller_stream)"""
+        rc = lib().ilupp_hip_ilucp_apply_device(self._h, dptr, int(n), 1 if transpose else 0, 1 if sync else 0)
+        if rc:
+            _raise(rc)
+
     @property
     def total_nnz(self):
         return int(lib().ilupp_hip_ilucp_total_nnz(self._h))
@@ -847,3 +861,66 @@ def ILUCPPreconditioner_batch(matrices, is_csr, max_fill_in, threshold, piv_tol,
 def ILUTPPreconditioner_batch(matrices, is_csr, max_fill_in, threshold, piv_tol, row_pos, mem_factor):
     """one ILUTP preconditioner per matrix of `matrices`, as ILUCPPreconditioner_batch (ilupp_hip_ilutp_create_batch)"""
     return _pivoted_batch(lib().ilupp_hip_ilutp_create_batch, True, matrices, is_csr, max_fill_in, threshold, piv_tol, row_pos, mem_factor)
+
+
+def _member_handles(members):
+    cnt = len(members)
+    H = (_VP * cnt)()
+    for k, m in enumerate(members):
+        if not isinstance(m, PivotedPreconditioner):
+            raise TypeError("a batched apply takes ILUCP / ILUTP preconditioners, got %s" % type(m).__name__)
+        H[k] = m._h
+    return H
+
+
+def pivot_apply_batch(members, arrays, transpose):
+    """the applies of `members` (PivotedPreconditioner objects of either kind) on `arrays` (writable contiguous float64 vectors, one per
+    member), in place, with ONE launch for all members that fit (ilupp_hip_pivot_apply_batch); returns the route of every member
+    (0 = the launch, 1 = too large, 2 = a factor with an empty row: the single apply inside the same call)"""
+    cnt = len(members)
+    if len(arrays) != cnt:
+        raise ValueError("%d preconditioners but %d vectors" % (cnt, len(arrays)))
+    if cnt == 0:
+        return []
+    H = _member_handles(members)
+    X, N = (_VP * cnt)(), (ctypes.c_int64 * cnt)()
+    keep = []
+    for k, (m, x) in enumerate(zip(members, arrays)):
+        mv = _check_real(x, "b")
+        if mv.readonly:
+            raise RuntimeError("b must be writable")
+        a = np.frombuffer(mv, dtype=np.float64)
+        if a.shape[0] != m._n:
+            raise RuntimeError("vector has wrong size for preconditioner!")
+        keep.append(a)
+        X[k], N[k] = a.ctypes.data, a.shape[0]
+    route = (ctypes.c_int32 * cnt)()
+    rc = lib().ilupp_hip_pivot_apply_batch(cnt, H, X, N, 1 if transpose else 0, route)
+    if rc:
+        _raise(rc)
+    return list(route)
+
+
+def pivot_apply_batch_device(members, dptr, offsets, transpose=False, sync=True):
+    """the same on device vectors: member k's vector starts `offsets[k]` doubles behind `dptr` (ilupp_hip_pivot_apply_batch_device),
+    ordered on the caller's stream (set_caller_stream); returns the routes"""
+    cnt = len(members)
+    if len(offsets) != cnt:
+        raise ValueError("%d preconditioners but %d offsets" % (cnt, len(offsets)))
+    if cnt == 0:
+        return []
+    H = _member_handles(members)
+    O = (ctypes.c_int64 * cnt)(*[int(o) for o in offsets])
+    route = (ctypes.c_int32 * cnt)()
+    rc = lib().ilupp_hip_pivot_apply_batch_device(cnt, H, dptr, O, 1 if transpose else 0, 1 if sync else 0, route)
+    if rc:
+        _raise(rc)
+    return list(route)
+
+
+def pivot_apply_batch_max_n():
+    """the largest n a member may have to take the batched launch on the current device (ILUPP_BATCH_APPLY_MAX_N applied)"""
+    v = int(lib().ilupp_hip_pivot_apply_batch_max_n())
+    if v < 0:
+        _raise(v)
+    return v

@@ -4,6 +4,7 @@
 #include <stdlib.h>
 #include <string.h>
 
+#include <algorithm>
 #include <atomic>
 #include <functional>
 #include <map>
@@ -2343,9 +2344,24 @@ struct ilupp_ilucp {
     double *tmp = nullptr, *xdev = nullptr;
     int32_t zero_pivots = 0;
     float kernel_ms = 0.f;
+    hipEvent_t batch_ev = nullptr;         // a batched apply that was not waited for reads this member (and writes tmp): what the member's own stream waits for next
 };
 
 namespace {
+
+// the member's own stream behind the batched launch that last used it (pivot_apply_batch_run), before anything else touches tmp or the factors go
+void after_batch(ilupp_ilucp *m)
+{
+    if (!m->batch_ev) return;
+    ILUPP_HIP(hipStreamWaitEvent(m->obj->stream, m->batch_ev, 0));
+    m->batch_ev = nullptr;
+}
+
+// ILUCP: COLUMN input + apply, ROW input + apply_trans start with the plain factor; ILUTP: ROW input + apply, COLUMN input + apply_trans
+bool pivot_plain_first(const ilupp_ilucp *m, int transpose)
+{
+    return m->row_kind ? ((transpose == 0) == m->input_csr) : ((transpose != 0) == m->input_csr);
+}
 
 __global__ void k_cp_map_indices(int64_t nnz, const int32_t *__restrict__ idx, const int32_t *__restrict__ map, int32_t *__restrict__ out)
 {
@@ -2371,6 +2387,7 @@ __global__ void k_cp_scatter(int32_t n, const double *__restrict__ t, const int3
 void ilucp_destroy(ilupp_ilucp *m)
 {
     if (!m) return;
+    if (m->batch_ev && m->obj) (void)hipStreamWaitEvent(m->obj->stream, m->batch_ev, 0);      // (destroy_obj waits for the stream)
     if (m->obj) destroy_obj(m->obj);
     m->U.release();
     for (void *q : {(void *)m->perm, (void *)m->tmp, (void *)m->xdev}) if (q) (void)pool_free(q);
@@ -2446,10 +2463,10 @@ int ilupp_hip_ilucp_apply(ilupp_ilucp *m, double *x, int64_t len, int transpose)
     const int32_t n = m->n;
     ilupp_precond *p = m->obj;
     hipStream_t st = p->stream;
+    after_batch(m);
     if (!m->xdev) ILUPP_HIP(pool_malloc(&m->xdev, sizeof(double) * (size_t)n));
     ILUPP_HIP(hipMemcpyAsync(m->xdev, x, sizeof(double) * (size_t)n, hipMemcpyHostToDevice, st));
-    // ILUCP: COLUMN input + apply, ROW input + apply_trans start with the plain factor; ILUTP: ROW input + apply, COLUMN input + apply_trans
-    const bool plain_first = m->row_kind ? ((transpose == 0) == m->input_csr) : ((transpose != 0) == m->input_csr);
+    const bool plain_first = pivot_plain_first(m, transpose);
     int rc;
     if (plain_first) {
         rc = apply_dev(p, m->xdev, 0);
@@ -2605,3 +2622,267 @@ extern "C" int ilupp_hip_ilutp_create_batch(int32_t count, const double *const *
     return pivot_create_batch(true, count, data, indices, indptr, n, is_csr, max_fill_in, threshold, piv_tol, row_pos, mem_factor, out, status);
     API_CATCH
 }
+
+// ---- many members applied at once: one launch, one workgroup per member (k_pivot_apply_batch, sptrsv_batch.hip) ----
+namespace {
+
+// the single apply in place on a device vector, on the member's own stream behind the caller's
+int pivot_apply_dev(ilupp_ilucp *m, double *x, int transpose)
+{
+    const int32_t n = m->n;
+    ilupp_precond *p = m->obj;
+    hipStream_t st = p->stream;
+    after_batch(m);
+    order_after_caller(st, p->sev[0]);
+    if (pivot_plain_first(m, transpose)) {
+        OR_RETURN(apply_dev(p, x, 0));
+        hipLaunchKernelGGL(k_cp_scatter, dim3((n + 255) / 256), dim3(256), 0, st, n, x, m->perm, m->tmp);
+    } else {
+        hipLaunchKernelGGL(k_cp_gather, dim3((n + 255) / 256), dim3(256), 0, st, n, x, m->perm, m->tmp);
+        OR_RETURN(apply_dev(p, m->tmp, 1));
+    }
+    ILUPP_HIP(hipGetLastError());
+    ILUPP_HIP(hipMemcpyAsync(x, m->tmp, sizeof(double) * (size_t)n, hipMemcpyDeviceToDevice, st));
+    return ILUPP_OK;
+}
+
+// What the batched apply keeps from call to call, one per device: its stream and events, the descriptor table (device copy and the pinned
+// host copy it was uploaded from: uploaded again only when a descriptor differs -- another member list, direction or vector layout), the
+// members' error words, and the staging of the host entry (one packed device buffer and its pinned host image).
+struct BatchScratch {
+    hipStream_t stream = nullptr;
+    hipEvent_t cev[2] = {nullptr, nullptr};       // ordering against the caller's stream
+    hipEvent_t in_ev = nullptr, done_ev = nullptr, up_ev = nullptr;      // the staged vectors are there; the launch is over; the table's upload is over
+    PivotApplyDesc *h_table = nullptr, *d_table = nullptr;
+    int32_t *d_err = nullptr;
+    int32_t cap = 0, used = 0;                    // descriptors allocated / valid
+    std::vector<PivotApplyDesc> fresh;
+    std::vector<int32_t> launched, route, h_err, status;      // member of workgroup k; per member: route, error word, code
+    double *d_stage = nullptr, *h_stage = nullptr;
+    size_t stage_cap = 0;
+};
+std::mutex g_batch_mu;
+std::map<int, BatchScratch> g_batch_scratch;
+
+BatchScratch &batch_scratch()
+{
+    int dev = 0;
+    ILUPP_HIP(hipGetDevice(&dev));
+    BatchScratch &S = g_batch_scratch[dev];
+    if (!S.up_ev) {
+        if (!S.stream) ILUPP_HIP(hipStreamCreateWithFlags(&S.stream, hipStreamNonBlocking));
+        for (hipEvent_t *e : {&S.cev[0], &S.cev[1], &S.in_ev, &S.done_ev, &S.up_ev})       // (up_ev comes last: a scratch that has it is complete)
+            if (!*e) ILUPP_HIP(hipEventCreateWithFlags(e, hipEventDisableTiming));
+    }
+    return S;
+}
+
+// n up to which a member goes to the launch: 8 n bytes of LDS must fit (ILUPP_BATCH_APPLY_MAX_N lowers it, read per call)
+int64_t batch_apply_max_n()
+{
+    int64_t cap_n = (int64_t)(pivot_apply_batch_lds_cap() / 8);
+    if (const char *e = getenv("ILUPP_BATCH_APPLY_MAX_N")) { const long long v = atoll(e); if (v >= 0 && v < cap_n) cap_n = v; }
+    return cap_n;
+}
+
+// Queue the applies of all members: route 0 = the launch (n within the LDS cap, object not degenerate), 1 = too large (for the LDS, or for
+// a launch it would have to itself) and 2 = degenerate through the single apply on the member's own stream.  Everything is joined on the scratch's stream when this returns; nothing is waited for.
+// staged: the vectors were put there by work on the scratch's stream (the host entry), not by the caller's stream.
+int pivot_apply_batch_run(BatchScratch &S, int32_t count, ilupp_ilucp *const *members, double *d_x, const int64_t *offsets, int transpose, bool staged)
+{
+    hipStream_t bs = S.stream;
+    if (!staged) order_after_caller(bs, S.cev[0]);
+    else ILUPP_HIP(hipEventRecord(S.in_ev, bs));
+    const int64_t cap_n = batch_apply_max_n();
+    S.route.assign((size_t)count, 0); S.status.assign((size_t)count, ILUPP_OK); S.h_err.assign((size_t)count, 0);
+    S.launched.clear(); S.fresh.clear();
+    size_t lds = 0;
+    for (int32_t i = 0; i < count; ++i) {
+        ilupp_ilucp *m = members[i];
+        ilupp_precond *p = m->obj;
+        if (m->n > cap_n) { S.route[(size_t)i] = 1; continue; }
+        // the two operands from the tables the single apply uses (apply_plan, sweep_parts, prepare_apply)
+        const bool plain_first = pivot_plain_first(m, transpose);
+        const ApplyPlan plan = apply_plan(p, plain_first ? 0 : 1);
+        PackedSweep *pf = nullptr, *pb = nullptr;
+        if (prepare_apply(p, plan, &pf, &pb) != ROUTE_SWEEPS || p->degenerate) { S.route[(size_t)i] = 2; continue; }
+        const DevMat &M1 = sweep_parts(p, plan.first).M, &M2 = sweep_parts(p, plan.second).M;
+        PivotApplyDesc d;
+        memset(&d, 0, sizeof(d));
+        d.n = m->n; d.kind1 = plan.first.kind; d.kind2 = plan.second.kind; d.plain_first = plain_first ? 1 : 0;
+        d.ptr1 = M1.ptr; d.idx1 = M1.idx; d.val1 = M1.val;
+        d.ptr2 = M2.ptr; d.idx2 = M2.idx; d.val2 = M2.val;
+        d.perm = m->perm; d.xoff = offsets[i]; d.tmp = m->tmp;
+        S.fresh.push_back(d);
+        S.launched.push_back(i);
+    }
+    // ONE member in the launch is one workgroup of 256 lanes walking all its rows, 0.06 ms + 0.015 ms per 1 000 rows, where the general sweeps
+    // of the single apply take 0.11 - 0.12 ms whatever n is: past n = 4 096 the member alone is faster on the single apply (n = 4 000: 0.92 -
+    // 1.18 x, 6 000: 1.2 - 1.5 x, 12 000: 1.9 - 2.5 x; two members of n = 12 000 break even, four take half the loop's time:
+    // profiles/r10_pivot_apply_batch.txt)
+    if (S.launched.size() == 1 && S.fresh[0].n > kSmallSweepMax) { S.route[(size_t)S.launched[0]] = 1; S.launched.clear(); S.fresh.clear(); }
+    const int32_t nl = (int32_t)S.launched.size();
+    if (nl > 0) {
+        // both arrays in LDS where 16 n bytes fit under the cap, else one: the launch takes what its largest member needs
+        const size_t cap_bytes = (size_t)cap_n * 8;
+        for (const PivotApplyDesc &d : S.fresh) {
+            const size_t two = (size_t)16 * (size_t)d.n, want = two <= cap_bytes ? two : (size_t)8 * (size_t)d.n;
+            if (want > lds) lds = want;
+        }
+        // (the kernel makes the same choice per member from the launch's size: 16 n <= lds exactly when 16 n <= the cap)
+        if (nl > S.cap) {
+            if (S.d_table) { ILUPP_HIP(hipStreamSynchronize(bs)); (void)hipFree(S.d_table); (void)hipFree(S.d_err); (void)hipHostFree(S.h_table); S.d_table = nullptr; S.d_err = nullptr; S.h_table = nullptr; }
+            S.cap = 0; S.used = 0;
+            const int32_t cap = nl < 64 ? 64 : nl;
+            ILUPP_HIP(hipMalloc(reinterpret_cast<void **>(&S.d_table), sizeof(PivotApplyDesc) * (size_t)cap));
+            ILUPP_HIP(hipMalloc(reinterpret_cast<void **>(&S.d_err), sizeof(int32_t) * (size_t)cap));
+            ILUPP_HIP(hipHostMalloc(reinterpret_cast<void **>(&S.h_table), sizeof(PivotApplyDesc) * (size_t)cap, hipHostMallocDefault));
+            S.cap = cap;
+        }
+        for (int32_t k = 0; k < nl; ++k) S.fresh[(size_t)k].err = S.d_err + k;
+        if (nl != S.used || memcmp(S.h_table, S.fresh.data(), sizeof(PivotApplyDesc) * (size_t)nl) != 0) {
+            ILUPP_HIP(hipEventSynchronize(S.up_ev));                    // (the upload before this one has read the pinned copy: long over)
+            memcpy(S.h_table, S.fresh.data(), sizeof(PivotApplyDesc) * (size_t)nl);
+            ILUPP_HIP(hipMemcpyAsync(S.d_table, S.h_table, sizeof(PivotApplyDesc) * (size_t)nl, hipMemcpyHostToDevice, bs));
+            ILUPP_HIP(hipEventRecord(S.up_ev, bs));
+            S.used = nl;
+        }
+        // behind whatever is still queued on a member's own stream (a single apply that was not waited for, the transposed storages of a first use)
+        for (int32_t k = 0; k < nl; ++k) {
+            ilupp_precond *p = members[S.launched[(size_t)k]]->obj;
+            if (hipStreamQuery(p->stream) == hipSuccess) continue;
+            (void)hipGetLastError();
+            ILUPP_HIP(hipEventRecord(p->sev[1], p->stream));
+            ILUPP_HIP(hipStreamWaitEvent(bs, p->sev[1], 0));
+        }
+        OR_RETURN(pivot_apply_batch_launch(bs, nl, S.d_table, d_x, lds));
+        ILUPP_HIP(hipEventRecord(S.done_ev, bs));
+        for (int32_t k = 0; k < nl; ++k) members[S.launched[(size_t)k]]->batch_ev = S.done_ev;      // (later single applies of the member come after it)
+    }
+    for (int32_t i = 0; i < count; ++i) {
+        if (S.route[(size_t)i] == 0) continue;
+        ilupp_ilucp *m = members[i];
+        hipStream_t st = m->obj->stream;
+        if (staged) ILUPP_HIP(hipStreamWaitEvent(st, S.in_ev, 0));
+        OR_RETURN(pivot_apply_dev(m, d_x + offsets[i], transpose));
+        ILUPP_HIP(hipEventRecord(m->obj->sev[1], st));
+        ILUPP_HIP(hipStreamWaitEvent(bs, m->obj->sev[1], 0));
+    }
+    return ILUPP_OK;
+}
+
+// wait for a batch that pivot_apply_batch_run queued and say how it went: status per member, the first failure returned and named by its number
+int pivot_apply_batch_finish(BatchScratch &S, int32_t count, ilupp_ilucp *const *members)
+{
+    const int32_t nl = (int32_t)S.launched.size();
+    std::vector<std::string> msgs((size_t)count);
+    for (int32_t i = 0; i < count; ++i)
+        if (S.route[(size_t)i] != 0) {
+            S.status[(size_t)i] = finish_apply(members[i]->obj);
+            if (S.status[(size_t)i]) msgs[(size_t)i] = g_last_error;
+        }
+    std::vector<int32_t> err((size_t)(nl > 0 ? nl : 1), 0);
+    if (nl > 0) ILUPP_HIP(d2h_async(S.stream, err.data(), S.d_err, sizeof(int32_t) * (size_t)nl));
+    ILUPP_HIP(stream_sync(S.stream));
+    for (int32_t k = 0; k < nl; ++k) {
+        const int32_t i = S.launched[(size_t)k];
+        members[i]->batch_ev = nullptr;
+        S.h_err[(size_t)i] = err[(size_t)k];
+        if (err[(size_t)k]) { S.status[(size_t)i] = ILUPP_ERR_TIMEOUT; msgs[(size_t)i] = "triangular solve: dependency wait timed out (factor not triangular?)"; }
+    }
+    for (int32_t i = 0; i < count; ++i)
+        if (S.status[(size_t)i]) { set_error("member " + std::to_string(i) + " of the batch: " + msgs[(size_t)i]); return S.status[(size_t)i]; }
+    return ILUPP_OK;
+}
+
+// null arguments, a negative count, a null member, a member named twice (its scratch vector serves one apply at a time): before any device call
+int pivot_batch_args(int32_t count, ilupp_ilucp *const *members, const void *a, const void *b)
+{
+    if (count < 0 || !members || !a || !b) { set_error("null argument"); return ILUPP_ERR_INVALID; }
+    for (int32_t i = 0; i < count; ++i) if (!members[i]) { set_error("null preconditioner"); return ILUPP_ERR_INVALID; }
+    std::vector<const ilupp_ilucp *> seen(members, members + count);
+    std::sort(seen.begin(), seen.end());
+    if (std::adjacent_find(seen.begin(), seen.end()) != seen.end()) { set_error("a preconditioner appears twice in the batch"); return ILUPP_ERR_INVALID; }
+    return ILUPP_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int ilupp_hip_ilucp_apply_device(ilupp_ilucp *m, double *d_x, int64_t len, int transpose, int sync)
+{
+    API_TRY
+    if (!m) { set_error("null preconditioner"); return ILUPP_ERR_INVALID; }
+    if (!d_x) { set_error("null argument"); return ILUPP_ERR_INVALID; }
+    if (len != m->n) { set_error("vector has wrong size for preconditioner!"); return ILUPP_ERR_WRONG_SIZE; }
+    const int rc = pivot_apply_dev(m, d_x, transpose);
+    if (rc) return rc;
+    if (sync) return finish_apply(m->obj);
+    order_caller_after(m->obj->stream, m->obj->sev[1]);
+    return ILUPP_OK;
+    API_CATCH
+}
+
+int ilupp_hip_pivot_apply_batch_device(int32_t count, ilupp_ilucp *const *members, double *d_x, const int64_t *offsets, int transpose, int sync,
+                                       int32_t *route)
+{
+    API_TRY
+    const int rc0 = pivot_batch_args(count, members, d_x, offsets);
+    if (rc0 || count == 0) return rc0;
+    std::lock_guard<std::mutex> lk(g_batch_mu);
+    BatchScratch &S = batch_scratch();
+    int rc = pivot_apply_batch_run(S, count, members, d_x, offsets, transpose, false);
+    if (route) for (int32_t i = 0; i < count; ++i) route[i] = S.route[(size_t)i];
+    if (rc) return rc;
+    if (sync) return pivot_apply_batch_finish(S, count, members);
+    order_caller_after(S.stream, S.cev[1]);
+    return ILUPP_OK;
+    API_CATCH
+}
+
+int ilupp_hip_pivot_apply_batch(int32_t count, ilupp_ilucp *const *members, double *const *x, const int64_t *len, int transpose, int32_t *route)
+{
+    API_TRY
+    const int rc0 = pivot_batch_args(count, members, x, len);
+    if (rc0) return rc0;
+    for (int32_t i = 0; i < count; ++i) {
+        if (!x[i]) { set_error("null argument"); return ILUPP_ERR_INVALID; }
+        if (len[i] != members[i]->n) { set_error("vector has wrong size for preconditioner!"); return ILUPP_ERR_WRONG_SIZE; }
+    }
+    if (count == 0) return ILUPP_OK;
+    std::lock_guard<std::mutex> lk(g_batch_mu);
+    BatchScratch &S = batch_scratch();
+    // all vectors through ONE device buffer: one packed upload, one download
+    std::vector<int64_t> off((size_t)count);
+    size_t total = 0;
+    for (int32_t i = 0; i < count; ++i) { off[(size_t)i] = (int64_t)total; total += (size_t)len[i]; }
+    if (total > S.stage_cap) {
+        if (S.d_stage) { ILUPP_HIP(hipStreamSynchronize(S.stream)); (void)hipFree(S.d_stage); (void)hipHostFree(S.h_stage); S.d_stage = nullptr; S.h_stage = nullptr; }
+        S.stage_cap = 0;
+        ILUPP_HIP(hipMalloc(reinterpret_cast<void **>(&S.d_stage), sizeof(double) * total));
+        ILUPP_HIP(hipHostMalloc(reinterpret_cast<void **>(&S.h_stage), sizeof(double) * total, hipHostMallocDefault));
+        S.stage_cap = total;
+    }
+    for (int32_t i = 0; i < count; ++i) memcpy(S.h_stage + off[(size_t)i], x[i], sizeof(double) * (size_t)len[i]);
+    ILUPP_HIP(hipMemcpyAsync(S.d_stage, S.h_stage, sizeof(double) * total, hipMemcpyHostToDevice, S.stream));
+    int rc = pivot_apply_batch_run(S, count, members, S.d_stage, off.data(), transpose, true);
+    if (route) for (int32_t i = 0; i < count; ++i) route[i] = S.route[(size_t)i];
+    if (rc) { (void)hipStreamSynchronize(S.stream); return rc; }
+    ILUPP_HIP(hipMemcpyAsync(S.h_stage, S.d_stage, sizeof(double) * total, hipMemcpyDeviceToHost, S.stream));
+    rc = pivot_apply_batch_finish(S, count, members);
+    // (a member that failed keeps its vector as it was; the others have theirs)
+    for (int32_t i = 0; i < count; ++i)
+        if (S.status[(size_t)i] == ILUPP_OK) memcpy(x[i], S.h_stage + off[(size_t)i], sizeof(double) * (size_t)len[i]);
+    return rc;
+    API_CATCH
+}
+
+int64_t ilupp_hip_pivot_apply_batch_max_n(void)
+{
+    API_TRY
+    return batch_apply_max_n();
+    API_CATCH
+}
+
+}  // extern "C"

@@ -544,6 +544,21 @@ int sptrsv_rows(hipStream_t st, SweepKind kind, const DevMat &M, double *rhs_and
 // sptrsv_small.hip: one workgroup, the unknowns in LDS (the small, dense levels of a multilevel preconditioner); rhs is left as it is
 static constexpr int32_t kSmallSweepMax = 4096;      // round 3 (one entry per trip): 20 against 27 ms per apply for a 7-level object of n = 700, no gain from n = 3 000 on; round 4 (up to four entries per trip): see DESIGN 4e
 int sptrsv_small(hipStream_t st, SweepKind kind, const DevMat &M, const double *rhs, double *out, int32_t *err);
+// sptrsv_batch.hip: the whole apply of many pivoting preconditioners in one launch, one workgroup per member (k_pivot_apply_batch).
+// One member: its two sweeps in the order they run (the triangle in the storage a gather sweep wants, and the manner), the permutation
+// and which side of the sweeps it stands on (plain_first: x[perm[k]] = t[k] after them; else y[i] = x[perm[i]] before them), its vector
+// (an offset from the launch's base pointer), its n doubles of scratch and its error word (1 = a dependency wait timed out).
+struct PivotApplyDesc {
+    int32_t n, kind1, kind2, plain_first;
+    const int32_t *ptr1, *idx1; const double *val1;
+    const int32_t *ptr2, *idx2; const double *val2;
+    const int32_t *perm;
+    int64_t xoff;
+    double *tmp;
+    int32_t *err;
+};
+size_t pivot_apply_batch_lds_cap();      // bytes of dynamic LDS a workgroup of the kernel may take on the current device: n <= cap / 8
+int pivot_apply_batch_launch(hipStream_t st, int32_t count, const PivotApplyDesc *d_table, double *d_x, size_t lds_bytes);
 
 // sptrsv_lvl.hip
 bool lvl_order(hipStream_t st, int mode, int32_t n, int64_t nnz, const int32_t *ptr, const int32_t *idx, const Schedule &sch,

@@ -355,6 +355,33 @@ PYBIND11_MODULE(_ilupp_hip, m)
         return make_pivoted_batch<ILUCP>(ilupp_hip_ilucp_create_batch, false, matrices, is_csr, max_fill_in, threshold, piv_tol, row_pos, mem_factor);
     });
 
+    // the applies of many ILUTP / ILUCP objects (mixed at will) on as many writable vectors, in place, with one launch for all members that
+    // fit (include/ilupp_hip.h: ilupp_hip_pivot_apply_batch); returns the route of every member
+    m.def("pivot_apply_batch", [](py::list members, py::list arrays, bool transpose) {
+        const size_t cnt = members.size();
+        if (arrays.size() != cnt) throw py::value_error(std::to_string(cnt) + " preconditioners but " + std::to_string(arrays.size()) + " vectors");
+        std::vector<ilupp_ilucp *> H;
+        std::vector<double *> X;
+        std::vector<int64_t> N;
+        std::vector<py::buffer_info> keep;
+        for (size_t k = 0; k < cnt; ++k) {
+            const Pivoted *f = nullptr;
+            if (py::isinstance<ILUTP>(members[k])) f = &members[k].cast<const ILUTP &>();
+            else if (py::isinstance<ILUCP>(members[k])) f = &members[k].cast<const ILUCP &>();
+            else throw py::type_error("a batched apply takes ILUCP / ILUTP preconditioners");
+            py::buffer_info v = reals(py::reinterpret_borrow<py::buffer>(arrays[k]), "b");
+            if (v.readonly) throw std::runtime_error("b must be writable");
+            if (v.shape[0] != f->n) throw std::runtime_error("vector has wrong size for preconditioner!");
+            H.push_back(f->h); X.push_back(static_cast<double *>(v.ptr)); N.push_back(v.shape[0]);
+            keep.push_back(std::move(v));
+        }
+        std::vector<int32_t> route(cnt, 0);
+        if (cnt > 0) ok(ilupp_hip_pivot_apply_batch((int32_t)cnt, H.data(), X.data(), N.data(), transpose ? 1 : 0, route.data()));
+        py::list out;
+        for (int32_t r : route) out.append(r);
+        return out;
+    });
+
     py::class_<Multilevel>(m, "MultilevelILUCDPPreconditioner")
         .def(py::init([](py::buffer data, py::buffer indices, py::buffer indptr, bool is_csr, py::object param) {
             const Csr a = borrow(data, indices, indptr, is_csr);

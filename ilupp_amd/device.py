@@ -173,6 +173,35 @@ class DevicePreconditioner:
         self.pr.sync()
 
 
+def pivot_apply_batch_(members, x, offsets, transpose=False):
+    """The applies of many ``ilupp_amd.ILUCPPreconditioner`` / ``ILUTPPreconditioner`` objects (mixed at will) in place on ONE contiguous
+    fp64 CUDA tensor: member k's vector is ``x[offsets[k] : offsets[k] + n_k]``; what lies between the vectors is left untouched.  One
+    kernel launch for all members that fit (``ilupp_hip_pivot_apply_batch_device``), ordered on torch's current stream, no host
+    synchronisation.  Returns the route of every member (0 = the launch, 1 = too large, 2 = a factor with an empty row: applied alone
+    inside the same call).  ValueError for a wrong tensor, unequal lengths or a vector that does not lie inside ``x``; TypeError for a
+    member of another class -- before any native call.  Out of scope: ``DevicePreconditioner("ILUTP" / "ILUCP")`` (construction from device
+    arrays) and a batched apply of the multilevel class."""
+    members, offsets = list(members), [int(o) for o in offsets]
+    if not isinstance(x, torch.Tensor) or x.dim() != 1 or x.dtype != torch.float64 or not x.is_cuda or not x.is_contiguous():
+        raise ValueError("x: expected a contiguous 1-D torch.float64 CUDA tensor")
+    if len(members) != len(offsets):
+        raise ValueError("%d preconditioners but %d offsets" % (len(members), len(offsets)))
+    natives = []
+    for P in members:
+        pr = getattr(P, "pr", P)
+        if not isinstance(pr, _native.PivotedPreconditioner):
+            raise TypeError("pivot_apply_batch_ takes ILUCPPreconditioner / ILUTPPreconditioner instances of the ctypes binding, got %s"
+                            % type(P).__name__)
+        natives.append(pr)
+    for pr, o in zip(natives, offsets):
+        if o < 0 or o + pr._n > x.numel():
+            raise ValueError("a vector of %d elements at offset %d does not lie inside x (%d elements)" % (pr._n, o, x.numel()))
+    if not natives:
+        return []
+    _on_current_stream()
+    return _native.pivot_apply_batch_device(natives, x.data_ptr(), offsets, transpose=transpose, sync=False)
+
+
 def cg(A, b, M=None, x0=None, maxiter=100, rtol=0.0, check_every=0, stats=None):
     """preconditioned conjugate gradients on device tensors.  No host round trip per iteration: the scalars stay 0-dim
     device tensors; the residual is only looked at every `check_every` iterations (0 = never: run maxiter iterations).

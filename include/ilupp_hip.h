@@ -375,6 +375,29 @@ int ilupp_hip_ilutp_create_batch(int32_t count, const double *const *data, const
                                  const int32_t *n, int is_csr, int32_t max_fill_in, double threshold, double piv_tol, int32_t row_pos,
                                  double mem_factor, ilupp_ilucp **out, int32_t *status);
 
+/* The single apply of an ILUCP / ILUTP object in place on a DEVICE vector of `len` doubles (both classes share the handle type), ordered on
+ * the caller's stream like ilupp_hip_apply_device: behind the work submitted to it so far, and with sync == 0 the caller's stream waits for
+ * the result instead of the host. */
+int ilupp_hip_ilucp_apply_device(ilupp_ilucp *p, double *d_x, int64_t len, int transpose, int sync);
+/* Many ILUCP / ILUTP objects (mixed at will, each at most once) applied at once: member i's vector is d_x + offsets[i] (offsets: a host
+ * array of `count` entries, in doubles), of length n_i, in place; what lies between the vectors is left untouched.  ONE launch for all
+ * members whose n fits the kernel's LDS cap (one workgroup per member: the permutation and both sweeps of the apply inside it, the unknowns
+ * in LDS -- k_pivot_apply_batch, sptrsv_batch.hip); a member that is too large (route 1: for the cap, or, with n > 4096, for a launch it
+ * would have to itself -- one workgroup is slower there than the single apply's sweeps) or whose factors have an empty row (route 2) goes
+ * through the single apply inside the same call, so the call succeeds wherever the loop of single applies would.  route (may be NULL)
+ * receives 0, 1 or 2 per member.  Every result has the bits of ilupp_hip_ilucp_apply.  Ordered on the caller's stream; sync == 0 returns
+ * without waiting (and without reading the members' error words), sync != 0 waits and reports a member whose sweep gave up as
+ * ILUPP_ERR_TIMEOUT, "member i of the batch: triangular solve: dependency wait timed out ..."; the other members' vectors are complete.
+ * ILUPP_BATCH_APPLY_MAX_N (read on every call) lowers the cap.  count == 0 returns ILUPP_OK without touching the device. */
+int ilupp_hip_pivot_apply_batch_device(int32_t count, ilupp_ilucp *const *members, double *d_x, const int64_t *offsets, int transpose, int sync,
+                                       int32_t *route);
+/* The same on host vectors x[i] of len[i] == n_i doubles, in place: all vectors staged through one device buffer (one packed upload, one
+ * download); waits for the result.  A member that failed keeps its vector as it was. */
+int ilupp_hip_pivot_apply_batch(int32_t count, ilupp_ilucp *const *members, double *const *x, const int64_t *len, int transpose, int32_t *route);
+/* the largest n that takes route 0 on the current device (what the device gives a workgroup in LDS, ILUPP_BATCH_APPLY_MAX_N applied);
+ * negative: an error code */
+int64_t ilupp_hip_pivot_apply_batch_max_n(void);
+
 /* ---------------------------------------------------------------------------------------------
  * Measurement hooks used by bench.py (not part of the reference's surface).
  * Times are GPU milliseconds from hipEvents recorded on the object's stream.
