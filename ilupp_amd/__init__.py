@@ -281,7 +281,8 @@ def apply_batch(preconditioners, vectors, transpose=False):
     TypeError for a member of any other class, ValueError for lists of unequal length or a vector of the wrong length -- all before any
     native call; an empty list gives ``[]``.  Out of scope: the device classes (``ilupp_amd.device.DevicePreconditioner`` has no "ILUTP" /
     "ILUCP" kind; device vectors go through ``ilupp_amd.device.pivot_apply_batch_``) and a batched apply of
-    :class:`ILUppPreconditioner` objects."""
+    :class:`ILUppPreconditioner` objects.  Many systems SOLVED side by side, the whole preconditioned BiCGstab loop in one launch:
+    ``ilupp_amd.device.bicgstab_batch``."""
     preconditioners, vectors = list(preconditioners), list(vectors)
     for P in preconditioners:
         if not isinstance(P, (ILUCPPreconditioner, ILUTPPreconditioner)):

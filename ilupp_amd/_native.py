@@ -165,6 +165,10 @@ def lib():
                                                      ctypes.c_int, _I32P]
     L.ilupp_hip_pivot_apply_batch.argtypes = [ctypes.c_int32, ctypes.POINTER(_VP), ctypes.POINTER(_VP), ctypes.POINTER(ctypes.c_int64),
                                               ctypes.c_int, _I32P]
+    L.ilupp_hip_pivot_bicgstab_batch_device.argtypes = [ctypes.c_int32, ctypes.POINTER(_VP), ctypes.POINTER(_VP), ctypes.POINTER(_VP), ctypes.POINTER(_VP),
+                                                        ctypes.POINTER(ctypes.c_int64), _VP, _VP, _VP, ctypes.POINTER(ctypes.c_int64), _VP,
+                                                        ctypes.c_int64, ctypes.c_int32, ctypes.c_double, ctypes.c_int32, _VP, _VP, _VP, _VP,
+                                                        ctypes.c_int, _I32P]
     L.ilupp_hip_pivot_apply_batch_max_n.argtypes = []
     L.ilupp_hip_pivot_apply_batch_max_n.restype = ctypes.c_int64
     L.ilupp_hip_ilucp_total_nnz.argtypes = [_VP]
@@ -204,6 +208,7 @@ ABI_SYMBOLS = [
     "ilupp_hip_ilucp_create", "ilupp_hip_ilucp_destroy", "ilupp_hip_ilucp_apply", "ilupp_hip_ilucp_total_nnz", "ilupp_hip_ilucp_zero_pivots",
     "ilupp_hip_ilucp_info", "ilupp_hip_ilucp_copy", "ilupp_hip_ilutp_create", "ilupp_hip_ilucp_create_batch", "ilupp_hip_ilutp_create_batch",
     "ilupp_hip_ilucp_apply_device", "ilupp_hip_pivot_apply_batch_device", "ilupp_hip_pivot_apply_batch", "ilupp_hip_pivot_apply_batch_max_n",
+    "ilupp_hip_pivot_bicgstab_batch_device",
     "ilupp_hip_apply_block", "ilupp_hip_apply_block_device", "ilupp_hip_block_path",
     "ilupp_hip_spmm_device", "ilupp_hip_block_dot_device", "ilupp_hip_cg_block_update_device", "ilupp_hip_bicgstab_block_update_device",
 ]
@@ -913,6 +918,32 @@ def pivot_apply_batch_device(members, dptr, offsets, transpose=False, sync=True)
     O = (ctypes.c_int64 * cnt)(*[int(o) for o in offsets])
     route = (ctypes.c_int32 * cnt)()
     rc = lib().ilupp_hip_pivot_apply_batch_device(cnt, H, dptr, O, 1 if transpose else 0, 1 if sync else 0, route)
+    if rc:
+        _raise(rc)
+    return list(route)
+
+
+def pivot_bicgstab_batch_device(members, matrices, b_ptr, x0_ptr, x_ptr, offsets, work_ptr, work_doubles, maxiter, rtol, check_every,
+                                iterations_ptr, flags_ptr, rr_ptr, init_ptr, sync=True):
+    """left-preconditioned BiCGstab for many small systems in ONE launch (ilupp_hip_pivot_bicgstab_batch_device): `matrices` is a list of
+    (data_ptr, indices_ptr, indptr_ptr, nnz) of device CSR arrays, one per member; member k's right-hand side, start (x0_ptr may be 0)
+    and result lie `offsets[k]` doubles behind b_ptr / x0_ptr / x_ptr; the other pointers are device arrays as the header describes
+    them.  Ordered on the caller's stream (set_caller_stream).  Returns the routes: members of route 1 or 2 are NOT solved."""
+    cnt = len(members)
+    if len(matrices) != cnt or len(offsets) != cnt:
+        raise ValueError("%d preconditioners but %d matrices and %d offsets" % (cnt, len(matrices), len(offsets)))
+    if cnt == 0:
+        return []
+    H = _member_handles(members)
+    D, I, P = (_VP * cnt)(), (_VP * cnt)(), (_VP * cnt)()
+    NNZ = (ctypes.c_int64 * cnt)()
+    for k, (d, i, p, nnz) in enumerate(matrices):
+        D[k], I[k], P[k], NNZ[k] = d, i, p, int(nnz)
+    O = (ctypes.c_int64 * cnt)(*[int(o) for o in offsets])
+    route = (ctypes.c_int32 * cnt)()
+    rc = lib().ilupp_hip_pivot_bicgstab_batch_device(cnt, H, D, I, P, NNZ, b_ptr, x0_ptr or None, x_ptr, O, work_ptr, int(work_doubles),
+                                                     int(maxiter), float(rtol), int(check_every), iterations_ptr, flags_ptr, rr_ptr,
+                                                     init_ptr, 1 if sync else 0, route)
     if rc:
         _raise(rc)
     return list(route)

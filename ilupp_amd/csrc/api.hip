@@ -2660,6 +2660,9 @@ struct BatchScratch {
     std::vector<int32_t> launched, route, h_err, status;      // member of workgroup k; per member: route, error word, code
     double *d_stage = nullptr, *h_stage = nullptr;
     size_t stage_cap = 0;
+    PivotSolveDesc *h_sys = nullptr, *d_sys = nullptr;      // the batched solve's second table (pinned host copy, device copy) and what says its upload is over
+    int32_t sys_cap = 0;
+    hipEvent_t sys_ev = nullptr;
 };
 std::mutex g_batch_mu;
 std::map<int, BatchScratch> g_batch_scratch;
@@ -2685,23 +2688,17 @@ int64_t batch_apply_max_n()
     return cap_n;
 }
 
-// Queue the applies of all members: route 0 = the launch (n within the LDS cap, object not degenerate), 1 = too large (for the LDS, or for
-// a launch it would have to itself) and 2 = degenerate through the single apply on the member's own stream.  Everything is joined on the scratch's stream when this returns; nothing is waited for.
-// staged: the vectors were put there by work on the scratch's stream (the host entry), not by the caller's stream.
-int pivot_apply_batch_run(BatchScratch &S, int32_t count, ilupp_ilucp *const *members, double *d_x, const int64_t *offsets, int transpose, bool staged)
+// Route and describe the members of a batched launch: route 0 = the launch (n <= cap_n, object not degenerate), 1 = too large, 2 = degenerate.
+// S.fresh / S.launched receive the descriptors and member numbers of route 0, from the tables the single apply uses (apply_plan,
+// sweep_parts, prepare_apply); xoff = offsets[i].
+void pivot_batch_describe(BatchScratch &S, int32_t count, ilupp_ilucp *const *members, const int64_t *offsets, int transpose, int64_t cap_n)
 {
-    hipStream_t bs = S.stream;
-    if (!staged) order_after_caller(bs, S.cev[0]);
-    else ILUPP_HIP(hipEventRecord(S.in_ev, bs));
-    const int64_t cap_n = batch_apply_max_n();
     S.route.assign((size_t)count, 0); S.status.assign((size_t)count, ILUPP_OK); S.h_err.assign((size_t)count, 0);
     S.launched.clear(); S.fresh.clear();
-    size_t lds = 0;
     for (int32_t i = 0; i < count; ++i) {
         ilupp_ilucp *m = members[i];
         ilupp_precond *p = m->obj;
         if (m->n > cap_n) { S.route[(size_t)i] = 1; continue; }
-        // the two operands from the tables the single apply uses (apply_plan, sweep_parts, prepare_apply)
         const bool plain_first = pivot_plain_first(m, transpose);
         const ApplyPlan plan = apply_plan(p, plain_first ? 0 : 1);
         PackedSweep *pf = nullptr, *pb = nullptr;
@@ -2716,48 +2713,76 @@ int pivot_apply_batch_run(BatchScratch &S, int32_t count, ilupp_ilucp *const *me
         S.fresh.push_back(d);
         S.launched.push_back(i);
     }
+}
+
+// The described members (at least one) made ready for their launch on the scratch's stream: the bytes of LDS the sweeps of the launch take
+// (returned), the error words, the descriptor table on the device (uploaded again only when a descriptor differs), and the stream behind
+// whatever is still queued on a member's own stream (a single apply that was not waited for, the transposed storages of a first use).
+size_t pivot_batch_stage(BatchScratch &S, ilupp_ilucp *const *members, int64_t cap_n)
+{
+    hipStream_t bs = S.stream;
+    const int32_t nl = (int32_t)S.launched.size();
+    // both arrays in LDS where 16 n bytes fit under the cap, else one: the launch takes what its largest member needs
+    size_t lds = 0;
+    const size_t cap_bytes = (size_t)cap_n * 8;
+    for (const PivotApplyDesc &d : S.fresh) {
+        const size_t two = (size_t)16 * (size_t)d.n, want = two <= cap_bytes ? two : (size_t)8 * (size_t)d.n;
+        if (want > lds) lds = want;
+    }
+    // (the kernel makes the same choice per member from the launch's size: 16 n <= lds exactly when 16 n <= the cap)
+    if (nl > S.cap) {
+        if (S.d_table) { ILUPP_HIP(hipStreamSynchronize(bs)); (void)hipFree(S.d_table); (void)hipFree(S.d_err); (void)hipHostFree(S.h_table); S.d_table = nullptr; S.d_err = nullptr; S.h_table = nullptr; }
+        S.cap = 0; S.used = 0;
+        const int32_t cap = nl < 64 ? 64 : nl;
+        ILUPP_HIP(hipMalloc(reinterpret_cast<void **>(&S.d_table), sizeof(PivotApplyDesc) * (size_t)cap));
+        ILUPP_HIP(hipMalloc(reinterpret_cast<void **>(&S.d_err), sizeof(int32_t) * (size_t)cap));
+        ILUPP_HIP(hipHostMalloc(reinterpret_cast<void **>(&S.h_table), sizeof(PivotApplyDesc) * (size_t)cap, hipHostMallocDefault));
+        S.cap = cap;
+    }
+    for (int32_t k = 0; k < nl; ++k) S.fresh[(size_t)k].err = S.d_err + k;
+    if (nl != S.used || memcmp(S.h_table, S.fresh.data(), sizeof(PivotApplyDesc) * (size_t)nl) != 0) {
+        ILUPP_HIP(hipEventSynchronize(S.up_ev));                    // (the upload before this one has read the pinned copy: long over)
+        memcpy(S.h_table, S.fresh.data(), sizeof(PivotApplyDesc) * (size_t)nl);
+        ILUPP_HIP(hipMemcpyAsync(S.d_table, S.h_table, sizeof(PivotApplyDesc) * (size_t)nl, hipMemcpyHostToDevice, bs));
+        ILUPP_HIP(hipEventRecord(S.up_ev, bs));
+        S.used = nl;
+    }
+    for (int32_t k = 0; k < nl; ++k) {
+        ilupp_precond *p = members[S.launched[(size_t)k]]->obj;
+        if (hipStreamQuery(p->stream) == hipSuccess) continue;
+        (void)hipGetLastError();
+        ILUPP_HIP(hipEventRecord(p->sev[1], p->stream));
+        ILUPP_HIP(hipStreamWaitEvent(bs, p->sev[1], 0));
+    }
+    return lds;
+}
+
+// behind the launch: later single applies of its members come after it
+void pivot_batch_launched(BatchScratch &S, ilupp_ilucp *const *members)
+{
+    ILUPP_HIP(hipEventRecord(S.done_ev, S.stream));
+    for (int32_t i : S.launched) members[i]->batch_ev = S.done_ev;
+}
+
+// Queue the applies of all members: route 0 = the launch (n within the LDS cap, object not degenerate), 1 = too large (for the LDS, or for
+// a launch it would have to itself) and 2 = degenerate through the single apply on the member's own stream.  Everything is joined on the scratch's stream when this returns; nothing is waited for.
+// staged: the vectors were put there by work on the scratch's stream (the host entry), not by the caller's stream.
+int pivot_apply_batch_run(BatchScratch &S, int32_t count, ilupp_ilucp *const *members, double *d_x, const int64_t *offsets, int transpose, bool staged)
+{
+    hipStream_t bs = S.stream;
+    if (!staged) order_after_caller(bs, S.cev[0]);
+    else ILUPP_HIP(hipEventRecord(S.in_ev, bs));
+    const int64_t cap_n = batch_apply_max_n();
+    pivot_batch_describe(S, count, members, offsets, transpose, cap_n);
     // ONE member in the launch is one workgroup of 256 lanes walking all its rows, 0.06 ms + 0.015 ms per 1 000 rows, where the general sweeps
     // of the single apply take 0.11 - 0.12 ms whatever n is: past n = 4 096 the member alone is faster on the single apply (n = 4 000: 0.92 -
     // 1.18 x, 6 000: 1.2 - 1.5 x, 12 000: 1.9 - 2.5 x; two members of n = 12 000 break even, four take half the loop's time:
     // profiles/r10_pivot_apply_batch.txt)
     if (S.launched.size() == 1 && S.fresh[0].n > kSmallSweepMax) { S.route[(size_t)S.launched[0]] = 1; S.launched.clear(); S.fresh.clear(); }
-    const int32_t nl = (int32_t)S.launched.size();
-    if (nl > 0) {
-        // both arrays in LDS where 16 n bytes fit under the cap, else one: the launch takes what its largest member needs
-        const size_t cap_bytes = (size_t)cap_n * 8;
-        for (const PivotApplyDesc &d : S.fresh) {
-            const size_t two = (size_t)16 * (size_t)d.n, want = two <= cap_bytes ? two : (size_t)8 * (size_t)d.n;
-            if (want > lds) lds = want;
-        }
-        // (the kernel makes the same choice per member from the launch's size: 16 n <= lds exactly when 16 n <= the cap)
-        if (nl > S.cap) {
-            if (S.d_table) { ILUPP_HIP(hipStreamSynchronize(bs)); (void)hipFree(S.d_table); (void)hipFree(S.d_err); (void)hipHostFree(S.h_table); S.d_table = nullptr; S.d_err = nullptr; S.h_table = nullptr; }
-            S.cap = 0; S.used = 0;
-            const int32_t cap = nl < 64 ? 64 : nl;
-            ILUPP_HIP(hipMalloc(reinterpret_cast<void **>(&S.d_table), sizeof(PivotApplyDesc) * (size_t)cap));
-            ILUPP_HIP(hipMalloc(reinterpret_cast<void **>(&S.d_err), sizeof(int32_t) * (size_t)cap));
-            ILUPP_HIP(hipHostMalloc(reinterpret_cast<void **>(&S.h_table), sizeof(PivotApplyDesc) * (size_t)cap, hipHostMallocDefault));
-            S.cap = cap;
-        }
-        for (int32_t k = 0; k < nl; ++k) S.fresh[(size_t)k].err = S.d_err + k;
-        if (nl != S.used || memcmp(S.h_table, S.fresh.data(), sizeof(PivotApplyDesc) * (size_t)nl) != 0) {
-            ILUPP_HIP(hipEventSynchronize(S.up_ev));                    // (the upload before this one has read the pinned copy: long over)
-            memcpy(S.h_table, S.fresh.data(), sizeof(PivotApplyDesc) * (size_t)nl);
-            ILUPP_HIP(hipMemcpyAsync(S.d_table, S.h_table, sizeof(PivotApplyDesc) * (size_t)nl, hipMemcpyHostToDevice, bs));
-            ILUPP_HIP(hipEventRecord(S.up_ev, bs));
-            S.used = nl;
-        }
-        // behind whatever is still queued on a member's own stream (a single apply that was not waited for, the transposed storages of a first use)
-        for (int32_t k = 0; k < nl; ++k) {
-            ilupp_precond *p = members[S.launched[(size_t)k]]->obj;
-            if (hipStreamQuery(p->stream) == hipSuccess) continue;
-            (void)hipGetLastError();
-            ILUPP_HIP(hipEventRecord(p->sev[1], p->stream));
-            ILUPP_HIP(hipStreamWaitEvent(bs, p->sev[1], 0));
-        }
-        OR_RETURN(pivot_apply_batch_launch(bs, nl, S.d_table, d_x, lds));
-        ILUPP_HIP(hipEventRecord(S.done_ev, bs));
-        for (int32_t k = 0; k < nl; ++k) members[S.launched[(size_t)k]]->batch_ev = S.done_ev;      // (later single applies of the member come after it)
+    if (!S.launched.empty()) {
+        const size_t lds = pivot_batch_stage(S, members, cap_n);
+        OR_RETURN(pivot_apply_batch_launch(bs, (int32_t)S.launched.size(), S.d_table, d_x, lds));
+        pivot_batch_launched(S, members);
     }
     for (int32_t i = 0; i < count; ++i) {
         if (S.route[(size_t)i] == 0) continue;
@@ -2772,12 +2797,13 @@ int pivot_apply_batch_run(BatchScratch &S, int32_t count, ilupp_ilucp *const *me
 }
 
 // wait for a batch that pivot_apply_batch_run queued and say how it went: status per member, the first failure returned and named by its number
-int pivot_apply_batch_finish(BatchScratch &S, int32_t count, ilupp_ilucp *const *members)
+// (singles: the members of routes 1 and 2 went through their single applies -- not so behind the batched solve, which leaves them alone)
+int pivot_apply_batch_finish(BatchScratch &S, int32_t count, ilupp_ilucp *const *members, bool singles = true)
 {
     const int32_t nl = (int32_t)S.launched.size();
     std::vector<std::string> msgs((size_t)count);
     for (int32_t i = 0; i < count; ++i)
-        if (S.route[(size_t)i] != 0) {
+        if (singles && S.route[(size_t)i] != 0) {
             S.status[(size_t)i] = finish_apply(members[i]->obj);
             if (S.status[(size_t)i]) msgs[(size_t)i] = g_last_error;
         }
@@ -2875,6 +2901,66 @@ int ilupp_hip_pivot_apply_batch(int32_t count, ilupp_ilucp *const *members, doub
     for (int32_t i = 0; i < count; ++i)
         if (S.status[(size_t)i] == ILUPP_OK) memcpy(x[i], S.h_stage + off[(size_t)i], sizeof(double) * (size_t)len[i]);
     return rc;
+    API_CATCH
+}
+
+int ilupp_hip_pivot_bicgstab_batch_device(int32_t count, ilupp_ilucp *const *members, const double *const *d_data, const int32_t *const *d_indices,
+                                          const int32_t *const *d_indptr, const int64_t *nnz, const double *d_b, const double *d_x0, double *d_x,
+                                          const int64_t *offsets, double *d_work, int64_t work_doubles, int32_t maxiter, double rtol,
+                                          int32_t check_every, int64_t *d_iterations, int32_t *d_flags, double *d_rr, double *d_init, int sync,
+                                          int32_t *route)
+{
+    API_TRY
+    const int rc0 = pivot_batch_args(count, members, d_x, offsets);
+    if (rc0) return rc0;
+    if (!d_data || !d_indices || !d_indptr || !nnz || !d_b || !d_work || !d_iterations || !d_flags || !d_rr || !d_init) { set_error("null argument"); return ILUPP_ERR_INVALID; }
+    if (maxiter < 0 || check_every < 0) { set_error("maxiter and check_every must not be negative"); return ILUPP_ERR_INVALID; }
+    int64_t total = 0;
+    for (int32_t i = 0; i < count; ++i) {
+        if (!d_data[i] || !d_indices[i] || !d_indptr[i]) { set_error("null argument"); return ILUPP_ERR_INVALID; }
+        total += members[i]->n;
+    }
+    if (work_doubles < 7 * total) { set_error("workspace too small: 7 doubles per unknown of the batch"); return ILUPP_ERR_INVALID; }
+    if (count == 0) return ILUPP_OK;
+    std::lock_guard<std::mutex> lk(g_batch_mu);
+    BatchScratch &S = batch_scratch();
+    hipStream_t bs = S.stream;
+    if (!S.sys_ev) ILUPP_HIP(hipEventCreateWithFlags(&S.sys_ev, hipEventDisableTiming));
+    order_after_caller(bs, S.cev[0]);
+    // the cap of the apply's launch, lowered by what the dot scratch takes (ILUPP_BATCH_APPLY_MAX_N lowers both)
+    int64_t cap_n = batch_apply_max_n();
+    if (pivot_bicgstab_batch_max_n() < cap_n) cap_n = pivot_bicgstab_batch_max_n();
+    pivot_batch_describe(S, count, members, offsets, 0, cap_n);
+    if (route) for (int32_t i = 0; i < count; ++i) route[i] = S.route[(size_t)i];
+    const int32_t nl = (int32_t)S.launched.size();
+    if (nl == 0) return ILUPP_OK;
+    const size_t lds = pivot_batch_stage(S, members, cap_n);
+    if (nl > S.sys_cap) {
+        if (S.d_sys) { ILUPP_HIP(hipStreamSynchronize(bs)); (void)hipFree(S.d_sys); (void)hipHostFree(S.h_sys); S.d_sys = nullptr; S.h_sys = nullptr; }
+        S.sys_cap = 0;
+        const int32_t cap = nl < 64 ? 64 : nl;
+        ILUPP_HIP(hipMalloc(reinterpret_cast<void **>(&S.d_sys), sizeof(PivotSolveDesc) * (size_t)cap));
+        ILUPP_HIP(hipHostMalloc(reinterpret_cast<void **>(&S.h_sys), sizeof(PivotSolveDesc) * (size_t)cap, hipHostMallocDefault));
+        S.sys_cap = cap;
+    }
+    ILUPP_HIP(hipEventSynchronize(S.sys_ev));                       // (the upload before this one has read the pinned copy)
+    std::vector<int64_t> woff((size_t)count);
+    total = 0;
+    for (int32_t i = 0; i < count; ++i) { woff[(size_t)i] = 7 * total; total += members[i]->n; }
+    for (int32_t k = 0; k < nl; ++k) {
+        const int32_t i = S.launched[(size_t)k];
+        PivotSolveDesc &e = S.h_sys[k];
+        e.aval = d_data[i]; e.aidx = d_indices[i]; e.aptr = d_indptr[i];
+        e.woff = woff[(size_t)i]; e.member = i; e.pad = 0;
+    }
+    ILUPP_HIP(hipMemcpyAsync(S.d_sys, S.h_sys, sizeof(PivotSolveDesc) * (size_t)nl, hipMemcpyHostToDevice, bs));
+    ILUPP_HIP(hipEventRecord(S.sys_ev, bs));
+    OR_RETURN(pivot_bicgstab_batch_launch(bs, nl, S.d_table, S.d_sys, d_b, d_x0, d_x, d_work, lds, maxiter, rtol, check_every, d_iterations,
+                                          d_flags, d_rr, d_init));
+    pivot_batch_launched(S, members);
+    if (sync) return pivot_apply_batch_finish(S, count, members, false);
+    order_caller_after(bs, S.cev[1]);
+    return ILUPP_OK;
     API_CATCH
 }
 

@@ -559,6 +559,18 @@ struct PivotApplyDesc {
 };
 size_t pivot_apply_batch_lds_cap();      // bytes of dynamic LDS a workgroup of the kernel may take on the current device: n <= cap / 8
 int pivot_apply_batch_launch(hipStream_t st, int32_t count, const PivotApplyDesc *d_table, double *d_x, size_t lds_bytes);
+// the same file: the whole left-preconditioned BiCGstab solve of many small systems in one launch, one workgroup per member
+// (k_pivot_bicgstab_batch).  Beside a member's PivotApplyDesc (xoff: its slice of the packed b / x0 / x; tmp; err): its CSR matrix, where
+// its seven vectors of n start in the workspace, and which words of the per-member outputs are its own.
+struct PivotSolveDesc {
+    const double *aval; const int32_t *aidx, *aptr;
+    int64_t woff;
+    int32_t member, pad;
+};
+int64_t pivot_bicgstab_batch_max_n();    // the largest n of a member of that launch on the current device (LDS: dot scratch + 8 n bytes)
+int pivot_bicgstab_batch_launch(hipStream_t st, int32_t count, const PivotApplyDesc *d_table, const PivotSolveDesc *d_systems, const double *d_b,
+                                const double *d_x0, double *d_x, double *d_work, size_t sweep_bytes, int32_t maxiter, double rtol,
+                                int32_t check_every, int64_t *d_iterations, int32_t *d_flags, double *d_rr, double *d_init);
 
 // sptrsv_lvl.hip
 bool lvl_order(hipStream_t st, int mode, int32_t n, int64_t nnz, const int32_t *ptr, const int32_t *idx, const Schedule &sch,

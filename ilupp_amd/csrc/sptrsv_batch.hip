@@ -21,6 +21,9 @@
 // unknowns) when 16 n bytes fit into the launch's dynamic LDS; otherwise the first sweep also writes its rows to the member's `tmp` in HBM,
 // the barrier makes them visible to the workgroup (one CU, one L1), the ONE LDS array is filled with sentinels again and the second sweep
 // reads its right-hand sides from `tmp`.
+//
+// Second kernel, further down: k_pivot_bicgstab_batch, the whole left-preconditioned BiCGstab SOLVE of many small systems in one launch,
+// one workgroup per system, with this apply (pivot_apply_member) inside its loop.
 #include "common.h"
 
 namespace ilupp {
@@ -128,6 +131,23 @@ __device__ __forceinline__ void batch_sweep(const int kind, const int n, const i
     __syncthreads();
 }
 
+// The apply of one member by its workgroup, in place on x: `arr` holds lds_bytes of LDS for the sweeps' unknowns.  *s_fail != 0 afterwards:
+// a sweep gave up (a member that gives up in its first sweep never starts the second and leaves x as it was).
+__device__ __forceinline__ void pivot_apply_member(const PivotApplyDesc &d, double *x, unsigned long long *arr, const unsigned lds_bytes,
+                                                   unsigned *s_progress, int *s_fail)
+{
+    const int n = d.n;
+    const bool two = (size_t)16 * (size_t)n <= (size_t)lds_bytes;
+    // first sweep: right-hand sides from the member's vector (through perm when the gather comes first)
+    batch_sweep(d.kind1, n, d.ptr1, d.idx1, d.val1, arr, nullptr, x, d.plain_first ? nullptr : d.perm, two ? nullptr : d.tmp, nullptr,
+                s_progress, s_fail);
+    if (*s_fail == 0) {
+        // second sweep: right-hand sides = the first one's unknowns; its store is the member's vector (through perm when the plain solve came first)
+        batch_sweep(d.kind2, n, d.ptr2, d.idx2, d.val2, two ? arr + n : arr, two ? arr : nullptr, d.tmp, nullptr, x,
+                    d.plain_first ? d.perm : nullptr, s_progress, s_fail);
+    }
+}
+
 __global__ void __launch_bounds__(kBatchThreads)
 k_pivot_apply_batch(const PivotApplyDesc *__restrict__ table, double *xbase, const unsigned lds_bytes)
 {
@@ -135,19 +155,9 @@ k_pivot_apply_batch(const PivotApplyDesc *__restrict__ table, double *xbase, con
     __shared__ unsigned s_progress;
     __shared__ int s_fail;
     const PivotApplyDesc d = table[blockIdx.x];
-    const int n = d.n;
     if (threadIdx.x == 0) { s_progress = 0; s_fail = 0; }
     // (the first sweep's fill-and-barrier publishes the two words before any wave looks at them)
-    double *x = xbase + d.xoff;
-    const bool two = (size_t)16 * (size_t)n <= (size_t)lds_bytes;
-    // first sweep: right-hand sides from the member's vector (through perm when the gather comes first)
-    batch_sweep(d.kind1, n, d.ptr1, d.idx1, d.val1, lds, nullptr, x, d.plain_first ? nullptr : d.perm, two ? nullptr : d.tmp, nullptr,
-                &s_progress, &s_fail);
-    if (s_fail == 0) {
-        // second sweep: right-hand sides = the first one's unknowns; its store is the member's vector (through perm when the plain solve came first)
-        batch_sweep(d.kind2, n, d.ptr2, d.idx2, d.val2, two ? lds + n : lds, two ? lds : nullptr, d.tmp, nullptr, x,
-                    d.plain_first ? d.perm : nullptr, &s_progress, &s_fail);
-    }
+    pivot_apply_member(d, xbase + d.xoff, lds, lds_bytes, &s_progress, &s_fail);
     if (threadIdx.x == 0) *d.err = s_fail;          // (one writer per member: its own word, whatever the other members do)
 }
 
@@ -178,6 +188,252 @@ int pivot_apply_batch_launch(hipStream_t st, int32_t count, const PivotApplyDesc
     if (count <= 0) return ILUPP_OK;
     if (lds_bytes > pivot_apply_batch_lds_cap()) return ILUPP_ERR_UNSUPPORTED;
     hipLaunchKernelGGL(k_pivot_apply_batch, dim3((unsigned)count), dim3(kBatchThreads), lds_bytes, st, d_table, d_x, (unsigned)lds_bytes);
+    ILUPP_HIP(hipGetLastError());
+    return ILUPP_OK;
+}
+
+
+// ---- the whole left-preconditioned BiCGstab solve of MANY small systems in ONE launch: one workgroup per member --------------------
+// k_pivot_bicgstab_batch runs _bicgstab_block of ilupp_amd/device.py with k = 1, statement for statement, for its member: the SpMV of
+// k_spmv_rows (one sum per row in stored order from 0.0), the apply above, the dot products in the shape of ilupp_hip_block_dot_device for
+// this n, the updates of k_block_update<1>, IEEE division and the correctly rounded square root -- so every member has the bits of the
+// same solve done alone with those launches.  The seven vectors y, r, r0*, p, s, Ap, As lie in the member's part of the workspace; one CU
+// touches them (its L1 and L2 keep them), and every hand-over between two phases of the workgroup is a __syncthreads().
+//
+// Dynamic LDS: [2][2][kDotMaxNb] doubles of dot scratch (the chunks' partial sums of up to two dots at once, two buffers used in
+// turn), then the sweeps' one or two arrays of n.
+static constexpr int kDotMaxNb = 128;                          // chunks of a dot: n <= 256 kDotMaxNb
+static constexpr int kDotScratch = 2 * 2 * kDotMaxNb;          // doubles
+
+// the tree over the lower 64 of 256 values a wave holds as v[l] = (t[l] + t[l + 128]) + (t[l + 64] + t[l + 192]): strides 32 .. 1,
+// lane l < s takes v[l] + v[l + s] as sh[w] = sh[w] + sh[w + s] does; lane 0 holds the sum
+__device__ __forceinline__ double wave_tree(double v)
+{
+#pragma unroll
+    for (int s = 32; s > 0; s >>= 1) { const double o = __shfl_down(v, s); v = v + o; }
+    return v;
+}
+
+// ND (1 or 2) dot products a[q] . b[q] of n elements by the whole workgroup, in the shape of k_bdot_part<1> / k_bdot_finish: nb chunks of
+// `chunk` <= 256 consecutive rows; partial v of chunk c is 0.0 + a[lo + v] * b[lo + v] (0.0 past the chunk's end); the tree over the 256
+// partials -- strides 128 and 64 are the lane's own four values, the rest wave_tree; then the finishing tree over s0[t] = 0.0 +
+// partial[t] (0.0 from nb on).  A wave takes the chunks w, w + 4, ...; the partial sums meet in `part` (one barrier), and EVERY wave adds
+// them up, so every lane returns the same bits.  part: 2 * kDotMaxNb doubles, not the buffer of the call before.
+template <int ND>
+__device__ __forceinline__ void wg_dots(const int n, const int nb, const int chunk, const double *a0, const double *b0, const double *a1,
+                                        const double *b1, double *part, double *out)
+{
+    const int l = threadIdx.x & 63, w = threadIdx.x >> 6;
+    for (int c = w; c < nb; c += kBatchThreads / 64) {
+        const int lo = c * chunk, hi = min(n, lo + chunk);
+        double t[ND][4];
+#pragma unroll
+        for (int m = 0; m < 4; ++m) {
+            const int i = lo + l + 64 * m;
+#pragma unroll
+            for (int q = 0; q < ND; ++q) {
+                const double *a = q ? a1 : a0, *b = q ? b1 : b0;
+                double acc = 0.0;
+                if (i < hi) { const double p = a[i] * b[i]; acc = acc + p; }
+                t[q][m] = acc;
+            }
+        }
+#pragma unroll
+        for (int q = 0; q < ND; ++q) {
+            const double lo2 = t[q][0] + t[q][2], hi2 = t[q][1] + t[q][3];      // stride 128, then stride 64
+            const double v = wave_tree(lo2 + hi2);
+            if (l == 0) part[q * kDotMaxNb + c] = v;
+        }
+    }
+    __syncthreads();
+#pragma unroll
+    for (int q = 0; q < ND; ++q) {
+        double t[4];
+#pragma unroll
+        for (int m = 0; m < 4; ++m) {
+            const int i = l + 64 * m;
+            double s0 = 0.0;
+            if (i < nb) s0 = s0 + part[q * kDotMaxNb + i];
+            t[m] = s0;
+        }
+        const double lo2 = t[0] + t[2], hi2 = t[1] + t[3];
+        out[q] = __shfl(wave_tree(lo2 + hi2), 0);
+    }
+}
+
+// dst = A src: one lane per row, acc = acc + val * x in stored order from 0.0 (k_spmv_rows)
+__device__ __forceinline__ void wg_spmv(const int n, const int32_t *__restrict__ ptr, const int32_t *__restrict__ idx,
+                                        const double *__restrict__ val, const double *src, double *dst)
+{
+    for (int r = threadIdx.x; r < n; r += kBatchThreads) {
+        const int q0 = ptr[r], q1 = ptr[r + 1];
+        double acc = 0.0;
+        for (int q = q0; q < q1; q += kBG) {         // kBG entries' loads in flight together, added one after the other in stored order
+            int c[kBG];
+            double v[kBG], xv[kBG];
+#pragma unroll
+            for (int w = 0; w < kBG; ++w) if (q + w < q1) { c[w] = idx[q + w]; v[w] = val[q + w]; }
+#pragma unroll
+            for (int w = 0; w < kBG; ++w) if (q + w < q1) xv[w] = src[c[w]];
+#pragma unroll
+            for (int w = 0; w < kBG; ++w) if (q + w < q1) { const double p = v[w] * xv[w]; acc = acc + p; }
+        }
+        dst[r] = acc;
+    }
+}
+
+__device__ __forceinline__ bool scalar_ok(const double v) { return v != 0.0 && isfinite(v); }      // what a recurrence may divide by
+
+__global__ void __launch_bounds__(kBatchThreads)
+k_pivot_bicgstab_batch(const PivotApplyDesc *__restrict__ table, const PivotSolveDesc *__restrict__ systems, const double *bbase,
+                       const double *x0base, double *xbase, double *work, const unsigned sweep_bytes, const int maxiter, const double rtol,
+                       const int check_every, long long *iterations, int32_t *flags, double *rr_out, double *init_out)
+{
+    extern __shared__ unsigned long long lds[];
+    __shared__ unsigned s_progress;
+    __shared__ int s_fail;
+    const PivotApplyDesc d = table[blockIdx.x];
+    const PivotSolveDesc e = systems[blockIdx.x];
+    const int n = d.n, tid = threadIdx.x;
+    if (tid == 0) { s_progress = 0; s_fail = 0; }
+    double *dots = reinterpret_cast<double *>(lds);
+    unsigned long long *arr = lds + kDotScratch;
+    const int nb = (n + 255) / 256, chunk = (n + nb - 1) / nb;      // (n <= 256 kDotMaxNb: nb is below the dot's 1 024)
+    unsigned turn = 0;
+    auto part = [&]() { return dots + (turn++ & 1u) * (2 * kDotMaxNb); };
+    double *y = work + e.woff, *r = y + n, *r0 = r + n, *p = r0 + n, *s = p + n, *Ap = s + n, *As = Ap + n;
+    const double *b = bbase + d.xoff;
+    const double *x0 = x0base ? x0base + d.xoff : nullptr;
+    double *x = xbase + d.xoff;
+
+    // The loop as a sequence of HALF steps, so that the SpMV, the apply and the pair of dots behind it stand in the code once (the apply
+    // is two inlined sweeps: three copies of it would not fit the instruction cache):
+    //   half 0 (once):   y = x0 or 0; r0* = b (or b - A y); r = M^-1 r0*; r0* = r; p = r; init = sqrt(r.r); zero = (b.b == 0) | (init == 0)
+    //   half 1:          Ap = M^-1 (A p); rho = r.r0*; apr = Ap.r0*; alpha = rho / apr; s = r - alpha Ap
+    //   half 2:          As = M^-1 (A s); omega = (As.s) / (As.As); y += alpha p; y += omega s; r = s - omega As;
+    //                    beta = ((r.r0*) / rho) * (alpha / omega); p = p - omega Ap; p = beta p + r; the convergence test
+    for (int i = tid; i < n; i += kBatchThreads) y[i] = x0 ? x0[i] : 0.0;
+    __syncthreads();
+    bool failed = false, zero = false, active = false, converged = false, have_rr = false;
+    double init = 0.0, rho = 0.0, alpha = 0.0, rr = 0.0, v2[2];
+    long long iters = 0;
+    for (int half = 0, it = 0;; half = half == 1 ? 2 : 1) {
+        double *vec = half == 0 ? r : half == 1 ? Ap : As;
+        if (half != 0 || x0) {
+            wg_spmv(n, e.aptr, e.aidx, e.aval, half == 0 ? y : half == 1 ? p : s, half == 0 ? As : vec);
+            __syncthreads();
+        }
+        if (half == 0) {
+            if (x0) { for (int i = tid; i < n; i += kBatchThreads) r[i] = b[i] - As[i]; }
+            else { for (int i = tid; i < n; i += kBatchThreads) r[i] = b[i]; }
+            __syncthreads();
+        }
+        pivot_apply_member(d, vec, arr, sweep_bytes, &s_progress, &s_fail);
+        if (s_fail != 0) { failed = true; active = false; break; }
+        if (half == 0) {
+            for (int i = tid; i < n; i += kBatchThreads) { const double v = r[i]; r0[i] = v; p[i] = v; }
+            __syncthreads();
+        }
+        wg_dots<2>(n, nb, chunk, half == 2 ? As : r, half == 0 ? r : half == 1 ? r0 : s, half == 0 ? b : vec, half == 0 ? b : half == 1 ? r0 : As,
+                   part(), v2);
+        if (half == 0) {
+            init = __dsqrt_rn(v2[0]);
+            zero = v2[1] == 0.0 || init == 0.0;
+            active = !zero;
+            converged = zero;
+            if (!active || maxiter <= 0) break;
+        } else if (half == 1) {
+            rho = v2[0];
+            if (!(scalar_ok(rho) && scalar_ok(v2[1]))) { active = false; break; }      // breakdown: nothing more is touched, not converged
+            alpha = rho / v2[1];
+            for (int i = tid; i < n; i += kBatchThreads) { const double aap = alpha * Ap[i]; s[i] = r[i] - aap; }
+            __syncthreads();
+        } else {
+            const double omega = v2[0] / v2[1];
+            if (!scalar_ok(omega)) { active = false; break; }
+            for (int i = tid; i < n; i += kBatchThreads) {
+                const double ap = alpha * p[i];
+                double yv = y[i] + ap;
+                const double os = omega * s[i];
+                yv = yv + os;
+                y[i] = yv;
+                const double oas = omega * As[i];
+                r[i] = s[i] - oas;
+            }
+            __syncthreads();
+            wg_dots<1>(n, nb, chunk, r, r0, nullptr, nullptr, part(), v2);
+            const double beta = (v2[0] / rho) * (alpha / omega);
+            for (int i = tid; i < n; i += kBatchThreads) {
+                const double oap = omega * Ap[i];
+                const double pv = p[i] - oap;
+                const double bp = beta * pv;
+                p[i] = bp + r[i];
+            }
+            __syncthreads();
+            ++iters;
+            ++it;
+            if (check_every > 0 && it % check_every == 0 && rtol > 0.0) {
+                wg_dots<1>(n, nb, chunk, r, r, nullptr, nullptr, part(), v2);
+                rr = v2[0];
+                have_rr = true;                      // (r stays as it is from here to the exit when the loop ends now)
+                const double rel = __dsqrt_rn(rr) / init;
+                if (rel <= rtol) { converged = true; active = false; break; }
+            }
+            if (it >= maxiter) break;
+            have_rr = false;
+        }
+    }
+    if (!failed) {
+        if (!have_rr) { wg_dots<1>(n, nb, chunk, r, r, nullptr, nullptr, part(), v2); rr = v2[0]; }      // (r.r at the exit)
+        for (int i = tid; i < n; i += kBatchThreads) x[i] = y[i];
+    }
+    if (tid == 0) {                                  // (one writer per member: its own words, whatever the other members do)
+        *d.err = failed ? 1 : 0;
+        iterations[e.member] = iters;
+        flags[e.member] = (active ? 1 : 0) | (converged ? 2 : 0) | (failed ? 4 : 0) | (zero ? 8 : 0);
+        rr_out[e.member] = rr;
+        init_out[e.member] = init;
+    }
+}
+
+// bytes of dynamic LDS a workgroup of k_pivot_bicgstab_batch may take on the current device (as pivot_apply_batch_lds_cap)
+size_t pivot_bicgstab_batch_lds_cap()
+{
+    static thread_local int cap_dev = -1;
+    static thread_local size_t cap = 0;
+    int dev = 0;
+    ILUPP_HIP(hipGetDevice(&dev));
+    if (cap_dev != dev) {
+        int max_lds = 0;
+        ILUPP_HIP(hipDeviceGetAttribute(&max_lds, hipDeviceAttributeMaxSharedMemoryPerBlock, dev));
+        hipFuncAttributes fa;
+        ILUPP_HIP(hipFuncGetAttributes(&fa, reinterpret_cast<const void *>(&k_pivot_bicgstab_batch)));
+        const size_t room = (size_t)max_lds > fa.sharedSizeBytes ? (size_t)max_lds - fa.sharedSizeBytes : 0;
+        ILUPP_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_pivot_bicgstab_batch), hipFuncAttributeMaxDynamicSharedMemorySize, (int)room));
+        cap = room;
+        cap_dev = dev;
+    }
+    return cap;
+}
+
+// the largest n of a member of the solve's launch: the dot scratch and 8 n bytes for the sweeps fit, and the dot has at most kDotMaxNb chunks
+int64_t pivot_bicgstab_batch_max_n()
+{
+    const size_t cap = pivot_bicgstab_batch_lds_cap(), scratch = sizeof(double) * (size_t)kDotScratch;
+    const int64_t by_lds = cap > scratch ? (int64_t)((cap - scratch) / 8) : 0;
+    return by_lds < 256 * kDotMaxNb ? by_lds : 256 * kDotMaxNb;
+}
+
+// `count` members, one workgroup each; sweep_bytes of LDS for the sweeps of every workgroup (the dot scratch comes on top)
+int pivot_bicgstab_batch_launch(hipStream_t st, int32_t count, const PivotApplyDesc *d_table, const PivotSolveDesc *d_systems, const double *d_b,
+                                const double *d_x0, double *d_x, double *d_work, size_t sweep_bytes, int32_t maxiter, double rtol,
+                                int32_t check_every, int64_t *d_iterations, int32_t *d_flags, double *d_rr, double *d_init)
+{
+    if (count <= 0) return ILUPP_OK;
+    const size_t lds_bytes = sizeof(double) * (size_t)kDotScratch + sweep_bytes;
+    if (lds_bytes > pivot_bicgstab_batch_lds_cap()) return ILUPP_ERR_UNSUPPORTED;
+    hipLaunchKernelGGL(k_pivot_bicgstab_batch, dim3((unsigned)count), dim3(kBatchThreads), lds_bytes, st, d_table, d_systems, d_b, d_x0, d_x, d_work,
+                       (unsigned)sweep_bytes, (int)maxiter, rtol, (int)check_every, reinterpret_cast<long long *>(d_iterations), d_flags, d_rr, d_init);
     ILUPP_HIP(hipGetLastError());
     return ILUPP_OK;
 }

@@ -180,7 +180,8 @@ def pivot_apply_batch_(members, x, offsets, transpose=False):
     synchronisation.  Returns the route of every member (0 = the launch, 1 = too large, 2 = a factor with an empty row: applied alone
     inside the same call).  ValueError for a wrong tensor, unequal lengths or a vector that does not lie inside ``x``; TypeError for a
     member of another class -- before any native call.  Out of scope: ``DevicePreconditioner("ILUTP" / "ILUCP")`` (construction from device
-    arrays) and a batched apply of the multilevel class."""
+    arrays) and a batched apply of the multilevel class.  The whole preconditioned BiCGstab solve of many systems in one launch:
+    ``bicgstab_batch``."""
     members, offsets = list(members), [int(o) for o in offsets]
     if not isinstance(x, torch.Tensor) or x.dim() != 1 or x.dtype != torch.float64 or not x.is_cuda or not x.is_contiguous():
         raise ValueError("x: expected a contiguous 1-D torch.float64 CUDA tensor")
@@ -200,6 +201,126 @@ def pivot_apply_batch_(members, x, offsets, transpose=False):
         return []
     _on_current_stream()
     return _native.pivot_apply_batch_device(natives, x.data_ptr(), offsets, transpose=transpose, sync=False)
+
+
+class PivotedOperator:
+    """An ``ilupp_amd.ILUCPPreconditioner`` / ``ILUTPPreconditioner`` (built on the host by the ctypes binding) as the ``M`` of ``cg`` /
+    ``bicgstab``: ``apply_`` works in place on a device tensor through the single device apply (ilupp_hip_ilucp_apply_device), ordered on
+    torch's current stream.  One right-hand side at a time: shape (n,) or (n, 1).  ``bicgstab(A, b[:, None], M=PivotedOperator(P))`` is
+    the solve every member of ``bicgstab_batch`` has the bits of.  Not ``DevicePreconditioner("ILUCP")``: these classes are not constructed
+    from device arrays."""
+
+    def __init__(self, P):
+        pr = getattr(P, "pr", P)
+        if not isinstance(pr, _native.PivotedPreconditioner):
+            raise TypeError("PivotedOperator takes an ILUCPPreconditioner / ILUTPPreconditioner instance of the ctypes binding, got %s"
+                            % type(P).__name__)
+        self.P, self.pr = P, pr
+        self.kind = "ILUTP" if pr._rows else "ILUCP"
+        self.n = pr._n
+        self.shape = (self.n, self.n)
+
+    def apply_(self, x, transpose=False):
+        """in place on a contiguous fp64 CUDA tensor of shape (n,) or (n, 1); asynchronous, ordered on torch's current stream"""
+        if not isinstance(x, torch.Tensor) or x.dim() not in (1, 2) or x.shape[0] != self.n:
+            raise ValueError("x: expected a tensor of shape (%d,) or (%d, 1), got %s" % (self.n, self.n, tuple(getattr(x, "shape", ()))))
+        if x.dim() == 2 and x.shape[1] != 1:
+            raise NotImplementedError("k right-hand sides with a pivoting preconditioner: apply_ one column at a time")
+        if x.dtype != torch.float64 or not x.is_cuda or not x.is_contiguous():
+            raise ValueError("x: expected a contiguous torch.float64 CUDA tensor")
+        _on_current_stream()
+        self.pr.apply_device(x.data_ptr(), self.n, transpose=transpose, sync=False)
+        return x
+
+    def matvec(self, x):
+        return self.apply_(x.clone())
+
+    __matmul__ = matvec
+
+    def sync(self):
+        """wait for what was queued on torch's current stream (the applies are ordered on it)"""
+        torch.cuda.current_stream().synchronize()
+
+
+def bicgstab_batch(As, b, offsets, Ms, x0=None, maxiter=100, rtol=0.0, check_every=0, stats=None):
+    """Left-preconditioned BiCGstab for MANY small systems in ONE kernel launch (ilupp_hip_pivot_bicgstab_batch_device: one workgroup per
+    system runs the whole loop -- SpMV, apply, dot products, updates, convergence test -- with no host round trip).
+
+    ``As``: a list of DeviceCSR; ``Ms``: as many ``ilupp_amd.ILUCPPreconditioner`` / ``ILUTPPreconditioner`` objects (mixed at will, each
+    at most once) or ``PivotedOperator``s; ``b``: ONE contiguous 1-D fp64 CUDA tensor, member k's right-hand side is
+    ``b[offsets[k] : offsets[k] + n_k]``; ``x0``: the same layout.  Returns a new tensor of b's shape, a clone of ``x0`` or zeros, whose
+    member slices hold the solutions; every other element is untouched.  Per member the loop of ``bicgstab`` for one column: ``maxiter``,
+    ``rtol`` and ``check_every`` mean what they mean there, a member that converges or breaks down stops alone, and every member has the
+    bits of ``bicgstab(A_k, b_k[:, None], PivotedOperator(M_k), ...)``.  ``stats``, when a dict, receives "iterations" (int64),
+    "converged" (bool), "relres" (float64) -- `count` entries each, on the CPU -- and "route" (a list: 0 = solved in the launch, 1 = n
+    above the launch's LDS cap, 2 = degenerate factor; members of routes 1 and 2 are solved by that single solve inside the same call).
+    Ordered on torch's current stream; the host waits only when ``stats`` is asked for or a member takes route 1 or 2.  ValueError for a
+    wrong tensor, lists of unequal length, a slice outside ``b`` or a matrix and a preconditioner of different dimensions; TypeError
+    for a member of another class -- before any native call.  Out of scope: a transposed solve, CG, host (numpy) vectors, the multilevel
+    class, several right-hand sides per member."""
+    As, Ms, offsets = list(As), list(Ms), [int(o) for o in offsets]
+    natives = []
+    for A in As:
+        if not isinstance(A, DeviceCSR):
+            raise TypeError("bicgstab_batch takes DeviceCSR matrices, got %s" % type(A).__name__)
+    for M in Ms:
+        pr = M.pr if isinstance(M, PivotedOperator) else getattr(M, "pr", M)
+        if not isinstance(pr, _native.PivotedPreconditioner):
+            raise TypeError("bicgstab_batch takes ILUCPPreconditioner / ILUTPPreconditioner instances of the ctypes binding or "
+                            "PivotedOperators, got %s" % type(M).__name__)
+        natives.append(pr)
+    if not (len(As) == len(Ms) == len(offsets)):
+        raise ValueError("%d matrices, %d preconditioners and %d offsets" % (len(As), len(Ms), len(offsets)))
+    for name, t in (("b", b), ("x0", x0)):
+        if t is None and name == "x0":
+            continue
+        if not isinstance(t, torch.Tensor) or t.dim() != 1 or t.dtype != torch.float64 or not t.is_cuda or not t.is_contiguous():
+            raise ValueError("%s: expected a contiguous 1-D torch.float64 CUDA tensor" % name)
+    if x0 is not None and x0.shape != b.shape:
+        raise ValueError("x0: expected shape %s, got %s" % (tuple(b.shape), tuple(x0.shape)))
+    for k, (A, pr, o) in enumerate(zip(As, natives, offsets)):
+        if A.n != pr._n:
+            raise ValueError("member %d: the matrix has dimension %d, the preconditioner %d" % (k, A.n, pr._n))
+        if o < 0 or o + pr._n > b.numel():
+            raise ValueError("a vector of %d elements at offset %d does not lie inside b (%d elements)" % (pr._n, o, b.numel()))
+    x = torch.zeros_like(b) if x0 is None else x0.clone()
+    count = len(natives)
+    if count == 0:
+        if isinstance(stats, dict):
+            stats.update(iterations=torch.zeros(0, dtype=torch.int64), converged=torch.zeros(0, dtype=torch.bool),
+                         relres=torch.zeros(0, dtype=torch.float64), route=[])
+        return x
+    total = sum(pr._n for pr in natives)
+    work = torch.empty(7 * total, dtype=torch.float64, device=b.device)
+    iters = torch.zeros(count, dtype=torch.int64, device=b.device)
+    flags = torch.zeros(count, dtype=torch.int32, device=b.device)
+    rr = torch.zeros(count, dtype=torch.float64, device=b.device)
+    init = torch.zeros(count, dtype=torch.float64, device=b.device)
+    _on_current_stream()
+    route = _native.pivot_bicgstab_batch_device(
+        natives, [(A.data.data_ptr(), A.indices.data_ptr(), A.indptr.data_ptr(), A.nnz) for A in As], b.data_ptr(),
+        0 if x0 is None else x0.data_ptr(), x.data_ptr(), offsets, work.data_ptr(), work.numel(), maxiter, rtol, check_every,
+        iters.data_ptr(), flags.data_ptr(), rr.data_ptr(), init.data_ptr(), sync=False)
+    alone = {}
+    for k, rt in enumerate(route):
+        if rt == 0:
+            continue
+        # too large for the launch or degenerate: the single solve, whose bits the launch's members have
+        o, n = offsets[k], natives[k]._n
+        st = {}
+        xk = bicgstab(As[k], b[o:o + n][:, None], PivotedOperator(natives[k]), x0=None if x0 is None else x0[o:o + n][:, None],
+                      maxiter=maxiter, rtol=rtol, check_every=check_every, stats=st)
+        x[o:o + n] = xk[:, 0]
+        alone[k] = st
+    if isinstance(stats, dict):
+        zero = (flags & 8) != 0
+        rel = torch.sqrt(rr) / init                      # as _bicgstab_block computes it
+        rel = torch.where(zero, torch.zeros_like(rel), rel).cpu()
+        its, conv = iters.cpu(), ((flags & 2) != 0).cpu()
+        for k, st in alone.items():
+            its[k], conv[k], rel[k] = st["iterations"][0], st["converged"][0], st["relres"][0]
+        stats["iterations"], stats["converged"], stats["relres"], stats["route"] = its, conv, rel, route
+    return x
 
 
 def cg(A, b, M=None, x0=None, maxiter=100, rtol=0.0, check_every=0, stats=None):

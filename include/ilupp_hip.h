@@ -394,6 +394,30 @@ int ilupp_hip_pivot_apply_batch_device(int32_t count, ilupp_ilucp *const *member
 /* The same on host vectors x[i] of len[i] == n_i doubles, in place: all vectors staged through one device buffer (one packed upload, one
  * download); waits for the result.  A member that failed keeps its vector as it was. */
 int ilupp_hip_pivot_apply_batch(int32_t count, ilupp_ilucp *const *members, double *const *x, const int64_t *len, int transpose, int32_t *route);
+/* Left-preconditioned BiCGstab for MANY small systems at once, each with its own ILUCP / ILUTP object (mixed at will, each at most once):
+ * ONE launch, one workgroup per system, which runs the whole loop on the device -- SpMV, apply, dot products, updates and the convergence
+ * test (k_pivot_bicgstab_batch, sptrsv_batch.hip) -- with no host round trip.  Member i: the CSR matrix d_data[i] / d_indices[i] /
+ * d_indptr[i] (device arrays; n_i = the object's n, nnz[i] entries; the four lists are host arrays), the right-hand side d_b + offsets[i],
+ * the start d_x0 + offsets[i] (d_x0 may be NULL: zero) and the result d_x + offsets[i], n_i doubles each; what lies between the vectors
+ * of d_x is left untouched.  d_work: 7 * sum n_i doubles of device memory (work_doubles says how many there are).  The loop is that of
+ * ilupp_amd.device.bicgstab for one column: at most maxiter iterations; every check_every iterations (0: never), when rtol > 0, a member
+ * whose ||r|| / ||r_0|| (preconditioned residuals) is at or below rtol stops as converged; a zero right-hand side or initial residual:
+ * converged at once, x = x0; rho, (Ap, r0*) or omega zero or not finite: the member stops, not converged.  Per member (device arrays of
+ * `count`): d_iterations, d_flags (bit 0: still active after maxiter iterations, 1: converged, 2: a sweep gave up -- x untouched, 3: zero
+ * right-hand side or initial residual), d_rr = (r, r) at exit and d_init = ||r_0||.  Every member has the bits of the same solve done alone
+ * with ilupp_hip_spmv_device, ilupp_hip_ilucp_apply_device, ilupp_hip_block_dot_device and ilupp_hip_bicgstab_block_update_device.
+ * route (may be NULL): 0 = solved in the launch; 1 = n above the launch's LDS cap (the apply's cap less the dot scratch;
+ * ILUPP_BATCH_APPLY_MAX_N lowers it); 2 = degenerate factor: members of routes 1 and 2 are NOT solved, their vectors and output words are
+ * left untouched -- the caller solves them one by one.  A lone member also takes the launch (measured
+ * faster than its single solve at n = 1 000 and 4 000: profiles/r11_pivot_bicgstab_batch.txt).  Ordered on the caller's stream; sync == 0
+ * returns without waiting, sync != 0 waits and reports a member whose sweep gave up as ILUPP_ERR_TIMEOUT.  Refused with ILUPP_ERR_INVALID
+ * before any device call: null lists or members, a negative count, maxiter or check_every, a member named twice, a workspace that is too
+ * small.  count == 0 returns ILUPP_OK without touching the device. */
+int ilupp_hip_pivot_bicgstab_batch_device(int32_t count, ilupp_ilucp *const *members, const double *const *d_data, const int32_t *const *d_indices,
+                                          const int32_t *const *d_indptr, const int64_t *nnz, const double *d_b, const double *d_x0, double *d_x,
+                                          const int64_t *offsets, double *d_work, int64_t work_doubles, int32_t maxiter, double rtol,
+                                          int32_t check_every, int64_t *d_iterations, int32_t *d_flags, double *d_rr, double *d_init, int sync,
+                                          int32_t *route);
 /* the largest n that takes route 0 on the current device (what the device gives a workgroup in LDS, ILUPP_BATCH_APPLY_MAX_N applied);
  * negative: an error code */
 int64_t ilupp_hip_pivot_apply_batch_max_n(void);
