@@ -171,6 +171,13 @@ def lib():
                                                         ctypes.c_int, _I32P]
     L.ilupp_hip_pivot_apply_batch_max_n.argtypes = []
     L.ilupp_hip_pivot_apply_batch_max_n.restype = ctypes.c_int64
+    L.ilupp_hip_apply_batch_device.argtypes = L.ilupp_hip_pivot_apply_batch_device.argtypes
+    L.ilupp_hip_cg_batch_device.argtypes = [ctypes.c_int32, ctypes.POINTER(_VP), ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(_VP), ctypes.POINTER(_VP),
+                                            ctypes.POINTER(_VP), ctypes.POINTER(ctypes.c_int64), _VP, _VP, _VP, ctypes.POINTER(ctypes.c_int64), _VP,
+                                            ctypes.c_int64, ctypes.c_int32, ctypes.c_double, ctypes.c_int32, _VP, _VP, _VP, _VP,
+                                            ctypes.c_int, _I32P]
+    L.ilupp_hip_cg_batch_max_n.argtypes = []
+    L.ilupp_hip_cg_batch_max_n.restype = ctypes.c_int64
     L.ilupp_hip_ilucp_total_nnz.argtypes = [_VP]
     L.ilupp_hip_ilucp_total_nnz.restype = ctypes.c_int64
     L.ilupp_hip_ilucp_zero_pivots.argtypes = [_VP]
@@ -208,7 +215,7 @@ ABI_SYMBOLS = [
     "ilupp_hip_ilucp_create", "ilupp_hip_ilucp_destroy", "ilupp_hip_ilucp_apply", "ilupp_hip_ilucp_total_nnz", "ilupp_hip_ilucp_zero_pivots",
     "ilupp_hip_ilucp_info", "ilupp_hip_ilucp_copy", "ilupp_hip_ilutp_create", "ilupp_hip_ilucp_create_batch", "ilupp_hip_ilutp_create_batch",
     "ilupp_hip_ilucp_apply_device", "ilupp_hip_pivot_apply_batch_device", "ilupp_hip_pivot_apply_batch", "ilupp_hip_pivot_apply_batch_max_n",
-    "ilupp_hip_pivot_bicgstab_batch_device",
+    "ilupp_hip_pivot_bicgstab_batch_device", "ilupp_hip_apply_batch_device", "ilupp_hip_cg_batch_device", "ilupp_hip_cg_batch_max_n",
     "ilupp_hip_apply_block", "ilupp_hip_apply_block_device", "ilupp_hip_block_path",
     "ilupp_hip_spmm_device", "ilupp_hip_block_dot_device", "ilupp_hip_cg_block_update_device", "ilupp_hip_bicgstab_block_update_device",
 ]
@@ -952,6 +959,73 @@ def pivot_bicgstab_batch_device(members, matrices, b_ptr, x0_ptr, x_ptr, offsets
 def pivot_apply_batch_max_n():
     """the largest n a member may have to take the batched launch on the current device (ILUPP_BATCH_APPLY_MAX_N applied)"""
     v = int(lib().ilupp_hip_pivot_apply_batch_max_n())
+    if v < 0:
+        _raise(v)
+    return v
+
+
+def _plain_handles(members, none_ok=False):
+    H = (_VP * len(members))()
+    for k, m in enumerate(members):
+        if m is None and none_ok:
+            H[k] = None
+            continue
+        if not isinstance(m, Preconditioner):
+            raise TypeError("a batched apply of the non-pivoting classes takes ILU0 / ILUT / ILUC / IChol0 / ICholT preconditioners, got %s"
+                            % type(m).__name__)
+        H[k] = m._h
+    return H
+
+
+def apply_batch_device(members, dptr, offsets, transpose=False, sync=True):
+    """the applies of `members` (Preconditioner objects: ILU0, ILUT, ILUC, IChol0, ICholT, mixed at will) on device vectors with ONE launch
+    for all members that fit (ilupp_hip_apply_batch_device): member k's vector starts `offsets[k]` doubles behind `dptr`; ordered on the
+    caller's stream (set_caller_stream); returns the routes (0 = the launch, 1 = too large, 2 = a factor with an empty row: the single
+    apply inside the same call)"""
+    cnt = len(members)
+    if len(offsets) != cnt:
+        raise ValueError("%d preconditioners but %d offsets" % (cnt, len(offsets)))
+    if cnt == 0:
+        return []
+    H = _plain_handles(members)
+    O = (ctypes.c_int64 * cnt)(*[int(o) for o in offsets])
+    route = (ctypes.c_int32 * cnt)()
+    rc = lib().ilupp_hip_apply_batch_device(cnt, H, dptr, O, 1 if transpose else 0, 1 if sync else 0, route)
+    if rc:
+        _raise(rc)
+    return list(route)
+
+
+def cg_batch_device(members, ns, matrices, b_ptr, x0_ptr, x_ptr, offsets, work_ptr, work_doubles, maxiter, rtol, check_every,
+                    iterations_ptr, flags_ptr, rr_ptr, bnorm_ptr, sync=True):
+    """preconditioned CG for many small systems in ONE launch (ilupp_hip_cg_batch_device): `members` are Preconditioner objects or None
+    (no preconditioner), `ns` the members' dimensions, `matrices` a list of (data_ptr, indices_ptr, indptr_ptr, nnz) of device CSR
+    arrays; the vectors as in pivot_bicgstab_batch_device; the workspace holds 5 doubles per unknown of the batch.  Ordered on the
+    caller's stream (set_caller_stream).  Returns the routes: members of route 1 or 2 are NOT solved."""
+    cnt = len(members)
+    if len(matrices) != cnt or len(offsets) != cnt or len(ns) != cnt:
+        raise ValueError("%d preconditioners but %d dimensions, %d matrices and %d offsets" % (cnt, len(ns), len(matrices), len(offsets)))
+    if cnt == 0:
+        return []
+    H = _plain_handles(members, none_ok=True)
+    D, I, P = (_VP * cnt)(), (_VP * cnt)(), (_VP * cnt)()
+    NNZ = (ctypes.c_int64 * cnt)()
+    for k, (d, i, p, nnz) in enumerate(matrices):
+        D[k], I[k], P[k], NNZ[k] = d, i, p, int(nnz)
+    N = (ctypes.c_int64 * cnt)(*[int(n) for n in ns])
+    O = (ctypes.c_int64 * cnt)(*[int(o) for o in offsets])
+    route = (ctypes.c_int32 * cnt)()
+    rc = lib().ilupp_hip_cg_batch_device(cnt, H, N, D, I, P, NNZ, b_ptr, x0_ptr or None, x_ptr, O, work_ptr, int(work_doubles),
+                                         int(maxiter), float(rtol), int(check_every), iterations_ptr, flags_ptr, rr_ptr, bnorm_ptr,
+                                         1 if sync else 0, route)
+    if rc:
+        _raise(rc)
+    return list(route)
+
+
+def cg_batch_max_n():
+    """the largest n a member may have to be solved in cg_batch_device's launch on the current device (ILUPP_BATCH_APPLY_MAX_N applied)"""
+    v = int(lib().ilupp_hip_cg_batch_max_n())
     if v < 0:
         _raise(v)
     return v

@@ -10,6 +10,7 @@
 #include <map>
 #include <chrono>
 #include <mutex>
+#include <set>
 #include <string>
 #include <thread>
 #include <unordered_map>
@@ -239,6 +240,7 @@ struct ilupp_precond {
     int64_t btk_cap = 0;
     const char *block_path = "";
     bool block_events = false;              // the last apply was a block apply: ev[3] .. ev[2] bracket all of it
+    hipEvent_t batch_ev = nullptr;          // a batched launch that was not waited for reads the factors (ilupp_hip_apply_batch_device, ilupp_hip_cg_batch_device): what a re-factorisation and the destruction wait for
 };
 
 namespace {
@@ -252,6 +254,7 @@ bool schedule_is_compact(const Schedule &s) { return s.B <= 32768 && s.nslots <=
 void destroy_obj(ilupp_precond *p)
 {
     if (!p) return;
+    if (p->batch_ev && p->stream) (void)hipStreamWaitEvent(p->stream, p->batch_ev, 0);      // (a batched launch may still read the factors)
     if (p->stream) (void)stream_sync(p->stream);   // pooled blocks may be handed out again at once
     p->Lc.release(); p->Uc.release(); p->LcT.release(); p->UcT.release();
     p->sA.release(); p->sL.release(); p->sU.release(); p->sUT.release(); p->sLT.release();
@@ -1145,6 +1148,7 @@ int ilupp_hip_ilu0_refactor_device(ilupp_precond *p, const double *d_data, const
     API_TRY_BUILD
     if (!p || p->kind != KIND_LU || p->nnz_mode != NNZ_GENERIC_LU || p->sA.nb <= 0) { set_error("not an ILU(0) object"); return ILUPP_ERR_INVALID; }
     order_after_caller(p->stream, p->sev[0]);
+    if (p->batch_ev) { ILUPP_HIP(hipStreamWaitEvent(p->stream, p->batch_ev, 0)); p->batch_ev = nullptr; }      // (a batched launch still reads the old factor)
     {
         // same pattern as the analysed one: at least the same number of stored entries
         int32_t nnz32 = -1;
@@ -1841,7 +1845,14 @@ int ilupp_hip_sync(ilupp_precond *p)
 // kernels the apply borrows one half at a time: preconditioner_implementation.h:441-453 (left: all levels upwards) and :468-486
 // (right: all levels downwards), each on the LAST n_level entries of the vector (sparse_implementation.h:4096-4165).
 // ================================================================================================================================
+// the live multilevel objects: a batched entry that is handed one in place of an ilupp_precond says so instead of reading it as one
+static std::mutex g_ml_live_mu;
+static std::set<const void *> g_ml_live;
+static bool is_live_ml(const void *h) { std::lock_guard<std::mutex> lk(g_ml_live_mu); return g_ml_live.count(h) != 0; }
+
 struct ilupp_ml {
+    ilupp_ml() { std::lock_guard<std::mutex> lk(g_ml_live_mu); g_ml_live.insert(this); }
+    ~ilupp_ml() { std::lock_guard<std::mutex> lk(g_ml_live_mu); g_ml_live.erase(this); }
     int32_t n = 0;
     std::vector<MlLevelDev> dev;              // per level: scalings, permutations, the middle diagonal (the factors move into `obj`)
     std::vector<ilupp_precond *> obj;         // per level: the sweeps of its two factors
@@ -2349,7 +2360,7 @@ struct ilupp_ilucp {
 
 namespace {
 
-// the member's own stream behind the batched launch that last used it (pivot_apply_batch_run), before anything else touches tmp or the factors go
+// the member's own stream behind the batched launch that last used it (apply_batch_run), before anything else touches tmp or the factors go
 void after_batch(ilupp_ilucp *m)
 {
     if (!m->batch_ev) return;
@@ -2663,7 +2674,42 @@ struct BatchScratch {
     PivotSolveDesc *h_sys = nullptr, *d_sys = nullptr;      // the batched solve's second table (pinned host copy, device copy) and what says its upload is over
     int32_t sys_cap = 0;
     hipEvent_t sys_ev = nullptr;
+    double *d_tmp = nullptr;                      // the hand-over vectors (`tmp`) of the non-pivoting members of a launch, one block: n doubles each
+    size_t tmp_cap = 0;
 };
+
+// One member as the batched kernels see it, whatever class it comes from: the object that holds the two triangles, the pivoting
+// permutation (or none) and the side it stands on, and the n doubles the one-array path hands its first sweep's result over in.  A
+// pivoting member brings its own tmp and is ordered through its owner's batch_ev; a non-pivoting one (owner == nullptr) gets a slice of
+// the scratch's block, which only launches on the scratch's stream ever touch, and is ordered through p->batch_ev.  p == nullptr: a
+// member without a preconditioner (the CG solve only).
+struct BatchMember {
+    ilupp_precond *p = nullptr;
+    ilupp_ilucp *owner = nullptr;
+    const int32_t *perm = nullptr;
+    bool plain_first = true;
+    double *tmp = nullptr;
+    int32_t n = 0;
+    hipEvent_t *batch_ev() const { return owner ? &owner->batch_ev : p ? &p->batch_ev : nullptr; }
+};
+BatchMember batch_member(ilupp_ilucp *m, int transpose)
+{
+    BatchMember v;
+    v.p = m->obj; v.owner = m; v.perm = m->perm; v.plain_first = pivot_plain_first(m, transpose); v.tmp = m->tmp; v.n = m->n;
+    return v;
+}
+BatchMember batch_member(ilupp_precond *p, int transpose)
+{
+    BatchMember v;
+    v.p = p; v.plain_first = transpose == 0; v.n = p->n;
+    return v;
+}
+std::vector<BatchMember> batch_members(int32_t count, ilupp_ilucp *const *members, int transpose)
+{
+    std::vector<BatchMember> v((size_t)count);
+    for (int32_t i = 0; i < count; ++i) v[(size_t)i] = batch_member(members[i], transpose);
+    return v;
+}
 std::mutex g_batch_mu;
 std::map<int, BatchScratch> g_batch_scratch;
 
@@ -2690,38 +2736,68 @@ int64_t batch_apply_max_n()
 
 // Route and describe the members of a batched launch: route 0 = the launch (n <= cap_n, object not degenerate), 1 = too large, 2 = degenerate.
 // S.fresh / S.launched receive the descriptors and member numbers of route 0, from the tables the single apply uses (apply_plan,
-// sweep_parts, prepare_apply); xoff = offsets[i].
-void pivot_batch_describe(BatchScratch &S, int32_t count, ilupp_ilucp *const *members, const int64_t *offsets, int transpose, int64_t cap_n)
+// sweep_parts); xoff = offsets[i].  A pivoting member is prepared as its single apply prepares it (prepare_apply).  A non-pivoting one
+// needs only the two CSR triangles with their values (ensure_csr_values: a static-form ILU(0) leaves them unwritten; ensure_transposed
+// when the plan reads slot 2 or 3): one whose single apply would take a static form goes to the launch all the same -- every route has
+// the reference's bits -- and no static analysis runs merely to describe it.  Its tmp is a slice of the scratch's block (batch_tmp).
+void batch_describe(BatchScratch &S, int32_t count, const BatchMember *members, const int64_t *offsets, int64_t cap_n)
 {
     S.route.assign((size_t)count, 0); S.status.assign((size_t)count, ILUPP_OK); S.h_err.assign((size_t)count, 0);
     S.launched.clear(); S.fresh.clear();
     for (int32_t i = 0; i < count; ++i) {
-        ilupp_ilucp *m = members[i];
-        ilupp_precond *p = m->obj;
-        if (m->n > cap_n) { S.route[(size_t)i] = 1; continue; }
-        const bool plain_first = pivot_plain_first(m, transpose);
-        const ApplyPlan plan = apply_plan(p, plain_first ? 0 : 1);
-        PackedSweep *pf = nullptr, *pb = nullptr;
-        if (prepare_apply(p, plan, &pf, &pb) != ROUTE_SWEEPS || p->degenerate) { S.route[(size_t)i] = 2; continue; }
-        const DevMat &M1 = sweep_parts(p, plan.first).M, &M2 = sweep_parts(p, plan.second).M;
+        const BatchMember &v = members[i];
+        ilupp_precond *p = v.p;
+        if (v.n > cap_n) { S.route[(size_t)i] = 1; continue; }
         PivotApplyDesc d;
         memset(&d, 0, sizeof(d));
-        d.n = m->n; d.kind1 = plan.first.kind; d.kind2 = plan.second.kind; d.plain_first = plain_first ? 1 : 0;
-        d.ptr1 = M1.ptr; d.idx1 = M1.idx; d.val1 = M1.val;
-        d.ptr2 = M2.ptr; d.idx2 = M2.idx; d.val2 = M2.val;
-        d.perm = m->perm; d.xoff = offsets[i]; d.tmp = m->tmp;
+        d.n = v.n; d.xoff = offsets[i];
+        if (p) {
+            const ApplyPlan plan = apply_plan(p, v.plain_first ? 0 : 1);
+            if (v.owner) {
+                PackedSweep *pf = nullptr, *pb = nullptr;
+                if (prepare_apply(p, plan, &pf, &pb) != ROUTE_SWEEPS || p->degenerate) { S.route[(size_t)i] = 2; continue; }
+            } else {
+                ensure_csr_values(p);
+                if (plan.transposed()) ensure_transposed(p);
+                if (p->degenerate) { S.route[(size_t)i] = 2; continue; }
+            }
+            const DevMat &M1 = sweep_parts(p, plan.first).M, &M2 = sweep_parts(p, plan.second).M;
+            d.kind1 = plan.first.kind; d.kind2 = plan.second.kind; d.plain_first = v.plain_first ? 1 : 0;
+            d.ptr1 = M1.ptr; d.idx1 = M1.idx; d.val1 = M1.val;
+            d.ptr2 = M2.ptr; d.idx2 = M2.idx; d.val2 = M2.val;
+            d.perm = v.perm; d.tmp = v.tmp;
+        }
         S.fresh.push_back(d);
         S.launched.push_back(i);
+    }
+}
+
+// the hand-over vectors of the launch's non-pivoting members: slices of one block of the scratch, in the order of the launch
+void batch_tmp(BatchScratch &S, const BatchMember *members)
+{
+    size_t total = 0;
+    for (int32_t i : S.launched) if (members[i].p && !members[i].owner) total += (size_t)members[i].n;
+    if (total > S.tmp_cap) {
+        if (S.d_tmp) { ILUPP_HIP(hipStreamSynchronize(S.stream)); (void)hipFree(S.d_tmp); S.d_tmp = nullptr; }
+        S.tmp_cap = 0;
+        ILUPP_HIP(hipMalloc(reinterpret_cast<void **>(&S.d_tmp), sizeof(double) * total));
+        S.tmp_cap = total;
+    }
+    size_t at = 0;
+    for (size_t k = 0; k < S.launched.size(); ++k) {
+        const BatchMember &v = members[S.launched[k]];
+        if (v.p && !v.owner) { S.fresh[k].tmp = S.d_tmp + at; at += (size_t)v.n; }
     }
 }
 
 // The described members (at least one) made ready for their launch on the scratch's stream: the bytes of LDS the sweeps of the launch take
 // (returned), the error words, the descriptor table on the device (uploaded again only when a descriptor differs), and the stream behind
 // whatever is still queued on a member's own stream (a single apply that was not waited for, the transposed storages of a first use).
-size_t pivot_batch_stage(BatchScratch &S, ilupp_ilucp *const *members, int64_t cap_n)
+size_t batch_stage(BatchScratch &S, const BatchMember *members, int64_t cap_n)
 {
     hipStream_t bs = S.stream;
     const int32_t nl = (int32_t)S.launched.size();
+    batch_tmp(S, members);
     // both arrays in LDS where 16 n bytes fit under the cap, else one: the launch takes what its largest member needs
     size_t lds = 0;
     const size_t cap_bytes = (size_t)cap_n * 8;
@@ -2748,8 +2824,8 @@ size_t pivot_batch_stage(BatchScratch &S, ilupp_ilucp *const *members, int64_t c
         S.used = nl;
     }
     for (int32_t k = 0; k < nl; ++k) {
-        ilupp_precond *p = members[S.launched[(size_t)k]]->obj;
-        if (hipStreamQuery(p->stream) == hipSuccess) continue;
+        ilupp_precond *p = members[S.launched[(size_t)k]].p;
+        if (!p || hipStreamQuery(p->stream) == hipSuccess) continue;
         (void)hipGetLastError();
         ILUPP_HIP(hipEventRecord(p->sev[1], p->stream));
         ILUPP_HIP(hipStreamWaitEvent(bs, p->sev[1], 0));
@@ -2757,54 +2833,56 @@ size_t pivot_batch_stage(BatchScratch &S, ilupp_ilucp *const *members, int64_t c
     return lds;
 }
 
-// behind the launch: later single applies of its members come after it
-void pivot_batch_launched(BatchScratch &S, ilupp_ilucp *const *members)
+// behind the launch: what touches a member's tmp or rewrites its factors comes after it (a pivoting member's later single apply, any
+// member's re-factorisation and destruction)
+void batch_launched(BatchScratch &S, const BatchMember *members)
 {
     ILUPP_HIP(hipEventRecord(S.done_ev, S.stream));
-    for (int32_t i : S.launched) members[i]->batch_ev = S.done_ev;
+    for (int32_t i : S.launched) if (hipEvent_t *ev = members[i].batch_ev()) *ev = S.done_ev;
 }
 
 // Queue the applies of all members: route 0 = the launch (n within the LDS cap, object not degenerate), 1 = too large (for the LDS, or for
 // a launch it would have to itself) and 2 = degenerate through the single apply on the member's own stream.  Everything is joined on the scratch's stream when this returns; nothing is waited for.
 // staged: the vectors were put there by work on the scratch's stream (the host entry), not by the caller's stream.
-int pivot_apply_batch_run(BatchScratch &S, int32_t count, ilupp_ilucp *const *members, double *d_x, const int64_t *offsets, int transpose, bool staged)
+int apply_batch_run(BatchScratch &S, int32_t count, const BatchMember *members, double *d_x, const int64_t *offsets, int transpose, bool staged)
 {
     hipStream_t bs = S.stream;
     if (!staged) order_after_caller(bs, S.cev[0]);
     else ILUPP_HIP(hipEventRecord(S.in_ev, bs));
     const int64_t cap_n = batch_apply_max_n();
-    pivot_batch_describe(S, count, members, offsets, transpose, cap_n);
+    batch_describe(S, count, members, offsets, cap_n);
     // ONE member in the launch is one workgroup of 256 lanes walking all its rows, 0.06 ms + 0.015 ms per 1 000 rows, where the general sweeps
     // of the single apply take 0.11 - 0.12 ms whatever n is: past n = 4 096 the member alone is faster on the single apply (n = 4 000: 0.92 -
     // 1.18 x, 6 000: 1.2 - 1.5 x, 12 000: 1.9 - 2.5 x; two members of n = 12 000 break even, four take half the loop's time:
     // profiles/r10_pivot_apply_batch.txt)
     if (S.launched.size() == 1 && S.fresh[0].n > kSmallSweepMax) { S.route[(size_t)S.launched[0]] = 1; S.launched.clear(); S.fresh.clear(); }
     if (!S.launched.empty()) {
-        const size_t lds = pivot_batch_stage(S, members, cap_n);
+        const size_t lds = batch_stage(S, members, cap_n);
         OR_RETURN(pivot_apply_batch_launch(bs, (int32_t)S.launched.size(), S.d_table, d_x, lds));
-        pivot_batch_launched(S, members);
+        batch_launched(S, members);
     }
     for (int32_t i = 0; i < count; ++i) {
         if (S.route[(size_t)i] == 0) continue;
-        ilupp_ilucp *m = members[i];
-        hipStream_t st = m->obj->stream;
+        const BatchMember &v = members[i];
+        hipStream_t st = v.p->stream;
         if (staged) ILUPP_HIP(hipStreamWaitEvent(st, S.in_ev, 0));
-        OR_RETURN(pivot_apply_dev(m, d_x + offsets[i], transpose));
-        ILUPP_HIP(hipEventRecord(m->obj->sev[1], st));
-        ILUPP_HIP(hipStreamWaitEvent(bs, m->obj->sev[1], 0));
+        if (v.owner) OR_RETURN(pivot_apply_dev(v.owner, d_x + offsets[i], transpose));
+        else OR_RETURN(apply_dev(v.p, d_x + offsets[i], transpose));
+        ILUPP_HIP(hipEventRecord(v.p->sev[1], st));
+        ILUPP_HIP(hipStreamWaitEvent(bs, v.p->sev[1], 0));
     }
     return ILUPP_OK;
 }
 
-// wait for a batch that pivot_apply_batch_run queued and say how it went: status per member, the first failure returned and named by its number
+// wait for a batch that apply_batch_run queued and say how it went: status per member, the first failure returned and named by its number
 // (singles: the members of routes 1 and 2 went through their single applies -- not so behind the batched solve, which leaves them alone)
-int pivot_apply_batch_finish(BatchScratch &S, int32_t count, ilupp_ilucp *const *members, bool singles = true)
+int apply_batch_finish(BatchScratch &S, int32_t count, const BatchMember *members, bool singles = true)
 {
     const int32_t nl = (int32_t)S.launched.size();
     std::vector<std::string> msgs((size_t)count);
     for (int32_t i = 0; i < count; ++i)
         if (singles && S.route[(size_t)i] != 0) {
-            S.status[(size_t)i] = finish_apply(members[i]->obj);
+            S.status[(size_t)i] = finish_apply(members[i].p);
             if (S.status[(size_t)i]) msgs[(size_t)i] = g_last_error;
         }
     std::vector<int32_t> err((size_t)(nl > 0 ? nl : 1), 0);
@@ -2812,7 +2890,7 @@ int pivot_apply_batch_finish(BatchScratch &S, int32_t count, ilupp_ilucp *const 
     ILUPP_HIP(stream_sync(S.stream));
     for (int32_t k = 0; k < nl; ++k) {
         const int32_t i = S.launched[(size_t)k];
-        members[i]->batch_ev = nullptr;
+        if (hipEvent_t *ev = members[i].batch_ev()) *ev = nullptr;
         S.h_err[(size_t)i] = err[(size_t)k];
         if (err[(size_t)k]) { S.status[(size_t)i] = ILUPP_ERR_TIMEOUT; msgs[(size_t)i] = "triangular solve: dependency wait timed out (factor not triangular?)"; }
     }
@@ -2832,9 +2910,117 @@ int pivot_batch_args(int32_t count, ilupp_ilucp *const *members, const void *a, 
     return ILUPP_OK;
 }
 
+// the same for a list of non-pivoting objects; null_ok: a null handle is a member without a preconditioner (the CG solve), any number of them.
+// A multilevel object handed in as a member is named before anything reads it as an ilupp_precond.
+int plain_batch_args(int32_t count, ilupp_precond *const *members, bool null_ok, const void *a, const void *b)
+{
+    if (count < 0 || !members || !a || !b) { set_error("null argument"); return ILUPP_ERR_INVALID; }
+    std::vector<const ilupp_precond *> seen;
+    for (int32_t i = 0; i < count; ++i) {
+        if (!members[i]) { if (null_ok) continue; set_error("null preconditioner"); return ILUPP_ERR_INVALID; }
+        if (is_live_ml(members[i])) { set_error("a multilevel preconditioner cannot be a member of a batch"); return ILUPP_ERR_INVALID; }
+        seen.push_back(members[i]);
+    }
+    std::sort(seen.begin(), seen.end());
+    if (std::adjacent_find(seen.begin(), seen.end()) != seen.end()) { set_error("a preconditioner appears twice in the batch"); return ILUPP_ERR_INVALID; }
+    return ILUPP_OK;
+}
+
 }  // namespace
 
 extern "C" {
+
+int ilupp_hip_apply_batch_device(int32_t count, ilupp_precond *const *members, double *d_x, const int64_t *offsets, int transpose, int sync,
+                                 int32_t *route)
+{
+    API_TRY
+    const int rc0 = plain_batch_args(count, members, false, d_x, offsets);
+    if (rc0 || count == 0) return rc0;
+    std::lock_guard<std::mutex> lk(g_batch_mu);
+    BatchScratch &S = batch_scratch();
+    std::vector<BatchMember> mv((size_t)count);
+    for (int32_t i = 0; i < count; ++i) mv[(size_t)i] = batch_member(members[i], transpose);
+    int rc = apply_batch_run(S, count, mv.data(), d_x, offsets, transpose, false);
+    if (route) for (int32_t i = 0; i < count; ++i) route[i] = S.route[(size_t)i];
+    if (rc) return rc;
+    if (sync) return apply_batch_finish(S, count, mv.data());
+    order_caller_after(S.stream, S.cev[1]);
+    return ILUPP_OK;
+    API_CATCH
+}
+
+int ilupp_hip_cg_batch_device(int32_t count, ilupp_precond *const *members, const int64_t *n, const double *const *d_data,
+                              const int32_t *const *d_indices, const int32_t *const *d_indptr, const int64_t *nnz, const double *d_b,
+                              const double *d_x0, double *d_x, const int64_t *offsets, double *d_work, int64_t work_doubles, int32_t maxiter,
+                              double rtol, int32_t check_every, int64_t *d_iterations, int32_t *d_flags, double *d_rr, double *d_bnorm, int sync,
+                              int32_t *route)
+{
+    API_TRY
+    const int rc0 = plain_batch_args(count, members, true, d_x, offsets);
+    if (rc0) return rc0;
+    if (!n || !d_data || !d_indices || !d_indptr || !nnz || !d_b || !d_work || !d_iterations || !d_flags || !d_rr || !d_bnorm) { set_error("null argument"); return ILUPP_ERR_INVALID; }
+    if (maxiter < 0 || check_every < 0) { set_error("maxiter and check_every must not be negative"); return ILUPP_ERR_INVALID; }
+    int64_t total = 0;
+    for (int32_t i = 0; i < count; ++i) {
+        if (!d_data[i] || !d_indices[i] || !d_indptr[i]) { set_error("null argument"); return ILUPP_ERR_INVALID; }
+        if (n[i] <= 0 || n[i] > INT32_MAX) { set_error("matrix has size 0!"); return ILUPP_ERR_INVALID; }
+        if (members[i] && members[i]->n != n[i]) { set_error("matrix has wrong size for preconditioner!"); return ILUPP_ERR_WRONG_SIZE; }
+        total += n[i];
+    }
+    const int64_t wf = cg_batch_work_factor();
+    if (work_doubles < wf * total) { set_error("workspace too small: " + std::to_string(wf) + " doubles per unknown of the batch"); return ILUPP_ERR_INVALID; }
+    if (count == 0) return ILUPP_OK;
+    std::lock_guard<std::mutex> lk(g_batch_mu);
+    BatchScratch &S = batch_scratch();
+    hipStream_t bs = S.stream;
+    if (!S.sys_ev) ILUPP_HIP(hipEventCreateWithFlags(&S.sys_ev, hipEventDisableTiming));
+    order_after_caller(bs, S.cev[0]);
+    // the cap of the apply's launch, lowered by what the dot scratch takes (ILUPP_BATCH_APPLY_MAX_N lowers both)
+    int64_t cap_n = batch_apply_max_n();
+    if (cg_batch_max_n() < cap_n) cap_n = cg_batch_max_n();
+    std::vector<BatchMember> mv((size_t)count);
+    for (int32_t i = 0; i < count; ++i) { if (members[i]) mv[(size_t)i] = batch_member(members[i], 0); mv[(size_t)i].n = (int32_t)n[i]; }
+    batch_describe(S, count, mv.data(), offsets, cap_n);
+    if (route) for (int32_t i = 0; i < count; ++i) route[i] = S.route[(size_t)i];
+    const int32_t nl = (int32_t)S.launched.size();
+    if (nl == 0) return ILUPP_OK;
+    const size_t lds = batch_stage(S, mv.data(), cap_n);
+    if (nl > S.sys_cap) {
+        if (S.d_sys) { ILUPP_HIP(hipStreamSynchronize(bs)); (void)hipFree(S.d_sys); (void)hipHostFree(S.h_sys); S.d_sys = nullptr; S.h_sys = nullptr; }
+        S.sys_cap = 0;
+        const int32_t cap = nl < 64 ? 64 : nl;
+        ILUPP_HIP(hipMalloc(reinterpret_cast<void **>(&S.d_sys), sizeof(PivotSolveDesc) * (size_t)cap));
+        ILUPP_HIP(hipHostMalloc(reinterpret_cast<void **>(&S.h_sys), sizeof(PivotSolveDesc) * (size_t)cap, hipHostMallocDefault));
+        S.sys_cap = cap;
+    }
+    ILUPP_HIP(hipEventSynchronize(S.sys_ev));                       // (the upload before this one has read the pinned copy)
+    std::vector<int64_t> woff((size_t)count);
+    total = 0;
+    for (int32_t i = 0; i < count; ++i) { woff[(size_t)i] = wf * total; total += n[i]; }
+    for (int32_t k = 0; k < nl; ++k) {
+        const int32_t i = S.launched[(size_t)k];
+        PivotSolveDesc &e = S.h_sys[k];
+        e.aval = d_data[i]; e.aidx = d_indices[i]; e.aptr = d_indptr[i];
+        e.woff = woff[(size_t)i]; e.member = i; e.pad = 0;
+    }
+    ILUPP_HIP(hipMemcpyAsync(S.d_sys, S.h_sys, sizeof(PivotSolveDesc) * (size_t)nl, hipMemcpyHostToDevice, bs));
+    ILUPP_HIP(hipEventRecord(S.sys_ev, bs));
+    OR_RETURN(cg_batch_launch(bs, nl, S.d_table, S.d_sys, d_b, d_x0, d_x, d_work, lds, maxiter, rtol, check_every, d_iterations, d_flags, d_rr,
+                              d_bnorm));
+    batch_launched(S, mv.data());
+    if (sync) return apply_batch_finish(S, count, mv.data(), false);
+    order_caller_after(bs, S.cev[1]);
+    return ILUPP_OK;
+    API_CATCH
+}
+
+int64_t ilupp_hip_cg_batch_max_n(void)
+{
+    API_TRY
+    const int64_t a = batch_apply_max_n(), b = cg_batch_max_n();
+    return a < b ? a : b;
+    API_CATCH
+}
 
 int ilupp_hip_ilucp_apply_device(ilupp_ilucp *m, double *d_x, int64_t len, int transpose, int sync)
 {
@@ -2858,10 +3044,11 @@ int ilupp_hip_pivot_apply_batch_device(int32_t count, ilupp_ilucp *const *member
     if (rc0 || count == 0) return rc0;
     std::lock_guard<std::mutex> lk(g_batch_mu);
     BatchScratch &S = batch_scratch();
-    int rc = pivot_apply_batch_run(S, count, members, d_x, offsets, transpose, false);
+    const std::vector<BatchMember> mv = batch_members(count, members, transpose);
+    int rc = apply_batch_run(S, count, mv.data(), d_x, offsets, transpose, false);
     if (route) for (int32_t i = 0; i < count; ++i) route[i] = S.route[(size_t)i];
     if (rc) return rc;
-    if (sync) return pivot_apply_batch_finish(S, count, members);
+    if (sync) return apply_batch_finish(S, count, mv.data());
     order_caller_after(S.stream, S.cev[1]);
     return ILUPP_OK;
     API_CATCH
@@ -2892,11 +3079,12 @@ int ilupp_hip_pivot_apply_batch(int32_t count, ilupp_ilucp *const *members, doub
     }
     for (int32_t i = 0; i < count; ++i) memcpy(S.h_stage + off[(size_t)i], x[i], sizeof(double) * (size_t)len[i]);
     ILUPP_HIP(hipMemcpyAsync(S.d_stage, S.h_stage, sizeof(double) * total, hipMemcpyHostToDevice, S.stream));
-    int rc = pivot_apply_batch_run(S, count, members, S.d_stage, off.data(), transpose, true);
+    const std::vector<BatchMember> mv = batch_members(count, members, transpose);
+    int rc = apply_batch_run(S, count, mv.data(), S.d_stage, off.data(), transpose, true);
     if (route) for (int32_t i = 0; i < count; ++i) route[i] = S.route[(size_t)i];
     if (rc) { (void)hipStreamSynchronize(S.stream); return rc; }
     ILUPP_HIP(hipMemcpyAsync(S.h_stage, S.d_stage, sizeof(double) * total, hipMemcpyDeviceToHost, S.stream));
-    rc = pivot_apply_batch_finish(S, count, members);
+    rc = apply_batch_finish(S, count, mv.data());
     // (a member that failed keeps its vector as it was; the others have theirs)
     for (int32_t i = 0; i < count; ++i)
         if (S.status[(size_t)i] == ILUPP_OK) memcpy(x[i], S.h_stage + off[(size_t)i], sizeof(double) * (size_t)len[i]);
@@ -2930,11 +3118,12 @@ int ilupp_hip_pivot_bicgstab_batch_device(int32_t count, ilupp_ilucp *const *mem
     // the cap of the apply's launch, lowered by what the dot scratch takes (ILUPP_BATCH_APPLY_MAX_N lowers both)
     int64_t cap_n = batch_apply_max_n();
     if (pivot_bicgstab_batch_max_n() < cap_n) cap_n = pivot_bicgstab_batch_max_n();
-    pivot_batch_describe(S, count, members, offsets, 0, cap_n);
+    const std::vector<BatchMember> mv = batch_members(count, members, 0);
+    batch_describe(S, count, mv.data(), offsets, cap_n);
     if (route) for (int32_t i = 0; i < count; ++i) route[i] = S.route[(size_t)i];
     const int32_t nl = (int32_t)S.launched.size();
     if (nl == 0) return ILUPP_OK;
-    const size_t lds = pivot_batch_stage(S, members, cap_n);
+    const size_t lds = batch_stage(S, mv.data(), cap_n);
     if (nl > S.sys_cap) {
         if (S.d_sys) { ILUPP_HIP(hipStreamSynchronize(bs)); (void)hipFree(S.d_sys); (void)hipHostFree(S.h_sys); S.d_sys = nullptr; S.h_sys = nullptr; }
         S.sys_cap = 0;
@@ -2957,8 +3146,8 @@ int ilupp_hip_pivot_bicgstab_batch_device(int32_t count, ilupp_ilucp *const *mem
     ILUPP_HIP(hipEventRecord(S.sys_ev, bs));
     OR_RETURN(pivot_bicgstab_batch_launch(bs, nl, S.d_table, S.d_sys, d_b, d_x0, d_x, d_work, lds, maxiter, rtol, check_every, d_iterations,
                                           d_flags, d_rr, d_init));
-    pivot_batch_launched(S, members);
-    if (sync) return pivot_apply_batch_finish(S, count, members, false);
+    batch_launched(S, mv.data());
+    if (sync) return apply_batch_finish(S, count, mv.data(), false);
     order_caller_after(bs, S.cev[1]);
     return ILUPP_OK;
     API_CATCH

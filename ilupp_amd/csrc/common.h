@@ -571,6 +571,14 @@ int64_t pivot_bicgstab_batch_max_n();    // the largest n of a member of that la
 int pivot_bicgstab_batch_launch(hipStream_t st, int32_t count, const PivotApplyDesc *d_table, const PivotSolveDesc *d_systems, const double *d_b,
                                 const double *d_x0, double *d_x, double *d_work, size_t sweep_bytes, int32_t maxiter, double rtol,
                                 int32_t check_every, int64_t *d_iterations, int32_t *d_flags, double *d_rr, double *d_init);
+// the same file: the whole preconditioned CG solve of many small systems in one launch (k_cg_batch), on the same two tables.  A
+// descriptor with perm == nullptr is a non-pivoting member (its two CSR triangles from apply_plan / sweep_parts), one with ptr1 == nullptr
+// a member without a preconditioner.  woff: where the member's cg_batch_work_factor() vectors of n start in the workspace.
+int64_t cg_batch_max_n();                // the largest n of a member of that launch on the current device (LDS: dot scratch + 8 n bytes)
+int cg_batch_work_factor();              // doubles of workspace per unknown of the batch: 5 (x, r, z, p, Ap)
+int cg_batch_launch(hipStream_t st, int32_t count, const PivotApplyDesc *d_table, const PivotSolveDesc *d_systems, const double *d_b,
+                    const double *d_x0, double *d_x, double *d_work, size_t sweep_bytes, int32_t maxiter, double rtol, int32_t check_every,
+                    int64_t *d_iterations, int32_t *d_flags, double *d_rr, double *d_bnorm);
 
 // sptrsv_lvl.hip
 bool lvl_order(hipStream_t st, int mode, int32_t n, int64_t nnz, const int32_t *ptr, const int32_t *idx, const Schedule &sch,

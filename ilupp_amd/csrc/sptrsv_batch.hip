@@ -24,6 +24,10 @@
 //
 // Second kernel, further down: k_pivot_bicgstab_batch, the whole left-preconditioned BiCGstab SOLVE of many small systems in one launch,
 // one workgroup per system, with this apply (pivot_apply_member) inside its loop.
+//
+// The non-pivoting classes (ILU0, ILUT, ILUC, IChol0, ICholT) take the same launch: a descriptor with perm == nullptr is an apply without a
+// permutation, its two triangles those of apply_plan / sweep_parts (api.hip: batch_describe).  Third kernel, at the end: k_cg_batch, the
+// whole preconditioned CG solve of many small symmetric positive definite systems in one launch, each with such a member or none.
 #include "common.h"
 
 namespace ilupp {
@@ -144,6 +148,21 @@ __device__ __forceinline__ void pivot_apply_member(const PivotApplyDesc &d, doub
     if (*s_fail == 0) {
         // second sweep: right-hand sides = the first one's unknowns; its store is the member's vector (through perm when the plain solve came first)
         batch_sweep(d.kind2, n, d.ptr2, d.idx2, d.val2, two ? arr + n : arr, two ? arr : nullptr, d.tmp, nullptr, x,
+                    d.plain_first ? d.perm : nullptr, s_progress, s_fail);
+    }
+}
+
+// The same with the source apart from the destination, dst = M^-1 src with src left as it is (the CG kernel's z = M^-1 r; kept apart from
+// the in-place form above, whose instruction stream the two older kernels keep): the first sweep reads src, the second stores to dst.
+__device__ __forceinline__ void apply_member_to(const PivotApplyDesc &d, const double *src, double *dst, unsigned long long *arr,
+                                                const unsigned lds_bytes, unsigned *s_progress, int *s_fail)
+{
+    const int n = d.n;
+    const bool two = (size_t)16 * (size_t)n <= (size_t)lds_bytes;
+    batch_sweep(d.kind1, n, d.ptr1, d.idx1, d.val1, arr, nullptr, src, d.plain_first ? nullptr : d.perm, two ? nullptr : d.tmp, nullptr,
+                s_progress, s_fail);
+    if (*s_fail == 0) {
+        batch_sweep(d.kind2, n, d.ptr2, d.idx2, d.val2, two ? arr + n : arr, two ? arr : nullptr, d.tmp, nullptr, dst,
                     d.plain_first ? d.perm : nullptr, s_progress, s_fail);
     }
 }
@@ -434,6 +453,166 @@ int pivot_bicgstab_batch_launch(hipStream_t st, int32_t count, const PivotApplyD
     if (lds_bytes > pivot_bicgstab_batch_lds_cap()) return ILUPP_ERR_UNSUPPORTED;
     hipLaunchKernelGGL(k_pivot_bicgstab_batch, dim3((unsigned)count), dim3(kBatchThreads), lds_bytes, st, d_table, d_systems, d_b, d_x0, d_x, d_work,
                        (unsigned)sweep_bytes, (int)maxiter, rtol, (int)check_every, reinterpret_cast<long long *>(d_iterations), d_flags, d_rr, d_init);
+    ILUPP_HIP(hipGetLastError());
+    return ILUPP_OK;
+}
+
+
+// ---- the whole preconditioned CG solve of MANY small symmetric positive definite systems in ONE launch: one workgroup per member ----
+// k_cg_batch runs _cg_block of ilupp_amd/device.py with k = 1, statement for statement, for its member, out of the same pieces as the
+// kernel above: wg_spmv, apply_member_to (z = M^-1 r, r left as it is), wg_dots, the updates of k_block_update<0>, IEEE division and the
+// correctly rounded square root -- so every member has the bits of cg(A_k, b_k[:, None], M_k).  The descriptors are those of the
+// batched apply with perm == nullptr (IChol0, ICholT, ILU0, ILUT, ILUC); ptr1 == nullptr: a member without a preconditioner, z = r.
+// The FIVE vectors x, r, z, p, Ap lie in the member's part of the workspace (x too: a member whose sweep gives up leaves its slice of
+// the output as it was); a member without a preconditioner leaves its z unused.  Dynamic LDS as above: kDotScratch doubles, then the
+// sweeps' one or two arrays of n.
+static constexpr int kCgBatchVectors = 5;
+
+__global__ void __launch_bounds__(kBatchThreads)
+k_cg_batch(const PivotApplyDesc *__restrict__ table, const PivotSolveDesc *__restrict__ systems, const double *bbase, const double *x0base,
+           double *xbase, double *work, const unsigned sweep_bytes, const int maxiter, const double rtol, const int check_every,
+           long long *iterations, int32_t *flags, double *rr_out, double *bnorm_out)
+{
+    extern __shared__ unsigned long long lds[];
+    __shared__ unsigned s_progress;
+    __shared__ int s_fail;
+    const PivotApplyDesc d = table[blockIdx.x];
+    const PivotSolveDesc e = systems[blockIdx.x];
+    const int n = d.n, tid = threadIdx.x;
+    if (tid == 0) { s_progress = 0; s_fail = 0; }
+    double *dots = reinterpret_cast<double *>(lds);
+    unsigned long long *arr = lds + kDotScratch;
+    const int nb = (n + 255) / 256, chunk = (n + nb - 1) / nb;      // (n <= 256 kDotMaxNb)
+    unsigned turn = 0;
+    auto part = [&]() { return dots + (turn++ & 1u) * (2 * kDotMaxNb); };
+    const bool has_m = d.ptr1 != nullptr;
+    double *xw = work + e.woff, *r = xw + n, *z = has_m ? r + n : r, *p = r + 2 * n, *Ap = p + n;
+    const double *b = bbase + d.xoff;
+    const double *x0 = x0base ? x0base + d.xoff : nullptr;
+    double *x = xbase + d.xoff;
+
+    // x = x0 or 0; r = b, or b - A x
+    for (int i = tid; i < n; i += kBatchThreads) xw[i] = x0 ? x0[i] : 0.0;
+    __syncthreads();                                 // (also publishes s_progress and s_fail)
+    if (x0) {
+        wg_spmv(n, e.aptr, e.aidx, e.aval, xw, Ap);
+        __syncthreads();
+        for (int i = tid; i < n; i += kBatchThreads) r[i] = b[i] - Ap[i];
+    } else {
+        for (int i = tid; i < n; i += kBatchThreads) r[i] = b[i];
+    }
+    __syncthreads();
+    bool failed = false, zero = false, active = false, converged = false, have_rr = false, first = true;
+    double bnorm = 0.0, rz = 0.0, rr = 0.0, v2[2];
+    long long iters = 0;
+    for (int it = 0;;) {
+        // loop top: the one place where the apply stands
+        if (has_m) {
+            apply_member_to(d, r, z, arr, sweep_bytes, &s_progress, &s_fail);
+            if (s_fail != 0) { failed = true; active = false; break; }
+        }
+        double rz_new;
+        if (first) {
+            first = false;
+            wg_dots<2>(n, nb, chunk, r, z, b, b, part(), v2);
+            rz_new = v2[0];
+            bnorm = __dsqrt_rn(v2[1]);
+            wg_dots<1>(n, nb, chunk, r, r, nullptr, nullptr, part(), v2);
+            rr = v2[0];
+            have_rr = true;
+            zero = bnorm == 0.0 || rr == 0.0;
+            active = !zero;
+            converged = zero;
+            if (!active || maxiter <= 0) break;
+            for (int i = tid; i < n; i += kBatchThreads) p[i] = z[i];
+        } else {
+            wg_dots<1>(n, nb, chunk, r, z, nullptr, nullptr, part(), v2);
+            rz_new = v2[0];
+            const double beta = rz_new / rz;
+            for (int i = tid; i < n; i += kBatchThreads) { const double pb = p[i] * beta; p[i] = z[i] + pb; }
+        }
+        __syncthreads();
+        rz = rz_new;
+        // loop body
+        wg_spmv(n, e.aptr, e.aidx, e.aval, p, Ap);
+        __syncthreads();
+        wg_dots<1>(n, nb, chunk, p, Ap, nullptr, nullptr, part(), v2);
+        const double pap = v2[0];
+        const double alpha = rz / pap;
+        if (!scalar_ok(pap)) { active = false; break; }      // breakdown: nothing more is touched, not converged
+        for (int i = tid; i < n; i += kBatchThreads) {
+            const double pa = p[i] * alpha;
+            xw[i] = xw[i] + pa;
+            const double apa = Ap[i] * alpha;
+            r[i] = r[i] - apa;
+        }
+        __syncthreads();
+        have_rr = false;
+        ++iters;
+        ++it;
+        if (check_every > 0 && it % check_every == 0 && rtol > 0.0) {
+            wg_dots<1>(n, nb, chunk, r, r, nullptr, nullptr, part(), v2);
+            rr = v2[0];
+            have_rr = true;
+            const double rel = __dsqrt_rn(rr) / bnorm;
+            if (rel <= rtol) { converged = true; active = false; break; }
+        }
+        if (it >= maxiter) break;
+    }
+    if (!failed) {
+        if (!have_rr) { wg_dots<1>(n, nb, chunk, r, r, nullptr, nullptr, part(), v2); rr = v2[0]; }      // (r.r at the exit)
+        for (int i = tid; i < n; i += kBatchThreads) x[i] = xw[i];
+    }
+    if (tid == 0) {                                  // (one writer per member: its own words, whatever the other members do)
+        *d.err = failed ? 1 : 0;
+        iterations[e.member] = iters;
+        flags[e.member] = (active ? 1 : 0) | (converged ? 2 : 0) | (failed ? 4 : 0) | (zero ? 8 : 0);
+        rr_out[e.member] = rr;
+        bnorm_out[e.member] = bnorm;
+    }
+}
+
+// bytes of dynamic LDS a workgroup of k_cg_batch may take on the current device (as pivot_apply_batch_lds_cap)
+size_t cg_batch_lds_cap()
+{
+    static thread_local int cap_dev = -1;
+    static thread_local size_t cap = 0;
+    int dev = 0;
+    ILUPP_HIP(hipGetDevice(&dev));
+    if (cap_dev != dev) {
+        int max_lds = 0;
+        ILUPP_HIP(hipDeviceGetAttribute(&max_lds, hipDeviceAttributeMaxSharedMemoryPerBlock, dev));
+        hipFuncAttributes fa;
+        ILUPP_HIP(hipFuncGetAttributes(&fa, reinterpret_cast<const void *>(&k_cg_batch)));
+        const size_t room = (size_t)max_lds > fa.sharedSizeBytes ? (size_t)max_lds - fa.sharedSizeBytes : 0;
+        ILUPP_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_cg_batch), hipFuncAttributeMaxDynamicSharedMemorySize, (int)room));
+        cap = room;
+        cap_dev = dev;
+    }
+    return cap;
+}
+
+// the largest n of a member of the CG launch: pivot_bicgstab_batch_max_n's formula on this kernel's own attributes
+int64_t cg_batch_max_n()
+{
+    const size_t cap = cg_batch_lds_cap(), scratch = sizeof(double) * (size_t)kDotScratch;
+    const int64_t by_lds = cap > scratch ? (int64_t)((cap - scratch) / 8) : 0;
+    return by_lds < 256 * kDotMaxNb ? by_lds : 256 * kDotMaxNb;
+}
+
+int cg_batch_work_factor() { return kCgBatchVectors; }
+
+// `count` members, one workgroup each; sweep_bytes of LDS for the sweeps of every workgroup (the dot scratch comes on top)
+int cg_batch_launch(hipStream_t st, int32_t count, const PivotApplyDesc *d_table, const PivotSolveDesc *d_systems, const double *d_b,
+                    const double *d_x0, double *d_x, double *d_work, size_t sweep_bytes, int32_t maxiter, double rtol, int32_t check_every,
+                    int64_t *d_iterations, int32_t *d_flags, double *d_rr, double *d_bnorm)
+{
+    if (count <= 0) return ILUPP_OK;
+    const size_t lds_bytes = sizeof(double) * (size_t)kDotScratch + sweep_bytes;
+    if (lds_bytes > cg_batch_lds_cap()) return ILUPP_ERR_UNSUPPORTED;
+    hipLaunchKernelGGL(k_cg_batch, dim3((unsigned)count), dim3(kBatchThreads), lds_bytes, st, d_table, d_systems, d_b, d_x0, d_x, d_work,
+                       (unsigned)sweep_bytes, (int)maxiter, rtol, (int)check_every, reinterpret_cast<long long *>(d_iterations), d_flags, d_rr,
+                       d_bnorm);
     ILUPP_HIP(hipGetLastError());
     return ILUPP_OK;
 }

@@ -256,8 +256,8 @@ def bicgstab_batch(As, b, offsets, Ms, x0=None, maxiter=100, rtol=0.0, check_eve
     above the launch's LDS cap, 2 = degenerate factor; members of routes 1 and 2 are solved by that single solve inside the same call).
     Ordered on torch's current stream; the host waits only when ``stats`` is asked for or a member takes route 1 or 2.  ValueError for a
     wrong tensor, lists of unequal length, a slice outside ``b`` or a matrix and a preconditioner of different dimensions; TypeError
-    for a member of another class -- before any native call.  Out of scope: a transposed solve, CG, host (numpy) vectors, the multilevel
-    class, several right-hand sides per member."""
+    for a member of another class -- before any native call.  Out of scope: a transposed solve, host (numpy) vectors, the multilevel
+    class, several right-hand sides per member.  CG with the non-pivoting classes: ``cg_batch``."""
     As, Ms, offsets = list(As), list(Ms), [int(o) for o in offsets]
     natives = []
     for A in As:
@@ -316,6 +316,187 @@ def bicgstab_batch(As, b, offsets, Ms, x0=None, maxiter=100, rtol=0.0, check_eve
         zero = (flags & 8) != 0
         rel = torch.sqrt(rr) / init                      # as _bicgstab_block computes it
         rel = torch.where(zero, torch.zeros_like(rel), rel).cpu()
+        its, conv = iters.cpu(), ((flags & 2) != 0).cpu()
+        for k, st in alone.items():
+            its[k], conv[k], rel[k] = st["iterations"][0], st["converged"][0], st["relres"][0]
+        stats["iterations"], stats["converged"], stats["relres"], stats["route"] = its, conv, rel, route
+    return x
+
+
+_FACTOR_KINDS = ("ILU0", "ILUT", "ILUC", "IChol0", "ICholT")
+
+
+def _factor_native(P, who):
+    """the native object and the kind of a non-pivoting member: a DevicePreconditioner of the five kinds, a FactorOperator, or a host-built
+    ILU0 / ILUT / ILUC / IChol0 / ICholT Preconditioner of the ctypes binding.  TypeError for anything else -- no native call"""
+    if isinstance(P, FactorOperator):
+        return P.pr, P.kind
+    if isinstance(P, DevicePreconditioner):
+        if getattr(P, "kind", None) not in _FACTOR_KINDS:
+            raise TypeError("%s: the multilevel (\"ILUpp\") class is not a member of a batch" % who)
+        return P.pr, P.kind
+    pr = getattr(P, "pr", P)
+    if isinstance(pr, _native.PivotedPreconditioner):
+        raise TypeError("%s takes the non-pivoting classes; ILUCPPreconditioner / ILUTPPreconditioner go through pivot_apply_batch_ / "
+                        "bicgstab_batch" % who)
+    kind = type(P).__name__[:-len("Preconditioner")] if type(P).__name__.endswith("Preconditioner") else ""
+    if not isinstance(pr, _native.Preconditioner) or (pr is not P and kind not in _FACTOR_KINDS):
+        raise TypeError("%s takes ILU0 / ILUT / ILUC / IChol0 / ICholT preconditioners of the ctypes binding, DevicePreconditioners of "
+                        "those kinds or FactorOperators, got %s" % (who, type(P).__name__))
+    return pr, kind if kind in _FACTOR_KINDS else "factor"
+
+
+def _factor_n(P, pr):
+    """the dimension of a member: what the wrapper knows, else the library's answer"""
+    if hasattr(P, "n"):
+        return int(P.n)
+    if hasattr(P, "shape"):
+        return int(P.shape[0])
+    return int(_native.lib().ilupp_hip_dimension(pr._h))
+
+
+class FactorOperator:
+    """An ``ilupp_amd.ILU0Preconditioner`` / ``ILUTPreconditioner`` / ``ILUCPreconditioner`` / ``IChol0Preconditioner`` /
+    ``ICholTPreconditioner`` (built on the host by the ctypes binding) as the ``M`` of ``cg`` / ``bicgstab``: the counterpart of
+    ``PivotedOperator`` for the non-pivoting classes.  ``apply_`` works in place on a device tensor of shape (n,) or (n, k) through
+    ilupp_hip_apply_device / ilupp_hip_apply_block_device, ordered on torch's current stream.  ``cg(A, b[:, None], FactorOperator(P))``
+    is the solve every member of ``cg_batch`` has the bits of.  TypeError for any other class."""
+
+    def __init__(self, P):
+        if isinstance(P, (FactorOperator, DevicePreconditioner)):
+            raise TypeError("FactorOperator takes a host-built ILU0 / ILUT / ILUC / IChol0 / ICholT preconditioner of the ctypes binding, "
+                            "got %s" % type(P).__name__)
+        pr, kind = _factor_native(P, "FactorOperator")
+        self.P, self.pr, self.kind = P, pr, kind
+        self.n = _factor_n(P, pr)
+        self.shape = (self.n, self.n)
+
+    def apply_(self, x, transpose=False):
+        """in place on a contiguous fp64 CUDA tensor of shape (n,) or (n, k); asynchronous, ordered on torch's current stream"""
+        if not isinstance(x, torch.Tensor) or x.dim() not in (1, 2) or x.shape[0] != self.n:
+            raise ValueError("x: expected a tensor of shape (%d,) or (%d, k), got %s" % (self.n, self.n, tuple(getattr(x, "shape", ()))))
+        if x.dtype != torch.float64 or not x.is_cuda or not x.is_contiguous():
+            raise ValueError("x: expected a contiguous torch.float64 CUDA tensor")
+        _on_current_stream()
+        if x.dim() == 2:
+            self.pr.apply_block_device(x.data_ptr(), self.n, x.shape[1], transpose=transpose, sync=False)
+        else:
+            self.pr.apply_device(x.data_ptr(), self.n, transpose=transpose, sync=False)
+        return x
+
+    def matvec(self, x):
+        return self.apply_(x.clone())
+
+    __matmul__ = matvec
+
+    def sync(self):
+        """wait for what was queued on torch's current stream (the applies are ordered on it)"""
+        torch.cuda.current_stream().synchronize()
+
+
+def _packed_vector(t, name):
+    if not isinstance(t, torch.Tensor) or t.dim() != 1 or t.dtype != torch.float64 or not t.is_contiguous():
+        raise ValueError("%s: expected a contiguous 1-D torch.float64 CUDA tensor" % name)
+
+
+def _on_device(t, name):
+    if not t.is_cuda:
+        raise ValueError("%s: expected a contiguous 1-D torch.float64 CUDA tensor" % name)
+
+
+def apply_batch_(members, x, offsets, transpose=False):
+    """``pivot_apply_batch_`` for the NON-pivoting classes: the applies of many ILU0 / ILUT / ILUC / IChol0 / ICholT objects in place on
+    ONE contiguous fp64 CUDA tensor, member k's vector being ``x[offsets[k] : offsets[k] + n_k]``, with one kernel launch for all members
+    that fit (``ilupp_hip_apply_batch_device``), ordered on torch's current stream.  Members: ``DevicePreconditioner`` objects of the
+    five kinds, ``FactorOperator``s, or the host classes of the ctypes binding themselves, mixed at will, each at most once.  Every
+    member's vector has the bits of its single ``apply_``.  Returns the routes (0 = the launch, 1 = too large, 2 = a factor with an empty
+    row: applied alone inside the same call).  ValueError for a wrong tensor, unequal lengths or a vector that does not lie inside ``x``;
+    TypeError for the "ILUpp" kind, a pivoting member or any other class -- before any native call."""
+    members, offsets = list(members), [int(o) for o in offsets]
+    natives = [_factor_native(P, "apply_batch_")[0] for P in members]
+    _packed_vector(x, "x")
+    if len(members) != len(offsets):
+        raise ValueError("%d preconditioners but %d offsets" % (len(members), len(offsets)))
+    for P, pr, o in zip(members, natives, offsets):
+        n = _factor_n(P, pr)
+        if o < 0 or o + n > x.numel():
+            raise ValueError("a vector of %d elements at offset %d does not lie inside x (%d elements)" % (n, o, x.numel()))
+    _on_device(x, "x")
+    if not natives:
+        return []
+    _on_current_stream()
+    return _native.apply_batch_device(natives, x.data_ptr(), offsets, transpose=transpose, sync=False)
+
+
+def cg_batch(As, b, offsets, Ms, x0=None, maxiter=100, rtol=0.0, check_every=0, stats=None):
+    """Preconditioned conjugate gradients for MANY small symmetric positive definite systems in ONE kernel launch
+    (ilupp_hip_cg_batch_device: one workgroup per system runs the whole loop -- SpMV, apply, dot products, updates, convergence test --
+    with no host round trip).
+
+    ``As``: a list of DeviceCSR; ``Ms``: as many members as for ``apply_batch_`` (``DevicePreconditioner`` objects of the ILU0 / ILUT /
+    ILUC / IChol0 / ICholT kinds, ``FactorOperator``s or the host classes, mixed at will, each at most once) or ``None`` (no
+    preconditioner); ``b``, ``x0``, ``offsets`` and the result as in ``bicgstab_batch``.  Per member the loop of ``cg`` for one column:
+    ``maxiter``, ``rtol`` and ``check_every`` mean what they mean there, a member that converges or breaks down stops alone, and every
+    member has the bits of ``cg(A_k, b_k[:, None], M_k, ...)``.  ``stats``, when a dict, receives "iterations" (int64), "converged"
+    (bool), "relres" (float64: sqrt(r.r) / ||b||, 0 where ||b|| is 0) -- `count` entries each, on the CPU -- and "route" (0 = solved in
+    the launch, 1 = n above the launch's LDS cap, 2 = degenerate factor; members of routes 1 and 2 are solved by that single solve
+    inside the same call).  Ordered on torch's current stream; the host waits only when ``stats`` is asked for or a member takes route 1
+    or 2.  ValueError for a wrong tensor, lists of unequal length, a slice outside ``b`` or a matrix and a preconditioner of different
+    dimensions; TypeError for a member of another class -- before any native call.  Out of scope: the multilevel class, pivoting members
+    (``bicgstab_batch``), k > 1 right-hand sides per member, host (numpy) vectors, a batched construction of the non-pivoting classes."""
+    As, Ms, offsets = list(As), list(Ms), [int(o) for o in offsets]
+    for A in As:
+        if not isinstance(A, DeviceCSR):
+            raise TypeError("cg_batch takes DeviceCSR matrices, got %s" % type(A).__name__)
+    natives = [None if M is None else _factor_native(M, "cg_batch")[0] for M in Ms]
+    if not (len(As) == len(Ms) == len(offsets)):
+        raise ValueError("%d matrices, %d preconditioners and %d offsets" % (len(As), len(Ms), len(offsets)))
+    _packed_vector(b, "b")
+    if x0 is not None:
+        _packed_vector(x0, "x0")
+        if x0.shape != b.shape:
+            raise ValueError("x0: expected shape %s, got %s" % (tuple(b.shape), tuple(x0.shape)))
+    for k, (A, M, pr, o) in enumerate(zip(As, Ms, natives, offsets)):
+        if pr is not None and _factor_n(M, pr) != A.n:
+            raise ValueError("member %d: the matrix has dimension %d, the preconditioner %d" % (k, A.n, _factor_n(M, pr)))
+        if o < 0 or o + A.n > b.numel():
+            raise ValueError("a vector of %d elements at offset %d does not lie inside b (%d elements)" % (A.n, o, b.numel()))
+    _on_device(b, "b")
+    if x0 is not None:
+        _on_device(x0, "x0")
+    x = torch.zeros_like(b) if x0 is None else x0.clone()
+    count = len(natives)
+    if count == 0:
+        if isinstance(stats, dict):
+            stats.update(iterations=torch.zeros(0, dtype=torch.int64), converged=torch.zeros(0, dtype=torch.bool),
+                         relres=torch.zeros(0, dtype=torch.float64), route=[])
+        return x
+    ns = [A.n for A in As]
+    work = torch.empty(5 * sum(ns), dtype=torch.float64, device=b.device)
+    iters = torch.zeros(count, dtype=torch.int64, device=b.device)
+    flags = torch.zeros(count, dtype=torch.int32, device=b.device)
+    rr = torch.zeros(count, dtype=torch.float64, device=b.device)
+    bnorm = torch.ones(count, dtype=torch.float64, device=b.device)
+    _on_current_stream()
+    route = _native.cg_batch_device(
+        natives, ns, [(A.data.data_ptr(), A.indices.data_ptr(), A.indptr.data_ptr(), A.nnz) for A in As], b.data_ptr(),
+        0 if x0 is None else x0.data_ptr(), x.data_ptr(), offsets, work.data_ptr(), work.numel(), maxiter, rtol, check_every,
+        iters.data_ptr(), flags.data_ptr(), rr.data_ptr(), bnorm.data_ptr(), sync=False)
+    alone = {}
+    for k, rt in enumerate(route):
+        if rt == 0:
+            continue
+        # too large for the launch or degenerate: the single solve, whose bits the launch's members have
+        o, n = offsets[k], ns[k]
+        M = Ms[k] if (Ms[k] is None or hasattr(Ms[k], "apply_")) else FactorOperator(Ms[k])
+        st = {}
+        xk = cg(As[k], b[o:o + n][:, None], M, x0=None if x0 is None else x0[o:o + n][:, None], maxiter=maxiter, rtol=rtol,
+                check_every=check_every, stats=st)
+        x[o:o + n] = xk[:, 0]
+        alone[k] = st
+    if isinstance(stats, dict):
+        rel = torch.sqrt(rr) / bnorm                     # as _cg_block computes it
+        rel = torch.where(bnorm == 0, torch.zeros_like(rel), rel).cpu()
         its, conv = iters.cpu(), ((flags & 2) != 0).cpu()
         for k, st in alone.items():
             its[k], conv[k], rel[k] = st["iterations"][0], st["converged"][0], st["relres"][0]

@@ -421,6 +421,39 @@ int ilupp_hip_pivot_bicgstab_batch_device(int32_t count, ilupp_ilucp *const *mem
 /* the largest n that takes route 0 on the current device (what the device gives a workgroup in LDS, ILUPP_BATCH_APPLY_MAX_N applied);
  * negative: an error code */
 int64_t ilupp_hip_pivot_apply_batch_max_n(void);
+/* The batched apply for the NON-pivoting classes: many ILU0 / ILUT / ILUC / IChol0 / ICholT objects (mixed at will, each at most once)
+ * applied at once by the same launch (k_pivot_apply_batch on descriptors without a permutation).  Arguments, routes, ordering, sync and
+ * ILUPP_BATCH_APPLY_MAX_N as for ilupp_hip_pivot_apply_batch_device; members of routes 1 and 2 go through ilupp_hip_apply_device's path
+ * inside the call.  Every result has the bits of ilupp_hip_apply_device, whichever route that single apply takes (a member whose single
+ * apply runs a static form is swept from its CSR triangles here; the launch never starts a static analysis).  A re-factorisation
+ * (ilupp_hip_ilu0_refactor_device) or the destruction of a member is queued behind a launch that was not waited for.  Refused with
+ * ILUPP_ERR_INVALID before any device call: null lists or members, a negative count, a member named twice ("a preconditioner appears
+ * twice in the batch"), a multilevel handle.  count == 0 returns ILUPP_OK without touching the device. */
+int ilupp_hip_apply_batch_device(int32_t count, ilupp_precond *const *members, double *d_x, const int64_t *offsets, int transpose, int sync,
+                                 int32_t *route);
+/* Preconditioned conjugate gradients for MANY small symmetric positive definite systems at once, each with its own non-pivoting object
+ * (as above) or none: ONE launch, one workgroup per system, the whole loop on the device (k_cg_batch, sptrsv_batch.hip).  The layout is
+ * that of ilupp_hip_pivot_bicgstab_batch_device, with two differences: members[i] may be NULL (no preconditioner, z = r), and n (a host
+ * array of `count`) gives every member's dimension (it must agree with a member's object: ILUPP_ERR_WRONG_SIZE otherwise).  d_work:
+ * 5 * sum n_i doubles (x, r, z, p, Ap of every member).  The loop is that of ilupp_amd.device.cg for one column: at most maxiter
+ * iterations; every check_every iterations (0: never), when rtol > 0, a member whose ||r|| / ||b|| is at or below rtol stops as
+ * converged, before the next apply; a zero right-hand side or initial residual: converged at once, x = x0; p^T A p zero or not finite:
+ * the member stops, not converged.  Per member (device arrays of `count`): d_iterations, d_flags (bit 0: still active after maxiter
+ * iterations, 1: converged, 2: a sweep gave up -- x untouched, 3: zero right-hand side or initial residual), d_rr = (r, r) at exit and
+ * d_bnorm = ||b||.  Every member has the bits of the same solve done alone with ilupp_hip_spmm_device, ilupp_hip_apply_block_device,
+ * ilupp_hip_block_dot_device and ilupp_hip_cg_block_update_device.  route (may be NULL): 0 = solved in the launch; 1 = n above the
+ * launch's LDS cap (ilupp_hip_cg_batch_max_n); 2 = degenerate factor: members of routes 1 and 2 are NOT solved, their vectors and output
+ * words are left untouched.  Ordered on the caller's stream; sync as above.  Refused with ILUPP_ERR_INVALID before any device call: null
+ * lists, a negative count, maxiter or check_every, a member named twice, a workspace that is too small, a multilevel handle.
+ * count == 0 returns ILUPP_OK without touching the device. */
+int ilupp_hip_cg_batch_device(int32_t count, ilupp_precond *const *members, const int64_t *n, const double *const *d_data,
+                              const int32_t *const *d_indices, const int32_t *const *d_indptr, const int64_t *nnz, const double *d_b,
+                              const double *d_x0, double *d_x, const int64_t *offsets, double *d_work, int64_t work_doubles, int32_t maxiter,
+                              double rtol, int32_t check_every, int64_t *d_iterations, int32_t *d_flags, double *d_rr, double *d_bnorm, int sync,
+                              int32_t *route);
+/* the largest n that takes route 0 in ilupp_hip_cg_batch_device on the current device (ILUPP_BATCH_APPLY_MAX_N applied); negative: an
+ * error code */
+int64_t ilupp_hip_cg_batch_max_n(void);
 
 /* ---------------------------------------------------------------------------------------------
  * Measurement hooks used by bench.py (not part of the reference's surface).
