@@ -178,6 +178,10 @@ def lib():
                                             ctypes.c_int, _I32P]
     L.ilupp_hip_cg_batch_max_n.argtypes = []
     L.ilupp_hip_cg_batch_max_n.restype = ctypes.c_int64
+    L.ilupp_hip_ilu0_refactor_batch_device.argtypes = [ctypes.c_int32, ctypes.POINTER(_VP), ctypes.POINTER(_VP), ctypes.POINTER(_VP),
+                                                       ctypes.POINTER(_VP), ctypes.POINTER(ctypes.c_int64), _VP, ctypes.c_int, _I32P]
+    L.ilupp_hip_ilu0_refactor_batch_max_n.argtypes = []
+    L.ilupp_hip_ilu0_refactor_batch_max_n.restype = ctypes.c_int64
     L.ilupp_hip_ilucp_total_nnz.argtypes = [_VP]
     L.ilupp_hip_ilucp_total_nnz.restype = ctypes.c_int64
     L.ilupp_hip_ilucp_zero_pivots.argtypes = [_VP]
@@ -216,6 +220,7 @@ ABI_SYMBOLS = [
     "ilupp_hip_ilucp_info", "ilupp_hip_ilucp_copy", "ilupp_hip_ilutp_create", "ilupp_hip_ilucp_create_batch", "ilupp_hip_ilutp_create_batch",
     "ilupp_hip_ilucp_apply_device", "ilupp_hip_pivot_apply_batch_device", "ilupp_hip_pivot_apply_batch", "ilupp_hip_pivot_apply_batch_max_n",
     "ilupp_hip_pivot_bicgstab_batch_device", "ilupp_hip_apply_batch_device", "ilupp_hip_cg_batch_device", "ilupp_hip_cg_batch_max_n",
+    "ilupp_hip_ilu0_refactor_batch_device", "ilupp_hip_ilu0_refactor_batch_max_n",
     "ilupp_hip_apply_block", "ilupp_hip_apply_block_device", "ilupp_hip_block_path",
     "ilupp_hip_spmm_device", "ilupp_hip_block_dot_device", "ilupp_hip_cg_block_update_device", "ilupp_hip_bicgstab_block_update_device",
 ]
@@ -1021,6 +1026,38 @@ def cg_batch_device(members, ns, matrices, b_ptr, x0_ptr, x_ptr, offsets, work_p
     if rc:
         _raise(rc)
     return list(route)
+
+
+def ilu0_refactor_batch_device(members, matrices, status_ptr, sync=True):
+    """the numeric re-factorisation of `members` (Preconditioner objects of the ILU0 class, each at most once) with ONE launch for all
+    members that fit (ilupp_hip_ilu0_refactor_batch_device): `matrices` is a list of (data_ptr, indices_ptr, indptr_ptr, nnz) of device CSR
+    arrays with the members' patterns and the new values, `status_ptr` a device array of one int32 per member (0 = re-factorised, 1 = the
+    matrix does not have the analysed pattern, 2 = a dependency wait gave up).  Ordered on the caller's stream (set_caller_stream).
+    Returns the routes: 0 = the launch; 1 = n above the cap, a longest row above the row cap (31 entries, fewer where the LDS does not
+    hold them), or alone in the launch with n >= 1 000; 2 = static form -- routes 1 and 2: the single re-factorisation inside the same call"""
+    cnt = len(members)
+    if len(matrices) != cnt:
+        raise ValueError("%d preconditioners but %d matrices" % (cnt, len(matrices)))
+    if cnt == 0:
+        return []
+    H = _plain_handles(members)
+    D, I, P = (_VP * cnt)(), (_VP * cnt)(), (_VP * cnt)()
+    NNZ = (ctypes.c_int64 * cnt)()
+    for k, (d, i, p, nnz) in enumerate(matrices):
+        D[k], I[k], P[k], NNZ[k] = d, i, p, int(nnz)
+    route = (ctypes.c_int32 * cnt)()
+    rc = lib().ilupp_hip_ilu0_refactor_batch_device(cnt, H, D, I, P, NNZ, status_ptr, 1 if sync else 0, route)
+    if rc:
+        _raise(rc)
+    return list(route)
+
+
+def ilu0_refactor_batch_max_n():
+    """the largest n a member may have to take ilu0_refactor_batch_device's launch on the current device (ILUPP_BATCH_APPLY_MAX_N applied)"""
+    v = int(lib().ilupp_hip_ilu0_refactor_batch_max_n())
+    if v < 0:
+        _raise(v)
+    return v
 
 
 def cg_batch_max_n():

@@ -1051,6 +1051,46 @@ int ilu0_create_common(const DevMat &A, int is_csr, const int32_t *head, ilupp_p
     return ILUPP_OK;
 }
 
+// what ilupp_hip_ilu0_refactor_device does, under the construction lock its caller holds (the batched re-factorisation runs it for the
+// members that do not go to its launch)
+bool is_ilu0_object(const ilupp_precond *p) { return p && p->kind == KIND_LU && p->nnz_mode == NNZ_GENERIC_LU && p->sA.nb > 0; }
+
+int ilu0_refactor_single(ilupp_precond *p, const double *d_data, const int32_t *d_indices, const int32_t *d_indptr)
+{
+    if (!is_ilu0_object(p)) { set_error("not an ILU(0) object"); return ILUPP_ERR_INVALID; }
+    order_after_caller(p->stream, p->sev[0]);
+    if (p->batch_ev) { ILUPP_HIP(hipStreamWaitEvent(p->stream, p->batch_ev, 0)); p->batch_ev = nullptr; }      // (a batched launch still reads the old factor)
+    {
+        // same pattern as the analysed one: at least the same number of stored entries
+        int32_t nnz32 = -1;
+        ILUPP_HIP(hipMemcpyAsync(&nnz32, d_indptr + p->n, sizeof(int32_t), hipMemcpyDeviceToHost, p->stream));
+        ILUPP_HIP(hipStreamSynchronize(p->stream));
+        if ((int64_t)nnz32 != p->nnzA) { set_error("ILU0 refactor: the matrix does not have the analysed pattern"); return ILUPP_ERR_INVALID; }
+    }
+    const DevMat A = borrow_csr(d_data, d_indices, d_indptr, p->n, p->nnzA, true);
+    hipStream_t st = p->stream;
+    ILUPP_HIP(hipEventRecord(p->ev[1], st));
+    float kms = 0.f;
+    int rc = ilu0_numeric_any(p, A, p->prog.prog != nullptr, &kms);
+    ILUPP_HIP(hipEventRecord(p->ev[2], st));
+    ILUPP_HIP(stream_sync(st));
+    ILUPP_HIP(hipEventElapsedTime(&p->tm.numeric_ms, p->ev[1], p->ev[2]));
+    p->tm.numeric_kernel_ms = kms;
+    p->apply_events_valid = false;
+    st_drop_transposed(&p->pkL, &p->pkU);
+    for (auto &l : p->lvl) l.release();            // (copies of the old values)
+    if (p->haveT) {
+        p->LcT.release(); p->UcT.release(); p->sUT.release(); p->sLT.release();
+        if (p->dUT) (void)pool_free(p->dUT);
+        if (p->dLT) (void)pool_free(p->dLT);
+        p->dUT = p->dLT = nullptr; p->haveT = false;
+        p->pkUT.release(); p->pkLT.release(); p->pack_tried[2] = p->pack_tried[3] = false;
+    }
+    if (rc == ILUPP_OK) arm_apply(p);
+    if (rc == ILUPP_ERR_TIMEOUT) set_error("ILU0: dependency wait timed out");
+    return rc;
+}
+
 }  // namespace
 
 #define API_TRY try {
@@ -1146,38 +1186,7 @@ int ilupp_hip_ilu0_create_device_nnz(const double *d_data, const int32_t *d_indi
 int ilupp_hip_ilu0_refactor_device(ilupp_precond *p, const double *d_data, const int32_t *d_indices, const int32_t *d_indptr)
 {
     API_TRY_BUILD
-    if (!p || p->kind != KIND_LU || p->nnz_mode != NNZ_GENERIC_LU || p->sA.nb <= 0) { set_error("not an ILU(0) object"); return ILUPP_ERR_INVALID; }
-    order_after_caller(p->stream, p->sev[0]);
-    if (p->batch_ev) { ILUPP_HIP(hipStreamWaitEvent(p->stream, p->batch_ev, 0)); p->batch_ev = nullptr; }      // (a batched launch still reads the old factor)
-    {
-        // same pattern as the analysed one: at least the same number of stored entries
-        int32_t nnz32 = -1;
-        ILUPP_HIP(hipMemcpyAsync(&nnz32, d_indptr + p->n, sizeof(int32_t), hipMemcpyDeviceToHost, p->stream));
-        ILUPP_HIP(hipStreamSynchronize(p->stream));
-        if ((int64_t)nnz32 != p->nnzA) { set_error("ILU0 refactor: the matrix does not have the analysed pattern"); return ILUPP_ERR_INVALID; }
-    }
-    const DevMat A = borrow_csr(d_data, d_indices, d_indptr, p->n, p->nnzA, true);
-    hipStream_t st = p->stream;
-    ILUPP_HIP(hipEventRecord(p->ev[1], st));
-    float kms = 0.f;
-    int rc = ilu0_numeric_any(p, A, p->prog.prog != nullptr, &kms);
-    ILUPP_HIP(hipEventRecord(p->ev[2], st));
-    ILUPP_HIP(stream_sync(st));
-    ILUPP_HIP(hipEventElapsedTime(&p->tm.numeric_ms, p->ev[1], p->ev[2]));
-    p->tm.numeric_kernel_ms = kms;
-    p->apply_events_valid = false;
-    st_drop_transposed(&p->pkL, &p->pkU);
-    for (auto &l : p->lvl) l.release();            // (copies of the old values)
-    if (p->haveT) {
-        p->LcT.release(); p->UcT.release(); p->sUT.release(); p->sLT.release();
-        if (p->dUT) (void)pool_free(p->dUT);
-        if (p->dLT) (void)pool_free(p->dLT);
-        p->dUT = p->dLT = nullptr; p->haveT = false;
-        p->pkUT.release(); p->pkLT.release(); p->pack_tried[2] = p->pack_tried[3] = false;
-    }
-    if (rc == ILUPP_OK) arm_apply(p);
-    if (rc == ILUPP_ERR_TIMEOUT) set_error("ILU0: dependency wait timed out");
-    return rc;
+    return ilu0_refactor_single(p, d_data, d_indices, d_indptr);
     API_CATCH
 }
 
@@ -2676,6 +2685,11 @@ struct BatchScratch {
     hipEvent_t sys_ev = nullptr;
     double *d_tmp = nullptr;                      // the hand-over vectors (`tmp`) of the non-pivoting members of a launch, one block: n doubles each
     size_t tmp_cap = 0;
+    // the batched ILU(0) re-factorisation's own descriptor table (pinned host copy, device copy, entries allocated / valid) and what says
+    // its upload is over: apart from h_table / d_table / used, so that the apply's descriptor cache still hits after a re-factorisation
+    RefactorDesc *h_rtable = nullptr, *d_rtable = nullptr;
+    int32_t rcap = 0, rused = 0;
+    hipEvent_t rup_ev = nullptr;
 };
 
 // One member as the batched kernels see it, whatever class it comes from: the object that holds the two triangles, the pivoting
@@ -3157,6 +3171,159 @@ int64_t ilupp_hip_pivot_apply_batch_max_n(void)
 {
     API_TRY
     return batch_apply_max_n();
+    API_CATCH
+}
+
+// n up to which a member goes to the re-factorisation's launch: one flag word per row of LDS (ILUPP_BATCH_APPLY_MAX_N lowers it, read per call)
+static int64_t refactor_batch_max_n()
+{
+    int64_t cap_n = ilu0_refactor_batch_max_n();
+    if (const char *e = getenv("ILUPP_BATCH_APPLY_MAX_N")) { const long long v = atoll(e); if (v >= 0 && v < cap_n) cap_n = v; }
+    return cap_n;
+}
+
+int ilupp_hip_ilu0_refactor_batch_device(int32_t count, ilupp_precond *const *members, const double *const *d_data,
+                                         const int32_t *const *d_indices, const int32_t *const *d_indptr, const int64_t *nnz,
+                                         int32_t *d_status, int sync, int32_t *route)
+{
+    // (the construction lock first, then the batch lock: pool blocks are freed below; no path takes the two in the other order)
+    API_TRY_BUILD
+    const int rc0 = plain_batch_args(count, members, false, d_data, nnz);
+    if (rc0) return rc0;
+    if (!d_indices || !d_indptr || !d_status) { set_error("null argument"); return ILUPP_ERR_INVALID; }
+    for (int32_t i = 0; i < count; ++i) {
+        if (!d_data[i] || !d_indices[i] || !d_indptr[i]) { set_error("null argument"); return ILUPP_ERR_INVALID; }
+        if (!is_ilu0_object(members[i])) { set_error("member " + std::to_string(i) + " of the batch: not an ILU(0) object"); return ILUPP_ERR_INVALID; }
+        if (nnz[i] != members[i]->nnzA) {
+            set_error("member " + std::to_string(i) + " of the batch: the matrix does not have the analysed pattern");
+            return ILUPP_ERR_INVALID;
+        }
+    }
+    if (count == 0) return ILUPP_OK;
+    std::lock_guard<std::mutex> lk(g_batch_mu);
+    BatchScratch &S = batch_scratch();
+    hipStream_t bs = S.stream;
+    if (!S.rup_ev) ILUPP_HIP(hipEventCreateWithFlags(&S.rup_ev, hipEventDisableTiming));
+    order_after_caller(bs, S.cev[0]);
+    // routes: 0 = the launch, 1 = n above the cap or a row above the row cap (ilu0_refactor_batch_fits), 2 = static form (its values live in
+    // lane-table records)
+    const int64_t cap_n = refactor_batch_max_n();
+    S.route.assign((size_t)count, 0); S.launched.clear();
+    size_t lds = 0;                                                     // what the launch's most demanding member asks for
+    for (int32_t i = 0; i < count; ++i) {
+        const ilupp_precond *p = members[i];
+        if (p->flm.built) { S.route[(size_t)i] = 2; continue; }
+        if (p->n > cap_n) { S.route[(size_t)i] = 1; continue; }
+        const size_t want = ilu0_refactor_batch_fits(p->n, p->max_row_len);
+        if (want == 0) { S.route[(size_t)i] = 1; continue; }
+        S.launched.push_back(i);
+        if (want > lds) lds = want;
+    }
+    // ONE member in the launch is one workgroup walking all its rows where the single path's factor kernels spread them over the chip, and
+    // the launch then saves no host wait that matters: alone, n = 1 000 takes 0.447 ms in the launch against 0.202 ms on the single path,
+    // n = 4 000 0.858 against 0.167 ms (profiles/r13_refactor_batch.txt, "alone in the launch"; smaller n not measured: it stays in the
+    // launch).  From kRefactorAloneMin rows on, a member that would have the launch to itself takes the single path.
+    // ILUPP_REFACTOR_ALONE_MIN moves the threshold (read per call; the measurement sets it above n to time the launch of one member).
+    constexpr int32_t kRefactorAloneMin = 1000;
+    long long alone_min = kRefactorAloneMin;
+    if (const char *e = getenv("ILUPP_REFACTOR_ALONE_MIN")) { const long long v = atoll(e); if (v > 0) alone_min = v; }
+    if (S.launched.size() == 1 && members[S.launched[0]]->n >= alone_min) { S.route[(size_t)S.launched[0]] = 1; S.launched.clear(); }
+    if (route) for (int32_t i = 0; i < count; ++i) route[i] = S.route[(size_t)i];
+    const int32_t nl = (int32_t)S.launched.size();
+    if (nl > 0) {
+        if (nl > S.rcap) {
+            if (S.d_rtable) { ILUPP_HIP(hipStreamSynchronize(bs)); (void)hipFree(S.d_rtable); (void)hipHostFree(S.h_rtable); S.d_rtable = nullptr; S.h_rtable = nullptr; }
+            S.rcap = 0; S.rused = 0;
+            const int32_t cap = nl < 64 ? 64 : nl;
+            ILUPP_HIP(hipMalloc(reinterpret_cast<void **>(&S.d_rtable), sizeof(RefactorDesc) * (size_t)cap));
+            ILUPP_HIP(hipHostMalloc(reinterpret_cast<void **>(&S.h_rtable), sizeof(RefactorDesc) * (size_t)cap, hipHostMallocDefault));
+            S.rcap = cap;
+        }
+        std::vector<RefactorDesc> fresh((size_t)nl);
+        std::vector<BatchMember> mv((size_t)count);
+        for (int32_t i = 0; i < count; ++i) mv[(size_t)i] = batch_member(members[i], 0);
+        for (int32_t k = 0; k < nl; ++k) {
+            const int32_t i = S.launched[(size_t)k];
+            ilupp_precond *p = members[i];
+            RefactorDesc &d = fresh[(size_t)k];
+            memset(&d, 0, sizeof(d));
+            d.aptr = d_indptr[i]; d.aidx = d_indices[i]; d.aval = d_data[i];
+            d.lptr = p->Lc.ptr; d.lidx = p->Lc.idx; d.lval = p->Lc.val;
+            d.uptr = p->Uc.ptr; d.uidx = p->Uc.idx; d.uval = p->Uc.val;
+            d.nnzA = p->nnzA; d.n = p->n; d.member = i;
+        }
+        // (uploaded again only when a descriptor differs: the same members with their matrices in the same buffers, step after step, upload nothing)
+        if (nl != S.rused || memcmp(S.h_rtable, fresh.data(), sizeof(RefactorDesc) * (size_t)nl) != 0) {
+            ILUPP_HIP(hipEventSynchronize(S.rup_ev));                   // (the upload before this one has read the pinned copy: long over)
+            memcpy(S.h_rtable, fresh.data(), sizeof(RefactorDesc) * (size_t)nl);
+            ILUPP_HIP(hipMemcpyAsync(S.d_rtable, S.h_rtable, sizeof(RefactorDesc) * (size_t)nl, hipMemcpyHostToDevice, bs));
+            ILUPP_HIP(hipEventRecord(S.rup_ev, bs));
+            S.rused = nl;
+        }
+        // the launch behind whatever is still queued on a member's own stream (a single apply or factors() that was not waited for); what
+        // earlier batched launches read of the factors lies on the scratch's stream itself
+        bool stale = false;
+        for (int32_t k = 0; k < nl; ++k) {
+            ilupp_precond *p = members[S.launched[(size_t)k]];
+            stale = stale || p->pkL.valid || p->pkU.valid || p->pkL.pkT || p->pkU.pkT || p->haveT;
+            for (const auto &l : p->lvl) stale = stale || l.tried;
+            if (hipStreamQuery(p->stream) == hipSuccess) continue;
+            (void)hipGetLastError();
+            ILUPP_HIP(hipEventRecord(p->sev[1], p->stream));
+            ILUPP_HIP(hipStreamWaitEvent(bs, p->sev[1], 0));
+        }
+        OR_RETURN(ilu0_refactor_batch_launch(bs, nl, S.d_rtable, d_status, lds));
+        batch_launched(S, mv.data());
+        // this launch WRITES the factors: whatever a member's own stream does next (a single apply, factors(), ensure_*) comes after it
+        for (int32_t k = 0; k < nl; ++k) ILUPP_HIP(hipStreamWaitEvent(members[S.launched[(size_t)k]]->stream, S.done_ev, 0));
+        // copies of the old values go (as in the single path; the non-static packed sweeps too: they are rebuilt at the next single apply,
+        // not re-packed per member here).  The pool knows nothing of streams: ONE wait for the whole call before the first free, and none
+        // when no member holds such a copy -- the steady state of refactor -> cg_batch -> refactor.
+        if (stale) ILUPP_HIP(hipStreamSynchronize(bs));
+        for (int32_t k = 0; k < nl; ++k) {
+            ilupp_precond *p = members[S.launched[(size_t)k]];
+            p->csr_vals = true;
+            p->apply_events_valid = false;
+            st_drop_transposed(&p->pkL, &p->pkU);
+            for (auto &l : p->lvl) l.release();
+            if (p->haveT) {
+                p->LcT.release(); p->UcT.release(); p->sUT.release(); p->sLT.release();
+                if (p->dUT) (void)pool_free(p->dUT);
+                if (p->dLT) (void)pool_free(p->dLT);
+                p->dUT = p->dLT = nullptr; p->haveT = false;
+                p->pkUT.release(); p->pkLT.release(); p->pack_tried[2] = p->pack_tried[3] = false;
+            }
+            if (p->pkL.valid) { p->pkL.release(); p->pack_tried[0] = false; }
+            if (p->pkU.valid) { p->pkU.release(); p->pack_tried[1] = false; }
+        }
+    }
+    // routes 1 and 2: the single path on the member's own stream (it waits for its stream itself); the status word by the host afterwards
+    for (int32_t i = 0; i < count; ++i) {
+        if (S.route[(size_t)i] == 0) continue;
+        const int rc = ilu0_refactor_single(members[i], d_data[i], d_indices[i], d_indptr[i]);
+        if (rc != ILUPP_OK && rc != ILUPP_ERR_INVALID && rc != ILUPP_ERR_TIMEOUT) return rc;
+        ILUPP_HIP(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(d_status + i), rc == ILUPP_OK ? 0 : rc == ILUPP_ERR_INVALID ? 1 : 2, 1, bs));
+    }
+    if (sync) {
+        std::vector<int32_t> st((size_t)count, 0);
+        ILUPP_HIP(d2h_async(bs, st.data(), d_status, sizeof(int32_t) * (size_t)count));
+        ILUPP_HIP(stream_sync(bs));
+        for (int32_t i : S.launched) members[i]->batch_ev = nullptr;
+        for (int32_t i = 0; i < count; ++i) {
+            if (st[(size_t)i] == 1) { set_error("member " + std::to_string(i) + " of the batch: the matrix does not have the analysed pattern"); return ILUPP_ERR_INVALID; }
+            if (st[(size_t)i] != 0) { set_error("member " + std::to_string(i) + " of the batch: ILU0: dependency wait timed out"); return ILUPP_ERR_TIMEOUT; }
+        }
+        return ILUPP_OK;
+    }
+    order_caller_after(bs, S.cev[1]);
+    return ILUPP_OK;
+    API_CATCH
+}
+
+int64_t ilupp_hip_ilu0_refactor_batch_max_n(void)
+{
+    API_TRY
+    return refactor_batch_max_n();
     API_CATCH
 }
 

@@ -580,6 +580,25 @@ int cg_batch_launch(hipStream_t st, int32_t count, const PivotApplyDesc *d_table
                     const double *d_x0, double *d_x, double *d_work, size_t sweep_bytes, int32_t maxiter, double rtol, int32_t check_every,
                     int64_t *d_iterations, int32_t *d_flags, double *d_rr, double *d_bnorm);
 
+// ilu0_batch.hip: the numeric ILU(0) re-factorisation of many small objects in one launch, one workgroup per member
+// (k_ilu0_refactor_batch).  One member: the matrix with the new values (device CSR arrays), the two triangles whose values are rewritten
+// in place (L strictly lower ascending with the unit diagonal last, U diagonal first then ascending), n, the number of stored entries
+// the analysed pattern has, and the member's status word (0 = re-factorised, 1 = the matrix does not have the analysed pattern: nothing
+// was written, 2 = a dependency wait gave up; word `member` of the launch's status array, which is no part of the descriptor, so that the
+// table's upload is skipped whenever the same members come with their matrices in the same buffers).
+struct RefactorDesc {
+    const int32_t *aptr, *aidx; const double *aval;
+    const int32_t *lptr, *lidx; double *lval;
+    const int32_t *uptr, *uidx; double *uval;
+    int64_t nnzA;
+    int32_t n, member;
+};
+int64_t ilu0_refactor_batch_max_n();     // the largest n of a member of that launch on the current device (LDS: flags + working rows of 8 entries)
+// bytes of LDS a member asks of the launch (its flags and its lanes' working rows: 5 120 bytes per entry of its longest row), 0 = above the
+// ROW CAP: longest row > 31 entries, or flags and rows do not fit (longest row <= (cap - 4 n) / 5 120)
+size_t ilu0_refactor_batch_fits(int32_t n, int32_t max_row_len);
+int ilu0_refactor_batch_launch(hipStream_t st, int32_t count, const RefactorDesc *d_table, int32_t *d_status, size_t lds_bytes);      // lds_bytes: the largest fits()
+
 // sptrsv_lvl.hip
 bool lvl_order(hipStream_t st, int mode, int32_t n, int64_t nnz, const int32_t *ptr, const int32_t *idx, const Schedule &sch,
                int32_t **perm_out, int32_t *nlevels);

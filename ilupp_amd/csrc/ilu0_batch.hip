@@ -1,0 +1,263 @@
+// ilupp_amd/csrc/ilu0_batch.hip -- the numeric ILU(0) re-factorisation of MANY small objects in ONE launch: one workgroup per member, the
+// member's rows side by side inside it (gfx950 only).
+//
+// The objects keep their patterns, schedules and tables; only the VALUES of the two CSR triangles change (same pattern, new values of A).
+// One re-factorisation alone is a latency chain that costs two host waits (ilupp_hip_ilu0_refactor_device); a batch of members fills the
+// chip's CUs and waits for nothing.
+//
+// Per member (RefactorDesc: A's CSR triple, L's and U's triples, n, nnzA, the status word):
+//   pass 1, a PROOF that reads everything and writes nothing: aptr[n] == nnzA, and row by row A's stored row is exactly L's strictly-lower
+//     indices followed by U's diagonal-plus-upper indices (every extent is checked against nnzA before an index of A is read through it).
+//     On any difference the status word becomes 1 and the workgroup returns: the factor stays bitwise as it was.  The pass also finds the
+//     member's longest row.
+//   pass 2, compute_ilu0 of the reference operation for operation (ILU0.hpp:26-66, sparse_vec_update :8-23; k_ilu0_numeric of ilu0.hip is
+//     the same loop): row-wise IKJ, k ascending over the row's strictly-lower entries, l_ik = w_k / u_kk, then w_j = w_j - l_ik * u_kj for
+//     every column j > k present in both rows (separate multiply and subtract: -ffp-contract=off).  L's unit diagonal is written too.  A
+//     zero or non-finite pivot is no error: the Inf / NaN that follows is what the single call gives, bit for bit.
+//
+// Rows run side by side in batch_sweep's idiom (sptrsv_batch.hip): one lane per row (rows t, t + 256, ...: a lane's rows ascend, so the
+// lowest unfinished row of the member is always somebody's current row), every lane retries its pending pivot row once per trip of its
+// wave, no lane ever blocks inside divergent code.  A finished row is published by a workgroup-scope RELEASE store of its flag in LDS
+// behind its value stores; a consumer ACQUIRES the flag at workgroup scope before it reads the pivot row's U values.  All waves of a
+// workgroup sit on one CU with one L1 (the `tmp` hand-over of sptrsv_batch.hip relies on the same); nothing here crosses a CU, and
+// members share nothing.  Waits are bounded as batch_sweep's: a workgroup progress counter and an idle limit; a wave that gives up sets
+// the member's status to 2 and every other wave of the workgroup leaves.
+//
+// The working row.  An elimination is a chain of dependent loads, and the chain of a member's levels is what the launch lasts.  A lane keeps
+// its working row in LDS: per stored entry the column, the working value and -- for the strictly-lower entries, which name the pivot rows
+// -- where that pivot's U row starts and how long it is (pattern only: fetched when the row is opened, before any pivot row is finished).
+// The pivot row's entries come kRG at a time with their loads in flight together, so an elimination costs one trip to memory behind the
+// flag instead of one per entry, and the merge walks the row in LDS; the row's L and U values are stored once, when it is finished.
+//
+// ROW CAP.  That takes 20 bytes x 256 lanes = 5 120 bytes per entry of the member's longest row behind the 4 n bytes of flags, and both
+// must fit into the LDS a workgroup may have: longest row <= (cap - 4 n) / 5 120 and never above kRfMaxRow = 31 (28 entries at n = 4 000,
+// 16 at n = 20 000).  A member above it is not launched (the host sends it to the single path, route 1: ilu0_refactor_batch_fits).  The
+// cap is also what bounds a trip: a lane opens at most one row (31 entries) and eliminates at most 30 pivots of 31 LDS steps each, tens
+// of microseconds at the worst, against an idle limit of 2^20 trips of a waiting wave (tenths of a second).
+//
+// LDS: 4 n bytes of flags, then 5 120 bytes per entry of the longest row (dynamic); four words static.
+#include "common.h"
+
+namespace ilupp {
+
+static constexpr int kRfThreads = 256;         // one wave per SIMD, as k_pivot_apply_batch
+static constexpr int kRG = 8;                  // entries of a row fetched together, their loads in flight at once
+static constexpr int kRfMaxRow = 31;            // the row cap where LDS allows it (see above)
+static constexpr size_t kRfRowBytes = (size_t)kRfThreads * (sizeof(double) + 3 * sizeof(int));      // LDS per entry of the longest row
+
+// bytes of LDS in front of the working rows: the flags, to a multiple of 8
+__host__ __device__ inline size_t rf_flag_bytes(int n) { return ((size_t)(n > 0 ? n : 1) * sizeof(int) + 7) & ~(size_t)7; }
+
+// The arrays come out of a descriptor in memory, so the compiler cannot tell their address space and would reach them with flat_
+// instructions, which count against the LDS counter as well: every wait for a working-row access would wait for the loads in flight.
+// Typed as global pointers they are reached with global_ instructions.
+#if defined(__HIP_DEVICE_COMPILE__)
+#define RF_HBM __attribute__((address_space(1)))
+#else
+#define RF_HBM
+#endif
+typedef const RF_HBM int32_t *rf_cint;
+typedef const RF_HBM double *rf_cdbl;
+typedef RF_HBM double *rf_dbl;
+
+// pass 2 for one member; the working rows in LDS (wv, wc, wk0, wkl: entry q of this lane at [q * 256 + tid])
+__device__ __forceinline__ void refactor_rows(const RefactorDesc &d, int *rf_done, double *wv, int *wc, int *wk0, int *wkl,
+                                              unsigned *s_progress, int *s_fail)
+{
+    const int n = d.n, tid = threadIdx.x;
+    const rf_cint aptr = (rf_cint)d.aptr, aidx = (rf_cint)d.aidx, lptr = (rf_cint)d.lptr, uptr = (rf_cint)d.uptr, uidx = (rf_cint)d.uidx;
+    const rf_cdbl aval = (rf_cdbl)d.aval;
+    const rf_dbl lval = (rf_dbl)d.lval, uval = (rf_dbl)d.uval;      // (written by one lane, read by others)
+    constexpr unsigned kIdleLimit = 1u << 20;       // trips of a wave without progress anywhere in the workgroup, as batch_sweep
+    unsigned seen = 0, idle = 0;
+    int r = tid;
+    bool alive = r < n, need_init = true;
+    int a0 = 0, len = 0, cl = 0, l0 = 0, u0 = 0, p = 0;
+    auto col = [&](int q) -> int { return wc[q * kRfThreads + tid]; };
+    auto wget = [&](int q) -> double { return wv[q * kRfThreads + tid]; };
+    auto wset = [&](int q, double v) { wv[q * kRfThreads + tid] = v; };
+    while (__ballot(alive) != 0ull) {
+        if (idle > kIdleLimit) {
+            if ((tid & 63) == 0) __hip_atomic_store(s_fail, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+            break;
+        }
+        bool did = false;
+        if (alive) {
+            if (need_init) {                                                    // U[i,:] = A[i,:]   (ILU0.hpp:36-37)
+                a0 = aptr[r]; len = aptr[r + 1] - a0;
+                l0 = lptr[r]; cl = lptr[r + 1] - l0 - 1; u0 = uptr[r];
+                // (kRG entries' loads in flight together: a loop of load-then-store to LDS waits for memory once per entry)
+                for (int q0 = 0; q0 < len; q0 += kRG) {
+                    int c[kRG];
+                    double v[kRG];
+#pragma unroll
+                    for (int q = 0; q < kRG; ++q) if (q0 + q < len) { c[q] = aidx[a0 + q0 + q]; v[q] = aval[a0 + q0 + q]; }
+#pragma unroll
+                    for (int q = 0; q < kRG; ++q) if (q0 + q < len) { wc[(q0 + q) * kRfThreads + tid] = c[q]; wv[(q0 + q) * kRfThreads + tid] = v[q]; }
+                }
+                for (int q0 = 0; q0 < cl; q0 += kRG) {
+                    int b[kRG], e[kRG];
+#pragma unroll
+                    for (int q = 0; q < kRG; ++q) if (q0 + q < cl) { const int k = wc[(q0 + q) * kRfThreads + tid]; b[q] = uptr[k]; e[q] = uptr[k + 1]; }
+#pragma unroll
+                    for (int q = 0; q < kRG; ++q) if (q0 + q < cl) { wk0[(q0 + q) * kRfThreads + tid] = b[q]; wkl[(q0 + q) * kRfThreads + tid] = e[q] - b[q]; }
+                }
+                p = 0;
+                need_init = false;
+                did = true;
+            }
+            while (p < cl) {                                                    // for k < i in row  (ILU0.hpp:47-62)
+                const int k = col(p);
+                if (__hip_atomic_load(&rf_done[k], __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP) == 0) break;      // row k not finished: next trip
+                const int ku0 = wk0[p * kRfThreads + tid], kl = wkl[p * kRfThreads + tid];
+                const double piv = uval[ku0];                                   // the first entry of U's row k
+                const double l_ik = wget(p) / piv;                              // ILU0.hpp:52
+                int pp = p + 1;
+                bool stop = false;
+                for (int jb = 1; jb < kl && !stop; jb += kRG) {                 // sparse_vec_update (ILU0.hpp:8-23), kRG entries' loads together
+                    int m[kRG];
+                    double u[kRG];
+#pragma unroll
+                    for (int q = 0; q < kRG; ++q) if (jb + q < kl) { m[q] = uidx[ku0 + jb + q]; u[q] = uval[ku0 + jb + q]; }
+#pragma unroll
+                    for (int q = 0; q < kRG; ++q)
+                        if (jb + q < kl && !stop) {
+                            while (pp < len && col(pp) < m[q]) ++pp;
+                            if (pp >= len) {
+                                stop = true;
+                            } else if (col(pp) == m[q]) {
+                                const double prod = l_ik * u[q];
+                                wset(pp, wget(pp) - prod);
+                                ++pp;
+                            }
+                        }
+                }
+                wset(p, l_ik);                                                  // ILU0.hpp:61
+                ++p;
+                did = true;
+            }
+            if (p == cl) {
+                for (int q = 0; q < cl; ++q) lval[l0 + q] = wv[q * kRfThreads + tid];
+                for (int q = cl; q < len; ++q) uval[u0 + q - cl] = wv[q * kRfThreads + tid];
+                lval[l0 + cl] = 1.0;                                            // L's unit diagonal (ILU0.hpp:93)
+                __hip_atomic_store(&rf_done[r], 1, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);      // behind the row's value stores
+                r += kRfThreads;
+                alive = r < n;
+                need_init = true;
+                did = true;
+            }
+        }
+        if (__ballot(did) != 0ull) {
+            if ((tid & 63) == 0) atomicAdd(s_progress, 1u);
+            idle = 0;
+        } else {
+            const unsigned now = __hip_atomic_load(s_progress, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+            if (now != seen) { seen = now; idle = 0; } else ++idle;
+            if (__hip_atomic_load(s_fail, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) != 0) break;      // (another wave gave up: its rows never come)
+        }
+    }
+}
+
+__global__ void __launch_bounds__(kRfThreads)
+k_ilu0_refactor_batch(const RefactorDesc *__restrict__ table, int32_t *__restrict__ status, const unsigned lds_bytes)
+{
+    extern __shared__ __attribute__((aligned(16))) unsigned char rf_lds[];
+    __shared__ unsigned s_progress;
+    __shared__ int s_fail, s_bad, s_maxlen;
+    const RefactorDesc d = table[blockIdx.x];
+    const int n = d.n, tid = threadIdx.x;
+    int *rf_done = reinterpret_cast<int *>(rf_lds);                             // row r of the member is finished (its L and U values are stored)
+    if (tid == 0) { s_progress = 0; s_fail = 0; s_maxlen = 0; s_bad = (int64_t)d.aptr[n] != d.nnzA ? 1 : 0; }
+    for (int i = tid; i < n; i += kRfThreads) rf_done[i] = 0;
+
+    // ---- pass 1: the proof ----
+    bool bad = false;
+    int maxlen = 0;
+    const rf_cint aptr = (rf_cint)d.aptr, aidx = (rf_cint)d.aidx, lptr = (rf_cint)d.lptr, lidx = (rf_cint)d.lidx, uptr = (rf_cint)d.uptr,
+                  uidx = (rf_cint)d.uidx;
+    for (int r = tid; r < n; r += kRfThreads) {
+        const int a0 = aptr[r], a1 = aptr[r + 1];
+        const int l0 = lptr[r], cl = lptr[r + 1] - l0 - 1, u0 = uptr[r], ul = uptr[r + 1] - u0;
+        if (a0 < 0 || a1 < a0 || (int64_t)a1 > d.nnzA || cl < 0 || ul < 1 || a1 - a0 != cl + ul) { bad = true; continue; }
+        for (int q0 = 0; q0 < cl + ul; q0 += kRG) {  // (kRG entries' loads in flight together)
+            int a[kRG], f[kRG];
+#pragma unroll
+            for (int q = 0; q < kRG; ++q)
+                if (q0 + q < cl + ul) { a[q] = aidx[a0 + q0 + q]; f[q] = q0 + q < cl ? lidx[l0 + q0 + q] : uidx[u0 + (q0 + q - cl)]; }
+#pragma unroll
+            for (int q = 0; q < kRG; ++q) if (q0 + q < cl + ul) bad |= a[q] != f[q];
+        }
+        maxlen = max(maxlen, a1 - a0);
+    }
+    __syncthreads();                                 // (thread 0's words and the flags are there)
+    if (bad) __hip_atomic_store(&s_bad, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+    atomicMax(&s_maxlen, maxlen);
+    __syncthreads();
+    if (s_bad != 0) {
+        if (tid == 0) status[d.member] = 1;          // (one writer per member: its own word; nothing else was written)
+        return;
+    }
+
+    // ---- pass 2: the factorisation ----
+    const size_t fb = rf_flag_bytes(n), rows = (size_t)s_maxlen * kRfRowBytes;
+    if (s_maxlen > kRfMaxRow || fb + rows > (size_t)lds_bytes) {
+        // (a row above the cap: the host launches no such member -- its routing reads the longest row the analysis recorded; nothing was written)
+        if (tid == 0) status[d.member] = 2;
+        return;
+    }
+    double *wv = reinterpret_cast<double *>(rf_lds + fb);
+    int *wc = reinterpret_cast<int *>(wv + (size_t)s_maxlen * kRfThreads);
+    int *wk0 = wc + (size_t)s_maxlen * kRfThreads, *wkl = wk0 + (size_t)s_maxlen * kRfThreads;
+    refactor_rows(d, rf_done, wv, wc, wk0, wkl, &s_progress, &s_fail);
+    __syncthreads();
+    if (tid == 0) status[d.member] = s_fail != 0 ? 2 : 0;
+}
+
+// bytes of dynamic LDS one workgroup of k_ilu0_refactor_batch may take on the current device (as pivot_apply_batch_lds_cap)
+size_t ilu0_refactor_batch_lds_cap()
+{
+    static thread_local int cap_dev = -1;
+    static thread_local size_t cap = 0;
+    int dev = 0;
+    ILUPP_HIP(hipGetDevice(&dev));
+    if (cap_dev != dev) {
+        int max_lds = 0;
+        ILUPP_HIP(hipDeviceGetAttribute(&max_lds, hipDeviceAttributeMaxSharedMemoryPerBlock, dev));
+        hipFuncAttributes fa;
+        ILUPP_HIP(hipFuncGetAttributes(&fa, reinterpret_cast<const void *>(&k_ilu0_refactor_batch)));
+        const size_t room = (size_t)max_lds > fa.sharedSizeBytes ? (size_t)max_lds - fa.sharedSizeBytes : 0;
+        ILUPP_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_ilu0_refactor_batch), hipFuncAttributeMaxDynamicSharedMemorySize, (int)room));
+        cap = room;
+        cap_dev = dev;
+    }
+    return cap;
+}
+
+// the largest n of a member of the launch: its flags and working rows of kRfMinRow entries fit (a member of that n with longer rows does not)
+static constexpr int kRfMinRow = 8;
+int64_t ilu0_refactor_batch_max_n()
+{
+    const size_t cap = ilu0_refactor_batch_lds_cap(), rows = (size_t)kRfMinRow * kRfRowBytes;
+    return cap > rows + 8 ? (int64_t)((cap - rows) / sizeof(int)) - 1 : 0;
+}
+
+// the bytes of LDS a member of n rows whose longest row has max_row_len entries asks of the launch (flags + working rows), or 0 when it is
+// above the row cap: max_row_len > kRfMaxRow, or flags and rows do not fit into the LDS a workgroup may have
+size_t ilu0_refactor_batch_fits(int32_t n, int32_t max_row_len)
+{
+    if (max_row_len < 1 || max_row_len > kRfMaxRow) return 0;
+    const size_t want = rf_flag_bytes(n) + (size_t)max_row_len * kRfRowBytes;
+    return want <= ilu0_refactor_batch_lds_cap() ? want : 0;
+}
+
+// `count` members, one workgroup each; lds_bytes: the largest ilu0_refactor_batch_fits among them; member k's status goes to d_status[table[k].member]
+int ilu0_refactor_batch_launch(hipStream_t st, int32_t count, const RefactorDesc *d_table, int32_t *d_status, size_t lds_bytes)
+{
+    if (count <= 0) return ILUPP_OK;
+    if (lds_bytes > ilu0_refactor_batch_lds_cap()) return ILUPP_ERR_UNSUPPORTED;
+    hipLaunchKernelGGL(k_ilu0_refactor_batch, dim3((unsigned)count), dim3(kRfThreads), lds_bytes, st, d_table, d_status, (unsigned)lds_bytes);
+    ILUPP_HIP(hipGetLastError());
+    return ILUPP_OK;
+}
+
+}  // namespace ilupp

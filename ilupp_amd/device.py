@@ -169,6 +169,22 @@ class DevicePreconditioner:
         self.pr.apply_part_device(x.data_ptr(), self.n, left, transpose=transpose, sync=False)
         return x
 
+    def refactor_(self, A):
+        """the numeric phase again on a DeviceCSR with the SAME pattern and (possibly) new values, the analysis kept
+        (ilupp_hip_ilu0_refactor_device); ordered on torch's current stream, the host waits for the new factor.  "ILU0" only:
+        NotImplementedError for any other kind; ValueError for a matrix of another dimension -- before any native call.  A matrix whose
+        number of stored entries differs from the analysed one's is refused by the library (RuntimeError).  Many small members at once:
+        ``refactor_batch_``."""
+        if self.kind != "ILU0":
+            raise NotImplementedError("refactor_: only the \"ILU0\" kind has a numeric re-factorisation, not %s" % self.kind)
+        if not isinstance(A, DeviceCSR):
+            raise TypeError("refactor_ takes a DeviceCSR, got %s" % type(A).__name__)
+        if A.n != self.n:
+            raise ValueError("refactor_: the matrix has dimension %d, the preconditioner %d" % (A.n, self.n))
+        _on_current_stream()
+        self.pr.refactor_device(A.data.data_ptr(), A.indices.data_ptr(), A.indptr.data_ptr())
+        return self
+
     def sync(self):
         self.pr.sync()
 
@@ -426,6 +442,60 @@ def apply_batch_(members, x, offsets, transpose=False):
         return []
     _on_current_stream()
     return _native.apply_batch_device(natives, x.data_ptr(), offsets, transpose=transpose, sync=False)
+
+
+def refactor_batch_(members, As, check=True):
+    """The numeric ILU(0) re-factorisation of MANY small members in ONE kernel launch (ilupp_hip_ilu0_refactor_batch_device: one workgroup
+    per member, its rows side by side): the members keep their patterns, schedules and tables and get the factors of ``As[k]``, a
+    DeviceCSR with member k's pattern and new values -- the step in front of ``cg_batch`` / ``apply_batch_`` when the values change and the
+    patterns do not.  ``members``: as for ``apply_batch_`` but of the ILU0 kind only (``DevicePreconditioner("ILU0", ...)``,
+    ``FactorOperator``s of, or the host class ``ILU0Preconditioner`` itself), each at most once.  Every member's factor has the bits of a
+    fresh construction from ``As[k]`` (and of the single ``refactor_``).  Returns the routes: 0 = the launch; 1 = n above the launch's
+    cap (``_native.ilu0_refactor_batch_max_n()``), a longest row above the row cap (31 entries, fewer where 4 n + 5 120 bytes per entry
+    do not fit into a workgroup's LDS: 28 at n = 4 000), or a member that would have the launch to itself with n >= 1 000 (alone it is
+    faster on the single path); 2 = static form.  Members of routes 1 and 2 are re-factorised alone inside the same call, with the
+    single path's host waits.  Ordered on torch's current stream.  Inside the launch every member's pattern is PROVED equal to the analysed one row by row; a member
+    whose pattern differs keeps its factor bitwise as it was (status 1), the others are re-factorised.  ``check=True`` reads the status
+    words with one host wait and raises ValueError naming the first such member (RuntimeError for status 2, a dependency wait that gave
+    up); ``check=False`` returns ``(routes, status)``, status an int32 CUDA tensor, and waits for nothing in the steady state (refactor_batch_
+    -> ``cg_batch`` / plain ``apply_batch_`` -> refactor_batch_ with all members on route 0): a call whose launched members still hold copies of
+    the old values -- the packed sweeps a construction leaves, the packed / transposed / level-ordered sweeps of single or block applies --
+    waits once for its launch before it frees them, whatever the members' statuses turn out to be.  TypeError for a member of
+    another kind or class, a pivoting member, the multilevel class or a matrix that is not a DeviceCSR; ValueError for lists of unequal
+    length, a member named twice or a matrix and a member of different dimensions -- before any native call.  Out of scope: the other
+    classes (no single re-factorisation to match), a batched FIRST construction, host (numpy) matrices."""
+    members, As = list(members), list(As)
+    for A in As:
+        if not isinstance(A, DeviceCSR):
+            raise TypeError("refactor_batch_ takes DeviceCSR matrices, got %s" % type(A).__name__)
+    natives = []
+    for P in members:
+        pr, kind = _factor_native(P, "refactor_batch_")
+        if kind != "ILU0":
+            raise TypeError("refactor_batch_ takes members of the ILU0 kind only (DevicePreconditioner(\"ILU0\"), ILU0Preconditioner or a "
+                            "FactorOperator of one), got %s" % (kind if kind != "factor" else type(P).__name__))
+        natives.append(pr)
+    if len(members) != len(As):
+        raise ValueError("%d preconditioners but %d matrices" % (len(members), len(As)))
+    if len(set(id(pr) for pr in natives)) != len(natives):
+        raise ValueError("a preconditioner appears twice in the batch")
+    for k, (P, pr, A) in enumerate(zip(members, natives, As)):
+        if _factor_n(P, pr) != A.n:
+            raise ValueError("member %d: the matrix has dimension %d, the preconditioner %d" % (k, A.n, _factor_n(P, pr)))
+    if not natives:
+        return [] if check else ([], torch.zeros(0, dtype=torch.int32))
+    status = torch.zeros(len(natives), dtype=torch.int32, device=As[0].data.device)
+    _on_current_stream()
+    route = _native.ilu0_refactor_batch_device(
+        natives, [(A.data.data_ptr(), A.indices.data_ptr(), A.indptr.data_ptr(), A.nnz) for A in As], status.data_ptr(), sync=False)
+    if not check:
+        return route, status
+    for k, v in enumerate(status.cpu().tolist()):                        # the one host wait
+        if v == 1:
+            raise ValueError("member %d of the batch: the matrix does not have the analysed pattern (its factor is unchanged)" % k)
+        if v != 0:
+            raise RuntimeError("member %d of the batch: ILU0: dependency wait timed out" % k)
+    return route
 
 
 def cg_batch(As, b, offsets, Ms, x0=None, maxiter=100, rtol=0.0, check_every=0, stats=None):

@@ -454,6 +454,32 @@ int ilupp_hip_cg_batch_device(int32_t count, ilupp_precond *const *members, cons
 /* the largest n that takes route 0 in ilupp_hip_cg_batch_device on the current device (ILUPP_BATCH_APPLY_MAX_N applied); negative: an
  * error code */
 int64_t ilupp_hip_cg_batch_max_n(void);
+/* The numeric re-factorisation of MANY small ILU(0) objects at once (same patterns, new values): ONE launch, one workgroup per member,
+ * the member's rows side by side inside it (k_ilu0_refactor_batch, ilu0_batch.hip).  members: `count` distinct ILU(0) objects; d_data /
+ * d_indices / d_indptr: host arrays of `count` DEVICE pointers, member i's matrix in CSR form as ilupp_hip_ilu0_refactor_device takes
+ * it; nnz[i]: its number of stored entries; d_status: a device array of `count` words, member i's being 0 = re-factorised, 1 = the
+ * matrix does not have the analysed pattern (proved inside the launch for every row, with no host round trip: the member's factor is
+ * bitwise unchanged), 2 = a dependency wait gave up.  Every member's factor has the bits of ilupp_hip_ilu0_refactor_device on the same
+ * values, Inf / NaN behind a zero or non-finite pivot included.  route (may be NULL): 0 = the launch; 1 = n above the launch's cap
+ * (ilupp_hip_ilu0_refactor_batch_max_n), a longest row above the ROW CAP (a lane's working row lives in LDS: at most 31 entries, and
+ * 4 n + 5 120 bytes per entry must fit into a workgroup's LDS -- 28 entries at n = 4 000, 16 at n = 20 000), or a member that would have
+ * the launch to itself and has 1 000 rows or more (alone it is faster on the single path); 2 = static form (the values live in
+ * lane-table records): members of
+ * routes 1 and 2 are re-factorised by ilupp_hip_ilu0_refactor_device's path inside the call (with its host waits), their status words
+ * written afterwards.  Ordered on the caller's stream; the launch comes after whatever is queued on a member's own stream, and the
+ * member's own stream (single applies, ilupp_hip_factor_copy) and every later batched launch come after it.  sync == 0: nothing is
+ * waited for, unless a launched member still holds copies of the old values that have to be freed (packed, transposed or level-ordered
+ * sweeps of single applies: one wait for the whole call; members used through ilupp_hip_cg_batch_device / the plain
+ * ilupp_hip_apply_batch_device hold none).  sync != 0: the call waits and returns ILUPP_ERR_INVALID / ILUPP_ERR_TIMEOUT naming the first
+ * member whose status is 1 / 2.  Refused with ILUPP_ERR_INVALID before any device call: null lists or members, a negative count, a
+ * member named twice, a multilevel handle, a member that is not an ILU(0) object, nnz[i] that is not the analysed pattern's ("member i
+ * of the batch: the matrix does not have the analysed pattern").  count == 0 returns ILUPP_OK without touching the device. */
+int ilupp_hip_ilu0_refactor_batch_device(int32_t count, ilupp_precond *const *members, const double *const *d_data,
+                                         const int32_t *const *d_indices, const int32_t *const *d_indptr, const int64_t *nnz,
+                                         int32_t *d_status, int sync, int32_t *route);
+/* the largest n that takes route 0 in ilupp_hip_ilu0_refactor_batch_device on the current device (ILUPP_BATCH_APPLY_MAX_N applied);
+ * negative: an error code */
+int64_t ilupp_hip_ilu0_refactor_batch_max_n(void);
 
 /* ---------------------------------------------------------------------------------------------
  * Measurement hooks used by bench.py (not part of the reference's surface).
