@@ -482,14 +482,19 @@ int ilu0_factor(ilupp_precond *p, const DevMat &A, const int32_t *head)
     bool grid = head != nullptr && p->side != nullptr && grid_guess(A.n, A.nnz, head, &gd);
     int32_t grid_bad = 0;
     bool lm = false;
+    // (a grid whose factor launch holds one workgroup per CU: that launch proves the pattern itself, on the CUs whose tile has ended --
+    // st_wave.hip: wa_tail_proof --, and nothing runs on the side stream)
+    const bool tail = grid && wx_tail_proof_wanted(gd.ny, gd.nz);
     for (;;) {
         if (grid) {
             if (p->verdict_clean) p->verdict_clean = false;
             else ILUPP_HIP(hipMemsetAsync(p->ctrl + 8, 0, sizeof(int32_t), st));
-            ILUPP_HIP(hipEventRecord(p->jev[0], st));
-            ILUPP_HIP(hipStreamWaitEvent(p->side, p->jev[0], 0));
-            grid_check_launch(p->side, A, gd, p->ctrl + 8);
-            ILUPP_HIP(hipEventRecord(p->jev[1], p->side));
+            if (!tail) {
+                ILUPP_HIP(hipEventRecord(p->jev[0], st));
+                ILUPP_HIP(hipStreamWaitEvent(p->side, p->jev[0], 0));
+                grid_check_launch(p->side, A, gd, p->ctrl + 8);
+                ILUPP_HIP(hipEventRecord(p->jev[1], p->side));
+            }
             grid_schedules(st, A, gd, &p->Lc, &p->Uc, &p->sA, &p->sU, &p->max_row_len, max_wgs);
         } else {
             // one pass over A's pattern: row counts of L and U, diagonal check, and the factor-sweep schedules (L shares A's
@@ -579,8 +584,15 @@ int ilu0_factor(ilupp_precond *p, const DevMat &A, const int32_t *head)
     // (the factor kernel waits for the proof -- it lives on short hand-over latencies and loses more next to the proof's 4.6 TB/s
     // stream than the wait costs --, but what is queued in front of it, the clearing of its control words and exchange, does not;
     // with the lane tables in closed form the proof is what the analysis phase lasts)
-    p->pkL.join_ev = (grid && wx_numeric) ? p->jev[1] : nullptr;
-    if (grid && !wx_numeric) ILUPP_HIP(hipStreamWaitEvent(st, p->jev[1], 0));
+    // (... unless that kernel proves the pattern itself, behind its tiles: then it waits for nothing, and the analysis phase is the table chain)
+    p->pkL.join_ev = (grid && wx_numeric && !tail) ? p->jev[1] : nullptr;
+    p->pkL.tail_proof = grid && tail && wx_numeric;
+    p->pkL.tail_g[0] = gd.nx; p->pkL.tail_g[1] = gd.ny; p->pkL.tail_g[2] = gd.nz;
+    bool proof_queued = !tail;                      // (on the side stream, above)
+    if (grid && !wx_numeric) {
+        if (tail) { grid_check_launch(st, A, gd, p->ctrl + 8); proof_queued = true; }      // (another factor kernel runs: the proof here and now)
+        else ILUPP_HIP(hipStreamWaitEvent(st, p->jev[1], 0));
+    }
     p->pkL.join_verdict = -1;                       // (-1: nobody has read the verdict yet)
     // (... and queues the arming of the first apply behind that read-back; the speculation's leftovers -- pending read-backs of the lane
     // tables' flags -- lie in front of it too)
@@ -588,6 +600,7 @@ int ilu0_factor(ilupp_precond *p, const DevMat &A, const int32_t *head)
     rc = ilu0_numeric_any(p, A, have_prog, &kms);
     p->pkL.arm = nullptr; p->pkL.arm_ctx = nullptr; p->pkL.arm_ev = nullptr;
     p->pkL.join_ev = nullptr;
+    p->pkL.tail_proof = false;
     // (the wave-exchange factor kernel's own read-back has been waited for -- through an event, so that what it queued behind it, the
     // arming of the first apply, runs on: no wait for the whole stream here then)
     const bool waited = wx_numeric && p->pkL.join_verdict >= 0;
@@ -595,7 +608,8 @@ int ilu0_factor(ilupp_precond *p, const DevMat &A, const int32_t *head)
     if (grid && p->pkL.join_verdict >= 0) {
         grid_bad = p->pkL.join_verdict;
     } else if (grid) {
-        ILUPP_HIP(hipStreamWaitEvent(st, p->jev[1], 0));
+        if (!tail) ILUPP_HIP(hipStreamWaitEvent(st, p->jev[1], 0));
+        else if (!proof_queued) grid_check_launch(st, A, gd, p->ctrl + 8);      // (the factor kernel that ran was not the one that proves)
         ILUPP_HIP(d2h_async(st, &grid_bad, p->ctrl + 8, sizeof(int32_t)));
     }
     if (!waited) ILUPP_HIP(stream_sync(st));

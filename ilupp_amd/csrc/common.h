@@ -154,6 +154,10 @@ struct PackedSweep {
     // the factor kernel waits for the one (behind the launches that prepare it) and its own read-back takes the other along
     hipEvent_t join_ev = nullptr;
     int32_t join_verdict = 0;
+    // ... or no proof has been launched at all (tail_proof: st_wave.hip's wx_tail_proof_wanted said the factor launch will hold one workgroup
+    // per CU): the factor kernel's workgroups prove the grid tail_g = (nx, ny, nz) themselves, behind their tiles (st_wave.hip: wa_tail_proof)
+    bool tail_proof = false;
+    int32_t tail_g[3] = {0, 0, 0};
     // (forward sweep of a static ILU(0)) what the factor kernel's launch is followed by, behind its read-back and in front of the wait for
     // it: the arming of the first apply (api.hip: arm_apply) -- `arm` runs with `arm_ctx`, the wait is for `arm_ev` instead of the stream
     void (*arm)(void *) = nullptr;
@@ -312,6 +316,7 @@ int ilu0_symbolic_and_schedule(hipStream_t st, const DevMat &A, DevMat *L, DevMa
 void ilu0_write_patterns(hipStream_t st, const DevMat &A, DevMat *L, DevMat *U);
 void finish_chains(Schedule *fwd, Schedule *bwd);
 const char *wx_factor_kernel_name();     // st_wave.hip: the factor kernel ilu0_numeric_wx launches (k_ilu0_wa<0, 4, 4>), as a profiler names it
+bool wx_tail_proof_wanted(int32_t ny, int32_t nz);   // st_wave.hip: the factor launch of a box grid of ny x nz lines will prove the pattern itself (no k_grid_check)
 bool wx_vec_on();            // st_wave.hip: the sweeps move the caller's vector through their vector wave (no level-major copies, no k_st_vec)
 // grid.hip: the first analysis pass for lexicographic box-grid stencil matrices (guess from row 0, proof on a side stream)
 struct GridDims { int32_t nx, ny, nz; };

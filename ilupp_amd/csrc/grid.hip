@@ -108,46 +108,17 @@ void grid_shape_forget(int32_t n, int64_t nnz, const void *idx)
     if (victim >= 0) g_shapes.seen.erase(g_shapes.seen.begin() + victim);
 }
 
-// One row per lane.  The eight index words a row can reach from its expected start are fetched with two 16-byte loads whatever the
-// row turns out to hold (buffer loads: past the end of the array they return zeros), so nothing about a row waits for anything else
-// about it; a wave's 64 rows read one contiguous run of the index array (1.8 KB).
+// The proof as a launch of its own: one row per thread and pass (st_common.h: grid_row_ok).
 __global__ void __launch_bounds__(256)
 k_grid_check(const int32_t n, const long long nnz, const GridDims g, const int32_t *__restrict__ ptr, const int32_t *__restrict__ idx,
              int32_t *__restrict__ bad)
 {
-    typedef unsigned int v4u_ __attribute__((ext_vector_type(4)));
     bool ok = true;
-    const unsigned unx = (unsigned)g.nx, uny = (unsigned)g.ny;
-    const int sxy = g.nx * g.ny;
-    // (an index array of more than 4 GB cannot be covered by one buffer resource: the host does not take such a matrix here)
-    const __amdgpu_buffer_rsrc_t ri = __builtin_amdgcn_make_buffer_rsrc(const_cast<int32_t *>(idx), 0, (int)((unsigned)nnz * 4u), 0x00020000);
+    const __amdgpu_buffer_rsrc_t ri = grid_idx_rsrc(idx, nnz);
     for (long long r0 = (long long)blockIdx.x * 256; r0 < n; r0 += (long long)gridDim.x * 256) {
         const long long rr = r0 + threadIdx.x;
         if (rr >= n) break;
-        const unsigned r = (unsigned)rr;
-        const unsigned l = r / unx, x = r - l * unx;
-        const unsigned z = l / uny, y = l - z * uny;
-        const long long e = grid_row_start((int)x, (int)y, (int)z, g);
-        const unsigned eo = (unsigned)e * 4u;
-        const v4u_ c0 = __builtin_amdgcn_raw_buffer_load_b128(ri, eo, 0, 0);
-        const v4u_ c1 = __builtin_amdgcn_raw_buffer_load_b128(ri, eo + 16u, 0, 0);
-        const int p = ptr[r];
-        const int pn = rr == n - 1 ? ptr[n] : 0;
-        ok = ok && (long long)p == e && (rr != n - 1 || (long long)pn == nnz);
-        // the expected columns, in stored order, against the words that were fetched
-        const int ri_ = (int)r;
-        int want[7];
-        int m = 0;
-        if (z > 0) want[m++] = ri_ - sxy;
-        if (y > 0) want[m++] = ri_ - g.nx;
-        if (x > 0) want[m++] = ri_ - 1;
-        want[m++] = ri_;
-        if ((int)x < g.nx - 1) want[m++] = ri_ + 1;
-        if ((int)y < g.ny - 1) want[m++] = ri_ + g.nx;
-        if ((int)z < g.nz - 1) want[m++] = ri_ + sxy;
-        const int got[8] = {(int)c0.x, (int)c0.y, (int)c0.z, (int)c0.w, (int)c1.x, (int)c1.y, (int)c1.z, (int)c1.w};
-#pragma unroll
-        for (int j = 0; j < 7; ++j) ok = ok && (j >= m || got[j] == want[j]);
+        ok = grid_row_ok(n, nnz, g, ptr, ri, rr) && ok;
     }
     if (__builtin_amdgcn_ballot_w64(!ok) != 0 && (threadIdx.x & 63) == 0) atomicOr(bad, 1);
 }

@@ -62,6 +62,60 @@ __device__ __forceinline__ long long grid_row_start(const int x, const int y, co
     return 7 * r - miss;
 }
 
+// The proof that a matrix IS the box grid g, for ONE row r < n: row pointer and columns against the closed form, and ptr[n] == nnz with
+// row n - 1.  The eight index words a row can reach from its expected start are fetched with two 16-byte loads whatever the row turns out
+// to hold (buffer loads: past the end of the array they return zeros), so nothing about a row waits for anything else about it; a wave's
+// 64 rows read one contiguous run of the index array (1.8 KB).  `ri` covers the index array (grid_idx_rsrc).
+__device__ __forceinline__ bool grid_row_ok(const int32_t n, const long long nnz, const GridDims &g, const int32_t *__restrict__ ptr,
+                                            const __amdgpu_buffer_rsrc_t ri, const long long rr)
+{
+    typedef unsigned int v4u_ __attribute__((ext_vector_type(4)));
+    const unsigned unx = (unsigned)g.nx, uny = (unsigned)g.ny;
+    const int sxy = g.nx * g.ny;
+    const unsigned r = (unsigned)rr;
+    const unsigned l = r / unx, x = r - l * unx;
+    const unsigned z = l / uny, y = l - z * uny;
+    const long long e = grid_row_start((int)x, (int)y, (int)z, g);
+    const unsigned eo = (unsigned)e * 4u;
+    const v4u_ c0 = __builtin_amdgcn_raw_buffer_load_b128(ri, eo, 0, 0);
+    const v4u_ c1 = __builtin_amdgcn_raw_buffer_load_b128(ri, eo + 16u, 0, 0);
+    const int p = ptr[r];
+    const int pn = rr == n - 1 ? ptr[n] : 0;
+    bool ok = (long long)p == e && (rr != n - 1 || (long long)pn == nnz);
+    // the expected columns, in stored order, against the words that were fetched
+    const int ri_ = (int)r;
+    int want[7];
+    int m = 0;
+    if (z > 0) want[m++] = ri_ - sxy;
+    if (y > 0) want[m++] = ri_ - g.nx;
+    if (x > 0) want[m++] = ri_ - 1;
+    want[m++] = ri_;
+    if ((int)x < g.nx - 1) want[m++] = ri_ + 1;
+    if ((int)y < g.ny - 1) want[m++] = ri_ + g.nx;
+    if ((int)z < g.nz - 1) want[m++] = ri_ + sxy;
+    const int got[8] = {(int)c0.x, (int)c0.y, (int)c0.z, (int)c0.w, (int)c1.x, (int)c1.y, (int)c1.z, (int)c1.w};
+#pragma unroll
+    for (int j = 0; j < 7; ++j) ok = ok && (j >= m || got[j] == want[j]);
+    return ok;
+}
+// ... for the run of rows [r0, r1), r1 <= n, one row per lane and pass: lane `lane` of `nlanes` takes r0 + lane, r0 + lane + nlanes, ...
+// (UNR passes are unrolled).  Callers: grid.hip's k_grid_check, and the factor kernel's workgroups behind their tile (st_wave.hip: wa_tail_proof).
+template <int UNR>
+__device__ __forceinline__ bool grid_rows_ok(const int32_t n, const long long nnz, const GridDims &g, const int32_t *__restrict__ ptr,
+                                             const __amdgpu_buffer_rsrc_t ri, const long long r0, const long long r1, const int lane,
+                                             const int nlanes)
+{
+    bool ok = true;
+#pragma unroll UNR
+    for (long long rr = r0 + lane; rr < r1; rr += nlanes) ok = grid_row_ok(n, nnz, g, ptr, ri, rr) && ok;
+    return ok;
+}
+// (an index array of more than 4 GB cannot be covered by one buffer resource: grid_guess does not take such a matrix)
+__device__ __forceinline__ __amdgpu_buffer_rsrc_t grid_idx_rsrc(const int32_t *idx, const long long nnz)
+{
+    return __builtin_amdgcn_make_buffer_rsrc(const_cast<int32_t *>(idx), 0, (int)((unsigned)nnz * 4u), 0x00020000);
+}
+
 // entries of L before column r = (x, y, z): four per column minus the neighbours beyond the box
 __device__ __forceinline__ long long ig_col_start(const int x, const int y, const int z, const GridDims &g)
 {

@@ -751,8 +751,14 @@ struct WfArgs {
     double *xch;
     int64_t xch_len;                              // doubles of the exchange: a workgroup's export window never reaches past it
     int32_t *ctrl;                                // [0] ticket, [1] error
-    int32_t flags;                                // 2 = every workgroup of the launch is resident at once; 8 = compact L records (format 2)
+    int32_t flags;                                // 2 = every workgroup of the launch is resident at once; 8 = compact L records (format 2);
+                                                  // 16 = the workgroups prove the box grid pf_g behind their tiles (wa_tail_proof; with 2 only)
     int32_t *prog;                                // [tile] steps done, [nwg + tile] blocks of eight steps somebody has asked for
+    // the tail proof: A's index arrays, and what they are compared with (ctrl[9]: the next row nobody has claimed, ctrl[8]: the verdict)
+    const int32_t *pf_ptr, *pf_idx;
+    long long pf_nnz;
+    int32_t pf_n;
+    GridDims pf_g;
 };
 struct WfPair { int idx0, stride, sk, cnt; unsigned at0; int atm, klast, sh, hasT; int astart, pw; };    // (st_direct.hip: SdPair; astart: where the producer's workgroup exports its first step; pw: that workgroup)
 
@@ -796,6 +802,7 @@ struct WaCfg {
     static_assert(Lds * (4 / NCW) <= 160 * 1024 - 256 * (4 / NCW), "the LDS of a CU");
 };
 enum { WA_CP = 0, WA_LF = 4, WA_IP = 8, WA_TP = 9, WA_EP = 10, WA_DEAD = 11, WA_BIG = 12, WA_WARM = 13,          // (set by the set-up)
+       WA_TAIL = 14,            // (tail proof, set by the prefetcher) bit 0: the trigger has been seen, bit 1: the prefetcher has left
        WA_BARC = 20, WA_BARG = 21 };
 static constexpr unsigned kWaSpinLimit = 1u << 24;
 
@@ -1284,6 +1291,7 @@ __device__ __forceinline__ void wa_loader(const WfArgs &A, unsigned char *lds, c
 // atomic add on claim[tile] (from -1; block 0 is what the tile's loaders bring before its first step); a tile counts as begun, for
 // this purpose, when its poller says that every workgroup it reads from has begun -- some twenty steps before its first.  While
 // its own tile works the wave sleeps (it would take from what its CU can have in flight).
+static constexpr int kTailSlice = 4096;                      // rows a wave of the tail proof claims at a time (wa_tail_proof; 256^3: 2048 the same, 1024 and 8192 slower)
 static constexpr int kPfLead = 32;                           // steps ahead of a tile's published progress that are asked for
 
 template <int NCW, int D>
@@ -1331,6 +1339,10 @@ __device__ __forceinline__ void wa_helper(const WfArgs &A, unsigned char *lds, c
     const __amdgpu_buffer_rsrc_t rs = wf_rsrc(A);
     unsigned acc = 0;
     bool own_done = false, own_warm = false;
+    // (tail proof) the role waves of a workgroup whose tile has ended sleep on WA_TAIL until this wave has seen the trigger: the LAST
+    // ticket's tile has begun -- from then on no CU gets a new tile, and the ones without one are the proof's
+    const bool tail = (A.flags & 16) != 0;
+    bool trig = !tail;
     unsigned idle = 0;
     // the (first two) workgroups this one imports from: they work right before it does, and until it begins it has nothing else to do
     int up1 = -1, up2 = -1;
@@ -1369,6 +1381,10 @@ __device__ __forceinline__ void wa_helper(const WfArgs &A, unsigned char *lds, c
             // (a launch of more workgroups than the chip holds: this one's CU is wanted by the next)
             if (!(A.flags & 2)) break;
         }
+        if (!trig && own_done) {
+            if (ld_agent_i32(&prog[nwg - 1]) >= 0) { trig = true; if (ln == 0) wa_set<C>(lds, WA_TAIL, 1); }
+            else if (ld_agent_i32(&A.ctrl[1]) != 0) break;
+        }
         // FIVE other tiles, fixed.  The (two) tiles this one imports from: they begin some twenty steps before it and it is idle till
         // then -- a tile's first steps, which the next tile waits for, always have somebody.  And three far ones: half the launch
         // away, an eighth of a line of tiles away, and both (on a box grid in 16 x 16 patches: eight patches on in z, in y, in both --
@@ -1398,7 +1414,7 @@ __device__ __forceinline__ void wa_helper(const WfArgs &A, unsigned char *lds, c
             lead_ += (long long)(8 * (cl + 2) - pr);
 #endif
         }
-        if (allfin && own_done) break;
+        if (allfin && own_done && trig) break;
         if (!did) {
             __builtin_amdgcn_s_sleep(64);
             if (own_done && ++idle > (1u << 18)) break;
@@ -1408,7 +1424,52 @@ __device__ __forceinline__ void wa_helper(const WfArgs &A, unsigned char *lds, c
 #ifdef WX_STAMP
     if (ln == 0 && wg < 4096) { g_wf_wait[wg * 16 + 9] = npf_; g_wf_wait[wg * 16 + 10] = nscan_; g_wf_wait[wg * 16 + 11] = (unsigned long long)lead_; }
 #endif
+    if (tail && ln == 0) wa_set<C>(lds, WA_TAIL, trig ? 3 : 2);                                    // (nobody waits for a wave that has left)
     if (acc == 0x9e3779b9u && A.val_bytes == 0xfffffff3u) atomicExch(&A.ctrl[1], (int)acc);        // (the loads above are not dead code)
+}
+
+// The tail proof (flags & 16): what k_grid_check does in a launch of its own in front of this kernel, done by the role waves of the
+// workgroups whose tile has ended, late in the launch -- the kernel's result does not depend on the verdict (its dependencies come
+// from the dimensions, its loads of A are clamped), the host drops it when the verdict is bad.  A wave claims `slice` rows at a time
+// from ctrl[9] until all n are taken; every claimed slice is finished by its claimer, and the workgroup of the last tile to end always
+// comes here behind the trigger, so when the launch ends ctrl[9] >= n and rows 0 .. n - 1 have been checked.  The 0.5 GB stream must
+// not run beside tiles at work on the same CU, nor while the chip is busy: nothing is claimed before the
+// LAST ticket's tile has begun.  A wave that comes earlier looks at that tile's progress word ONCE and then sleeps on WA_TAIL, which
+// its workgroup's prefetcher sets from the scan loop it runs anyway; it leaves when told to, on WA_DEAD, when the prefetcher has left
+// and after a bounded number of looks.
+// (Not inlined, and its arguments by value: folded into the kernel's body this code takes part in the register allocation of the
+// tile's loops.  As a call at the kernel's end it costs the kernel two VGPRs -- 138 against 136, three waves per SIMD as before --, no
+// scratch and no spill; unrolled twice it needs 160 registers and scratch for the ones a callee must save, and is no faster.)
+typedef __attribute__((address_space(3))) const int WaLdsInt;
+__device__ __noinline__ void wa_tail_proof(int32_t *ctrl, const int32_t *last_prog, WaLdsInt *cnt, const int32_t *ptr, const int32_t *idx,
+                                           const long long nnz, const int32_t n, const int32_t nx, const int32_t ny, const int32_t nz,
+                                           const int ln)
+{
+    constexpr int slice = kTailSlice;
+    if (ld_agent_i32(last_prog) < 0) {
+        unsigned looks = 0;
+        for (;;) {
+            asm volatile("" ::: "memory");
+            const int v = cnt[WA_TAIL], dead = cnt[WA_DEAD];
+            asm volatile("" ::: "memory");
+            if (dead != 0) return;
+            if (v & 1) break;
+            if ((v & 2) || ++looks > (1u << 18)) return;
+            __builtin_amdgcn_s_sleep(127);
+        }
+    }
+    const GridDims g = {nx, ny, nz};
+    const __amdgpu_buffer_rsrc_t ri = grid_idx_rsrc(idx, nnz);
+    bool ok = true;
+    for (;;) {
+        int r0 = 0;
+        if (ln == 0) r0 = atomicAdd(&ctrl[9], slice);
+        r0 = __builtin_amdgcn_readfirstlane(r0);
+        if (r0 < 0 || r0 >= n) break;
+        const long long r1 = (long long)r0 + slice < n ? (long long)r0 + slice : n;
+        ok = grid_rows_ok<1>(n, nnz, g, ptr, ri, r0, r1, ln, 64) && ok;
+    }
+    if (__builtin_amdgcn_ballot_w64(!ok) != 0 && ln == 0) atomicOr(ctrl + 8, 1);
 }
 
 // The waves of the roles on the workgroup's tile.  They meet at wa_bar, not at s_barrier (which would count the prefetcher too).  (A
@@ -1679,6 +1740,9 @@ k_ilu0_wa(WfArgs A)
         return;
     }
     wa_tile<NCW, D>(A, lds, s_cnt, s_total, wg);
+    if (A.flags & 16)
+        wa_tail_proof(A.ctrl, A.prog + (gridDim.x - 1), (WaLdsInt *)(lds + C::Cnt), A.pf_ptr, A.pf_idx, A.pf_nnz, A.pf_n, A.pf_g.nx,
+                      A.pf_g.ny, A.pf_g.nz, t & 63);
 }
 
 // the factor kernel ilu0_numeric_wx launches, as a profiler names it (ilupp_hip_kernel_names)
@@ -1695,8 +1759,28 @@ __global__ void k_wa_prepare(int32_t *__restrict__ ctrl, int32_t *__restrict__ p
 {
     const long long i0 = (long long)blockIdx.x * blockDim.x + threadIdx.x, stride = (long long)gridDim.x * blockDim.x;
     if (i0 < 4) ctrl[i0] = 0;
+    if (i0 == 9) ctrl[9] = 0;                                          // (the tail proof's claim counter)
     for (long long i = i0; i < nprog; i += stride) prog[i] = -1;
     for (long long i = i0; i < nx; i += stride) xch[i] = kSentinel;
+}
+
+// compute units of the current device (-1: unknown)
+static int wa_cu_count()
+{
+    static int ncu[64];
+    int dev = 0;
+    ILUPP_HIP(hipGetDevice(&dev));
+    if (ncu[dev & 63] == 0) { int v = 0; ILUPP_HIP(hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev)); ncu[dev & 63] = v > 0 ? v : -1; }
+    return ncu[dev & 63];
+}
+
+// Will the factor launch of a box grid of ny x nz lines prove the pattern itself (wa_tail_proof)?  When its 16 x 16 patches are no more
+// than the chip has CUs (flags & 2 below) -- the caller then launches no k_grid_check.  ILUPP_GRID_TAIL_PROOF=0: never.
+bool wx_tail_proof_wanted(int32_t ny, int32_t nz)
+{
+    static const bool off = []() { const char *e = getenv("ILUPP_GRID_TAIL_PROOF"); return e && atoi(e) == 0; }();
+    if (off || ny < 16 || nz < 16) return false;
+    return (int64_t)((ny + 15) / 16) * ((nz + 15) / 16) <= (int64_t)wa_cu_count();
 }
 
 int ilu0_numeric_wx(hipStream_t st, const DevMat &A, PackedSweep *pl, PackedSweep *pu, int32_t *d_ctrl, float *kernel_ms,
@@ -1744,11 +1828,19 @@ int ilu0_numeric_wx(hipStream_t st, const DevMat &A, PackedSweep *pl, PackedSwee
     {
         // does the chip hold every workgroup of the launch at once?  (Then the prefetchers stay behind their own tile's end, for the
         // tiles that still work.)
-        static int ncu[64];
-        int dev = 0;
-        ILUPP_HIP(hipGetDevice(&dev));
-        if (ncu[dev & 63] == 0) { int v = 0; ILUPP_HIP(hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev)); ncu[dev & 63] = v > 0 ? v : -1; }
-        if (ncu[dev & 63] > 0 && (int64_t)pl->nwg <= (int64_t)ncu[dev & 63]) a.flags |= 2;
+        const int ncu = wa_cu_count();
+        if (ncu > 0 && (int64_t)pl->nwg <= (int64_t)ncu) a.flags |= 2;
+    }
+    a.pf_ptr = a.pf_idx = nullptr; a.pf_nnz = 0; a.pf_n = 0; a.pf_g = {0, 0, 0};
+    if (pl->tail_proof) {
+        const GridDims g = {pl->tail_g[0], pl->tail_g[1], pl->tail_g[2]};
+        if (a.flags & 2) {
+            a.flags |= 16;
+            a.pf_ptr = A.ptr; a.pf_idx = A.idx; a.pf_nnz = A.nnz; a.pf_n = A.n; a.pf_g = g;
+        } else {
+            // (the schedule has more workgroups than wx_tail_proof_wanted counted patches: the proof as a launch, in front of the kernel)
+            grid_check_launch(st, A, g, d_ctrl + 8);
+        }
     }
     if (pl->join_ev) ILUPP_HIP(hipStreamWaitEvent(st, pl->join_ev, 0));       // (grid.hip's proof, on its side stream)
     ILUPP_HIP(hipEventRecord(e0, st));
@@ -1771,7 +1863,8 @@ int ilu0_numeric_wx(hipStream_t st, const DevMat &A, PackedSweep *pl, PackedSwee
     } else {
         ILUPP_HIP(stream_sync(st));
     }
-    pl->join_verdict = ctrl[8];
+    // (a tail proof that did not get through all rows -- a launch that gave up -- has proven nothing)
+    pl->join_verdict = ((a.flags & 16) && ctrl[9] < A.n) ? 1 : ctrl[8];
     if (kernel_ms) ILUPP_HIP(hipEventElapsedTime(kernel_ms, e0, e1));
     if (ctrl[1] != 0) return ILUPP_ERR_TIMEOUT;
     pl->fmt = compact ? 2 : 1; pu->fmt = 1;
