@@ -282,7 +282,7 @@ def apply_batch(preconditioners, vectors, transpose=False):
     native call; an empty list gives ``[]``.  Out of scope: the device classes (``ilupp_amd.device.DevicePreconditioner`` has no "ILUTP" /
     "ILUCP" kind; device vectors go through ``ilupp_amd.device.pivot_apply_batch_``) and a batched apply of
     :class:`ILUppPreconditioner` objects.  Many systems SOLVED side by side, the whole preconditioned BiCGstab loop in one launch:
-    ``ilupp_amd.device.bicgstab_batch``."""
+    ``ilupp_amd.device.bicgstab_batch`` (these classes, the non-pivoting ones and members without a preconditioner, mixed at will)."""
     preconditioners, vectors = list(preconditioners), list(vectors)
     for P in preconditioners:
         if not isinstance(P, (ILUCPPreconditioner, ILUTPPreconditioner)):

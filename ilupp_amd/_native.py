@@ -178,6 +178,12 @@ def lib():
                                             ctypes.c_int, _I32P]
     L.ilupp_hip_cg_batch_max_n.argtypes = []
     L.ilupp_hip_cg_batch_max_n.restype = ctypes.c_int64
+    L.ilupp_hip_bicgstab_batch_device.argtypes = [ctypes.c_int32, ctypes.POINTER(_VP), ctypes.POINTER(_VP), ctypes.POINTER(ctypes.c_int64),
+                                                  ctypes.POINTER(_VP), ctypes.POINTER(_VP), ctypes.POINTER(_VP), ctypes.POINTER(ctypes.c_int64),
+                                                  _VP, _VP, _VP, ctypes.POINTER(ctypes.c_int64), _VP, ctypes.c_int64, ctypes.c_int32,
+                                                  ctypes.c_double, ctypes.c_int32, _VP, _VP, _VP, _VP, ctypes.c_int, _I32P]
+    L.ilupp_hip_bicgstab_batch_max_n.argtypes = []
+    L.ilupp_hip_bicgstab_batch_max_n.restype = ctypes.c_int64
     L.ilupp_hip_ilu0_refactor_batch_device.argtypes = [ctypes.c_int32, ctypes.POINTER(_VP), ctypes.POINTER(_VP), ctypes.POINTER(_VP),
                                                        ctypes.POINTER(_VP), ctypes.POINTER(ctypes.c_int64), _VP, ctypes.c_int, _I32P]
     L.ilupp_hip_ilu0_refactor_batch_max_n.argtypes = []
@@ -220,6 +226,7 @@ ABI_SYMBOLS = [
     "ilupp_hip_ilucp_info", "ilupp_hip_ilucp_copy", "ilupp_hip_ilutp_create", "ilupp_hip_ilucp_create_batch", "ilupp_hip_ilutp_create_batch",
     "ilupp_hip_ilucp_apply_device", "ilupp_hip_pivot_apply_batch_device", "ilupp_hip_pivot_apply_batch", "ilupp_hip_pivot_apply_batch_max_n",
     "ilupp_hip_pivot_bicgstab_batch_device", "ilupp_hip_apply_batch_device", "ilupp_hip_cg_batch_device", "ilupp_hip_cg_batch_max_n",
+    "ilupp_hip_bicgstab_batch_device", "ilupp_hip_bicgstab_batch_max_n",
     "ilupp_hip_ilu0_refactor_batch_device", "ilupp_hip_ilu0_refactor_batch_max_n",
     "ilupp_hip_apply_block", "ilupp_hip_apply_block_device", "ilupp_hip_block_path",
     "ilupp_hip_spmm_device", "ilupp_hip_block_dot_device", "ilupp_hip_cg_block_update_device", "ilupp_hip_bicgstab_block_update_device",
@@ -1063,6 +1070,53 @@ def ilu0_refactor_batch_max_n():
 def cg_batch_max_n():
     """the largest n a member may have to be solved in cg_batch_device's launch on the current device (ILUPP_BATCH_APPLY_MAX_N applied)"""
     v = int(lib().ilupp_hip_cg_batch_max_n())
+    if v < 0:
+        _raise(v)
+    return v
+
+
+def bicgstab_batch_device(members, ns, matrices, b_ptr, x0_ptr, x_ptr, offsets, work_ptr, work_doubles, maxiter, rtol, check_every,
+                          iterations_ptr, flags_ptr, rr_ptr, init_ptr, sync=True):
+    """left-preconditioned BiCGstab for many small systems in ONE launch with members of every batched class
+    (ilupp_hip_bicgstab_batch_device): `members` are PivotedPreconditioner objects (ILUCP / ILUTP), Preconditioner objects (ILU0, ILUT,
+    ILUC, IChol0, ICholT) or None (no preconditioner), mixed at will; `ns` the members' dimensions; everything else as in
+    pivot_bicgstab_batch_device (7 doubles of workspace per unknown of the batch).  Ordered on the caller's stream (set_caller_stream).
+    Returns the routes: members of route 1 or 2 are NOT solved."""
+    cnt = len(members)
+    if len(matrices) != cnt or len(offsets) != cnt or len(ns) != cnt:
+        raise ValueError("%d preconditioners but %d dimensions, %d matrices and %d offsets" % (cnt, len(ns), len(matrices), len(offsets)))
+    if cnt == 0:
+        return []
+    HP, HV = (_VP * cnt)(), (_VP * cnt)()
+    for k, m in enumerate(members):
+        if m is None:
+            continue
+        if isinstance(m, PivotedPreconditioner):
+            HV[k] = m._h
+        elif isinstance(m, Preconditioner):
+            HP[k] = m._h
+        else:
+            raise TypeError("a batched solve takes ILUCP / ILUTP / ILU0 / ILUT / ILUC / IChol0 / ICholT preconditioners or None, got %s"
+                            % type(m).__name__)
+    D, I, P = (_VP * cnt)(), (_VP * cnt)(), (_VP * cnt)()
+    NNZ = (ctypes.c_int64 * cnt)()
+    for k, (d, i, p, nnz) in enumerate(matrices):
+        D[k], I[k], P[k], NNZ[k] = d, i, p, int(nnz)
+    N = (ctypes.c_int64 * cnt)(*[int(n) for n in ns])
+    O = (ctypes.c_int64 * cnt)(*[int(o) for o in offsets])
+    route = (ctypes.c_int32 * cnt)()
+    rc = lib().ilupp_hip_bicgstab_batch_device(cnt, HP, HV, N, D, I, P, NNZ, b_ptr, x0_ptr or None, x_ptr, O, work_ptr, int(work_doubles),
+                                               int(maxiter), float(rtol), int(check_every), iterations_ptr, flags_ptr, rr_ptr, init_ptr,
+                                               1 if sync else 0, route)
+    if rc:
+        _raise(rc)
+    return list(route)
+
+
+def bicgstab_batch_max_n():
+    """the largest n a member may have to be solved in bicgstab_batch_device's launch on the current device (ILUPP_BATCH_APPLY_MAX_N
+    applied)"""
+    v = int(lib().ilupp_hip_bicgstab_batch_max_n())
     if v < 0:
         _raise(v)
     return v

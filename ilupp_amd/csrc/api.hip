@@ -2869,6 +2869,36 @@ void batch_launched(BatchScratch &S, const BatchMember *members)
     for (int32_t i : S.launched) if (hipEvent_t *ev = members[i].batch_ev()) *ev = S.done_ev;
 }
 
+// The second table of a batched solve on the device: for every launched member (at least one) its matrix, its own words of the per-member
+// outputs and where its `wf` vectors of n start in the workspace -- member i's behind those of the members before it, launched or not.
+// The table grows as the launch does; the upload goes through the pinned copy on the scratch's stream.
+void batch_systems(BatchScratch &S, int32_t count, const BatchMember *members, int64_t wf, const double *const *d_data,
+                   const int32_t *const *d_indices, const int32_t *const *d_indptr)
+{
+    hipStream_t bs = S.stream;
+    const int32_t nl = (int32_t)S.launched.size();
+    if (nl > S.sys_cap) {
+        if (S.d_sys) { ILUPP_HIP(hipStreamSynchronize(bs)); (void)hipFree(S.d_sys); (void)hipHostFree(S.h_sys); S.d_sys = nullptr; S.h_sys = nullptr; }
+        S.sys_cap = 0;
+        const int32_t cap = nl < 64 ? 64 : nl;
+        ILUPP_HIP(hipMalloc(reinterpret_cast<void **>(&S.d_sys), sizeof(PivotSolveDesc) * (size_t)cap));
+        ILUPP_HIP(hipHostMalloc(reinterpret_cast<void **>(&S.h_sys), sizeof(PivotSolveDesc) * (size_t)cap, hipHostMallocDefault));
+        S.sys_cap = cap;
+    }
+    ILUPP_HIP(hipEventSynchronize(S.sys_ev));                       // (the upload before this one has read the pinned copy)
+    std::vector<int64_t> woff((size_t)count);
+    int64_t total = 0;
+    for (int32_t i = 0; i < count; ++i) { woff[(size_t)i] = wf * total; total += members[i].n; }
+    for (int32_t k = 0; k < nl; ++k) {
+        const int32_t i = S.launched[(size_t)k];
+        PivotSolveDesc &e = S.h_sys[k];
+        e.aval = d_data[i]; e.aidx = d_indices[i]; e.aptr = d_indptr[i];
+        e.woff = woff[(size_t)i]; e.member = i; e.pad = 0;
+    }
+    ILUPP_HIP(hipMemcpyAsync(S.d_sys, S.h_sys, sizeof(PivotSolveDesc) * (size_t)nl, hipMemcpyHostToDevice, bs));
+    ILUPP_HIP(hipEventRecord(S.sys_ev, bs));
+}
+
 // Queue the applies of all members: route 0 = the launch (n within the LDS cap, object not degenerate), 1 = too large (for the LDS, or for
 // a launch it would have to itself) and 2 = degenerate through the single apply on the member's own stream.  Everything is joined on the scratch's stream when this returns; nothing is waited for.
 // staged: the vectors were put there by work on the scratch's stream (the host entry), not by the caller's stream.
@@ -3013,26 +3043,7 @@ int ilupp_hip_cg_batch_device(int32_t count, ilupp_precond *const *members, cons
     const int32_t nl = (int32_t)S.launched.size();
     if (nl == 0) return ILUPP_OK;
     const size_t lds = batch_stage(S, mv.data(), cap_n);
-    if (nl > S.sys_cap) {
-        if (S.d_sys) { ILUPP_HIP(hipStreamSynchronize(bs)); (void)hipFree(S.d_sys); (void)hipHostFree(S.h_sys); S.d_sys = nullptr; S.h_sys = nullptr; }
-        S.sys_cap = 0;
-        const int32_t cap = nl < 64 ? 64 : nl;
-        ILUPP_HIP(hipMalloc(reinterpret_cast<void **>(&S.d_sys), sizeof(PivotSolveDesc) * (size_t)cap));
-        ILUPP_HIP(hipHostMalloc(reinterpret_cast<void **>(&S.h_sys), sizeof(PivotSolveDesc) * (size_t)cap, hipHostMallocDefault));
-        S.sys_cap = cap;
-    }
-    ILUPP_HIP(hipEventSynchronize(S.sys_ev));                       // (the upload before this one has read the pinned copy)
-    std::vector<int64_t> woff((size_t)count);
-    total = 0;
-    for (int32_t i = 0; i < count; ++i) { woff[(size_t)i] = wf * total; total += n[i]; }
-    for (int32_t k = 0; k < nl; ++k) {
-        const int32_t i = S.launched[(size_t)k];
-        PivotSolveDesc &e = S.h_sys[k];
-        e.aval = d_data[i]; e.aidx = d_indices[i]; e.aptr = d_indptr[i];
-        e.woff = woff[(size_t)i]; e.member = i; e.pad = 0;
-    }
-    ILUPP_HIP(hipMemcpyAsync(S.d_sys, S.h_sys, sizeof(PivotSolveDesc) * (size_t)nl, hipMemcpyHostToDevice, bs));
-    ILUPP_HIP(hipEventRecord(S.sys_ev, bs));
+    batch_systems(S, count, mv.data(), wf, d_data, d_indices, d_indptr);
     OR_RETURN(cg_batch_launch(bs, nl, S.d_table, S.d_sys, d_b, d_x0, d_x, d_work, lds, maxiter, rtol, check_every, d_iterations, d_flags, d_rr,
                               d_bnorm));
     batch_launched(S, mv.data());
@@ -3152,32 +3163,82 @@ int ilupp_hip_pivot_bicgstab_batch_device(int32_t count, ilupp_ilucp *const *mem
     const int32_t nl = (int32_t)S.launched.size();
     if (nl == 0) return ILUPP_OK;
     const size_t lds = batch_stage(S, mv.data(), cap_n);
-    if (nl > S.sys_cap) {
-        if (S.d_sys) { ILUPP_HIP(hipStreamSynchronize(bs)); (void)hipFree(S.d_sys); (void)hipHostFree(S.h_sys); S.d_sys = nullptr; S.h_sys = nullptr; }
-        S.sys_cap = 0;
-        const int32_t cap = nl < 64 ? 64 : nl;
-        ILUPP_HIP(hipMalloc(reinterpret_cast<void **>(&S.d_sys), sizeof(PivotSolveDesc) * (size_t)cap));
-        ILUPP_HIP(hipHostMalloc(reinterpret_cast<void **>(&S.h_sys), sizeof(PivotSolveDesc) * (size_t)cap, hipHostMallocDefault));
-        S.sys_cap = cap;
-    }
-    ILUPP_HIP(hipEventSynchronize(S.sys_ev));                       // (the upload before this one has read the pinned copy)
-    std::vector<int64_t> woff((size_t)count);
-    total = 0;
-    for (int32_t i = 0; i < count; ++i) { woff[(size_t)i] = 7 * total; total += members[i]->n; }
-    for (int32_t k = 0; k < nl; ++k) {
-        const int32_t i = S.launched[(size_t)k];
-        PivotSolveDesc &e = S.h_sys[k];
-        e.aval = d_data[i]; e.aidx = d_indices[i]; e.aptr = d_indptr[i];
-        e.woff = woff[(size_t)i]; e.member = i; e.pad = 0;
-    }
-    ILUPP_HIP(hipMemcpyAsync(S.d_sys, S.h_sys, sizeof(PivotSolveDesc) * (size_t)nl, hipMemcpyHostToDevice, bs));
-    ILUPP_HIP(hipEventRecord(S.sys_ev, bs));
+    batch_systems(S, count, mv.data(), 7, d_data, d_indices, d_indptr);
     OR_RETURN(pivot_bicgstab_batch_launch(bs, nl, S.d_table, S.d_sys, d_b, d_x0, d_x, d_work, lds, maxiter, rtol, check_every, d_iterations,
                                           d_flags, d_rr, d_init));
     batch_launched(S, mv.data());
     if (sync) return apply_batch_finish(S, count, mv.data(), false);
     order_caller_after(bs, S.cev[1]);
     return ILUPP_OK;
+    API_CATCH
+}
+
+int ilupp_hip_bicgstab_batch_device(int32_t count, ilupp_precond *const *plain, ilupp_ilucp *const *pivoted, const int64_t *n,
+                                    const double *const *d_data, const int32_t *const *d_indices, const int32_t *const *d_indptr,
+                                    const int64_t *nnz, const double *d_b, const double *d_x0, double *d_x, const int64_t *offsets,
+                                    double *d_work, int64_t work_doubles, int32_t maxiter, double rtol, int32_t check_every,
+                                    int64_t *d_iterations, int32_t *d_flags, double *d_rr, double *d_init, int sync, int32_t *route)
+{
+    API_TRY
+    if (count < 0 || !d_x || !offsets || !n || !d_data || !d_indices || !d_indptr || !nnz || !d_b || !d_work || !d_iterations || !d_flags ||
+        !d_rr || !d_init) { set_error("null argument"); return ILUPP_ERR_INVALID; }
+    if (maxiter < 0 || check_every < 0) { set_error("maxiter and check_every must not be negative"); return ILUPP_ERR_INVALID; }
+    // member i: pivoted[i], or plain[i], or neither (no preconditioner); a multilevel object among `plain` is named before anything reads
+    // it as an ilupp_precond
+    std::vector<const void *> seen_plain, seen_pivoted;
+    int64_t total = 0;
+    for (int32_t i = 0; i < count; ++i) {
+        ilupp_precond *p = plain ? plain[i] : nullptr;
+        ilupp_ilucp *m = pivoted ? pivoted[i] : nullptr;
+        if (p && m) { set_error("member " + std::to_string(i) + " of the batch: both a pivoting and a non-pivoting preconditioner"); return ILUPP_ERR_INVALID; }
+        if (p && is_live_ml(p)) { set_error("a multilevel preconditioner cannot be a member of a batch"); return ILUPP_ERR_INVALID; }
+        if (!d_data[i] || !d_indices[i] || !d_indptr[i]) { set_error("null argument"); return ILUPP_ERR_INVALID; }
+        if (n[i] <= 0 || n[i] > INT32_MAX) { set_error("matrix has size 0!"); return ILUPP_ERR_INVALID; }
+        if ((p && p->n != n[i]) || (m && m->n != n[i])) { set_error("matrix has wrong size for preconditioner!"); return ILUPP_ERR_WRONG_SIZE; }
+        if (p) seen_plain.push_back(p);
+        if (m) seen_pivoted.push_back(m);
+        total += n[i];
+    }
+    for (std::vector<const void *> *seen : {&seen_plain, &seen_pivoted}) {
+        std::sort(seen->begin(), seen->end());
+        if (std::adjacent_find(seen->begin(), seen->end()) != seen->end()) { set_error("a preconditioner appears twice in the batch"); return ILUPP_ERR_INVALID; }
+    }
+    if (work_doubles < 7 * total) { set_error("workspace too small: 7 doubles per unknown of the batch"); return ILUPP_ERR_INVALID; }
+    if (count == 0) return ILUPP_OK;
+    std::lock_guard<std::mutex> lk(g_batch_mu);
+    BatchScratch &S = batch_scratch();
+    hipStream_t bs = S.stream;
+    if (!S.sys_ev) ILUPP_HIP(hipEventCreateWithFlags(&S.sys_ev, hipEventDisableTiming));
+    order_after_caller(bs, S.cev[0]);
+    // the cap of the apply's launch, lowered by what the dot scratch takes (ILUPP_BATCH_APPLY_MAX_N lowers both)
+    int64_t cap_n = batch_apply_max_n();
+    if (bicgstab_batch_max_n() < cap_n) cap_n = bicgstab_batch_max_n();
+    std::vector<BatchMember> mv((size_t)count);
+    for (int32_t i = 0; i < count; ++i) {
+        if (pivoted && pivoted[i]) mv[(size_t)i] = batch_member(pivoted[i], 0);
+        else if (plain && plain[i]) mv[(size_t)i] = batch_member(plain[i], 0);
+        mv[(size_t)i].n = (int32_t)n[i];
+    }
+    batch_describe(S, count, mv.data(), offsets, cap_n);
+    if (route) for (int32_t i = 0; i < count; ++i) route[i] = S.route[(size_t)i];
+    const int32_t nl = (int32_t)S.launched.size();
+    if (nl == 0) return ILUPP_OK;
+    const size_t lds = batch_stage(S, mv.data(), cap_n);
+    batch_systems(S, count, mv.data(), 7, d_data, d_indices, d_indptr);
+    OR_RETURN(bicgstab_batch_launch(bs, nl, S.d_table, S.d_sys, d_b, d_x0, d_x, d_work, lds, maxiter, rtol, check_every, d_iterations, d_flags,
+                                    d_rr, d_init));
+    batch_launched(S, mv.data());
+    if (sync) return apply_batch_finish(S, count, mv.data(), false);
+    order_caller_after(bs, S.cev[1]);
+    return ILUPP_OK;
+    API_CATCH
+}
+
+int64_t ilupp_hip_bicgstab_batch_max_n(void)
+{
+    API_TRY
+    const int64_t a = batch_apply_max_n(), b = bicgstab_batch_max_n();
+    return a < b ? a : b;
     API_CATCH
 }
 

@@ -584,6 +584,12 @@ int cg_batch_work_factor();              // doubles of workspace per unknown of 
 int cg_batch_launch(hipStream_t st, int32_t count, const PivotApplyDesc *d_table, const PivotSolveDesc *d_systems, const double *d_b,
                     const double *d_x0, double *d_x, double *d_work, size_t sweep_bytes, int32_t maxiter, double rtol, int32_t check_every,
                     int64_t *d_iterations, int32_t *d_flags, double *d_rr, double *d_bnorm);
+// the same file: left-preconditioned BiCGstab with members of every batched class in one launch (k_bicgstab_batch), on the same two
+// tables: perm != nullptr a pivoting member, perm == nullptr a non-pivoting one, ptr1 == nullptr none; seven vectors of n from woff on.
+int64_t bicgstab_batch_max_n();          // the largest n of a member of that launch on the current device (LDS: dot scratch + 8 n bytes)
+int bicgstab_batch_launch(hipStream_t st, int32_t count, const PivotApplyDesc *d_table, const PivotSolveDesc *d_systems, const double *d_b,
+                          const double *d_x0, double *d_x, double *d_work, size_t sweep_bytes, int32_t maxiter, double rtol,
+                          int32_t check_every, int64_t *d_iterations, int32_t *d_flags, double *d_rr, double *d_init);
 
 // ilu0_batch.hip: the numeric ILU(0) re-factorisation of many small objects in one launch, one workgroup per member
 // (k_ilu0_refactor_batch).  One member: the matrix with the new values (device CSR arrays), the two triangles whose values are rewritten

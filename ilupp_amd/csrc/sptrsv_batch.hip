@@ -28,6 +28,7 @@
 // The non-pivoting classes (ILU0, ILUT, ILUC, IChol0, ICholT) take the same launch: a descriptor with perm == nullptr is an apply without a
 // permutation, its two triangles those of apply_plan / sweep_parts (api.hip: batch_describe).  Third kernel, at the end: k_cg_batch, the
 // whole preconditioned CG solve of many small symmetric positive definite systems in one launch, each with such a member or none.
+// Fourth kernel: k_bicgstab_batch, the BiCGstab solve for members of every class above, pivoting or not, or none, mixed in one launch.
 #include "common.h"
 
 namespace ilupp {
@@ -613,6 +614,172 @@ int cg_batch_launch(hipStream_t st, int32_t count, const PivotApplyDesc *d_table
     hipLaunchKernelGGL(k_cg_batch, dim3((unsigned)count), dim3(kBatchThreads), lds_bytes, st, d_table, d_systems, d_b, d_x0, d_x, d_work,
                        (unsigned)sweep_bytes, (int)maxiter, rtol, (int)check_every, reinterpret_cast<long long *>(d_iterations), d_flags, d_rr,
                        d_bnorm);
+    ILUPP_HIP(hipGetLastError());
+    return ILUPP_OK;
+}
+
+
+// ---- left-preconditioned BiCGstab for members of EVERY batched class, or none, in ONE launch: one workgroup per member --------------
+// k_bicgstab_batch is k_pivot_bicgstab_batch with the member's preconditioner left open: a descriptor with perm != nullptr is an ILUCP /
+// ILUTP member as there; perm == nullptr a non-pivoting one (ILU0, ILUT, ILUC, IChol0, ICholT: the two triangles of apply_plan /
+// sweep_parts, tmp from the scratch's block), which pivot_apply_member applies without a permutation; ptr1 == nullptr a member without a
+// preconditioner, prec_ of _bicgstab_block being the identity: the apply is skipped (the branch is uniform over the workgroup), r = r0*,
+// Ap = A p, As = A s.  Everything else is that kernel's: the half steps, the seven vectors, the LDS layout, the exit words -- and hence,
+// for every member, the bits of bicgstab(A_k, b_k[:, None], M_k).  k_pivot_bicgstab_batch stays as it is (the pivot-only batches of
+// device.bicgstab_batch still run it); it computes a subset of what this kernel computes.
+__global__ void __launch_bounds__(kBatchThreads)
+k_bicgstab_batch(const PivotApplyDesc *__restrict__ table, const PivotSolveDesc *__restrict__ systems, const double *bbase,
+                 const double *x0base, double *xbase, double *work, const unsigned sweep_bytes, const int maxiter, const double rtol,
+                 const int check_every, long long *iterations, int32_t *flags, double *rr_out, double *init_out)
+{
+    extern __shared__ unsigned long long lds[];
+    __shared__ unsigned s_progress;
+    __shared__ int s_fail;
+    const PivotApplyDesc d = table[blockIdx.x];
+    const PivotSolveDesc e = systems[blockIdx.x];
+    const int n = d.n, tid = threadIdx.x;
+    if (tid == 0) { s_progress = 0; s_fail = 0; }
+    double *dots = reinterpret_cast<double *>(lds);
+    unsigned long long *arr = lds + kDotScratch;
+    const int nb = (n + 255) / 256, chunk = (n + nb - 1) / nb;      // (n <= 256 kDotMaxNb)
+    unsigned turn = 0;
+    auto part = [&]() { return dots + (turn++ & 1u) * (2 * kDotMaxNb); };
+    const bool has_m = d.ptr1 != nullptr;
+    double *y = work + e.woff, *r = y + n, *r0 = r + n, *p = r0 + n, *s = p + n, *Ap = s + n, *As = Ap + n;
+    const double *b = bbase + d.xoff;
+    const double *x0 = x0base ? x0base + d.xoff : nullptr;
+    double *x = xbase + d.xoff;
+
+    // The loop as a sequence of HALF steps, so that the SpMV, the apply and the pair of dots behind it stand in the code once (the apply
+    // is two inlined sweeps: three copies of it would not fit the instruction cache):
+    //   half 0 (once):   y = x0 or 0; r0* = b (or b - A y); r = M^-1 r0*; r0* = r; p = r; init = sqrt(r.r); zero = (b.b == 0) | (init == 0)
+    //   half 1:          Ap = M^-1 (A p); rho = r.r0*; apr = Ap.r0*; alpha = rho / apr; s = r - alpha Ap
+    //   half 2:          As = M^-1 (A s); omega = (As.s) / (As.As); y += alpha p; y += omega s; r = s - omega As;
+    //                    beta = ((r.r0*) / rho) * (alpha / omega); p = p - omega Ap; p = beta p + r; the convergence test
+    for (int i = tid; i < n; i += kBatchThreads) y[i] = x0 ? x0[i] : 0.0;
+    __syncthreads();                                 // (also publishes s_progress and s_fail: a member without M meets no sweep's barrier)
+    bool failed = false, zero = false, active = false, converged = false, have_rr = false;
+    double init = 0.0, rho = 0.0, alpha = 0.0, rr = 0.0, v2[2];
+    long long iters = 0;
+    for (int half = 0, it = 0;; half = half == 1 ? 2 : 1) {
+        double *vec = half == 0 ? r : half == 1 ? Ap : As;
+        if (half != 0 || x0) {
+            wg_spmv(n, e.aptr, e.aidx, e.aval, half == 0 ? y : half == 1 ? p : s, half == 0 ? As : vec);
+            __syncthreads();
+        }
+        if (half == 0) {
+            if (x0) { for (int i = tid; i < n; i += kBatchThreads) r[i] = b[i] - As[i]; }
+            else { for (int i = tid; i < n; i += kBatchThreads) r[i] = b[i]; }
+            __syncthreads();
+        }
+        if (has_m) {
+            pivot_apply_member(d, vec, arr, sweep_bytes, &s_progress, &s_fail);
+            if (s_fail != 0) { failed = true; active = false; break; }
+        }
+        if (half == 0) {
+            for (int i = tid; i < n; i += kBatchThreads) { const double v = r[i]; r0[i] = v; p[i] = v; }
+            __syncthreads();
+        }
+        wg_dots<2>(n, nb, chunk, half == 2 ? As : r, half == 0 ? r : half == 1 ? r0 : s, half == 0 ? b : vec, half == 0 ? b : half == 1 ? r0 : As,
+                   part(), v2);
+        if (half == 0) {
+            init = __dsqrt_rn(v2[0]);
+            zero = v2[1] == 0.0 || init == 0.0;
+            active = !zero;
+            converged = zero;
+            if (!active || maxiter <= 0) break;
+        } else if (half == 1) {
+            rho = v2[0];
+            if (!(scalar_ok(rho) && scalar_ok(v2[1]))) { active = false; break; }      // breakdown: nothing more is touched, not converged
+            alpha = rho / v2[1];
+            for (int i = tid; i < n; i += kBatchThreads) { const double aap = alpha * Ap[i]; s[i] = r[i] - aap; }
+            __syncthreads();
+        } else {
+            const double omega = v2[0] / v2[1];
+            if (!scalar_ok(omega)) { active = false; break; }
+            for (int i = tid; i < n; i += kBatchThreads) {
+                const double ap = alpha * p[i];
+                double yv = y[i] + ap;
+                const double os = omega * s[i];
+                yv = yv + os;
+                y[i] = yv;
+                const double oas = omega * As[i];
+                r[i] = s[i] - oas;
+            }
+            __syncthreads();
+            wg_dots<1>(n, nb, chunk, r, r0, nullptr, nullptr, part(), v2);
+            const double beta = (v2[0] / rho) * (alpha / omega);
+            for (int i = tid; i < n; i += kBatchThreads) {
+                const double oap = omega * Ap[i];
+                const double pv = p[i] - oap;
+                const double bp = beta * pv;
+                p[i] = bp + r[i];
+            }
+            __syncthreads();
+            ++iters;
+            ++it;
+            if (check_every > 0 && it % check_every == 0 && rtol > 0.0) {
+                wg_dots<1>(n, nb, chunk, r, r, nullptr, nullptr, part(), v2);
+                rr = v2[0];
+                have_rr = true;                      // (r stays as it is from here to the exit when the loop ends now)
+                const double rel = __dsqrt_rn(rr) / init;
+                if (rel <= rtol) { converged = true; active = false; break; }
+            }
+            if (it >= maxiter) break;
+            have_rr = false;
+        }
+    }
+    if (!failed) {
+        if (!have_rr) { wg_dots<1>(n, nb, chunk, r, r, nullptr, nullptr, part(), v2); rr = v2[0]; }      // (r.r at the exit)
+        for (int i = tid; i < n; i += kBatchThreads) x[i] = y[i];
+    }
+    if (tid == 0) {                                  // (one writer per member: its own words, whatever the other members do)
+        *d.err = failed ? 1 : 0;
+        iterations[e.member] = iters;
+        flags[e.member] = (active ? 1 : 0) | (converged ? 2 : 0) | (failed ? 4 : 0) | (zero ? 8 : 0);
+        rr_out[e.member] = rr;
+        init_out[e.member] = init;
+    }
+}
+
+// bytes of dynamic LDS a workgroup of k_bicgstab_batch may take on the current device (as pivot_apply_batch_lds_cap)
+size_t bicgstab_batch_lds_cap()
+{
+    static thread_local int cap_dev = -1;
+    static thread_local size_t cap = 0;
+    int dev = 0;
+    ILUPP_HIP(hipGetDevice(&dev));
+    if (cap_dev != dev) {
+        int max_lds = 0;
+        ILUPP_HIP(hipDeviceGetAttribute(&max_lds, hipDeviceAttributeMaxSharedMemoryPerBlock, dev));
+        hipFuncAttributes fa;
+        ILUPP_HIP(hipFuncGetAttributes(&fa, reinterpret_cast<const void *>(&k_bicgstab_batch)));
+        const size_t room = (size_t)max_lds > fa.sharedSizeBytes ? (size_t)max_lds - fa.sharedSizeBytes : 0;
+        ILUPP_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_bicgstab_batch), hipFuncAttributeMaxDynamicSharedMemorySize, (int)room));
+        cap = room;
+        cap_dev = dev;
+    }
+    return cap;
+}
+
+// the largest n of a member of this launch: pivot_bicgstab_batch_max_n's formula on this kernel's own attributes
+int64_t bicgstab_batch_max_n()
+{
+    const size_t cap = bicgstab_batch_lds_cap(), scratch = sizeof(double) * (size_t)kDotScratch;
+    const int64_t by_lds = cap > scratch ? (int64_t)((cap - scratch) / 8) : 0;
+    return by_lds < 256 * kDotMaxNb ? by_lds : 256 * kDotMaxNb;
+}
+
+// `count` members, one workgroup each; sweep_bytes of LDS for the sweeps of every workgroup (the dot scratch comes on top)
+int bicgstab_batch_launch(hipStream_t st, int32_t count, const PivotApplyDesc *d_table, const PivotSolveDesc *d_systems, const double *d_b,
+                          const double *d_x0, double *d_x, double *d_work, size_t sweep_bytes, int32_t maxiter, double rtol,
+                          int32_t check_every, int64_t *d_iterations, int32_t *d_flags, double *d_rr, double *d_init)
+{
+    if (count <= 0) return ILUPP_OK;
+    const size_t lds_bytes = sizeof(double) * (size_t)kDotScratch + sweep_bytes;
+    if (lds_bytes > bicgstab_batch_lds_cap()) return ILUPP_ERR_UNSUPPORTED;
+    hipLaunchKernelGGL(k_bicgstab_batch, dim3((unsigned)count), dim3(kBatchThreads), lds_bytes, st, d_table, d_systems, d_b, d_x0, d_x, d_work,
+                       (unsigned)sweep_bytes, (int)maxiter, rtol, (int)check_every, reinterpret_cast<long long *>(d_iterations), d_flags, d_rr, d_init);
     ILUPP_HIP(hipGetLastError());
     return ILUPP_OK;
 }

@@ -259,32 +259,46 @@ class PivotedOperator:
 
 
 def bicgstab_batch(As, b, offsets, Ms, x0=None, maxiter=100, rtol=0.0, check_every=0, stats=None):
-    """Left-preconditioned BiCGstab for MANY small systems in ONE kernel launch (ilupp_hip_pivot_bicgstab_batch_device: one workgroup per
-    system runs the whole loop -- SpMV, apply, dot products, updates, convergence test -- with no host round trip).
+    """Left-preconditioned BiCGstab for MANY small systems in ONE kernel launch (one workgroup per system runs the whole loop -- SpMV,
+    apply, dot products, updates, convergence test -- with no host round trip).
 
-    ``As``: a list of DeviceCSR; ``Ms``: as many ``ilupp_amd.ILUCPPreconditioner`` / ``ILUTPPreconditioner`` objects (mixed at will, each
-    at most once) or ``PivotedOperator``s; ``b``: ONE contiguous 1-D fp64 CUDA tensor, member k's right-hand side is
+    ``As``: a list of DeviceCSR; ``Ms``: as many members, each of them an ``ilupp_amd.ILUCPPreconditioner`` / ``ILUTPPreconditioner``
+    object or a ``PivotedOperator``; or anything ``cg_batch`` takes (a ``DevicePreconditioner`` of the ILU0 / ILUT / ILUC / IChol0 /
+    ICholT kinds, a ``FactorOperator`` or a host class of the ctypes binding); or ``None`` (no preconditioner) -- mixed at will, each
+    object at most once.  A batch of pivoting members only goes through ilupp_hip_pivot_bicgstab_batch_device (k_pivot_bicgstab_batch),
+    every other batch through ilupp_hip_bicgstab_batch_device (k_bicgstab_batch, which takes all three kinds of member in the same
+    launch); a pivoting member has the same bits either way.  ``b``: ONE contiguous 1-D fp64 CUDA tensor, member k's right-hand side is
     ``b[offsets[k] : offsets[k] + n_k]``; ``x0``: the same layout.  Returns a new tensor of b's shape, a clone of ``x0`` or zeros, whose
     member slices hold the solutions; every other element is untouched.  Per member the loop of ``bicgstab`` for one column: ``maxiter``,
     ``rtol`` and ``check_every`` mean what they mean there, a member that converges or breaks down stops alone, and every member has the
-    bits of ``bicgstab(A_k, b_k[:, None], PivotedOperator(M_k), ...)``.  ``stats``, when a dict, receives "iterations" (int64),
-    "converged" (bool), "relres" (float64) -- `count` entries each, on the CPU -- and "route" (a list: 0 = solved in the launch, 1 = n
-    above the launch's LDS cap, 2 = degenerate factor; members of routes 1 and 2 are solved by that single solve inside the same call).
-    Ordered on torch's current stream; the host waits only when ``stats`` is asked for or a member takes route 1 or 2.  ValueError for a
-    wrong tensor, lists of unequal length, a slice outside ``b`` or a matrix and a preconditioner of different dimensions; TypeError
-    for a member of another class -- before any native call.  Out of scope: a transposed solve, host (numpy) vectors, the multilevel
-    class, several right-hand sides per member.  CG with the non-pivoting classes: ``cg_batch``."""
+    bits of ``bicgstab(A_k, b_k[:, None], M_k, ...)`` (``M_k`` in a ``PivotedOperator`` / ``FactorOperator`` where it has no ``apply_``).
+    ``stats``, when a dict, receives "iterations" (int64), "converged" (bool), "relres" (float64: sqrt(r.r) / ||r_0|| of the
+    preconditioned residuals, 0 for a zero member) -- `count` entries each, on the CPU -- and "route" (a list: 0 = solved in the launch,
+    1 = n above the launch's LDS cap, 2 = degenerate factor; members of routes 1 and 2 are solved by that single solve inside the same
+    call).  Ordered on torch's current stream; the host waits only when ``stats`` is asked for or a member takes route 1 or 2, so
+    ``refactor_batch_(check=False)`` -> ``bicgstab_batch`` -> ``refactor_batch_`` runs without a host wait.  ValueError for a wrong
+    tensor, lists of unequal length, a slice outside ``b`` or a matrix and a preconditioner of different dimensions; TypeError for a
+    member of another class or of the "ILUpp" kind -- before any native call.  Out of scope: a transposed solve, host (numpy) vectors,
+    the multilevel class, several right-hand sides per member."""
     As, Ms, offsets = list(As), list(Ms), [int(o) for o in offsets]
-    natives = []
+    natives, dims = [], []
     for A in As:
         if not isinstance(A, DeviceCSR):
             raise TypeError("bicgstab_batch takes DeviceCSR matrices, got %s" % type(A).__name__)
     for M in Ms:
+        if M is None:
+            natives.append(None)
+            continue
         pr = M.pr if isinstance(M, PivotedOperator) else getattr(M, "pr", M)
         if not isinstance(pr, _native.PivotedPreconditioner):
-            raise TypeError("bicgstab_batch takes ILUCPPreconditioner / ILUTPPreconditioner instances of the ctypes binding or "
-                            "PivotedOperators, got %s" % type(M).__name__)
+            try:
+                pr = _factor_native(M, "bicgstab_batch")[0]
+            except TypeError:
+                raise TypeError("bicgstab_batch takes ILUCPPreconditioner / ILUTPPreconditioner instances of the ctypes binding or "
+                                "PivotedOperators, ILU0 / ILUT / ILUC / IChol0 / ICholT preconditioners (DevicePreconditioners of those "
+                                "kinds, FactorOperators or the host classes) or None, got %s" % type(M).__name__) from None
         natives.append(pr)
+    pivot_only = all(isinstance(pr, _native.PivotedPreconditioner) for pr in natives)
     if not (len(As) == len(Ms) == len(offsets)):
         raise ValueError("%d matrices, %d preconditioners and %d offsets" % (len(As), len(Ms), len(offsets)))
     for name, t in (("b", b), ("x0", x0)):
@@ -294,11 +308,13 @@ def bicgstab_batch(As, b, offsets, Ms, x0=None, maxiter=100, rtol=0.0, check_eve
             raise ValueError("%s: expected a contiguous 1-D torch.float64 CUDA tensor" % name)
     if x0 is not None and x0.shape != b.shape:
         raise ValueError("x0: expected shape %s, got %s" % (tuple(b.shape), tuple(x0.shape)))
-    for k, (A, pr, o) in enumerate(zip(As, natives, offsets)):
-        if A.n != pr._n:
-            raise ValueError("member %d: the matrix has dimension %d, the preconditioner %d" % (k, A.n, pr._n))
-        if o < 0 or o + pr._n > b.numel():
-            raise ValueError("a vector of %d elements at offset %d does not lie inside b (%d elements)" % (pr._n, o, b.numel()))
+    for k, (A, M, pr, o) in enumerate(zip(As, Ms, natives, offsets)):
+        n = A.n if pr is None else pr._n if isinstance(pr, _native.PivotedPreconditioner) else _factor_n(M, pr)
+        if A.n != n:
+            raise ValueError("member %d: the matrix has dimension %d, the preconditioner %d" % (k, A.n, n))
+        if o < 0 or o + n > b.numel():
+            raise ValueError("a vector of %d elements at offset %d does not lie inside b (%d elements)" % (n, o, b.numel()))
+        dims.append(n)
     x = torch.zeros_like(b) if x0 is None else x0.clone()
     count = len(natives)
     if count == 0:
@@ -306,26 +322,33 @@ def bicgstab_batch(As, b, offsets, Ms, x0=None, maxiter=100, rtol=0.0, check_eve
             stats.update(iterations=torch.zeros(0, dtype=torch.int64), converged=torch.zeros(0, dtype=torch.bool),
                          relres=torch.zeros(0, dtype=torch.float64), route=[])
         return x
-    total = sum(pr._n for pr in natives)
-    work = torch.empty(7 * total, dtype=torch.float64, device=b.device)
+    work = torch.empty(7 * sum(dims), dtype=torch.float64, device=b.device)
     iters = torch.zeros(count, dtype=torch.int64, device=b.device)
     flags = torch.zeros(count, dtype=torch.int32, device=b.device)
     rr = torch.zeros(count, dtype=torch.float64, device=b.device)
     init = torch.zeros(count, dtype=torch.float64, device=b.device)
+    matrices = [(A.data.data_ptr(), A.indices.data_ptr(), A.indptr.data_ptr(), A.nnz) for A in As]
     _on_current_stream()
-    route = _native.pivot_bicgstab_batch_device(
-        natives, [(A.data.data_ptr(), A.indices.data_ptr(), A.indptr.data_ptr(), A.nnz) for A in As], b.data_ptr(),
-        0 if x0 is None else x0.data_ptr(), x.data_ptr(), offsets, work.data_ptr(), work.numel(), maxiter, rtol, check_every,
-        iters.data_ptr(), flags.data_ptr(), rr.data_ptr(), init.data_ptr(), sync=False)
+    if pivot_only:
+        route = _native.pivot_bicgstab_batch_device(
+            natives, matrices, b.data_ptr(), 0 if x0 is None else x0.data_ptr(), x.data_ptr(), offsets, work.data_ptr(), work.numel(),
+            maxiter, rtol, check_every, iters.data_ptr(), flags.data_ptr(), rr.data_ptr(), init.data_ptr(), sync=False)
+    else:
+        route = _native.bicgstab_batch_device(
+            natives, dims, matrices, b.data_ptr(), 0 if x0 is None else x0.data_ptr(), x.data_ptr(), offsets, work.data_ptr(),
+            work.numel(), maxiter, rtol, check_every, iters.data_ptr(), flags.data_ptr(), rr.data_ptr(), init.data_ptr(), sync=False)
     alone = {}
     for k, rt in enumerate(route):
         if rt == 0:
             continue
         # too large for the launch or degenerate: the single solve, whose bits the launch's members have
-        o, n = offsets[k], natives[k]._n
+        o, n = offsets[k], dims[k]
+        M = Ms[k]
+        if M is not None and not hasattr(M, "apply_"):
+            M = PivotedOperator(M) if isinstance(natives[k], _native.PivotedPreconditioner) else FactorOperator(M)
         st = {}
-        xk = bicgstab(As[k], b[o:o + n][:, None], PivotedOperator(natives[k]), x0=None if x0 is None else x0[o:o + n][:, None],
-                      maxiter=maxiter, rtol=rtol, check_every=check_every, stats=st)
+        xk = bicgstab(As[k], b[o:o + n][:, None], M, x0=None if x0 is None else x0[o:o + n][:, None], maxiter=maxiter, rtol=rtol,
+                      check_every=check_every, stats=st)
         x[o:o + n] = xk[:, 0]
         alone[k] = st
     if isinstance(stats, dict):
@@ -354,7 +377,7 @@ def _factor_native(P, who):
     pr = getattr(P, "pr", P)
     if isinstance(pr, _native.PivotedPreconditioner):
         raise TypeError("%s takes the non-pivoting classes; ILUCPPreconditioner / ILUTPPreconditioner go through pivot_apply_batch_ / "
-                        "bicgstab_batch" % who)
+                        "bicgstab_batch (which takes both families in one batch)" % who)
     kind = type(P).__name__[:-len("Preconditioner")] if type(P).__name__.endswith("Preconditioner") else ""
     if not isinstance(pr, _native.Preconditioner) or (pr is not P and kind not in _FACTOR_KINDS):
         raise TypeError("%s takes ILU0 / ILUT / ILUC / IChol0 / ICholT preconditioners of the ctypes binding, DevicePreconditioners of "
@@ -376,7 +399,8 @@ class FactorOperator:
     ``ICholTPreconditioner`` (built on the host by the ctypes binding) as the ``M`` of ``cg`` / ``bicgstab``: the counterpart of
     ``PivotedOperator`` for the non-pivoting classes.  ``apply_`` works in place on a device tensor of shape (n,) or (n, k) through
     ilupp_hip_apply_device / ilupp_hip_apply_block_device, ordered on torch's current stream.  ``cg(A, b[:, None], FactorOperator(P))``
-    is the solve every member of ``cg_batch`` has the bits of.  TypeError for any other class."""
+    is the solve every member of ``cg_batch`` has the bits of, ``bicgstab(A, b[:, None], FactorOperator(P))`` the one every such member
+    of ``bicgstab_batch`` has the bits of.  TypeError for any other class."""
 
     def __init__(self, P):
         if isinstance(P, (FactorOperator, DevicePreconditioner)):
@@ -447,10 +471,10 @@ def apply_batch_(members, x, offsets, transpose=False):
 def refactor_batch_(members, As, check=True):
     """The numeric ILU(0) re-factorisation of MANY small members in ONE kernel launch (ilupp_hip_ilu0_refactor_batch_device: one workgroup
     per member, its rows side by side): the members keep their patterns, schedules and tables and get the factors of ``As[k]``, a
-    DeviceCSR with member k's pattern and new values -- the step in front of ``cg_batch`` / ``apply_batch_`` when the values change and the
-    patterns do not.  ``members``: as for ``apply_batch_`` but of the ILU0 kind only (``DevicePreconditioner("ILU0", ...)``,
-    ``FactorOperator``s of, or the host class ``ILU0Preconditioner`` itself), each at most once.  Every member's factor has the bits of a
-    fresh construction from ``As[k]`` (and of the single ``refactor_``).  Returns the routes: 0 = the launch; 1 = n above the launch's
+    DeviceCSR with member k's pattern and new values -- the step in front of ``bicgstab_batch`` (nonsymmetric systems), ``cg_batch`` /
+    ``apply_batch_`` when the values change and the patterns do not.  ``members``: as for ``apply_batch_`` but of the ILU0 kind only
+    (``DevicePreconditioner("ILU0", ...)``, ``FactorOperator``s of, or the host class ``ILU0Preconditioner`` itself), each at most
+    once.  Every member's factor has the bits of a fresh construction from ``As[k]`` (and of the single ``refactor_``).  Returns the routes: 0 = the launch; 1 = n above the launch's
     cap (``_native.ilu0_refactor_batch_max_n()``), a longest row above the row cap (31 entries, fewer where 4 n + 5 120 bytes per entry
     do not fit into a workgroup's LDS: 28 at n = 4 000), or a member that would have the launch to itself with n >= 1 000 (alone it is
     faster on the single path); 2 = static form.  Members of routes 1 and 2 are re-factorised alone inside the same call, with the
@@ -458,9 +482,9 @@ def refactor_batch_(members, As, check=True):
     whose pattern differs keeps its factor bitwise as it was (status 1), the others are re-factorised.  ``check=True`` reads the status
     words with one host wait and raises ValueError naming the first such member (RuntimeError for status 2, a dependency wait that gave
     up); ``check=False`` returns ``(routes, status)``, status an int32 CUDA tensor, and waits for nothing in the steady state (refactor_batch_
-    -> ``cg_batch`` / plain ``apply_batch_`` -> refactor_batch_ with all members on route 0): a call whose launched members still hold copies of
-    the old values -- the packed sweeps a construction leaves, the packed / transposed / level-ordered sweeps of single or block applies --
-    waits once for its launch before it frees them, whatever the members' statuses turn out to be.  TypeError for a member of
+    -> ``bicgstab_batch`` / ``cg_batch`` / plain ``apply_batch_`` -> refactor_batch_ with all members on route 0): a call whose launched
+    members still hold copies of the old values -- the packed sweeps a construction leaves, the packed / transposed / level-ordered
+    sweeps of single or block applies -- waits once for its launch before it frees them, whatever the members' statuses turn out to be.  TypeError for a member of
     another kind or class, a pivoting member, the multilevel class or a matrix that is not a DeviceCSR; ValueError for lists of unequal
     length, a member named twice or a matrix and a member of different dimensions -- before any native call.  Out of scope: the other
     classes (no single re-factorisation to match), a batched FIRST construction, host (numpy) matrices."""
@@ -513,7 +537,8 @@ def cg_batch(As, b, offsets, Ms, x0=None, maxiter=100, rtol=0.0, check_every=0, 
     inside the same call).  Ordered on torch's current stream; the host waits only when ``stats`` is asked for or a member takes route 1
     or 2.  ValueError for a wrong tensor, lists of unequal length, a slice outside ``b`` or a matrix and a preconditioner of different
     dimensions; TypeError for a member of another class -- before any native call.  Out of scope: the multilevel class, pivoting members
-    (``bicgstab_batch``), k > 1 right-hand sides per member, host (numpy) vectors, a batched construction of the non-pivoting classes."""
+    (``bicgstab_batch``, which takes them next to everything this function takes, for nonsymmetric systems), k > 1 right-hand sides
+    per member, host (numpy) vectors, a batched construction of the non-pivoting classes."""
     As, Ms, offsets = list(As), list(Ms), [int(o) for o in offsets]
     for A in As:
         if not isinstance(A, DeviceCSR):

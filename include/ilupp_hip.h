@@ -454,6 +454,25 @@ int ilupp_hip_cg_batch_device(int32_t count, ilupp_precond *const *members, cons
 /* the largest n that takes route 0 in ilupp_hip_cg_batch_device on the current device (ILUPP_BATCH_APPLY_MAX_N applied); negative: an
  * error code */
 int64_t ilupp_hip_cg_batch_max_n(void);
+/* Left-preconditioned BiCGstab for MANY small systems at once with members of EVERY batched class in the same launch
+ * (k_bicgstab_batch, sptrsv_batch.hip): member i's preconditioner is pivoted[i] (an ILUCP / ILUTP object), or plain[i] (ILU0 / ILUT /
+ * ILUC / IChol0 / ICholT), or none when both are NULL (r = r0*, Ap = A p, As = A s); either array may be NULL as a whole; both entries
+ * non-NULL for one member: ILUPP_ERR_INVALID.  n (a host array of `count`) gives every member's dimension (it must agree with the
+ * member's object: ILUPP_ERR_WRONG_SIZE otherwise).  Matrices, vectors, d_work (7 * sum n_i doubles), the loop, the per-member outputs,
+ * routes (1 and 2 are NOT solved: the caller solves them one by one), ordering and sync as for ilupp_hip_pivot_bicgstab_batch_device,
+ * whose launch this one contains: a pivoting member has the same bits from either entry; a non-pivoting one those of the same solve
+ * with ilupp_hip_apply_block_device as its apply.  A re-factorisation (ilupp_hip_ilu0_refactor_device, ..._batch_device) or the
+ * destruction of a member is queued behind a launch that was not waited for.  Refused before any device call: null lists, a negative
+ * count, maxiter or check_every, n[i] <= 0, a handle named twice within either family, a workspace that is too small, a multilevel
+ * handle among `plain`.  count == 0 returns ILUPP_OK without touching the device. */
+int ilupp_hip_bicgstab_batch_device(int32_t count, ilupp_precond *const *plain, ilupp_ilucp *const *pivoted, const int64_t *n,
+                                    const double *const *d_data, const int32_t *const *d_indices, const int32_t *const *d_indptr,
+                                    const int64_t *nnz, const double *d_b, const double *d_x0, double *d_x, const int64_t *offsets,
+                                    double *d_work, int64_t work_doubles, int32_t maxiter, double rtol, int32_t check_every,
+                                    int64_t *d_iterations, int32_t *d_flags, double *d_rr, double *d_init, int sync, int32_t *route);
+/* the largest n that takes route 0 in ilupp_hip_bicgstab_batch_device on the current device (ILUPP_BATCH_APPLY_MAX_N applied);
+ * negative: an error code */
+int64_t ilupp_hip_bicgstab_batch_max_n(void);
 /* The numeric re-factorisation of MANY small ILU(0) objects at once (same patterns, new values): ONE launch, one workgroup per member,
  * the member's rows side by side inside it (k_ilu0_refactor_batch, ilu0_batch.hip).  members: `count` distinct ILU(0) objects; d_data /
  * d_indices / d_indptr: host arrays of `count` DEVICE pointers, member i's matrix in CSR form as ilupp_hip_ilu0_refactor_device takes
