@@ -942,6 +942,32 @@ def pivot_apply_batch_device(members, dptr, offsets, transpose=False, sync=True)
     return list(route)
 
 
+def _matrix_arrays(matrices):
+    """the C arrays (data, indices, indptr, nnz) of a list of (data_ptr, indices_ptr, indptr_ptr, nnz)"""
+    cnt = len(matrices)
+    D, I, P = (_VP * cnt)(), (_VP * cnt)(), (_VP * cnt)()
+    NNZ = (ctypes.c_int64 * cnt)()
+    for k, (d, i, p, nnz) in enumerate(matrices):
+        D[k], I[k], P[k], NNZ[k] = d, i, p, int(nnz)
+    return D, I, P, NNZ
+
+
+def _solve_batch(entry, handles, ns, matrices, b_ptr, x0_ptr, x_ptr, offsets, work_ptr, work_doubles, maxiter, rtol, check_every,
+                 iterations_ptr, flags_ptr, rr_ptr, last_ptr, sync):
+    """one call of a batched solve's C entry (by name): `handles` are its handle arrays, `ns` the dimensions where the entry takes them
+    (None: it reads them from the handles); returns the routes"""
+    cnt = len(matrices)
+    D, I, P, NNZ = _matrix_arrays(matrices)
+    N = () if ns is None else ((ctypes.c_int64 * cnt)(*[int(n) for n in ns]),)
+    O = (ctypes.c_int64 * cnt)(*[int(o) for o in offsets])
+    route = (ctypes.c_int32 * cnt)()
+    rc = getattr(lib(), entry)(cnt, *handles, *N, D, I, P, NNZ, b_ptr, x0_ptr or None, x_ptr, O, work_ptr, int(work_doubles), int(maxiter),
+                               float(rtol), int(check_every), iterations_ptr, flags_ptr, rr_ptr, last_ptr, 1 if sync else 0, route)
+    if rc:
+        _raise(rc)
+    return list(route)
+
+
 def pivot_bicgstab_batch_device(members, matrices, b_ptr, x0_ptr, x_ptr, offsets, work_ptr, work_doubles, maxiter, rtol, check_every,
                                 iterations_ptr, flags_ptr, rr_ptr, init_ptr, sync=True):
     """left-preconditioned BiCGstab for many small systems in ONE launch (ilupp_hip_pivot_bicgstab_batch_device): `matrices` is a list of
@@ -953,19 +979,8 @@ def pivot_bicgstab_batch_device(members, matrices, b_ptr, x0_ptr, x_ptr, offsets
         raise ValueError("%d preconditioners but %d matrices and %d offsets" % (cnt, len(matrices), len(offsets)))
     if cnt == 0:
         return []
-    H = _member_handles(members)
-    D, I, P = (_VP * cnt)(), (_VP * cnt)(), (_VP * cnt)()
-    NNZ = (ctypes.c_int64 * cnt)()
-    for k, (d, i, p, nnz) in enumerate(matrices):
-        D[k], I[k], P[k], NNZ[k] = d, i, p, int(nnz)
-    O = (ctypes.c_int64 * cnt)(*[int(o) for o in offsets])
-    route = (ctypes.c_int32 * cnt)()
-    rc = lib().ilupp_hip_pivot_bicgstab_batch_device(cnt, H, D, I, P, NNZ, b_ptr, x0_ptr or None, x_ptr, O, work_ptr, int(work_doubles),
-                                                     int(maxiter), float(rtol), int(check_every), iterations_ptr, flags_ptr, rr_ptr,
-                                                     init_ptr, 1 if sync else 0, route)
-    if rc:
-        _raise(rc)
-    return list(route)
+    return _solve_batch("ilupp_hip_pivot_bicgstab_batch_device", (_member_handles(members),), None, matrices, b_ptr, x0_ptr, x_ptr, offsets,
+                        work_ptr, work_doubles, maxiter, rtol, check_every, iterations_ptr, flags_ptr, rr_ptr, init_ptr, sync)
 
 
 def pivot_apply_batch_max_n():
@@ -1019,20 +1034,8 @@ def cg_batch_device(members, ns, matrices, b_ptr, x0_ptr, x_ptr, offsets, work_p
         raise ValueError("%d preconditioners but %d dimensions, %d matrices and %d offsets" % (cnt, len(ns), len(matrices), len(offsets)))
     if cnt == 0:
         return []
-    H = _plain_handles(members, none_ok=True)
-    D, I, P = (_VP * cnt)(), (_VP * cnt)(), (_VP * cnt)()
-    NNZ = (ctypes.c_int64 * cnt)()
-    for k, (d, i, p, nnz) in enumerate(matrices):
-        D[k], I[k], P[k], NNZ[k] = d, i, p, int(nnz)
-    N = (ctypes.c_int64 * cnt)(*[int(n) for n in ns])
-    O = (ctypes.c_int64 * cnt)(*[int(o) for o in offsets])
-    route = (ctypes.c_int32 * cnt)()
-    rc = lib().ilupp_hip_cg_batch_device(cnt, H, N, D, I, P, NNZ, b_ptr, x0_ptr or None, x_ptr, O, work_ptr, int(work_doubles),
-                                         int(maxiter), float(rtol), int(check_every), iterations_ptr, flags_ptr, rr_ptr, bnorm_ptr,
-                                         1 if sync else 0, route)
-    if rc:
-        _raise(rc)
-    return list(route)
+    return _solve_batch("ilupp_hip_cg_batch_device", (_plain_handles(members, none_ok=True),), ns, matrices, b_ptr, x0_ptr, x_ptr, offsets,
+                        work_ptr, work_doubles, maxiter, rtol, check_every, iterations_ptr, flags_ptr, rr_ptr, bnorm_ptr, sync)
 
 
 def ilu0_refactor_batch_device(members, matrices, status_ptr, sync=True):
@@ -1048,12 +1051,8 @@ def ilu0_refactor_batch_device(members, matrices, status_ptr, sync=True):
     if cnt == 0:
         return []
     H = _plain_handles(members)
-    D, I, P = (_VP * cnt)(), (_VP * cnt)(), (_VP * cnt)()
-    NNZ = (ctypes.c_int64 * cnt)()
-    for k, (d, i, p, nnz) in enumerate(matrices):
-        D[k], I[k], P[k], NNZ[k] = d, i, p, int(nnz)
     route = (ctypes.c_int32 * cnt)()
-    rc = lib().ilupp_hip_ilu0_refactor_batch_device(cnt, H, D, I, P, NNZ, status_ptr, 1 if sync else 0, route)
+    rc = lib().ilupp_hip_ilu0_refactor_batch_device(cnt, H, *_matrix_arrays(matrices), status_ptr, 1 if sync else 0, route)
     if rc:
         _raise(rc)
     return list(route)
@@ -1098,19 +1097,8 @@ def bicgstab_batch_device(members, ns, matrices, b_ptr, x0_ptr, x_ptr, offsets, 
         else:
             raise TypeError("a batched solve takes ILUCP / ILUTP / ILU0 / ILUT / ILUC / IChol0 / ICholT preconditioners or None, got %s"
                             % type(m).__name__)
-    D, I, P = (_VP * cnt)(), (_VP * cnt)(), (_VP * cnt)()
-    NNZ = (ctypes.c_int64 * cnt)()
-    for k, (d, i, p, nnz) in enumerate(matrices):
-        D[k], I[k], P[k], NNZ[k] = d, i, p, int(nnz)
-    N = (ctypes.c_int64 * cnt)(*[int(n) for n in ns])
-    O = (ctypes.c_int64 * cnt)(*[int(o) for o in offsets])
-    route = (ctypes.c_int32 * cnt)()
-    rc = lib().ilupp_hip_bicgstab_batch_device(cnt, HP, HV, N, D, I, P, NNZ, b_ptr, x0_ptr or None, x_ptr, O, work_ptr, int(work_doubles),
-                                               int(maxiter), float(rtol), int(check_every), iterations_ptr, flags_ptr, rr_ptr, init_ptr,
-                                               1 if sync else 0, route)
-    if rc:
-        _raise(rc)
-    return list(route)
+    return _solve_batch("ilupp_hip_bicgstab_batch_device", (HP, HV), ns, matrices, b_ptr, x0_ptr, x_ptr, offsets, work_ptr, work_doubles,
+                        maxiter, rtol, check_every, iterations_ptr, flags_ptr, rr_ptr, init_ptr, sync)
 
 
 def bicgstab_batch_max_n():

@@ -2984,6 +2984,42 @@ int plain_batch_args(int32_t count, ilupp_precond *const *members, bool null_ok,
     return ILUPP_OK;
 }
 
+// n up to which a member goes to a solver's launch: the cap of the apply's launch, lowered by what the dot scratch takes
+// (ILUPP_BATCH_APPLY_MAX_N lowers both)
+int64_t solve_batch_cap_n(BatchSolver solver)
+{
+    const int64_t a = batch_apply_max_n(), b = solve_batch_max_n(solver);
+    return a < b ? a : b;
+}
+
+// What the three batched solves do once their arguments are checked and their members named (count > 0): the members routed and
+// described, those of route 0 solved in ONE launch of `solver`'s kernel on the scratch's stream behind the caller's, and either waited
+// for (sync) or the caller's stream ordered behind them.  Members of routes 1 and 2 are left alone.
+int solve_batch_run(BatchSolver solver, int32_t count, const std::vector<BatchMember> &mv, const double *const *d_data,
+                    const int32_t *const *d_indices, const int32_t *const *d_indptr, const double *d_b, const double *d_x0, double *d_x,
+                    const int64_t *offsets, double *d_work, int32_t maxiter, double rtol, int32_t check_every, int64_t *d_iterations,
+                    int32_t *d_flags, double *d_rr, double *d_last, int sync, int32_t *route)
+{
+    std::lock_guard<std::mutex> lk(g_batch_mu);
+    BatchScratch &S = batch_scratch();
+    hipStream_t bs = S.stream;
+    if (!S.sys_ev) ILUPP_HIP(hipEventCreateWithFlags(&S.sys_ev, hipEventDisableTiming));
+    order_after_caller(bs, S.cev[0]);
+    const int64_t cap_n = solve_batch_cap_n(solver);
+    batch_describe(S, count, mv.data(), offsets, cap_n);
+    if (route) for (int32_t i = 0; i < count; ++i) route[i] = S.route[(size_t)i];
+    const int32_t nl = (int32_t)S.launched.size();
+    if (nl == 0) return ILUPP_OK;
+    const size_t lds = batch_stage(S, mv.data(), cap_n);
+    batch_systems(S, count, mv.data(), solve_batch_work_factor(solver), d_data, d_indices, d_indptr);
+    OR_RETURN(solve_batch_launch(solver, bs, nl, S.d_table, S.d_sys, d_b, d_x0, d_x, d_work, lds, maxiter, rtol, check_every, d_iterations,
+                                 d_flags, d_rr, d_last));
+    batch_launched(S, mv.data());
+    if (sync) return apply_batch_finish(S, count, mv.data(), false);
+    order_caller_after(bs, S.cev[1]);
+    return ILUPP_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -3025,39 +3061,20 @@ int ilupp_hip_cg_batch_device(int32_t count, ilupp_precond *const *members, cons
         if (members[i] && members[i]->n != n[i]) { set_error("matrix has wrong size for preconditioner!"); return ILUPP_ERR_WRONG_SIZE; }
         total += n[i];
     }
-    const int64_t wf = cg_batch_work_factor();
+    const int64_t wf = solve_batch_work_factor(BATCH_CG);
     if (work_doubles < wf * total) { set_error("workspace too small: " + std::to_string(wf) + " doubles per unknown of the batch"); return ILUPP_ERR_INVALID; }
     if (count == 0) return ILUPP_OK;
-    std::lock_guard<std::mutex> lk(g_batch_mu);
-    BatchScratch &S = batch_scratch();
-    hipStream_t bs = S.stream;
-    if (!S.sys_ev) ILUPP_HIP(hipEventCreateWithFlags(&S.sys_ev, hipEventDisableTiming));
-    order_after_caller(bs, S.cev[0]);
-    // the cap of the apply's launch, lowered by what the dot scratch takes (ILUPP_BATCH_APPLY_MAX_N lowers both)
-    int64_t cap_n = batch_apply_max_n();
-    if (cg_batch_max_n() < cap_n) cap_n = cg_batch_max_n();
     std::vector<BatchMember> mv((size_t)count);
     for (int32_t i = 0; i < count; ++i) { if (members[i]) mv[(size_t)i] = batch_member(members[i], 0); mv[(size_t)i].n = (int32_t)n[i]; }
-    batch_describe(S, count, mv.data(), offsets, cap_n);
-    if (route) for (int32_t i = 0; i < count; ++i) route[i] = S.route[(size_t)i];
-    const int32_t nl = (int32_t)S.launched.size();
-    if (nl == 0) return ILUPP_OK;
-    const size_t lds = batch_stage(S, mv.data(), cap_n);
-    batch_systems(S, count, mv.data(), wf, d_data, d_indices, d_indptr);
-    OR_RETURN(cg_batch_launch(bs, nl, S.d_table, S.d_sys, d_b, d_x0, d_x, d_work, lds, maxiter, rtol, check_every, d_iterations, d_flags, d_rr,
-                              d_bnorm));
-    batch_launched(S, mv.data());
-    if (sync) return apply_batch_finish(S, count, mv.data(), false);
-    order_caller_after(bs, S.cev[1]);
-    return ILUPP_OK;
+    return solve_batch_run(BATCH_CG, count, mv, d_data, d_indices, d_indptr, d_b, d_x0, d_x, offsets, d_work, maxiter, rtol, check_every,
+                           d_iterations, d_flags, d_rr, d_bnorm, sync, route);
     API_CATCH
 }
 
 int64_t ilupp_hip_cg_batch_max_n(void)
 {
     API_TRY
-    const int64_t a = batch_apply_max_n(), b = cg_batch_max_n();
-    return a < b ? a : b;
+    return solve_batch_cap_n(BATCH_CG);
     API_CATCH
 }
 
@@ -3147,29 +3164,11 @@ int ilupp_hip_pivot_bicgstab_batch_device(int32_t count, ilupp_ilucp *const *mem
         if (!d_data[i] || !d_indices[i] || !d_indptr[i]) { set_error("null argument"); return ILUPP_ERR_INVALID; }
         total += members[i]->n;
     }
-    if (work_doubles < 7 * total) { set_error("workspace too small: 7 doubles per unknown of the batch"); return ILUPP_ERR_INVALID; }
+    const int64_t wf = solve_batch_work_factor(BATCH_BICGSTAB);
+    if (work_doubles < wf * total) { set_error("workspace too small: " + std::to_string(wf) + " doubles per unknown of the batch"); return ILUPP_ERR_INVALID; }
     if (count == 0) return ILUPP_OK;
-    std::lock_guard<std::mutex> lk(g_batch_mu);
-    BatchScratch &S = batch_scratch();
-    hipStream_t bs = S.stream;
-    if (!S.sys_ev) ILUPP_HIP(hipEventCreateWithFlags(&S.sys_ev, hipEventDisableTiming));
-    order_after_caller(bs, S.cev[0]);
-    // the cap of the apply's launch, lowered by what the dot scratch takes (ILUPP_BATCH_APPLY_MAX_N lowers both)
-    int64_t cap_n = batch_apply_max_n();
-    if (pivot_bicgstab_batch_max_n() < cap_n) cap_n = pivot_bicgstab_batch_max_n();
-    const std::vector<BatchMember> mv = batch_members(count, members, 0);
-    batch_describe(S, count, mv.data(), offsets, cap_n);
-    if (route) for (int32_t i = 0; i < count; ++i) route[i] = S.route[(size_t)i];
-    const int32_t nl = (int32_t)S.launched.size();
-    if (nl == 0) return ILUPP_OK;
-    const size_t lds = batch_stage(S, mv.data(), cap_n);
-    batch_systems(S, count, mv.data(), 7, d_data, d_indices, d_indptr);
-    OR_RETURN(pivot_bicgstab_batch_launch(bs, nl, S.d_table, S.d_sys, d_b, d_x0, d_x, d_work, lds, maxiter, rtol, check_every, d_iterations,
-                                          d_flags, d_rr, d_init));
-    batch_launched(S, mv.data());
-    if (sync) return apply_batch_finish(S, count, mv.data(), false);
-    order_caller_after(bs, S.cev[1]);
-    return ILUPP_OK;
+    return solve_batch_run(BATCH_BICGSTAB, count, batch_members(count, members, 0), d_data, d_indices, d_indptr, d_b, d_x0, d_x, offsets,
+                           d_work, maxiter, rtol, check_every, d_iterations, d_flags, d_rr, d_init, sync, route);
     API_CATCH
 }
 
@@ -3203,42 +3202,24 @@ int ilupp_hip_bicgstab_batch_device(int32_t count, ilupp_precond *const *plain, 
         std::sort(seen->begin(), seen->end());
         if (std::adjacent_find(seen->begin(), seen->end()) != seen->end()) { set_error("a preconditioner appears twice in the batch"); return ILUPP_ERR_INVALID; }
     }
-    if (work_doubles < 7 * total) { set_error("workspace too small: 7 doubles per unknown of the batch"); return ILUPP_ERR_INVALID; }
+    const int64_t wf = solve_batch_work_factor(BATCH_BICGSTAB);
+    if (work_doubles < wf * total) { set_error("workspace too small: " + std::to_string(wf) + " doubles per unknown of the batch"); return ILUPP_ERR_INVALID; }
     if (count == 0) return ILUPP_OK;
-    std::lock_guard<std::mutex> lk(g_batch_mu);
-    BatchScratch &S = batch_scratch();
-    hipStream_t bs = S.stream;
-    if (!S.sys_ev) ILUPP_HIP(hipEventCreateWithFlags(&S.sys_ev, hipEventDisableTiming));
-    order_after_caller(bs, S.cev[0]);
-    // the cap of the apply's launch, lowered by what the dot scratch takes (ILUPP_BATCH_APPLY_MAX_N lowers both)
-    int64_t cap_n = batch_apply_max_n();
-    if (bicgstab_batch_max_n() < cap_n) cap_n = bicgstab_batch_max_n();
     std::vector<BatchMember> mv((size_t)count);
     for (int32_t i = 0; i < count; ++i) {
         if (pivoted && pivoted[i]) mv[(size_t)i] = batch_member(pivoted[i], 0);
         else if (plain && plain[i]) mv[(size_t)i] = batch_member(plain[i], 0);
         mv[(size_t)i].n = (int32_t)n[i];
     }
-    batch_describe(S, count, mv.data(), offsets, cap_n);
-    if (route) for (int32_t i = 0; i < count; ++i) route[i] = S.route[(size_t)i];
-    const int32_t nl = (int32_t)S.launched.size();
-    if (nl == 0) return ILUPP_OK;
-    const size_t lds = batch_stage(S, mv.data(), cap_n);
-    batch_systems(S, count, mv.data(), 7, d_data, d_indices, d_indptr);
-    OR_RETURN(bicgstab_batch_launch(bs, nl, S.d_table, S.d_sys, d_b, d_x0, d_x, d_work, lds, maxiter, rtol, check_every, d_iterations, d_flags,
-                                    d_rr, d_init));
-    batch_launched(S, mv.data());
-    if (sync) return apply_batch_finish(S, count, mv.data(), false);
-    order_caller_after(bs, S.cev[1]);
-    return ILUPP_OK;
+    return solve_batch_run(BATCH_BICGSTAB, count, mv, d_data, d_indices, d_indptr, d_b, d_x0, d_x, offsets, d_work, maxiter, rtol,
+                           check_every, d_iterations, d_flags, d_rr, d_init, sync, route);
     API_CATCH
 }
 
 int64_t ilupp_hip_bicgstab_batch_max_n(void)
 {
     API_TRY
-    const int64_t a = batch_apply_max_n(), b = bicgstab_batch_max_n();
-    return a < b ? a : b;
+    return solve_batch_cap_n(BATCH_BICGSTAB);
     API_CATCH
 }
 

@@ -562,34 +562,47 @@ struct PivotApplyDesc {
     double *tmp;
     int32_t *err;
 };
+// Bytes of dynamic LDS one workgroup of Kernel may take on the current device: what the device gives a workgroup minus the kernel's
+// static words; the kernel is told once per device (and host thread) that it may ask for that much.  One-workgroup-per-member kernels:
+// k_pivot_apply_batch, k_cg_batch, k_bicgstab_batch, k_ilu0_refactor_batch.
+template <auto Kernel>
+size_t kernel_lds_cap()
+{
+    static thread_local int cap_dev = -1;
+    static thread_local size_t cap = 0;
+    int dev = 0;
+    ILUPP_HIP(hipGetDevice(&dev));
+    if (cap_dev != dev) {
+        int max_lds = 0;
+        ILUPP_HIP(hipDeviceGetAttribute(&max_lds, hipDeviceAttributeMaxSharedMemoryPerBlock, dev));
+        hipFuncAttributes fa;
+        ILUPP_HIP(hipFuncGetAttributes(&fa, reinterpret_cast<const void *>(Kernel)));
+        const size_t room = (size_t)max_lds > fa.sharedSizeBytes ? (size_t)max_lds - fa.sharedSizeBytes : 0;
+        ILUPP_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(Kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)room));
+        cap = room;
+        cap_dev = dev;
+    }
+    return cap;
+}
 size_t pivot_apply_batch_lds_cap();      // bytes of dynamic LDS a workgroup of the kernel may take on the current device: n <= cap / 8
 int pivot_apply_batch_launch(hipStream_t st, int32_t count, const PivotApplyDesc *d_table, double *d_x, size_t lds_bytes);
-// the same file: the whole left-preconditioned BiCGstab solve of many small systems in one launch, one workgroup per member
-// (k_pivot_bicgstab_batch).  Beside a member's PivotApplyDesc (xoff: its slice of the packed b / x0 / x; tmp; err): its CSR matrix, where
-// its seven vectors of n start in the workspace, and which words of the per-member outputs are its own.
+// the same file: the whole preconditioned Krylov solve of many small systems in one launch, one workgroup per member: left-preconditioned
+// BiCGstab (k_bicgstab_batch) or CG (k_cg_batch).  Beside a member's PivotApplyDesc (xoff: its slice of the packed b / x0 / x; tmp; err;
+// perm != nullptr a pivoting member, perm == nullptr a non-pivoting one with its two CSR triangles from apply_plan / sweep_parts,
+// ptr1 == nullptr a member without a preconditioner): its CSR matrix, where its solve_batch_work_factor() vectors of n start in the
+// workspace, and which words of the per-member outputs are its own.
 struct PivotSolveDesc {
     const double *aval; const int32_t *aidx, *aptr;
     int64_t woff;
     int32_t member, pad;
 };
-int64_t pivot_bicgstab_batch_max_n();    // the largest n of a member of that launch on the current device (LDS: dot scratch + 8 n bytes)
-int pivot_bicgstab_batch_launch(hipStream_t st, int32_t count, const PivotApplyDesc *d_table, const PivotSolveDesc *d_systems, const double *d_b,
-                                const double *d_x0, double *d_x, double *d_work, size_t sweep_bytes, int32_t maxiter, double rtol,
-                                int32_t check_every, int64_t *d_iterations, int32_t *d_flags, double *d_rr, double *d_init);
-// the same file: the whole preconditioned CG solve of many small systems in one launch (k_cg_batch), on the same two tables.  A
-// descriptor with perm == nullptr is a non-pivoting member (its two CSR triangles from apply_plan / sweep_parts), one with ptr1 == nullptr
-// a member without a preconditioner.  woff: where the member's cg_batch_work_factor() vectors of n start in the workspace.
-int64_t cg_batch_max_n();                // the largest n of a member of that launch on the current device (LDS: dot scratch + 8 n bytes)
-int cg_batch_work_factor();              // doubles of workspace per unknown of the batch: 5 (x, r, z, p, Ap)
-int cg_batch_launch(hipStream_t st, int32_t count, const PivotApplyDesc *d_table, const PivotSolveDesc *d_systems, const double *d_b,
-                    const double *d_x0, double *d_x, double *d_work, size_t sweep_bytes, int32_t maxiter, double rtol, int32_t check_every,
-                    int64_t *d_iterations, int32_t *d_flags, double *d_rr, double *d_bnorm);
-// the same file: left-preconditioned BiCGstab with members of every batched class in one launch (k_bicgstab_batch), on the same two
-// tables: perm != nullptr a pivoting member, perm == nullptr a non-pivoting one, ptr1 == nullptr none; seven vectors of n from woff on.
-int64_t bicgstab_batch_max_n();          // the largest n of a member of that launch on the current device (LDS: dot scratch + 8 n bytes)
-int bicgstab_batch_launch(hipStream_t st, int32_t count, const PivotApplyDesc *d_table, const PivotSolveDesc *d_systems, const double *d_b,
-                          const double *d_x0, double *d_x, double *d_work, size_t sweep_bytes, int32_t maxiter, double rtol,
-                          int32_t check_every, int64_t *d_iterations, int32_t *d_flags, double *d_rr, double *d_init);
+enum BatchSolver { BATCH_CG = 0, BATCH_BICGSTAB = 1 };
+int64_t solve_batch_max_n(BatchSolver s);        // the largest n of a member of that launch on the current device (LDS: dot scratch + 8 n bytes)
+int solve_batch_work_factor(BatchSolver s);      // doubles of workspace per unknown of the batch: CG 5 (x, r, z, p, Ap), BiCGstab 7 (y, r, r0*, p, s, Ap, As)
+// d_last: the per-member word behind rr -- CG's ||b||, BiCGstab's ||r_0||
+int solve_batch_launch(BatchSolver s, hipStream_t st, int32_t count, const PivotApplyDesc *d_table, const PivotSolveDesc *d_systems,
+                       const double *d_b, const double *d_x0, double *d_x, double *d_work, size_t sweep_bytes, int32_t maxiter, double rtol,
+                       int32_t check_every, int64_t *d_iterations, int32_t *d_flags, double *d_rr, double *d_last);
 
 // ilu0_batch.hip: the numeric ILU(0) re-factorisation of many small objects in one launch, one workgroup per member
 // (k_ilu0_refactor_batch).  One member: the matrix with the new values (device CSR arrays), the two triangles whose values are rewritten

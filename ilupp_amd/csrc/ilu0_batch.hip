@@ -213,25 +213,8 @@ k_ilu0_refactor_batch(const RefactorDesc *__restrict__ table, int32_t *__restric
     if (tid == 0) status[d.member] = s_fail != 0 ? 2 : 0;
 }
 
-// bytes of dynamic LDS one workgroup of k_ilu0_refactor_batch may take on the current device (as pivot_apply_batch_lds_cap)
-size_t ilu0_refactor_batch_lds_cap()
-{
-    static thread_local int cap_dev = -1;
-    static thread_local size_t cap = 0;
-    int dev = 0;
-    ILUPP_HIP(hipGetDevice(&dev));
-    if (cap_dev != dev) {
-        int max_lds = 0;
-        ILUPP_HIP(hipDeviceGetAttribute(&max_lds, hipDeviceAttributeMaxSharedMemoryPerBlock, dev));
-        hipFuncAttributes fa;
-        ILUPP_HIP(hipFuncGetAttributes(&fa, reinterpret_cast<const void *>(&k_ilu0_refactor_batch)));
-        const size_t room = (size_t)max_lds > fa.sharedSizeBytes ? (size_t)max_lds - fa.sharedSizeBytes : 0;
-        ILUPP_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_ilu0_refactor_batch), hipFuncAttributeMaxDynamicSharedMemorySize, (int)room));
-        cap = room;
-        cap_dev = dev;
-    }
-    return cap;
-}
+// bytes of dynamic LDS one workgroup of k_ilu0_refactor_batch may take on the current device
+static size_t ilu0_refactor_batch_lds_cap() { return kernel_lds_cap<k_ilu0_refactor_batch>(); }
 
 // the largest n of a member of the launch: its flags and working rows of kRfMinRow entries fit (a member of that n with longer rows does not)
 static constexpr int kRfMinRow = 8;

@@ -22,13 +22,13 @@
 // the barrier makes them visible to the workgroup (one CU, one L1), the ONE LDS array is filled with sentinels again and the second sweep
 // reads its right-hand sides from `tmp`.
 //
-// Second kernel, further down: k_pivot_bicgstab_batch, the whole left-preconditioned BiCGstab SOLVE of many small systems in one launch,
-// one workgroup per system, with this apply (pivot_apply_member) inside its loop.
-//
 // The non-pivoting classes (ILU0, ILUT, ILUC, IChol0, ICholT) take the same launch: a descriptor with perm == nullptr is an apply without a
-// permutation, its two triangles those of apply_plan / sweep_parts (api.hip: batch_describe).  Third kernel, at the end: k_cg_batch, the
-// whole preconditioned CG solve of many small symmetric positive definite systems in one launch, each with such a member or none.
-// Fourth kernel: k_bicgstab_batch, the BiCGstab solve for members of every class above, pivoting or not, or none, mixed in one launch.
+// permutation, its two triangles those of apply_plan / sweep_parts (api.hip: batch_describe).
+//
+// Two more kernels further down, each one workgroup per system with this apply (apply_member) inside its loop: k_bicgstab_batch, the whole
+// left-preconditioned BiCGstab SOLVE of many small systems in one launch, and k_cg_batch, the whole preconditioned CG solve of many small
+// symmetric positive definite systems.  Both take members of every class above, pivoting or not, or without a preconditioner, mixed in
+// one launch.
 #include "common.h"
 
 namespace ilupp {
@@ -136,33 +136,19 @@ __device__ __forceinline__ void batch_sweep(const int kind, const int n, const i
     __syncthreads();
 }
 
-// The apply of one member by its workgroup, in place on x: `arr` holds lds_bytes of LDS for the sweeps' unknowns.  *s_fail != 0 afterwards:
-// a sweep gave up (a member that gives up in its first sweep never starts the second and leaves x as it was).
-__device__ __forceinline__ void pivot_apply_member(const PivotApplyDesc &d, double *x, unsigned long long *arr, const unsigned lds_bytes,
-                                                   unsigned *s_progress, int *s_fail)
+// The apply of one member by its workgroup, dst = M^-1 src; in place when dst == src (see the file's header), else src is left as it is.
+// `arr` holds lds_bytes of LDS for the sweeps' unknowns.  *s_fail != 0 afterwards: a sweep gave up (a member that gives up in its first
+// sweep never starts the second and leaves dst as it was).
+__device__ __forceinline__ void apply_member(const PivotApplyDesc &d, const double *src, double *dst, unsigned long long *arr,
+                                             const unsigned lds_bytes, unsigned *s_progress, int *s_fail)
 {
     const int n = d.n;
     const bool two = (size_t)16 * (size_t)n <= (size_t)lds_bytes;
-    // first sweep: right-hand sides from the member's vector (through perm when the gather comes first)
-    batch_sweep(d.kind1, n, d.ptr1, d.idx1, d.val1, arr, nullptr, x, d.plain_first ? nullptr : d.perm, two ? nullptr : d.tmp, nullptr,
-                s_progress, s_fail);
-    if (*s_fail == 0) {
-        // second sweep: right-hand sides = the first one's unknowns; its store is the member's vector (through perm when the plain solve came first)
-        batch_sweep(d.kind2, n, d.ptr2, d.idx2, d.val2, two ? arr + n : arr, two ? arr : nullptr, d.tmp, nullptr, x,
-                    d.plain_first ? d.perm : nullptr, s_progress, s_fail);
-    }
-}
-
-// The same with the source apart from the destination, dst = M^-1 src with src left as it is (the CG kernel's z = M^-1 r; kept apart from
-// the in-place form above, whose instruction stream the two older kernels keep): the first sweep reads src, the second stores to dst.
-__device__ __forceinline__ void apply_member_to(const PivotApplyDesc &d, const double *src, double *dst, unsigned long long *arr,
-                                                const unsigned lds_bytes, unsigned *s_progress, int *s_fail)
-{
-    const int n = d.n;
-    const bool two = (size_t)16 * (size_t)n <= (size_t)lds_bytes;
+    // first sweep: right-hand sides from src (through perm when the gather comes first)
     batch_sweep(d.kind1, n, d.ptr1, d.idx1, d.val1, arr, nullptr, src, d.plain_first ? nullptr : d.perm, two ? nullptr : d.tmp, nullptr,
                 s_progress, s_fail);
     if (*s_fail == 0) {
+        // second sweep: right-hand sides = the first one's unknowns; its store is dst (through perm when the plain solve came first)
         batch_sweep(d.kind2, n, d.ptr2, d.idx2, d.val2, two ? arr + n : arr, two ? arr : nullptr, d.tmp, nullptr, dst,
                     d.plain_first ? d.perm : nullptr, s_progress, s_fail);
     }
@@ -177,30 +163,13 @@ k_pivot_apply_batch(const PivotApplyDesc *__restrict__ table, double *xbase, con
     const PivotApplyDesc d = table[blockIdx.x];
     if (threadIdx.x == 0) { s_progress = 0; s_fail = 0; }
     // (the first sweep's fill-and-barrier publishes the two words before any wave looks at them)
-    pivot_apply_member(d, xbase + d.xoff, lds, lds_bytes, &s_progress, &s_fail);
+    double *x = xbase + d.xoff;
+    apply_member(d, x, x, lds, lds_bytes, &s_progress, &s_fail);
     if (threadIdx.x == 0) *d.err = s_fail;          // (one writer per member: its own word, whatever the other members do)
 }
 
-// bytes of dynamic LDS one workgroup of k_pivot_apply_batch may take on the current device: what the device gives a workgroup minus the
-// kernel's static words; the kernel is told once per device that it may ask for that much
-size_t pivot_apply_batch_lds_cap()
-{
-    static thread_local int cap_dev = -1;
-    static thread_local size_t cap = 0;
-    int dev = 0;
-    ILUPP_HIP(hipGetDevice(&dev));
-    if (cap_dev != dev) {
-        int max_lds = 0;
-        ILUPP_HIP(hipDeviceGetAttribute(&max_lds, hipDeviceAttributeMaxSharedMemoryPerBlock, dev));
-        hipFuncAttributes fa;
-        ILUPP_HIP(hipFuncGetAttributes(&fa, reinterpret_cast<const void *>(&k_pivot_apply_batch)));
-        const size_t room = (size_t)max_lds > fa.sharedSizeBytes ? (size_t)max_lds - fa.sharedSizeBytes : 0;
-        ILUPP_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_pivot_apply_batch), hipFuncAttributeMaxDynamicSharedMemorySize, (int)room));
-        cap = room;
-        cap_dev = dev;
-    }
-    return cap;
-}
+// bytes of dynamic LDS one workgroup of k_pivot_apply_batch may take on the current device
+size_t pivot_apply_batch_lds_cap() { return kernel_lds_cap<k_pivot_apply_batch>(); }
 
 // `count` members, one workgroup each; member i's vector is d_x + table[i].xoff; lds_bytes for every workgroup (<= the cap)
 int pivot_apply_batch_launch(hipStream_t st, int32_t count, const PivotApplyDesc *d_table, double *d_x, size_t lds_bytes)
@@ -214,16 +183,22 @@ int pivot_apply_batch_launch(hipStream_t st, int32_t count, const PivotApplyDesc
 
 
 // ---- the whole left-preconditioned BiCGstab solve of MANY small systems in ONE launch: one workgroup per member --------------------
-// k_pivot_bicgstab_batch runs _bicgstab_block of ilupp_amd/device.py with k = 1, statement for statement, for its member: the SpMV of
+// k_bicgstab_batch runs _bicgstab_block of ilupp_amd/device.py with k = 1, statement for statement, for its member: the SpMV of
 // k_spmv_rows (one sum per row in stored order from 0.0), the apply above, the dot products in the shape of ilupp_hip_block_dot_device for
-// this n, the updates of k_block_update<1>, IEEE division and the correctly rounded square root -- so every member has the bits of the
-// same solve done alone with those launches.  The seven vectors y, r, r0*, p, s, Ap, As lie in the member's part of the workspace; one CU
-// touches them (its L1 and L2 keep them), and every hand-over between two phases of the workgroup is a __syncthreads().
+// this n, the updates of k_block_update<1>, IEEE division and the correctly rounded square root -- so every member has the bits of
+// bicgstab(A_k, b_k[:, None], M_k), the same solve done alone with those launches.  The member's preconditioner is left open: a
+// descriptor with perm != nullptr is an ILUCP / ILUTP member; perm == nullptr a non-pivoting one (ILU0, ILUT, ILUC, IChol0, ICholT: the
+// two triangles of apply_plan / sweep_parts, tmp from the scratch's block), which apply_member applies without a permutation;
+// ptr1 == nullptr a member without a preconditioner, prec_ of _bicgstab_block being the identity: the apply is skipped (the branch is
+// uniform over the workgroup), r = r0*, Ap = A p, As = A s.  The seven vectors y, r, r0*, p, s, Ap, As lie in the member's part of the
+// workspace; one CU touches them (its L1 and L2 keep them), and every hand-over between two phases of the workgroup is a
+// __syncthreads().
 //
 // Dynamic LDS: [2][2][kDotMaxNb] doubles of dot scratch (the chunks' partial sums of up to two dots at once, two buffers used in
 // turn), then the sweeps' one or two arrays of n.
 static constexpr int kDotMaxNb = 128;                          // chunks of a dot: n <= 256 kDotMaxNb
 static constexpr int kDotScratch = 2 * 2 * kDotMaxNb;          // doubles
+static constexpr int kBicgstabBatchVectors = 7;
 
 // the tree over the lower 64 of 256 values a wave holds as v[l] = (t[l] + t[l + 128]) + (t[l + 64] + t[l + 192]): strides 32 .. 1,
 // lane l < s takes v[l] + v[l + s] as sh[w] = sh[w] + sh[w + s] does; lane 0 holds the sum
@@ -304,10 +279,33 @@ __device__ __forceinline__ void wg_spmv(const int n, const int32_t *__restrict__
 
 __device__ __forceinline__ bool scalar_ok(const double v) { return v != 0.0 && isfinite(v); }      // what a recurrence may divide by
 
+// The way out of a solver kernel: r.r at the exit (unless the loop's last check has just taken it) and the iterate copied to the member's
+// slice of the output -- a member whose sweep gave up leaves both as they were -- then the member's own words.  `last`: ||r_0|| of the
+// preconditioned residuals (BiCGstab) / ||b|| (CG).
+__device__ __forceinline__ void solve_member_exit(const PivotApplyDesc &d, const PivotSolveDesc &e, const int n, const int nb, const int chunk,
+                                                  const double *r, const double *xw, double *x, double *part, const bool failed,
+                                                  const bool active, const bool converged, const bool zero, const bool have_rr, double rr,
+                                                  const long long iters, const double last, long long *iterations, int32_t *flags,
+                                                  double *rr_out, double *last_out)
+{
+    const int tid = threadIdx.x;
+    if (!failed) {
+        if (!have_rr) { double v[2]; wg_dots<1>(n, nb, chunk, r, r, nullptr, nullptr, part, v); rr = v[0]; }      // (r.r at the exit)
+        for (int i = tid; i < n; i += kBatchThreads) x[i] = xw[i];
+    }
+    if (tid == 0) {                                  // (one writer per member: its own words, whatever the other members do)
+        *d.err = failed ? 1 : 0;
+        iterations[e.member] = iters;
+        flags[e.member] = (active ? 1 : 0) | (converged ? 2 : 0) | (failed ? 4 : 0) | (zero ? 8 : 0);
+        rr_out[e.member] = rr;
+        last_out[e.member] = last;
+    }
+}
+
 __global__ void __launch_bounds__(kBatchThreads)
-k_pivot_bicgstab_batch(const PivotApplyDesc *__restrict__ table, const PivotSolveDesc *__restrict__ systems, const double *bbase,
-                       const double *x0base, double *xbase, double *work, const unsigned sweep_bytes, const int maxiter, const double rtol,
-                       const int check_every, long long *iterations, int32_t *flags, double *rr_out, double *init_out)
+k_bicgstab_batch(const PivotApplyDesc *__restrict__ table, const PivotSolveDesc *__restrict__ systems, const double *bbase,
+                 const double *x0base, double *xbase, double *work, const unsigned sweep_bytes, const int maxiter, const double rtol,
+                 const int check_every, long long *iterations, int32_t *flags, double *rr_out, double *init_out)
 {
     extern __shared__ unsigned long long lds[];
     __shared__ unsigned s_progress;
@@ -318,9 +316,10 @@ k_pivot_bicgstab_batch(const PivotApplyDesc *__restrict__ table, const PivotSolv
     if (tid == 0) { s_progress = 0; s_fail = 0; }
     double *dots = reinterpret_cast<double *>(lds);
     unsigned long long *arr = lds + kDotScratch;
-    const int nb = (n + 255) / 256, chunk = (n + nb - 1) / nb;      // (n <= 256 kDotMaxNb: nb is below the dot's 1 024)
+    const int nb = (n + 255) / 256, chunk = (n + nb - 1) / nb;      // (n <= 256 kDotMaxNb)
     unsigned turn = 0;
     auto part = [&]() { return dots + (turn++ & 1u) * (2 * kDotMaxNb); };
+    const bool has_m = d.ptr1 != nullptr;
     double *y = work + e.woff, *r = y + n, *r0 = r + n, *p = r0 + n, *s = p + n, *Ap = s + n, *As = Ap + n;
     const double *b = bbase + d.xoff;
     const double *x0 = x0base ? x0base + d.xoff : nullptr;
@@ -333,7 +332,7 @@ k_pivot_bicgstab_batch(const PivotApplyDesc *__restrict__ table, const PivotSolv
     //   half 2:          As = M^-1 (A s); omega = (As.s) / (As.As); y += alpha p; y += omega s; r = s - omega As;
     //                    beta = ((r.r0*) / rho) * (alpha / omega); p = p - omega Ap; p = beta p + r; the convergence test
     for (int i = tid; i < n; i += kBatchThreads) y[i] = x0 ? x0[i] : 0.0;
-    __syncthreads();
+    __syncthreads();                                 // (also publishes s_progress and s_fail: a member without M meets no sweep's barrier)
     bool failed = false, zero = false, active = false, converged = false, have_rr = false;
     double init = 0.0, rho = 0.0, alpha = 0.0, rr = 0.0, v2[2];
     long long iters = 0;
@@ -348,8 +347,10 @@ k_pivot_bicgstab_batch(const PivotApplyDesc *__restrict__ table, const PivotSolv
             else { for (int i = tid; i < n; i += kBatchThreads) r[i] = b[i]; }
             __syncthreads();
         }
-        pivot_apply_member(d, vec, arr, sweep_bytes, &s_progress, &s_fail);
-        if (s_fail != 0) { failed = true; active = false; break; }
+        if (has_m) {
+            apply_member(d, vec, vec, arr, sweep_bytes, &s_progress, &s_fail);
+            if (s_fail != 0) { failed = true; active = false; break; }
+        }
         if (half == 0) {
             for (int i = tid; i < n; i += kBatchThreads) { const double v = r[i]; r0[i] = v; p[i] = v; }
             __syncthreads();
@@ -403,65 +404,14 @@ k_pivot_bicgstab_batch(const PivotApplyDesc *__restrict__ table, const PivotSolv
             have_rr = false;
         }
     }
-    if (!failed) {
-        if (!have_rr) { wg_dots<1>(n, nb, chunk, r, r, nullptr, nullptr, part(), v2); rr = v2[0]; }      // (r.r at the exit)
-        for (int i = tid; i < n; i += kBatchThreads) x[i] = y[i];
-    }
-    if (tid == 0) {                                  // (one writer per member: its own words, whatever the other members do)
-        *d.err = failed ? 1 : 0;
-        iterations[e.member] = iters;
-        flags[e.member] = (active ? 1 : 0) | (converged ? 2 : 0) | (failed ? 4 : 0) | (zero ? 8 : 0);
-        rr_out[e.member] = rr;
-        init_out[e.member] = init;
-    }
-}
-
-// bytes of dynamic LDS a workgroup of k_pivot_bicgstab_batch may take on the current device (as pivot_apply_batch_lds_cap)
-size_t pivot_bicgstab_batch_lds_cap()
-{
-    static thread_local int cap_dev = -1;
-    static thread_local size_t cap = 0;
-    int dev = 0;
-    ILUPP_HIP(hipGetDevice(&dev));
-    if (cap_dev != dev) {
-        int max_lds = 0;
-        ILUPP_HIP(hipDeviceGetAttribute(&max_lds, hipDeviceAttributeMaxSharedMemoryPerBlock, dev));
-        hipFuncAttributes fa;
-        ILUPP_HIP(hipFuncGetAttributes(&fa, reinterpret_cast<const void *>(&k_pivot_bicgstab_batch)));
-        const size_t room = (size_t)max_lds > fa.sharedSizeBytes ? (size_t)max_lds - fa.sharedSizeBytes : 0;
-        ILUPP_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_pivot_bicgstab_batch), hipFuncAttributeMaxDynamicSharedMemorySize, (int)room));
-        cap = room;
-        cap_dev = dev;
-    }
-    return cap;
-}
-
-// the largest n of a member of the solve's launch: the dot scratch and 8 n bytes for the sweeps fit, and the dot has at most kDotMaxNb chunks
-int64_t pivot_bicgstab_batch_max_n()
-{
-    const size_t cap = pivot_bicgstab_batch_lds_cap(), scratch = sizeof(double) * (size_t)kDotScratch;
-    const int64_t by_lds = cap > scratch ? (int64_t)((cap - scratch) / 8) : 0;
-    return by_lds < 256 * kDotMaxNb ? by_lds : 256 * kDotMaxNb;
-}
-
-// `count` members, one workgroup each; sweep_bytes of LDS for the sweeps of every workgroup (the dot scratch comes on top)
-int pivot_bicgstab_batch_launch(hipStream_t st, int32_t count, const PivotApplyDesc *d_table, const PivotSolveDesc *d_systems, const double *d_b,
-                                const double *d_x0, double *d_x, double *d_work, size_t sweep_bytes, int32_t maxiter, double rtol,
-                                int32_t check_every, int64_t *d_iterations, int32_t *d_flags, double *d_rr, double *d_init)
-{
-    if (count <= 0) return ILUPP_OK;
-    const size_t lds_bytes = sizeof(double) * (size_t)kDotScratch + sweep_bytes;
-    if (lds_bytes > pivot_bicgstab_batch_lds_cap()) return ILUPP_ERR_UNSUPPORTED;
-    hipLaunchKernelGGL(k_pivot_bicgstab_batch, dim3((unsigned)count), dim3(kBatchThreads), lds_bytes, st, d_table, d_systems, d_b, d_x0, d_x, d_work,
-                       (unsigned)sweep_bytes, (int)maxiter, rtol, (int)check_every, reinterpret_cast<long long *>(d_iterations), d_flags, d_rr, d_init);
-    ILUPP_HIP(hipGetLastError());
-    return ILUPP_OK;
+    solve_member_exit(d, e, n, nb, chunk, r, y, x, part(), failed, active, converged, zero, have_rr, rr, iters, init, iterations, flags, rr_out,
+                      init_out);
 }
 
 
 // ---- the whole preconditioned CG solve of MANY small symmetric positive definite systems in ONE launch: one workgroup per member ----
 // k_cg_batch runs _cg_block of ilupp_amd/device.py with k = 1, statement for statement, for its member, out of the same pieces as the
-// kernel above: wg_spmv, apply_member_to (z = M^-1 r, r left as it is), wg_dots, the updates of k_block_update<0>, IEEE division and the
+// kernel above: wg_spmv, apply_member (z = M^-1 r, r left as it is), wg_dots, the updates of k_block_update<0>, IEEE division and the
 // correctly rounded square root -- so every member has the bits of cg(A_k, b_k[:, None], M_k).  The descriptors are those of the
 // batched apply with perm == nullptr (IChol0, ICholT, ILU0, ILUT, ILUC); ptr1 == nullptr: a member without a preconditioner, z = r.
 // The FIVE vectors x, r, z, p, Ap lie in the member's part of the workspace (x too: a member whose sweep gives up leaves its slice of
@@ -509,7 +459,7 @@ k_cg_batch(const PivotApplyDesc *__restrict__ table, const PivotSolveDesc *__res
     for (int it = 0;;) {
         // loop top: the one place where the apply stands
         if (has_m) {
-            apply_member_to(d, r, z, arr, sweep_bytes, &s_progress, &s_fail);
+            apply_member(d, r, z, arr, sweep_bytes, &s_progress, &s_fail);
             if (s_fail != 0) { failed = true; active = false; break; }
         }
         double rz_new;
@@ -560,226 +510,35 @@ k_cg_batch(const PivotApplyDesc *__restrict__ table, const PivotSolveDesc *__res
         }
         if (it >= maxiter) break;
     }
-    if (!failed) {
-        if (!have_rr) { wg_dots<1>(n, nb, chunk, r, r, nullptr, nullptr, part(), v2); rr = v2[0]; }      // (r.r at the exit)
-        for (int i = tid; i < n; i += kBatchThreads) x[i] = xw[i];
-    }
-    if (tid == 0) {                                  // (one writer per member: its own words, whatever the other members do)
-        *d.err = failed ? 1 : 0;
-        iterations[e.member] = iters;
-        flags[e.member] = (active ? 1 : 0) | (converged ? 2 : 0) | (failed ? 4 : 0) | (zero ? 8 : 0);
-        rr_out[e.member] = rr;
-        bnorm_out[e.member] = bnorm;
-    }
+    solve_member_exit(d, e, n, nb, chunk, r, xw, x, part(), failed, active, converged, zero, have_rr, rr, iters, bnorm, iterations, flags, rr_out,
+                      bnorm_out);
 }
 
-// bytes of dynamic LDS a workgroup of k_cg_batch may take on the current device (as pivot_apply_batch_lds_cap)
-size_t cg_batch_lds_cap()
-{
-    static thread_local int cap_dev = -1;
-    static thread_local size_t cap = 0;
-    int dev = 0;
-    ILUPP_HIP(hipGetDevice(&dev));
-    if (cap_dev != dev) {
-        int max_lds = 0;
-        ILUPP_HIP(hipDeviceGetAttribute(&max_lds, hipDeviceAttributeMaxSharedMemoryPerBlock, dev));
-        hipFuncAttributes fa;
-        ILUPP_HIP(hipFuncGetAttributes(&fa, reinterpret_cast<const void *>(&k_cg_batch)));
-        const size_t room = (size_t)max_lds > fa.sharedSizeBytes ? (size_t)max_lds - fa.sharedSizeBytes : 0;
-        ILUPP_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_cg_batch), hipFuncAttributeMaxDynamicSharedMemorySize, (int)room));
-        cap = room;
-        cap_dev = dev;
-    }
-    return cap;
-}
+// ---- the host side of the two solver kernels ---------------------------------------------------------------------------------------
+static size_t solve_batch_lds_cap(BatchSolver s) { return s == BATCH_CG ? kernel_lds_cap<k_cg_batch>() : kernel_lds_cap<k_bicgstab_batch>(); }
 
-// the largest n of a member of the CG launch: pivot_bicgstab_batch_max_n's formula on this kernel's own attributes
-int64_t cg_batch_max_n()
+// the largest n of a member of the solve's launch: the dot scratch and 8 n bytes for the sweeps fit, and the dot has at most kDotMaxNb chunks
+int64_t solve_batch_max_n(BatchSolver s)
 {
-    const size_t cap = cg_batch_lds_cap(), scratch = sizeof(double) * (size_t)kDotScratch;
+    const size_t cap = solve_batch_lds_cap(s), scratch = sizeof(double) * (size_t)kDotScratch;
     const int64_t by_lds = cap > scratch ? (int64_t)((cap - scratch) / 8) : 0;
     return by_lds < 256 * kDotMaxNb ? by_lds : 256 * kDotMaxNb;
 }
 
-int cg_batch_work_factor() { return kCgBatchVectors; }
+int solve_batch_work_factor(BatchSolver s) { return s == BATCH_CG ? kCgBatchVectors : kBicgstabBatchVectors; }
 
 // `count` members, one workgroup each; sweep_bytes of LDS for the sweeps of every workgroup (the dot scratch comes on top)
-int cg_batch_launch(hipStream_t st, int32_t count, const PivotApplyDesc *d_table, const PivotSolveDesc *d_systems, const double *d_b,
-                    const double *d_x0, double *d_x, double *d_work, size_t sweep_bytes, int32_t maxiter, double rtol, int32_t check_every,
-                    int64_t *d_iterations, int32_t *d_flags, double *d_rr, double *d_bnorm)
+int solve_batch_launch(BatchSolver s, hipStream_t st, int32_t count, const PivotApplyDesc *d_table, const PivotSolveDesc *d_systems,
+                       const double *d_b, const double *d_x0, double *d_x, double *d_work, size_t sweep_bytes, int32_t maxiter, double rtol,
+                       int32_t check_every, int64_t *d_iterations, int32_t *d_flags, double *d_rr, double *d_last)
 {
     if (count <= 0) return ILUPP_OK;
     const size_t lds_bytes = sizeof(double) * (size_t)kDotScratch + sweep_bytes;
-    if (lds_bytes > cg_batch_lds_cap()) return ILUPP_ERR_UNSUPPORTED;
-    hipLaunchKernelGGL(k_cg_batch, dim3((unsigned)count), dim3(kBatchThreads), lds_bytes, st, d_table, d_systems, d_b, d_x0, d_x, d_work,
+    if (lds_bytes > solve_batch_lds_cap(s)) return ILUPP_ERR_UNSUPPORTED;
+    const auto kernel = s == BATCH_CG ? k_cg_batch : k_bicgstab_batch;
+    hipLaunchKernelGGL(kernel, dim3((unsigned)count), dim3(kBatchThreads), lds_bytes, st, d_table, d_systems, d_b, d_x0, d_x, d_work,
                        (unsigned)sweep_bytes, (int)maxiter, rtol, (int)check_every, reinterpret_cast<long long *>(d_iterations), d_flags, d_rr,
-                       d_bnorm);
-    ILUPP_HIP(hipGetLastError());
-    return ILUPP_OK;
-}
-
-
-// ---- left-preconditioned BiCGstab for members of EVERY batched class, or none, in ONE launch: one workgroup per member --------------
-// k_bicgstab_batch is k_pivot_bicgstab_batch with the member's preconditioner left open: a descriptor with perm != nullptr is an ILUCP /
-// ILUTP member as there; perm == nullptr a non-pivoting one (ILU0, ILUT, ILUC, IChol0, ICholT: the two triangles of apply_plan /
-// sweep_parts, tmp from the scratch's block), which pivot_apply_member applies without a permutation; ptr1 == nullptr a member without a
-// preconditioner, prec_ of _bicgstab_block being the identity: the apply is skipped (the branch is uniform over the workgroup), r = r0*,
-// Ap = A p, As = A s.  Everything else is that kernel's: the half steps, the seven vectors, the LDS layout, the exit words -- and hence,
-// for every member, the bits of bicgstab(A_k, b_k[:, None], M_k).  k_pivot_bicgstab_batch stays as it is (the pivot-only batches of
-// device.bicgstab_batch still run it); it computes a subset of what this kernel computes.
-__global__ void __launch_bounds__(kBatchThreads)
-k_bicgstab_batch(const PivotApplyDesc *__restrict__ table, const PivotSolveDesc *__restrict__ systems, const double *bbase,
-                 const double *x0base, double *xbase, double *work, const unsigned sweep_bytes, const int maxiter, const double rtol,
-                 const int check_every, long long *iterations, int32_t *flags, double *rr_out, double *init_out)
-{
-    extern __shared__ unsigned long long lds[];
-    __shared__ unsigned s_progress;
-    __shared__ int s_fail;
-    const PivotApplyDesc d = table[blockIdx.x];
-    const PivotSolveDesc e = systems[blockIdx.x];
-    const int n = d.n, tid = threadIdx.x;
-    if (tid == 0) { s_progress = 0; s_fail = 0; }
-    double *dots = reinterpret_cast<double *>(lds);
-    unsigned long long *arr = lds + kDotScratch;
-    const int nb = (n + 255) / 256, chunk = (n + nb - 1) / nb;      // (n <= 256 kDotMaxNb)
-    unsigned turn = 0;
-    auto part = [&]() { return dots + (turn++ & 1u) * (2 * kDotMaxNb); };
-    const bool has_m = d.ptr1 != nullptr;
-    double *y = work + e.woff, *r = y + n, *r0 = r + n, *p = r0 + n, *s = p + n, *Ap = s + n, *As = Ap + n;
-    const double *b = bbase + d.xoff;
-    const double *x0 = x0base ? x0base + d.xoff : nullptr;
-    double *x = xbase + d.xoff;
-
-    // The loop as a sequence of HALF steps, so that the SpMV, the apply and the pair of dots behind it stand in the code once (the apply
-    // is two inlined sweeps: three copies of it would not fit the instruction cache):
-    //   half 0 (once):   y = x0 or 0; r0* = b (or b - A y); r = M^-1 r0*; r0* = r; p = r; init = sqrt(r.r); zero = (b.b == 0) | (init == 0)
-    //   half 1:          Ap = M^-1 (A p); rho = r.r0*; apr = Ap.r0*; alpha = rho / apr; s = r - alpha Ap
-    //   half 2:          As = M^-1 (A s); omega = (As.s) / (As.As); y += alpha p; y += omega s; r = s - omega As;
-    //                    beta = ((r.r0*) / rho) * (alpha / omega); p = p - omega Ap; p = beta p + r; the convergence test
-    for (int i = tid; i < n; i += kBatchThreads) y[i] = x0 ? x0[i] : 0.0;
-    __syncthreads();                                 // (also publishes s_progress and s_fail: a member without M meets no sweep's barrier)
-    bool failed = false, zero = false, active = false, converged = false, have_rr = false;
-    double init = 0.0, rho = 0.0, alpha = 0.0, rr = 0.0, v2[2];
-    long long iters = 0;
-    for (int half = 0, it = 0;; half = half == 1 ? 2 : 1) {
-        double *vec = half == 0 ? r : half == 1 ? Ap : As;
-        if (half != 0 || x0) {
-            wg_spmv(n, e.aptr, e.aidx, e.aval, half == 0 ? y : half == 1 ? p : s, half == 0 ? As : vec);
-            __syncthreads();
-        }
-        if (half == 0) {
-            if (x0) { for (int i = tid; i < n; i += kBatchThreads) r[i] = b[i] - As[i]; }
-            else { for (int i = tid; i < n; i += kBatchThreads) r[i] = b[i]; }
-            __syncthreads();
-        }
-        if (has_m) {
-            pivot_apply_member(d, vec, arr, sweep_bytes, &s_progress, &s_fail);
-            if (s_fail != 0) { failed = true; active = false; break; }
-        }
-        if (half == 0) {
-            for (int i = tid; i < n; i += kBatchThreads) { const double v = r[i]; r0[i] = v; p[i] = v; }
-            __syncthreads();
-        }
-        wg_dots<2>(n, nb, chunk, half == 2 ? As : r, half == 0 ? r : half == 1 ? r0 : s, half == 0 ? b : vec, half == 0 ? b : half == 1 ? r0 : As,
-                   part(), v2);
-        if (half == 0) {
-            init = __dsqrt_rn(v2[0]);
-            zero = v2[1] == 0.0 || init == 0.0;
-            active = !zero;
-            converged = zero;
-            if (!active || maxiter <= 0) break;
-        } else if (half == 1) {
-            rho = v2[0];
-            if (!(scalar_ok(rho) && scalar_ok(v2[1]))) { active = false; break; }      // breakdown: nothing more is touched, not converged
-            alpha = rho / v2[1];
-            for (int i = tid; i < n; i += kBatchThreads) { const double aap = alpha * Ap[i]; s[i] = r[i] - aap; }
-            __syncthreads();
-        } else {
-            const double omega = v2[0] / v2[1];
-            if (!scalar_ok(omega)) { active = false; break; }
-            for (int i = tid; i < n; i += kBatchThreads) {
-                const double ap = alpha * p[i];
-                double yv = y[i] + ap;
-                const double os = omega * s[i];
-                yv = yv + os;
-                y[i] = yv;
-                const double oas = omega * As[i];
-                r[i] = s[i] - oas;
-            }
-            __syncthreads();
-            wg_dots<1>(n, nb, chunk, r, r0, nullptr, nullptr, part(), v2);
-            const double beta = (v2[0] / rho) * (alpha / omega);
-            for (int i = tid; i < n; i += kBatchThreads) {
-                const double oap = omega * Ap[i];
-                const double pv = p[i] - oap;
-                const double bp = beta * pv;
-                p[i] = bp + r[i];
-            }
-            __syncthreads();
-            ++iters;
-            ++it;
-            if (check_every > 0 && it % check_every == 0 && rtol > 0.0) {
-                wg_dots<1>(n, nb, chunk, r, r, nullptr, nullptr, part(), v2);
-                rr = v2[0];
-                have_rr = true;                      // (r stays as it is from here to the exit when the loop ends now)
-                const double rel = __dsqrt_rn(rr) / init;
-                if (rel <= rtol) { converged = true; active = false; break; }
-            }
-            if (it >= maxiter) break;
-            have_rr = false;
-        }
-    }
-    if (!failed) {
-        if (!have_rr) { wg_dots<1>(n, nb, chunk, r, r, nullptr, nullptr, part(), v2); rr = v2[0]; }      // (r.r at the exit)
-        for (int i = tid; i < n; i += kBatchThreads) x[i] = y[i];
-    }
-    if (tid == 0) {                                  // (one writer per member: its own words, whatever the other members do)
-        *d.err = failed ? 1 : 0;
-        iterations[e.member] = iters;
-        flags[e.member] = (active ? 1 : 0) | (converged ? 2 : 0) | (failed ? 4 : 0) | (zero ? 8 : 0);
-        rr_out[e.member] = rr;
-        init_out[e.member] = init;
-    }
-}
-
-// bytes of dynamic LDS a workgroup of k_bicgstab_batch may take on the current device (as pivot_apply_batch_lds_cap)
-size_t bicgstab_batch_lds_cap()
-{
-    static thread_local int cap_dev = -1;
-    static thread_local size_t cap = 0;
-    int dev = 0;
-    ILUPP_HIP(hipGetDevice(&dev));
-    if (cap_dev != dev) {
-        int max_lds = 0;
-        ILUPP_HIP(hipDeviceGetAttribute(&max_lds, hipDeviceAttributeMaxSharedMemoryPerBlock, dev));
-        hipFuncAttributes fa;
-        ILUPP_HIP(hipFuncGetAttributes(&fa, reinterpret_cast<const void *>(&k_bicgstab_batch)));
-        const size_t room = (size_t)max_lds > fa.sharedSizeBytes ? (size_t)max_lds - fa.sharedSizeBytes : 0;
-        ILUPP_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_bicgstab_batch), hipFuncAttributeMaxDynamicSharedMemorySize, (int)room));
-        cap = room;
-        cap_dev = dev;
-    }
-    return cap;
-}
-
-// the largest n of a member of this launch: pivot_bicgstab_batch_max_n's formula on this kernel's own attributes
-int64_t bicgstab_batch_max_n()
-{
-    const size_t cap = bicgstab_batch_lds_cap(), scratch = sizeof(double) * (size_t)kDotScratch;
-    const int64_t by_lds = cap > scratch ? (int64_t)((cap - scratch) / 8) : 0;
-    return by_lds < 256 * kDotMaxNb ? by_lds : 256 * kDotMaxNb;
-}
-
-// `count` members, one workgroup each; sweep_bytes of LDS for the sweeps of every workgroup (the dot scratch comes on top)
-int bicgstab_batch_launch(hipStream_t st, int32_t count, const PivotApplyDesc *d_table, const PivotSolveDesc *d_systems, const double *d_b,
-                          const double *d_x0, double *d_x, double *d_work, size_t sweep_bytes, int32_t maxiter, double rtol,
-                          int32_t check_every, int64_t *d_iterations, int32_t *d_flags, double *d_rr, double *d_init)
-{
-    if (count <= 0) return ILUPP_OK;
-    const size_t lds_bytes = sizeof(double) * (size_t)kDotScratch + sweep_bytes;
-    if (lds_bytes > bicgstab_batch_lds_cap()) return ILUPP_ERR_UNSUPPORTED;
-    hipLaunchKernelGGL(k_bicgstab_batch, dim3((unsigned)count), dim3(kBatchThreads), lds_bytes, st, d_table, d_systems, d_b, d_x0, d_x, d_work,
-                       (unsigned)sweep_bytes, (int)maxiter, rtol, (int)check_every, reinterpret_cast<long long *>(d_iterations), d_flags, d_rr, d_init);
+                       d_last);
     ILUPP_HIP(hipGetLastError());
     return ILUPP_OK;
 }

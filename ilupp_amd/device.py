@@ -265,9 +265,8 @@ def bicgstab_batch(As, b, offsets, Ms, x0=None, maxiter=100, rtol=0.0, check_eve
     ``As``: a list of DeviceCSR; ``Ms``: as many members, each of them an ``ilupp_amd.ILUCPPreconditioner`` / ``ILUTPPreconditioner``
     object or a ``PivotedOperator``; or anything ``cg_batch`` takes (a ``DevicePreconditioner`` of the ILU0 / ILUT / ILUC / IChol0 /
     ICholT kinds, a ``FactorOperator`` or a host class of the ctypes binding); or ``None`` (no preconditioner) -- mixed at will, each
-    object at most once.  A batch of pivoting members only goes through ilupp_hip_pivot_bicgstab_batch_device (k_pivot_bicgstab_batch),
-    every other batch through ilupp_hip_bicgstab_batch_device (k_bicgstab_batch, which takes all three kinds of member in the same
-    launch); a pivoting member has the same bits either way.  ``b``: ONE contiguous 1-D fp64 CUDA tensor, member k's right-hand side is
+    object at most once.  Every batch goes through ilupp_hip_bicgstab_batch_device (k_bicgstab_batch, which takes all three kinds of
+    member in the same launch).  ``b``: ONE contiguous 1-D fp64 CUDA tensor, member k's right-hand side is
     ``b[offsets[k] : offsets[k] + n_k]``; ``x0``: the same layout.  Returns a new tensor of b's shape, a clone of ``x0`` or zeros, whose
     member slices hold the solutions; every other element is untouched.  Per member the loop of ``bicgstab`` for one column: ``maxiter``,
     ``rtol`` and ``check_every`` mean what they mean there, a member that converges or breaks down stops alone, and every member has the
@@ -298,7 +297,6 @@ def bicgstab_batch(As, b, offsets, Ms, x0=None, maxiter=100, rtol=0.0, check_eve
                                 "PivotedOperators, ILU0 / ILUT / ILUC / IChol0 / ICholT preconditioners (DevicePreconditioners of those "
                                 "kinds, FactorOperators or the host classes) or None, got %s" % type(M).__name__) from None
         natives.append(pr)
-    pivot_only = all(isinstance(pr, _native.PivotedPreconditioner) for pr in natives)
     if not (len(As) == len(Ms) == len(offsets)):
         raise ValueError("%d matrices, %d preconditioners and %d offsets" % (len(As), len(Ms), len(offsets)))
     for name, t in (("b", b), ("x0", x0)):
@@ -315,6 +313,16 @@ def bicgstab_batch(As, b, offsets, Ms, x0=None, maxiter=100, rtol=0.0, check_eve
         if o < 0 or o + n > b.numel():
             raise ValueError("a vector of %d elements at offset %d does not lie inside b (%d elements)" % (n, o, b.numel()))
         dims.append(n)
+    return _solve_batch(bicgstab, _native.bicgstab_batch_device, 7, "init", As, Ms, natives, dims, b, offsets, x0, maxiter, rtol,
+                        check_every, stats)
+
+
+def _solve_batch(single, entry, work_factor, relres, As, Ms, natives, dims, b, offsets, x0, maxiter, rtol, check_every, stats):
+    """``bicgstab_batch`` / ``cg_batch`` behind their argument checks: the result tensor, the workspace of ``work_factor`` doubles per
+    unknown and the per-member outputs, the launch through ``entry`` (``_native.bicgstab_batch_device`` / ``cg_batch_device``) on torch's
+    current stream, ``single`` (``bicgstab`` / ``cg``) for the members of routes 1 and 2, and the stats.  ``relres`` names the launch's last
+    per-member word, which sqrt(r.r) is divided by: "init", BiCGstab's ||r_0|| (0 where flag 8 marks a zero member), or "bnorm", CG's
+    ||b|| (0 where it is 0; 1 for a member that was not launched)."""
     x = torch.zeros_like(b) if x0 is None else x0.clone()
     count = len(natives)
     if count == 0:
@@ -322,21 +330,15 @@ def bicgstab_batch(As, b, offsets, Ms, x0=None, maxiter=100, rtol=0.0, check_eve
             stats.update(iterations=torch.zeros(0, dtype=torch.int64), converged=torch.zeros(0, dtype=torch.bool),
                          relres=torch.zeros(0, dtype=torch.float64), route=[])
         return x
-    work = torch.empty(7 * sum(dims), dtype=torch.float64, device=b.device)
+    work = torch.empty(work_factor * sum(dims), dtype=torch.float64, device=b.device)
     iters = torch.zeros(count, dtype=torch.int64, device=b.device)
     flags = torch.zeros(count, dtype=torch.int32, device=b.device)
     rr = torch.zeros(count, dtype=torch.float64, device=b.device)
-    init = torch.zeros(count, dtype=torch.float64, device=b.device)
+    last = (torch.zeros if relres == "init" else torch.ones)(count, dtype=torch.float64, device=b.device)
     matrices = [(A.data.data_ptr(), A.indices.data_ptr(), A.indptr.data_ptr(), A.nnz) for A in As]
     _on_current_stream()
-    if pivot_only:
-        route = _native.pivot_bicgstab_batch_device(
-            natives, matrices, b.data_ptr(), 0 if x0 is None else x0.data_ptr(), x.data_ptr(), offsets, work.data_ptr(), work.numel(),
-            maxiter, rtol, check_every, iters.data_ptr(), flags.data_ptr(), rr.data_ptr(), init.data_ptr(), sync=False)
-    else:
-        route = _native.bicgstab_batch_device(
-            natives, dims, matrices, b.data_ptr(), 0 if x0 is None else x0.data_ptr(), x.data_ptr(), offsets, work.data_ptr(),
-            work.numel(), maxiter, rtol, check_every, iters.data_ptr(), flags.data_ptr(), rr.data_ptr(), init.data_ptr(), sync=False)
+    route = entry(natives, dims, matrices, b.data_ptr(), 0 if x0 is None else x0.data_ptr(), x.data_ptr(), offsets, work.data_ptr(),
+                  work.numel(), maxiter, rtol, check_every, iters.data_ptr(), flags.data_ptr(), rr.data_ptr(), last.data_ptr(), sync=False)
     alone = {}
     for k, rt in enumerate(route):
         if rt == 0:
@@ -347,13 +349,13 @@ def bicgstab_batch(As, b, offsets, Ms, x0=None, maxiter=100, rtol=0.0, check_eve
         if M is not None and not hasattr(M, "apply_"):
             M = PivotedOperator(M) if isinstance(natives[k], _native.PivotedPreconditioner) else FactorOperator(M)
         st = {}
-        xk = bicgstab(As[k], b[o:o + n][:, None], M, x0=None if x0 is None else x0[o:o + n][:, None], maxiter=maxiter, rtol=rtol,
-                      check_every=check_every, stats=st)
+        xk = single(As[k], b[o:o + n][:, None], M, x0=None if x0 is None else x0[o:o + n][:, None], maxiter=maxiter, rtol=rtol,
+                    check_every=check_every, stats=st)
         x[o:o + n] = xk[:, 0]
         alone[k] = st
     if isinstance(stats, dict):
-        zero = (flags & 8) != 0
-        rel = torch.sqrt(rr) / init                      # as _bicgstab_block computes it
+        zero = (flags & 8) != 0 if relres == "init" else last == 0
+        rel = torch.sqrt(rr) / last                      # as _bicgstab_block / _cg_block computes it
         rel = torch.where(zero, torch.zeros_like(rel), rel).cpu()
         its, conv = iters.cpu(), ((flags & 2) != 0).cpu()
         for k, st in alone.items():
@@ -559,44 +561,8 @@ def cg_batch(As, b, offsets, Ms, x0=None, maxiter=100, rtol=0.0, check_every=0, 
     _on_device(b, "b")
     if x0 is not None:
         _on_device(x0, "x0")
-    x = torch.zeros_like(b) if x0 is None else x0.clone()
-    count = len(natives)
-    if count == 0:
-        if isinstance(stats, dict):
-            stats.update(iterations=torch.zeros(0, dtype=torch.int64), converged=torch.zeros(0, dtype=torch.bool),
-                         relres=torch.zeros(0, dtype=torch.float64), route=[])
-        return x
-    ns = [A.n for A in As]
-    work = torch.empty(5 * sum(ns), dtype=torch.float64, device=b.device)
-    iters = torch.zeros(count, dtype=torch.int64, device=b.device)
-    flags = torch.zeros(count, dtype=torch.int32, device=b.device)
-    rr = torch.zeros(count, dtype=torch.float64, device=b.device)
-    bnorm = torch.ones(count, dtype=torch.float64, device=b.device)
-    _on_current_stream()
-    route = _native.cg_batch_device(
-        natives, ns, [(A.data.data_ptr(), A.indices.data_ptr(), A.indptr.data_ptr(), A.nnz) for A in As], b.data_ptr(),
-        0 if x0 is None else x0.data_ptr(), x.data_ptr(), offsets, work.data_ptr(), work.numel(), maxiter, rtol, check_every,
-        iters.data_ptr(), flags.data_ptr(), rr.data_ptr(), bnorm.data_ptr(), sync=False)
-    alone = {}
-    for k, rt in enumerate(route):
-        if rt == 0:
-            continue
-        # too large for the launch or degenerate: the single solve, whose bits the launch's members have
-        o, n = offsets[k], ns[k]
-        M = Ms[k] if (Ms[k] is None or hasattr(Ms[k], "apply_")) else FactorOperator(Ms[k])
-        st = {}
-        xk = cg(As[k], b[o:o + n][:, None], M, x0=None if x0 is None else x0[o:o + n][:, None], maxiter=maxiter, rtol=rtol,
-                check_every=check_every, stats=st)
-        x[o:o + n] = xk[:, 0]
-        alone[k] = st
-    if isinstance(stats, dict):
-        rel = torch.sqrt(rr) / bnorm                     # as _cg_block computes it
-        rel = torch.where(bnorm == 0, torch.zeros_like(rel), rel).cpu()
-        its, conv = iters.cpu(), ((flags & 2) != 0).cpu()
-        for k, st in alone.items():
-            its[k], conv[k], rel[k] = st["iterations"][0], st["converged"][0], st["relres"][0]
-        stats["iterations"], stats["converged"], stats["relres"], stats["route"] = its, conv, rel, route
-    return x
+    return _solve_batch(cg, _native.cg_batch_device, 5, "bnorm", As, Ms, natives, [A.n for A in As], b, offsets, x0, maxiter, rtol,
+                        check_every, stats)
 
 
 def cg(A, b, M=None, x0=None, maxiter=100, rtol=0.0, check_every=0, stats=None):

@@ -396,7 +396,7 @@ int ilupp_hip_pivot_apply_batch_device(int32_t count, ilupp_ilucp *const *member
 int ilupp_hip_pivot_apply_batch(int32_t count, ilupp_ilucp *const *members, double *const *x, const int64_t *len, int transpose, int32_t *route);
 /* Left-preconditioned BiCGstab for MANY small systems at once, each with its own ILUCP / ILUTP object (mixed at will, each at most once):
  * ONE launch, one workgroup per system, which runs the whole loop on the device -- SpMV, apply, dot products, updates and the convergence
- * test (k_pivot_bicgstab_batch, sptrsv_batch.hip) -- with no host round trip.  Member i: the CSR matrix d_data[i] / d_indices[i] /
+ * test (k_bicgstab_batch, sptrsv_batch.hip) -- with no host round trip.  Member i: the CSR matrix d_data[i] / d_indices[i] /
  * d_indptr[i] (device arrays; n_i = the object's n, nnz[i] entries; the four lists are host arrays), the right-hand side d_b + offsets[i],
  * the start d_x0 + offsets[i] (d_x0 may be NULL: zero) and the result d_x + offsets[i], n_i doubles each; what lies between the vectors
  * of d_x is left untouched.  d_work: 7 * sum n_i doubles of device memory (work_doubles says how many there are).  The loop is that of

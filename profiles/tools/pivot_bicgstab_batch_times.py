@@ -1,4 +1,4 @@
-"""ilupp_amd.device.bicgstab_batch (the whole left-preconditioned BiCGstab loop of every member in ONE launch, k_pivot_bicgstab_batch) next to
+"""ilupp_amd.device.bicgstab_batch (the whole left-preconditioned BiCGstab loop of every member in ONE launch, k_bicgstab_batch) next to
 the loop of single solves ilupp_amd.device.bicgstab(A_k, b_k[:, None], PivotedOperator(P_k)) on the same objects, for 1, 16 and 64 members
 of matgen.random_dd(n, 8, 25.0, seed), `iters` iterations each (rtol = 0: the work is fixed); a host clock around the call and a device
 synchronisation; 2 warm-up and `reps` timed repetitions of each, alternating; median [min, max] in ms.

@@ -1,6 +1,6 @@
 """CPU tests of the batched BiCGstab solve with members of every class: the C ABI exports ilupp_hip_bicgstab_batch_device and
 ilupp_hip_bicgstab_batch_max_n and refuses bad arguments before any HIP call; ilupp_amd.device.bicgstab_batch checks a mixed batch before
-any native call and still sends a batch of pivoting members only to ilupp_hip_pivot_bicgstab_batch_device.  (The refusal of a multilevel
+any native call and sends every batch, one of pivoting members only included, to ilupp_hip_bicgstab_batch_device.  (The refusal of a multilevel
 handle needs a built multilevel object: tests/test_gpu_bicgstab_batch.py.)"""
 import ctypes
 
@@ -215,9 +215,10 @@ def test_dimension_and_slice_checks_of_a_mixed_batch(monkeypatch):
         ild.bicgstab_batch([A4], b, [0], [P4], x0=torch.zeros(7, dtype=torch.float64).as_subclass(OnDevice))
 
 
-def test_a_pivot_only_batch_still_takes_the_pivot_entry(monkeypatch):
-    """a batch of pivoting members only reaches _native.pivot_bicgstab_batch_device, a batch with one other member the new entry: the
-    call is recorded and ended there (the tensors are CPU tensors that say they are on the device; nothing native runs)"""
+def test_every_batch_takes_the_one_entry(monkeypatch):
+    """every batch, one of pivoting members only included, reaches _native.bicgstab_batch_device with the members' native objects and
+    dimensions, and _native.pivot_bicgstab_batch_device is never called: the call is recorded and ended there (the tensors are CPU
+    tensors that say they are on the device; nothing native runs)"""
     torch = pytest.importorskip("torch")
     import ilupp_amd.device as ild
     from ilupp_amd import _native
@@ -236,17 +237,16 @@ def test_a_pivot_only_batch_still_takes_the_pivot_entry(monkeypatch):
         return f
     monkeypatch.setattr(_native, "lib", lambda: _Boom())
     monkeypatch.setattr(_native, "set_caller_stream", lambda *a, **k: None)
-    monkeypatch.setattr(_native, "pivot_bicgstab_batch_device", entry("pivot"))
+    monkeypatch.setattr(_native, "pivot_bicgstab_batch_device",
+                        lambda *a, **k: (_ for _ in ()).throw(AssertionError("the pivot entry was called")))
     monkeypatch.setattr(_native, "bicgstab_batch_device", entry("all"))
     monkeypatch.setattr(torch.cuda, "current_stream", lambda *a, **k: type("S", (), {"cuda_stream": 0})())
     b = torch.zeros(8, dtype=torch.float64).as_subclass(OnDevice)
     A4, A3, V4, V3, P3 = _fake_csr(4), _fake_csr(3), _pivoting(4), _pivoting(3, rows=True), _unbuilt("ILU0", 3)
     for A in (A4, A3):
         A.data = A.indices = A.indptr = torch.zeros(1)
-    with pytest.raises(Reached, match="pivot"):
-        ild.bicgstab_batch([A4, A3], b, [0, 4], [V4, ild.PivotedOperator(V3)])
-    assert [c[0] for c in calls] == ["pivot"] and calls[0][1][0] == [V4, V3]
-    for Ms, natives in (([V4, P3], [V4, P3.pr]), ([V4, None], [V4, None]), ([None, P3], [None, P3.pr])):
+    for Ms, natives in (([V4, ild.PivotedOperator(V3)], [V4, V3]), ([V4, P3], [V4, P3.pr]), ([V4, None], [V4, None]),
+                        ([None, P3], [None, P3.pr])):
         del calls[:]
         with pytest.raises(Reached, match="all"):
             ild.bicgstab_batch([A4, A3], b, [0, 4], Ms)

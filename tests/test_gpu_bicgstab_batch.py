@@ -220,8 +220,7 @@ def test_solves_equal_the_loop(solve_members, check_every):
 # ---- 2. pivoting and non-pivoting members in one launch ----
 def test_mixed_families_in_one_launch():
     """ILUCP and ILUTP members (n = 65, 300, 513; random_dd and tridiagonal matrices) interleaved with ILU0 members and members without a
-    preconditioner: every member equals its single solve, and the pivoting members have, bit for bit, what a batch of them alone gives
-    through k_pivot_bicgstab_batch"""
+    preconditioner: every member equals its single solve, and the pivoting members have, bit for bit, what a batch of them alone gives"""
     import torch
     import ilupp_amd as ilupp
     import ilupp_amd.device as ild
@@ -243,7 +242,7 @@ def test_mixed_families_in_one_launch():
         assert st["route"] == [0] * 12
         assert all(it > 0 for _, it, _, _ in ref)
         sto = {}
-        old = ild.bicgstab_batch(As[0::2], b, offsets[0::2], Ms[0::2], stats=sto, **kw).cpu().numpy()      # pivoting members only: the old kernel
+        old = ild.bicgstab_batch(As[0::2], b, offsets[0::2], Ms[0::2], stats=sto, **kw).cpu().numpy()      # the pivoting members in a batch of their own
         assert sto["route"] == [0] * 6
         for j, (A, o) in enumerate(zip(As[0::2], offsets[0::2])):
             assert np.array_equal(_bits(old[o:o + A.n]), _bits(xh[o:o + A.n])), j

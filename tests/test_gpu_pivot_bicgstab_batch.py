@@ -1,6 +1,7 @@
 """GPU tests of the batched BiCGstab solve of the two pivoting classes (ilupp_amd.device.bicgstab_batch over
-ilupp_hip_pivot_bicgstab_batch_device: one launch of k_pivot_bicgstab_batch, one workgroup per system with the whole preconditioned loop
-inside it).  Every member has the bits of ilupp_amd.device.bicgstab(A_k, b_k[:, None], PivotedOperator(P_k), ...) -- the loop of SpMM,
+ilupp_hip_bicgstab_batch_device: one launch of k_bicgstab_batch, one workgroup per system with the whole preconditioned loop inside it;
+the C entry of these classes alone, ilupp_hip_pivot_bicgstab_batch_device, runs the same kernel and is called directly in the last
+test).  Every member has the bits of ilupp_amd.device.bicgstab(A_k, b_k[:, None], PivotedOperator(P_k), ...) -- the loop of SpMM,
 single device apply, block dots and block updates -- run one member at a time: the solution on its int64 view, the iteration count, the
 converged flag and the relative residual.  Across the dot's and the sweeps' shapes, with convergence per member, with x0, next to a zero
 and a NaN member, with more members than CUs, across the LDS cap, between a producer and a consumer on a side stream; and sixteen
@@ -359,3 +360,65 @@ def test_sixteen_solves_side_by_side_beat_the_loop():
     t_loop = float(np.median([looped()[0] for _ in range(5)]))
     print("ilucp n %d x 16, 20 iterations: t_batch %.5f s, t_loop %.5f s" % (n, t_batch, t_loop))
     assert t_batch < t_loop, (t_batch, t_loop)
+
+
+# ---- 10. the C entry of the pivoting classes alone, which ilupp_amd.device does not call ----
+def test_the_pivot_entry_called_directly_equals_bicgstab_batch(monkeypatch):
+    """_native.pivot_bicgstab_batch_device with ILUPP_BATCH_APPLY_MAX_N = 600 on ILUCP / ILUTP members of n = 65, 300 (both sweep arrays
+    in LDS: 16 n <= 8 * 600), 513 (one array, the hand-over through tmp) and 700 (route 1: not launched, not solved): the three launched
+    members' solutions and their iterations / flags / rr / init words have the bits of device.bicgstab_batch on the same three members
+    (and of _native.bicgstab_batch_device, the entry behind it, word for word); the fourth member's slice of x, its words and the gaps
+    keep the bits they came with"""
+    import torch
+    import ilupp_amd.device as ild
+    from ilupp_amd import _native
+    monkeypatch.setenv("ILUPP_BATCH_APPLY_MAX_N", "600")
+    ns = [65, 300, 513, 700]
+    mats = [_random(n, 600 + k, "csr") for k, n in enumerate(ns)]
+    Ps = _mixed(mats)
+    As = _device(mats)
+    host, offsets = _pack([C.rhs(n) for n in ns])
+    b = torch.from_numpy(host).cuda()
+    natives = [P.pr for P in Ps]
+    matrices = [(A.data.data_ptr(), A.indices.data_ptr(), A.indptr.data_ptr(), A.nnz) for A in As]
+    pattern = np.int64(0x7FF4DEADBEEF0123)                   # (a signalling NaN's bits: arithmetic on it would not give it back)
+    kw = dict(maxiter=7, rtol=0.0, check_every=0)
+
+    def direct(entry, *dims):
+        x = torch.full((host.shape[0],), int(pattern), dtype=torch.int64, device="cuda").view(torch.float64)
+        work = torch.empty(7 * sum(ns), dtype=torch.float64, device="cuda")
+        iters = torch.full((4,), -1, dtype=torch.int64, device="cuda")
+        flags = torch.full((4,), -1, dtype=torch.int32, device="cuda")
+        rr = torch.full((4,), -1.0, dtype=torch.float64, device="cuda")
+        init = torch.full((4,), -1.0, dtype=torch.float64, device="cuda")
+        _native.set_caller_stream(torch.cuda.current_stream().cuda_stream, True)
+        route = entry(natives, *dims, matrices, b.data_ptr(), 0, x.data_ptr(), offsets, work.data_ptr(), work.numel(), kw["maxiter"],
+                      kw["rtol"], kw["check_every"], iters.data_ptr(), flags.data_ptr(), rr.data_ptr(), init.data_ptr(), sync=True)
+        torch.cuda.synchronize()
+        return route, x.cpu().numpy(), iters.cpu().numpy(), flags.cpu().numpy(), rr, init
+
+    route, xh, iters, flags, rr, init = direct(_native.pivot_bicgstab_batch_device)
+    assert route == [0, 0, 0, 1]
+    st = {}
+    want = ild.bicgstab_batch(As[:3], b, offsets[:3], Ps[:3], stats=st, **kw).cpu().numpy()
+    assert st["route"] == [0, 0, 0]
+    relres = (torch.sqrt(rr) / init).cpu().numpy()           # (as bicgstab_batch computes it from the two words)
+    for k in range(3):
+        o, n = offsets[k], ns[k]
+        assert np.array_equal(_bits(xh[o:o + n]), _bits(want[o:o + n])), (k, "x", float(np.max(np.abs(xh[o:o + n] - want[o:o + n]))))
+        assert int(iters[k]) == int(st["iterations"][k]) == 7, (k, "iterations", int(iters[k]), int(st["iterations"][k]))
+        assert bool(flags[k] & 2) == bool(st["converged"][k]) and not flags[k] & (4 | 8), (k, "flags", int(flags[k]))
+        assert np.array_equal(_bits(relres[k:k + 1]), _bits(st["relres"][k:k + 1].numpy())), (k, "relres", float(relres[k]), float(st["relres"][k]))
+        assert np.all(np.isfinite(xh[o:o + n]))
+    # the same words from the entry bicgstab_batch goes through, all four members named
+    route2, xh2, iters2, flags2, rr2, init2 = direct(_native.bicgstab_batch_device, ns)
+    assert route2 == [0, 0, 0, 1]
+    assert np.array_equal(_bits(xh), _bits(xh2))
+    assert np.array_equal(iters, iters2) and np.array_equal(flags, flags2)
+    assert np.array_equal(_bits(rr.cpu().numpy()), _bits(rr2.cpu().numpy())) and np.array_equal(_bits(init.cpu().numpy()), _bits(init2.cpu().numpy()))
+    # the member that was not launched, and the gaps
+    mask = np.ones(host.shape[0], dtype=bool)
+    for o, n in zip(offsets[:3], ns[:3]):
+        mask[o:o + n] = False
+    assert np.all(_bits(xh[mask]) == pattern)
+    assert int(iters[3]) == -1 and int(flags[3]) == -1 and float(rr.cpu()[3]) == -1.0 and float(init.cpu()[3]) == -1.0
