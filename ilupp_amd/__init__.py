@@ -306,6 +306,20 @@ class ILU0Preconditioner(_BlockApply, _HipPreconditioner):
     def __init__(self, A):
         super().__init__(A, lambda m: _backend.ILU0Preconditioner(*m))
 
+    @classmethod
+    def batch(cls, matrices):
+        """One preconditioner per matrix of `matrices` (all CSR or all CSC), built by ONE native call: the objects
+        ``[ILU0Preconditioner(A) for A in matrices]`` gives -- factors, ``total_nnz`` and every apply bit for bit -- from two kernel
+        launches of one workgroup per matrix around one read-back (``ilupp_hip_ilu0_create_batch``), where the loop pays the single
+        constructor's analysis and host waits per object.  Made for MANY SMALL matrices (per-cell implicit steps, finite-element patches,
+        block-Jacobi blocks): a matrix above the launches' caps (n above ``_native.ilu0_refactor_batch_max_n()``, a row of more than 31
+        entries) and a batch of one are built by the single constructor inside the same call.  The members go into
+        ``ilupp_amd.device.apply_batch_`` / ``cg_batch`` / ``bicgstab_batch`` / ``refactor_batch_`` as they are; the tables of the
+        single applies are built at a member's first ``P @ x``.  A matrix that fails (no diagonal entry in a row) raises what the
+        constructor raises, named by its number; no object is returned then.  TypeError for matrices of both formats; an empty list
+        gives ``[]``."""
+        return _batch(cls, matrices, lambda ms, is_csr: _native.ILU0Preconditioner_batch(ms, is_csr))
+
 
 class IChol0Preconditioner(_BlockApply, _HipPreconditioner):
     """IChol(0) of a symmetric positive definite matrix, in the pattern of its lower triangle."""

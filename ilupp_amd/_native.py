@@ -188,6 +188,10 @@ def lib():
                                                        ctypes.POINTER(_VP), ctypes.POINTER(ctypes.c_int64), _VP, ctypes.c_int, _I32P]
     L.ilupp_hip_ilu0_refactor_batch_max_n.argtypes = []
     L.ilupp_hip_ilu0_refactor_batch_max_n.restype = ctypes.c_int64
+    L.ilupp_hip_ilu0_create_batch.argtypes = [ctypes.c_int32, ctypes.POINTER(_VP), ctypes.POINTER(_VP), ctypes.POINTER(_VP), _I32P, ctypes.c_int,
+                                              ctypes.POINTER(_VP), _I32P, _I32P]
+    L.ilupp_hip_ilu0_create_batch_device.argtypes = [ctypes.c_int32, ctypes.POINTER(_VP), ctypes.POINTER(_VP), ctypes.POINTER(_VP), _I32P,
+                                                     ctypes.POINTER(ctypes.c_int64), ctypes.c_int, ctypes.POINTER(_VP), _I32P, _I32P]
     L.ilupp_hip_ilucp_total_nnz.argtypes = [_VP]
     L.ilupp_hip_ilucp_total_nnz.restype = ctypes.c_int64
     L.ilupp_hip_ilucp_zero_pivots.argtypes = [_VP]
@@ -228,6 +232,7 @@ ABI_SYMBOLS = [
     "ilupp_hip_pivot_bicgstab_batch_device", "ilupp_hip_apply_batch_device", "ilupp_hip_cg_batch_device", "ilupp_hip_cg_batch_max_n",
     "ilupp_hip_bicgstab_batch_device", "ilupp_hip_bicgstab_batch_max_n",
     "ilupp_hip_ilu0_refactor_batch_device", "ilupp_hip_ilu0_refactor_batch_max_n",
+    "ilupp_hip_ilu0_create_batch", "ilupp_hip_ilu0_create_batch_device",
     "ilupp_hip_apply_block", "ilupp_hip_apply_block_device", "ilupp_hip_block_path",
     "ilupp_hip_spmm_device", "ilupp_hip_block_dot_device", "ilupp_hip_cg_block_update_device", "ilupp_hip_bicgstab_block_update_device",
 ]
@@ -635,6 +640,58 @@ def ILU0Preconditioner_device(d_data, d_indices, d_indptr, n, is_csr, nnz=None):
     if rc:
         _raise(rc)
     return Preconditioner(h)
+
+
+def _ilu0_batch_result(rc, cnt, out, status):
+    """the native objects of a batched ILU(0) construction, or its error (the library has destroyed every object of a failed call)"""
+    if rc:
+        first = next((k for k in range(cnt) if status[k] != 0), -1)
+        msg = lib().ilupp_hip_last_error().decode() + " (matrix %d of the batch, status %d)" % (first, status[first] if first >= 0 else rc)
+        if rc == ILUPP_ERR_UNSUPPORTED:
+            raise NotImplementedError(msg)
+        raise RuntimeError(msg)
+    return [Preconditioner(_VP(out[k])) for k in range(cnt)]
+
+
+def ILU0Preconditioner_batch(matrices, is_csr, routes=None):
+    """one ILU(0) preconditioner per matrix of `matrices` (a list of (data, indices, indptr)), built by two launches of one workgroup per
+    matrix around one read-back (ilupp_hip_ilu0_create_batch): the factors and applies of the objects the constructor gives one at a
+    time, bit for bit.  `routes`, when a list, receives every member's route (0 = the launches, 1 = the single constructor inside the
+    same call)"""
+    cnt = len(matrices)
+    if cnt == 0:
+        return []
+    keep, ns = [], []
+    D, I, P = (_VP * cnt)(), (_VP * cnt)(), (_VP * cnt)()
+    for k, (d, i, ptr) in enumerate(matrices):
+        args, arrays = _matrix_args(d, i, ptr, is_csr)
+        keep.append(arrays)
+        D[k], I[k], P[k] = args[0], args[1], args[2]
+        ns.append(args[3])
+    N = (ctypes.c_int32 * cnt)(*ns)
+    out, status, route = (_VP * cnt)(), (ctypes.c_int32 * cnt)(), (ctypes.c_int32 * cnt)()
+    rc = lib().ilupp_hip_ilu0_create_batch(cnt, D, I, P, N, 1 if is_csr else 0, out, status, route)
+    if routes is not None:
+        routes[:] = list(route)
+    return _ilu0_batch_result(rc, cnt, out, status)
+
+
+def ILU0Preconditioner_batch_device(matrices, is_csr, routes=None):
+    """the same for matrices already resident in HBM: `matrices` is a list of (data_ptr, indices_ptr, indptr_ptr, n, nnz) of device CSR
+    arrays (ilupp_hip_ilu0_create_batch_device).  Ordered on the caller's stream (set_caller_stream); the call returns when every member
+    is built"""
+    cnt = len(matrices)
+    if cnt == 0:
+        return []
+    D, I, P = (_VP * cnt)(), (_VP * cnt)(), (_VP * cnt)()
+    N, NNZ = (ctypes.c_int32 * cnt)(), (ctypes.c_int64 * cnt)()
+    for k, (d, i, p, n, nnz) in enumerate(matrices):
+        D[k], I[k], P[k], N[k], NNZ[k] = d, i, p, int(n), int(nnz)
+    out, status, route = (_VP * cnt)(), (ctypes.c_int32 * cnt)(), (ctypes.c_int32 * cnt)()
+    rc = lib().ilupp_hip_ilu0_create_batch_device(cnt, D, I, P, N, NNZ, 1 if is_csr else 0, out, status, route)
+    if routes is not None:
+        routes[:] = list(route)
+    return _ilu0_batch_result(rc, cnt, out, status)
 
 
 def _create_device(fn, d_data, d_indices, d_indptr, n, is_csr, *extra):

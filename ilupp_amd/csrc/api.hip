@@ -241,6 +241,11 @@ struct ilupp_precond {
     const char *block_path = "";
     bool block_events = false;              // the last apply was a block apply: ev[3] .. ev[2] bracket all of it
     hipEvent_t batch_ev = nullptr;          // a batched launch that was not waited for reads the factors (ilupp_hip_apply_batch_device, ilupp_hip_cg_batch_device): what a re-factorisation and the destruction wait for
+    // ILU(0) built by the launches of a batched first construction (ilupp_hip_ilu0_create_batch*): Lc, Uc, nnzA and max_row_len, and nothing of
+    // the single paths' analysis -- no sA / sU, no program, no packed sweeps, never the static form.  The batched launches take it as it
+    // is; the single sweeps' tables (sL, sU, dL, dU) are built from the factors' own patterns on first use (ensure_sweep_tables)
+    bool batch_built = false;
+    bool sweeps_ready = false;
 };
 
 namespace {
@@ -696,6 +701,17 @@ void ensure_transposed(ilupp_precond *p)
     p->haveT = true;
 }
 
+// What the single sweeps of a batch-built ILU(0) object need -- cuts and schedules, tilings, slot tables, descriptors --, on first use and
+// from the factors' own patterns: L forward, U backward, as an ILUT object gets its own (ilut_create_common).  max_row_len stays A's
+// longest row (no row of L or U is longer): it is what the batched re-factorisation routes by.
+void ensure_sweep_tables(ilupp_precond *p)
+{
+    if (!p->batch_built || p->sweeps_ready) return;
+    int32_t longest = 0;
+    p->compact = sweep_tables(p->stream, p, {&p->Lc, true, &p->sL, &p->dL}, {&p->Uc, false, &p->sU, &p->dU}, true, &longest);
+    p->sweeps_ready = true;
+}
+
 // ---- the sweeps of an apply -----------------------------------------------------------------------------------------------------------
 // One sweep of one object: the stored triangle it walks (slot 0 = Lc, 1 = Uc, 2 = UcT, 3 = LcT: the numbering of pack_tried[] and lvl[])
 // and the manner.  Whatever else a sweep needs follows from the slot: sweep_parts.
@@ -857,6 +873,7 @@ static bool llt_static_pair(ilupp_precond *p, PackedSweep **pf_out, PackedSweep 
 enum ApplyRoute { ROUTE_SWEEPS, ROUTE_STATIC_T, ROUTE_STATIC_PAIR };
 static ApplyRoute prepare_apply(ilupp_precond *p, const ApplyPlan &plan, PackedSweep **pf, PackedSweep **pb)
 {
+    ensure_sweep_tables(p);                          // (a batch-built ILU(0) object's first single sweep)
     if (!plan.transposed()) return ROUTE_SWEEPS;
     if (p->kind == KIND_LU) {
         p->pkL.xch_armed = p->pkU.xch_armed = false;
@@ -1065,9 +1082,29 @@ int ilu0_create_common(const DevMat &A, int is_csr, const int32_t *head, ilupp_p
     return ILUPP_OK;
 }
 
+// what ilupp_hip_ilu0_create_device does, under the construction lock its caller holds (the batched construction runs it for the members
+// that do not go to its launches)
+int ilu0_create_device_locked(const double *d_data, const int32_t *d_indices, const int32_t *d_indptr, int32_t n, int is_csr, ilupp_precond **out)
+{
+    if (n <= 0 || !d_indptr) { set_error("matrix has size 0!"); return ILUPP_ERR_INVALID; }
+    // indptr[n], and the head of the matrix for grid.hip's guess: one read-back
+    int32_t head[10];
+    ObjGuard g(new_obj(n));                        // (first: the read-back below also cleans the object's verdict word)
+    const int32_t nnz32 = read_device_head(d_indptr, d_indices, n, head, g.p->ctrl + 8);
+    g.p->verdict_clean = true;
+    return ilu0_create_common(borrow_csr(d_data, d_indices, d_indptr, n, nnz32, true), is_csr, head, out, g.release());
+}
+
 // what ilupp_hip_ilu0_refactor_device does, under the construction lock its caller holds (the batched re-factorisation runs it for the
 // members that do not go to its launch)
-bool is_ilu0_object(const ilupp_precond *p) { return p && p->kind == KIND_LU && p->nnz_mode == NNZ_GENERIC_LU && p->sA.nb > 0; }
+bool is_ilu0_object(const ilupp_precond *p)
+{
+    return p && p->kind == KIND_LU && p->nnz_mode == NNZ_GENERIC_LU && (p->sA.nb > 0 || p->batch_built);
+}
+
+// the launch of the batched re-factorisation with this one member (defined with that launch's host code, below): the single
+// re-factorisation of a batch-built object, which has none of the single numeric paths' tables
+int refactor_in_launch(ilupp_precond *p, const double *d_data, const int32_t *d_indices, const int32_t *d_indptr);
 
 int ilu0_refactor_single(ilupp_precond *p, const double *d_data, const int32_t *d_indices, const int32_t *d_indptr)
 {
@@ -1081,6 +1118,7 @@ int ilu0_refactor_single(ilupp_precond *p, const double *d_data, const int32_t *
         ILUPP_HIP(hipStreamSynchronize(p->stream));
         if ((int64_t)nnz32 != p->nnzA) { set_error("ILU0 refactor: the matrix does not have the analysed pattern"); return ILUPP_ERR_INVALID; }
     }
+    if (p->batch_built) return refactor_in_launch(p, d_data, d_indices, d_indptr);
     const DevMat A = borrow_csr(d_data, d_indices, d_indptr, p->n, p->nnzA, true);
     hipStream_t st = p->stream;
     ILUPP_HIP(hipEventRecord(p->ev[1], st));
@@ -1158,13 +1196,7 @@ int ilupp_hip_ilu0_create_device(const double *d_data, const int32_t *d_indices,
     API_TRY_BUILD
     if (!out) { set_error("null output"); return ILUPP_ERR_INVALID; }
     *out = nullptr;
-    if (n <= 0 || !d_indptr) { set_error("matrix has size 0!"); return ILUPP_ERR_INVALID; }
-    // indptr[n], and the head of the matrix for grid.hip's guess: one read-back
-    int32_t head[10];
-    ObjGuard g(new_obj(n));                        // (first: the read-back below also cleans the object's verdict word)
-    const int32_t nnz32 = read_device_head(d_indptr, d_indices, n, head, g.p->ctrl + 8);
-    g.p->verdict_clean = true;
-    return ilu0_create_common(borrow_csr(d_data, d_indices, d_indptr, n, nnz32, true), is_csr, head, out, g.release());
+    return ilu0_create_device_locked(d_data, d_indices, d_indptr, n, is_csr, out);
     API_CATCH
 }
 
@@ -1648,6 +1680,7 @@ const char *ilupp_hip_path(const ilupp_precond *p)
 {
     if (!p) return "";
     if (p->kind == KIND_LU && p->nnz_mode == NNZ_GENERIC_LU) {
+        if (p->batch_built) return "ilu0:batch";
         if (p->flm.built) return p->flm.direct ? "ilu0:static-direct" : "ilu0:static-level-major";
         if (p->fperm) return "ilu0:level-order";
         return p->prog_f3 ? "ilu0:csr-program" : "ilu0:csr";
@@ -2704,6 +2737,12 @@ struct BatchScratch {
     RefactorDesc *h_rtable = nullptr, *d_rtable = nullptr;
     int32_t rcap = 0, rused = 0;
     hipEvent_t rup_ev = nullptr;
+    // the batched ILU(0) construction: the symbolic launch's records (device, pinned host), the create launch's status words, entries
+    // allocated, and the events around the two launches (timed)
+    CreateInfo *d_cinfo = nullptr, *h_cinfo = nullptr;
+    int32_t *d_cstat = nullptr;
+    int32_t ccap = 0;
+    hipEvent_t tev[4] = {nullptr, nullptr, nullptr, nullptr};
 };
 
 // One member as the batched kernels see it, whatever class it comes from: the object that holds the two triangles, the pivoting
@@ -2752,6 +2791,29 @@ BatchScratch &batch_scratch()
             if (!*e) ILUPP_HIP(hipEventCreateWithFlags(e, hipEventDisableTiming));
     }
     return S;
+}
+
+// the packed staging buffer of the host entries (device block and its pinned host image) with room for `total` doubles
+void batch_stage_reserve(BatchScratch &S, size_t total)
+{
+    if (total <= S.stage_cap) return;
+    if (S.d_stage) { ILUPP_HIP(hipStreamSynchronize(S.stream)); (void)hipFree(S.d_stage); (void)hipHostFree(S.h_stage); S.d_stage = nullptr; S.h_stage = nullptr; }
+    S.stage_cap = 0;
+    ILUPP_HIP(hipMalloc(reinterpret_cast<void **>(&S.d_stage), sizeof(double) * total));
+    ILUPP_HIP(hipHostMalloc(reinterpret_cast<void **>(&S.h_stage), sizeof(double) * total, hipHostMallocDefault));
+    S.stage_cap = total;
+}
+
+// the re-factorisation's descriptor table (device copy and pinned host copy) with room for nl members; the cached table goes when it grows
+void batch_rtable_reserve(BatchScratch &S, int32_t nl)
+{
+    if (nl <= S.rcap) return;
+    if (S.d_rtable) { ILUPP_HIP(hipStreamSynchronize(S.stream)); (void)hipFree(S.d_rtable); (void)hipHostFree(S.h_rtable); S.d_rtable = nullptr; S.h_rtable = nullptr; }
+    S.rcap = 0; S.rused = 0;
+    const int32_t cap = nl < 64 ? 64 : nl;
+    ILUPP_HIP(hipMalloc(reinterpret_cast<void **>(&S.d_rtable), sizeof(RefactorDesc) * (size_t)cap));
+    ILUPP_HIP(hipHostMalloc(reinterpret_cast<void **>(&S.h_rtable), sizeof(RefactorDesc) * (size_t)cap, hipHostMallocDefault));
+    S.rcap = cap;
 }
 
 // n up to which a member goes to the launch: 8 n bytes of LDS must fit (ILUPP_BATCH_APPLY_MAX_N lowers it, read per call)
@@ -3126,13 +3188,7 @@ int ilupp_hip_pivot_apply_batch(int32_t count, ilupp_ilucp *const *members, doub
     std::vector<int64_t> off((size_t)count);
     size_t total = 0;
     for (int32_t i = 0; i < count; ++i) { off[(size_t)i] = (int64_t)total; total += (size_t)len[i]; }
-    if (total > S.stage_cap) {
-        if (S.d_stage) { ILUPP_HIP(hipStreamSynchronize(S.stream)); (void)hipFree(S.d_stage); (void)hipHostFree(S.h_stage); S.d_stage = nullptr; S.h_stage = nullptr; }
-        S.stage_cap = 0;
-        ILUPP_HIP(hipMalloc(reinterpret_cast<void **>(&S.d_stage), sizeof(double) * total));
-        ILUPP_HIP(hipHostMalloc(reinterpret_cast<void **>(&S.h_stage), sizeof(double) * total, hipHostMallocDefault));
-        S.stage_cap = total;
-    }
+    batch_stage_reserve(S, total);
     for (int32_t i = 0; i < count; ++i) memcpy(S.h_stage + off[(size_t)i], x[i], sizeof(double) * (size_t)len[i]);
     ILUPP_HIP(hipMemcpyAsync(S.d_stage, S.h_stage, sizeof(double) * total, hipMemcpyHostToDevice, S.stream));
     const std::vector<BatchMember> mv = batch_members(count, members, transpose);
@@ -3238,12 +3294,12 @@ static int64_t refactor_batch_max_n()
     return cap_n;
 }
 
-int ilupp_hip_ilu0_refactor_batch_device(int32_t count, ilupp_precond *const *members, const double *const *d_data,
-                                         const int32_t *const *d_indices, const int32_t *const *d_indptr, const int64_t *nnz,
-                                         int32_t *d_status, int sync, int32_t *route)
+// what ilupp_hip_ilu0_refactor_batch_device does, under the construction lock its caller holds (the construction lock first, then the
+// batch lock: pool blocks are freed below; no path takes the two in the other order)
+static int refactor_batch_locked(int32_t count, ilupp_precond *const *members, const double *const *d_data,
+                                 const int32_t *const *d_indices, const int32_t *const *d_indptr, const int64_t *nnz,
+                                 int32_t *d_status, int sync, int32_t *route)
 {
-    // (the construction lock first, then the batch lock: pool blocks are freed below; no path takes the two in the other order)
-    API_TRY_BUILD
     const int rc0 = plain_batch_args(count, members, false, d_data, nnz);
     if (rc0) return rc0;
     if (!d_indices || !d_indptr || !d_status) { set_error("null argument"); return ILUPP_ERR_INVALID; }
@@ -3269,7 +3325,8 @@ int ilupp_hip_ilu0_refactor_batch_device(int32_t count, ilupp_precond *const *me
     for (int32_t i = 0; i < count; ++i) {
         const ilupp_precond *p = members[i];
         if (p->flm.built) { S.route[(size_t)i] = 2; continue; }
-        if (p->n > cap_n) { S.route[(size_t)i] = 1; continue; }
+        // (a member the batched construction built has no single numeric path, and fits by construction: the launch, whatever the cap says)
+        if (p->n > cap_n && !p->batch_built) { S.route[(size_t)i] = 1; continue; }
         const size_t want = ilu0_refactor_batch_fits(p->n, p->max_row_len);
         if (want == 0) { S.route[(size_t)i] = 1; continue; }
         S.launched.push_back(i);
@@ -3283,18 +3340,11 @@ int ilupp_hip_ilu0_refactor_batch_device(int32_t count, ilupp_precond *const *me
     constexpr int32_t kRefactorAloneMin = 1000;
     long long alone_min = kRefactorAloneMin;
     if (const char *e = getenv("ILUPP_REFACTOR_ALONE_MIN")) { const long long v = atoll(e); if (v > 0) alone_min = v; }
-    if (S.launched.size() == 1 && members[S.launched[0]]->n >= alone_min) { S.route[(size_t)S.launched[0]] = 1; S.launched.clear(); }
+    if (S.launched.size() == 1 && members[S.launched[0]]->n >= alone_min && !members[S.launched[0]]->batch_built) { S.route[(size_t)S.launched[0]] = 1; S.launched.clear(); }
     if (route) for (int32_t i = 0; i < count; ++i) route[i] = S.route[(size_t)i];
     const int32_t nl = (int32_t)S.launched.size();
     if (nl > 0) {
-        if (nl > S.rcap) {
-            if (S.d_rtable) { ILUPP_HIP(hipStreamSynchronize(bs)); (void)hipFree(S.d_rtable); (void)hipHostFree(S.h_rtable); S.d_rtable = nullptr; S.h_rtable = nullptr; }
-            S.rcap = 0; S.rused = 0;
-            const int32_t cap = nl < 64 ? 64 : nl;
-            ILUPP_HIP(hipMalloc(reinterpret_cast<void **>(&S.d_rtable), sizeof(RefactorDesc) * (size_t)cap));
-            ILUPP_HIP(hipHostMalloc(reinterpret_cast<void **>(&S.h_rtable), sizeof(RefactorDesc) * (size_t)cap, hipHostMallocDefault));
-            S.rcap = cap;
-        }
+        batch_rtable_reserve(S, nl);
         std::vector<RefactorDesc> fresh((size_t)nl);
         std::vector<BatchMember> mv((size_t)count);
         for (int32_t i = 0; i < count; ++i) mv[(size_t)i] = batch_member(members[i], 0);
@@ -3373,6 +3423,14 @@ int ilupp_hip_ilu0_refactor_batch_device(int32_t count, ilupp_precond *const *me
     }
     order_caller_after(bs, S.cev[1]);
     return ILUPP_OK;
+}
+
+int ilupp_hip_ilu0_refactor_batch_device(int32_t count, ilupp_precond *const *members, const double *const *d_data,
+                                         const int32_t *const *d_indices, const int32_t *const *d_indptr, const int64_t *nnz,
+                                         int32_t *d_status, int sync, int32_t *route)
+{
+    API_TRY_BUILD
+    return refactor_batch_locked(count, members, d_data, d_indices, d_indptr, nnz, d_status, sync, route);
     API_CATCH
 }
 
@@ -3380,6 +3438,272 @@ int64_t ilupp_hip_ilu0_refactor_batch_max_n(void)
 {
     API_TRY
     return refactor_batch_max_n();
+    API_CATCH
+}
+
+}  // extern "C"
+
+// ---- many ILU(0) objects built at once: a symbolic launch, one read-back, a create launch (ilu0_batch.hip) ----
+namespace {
+
+int refactor_in_launch(ilupp_precond *p, const double *d_data, const int32_t *d_indices, const int32_t *d_indptr)
+{
+    // (never reached from the batched re-factorisation, which holds the batch lock and sends such a member to its launch)
+    ilupp_precond *const one[1] = {p};
+    const double *const dd[1] = {d_data};
+    const int32_t *const di[1] = {d_indices}, *const dp[1] = {d_indptr};
+    const int64_t nz[1] = {p->nnzA};
+    const int rc = refactor_batch_locked(1, one, dd, di, dp, nz, p->ctrl + 2, 1, nullptr);      // (ctrl[2]: a word no sweep of such an object uses)
+    if (rc) {
+        const std::string prefix = "member 0 of the batch: ", msg = g_last_error;
+        if (msg.compare(0, prefix.size(), prefix) == 0) set_error(msg.substr(prefix.size()));
+    }
+    return rc;
+}
+
+// one matrix of a batched construction: device CSR arrays (the caller's, or slices of the scratch's staging block), and for the host
+// entry the host arrays they were copied from
+struct CreateMember {
+    const double *data = nullptr; const int32_t *indices = nullptr, *indptr = nullptr;
+    int32_t n = 0; int64_t nnz = 0;
+    const int32_t *h_indices = nullptr, *h_indptr = nullptr;
+};
+
+// the objects of a call until it has succeeded: whatever makes it unwind destroys them all
+struct CreatedObjects {
+    std::vector<ilupp_precond *> v;
+    ~CreatedObjects() { for (ilupp_precond *p : v) if (p) { if (p->side) (void)stream_sync(p->side); destroy_obj(p); } }
+};
+
+// What both entries of the batched ILU(0) construction do once the matrices are in device memory (count > 0; the caller holds the
+// construction lock and the batch lock).  staged: the matrices were uploaded on the scratch's stream (S.in_ev behind the upload), not
+// produced on the caller's.  Routes: 0 = built by the two launches; 1 = built by the single constructor inside this call (n above the cap
+// of the re-factorisation's launch, a longest row above its row cap, a matrix whose rows are not sorted or whose indices are out of
+// range -- whatever the single constructor does with it, it does here --, or a batch of one: a user who builds one object wants the
+// fully analysed one).  The first failing member is reported as "matrix i of the batch: ...", status[i] says which failed, and no
+// object of the call survives a failure (batch_build's convention).
+int ilu0_create_batch_run(BatchScratch &S, int32_t count, const CreateMember *m, int is_csr, bool staged, ilupp_precond **out, int32_t *status,
+                          int32_t *route)
+{
+    hipStream_t bs = S.stream;
+    if (!S.rup_ev) ILUPP_HIP(hipEventCreateWithFlags(&S.rup_ev, hipEventDisableTiming));
+    for (hipEvent_t &e : S.tev) if (!e) ILUPP_HIP(hipEventCreate(&e));
+    std::vector<int> rcs((size_t)count, ILUPP_OK);
+    std::vector<std::string> msgs((size_t)count);
+    std::vector<int32_t> rt((size_t)count, 0);
+    CreatedObjects objs;
+    objs.v.assign((size_t)count, nullptr);
+    const int64_t cap_n = refactor_batch_max_n();
+    std::vector<int32_t> cand;                       // the members of the symbolic launch
+    for (int32_t i = 0; i < count; ++i) {
+        if (m[i].n <= 0 || !m[i].indptr) { rcs[(size_t)i] = ILUPP_ERR_INVALID; msgs[(size_t)i] = "matrix has size 0!"; continue; }
+        if (m[i].nnz < 0 || m[i].nnz + (int64_t)m[i].n > INT32_MAX) { rcs[(size_t)i] = ILUPP_ERR_INVALID; msgs[(size_t)i] = "ILU0: too many stored entries for 32-bit indices"; continue; }
+        if (count == 1 || m[i].n > cap_n) { rt[(size_t)i] = 1; continue; }
+        cand.push_back(i);
+    }
+    if (!staged) order_after_caller(bs, S.cev[0]);
+    const int32_t nc = (int32_t)cand.size();
+    std::vector<int32_t> launched;                   // the members of the create launch
+    float sym_ms = 0.f, create_ms = 0.f;
+    if (nc > 0) {
+        batch_rtable_reserve(S, nc);
+        if (count > S.ccap) {
+            if (S.d_cinfo) { ILUPP_HIP(hipStreamSynchronize(bs)); (void)hipFree(S.d_cinfo); (void)hipFree(S.d_cstat); (void)hipHostFree(S.h_cinfo); S.d_cinfo = nullptr; S.d_cstat = nullptr; S.h_cinfo = nullptr; }
+            S.ccap = 0;
+            const int32_t cap = count < 64 ? 64 : count;
+            ILUPP_HIP(hipMalloc(reinterpret_cast<void **>(&S.d_cinfo), sizeof(CreateInfo) * (size_t)cap));
+            ILUPP_HIP(hipMalloc(reinterpret_cast<void **>(&S.d_cstat), sizeof(int32_t) * (size_t)cap));
+            ILUPP_HIP(hipHostMalloc(reinterpret_cast<void **>(&S.h_cinfo), sizeof(CreateInfo) * (size_t)cap, hipHostMallocDefault));
+            S.ccap = cap;
+        }
+        ILUPP_HIP(hipEventSynchronize(S.rup_ev));                       // (the upload before this one has read the pinned copy)
+        S.rused = 0;                                                    // (the re-factorisation's cached table is overwritten)
+        // the objects, and the n + 1 row pointers of L and of U the symbolic launch writes
+        for (int32_t k = 0; k < nc; ++k) {
+            const int32_t i = cand[(size_t)k];
+            ilupp_precond *p = objs.v[(size_t)i] = new_obj(m[i].n);
+            p->kind = KIND_LU; p->nnz_mode = NNZ_GENERIC_LU; p->input_csc = !is_csr;
+            for (DevMat *M : {&p->Lc, &p->Uc}) {
+                M->n = m[i].n; M->is_csr = true; M->owns = true;
+                ILUPP_HIP(pool_malloc(&M->ptr, sizeof(int32_t) * (size_t)(m[i].n + 1)));
+            }
+            RefactorDesc &d = S.h_rtable[k];
+            memset(&d, 0, sizeof(d));
+            d.aptr = m[i].indptr; d.aidx = m[i].indices; d.aval = m[i].data;
+            d.lptr = p->Lc.ptr; d.uptr = p->Uc.ptr;
+            d.nnzA = m[i].nnz; d.n = m[i].n; d.member = i;
+        }
+        ILUPP_HIP(hipMemcpyAsync(S.d_rtable, S.h_rtable, sizeof(RefactorDesc) * (size_t)nc, hipMemcpyHostToDevice, bs));
+        ILUPP_HIP(hipEventRecord(S.tev[0], bs));
+        OR_RETURN(ilu0_symbolic_batch_launch(bs, nc, S.d_rtable, S.d_cinfo));
+        ILUPP_HIP(hipEventRecord(S.tev[1], bs));
+        // the call's one host wait in front of the numeric launch: all result records with one read-back
+        ILUPP_HIP(hipMemcpyAsync(S.h_cinfo, S.d_cinfo, sizeof(CreateInfo) * (size_t)nc, hipMemcpyDeviceToHost, bs));
+        ILUPP_HIP(stream_sync(bs));
+        ILUPP_HIP(hipEventElapsedTime(&sym_ms, S.tev[0], S.tev[1]));
+        size_t lds = 0;
+        for (int32_t k = 0; k < nc; ++k) {
+            const int32_t i = cand[(size_t)k];
+            const CreateInfo &o = S.h_cinfo[k];
+            ilupp_precond *p = objs.v[(size_t)i];
+            if (o.flags & kCreateNnzDiffers) {
+                rcs[(size_t)i] = ILUPP_ERR_INVALID; msgs[(size_t)i] = "ILU0: the number of stored entries handed in is not indptr[n]";
+            } else if (o.flags & kCreateUnsorted) {
+                rt[(size_t)i] = 1;
+            } else if (o.missing >= 0) {
+                rcs[(size_t)i] = ILUPP_ERR_NO_DIAGONAL;
+                msgs[(size_t)i] = "ILU0: structurally missing diagonal entry in row " + std::to_string(o.missing);
+            } else {
+                const size_t want = ilu0_refactor_batch_fits(m[i].n, o.max_row_len);
+                if (want == 0) { rt[(size_t)i] = 1; continue; }
+                if (want > lds) lds = want;
+                // exact index and value arrays, and what the object records of the factored matrix
+                p->Lc.nnz = o.nnz_l; p->Uc.nnz = o.nnz_u;
+                for (DevMat *M : {&p->Lc, &p->Uc}) {
+                    ILUPP_HIP(pool_malloc(&M->idx, sizeof(int32_t) * (size_t)M->nnz));
+                    ILUPP_HIP(pool_malloc(&M->val, sizeof(double) * (size_t)M->nnz));
+                }
+                p->nnzA = m[i].nnz; p->max_row_len = o.max_row_len; p->csr_vals = true; p->batch_built = true;
+                launched.push_back(i);
+            }
+        }
+    }
+    bool failed = false;
+    for (int32_t i = 0; i < count; ++i) failed = failed || rcs[(size_t)i] != ILUPP_OK;
+    const int32_t nl = failed ? 0 : (int32_t)launched.size();
+    if (nl > 0) {
+        for (int32_t k = 0; k < nl; ++k) {
+            const int32_t i = launched[(size_t)k];
+            const ilupp_precond *p = objs.v[(size_t)i];
+            RefactorDesc &d = S.h_rtable[k];
+            memset(&d, 0, sizeof(d));
+            d.aptr = m[i].indptr; d.aidx = m[i].indices; d.aval = m[i].data;
+            d.lptr = p->Lc.ptr; d.lidx = p->Lc.idx; d.lval = p->Lc.val;
+            d.uptr = p->Uc.ptr; d.uidx = p->Uc.idx; d.uval = p->Uc.val;
+            d.nnzA = p->nnzA; d.n = p->n; d.member = i;
+        }
+        // (this table is what the batched re-factorisation of the same members from the same buffers describes: its cache may hit)
+        ILUPP_HIP(hipMemcpyAsync(S.d_rtable, S.h_rtable, sizeof(RefactorDesc) * (size_t)nl, hipMemcpyHostToDevice, bs));
+        ILUPP_HIP(hipEventRecord(S.rup_ev, bs));
+        S.rused = nl;
+        size_t lds = 0;
+        for (int32_t i : launched) { const size_t want = ilu0_refactor_batch_fits(m[i].n, objs.v[(size_t)i]->max_row_len); if (want > lds) lds = want; }
+        ILUPP_HIP(hipEventRecord(S.tev[2], bs));
+        OR_RETURN(ilu0_create_batch_launch(bs, nl, S.d_rtable, S.d_cstat, lds));
+        ILUPP_HIP(hipEventRecord(S.tev[3], bs));
+        // whatever a member's own stream does next (an apply, factors(), ensure_*) comes after the launch that writes its factors
+        ILUPP_HIP(hipEventRecord(S.done_ev, bs));
+        for (int32_t i : launched) ILUPP_HIP(hipStreamWaitEvent(objs.v[(size_t)i]->stream, S.done_ev, 0));
+    }
+    // route 1: the single constructor, on the member's own stream, next to the launch (it waits for its stream itself)
+    for (int32_t i = 0; i < count && !failed; ++i) {
+        if (rt[(size_t)i] != 1) continue;
+        if (objs.v[(size_t)i]) { destroy_obj(objs.v[(size_t)i]); objs.v[(size_t)i] = nullptr; }      // (it only held the two row-pointer arrays)
+        int rc;
+        if (staged) {
+            int32_t head[10];
+            host_head(m[i].h_indptr, m[i].h_indices, m[i].nnz, head);
+            ilupp_precond *made = new_obj(m[i].n);
+            if (hipStreamWaitEvent(made->stream, S.in_ev, 0) != hipSuccess) { destroy_obj(made); set_error("batched construction: no stream"); return ILUPP_ERR_HIP; }
+            rc = ilu0_create_common(borrow_csr(m[i].data, m[i].indices, m[i].indptr, m[i].n, m[i].nnz, true), is_csr, head, &objs.v[(size_t)i], made);
+        } else {
+            rc = ilu0_create_device_locked(m[i].data, m[i].indices, m[i].indptr, m[i].n, is_csr, &objs.v[(size_t)i]);
+            if (rc == ILUPP_OK && objs.v[(size_t)i]->nnzA != m[i].nnz) { rc = ILUPP_ERR_INVALID; set_error("ILU0: the number of stored entries handed in is not indptr[n]"); }
+        }
+        if (rc) { rcs[(size_t)i] = rc; msgs[(size_t)i] = g_last_error; failed = true; }
+    }
+    if (nl > 0) {
+        // a construction synchronises: the launch is over when the call returns
+        std::vector<int32_t> st((size_t)count, 0);
+        ILUPP_HIP(d2h_async(bs, st.data(), S.d_cstat, sizeof(int32_t) * (size_t)count));
+        ILUPP_HIP(stream_sync(bs));
+        ILUPP_HIP(hipEventElapsedTime(&create_ms, S.tev[2], S.tev[3]));
+        for (int32_t i : launched) {
+            ilupp_precond *p = objs.v[(size_t)i];
+            if (st[(size_t)i] == 2) { rcs[(size_t)i] = ILUPP_ERR_TIMEOUT; msgs[(size_t)i] = "ILU0: dependency wait timed out (invalid structure?)"; }
+            else if (st[(size_t)i] != 0) { rcs[(size_t)i] = ILUPP_ERR_INVALID; msgs[(size_t)i] = "ILU0: the matrix changed while it was factored"; }
+            // (the two launches' times, shared by the call's members)
+            p->tm.analysis_ms = sym_ms; p->tm.numeric_ms = create_ms; p->tm.numeric_kernel_ms = create_ms;
+        }
+    }
+    if (route) for (int32_t i = 0; i < count; ++i) route[i] = rt[(size_t)i];
+    int first = ILUPP_OK;
+    for (int32_t i = 0; i < count; ++i) {
+        if (status) status[i] = rcs[(size_t)i];
+        if (rcs[(size_t)i] && !first) { first = rcs[(size_t)i]; set_error("matrix " + std::to_string(i) + " of the batch: " + msgs[(size_t)i]); }
+    }
+    if (first) return first;                         // (objs goes, and every object of the call with it)
+    for (int32_t i = 0; i < count; ++i) { out[i] = objs.v[(size_t)i]; objs.v[(size_t)i] = nullptr; }
+    return ILUPP_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int ilupp_hip_ilu0_create_batch_device(int32_t count, const double *const *d_data, const int32_t *const *d_indices,
+                                       const int32_t *const *d_indptr, const int32_t *n, const int64_t *nnz, int is_csr, ilupp_precond **out,
+                                       int32_t *status, int32_t *route)
+{
+    API_TRY_BUILD
+    if (count < 0 || !d_data || !d_indices || !d_indptr || !n || !nnz || !out) { set_error("null argument"); return ILUPP_ERR_INVALID; }
+    for (int32_t i = 0; i < count; ++i) { out[i] = nullptr; if (status) status[i] = ILUPP_OK; if (route) route[i] = 0; }
+    std::vector<CreateMember> m((size_t)count);
+    for (int32_t i = 0; i < count; ++i) {
+        if (n[i] > 0 && (!d_data[i] || !d_indices[i] || !d_indptr[i])) { set_error("null argument"); return ILUPP_ERR_INVALID; }
+        m[(size_t)i].data = d_data[i]; m[(size_t)i].indices = d_indices[i]; m[(size_t)i].indptr = d_indptr[i];
+        m[(size_t)i].n = n[i]; m[(size_t)i].nnz = nnz[i];
+    }
+    if (count == 0) return ILUPP_OK;
+    std::lock_guard<std::mutex> lk(g_batch_mu);
+    return ilu0_create_batch_run(batch_scratch(), count, m.data(), is_csr, false, out, status, route);
+    API_CATCH
+}
+
+int ilupp_hip_ilu0_create_batch(int32_t count, const double *const *data, const int32_t *const *indices, const int32_t *const *indptr,
+                                const int32_t *n, int is_csr, ilupp_precond **out, int32_t *status, int32_t *route)
+{
+    API_TRY_BUILD
+    if (count < 0 || !data || !indices || !indptr || !n || !out) { set_error("null argument"); return ILUPP_ERR_INVALID; }
+    for (int32_t i = 0; i < count; ++i) { out[i] = nullptr; if (status) status[i] = ILUPP_OK; if (route) route[i] = 0; }
+    for (int32_t i = 0; i < count; ++i)
+        if (n[i] > 0 && (!data[i] || !indices[i] || !indptr[i])) { set_error("null argument"); return ILUPP_ERR_INVALID; }
+    if (count == 0) return ILUPP_OK;
+    std::lock_guard<std::mutex> lk(g_batch_mu);
+    BatchScratch &S = batch_scratch();
+    // all members through ONE packed block, one upload: per member its values, then its indices and its row pointers (each padded to 8 bytes)
+    std::vector<CreateMember> m((size_t)count);
+    std::vector<size_t> at((size_t)count);
+    size_t total = 0;
+    auto words = [](int64_t ints) { return (size_t)((ints + 1) / 2); };
+    for (int32_t i = 0; i < count; ++i) {
+        m[(size_t)i].n = n[i];
+        if (n[i] <= 0) continue;
+        const int64_t nz = indptr[i][n[i]];
+        m[(size_t)i].nnz = nz;
+        if (nz < 0 || nz + (int64_t)n[i] > INT32_MAX) continue;      // (refused per member below; nothing of it is staged)
+        at[(size_t)i] = total;
+        total += (size_t)nz + words(nz) + words((int64_t)n[i] + 1);
+    }
+    batch_stage_reserve(S, total > 0 ? total : 1);
+    for (int32_t i = 0; i < count; ++i) {
+        CreateMember &c = m[(size_t)i];
+        if (c.n <= 0 || c.nnz < 0 || c.nnz + (int64_t)c.n > INT32_MAX) continue;
+        const size_t nz = (size_t)c.nnz, o_idx = at[(size_t)i] + nz, o_ptr = o_idx + words(c.nnz);
+        memcpy(S.h_stage + at[(size_t)i], data[i], sizeof(double) * nz);
+        memcpy(S.h_stage + o_idx, indices[i], sizeof(int32_t) * nz);
+        memcpy(S.h_stage + o_ptr, indptr[i], sizeof(int32_t) * ((size_t)c.n + 1));
+        c.data = S.d_stage + at[(size_t)i];
+        c.indices = reinterpret_cast<const int32_t *>(S.d_stage + o_idx);
+        c.indptr = reinterpret_cast<const int32_t *>(S.d_stage + o_ptr);
+        c.h_indices = indices[i]; c.h_indptr = indptr[i];
+    }
+    if (total > 0) ILUPP_HIP(hipMemcpyAsync(S.d_stage, S.h_stage, sizeof(double) * total, hipMemcpyHostToDevice, S.stream));
+    ILUPP_HIP(hipEventRecord(S.in_ev, S.stream));
+    const int rc = ilu0_create_batch_run(S, count, m.data(), is_csr, true, out, status, route);
+    // (the staged matrices are read by nothing once the call is over: every member's construction has been waited for)
+    if (rc) (void)hipStreamSynchronize(S.stream);
+    return rc;
     API_CATCH
 }
 

@@ -610,10 +610,12 @@ int solve_batch_launch(BatchSolver s, hipStream_t st, int32_t count, const Pivot
 // the analysed pattern has, and the member's status word (0 = re-factorised, 1 = the matrix does not have the analysed pattern: nothing
 // was written, 2 = a dependency wait gave up; word `member` of the launch's status array, which is no part of the descriptor, so that the
 // table's upload is skipped whenever the same members come with their matrices in the same buffers).
+// (The launches of a batched FIRST construction take the same descriptor: k_ilu0_symbolic_batch writes the two row-pointer arrays,
+// k_ilu0_create_batch the two index arrays and then the values; the re-factorisation only reads the four.)
 struct RefactorDesc {
     const int32_t *aptr, *aidx; const double *aval;
-    const int32_t *lptr, *lidx; double *lval;
-    const int32_t *uptr, *uidx; double *uval;
+    int32_t *lptr, *lidx; double *lval;
+    int32_t *uptr, *uidx; double *uval;
     int64_t nnzA;
     int32_t n, member;
 };
@@ -622,6 +624,16 @@ int64_t ilu0_refactor_batch_max_n();     // the largest n of a member of that la
 // ROW CAP: longest row > 31 entries, or flags and rows do not fit (longest row <= (cap - 4 n) / 5 120)
 size_t ilu0_refactor_batch_fits(int32_t n, int32_t max_row_len);
 int ilu0_refactor_batch_launch(hipStream_t st, int32_t count, const RefactorDesc *d_table, int32_t *d_status, size_t lds_bytes);      // lds_bytes: the largest fits()
+// The batched first construction (same file).  What the symbolic launch leaves per member: the entries of L (unit diagonal counted) and
+// of U, the longest row of A, the first row without a diagonal entry or -1, and the flags: kCreateUnsorted = a row pointer outside
+// 0 <= aptr[r] <= aptr[r + 1] <= nnzA, or a row whose column indices are not strictly ascending inside [0, n) (the member goes to the
+// single constructor); kCreateNnzDiffers = aptr[n] is not the number of stored entries the caller named.
+enum { kCreateUnsorted = 1, kCreateNnzDiffers = 2 };
+struct CreateInfo { int32_t nnz_l, nnz_u, max_row_len, missing, flags, pad[3]; };
+int ilu0_symbolic_batch_launch(hipStream_t st, int32_t count, const RefactorDesc *d_table, CreateInfo *d_info);      // member k's record: d_info[k]
+// the patterns of L and U in the single constructor's layout, then the factorisation by the re-factorisation's device function; status as
+// ilu0_refactor_batch_launch's (1: the matrix is no longer the one the symbolic launch read); lds_bytes: the largest fits()
+int ilu0_create_batch_launch(hipStream_t st, int32_t count, const RefactorDesc *d_table, int32_t *d_status, size_t lds_bytes);
 
 // sptrsv_lvl.hip
 bool lvl_order(hipStream_t st, int mode, int32_t n, int64_t nnz, const int32_t *ptr, const int32_t *idx, const Schedule &sch,

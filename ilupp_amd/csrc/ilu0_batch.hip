@@ -36,6 +36,19 @@
 // of microseconds at the worst, against an idle limit of 2^20 trips of a waiting wave (tenths of a second).
 //
 // LDS: 4 n bytes of flags, then 5 120 bytes per entry of the longest row (dynamic); four words static.
+//
+// FIRST CONSTRUCTION of many members (ilupp_hip_ilu0_create_batch*): two more launches of one workgroup per member around one read-back.
+//   k_ilu0_symbolic_batch reads A's pattern row by row -- 0 <= aptr[r] <= aptr[r + 1] <= nnzA before an index is read through them, column
+//     indices strictly ascending inside [0, n), the diagonal present --, counts the strictly-lower and the diagonal-plus-upper entries and
+//     writes L's and U's row pointers with a workgroup-wide running scan over the rows (256 rows a round, the carry in registers; L's rows
+//     carry one entry more, the unit diagonal).  It leaves a CreateInfo per member: nnz(L), nnz(U), the longest row, the first row without
+//     a diagonal, and the flags that send the member to the single constructor or refuse it.
+//   k_ilu0_create_batch, once the host has allocated the exact index and value arrays: the two patterns in the layout ilu0_write_patterns /
+//     ilu0_unit_diagonal leave (L strictly lower ascending, the unit diagonal last; U the diagonal first, then ascending), a workgroup
+//     barrier that makes them visible to the workgroup's other waves, and then pass 2 above on the member -- refactor_member, the same
+//     device function with the same LDS layout, row cap, bounded waits and status words as k_ilu0_refactor_batch.
+#include <limits.h>
+
 #include "common.h"
 
 namespace ilupp {
@@ -158,6 +171,27 @@ __device__ __forceinline__ void refactor_rows(const RefactorDesc &d, int *rf_don
     }
 }
 
+// pass 2 for one member whose pattern is proved (or was just written), behind a workgroup barrier: the LDS behind the flags carved into the
+// lanes' working rows, the rows factored, the member's status word written.  What k_ilu0_refactor_batch and k_ilu0_create_batch share.
+__device__ __forceinline__ void refactor_member(const RefactorDesc &d, unsigned char *rf_lds, unsigned lds_bytes, int maxlen, int32_t *status,
+                                                unsigned *s_progress, int *s_fail)
+{
+    const int n = d.n, tid = threadIdx.x;
+    int *rf_done = reinterpret_cast<int *>(rf_lds);
+    const size_t fb = rf_flag_bytes(n), rows = (size_t)maxlen * kRfRowBytes;
+    if (maxlen > kRfMaxRow || fb + rows > (size_t)lds_bytes) {
+        // (a row above the cap: the host launches no such member -- its routing reads the longest row the analysis recorded; no value was written)
+        if (tid == 0) status[d.member] = 2;
+        return;
+    }
+    double *wv = reinterpret_cast<double *>(rf_lds + fb);
+    int *wc = reinterpret_cast<int *>(wv + (size_t)maxlen * kRfThreads);
+    int *wk0 = wc + (size_t)maxlen * kRfThreads, *wkl = wk0 + (size_t)maxlen * kRfThreads;
+    refactor_rows(d, rf_done, wv, wc, wk0, wkl, s_progress, s_fail);
+    __syncthreads();
+    if (tid == 0) status[d.member] = *s_fail != 0 ? 2 : 0;
+}
+
 __global__ void __launch_bounds__(kRfThreads)
 k_ilu0_refactor_batch(const RefactorDesc *__restrict__ table, int32_t *__restrict__ status, const unsigned lds_bytes)
 {
@@ -198,23 +232,137 @@ k_ilu0_refactor_batch(const RefactorDesc *__restrict__ table, int32_t *__restric
         return;
     }
 
-    // ---- pass 2: the factorisation ----
-    const size_t fb = rf_flag_bytes(n), rows = (size_t)s_maxlen * kRfRowBytes;
-    if (s_maxlen > kRfMaxRow || fb + rows > (size_t)lds_bytes) {
-        // (a row above the cap: the host launches no such member -- its routing reads the longest row the analysis recorded; nothing was written)
-        if (tid == 0) status[d.member] = 2;
+    refactor_member(d, rf_lds, lds_bytes, s_maxlen, status, &s_progress, &s_fail);
+}
+
+// ---- first construction: the symbolic launch ----
+typedef RF_HBM int32_t *rf_int;
+
+__global__ void __launch_bounds__(kRfThreads)
+k_ilu0_symbolic_batch(const RefactorDesc *__restrict__ table, CreateInfo *__restrict__ info)
+{
+    __shared__ int s_wl[kRfThreads / 64], s_wu[kRfThreads / 64];                // the waves' totals of one round of the scan
+    __shared__ int s_missing, s_flags, s_maxlen;
+    const RefactorDesc d = table[blockIdx.x];
+    const int n = d.n, tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+    const rf_cint aptr = (rf_cint)d.aptr, aidx = (rf_cint)d.aidx;
+    const rf_int lptr = (rf_int)d.lptr, uptr = (rf_int)d.uptr;
+    if (tid == 0) { s_missing = INT_MAX; s_flags = 0; s_maxlen = 0; lptr[0] = 0; uptr[0] = 0; }
+    bool bad = false;
+    int maxlen = 0, missing = INT_MAX;
+    int carry_l = 0, carry_u = 0;                    // entries of L and of U in the rows of the rounds before
+    for (int base = 0; base < n; base += kRfThreads) {
+        const int r = base + tid;
+        int nl = 0, nu = 0;                          // row r's entries in L (the unit diagonal counted) and in U
+        if (r < n) {
+            const int a0 = aptr[r], a1 = aptr[r + 1];
+            nl = 1;
+            if (a0 < 0 || a1 < a0 || (int64_t)a1 > d.nnzA) {
+                bad = true;                          // (nothing is read through such extents)
+            } else {
+                const int len = a1 - a0;
+                int cl = 0, prev = -1;
+                bool diag = false;
+                for (int q0 = 0; q0 < len; q0 += kRG) {      // (kRG entries' loads in flight together)
+                    int c[kRG];
+#pragma unroll
+                    for (int q = 0; q < kRG; ++q) if (q0 + q < len) c[q] = aidx[a0 + q0 + q];
+#pragma unroll
+                    for (int q = 0; q < kRG; ++q)
+                        if (q0 + q < len) {
+                            bad |= c[q] <= prev || c[q] >= n;              // (prev >= -1: a negative index is caught too)
+                            cl += c[q] < r ? 1 : 0;
+                            diag |= c[q] == r;
+                            prev = c[q];
+                        }
+                }
+                nl = cl + 1; nu = len - cl;
+                if (!diag) missing = min(missing, r);
+                maxlen = max(maxlen, len);
+            }
+        }
+        int xl = nl, xu = nu;                        // inclusive scan over the wave, then over the waves' totals
+#pragma unroll
+        for (int off = 1; off < 64; off <<= 1) {
+            const int tl = __shfl_up(xl, off), tu = __shfl_up(xu, off);
+            if (lane >= off) { xl += tl; xu += tu; }
+        }
+        if (lane == 63) { s_wl[w] = xl; s_wu[w] = xu; }
+        __syncthreads();
+        int before_l = 0, before_u = 0, all_l = 0, all_u = 0;
+#pragma unroll
+        for (int k = 0; k < kRfThreads / 64; ++k) {
+            if (k < w) { before_l += s_wl[k]; before_u += s_wu[k]; }
+            all_l += s_wl[k]; all_u += s_wu[k];
+        }
+        if (r < n) { lptr[r + 1] = carry_l + before_l + xl; uptr[r + 1] = carry_u + before_u + xu; }
+        carry_l += all_l; carry_u += all_u;
+        __syncthreads();                             // (the totals are read: the next round may write them)
+    }
+    if (bad) atomicOr(&s_flags, kCreateUnsorted);
+    atomicMin(&s_missing, missing);
+    atomicMax(&s_maxlen, maxlen);
+    __syncthreads();
+    if (tid == 0) {
+        CreateInfo o;
+        o.nnz_l = carry_l; o.nnz_u = carry_u; o.max_row_len = s_maxlen;
+        o.missing = s_missing == INT_MAX ? -1 : s_missing;
+        o.flags = s_flags | ((int64_t)aptr[n] != d.nnzA ? kCreateNnzDiffers : 0);
+        o.pad[0] = o.pad[1] = o.pad[2] = 0;
+        info[blockIdx.x] = o;
+    }
+}
+
+// ---- first construction: the patterns, then the factorisation ----
+__global__ void __launch_bounds__(kRfThreads)
+k_ilu0_create_batch(const RefactorDesc *__restrict__ table, int32_t *__restrict__ status, const unsigned lds_bytes)
+{
+    extern __shared__ __attribute__((aligned(16))) unsigned char rf_lds[];
+    __shared__ unsigned s_progress;
+    __shared__ int s_fail, s_bad, s_maxlen;
+    const RefactorDesc d = table[blockIdx.x];
+    const int n = d.n, tid = threadIdx.x;
+    int *rf_done = reinterpret_cast<int *>(rf_lds);
+    if (tid == 0) { s_progress = 0; s_fail = 0; s_maxlen = 0; s_bad = 0; }
+    for (int i = tid; i < n; i += kRfThreads) rf_done[i] = 0;
+    const rf_cint aptr = (rf_cint)d.aptr, aidx = (rf_cint)d.aidx, lptr = (rf_cint)d.lptr, uptr = (rf_cint)d.uptr;
+    const rf_int lidx = (rf_int)d.lidx, uidx = (rf_int)d.uidx;
+    bool bad = false;
+    int maxlen = 0;
+    for (int r = tid; r < n; r += kRfThreads) {
+        const int a0 = aptr[r], a1 = aptr[r + 1];
+        const int l0 = lptr[r], cl = lptr[r + 1] - l0 - 1, u0 = uptr[r], ul = uptr[r + 1] - u0;
+        // (the row pointers are the symbolic launch's; a matrix that is no longer the one it read writes nothing)
+        if (a0 < 0 || a1 < a0 || (int64_t)a1 > d.nnzA || cl < 0 || ul < 1 || a1 - a0 != cl + ul) { bad = true; continue; }
+        for (int q0 = 0; q0 < cl + ul; q0 += kRG) {  // (kRG entries' loads in flight together)
+            int c[kRG];
+#pragma unroll
+            for (int q = 0; q < kRG; ++q) if (q0 + q < cl + ul) c[q] = aidx[a0 + q0 + q];
+#pragma unroll
+            for (int q = 0; q < kRG; ++q)
+                if (q0 + q < cl + ul) { if (q0 + q < cl) lidx[l0 + q0 + q] = c[q]; else uidx[u0 + (q0 + q - cl)] = c[q]; }
+        }
+        lidx[l0 + cl] = r;                           // L's unit diagonal comes last (ILU0.hpp:93)
+        maxlen = max(maxlen, a1 - a0);
+    }
+    __syncthreads();                                 // (thread 0's words and the flags are there)
+    if (bad) __hip_atomic_store(&s_bad, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+    atomicMax(&s_maxlen, maxlen);
+    __syncthreads();                                 // (... and the patterns, for the workgroup's other waves: refactor_rows reads uidx of other lanes' rows)
+    if (s_bad != 0) {
+        if (tid == 0) status[d.member] = 1;
         return;
     }
-    double *wv = reinterpret_cast<double *>(rf_lds + fb);
-    int *wc = reinterpret_cast<int *>(wv + (size_t)s_maxlen * kRfThreads);
-    int *wk0 = wc + (size_t)s_maxlen * kRfThreads, *wkl = wk0 + (size_t)s_maxlen * kRfThreads;
-    refactor_rows(d, rf_done, wv, wc, wk0, wkl, &s_progress, &s_fail);
-    __syncthreads();
-    if (tid == 0) status[d.member] = s_fail != 0 ? 2 : 0;
+    refactor_member(d, rf_lds, lds_bytes, s_maxlen, status, &s_progress, &s_fail);
 }
 
 // bytes of dynamic LDS one workgroup of k_ilu0_refactor_batch may take on the current device
-static size_t ilu0_refactor_batch_lds_cap() { return kernel_lds_cap<k_ilu0_refactor_batch>(); }
+// (... and of k_ilu0_create_batch, which has the same static words: the smaller of the two, so that one routing serves both launches)
+static size_t ilu0_refactor_batch_lds_cap()
+{
+    const size_t a = kernel_lds_cap<k_ilu0_refactor_batch>(), b = kernel_lds_cap<k_ilu0_create_batch>();
+    return a < b ? a : b;
+}
 
 // the largest n of a member of the launch: its flags and working rows of kRfMinRow entries fit (a member of that n with longer rows does not)
 static constexpr int kRfMinRow = 8;
@@ -239,6 +387,25 @@ int ilu0_refactor_batch_launch(hipStream_t st, int32_t count, const RefactorDesc
     if (count <= 0) return ILUPP_OK;
     if (lds_bytes > ilu0_refactor_batch_lds_cap()) return ILUPP_ERR_UNSUPPORTED;
     hipLaunchKernelGGL(k_ilu0_refactor_batch, dim3((unsigned)count), dim3(kRfThreads), lds_bytes, st, d_table, d_status, (unsigned)lds_bytes);
+    ILUPP_HIP(hipGetLastError());
+    return ILUPP_OK;
+}
+
+// the symbolic launch of a batched first construction: member k's record goes to d_info[k]
+int ilu0_symbolic_batch_launch(hipStream_t st, int32_t count, const RefactorDesc *d_table, CreateInfo *d_info)
+{
+    if (count <= 0) return ILUPP_OK;
+    hipLaunchKernelGGL(k_ilu0_symbolic_batch, dim3((unsigned)count), dim3(kRfThreads), 0, st, d_table, d_info);
+    ILUPP_HIP(hipGetLastError());
+    return ILUPP_OK;
+}
+
+// its create launch: as ilu0_refactor_batch_launch (status 1: the matrix is not the one the symbolic launch read, nothing was written)
+int ilu0_create_batch_launch(hipStream_t st, int32_t count, const RefactorDesc *d_table, int32_t *d_status, size_t lds_bytes)
+{
+    if (count <= 0) return ILUPP_OK;
+    if (lds_bytes > ilu0_refactor_batch_lds_cap()) return ILUPP_ERR_UNSUPPORTED;
+    hipLaunchKernelGGL(k_ilu0_create_batch, dim3((unsigned)count), dim3(kRfThreads), lds_bytes, st, d_table, d_status, (unsigned)lds_bytes);
     ILUPP_HIP(hipGetLastError());
     return ILUPP_OK;
 }

@@ -142,6 +142,38 @@ class DevicePreconditioner:
         self.n = A.n
         self.shape = A.shape
 
+    @classmethod
+    def batch(cls, kind, As):
+        """``[DevicePreconditioner(kind, A) for A in As]`` from ONE native call, for MANY SMALL matrices: ``As`` is a list of DeviceCSR,
+        ``kind`` must be "ILU0" (the one class whose pattern does not depend on the values and which has a re-factorisation to share a
+        kernel with).  Two kernel launches of one workgroup per matrix around one read-back (ilupp_hip_ilu0_create_batch_device) where
+        the loop pays the single constructor's analysis and host waits per object; factors and every apply of a member have the bits
+        of the singly built object.  The members go into ``apply_batch_`` / ``cg_batch`` / ``bicgstab_batch`` / ``refactor_batch_``
+        (always route 0 there) as they are; the tables of the single ``apply_`` are built at a member's first one, and ``refactor_``
+        runs the batched launch with that one member.  A matrix above the launches' caps (n above
+        ``_native.ilu0_refactor_batch_max_n()``, a row of more than 31 entries), one with an unsorted row, and a batch of one are built
+        by the single constructor inside the same call.  Ordered on torch's current stream; the call returns when every member is
+        built.  A matrix without a diagonal entry in some row raises the constructor's RuntimeError, named by its number, and no object
+        is returned.  NotImplementedError for any other kind, TypeError for a member that is not a DeviceCSR -- before any native call;
+        an empty list gives ``[]``."""
+        if kind != "ILU0":
+            raise NotImplementedError("DevicePreconditioner.batch: only the \"ILU0\" kind has a batched construction, not %s" % (kind,))
+        As = list(As)
+        for A in As:
+            if not isinstance(A, DeviceCSR):
+                raise TypeError("DevicePreconditioner.batch takes DeviceCSR matrices, got %s" % type(A).__name__)
+        if not As:
+            return []
+        _on_current_stream()
+        natives = _native.ILU0Preconditioner_batch_device(
+            [(A.data.data_ptr(), A.indices.data_ptr(), A.indptr.data_ptr(), A.n, A.nnz) for A in As], True)
+        out = []
+        for A, pr in zip(As, natives):
+            M = cls.__new__(cls)
+            M.pr, M.kind, M.n, M.shape = pr, kind, A.n, A.shape
+            out.append(M)
+        return out
+
     def apply_(self, x, transpose=False):
         """in place on a contiguous fp64 device tensor; asynchronous, ordered on torch's current stream.  A tensor of shape (n, k) is
         k right-hand sides, solved in one block apply (every column as apply_ on that column gives it; not for the "ILUpp" kind)"""
@@ -488,8 +520,9 @@ def refactor_batch_(members, As, check=True):
     members still hold copies of the old values -- the packed sweeps a construction leaves, the packed / transposed / level-ordered
     sweeps of single or block applies -- waits once for its launch before it frees them, whatever the members' statuses turn out to be.  TypeError for a member of
     another kind or class, a pivoting member, the multilevel class or a matrix that is not a DeviceCSR; ValueError for lists of unequal
-    length, a member named twice or a matrix and a member of different dimensions -- before any native call.  Out of scope: the other
-    classes (no single re-factorisation to match), a batched FIRST construction, host (numpy) matrices."""
+    length, a member named twice or a matrix and a member of different dimensions -- before any native call.  The batched FIRST
+    construction of such members: ``DevicePreconditioner.batch("ILU0", As)`` / ``ilupp_amd.ILU0Preconditioner.batch`` (members built
+    that way always take route 0 here).  Out of scope: the other classes (no single re-factorisation to match), host (numpy) matrices."""
     members, As = list(members), list(As)
     for A in As:
         if not isinstance(A, DeviceCSR):
@@ -540,7 +573,8 @@ def cg_batch(As, b, offsets, Ms, x0=None, maxiter=100, rtol=0.0, check_every=0, 
     or 2.  ValueError for a wrong tensor, lists of unequal length, a slice outside ``b`` or a matrix and a preconditioner of different
     dimensions; TypeError for a member of another class -- before any native call.  Out of scope: the multilevel class, pivoting members
     (``bicgstab_batch``, which takes them next to everything this function takes, for nonsymmetric systems), k > 1 right-hand sides
-    per member, host (numpy) vectors, a batched construction of the non-pivoting classes."""
+    per member, host (numpy) vectors, a batched construction of the non-pivoting classes other than ILU(0)
+    (``DevicePreconditioner.batch("ILU0", As)`` builds such members with two launches)."""
     As, Ms, offsets = list(As), list(Ms), [int(o) for o in offsets]
     for A in As:
         if not isinstance(A, DeviceCSR):

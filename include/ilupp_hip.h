@@ -499,6 +499,29 @@ int ilupp_hip_ilu0_refactor_batch_device(int32_t count, ilupp_precond *const *me
 /* the largest n that takes route 0 in ilupp_hip_ilu0_refactor_batch_device on the current device (ILUPP_BATCH_APPLY_MAX_N applied);
  * negative: an error code */
 int64_t ilupp_hip_ilu0_refactor_batch_max_n(void);
+/* The FIRST construction of MANY small ILU(0) objects at once: a symbolic launch and a create launch of one workgroup per member
+ * (k_ilu0_symbolic_batch, k_ilu0_create_batch: ilu0_batch.hip) around ONE read-back, where a loop of ilupp_hip_ilu0_create* pays the single
+ * path's analysis and host waits per object.  ilupp_hip_ilu0_create_batch takes host CSR arrays (all members are staged through one packed
+ * block with one upload), ilupp_hip_ilu0_create_batch_device host arrays of `count` DEVICE pointers, n[i] and nnz[i] (member i's number
+ * of stored entries; a member whose indptr[n] differs is refused).  is_csr as for ilupp_hip_ilu0_create (CSC input: the row-major view
+ * is factored).  out: `count` handles (ilupp_hip_destroy); status (may be NULL): member i's code; route (may be NULL): 0 = built by the
+ * launches, 1 = built by ilupp_hip_ilu0_create* inside the same call -- n above ilupp_hip_ilu0_refactor_batch_max_n(), a longest row
+ * above the row cap of ilupp_hip_ilu0_refactor_batch_device, a matrix with an unsorted row or an index out of range (whatever the single
+ * constructor does with it happens here), or a batch of ONE member (who builds one object wants the fully analysed one).
+ * A route-0 object holds L and U as CSR triangles with their values and none of the single paths' analysis: factors, total_nnz and every
+ * apply have the bits of ilupp_hip_ilu0_create's object, ilupp_hip_path is "ilu0:batch", the batched launches (ilupp_hip_apply_batch_device,
+ * ilupp_hip_cg_batch_device, ilupp_hip_bicgstab_batch_device, ilupp_hip_ilu0_refactor_batch_device: always route 0 there) take it as it is,
+ * the tables of the single sweeps are built at its first single apply, ilupp_hip_ilu0_refactor_device runs the batched launch with that one
+ * member, and ilupp_hip_get_timings reports the two launches' times (analysis_ms, numeric_ms), shared by the call's members.
+ * The launches run on the library's batch stream behind the caller's (ilupp_hip_set_caller_stream); the call returns when every member is
+ * built.  A member that fails fails as its single construction does ("matrix i of the batch: ILU0: structurally missing diagonal entry in
+ * row r"): the first failure is returned, status[i] says which members failed, every object of the call is destroyed and no handle is
+ * returned.  count == 0 returns ILUPP_OK without touching the device. */
+int ilupp_hip_ilu0_create_batch(int32_t count, const double *const *data, const int32_t *const *indices, const int32_t *const *indptr,
+                                const int32_t *n, int is_csr, ilupp_precond **out, int32_t *status, int32_t *route);
+int ilupp_hip_ilu0_create_batch_device(int32_t count, const double *const *d_data, const int32_t *const *d_indices,
+                                       const int32_t *const *d_indptr, const int32_t *n, const int64_t *nnz, int is_csr, ilupp_precond **out,
+                                       int32_t *status, int32_t *route);
 
 /* ---------------------------------------------------------------------------------------------
  * Measurement hooks used by bench.py (not part of the reference's surface).
@@ -514,7 +537,7 @@ typedef struct {
 } ilupp_timings;
 int ilupp_hip_get_timings(const ilupp_precond *p, ilupp_timings *t);
 /* which kernel family built this object ("ilu0:static-direct", "ilu0:static-level-major", "ilu0:level-order",
- * "ilu0:csr-program", "ilu0:csr", "ilut", "ichol0", "icholt"): bench.py names the kernel its roofline line is about */
+ * "ilu0:csr-program", "ilu0:csr", "ilu0:batch", "ilut", "ichol0", "icholt"): bench.py names the kernel its roofline line is about */
 const char *ilupp_hip_path(const ilupp_precond *p);
 /* how the row blocks of an ILU(0) object were found: "grid" (the pattern is a lexicographic box-grid stencil: guessed from row 0, proven
  * for every row by one streaming pass next to the lane-table kernels, grid.hip) or "general" (the pass over the pattern that finds the
