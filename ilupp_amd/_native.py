@@ -982,21 +982,26 @@ def pivot_apply_batch(members, arrays, transpose):
     return list(route)
 
 
-def pivot_apply_batch_device(members, dptr, offsets, transpose=False, sync=True):
-    """the same on device vectors: member k's vector starts `offsets[k]` doubles behind `dptr` (ilupp_hip_pivot_apply_batch_device),
-    ordered on the caller's stream (set_caller_stream); returns the routes"""
+def _apply_batch_device(entry, handles, members, dptr, offsets, transpose, sync):
+    """one call of a batched device apply's C entry (by name) with the handle array `handles(members)`; returns the routes"""
     cnt = len(members)
     if len(offsets) != cnt:
         raise ValueError("%d preconditioners but %d offsets" % (cnt, len(offsets)))
     if cnt == 0:
         return []
-    H = _member_handles(members)
+    H = handles(members)
     O = (ctypes.c_int64 * cnt)(*[int(o) for o in offsets])
     route = (ctypes.c_int32 * cnt)()
-    rc = lib().ilupp_hip_pivot_apply_batch_device(cnt, H, dptr, O, 1 if transpose else 0, 1 if sync else 0, route)
+    rc = getattr(lib(), entry)(cnt, H, dptr, O, 1 if transpose else 0, 1 if sync else 0, route)
     if rc:
         _raise(rc)
     return list(route)
+
+
+def pivot_apply_batch_device(members, dptr, offsets, transpose=False, sync=True):
+    """the same on device vectors: member k's vector starts `offsets[k]` doubles behind `dptr` (ilupp_hip_pivot_apply_batch_device),
+    ordered on the caller's stream (set_caller_stream); returns the routes"""
+    return _apply_batch_device("ilupp_hip_pivot_apply_batch_device", _member_handles, members, dptr, offsets, transpose, sync)
 
 
 def _matrix_arrays(matrices):
@@ -1040,12 +1045,17 @@ def pivot_bicgstab_batch_device(members, matrices, b_ptr, x0_ptr, x_ptr, offsets
                         work_ptr, work_doubles, maxiter, rtol, check_every, iterations_ptr, flags_ptr, rr_ptr, init_ptr, sync)
 
 
-def pivot_apply_batch_max_n():
-    """the largest n a member may have to take the batched launch on the current device (ILUPP_BATCH_APPLY_MAX_N applied)"""
-    v = int(lib().ilupp_hip_pivot_apply_batch_max_n())
+def _batch_max_n(entry):
+    """what a C entry (by name) gives as the largest n of a member of its launch; a negative value is an error code"""
+    v = int(getattr(lib(), entry)())
     if v < 0:
         _raise(v)
     return v
+
+
+def pivot_apply_batch_max_n():
+    """the largest n a member may have to take the batched launch on the current device (ILUPP_BATCH_APPLY_MAX_N applied)"""
+    return _batch_max_n("ilupp_hip_pivot_apply_batch_max_n")
 
 
 def _plain_handles(members, none_ok=False):
@@ -1066,18 +1076,7 @@ def apply_batch_device(members, dptr, offsets, transpose=False, sync=True):
     for all members that fit (ilupp_hip_apply_batch_device): member k's vector starts `offsets[k]` doubles behind `dptr`; ordered on the
     caller's stream (set_caller_stream); returns the routes (0 = the launch, 1 = too large, 2 = a factor with an empty row: the single
     apply inside the same call)"""
-    cnt = len(members)
-    if len(offsets) != cnt:
-        raise ValueError("%d preconditioners but %d offsets" % (cnt, len(offsets)))
-    if cnt == 0:
-        return []
-    H = _plain_handles(members)
-    O = (ctypes.c_int64 * cnt)(*[int(o) for o in offsets])
-    route = (ctypes.c_int32 * cnt)()
-    rc = lib().ilupp_hip_apply_batch_device(cnt, H, dptr, O, 1 if transpose else 0, 1 if sync else 0, route)
-    if rc:
-        _raise(rc)
-    return list(route)
+    return _apply_batch_device("ilupp_hip_apply_batch_device", _plain_handles, members, dptr, offsets, transpose, sync)
 
 
 def cg_batch_device(members, ns, matrices, b_ptr, x0_ptr, x_ptr, offsets, work_ptr, work_doubles, maxiter, rtol, check_every,
@@ -1117,18 +1116,12 @@ def ilu0_refactor_batch_device(members, matrices, status_ptr, sync=True):
 
 def ilu0_refactor_batch_max_n():
     """the largest n a member may have to take ilu0_refactor_batch_device's launch on the current device (ILUPP_BATCH_APPLY_MAX_N applied)"""
-    v = int(lib().ilupp_hip_ilu0_refactor_batch_max_n())
-    if v < 0:
-        _raise(v)
-    return v
+    return _batch_max_n("ilupp_hip_ilu0_refactor_batch_max_n")
 
 
 def cg_batch_max_n():
     """the largest n a member may have to be solved in cg_batch_device's launch on the current device (ILUPP_BATCH_APPLY_MAX_N applied)"""
-    v = int(lib().ilupp_hip_cg_batch_max_n())
-    if v < 0:
-        _raise(v)
-    return v
+    return _batch_max_n("ilupp_hip_cg_batch_max_n")
 
 
 def bicgstab_batch_device(members, ns, matrices, b_ptr, x0_ptr, x_ptr, offsets, work_ptr, work_doubles, maxiter, rtol, check_every,
@@ -1161,7 +1154,4 @@ def bicgstab_batch_device(members, ns, matrices, b_ptr, x0_ptr, x_ptr, offsets, 
 def bicgstab_batch_max_n():
     """the largest n a member may have to be solved in bicgstab_batch_device's launch on the current device (ILUPP_BATCH_APPLY_MAX_N
     applied)"""
-    v = int(lib().ilupp_hip_bicgstab_batch_max_n())
-    if v < 0:
-        _raise(v)
-    return v
+    return _batch_max_n("ilupp_hip_bicgstab_batch_max_n")

@@ -1106,6 +1106,23 @@ bool is_ilu0_object(const ilupp_precond *p)
 // re-factorisation of a batch-built object, which has none of the single numeric paths' tables
 int refactor_in_launch(ilupp_precond *p, const double *d_data, const int32_t *d_indices, const int32_t *d_indptr);
 
+// behind a re-factorisation: every copy of the OLD values goes (the static forms' transposed records, the level-ordered sweeps, the
+// transposed storages with their schedules, descriptors and packed sweeps); each is built again on its first use.  The caller has
+// waited for whatever still reads them: the pool knows nothing of streams.
+void drop_old_value_copies(ilupp_precond *p)
+{
+    p->apply_events_valid = false;
+    st_drop_transposed(&p->pkL, &p->pkU);
+    for (auto &l : p->lvl) l.release();
+    if (p->haveT) {
+        p->LcT.release(); p->UcT.release(); p->sUT.release(); p->sLT.release();
+        if (p->dUT) (void)pool_free(p->dUT);
+        if (p->dLT) (void)pool_free(p->dLT);
+        p->dUT = p->dLT = nullptr; p->haveT = false;
+        p->pkUT.release(); p->pkLT.release(); p->pack_tried[2] = p->pack_tried[3] = false;
+    }
+}
+
 int ilu0_refactor_single(ilupp_precond *p, const double *d_data, const int32_t *d_indices, const int32_t *d_indptr)
 {
     if (!is_ilu0_object(p)) { set_error("not an ILU(0) object"); return ILUPP_ERR_INVALID; }
@@ -1128,16 +1145,7 @@ int ilu0_refactor_single(ilupp_precond *p, const double *d_data, const int32_t *
     ILUPP_HIP(stream_sync(st));
     ILUPP_HIP(hipEventElapsedTime(&p->tm.numeric_ms, p->ev[1], p->ev[2]));
     p->tm.numeric_kernel_ms = kms;
-    p->apply_events_valid = false;
-    st_drop_transposed(&p->pkL, &p->pkU);
-    for (auto &l : p->lvl) l.release();            // (copies of the old values)
-    if (p->haveT) {
-        p->LcT.release(); p->UcT.release(); p->sUT.release(); p->sLT.release();
-        if (p->dUT) (void)pool_free(p->dUT);
-        if (p->dLT) (void)pool_free(p->dLT);
-        p->dUT = p->dLT = nullptr; p->haveT = false;
-        p->pkUT.release(); p->pkLT.release(); p->pack_tried[2] = p->pack_tried[3] = false;
-    }
+    drop_old_value_copies(p);
     if (rc == ILUPP_OK) arm_apply(p);
     if (rc == ILUPP_ERR_TIMEOUT) set_error("ILU0: dependency wait timed out");
     return rc;
@@ -2713,36 +2721,73 @@ int pivot_apply_dev(ilupp_ilucp *m, double *x, int transpose)
     return ILUPP_OK;
 }
 
-// What the batched apply keeps from call to call, one per device: its stream and events, the descriptor table (device copy and the pinned
-// host copy it was uploaded from: uploaded again only when a descriptor differs -- another member list, direction or vector layout), the
-// members' error words, and the staging of the host entry (one packed device buffer and its pinned host image).
+// One array of the batched entries' scratch: `cap` elements on the device (d) and, where the instance is pinned, as many in page-locked
+// host memory (h), with the event that says the last upload from there is over (never recorded: over).  It only grows, and is never
+// smaller than its floor: the descriptor tables start at 64 entries, the staging blocks take exactly what is asked for.
+template <class T>
+struct BatchBuf {
+    const size_t floor;
+    const bool pinned;
+    T *d = nullptr, *h = nullptr;
+    size_t cap = 0;
+    size_t used = 0;              // batch_upload's cache: so many entries of h are on the device as they stand there (0 = none)
+    hipEvent_t up = nullptr;
+    BatchBuf(size_t floor_, bool pinned_) : floor(floor_), pinned(pinned_) {}
+    // Room for `want` elements.  true: the arrays are new ones and what the old ones held is gone.  Work queued on `st` may still read
+    // the old ones, hence the wait before they are freed.  A growth that throws leaves cap == 0 and each pointer either null or
+    // allocated: nothing is reached through a buffer without capacity, and the next call frees what is there and starts over.
+    bool reserve(hipStream_t st, size_t want)
+    {
+        if (want <= cap) return false;
+        if (d) ILUPP_HIP(hipStreamSynchronize(st));
+        cap = 0;
+        if (d) (void)hipFree(d);
+        if (h) (void)hipHostFree(h);
+        d = h = nullptr;
+        if (pinned && !up) ILUPP_HIP(hipEventCreateWithFlags(&up, hipEventDisableTiming));
+        const size_t n = want < floor ? floor : want;
+        ILUPP_HIP(hipMalloc(reinterpret_cast<void **>(&d), sizeof(T) * n));
+        if (pinned) ILUPP_HIP(hipHostMalloc(reinterpret_cast<void **>(&h), sizeof(T) * n, hipHostMallocDefault));
+        cap = n;
+        return true;
+    }
+};
+
+// `fresh` (at least one entry) into B's pinned copy and from there to the device, on `st`.  cached: nothing is sent when the count and
+// the bytes are those the device holds already -- the same members with the same buffers, call after call -- and what is sent is
+// remembered.  Not cached: always sent and nothing remembered (a table nobody describes a second time).
+template <class T>
+void batch_upload(hipStream_t st, BatchBuf<T> &B, const std::vector<T> &fresh, bool cached = true)
+{
+    const size_t nl = fresh.size(), bytes = sizeof(T) * nl;
+    if (B.reserve(st, nl)) B.used = 0;
+    if (cached && nl == B.used && memcmp(B.h, fresh.data(), bytes) == 0) return;
+    ILUPP_HIP(hipEventSynchronize(B.up));                               // (the upload before this one has read the pinned copy: long over)
+    B.used = 0;
+    memcpy(B.h, fresh.data(), bytes);
+    ILUPP_HIP(hipMemcpyAsync(B.d, B.h, bytes, hipMemcpyHostToDevice, st));
+    ILUPP_HIP(hipEventRecord(B.up, st));
+    if (cached) B.used = nl;
+}
+
+// What the batched entries keep from call to call, one per device: a stream, the events that order it, what the last describing pass
+// left, and the arrays that grow with the largest call so far.
 struct BatchScratch {
     hipStream_t stream = nullptr;
     hipEvent_t cev[2] = {nullptr, nullptr};       // ordering against the caller's stream
-    hipEvent_t in_ev = nullptr, done_ev = nullptr, up_ev = nullptr;      // the staged vectors are there; the launch is over; the table's upload is over
-    PivotApplyDesc *h_table = nullptr, *d_table = nullptr;
-    int32_t *d_err = nullptr;
-    int32_t cap = 0, used = 0;                    // descriptors allocated / valid
-    std::vector<PivotApplyDesc> fresh;
+    hipEvent_t in_ev = nullptr, done_ev = nullptr;      // the staged vectors are there; the launch is over
+    hipEvent_t tev[4] = {nullptr, nullptr, nullptr, nullptr};      // around the two launches of a batched construction (timed; made there)
+    std::vector<PivotApplyDesc> fresh;            // the descriptors of the launch
     std::vector<int32_t> launched, route, h_err, status;      // member of workgroup k; per member: route, error word, code
-    double *d_stage = nullptr, *h_stage = nullptr;
-    size_t stage_cap = 0;
-    PivotSolveDesc *h_sys = nullptr, *d_sys = nullptr;      // the batched solve's second table (pinned host copy, device copy) and what says its upload is over
-    int32_t sys_cap = 0;
-    hipEvent_t sys_ev = nullptr;
-    double *d_tmp = nullptr;                      // the hand-over vectors (`tmp`) of the non-pivoting members of a launch, one block: n doubles each
-    size_t tmp_cap = 0;
-    // the batched ILU(0) re-factorisation's own descriptor table (pinned host copy, device copy, entries allocated / valid) and what says
-    // its upload is over: apart from h_table / d_table / used, so that the apply's descriptor cache still hits after a re-factorisation
-    RefactorDesc *h_rtable = nullptr, *d_rtable = nullptr;
-    int32_t rcap = 0, rused = 0;
-    hipEvent_t rup_ev = nullptr;
-    // the batched ILU(0) construction: the symbolic launch's records (device, pinned host), the create launch's status words, entries
-    // allocated, and the events around the two launches (timed)
-    CreateInfo *d_cinfo = nullptr, *h_cinfo = nullptr;
-    int32_t *d_cstat = nullptr;
-    int32_t ccap = 0;
-    hipEvent_t tev[4] = {nullptr, nullptr, nullptr, nullptr};
+    BatchBuf<PivotApplyDesc> table{64, true};     // the descriptors of an apply or a solve, cached: another member list, direction or vector layout uploads
+    BatchBuf<int32_t> err{64, false};             // ... and the error word of each
+    BatchBuf<PivotSolveDesc> sys{64, true};       // a solve's second table (the members' matrices), sent with every call
+    BatchBuf<double> tmp{0, false};               // the hand-over vectors (`tmp`) of a launch's non-pivoting members, one block: n doubles each
+    BatchBuf<double> stage{0, true};              // the host entries' packed block: the vectors of an apply, the matrices of a construction
+    // the descriptors of an ILU(0) re-factorisation or construction, cached apart from `table`: the apply's cache still hits after a re-factorisation
+    BatchBuf<RefactorDesc> rtable{64, true};
+    BatchBuf<CreateInfo> cinfo{64, true};         // a construction's symbolic records, read back through the pinned copy
+    BatchBuf<int32_t> cstat{64, false};           // ... and the status words of its create launch
 };
 
 // One member as the batched kernels see it, whatever class it comes from: the object that holds the two triangles, the pivoting
@@ -2771,7 +2816,8 @@ BatchMember batch_member(ilupp_precond *p, int transpose)
     v.p = p; v.plain_first = transpose == 0; v.n = p->n;
     return v;
 }
-std::vector<BatchMember> batch_members(int32_t count, ilupp_ilucp *const *members, int transpose)
+template <class Handle>
+std::vector<BatchMember> batch_members(int32_t count, Handle *const *members, int transpose)
 {
     std::vector<BatchMember> v((size_t)count);
     for (int32_t i = 0; i < count; ++i) v[(size_t)i] = batch_member(members[i], transpose);
@@ -2785,43 +2831,48 @@ BatchScratch &batch_scratch()
     int dev = 0;
     ILUPP_HIP(hipGetDevice(&dev));
     BatchScratch &S = g_batch_scratch[dev];
-    if (!S.up_ev) {
+    if (!S.done_ev) {
         if (!S.stream) ILUPP_HIP(hipStreamCreateWithFlags(&S.stream, hipStreamNonBlocking));
-        for (hipEvent_t *e : {&S.cev[0], &S.cev[1], &S.in_ev, &S.done_ev, &S.up_ev})       // (up_ev comes last: a scratch that has it is complete)
+        for (hipEvent_t *e : {&S.cev[0], &S.cev[1], &S.in_ev, &S.done_ev})       // (done_ev comes last: a scratch that has it is complete)
             if (!*e) ILUPP_HIP(hipEventCreateWithFlags(e, hipEventDisableTiming));
     }
     return S;
 }
 
-// the packed staging buffer of the host entries (device block and its pinned host image) with room for `total` doubles
-void batch_stage_reserve(BatchScratch &S, size_t total)
+// ILUPP_BATCH_APPLY_MAX_N lowers the n up to which a member goes to a launch (read per call)
+int64_t batch_env_cap(int64_t cap_n)
 {
-    if (total <= S.stage_cap) return;
-    if (S.d_stage) { ILUPP_HIP(hipStreamSynchronize(S.stream)); (void)hipFree(S.d_stage); (void)hipHostFree(S.h_stage); S.d_stage = nullptr; S.h_stage = nullptr; }
-    S.stage_cap = 0;
-    ILUPP_HIP(hipMalloc(reinterpret_cast<void **>(&S.d_stage), sizeof(double) * total));
-    ILUPP_HIP(hipHostMalloc(reinterpret_cast<void **>(&S.h_stage), sizeof(double) * total, hipHostMallocDefault));
-    S.stage_cap = total;
-}
-
-// the re-factorisation's descriptor table (device copy and pinned host copy) with room for nl members; the cached table goes when it grows
-void batch_rtable_reserve(BatchScratch &S, int32_t nl)
-{
-    if (nl <= S.rcap) return;
-    if (S.d_rtable) { ILUPP_HIP(hipStreamSynchronize(S.stream)); (void)hipFree(S.d_rtable); (void)hipHostFree(S.h_rtable); S.d_rtable = nullptr; S.h_rtable = nullptr; }
-    S.rcap = 0; S.rused = 0;
-    const int32_t cap = nl < 64 ? 64 : nl;
-    ILUPP_HIP(hipMalloc(reinterpret_cast<void **>(&S.d_rtable), sizeof(RefactorDesc) * (size_t)cap));
-    ILUPP_HIP(hipHostMalloc(reinterpret_cast<void **>(&S.h_rtable), sizeof(RefactorDesc) * (size_t)cap, hipHostMallocDefault));
-    S.rcap = cap;
-}
-
-// n up to which a member goes to the launch: 8 n bytes of LDS must fit (ILUPP_BATCH_APPLY_MAX_N lowers it, read per call)
-int64_t batch_apply_max_n()
-{
-    int64_t cap_n = (int64_t)(pivot_apply_batch_lds_cap() / 8);
     if (const char *e = getenv("ILUPP_BATCH_APPLY_MAX_N")) { const long long v = atoll(e); if (v >= 0 && v < cap_n) cap_n = v; }
     return cap_n;
+}
+
+// n up to which a member goes to the apply's launch: 8 n bytes of LDS must fit
+int64_t batch_apply_max_n() { return batch_env_cap((int64_t)(pivot_apply_batch_lds_cap() / 8)); }
+
+// ... to a solver's launch: the cap of the apply's launch, lowered by what the dot scratch takes
+int64_t solve_batch_cap_n(BatchSolver solver)
+{
+    const int64_t a = batch_apply_max_n(), b = solve_batch_max_n(solver);
+    return a < b ? a : b;
+}
+
+// ... to the re-factorisation's and the construction's launches: one flag word per row of LDS
+int64_t refactor_batch_max_n() { return batch_env_cap(ilu0_refactor_batch_max_n()); }
+
+// the scratch's stream behind whatever is still queued on a member's own stream (a single apply or factors() that was not waited for,
+// the transposed storages of a first use)
+void batch_join(hipStream_t bs, ilupp_precond *p)
+{
+    if (!p || hipStreamQuery(p->stream) == hipSuccess) return;
+    (void)hipGetLastError();
+    ILUPP_HIP(hipEventRecord(p->sev[1], p->stream));
+    ILUPP_HIP(hipStreamWaitEvent(bs, p->sev[1], 0));
+}
+
+// the routes of a call into the caller's array, if it gave one
+void routes_out(const std::vector<int32_t> &from, int32_t *route)
+{
+    if (route) std::copy(from.begin(), from.end(), route);
 }
 
 // Route and describe the members of a batched launch: route 0 = the launch (n <= cap_n, object not degenerate), 1 = too large, 2 = degenerate.
@@ -2867,26 +2918,20 @@ void batch_tmp(BatchScratch &S, const BatchMember *members)
 {
     size_t total = 0;
     for (int32_t i : S.launched) if (members[i].p && !members[i].owner) total += (size_t)members[i].n;
-    if (total > S.tmp_cap) {
-        if (S.d_tmp) { ILUPP_HIP(hipStreamSynchronize(S.stream)); (void)hipFree(S.d_tmp); S.d_tmp = nullptr; }
-        S.tmp_cap = 0;
-        ILUPP_HIP(hipMalloc(reinterpret_cast<void **>(&S.d_tmp), sizeof(double) * total));
-        S.tmp_cap = total;
-    }
+    S.tmp.reserve(S.stream, total);
     size_t at = 0;
     for (size_t k = 0; k < S.launched.size(); ++k) {
         const BatchMember &v = members[S.launched[k]];
-        if (v.p && !v.owner) { S.fresh[k].tmp = S.d_tmp + at; at += (size_t)v.n; }
+        if (v.p && !v.owner) { S.fresh[k].tmp = S.tmp.d + at; at += (size_t)v.n; }
     }
 }
 
 // The described members (at least one) made ready for their launch on the scratch's stream: the bytes of LDS the sweeps of the launch take
 // (returned), the error words, the descriptor table on the device (uploaded again only when a descriptor differs), and the stream behind
-// whatever is still queued on a member's own stream (a single apply that was not waited for, the transposed storages of a first use).
+// whatever is still queued on a member's own stream.
 size_t batch_stage(BatchScratch &S, const BatchMember *members, int64_t cap_n)
 {
     hipStream_t bs = S.stream;
-    const int32_t nl = (int32_t)S.launched.size();
     batch_tmp(S, members);
     // both arrays in LDS where 16 n bytes fit under the cap, else one: the launch takes what its largest member needs
     size_t lds = 0;
@@ -2896,30 +2941,10 @@ size_t batch_stage(BatchScratch &S, const BatchMember *members, int64_t cap_n)
         if (want > lds) lds = want;
     }
     // (the kernel makes the same choice per member from the launch's size: 16 n <= lds exactly when 16 n <= the cap)
-    if (nl > S.cap) {
-        if (S.d_table) { ILUPP_HIP(hipStreamSynchronize(bs)); (void)hipFree(S.d_table); (void)hipFree(S.d_err); (void)hipHostFree(S.h_table); S.d_table = nullptr; S.d_err = nullptr; S.h_table = nullptr; }
-        S.cap = 0; S.used = 0;
-        const int32_t cap = nl < 64 ? 64 : nl;
-        ILUPP_HIP(hipMalloc(reinterpret_cast<void **>(&S.d_table), sizeof(PivotApplyDesc) * (size_t)cap));
-        ILUPP_HIP(hipMalloc(reinterpret_cast<void **>(&S.d_err), sizeof(int32_t) * (size_t)cap));
-        ILUPP_HIP(hipHostMalloc(reinterpret_cast<void **>(&S.h_table), sizeof(PivotApplyDesc) * (size_t)cap, hipHostMallocDefault));
-        S.cap = cap;
-    }
-    for (int32_t k = 0; k < nl; ++k) S.fresh[(size_t)k].err = S.d_err + k;
-    if (nl != S.used || memcmp(S.h_table, S.fresh.data(), sizeof(PivotApplyDesc) * (size_t)nl) != 0) {
-        ILUPP_HIP(hipEventSynchronize(S.up_ev));                    // (the upload before this one has read the pinned copy: long over)
-        memcpy(S.h_table, S.fresh.data(), sizeof(PivotApplyDesc) * (size_t)nl);
-        ILUPP_HIP(hipMemcpyAsync(S.d_table, S.h_table, sizeof(PivotApplyDesc) * (size_t)nl, hipMemcpyHostToDevice, bs));
-        ILUPP_HIP(hipEventRecord(S.up_ev, bs));
-        S.used = nl;
-    }
-    for (int32_t k = 0; k < nl; ++k) {
-        ilupp_precond *p = members[S.launched[(size_t)k]].p;
-        if (!p || hipStreamQuery(p->stream) == hipSuccess) continue;
-        (void)hipGetLastError();
-        ILUPP_HIP(hipEventRecord(p->sev[1], p->stream));
-        ILUPP_HIP(hipStreamWaitEvent(bs, p->sev[1], 0));
-    }
+    S.err.reserve(bs, S.fresh.size());
+    for (size_t k = 0; k < S.fresh.size(); ++k) S.fresh[k].err = S.err.d + k;
+    batch_upload(bs, S.table, S.fresh);
+    for (int32_t i : S.launched) batch_join(bs, members[i].p);
     return lds;
 }
 
@@ -2933,32 +2958,21 @@ void batch_launched(BatchScratch &S, const BatchMember *members)
 
 // The second table of a batched solve on the device: for every launched member (at least one) its matrix, its own words of the per-member
 // outputs and where its `wf` vectors of n start in the workspace -- member i's behind those of the members before it, launched or not.
-// The table grows as the launch does; the upload goes through the pinned copy on the scratch's stream.
 void batch_systems(BatchScratch &S, int32_t count, const BatchMember *members, int64_t wf, const double *const *d_data,
                    const int32_t *const *d_indices, const int32_t *const *d_indptr)
 {
-    hipStream_t bs = S.stream;
-    const int32_t nl = (int32_t)S.launched.size();
-    if (nl > S.sys_cap) {
-        if (S.d_sys) { ILUPP_HIP(hipStreamSynchronize(bs)); (void)hipFree(S.d_sys); (void)hipHostFree(S.h_sys); S.d_sys = nullptr; S.h_sys = nullptr; }
-        S.sys_cap = 0;
-        const int32_t cap = nl < 64 ? 64 : nl;
-        ILUPP_HIP(hipMalloc(reinterpret_cast<void **>(&S.d_sys), sizeof(PivotSolveDesc) * (size_t)cap));
-        ILUPP_HIP(hipHostMalloc(reinterpret_cast<void **>(&S.h_sys), sizeof(PivotSolveDesc) * (size_t)cap, hipHostMallocDefault));
-        S.sys_cap = cap;
-    }
-    ILUPP_HIP(hipEventSynchronize(S.sys_ev));                       // (the upload before this one has read the pinned copy)
     std::vector<int64_t> woff((size_t)count);
     int64_t total = 0;
     for (int32_t i = 0; i < count; ++i) { woff[(size_t)i] = wf * total; total += members[i].n; }
-    for (int32_t k = 0; k < nl; ++k) {
-        const int32_t i = S.launched[(size_t)k];
-        PivotSolveDesc &e = S.h_sys[k];
+    std::vector<PivotSolveDesc> fresh;
+    fresh.reserve(S.launched.size());
+    for (int32_t i : S.launched) {
+        PivotSolveDesc e;
         e.aval = d_data[i]; e.aidx = d_indices[i]; e.aptr = d_indptr[i];
         e.woff = woff[(size_t)i]; e.member = i; e.pad = 0;
+        fresh.push_back(e);
     }
-    ILUPP_HIP(hipMemcpyAsync(S.d_sys, S.h_sys, sizeof(PivotSolveDesc) * (size_t)nl, hipMemcpyHostToDevice, bs));
-    ILUPP_HIP(hipEventRecord(S.sys_ev, bs));
+    batch_upload(S.stream, S.sys, fresh, false);
 }
 
 // Queue the applies of all members: route 0 = the launch (n within the LDS cap, object not degenerate), 1 = too large (for the LDS, or for
@@ -2978,7 +2992,7 @@ int apply_batch_run(BatchScratch &S, int32_t count, const BatchMember *members, 
     if (S.launched.size() == 1 && S.fresh[0].n > kSmallSweepMax) { S.route[(size_t)S.launched[0]] = 1; S.launched.clear(); S.fresh.clear(); }
     if (!S.launched.empty()) {
         const size_t lds = batch_stage(S, members, cap_n);
-        OR_RETURN(pivot_apply_batch_launch(bs, (int32_t)S.launched.size(), S.d_table, d_x, lds));
+        OR_RETURN(pivot_apply_batch_launch(bs, (int32_t)S.launched.size(), S.table.d, d_x, lds));
         batch_launched(S, members);
     }
     for (int32_t i = 0; i < count; ++i) {
@@ -3006,7 +3020,7 @@ int apply_batch_finish(BatchScratch &S, int32_t count, const BatchMember *member
             if (S.status[(size_t)i]) msgs[(size_t)i] = g_last_error;
         }
     std::vector<int32_t> err((size_t)(nl > 0 ? nl : 1), 0);
-    if (nl > 0) ILUPP_HIP(d2h_async(S.stream, err.data(), S.d_err, sizeof(int32_t) * (size_t)nl));
+    if (nl > 0) ILUPP_HIP(d2h_async(S.stream, err.data(), S.err.d, sizeof(int32_t) * (size_t)nl));
     ILUPP_HIP(stream_sync(S.stream));
     for (int32_t k = 0; k < nl; ++k) {
         const int32_t i = S.launched[(size_t)k];
@@ -3019,15 +3033,58 @@ int apply_batch_finish(BatchScratch &S, int32_t count, const BatchMember *member
     return ILUPP_OK;
 }
 
-// null arguments, a negative count, a null member, a member named twice (its scratch vector serves one apply at a time): before any device call
+// What both device entries of the batched apply do once their arguments are checked and their members named (count > 0): queue the
+// applies, hand the routes out, and either wait for them (sync) or order the caller's stream behind them.
+int apply_batch_device(int32_t count, const std::vector<BatchMember> &mv, double *d_x, const int64_t *offsets, int transpose, int sync,
+                       int32_t *route)
+{
+    std::lock_guard<std::mutex> lk(g_batch_mu);
+    BatchScratch &S = batch_scratch();
+    const int rc = apply_batch_run(S, count, mv.data(), d_x, offsets, transpose, false);
+    routes_out(S.route, route);
+    if (rc) return rc;
+    if (sync) return apply_batch_finish(S, count, mv.data());
+    order_caller_after(S.stream, S.cev[1]);
+    return ILUPP_OK;
+}
+
+// ---- the argument checks the entries share, each entry in its own order: all before any device call ----
+// a handle that stands twice in `seen` (a member's scratch vector and its factors serve one launch at a time)
+int batch_no_duplicates(std::vector<const void *> &seen)
+{
+    std::sort(seen.begin(), seen.end());
+    if (std::adjacent_find(seen.begin(), seen.end()) != seen.end()) { set_error("a preconditioner appears twice in the batch"); return ILUPP_ERR_INVALID; }
+    return ILUPP_OK;
+}
+
+// the three arrays of member i's matrix
+int batch_matrix_arrays(const double *const *d_data, const int32_t *const *d_indices, const int32_t *const *d_indptr, int32_t i)
+{
+    if (!d_data[i] || !d_indices[i] || !d_indptr[i]) { set_error("null argument"); return ILUPP_ERR_INVALID; }
+    return ILUPP_OK;
+}
+
+int batch_iteration_args(int32_t maxiter, int32_t check_every)
+{
+    if (maxiter < 0 || check_every < 0) { set_error("maxiter and check_every must not be negative"); return ILUPP_ERR_INVALID; }
+    return ILUPP_OK;
+}
+
+// the workspace of a solve over `total` unknowns
+int batch_workspace(BatchSolver solver, int64_t work_doubles, int64_t total)
+{
+    const int64_t wf = solve_batch_work_factor(solver);
+    if (work_doubles < wf * total) { set_error("workspace too small: " + std::to_string(wf) + " doubles per unknown of the batch"); return ILUPP_ERR_INVALID; }
+    return ILUPP_OK;
+}
+
+// null arguments, a negative count, a null member, a member named twice
 int pivot_batch_args(int32_t count, ilupp_ilucp *const *members, const void *a, const void *b)
 {
     if (count < 0 || !members || !a || !b) { set_error("null argument"); return ILUPP_ERR_INVALID; }
     for (int32_t i = 0; i < count; ++i) if (!members[i]) { set_error("null preconditioner"); return ILUPP_ERR_INVALID; }
-    std::vector<const ilupp_ilucp *> seen(members, members + count);
-    std::sort(seen.begin(), seen.end());
-    if (std::adjacent_find(seen.begin(), seen.end()) != seen.end()) { set_error("a preconditioner appears twice in the batch"); return ILUPP_ERR_INVALID; }
-    return ILUPP_OK;
+    std::vector<const void *> seen(members, members + count);
+    return batch_no_duplicates(seen);
 }
 
 // the same for a list of non-pivoting objects; null_ok: a null handle is a member without a preconditioner (the CG solve), any number of them.
@@ -3035,23 +3092,13 @@ int pivot_batch_args(int32_t count, ilupp_ilucp *const *members, const void *a, 
 int plain_batch_args(int32_t count, ilupp_precond *const *members, bool null_ok, const void *a, const void *b)
 {
     if (count < 0 || !members || !a || !b) { set_error("null argument"); return ILUPP_ERR_INVALID; }
-    std::vector<const ilupp_precond *> seen;
+    std::vector<const void *> seen;
     for (int32_t i = 0; i < count; ++i) {
         if (!members[i]) { if (null_ok) continue; set_error("null preconditioner"); return ILUPP_ERR_INVALID; }
         if (is_live_ml(members[i])) { set_error("a multilevel preconditioner cannot be a member of a batch"); return ILUPP_ERR_INVALID; }
         seen.push_back(members[i]);
     }
-    std::sort(seen.begin(), seen.end());
-    if (std::adjacent_find(seen.begin(), seen.end()) != seen.end()) { set_error("a preconditioner appears twice in the batch"); return ILUPP_ERR_INVALID; }
-    return ILUPP_OK;
-}
-
-// n up to which a member goes to a solver's launch: the cap of the apply's launch, lowered by what the dot scratch takes
-// (ILUPP_BATCH_APPLY_MAX_N lowers both)
-int64_t solve_batch_cap_n(BatchSolver solver)
-{
-    const int64_t a = batch_apply_max_n(), b = solve_batch_max_n(solver);
-    return a < b ? a : b;
+    return batch_no_duplicates(seen);
 }
 
 // What the three batched solves do once their arguments are checked and their members named (count > 0): the members routed and
@@ -3065,16 +3112,15 @@ int solve_batch_run(BatchSolver solver, int32_t count, const std::vector<BatchMe
     std::lock_guard<std::mutex> lk(g_batch_mu);
     BatchScratch &S = batch_scratch();
     hipStream_t bs = S.stream;
-    if (!S.sys_ev) ILUPP_HIP(hipEventCreateWithFlags(&S.sys_ev, hipEventDisableTiming));
     order_after_caller(bs, S.cev[0]);
     const int64_t cap_n = solve_batch_cap_n(solver);
     batch_describe(S, count, mv.data(), offsets, cap_n);
-    if (route) for (int32_t i = 0; i < count; ++i) route[i] = S.route[(size_t)i];
+    routes_out(S.route, route);
     const int32_t nl = (int32_t)S.launched.size();
     if (nl == 0) return ILUPP_OK;
     const size_t lds = batch_stage(S, mv.data(), cap_n);
     batch_systems(S, count, mv.data(), solve_batch_work_factor(solver), d_data, d_indices, d_indptr);
-    OR_RETURN(solve_batch_launch(solver, bs, nl, S.d_table, S.d_sys, d_b, d_x0, d_x, d_work, lds, maxiter, rtol, check_every, d_iterations,
+    OR_RETURN(solve_batch_launch(solver, bs, nl, S.table.d, S.sys.d, d_b, d_x0, d_x, d_work, lds, maxiter, rtol, check_every, d_iterations,
                                  d_flags, d_rr, d_last));
     batch_launched(S, mv.data());
     if (sync) return apply_batch_finish(S, count, mv.data(), false);
@@ -3092,16 +3138,7 @@ int ilupp_hip_apply_batch_device(int32_t count, ilupp_precond *const *members, d
     API_TRY
     const int rc0 = plain_batch_args(count, members, false, d_x, offsets);
     if (rc0 || count == 0) return rc0;
-    std::lock_guard<std::mutex> lk(g_batch_mu);
-    BatchScratch &S = batch_scratch();
-    std::vector<BatchMember> mv((size_t)count);
-    for (int32_t i = 0; i < count; ++i) mv[(size_t)i] = batch_member(members[i], transpose);
-    int rc = apply_batch_run(S, count, mv.data(), d_x, offsets, transpose, false);
-    if (route) for (int32_t i = 0; i < count; ++i) route[i] = S.route[(size_t)i];
-    if (rc) return rc;
-    if (sync) return apply_batch_finish(S, count, mv.data());
-    order_caller_after(S.stream, S.cev[1]);
-    return ILUPP_OK;
+    return apply_batch_device(count, batch_members(count, members, transpose), d_x, offsets, transpose, sync, route);
     API_CATCH
 }
 
@@ -3112,19 +3149,17 @@ int ilupp_hip_cg_batch_device(int32_t count, ilupp_precond *const *members, cons
                               int32_t *route)
 {
     API_TRY
-    const int rc0 = plain_batch_args(count, members, true, d_x, offsets);
-    if (rc0) return rc0;
+    OR_RETURN(plain_batch_args(count, members, true, d_x, offsets));
     if (!n || !d_data || !d_indices || !d_indptr || !nnz || !d_b || !d_work || !d_iterations || !d_flags || !d_rr || !d_bnorm) { set_error("null argument"); return ILUPP_ERR_INVALID; }
-    if (maxiter < 0 || check_every < 0) { set_error("maxiter and check_every must not be negative"); return ILUPP_ERR_INVALID; }
+    OR_RETURN(batch_iteration_args(maxiter, check_every));
     int64_t total = 0;
     for (int32_t i = 0; i < count; ++i) {
-        if (!d_data[i] || !d_indices[i] || !d_indptr[i]) { set_error("null argument"); return ILUPP_ERR_INVALID; }
+        OR_RETURN(batch_matrix_arrays(d_data, d_indices, d_indptr, i));
         if (n[i] <= 0 || n[i] > INT32_MAX) { set_error("matrix has size 0!"); return ILUPP_ERR_INVALID; }
         if (members[i] && members[i]->n != n[i]) { set_error("matrix has wrong size for preconditioner!"); return ILUPP_ERR_WRONG_SIZE; }
         total += n[i];
     }
-    const int64_t wf = solve_batch_work_factor(BATCH_CG);
-    if (work_doubles < wf * total) { set_error("workspace too small: " + std::to_string(wf) + " doubles per unknown of the batch"); return ILUPP_ERR_INVALID; }
+    OR_RETURN(batch_workspace(BATCH_CG, work_doubles, total));
     if (count == 0) return ILUPP_OK;
     std::vector<BatchMember> mv((size_t)count);
     for (int32_t i = 0; i < count; ++i) { if (members[i]) mv[(size_t)i] = batch_member(members[i], 0); mv[(size_t)i].n = (int32_t)n[i]; }
@@ -3160,23 +3195,14 @@ int ilupp_hip_pivot_apply_batch_device(int32_t count, ilupp_ilucp *const *member
     API_TRY
     const int rc0 = pivot_batch_args(count, members, d_x, offsets);
     if (rc0 || count == 0) return rc0;
-    std::lock_guard<std::mutex> lk(g_batch_mu);
-    BatchScratch &S = batch_scratch();
-    const std::vector<BatchMember> mv = batch_members(count, members, transpose);
-    int rc = apply_batch_run(S, count, mv.data(), d_x, offsets, transpose, false);
-    if (route) for (int32_t i = 0; i < count; ++i) route[i] = S.route[(size_t)i];
-    if (rc) return rc;
-    if (sync) return apply_batch_finish(S, count, mv.data());
-    order_caller_after(S.stream, S.cev[1]);
-    return ILUPP_OK;
+    return apply_batch_device(count, batch_members(count, members, transpose), d_x, offsets, transpose, sync, route);
     API_CATCH
 }
 
 int ilupp_hip_pivot_apply_batch(int32_t count, ilupp_ilucp *const *members, double *const *x, const int64_t *len, int transpose, int32_t *route)
 {
     API_TRY
-    const int rc0 = pivot_batch_args(count, members, x, len);
-    if (rc0) return rc0;
+    OR_RETURN(pivot_batch_args(count, members, x, len));
     for (int32_t i = 0; i < count; ++i) {
         if (!x[i]) { set_error("null argument"); return ILUPP_ERR_INVALID; }
         if (len[i] != members[i]->n) { set_error("vector has wrong size for preconditioner!"); return ILUPP_ERR_WRONG_SIZE; }
@@ -3188,18 +3214,18 @@ int ilupp_hip_pivot_apply_batch(int32_t count, ilupp_ilucp *const *members, doub
     std::vector<int64_t> off((size_t)count);
     size_t total = 0;
     for (int32_t i = 0; i < count; ++i) { off[(size_t)i] = (int64_t)total; total += (size_t)len[i]; }
-    batch_stage_reserve(S, total);
-    for (int32_t i = 0; i < count; ++i) memcpy(S.h_stage + off[(size_t)i], x[i], sizeof(double) * (size_t)len[i]);
-    ILUPP_HIP(hipMemcpyAsync(S.d_stage, S.h_stage, sizeof(double) * total, hipMemcpyHostToDevice, S.stream));
+    S.stage.reserve(S.stream, total);
+    for (int32_t i = 0; i < count; ++i) memcpy(S.stage.h + off[(size_t)i], x[i], sizeof(double) * (size_t)len[i]);
+    ILUPP_HIP(hipMemcpyAsync(S.stage.d, S.stage.h, sizeof(double) * total, hipMemcpyHostToDevice, S.stream));
     const std::vector<BatchMember> mv = batch_members(count, members, transpose);
-    int rc = apply_batch_run(S, count, mv.data(), S.d_stage, off.data(), transpose, true);
-    if (route) for (int32_t i = 0; i < count; ++i) route[i] = S.route[(size_t)i];
+    int rc = apply_batch_run(S, count, mv.data(), S.stage.d, off.data(), transpose, true);
+    routes_out(S.route, route);
     if (rc) { (void)hipStreamSynchronize(S.stream); return rc; }
-    ILUPP_HIP(hipMemcpyAsync(S.h_stage, S.d_stage, sizeof(double) * total, hipMemcpyDeviceToHost, S.stream));
+    ILUPP_HIP(hipMemcpyAsync(S.stage.h, S.stage.d, sizeof(double) * total, hipMemcpyDeviceToHost, S.stream));
     rc = apply_batch_finish(S, count, mv.data());
     // (a member that failed keeps its vector as it was; the others have theirs)
     for (int32_t i = 0; i < count; ++i)
-        if (S.status[(size_t)i] == ILUPP_OK) memcpy(x[i], S.h_stage + off[(size_t)i], sizeof(double) * (size_t)len[i]);
+        if (S.status[(size_t)i] == ILUPP_OK) memcpy(x[i], S.stage.h + off[(size_t)i], sizeof(double) * (size_t)len[i]);
     return rc;
     API_CATCH
 }
@@ -3211,17 +3237,15 @@ int ilupp_hip_pivot_bicgstab_batch_device(int32_t count, ilupp_ilucp *const *mem
                                           int32_t *route)
 {
     API_TRY
-    const int rc0 = pivot_batch_args(count, members, d_x, offsets);
-    if (rc0) return rc0;
+    OR_RETURN(pivot_batch_args(count, members, d_x, offsets));
     if (!d_data || !d_indices || !d_indptr || !nnz || !d_b || !d_work || !d_iterations || !d_flags || !d_rr || !d_init) { set_error("null argument"); return ILUPP_ERR_INVALID; }
-    if (maxiter < 0 || check_every < 0) { set_error("maxiter and check_every must not be negative"); return ILUPP_ERR_INVALID; }
+    OR_RETURN(batch_iteration_args(maxiter, check_every));
     int64_t total = 0;
     for (int32_t i = 0; i < count; ++i) {
-        if (!d_data[i] || !d_indices[i] || !d_indptr[i]) { set_error("null argument"); return ILUPP_ERR_INVALID; }
+        OR_RETURN(batch_matrix_arrays(d_data, d_indices, d_indptr, i));
         total += members[i]->n;
     }
-    const int64_t wf = solve_batch_work_factor(BATCH_BICGSTAB);
-    if (work_doubles < wf * total) { set_error("workspace too small: " + std::to_string(wf) + " doubles per unknown of the batch"); return ILUPP_ERR_INVALID; }
+    OR_RETURN(batch_workspace(BATCH_BICGSTAB, work_doubles, total));
     if (count == 0) return ILUPP_OK;
     return solve_batch_run(BATCH_BICGSTAB, count, batch_members(count, members, 0), d_data, d_indices, d_indptr, d_b, d_x0, d_x, offsets,
                            d_work, maxiter, rtol, check_every, d_iterations, d_flags, d_rr, d_init, sync, route);
@@ -3237,7 +3261,7 @@ int ilupp_hip_bicgstab_batch_device(int32_t count, ilupp_precond *const *plain, 
     API_TRY
     if (count < 0 || !d_x || !offsets || !n || !d_data || !d_indices || !d_indptr || !nnz || !d_b || !d_work || !d_iterations || !d_flags ||
         !d_rr || !d_init) { set_error("null argument"); return ILUPP_ERR_INVALID; }
-    if (maxiter < 0 || check_every < 0) { set_error("maxiter and check_every must not be negative"); return ILUPP_ERR_INVALID; }
+    OR_RETURN(batch_iteration_args(maxiter, check_every));
     // member i: pivoted[i], or plain[i], or neither (no preconditioner); a multilevel object among `plain` is named before anything reads
     // it as an ilupp_precond
     std::vector<const void *> seen_plain, seen_pivoted;
@@ -3247,19 +3271,16 @@ int ilupp_hip_bicgstab_batch_device(int32_t count, ilupp_precond *const *plain, 
         ilupp_ilucp *m = pivoted ? pivoted[i] : nullptr;
         if (p && m) { set_error("member " + std::to_string(i) + " of the batch: both a pivoting and a non-pivoting preconditioner"); return ILUPP_ERR_INVALID; }
         if (p && is_live_ml(p)) { set_error("a multilevel preconditioner cannot be a member of a batch"); return ILUPP_ERR_INVALID; }
-        if (!d_data[i] || !d_indices[i] || !d_indptr[i]) { set_error("null argument"); return ILUPP_ERR_INVALID; }
+        OR_RETURN(batch_matrix_arrays(d_data, d_indices, d_indptr, i));
         if (n[i] <= 0 || n[i] > INT32_MAX) { set_error("matrix has size 0!"); return ILUPP_ERR_INVALID; }
         if ((p && p->n != n[i]) || (m && m->n != n[i])) { set_error("matrix has wrong size for preconditioner!"); return ILUPP_ERR_WRONG_SIZE; }
         if (p) seen_plain.push_back(p);
         if (m) seen_pivoted.push_back(m);
         total += n[i];
     }
-    for (std::vector<const void *> *seen : {&seen_plain, &seen_pivoted}) {
-        std::sort(seen->begin(), seen->end());
-        if (std::adjacent_find(seen->begin(), seen->end()) != seen->end()) { set_error("a preconditioner appears twice in the batch"); return ILUPP_ERR_INVALID; }
-    }
-    const int64_t wf = solve_batch_work_factor(BATCH_BICGSTAB);
-    if (work_doubles < wf * total) { set_error("workspace too small: " + std::to_string(wf) + " doubles per unknown of the batch"); return ILUPP_ERR_INVALID; }
+    OR_RETURN(batch_no_duplicates(seen_plain));
+    OR_RETURN(batch_no_duplicates(seen_pivoted));
+    OR_RETURN(batch_workspace(BATCH_BICGSTAB, work_doubles, total));
     if (count == 0) return ILUPP_OK;
     std::vector<BatchMember> mv((size_t)count);
     for (int32_t i = 0; i < count; ++i) {
@@ -3286,12 +3307,17 @@ int64_t ilupp_hip_pivot_apply_batch_max_n(void)
     API_CATCH
 }
 
-// n up to which a member goes to the re-factorisation's launch: one flag word per row of LDS (ILUPP_BATCH_APPLY_MAX_N lowers it, read per call)
-static int64_t refactor_batch_max_n()
+// one member of the ILU(0) launches: the matrix and the two triangles of p (at the symbolic launch their index and value arrays are not
+// there yet: null), the number of stored entries the matrix is to have, and the member's number in the call
+static RefactorDesc refactor_desc(const ilupp_precond *p, const double *aval, const int32_t *aidx, const int32_t *aptr, int64_t nnzA, int32_t member)
 {
-    int64_t cap_n = ilu0_refactor_batch_max_n();
-    if (const char *e = getenv("ILUPP_BATCH_APPLY_MAX_N")) { const long long v = atoll(e); if (v >= 0 && v < cap_n) cap_n = v; }
-    return cap_n;
+    RefactorDesc d;
+    memset(&d, 0, sizeof(d));
+    d.aptr = aptr; d.aidx = aidx; d.aval = aval;
+    d.lptr = p->Lc.ptr; d.lidx = p->Lc.idx; d.lval = p->Lc.val;
+    d.uptr = p->Uc.ptr; d.uidx = p->Uc.idx; d.uval = p->Uc.val;
+    d.nnzA = nnzA; d.n = p->n; d.member = member;
+    return d;
 }
 
 // what ilupp_hip_ilu0_refactor_batch_device does, under the construction lock its caller holds (the construction lock first, then the
@@ -3300,11 +3326,10 @@ static int refactor_batch_locked(int32_t count, ilupp_precond *const *members, c
                                  const int32_t *const *d_indices, const int32_t *const *d_indptr, const int64_t *nnz,
                                  int32_t *d_status, int sync, int32_t *route)
 {
-    const int rc0 = plain_batch_args(count, members, false, d_data, nnz);
-    if (rc0) return rc0;
+    OR_RETURN(plain_batch_args(count, members, false, d_data, nnz));
     if (!d_indices || !d_indptr || !d_status) { set_error("null argument"); return ILUPP_ERR_INVALID; }
     for (int32_t i = 0; i < count; ++i) {
-        if (!d_data[i] || !d_indices[i] || !d_indptr[i]) { set_error("null argument"); return ILUPP_ERR_INVALID; }
+        OR_RETURN(batch_matrix_arrays(d_data, d_indices, d_indptr, i));
         if (!is_ilu0_object(members[i])) { set_error("member " + std::to_string(i) + " of the batch: not an ILU(0) object"); return ILUPP_ERR_INVALID; }
         if (nnz[i] != members[i]->nnzA) {
             set_error("member " + std::to_string(i) + " of the batch: the matrix does not have the analysed pattern");
@@ -3315,7 +3340,6 @@ static int refactor_batch_locked(int32_t count, ilupp_precond *const *members, c
     std::lock_guard<std::mutex> lk(g_batch_mu);
     BatchScratch &S = batch_scratch();
     hipStream_t bs = S.stream;
-    if (!S.rup_ev) ILUPP_HIP(hipEventCreateWithFlags(&S.rup_ev, hipEventDisableTiming));
     order_after_caller(bs, S.cev[0]);
     // routes: 0 = the launch, 1 = n above the cap or a row above the row cap (ilu0_refactor_batch_fits), 2 = static form (its values live in
     // lane-table records)
@@ -3341,64 +3365,36 @@ static int refactor_batch_locked(int32_t count, ilupp_precond *const *members, c
     long long alone_min = kRefactorAloneMin;
     if (const char *e = getenv("ILUPP_REFACTOR_ALONE_MIN")) { const long long v = atoll(e); if (v > 0) alone_min = v; }
     if (S.launched.size() == 1 && members[S.launched[0]]->n >= alone_min && !members[S.launched[0]]->batch_built) { S.route[(size_t)S.launched[0]] = 1; S.launched.clear(); }
-    if (route) for (int32_t i = 0; i < count; ++i) route[i] = S.route[(size_t)i];
+    routes_out(S.route, route);
     const int32_t nl = (int32_t)S.launched.size();
     if (nl > 0) {
-        batch_rtable_reserve(S, nl);
-        std::vector<RefactorDesc> fresh((size_t)nl);
-        std::vector<BatchMember> mv((size_t)count);
-        for (int32_t i = 0; i < count; ++i) mv[(size_t)i] = batch_member(members[i], 0);
-        for (int32_t k = 0; k < nl; ++k) {
-            const int32_t i = S.launched[(size_t)k];
-            ilupp_precond *p = members[i];
-            RefactorDesc &d = fresh[(size_t)k];
-            memset(&d, 0, sizeof(d));
-            d.aptr = d_indptr[i]; d.aidx = d_indices[i]; d.aval = d_data[i];
-            d.lptr = p->Lc.ptr; d.lidx = p->Lc.idx; d.lval = p->Lc.val;
-            d.uptr = p->Uc.ptr; d.uidx = p->Uc.idx; d.uval = p->Uc.val;
-            d.nnzA = p->nnzA; d.n = p->n; d.member = i;
-        }
         // (uploaded again only when a descriptor differs: the same members with their matrices in the same buffers, step after step, upload nothing)
-        if (nl != S.rused || memcmp(S.h_rtable, fresh.data(), sizeof(RefactorDesc) * (size_t)nl) != 0) {
-            ILUPP_HIP(hipEventSynchronize(S.rup_ev));                   // (the upload before this one has read the pinned copy: long over)
-            memcpy(S.h_rtable, fresh.data(), sizeof(RefactorDesc) * (size_t)nl);
-            ILUPP_HIP(hipMemcpyAsync(S.d_rtable, S.h_rtable, sizeof(RefactorDesc) * (size_t)nl, hipMemcpyHostToDevice, bs));
-            ILUPP_HIP(hipEventRecord(S.rup_ev, bs));
-            S.rused = nl;
-        }
-        // the launch behind whatever is still queued on a member's own stream (a single apply or factors() that was not waited for); what
-        // earlier batched launches read of the factors lies on the scratch's stream itself
+        std::vector<RefactorDesc> fresh;
+        fresh.reserve((size_t)nl);
+        for (int32_t i : S.launched) fresh.push_back(refactor_desc(members[i], d_data[i], d_indices[i], d_indptr[i], members[i]->nnzA, i));
+        batch_upload(bs, S.rtable, fresh);
+        // the launch behind whatever is still queued on a member's own stream; what earlier batched launches read of the factors lies on
+        // the scratch's stream itself
         bool stale = false;
-        for (int32_t k = 0; k < nl; ++k) {
-            ilupp_precond *p = members[S.launched[(size_t)k]];
+        for (int32_t i : S.launched) {
+            ilupp_precond *p = members[i];
             stale = stale || p->pkL.valid || p->pkU.valid || p->pkL.pkT || p->pkU.pkT || p->haveT;
             for (const auto &l : p->lvl) stale = stale || l.tried;
-            if (hipStreamQuery(p->stream) == hipSuccess) continue;
-            (void)hipGetLastError();
-            ILUPP_HIP(hipEventRecord(p->sev[1], p->stream));
-            ILUPP_HIP(hipStreamWaitEvent(bs, p->sev[1], 0));
+            batch_join(bs, p);
         }
-        OR_RETURN(ilu0_refactor_batch_launch(bs, nl, S.d_rtable, d_status, lds));
+        OR_RETURN(ilu0_refactor_batch_launch(bs, nl, S.rtable.d, d_status, lds));
+        const std::vector<BatchMember> mv = batch_members(count, members, 0);
         batch_launched(S, mv.data());
         // this launch WRITES the factors: whatever a member's own stream does next (a single apply, factors(), ensure_*) comes after it
-        for (int32_t k = 0; k < nl; ++k) ILUPP_HIP(hipStreamWaitEvent(members[S.launched[(size_t)k]]->stream, S.done_ev, 0));
+        for (int32_t i : S.launched) ILUPP_HIP(hipStreamWaitEvent(members[i]->stream, S.done_ev, 0));
         // copies of the old values go (as in the single path; the non-static packed sweeps too: they are rebuilt at the next single apply,
         // not re-packed per member here).  The pool knows nothing of streams: ONE wait for the whole call before the first free, and none
         // when no member holds such a copy -- the steady state of refactor -> cg_batch -> refactor.
         if (stale) ILUPP_HIP(hipStreamSynchronize(bs));
-        for (int32_t k = 0; k < nl; ++k) {
-            ilupp_precond *p = members[S.launched[(size_t)k]];
+        for (int32_t i : S.launched) {
+            ilupp_precond *p = members[i];
             p->csr_vals = true;
-            p->apply_events_valid = false;
-            st_drop_transposed(&p->pkL, &p->pkU);
-            for (auto &l : p->lvl) l.release();
-            if (p->haveT) {
-                p->LcT.release(); p->UcT.release(); p->sUT.release(); p->sLT.release();
-                if (p->dUT) (void)pool_free(p->dUT);
-                if (p->dLT) (void)pool_free(p->dLT);
-                p->dUT = p->dLT = nullptr; p->haveT = false;
-                p->pkUT.release(); p->pkLT.release(); p->pack_tried[2] = p->pack_tried[3] = false;
-            }
+            drop_old_value_copies(p);
             if (p->pkL.valid) { p->pkL.release(); p->pack_tried[0] = false; }
             if (p->pkU.valid) { p->pkU.release(); p->pack_tried[1] = false; }
         }
@@ -3486,7 +3482,6 @@ int ilu0_create_batch_run(BatchScratch &S, int32_t count, const CreateMember *m,
                           int32_t *route)
 {
     hipStream_t bs = S.stream;
-    if (!S.rup_ev) ILUPP_HIP(hipEventCreateWithFlags(&S.rup_ev, hipEventDisableTiming));
     for (hipEvent_t &e : S.tev) if (!e) ILUPP_HIP(hipEventCreate(&e));
     std::vector<int> rcs((size_t)count, ILUPP_OK);
     std::vector<std::string> msgs((size_t)count);
@@ -3504,47 +3499,33 @@ int ilu0_create_batch_run(BatchScratch &S, int32_t count, const CreateMember *m,
     if (!staged) order_after_caller(bs, S.cev[0]);
     const int32_t nc = (int32_t)cand.size();
     std::vector<int32_t> launched;                   // the members of the create launch
+    std::vector<RefactorDesc> fresh;
     float sym_ms = 0.f, create_ms = 0.f;
     if (nc > 0) {
-        batch_rtable_reserve(S, nc);
-        if (count > S.ccap) {
-            if (S.d_cinfo) { ILUPP_HIP(hipStreamSynchronize(bs)); (void)hipFree(S.d_cinfo); (void)hipFree(S.d_cstat); (void)hipHostFree(S.h_cinfo); S.d_cinfo = nullptr; S.d_cstat = nullptr; S.h_cinfo = nullptr; }
-            S.ccap = 0;
-            const int32_t cap = count < 64 ? 64 : count;
-            ILUPP_HIP(hipMalloc(reinterpret_cast<void **>(&S.d_cinfo), sizeof(CreateInfo) * (size_t)cap));
-            ILUPP_HIP(hipMalloc(reinterpret_cast<void **>(&S.d_cstat), sizeof(int32_t) * (size_t)cap));
-            ILUPP_HIP(hipHostMalloc(reinterpret_cast<void **>(&S.h_cinfo), sizeof(CreateInfo) * (size_t)cap, hipHostMallocDefault));
-            S.ccap = cap;
-        }
-        ILUPP_HIP(hipEventSynchronize(S.rup_ev));                       // (the upload before this one has read the pinned copy)
-        S.rused = 0;                                                    // (the re-factorisation's cached table is overwritten)
+        S.cinfo.reserve(bs, (size_t)count);
+        S.cstat.reserve(bs, (size_t)count);
         // the objects, and the n + 1 row pointers of L and of U the symbolic launch writes
-        for (int32_t k = 0; k < nc; ++k) {
-            const int32_t i = cand[(size_t)k];
+        for (int32_t i : cand) {
             ilupp_precond *p = objs.v[(size_t)i] = new_obj(m[i].n);
             p->kind = KIND_LU; p->nnz_mode = NNZ_GENERIC_LU; p->input_csc = !is_csr;
             for (DevMat *M : {&p->Lc, &p->Uc}) {
                 M->n = m[i].n; M->is_csr = true; M->owns = true;
                 ILUPP_HIP(pool_malloc(&M->ptr, sizeof(int32_t) * (size_t)(m[i].n + 1)));
             }
-            RefactorDesc &d = S.h_rtable[k];
-            memset(&d, 0, sizeof(d));
-            d.aptr = m[i].indptr; d.aidx = m[i].indices; d.aval = m[i].data;
-            d.lptr = p->Lc.ptr; d.uptr = p->Uc.ptr;
-            d.nnzA = m[i].nnz; d.n = m[i].n; d.member = i;
+            fresh.push_back(refactor_desc(p, m[i].data, m[i].indices, m[i].indptr, m[i].nnz, i));
         }
-        ILUPP_HIP(hipMemcpyAsync(S.d_rtable, S.h_rtable, sizeof(RefactorDesc) * (size_t)nc, hipMemcpyHostToDevice, bs));
+        // (sent whatever the table holds, and the re-factorisation's cached table is gone: these descriptors are half filled)
+        batch_upload(bs, S.rtable, fresh, false);
         ILUPP_HIP(hipEventRecord(S.tev[0], bs));
-        OR_RETURN(ilu0_symbolic_batch_launch(bs, nc, S.d_rtable, S.d_cinfo));
+        OR_RETURN(ilu0_symbolic_batch_launch(bs, nc, S.rtable.d, S.cinfo.d));
         ILUPP_HIP(hipEventRecord(S.tev[1], bs));
         // the call's one host wait in front of the numeric launch: all result records with one read-back
-        ILUPP_HIP(hipMemcpyAsync(S.h_cinfo, S.d_cinfo, sizeof(CreateInfo) * (size_t)nc, hipMemcpyDeviceToHost, bs));
+        ILUPP_HIP(hipMemcpyAsync(S.cinfo.h, S.cinfo.d, sizeof(CreateInfo) * (size_t)nc, hipMemcpyDeviceToHost, bs));
         ILUPP_HIP(stream_sync(bs));
         ILUPP_HIP(hipEventElapsedTime(&sym_ms, S.tev[0], S.tev[1]));
-        size_t lds = 0;
         for (int32_t k = 0; k < nc; ++k) {
             const int32_t i = cand[(size_t)k];
-            const CreateInfo &o = S.h_cinfo[k];
+            const CreateInfo &o = S.cinfo.h[k];
             ilupp_precond *p = objs.v[(size_t)i];
             if (o.flags & kCreateNnzDiffers) {
                 rcs[(size_t)i] = ILUPP_ERR_INVALID; msgs[(size_t)i] = "ILU0: the number of stored entries handed in is not indptr[n]";
@@ -3554,9 +3535,7 @@ int ilu0_create_batch_run(BatchScratch &S, int32_t count, const CreateMember *m,
                 rcs[(size_t)i] = ILUPP_ERR_NO_DIAGONAL;
                 msgs[(size_t)i] = "ILU0: structurally missing diagonal entry in row " + std::to_string(o.missing);
             } else {
-                const size_t want = ilu0_refactor_batch_fits(m[i].n, o.max_row_len);
-                if (want == 0) { rt[(size_t)i] = 1; continue; }
-                if (want > lds) lds = want;
+                if (ilu0_refactor_batch_fits(m[i].n, o.max_row_len) == 0) { rt[(size_t)i] = 1; continue; }
                 // exact index and value arrays, and what the object records of the factored matrix
                 p->Lc.nnz = o.nnz_l; p->Uc.nnz = o.nnz_u;
                 for (DevMat *M : {&p->Lc, &p->Uc}) {
@@ -3572,24 +3551,18 @@ int ilu0_create_batch_run(BatchScratch &S, int32_t count, const CreateMember *m,
     for (int32_t i = 0; i < count; ++i) failed = failed || rcs[(size_t)i] != ILUPP_OK;
     const int32_t nl = failed ? 0 : (int32_t)launched.size();
     if (nl > 0) {
-        for (int32_t k = 0; k < nl; ++k) {
-            const int32_t i = launched[(size_t)k];
-            const ilupp_precond *p = objs.v[(size_t)i];
-            RefactorDesc &d = S.h_rtable[k];
-            memset(&d, 0, sizeof(d));
-            d.aptr = m[i].indptr; d.aidx = m[i].indices; d.aval = m[i].data;
-            d.lptr = p->Lc.ptr; d.lidx = p->Lc.idx; d.lval = p->Lc.val;
-            d.uptr = p->Uc.ptr; d.uidx = p->Uc.idx; d.uval = p->Uc.val;
-            d.nnzA = p->nnzA; d.n = p->n; d.member = i;
-        }
         // (this table is what the batched re-factorisation of the same members from the same buffers describes: its cache may hit)
-        ILUPP_HIP(hipMemcpyAsync(S.d_rtable, S.h_rtable, sizeof(RefactorDesc) * (size_t)nl, hipMemcpyHostToDevice, bs));
-        ILUPP_HIP(hipEventRecord(S.rup_ev, bs));
-        S.rused = nl;
+        fresh.clear();
         size_t lds = 0;
-        for (int32_t i : launched) { const size_t want = ilu0_refactor_batch_fits(m[i].n, objs.v[(size_t)i]->max_row_len); if (want > lds) lds = want; }
+        for (int32_t i : launched) {
+            const ilupp_precond *p = objs.v[(size_t)i];
+            fresh.push_back(refactor_desc(p, m[i].data, m[i].indices, m[i].indptr, p->nnzA, i));
+            const size_t want = ilu0_refactor_batch_fits(m[i].n, p->max_row_len);
+            if (want > lds) lds = want;
+        }
+        batch_upload(bs, S.rtable, fresh);
         ILUPP_HIP(hipEventRecord(S.tev[2], bs));
-        OR_RETURN(ilu0_create_batch_launch(bs, nl, S.d_rtable, S.d_cstat, lds));
+        OR_RETURN(ilu0_create_batch_launch(bs, nl, S.rtable.d, S.cstat.d, lds));
         ILUPP_HIP(hipEventRecord(S.tev[3], bs));
         // whatever a member's own stream does next (an apply, factors(), ensure_*) comes after the launch that writes its factors
         ILUPP_HIP(hipEventRecord(S.done_ev, bs));
@@ -3615,7 +3588,7 @@ int ilu0_create_batch_run(BatchScratch &S, int32_t count, const CreateMember *m,
     if (nl > 0) {
         // a construction synchronises: the launch is over when the call returns
         std::vector<int32_t> st((size_t)count, 0);
-        ILUPP_HIP(d2h_async(bs, st.data(), S.d_cstat, sizeof(int32_t) * (size_t)count));
+        ILUPP_HIP(d2h_async(bs, st.data(), S.cstat.d, sizeof(int32_t) * (size_t)count));
         ILUPP_HIP(stream_sync(bs));
         ILUPP_HIP(hipEventElapsedTime(&create_ms, S.tev[2], S.tev[3]));
         for (int32_t i : launched) {
@@ -3626,7 +3599,7 @@ int ilu0_create_batch_run(BatchScratch &S, int32_t count, const CreateMember *m,
             p->tm.analysis_ms = sym_ms; p->tm.numeric_ms = create_ms; p->tm.numeric_kernel_ms = create_ms;
         }
     }
-    if (route) for (int32_t i = 0; i < count; ++i) route[i] = rt[(size_t)i];
+    routes_out(rt, route);
     int first = ILUPP_OK;
     for (int32_t i = 0; i < count; ++i) {
         if (status) status[i] = rcs[(size_t)i];
@@ -3650,7 +3623,7 @@ int ilupp_hip_ilu0_create_batch_device(int32_t count, const double *const *d_dat
     for (int32_t i = 0; i < count; ++i) { out[i] = nullptr; if (status) status[i] = ILUPP_OK; if (route) route[i] = 0; }
     std::vector<CreateMember> m((size_t)count);
     for (int32_t i = 0; i < count; ++i) {
-        if (n[i] > 0 && (!d_data[i] || !d_indices[i] || !d_indptr[i])) { set_error("null argument"); return ILUPP_ERR_INVALID; }
+        if (n[i] > 0) OR_RETURN(batch_matrix_arrays(d_data, d_indices, d_indptr, i));
         m[(size_t)i].data = d_data[i]; m[(size_t)i].indices = d_indices[i]; m[(size_t)i].indptr = d_indptr[i];
         m[(size_t)i].n = n[i]; m[(size_t)i].nnz = nnz[i];
     }
@@ -3667,7 +3640,7 @@ int ilupp_hip_ilu0_create_batch(int32_t count, const double *const *data, const 
     if (count < 0 || !data || !indices || !indptr || !n || !out) { set_error("null argument"); return ILUPP_ERR_INVALID; }
     for (int32_t i = 0; i < count; ++i) { out[i] = nullptr; if (status) status[i] = ILUPP_OK; if (route) route[i] = 0; }
     for (int32_t i = 0; i < count; ++i)
-        if (n[i] > 0 && (!data[i] || !indices[i] || !indptr[i])) { set_error("null argument"); return ILUPP_ERR_INVALID; }
+        if (n[i] > 0) OR_RETURN(batch_matrix_arrays(data, indices, indptr, i));
     if (count == 0) return ILUPP_OK;
     std::lock_guard<std::mutex> lk(g_batch_mu);
     BatchScratch &S = batch_scratch();
@@ -3685,20 +3658,20 @@ int ilupp_hip_ilu0_create_batch(int32_t count, const double *const *data, const 
         at[(size_t)i] = total;
         total += (size_t)nz + words(nz) + words((int64_t)n[i] + 1);
     }
-    batch_stage_reserve(S, total > 0 ? total : 1);
+    S.stage.reserve(S.stream, total > 0 ? total : 1);
     for (int32_t i = 0; i < count; ++i) {
         CreateMember &c = m[(size_t)i];
         if (c.n <= 0 || c.nnz < 0 || c.nnz + (int64_t)c.n > INT32_MAX) continue;
         const size_t nz = (size_t)c.nnz, o_idx = at[(size_t)i] + nz, o_ptr = o_idx + words(c.nnz);
-        memcpy(S.h_stage + at[(size_t)i], data[i], sizeof(double) * nz);
-        memcpy(S.h_stage + o_idx, indices[i], sizeof(int32_t) * nz);
-        memcpy(S.h_stage + o_ptr, indptr[i], sizeof(int32_t) * ((size_t)c.n + 1));
-        c.data = S.d_stage + at[(size_t)i];
-        c.indices = reinterpret_cast<const int32_t *>(S.d_stage + o_idx);
-        c.indptr = reinterpret_cast<const int32_t *>(S.d_stage + o_ptr);
+        memcpy(S.stage.h + at[(size_t)i], data[i], sizeof(double) * nz);
+        memcpy(S.stage.h + o_idx, indices[i], sizeof(int32_t) * nz);
+        memcpy(S.stage.h + o_ptr, indptr[i], sizeof(int32_t) * ((size_t)c.n + 1));
+        c.data = S.stage.d + at[(size_t)i];
+        c.indices = reinterpret_cast<const int32_t *>(S.stage.d + o_idx);
+        c.indptr = reinterpret_cast<const int32_t *>(S.stage.d + o_ptr);
         c.h_indices = indices[i]; c.h_indptr = indptr[i];
     }
-    if (total > 0) ILUPP_HIP(hipMemcpyAsync(S.d_stage, S.h_stage, sizeof(double) * total, hipMemcpyHostToDevice, S.stream));
+    if (total > 0) ILUPP_HIP(hipMemcpyAsync(S.stage.d, S.stage.h, sizeof(double) * total, hipMemcpyHostToDevice, S.stream));
     ILUPP_HIP(hipEventRecord(S.in_ev, S.stream));
     const int rc = ilu0_create_batch_run(S, count, m.data(), is_csr, true, out, status, route);
     // (the staged matrices are read by nothing once the call is over: every member's construction has been waited for)
