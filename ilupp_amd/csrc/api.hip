@@ -437,8 +437,8 @@ static void arm_apply(ilupp_precond *p)
     p->ctrl_armed = true; p->pkL.xch_armed = p->pkU.xch_armed = true;
 }
 
-// numeric phase with whatever machinery the analysis could set up; leaves the sweep records' values in place
-static int ilu0_numeric_any(ilupp_precond *p, const DevMat &A, bool have_prog, float *kms)
+// numeric phase with whatever machinery the analysis could set up; leaves the sweep records' values in place (gp: common.h, GridProof)
+static int ilu0_numeric_any(ilupp_precond *p, const DevMat &A, bool have_prog, float *kms, GridProof *gp)
 {
     hipStream_t st = p->stream;
     p->ctrl_armed = false; p->pkL.xch_armed = p->pkU.xch_armed = false;      // (the factor kernels use the control words and the forward exchange)
@@ -446,7 +446,7 @@ static int ilu0_numeric_any(ilupp_precond *p, const DevMat &A, bool have_prog, f
     if (p->flm.built) {
         // (flm.built means the static form: round 1's record-decoding level-major FACTOR kernel, which only matrices the static form takes
         // ever reached -- and then only under ILUPP_NO_STATIC --, was removed in round 5)
-        rc = ilu0_numeric_st(st, A, &p->pkL, &p->pkU, &p->flm, p->ctrl, kms, p->ev[4], p->ev[5]);
+        rc = ilu0_numeric_st(st, A, &p->pkL, &p->pkU, &p->flm, p->ctrl, kms, p->ev[4], p->ev[5], gp);
         p->csr_vals = false;
         return rc;
     }
@@ -469,83 +469,56 @@ static int ilu0_numeric_any(ilupp_precond *p, const DevMat &A, bool have_prog, f
     return rc;
 }
 
-// ILU(0) of the row-major view held in A (device).  Fills p->Lc/Uc, schedules and timings.
-int ilu0_factor(ilupp_precond *p, const DevMat &A, const int32_t *head)
+// The steps of ilu0_factor, in its order.  A grid attempt begins (false: no guess, *gp stays NOT_A_GRID):
+// a matrix whose row 0 and entry count are those of a lexicographic box-grid stencil (grid.hip): the row blocks follow from the
+// three dimensions, and ONE streaming kernel on the side stream proves the guess for every row while the lane tables are built.
+// Its verdict comes home with the construction's last read-back.  (Measured at 256^3: k_grid_lanes only stores and the skew fixpoint
+// lives in LDS, so they lose little next to the 4.6 TB/s stream of the proof; DESIGN.md section 4.0.2 has the other placements.)
+// (a grid whose factor launch holds one workgroup per CU: that launch proves the pattern itself, on the CUs whose tile has ended --
+// st_wave.hip: wa_tail_proof --, and nothing runs on the side stream)
+static bool grid_attempt_begin(ilupp_precond *p, const DevMat &A, const int32_t *head, GridProof *gp, int max_wgs)
+{
+    if (head == nullptr || p->side == nullptr || !grid_guess(A.n, A.nnz, head, &gp->g)) return false;
+    gp->how = wx_tail_proof_wanted(gp->g.ny, gp->g.nz) ? GridProof::FACTOR_LAUNCH : GridProof::SIDE_STREAM;
+    gp->side = p->side; gp->fork_ev = p->jev[0]; gp->join_ev = p->jev[1]; gp->d_verdict = p->ctrl + 8;
+    if (p->verdict_clean) p->verdict_clean = false;
+    else ILUPP_HIP(hipMemsetAsync(gp->d_verdict, 0, sizeof(int32_t), p->stream));
+    if (gp->how == GridProof::SIDE_STREAM) gp->queue(p->stream, A);
+    grid_schedules(p->stream, A, gp->g, &p->Lc, &p->Uc, &p->sA, &p->sU, &p->max_row_len, max_wgs);
+    return true;
+}
+// one pass over A's pattern: row counts of L and U, diagonal check, and the factor-sweep schedules (L shares A's
+// forward cuts and U its backward cuts: same strictly-lower / strictly-upper patterns)
+static int general_symbolic(ilupp_precond *p, const DevMat &A, int max_wgs)
+{
+    int32_t missing = -1;
+    const int rc = ilu0_symbolic_and_schedule(p->stream, A, &p->Lc, &p->Uc, &missing, p->max_lanes, &p->sA, &p->sU, &p->max_row_len);
+    if (rc == ILUPP_ERR_NO_DIAGONAL) set_error("ILU0: structurally missing diagonal entry in row " + std::to_string(missing));
+    if (rc) return rc;
+    choose_tiling_pair(p->stream, A.ptr, A.idx, &p->sA, &p->sU, max_wgs);
+    finish_chains(&p->sA, &p->sU);             // (the read-back ilu0_symbolic_and_schedule queued came with the tiling's wait)
+    return ILUPP_OK;
+}
+// nothing built on a grid guess survives it (forget: nor the shape remembered for this index array); the general pass decides
+static void drop_grid_guess(ilupp_precond *p, const GridProof &gp, const char *why, const DevMat *forget)
+{
+    if (getenv("ILUPP_DEBUG")) fprintf(stderr, "[ilupp] grid guess %d x %d x %d dropped (%s)\n", gp.g.nx, gp.g.ny, gp.g.nz, why);
+    p->pkL.release(); p->pkU.release(); p->flm.release();
+    p->sA.release(); p->sU.release();
+    p->sA = Schedule(); p->sU = Schedule();
+    p->grid_path = false;
+    if (forget) grid_shape_forget(forget->n, forget->nnz, forget->idx);
+}
+
+// CSR patterns of L and U (ILU0.hpp:85-98).  The level-major kernels never read them (they are for factors() and the
+// generic transposed solves).  (Running this pass on a side stream next to the factor kernel cost the kernel more --
+// 2.0 -> 2.5 ms -- than the pass takes, 0.28 ms.)  Static form: nothing here; row pointers, column indices and values all
+// come out of the records when somebody asks (ensure_csr_values).  lm: the static form took the matrix.
+static int csr_and_level_fallbacks(ilupp_precond *p, const DevMat &A, bool lm, bool *have_prog)
 {
     hipStream_t st = p->stream;
-    hipEvent_t a0 = p->ev[0], a1 = p->ev[1], a2 = p->ev[2];
-    p->nnzA = A.nnz;
-    ILUPP_HIP(hipEventRecord(a0, st));
-    int32_t missing = -1;
-    const int max_wgs = p->max_lanes / kThreads;
-    int rc = ILUPP_OK;
-    // A matrix whose row 0 and entry count are those of a lexicographic box-grid stencil (grid.hip): the row blocks follow from the
-    // three dimensions, and ONE streaming kernel on the side stream proves the guess for every row while the lane tables are built.
-    // Its verdict comes home with the construction's last read-back.  (Measured at 256^3: k_grid_lanes only stores and the skew fixpoint
-    // lives in LDS, so they lose little next to the 4.6 TB/s stream of the proof; DESIGN.md section 4.0.2 has the other placements.)
-    GridDims gd = {0, 0, 0};
-    bool grid = head != nullptr && p->side != nullptr && grid_guess(A.n, A.nnz, head, &gd);
-    int32_t grid_bad = 0;
-    bool lm = false;
-    // (a grid whose factor launch holds one workgroup per CU: that launch proves the pattern itself, on the CUs whose tile has ended --
-    // st_wave.hip: wa_tail_proof --, and nothing runs on the side stream)
-    const bool tail = grid && wx_tail_proof_wanted(gd.ny, gd.nz);
-    for (;;) {
-        if (grid) {
-            if (p->verdict_clean) p->verdict_clean = false;
-            else ILUPP_HIP(hipMemsetAsync(p->ctrl + 8, 0, sizeof(int32_t), st));
-            if (!tail) {
-                ILUPP_HIP(hipEventRecord(p->jev[0], st));
-                ILUPP_HIP(hipStreamWaitEvent(p->side, p->jev[0], 0));
-                grid_check_launch(p->side, A, gd, p->ctrl + 8);
-                ILUPP_HIP(hipEventRecord(p->jev[1], p->side));
-            }
-            grid_schedules(st, A, gd, &p->Lc, &p->Uc, &p->sA, &p->sU, &p->max_row_len, max_wgs);
-        } else {
-            // one pass over A's pattern: row counts of L and U, diagonal check, and the factor-sweep schedules (L shares A's
-            // forward cuts and U its backward cuts: same strictly-lower / strictly-upper patterns)
-            rc = ilu0_symbolic_and_schedule(st, A, &p->Lc, &p->Uc, &missing, p->max_lanes, &p->sA, &p->sU, &p->max_row_len);
-            if (rc == ILUPP_ERR_NO_DIAGONAL) {
-                set_error("ILU0: structurally missing diagonal entry in row " + std::to_string(missing));
-                return rc;
-            }
-            if (rc) return rc;
-            choose_tiling_pair(st, A.ptr, A.idx, &p->sA, &p->sU, max_wgs);
-            finish_chains(&p->sA, &p->sU);             // (the read-back ilu0_symbolic_and_schedule queued came with the tiling's wait)
-        }
-        // (a grid's slot tables are filled together with its lane templates: grid.hip, k_grid_lanes; ILUPP_GRID_TABLES=0: by the general kernels)
-        static const bool grid_tables = []() { const char *e = getenv("ILUPP_GRID_TABLES"); return !(e && atoi(e) == 0); }();
-        build_slot_tables(st, &p->sA, true, !(grid && grid_tables));
-        build_slot_tables(st, &p->sU, false, !(grid && grid_tables));
-        p->compact = schedule_is_compact(p->sA) && schedule_is_compact(p->sU);
-        // static form first (lane tables, values-only records: st.hip; no descriptor words, hence no limit on block size or number
-        // of slots), then the record-decoding level-major form
-        lm = st_analyse_ilu0(st, A, p->sA, p->sU, &p->pkL, &p->pkU, &p->flm, nullptr, (grid && grid_tables) ? &gd : nullptr);
-        if (grid && !(lm && p->flm.stat && p->flm.direct) && p->no_general_retry) {
-            ILUPP_HIP(hipStreamSynchronize(p->side));
-            return ILUPP_ERR_UNSUPPORTED;
-        }
-        if (grid && !(lm && p->flm.stat && p->flm.direct)) {
-            // a grid the static direct-feed form does not take (or not the guessed grid: the lane templates of sampled rows disagree):
-            // nothing built on the guess survives; the general pass decides
-            if (getenv("ILUPP_DEBUG")) fprintf(stderr, "[ilupp] grid guess %d x %d x %d dropped (static analysis declined)\n", gd.nx, gd.ny, gd.nz);
-            ILUPP_HIP(hipStreamSynchronize(p->side));
-            p->pkL.release(); p->pkU.release(); p->flm.release();
-            p->sA.release(); p->sU.release();
-            p->sA = Schedule(); p->sU = Schedule();
-            grid = false;
-            continue;
-        }
-        break;
-    }
-    p->grid_path = grid;
-    bool have_prog = false;
-    // CSR patterns of L and U (ILU0.hpp:85-98).  The level-major kernels never read them (they are for factors() and the
-    // generic transposed solves).  (Running this pass on a side stream next to the factor kernel cost the kernel more --
-    // 2.0 -> 2.5 ms -- than the pass takes, 0.28 ms.)  Static form: nothing here; row pointers, column indices and values all
-    // come out of the records when somebody asks (ensure_csr_values).
     if (!p->flm.stat) {
-        rc = ilu0_csr_ptrs(st, A, &p->Lc, &p->Uc);
+        const int rc = ilu0_csr_ptrs(st, A, &p->Lc, &p->Uc);
         if (rc) return rc;
         ilu0_write_patterns(st, A, &p->Lc, &p->Uc);
     }
@@ -569,7 +542,7 @@ int ilu0_factor(ilupp_precond *p, const DevMat &A, const int32_t *head)
     if (p->compact && !lm && !by_level) {
         // not a short-row matrix (or an irregular one): descriptors, update program and the CSR-streaming kernels
         if (!(A.nnz >= 16 && build_ilu0_program_f3(st, A, p->Uc, p->sA, &p->prog_f3)))
-            have_prog = build_ilu0_program(st, A, p->Uc, p->sA, &p->prog);
+            *have_prog = build_ilu0_program(st, A, p->Uc, p->sA, &p->prog);
         make_desc(st, p->Lc, p->sA, &p->dL);
         make_desc(st, p->Uc, p->sU, &p->dU);
         // the sweeps may still have a level-major form (records from the descriptors, values by a pass after the factor kernel)
@@ -582,79 +555,100 @@ int ilu0_factor(ilupp_precond *p, const DevMat &A, const int32_t *head)
         }
         if (!(p->pkL.valid && p->pkU.valid)) { p->pkL.release(); p->pkU.release(); }
     }
-    ILUPP_HIP(hipEventRecord(a1, st));
+    return ILUPP_OK;
+}
+
+// The verdict on a grid attempt: 0 = proven, 1 = the pattern differs, 2 = a size was mispredicted.  The factor kernel's own read-back took the verdict word along, or it is
+// read here, behind the proof (queued now if the factor kernel that ran was not the one that proves).  waited: for that read-back, already; else for the stream, here.
+static int32_t grid_verdict(ilupp_precond *p, const DevMat &A, GridProof *gp, bool waited)
+{
+    int32_t bad = gp->verdict;
+    if (bad < 0) {
+        gp->settle(p->stream, A);
+        ILUPP_HIP(d2h_async(p->stream, &bad, gp->d_verdict, sizeof(int32_t)));
+    }
+    if (!waited) ILUPP_HIP(stream_sync(p->stream));
+    const FactorLM &f = p->flm;
+    if (!f.spec || bad != 0) return bad;
+    // the sizes the lane-table kernels were launched with were predicted (st.hip: st_analyse_ilu0); what the device found is here now
+    bool same = f.chk_hl[0] == 0 && f.chk_hu[0] == 0 && f.chk_hu[3] == 0 && f.chk_hl[8] == 0 && f.chk_hl[9] == 0 && f.chk_hu[9] == 0 && f.chk_hl[10] == 0;
+    same = same && f.chk_hl[1] == f.pred[0] && f.chk_hu[1] == f.pred[0] && f.chk_hl[2] == f.pred[1] && f.chk_hu[2] == f.pred[1];
+    same = same && f.chk_xtot[0] == f.pred[2] && f.chk_xtot[2] == f.pred[2] && f.chk_xtot[1] == f.pred[3] && f.chk_xtot[3] == f.pred[3];
+    if (!same && getenv("ILUPP_DEBUG"))
+        fprintf(stderr, "[ilupp] grid %d x %d x %d: predicted sizes %d %d %d %d, found %d/%d %d/%d %d/%d %d/%d, flags %d %d %d %d %d %d %d: redone\n", gp->g.nx, gp->g.ny, gp->g.nz,
+                f.pred[0], f.pred[1], f.pred[2], f.pred[3], f.chk_hl[1], f.chk_hu[1], f.chk_hl[2], f.chk_hu[2], f.chk_xtot[0], f.chk_xtot[2], f.chk_xtot[1], f.chk_xtot[3],
+                f.chk_hl[0], f.chk_hu[0], f.chk_hu[3], f.chk_hl[8], f.chk_hl[9], f.chk_hu[9], f.chk_hl[10]);
+    return same ? 0 : 2;
+}
+
+// The two phases' times; the numeric phase ends at `end`.  kernel_events (a grid whose factor kernel is the wave-exchange one): the proof ends in front of the factor
+// kernel, behind the launches that clear its control words, so the analysis phase lasts until the event in front of that kernel, ev[4], not until ev[1].
+static void factor_timing(ilupp_precond *p, bool kernel_events, hipEvent_t end, float kms)
+{
+    hipEvent_t mid = kernel_events ? p->ev[4] : p->ev[1];
+    ILUPP_HIP(hipEventElapsedTime(&p->tm.analysis_ms, p->ev[0], mid));
+    ILUPP_HIP(hipEventElapsedTime(&p->tm.numeric_ms, mid, end));
+    p->tm.numeric_kernel_ms = kms;
+}
+
+// ILU(0) of the row-major view held in A (device).  Fills p->Lc/Uc, schedules and timings.
+int ilu0_factor(ilupp_precond *p, const DevMat &A, const int32_t *head)
+{
+    hipStream_t st = p->stream;
+    p->nnzA = A.nnz;
+    ILUPP_HIP(hipEventRecord(p->ev[0], st));
+    const int max_wgs = p->max_lanes / kThreads;
+    GridProof gp;
+    bool grid = grid_attempt_begin(p, A, head, &gp, max_wgs), lm = false;
+    for (;;) {
+        if (!grid) { const int rc = general_symbolic(p, A, max_wgs); if (rc) return rc; }
+        // (a grid's slot tables are filled together with its lane templates: grid.hip, k_grid_lanes; ILUPP_GRID_TABLES=0: by the general kernels)
+        static const bool grid_tables = []() { const char *e = getenv("ILUPP_GRID_TABLES"); return !(e && atoi(e) == 0); }();
+        build_slot_tables(st, &p->sA, true, !(grid && grid_tables));
+        build_slot_tables(st, &p->sU, false, !(grid && grid_tables));
+        p->compact = schedule_is_compact(p->sA) && schedule_is_compact(p->sU);
+        // static form first (lane tables, values-only records: st.hip; no descriptor words, hence no limit on block size or number
+        // of slots), then the record-decoding level-major form
+        lm = st_analyse_ilu0(st, A, p->sA, p->sU, &p->pkL, &p->pkU, &p->flm, (grid && grid_tables) ? &gp.g : nullptr);
+        if (!grid || (lm && p->flm.stat && p->flm.direct)) break;
+        // a grid the static direct-feed form does not take (or not the guessed grid: the lane templates of sampled rows disagree)
+        ILUPP_HIP(hipStreamSynchronize(p->side));
+        if (p->no_general_retry) return ILUPP_ERR_UNSUPPORTED;
+        drop_grid_guess(p, gp, "static analysis declined", nullptr);
+        gp = GridProof();
+        grid = false;
+    }
+    p->grid_path = grid;
+    bool have_prog = false;
+    int rc = csr_and_level_fallbacks(p, A, lm, &have_prog);
+    if (rc) return rc;
+    ILUPP_HIP(hipEventRecord(p->ev[1], st));
     float kms = 0.f;
     // (the factor kernel's own read-back waits for the proof and takes its verdict along: no round trip of its own)
-    const bool wx_numeric = p->flm.built && p->flm.stat && p->flm.direct && p->flm.wxf;
+    const bool wx_numeric = p->flm.built && p->flm.stat && ilu0_numeric_st_is_wx(p->pkL, p->flm);
     // (the factor kernel waits for the proof -- it lives on short hand-over latencies and loses more next to the proof's 4.6 TB/s
     // stream than the wait costs --, but what is queued in front of it, the clearing of its control words and exchange, does not;
     // with the lane tables in closed form the proof is what the analysis phase lasts)
     // (... unless that kernel proves the pattern itself, behind its tiles: then it waits for nothing, and the analysis phase is the table chain)
-    p->pkL.join_ev = (grid && wx_numeric && !tail) ? p->jev[1] : nullptr;
-    p->pkL.tail_proof = grid && tail && wx_numeric;
-    p->pkL.tail_g[0] = gd.nx; p->pkL.tail_g[1] = gd.ny; p->pkL.tail_g[2] = gd.nz;
-    bool proof_queued = !tail;                      // (on the side stream, above)
-    if (grid && !wx_numeric) {
-        if (tail) { grid_check_launch(st, A, gd, p->ctrl + 8); proof_queued = true; }      // (another factor kernel runs: the proof here and now)
-        else ILUPP_HIP(hipStreamWaitEvent(st, p->jev[1], 0));
-    }
-    p->pkL.join_verdict = -1;                       // (-1: nobody has read the verdict yet)
+    if (grid && !wx_numeric) gp.settle(st, A);      // (another factor kernel runs: the proof in front of it, here and now if the factor launch was to hold it)
     // (... and queues the arming of the first apply behind that read-back; the speculation's leftovers -- pending read-backs of the lane
     // tables' flags -- lie in front of it too)
-    if (wx_numeric && p->jev[0]) { p->pkL.arm = [](void *c) { arm_apply(static_cast<ilupp_precond *>(c)); }; p->pkL.arm_ctx = p; p->pkL.arm_ev = p->jev[0]; }
-    rc = ilu0_numeric_any(p, A, have_prog, &kms);
-    p->pkL.arm = nullptr; p->pkL.arm_ctx = nullptr; p->pkL.arm_ev = nullptr;
-    p->pkL.join_ev = nullptr;
-    p->pkL.tail_proof = false;
+    if (wx_numeric && p->jev[0]) { gp.arm = [](void *c) { arm_apply(static_cast<ilupp_precond *>(c)); }; gp.arm_ctx = p; gp.arm_ev = p->jev[0]; }
+    rc = ilu0_numeric_any(p, A, have_prog, &kms, &gp);
     // (the wave-exchange factor kernel's own read-back has been waited for -- through an event, so that what it queued behind it, the
-    // arming of the first apply, runs on: no wait for the whole stream here then)
-    const bool waited = wx_numeric && p->pkL.join_verdict >= 0;
-    if (!waited) ILUPP_HIP(hipEventRecord(a2, st));
-    if (grid && p->pkL.join_verdict >= 0) {
-        grid_bad = p->pkL.join_verdict;
-    } else if (grid) {
-        if (!tail) ILUPP_HIP(hipStreamWaitEvent(st, p->jev[1], 0));
-        else if (!proof_queued) grid_check_launch(st, A, gd, p->ctrl + 8);      // (the factor kernel that ran was not the one that proves)
-        ILUPP_HIP(d2h_async(st, &grid_bad, p->ctrl + 8, sizeof(int32_t)));
-    }
-    if (!waited) ILUPP_HIP(stream_sync(st));
-    if (waited) a2 = p->ev[5];                        // (recorded behind the factor kernel)
-    if (grid && p->flm.spec && grid_bad == 0) {
-        // the sizes the lane-table kernels were launched with were predicted (st.hip: st_analyse_ilu0); what the device found is here now
-        const FactorLM &f = p->flm;
-        bool same = f.chk_hl[0] == 0 && f.chk_hu[0] == 0 && f.chk_hu[3] == 0 && f.chk_hl[8] == 0 && f.chk_hl[9] == 0 && f.chk_hu[9] == 0 && f.chk_hl[10] == 0;
-        same = same && f.chk_hl[1] == f.pred[0] && f.chk_hu[1] == f.pred[0] && f.chk_hl[2] == f.pred[1] && f.chk_hu[2] == f.pred[1];
-        same = same && f.chk_xtot[0] == f.pred[2] && f.chk_xtot[2] == f.pred[2] && f.chk_xtot[1] == f.pred[3] && f.chk_xtot[3] == f.pred[3];
-        if (!same) {
-            if (getenv("ILUPP_DEBUG"))
-                fprintf(stderr, "[ilupp] grid %d x %d x %d: predicted sizes %d %d %d %d, found %d/%d %d/%d %d/%d %d/%d, flags %d %d %d %d %d %d %d: redone\n", gd.nx, gd.ny, gd.nz,
-                        f.pred[0], f.pred[1], f.pred[2], f.pred[3], f.chk_hl[1], f.chk_hu[1], f.chk_hl[2], f.chk_hu[2], f.chk_xtot[0], f.chk_xtot[2], f.chk_xtot[1], f.chk_xtot[3],
-                        f.chk_hl[0], f.chk_hu[0], f.chk_hu[3], f.chk_hl[8], f.chk_hl[9], f.chk_hu[9], f.chk_hl[10]);
-            grid_bad = 2;
-        }
-    }
-    if (grid && grid_bad != 0) {
-        // the matrix only began like a grid (or a size was mispredicted): everything built on the guess is dropped, the general pass runs
-        if (getenv("ILUPP_DEBUG")) fprintf(stderr, "[ilupp] grid guess %d x %d x %d dropped (%s)\n", gd.nx, gd.ny, gd.nz, grid_bad == 2 ? "sizes mispredicted" : "pattern differs");
-        p->pkL.release(); p->pkU.release(); p->flm.release();
-        p->sA.release(); p->sU.release();
-        p->sA = Schedule(); p->sU = Schedule();
-        p->grid_path = false;
-        grid_shape_forget(A.n, A.nnz, A.idx);
+    // arming of the first apply, runs on: no wait for the whole stream here then; ev[5] was recorded behind that kernel)
+    const bool waited = wx_numeric && gp.verdict >= 0;
+    if (!waited) ILUPP_HIP(hipEventRecord(p->ev[2], st));
+    const int32_t grid_bad = grid ? grid_verdict(p, A, &gp, waited) : 0;
+    if (!grid && !waited) ILUPP_HIP(stream_sync(st));
+    if (grid_bad != 0) {
+        // the matrix only began like a grid (or a size was mispredicted): the general pass runs
+        drop_grid_guess(p, gp, grid_bad == 2 ? "sizes mispredicted" : "pattern differs", &A);
         if (p->no_general_retry) return ILUPP_ERR_UNSUPPORTED;
         return ilu0_factor(p, A, nullptr);
     }
-    if (grid && rc == ILUPP_OK) grid_shape_remember(A.n, A.nnz, gd, A.idx);
-    if (grid && wx_numeric && rc == ILUPP_OK) {
-        // (the proof ends in front of the factor kernel, behind the launches that clear its control words: the analysis phase lasts until
-        // the event in front of that kernel, ev[4], not until a1)
-        ILUPP_HIP(hipEventElapsedTime(&p->tm.analysis_ms, a0, p->ev[4]));
-        ILUPP_HIP(hipEventElapsedTime(&p->tm.numeric_ms, p->ev[4], a2));
-    } else {
-        ILUPP_HIP(hipEventElapsedTime(&p->tm.analysis_ms, a0, a1));
-        ILUPP_HIP(hipEventElapsedTime(&p->tm.numeric_ms, a1, a2));
-    }
-    p->tm.numeric_kernel_ms = kms;
+    if (grid && rc == ILUPP_OK) grid_shape_remember(A.n, A.nnz, gp.g, A.idx);
+    factor_timing(p, grid && wx_numeric && rc == ILUPP_OK, waited ? p->ev[5] : p->ev[2], kms);
     if (rc == ILUPP_ERR_TIMEOUT) set_error("ILU0: dependency wait timed out (invalid structure?)");
     if (rc == ILUPP_OK && !p->ctrl_armed) arm_apply(p);
     return rc;
@@ -1140,7 +1134,7 @@ int ilu0_refactor_single(ilupp_precond *p, const double *d_data, const int32_t *
     hipStream_t st = p->stream;
     ILUPP_HIP(hipEventRecord(p->ev[1], st));
     float kms = 0.f;
-    int rc = ilu0_numeric_any(p, A, p->prog.prog != nullptr, &kms);
+    int rc = ilu0_numeric_any(p, A, p->prog.prog != nullptr, &kms, nullptr);
     ILUPP_HIP(hipEventRecord(p->ev[2], st));
     ILUPP_HIP(stream_sync(st));
     ILUPP_HIP(hipEventElapsedTime(&p->tm.numeric_ms, p->ev[1], p->ev[2]));

@@ -150,19 +150,6 @@ struct PackedSweep {
     // static sweeps made from a pair of stored triangular factors (st_analyse_pair): the forward sweep divides by its stored
     // diagonal; the backward sweep accumulates in descending column order when `desc` (a row-stored lower factor used transposed)
     bool pair = false, desc = false;
-    // (forward sweep of an ILU(0) whose row blocks were guessed, grid.hip) the proof's end on its side stream and its verdict word, ctrl[8]:
-    // the factor kernel waits for the one (behind the launches that prepare it) and its own read-back takes the other along
-    hipEvent_t join_ev = nullptr;
-    int32_t join_verdict = 0;
-    // ... or no proof has been launched at all (tail_proof: st_wave.hip's wx_tail_proof_wanted said the factor launch will hold one workgroup
-    // per CU): the factor kernel's workgroups prove the grid tail_g = (nx, ny, nz) themselves, behind their tiles (st_wave.hip: wa_tail_proof)
-    bool tail_proof = false;
-    int32_t tail_g[3] = {0, 0, 0};
-    // (forward sweep of a static ILU(0)) what the factor kernel's launch is followed by, behind its read-back and in front of the wait for
-    // it: the arming of the first apply (api.hip: arm_apply) -- `arm` runs with `arm_ctx`, the wait is for `arm_ev` instead of the stream
-    void (*arm)(void *) = nullptr;
-    void *arm_ctx = nullptr;
-    hipEvent_t arm_ev = nullptr;
     mutable bool xch_armed = false;     // the exchange buffer is all-sentinel already (api.hip: arm_apply, behind the previous call's last wait): the sweep need not fill it
     void release();
 };
@@ -325,6 +312,28 @@ bool grid_shape_recall(int32_t n, int64_t nnz, GridDims *g, const void *idx);
 void grid_shape_remember(int32_t n, int64_t nnz, const GridDims &g, const void *idx);
 void grid_shape_forget(int32_t n, int64_t nnz, const void *idx);
 void grid_check_launch(hipStream_t side, const DevMat &A, const GridDims &g, int32_t *d_bad);
+// What ONE construction call (api.hip: ilu0_factor) and the factor-kernel driver (st_wave.hip: ilu0_numeric_wx) hand each other about the
+// proof of a guessed grid and the end of the factor launch.  It lives for that call; a re-factorisation hands the drivers nullptr.
+struct GridProof {
+    // in: how g's pattern is proven.  SIDE_STREAM: by k_grid_check on `side`, between fork_ev and join_ev, beside the lane-table kernels; the factor
+    // kernel waits for join_ev, behind the launches that prepare it.  FACTOR_LAUNCH: no proof has been launched at all (st_wave.hip's wx_tail_proof_wanted
+    // said the factor launch will hold one workgroup per CU): the factor kernel's workgroups prove g themselves, behind their tiles (st_wave.hip:
+    // wa_tail_proof) -- where that kernel does not run, or cannot, k_grid_check on the construction's own stream.
+    enum How { NOT_A_GRID, SIDE_STREAM, FACTOR_LAUNCH } how = NOT_A_GRID;
+    GridDims g = {0, 0, 0};
+    hipStream_t side = nullptr; hipEvent_t fork_ev = nullptr, join_ev = nullptr;
+    int32_t *d_verdict = nullptr;       // the verdict word on the device, ctrl[8]: nonzero = the pattern is not g's
+    // in: what the factor kernel's launch is followed by, behind its read-back and in front of the wait for it: the arming of the first
+    // apply (api.hip: arm_apply) -- `arm` runs with `arm_ctx`, the wait is for `arm_ev` instead of the stream
+    void (*arm)(void *) = nullptr; void *arm_ctx = nullptr; hipEvent_t arm_ev = nullptr;
+    // out: who has queued this attempt's proof, and the verdict word as the factor kernel's own read-back took it along (-1: nobody has read it yet)
+    enum By { NOBODY, BY_SIDE_STREAM, BY_LAUNCH, BY_FACTOR_KERNEL } queued = NOBODY;
+    int32_t verdict = -1;
+    // the ONE place that launches k_grid_check for an attempt (grid.hip), on the side stream or on `st` as `how` says; exactly one proof per
+    // attempt, whoever asks: nothing if it is queued already.  settle: ... and `st` waits for it (one nobody has queued yet: here and now)
+    void queue(hipStream_t st, const DevMat &A);
+    void settle(hipStream_t st, const DevMat &A) { queue(st, A); if (queued == BY_SIDE_STREAM) ILUPP_HIP(hipStreamWaitEvent(st, join_ev, 0)); }
+};
 bool grid_llt_schedule(hipStream_t st, int32_t n, const GridDims &g, int max_lanes, Schedule *bwd);
 bool llt_grid_rows(hipStream_t st, const DevMat &Lc, const GridDims &g, DevMat *T);      // row-major copy of a column-major factor with the grid's lower pattern
 void make_desc_llt_grid(hipStream_t st, const DevMat &M, const Schedule &sch, const GridDims &g, int32_t **desc, bool with_pattern = false);
@@ -344,8 +353,6 @@ bool grid_predict_sizes(const GridDims &g, int ty, int tz, int64_t *nchunks, int
 void grid_scat_tables(hipStream_t st, const GridDims &gd, const Schedule &fwd, int32_t *ltabF, int32_t *ltabB, int32_t *wtabF, int32_t *wtabB,
                       int32_t *ysrc, int32_t *rtab, int32_t *xeF, int32_t *xeB, int32_t *xwF, int32_t *xwB, int32_t *flagsF, int32_t *flagsB,
                       int32_t *tot);
-// a verdict computed on another stream that a read-back of the analysis takes along: the stream waits for `ev`, then *host = *dev
-struct SideJoin { hipEvent_t ev; const int32_t *dev; int32_t *host; bool done; };
 int ilu0_csr_ptrs(hipStream_t st, const DevMat &A, DevMat *L, DevMat *U);
 int csr_ptrs_from_counts(hipStream_t st, int32_t n, int32_t *counts, DevMat *M);
 int st_make_csr(hipStream_t st, int32_t n, const PackedSweep &pl, const PackedSweep &pu, DevMat *L, DevMat *U);
@@ -386,6 +393,9 @@ hipError_t event_sync(hipStream_t st, hipEvent_t ev);      // ... for an event b
 void d2h_cancel_all();
 
 // schedule.hip
+// the patch of ty x tz = 256 lines, as square as s2 lines by nbz planes allow; false: no tiling (lines too few, or more patches than
+// max_wgs workgroups: every workgroup must be resident at once, a patch may wait on a higher-numbered patch)
+bool patch_shape(int s2, int nbz, int max_wgs, int *ty, int *tz);
 void choose_tiling(hipStream_t st, int32_t n, const int32_t *ptr, const int32_t *idx, Schedule *sch, bool fwd, int max_wgs);
 void choose_tiling_pair(hipStream_t st, const int32_t *ptr, const int32_t *idx, Schedule *fwd, Schedule *bwd, int max_wgs);
 void build_slot_tables(hipStream_t st, Schedule *sch, bool fwd, bool fill = true);      // fill = false: the arrays only (grid.hip fills them)
@@ -661,9 +671,10 @@ void lm_link_y(hipStream_t st, const Schedule &fwd, PackedSweep *pl, PackedSweep
 
 // st.hip
 bool st_analyse_ilu0(hipStream_t st, const DevMat &A, const Schedule &fwd, const Schedule &bwd, PackedSweep *pl,
-                     PackedSweep *pu, FactorLM *f, SideJoin *join = nullptr, const GridDims *grid = nullptr);
+                     PackedSweep *pu, FactorLM *f, const GridDims *grid = nullptr);
 int ilu0_numeric_st(hipStream_t st, const DevMat &A, PackedSweep *pl, PackedSweep *pu, FactorLM *f, int32_t *d_ctrl, float *kernel_ms,
-                    hipEvent_t e0, hipEvent_t e1);
+                    hipEvent_t e0, hipEvent_t e1, GridProof *gp);
+bool ilu0_numeric_st_is_wx(const PackedSweep &pl, const FactorLM &f);     // ... will launch the wave-exchange factor kernel (ilu0_numeric_wx)
 int sptrsv_st(hipStream_t st, const PackedSweep &ps, int32_t n, const double *rhs, double *out, int32_t *d_ticket, int32_t *d_err,
               double *ypk_out = nullptr, const double *ypk_in = nullptr, const int32_t *ysrc = nullptr);
 void st_unpack(hipStream_t st, const DevMat &M, const PackedSweep &ps);

@@ -528,6 +528,17 @@ void grid_check_launch(hipStream_t side, const DevMat &A, const GridDims &g, int
     ILUPP_HIP(hipGetLastError());
 }
 
+void GridProof::queue(hipStream_t st, const DevMat &A)
+{
+    if (queued != NOBODY) return;
+    queued = how == SIDE_STREAM ? BY_SIDE_STREAM : BY_LAUNCH;
+    if (queued == BY_LAUNCH) { grid_check_launch(st, A, g, d_verdict); return; }
+    ILUPP_HIP(hipEventRecord(fork_ev, st));
+    ILUPP_HIP(hipStreamWaitEvent(side, fork_ev, 0));
+    grid_check_launch(side, A, g, d_verdict);
+    ILUPP_HIP(hipEventRecord(join_ev, side));
+}
+
 // What ilu0_symbolic_and_schedule + choose_tiling_pair + finish_chains leave behind, for a matrix that IS the guessed grid (the proof
 // runs next to what follows).  The placement of the lines on workgroups is the one choose_tiling makes for a (1, ny) line grid.
 void grid_schedules(hipStream_t st, const DevMat &A, const GridDims &g, DevMat *L, DevMat *U, Schedule *fwd, Schedule *bwd,
@@ -548,17 +559,9 @@ void grid_schedules(hipStream_t st, const DevMat &A, const GridDims &g, DevMat *
     }
     hipLaunchKernelGGL(k_grid_starts, dim3((unsigned)((nb + 1 + 255) / 256)), dim3(256), 0, st, n, g.nx, nb, fwd->start, bwd->start);
     ILUPP_HIP(hipGetLastError());
-    // patches of 16 x 16 lines, as square as the grid allows (schedule.hip: tiling_decide)
-    if (g.nz >= 2 && getenv("ILUPP_NO_TILES") == nullptr) {
-        const int s2 = g.ny, nbz = g.nz;
-        int ty = 16, tz = 16;
-        while (ty > s2 && ty > 1) { ty >>= 1; tz <<= 1; }
-        while (tz > nbz && tz > 1) { tz >>= 1; ty <<= 1; }
-        if (ty <= s2 && ty * tz == kThreads) {
-            const int NY = (s2 + ty - 1) / ty, NZ = (nbz + tz - 1) / tz;
-            if ((long)NY * NZ <= max_wgs)
-                for (Schedule *s : {fwd, bwd}) { s->tile_s2 = s2; s->tile_ty = ty; s->tile_tz = tz; }
-        }
+    // patches of 16 x 16 lines, as square as the grid allows (schedule.hip: patch_shape, as tiling_decide)
+    if (g.nz >= 2 && getenv("ILUPP_NO_TILES") == nullptr && patch_shape(g.ny, g.nz, max_wgs, &fwd->tile_ty, &fwd->tile_tz)) {
+        fwd->tile_s2 = bwd->tile_s2 = g.ny; bwd->tile_ty = fwd->tile_ty; bwd->tile_tz = fwd->tile_tz;
     }
 }
 
@@ -574,17 +577,9 @@ bool grid_llt_schedule(hipStream_t st, int32_t n, const GridDims &g, int max_lan
     bwd->tile_s2 = bwd->tile_ty = bwd->tile_tz = 0;
     hipLaunchKernelGGL(k_grid_starts, dim3((unsigned)((nb + 1 + 255) / 256)), dim3(256), 0, st, n, g.nx, nb, bwd->start, bwd->start);
     ILUPP_HIP(hipGetLastError());
-    // patches of 16 x 16 lines, as square as the grid allows (schedule.hip: tiling_decide; grid_schedules above)
-    if (g.nz >= 2 && getenv("ILUPP_NO_TILES") == nullptr) {
-        const int s2 = g.ny, nbz = g.nz;
-        int ty = 16, tz = 16;
-        while (ty > s2 && ty > 1) { ty >>= 1; tz <<= 1; }
-        while (tz > nbz && tz > 1) { tz >>= 1; ty <<= 1; }
-        if (ty <= s2 && ty * tz == kThreads) {
-            const int NY = (s2 + ty - 1) / ty, NZ = (nbz + tz - 1) / tz;
-            if ((long)NY * NZ <= max_lanes / kThreads) { bwd->tile_s2 = s2; bwd->tile_ty = ty; bwd->tile_tz = tz; }
-        }
-    }
+    // patches of 16 x 16 lines, as square as the grid allows (schedule.hip: patch_shape, as tiling_decide; grid_schedules above)
+    if (g.nz >= 2 && getenv("ILUPP_NO_TILES") == nullptr && patch_shape(g.ny, g.nz, max_lanes / kThreads, &bwd->tile_ty, &bwd->tile_tz))
+        bwd->tile_s2 = g.ny;
     return true;
 }
 

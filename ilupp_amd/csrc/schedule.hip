@@ -128,6 +128,15 @@ static int32_t *tiling_sample(hipStream_t st, const int32_t *ptr, const int32_t 
     ILUPP_HIP(d2h_async(st, h->data(), d_offs, sizeof(int32_t) * h->size()));
     return d_offs;
 }
+bool patch_shape(int s2, int nbz, int max_wgs, int *ty_out, int *tz_out)
+{
+    int ty = 16, tz = 16;
+    while (ty > s2 && ty > 1) { ty >>= 1; tz <<= 1; }
+    while (tz > nbz && tz > 1) { tz >>= 1; ty <<= 1; }
+    if (ty > s2 || ty * tz != kThreads || (long)((s2 + ty - 1) / ty) * ((nbz + tz - 1) / tz) > max_wgs) return false;
+    *ty_out = ty; *tz_out = tz;
+    return true;
+}
 static void tiling_decide(const std::vector<int32_t> &h, Schedule *sch, int max_wgs)
 {
     const int nsamp = (int)(h.size() / 8);
@@ -151,16 +160,11 @@ static void tiling_decide(const std::vector<int32_t> &h, Schedule *sch, int max_
     for (auto &pr : cnt) if (pr.second > best) { best = pr.second; s2 = pr.first; }
     if (nonempty == 0 || s2 < 4 || best * 2 < nonempty || has1 * 2 < nonempty) return;
     const int nbz = (sch->nb + s2 - 1) / s2;
-    // patch shape ty x tz = 256, as square as the grid allows
-    int ty = 16, tz = 16;
-    while (ty > s2 && ty > 1) { ty >>= 1; tz <<= 1; }
-    while (tz > nbz && tz > 1) { tz >>= 1; ty <<= 1; }
-    if (ty > s2 || ty * tz != kThreads) return;
-    // (experiment hook: patches of fewer lines than lanes -- the lanes left over own no block)
+    int ty = 0, tz = 0;
+    if (!patch_shape(s2, nbz, max_wgs, &ty, &tz)) return;
+    // (experiment hook: patches of fewer lines than lanes -- the lanes left over own no block; they are more patches: the limit once more)
     if (const char *e = getenv("ILUPP_TILE_TZ")) { const int v = atoi(e); if (v >= 1 && v <= tz) tz = v; }
-    const int NY = (s2 + ty - 1) / ty, NZ = (nbz + tz - 1) / tz;
-    // every workgroup must be resident at once (a patch may wait on a higher-numbered patch)
-    if ((long)NY * NZ > max_wgs) return;
+    if ((long)((s2 + ty - 1) / ty) * ((nbz + tz - 1) / tz) > max_wgs) return;
     sch->tile_s2 = s2; sch->tile_ty = ty; sch->tile_tz = tz;
 }
 

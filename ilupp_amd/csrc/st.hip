@@ -1623,7 +1623,7 @@ static void st_close(PackedSweep *pl, PackedSweep *pu, const int32_t *hl, const 
 // The whole static analysis of an ILU(0): true when the factor kernel and both sweeps can run from lane tables
 // (pl, pu, f then complete, the values of A packed); false leaves the three objects released.
 bool st_analyse_ilu0(hipStream_t st, const DevMat &A, const Schedule &fwd, const Schedule &bwd, PackedSweep *pl,
-                     PackedSweep *pu, FactorLM *f, SideJoin *join, const GridDims *grid)
+                     PackedSweep *pu, FactorLM *f, const GridDims *grid)
 {
     pl->release(); pu->release(); f->release();
     static const bool classic = getenv("ILUPP_CLASSIC_ANALYSIS") != nullptr;
@@ -1687,18 +1687,11 @@ bool st_analyse_ilu0(hipStream_t st, const DevMat &A, const Schedule &fwd, const
                              pl->flags, pu->flags, tot);
         else
             st_xch_layout(st, fwd, &bwd, pl, pu, xsz);
-        D2HItem items[4];
+        D2HItem items[3];
         items[0] = {f->chk_xtot, tot, 4 * sizeof(int32_t)};
         items[1] = {f->chk_hl, pl->flags, sizeof(f->chk_hl)};
         items[2] = {f->chk_hu, pu->flags, sizeof(f->chk_hu)};
-        int ni = 3;
-        if (join) {
-            // (a verdict from a side stream comes home with this read-back)
-            ILUPP_HIP(hipStreamWaitEvent(st, join->ev, 0));
-            items[ni++] = {join->host, join->dev, sizeof(int32_t)};
-            join->done = true;
-        }
-        ILUPP_HIP(d2h_async_many(st, items, ni));
+        ILUPP_HIP(d2h_async_many(st, items, 3));
     }
     // A box grid in 16 x 16 patches: the sizes are known from the dimensions (grid.hip: grid_predict_sizes), so nothing is waited for
     // here -- the factor kernel follows the lane-table kernels at once, and what the device found is compared with the prediction when
@@ -1706,7 +1699,7 @@ bool st_analyse_ilu0(hipStream_t st, const DevMat &A, const Schedule &fwd, const
     {
         static const bool nospec = getenv("ILUPP_NO_SPEC") != nullptr;
         int64_t pn = 0, px = 0; int32_t pm = 0, pxl = 0;
-        f->spec = grid && !nospec && !join && st_wx_on() && try_direct && getenv("ILUPP_NO_WXF") == nullptr &&
+        f->spec = grid && !nospec && st_wx_on() && try_direct && getenv("ILUPP_NO_WXF") == nullptr &&
                   grid_predict_sizes(*grid, fwd.tile_ty, fwd.tile_tz, &pn, &pm, &px, &pxl);
         if (f->spec) {
             for (int i = 0; i < 12; ++i) hl[i] = hu[i] = 0;
@@ -1748,12 +1741,17 @@ bool st_analyse_ilu0(hipStream_t st, const DevMat &A, const Schedule &fwd, const
     return true;
 }
 
+// the one predicate by which ilu0_numeric_st hands over to ilu0_numeric_wx (callers that prepare for that kernel ask here: api.hip)
+bool ilu0_numeric_st_is_wx(const PackedSweep &pl, const FactorLM &f)
+{
+    return f.direct && f.wxf && (uint64_t)(pl.nchunks + 4 * (int64_t)pl.nwg) * 2048u < 0xfff00000ull;
+}
+
 int ilu0_numeric_st(hipStream_t st, const DevMat &A, PackedSweep *pl, PackedSweep *pu, FactorLM *f, int32_t *d_ctrl, float *kernel_ms,
-                    hipEvent_t e0, hipEvent_t e1)
+                    hipEvent_t e0, hipEvent_t e1, GridProof *gp)
 {
     pl->fmt = pu->fmt = 0;                               // (the factor kernels below write records by template position)
-    if (f->direct && f->wxf && (uint64_t)(pl->nchunks + 4 * (int64_t)pl->nwg) * 2048u < 0xfff00000ull)
-        return ilu0_numeric_wx(st, A, pl, pu, d_ctrl, kernel_ms, e0, e1);
+    if (ilu0_numeric_st_is_wx(*pl, *f)) return ilu0_numeric_wx(st, A, pl, pu, d_ctrl, kernel_ms, e0, e1, gp);
     if (f->direct) {
         const int rc = ilu0_numeric_sd(st, A, pl, pu, d_ctrl, kernel_ms, e0, e1);
         // the sweeps of st_wave.hip read class-aligned records

@@ -417,6 +417,6 @@ int ilu0_numeric_sd(hipStream_t st, const DevMat &A, PackedSweep *pl, PackedSwee
                     hipEvent_t e0, hipEvent_t e1);
 // st_wave.hip
 int ilu0_numeric_wx(hipStream_t st, const DevMat &A, PackedSweep *pl, PackedSweep *pu, int32_t *d_ctrl, float *kernel_ms,
-                    hipEvent_t e0, hipEvent_t e1);
+                    hipEvent_t e0, hipEvent_t e1, GridProof *gp);
 
 }  // namespace ilupp

@@ -1784,7 +1784,7 @@ bool wx_tail_proof_wanted(int32_t ny, int32_t nz)
 }
 
 int ilu0_numeric_wx(hipStream_t st, const DevMat &A, PackedSweep *pl, PackedSweep *pu, int32_t *d_ctrl, float *kernel_ms,
-                    hipEvent_t e0, hipEvent_t e1)
+                    hipEvent_t e0, hipEvent_t e1, GridProof *gp)
 {
     {
         static std::once_flag once[64];      // once per device
@@ -1832,17 +1832,13 @@ int ilu0_numeric_wx(hipStream_t st, const DevMat &A, PackedSweep *pl, PackedSwee
         if (ncu > 0 && (int64_t)pl->nwg <= (int64_t)ncu) a.flags |= 2;
     }
     a.pf_ptr = a.pf_idx = nullptr; a.pf_nnz = 0; a.pf_n = 0; a.pf_g = {0, 0, 0};
-    if (pl->tail_proof) {
-        const GridDims g = {pl->tail_g[0], pl->tail_g[1], pl->tail_g[2]};
-        if (a.flags & 2) {
-            a.flags |= 16;
-            a.pf_ptr = A.ptr; a.pf_idx = A.idx; a.pf_nnz = A.nnz; a.pf_n = A.n; a.pf_g = g;
-        } else {
-            // (the schedule has more workgroups than wx_tail_proof_wanted counted patches: the proof as a launch, in front of the kernel)
-            grid_check_launch(st, A, g, d_ctrl + 8);
-        }
+    if (gp && gp->how == GridProof::FACTOR_LAUNCH && gp->queued == GridProof::NOBODY && (a.flags & 2)) {
+        a.flags |= 16;
+        a.pf_ptr = A.ptr; a.pf_idx = A.idx; a.pf_nnz = A.nnz; a.pf_n = A.n; a.pf_g = gp->g;
+        gp->queued = GridProof::BY_FACTOR_KERNEL;
     }
-    if (pl->join_ev) ILUPP_HIP(hipStreamWaitEvent(st, pl->join_ev, 0));       // (grid.hip's proof, on its side stream)
+    // (grid.hip's proof on its side stream: the wait for it; a schedule of more workgroups than wx_tail_proof_wanted counted patches: the proof as a launch, in front of the kernel)
+    if (gp && gp->how != GridProof::NOT_A_GRID) gp->settle(st, A);
     ILUPP_HIP(hipEventRecord(e0, st));
     // compact L records when the L sweep that reads them will run (the vector-wave sweep: ILUPP_NO_COMPACT_L=1 for format 1)
     static const bool no_compact = getenv("ILUPP_NO_COMPACT_L") != nullptr;
@@ -1854,17 +1850,17 @@ int ilu0_numeric_wx(hipStream_t st, const DevMat &A, PackedSweep *pl, PackedSwee
     ILUPP_HIP(hipGetLastError());
     int32_t ctrl[12];
     ILUPP_HIP(d2h_async(st, ctrl, d_ctrl, sizeof(ctrl)));
-    if (pl->arm && pl->arm_ev) {
+    if (gp && gp->arm && gp->arm_ev) {
         // (the first apply's control words and exchange buffers are made ready behind the read-back, while the host is on its way back)
         pl->fmt = compact ? 2 : 1; pu->fmt = 1;      // (what the kernel in flight writes)
-        ILUPP_HIP(hipEventRecord(pl->arm_ev, st));
-        pl->arm(pl->arm_ctx);
-        ILUPP_HIP(event_sync(st, pl->arm_ev));
+        ILUPP_HIP(hipEventRecord(gp->arm_ev, st));
+        gp->arm(gp->arm_ctx);
+        ILUPP_HIP(event_sync(st, gp->arm_ev));
     } else {
         ILUPP_HIP(stream_sync(st));
     }
-    // (a tail proof that did not get through all rows -- a launch that gave up -- has proven nothing)
-    pl->join_verdict = ((a.flags & 16) && ctrl[9] < A.n) ? 1 : ctrl[8];
+    // (a tail proof that did not get through all rows -- a launch that gave up -- has proven nothing; ctrl[8] is the verdict word, gp->d_verdict)
+    if (gp) gp->verdict = ((a.flags & 16) && ctrl[9] < A.n) ? 1 : ctrl[8];
     if (kernel_ms) ILUPP_HIP(hipEventElapsedTime(kernel_ms, e0, e1));
     if (ctrl[1] != 0) return ILUPP_ERR_TIMEOUT;
     pl->fmt = compact ? 2 : 1; pu->fmt = 1;
