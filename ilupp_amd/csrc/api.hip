@@ -437,6 +437,16 @@ static void arm_apply(ilupp_precond *p)
     p->ctrl_armed = true; p->pkL.xch_armed = p->pkU.xch_armed = true;
 }
 
+// Behind a factor kernel: the control words as a sync() and the next apply expect them.  The wave-exchange objects get the whole apply armed
+// (arm_apply).  Every other factor kernel counts its workgroups in ctrl[0], the word the sweeps report a timeout through: a sync() that
+// comes before the next apply -- behind device applies or a batched launch that were not waited for -- must not read that count as a
+// sweep that gave up.
+static void settle_ctrl(ilupp_precond *p)
+{
+    if (!p->ctrl_armed) arm_apply(p);
+    if (!p->ctrl_armed) ILUPP_HIP(hipMemsetAsync(p->ctrl, 0, 16, p->stream));
+}
+
 // numeric phase with whatever machinery the analysis could set up; leaves the sweep records' values in place (gp: common.h, GridProof)
 static int ilu0_numeric_any(ilupp_precond *p, const DevMat &A, bool have_prog, float *kms, GridProof *gp)
 {
@@ -650,7 +660,7 @@ int ilu0_factor(ilupp_precond *p, const DevMat &A, const int32_t *head)
     if (grid && rc == ILUPP_OK) grid_shape_remember(A.n, A.nnz, gp.g, A.idx);
     factor_timing(p, grid && wx_numeric && rc == ILUPP_OK, waited ? p->ev[5] : p->ev[2], kms);
     if (rc == ILUPP_ERR_TIMEOUT) set_error("ILU0: dependency wait timed out (invalid structure?)");
-    if (rc == ILUPP_OK && !p->ctrl_armed) arm_apply(p);
+    if (rc == ILUPP_OK) settle_ctrl(p);
     return rc;
 }
 
@@ -1140,7 +1150,7 @@ int ilu0_refactor_single(ilupp_precond *p, const double *d_data, const int32_t *
     ILUPP_HIP(hipEventElapsedTime(&p->tm.numeric_ms, p->ev[1], p->ev[2]));
     p->tm.numeric_kernel_ms = kms;
     drop_old_value_copies(p);
-    if (rc == ILUPP_OK) arm_apply(p);
+    if (rc == ILUPP_OK) settle_ctrl(p);
     if (rc == ILUPP_ERR_TIMEOUT) set_error("ILU0: dependency wait timed out");
     return rc;
 }
