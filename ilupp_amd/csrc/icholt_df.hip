@@ -458,8 +458,10 @@ static int icholt_attempt(hipStream_t st, const DevMat &Atri, int32_t add_fill_i
     while (T < 4 * (avg + (add_fill_in > 0 ? add_fill_in : 0)) && T < Tlimit) T *= 2;
     // largest class: as many touch records per row as the matrix can need (every column may reach a row), within 8 GB
     if (cls == 3) { while (T < Tlimit && T < m && (size_t)m * T * 2 * 32 <= ((size_t)8 << 30)) T *= 2; }
-    if (cls == 1 && T > kCtTsmall) return 1;
-    if (cls == 0 && T > kCtTtiny) return 1;
+    if ((cls == 1 && T > kCtTsmall) || (cls == 0 && T > kCtTtiny)) {
+        if (getenv("ILUPP_DEBUG")) fprintf(stderr, "[ilupp] icholt: class %d, T %d, waves %d: status %d, %.1f ms\n", cls, T, 0, 1, 0.0);
+        return 1;
+    }
     while (T > 16 && ((long)m * T > 0x7fffffffL || (size_t)m * T * 32 > ((size_t)96 << 30))) T /= 2;
     if ((long)m * T > 0x7fffffffL) return 1;
 
@@ -544,6 +546,11 @@ static int icholt_attempt(hipStream_t st, const DevMat &Atri, int32_t add_fill_i
     ILUPP_HIP(hipMemcpyAsync(h, ctrl, 16, hipMemcpyDeviceToHost, st));
     ILUPP_HIP(hipStreamSynchronize(st));
     if (kernel_ms) ILUPP_HIP(hipEventElapsedTime(kernel_ms, e0, e1));
+    if (getenv("ILUPP_DEBUG")) {
+        float ms = 0.f;
+        ILUPP_HIP(hipEventElapsedTime(&ms, e0, e1));
+        fprintf(stderr, "[ilupp] icholt: class %d, T %d, waves %d: status %d, %.1f ms\n", cls, T, waves, h[2], ms);
+    }
     ILUPP_HIP(hipEventDestroy(e0));
     ILUPP_HIP(hipEventDestroy(e1));
     int rc = ILUPP_OK;

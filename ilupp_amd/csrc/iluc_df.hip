@@ -811,16 +811,23 @@ int iluc_factor(hipStream_t st, const DevMat &Av, int32_t max_fill_in, double th
     const long fill = max_fill_in < 1 ? 1 : max_fill_in;
     const long est = (Av.nnz / (Av.n > 0 ? Av.n : 1) / 2 + 1 + fill) * fill;
 #ifdef ILUC_FIRST
-    const int first = ILUC_FIRST;
+    int first = ILUC_FIRST;
 #else
-    const int first = est <= 192 ? 0 : (est <= 640 ? 1 : 2);
+    int first = est <= 192 ? 0 : (est <= 640 ? 1 : 2);
 #endif
+    if (const char *e = getenv("ILUPP_ILUC_CLASS")) first = atoi(e) < 0 ? 0 : (atoi(e) > 4 ? 4 : atoi(e));     // tests: start with a given class
     for (int cls = first; cls < 5 && rc == 1; ++cls) {
         int which = 0;
         rc = iluc_attempt(st, Av, max_fill_in, threshold, L, U, err_row, kernel_ms, cls, &which);
+        if (rc != 1) break;
+        const bool records = which == 12 || which == 15;
         // a step reached by more stored entries than the class has touch records: the next class has only twice as many, the
         // one after it 512 (a matrix with a few heavily reached rows would fail there again, after a longer run)
-        if (rc == 1 && (which == 12 || which == 15) && cls < 2) cls = 2;
+        // (the routes: records 0 -> 3, 1 -> 3, 2 -> 3 -> 4: the loop's increment comes on top of cls = 2;
+        //  entries or slots 0 -> 1 -> 2 -> 4)
+        if (records && cls < 2) cls = 2;
+        // (class 3 has the records of many steps but no more entries or slots than class 2, as in piluc_level)
+        else if (!records && which != 0 && cls == 2) cls = 3;
     }
     if (rc == 1) { set_error("ILUC: a working row does not fit the largest capacity class"); rc = ILUPP_ERR_UNSUPPORTED; }
     return rc;
