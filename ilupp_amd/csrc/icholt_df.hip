@@ -42,25 +42,20 @@
 
 #include <mutex>
 
-#include <hipcub/hipcub.hpp>
+#include <vector>
 
 #include "common.h"
-#include <vector>
+#include "iluc_common.h"
 #include "stdsort.h"
 
 namespace ilupp {
 
-// LDS capacities come in three classes (template parameters of the kernel): NE = entries gathered per column (A's column +
-// the contributors' tails), NS = slots of the working column, TM = touch records per row.  The tiny class keeps 24 waves per CU resident, the small one 12 (the kernel is bound by the latency of its ~8 dependent memory round trips per column, so resident waves
-// are throughput); a factorisation that exceeds it is run again with the large class, then by the sequential kernel.
-static constexpr int kCtTmax = 128;   // touch records per row, large class (run-time T <= this)
-static constexpr int kCtTsmall = 64;
-static constexpr int kCtTtiny = 32;
-// ready queues: kCtQ of them, column i goes to queue i % kCtQ (so the number of entries a queue will ever get is known:
-// a worker whose ticket lies beyond it is done), wave w serves queue w % kCtQ.  One queue would put two atomics per
+// LDS capacities come in three classes (template parameters of the kernel, kIcholtClass in df_ladder.h): NE = entries gathered per column
+// (A's column + the contributors' tails), NS = slots of the working column, TM = touch records per row.  The kernel is bound by the latency
+// of its ~8 dependent memory round trips per column, so resident waves are throughput: the smallest class that holds a factorisation runs it.
+// ready queues: kCuQ of them (iluc_common.h), column i goes to queue i % kCuQ (so the number of entries a queue will ever get is known:
+// a worker whose ticket lies beyond it is done), wave w serves queue w % kCuQ.  One queue would put two atomics per
 // column on two addresses -- 33 M same-address atomics at 256^3, which alone take longer than the factorisation.
-static constexpr int kCtQ = 64;     // at most; fewer when there are fewer waves than that (every queue needs a worker)
-static constexpr int kCtQBase = 64;   // ctrl word of queue 0's head; queue q: head at kCtQBase + 64 q, tail 32 words later
 static constexpr unsigned kCtSpinLimit = 1u << 22;
 
 // ctrl: [2] error (1 = capacity exceeded -> next class, 2 = timeout), [3] malformed column, [4] finished columns (progress), then the queues' heads/tails
@@ -82,7 +77,7 @@ __global__ void k_ict_seed(int32_t m, int32_t nq, const int32_t *__restrict__ pe
     if (pending[j] == 0) {
         const int q = j % nq;
         const int qcap = (m + nq - 1) / nq;
-        rq[(size_t)q * qcap + atomicAdd(&ctrl[kCtQBase + 64 * q + 32], 1)] = j;
+        rq[(size_t)q * qcap + atomicAdd(&ctrl[kCuQBase + 64 * q + 32], 1)] = j;
     }
 }
 
@@ -150,7 +145,7 @@ k_icholt_df(int32_t m, const int32_t *__restrict__ Aptr, const int32_t *__restri
     const int myq = (int)(blockIdx.x % nq);
     const int qcap = (m + nq - 1) / nq;
     const int qtotal = (m - myq + nq - 1) / nq;              // columns i = myq (mod nq) below m
-    int32_t *const qhead = &ctrl[kCtQBase + 64 * myq];
+    int32_t *const qhead = &ctrl[kCuQBase + 64 * myq];
     const int32_t *const myrq = rq + (size_t)myq * qcap;
     for (;;) {
         int tkt = 0;
@@ -170,7 +165,7 @@ k_icholt_df(int32_t m, const int32_t *__restrict__ Aptr, const int32_t *__restri
                 // of them took longer than a fixed limit on the wait (found by profiles/tools/fuzz_kernels.py, seed 1245)
                 const int done = ld_agent_i32(&ctrl[4]);
                 if (done != last_done) { last_done = done; spins = 0; }
-                else if (spins > kCtSpinLimit) CT_FAIL(2);
+                else if (spins > kCtSpinLimit) CT_FAIL(kStTimeout);
             }
             __builtin_amdgcn_s_sleep(4);
         }
@@ -181,7 +176,7 @@ k_icholt_df(int32_t m, const int32_t *__restrict__ Aptr, const int32_t *__restri
         const int capj = clen + add;
         const int loff = __builtin_amdgcn_readfirstlane(Loff[j]);
         const int nt = __builtin_amdgcn_readfirstlane(ld_agent_i32(&cnt[j]));
-        if (clen > kCtNS || nt > T || nt > kCtTM) CT_FAIL(1);
+        if (clen > kCtNS || nt > T || nt > kCtTM) CT_FAIL(kStCapacity);
 
         // ---- the column of A (slots 0..clen-1, IChol.hpp:110-112) and the touch records of row j ----
         for (int e = lane; e < clen; e += 64) { erow[e] = Aidx[c0 + e]; eval[e] = Aval[c0 + e]; eslot[e] = e; srow[e] = erow[e]; }
@@ -234,7 +229,7 @@ k_icholt_df(int32_t m, const int32_t *__restrict__ Aptr, const int32_t *__restri
         __syncthreads();
         const int net = __builtin_amdgcn_readfirstlane(cbase[nc]);
         const int ne = clen + net;
-        if (ne > kCtNE) CT_FAIL(1);
+        if (ne > kCtNE) CT_FAIL(kStCapacity);
 
         // ---- tails of the contributing columns: entry e = (row, L_ik * L_jk)  (:122-131) ----
         for (int e = lane; e < net; e += 64) {
@@ -288,7 +283,7 @@ k_icholt_df(int32_t m, const int32_t *__restrict__ Aptr, const int32_t *__restri
             if (ns > kCtNS) break;
         }
         ns = __builtin_amdgcn_readfirstlane(ns);
-        if (ns > kCtNS) CT_FAIL(1);
+        if (ns > kCtNS) CT_FAIL(kStCapacity);
         __syncthreads();
 
         // ---- accumulate every slot sequentially over the entries, scale by 1/L_jj  (:126-131, :135-141) ----
@@ -377,7 +372,7 @@ k_icholt_df(int32_t m, const int32_t *__restrict__ Aptr, const int32_t *__restri
             // (ILUPP_REFERENCE_NANS=1: what the reference does with a NaN pivot -- every entry of the column is NaN, none passes
             // `|w| > norm * tau`, the column is stored EMPTY, and its NaNs reach the diagonals of the rows it touches through the
             // records below, whose columns end the same way: IChol.hpp:115-141, dropping.hpp:15-21)
-            if (!(refnans != 0 && piv != piv && nk == 0)) CT_FAIL(piv != piv ? 3 : 4);
+            if (!(refnans != 0 && piv != piv && nk == 0)) CT_FAIL(piv != piv ? kStPivotNaN : kStPivotDropped);
         }
 
         // ---- append  (sparse_implementation.h:3170-3186) ----
@@ -396,7 +391,7 @@ k_icholt_df(int32_t m, const int32_t *__restrict__ Aptr, const int32_t *__restri
             if (pos >= T) ovf = true;
             sridx[s] = i * T + pos;
         }
-        if (__ballot(ovf) != 0ull) CT_FAIL(1);
+        if (__ballot(ovf) != 0ull) CT_FAIL(kStCapacity);
         __syncthreads();
         for (int s = 1 + lane; s < ns; s += 64) {
             const int r = srank[s];
@@ -418,7 +413,7 @@ k_icholt_df(int32_t m, const int32_t *__restrict__ Aptr, const int32_t *__restri
             if (delta != 0) ready = atomicAdd(&pending[i], delta) + delta == 0;
             if (ready) {
                 const int q = i % nq;
-                const int pos = atomicAdd(&ctrl[kCtQBase + 64 * q + 32], 1);
+                const int pos = atomicAdd(&ctrl[kCuQBase + 64 * q + 32], 1);
                 st_agent_i32(&rq[(size_t)q * qcap + pos], i);
             }
         }
@@ -437,75 +432,50 @@ __global__ void k_ict_compact(int32_t m, const int32_t *__restrict__ Loff, const
     for (int q = threadIdx.x % 8; q < len; q += 8) { oidx[dst + q] = sidx[src + q]; oval[dst + q] = sval[src + q]; }
 }
 
-// one attempt with one capacity class; returns ILUPP_OK / an error of the reference / +1 = "outside this class"
-static int icholt_attempt(hipStream_t st, const DevMat &Atri, int32_t add_fill_in, double threshold, DevMat *L, float *kernel_ms,
-                          int cls)          // capacity class: 0 tiny (24 waves per CU), 1 small (12), 2 large (3)
+#define ICT_ARGS m, Atri.ptr, Atri.idx, Atri.val, add_fill_in, threshold, T, nq, Loff, Lidx, Lval, Llen, cnt, rec, pending, q.rq, q.ctrl, b_gws.as<unsigned char>(), gNE, gNS, gTM, refnans
+
+// one attempt with one capacity class (0 tiny, 1 small, 2 large, 3 the largest); returns ILUPP_OK / an error of the reference / kOutsideClass
+static int icholt_attempt(hipStream_t st, const DevMat &Atri, int32_t add_fill_in, double threshold, DevMat *L, float *kernel_ms, int cls)
 {
-    const bool small = cls <= 1;
     const int32_t m = Atri.n;
-    if (m < 1) return 1;
+    if (m < 1) return kOutsideClass;
     const long slab = (long)Atri.nnz + (long)(add_fill_in > 0 ? add_fill_in : 0) * (long)m;
-    if (slab > 0x7fffffffL) return 1;
+    if (slab > 0x7fffffffL) return kOutsideClass;
     long a = slab;                                                      // IChol.hpp:85-87
     long b = (long)((double)Atri.nnz * 10.0);
     long reserved = a < b ? a : b;
     if (reserved > 0x7fffffffL) reserved = 0x7fffffffL;
 
-    // touch-record capacity per row: the number of reaches of a row is about the length of a pre-drop column
-    const long avg = Atri.nnz / m + 1;
-    int T = 16;
-    const int Tlimit = cls == 3 ? (1 << 16) : kCtTmax;
-    while (T < 4 * (avg + (add_fill_in > 0 ? add_fill_in : 0)) && T < Tlimit) T *= 2;
-    // largest class: as many touch records per row as the matrix can need (every column may reach a row), within 8 GB
-    if (cls == 3) { while (T < Tlimit && T < m && (size_t)m * T * 2 * 32 <= ((size_t)8 << 30)) T *= 2; }
-    if ((cls == 1 && T > kCtTsmall) || (cls == 0 && T > kCtTtiny)) {
-        if (getenv("ILUPP_DEBUG")) fprintf(stderr, "[ilupp] icholt: class %d, T %d, waves %d: status %d, %.1f ms\n", cls, T, 0, 1, 0.0);
-        return 1;
+    int T = icholt_records(Atri.nnz, m, add_fill_in, cls);
+    if (T == kIcholtRefused) {
+        // (the line shows the T that the class cannot hold: what class 2 would take)
+        if (getenv("ILUPP_DEBUG")) fprintf(stderr, "[ilupp] icholt: class %d, T %d, waves %d: status %d, %.1f ms\n", cls, icholt_records(Atri.nnz, m, add_fill_in, 2), 0, kStCapacity, 0.0);
+        return kOutsideClass;
     }
     while (T > 16 && ((long)m * T > 0x7fffffffL || (size_t)m * T * 32 > ((size_t)96 << 30))) T /= 2;
-    if ((long)m * T > 0x7fffffffL) return 1;
+    if ((long)m * T > 0x7fffffffL) return kOutsideClass;
 
-    int32_t *cap, *Loff, *Lidx, *Llen, *cnt, *pending, *rq, *ctrl, *Lptr;
-    double *Lval;
-    unsigned long long *rec;
-    ILUPP_HIP(pool_malloc(&cap, sizeof(int32_t) * (size_t)(m + 1)));
-    ILUPP_HIP(pool_malloc(&Loff, sizeof(int32_t) * (size_t)(m + 1)));
-    ILUPP_HIP(pool_malloc(&Llen, sizeof(int32_t) * (size_t)(m + 1)));
-    ILUPP_HIP(pool_malloc(&Lptr, sizeof(int32_t) * (size_t)(m + 1)));
-    ILUPP_HIP(pool_malloc(&Lidx, sizeof(int32_t) * (size_t)(slab > 0 ? slab : 1)));
-    ILUPP_HIP(pool_malloc(&Lval, sizeof(double) * (size_t)(slab > 0 ? slab : 1)));
-    ILUPP_HIP(pool_malloc(&cnt, sizeof(int32_t) * (size_t)m));
-    ILUPP_HIP(pool_malloc(&pending, sizeof(int32_t) * (size_t)m));
-    const size_t rq_len = (size_t)kCtQ * (size_t)((m + kCtQ - 1) / kCtQ) + (size_t)m;   // (nq <= kCtQ queues of ceil(m / nq) entries)
-    ILUPP_HIP(pool_malloc(&rq, sizeof(int32_t) * rq_len));
-    const size_t ctrl_bytes = sizeof(int32_t) * (size_t)(kCtQBase + 64 * kCtQ);
-    ILUPP_HIP(pool_malloc(&ctrl, ctrl_bytes));
-    if (pool_malloc(&rec, (size_t)m * T * 32) != hipSuccess) {
-        (void)hipGetLastError();
-        for (void *q : {(void *)cap, (void *)Loff, (void *)Llen, (void *)Lptr, (void *)Lidx, (void *)Lval, (void *)cnt, (void *)pending,
-                        (void *)rq, (void *)ctrl})
-            ILUPP_HIP(pool_free(q));
-        return 1;
-    }
-    ILUPP_HIP(hipMemsetAsync(cnt, 0, sizeof(int32_t) * (size_t)m, st));
-    ILUPP_HIP(hipMemsetAsync(pending, 0, sizeof(int32_t) * (size_t)m, st));
-    ILUPP_HIP(hipMemsetAsync(Llen, 0, sizeof(int32_t) * (size_t)(m + 1), st));
-    ILUPP_HIP(hipMemsetAsync(rq, 0xff, sizeof(int32_t) * rq_len, st));
-    ILUPP_HIP(hipMemsetAsync(ctrl, 0, ctrl_bytes, st));
-    const int32_t big = 0x7fffffff;
-    ILUPP_HIP(hipMemcpyAsync(ctrl + 3, &big, sizeof(int32_t), hipMemcpyHostToDevice, st));
-    int waves = device_cu_count() * (cls == 0 ? 24 : (cls == 1 ? 12 : 3));
+    PoolArray<int32_t> cap, Loff, Llen, Lptr, Lidx, cnt, pending;
+    PoolArray<double> Lval;
+    PoolBlock b_rec, b_gws;
+    DfQueues q;
+    cap.alloc(m + 1); Loff.alloc(m + 1); Llen.alloc(m + 1); Lptr.alloc(m + 1);
+    Lidx.alloc(slab > 0 ? slab : 1); Lval.alloc(slab > 0 ? slab : 1);
+    cnt.alloc(m); pending.alloc(m);
+    q.alloc(m);
+    if (b_rec.alloc((size_t)m * T * 32) != hipSuccess) { (void)hipGetLastError(); return kOutsideClass; }    // (the next class has room for more)
+    unsigned long long *rec = b_rec.as<unsigned long long>();
+    cnt.zero(st, m); pending.zero(st, m); Llen.zero(st, m + 1);
+    q.clear(st);
+    int waves = device_cu_count() * kIcholtClass[cls].waves_per_cu;
     if (waves > m) waves = m;
     // largest class: one wave per CU, working arrays in a dynamic LDS allocation
-    unsigned char *gws = nullptr;
     int gNE = 0, gNS = 0, gTM = 0;
     size_t dyn_bytes = 0;
-    if (cls == 3) {
-        gTM = T; gNS = 2048; gNE = 1 << 18;
+    if (cls == kIcholtGlobal) {
+        gTM = T; gNS = kIcholtClass[cls].slots; gNE = kIcholtClass[cls].entries;
         dyn_bytes = ict_lds_bytes(gNS);
-        waves = device_cu_count();
-        if (waves > m) waves = m;
-        ILUPP_HIP(pool_malloc(&gws, (ict_touch_bytes(gTM) + (size_t)gNE * 16) * (size_t)waves));
+        ILUPP_HIP(b_gws.alloc((ict_touch_bytes(gTM) + (size_t)gNE * 16) * (size_t)waves));
         static std::once_flag once[64];
         int dev = 0;
         ILUPP_HIP(hipGetDevice(&dev));
@@ -513,49 +483,33 @@ static int icholt_attempt(hipStream_t st, const DevMat &Atri, int32_t add_fill_i
             ILUPP_HIP(hipFuncSetAttribute((const void *)k_icholt_df<1, 1, 1, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 256));
         });
     }
-    const int nq = waves < kCtQ ? waves : kCtQ;
+    const int nq = DfQueues::queues_for(waves);
     const int gb = (m + 255) / 256;
-    hipLaunchKernelGGL(k_ict_prep, dim3(gb), dim3(256), 0, st, m, Atri.ptr, Atri.idx, add_fill_in, cap, pending, ctrl);
-    {
-        size_t tb = 0;
-        ILUPP_HIP(hipcub::DeviceScan::ExclusiveSum(nullptr, tb, cap, Loff, m, st));
-        void *tmp;
-        ILUPP_HIP(pool_malloc(&tmp, tb > 0 ? tb : 1));
-        ILUPP_HIP(hipcub::DeviceScan::ExclusiveSum(tmp, tb, cap, Loff, m, st));
-        ILUPP_HIP(pool_free(tmp));
-    }
-    hipLaunchKernelGGL(k_ict_seed, dim3(gb), dim3(256), 0, st, m, nq, pending, rq, ctrl);
-    hipEvent_t e0, e1;
-    ILUPP_HIP(hipEventCreate(&e0));
-    ILUPP_HIP(hipEventCreate(&e1));
-    ILUPP_HIP(hipEventRecord(e0, st));
+    hipLaunchKernelGGL(k_ict_prep, dim3(gb), dim3(256), 0, st, m, Atri.ptr, Atri.idx, add_fill_in, cap, pending, q.ctrl);
+    { PoolBlock tmp; scan_i32(st, cap.get(), Loff.get(), m, &tmp); }     // (nothing takes the scratch over before the wait below: what follows is queued behind the scan)
+    hipLaunchKernelGGL(k_ict_seed, dim3(gb), dim3(256), 0, st, m, nq, pending, q.rq, q.ctrl);
+    EventPair ev;
+    ILUPP_HIP(ev.create());
+    ILUPP_HIP(hipEventRecord(ev.a, st));
     static const int refnans = getenv("ILUPP_REFERENCE_NANS") != nullptr ? 1 : 0;
-#define ICT_ARGS m, Atri.ptr, Atri.idx, Atri.val, add_fill_in, threshold, T, nq, Loff, Lidx, Lval, Llen, cnt, rec, pending, rq, ctrl, gws, gNE, gNS, gTM, refnans
-    if (cls == 0)
-        hipLaunchKernelGGL((k_icholt_df<128, 64, kCtTtiny, false>), dim3(waves), dim3(64), 0, st, ICT_ARGS);
-    else if (small)
-        hipLaunchKernelGGL((k_icholt_df<256, 128, kCtTsmall, false>), dim3(waves), dim3(64), 0, st, ICT_ARGS);
-    else if (cls == 2)
-        hipLaunchKernelGGL((k_icholt_df<1024, 512, kCtTmax, false>), dim3(waves), dim3(64), 0, st, ICT_ARGS);
-    else
-        hipLaunchKernelGGL((k_icholt_df<1, 1, 1, true>), dim3(waves), dim3(64), dyn_bytes, st, ICT_ARGS);
-#undef ICT_ARGS
-    ILUPP_HIP(hipEventRecord(e1, st));
+    if (cls == 0) hipLaunchKernelGGL((k_icholt_df<DF_LDS_CLASS(kIcholtClass, 0)>), dim3(waves), dim3(64), 0, st, ICT_ARGS);
+    else if (cls == 1) hipLaunchKernelGGL((k_icholt_df<DF_LDS_CLASS(kIcholtClass, 1)>), dim3(waves), dim3(64), 0, st, ICT_ARGS);
+    else if (cls == 2) hipLaunchKernelGGL((k_icholt_df<DF_LDS_CLASS(kIcholtClass, 2)>), dim3(waves), dim3(64), 0, st, ICT_ARGS);
+    else hipLaunchKernelGGL((k_icholt_df<1, 1, 1, true>), dim3(waves), dim3(64), dyn_bytes, st, ICT_ARGS);
+    ILUPP_HIP(hipEventRecord(ev.b, st));
     ILUPP_HIP(hipGetLastError());
     int32_t h[4];
-    ILUPP_HIP(hipMemcpyAsync(h, ctrl, 16, hipMemcpyDeviceToHost, st));
+    ILUPP_HIP(hipMemcpyAsync(h, q.ctrl, 16, hipMemcpyDeviceToHost, st));
     ILUPP_HIP(hipStreamSynchronize(st));
-    if (kernel_ms) ILUPP_HIP(hipEventElapsedTime(kernel_ms, e0, e1));
+    if (kernel_ms) ILUPP_HIP(hipEventElapsedTime(kernel_ms, ev.a, ev.b));
     if (getenv("ILUPP_DEBUG")) {
         float ms = 0.f;
-        ILUPP_HIP(hipEventElapsedTime(&ms, e0, e1));
+        ILUPP_HIP(hipEventElapsedTime(&ms, ev.a, ev.b));
         fprintf(stderr, "[ilupp] icholt: class %d, T %d, waves %d: status %d, %.1f ms\n", cls, T, waves, h[2], ms);
     }
-    ILUPP_HIP(hipEventDestroy(e0));
-    ILUPP_HIP(hipEventDestroy(e1));
     int rc = ILUPP_OK;
-    if (gws) ILUPP_HIP(pool_free(gws));
-    if (h[2] == 2 && getenv("ILUPP_DEBUG")) {
+    { PoolBlock gone; gone.swap(b_gws); }                            // (the largest class's work space goes before the compaction allocates)
+    if (h[2] == kStTimeout && getenv("ILUPP_DEBUG")) {
         std::vector<int32_t> hp(m), hl(m + 1), hc(m);
         ILUPP_HIP(hipMemcpy(hp.data(), pending, sizeof(int32_t) * (size_t)m, hipMemcpyDeviceToHost));
         ILUPP_HIP(hipMemcpy(hl.data(), Llen, sizeof(int32_t) * (size_t)(m + 1), hipMemcpyDeviceToHost));
@@ -566,46 +520,41 @@ static int icholt_attempt(hipStream_t st, const DevMat &Atri, int32_t add_fill_i
                 cls, T, waves, nq, unfinished, m, firstu, firstu >= 0 ? hp[firstu] : 0, firstu >= 0 ? hc[firstu] : 0, negp);
         for (int j = firstu; j >= 0 && j < m && j < firstu + 6; ++j) fprintf(stderr, "   col %d: len %d pending %d cnt %d\n", j, hl[j], hp[j], hc[j]);
     }
-    if (h[3] != big) rc = ILUPP_ERR_NOT_TRIANGULAR;
-    else if (h[2] == 3) rc = ILUPP_ERR_NOT_SPD;          // a column lost its diagonal: the pivot is NaN (not positive definite)
-    else if (h[2] == 4) rc = ILUPP_ERR_DIAG_DROPPED;     // ... a finite pivot dropped by the threshold / the budget
-    else if (h[2] == 2) rc = ILUPP_ERR_TIMEOUT;
-    else if (h[2] != 0) rc = 1;
+    if (h[3] != kDfNone) rc = ILUPP_ERR_NOT_TRIANGULAR;
+    else if (h[2] == kStPivotNaN) rc = ILUPP_ERR_NOT_SPD;          // a column lost its diagonal: the pivot is NaN (not positive definite)
+    else if (h[2] == kStPivotDropped) rc = ILUPP_ERR_DIAG_DROPPED; // ... a finite pivot dropped by the threshold / the budget
+    else if (h[2] == kStTimeout) rc = ILUPP_ERR_TIMEOUT;
+    else if (h[2] != kStOk) rc = kOutsideClass;
     if (rc == ILUPP_OK) {
-        size_t tb = 0;
-        ILUPP_HIP(hipcub::DeviceScan::ExclusiveSum(nullptr, tb, Llen, Lptr, m + 1, st));
-        void *tmp;
-        ILUPP_HIP(pool_malloc(&tmp, tb > 0 ? tb : 1));
-        ILUPP_HIP(hipcub::DeviceScan::ExclusiveSum(tmp, tb, Llen, Lptr, m + 1, st));
         int32_t nnz = 0;
-        ILUPP_HIP(hipMemcpyAsync(&nnz, Lptr + m, sizeof(int32_t), hipMemcpyDeviceToHost, st));
-        ILUPP_HIP(hipStreamSynchronize(st));
-        ILUPP_HIP(pool_free(tmp));                   // (after the wait: the pool knows nothing of streams)
+        {
+            PoolBlock tmp;
+            rowptr_nnz_queue(st, Llen.get(), Lptr.get(), m, &nnz, tmp);
+            ILUPP_HIP(hipStreamSynchronize(st));
+        }                                            // (the scratch goes after the wait: the pool knows nothing of streams)
         if ((long)nnz > reserved) rc = ILUPP_ERR_MEMORY;             // append_row's capacity check, :3178-3179
         else {
             L->n = m; L->nnz = nnz; L->is_csr = false; L->owns = true;
-            L->ptr = Lptr;
+            L->ptr = static_cast<int32_t *>(Lptr.release());
             ILUPP_HIP(pool_malloc(&L->idx, sizeof(int32_t) * (size_t)(nnz > 0 ? nnz : 1)));
             ILUPP_HIP(pool_malloc(&L->val, sizeof(double) * (size_t)(nnz > 0 ? nnz : 1)));
-            hipLaunchKernelGGL(k_ict_compact, dim3((m + 31) / 32), dim3(256), 0, st, m, Loff, Llen, Lptr, Lidx, Lval, L->idx, L->val);
+            hipLaunchKernelGGL(k_ict_compact, dim3((m + 31) / 32), dim3(256), 0, st, m, Loff, Llen, L->ptr, Lidx, Lval, L->idx, L->val);
             ILUPP_HIP(hipStreamSynchronize(st));
         }
     }
-    if (rc != ILUPP_OK) ILUPP_HIP(pool_free(Lptr));
-    for (void *q : {(void *)cap, (void *)Loff, (void *)Llen, (void *)Lidx, (void *)Lval, (void *)cnt, (void *)pending, (void *)rq,
-                    (void *)ctrl, (void *)rec})
-        ILUPP_HIP(pool_free(q));
     return rc;
 }
+#undef ICT_ARGS
 
 // returns ILUPP_OK / an error; the capacity classes are tried from the one with the most resident waves to the one that
-// takes the whole LDS of a CU per wave; +1 when a working column does not fit even there
+// takes the whole LDS of a CU per wave; kOutsideClass when a working column does not fit even there
 int icholt_factor_df(hipStream_t st, const DevMat &Atri, int32_t add_fill_in, double threshold, DevMat *L, float *kernel_ms)
 {
-    int rc = 1;
-    const char *force = getenv("ILUPP_ICHOLT_CLASS");                  // tests: start with a given class
-    const int first = force ? atoi(force) : 0;
-    for (int cls = first; cls < 4 && rc == 1; ++cls) rc = icholt_attempt(st, Atri, add_fill_in, threshold, L, kernel_ms, cls);
+    int rc = kOutsideClass;
+    // (tests: start with a given class; at kIcholtClasses no attempt is made)
+    for (int cls = start_class_from_env("ILUPP_ICHOLT_CLASS", 0, kIcholtClasses); cls < kIcholtClasses && rc == kOutsideClass;
+         cls = icholt_next_class(cls, kStCapacity))
+        rc = icholt_attempt(st, Atri, add_fill_in, threshold, L, kernel_ms, cls);
     return rc;
 }
 

@@ -32,25 +32,19 @@
 // would); the reservation check of append_row_with_prefix (min(p n, 10 nnz)) is made on the final lengths.
 #include <stdlib.h>
 
-#include <mutex>
 #include <vector>
-
-#include <hipcub/hipcub.hpp>
 
 #include "common.h"
 #include "iluc_common.h"
 #include "stdsort.h"
 
-#ifndef ILUC_W4
-#define ILUC_W4 4
-#endif
 #ifndef ILUC_WSGB
 #define ILUC_WSGB 16
 #endif
 
 namespace ilupp {
 
-// ctrl: [2] error (1 = capacity exceeded -> next class, 2 = timeout), [3] smallest step without a pivot, [4] finished steps, then the queues
+// ctrl: [2] status (df_ladder.h), [3] smallest step without a pivot, [4] finished steps, then the queues
 // pending[x]: entries of A left of the diagonal in row x and above it in column x
 __global__ void k_iluc_prep(int32_t n, const int32_t *__restrict__ ptr, const int32_t *__restrict__ idx, int32_t *pending,
                             int32_t *colcnt)
@@ -286,7 +280,7 @@ k_iluc_df(IlucArgs A)
                 // expensive steps (a complete factorisation in the global class) makes a late step wait for seconds
                 const int done = ld_agent_i32(&A.ctrl[4]);
                 if (done != seen) { seen = done; spins = 0; }
-                if (spins > kCuSpinLimit) CU_FAIL(2);
+                if (spins > kCuSpinLimit) CU_FAIL(kStTimeout);
             }
             __builtin_amdgcn_s_sleep(4);
         }
@@ -310,17 +304,17 @@ k_iluc_df(IlucArgs A)
                 }
                 first = __builtin_amdgcn_readfirstlane(first);
                 na = r1 - first;
-                if (na > kNS) CU_FAIL(11);
+                if (na > kNS) CU_FAIL(kStOwnPart);
                 for (int e = lane; e < na; e += 64) { erow[e] = A.idx[first + e]; eval[e] = A.val[first + e]; eslot[e] = e; srow[e] = erow[e]; }
             } else {
                 const int b = __builtin_amdgcn_readfirstlane(A.colptr[k]);
                 na = __builtin_amdgcn_readfirstlane(A.colptr[k + 1]) - b;
-                if (na > kNS) CU_FAIL(11);
+                if (na > kNS) CU_FAIL(kStOwnPart);
                 for (int e = lane; e < na; e += 64) { const int q = A.colord[b + e]; erow[e] = A.rowof[q]; eval[e] = A.val[q]; eslot[e] = e; srow[e] = erow[e]; }
             }
             // ---- the touch records of this kind ----
             const int nt = __builtin_amdgcn_readfirstlane(ld_agent_i32(Z ? &A.cntL[k] : &A.cntU[k]));
-            if (nt > T || nt > kTM) CU_FAIL(12);
+            if (nt > T || nt > kTM) CU_FAIL(kStRecordsRead);
             const unsigned long long *recs = (Z ? A.recL : A.recU) + (size_t)k * T * 4;
             for (int q = lane; q < nt; q += 64) {
                 const Rec32 rr = ld_agent_rec32(recs + (size_t)q * 4);
@@ -352,7 +346,7 @@ k_iluc_df(IlucArgs A)
             CU_SYNC();
             const int net = __builtin_amdgcn_readfirstlane(cbase[nt]);
             const int ne = na + net;
-            if (ne > kNE) CU_FAIL(13);
+            if (ne > kNE) CU_FAIL(kStEntries);
             // ---- tails: z takes u(h, j >= k) * l(k,h) from the contributor's U row, w takes l(i > k, h) * u(h,k) from its L column ----
             {
                 const int32_t *Oidx = Z ? A.Uidx : A.Lidx;
@@ -405,7 +399,7 @@ k_iluc_df(IlucArgs A)
                 if (ns > kNS) break;
             }
             ns = __builtin_amdgcn_readfirstlane(ns);
-            if (ns > kNS) CU_FAIL(14);
+            if (ns > kNS) CU_FAIL(kStSlots);
             CU_SYNC();
             // ---- accumulate every slot sequentially over the entries (batches of 64 in order, inside a batch lowest lane first) ----
             for (int sl = lane; sl < ns; sl += 64) {
@@ -540,7 +534,7 @@ k_iluc_df(IlucArgs A)
                     if (pos >= T) ovf = true;
                     zridx[r] = j * T + pos;
                 }
-                if (__ballot(ovf) != 0ull) CU_FAIL(15);
+                if (__ballot(ovf) != 0ull) CU_FAIL(kStRecordsWritten);
                 CU_SYNC();
                 // kind L, stored row i at position r: the step of row i will take the tail u(k, j >= i) of THIS step's U row
                 for (int r = 1 + lane; r <= nkw; r += 64) {
@@ -635,12 +629,12 @@ __global__ void k_iluc_compact(int32_t m, int32_t cap, const int32_t *__restrict
     for (int q = threadIdx.x % 8; q < n; q += 8) { oidx[dst + q] = sidx[src + q]; oval[dst + q] = sval[src + q]; }
 }
 
-// one attempt with one capacity class; ILUPP_OK / an error of the reference / +1 = "outside this class"
+// one attempt with one capacity class; ILUPP_OK / an error of the reference / kOutsideClass
 static int iluc_attempt(hipStream_t st, const DevMat &Av, int32_t max_fill_in, double threshold, DevMat *L, DevMat *U, int32_t *err_row,
                         float *kernel_ms, int cls, int *which_capacity)
 {
     const int32_t m = Av.n;
-    if (m < 1) return 1;
+    if (m < 1) return kOutsideClass;
     const long reserved_l = [&] {                                     // ILUC.hpp:120 (with the caller's max_fill_in)
         const long a = (long)max_fill_in * (long)m, b = (long)(10.0 * (double)Av.nnz);
         const long r = a < b ? a : b;
@@ -649,112 +643,67 @@ static int iluc_attempt(hipStream_t st, const DevMat &Av, int32_t max_fill_in, d
     int32_t fill = max_fill_in < 1 ? 1 : max_fill_in;               // :133
     if (fill > m) fill = m;
     const int cap = fill;                                             // diagonal + (fill - 1) kept entries
-    if ((long)m * cap > 0x7fffffffL) return 1;
-    const long avg = Av.nnz / m + 1;
-    int T = 16;
-    const int Tlimit = cls == 0 ? 32 : (cls == 1 ? 64 : (cls == 2 ? 128 : (cls == 3 ? 512 : 4096)));
-    (void)avg;
-    T = Tlimit < 4096 ? Tlimit : 16;           // as many touch records per step as the class can read (a row of L may be reached by many)
-    if (cls == 4) { while (T < Tlimit && T < m) T *= 2; }                  // (a row of L can be reached by every earlier step)
+    if ((long)m * cap > 0x7fffffffL) return kOutsideClass;
+    // as many touch records per step as the class can read (a row of L may be reached by many; in the largest class by every earlier step)
+    int T = crout_records(kIlucClass, cls, m);
     while (T > 16 && ((long)m * T > 0x7fffffffL || (size_t)m * T * 64 > ((size_t)64 << 30))) T /= 2;
-    if ((long)m * T > 0x7fffffffL || (size_t)m * T * 64 > ((size_t)64 << 30)) return 1;
+    if ((long)m * T > 0x7fffffffL || (size_t)m * T * 64 > ((size_t)64 << 30)) return kOutsideClass;
 
-    // (work arrays in holders that give them back when the scope ends: an ILUPP_HIP that throws in the middle must not leak them)
-    PoolBlock b_pending, b_colcnt, b_colptr, b_fillc, b_colpos, b_colord, b_rowof, b_Uidx, b_Lidx, b_Uval, b_Lval, b_Ulen, b_Llen, b_cntL,
-              b_cntU, b_recL, b_recU, b_rq, b_ctrl, b_gws;
+    CroutWork w;
+    DfQueues q;
+    PoolArray<int32_t> Uidx, Lidx, Ulen, Llen;                       // the slabs [m][cap] and the lengths of their rows
+    PoolArray<double> Uval, Lval;
+    PoolBlock b_gws;
     const size_t slab = (size_t)m * cap;
-    ILUPP_HIP(b_pending.alloc(sizeof(int32_t) * (size_t)m));
-    ILUPP_HIP(b_colcnt.alloc(sizeof(int32_t) * (size_t)(m + 1)));
-    ILUPP_HIP(b_colptr.alloc(sizeof(int32_t) * (size_t)(m + 1)));
-    ILUPP_HIP(b_fillc.alloc(sizeof(int32_t) * (size_t)(m + 1)));
-    ILUPP_HIP(b_colpos.alloc(sizeof(int32_t) * (size_t)(Av.nnz > 0 ? Av.nnz : 1)));
-    ILUPP_HIP(b_colord.alloc(sizeof(int32_t) * (size_t)(Av.nnz > 0 ? Av.nnz : 1)));
-    ILUPP_HIP(b_rowof.alloc(sizeof(int32_t) * (size_t)(Av.nnz > 0 ? Av.nnz : 1)));
-    ILUPP_HIP(b_Uidx.alloc(sizeof(int32_t) * slab));
-    ILUPP_HIP(b_Lidx.alloc(sizeof(int32_t) * slab));
-    ILUPP_HIP(b_Uval.alloc(sizeof(double) * slab));
-    ILUPP_HIP(b_Lval.alloc(sizeof(double) * slab));
-    ILUPP_HIP(b_Ulen.alloc(sizeof(int32_t) * (size_t)(m + 1)));
-    ILUPP_HIP(b_Llen.alloc(sizeof(int32_t) * (size_t)(m + 1)));
-    ILUPP_HIP(b_cntL.alloc(sizeof(int32_t) * (size_t)m));
-    ILUPP_HIP(b_cntU.alloc(sizeof(int32_t) * (size_t)m));
-    ILUPP_HIP(b_recL.alloc((size_t)m * T * 32));
-    ILUPP_HIP(b_recU.alloc((size_t)m * T * 32));
-    const size_t rq_len = (size_t)kCuQ * (size_t)((m + kCuQ - 1) / kCuQ) + (size_t)m;
-    ILUPP_HIP(b_rq.alloc(sizeof(int32_t) * rq_len));
-    const size_t ctrl_bytes = sizeof(int32_t) * (size_t)(kCuQBase + 64 * kCuQ);
-    ILUPP_HIP(b_ctrl.alloc(ctrl_bytes));
-    int32_t *pending = b_pending.as<int32_t>(), *colcnt = b_colcnt.as<int32_t>(), *colptr = b_colptr.as<int32_t>(), *fillc = b_fillc.as<int32_t>(),
-            *colpos = b_colpos.as<int32_t>(), *colord = b_colord.as<int32_t>(), *rowof = b_rowof.as<int32_t>(), *Uidx = b_Uidx.as<int32_t>(),
-            *Lidx = b_Lidx.as<int32_t>(), *Ulen = b_Ulen.as<int32_t>(), *Llen = b_Llen.as<int32_t>(), *cntL = b_cntL.as<int32_t>(),
-            *cntU = b_cntU.as<int32_t>(), *rq = b_rq.as<int32_t>(), *ctrl = b_ctrl.as<int32_t>();
-    double *Uval = b_Uval.as<double>(), *Lval = b_Lval.as<double>();
-    unsigned long long *recL = b_recL.as<unsigned long long>(), *recU = b_recU.as<unsigned long long>();
-    ILUPP_HIP(hipMemsetAsync(pending, 0, sizeof(int32_t) * (size_t)m, st));
-    ILUPP_HIP(hipMemsetAsync(colcnt, 0, sizeof(int32_t) * (size_t)(m + 1), st));
-    ILUPP_HIP(hipMemsetAsync(fillc, 0, sizeof(int32_t) * (size_t)(m + 1), st));
-    ILUPP_HIP(hipMemsetAsync(cntL, 0, sizeof(int32_t) * (size_t)m, st));
-    ILUPP_HIP(hipMemsetAsync(cntU, 0, sizeof(int32_t) * (size_t)m, st));
-    ILUPP_HIP(hipMemsetAsync(Ulen, 0, sizeof(int32_t) * (size_t)(m + 1), st));
-    ILUPP_HIP(hipMemsetAsync(Llen, 0, sizeof(int32_t) * (size_t)(m + 1), st));
-    ILUPP_HIP(hipMemsetAsync(rq, 0xff, sizeof(int32_t) * rq_len, st));
-    ILUPP_HIP(hipMemsetAsync(ctrl, 0, ctrl_bytes, st));
-    const int32_t big = 0x7fffffff;
-    ILUPP_HIP(hipMemcpyAsync(ctrl + 3, &big, sizeof(int32_t), hipMemcpyHostToDevice, st));
-    const int gb = (m + 255) / 256;
-    hipLaunchKernelGGL(k_iluc_prep, dim3(gb), dim3(256), 0, st, m, Av.ptr, Av.idx, pending, colcnt);
-    hipLaunchKernelGGL(k_iluc_rowof, dim3(gb), dim3(256), 0, st, m, Av.ptr, rowof);
-    {
-        size_t tb = 0;
-        ILUPP_HIP(hipcub::DeviceScan::ExclusiveSum(nullptr, tb, colcnt, colptr, m + 1, st));
-        PoolBlock tmp;
-        ILUPP_HIP(tmp.alloc(tb > 0 ? tb : 1));
-        ILUPP_HIP(hipcub::DeviceScan::ExclusiveSum(tmp.p, tb, colcnt, colptr, m + 1, st));
-        ILUPP_HIP(hipStreamSynchronize(st));
-    }
-    { const int rc = iluc_column_order(st, m, Av, colcnt, colptr, fillc, colpos, rowof, colord); if (rc) return rc; }
-    int waves = device_cu_count() * (cls == 0 ? 16 : (cls == 1 ? 8 : (cls == 2 ? 2 : (cls == 3 ? 2 : ILUC_W4))));
+    w.alloc(m, Av.nnz, T);
+    Uidx.alloc(slab); Lidx.alloc(slab); Uval.alloc(slab); Lval.alloc(slab);
+    Ulen.alloc(m + 1); Llen.alloc(m + 1);
+    q.alloc(m);
+    w.clear(st);
+    Ulen.zero(st, m + 1); Llen.zero(st, m + 1);
+    q.clear(st);
+    w.count_columns(st, Av);
+    scan_i32(st, w.colcnt.get(), w.colptr.get(), m + 1);
+    { const int rc = w.column_order(st, Av); if (rc) return rc; }
+    const DfClass &C = kIlucClass[cls];
+    int waves = device_cu_count() * C.waves_per_cu;
     if (waves > m) waves = m;
-    unsigned char *gws = nullptr;
     int gNE = 0, gNS = 0, gTM = 0;
-    if (cls == 4) {
-        gTM = T; gNS = 1024; while (gNS < m + 1 && gNS < 16384) gNS *= 2;       // (a power of two: the slot hash masks with 4 gNS - 1)
-        gNE = 1 << 19;
+    if (cls == kCroutGlobal) {
+        gTM = T; gNS = 1024; while (gNS < m + 1 && gNS < C.slots) gNS *= 2;       // (a power of two: the slot hash masks with 4 gNS - 1)
+        gNE = C.entries;
         while (gNE > 4096 && (size_t)waves * iluc_ws_bytes(gNE, gNS, gTM) > ((size_t)ILUC_WSGB << 30)) gNE /= 2;
         ILUPP_HIP(b_gws.alloc((size_t)waves * iluc_ws_bytes(gNE, gNS, gTM)));
-        gws = b_gws.as<unsigned char>();
     }
-    const int nq = waves < kCuQ ? waves : kCuQ;
-    hipLaunchKernelGGL(k_iluc_seed, dim3(gb), dim3(256), 0, st, m, nq, pending, rq, ctrl);
+    const int nq = DfQueues::queues_for(waves);
+    hipLaunchKernelGGL(k_iluc_seed, dim3((m + 255) / 256), dim3(256), 0, st, m, nq, w.pending, q.rq, q.ctrl);
     IlucArgs a;
-    a.gws = gws; a.gNE = gNE; a.gNS = gNS; a.gTM = gTM;
-    a.n = m; a.ptr = Av.ptr; a.idx = Av.idx; a.val = Av.val; a.colptr = colptr; a.colord = colord; a.rowof = rowof;
+    a.gws = b_gws.as<unsigned char>(); a.gNE = gNE; a.gNS = gNS; a.gTM = gTM;
+    a.n = m; a.ptr = Av.ptr; a.idx = Av.idx; a.val = Av.val; a.colptr = w.colptr; a.colord = w.colord; a.rowof = w.rowof;
     a.p = fill - 1; a.cap = cap; a.tau = threshold; a.T = T; a.nq = nq;
     a.Uidx = Uidx; a.Lidx = Lidx; a.Ulen = Ulen; a.Llen = Llen; a.Uval = Uval; a.Lval = Lval;
-    a.cntL = cntL; a.cntU = cntU; a.recL = recL; a.recU = recU; a.pending = pending; a.rq = rq; a.ctrl = ctrl;
-    struct Events { hipEvent_t a = nullptr, b = nullptr; ~Events() { if (a) (void)hipEventDestroy(a); if (b) (void)hipEventDestroy(b); } } ev;
-    ILUPP_HIP(hipEventCreate(&ev.a));
-    ILUPP_HIP(hipEventCreate(&ev.b));
-    const hipEvent_t e0 = ev.a, e1 = ev.b;
-    ILUPP_HIP(hipEventRecord(e0, st));
-    if (cls == 0) hipLaunchKernelGGL((k_iluc_df<256, 128, 32, false>), dim3(waves), dim3(64), 0, st, a);
-    else if (cls == 1) hipLaunchKernelGGL((k_iluc_df<768, 256, 64, false>), dim3(waves), dim3(64), 0, st, a);
-    else if (cls == 2) hipLaunchKernelGGL((k_iluc_df<1024, 512, 128, false>), dim3(waves), dim3(64), 0, st, a);
-    else if (cls == 3) hipLaunchKernelGGL((k_iluc_df<960, 256, 512, false>), dim3(waves), dim3(64), 0, st, a);
+    a.cntL = w.cntL; a.cntU = w.cntU; a.recL = w.recL; a.recU = w.recU; a.pending = w.pending; a.rq = q.rq; a.ctrl = q.ctrl;
+    EventPair ev;
+    ILUPP_HIP(ev.create());
+    ILUPP_HIP(hipEventRecord(ev.a, st));
+    if (cls == 0) hipLaunchKernelGGL((k_iluc_df<DF_LDS_CLASS(kIlucClass, 0)>), dim3(waves), dim3(64), 0, st, a);
+    else if (cls == 1) hipLaunchKernelGGL((k_iluc_df<DF_LDS_CLASS(kIlucClass, 1)>), dim3(waves), dim3(64), 0, st, a);
+    else if (cls == 2) hipLaunchKernelGGL((k_iluc_df<DF_LDS_CLASS(kIlucClass, 2)>), dim3(waves), dim3(64), 0, st, a);
+    else if (cls == 3) hipLaunchKernelGGL((k_iluc_df<DF_LDS_CLASS(kIlucClass, 3)>), dim3(waves), dim3(64), 0, st, a);
     else hipLaunchKernelGGL((k_iluc_df<1, 1, 1, true>), dim3(waves), dim3(64), 0, st, a);
-    ILUPP_HIP(hipEventRecord(e1, st));
+    ILUPP_HIP(hipEventRecord(ev.b, st));
     ILUPP_HIP(hipGetLastError());
     int32_t h[4];
-    ILUPP_HIP(hipMemcpyAsync(h, ctrl, 16, hipMemcpyDeviceToHost, st));
+    ILUPP_HIP(hipMemcpyAsync(h, q.ctrl, 16, hipMemcpyDeviceToHost, st));
     ILUPP_HIP(hipStreamSynchronize(st));
-    if (kernel_ms) ILUPP_HIP(hipEventElapsedTime(kernel_ms, e0, e1));
+    if (kernel_ms) ILUPP_HIP(hipEventElapsedTime(kernel_ms, ev.a, ev.b));
     float ms = 0.f;
-    ILUPP_HIP(hipEventElapsedTime(&ms, e0, e1));
+    ILUPP_HIP(hipEventElapsedTime(&ms, ev.a, ev.b));
     if (getenv("ILUPP_DEBUG")) { fprintf(stderr, "[ilupp] iluc: class %d, T %d, waves %d: status %d, %.1f ms\n", cls, T, waves, h[2], ms); }
     int rc = ILUPP_OK;
-    if (h[2] == 2) rc = ILUPP_ERR_TIMEOUT;
-    else if (h[2] != 0) { rc = 1; if (which_capacity) *which_capacity = h[2]; }      // 11..15: which capacity (A's part, touch records read, entries, slots, touch records written)
-    else if (h[3] != big) {
+    if (h[2] == kStTimeout) rc = ILUPP_ERR_TIMEOUT;
+    else if (h[2] != kStOk) { rc = kOutsideClass; if (which_capacity) *which_capacity = h[2]; }      // kStOwnPart .. kStRecordsWritten: which capacity
+    else if (h[3] != kDfNone) {
         // the reference's loop fails at the FIRST step that fails: a step k checks its pivot (ILUC.hpp:174-175), then appends the row of
         // U and the column of L (their reservation checks, sparse_implementation.h:3196-3197).  So the zero pivot of step h[3] is
         // what it reports -- unless the entries of an earlier step already exceeded the reservation
@@ -762,10 +711,7 @@ static int iluc_attempt(hipStream_t st, const DevMat &Av, int32_t max_fill_in, d
         for (int d = 0; d < 2 && h[3] > 0; ++d) {
             PoolBlock pre, tmp;
             ILUPP_HIP(pre.alloc(sizeof(int32_t) * (size_t)(m + 1)));
-            size_t tb = 0;
-            ILUPP_HIP(hipcub::DeviceScan::ExclusiveSum(nullptr, tb, d == 0 ? Ulen : Llen, pre.as<int32_t>(), m + 1, st));
-            ILUPP_HIP(tmp.alloc(tb > 0 ? tb : 1));
-            ILUPP_HIP(hipcub::DeviceScan::ExclusiveSum(tmp.p, tb, d == 0 ? Ulen : Llen, pre.as<int32_t>(), m + 1, st));
+            scan_i32(st, d == 0 ? Ulen.get() : Llen.get(), pre.as<int32_t>(), m + 1, &tmp);
             int32_t upto = 0;
             ILUPP_HIP(hipMemcpyAsync(&upto, pre.as<int32_t>() + h[3], sizeof(int32_t), hipMemcpyDeviceToHost, st));
             ILUPP_HIP(hipStreamSynchronize(st));
@@ -779,13 +725,9 @@ static int iluc_attempt(hipStream_t st, const DevMat &Av, int32_t max_fill_in, d
         for (int d = 0; d < 2 && rc == ILUPP_OK; ++d) {
             DevMat *M = out[d];
             ILUPP_HIP(pool_malloc(&M->ptr, sizeof(int32_t) * (size_t)(m + 1)));
-            size_t tb = 0;
-            ILUPP_HIP(hipcub::DeviceScan::ExclusiveSum(nullptr, tb, lens[d], M->ptr, m + 1, st));
             PoolBlock tmp;
-            ILUPP_HIP(tmp.alloc(tb > 0 ? tb : 1));
-            ILUPP_HIP(hipcub::DeviceScan::ExclusiveSum(tmp.p, tb, lens[d], M->ptr, m + 1, st));
             int32_t nnz = 0;
-            ILUPP_HIP(hipMemcpyAsync(&nnz, M->ptr + m, sizeof(int32_t), hipMemcpyDeviceToHost, st));
+            rowptr_nnz_queue(st, lens[d], M->ptr, m, &nnz, tmp);
             ILUPP_HIP(hipStreamSynchronize(st));
             if ((long)nnz > reserved_l) { rc = ILUPP_ERR_MEMORY; break; }     // append_row_with_prefix's check, :3196-3197
             M->n = m; M->nnz = nnz; M->is_csr = true; M->owns = true;
@@ -796,7 +738,6 @@ static int iluc_attempt(hipStream_t st, const DevMat &Av, int32_t max_fill_in, d
         ILUPP_HIP(hipStreamSynchronize(st));
         if (rc != ILUPP_OK) { L->release(); U->release(); }
     }
-    // (the holders give the work arrays back)
     return rc;
 }
 
@@ -805,31 +746,14 @@ static int iluc_attempt(hipStream_t st, const DevMat &Av, int32_t max_fill_in, d
 int iluc_factor(hipStream_t st, const DevMat &Av, int32_t max_fill_in, double threshold, DevMat *L, DevMat *U, int32_t *err_row,
                 float *kernel_ms)
 {
-    int rc = 1;
-    // where to start: a working row gathers about (entries of A's row + fill) tails of up to fill entries; an attempt in a class
-    // that turns out too small costs the time until the first step that does not fit
-    const long fill = max_fill_in < 1 ? 1 : max_fill_in;
-    const long est = (Av.nnz / (Av.n > 0 ? Av.n : 1) / 2 + 1 + fill) * fill;
-#ifdef ILUC_FIRST
-    int first = ILUC_FIRST;
-#else
-    int first = est <= 192 ? 0 : (est <= 640 ? 1 : 2);
-#endif
-    if (const char *e = getenv("ILUPP_ILUC_CLASS")) first = atoi(e) < 0 ? 0 : (atoi(e) > 4 ? 4 : atoi(e));     // tests: start with a given class
-    for (int cls = first; cls < 5 && rc == 1; ++cls) {
-        int which = 0;
+    int rc = kOutsideClass;
+    int cls = start_class_from_env("ILUPP_ILUC_CLASS", iluc_start_class(Av.nnz, Av.n, max_fill_in), kCroutGlobal);
+    while (cls < kCroutClasses && rc == kOutsideClass) {
+        int which = kStOk;
         rc = iluc_attempt(st, Av, max_fill_in, threshold, L, U, err_row, kernel_ms, cls, &which);
-        if (rc != 1) break;
-        const bool records = which == 12 || which == 15;
-        // a step reached by more stored entries than the class has touch records: the next class has only twice as many, the
-        // one after it 512 (a matrix with a few heavily reached rows would fail there again, after a longer run)
-        // (the routes: records 0 -> 3, 1 -> 3, 2 -> 3 -> 4: the loop's increment comes on top of cls = 2;
-        //  entries or slots 0 -> 1 -> 2 -> 4)
-        if (records && cls < 2) cls = 2;
-        // (class 3 has the records of many steps but no more entries or slots than class 2, as in piluc_level)
-        else if (!records && which != 0 && cls == 2) cls = 3;
+        cls = iluc_next_class(cls, which);
     }
-    if (rc == 1) { set_error("ILUC: a working row does not fit the largest capacity class"); rc = ILUPP_ERR_UNSUPPORTED; }
+    if (rc == kOutsideClass) { set_error("ILUC: a working row does not fit the largest capacity class"); rc = ILUPP_ERR_UNSUPPORTED; }
     return rc;
 }
 

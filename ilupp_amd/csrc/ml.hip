@@ -15,8 +15,6 @@
 #include <chrono>
 #include <vector>
 
-#include <hipcub/hipcub.hpp>
-
 #include "common.h"
 #include "iluc_common.h"
 
@@ -152,17 +150,6 @@ __global__ void k_ml_keys_low(int64_t nnz, const unsigned long long *__restrict_
     if (j < nnz) idx[j] = (int32_t)(unsigned)keys[j];
 }
 
-static int scan_i32(hipStream_t st, const int32_t *in, int32_t *out, int count)
-{
-    size_t tb = 0;
-    ILUPP_HIP(hipcub::DeviceScan::ExclusiveSum(nullptr, tb, in, out, count, st));
-    PoolBlock tmp;
-    ILUPP_HIP(tmp.alloc(tb > 0 ? tb : 1));
-    ILUPP_HIP(hipcub::DeviceScan::ExclusiveSum(tmp.p, tb, in, out, count, st));
-    ILUPP_HIP(hipStreamSynchronize(st));
-    return ILUPP_OK;
-}
-
 // A (ROW storage, owned) := P A Q with the rows re-sorted
 static int permute_matrix(hipStream_t st, DevMat *A, const int32_t *d_p1, const int32_t *d_ip1, const int32_t *d_ip2)
 {
@@ -173,7 +160,7 @@ static int permute_matrix(hipStream_t st, DevMat *A, const int32_t *d_p1, const 
     ILUPP_HIP(b_nptr.alloc(sizeof(int32_t) * (size_t)(n + 1)));
     int32_t *nptr = b_nptr.as<int32_t>();
     hipLaunchKernelGGL(k_ml_perm_lengths, dim3((n + 256) / 256), dim3(256), 0, st, n, A->ptr, d_p1, b_len.as<int32_t>());
-    { const int rc = scan_i32(st, b_len.as<int32_t>(), nptr, n + 1); if (rc) return rc; }
+    scan_i32(st, b_len.as<const int32_t>(), nptr, n + 1);
     if (nnz > 0) {
         ILUPP_HIP(b_k0.alloc(sizeof(unsigned long long) * (size_t)nnz));
         ILUPP_HIP(b_k1.alloc(sizeof(unsigned long long) * (size_t)nnz));
@@ -358,11 +345,11 @@ static int preprocess_level(hipStream_t st, DevMat *A, const MlParams &IP, int32
                 ILUPP_HIP(hipMemsetAsync(ip2, 0xff, sizeof(int32_t) * (size_t)n, st));
                 hipLaunchKernelGGL(k_ml_pq_first, dim3(gb), dim3(256), 0, st, n, W2, I2, J, IP.pq_threshold, tmpi);
                 hipLaunchKernelGGL(k_ml_pq_sel, dim3(gb1), dim3(256), 0, st, n, W2, I2, J, IP.pq_threshold, tmpi, b_sel.as<int32_t>());
-                { const int rc = scan_i32(st, b_sel.as<int32_t>(), b_rank.as<int32_t>(), n + 1); if (rc) return rc; }
+                scan_i32(st, b_sel.as<const int32_t>(), b_rank.as<int32_t>(), n + 1);
                 hipLaunchKernelGGL(k_ml_pq_assign, dim3(gb), dim3(256), 0, st, n, I2, J, b_sel.as<int32_t>(), b_rank.as<int32_t>(), ip1, ip2);
                 for (int32_t *ip : {ip1, ip2}) {
                     hipLaunchKernelGGL(k_ml_flag_free, dim3(gb1), dim3(256), 0, st, n, ip, b_sel.as<int32_t>());
-                    { const int rc = scan_i32(st, b_sel.as<int32_t>(), b_off.as<int32_t>(), n + 1); if (rc) return rc; }
+                    scan_i32(st, b_sel.as<const int32_t>(), b_off.as<int32_t>(), n + 1);
                     hipLaunchKernelGGL(k_ml_pq_rest, dim3(gb), dim3(256), 0, st, n, ip, b_sel.as<int32_t>(), b_off.as<int32_t>(), b_rank.as<int32_t>());
                 }
                 hipLaunchKernelGGL(k_ml_invert_i32, dim3(gb), dim3(256), 0, st, n, ip1, p1);

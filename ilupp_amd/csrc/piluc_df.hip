@@ -28,8 +28,6 @@
 
 #include <chrono>
 
-#include <hipcub/hipcub.hpp>
-
 #include "common.h"
 #include "iluc_common.h"
 #include "piluc_dev.h"
@@ -206,7 +204,7 @@ k_piluc_df(PilucArgs A)
                 }
                 const int done = ld_agent_i32(&A.ctrl[9]);
                 if (done != seen) { seen = done; spins = 0; }
-                if (spins > kCuSpinLimit) PU_FAIL(2);
+                if (spins > kCuSpinLimit) PU_FAIL(kStTimeout);
             }
             __builtin_amdgcn_s_sleep(4);
         }
@@ -234,17 +232,17 @@ k_piluc_df(PilucArgs A)
                 }
                 first = __builtin_amdgcn_readfirstlane(first);
                 na = r1 - first;
-                if (na > kNS) PU_FAIL(11);
+                if (na > kNS) PU_FAIL(kStOwnPart);
                 for (int e = lane; e < na; e += 64) { erow[e] = A.idx[first + e]; eval[e] = A.val[first + e]; eslot[e] = e; srow[e] = erow[e]; }
             } else {
                 const int b = __builtin_amdgcn_readfirstlane(A.colptr[k]);
                 na = __builtin_amdgcn_readfirstlane(A.colptr[k + 1]) - b;
-                if (na > kNS) PU_FAIL(11);
+                if (na > kNS) PU_FAIL(kStOwnPart);
                 for (int e = lane; e < na; e += 64) { const int q = A.colord[b + e]; erow[e] = A.rowof[q]; eval[e] = A.val[q]; eslot[e] = e; srow[e] = erow[e]; }
             }
             // ---- the touch records of this kind (Schur mode: only those written by steps below kterm) ----
             const int ntraw = __builtin_amdgcn_readfirstlane(ld_agent_i32(Z ? &A.cntL[k] : &A.cntU[k]));
-            if (ntraw > T) PU_FAIL(12);
+            if (ntraw > T) PU_FAIL(kStRecordsRead);
             const unsigned long long *recs = (Z ? A.recL : A.recU) + (size_t)k * T * 4;
             int nt = 0;
             for (int base = 0; base < ntraw; base += 64) {
@@ -265,7 +263,7 @@ k_piluc_df(PilucArgs A)
                 nt += __popcll(mk);
             }
             nt = __builtin_amdgcn_readfirstlane(nt);
-            if (nt > kTM) PU_FAIL(12);
+            if (nt > kTM) PU_FAIL(kStRecordsRead);
             PU_SYNC();
             // ---- contributors in the reference's linked-list order: (previous stored index desc, seq desc) ----
             if (nt <= 64) {
@@ -334,7 +332,7 @@ k_piluc_df(PilucArgs A)
             PU_SYNC();
             const int net = __builtin_amdgcn_readfirstlane(cbase[nt]);
             const int ne = na + net;
-            if (ne > kNE) PU_FAIL(13);
+            if (ne > kNE) PU_FAIL(kStEntries);
             // ---- tails: z takes (l(k,h) / Dinv[h]) * u(h, j >= k) from the contributor's U row, w takes (u(h,k) / Dinv[h]) * l(i >= k, h) ----
             {
                 const int32_t *Oidx = Z ? A.Uidx : A.Lidx;
@@ -401,7 +399,7 @@ k_piluc_df(PilucArgs A)
                 if (ns > kNS) break;
             }
             ns = __builtin_amdgcn_readfirstlane(ns);
-            if (ns > kNS) PU_FAIL(14);
+            if (ns > kNS) PU_FAIL(kStSlots);
             PU_SYNC();
             // ---- accumulate every slot sequentially over the entries (batches of 64 in order, inside a batch lowest lane first) ----
             for (int sl = lane; sl < ns; sl += 64) {
@@ -452,7 +450,7 @@ k_piluc_df(PilucArgs A)
                     int base = 0;
                     if (lane == 0) base = atomicAdd(&A.ctrl[6], take);
                     base = __builtin_amdgcn_readfirstlane(base);
-                    if (base < 0 || (long)base + take > (long)A.capS) PU_FAIL(16);
+                    if (base < 0 || (long)base + take > (long)A.capS) PU_FAIL(kStStores);
                     uoff = base; uend = base + take;
                 }
                 const int pos = uoff;
@@ -489,7 +487,7 @@ k_piluc_df(PilucArgs A)
                 }
                 dslot = __builtin_amdgcn_readfirstlane(dslot);
                 if (dslot < 0) {
-                    if (ns >= kNS) PU_FAIL(14);
+                    if (ns >= kNS) PU_FAIL(kStSlots);
                     if (lane == 0) { srow[ns] = k; sval[ns] = 0.0; scnt[ns] = 0; srank[ns] = -1; }
                     dslot = ns; ++ns;
                     PU_SYNC();
@@ -593,7 +591,7 @@ k_piluc_df(PilucArgs A)
                     int base = 0;
                     if (lane == 0) base = atomicAdd(&A.ctrl[6], take);
                     base = __builtin_amdgcn_readfirstlane(base);
-                    if (base < 0 || (long)base + take > (long)A.capU) PU_FAIL(16);
+                    if (base < 0 || (long)base + take > (long)A.capU) PU_FAIL(kStStores);
                     uoff = base; uend = base + take;
                 }
                 if (loff + nkw + 1 > lend) {
@@ -601,7 +599,7 @@ k_piluc_df(PilucArgs A)
                     int base = 0;
                     if (lane == 0) base = atomicAdd(&A.ctrl[7], take);
                     base = __builtin_amdgcn_readfirstlane(base);
-                    if (base < 0 || (long)base + take > (long)A.capL) PU_FAIL(16);
+                    if (base < 0 || (long)base + take > (long)A.capL) PU_FAIL(kStStores);
                     loff = base; lend = base + take;
                 }
                 const int posU = uoff, posL = loff;
@@ -629,7 +627,7 @@ k_piluc_df(PilucArgs A)
                     if (pos >= T) ovf = true;
                     zridx[r] = j * T + pos;
                 }
-                if (__ballot(ovf) != 0ull) PU_FAIL(15);
+                if (__ballot(ovf) != 0ull) PU_FAIL(kStRecordsWritten);
                 PU_SYNC();
                 // kind L, stored row i at position r: the step of row i will take (l(i,k) / Dinv[k]) times the tail u(k, j >= i) of THIS row of U
                 for (int r = 1 + lane; r <= nkw; r += 64) {
@@ -776,17 +774,6 @@ __global__ void k_piluc_schur_write(int32_t ns, int32_t kterm, const int32_t *__
     for (int q = threadIdx.x % 8; q < l; q += 8) { oidx[d + q] = sidx[s + q] - kterm; oval[d + q] = sval[s + q]; }
 }
 
-static int scan_i32(hipStream_t st, const int32_t *in, int32_t *out, int count)
-{
-    size_t tb = 0;
-    ILUPP_HIP(hipcub::DeviceScan::ExclusiveSum(nullptr, tb, in, out, count, st));
-    PoolBlock tmp;
-    ILUPP_HIP(tmp.alloc(tb > 0 ? tb : 1));
-    ILUPP_HIP(hipcub::DeviceScan::ExclusiveSum(tmp.p, tb, in, out, count, st));
-    ILUPP_HIP(hipStreamSynchronize(st));
-    return ILUPP_OK;
-}
-
 struct HostLap {                               // wall-clock laps of an attempt (ILUPP_DEBUG)
     bool on; std::chrono::steady_clock::time_point t;
     explicit HostLap(bool o) : on(o), t(std::chrono::steady_clock::now()) {}
@@ -799,99 +786,59 @@ struct HostLap {                               // wall-clock laps of an attempt 
     }
 };
 
-static void launch_class(int cls, int waves, hipStream_t st, const PilucArgs &a)
-{
-    if (cls == 0) hipLaunchKernelGGL((k_piluc_df<256, 128, 32, false>), dim3(waves), dim3(64), 0, st, a);
-    else if (cls == 1) hipLaunchKernelGGL((k_piluc_df<768, 256, 64, false>), dim3(waves), dim3(64), 0, st, a);
-    else if (cls == 2) hipLaunchKernelGGL((k_piluc_df<1024, 512, 128, false>), dim3(waves), dim3(64), 0, st, a);
-    else if (cls == 3) hipLaunchKernelGGL((k_piluc_df<768, 256, 512, false>), dim3(waves), dim3(64), 0, st, a);
-    else hipLaunchKernelGGL((k_piluc_df<1, 1, 1, true>), dim3(waves), dim3(64), 0, st, a);
-}
-
-// one attempt with one capacity class and one store size; ILUPP_OK / an error / +1 = "outside this class" / +2 = "stores too small"
+// one attempt with one capacity class and one store size; ILUPP_OK / an error / kOutsideClass / kStoresTooSmall
 static int piluc_attempt(hipStream_t st, const DevMat &Av, const PilucParams &P, bool force_finish, double tau, DevMat *L, DevMat *U, double **Dinv_out,
                          DevMat *Anew, int32_t *kterm_out, float *kernel_ms, int cls, long store, int gns, long gne, int *which_capacity)
 {
     const int32_t m = Av.n;
-    int T = cls == 0 ? 32 : (cls == 1 ? 64 : (cls == 2 ? 128 : (cls == 3 ? 512 : 16)));
-    if (cls == 4) { while (T < 4096 && T < m) T *= 2; }
+    int T = crout_records(kPilucClass, cls, m);
     while (T > 16 && ((long)m * T > 0x7fffffffL || (size_t)m * T * 64 > ((size_t)64 << 30))) T /= 2;
-    if ((long)m * T > 0x7fffffffL) return 1;
+    if ((long)m * T > 0x7fffffffL) return kOutsideClass;
     if (store > 0x7ffffff0L) store = 0x7ffffff0L;
 
     HostLap laps(getenv("ILUPP_DEBUG") != nullptr && getenv("ILUPP_PILUC_LAPS") != nullptr);
-    PoolBlock b_pending, b_colcnt, b_colptr, b_fillc, b_colpos, b_colord, b_rowof, b_Uidx, b_Lidx, b_Uval, b_Lval, b_Ustart, b_Ulen, b_Lstart, b_Llen,
-              b_cntL, b_cntU, b_recL, b_recU, b_rq, b_ctrl, b_gws, b_dinv;
-    const size_t nz = (size_t)(Av.nnz > 0 ? Av.nnz : 1);
-    ILUPP_HIP(b_pending.alloc(sizeof(int32_t) * (size_t)m));
-    ILUPP_HIP(b_colcnt.alloc(sizeof(int32_t) * (size_t)(m + 1)));
-    ILUPP_HIP(b_colptr.alloc(sizeof(int32_t) * (size_t)(m + 1)));
-    ILUPP_HIP(b_fillc.alloc(sizeof(int32_t) * (size_t)(m + 1)));
-    ILUPP_HIP(b_colpos.alloc(sizeof(int32_t) * nz));
-    ILUPP_HIP(b_colord.alloc(sizeof(int32_t) * nz));
-    ILUPP_HIP(b_rowof.alloc(sizeof(int32_t) * nz));
-    ILUPP_HIP(b_Uidx.alloc(sizeof(int32_t) * (size_t)store));
-    ILUPP_HIP(b_Lidx.alloc(sizeof(int32_t) * (size_t)store));
-    ILUPP_HIP(b_Uval.alloc(sizeof(double) * (size_t)store));
-    ILUPP_HIP(b_Lval.alloc(sizeof(double) * (size_t)store));
-    ILUPP_HIP(b_Ustart.alloc(sizeof(int32_t) * (size_t)(m + 1)));
-    ILUPP_HIP(b_Ulen.alloc(sizeof(int32_t) * (size_t)(m + 1)));
-    ILUPP_HIP(b_Lstart.alloc(sizeof(int32_t) * (size_t)(m + 1)));
-    ILUPP_HIP(b_Llen.alloc(sizeof(int32_t) * (size_t)(m + 1)));
-    ILUPP_HIP(b_cntL.alloc(sizeof(int32_t) * (size_t)m));
-    ILUPP_HIP(b_cntU.alloc(sizeof(int32_t) * (size_t)m));
-    ILUPP_HIP(b_recL.alloc((size_t)m * T * 32));
-    ILUPP_HIP(b_recU.alloc((size_t)m * T * 32));
-    const size_t rq_len = (size_t)kCuQ * (size_t)((m + kCuQ - 1) / kCuQ) + (size_t)m;
-    ILUPP_HIP(b_rq.alloc(sizeof(int32_t) * rq_len));
-    const size_t ctrl_bytes = sizeof(int32_t) * (size_t)(kCuQBase + 64 * kCuQ);
-    ILUPP_HIP(b_ctrl.alloc(ctrl_bytes));
+    CroutWork w;
+    DfQueues q;
+    PoolArray<int32_t> Uidx, Lidx, Ustart, Ulen, Lstart, Llen;      // the stores, and where a step's row of U / column of L lies in them
+    PoolArray<double> Uval, Lval;
+    PoolBlock b_gws, b_dinv;
+    w.alloc(m, Av.nnz, T);
+    Uidx.alloc(store); Lidx.alloc(store); Uval.alloc(store); Lval.alloc(store);
+    Ustart.alloc(m + 1); Ulen.alloc(m + 1); Lstart.alloc(m + 1); Llen.alloc(m + 1);
+    q.alloc(m);
     ILUPP_HIP(b_dinv.alloc(sizeof(double) * (size_t)m));
-    int32_t *pending = b_pending.as<int32_t>(), *colcnt = b_colcnt.as<int32_t>(), *colptr = b_colptr.as<int32_t>(), *fillc = b_fillc.as<int32_t>(),
-            *colpos = b_colpos.as<int32_t>(), *colord = b_colord.as<int32_t>(), *rowof = b_rowof.as<int32_t>(), *cntL = b_cntL.as<int32_t>(),
-            *cntU = b_cntU.as<int32_t>(), *rq = b_rq.as<int32_t>(), *ctrl = b_ctrl.as<int32_t>();
-    unsigned long long *recL = b_recL.as<unsigned long long>(), *recU = b_recU.as<unsigned long long>();
-    ILUPP_HIP(hipMemsetAsync(pending, 0, sizeof(int32_t) * (size_t)m, st));
-    ILUPP_HIP(hipMemsetAsync(colcnt, 0, sizeof(int32_t) * (size_t)(m + 1), st));
-    ILUPP_HIP(hipMemsetAsync(fillc, 0, sizeof(int32_t) * (size_t)(m + 1), st));
-    ILUPP_HIP(hipMemsetAsync(cntL, 0, sizeof(int32_t) * (size_t)m, st));
-    ILUPP_HIP(hipMemsetAsync(cntU, 0, sizeof(int32_t) * (size_t)m, st));
-    ILUPP_HIP(hipMemsetAsync(b_Ulen.p, 0, sizeof(int32_t) * (size_t)(m + 1), st));
-    ILUPP_HIP(hipMemsetAsync(b_Llen.p, 0, sizeof(int32_t) * (size_t)(m + 1), st));
-    ILUPP_HIP(hipMemsetAsync(rq, 0xff, sizeof(int32_t) * rq_len, st));
-    ILUPP_HIP(hipMemsetAsync(ctrl, 0, ctrl_bytes, st));
-    const int32_t big = 0x7fffffff;
-    ILUPP_HIP(hipMemcpyAsync(ctrl + 3, &big, sizeof(int32_t), hipMemcpyHostToDevice, st));
+    w.clear(st);
+    Ulen.zero(st, m + 1); Llen.zero(st, m + 1);
+    q.clear(st);
     laps.lap(st, "allocations, memsets");
     const int gb = (m + 255) / 256;
-    hipLaunchKernelGGL(k_iluc_prep, dim3(gb), dim3(256), 0, st, m, Av.ptr, Av.idx, pending, colcnt);
-    hipLaunchKernelGGL(k_iluc_rowof, dim3(gb), dim3(256), 0, st, m, Av.ptr, rowof);
-    { const int rc = scan_i32(st, colcnt, colptr, m + 1); if (rc) return rc; }
-    { const int rc = iluc_column_order(st, m, Av, colcnt, colptr, fillc, colpos, rowof, colord); if (rc) return rc; }
-    int waves = device_cu_count() * (cls == 0 ? 16 : (cls == 1 ? 8 : (cls == 2 ? 2 : (cls == 3 ? 2 : 4))));
+    w.count_columns(st, Av);
+    scan_i32(st, (const int32_t *)w.colcnt.get(), w.colptr.get(), m + 1);
+    { const int rc = w.column_order(st, Av); if (rc) return rc; }
+    int waves = device_cu_count() * kPilucClass[cls].waves_per_cu;
     if (waves > m) waves = m;
     int gNE = 0, gNS = 0, gTM = 0;
-    if (cls == 4) {
+    if (cls == kCroutGlobal) {
         gTM = T; gNS = gns;                                                     // (a power of two: the slot hash masks with a power of two <= 4 gNS)
-        gNE = (int)(gne > (1L << 26) ? (1L << 26) : gne);
+        gNE = (int)(gne > kPilucClass[kCroutGlobal].entries ? kPilucClass[kCroutGlobal].entries : gne);
         if (gNE < 2 * gNS) gNE = 2 * gNS;                        // (scratch of the sorts lies behind the first gNS entries)
         while (waves > 16 && (size_t)waves * piluc_ws_bytes(gNE, gNS, gTM) > ((size_t)PILUC_WSGB << 30)) waves /= 2;
         if ((size_t)waves * piluc_ws_bytes(gNE, gNS, gTM) > ((size_t)PILUC_WSGB << 30)) return ILUPP_ERR_UNSUPPORTED;
         ILUPP_HIP(b_gws.alloc((size_t)waves * piluc_ws_bytes(gNE, gNS, gTM)));
     }
     laps.lap(st, "column order of A, work space");
-    const int nq = waves < kCuQ ? waves : kCuQ;
-    hipLaunchKernelGGL(k_piluc_count_seeds, dim3(gb), dim3(256), 0, st, m, nq, pending, ctrl);
-    hipLaunchKernelGGL(k_iluc_seed, dim3(gb), dim3(256), 0, st, m, nq, pending, rq, ctrl);
+    const int nq = DfQueues::queues_for(waves);
+    hipLaunchKernelGGL(k_piluc_count_seeds, dim3(gb), dim3(256), 0, st, m, nq, w.pending, q.ctrl);
+    hipLaunchKernelGGL(k_iluc_seed, dim3(gb), dim3(256), 0, st, m, nq, w.pending, q.rq, q.ctrl);
     PilucArgs a;
     a.gws = b_gws.as<unsigned char>(); a.gNE = gNE; a.gNS = gNS; a.gTM = gTM;
-    a.n = m; a.ptr = Av.ptr; a.idx = Av.idx; a.val = Av.val; a.colptr = colptr; a.colord = colord; a.rowof = rowof;
+    a.n = m; a.ptr = Av.ptr; a.idx = Av.idx; a.val = Av.val; a.colptr = w.colptr; a.colord = w.colord; a.rowof = w.rowof;
     a.tau = tau; a.min_pivot = P.min_pivot;
-    a.park_from = big;
+    a.park_from = kDfNone;
     if (!force_finish && P.small_pivot_terminates) {
         // k > MIN_ELIM_FACTOR * n (:1619), k an integer: k > floor(x) for x >= 0
         const double x = P.min_elim_factor * (double)m;
-        a.park_from = x < 0.0 ? -1 : (x >= 2147483647.0 ? big : (int32_t)x);
+        a.park_from = x < 0.0 ? -1 : (x >= 2147483647.0 ? kDfNone : (int32_t)x);
     }
     a.rules = P.rules; a.combine = P.combine; a.scale_invdiag = P.scale_invdiag ? 1 : 0;
     for (int q = 0; q < 5; ++q) a.wgt[q] = P.wgt[q];
@@ -900,25 +847,31 @@ static int piluc_attempt(hipStream_t st, const DevMat &Av, const PilucParams &P,
     if (max_fill < 1) max_fill = 1;
     if (max_fill > m) max_fill = m;
     a.budget = max_fill - 1;
-    a.schur = 0; a.kterm = big; a.T = T; a.nq = nq;
-    a.Uidx = b_Uidx.as<int32_t>(); a.Lidx = b_Lidx.as<int32_t>(); a.Uval = b_Uval.as<double>(); a.Lval = b_Lval.as<double>();
+    a.schur = 0; a.kterm = kDfNone; a.T = T; a.nq = nq;
+    a.Uidx = Uidx; a.Lidx = Lidx; a.Uval = Uval; a.Lval = Lval;
     a.capU = (int32_t)store; a.capL = (int32_t)store;
     {
         long c = store / (4L * waves);                      // (the waves' open chunks together: at most a quarter of a store)
         a.chunk = (int32_t)(c < 16 ? 16 : (c > 4096 ? 4096 : c));
     }
-    a.Ustart = b_Ustart.as<int32_t>(); a.Ulen = b_Ulen.as<int32_t>(); a.Lstart = b_Lstart.as<int32_t>(); a.Llen = b_Llen.as<int32_t>();
+    a.Ustart = Ustart; a.Ulen = Ulen; a.Lstart = Lstart; a.Llen = Llen;
     a.Dinv = b_dinv.as<double>();
     a.Sidx = nullptr; a.Sval = nullptr; a.capS = 0; a.Sstart = nullptr; a.Slen = nullptr;
-    a.cntL = cntL; a.cntU = cntU; a.recL = recL; a.recU = recU; a.pending = pending; a.rq = rq; a.ctrl = ctrl;
-    struct Events { hipEvent_t a = nullptr, b = nullptr; ~Events() { if (a) (void)hipEventDestroy(a); if (b) (void)hipEventDestroy(b); } } ev;
-    ILUPP_HIP(hipEventCreate(&ev.a));
-    ILUPP_HIP(hipEventCreate(&ev.b));
+    a.cntL = w.cntL; a.cntU = w.cntU; a.recL = w.recL; a.recU = w.recU; a.pending = w.pending; a.rq = q.rq; a.ctrl = q.ctrl;
+    auto launch = [&](const PilucArgs &x) {              // (the elimination, then the Schur rows: the same class and waves)
+        if (cls == 0) hipLaunchKernelGGL((k_piluc_df<DF_LDS_CLASS(kPilucClass, 0)>), dim3(waves), dim3(64), 0, st, x);
+        else if (cls == 1) hipLaunchKernelGGL((k_piluc_df<DF_LDS_CLASS(kPilucClass, 1)>), dim3(waves), dim3(64), 0, st, x);
+        else if (cls == 2) hipLaunchKernelGGL((k_piluc_df<DF_LDS_CLASS(kPilucClass, 2)>), dim3(waves), dim3(64), 0, st, x);
+        else if (cls == 3) hipLaunchKernelGGL((k_piluc_df<DF_LDS_CLASS(kPilucClass, 3)>), dim3(waves), dim3(64), 0, st, x);
+        else hipLaunchKernelGGL((k_piluc_df<1, 1, 1, true>), dim3(waves), dim3(64), 0, st, x);
+    };
+    EventPair ev;
+    ILUPP_HIP(ev.create());
     ILUPP_HIP(hipEventRecord(ev.a, st));
-    launch_class(cls, waves, st, a);
+    launch(a);
     ILUPP_HIP(hipGetLastError());
     int32_t h[8];
-    ILUPP_HIP(hipMemcpyAsync(h, ctrl, 32, hipMemcpyDeviceToHost, st));
+    ILUPP_HIP(hipMemcpyAsync(h, q.ctrl, 32, hipMemcpyDeviceToHost, st));
     ILUPP_HIP(hipStreamSynchronize(st));
     laps.lap(st, "elimination kernel");
     const bool dbg = getenv("ILUPP_DEBUG") != nullptr;
@@ -928,42 +881,38 @@ static int piluc_attempt(hipStream_t st, const DevMat &Av, const PilucParams &P,
         ILUPP_HIP(hipEventSynchronize(ev.b));
         ILUPP_HIP(hipEventElapsedTime(&ms, ev.a, ev.b));
         fprintf(stderr, "[ilupp] piluc: n %d class %d (slots %d) T %d waves %d store %ld: status %d kterm %d finished %d left %d cursors %d %d, %.1f ms\n", m, cls,
-                cls == 4 ? gNS : 0, T, waves, store, h[2], h[3], h[4], h[5], h[6], h[7], ms);
+                cls == kCroutGlobal ? gNS : 0, T, waves, store, h[2], h[3], h[4], h[5], h[6], h[7], ms);
     }
-    if (h[2] == 2) return ILUPP_ERR_TIMEOUT;
-    if (h[2] == 16) return 2;
-    if (h[2] != 0) { if (which_capacity) *which_capacity = h[2]; return 1; }
-    const int32_t kterm = h[3] == big ? m : h[3];
+    if (h[2] == kStTimeout) return ILUPP_ERR_TIMEOUT;
+    if (h[2] == kStStores) return kStoresTooSmall;
+    if (h[2] != kStOk) { if (which_capacity) *which_capacity = h[2]; return kOutsideClass; }
+    const int32_t kterm = h[3] == kDfNone ? m : h[3];
     *kterm_out = kterm;
     // ---- the Schur complement ----
-    PoolBlock b_Sidx, b_Sval, b_Sstart, b_Slen, b_pendS;
+    PoolArray<int32_t> Sidx, Sstart, Slen, pendS;
+    PoolArray<double> Sval;
     const int32_t nS = m - kterm;
     if (nS > 0) {
         long capS = store;
-        ILUPP_HIP(b_Sidx.alloc(sizeof(int32_t) * (size_t)capS));
-        ILUPP_HIP(b_Sval.alloc(sizeof(double) * (size_t)capS));
-        ILUPP_HIP(b_Sstart.alloc(sizeof(int32_t) * (size_t)(nS + 1)));
-        ILUPP_HIP(b_Slen.alloc(sizeof(int32_t) * (size_t)(nS + 1)));
-        ILUPP_HIP(b_pendS.alloc(sizeof(int32_t) * (size_t)m));
-        ILUPP_HIP(hipMemsetAsync(b_Slen.p, 0, sizeof(int32_t) * (size_t)(nS + 1), st));
-        ILUPP_HIP(hipMemsetAsync(rq, 0xff, sizeof(int32_t) * rq_len, st));
-        ILUPP_HIP(hipMemsetAsync(ctrl, 0, ctrl_bytes, st));
+        Sidx.alloc(capS); Sval.alloc(capS); Sstart.alloc(nS + 1); Slen.alloc(nS + 1); pendS.alloc(m);
+        Slen.zero(st, nS + 1);
+        q.clear(st, false);
         const int gs = (nS + 255) / 256;
-        hipLaunchKernelGGL(k_piluc_schur_pending, dim3(gs), dim3(256), 0, st, m, kterm, T, cntL, recL, b_pendS.as<int32_t>());
-        hipLaunchKernelGGL(k_piluc_schur_seed, dim3(gs), dim3(256), 0, st, m, kterm, nq, b_pendS.as<int32_t>(), rq, ctrl);
+        hipLaunchKernelGGL(k_piluc_schur_pending, dim3(gs), dim3(256), 0, st, m, kterm, T, w.cntL, w.recL, pendS);
+        hipLaunchKernelGGL(k_piluc_schur_seed, dim3(gs), dim3(256), 0, st, m, kterm, nq, pendS, q.rq, q.ctrl);
         PilucArgs s = a;
         s.schur = 1; s.kterm = kterm; s.tau = tau * P.threshold_shift_schur;              // threshold *= threshold_Schur_factor, :1622
         s.budget = max_fill;                                                              // take_largest(..., max_fill_in, ...), :1717
-        s.pending = b_pendS.as<int32_t>();
-        s.Sidx = b_Sidx.as<int32_t>(); s.Sval = b_Sval.as<double>(); s.capS = (int32_t)capS; s.Sstart = b_Sstart.as<int32_t>(); s.Slen = b_Slen.as<int32_t>();
-        launch_class(cls, waves, st, s);
+        s.pending = pendS;
+        s.Sidx = Sidx; s.Sval = Sval; s.capS = (int32_t)capS; s.Sstart = Sstart; s.Slen = Slen;
+        launch(s);
         ILUPP_HIP(hipGetLastError());
-        ILUPP_HIP(hipMemcpyAsync(h, ctrl, 32, hipMemcpyDeviceToHost, st));
+        ILUPP_HIP(hipMemcpyAsync(h, q.ctrl, 32, hipMemcpyDeviceToHost, st));
         ILUPP_HIP(hipStreamSynchronize(st));
         if (dbg) fprintf(stderr, "[ilupp] piluc: Schur rows %d: status %d finished %d left %d cursor %d\n", nS, h[2], h[4], h[5], h[6]);
-        if (h[2] == 2) return ILUPP_ERR_TIMEOUT;
-        if (h[2] == 16) return 2;
-        if (h[2] != 0) { if (which_capacity) *which_capacity = h[2]; return 1; }
+        if (h[2] == kStTimeout) return ILUPP_ERR_TIMEOUT;
+        if (h[2] == kStStores) return kStoresTooSmall;
+        if (h[2] != kStOk) { if (which_capacity) *which_capacity = h[2]; return kOutsideClass; }
         if (h[4] != nS) { set_error("partialILUC: Schur rows left unprocessed"); return ILUPP_ERR_INTERNAL; }
     }
     laps.lap(st, "Schur complement");
@@ -982,8 +931,8 @@ static int piluc_attempt(hipStream_t st, const DevMat &Av, const PilucParams &P,
         hipLaunchKernelGGL(k_piluc_count, dim3(gb1), dim3(256), 0, st, m, kterm, starts[d], lens[d], svals[d], b_cnt.as<int32_t>(), b_err.as<int32_t>());
         ILUPP_HIP(pool_malloc(&M->ptr, sizeof(int32_t) * (size_t)(m + 1)));
         M->owns = true;
-        { const int rc = scan_i32(st, b_cnt.as<int32_t>(), M->ptr, m + 1); if (rc) return rc; }
         int32_t nnz = 0, e = 0;
+        scan_i32(st, b_cnt.as<const int32_t>(), M->ptr, m + 1);
         ILUPP_HIP(hipMemcpyAsync(&nnz, M->ptr + m, sizeof(int32_t), hipMemcpyDeviceToHost, st));
         ILUPP_HIP(hipMemcpyAsync(&e, b_err.p, sizeof(int32_t), hipMemcpyDeviceToHost, st));
         ILUPP_HIP(hipStreamSynchronize(st));
@@ -997,15 +946,15 @@ static int piluc_attempt(hipStream_t st, const DevMat &Av, const PilucParams &P,
     Anew->n = nS; Anew->nnz = 0; Anew->is_csr = true; Anew->owns = true;
     if (nS > 0) {
         ILUPP_HIP(pool_malloc(&Anew->ptr, sizeof(int32_t) * (size_t)(nS + 1)));
-        { const int rc = scan_i32(st, b_Slen.as<int32_t>(), Anew->ptr, nS + 1); if (rc) return rc; }
         int32_t nnz = 0;
+        scan_i32(st, (const int32_t *)Slen.get(), Anew->ptr, nS + 1);
         ILUPP_HIP(hipMemcpyAsync(&nnz, Anew->ptr + nS, sizeof(int32_t), hipMemcpyDeviceToHost, st));
         ILUPP_HIP(hipStreamSynchronize(st));
         Anew->nnz = nnz;
         ILUPP_HIP(pool_malloc(&Anew->idx, sizeof(int32_t) * (size_t)(nnz > 0 ? nnz : 1)));
         ILUPP_HIP(pool_malloc(&Anew->val, sizeof(double) * (size_t)(nnz > 0 ? nnz : 1)));
-        hipLaunchKernelGGL(k_piluc_schur_write, dim3((nS + 31) / 32), dim3(256), 0, st, nS, kterm, b_Sstart.as<int32_t>(), b_Slen.as<int32_t>(),
-                           b_Sidx.as<int32_t>(), b_Sval.as<double>(), Anew->ptr, Anew->idx, Anew->val);
+        hipLaunchKernelGGL(k_piluc_schur_write, dim3((nS + 31) / 32), dim3(256), 0, st, nS, kterm, Sstart, Slen, Sidx, Sval, Anew->ptr, Anew->idx,
+                           Anew->val);
     }
     ILUPP_HIP(hipStreamSynchronize(st));
     laps.lap(st, "factors as CSR arrays");
@@ -1022,15 +971,8 @@ int piluc_level(hipStream_t st, const DevMat &Av, const PilucParams &P, bool for
 {
     if (Av.n < 1) return ILUPP_ERR_INVALID;
     long store = 3 * (long)Av.nnz + 2 * (long)Av.n + 1024;            // (the reference starts from MEM_FACTOR = 3 times nnz and doubles, :1483-1485, :1771-1773)
-    int cls = 0;
-    {
-        const long avg = Av.nnz / Av.n + 1;
-        // the kernel's time goes like 1 / (resident waves) -- a step is a few dozen dependent memory round trips -- and the smallest class has
-        // the most waves (C5: 9 / 19 / 38 ms in classes 0 / 1 / 2); an attempt in a class that turns out too small costs at most its own short run
-        cls = avg <= 16 ? 0 : (avg <= 40 ? 1 : 2);
-        if (const char *e = getenv("ILUPP_PILUC_CLASS")) cls = atoi(e) < 0 ? 0 : (atoi(e) > 4 ? 4 : atoi(e));     // (experiments)
-    }
-    int rc = 1;
+    int cls = start_class_from_env("ILUPP_PILUC_CLASS", piluc_start_class(Av.nnz, Av.n), kCroutGlobal);
+    int rc = kOutsideClass;
     int gns = 2048;
     long gne = 65536;
     bool chain_tried = getenv("ILUPP_NO_PILUC_CHAIN") != nullptr;
@@ -1042,42 +984,40 @@ int piluc_level(hipStream_t st, const DevMat &Av, const PilucParams &P, bool for
         chain_tried = true;
         L->release(); U->release(); Anew->release();
         const int rcc = piluc_chain_level(st, Av, P, force_finish, tau, L, U, Dinv, Anew, kterm, kernel_ms, true);
-        if (rcc == 1) { set_error(why); return ILUPP_ERR_UNSUPPORTED; }
+        if (rcc == kOutsideClass) { set_error(why); return ILUPP_ERR_UNSUPPORTED; }
         return rcc;
     };
-    while (rc == 1 || rc == 2) {
+    while (rc == kOutsideClass || rc == kStoresTooSmall) {
         int which = 0;
         L->release(); U->release(); Anew->release();
-        if (cls == 4 && !chain_tried && Av.n <= (1 << 18)) {           // (a chain of more steps than that costs tens of seconds before it can find out that a row does not fit)
+        if (cls == kCroutGlobal && !chain_tried && Av.n <= (1 << 18)) {           // (a chain of more steps than that costs tens of seconds before it can find out that a row does not fit)
             // rows too long for the LDS classes: the steps of such a factorisation depend on one another almost one by one, and the largest
             // class walks them through global-memory slots (700 us per step on the critical path).  The chain kernel walks them in LDS, and from
             // the step whose vectors outgrow LDS on, in global memory (fill of 88 entries per row, n = 2e4: 5.3 s against 14.8 s in the largest class).
             chain_tried = true;
             const int rcc = piluc_chain_level(st, Av, P, force_finish, tau, L, U, Dinv, Anew, kterm, kernel_ms, getenv("ILUPP_NO_PILUC_MEM_CHAIN") == nullptr);
-            if (rcc != 1) { rc = rcc; break; }
+            if (rcc != kOutsideClass) { rc = rcc; break; }
             L->release(); U->release(); Anew->release();
         }
         rc = piluc_attempt(st, Av, P, force_finish, tau, L, U, Dinv, Anew, kterm, kernel_ms, cls, store, gns, gne, &which);
-        if (rc == 1) {
-            const bool records = which == 12 || which == 15;          // more touch records per step than the class holds
-            if (cls < 4) {
-                // (class 3 has the records of many steps but no more entries or slots than class 2)
-                cls = records ? (cls < 2 ? 2 : cls + 1) : (cls < 2 ? cls + 1 : 4);
+        if (rc == kOutsideClass) {
+            if (cls < kCroutGlobal) {
+                cls = piluc_next_class(cls, which);
                 // (an attempt in the largest class takes seconds where the others take milliseconds, and rows that long fill the factors: it
                 //  starts with stores that a "stores too small" is unlikely to send back to the start -- 16 nnz + 8 n entries per factor)
-                if (cls == 4) { const long big = 16 * (long)Av.nnz + 8 * (long)Av.n + 1024; if (store < big) store = big; }
-            } else if (records) {
+                if (cls == kCroutGlobal) { const long big = 16 * (long)Av.nnz + 8 * (long)Av.n + 1024; if (store < big) store = big; }
+            } else if (is_records(which)) {            // more touch records per step than the class holds
                 rc = last_resort("partialILUC: a step is reached by more than 4096 stored entries");
-            } else if (which == 13) {                                  // the entries of a working row: at most (contributors) x (row length)
-                if (gne >= (1L << 26)) rc = last_resort("partialILUC: a working row gathers more than 2^26 entries");
+            } else if (which == kStEntries) {                                  // the entries of a working row: at most (contributors) x (row length)
+                if (gne >= kPilucClass[kCroutGlobal].entries) rc = last_resort("partialILUC: a working row gathers more than 2^26 entries");
                 else gne *= 4;
             } else {                                                   // its slots: at most n + 1
                 if (gns > 2 * (long)Av.n + 2) rc = last_resort("partialILUC: a working row does not fit the largest capacity class");
                 else { gns *= 4; if (gne < 8L * gns) gne = 8L * gns; }
             }
-        } else if (rc == 2) {
+        } else if (rc == kStoresTooSmall) {
             if (store >= 0x7ffffff0L) { set_error("partialILUC: the factors of a level exceed 2^31 entries"); rc = ILUPP_ERR_MEMORY; break; }
-            store *= cls == 4 ? 4 : 2;
+            store *= cls == kCroutGlobal ? 4 : 2;
         } else if (rc == ILUPP_ERR_UNSUPPORTED) {
             set_error("partialILUC: the working arrays of the largest capacity class exceed the memory set aside for them");
         }
