@@ -100,6 +100,8 @@ def lib():
     L.ilupp_hip_analysis_path.restype = ctypes.c_char_p
     L.ilupp_hip_debug_static_table.argtypes = [_VP, ctypes.c_int, _VP, ctypes.c_longlong]
     L.ilupp_hip_debug_static_table.restype = ctypes.c_longlong
+    L.ilupp_hip_debug_level_order.argtypes = [_VP, ctypes.c_int, _VP, ctypes.c_longlong, _VP]
+    L.ilupp_hip_debug_level_order.restype = ctypes.c_longlong
     L.ilupp_hip_kernel_names.argtypes = [_VP]
     L.ilupp_hip_kernel_names.restype = ctypes.c_char_p
     L.ilupp_hip_destroy.argtypes = [_VP]
@@ -221,7 +223,7 @@ ABI_SYMBOLS = [
     "ilupp_hip_num_factors", "ilupp_hip_factor_info", "ilupp_hip_factor_copy",
     "ilupp_hip_factor_device_ptrs", "ilupp_hip_get_timings", "ilupp_hip_ilu0_refactor_device",
     "ilupp_hip_sync", "ilupp_hip_release_cached_memory", "ilupp_hip_set_cache_limit", "ilupp_hip_cached_bytes", "ilupp_hip_live_blocks", "ilupp_hip_ilut_create_device", "ilupp_hip_ichol0_create_device",
-    "ilupp_hip_icholt_create_device", "ilupp_hip_set_caller_stream", "ilupp_hip_path", "ilupp_hip_analysis_path", "ilupp_hip_debug_static_table", "ilupp_hip_kernel_names", "ilupp_hip_spmv_device",
+    "ilupp_hip_icholt_create_device", "ilupp_hip_set_caller_stream", "ilupp_hip_path", "ilupp_hip_analysis_path", "ilupp_hip_debug_static_table", "ilupp_hip_debug_level_order", "ilupp_hip_kernel_names", "ilupp_hip_spmv_device",
     "ilupp_hip_iluc_create", "ilupp_hip_iluc_create_device",
     "ilupp_hip_ml_default_params", "ilupp_hip_ml_create", "ilupp_hip_ml_create_device", "ilupp_hip_ml_destroy", "ilupp_hip_ml_apply",
     "ilupp_hip_ml_apply_device", "ilupp_hip_ml_apply_part_device", "ilupp_hip_ml_sync", "ilupp_hip_ml_levels", "ilupp_hip_ml_total_nnz", "ilupp_hip_ml_level_info",
@@ -426,6 +428,16 @@ class Preconditioner:
     def analysis_path(self):
         """ILU(0): "grid" when the row blocks came from the box-grid guess (proven row by row), else "general" (measurement hook)"""
         return lib().ilupp_hip_analysis_path(self._h).decode()
+
+    def level_order(self, which):
+        """(perm, info) of ilupp_hip_debug_level_order: the level order of slot `which` (0 .. 3 the level-ordered copies of L, U, U^T, L^T,
+        4 the factor order of an "ilu0:level-order" object) as perm[position] = row and the eight info words; perm is None where that order
+        does not exist.  Builds nothing: call an apply first (test hook)"""
+        n = lib().ilupp_hip_dimension(self._h)
+        perm = np.empty(n, dtype=np.int32)
+        info = np.zeros(8, dtype=np.int32)
+        got = lib().ilupp_hip_debug_level_order(self._h, which, perm.ctypes.data, n, info.ctypes.data)
+        return (perm[:got] if got >= 0 else None), info
 
     def kernel_names(self):
         """(factor kernel, forward sweep, backward sweep) of a static ILU(0) object or of an LL^T object (its sweeps once an apply has built them), else () (measurement hook)"""

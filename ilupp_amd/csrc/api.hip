@@ -205,6 +205,8 @@ struct ilupp_precond {
     LevelSweep lvl[4];               // Lc, Uc, UcT, LcT in level order (long-row factors), built on first use
     int32_t *fperm = nullptr;        // ILU(0) of a long-row matrix: its rows in level order (ilu0_lvl.hip), also the forward sweep's order
     int32_t fperm_levels = 0;
+    LevelNumbering fperm_how;        // ... and how it was numbered (diagnostics: ilupp_hip_debug_level_order)
+    int8_t last_route[4] = {0, 0, 0, 0};   // per slot, the kernel family its last sweep ran on (SweepRoute; diagnostics)
     FactorLM flm;                    // level-major factor kernel state (then Lc.val / Uc.val are filled on demand)
     bool csr_vals = true;            // Lc.val / Uc.val hold the factor values
     int64_t nnzA = 0;                // stored entries of the factored matrix (same pattern on a numeric re-factorisation)
@@ -543,7 +545,7 @@ static int csr_and_level_fallbacks(ilupp_precond *p, const DevMat &A, bool lm, b
     bool by_level = false;
     if (!lm && p->max_row_len <= 64 && A.n >= 1024) {
         const bool longrows = A.nnz > 8 * (int64_t)A.n;
-        if ((longrows || !lvl_never) && lvl_order(st, 2, A.n, A.nnz, A.ptr, A.idx, p->sA, &p->fperm, &p->fperm_levels)) {
+        if ((longrows || !lvl_never) && lvl_order(st, 2, A.n, A.nnz, A.ptr, A.idx, p->sA, &p->fperm, &p->fperm_levels, &p->fperm_how)) {
             // (deep AND wide: a 1-D chain has n levels of one row -- nothing to run side by side, natural order is as good as any)
             by_level = longrows || (p->fperm_levels > 64 && A.n / p->fperm_levels >= 256);
             if (!by_level) { (void)pool_free(p->fperm); p->fperm = nullptr; p->fperm_levels = 0; }
@@ -807,19 +809,25 @@ static LevelSweep *level_sweep(ilupp_precond *p, SweepOp op)
     return s.lvl->valid ? s.lvl : nullptr;
 }
 
+// the kernel family a sweep ran on, kept per slot in last_route[] (diagnostics: ilupp_hip_debug_level_order's info[6])
+enum SweepRoute { SWEPT_NEVER = 0, SWEPT_STATIC = 1, SWEPT_LEVEL_MAJOR = 2, SWEPT_LEVEL_ORDER = 3, SWEPT_ROWS = 4, SWEPT_ROWS_DEGENERATE = 5,
+                  SWEPT_DESCRIPTORS = 6, SWEPT_GENERIC = 7 };
+
 static int sweep(ilupp_precond *p, SweepOp op, const PackedSweep *ps, double *rhs, double *out, int32_t *ticket, int32_t *err,
                  double *ypk_out = nullptr, const double *ypk_in = nullptr, const int32_t *ysrc = nullptr)
 {
     const SweepParts s = sweep_parts(p, op);
+    int8_t &route = p->last_route[op.slot];
     // every sweep but the static ones hands its unknowns over through `out` (the data is the flag): all-sentinel before it runs.
     // The static sweeps never touch the work vector, so an object that only ever runs them never pays for the fill.
     if (!(ps && ps->valid && ps->stat && !p->degenerate) && !p->work_clean) {
         fill_u64(p->stream, reinterpret_cast<unsigned long long *>(p->work), p->n, kSentinel);
         p->work_clean = true;
     }
-    if (p->degenerate) return sptrsv_rows(p->stream, op.kind, s.M, rhs, out, ticket, err);
+    if (p->degenerate) { route = SWEPT_ROWS_DEGENERATE; return sptrsv_rows(p->stream, op.kind, s.M, rhs, out, ticket, err); }
     if (ps && ps->valid) {
         // (the static sweeps exchange through a buffer of their own: `out` needs no sentinels before and `rhs` none after)
+        route = ps->stat ? SWEPT_STATIC : SWEPT_LEVEL_MAJOR;
         if (ps->stat) return sptrsv_st(p->stream, *ps, p->n, rhs, out, ticket, err, ypk_out, ypk_in, ysrc);
         OR_RETURN(sptrsv_lm(p->stream, *ps, s.sch, p->n, rhs, out, ticket, err, ypk_out, ypk_in, ysrc));
         fill_u64(p->stream, reinterpret_cast<unsigned long long *>(rhs), p->n, kSentinel);
@@ -833,9 +841,11 @@ static int sweep(ilupp_precond *p, SweepOp op, const PackedSweep *ps, double *rh
         // ... and the rows in level order: in natural order only the rows inside the window of resident tickets can run, on a mesh a
         // few grid lines
         const LevelSweep *ls = level_sweep(p, op);
+        route = ls ? SWEPT_LEVEL_ORDER : SWEPT_ROWS;
         if (ls) return sptrsv_lvl(p->stream, *ls, rhs, out, ticket, err);
         return sptrsv_rows(p->stream, op.kind, s.M, rhs, out, ticket, err);
     }
+    route = s.desc ? SWEPT_DESCRIPTORS : SWEPT_GENERIC;
     return sptrsv(p->stream, op.kind, s.M, s.sch, s.desc, s.maxlen, rhs, out, ticket, err);
 }
 // static form: records of U^T and L^T exist (built on first use; a pattern they cannot express is remembered)
@@ -903,12 +913,14 @@ int apply_dev(ilupp_precond *p, double *x, int transpose)
     const ApplyRoute route = prepare_apply(p, plan, &pf, &pb);
     if (route == ROUTE_STATIC_T) {
         // static form: the same two sweep kernels on records of U^T and L^T
+        p->last_route[plan.first.slot] = p->last_route[plan.second.slot] = SWEPT_STATIC;
         ILUPP_HIP(hipEventRecord(p->ev[0], st));
         OR_RETURN(sptrsv_st_T(st, p->pkL, p->n, x, y, t1, err, p->pkL.ybuf, nullptr));
         ILUPP_HIP(hipEventRecord(p->ev[1], st));
         OR_RETURN(sptrsv_st_T(st, p->pkU, p->n, y, x, t2, err, p->pkL.ybuf, p->pkU.ysrc));
     } else if (route == ROUTE_STATIC_PAIR) {
         // stencil-like factors (IChol0, ICholT without fill on a mesh): the static sweep kernels on the factor's own values
+        p->last_route[plan.first.slot] = p->last_route[plan.second.slot] = SWEPT_STATIC;
         ILUPP_HIP(hipEventRecord(p->ev[0], st));
         OR_RETURN(sptrsv_st(st, *pf, p->n, x, y, t1, err, pf->ybuf, nullptr, nullptr));
         ILUPP_HIP(hipEventRecord(p->ev[1], st));
@@ -989,7 +1001,10 @@ static bool block_level_plan(ilupp_precond *p, int transpose, LevelSweep **first
     };
     *first = lvl(plan.first);
     *second = lvl(plan.second);
-    return *first && *second && !p->degenerate;
+    if (!(*first && *second) || p->degenerate) return false;
+    // (the caller's chunks are level-order sweeps over these two slots, and they do not pass through sweep())
+    p->last_route[plan.first.slot] = p->last_route[plan.second.slot] = SWEPT_LEVEL_ORDER;
+    return true;
 }
 
 static int chunk_width(int64_t left) { return left >= kSptrsmMaxKB ? kSptrsmMaxKB : left >= 8 ? 8 : left >= 4 ? 4 : left >= 2 ? 2 : 1; }
@@ -1731,6 +1746,38 @@ long long ilupp_hip_debug_static_table(ilupp_precond *p, int which, int32_t *out
         if (cnt > cap) cnt = cap;
         ILUPP_HIP(stream_sync(p->stream));
         ILUPP_HIP(hipMemcpy(out, src, sizeof(int32_t) * (size_t)cnt, hipMemcpyDeviceToHost));
+        return cnt;
+    } catch (...) { return -1; }
+}
+
+/* diagnostics: the level order of slot `which` (0 .. 3: lvl[] = Lc, Uc, UcT, LcT; 4: the factor order of an "ilu0:level-order" object) as
+ * perm[position] = row, and in info[] {levels, the sweep's w, its block, how it was numbered (0 given, 1 natural pass, 2 relaxation,
+ * 3 relaxation given up then natural pass), relaxation batches, W of the natural pass, route of the last sweep over the slot (SweepRoute), 0}.
+ * Builds nothing; -1 where that order does not exist (info[6] is still the slot's last route then, the rest zero) */
+long long ilupp_hip_debug_level_order(ilupp_precond *p, int which, int32_t *perm_out, long long cap, int32_t info[8])
+{
+    try {
+        if (info) for (int k = 0; k < 8; ++k) info[k] = 0;
+        if (!p || !info || which < 0 || which > 4) return -1;
+        const int32_t *src = nullptr;
+        LevelNumbering how;
+        if (which == 4) {
+            if (!p->fperm) return -1;
+            src = p->fperm; how = p->fperm_how;
+            info[0] = p->fperm_levels;
+        } else {
+            const LevelSweep &ls = p->lvl[which];
+            info[6] = p->last_route[which];
+            if (!ls.valid || !ls.perm) return -1;
+            src = ls.perm; how = ls.how;
+            info[0] = ls.nlevels; info[1] = ls.w; info[2] = ls.block;
+        }
+        info[3] = how.route; info[4] = how.batches; info[5] = how.w;
+        long long cnt = perm_out ? p->n : 0;
+        if (cnt > cap) cnt = cap;
+        if (cnt < 0) cnt = 0;
+        ILUPP_HIP(stream_sync(p->stream));
+        if (cnt > 0) ILUPP_HIP(hipMemcpy(perm_out, src, sizeof(int32_t) * (size_t)cnt, hipMemcpyDeviceToHost));
         return cnt;
     } catch (...) { return -1; }
 }

@@ -103,10 +103,15 @@ static constexpr int kGhostBase = (1 << 17) - kGhosts;
 
 // One triangular factor renumbered in level order for the one-lane-per-row sweep (sptrsv_lvl.hip): rows sorted by
 // (level, row), columns rewritten to positions, each row = off-diagonal entries in application order + diagonal.
+// How lvl_order numbered an order (diagnostics only): route 1 = the natural-order pass, 2 = the relaxation converged, 3 = the relaxation
+// was given up and the natural pass ran; the batches of 32 relaxation passes that ran; the window W of the natural pass (0: none ran)
+struct LevelNumbering { int route = 0, batches = 0, w = 0; };
+
 struct LevelSweep {
     bool tried = false, valid = false;
     int32_t n = 0, nlevels = 0;
     int w = 8, block = 1024;                                    // window and block size of the sweep kernel
+    LevelNumbering how;                                         // (route 0: the order was given, a copy of the factor order)
     int32_t *ptr = nullptr, *idx = nullptr, *perm = nullptr;    // n+1, nnz, n (position -> row)
     double *val = nullptr, *xp = nullptr;                       // nnz; n unknowns in position order (what the rows poll)
     void release();
@@ -647,7 +652,7 @@ int ilu0_create_batch_launch(hipStream_t st, int32_t count, const RefactorDesc *
 
 // sptrsv_lvl.hip
 bool lvl_order(hipStream_t st, int mode, int32_t n, int64_t nnz, const int32_t *ptr, const int32_t *idx, const Schedule &sch,
-               int32_t **perm_out, int32_t *nlevels);
+               int32_t **perm_out, int32_t *nlevels, LevelNumbering *how = nullptr);
 bool lvl_build(hipStream_t st, SweepKind kind, const DevMat &M, const Schedule &sch, LevelSweep *ls, const int32_t *perm_given = nullptr,
                int32_t nlevels_given = 0);
 int ilu0_numeric_lvl(hipStream_t st, const DevMat &A, DevMat *L, DevMat *U, const int32_t *perm, int32_t *d_ctrl, float *kernel_ms);

@@ -29,7 +29,7 @@ void LevelSweep::release()
 {
     for (void *q : {(void *)ptr, (void *)idx, (void *)perm, (void *)val, (void *)xp}) if (q) (void)pool_free(q);
     ptr = idx = perm = nullptr; val = xp = nullptr;
-    valid = false; tried = false; nlevels = 0;
+    valid = false; tried = false; nlevels = 0; how = LevelNumbering();
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -377,9 +377,10 @@ k_sptrsv_lvl(int32_t n, const int32_t *__restrict__ ptrp, const int32_t *__restr
 // ---------------------------------------------------------------------------------------------
 // rows of a triangular pattern (or of the lower part of a general one, mode 2) sorted by (level, row): perm[position] = row
 bool lvl_order(hipStream_t st, int mode, int32_t n, int64_t nnz, const int32_t *ptr, const int32_t *idx, const Schedule &sch,
-               int32_t **perm_out, int32_t *nlevels)
+               int32_t **perm_out, int32_t *nlevels, LevelNumbering *how)
 {
     *perm_out = nullptr;
+    if (how) *how = LevelNumbering();
     if (sch.nb <= 0 || !sch.start || sch.fwd != (mode != 1)) return false;
     const unsigned grid = (unsigned)((sch.nb + kLvBlock - 1) / kLvBlock);
     constexpr int kLvLds = kLvRing * kLvBlock * (int)sizeof(unsigned long long);
@@ -407,6 +408,7 @@ bool lvl_order(hipStream_t st, int mode, int32_t n, int64_t nnz, const int32_t *
     // the 3-D mesh with holes, reach 63 000, at every size).  For mesh-like patterns the number of levels is about 3 n / reach
     // (2-D: reach = sqrt n, 3 sqrt n levels; 3-D: n^(2/3), 3 n^(1/3)): the relaxation where that estimate is at most 1 024.
     bool relax_ok = false;
+    int batches = 0;
     if ((per_row <= 4.5 || relax_all) && n >= 65536 && !no_relax) {
         const dim3 rg((unsigned)(((int64_t)n + 255) / 256)), rb(256);
         if (mode == 1) hipLaunchKernelGGL((k_lvl_reach<1>), rg, rb, 0, st, n, ptr, idx, ctl + 4);
@@ -425,7 +427,6 @@ bool lvl_order(hipStream_t st, int mode, int32_t n, int64_t nnz, const int32_t *
         const dim3 rg((unsigned)(((int64_t)n + 255) / 256)), rb(256);
         int32_t hf[32];
         static const int max_batches = getenv("ILUPP_LVL_RELAX_BATCHES") ? atoi(getenv("ILUPP_LVL_RELAX_BATCHES")) : 64;
-        int batches = 0;
         for (int batch = 0; batch < max_batches && !relaxed; ++batch) {
             ++batches;
             ILUPP_HIP(hipMemsetAsync(flags, 0, 32 * sizeof(int32_t), st));
@@ -469,6 +470,7 @@ bool lvl_order(hipStream_t st, int mode, int32_t n, int64_t nnz, const int32_t *
     if (!ok) { (void)pool_free(perm); return false; }
     *perm_out = perm;
     *nlevels = h[2] + 1;
+    if (how) { how->route = relaxed ? 2 : (relax_ok ? 3 : 1); how->batches = batches; how->w = relaxed ? 0 : w; }
     return true;
 }
 
@@ -482,10 +484,11 @@ bool lvl_build(hipStream_t st, SweepKind kind, const DevMat &M, const Schedule &
     const int32_t n = M.n;
     if (n < 1024 || !M.ptr || !M.idx || !M.val || M.nnz >= 0x7fffffffLL) return false;
     int32_t nlev = nlevels_given;
+    LevelNumbering how;
     if (perm_given) {
         ILUPP_HIP(pool_malloc(&ls->perm, sizeof(int32_t) * (size_t)n));
         ILUPP_HIP(hipMemcpyAsync(ls->perm, perm_given, sizeof(int32_t) * (size_t)n, hipMemcpyDeviceToDevice, st));
-    } else if (!lvl_order(st, kind == SWEEP_FWD_LAST_ASC ? 0 : 1, n, M.nnz, M.ptr, M.idx, sch, &ls->perm, &nlev)) {
+    } else if (!lvl_order(st, kind == SWEEP_FWD_LAST_ASC ? 0 : 1, n, M.nnz, M.ptr, M.idx, sch, &ls->perm, &nlev, &how)) {
         if (dbg) fprintf(stderr, "[ilupp] level order of a factor (kind %d, n %d): declined\n", (int)kind, n);
         return false;
     }
@@ -525,6 +528,7 @@ bool lvl_build(hipStream_t st, SweepKind kind, const DevMat &M, const Schedule &
     if (!ok) { ls->release(); ls->tried = true; return false; }
     ls->n = n;
     ls->nlevels = nlev;
+    ls->how = how;
     // window = the off-diagonal entries of an average row (a wider one makes every trip of the wait loop longer: 9-point, 4 entries:
     // 23 ms with 8, 34 ms with 16; a narrower one costs a round trip per refill: 27-point, 13 entries: 12 ms with 8, 7.5 ms with 16)
     const double offd = (double)M.nnz / (double)n - 1.0;

@@ -1,6 +1,6 @@
 """Which generation of ILU(0) kernels a matrix class gets WITHOUT any switch (every generation that stays compiled
 serves some matrix no newer kernel accepts).  Each case is also compared, as arrays, with the oracle's restatement of the reference
-(ILU0.hpp:26-106, sparse_implementation.h:4040-4087)."""
+(ILU0.hpp:26-106, sparse_implementation.h:4040-4087), and the kernel family of every sweep of its two applies is pinned (SWEEP_ROUTES)."""
 import numpy as np
 import pytest
 import scipy.sparse as sp
@@ -59,6 +59,25 @@ CASES = [
 ]
 
 
+# The kernel family each of the four stored triangles (L, U, U^T, L^T) sweeps on after apply and apply_trans, as recorded on an MI355X
+# (info[6] of ilupp_hip_debug_level_order: 1 static, 2 level-major, 3 level order, 4 one lane per row in natural order, 5 the same because a
+# factor is degenerate, 6 descriptor kernels, 7 generic kernel).  A case that falls silently to 4 or 7 fails here.  Two rows are no accident:
+# the 1-D chain of 200 000 rows has blocks beyond the compact encoding, hence no descriptors, hence the generic kernel; the arrow matrix's U
+# and L^T are the diagonal plus one column / row and pack into level-major records, its L and U^T (one long row) stay on the descriptors.
+SWEEP_ROUTES = {
+    'box grid 64x48x40': (1, 1, 1, 1),
+    "2-D grid below the grid analysis' size": (1, 1, 1, 1),
+    'chains without side neighbours': (1, 1, 1, 1),
+    'mesh with missing transposed entries': (1, 1, 1, 1),
+    'mesh with holes': (3, 3, 3, 3),
+    'small mesh 20^3': (6, 6, 6, 6),
+    '1-D chain': (7, 7, 7, 7),
+    'arrow matrix': (6, 2, 6, 2),
+    '27-point box stencil': (3, 3, 3, 3),
+    'random rows, 8 per row': (3, 3, 3, 3),
+}
+
+
 @pytest.mark.parametrize("name,make,path,kernels", CASES, ids=[c[0] for c in CASES])
 def test_path_without_switches(name, make, path, kernels):
     from oracle import oracle as O
@@ -78,3 +97,5 @@ def test_path_without_switches(name, make, path, kernels):
     assert np.array_equal(x, O.orc().apply_lu(L, U, b, O.ID))
     xt = b.copy(); P.apply_trans(xt)
     assert np.array_equal(xt, O.orc().apply_lu(L, U, b, O.TRANSPOSE))
+    routes = tuple(int(P.level_order(slot)[1][6]) for slot in range(4))
+    assert routes == SWEEP_ROUTES[name], (name, routes)
