@@ -181,10 +181,26 @@ using namespace ilupp;
 enum { KIND_LU = 0, KIND_LLT = 1, KIND_UTU = 2 };     // UTU (ILUC): two factors whose arrays both read as an upper CSR matrix, diagonal first
 enum { NNZ_GENERIC_LU = 0, NNZ_ILUT = 1, NNZ_LLT = 2 };
 
-struct ilupp_precond {
+namespace ilupp {
+// an object's queue: streams and events, recycled through a pool of their own (queue_take / queue_give)
+struct QueuePack {
+    hipStream_t stream = nullptr;
+    hipEvent_t ev[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};   // [4],[5]: around the factor kernel
+    hipEvent_t sev[2] = {nullptr, nullptr};           // ordering against the caller's stream
+    hipStream_t side = nullptr;                       // a second stream for work that runs NEXT to the analysis (grid.hip's proof)
+    hipEvent_t jev[2] = {nullptr, nullptr};           // fork / join of the side stream
+    int device = 0;
+};
+// what an object is, in its first three words whatever else it is made of: the CPU tests of the batched entries' refusals hand in zeroed
+// memory with n in its third word for a handle -- hence a base of its own, in front of the queue pack
+struct PrecondHead {
     int kind = KIND_LU;
     int nnz_mode = NNZ_GENERIC_LU;
     int32_t n = 0;
+};
+}  // namespace ilupp
+
+struct ilupp_precond : ilupp::PrecondHead, ilupp::QueuePack {
     bool input_csc = false;      // factors were computed on the row-major view M = A^T
     // LU: row-major factors of M.  LLT: Lc = the factor in its stored major order, `llt_diag_last`
     DevMat Lc, Uc;
@@ -218,12 +234,6 @@ struct ilupp_precond {
     int32_t *done = nullptr;     // n
     bool degenerate = false;     // a factor has a major slice without entries (NaN columns of an indefinite ICholT): guarded sweeps only
     int32_t *ctrl = nullptr;     // 16 ints: [0] err, [1] ilu0 ticket (+ its err in [2]) , [4],[5] solve tickets
-    hipStream_t stream = nullptr;
-    hipEvent_t ev[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};   // [4],[5]: around the factor kernel
-    hipEvent_t sev[2] = {nullptr, nullptr};           // ordering against the caller's stream
-    hipStream_t side = nullptr;                       // a second stream for work that runs NEXT to the analysis (grid.hip's proof)
-    hipEvent_t jev[2] = {nullptr, nullptr};           // fork / join of the side stream
-    int device = 0;
     ilupp_timings tm = {0, 0, 0, 0, 0, 0};
     bool apply_events_valid = false;
     int max_lanes = 65536;
@@ -249,12 +259,37 @@ struct ilupp_precond {
     bool batch_built = false;
     bool sweeps_ready = false;
 };
+// (two bases with members: not a standard-layout type, so the order of the bases is the ABI's, not the language's -- checked here)
+#pragma clang diagnostic push
+#pragma clang diagnostic ignored "-Winvalid-offsetof"
+static_assert(offsetof(ilupp_precond, kind) == 0 && offsetof(ilupp_precond, nnz_mode) == 4 && offsetof(ilupp_precond, n) == 8,
+              "kind, nnz_mode and n are a handle's first three words");
+#pragma clang diagnostic pop
 
 namespace {
 
-struct QueuePack { hipStream_t stream = nullptr; hipEvent_t ev[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr}; hipEvent_t sev[2] = {nullptr, nullptr};
-                   hipStream_t side = nullptr; hipEvent_t jev[2] = {nullptr, nullptr}; int device = 0; };
+// streams and events are recycled: creating them costs more than a small kernel
 struct QueuePool { std::mutex mu; std::vector<QueuePack> free_list; } g_queues;
+
+// a kept pack of `device` into *q (false: none is kept)
+bool queue_take(int device, QueuePack *q)
+{
+    std::lock_guard<std::mutex> lk(g_queues.mu);
+    for (size_t k = 0; k < g_queues.free_list.size(); ++k)
+        if (g_queues.free_list[k].device == device) {
+            *q = g_queues.free_list[k];
+            g_queues.free_list.erase(g_queues.free_list.begin() + (long)k);
+            return true;
+        }
+    return false;
+}
+
+// ... and a pack that nothing uses any more back into the pool
+void queue_give(const QueuePack &q)
+{
+    std::lock_guard<std::mutex> lk(g_queues.mu);
+    g_queues.free_list.push_back(q);
+}
 
 bool schedule_is_compact(const Schedule &s) { return s.B <= 32768 && s.nslots <= kGhostBase; }
 
@@ -276,15 +311,8 @@ void destroy_obj(ilupp_precond *p)
     for (void *q : {(void *)p->bxp, (void *)p->by, (void *)p->bcol, (void *)p->btk}) if (q) (void)pool_free(q);
     if (p->done) (void)pool_free(p->done);
     if (p->ctrl) (void)pool_free(p->ctrl);
-    // streams and events are recycled: creating them costs more than a small kernel (not a pack new_obj could not finish: jev[1] comes last)
-    if (p->stream && !p->borrowed_queue && p->jev[1]) {
-        std::lock_guard<std::mutex> lk(g_queues.mu);
-        QueuePack q; q.stream = p->stream; q.device = p->device;
-        for (int k = 0; k < 6; ++k) q.ev[k] = p->ev[k];
-        q.sev[0] = p->sev[0]; q.sev[1] = p->sev[1];
-        q.side = p->side; q.jev[0] = p->jev[0]; q.jev[1] = p->jev[1];
-        g_queues.free_list.push_back(q);
-    }
+    // (not a pack new_obj could not finish: jev[1] comes last)
+    if (p->stream && !p->borrowed_queue && p->jev[1]) queue_give(*p);
     delete p;
 }
 
@@ -305,19 +333,7 @@ ilupp_precond *new_obj(int32_t n)
     ilupp_precond *p = g.p;
     p->n = n;
     ILUPP_HIP(hipGetDevice(&p->device));
-    {
-        std::lock_guard<std::mutex> lk(g_queues.mu);
-        for (size_t k = 0; k < g_queues.free_list.size(); ++k)
-            if (g_queues.free_list[k].device == p->device) {
-                p->stream = g_queues.free_list[k].stream;
-                for (int e = 0; e < 6; ++e) p->ev[e] = g_queues.free_list[k].ev[e];
-                p->sev[0] = g_queues.free_list[k].sev[0]; p->sev[1] = g_queues.free_list[k].sev[1];
-                p->side = g_queues.free_list[k].side; p->jev[0] = g_queues.free_list[k].jev[0]; p->jev[1] = g_queues.free_list[k].jev[1];
-                g_queues.free_list.erase(g_queues.free_list.begin() + (long)k);
-                break;
-            }
-    }
-    if (!p->stream) {
+    if (!queue_take(p->device, p)) {
         ILUPP_HIP(hipStreamCreateWithFlags(&p->stream, hipStreamNonBlocking));
         for (auto &e : p->ev) ILUPP_HIP(hipEventCreate(&e));
         for (auto &e : p->sev) ILUPP_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
@@ -1181,6 +1197,76 @@ int ilu0_refactor_single(ilupp_precond *p, const double *d_data, const int32_t *
     } catch (const ilupp::HipError &e) { ilupp::d2h_cancel_all(); return ilupp::report(e); }        \
     catch (const std::bad_alloc &) { ilupp::d2h_cancel_all(); ilupp::set_error("out of host memory"); return ILUPP_ERR_MEMORY; }
 
+// ---- what an entry of each shape is made of ----------------------------------------------------------------------------------------
+namespace {
+
+// A construction entry on host arrays: the triple copied to device memory this call owns, then `make(A)`.  args_ok / null_msg: what
+// else of the entry's arguments must not be null, and how the refusal reads (the multilevel entries: "null argument").
+template <class Handle, class Make>
+int create_from_host(const double *data, const int32_t *indices, const int32_t *indptr, int32_t n, bool is_csr, Handle **out, Make &&make,
+                     bool args_ok = true, const char *null_msg = "null output")
+{
+    API_TRY_BUILD
+    if (!out || !args_ok) { set_error(null_msg); return ILUPP_ERR_INVALID; }
+    *out = nullptr;
+    MatGuard A;
+    OR_RETURN(upload(data, indices, indptr, n, is_csr, &A.m));
+    return make(A.m);
+    API_CATCH
+}
+
+// ... on a matrix that already lives in HBM: the caller's arrays, borrowed for the call; indptr[n] is read back
+template <class Handle, class Make>
+int create_from_device(const double *d_data, const int32_t *d_indices, const int32_t *d_indptr, int32_t n, bool is_csr, Handle **out, Make &&make,
+                       bool args_ok = true, const char *null_msg = "null output")
+{
+    API_TRY_BUILD
+    if (!out || !args_ok) { set_error(null_msg); return ILUPP_ERR_INVALID; }
+    *out = nullptr;
+    if (n <= 0 || !d_indptr) { set_error("matrix has size 0!"); return ILUPP_ERR_INVALID; }
+    DevMat A = borrow_csr(d_data, d_indices, d_indptr, n, read_device_nnz(d_indptr, n), is_csr);
+    return make(A);
+    API_CATCH
+}
+
+// the handle and the length of the vector an apply entry is given (n: the handle's, 0 for none)
+int vector_args(const void *handle, int64_t len, int32_t n)
+{
+    if (!handle) { set_error("null preconditioner"); return ILUPP_ERR_INVALID; }
+    if (len != n) { set_error("vector has wrong size for preconditioner!"); return ILUPP_ERR_WRONG_SIZE; }   // binding.cpp:241-242
+    return ILUPP_OK;
+}
+
+// the end of a device apply queued on q: wait for it and say how it went (finish), or hand the result over to the caller's stream
+template <class Finish>
+int finish_or_hand_over(int sync, const QueuePack &q, Finish &&finish)
+{
+    if (sync) return finish();
+    order_caller_after(q.stream, q.sev[1]);
+    return ILUPP_OK;
+}
+
+// The apply of a host vector: staged in *slot (n doubles, allocated on first use), sent on the object's stream, apply(staged vector),
+// finish(), and a blocking copy back -- from `result` where the apply leaves its result elsewhere than in the staged vector.
+template <class Apply, class Finish>
+int apply_staged(hipStream_t st, double **slot, int32_t n, double *x, Apply &&apply, Finish &&finish, const double *result = nullptr)
+{
+    if (!*slot) ILUPP_HIP(pool_malloc(slot, sizeof(double) * (size_t)n));
+    ILUPP_HIP(hipMemcpyAsync(*slot, x, sizeof(double) * (size_t)n, hipMemcpyHostToDevice, st));
+    OR_RETURN(apply(*slot));
+    OR_RETURN(finish());
+    ILUPP_HIP(hipMemcpy(x, result ? result : *slot, sizeof(double) * (size_t)n, hipMemcpyDeviceToHost));
+    return ILUPP_OK;
+}
+
+// an optional host array of a handle's copy-out entry
+void get_host(void *dst, const void *src, size_t bytes)
+{
+    if (dst && bytes) ILUPP_HIP(hipMemcpy(dst, src, bytes, hipMemcpyDeviceToHost));
+}
+
+}  // namespace
+
 extern "C" {
 
 int ilupp_hip_index_size(void) { return (int)sizeof(int32_t); }
@@ -1205,16 +1291,11 @@ int ilupp_hip_device_count(void)
 int ilupp_hip_ilu0_create(const double *data, const int32_t *indices, const int32_t *indptr,
                           int32_t n, int is_csr, ilupp_precond **out)
 {
-    API_TRY_BUILD
-    if (!out) { set_error("null output"); return ILUPP_ERR_INVALID; }
-    *out = nullptr;
-    MatGuard A;
-    const int rc = upload(data, indices, indptr, n, true, &A.m);
-    if (rc) return rc;
-    int32_t head[10];
-    host_head(indptr, indices, A.m.nnz, head);
-    return ilu0_create_common(A.m, is_csr, head, out);
-    API_CATCH
+    return create_from_host(data, indices, indptr, n, true, out, [&](DevMat &A) {
+        int32_t head[10];
+        host_head(indptr, indices, A.nnz, head);
+        return ilu0_create_common(A, is_csr, head, out);
+    });
 }
 
 int ilupp_hip_ilu0_create_device(const double *d_data, const int32_t *d_indices, const int32_t *d_indptr,
@@ -1338,53 +1419,31 @@ extern "C" {
 int ilupp_hip_ilut_create(const double *data, const int32_t *indices, const int32_t *indptr,
         int32_t n, int is_csr, int32_t max_fill_in, double threshold, ilupp_precond **out)
 {
-    API_TRY_BUILD
-    if (!out) { set_error("null output"); return ILUPP_ERR_INVALID; }
-    *out = nullptr;
-    MatGuard A;
-    const int rc = upload(data, indices, indptr, n, true, &A.m);
-    if (rc) return rc;
-    return ilut_create_common(A.m, n, is_csr, max_fill_in, threshold, out);
-    API_CATCH
+    return create_from_host(data, indices, indptr, n, true, out,
+                            [&](DevMat &A) { return ilut_create_common(A, n, is_csr, max_fill_in, threshold, out); });
 }
 
 /* the same on a matrix that already lives in HBM (borrowed for the call) */
 int ilupp_hip_ilut_create_device(const double *d_data, const int32_t *d_indices, const int32_t *d_indptr,
         int32_t n, int is_csr, int32_t max_fill_in, double threshold, ilupp_precond **out)
 {
-    API_TRY_BUILD
-    if (!out) { set_error("null output"); return ILUPP_ERR_INVALID; }
-    *out = nullptr;
-    if (n <= 0 || !d_indptr) { set_error("matrix has size 0!"); return ILUPP_ERR_INVALID; }
-    DevMat A = borrow_csr(d_data, d_indices, d_indptr, n, read_device_nnz(d_indptr, n), true);
-    return ilut_create_common(A, n, is_csr, max_fill_in, threshold, out);
-    API_CATCH
+    return create_from_device(d_data, d_indices, d_indptr, n, true, out,
+                              [&](DevMat &A) { return ilut_create_common(A, n, is_csr, max_fill_in, threshold, out); });
 }
 
 /* binding.cpp:329-340 ILUCPreconditioner(A, max_fill_in, threshold): Crout ILU (Li, Saad, Chow), ILUC.hpp:112-207 */
 int ilupp_hip_iluc_create(const double *data, const int32_t *indices, const int32_t *indptr,
         int32_t n, int is_csr, int32_t max_fill_in, double threshold, ilupp_precond **out)
 {
-    API_TRY_BUILD
-    if (!out) { set_error("null output"); return ILUPP_ERR_INVALID; }
-    *out = nullptr;
-    MatGuard A;
-    const int rc = upload(data, indices, indptr, n, true, &A.m);
-    if (rc) return rc;
-    return iluc_create_common(A.m, n, is_csr, max_fill_in, threshold, out);
-    API_CATCH
+    return create_from_host(data, indices, indptr, n, true, out,
+                            [&](DevMat &A) { return iluc_create_common(A, n, is_csr, max_fill_in, threshold, out); });
 }
 
 int ilupp_hip_iluc_create_device(const double *d_data, const int32_t *d_indices, const int32_t *d_indptr,
         int32_t n, int is_csr, int32_t max_fill_in, double threshold, ilupp_precond **out)
 {
-    API_TRY_BUILD
-    if (!out) { set_error("null output"); return ILUPP_ERR_INVALID; }
-    *out = nullptr;
-    if (n <= 0 || !d_indptr) { set_error("matrix has size 0!"); return ILUPP_ERR_INVALID; }
-    DevMat A = borrow_csr(d_data, d_indices, d_indptr, n, read_device_nnz(d_indptr, n), true);
-    return iluc_create_common(A, n, is_csr, max_fill_in, threshold, out);
-    API_CATCH
+    return create_from_device(d_data, d_indices, d_indptr, n, true, out,
+                              [&](DevMat &A) { return iluc_create_common(A, n, is_csr, max_fill_in, threshold, out); });
 }
 
 }  // extern "C"
@@ -1428,27 +1487,16 @@ extern "C" {
 int ilupp_hip_ichol0_create(const double *data, const int32_t *indices, const int32_t *indptr,
         int32_t n, int is_csr, ilupp_precond **out)
 {
-    API_TRY_BUILD
     (void)is_csr;     // IChol0 keeps idx <= major in either orientation and labels the result ROW (IChol.hpp:63-68)
-    if (!out) { set_error("null output"); return ILUPP_ERR_INVALID; }
-    *out = nullptr;
-    MatGuard A;
-    const int rc = upload(data, indices, indptr, n, true, &A.m);
-    if (rc) return rc;
-    return ichol0_create_common(A.m, n, out);
-    API_CATCH
+    return create_from_host(data, indices, indptr, n, true, out,
+                            [&](DevMat &A) { return ichol0_create_common(A, n, out); });
 }
 
 int ilupp_hip_ichol0_create_device(const double *d_data, const int32_t *d_indices, const int32_t *d_indptr,
         int32_t n, int is_csr, ilupp_precond **out)
 {
-    API_TRY_BUILD
-    if (!out) { set_error("null output"); return ILUPP_ERR_INVALID; }
-    *out = nullptr;
-    if (n <= 0 || !d_indptr) { set_error("matrix has size 0!"); return ILUPP_ERR_INVALID; }
-    DevMat A = borrow_csr(d_data, d_indices, d_indptr, n, read_device_nnz(d_indptr, n), true);
-    return ichol0_create_common(A, n, out);
-    API_CATCH
+    return create_from_device(d_data, d_indices, d_indptr, n, true, out,
+                              [&](DevMat &A) { return ichol0_create_common(A, n, out); });
 }
 }  // extern "C"
 
@@ -1592,17 +1640,12 @@ extern "C" {
 int ilupp_hip_icholt_create(const double *data, const int32_t *indices, const int32_t *indptr,
         int32_t n, int is_csr, int32_t add_fill_in, double threshold, ilupp_precond **out)
 {
-    API_TRY_BUILD
     (void)is_csr;     // ICholT keeps idx >= major in either orientation and labels the result COLUMN (IChol.hpp:158-164)
-    if (!out) { set_error("null output"); return ILUPP_ERR_INVALID; }
-    *out = nullptr;
-    MatGuard A;
-    const int rc = upload(data, indices, indptr, n, true, &A.m);
-    if (rc) return rc;
-    int32_t head[10];
-    host_head(indptr, indices, A.m.nnz, head);
-    return icholt_create_common(A.m, n, add_fill_in, threshold, out, head);
-    API_CATCH
+    return create_from_host(data, indices, indptr, n, true, out, [&](DevMat &A) {
+        int32_t head[10];
+        host_head(indptr, indices, A.nnz, head);
+        return icholt_create_common(A, n, add_fill_in, threshold, out, head);
+    });
 }
 
 int ilupp_hip_icholt_create_device(const double *d_data, const int32_t *d_indices, const int32_t *d_indptr,
@@ -1623,20 +1666,15 @@ void ilupp_hip_destroy(ilupp_precond *p) { destroy_obj(p); }
 int ilupp_hip_apply_device(ilupp_precond *p, double *d_x, int64_t len, int transpose, int sync)
 {
     API_TRY
-    if (!p) { set_error("null preconditioner"); return ILUPP_ERR_INVALID; }
-    if (len != p->n) { set_error("vector has wrong size for preconditioner!"); return ILUPP_ERR_WRONG_SIZE; }   // binding.cpp:241-242
-    int rc = apply_dev(p, d_x, transpose);
-    if (rc) return rc;
-    if (sync) return finish_apply(p);
-    order_caller_after(p->stream, p->sev[1]);
-    return ILUPP_OK;
+    OR_RETURN(vector_args(p, len, p ? p->n : 0));
+    OR_RETURN(apply_dev(p, d_x, transpose));
+    return finish_or_hand_over(sync, *p, [&] { return finish_apply(p); });
     API_CATCH
 }
 
 static int block_args(const ilupp_precond *p, int64_t n, int64_t k)
 {
-    if (!p) { set_error("null preconditioner"); return ILUPP_ERR_INVALID; }
-    if (n != p->n) { set_error("vector has wrong size for preconditioner!"); return ILUPP_ERR_WRONG_SIZE; }   // binding.cpp:241-242
+    OR_RETURN(vector_args(p, n, p ? p->n : 0));
     if (k < 0) { set_error("number of right-hand sides must not be negative"); return ILUPP_ERR_INVALID; }
     return ILUPP_OK;
 }
@@ -1646,11 +1684,8 @@ int ilupp_hip_apply_block_device(ilupp_precond *p, double *d_X, int64_t n, int64
     API_TRY
     int rc = block_args(p, n, k);
     if (rc || k == 0) return rc;
-    rc = apply_block_dev(p, d_X, k, transpose);
-    if (rc) return rc;
-    if (sync) return finish_apply(p);
-    order_caller_after(p->stream, p->sev[1]);
-    return ILUPP_OK;
+    OR_RETURN(apply_block_dev(p, d_X, k, transpose));
+    return finish_or_hand_over(sync, *p, [&] { return finish_apply(p); });
     API_CATCH
 }
 
@@ -1820,16 +1855,10 @@ const char *ilupp_hip_kernel_names(const ilupp_precond *p)
 static int apply_host(ilupp_precond *p, double *x, int64_t len, int transpose)
 {
     API_TRY
-    if (!p) { set_error("null preconditioner"); return ILUPP_ERR_INVALID; }
-    if (len != p->n) { set_error("vector has wrong size for preconditioner!"); return ILUPP_ERR_WRONG_SIZE; }
-    if (!p->xdev) ILUPP_HIP(pool_malloc(&p->xdev, sizeof(double) * (size_t)p->n));
-    ILUPP_HIP(hipMemcpyAsync(p->xdev, x, sizeof(double) * (size_t)p->n, hipMemcpyHostToDevice, p->stream));
-    int rc = apply_dev(p, p->xdev, transpose);
-    if (rc) return rc;
-    rc = finish_apply(p);
-    if (rc) return rc;
-    ILUPP_HIP(hipMemcpy(x, p->xdev, sizeof(double) * (size_t)p->n, hipMemcpyDeviceToHost));
-    return ILUPP_OK;
+    OR_RETURN(vector_args(p, len, p ? p->n : 0));
+    return apply_staged(p->stream, &p->xdev, p->n, x,
+                        [&](double *d) { return apply_dev(p, d, transpose); },
+                        [&] { return finish_apply(p); });
     API_CATCH
 }
 
@@ -2118,18 +2147,9 @@ int ml_create_common(const DevMat &A, const ilupp_ml_params *ip, ilupp_ml **out)
         if (k > 0) {
             p = new_obj(l.n);
             m->obj.push_back(p);
-            {   // its own queue back to the pool: the level works on the first level's
-                std::lock_guard<std::mutex> lk(g_queues.mu);
-                QueuePack q; q.stream = p->stream; q.device = p->device;
-                for (int e = 0; e < 6; ++e) q.ev[e] = p->ev[e];
-                q.sev[0] = p->sev[0]; q.sev[1] = p->sev[1];
-                q.side = p->side; q.jev[0] = p->jev[0]; q.jev[1] = p->jev[1];
-                g_queues.free_list.push_back(q);
-            }
+            queue_give(*p);                                    // its own queue back to the pool: the level works on the first level's
+            static_cast<QueuePack &>(*p) = *p0;
             p->side = nullptr; p->jev[0] = p->jev[1] = nullptr;
-            p->stream = st;
-            for (int e = 0; e < 6; ++e) p->ev[e] = p0->ev[e];
-            p->sev[0] = p0->sev[0]; p->sev[1] = p0->sev[1];
             p->borrowed_queue = true;
         }
         p->kind = KIND_UTU; p->nnz_mode = NNZ_GENERIC_LU; p->input_csc = false;
@@ -2241,14 +2261,8 @@ void ilupp_hip_ml_default_params(ilupp_ml_params *p)
 int ilupp_hip_ml_create(const double *data, const int32_t *indices, const int32_t *indptr, int32_t n, int is_csr, const ilupp_ml_params *params,
                         ilupp_ml **out)
 {
-    API_TRY_BUILD
-    if (!out || !params) { set_error("null argument"); return ILUPP_ERR_INVALID; }
-    *out = nullptr;
-    MatGuard A;
-    const int rc = upload(data, indices, indptr, n, is_csr != 0, &A.m);
-    if (rc) return rc;
-    return ml_create_common(A.m, params, out);
-    API_CATCH
+    return create_from_host(data, indices, indptr, n, is_csr != 0, out, [&](DevMat &A) { return ml_create_common(A, params, out); },
+                            params != nullptr, "null argument");
 }
 
 int ilupp_hip_ml_create_batch(int32_t count, const double *const *data, const int32_t *const *indices, const int32_t *const *indptr, const int32_t *n,
@@ -2274,12 +2288,8 @@ int ilupp_hip_ml_create_batch(int32_t count, const double *const *data, const in
 int ilupp_hip_ml_create_device(const double *d_data, const int32_t *d_indices, const int32_t *d_indptr, int32_t n, int is_csr,
                                const ilupp_ml_params *params, ilupp_ml **out)
 {
-    API_TRY_BUILD
-    if (!out || !params) { set_error("null argument"); return ILUPP_ERR_INVALID; }
-    *out = nullptr;
-    if (n <= 0 || !d_indptr) { set_error("matrix has size 0!"); return ILUPP_ERR_INVALID; }
-    return ml_create_common(borrow_csr(d_data, d_indices, d_indptr, n, read_device_nnz(d_indptr, n), is_csr != 0), params, out);
-    API_CATCH
+    return create_from_device(d_data, d_indices, d_indptr, n, is_csr != 0, out, [&](DevMat &A) { return ml_create_common(A, params, out); },
+                              params != nullptr, "null argument");
 }
 
 void ilupp_hip_ml_destroy(ilupp_ml *p)
@@ -2290,44 +2300,30 @@ void ilupp_hip_ml_destroy(ilupp_ml *p)
 int ilupp_hip_ml_apply_device(ilupp_ml *m, double *d_x, int64_t len, int transpose, int sync)
 {
     API_TRY
-    if (!m) { set_error("null preconditioner"); return ILUPP_ERR_INVALID; }
-    if (len != m->n) { set_error("vector has wrong size for preconditioner!"); return ILUPP_ERR_WRONG_SIZE; }
-    int rc = ml_apply_dev(m, d_x, transpose);
-    if (rc) return rc;
-    if (sync) return ml_finish_apply(m);
-    order_caller_after(m->obj[0]->stream, m->obj[0]->sev[1]);
-    return ILUPP_OK;
+    OR_RETURN(vector_args(m, len, m ? m->n : 0));
+    OR_RETURN(ml_apply_dev(m, d_x, transpose));
+    return finish_or_hand_over(sync, *m->obj[0], [&] { return ml_finish_apply(m); });
     API_CATCH
 }
 
 int ilupp_hip_ml_apply_part_device(ilupp_ml *m, double *d_x, int64_t len, int transpose, int left, int sync)
 {
     API_TRY
-    if (!m) { set_error("null preconditioner"); return ILUPP_ERR_INVALID; }
-    if (len != m->n) { set_error("vector has wrong size for preconditioner!"); return ILUPP_ERR_WRONG_SIZE; }
+    OR_RETURN(vector_args(m, len, m ? m->n : 0));
     // ID: the left part is the first pass (upwards through the levels), the right part the second; TRANSPOSE: right^T first, then left^T
     const int part = (left != 0) == (transpose == 0) ? 1 : 2;
-    int rc = ml_apply_dev(m, d_x, transpose, part);
-    if (rc) return rc;
-    if (sync) return ml_finish_apply(m);
-    order_caller_after(m->obj[0]->stream, m->obj[0]->sev[1]);
-    return ILUPP_OK;
+    OR_RETURN(ml_apply_dev(m, d_x, transpose, part));
+    return finish_or_hand_over(sync, *m->obj[0], [&] { return ml_finish_apply(m); });
     API_CATCH
 }
 
 int ilupp_hip_ml_apply(ilupp_ml *m, double *x, int64_t len, int transpose)
 {
     API_TRY
-    if (!m) { set_error("null preconditioner"); return ILUPP_ERR_INVALID; }
-    if (len != m->n) { set_error("vector has wrong size for preconditioner!"); return ILUPP_ERR_WRONG_SIZE; }
-    if (!m->xdev) ILUPP_HIP(pool_malloc(&m->xdev, sizeof(double) * (size_t)m->n));
-    ILUPP_HIP(hipMemcpyAsync(m->xdev, x, sizeof(double) * (size_t)m->n, hipMemcpyHostToDevice, m->obj[0]->stream));
-    int rc = ml_apply_dev(m, m->xdev, transpose);
-    if (rc) return rc;
-    rc = ml_finish_apply(m);
-    if (rc) return rc;
-    ILUPP_HIP(hipMemcpy(x, m->xdev, sizeof(double) * (size_t)m->n, hipMemcpyDeviceToHost));
-    return ILUPP_OK;
+    OR_RETURN(vector_args(m, len, m ? m->n : 0));
+    return apply_staged(m->obj[0]->stream, &m->xdev, m->n, x,
+                        [&](double *d) { return ml_apply_dev(m, d, transpose); },
+                        [&] { return ml_finish_apply(m); });
     API_CATCH
 }
 
@@ -2429,13 +2425,12 @@ int ilupp_hip_ml_level_copy(const ilupp_ml *m, int32_t level, double *l_data, in
     const MlLevelDev &l = m->dev[(size_t)level];
     ILUPP_HIP(stream_sync(p->stream));
     const size_t n = (size_t)p->n;
-    auto get = [](void *dst, const void *src, size_t bytes) { if (dst && bytes) ILUPP_HIP(hipMemcpy(dst, src, bytes, hipMemcpyDeviceToHost)); };
-    get(l_data, p->Lc.val, sizeof(double) * (size_t)p->Lc.nnz); get(l_indices, p->Lc.idx, sizeof(int32_t) * (size_t)p->Lc.nnz); get(l_indptr, p->Lc.ptr, sizeof(int32_t) * (n + 1));
-    get(u_data, p->Uc.val, sizeof(double) * (size_t)p->Uc.nnz); get(u_indices, p->Uc.idx, sizeof(int32_t) * (size_t)p->Uc.nnz); get(u_indptr, p->Uc.ptr, sizeof(int32_t) * (n + 1));
-    get(middle, l.D, sizeof(double) * n);
-    get(perm_rows, l.pr, sizeof(int32_t) * n); get(perm_cols, l.pc, sizeof(int32_t) * n);
-    get(inv_perm_rows, l.ipr, sizeof(int32_t) * n); get(inv_perm_cols, l.ipc, sizeof(int32_t) * n);
-    get(d_left, l.Dl, sizeof(double) * n); get(d_right, l.Dr, sizeof(double) * n);
+    get_host(l_data, p->Lc.val, sizeof(double) * (size_t)p->Lc.nnz); get_host(l_indices, p->Lc.idx, sizeof(int32_t) * (size_t)p->Lc.nnz); get_host(l_indptr, p->Lc.ptr, sizeof(int32_t) * (n + 1));
+    get_host(u_data, p->Uc.val, sizeof(double) * (size_t)p->Uc.nnz); get_host(u_indices, p->Uc.idx, sizeof(int32_t) * (size_t)p->Uc.nnz); get_host(u_indptr, p->Uc.ptr, sizeof(int32_t) * (n + 1));
+    get_host(middle, l.D, sizeof(double) * n);
+    get_host(perm_rows, l.pr, sizeof(int32_t) * n); get_host(perm_cols, l.pc, sizeof(int32_t) * n);
+    get_host(inv_perm_rows, l.ipr, sizeof(int32_t) * n); get_host(inv_perm_cols, l.ipc, sizeof(int32_t) * n);
+    get_host(d_left, l.Dl, sizeof(double) * n); get_host(d_right, l.Dr, sizeof(double) * n);
     return ILUPP_OK;
     API_CATCH
 }
@@ -2520,45 +2515,76 @@ void ilucp_destroy(ilupp_ilucp *m)
     delete m;
 }
 
-int ilucp_create_common(DevMat &A, int32_t n, int is_csr, int32_t max_fill_in, double threshold, double piv_tol, int32_t row_pos, double mem_factor,
-                        ilupp_ilucp **out)
+// What the constructions of the two kinds share: the handle and its object, perm and tmp, the event pair round `factor(m, p, st)`, the
+// matrix given back, `fill(m, p, st)` -- the ilupp_precond made from the factor call's result --, the times and the hand-over.
+template <class Factor, class Fill>
+int pivot_create_frame(DevMat &A, int32_t n, int is_csr, bool row_kind, ilupp_ilucp **out, Factor &&factor, Fill &&fill)
 {
     struct Guard { ilupp_ilucp *m; ~Guard() { if (m) ilucp_destroy(m); } } g{new ilupp_ilucp};
     ilupp_ilucp *m = g.m;
-    m->n = n; m->input_csr = is_csr != 0;
+    m->n = n; m->input_csr = is_csr != 0; m->row_kind = row_kind;
     m->obj = new_obj(n);
     ilupp_precond *p = m->obj;
     hipStream_t st = p->stream;
     ILUPP_HIP(pool_malloc(&m->perm, sizeof(int32_t) * (size_t)n));
     ILUPP_HIP(pool_malloc(&m->tmp, sizeof(double) * (size_t)n));
     ILUPP_HIP(hipEventRecord(p->ev[0], st));
-    MatGuard gl;
-    const int rc = ilucp_factor(st, A, max_fill_in, threshold, piv_tol, row_pos, mem_factor, &gl.m, &m->U, m->perm, &m->zero_pivots, &m->kernel_ms);
+    const int rc = factor(m, p, st);
     ILUPP_HIP(hipEventRecord(p->ev[1], st));
     A.release();
     if (rc) return rc;
-    // U' = U with its column indices in the permuted numbering (values and pointers shared in content, own arrays)
-    DevMat Up;
-    Up.n = n; Up.nnz = m->U.nnz; Up.is_csr = true; Up.owns = true;
-    PoolBlock b_inv;
-    ILUPP_HIP(b_inv.alloc(sizeof(int32_t) * (size_t)n));
-    hipLaunchKernelGGL(k_cp_invert, dim3((n + 255) / 256), dim3(256), 0, st, n, m->perm, b_inv.as<int32_t>());
-    ILUPP_HIP(pool_malloc(&Up.ptr, sizeof(int32_t) * (size_t)(n + 1)));
-    ILUPP_HIP(pool_malloc(&Up.idx, sizeof(int32_t) * (size_t)(Up.nnz > 0 ? Up.nnz : 1)));
-    ILUPP_HIP(pool_malloc(&Up.val, sizeof(double) * (size_t)(Up.nnz > 0 ? Up.nnz : 1)));
-    ILUPP_HIP(hipMemcpyAsync(Up.ptr, m->U.ptr, sizeof(int32_t) * (size_t)(n + 1), hipMemcpyDeviceToDevice, st));
-    if (Up.nnz > 0) {
-        ILUPP_HIP(hipMemcpyAsync(Up.val, m->U.val, sizeof(double) * (size_t)Up.nnz, hipMemcpyDeviceToDevice, st));
-        hipLaunchKernelGGL(k_cp_map_indices, dim3((unsigned)((Up.nnz + 255) / 256)), dim3(256), 0, st, Up.nnz, m->U.idx, b_inv.as<int32_t>(), Up.idx);
-    }
-    ILUPP_HIP(stream_sync(st));
-    p->kind = KIND_UTU; p->nnz_mode = NNZ_GENERIC_LU; p->input_csc = false;
-    p->Lc = gl.m; p->Uc = Up;
-    gl.m = DevMat();                                            // (the object owns the arrays now)
-    utu_analyse(p);
+    fill(m, p, st);
     finish_timing(p, m->kernel_ms);
     *out = m;
     g.m = nullptr;
+    return ILUPP_OK;
+}
+
+int ilucp_create_common(DevMat &A, int32_t n, int is_csr, int32_t max_fill_in, double threshold, double piv_tol, int32_t row_pos, double mem_factor,
+                        ilupp_ilucp **out)
+{
+    MatGuard gl;
+    return pivot_create_frame(A, n, is_csr, false, out,
+        [&](ilupp_ilucp *m, ilupp_precond *, hipStream_t st) {
+            return ilucp_factor(st, A, max_fill_in, threshold, piv_tol, row_pos, mem_factor, &gl.m, &m->U, m->perm, &m->zero_pivots, &m->kernel_ms);
+        },
+        [&](ilupp_ilucp *m, ilupp_precond *p, hipStream_t st) {
+            // U' = U with its column indices in the permuted numbering (values and pointers shared in content, own arrays)
+            DevMat Up;
+            Up.n = n; Up.nnz = m->U.nnz; Up.is_csr = true; Up.owns = true;
+            PoolBlock b_inv;
+            ILUPP_HIP(b_inv.alloc(sizeof(int32_t) * (size_t)n));
+            hipLaunchKernelGGL(k_cp_invert, dim3((n + 255) / 256), dim3(256), 0, st, n, m->perm, b_inv.as<int32_t>());
+            ILUPP_HIP(pool_malloc(&Up.ptr, sizeof(int32_t) * (size_t)(n + 1)));
+            ILUPP_HIP(pool_malloc(&Up.idx, sizeof(int32_t) * (size_t)(Up.nnz > 0 ? Up.nnz : 1)));
+            ILUPP_HIP(pool_malloc(&Up.val, sizeof(double) * (size_t)(Up.nnz > 0 ? Up.nnz : 1)));
+            ILUPP_HIP(hipMemcpyAsync(Up.ptr, m->U.ptr, sizeof(int32_t) * (size_t)(n + 1), hipMemcpyDeviceToDevice, st));
+            if (Up.nnz > 0) {
+                ILUPP_HIP(hipMemcpyAsync(Up.val, m->U.val, sizeof(double) * (size_t)Up.nnz, hipMemcpyDeviceToDevice, st));
+                hipLaunchKernelGGL(k_cp_map_indices, dim3((unsigned)((Up.nnz + 255) / 256)), dim3(256), 0, st, Up.nnz, m->U.idx, b_inv.as<int32_t>(), Up.idx);
+            }
+            ILUPP_HIP(stream_sync(st));
+            p->kind = KIND_UTU; p->nnz_mode = NNZ_GENERIC_LU; p->input_csc = false;
+            p->Lc = gl.m; p->Uc = Up;
+            gl.m = DevMat();                                            // (the object owns the arrays now)
+            utu_analyse(p);
+        });
+}
+
+// The pivoted solve of x (device, n doubles; overwritten), on the member's own stream: the plain solve then the scatter through perm, or
+// the gather then the transposed solve.  The result is in m->tmp.
+int pivot_solve(ilupp_ilucp *m, double *x, int transpose)
+{
+    const int32_t n = m->n;
+    ilupp_precond *p = m->obj;
+    hipStream_t st = p->stream;
+    if (pivot_plain_first(m, transpose)) {
+        OR_RETURN(apply_dev(p, x, 0));
+        hipLaunchKernelGGL(k_cp_scatter, dim3((n + 255) / 256), dim3(256), 0, st, n, x, m->perm, m->tmp);
+    } else {
+        hipLaunchKernelGGL(k_cp_gather, dim3((n + 255) / 256), dim3(256), 0, st, n, x, m->perm, m->tmp);
+        OR_RETURN(apply_dev(p, m->tmp, 1));
+    }
     return ILUPP_OK;
 }
 
@@ -2569,14 +2595,8 @@ extern "C" {
 int ilupp_hip_ilucp_create(const double *data, const int32_t *indices, const int32_t *indptr, int32_t n, int is_csr, int32_t max_fill_in,
                            double threshold, double piv_tol, int32_t row_pos, double mem_factor, ilupp_ilucp **out)
 {
-    API_TRY_BUILD
-    if (!out) { set_error("null output"); return ILUPP_ERR_INVALID; }
-    *out = nullptr;
-    MatGuard A;
-    const int rc = upload(data, indices, indptr, n, true, &A.m);
-    if (rc) return rc;
-    return ilucp_create_common(A.m, n, is_csr, max_fill_in, threshold, piv_tol, row_pos, mem_factor, out);
-    API_CATCH
+    return create_from_host(data, indices, indptr, n, true, out,
+                            [&](DevMat &A) { return ilucp_create_common(A, n, is_csr, max_fill_in, threshold, piv_tol, row_pos, mem_factor, out); });
 }
 
 void ilupp_hip_ilucp_destroy(ilupp_ilucp *m) { ilucp_destroy(m); }
@@ -2584,32 +2604,11 @@ void ilupp_hip_ilucp_destroy(ilupp_ilucp *m) { ilucp_destroy(m); }
 int ilupp_hip_ilucp_apply(ilupp_ilucp *m, double *x, int64_t len, int transpose)
 {
     API_TRY
-    if (!m) { set_error("null preconditioner"); return ILUPP_ERR_INVALID; }
-    if (len != m->n) { set_error("vector has wrong size for preconditioner!"); return ILUPP_ERR_WRONG_SIZE; }
-    const int32_t n = m->n;
-    ilupp_precond *p = m->obj;
-    hipStream_t st = p->stream;
+    OR_RETURN(vector_args(m, len, m ? m->n : 0));
     after_batch(m);
-    if (!m->xdev) ILUPP_HIP(pool_malloc(&m->xdev, sizeof(double) * (size_t)n));
-    ILUPP_HIP(hipMemcpyAsync(m->xdev, x, sizeof(double) * (size_t)n, hipMemcpyHostToDevice, st));
-    const bool plain_first = pivot_plain_first(m, transpose);
-    int rc;
-    if (plain_first) {
-        rc = apply_dev(p, m->xdev, 0);
-        if (rc) return rc;
-        hipLaunchKernelGGL(k_cp_scatter, dim3((n + 255) / 256), dim3(256), 0, st, n, m->xdev, m->perm, m->tmp);
-        rc = finish_apply(p);
-        if (rc) return rc;
-        ILUPP_HIP(hipMemcpy(x, m->tmp, sizeof(double) * (size_t)n, hipMemcpyDeviceToHost));
-    } else {
-        hipLaunchKernelGGL(k_cp_gather, dim3((n + 255) / 256), dim3(256), 0, st, n, m->xdev, m->perm, m->tmp);
-        rc = apply_dev(p, m->tmp, 1);
-        if (rc) return rc;
-        rc = finish_apply(p);
-        if (rc) return rc;
-        ILUPP_HIP(hipMemcpy(x, m->tmp, sizeof(double) * (size_t)n, hipMemcpyDeviceToHost));
-    }
-    return ILUPP_OK;
+    return apply_staged(m->obj->stream, &m->xdev, m->n, x,
+                        [&](double *d) { return pivot_solve(m, d, transpose); },
+                        [&] { return finish_apply(m->obj); }, m->tmp);
     API_CATCH
 }
 
@@ -2635,10 +2634,9 @@ int ilupp_hip_ilucp_copy(const ilupp_ilucp *m, double *l_data, int32_t *l_indice
     const ilupp_precond *p = m->obj;
     ILUPP_HIP(stream_sync(p->stream));
     const size_t n = (size_t)m->n;
-    auto get = [](void *dst, const void *src, size_t bytes) { if (dst && bytes) ILUPP_HIP(hipMemcpy(dst, src, bytes, hipMemcpyDeviceToHost)); };
-    get(l_data, p->Lc.val, sizeof(double) * (size_t)p->Lc.nnz); get(l_indices, p->Lc.idx, sizeof(int32_t) * (size_t)p->Lc.nnz); get(l_indptr, p->Lc.ptr, sizeof(int32_t) * (n + 1));
-    get(u_data, m->U.val, sizeof(double) * (size_t)m->U.nnz); get(u_indices, m->U.idx, sizeof(int32_t) * (size_t)m->U.nnz); get(u_indptr, m->U.ptr, sizeof(int32_t) * (n + 1));
-    get(perm, m->perm, sizeof(int32_t) * n);
+    get_host(l_data, p->Lc.val, sizeof(double) * (size_t)p->Lc.nnz); get_host(l_indices, p->Lc.idx, sizeof(int32_t) * (size_t)p->Lc.nnz); get_host(l_indptr, p->Lc.ptr, sizeof(int32_t) * (n + 1));
+    get_host(u_data, m->U.val, sizeof(double) * (size_t)m->U.nnz); get_host(u_indices, m->U.idx, sizeof(int32_t) * (size_t)m->U.nnz); get_host(u_indptr, m->U.ptr, sizeof(int32_t) * (n + 1));
+    get_host(perm, m->perm, sizeof(int32_t) * n);
     return ILUPP_OK;
     API_CATCH
 }
@@ -2650,26 +2648,15 @@ namespace {
 int ilutp_create_common(DevMat &A, int32_t n, int is_csr, int32_t max_fill_in, double threshold, double piv_tol, int32_t row_pos, double mem_factor,
                         ilupp_ilucp **out)
 {
-    struct Guard { ilupp_ilucp *m; ~Guard() { if (m) ilucp_destroy(m); } } g{new ilupp_ilucp};
-    ilupp_ilucp *m = g.m;
-    m->n = n; m->input_csr = is_csr != 0; m->row_kind = true;
-    m->obj = new_obj(n);
-    ilupp_precond *p = m->obj;
-    hipStream_t st = p->stream;
-    ILUPP_HIP(pool_malloc(&m->perm, sizeof(int32_t) * (size_t)n));
-    ILUPP_HIP(pool_malloc(&m->tmp, sizeof(double) * (size_t)n));
-    ILUPP_HIP(hipEventRecord(p->ev[0], st));
-    const int rc = ilutp_factor(st, A, max_fill_in, threshold, piv_tol, row_pos, mem_factor, &p->Lc, &p->Uc, &m->U, m->perm, &m->zero_pivots, &m->kernel_ms);
-    ILUPP_HIP(hipEventRecord(p->ev[1], st));
-    A.release();
-    if (rc) return rc;
-    // an object of the ILUT kind: L by rows with its 1 last, U (permuted numbering) by rows with the pivot first
-    p->kind = KIND_LU; p->nnz_mode = NNZ_ILUT; p->input_csc = false;
-    p->compact = sweep_tables(st, p, {&p->Lc, true, &p->sL, &p->dL}, {&p->Uc, false, &p->sU, &p->dU}, true, &p->max_row_len);
-    finish_timing(p, m->kernel_ms);
-    *out = m;
-    g.m = nullptr;
-    return ILUPP_OK;
+    return pivot_create_frame(A, n, is_csr, true, out,
+        [&](ilupp_ilucp *m, ilupp_precond *p, hipStream_t st) {
+            return ilutp_factor(st, A, max_fill_in, threshold, piv_tol, row_pos, mem_factor, &p->Lc, &p->Uc, &m->U, m->perm, &m->zero_pivots, &m->kernel_ms);
+        },
+        [&](ilupp_ilucp *, ilupp_precond *p, hipStream_t st) {
+            // an object of the ILUT kind: L by rows with its 1 last, U (permuted numbering) by rows with the pivot first
+            p->kind = KIND_LU; p->nnz_mode = NNZ_ILUT; p->input_csc = false;
+            p->compact = sweep_tables(st, p, {&p->Lc, true, &p->sL, &p->dL}, {&p->Uc, false, &p->sU, &p->dU}, true, &p->max_row_len);
+        });
 }
 
 }  // namespace
@@ -2677,14 +2664,8 @@ int ilutp_create_common(DevMat &A, int32_t n, int is_csr, int32_t max_fill_in, d
 extern "C" int ilupp_hip_ilutp_create(const double *data, const int32_t *indices, const int32_t *indptr, int32_t n, int is_csr, int32_t max_fill_in,
                                       double threshold, double piv_tol, int32_t row_pos, double mem_factor, ilupp_ilucp **out)
 {
-    API_TRY_BUILD
-    if (!out) { set_error("null output"); return ILUPP_ERR_INVALID; }
-    *out = nullptr;
-    MatGuard A;
-    const int rc = upload(data, indices, indptr, n, true, &A.m);
-    if (rc) return rc;
-    return ilutp_create_common(A.m, n, is_csr, max_fill_in, threshold, piv_tol, row_pos, mem_factor, out);
-    API_CATCH
+    return create_from_host(data, indices, indptr, n, true, out,
+                            [&](DevMat &A) { return ilutp_create_common(A, n, is_csr, max_fill_in, threshold, piv_tol, row_pos, mem_factor, out); });
 }
 
 // ---- many matrices at once: the chains of the members side by side, one workgroup each (k_ilucp_batch / k_ilutp_batch) ----
@@ -2756,17 +2737,10 @@ namespace {
 int pivot_apply_dev(ilupp_ilucp *m, double *x, int transpose)
 {
     const int32_t n = m->n;
-    ilupp_precond *p = m->obj;
-    hipStream_t st = p->stream;
+    hipStream_t st = m->obj->stream;
     after_batch(m);
-    order_after_caller(st, p->sev[0]);
-    if (pivot_plain_first(m, transpose)) {
-        OR_RETURN(apply_dev(p, x, 0));
-        hipLaunchKernelGGL(k_cp_scatter, dim3((n + 255) / 256), dim3(256), 0, st, n, x, m->perm, m->tmp);
-    } else {
-        hipLaunchKernelGGL(k_cp_gather, dim3((n + 255) / 256), dim3(256), 0, st, n, x, m->perm, m->tmp);
-        OR_RETURN(apply_dev(p, m->tmp, 1));
-    }
+    order_after_caller(st, m->obj->sev[0]);
+    OR_RETURN(pivot_solve(m, x, transpose));
     ILUPP_HIP(hipGetLastError());
     ILUPP_HIP(hipMemcpyAsync(x, m->tmp, sizeof(double) * (size_t)n, hipMemcpyDeviceToDevice, st));
     return ILUPP_OK;
@@ -3234,9 +3208,7 @@ int ilupp_hip_ilucp_apply_device(ilupp_ilucp *m, double *d_x, int64_t len, int t
     if (len != m->n) { set_error("vector has wrong size for preconditioner!"); return ILUPP_ERR_WRONG_SIZE; }
     const int rc = pivot_apply_dev(m, d_x, transpose);
     if (rc) return rc;
-    if (sync) return finish_apply(m->obj);
-    order_caller_after(m->obj->stream, m->obj->sev[1]);
-    return ILUPP_OK;
+    return finish_or_hand_over(sync, *m->obj, [&] { return finish_apply(m->obj); });
     API_CATCH
 }
 
