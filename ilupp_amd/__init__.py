@@ -327,6 +327,18 @@ class IChol0Preconditioner(_BlockApply, _HipPreconditioner):
     def __init__(self, A):
         super().__init__(A, lambda m: _backend.IChol0Preconditioner(*m))
 
+    @classmethod
+    def batch(cls, matrices):
+        """One preconditioner per matrix of `matrices` (all CSR or all CSC), built by ONE native call: the objects
+        ``[IChol0Preconditioner(A) for A in matrices]`` gives -- factor, ``total_nnz`` and every apply bit for bit -- from two kernel
+        launches of one workgroup per matrix around one read-back (``ilupp_hip_ichol0_create_batch``), as
+        :meth:`ILU0Preconditioner.batch` builds ILU(0) objects.  A matrix above the launches' caps (n above
+        ``_native.ichol0_refactor_batch_max_n()``, a row of L of more than 31 entries) and a batch of one are built by the single
+        constructor inside the same call.  The members go into ``ilupp_amd.device.apply_batch_`` / ``cg_batch`` /
+        ``ichol0_refactor_batch_`` as they are.  A matrix that fails (no diagonal entry in a row) raises what the constructor raises,
+        named by its number; no object is returned then.  TypeError for matrices of both formats; an empty list gives ``[]``."""
+        return _batch(cls, matrices, lambda ms, is_csr: _native.IChol0Preconditioner_batch(ms, is_csr))
+
 
 class ICholTPreconditioner(_BlockApply, _HipPreconditioner):
     """Incomplete Cholesky with `add_fill_in` extra entries per column and relative drop `threshold`."""

@@ -194,6 +194,12 @@ def lib():
                                               ctypes.POINTER(_VP), _I32P, _I32P]
     L.ilupp_hip_ilu0_create_batch_device.argtypes = [ctypes.c_int32, ctypes.POINTER(_VP), ctypes.POINTER(_VP), ctypes.POINTER(_VP), _I32P,
                                                      ctypes.POINTER(ctypes.c_int64), ctypes.c_int, ctypes.POINTER(_VP), _I32P, _I32P]
+    L.ilupp_hip_ichol0_refactor_device.argtypes = [_VP, _VP, _VP, _VP]
+    L.ilupp_hip_ichol0_refactor_batch_device.argtypes = L.ilupp_hip_ilu0_refactor_batch_device.argtypes
+    L.ilupp_hip_ichol0_refactor_batch_max_n.argtypes = []
+    L.ilupp_hip_ichol0_refactor_batch_max_n.restype = ctypes.c_int64
+    L.ilupp_hip_ichol0_create_batch.argtypes = L.ilupp_hip_ilu0_create_batch.argtypes
+    L.ilupp_hip_ichol0_create_batch_device.argtypes = L.ilupp_hip_ilu0_create_batch_device.argtypes
     L.ilupp_hip_ilucp_total_nnz.argtypes = [_VP]
     L.ilupp_hip_ilucp_total_nnz.restype = ctypes.c_int64
     L.ilupp_hip_ilucp_zero_pivots.argtypes = [_VP]
@@ -235,6 +241,8 @@ ABI_SYMBOLS = [
     "ilupp_hip_bicgstab_batch_device", "ilupp_hip_bicgstab_batch_max_n",
     "ilupp_hip_ilu0_refactor_batch_device", "ilupp_hip_ilu0_refactor_batch_max_n",
     "ilupp_hip_ilu0_create_batch", "ilupp_hip_ilu0_create_batch_device",
+    "ilupp_hip_ichol0_refactor_device", "ilupp_hip_ichol0_refactor_batch_device", "ilupp_hip_ichol0_refactor_batch_max_n",
+    "ilupp_hip_ichol0_create_batch", "ilupp_hip_ichol0_create_batch_device",
     "ilupp_hip_apply_block", "ilupp_hip_apply_block_device", "ilupp_hip_block_path",
     "ilupp_hip_spmm_device", "ilupp_hip_block_dot_device", "ilupp_hip_cg_block_update_device", "ilupp_hip_bicgstab_block_update_device",
 ]
@@ -366,6 +374,12 @@ class Preconditioner:
 
     def sync(self):
         rc = lib().ilupp_hip_sync(self._h)
+        if rc:
+            _raise(rc)
+
+    def ichol0_refactor_device(self, d_data, d_indices, d_indptr):
+        """the numeric IChol(0) re-factorisation of this object on a matrix with the analysed pattern (ilupp_hip_ichol0_refactor_device)"""
+        rc = lib().ilupp_hip_ichol0_refactor_device(self._h, d_data, d_indices, d_indptr)
         if rc:
             _raise(rc)
 
@@ -665,11 +679,11 @@ def _ilu0_batch_result(rc, cnt, out, status):
     return [Preconditioner(_VP(out[k])) for k in range(cnt)]
 
 
-def ILU0Preconditioner_batch(matrices, is_csr, routes=None):
+def ILU0Preconditioner_batch(matrices, is_csr, routes=None, entry="ilupp_hip_ilu0_create_batch"):
     """one ILU(0) preconditioner per matrix of `matrices` (a list of (data, indices, indptr)), built by two launches of one workgroup per
     matrix around one read-back (ilupp_hip_ilu0_create_batch): the factors and applies of the objects the constructor gives one at a
     time, bit for bit.  `routes`, when a list, receives every member's route (0 = the launches, 1 = the single constructor inside the
-    same call)"""
+    same call).  `entry`: the C entry (IChol0Preconditioner_batch names its own)"""
     cnt = len(matrices)
     if cnt == 0:
         return []
@@ -682,13 +696,13 @@ def ILU0Preconditioner_batch(matrices, is_csr, routes=None):
         ns.append(args[3])
     N = (ctypes.c_int32 * cnt)(*ns)
     out, status, route = (_VP * cnt)(), (ctypes.c_int32 * cnt)(), (ctypes.c_int32 * cnt)()
-    rc = lib().ilupp_hip_ilu0_create_batch(cnt, D, I, P, N, 1 if is_csr else 0, out, status, route)
+    rc = getattr(lib(), entry)(cnt, D, I, P, N, 1 if is_csr else 0, out, status, route)
     if routes is not None:
         routes[:] = list(route)
     return _ilu0_batch_result(rc, cnt, out, status)
 
 
-def ILU0Preconditioner_batch_device(matrices, is_csr, routes=None):
+def ILU0Preconditioner_batch_device(matrices, is_csr, routes=None, entry="ilupp_hip_ilu0_create_batch_device"):
     """the same for matrices already resident in HBM: `matrices` is a list of (data_ptr, indices_ptr, indptr_ptr, n, nnz) of device CSR
     arrays (ilupp_hip_ilu0_create_batch_device).  Ordered on the caller's stream (set_caller_stream); the call returns when every member
     is built"""
@@ -700,10 +714,22 @@ def ILU0Preconditioner_batch_device(matrices, is_csr, routes=None):
     for k, (d, i, p, n, nnz) in enumerate(matrices):
         D[k], I[k], P[k], N[k], NNZ[k] = d, i, p, int(n), int(nnz)
     out, status, route = (_VP * cnt)(), (ctypes.c_int32 * cnt)(), (ctypes.c_int32 * cnt)()
-    rc = lib().ilupp_hip_ilu0_create_batch_device(cnt, D, I, P, N, NNZ, 1 if is_csr else 0, out, status, route)
+    rc = getattr(lib(), entry)(cnt, D, I, P, N, NNZ, 1 if is_csr else 0, out, status, route)
     if routes is not None:
         routes[:] = list(route)
     return _ilu0_batch_result(rc, cnt, out, status)
+
+
+def IChol0Preconditioner_batch(matrices, is_csr, routes=None):
+    """one IChol(0) preconditioner per matrix of `matrices` (a list of (data, indices, indptr)), built as ILU0Preconditioner_batch builds
+    ILU(0) objects (ilupp_hip_ichol0_create_batch): the factor and applies of the objects the constructor gives one at a time, bit for
+    bit.  is_csr is ignored, as by the constructor"""
+    return ILU0Preconditioner_batch(matrices, is_csr, routes, entry="ilupp_hip_ichol0_create_batch")
+
+
+def IChol0Preconditioner_batch_device(matrices, is_csr, routes=None):
+    """the same for matrices already resident in HBM, as ILU0Preconditioner_batch_device (ilupp_hip_ichol0_create_batch_device)"""
+    return ILU0Preconditioner_batch_device(matrices, is_csr, routes, entry="ilupp_hip_ichol0_create_batch_device")
 
 
 def _create_device(fn, d_data, d_indices, d_indptr, n, is_csr, *extra):
@@ -1106,7 +1132,7 @@ def cg_batch_device(members, ns, matrices, b_ptr, x0_ptr, x_ptr, offsets, work_p
                         work_ptr, work_doubles, maxiter, rtol, check_every, iterations_ptr, flags_ptr, rr_ptr, bnorm_ptr, sync)
 
 
-def ilu0_refactor_batch_device(members, matrices, status_ptr, sync=True):
+def ilu0_refactor_batch_device(members, matrices, status_ptr, sync=True, entry="ilupp_hip_ilu0_refactor_batch_device"):
     """the numeric re-factorisation of `members` (Preconditioner objects of the ILU0 class, each at most once) with ONE launch for all
     members that fit (ilupp_hip_ilu0_refactor_batch_device): `matrices` is a list of (data_ptr, indices_ptr, indptr_ptr, nnz) of device CSR
     arrays with the members' patterns and the new values, `status_ptr` a device array of one int32 per member (0 = re-factorised, 1 = the
@@ -1120,7 +1146,7 @@ def ilu0_refactor_batch_device(members, matrices, status_ptr, sync=True):
         return []
     H = _plain_handles(members)
     route = (ctypes.c_int32 * cnt)()
-    rc = lib().ilupp_hip_ilu0_refactor_batch_device(cnt, H, *_matrix_arrays(matrices), status_ptr, 1 if sync else 0, route)
+    rc = getattr(lib(), entry)(cnt, H, *_matrix_arrays(matrices), status_ptr, 1 if sync else 0, route)
     if rc:
         _raise(rc)
     return list(route)
@@ -1129,6 +1155,18 @@ def ilu0_refactor_batch_device(members, matrices, status_ptr, sync=True):
 def ilu0_refactor_batch_max_n():
     """the largest n a member may have to take ilu0_refactor_batch_device's launch on the current device (ILUPP_BATCH_APPLY_MAX_N applied)"""
     return _batch_max_n("ilupp_hip_ilu0_refactor_batch_max_n")
+
+
+def ichol0_refactor_batch_device(members, matrices, status_ptr, sync=True):
+    """the numeric re-factorisation of `members` (Preconditioner objects of the IChol0 class, each at most once) with ONE launch for all
+    members that fit (ilupp_hip_ichol0_refactor_batch_device); arguments, status words and routes as ilu0_refactor_batch_device's (route 2:
+    an object whose constructor ran the static form).  The launch also rewrites a member's transposed copy of the factor when it has one"""
+    return ilu0_refactor_batch_device(members, matrices, status_ptr, sync, entry="ilupp_hip_ichol0_refactor_batch_device")
+
+
+def ichol0_refactor_batch_max_n():
+    """the largest n a member may have to take ichol0_refactor_batch_device's launch on the current device (ILUPP_BATCH_APPLY_MAX_N applied)"""
+    return _batch_max_n("ilupp_hip_ichol0_refactor_batch_max_n")
 
 
 def cg_batch_max_n():

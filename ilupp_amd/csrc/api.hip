@@ -225,8 +225,8 @@ struct ilupp_precond : ilupp::PrecondHead, ilupp::QueuePack {
     int8_t last_route[4] = {0, 0, 0, 0};   // per slot, the kernel family its last sweep ran on (SweepRoute; diagnostics)
     FactorLM flm;                    // level-major factor kernel state (then Lc.val / Uc.val are filled on demand)
     bool csr_vals = true;            // Lc.val / Uc.val hold the factor values
-    int64_t nnzA = 0;                // stored entries of the factored matrix (same pattern on a numeric re-factorisation)
-    int32_t max_row_len = 0;
+    int64_t nnzA = 0;                // stored entries of the factored matrix (same pattern on a numeric re-factorisation; ILU(0), IChol(0))
+    int32_t max_row_len = 0;         // longest row of the factored matrix (LU objects) / of L (IChol(0)): what the batched launches route by
     int32_t max_len_T = 0;       // longest major slice of the transposed storages
     double *work = nullptr;      // n, all-sentinel between applies of the record-decoding / CSR sweeps (filled when the first of them runs)
     bool work_clean = false;
@@ -256,6 +256,7 @@ struct ilupp_precond : ilupp::PrecondHead, ilupp::QueuePack {
     // ILU(0) built by the launches of a batched first construction (ilupp_hip_ilu0_create_batch*): Lc, Uc, nnzA and max_row_len, and nothing of
     // the single paths' analysis -- no sA / sU, no program, no packed sweeps, never the static form.  The batched launches take it as it
     // is; the single sweeps' tables (sL, sU, dL, dU) are built from the factors' own patterns on first use (ensure_sweep_tables)
+    // IChol(0) built by ilupp_hip_ichol0_create_batch*: Lc, nnzA and max_row_len (the longest row of L) the same way; sL / dL on first use
     bool batch_built = false;
     bool sweeps_ready = false;
 };
@@ -730,7 +731,9 @@ void ensure_sweep_tables(ilupp_precond *p)
 {
     if (!p->batch_built || p->sweeps_ready) return;
     int32_t longest = 0;
-    p->compact = sweep_tables(p->stream, p, {&p->Lc, true, &p->sL, &p->dL}, {&p->Uc, false, &p->sU, &p->dU}, true, &longest);
+    // (a batch-built IChol(0) object: L forward, as ichol0_create_common builds it; the backward sweep's tables come with LcT)
+    if (p->kind == KIND_LLT) p->compact = sweep_tables(p->stream, p, {&p->Lc, true, &p->sL, &p->dL}, {}, true, &longest);
+    else p->compact = sweep_tables(p->stream, p, {&p->Lc, true, &p->sL, &p->dL}, {&p->Uc, false, &p->sU, &p->dU}, true, &longest);
     p->sweeps_ready = true;
 }
 
@@ -1158,6 +1161,55 @@ void drop_old_value_copies(ilupp_precond *p)
     }
 }
 
+// an IChol(0) object's copies of the factor's values beside Lc and LcT: the packed sweeps of the two (level-major or the static pair)
+// and the level-ordered copies; each is built again on its first use.  The caller has waited for whatever still reads them.
+void drop_llt_sweep_copies(ilupp_precond *p)
+{
+    p->apply_events_valid = false;
+    for (auto &l : p->lvl) l.release();
+    p->pkL.release(); p->pkLT.release();
+    p->pack_tried[0] = p->pack_tried[3] = false; p->pair_tried = false;
+}
+
+// an IChol(0) object: LL^T with the factor row-major and the diagonal last (ICholT keeps its factor column-major)
+bool is_ichol0_object(const ilupp_precond *p)
+{
+    return p && p->kind == KIND_LLT && p->nnz_mode == NNZ_LLT && p->llt_diag_last && (p->sL.nb > 0 || p->batch_built);
+}
+
+// what ilupp_hip_ichol0_refactor_device does, under the construction lock its caller holds: the pattern proved and Lc's values refilled with
+// A's lower triangle by two launches around one read-back, then the constructor's numeric path in place on Lc
+int ichol0_refactor_single(ilupp_precond *p, const double *d_data, const int32_t *d_indices, const int32_t *d_indptr)
+{
+    if (!is_ichol0_object(p)) { set_error("not an IChol(0) object"); return ILUPP_ERR_INVALID; }
+    order_after_caller(p->stream, p->sev[0]);
+    if (p->batch_ev) { ILUPP_HIP(hipStreamWaitEvent(p->stream, p->batch_ev, 0)); p->batch_ev = nullptr; }      // (a batched launch still reads the old factor)
+    if (p->batch_built) return refactor_in_launch(p, d_data, d_indices, d_indptr);
+    hipStream_t st = p->stream;
+    {
+        int32_t *d_bad = p->ctrl + 2, bad = 1;       // (ctrl[2]: a word no sweep of such an object uses)
+        OR_RETURN(ichol0_refill_proof(st, p->n, p->nnzA, d_indptr, d_indices, p->Lc, d_bad));
+        ILUPP_HIP(hipMemcpyAsync(&bad, d_bad, sizeof(int32_t), hipMemcpyDeviceToHost, st));
+        ILUPP_HIP(hipStreamSynchronize(st));
+        if (bad) { set_error("IChol0 refactor: the matrix does not have the analysed pattern"); return ILUPP_ERR_INVALID; }
+    }
+    ILUPP_HIP(hipEventRecord(p->ev[1], st));
+    OR_RETURN(ichol0_refill(st, p->n, d_indptr, d_indices, d_data, &p->Lc));
+    float kms = 0.f;
+    int rc = ILUPP_OK;
+    if (!(p->chol_static && ichol0_numeric_st(st, &p->Lc, p->sL, p->ctrl, &kms, &rc)))
+        rc = ichol0_numeric(st, &p->Lc, p->sL, p->max_row_len, p->done, p->ctrl, &kms);
+    ILUPP_HIP(hipEventRecord(p->ev[2], st));
+    ILUPP_HIP(stream_sync(st));
+    ILUPP_HIP(hipEventElapsedTime(&p->tm.numeric_ms, p->ev[1], p->ev[2]));
+    p->tm.numeric_kernel_ms = kms;
+    drop_old_value_copies(p);
+    drop_llt_sweep_copies(p);
+    if (rc == ILUPP_OK) settle_ctrl(p);
+    if (rc == ILUPP_ERR_TIMEOUT) set_error("IChol0: dependency wait timed out");
+    return rc;
+}
+
 int ilu0_refactor_single(ilupp_precond *p, const double *d_data, const int32_t *d_indices, const int32_t *d_indptr)
 {
     if (!is_ilu0_object(p)) { set_error("not an ILU(0) object"); return ILUPP_ERR_INVALID; }
@@ -1448,10 +1500,11 @@ int ilupp_hip_iluc_create_device(const double *d_data, const int32_t *d_indices,
 
 }  // extern "C"
 
-static int ichol0_create_common(DevMat &A, int32_t n, ilupp_precond **out)
+static int ichol0_create_common(DevMat &A, int32_t n, ilupp_precond **out, ilupp_precond *made = nullptr)
 {
-    ObjGuard g(new_obj(n));
+    ObjGuard g(made ? made : new_obj(n));
     ilupp_precond *p = g.p;
+    p->nnzA = A.nnz;
     p->kind = KIND_LLT;
     p->nnz_mode = NNZ_LLT;
     p->llt_diag_last = true;
@@ -1497,6 +1550,14 @@ int ilupp_hip_ichol0_create_device(const double *d_data, const int32_t *d_indice
 {
     return create_from_device(d_data, d_indices, d_indptr, n, true, out,
                               [&](DevMat &A) { return ichol0_create_common(A, n, out); });
+}
+
+int ilupp_hip_ichol0_refactor_device(ilupp_precond *p, const double *d_data, const int32_t *d_indices, const int32_t *d_indptr)
+{
+    API_TRY_BUILD
+    if (!p || !d_data || !d_indices || !d_indptr) { set_error("null argument"); return ILUPP_ERR_INVALID; }
+    return ichol0_refactor_single(p, d_data, d_indices, d_indptr);
+    API_CATCH
 }
 }  // extern "C"
 
@@ -1749,6 +1810,7 @@ const char *ilupp_hip_path(const ilupp_precond *p)
     }
     if (p->kind == KIND_LU) return "ilut";
     if (p->kind == KIND_UTU) return "iluc";
+    if (p->llt_diag_last && p->batch_built) return "ichol0:batch";
     return p->llt_diag_last ? (p->chol_static ? "ichol0:static-level-major" : "ichol0") : (p->icholt_grid ? "icholt:grid-static" : "icholt");
 }
 
@@ -1830,7 +1892,7 @@ const char *ilupp_hip_kernel_names(const ilupp_precond *p)
     if (p && p->kind == KIND_LLT) {
         // an LL^T object: the factor kernel of its construction and -- once an apply has built them -- the sweeps of its factor pair
         const PackedSweep &pf = p->llt_diag_last ? p->pkL : p->pkLT, &pb = p->llt_diag_last ? p->pkLT : p->pkL;
-        const char *fk = p->llt_diag_last ? (p->chol_static ? "k_ichol0_st" : "k_ichol0") : (p->icholt_grid ? "k_icholt_grid" : "k_icholt_df");
+        const char *fk = p->llt_diag_last ? (p->batch_built ? "k_ichol0_create_batch" : p->chol_static ? "k_ichol0_st" : "k_ichol0") : (p->icholt_grid ? "k_icholt_grid" : "k_icholt_df");
         static thread_local std::string names;
         names = fk;
         if (pf.valid && pf.pair && pb.valid && pb.pair) {
@@ -3330,22 +3392,67 @@ int64_t ilupp_hip_pivot_apply_batch_max_n(void)
     API_CATCH
 }
 
-// one member of the ILU(0) launches: the matrix and the two triangles of p (at the symbolic launch their index and value arrays are not
-// there yet: null), the number of stored entries the matrix is to have, and the member's number in the call
-static RefactorDesc refactor_desc(const ilupp_precond *p, const double *aval, const int32_t *aidx, const int32_t *aptr, int64_t nnzA, int32_t member)
+}  // extern "C"
+
+namespace {
+
+// What the batched re-factorisation and the batched first construction of ILU(0) and of IChol(0) differ in; everything else of the two
+// host scaffolds below is one copy.
+struct CreateMember;
+struct FactorBatchKind {
+    const char *name, *object;                       // in messages: "ILU0", "an ILU(0) object"
+    bool llt;                                        // one factor Lc (and its transposed copy, kept current) instead of Lc and Uc
+    int32_t alone_min;                               // rows from which a member that would have the launch to itself takes the single path
+    bool (*is_object)(const ilupp_precond *);
+    bool (*is_static)(const ilupp_precond *);        // the values live elsewhere than in the CSR factor(s), or the single path is the static form's
+    size_t (*fits)(int32_t n, int32_t max_row_len);
+    int64_t (*max_n)();
+    int (*refactor_launch)(hipStream_t, int32_t, const RefactorDesc *, int32_t *, size_t);
+    int (*symbolic_launch)(hipStream_t, int32_t, const RefactorDesc *, CreateInfo *);
+    int (*create_launch)(hipStream_t, int32_t, const RefactorDesc *, int32_t *, size_t);
+    int (*refactor_single)(ilupp_precond *, const double *, const int32_t *, const int32_t *);
+    // the single constructor inside a batched construction (staged: the matrix was uploaded on the scratch's stream, in_ev behind it)
+    int (*create_single)(const CreateMember &, int is_csr, bool staged, hipEvent_t in_ev, ilupp_precond **out);
+};
+int ilu0_create_single(const CreateMember &m, int is_csr, bool staged, hipEvent_t in_ev, ilupp_precond **out);
+int ichol0_create_single(const CreateMember &m, int is_csr, bool staged, hipEvent_t in_ev, ilupp_precond **out);
+// ONE member in the launch is one workgroup walking all its rows where the single path's factor kernels spread them over the chip, and
+// the launch then saves no host wait that matters.  ILU(0) alone: n = 1 000 takes 0.447 ms in the launch against 0.202 ms on the single
+// path, n = 4 000 0.858 against 0.167 ms (profiles/r13_refactor_batch.txt, "alone in the launch"; smaller n not measured: it stays in
+// the launch).  IChol(0) alone: n = 250 0.461 ms in the launch against 0.636 ms, n = 1 000 1.423 against 0.738 ms, n = 4 000 3.354 against
+// 0.843 ms (profiles/r16_ichol0_batch.txt, "alone in the launch"): the single path wins from the same 1 000 rows on.
+const FactorBatchKind kIlu0Batch = {"ILU0", "an ILU(0) object", false, 1000, is_ilu0_object,
+                                    [](const ilupp_precond *p) { return p->flm.built; }, ilu0_refactor_batch_fits, ilu0_refactor_batch_max_n,
+                                    ilu0_refactor_batch_launch, ilu0_symbolic_batch_launch, ilu0_create_batch_launch, ilu0_refactor_single,
+                                    ilu0_create_single};
+const FactorBatchKind kIchol0Batch = {"IChol0", "an IChol(0) object", true, 1000, is_ichol0_object,
+                                      [](const ilupp_precond *p) { return p->chol_static; }, ichol0_refactor_batch_fits, ichol0_refactor_batch_max_n,
+                                      ichol0_refactor_batch_launch, ichol0_symbolic_batch_launch, ichol0_create_batch_launch, ichol0_refactor_single,
+                                      ichol0_create_single};
+
+}  // namespace
+
+extern "C" {
+
+// one member of the launches: the matrix and the two triangles of p -- Lc and Uc, for IChol(0) Lc and its transposed copy LcT when the
+// object has one (at the symbolic launch the index and value arrays are not there yet: null) --, the number of stored entries the matrix
+// is to have, and the member's number in the call
+static RefactorDesc refactor_desc(const FactorBatchKind &K, const ilupp_precond *p, const double *aval, const int32_t *aidx, const int32_t *aptr,
+                                  int64_t nnzA, int32_t member)
 {
     RefactorDesc d;
     memset(&d, 0, sizeof(d));
     d.aptr = aptr; d.aidx = aidx; d.aval = aval;
     d.lptr = p->Lc.ptr; d.lidx = p->Lc.idx; d.lval = p->Lc.val;
-    d.uptr = p->Uc.ptr; d.uidx = p->Uc.idx; d.uval = p->Uc.val;
+    if (!K.llt) { d.uptr = p->Uc.ptr; d.uidx = p->Uc.idx; d.uval = p->Uc.val; }
+    else if (p->haveT) { d.uptr = p->LcT.ptr; d.uidx = p->LcT.idx; d.uval = p->LcT.val; }
     d.nnzA = nnzA; d.n = p->n; d.member = member;
     return d;
 }
 
-// what ilupp_hip_ilu0_refactor_batch_device does, under the construction lock its caller holds (the construction lock first, then the
+// what ilupp_hip_ilu0_refactor_batch_device and ilupp_hip_ichol0_refactor_batch_device do, under the construction lock its caller holds (the construction lock first, then the
 // batch lock: pool blocks are freed below; no path takes the two in the other order)
-static int refactor_batch_locked(int32_t count, ilupp_precond *const *members, const double *const *d_data,
+static int refactor_batch_locked(const FactorBatchKind &K, int32_t count, ilupp_precond *const *members, const double *const *d_data,
                                  const int32_t *const *d_indices, const int32_t *const *d_indptr, const int64_t *nnz,
                                  int32_t *d_status, int sync, int32_t *route)
 {
@@ -3353,7 +3460,7 @@ static int refactor_batch_locked(int32_t count, ilupp_precond *const *members, c
     if (!d_indices || !d_indptr || !d_status) { set_error("null argument"); return ILUPP_ERR_INVALID; }
     for (int32_t i = 0; i < count; ++i) {
         OR_RETURN(batch_matrix_arrays(d_data, d_indices, d_indptr, i));
-        if (!is_ilu0_object(members[i])) { set_error("member " + std::to_string(i) + " of the batch: not an ILU(0) object"); return ILUPP_ERR_INVALID; }
+        if (!K.is_object(members[i])) { set_error("member " + std::to_string(i) + " of the batch: not " + K.object); return ILUPP_ERR_INVALID; }
         if (nnz[i] != members[i]->nnzA) {
             set_error("member " + std::to_string(i) + " of the batch: the matrix does not have the analysed pattern");
             return ILUPP_ERR_INVALID;
@@ -3364,28 +3471,24 @@ static int refactor_batch_locked(int32_t count, ilupp_precond *const *members, c
     BatchScratch &S = batch_scratch();
     hipStream_t bs = S.stream;
     order_after_caller(bs, S.cev[0]);
-    // routes: 0 = the launch, 1 = n above the cap or a row above the row cap (ilu0_refactor_batch_fits), 2 = static form (its values live in
-    // lane-table records)
-    const int64_t cap_n = refactor_batch_max_n();
+    // routes: 0 = the launch, 1 = n above the cap or a row above the row cap (K.fits), 2 = static form (ILU(0): its values live in
+    // lane-table records; IChol(0): its single path is the static kernel)
+    const int64_t cap_n = batch_env_cap(K.max_n());
     S.route.assign((size_t)count, 0); S.launched.clear();
     size_t lds = 0;                                                     // what the launch's most demanding member asks for
     for (int32_t i = 0; i < count; ++i) {
         const ilupp_precond *p = members[i];
-        if (p->flm.built) { S.route[(size_t)i] = 2; continue; }
+        if (K.is_static(p)) { S.route[(size_t)i] = 2; continue; }
         // (a member the batched construction built has no single numeric path, and fits by construction: the launch, whatever the cap says)
         if (p->n > cap_n && !p->batch_built) { S.route[(size_t)i] = 1; continue; }
-        const size_t want = ilu0_refactor_batch_fits(p->n, p->max_row_len);
+        const size_t want = K.fits(p->n, p->max_row_len);
         if (want == 0) { S.route[(size_t)i] = 1; continue; }
         S.launched.push_back(i);
         if (want > lds) lds = want;
     }
-    // ONE member in the launch is one workgroup walking all its rows where the single path's factor kernels spread them over the chip, and
-    // the launch then saves no host wait that matters: alone, n = 1 000 takes 0.447 ms in the launch against 0.202 ms on the single path,
-    // n = 4 000 0.858 against 0.167 ms (profiles/r13_refactor_batch.txt, "alone in the launch"; smaller n not measured: it stays in the
-    // launch).  From kRefactorAloneMin rows on, a member that would have the launch to itself takes the single path.
+    // From K.alone_min rows on, a member that would have the launch to itself takes the single path (the measurements: at the kinds' table).
     // ILUPP_REFACTOR_ALONE_MIN moves the threshold (read per call; the measurement sets it above n to time the launch of one member).
-    constexpr int32_t kRefactorAloneMin = 1000;
-    long long alone_min = kRefactorAloneMin;
+    long long alone_min = K.alone_min;
     if (const char *e = getenv("ILUPP_REFACTOR_ALONE_MIN")) { const long long v = atoll(e); if (v > 0) alone_min = v; }
     if (S.launched.size() == 1 && members[S.launched[0]]->n >= alone_min && !members[S.launched[0]]->batch_built) { S.route[(size_t)S.launched[0]] = 1; S.launched.clear(); }
     routes_out(S.route, route);
@@ -3394,18 +3497,20 @@ static int refactor_batch_locked(int32_t count, ilupp_precond *const *members, c
         // (uploaded again only when a descriptor differs: the same members with their matrices in the same buffers, step after step, upload nothing)
         std::vector<RefactorDesc> fresh;
         fresh.reserve((size_t)nl);
-        for (int32_t i : S.launched) fresh.push_back(refactor_desc(members[i], d_data[i], d_indices[i], d_indptr[i], members[i]->nnzA, i));
+        for (int32_t i : S.launched) fresh.push_back(refactor_desc(K, members[i], d_data[i], d_indices[i], d_indptr[i], members[i]->nnzA, i));
         batch_upload(bs, S.rtable, fresh);
         // the launch behind whatever is still queued on a member's own stream; what earlier batched launches read of the factors lies on
         // the scratch's stream itself
         bool stale = false;
         for (int32_t i : S.launched) {
             ilupp_precond *p = members[i];
-            stale = stale || p->pkL.valid || p->pkU.valid || p->pkL.pkT || p->pkU.pkT || p->haveT;
+            // (IChol(0): the launch writes the transposed copy too, which therefore stays; what goes are the packed sweeps of the two)
+            if (K.llt) stale = stale || p->pkL.built || p->pkL.valid || p->pkLT.built || p->pkLT.valid;
+            else stale = stale || p->pkL.valid || p->pkU.valid || p->pkL.pkT || p->pkU.pkT || p->haveT;
             for (const auto &l : p->lvl) stale = stale || l.tried;
             batch_join(bs, p);
         }
-        OR_RETURN(ilu0_refactor_batch_launch(bs, nl, S.rtable.d, d_status, lds));
+        OR_RETURN(K.refactor_launch(bs, nl, S.rtable.d, d_status, lds));
         const std::vector<BatchMember> mv = batch_members(count, members, 0);
         batch_launched(S, mv.data());
         // this launch WRITES the factors: whatever a member's own stream does next (a single apply, factors(), ensure_*) comes after it
@@ -3417,6 +3522,7 @@ static int refactor_batch_locked(int32_t count, ilupp_precond *const *members, c
         for (int32_t i : S.launched) {
             ilupp_precond *p = members[i];
             p->csr_vals = true;
+            if (K.llt) { drop_llt_sweep_copies(p); continue; }      // (Lc and LcT, with LcT's schedule and descriptors, hold the new values)
             drop_old_value_copies(p);
             if (p->pkL.valid) { p->pkL.release(); p->pack_tried[0] = false; }
             if (p->pkU.valid) { p->pkU.release(); p->pack_tried[1] = false; }
@@ -3425,7 +3531,7 @@ static int refactor_batch_locked(int32_t count, ilupp_precond *const *members, c
     // routes 1 and 2: the single path on the member's own stream (it waits for its stream itself); the status word by the host afterwards
     for (int32_t i = 0; i < count; ++i) {
         if (S.route[(size_t)i] == 0) continue;
-        const int rc = ilu0_refactor_single(members[i], d_data[i], d_indices[i], d_indptr[i]);
+        const int rc = K.refactor_single(members[i], d_data[i], d_indices[i], d_indptr[i]);
         if (rc != ILUPP_OK && rc != ILUPP_ERR_INVALID && rc != ILUPP_ERR_TIMEOUT) return rc;
         ILUPP_HIP(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(d_status + i), rc == ILUPP_OK ? 0 : rc == ILUPP_ERR_INVALID ? 1 : 2, 1, bs));
     }
@@ -3436,7 +3542,7 @@ static int refactor_batch_locked(int32_t count, ilupp_precond *const *members, c
         for (int32_t i : S.launched) members[i]->batch_ev = nullptr;
         for (int32_t i = 0; i < count; ++i) {
             if (st[(size_t)i] == 1) { set_error("member " + std::to_string(i) + " of the batch: the matrix does not have the analysed pattern"); return ILUPP_ERR_INVALID; }
-            if (st[(size_t)i] != 0) { set_error("member " + std::to_string(i) + " of the batch: ILU0: dependency wait timed out"); return ILUPP_ERR_TIMEOUT; }
+            if (st[(size_t)i] != 0) { set_error("member " + std::to_string(i) + " of the batch: " + K.name + ": dependency wait timed out"); return ILUPP_ERR_TIMEOUT; }
         }
         return ILUPP_OK;
     }
@@ -3449,7 +3555,7 @@ int ilupp_hip_ilu0_refactor_batch_device(int32_t count, ilupp_precond *const *me
                                          int32_t *d_status, int sync, int32_t *route)
 {
     API_TRY_BUILD
-    return refactor_batch_locked(count, members, d_data, d_indices, d_indptr, nnz, d_status, sync, route);
+    return refactor_batch_locked(kIlu0Batch, count, members, d_data, d_indices, d_indptr, nnz, d_status, sync, route);
     API_CATCH
 }
 
@@ -3460,9 +3566,25 @@ int64_t ilupp_hip_ilu0_refactor_batch_max_n(void)
     API_CATCH
 }
 
+int ilupp_hip_ichol0_refactor_batch_device(int32_t count, ilupp_precond *const *members, const double *const *d_data,
+                                           const int32_t *const *d_indices, const int32_t *const *d_indptr, const int64_t *nnz,
+                                           int32_t *d_status, int sync, int32_t *route)
+{
+    API_TRY_BUILD
+    return refactor_batch_locked(kIchol0Batch, count, members, d_data, d_indices, d_indptr, nnz, d_status, sync, route);
+    API_CATCH
+}
+
+int64_t ilupp_hip_ichol0_refactor_batch_max_n(void)
+{
+    API_TRY
+    return batch_env_cap(ichol0_refactor_batch_max_n());
+    API_CATCH
+}
+
 }  // extern "C"
 
-// ---- many ILU(0) objects built at once: a symbolic launch, one read-back, a create launch (ilu0_batch.hip) ----
+// ---- many ILU(0) or IChol(0) objects built at once: a symbolic launch, one read-back, a create launch (ilu0_batch.hip, ichol0_batch.hip) ----
 namespace {
 
 int refactor_in_launch(ilupp_precond *p, const double *d_data, const int32_t *d_indices, const int32_t *d_indptr)
@@ -3472,7 +3594,7 @@ int refactor_in_launch(ilupp_precond *p, const double *d_data, const int32_t *d_
     const double *const dd[1] = {d_data};
     const int32_t *const di[1] = {d_indices}, *const dp[1] = {d_indptr};
     const int64_t nz[1] = {p->nnzA};
-    const int rc = refactor_batch_locked(1, one, dd, di, dp, nz, p->ctrl + 2, 1, nullptr);      // (ctrl[2]: a word no sweep of such an object uses)
+    const int rc = refactor_batch_locked(p->kind == KIND_LLT ? kIchol0Batch : kIlu0Batch, 1, one, dd, di, dp, nz, p->ctrl + 2, 1, nullptr);      // (ctrl[2]: a word no sweep of such an object uses)
     if (rc) {
         const std::string prefix = "member 0 of the batch: ", msg = g_last_error;
         if (msg.compare(0, prefix.size(), prefix) == 0) set_error(msg.substr(prefix.size()));
@@ -3494,14 +3616,14 @@ struct CreatedObjects {
     ~CreatedObjects() { for (ilupp_precond *p : v) if (p) { if (p->side) (void)stream_sync(p->side); destroy_obj(p); } }
 };
 
-// What both entries of the batched ILU(0) construction do once the matrices are in device memory (count > 0; the caller holds the
+// What the entries of the batched ILU(0) and IChol(0) constructions do once the matrices are in device memory (count > 0; the caller holds the
 // construction lock and the batch lock).  staged: the matrices were uploaded on the scratch's stream (S.in_ev behind the upload), not
 // produced on the caller's.  Routes: 0 = built by the two launches; 1 = built by the single constructor inside this call (n above the cap
 // of the re-factorisation's launch, a longest row above its row cap, a matrix whose rows are not sorted or whose indices are out of
 // range -- whatever the single constructor does with it, it does here --, or a batch of one: a user who builds one object wants the
 // fully analysed one).  The first failing member is reported as "matrix i of the batch: ...", status[i] says which failed, and no
 // object of the call survives a failure (batch_build's convention).
-int ilu0_create_batch_run(BatchScratch &S, int32_t count, const CreateMember *m, int is_csr, bool staged, ilupp_precond **out, int32_t *status,
+int factor_create_batch_run(const FactorBatchKind &K, BatchScratch &S, int32_t count, const CreateMember *m, int is_csr, bool staged, ilupp_precond **out, int32_t *status,
                           int32_t *route)
 {
     hipStream_t bs = S.stream;
@@ -3511,11 +3633,11 @@ int ilu0_create_batch_run(BatchScratch &S, int32_t count, const CreateMember *m,
     std::vector<int32_t> rt((size_t)count, 0);
     CreatedObjects objs;
     objs.v.assign((size_t)count, nullptr);
-    const int64_t cap_n = refactor_batch_max_n();
+    const int64_t cap_n = batch_env_cap(K.max_n());
     std::vector<int32_t> cand;                       // the members of the symbolic launch
     for (int32_t i = 0; i < count; ++i) {
         if (m[i].n <= 0 || !m[i].indptr) { rcs[(size_t)i] = ILUPP_ERR_INVALID; msgs[(size_t)i] = "matrix has size 0!"; continue; }
-        if (m[i].nnz < 0 || m[i].nnz + (int64_t)m[i].n > INT32_MAX) { rcs[(size_t)i] = ILUPP_ERR_INVALID; msgs[(size_t)i] = "ILU0: too many stored entries for 32-bit indices"; continue; }
+        if (m[i].nnz < 0 || m[i].nnz + (int64_t)m[i].n > INT32_MAX) { rcs[(size_t)i] = ILUPP_ERR_INVALID; msgs[(size_t)i] = std::string(K.name) + ": too many stored entries for 32-bit indices"; continue; }
         if (count == 1 || m[i].n > cap_n) { rt[(size_t)i] = 1; continue; }
         cand.push_back(i);
     }
@@ -3530,17 +3652,19 @@ int ilu0_create_batch_run(BatchScratch &S, int32_t count, const CreateMember *m,
         // the objects, and the n + 1 row pointers of L and of U the symbolic launch writes
         for (int32_t i : cand) {
             ilupp_precond *p = objs.v[(size_t)i] = new_obj(m[i].n);
-            p->kind = KIND_LU; p->nnz_mode = NNZ_GENERIC_LU; p->input_csc = !is_csr;
+            if (K.llt) { p->kind = KIND_LLT; p->nnz_mode = NNZ_LLT; p->llt_diag_last = true; }
+            else { p->kind = KIND_LU; p->nnz_mode = NNZ_GENERIC_LU; p->input_csc = !is_csr; }
             for (DevMat *M : {&p->Lc, &p->Uc}) {
+                if (K.llt && M == &p->Uc) continue;
                 M->n = m[i].n; M->is_csr = true; M->owns = true;
                 ILUPP_HIP(pool_malloc(&M->ptr, sizeof(int32_t) * (size_t)(m[i].n + 1)));
             }
-            fresh.push_back(refactor_desc(p, m[i].data, m[i].indices, m[i].indptr, m[i].nnz, i));
+            fresh.push_back(refactor_desc(K, p, m[i].data, m[i].indices, m[i].indptr, m[i].nnz, i));
         }
         // (sent whatever the table holds, and the re-factorisation's cached table is gone: these descriptors are half filled)
         batch_upload(bs, S.rtable, fresh, false);
         ILUPP_HIP(hipEventRecord(S.tev[0], bs));
-        OR_RETURN(ilu0_symbolic_batch_launch(bs, nc, S.rtable.d, S.cinfo.d));
+        OR_RETURN(K.symbolic_launch(bs, nc, S.rtable.d, S.cinfo.d));
         ILUPP_HIP(hipEventRecord(S.tev[1], bs));
         // the call's one host wait in front of the numeric launch: all result records with one read-back
         ILUPP_HIP(hipMemcpyAsync(S.cinfo.h, S.cinfo.d, sizeof(CreateInfo) * (size_t)nc, hipMemcpyDeviceToHost, bs));
@@ -3551,17 +3675,18 @@ int ilu0_create_batch_run(BatchScratch &S, int32_t count, const CreateMember *m,
             const CreateInfo &o = S.cinfo.h[k];
             ilupp_precond *p = objs.v[(size_t)i];
             if (o.flags & kCreateNnzDiffers) {
-                rcs[(size_t)i] = ILUPP_ERR_INVALID; msgs[(size_t)i] = "ILU0: the number of stored entries handed in is not indptr[n]";
+                rcs[(size_t)i] = ILUPP_ERR_INVALID; msgs[(size_t)i] = std::string(K.name) + ": the number of stored entries handed in is not indptr[n]";
             } else if (o.flags & kCreateUnsorted) {
                 rt[(size_t)i] = 1;
             } else if (o.missing >= 0) {
                 rcs[(size_t)i] = ILUPP_ERR_NO_DIAGONAL;
-                msgs[(size_t)i] = "ILU0: structurally missing diagonal entry in row " + std::to_string(o.missing);
+                msgs[(size_t)i] = std::string(K.name) + ": structurally missing diagonal entry in row " + std::to_string(o.missing);
             } else {
-                if (ilu0_refactor_batch_fits(m[i].n, o.max_row_len) == 0) { rt[(size_t)i] = 1; continue; }
+                if (K.fits(m[i].n, o.max_row_len) == 0) { rt[(size_t)i] = 1; continue; }
                 // exact index and value arrays, and what the object records of the factored matrix
                 p->Lc.nnz = o.nnz_l; p->Uc.nnz = o.nnz_u;
                 for (DevMat *M : {&p->Lc, &p->Uc}) {
+                    if (K.llt && M == &p->Uc) continue;
                     ILUPP_HIP(pool_malloc(&M->idx, sizeof(int32_t) * (size_t)M->nnz));
                     ILUPP_HIP(pool_malloc(&M->val, sizeof(double) * (size_t)M->nnz));
                 }
@@ -3579,13 +3704,13 @@ int ilu0_create_batch_run(BatchScratch &S, int32_t count, const CreateMember *m,
         size_t lds = 0;
         for (int32_t i : launched) {
             const ilupp_precond *p = objs.v[(size_t)i];
-            fresh.push_back(refactor_desc(p, m[i].data, m[i].indices, m[i].indptr, p->nnzA, i));
-            const size_t want = ilu0_refactor_batch_fits(m[i].n, p->max_row_len);
+            fresh.push_back(refactor_desc(K, p, m[i].data, m[i].indices, m[i].indptr, p->nnzA, i));
+            const size_t want = K.fits(m[i].n, p->max_row_len);
             if (want > lds) lds = want;
         }
         batch_upload(bs, S.rtable, fresh);
         ILUPP_HIP(hipEventRecord(S.tev[2], bs));
-        OR_RETURN(ilu0_create_batch_launch(bs, nl, S.rtable.d, S.cstat.d, lds));
+        OR_RETURN(K.create_launch(bs, nl, S.rtable.d, S.cstat.d, lds));
         ILUPP_HIP(hipEventRecord(S.tev[3], bs));
         // whatever a member's own stream does next (an apply, factors(), ensure_*) comes after the launch that writes its factors
         ILUPP_HIP(hipEventRecord(S.done_ev, bs));
@@ -3595,17 +3720,7 @@ int ilu0_create_batch_run(BatchScratch &S, int32_t count, const CreateMember *m,
     for (int32_t i = 0; i < count && !failed; ++i) {
         if (rt[(size_t)i] != 1) continue;
         if (objs.v[(size_t)i]) { destroy_obj(objs.v[(size_t)i]); objs.v[(size_t)i] = nullptr; }      // (it only held the two row-pointer arrays)
-        int rc;
-        if (staged) {
-            int32_t head[10];
-            host_head(m[i].h_indptr, m[i].h_indices, m[i].nnz, head);
-            ilupp_precond *made = new_obj(m[i].n);
-            if (hipStreamWaitEvent(made->stream, S.in_ev, 0) != hipSuccess) { destroy_obj(made); set_error("batched construction: no stream"); return ILUPP_ERR_HIP; }
-            rc = ilu0_create_common(borrow_csr(m[i].data, m[i].indices, m[i].indptr, m[i].n, m[i].nnz, true), is_csr, head, &objs.v[(size_t)i], made);
-        } else {
-            rc = ilu0_create_device_locked(m[i].data, m[i].indices, m[i].indptr, m[i].n, is_csr, &objs.v[(size_t)i]);
-            if (rc == ILUPP_OK && objs.v[(size_t)i]->nnzA != m[i].nnz) { rc = ILUPP_ERR_INVALID; set_error("ILU0: the number of stored entries handed in is not indptr[n]"); }
-        }
+        const int rc = K.create_single(m[i], is_csr, staged, S.in_ev, &objs.v[(size_t)i]);
         if (rc) { rcs[(size_t)i] = rc; msgs[(size_t)i] = g_last_error; failed = true; }
     }
     if (nl > 0) {
@@ -3616,8 +3731,8 @@ int ilu0_create_batch_run(BatchScratch &S, int32_t count, const CreateMember *m,
         ILUPP_HIP(hipEventElapsedTime(&create_ms, S.tev[2], S.tev[3]));
         for (int32_t i : launched) {
             ilupp_precond *p = objs.v[(size_t)i];
-            if (st[(size_t)i] == 2) { rcs[(size_t)i] = ILUPP_ERR_TIMEOUT; msgs[(size_t)i] = "ILU0: dependency wait timed out (invalid structure?)"; }
-            else if (st[(size_t)i] != 0) { rcs[(size_t)i] = ILUPP_ERR_INVALID; msgs[(size_t)i] = "ILU0: the matrix changed while it was factored"; }
+            if (st[(size_t)i] == 2) { rcs[(size_t)i] = ILUPP_ERR_TIMEOUT; msgs[(size_t)i] = std::string(K.name) + ": dependency wait timed out (invalid structure?)"; }
+            else if (st[(size_t)i] != 0) { rcs[(size_t)i] = ILUPP_ERR_INVALID; msgs[(size_t)i] = std::string(K.name) + ": the matrix changed while it was factored"; }
             // (the two launches' times, shared by the call's members)
             p->tm.analysis_ms = sym_ms; p->tm.numeric_ms = create_ms; p->tm.numeric_kernel_ms = create_ms;
         }
@@ -3633,15 +3748,38 @@ int ilu0_create_batch_run(BatchScratch &S, int32_t count, const CreateMember *m,
     return ILUPP_OK;
 }
 
-}  // namespace
-
-extern "C" {
-
-int ilupp_hip_ilu0_create_batch_device(int32_t count, const double *const *d_data, const int32_t *const *d_indices,
-                                       const int32_t *const *d_indptr, const int32_t *n, const int64_t *nnz, int is_csr, ilupp_precond **out,
-                                       int32_t *status, int32_t *route)
+int ilu0_create_single(const CreateMember &m, int is_csr, bool staged, hipEvent_t in_ev, ilupp_precond **out)
 {
-    API_TRY_BUILD
+    if (staged) {
+        int32_t head[10];
+        host_head(m.h_indptr, m.h_indices, m.nnz, head);
+        ilupp_precond *made = new_obj(m.n);
+        if (hipStreamWaitEvent(made->stream, in_ev, 0) != hipSuccess) { destroy_obj(made); set_error("batched construction: no stream"); return ILUPP_ERR_HIP; }
+        return ilu0_create_common(borrow_csr(m.data, m.indices, m.indptr, m.n, m.nnz, true), is_csr, head, out, made);
+    }
+    const int rc = ilu0_create_device_locked(m.data, m.indices, m.indptr, m.n, is_csr, out);
+    if (rc == ILUPP_OK && (*out)->nnzA != m.nnz) { set_error("ILU0: the number of stored entries handed in is not indptr[n]"); return ILUPP_ERR_INVALID; }
+    return rc;
+}
+
+int ichol0_create_single(const CreateMember &m, int is_csr, bool staged, hipEvent_t in_ev, ilupp_precond **out)
+{
+    (void)is_csr;                                    // (as ilupp_hip_ichol0_create)
+    if (!staged && (int64_t)read_device_nnz(m.indptr, m.n) != m.nnz) {
+        set_error("IChol0: the number of stored entries handed in is not indptr[n]");
+        return ILUPP_ERR_INVALID;
+    }
+    ilupp_precond *made = new_obj(m.n);
+    if (staged && hipStreamWaitEvent(made->stream, in_ev, 0) != hipSuccess) { destroy_obj(made); set_error("batched construction: no stream"); return ILUPP_ERR_HIP; }
+    DevMat A = borrow_csr(m.data, m.indices, m.indptr, m.n, m.nnz, true);
+    return ichol0_create_common(A, m.n, out, made);
+}
+
+// the arguments of the *_create_batch_device entries, then the run
+int factor_create_batch_device(const FactorBatchKind &K, int32_t count, const double *const *d_data, const int32_t *const *d_indices,
+                               const int32_t *const *d_indptr, const int32_t *n, const int64_t *nnz, int is_csr, ilupp_precond **out,
+                               int32_t *status, int32_t *route)
+{
     if (count < 0 || !d_data || !d_indices || !d_indptr || !n || !nnz || !out) { set_error("null argument"); return ILUPP_ERR_INVALID; }
     for (int32_t i = 0; i < count; ++i) { out[i] = nullptr; if (status) status[i] = ILUPP_OK; if (route) route[i] = 0; }
     std::vector<CreateMember> m((size_t)count);
@@ -3652,14 +3790,13 @@ int ilupp_hip_ilu0_create_batch_device(int32_t count, const double *const *d_dat
     }
     if (count == 0) return ILUPP_OK;
     std::lock_guard<std::mutex> lk(g_batch_mu);
-    return ilu0_create_batch_run(batch_scratch(), count, m.data(), is_csr, false, out, status, route);
-    API_CATCH
+    return factor_create_batch_run(K, batch_scratch(), count, m.data(), is_csr, false, out, status, route);
 }
 
-int ilupp_hip_ilu0_create_batch(int32_t count, const double *const *data, const int32_t *const *indices, const int32_t *const *indptr,
-                                const int32_t *n, int is_csr, ilupp_precond **out, int32_t *status, int32_t *route)
+// ... of the host-array entries: all members through ONE packed block, one upload
+int factor_create_batch_host(const FactorBatchKind &K, int32_t count, const double *const *data, const int32_t *const *indices,
+                             const int32_t *const *indptr, const int32_t *n, int is_csr, ilupp_precond **out, int32_t *status, int32_t *route)
 {
-    API_TRY_BUILD
     if (count < 0 || !data || !indices || !indptr || !n || !out) { set_error("null argument"); return ILUPP_ERR_INVALID; }
     for (int32_t i = 0; i < count; ++i) { out[i] = nullptr; if (status) status[i] = ILUPP_OK; if (route) route[i] = 0; }
     for (int32_t i = 0; i < count; ++i)
@@ -3696,11 +3833,49 @@ int ilupp_hip_ilu0_create_batch(int32_t count, const double *const *data, const 
     }
     if (total > 0) ILUPP_HIP(hipMemcpyAsync(S.stage.d, S.stage.h, sizeof(double) * total, hipMemcpyHostToDevice, S.stream));
     ILUPP_HIP(hipEventRecord(S.in_ev, S.stream));
-    const int rc = ilu0_create_batch_run(S, count, m.data(), is_csr, true, out, status, route);
+    const int rc = factor_create_batch_run(K, S, count, m.data(), is_csr, true, out, status, route);
     // (the staged matrices are read by nothing once the call is over: every member's construction has been waited for)
     if (rc) (void)hipStreamSynchronize(S.stream);
     return rc;
+}
+
+}  // namespace
+
+extern "C" {
+
+int ilupp_hip_ilu0_create_batch_device(int32_t count, const double *const *d_data, const int32_t *const *d_indices,
+                                       const int32_t *const *d_indptr, const int32_t *n, const int64_t *nnz, int is_csr, ilupp_precond **out,
+                                       int32_t *status, int32_t *route)
+{
+    API_TRY_BUILD
+    return factor_create_batch_device(kIlu0Batch, count, d_data, d_indices, d_indptr, n, nnz, is_csr, out, status, route);
+    API_CATCH
+}
+
+int ilupp_hip_ilu0_create_batch(int32_t count, const double *const *data, const int32_t *const *indices, const int32_t *const *indptr,
+                                const int32_t *n, int is_csr, ilupp_precond **out, int32_t *status, int32_t *route)
+{
+    API_TRY_BUILD
+    return factor_create_batch_host(kIlu0Batch, count, data, indices, indptr, n, is_csr, out, status, route);
+    API_CATCH
+}
+
+int ilupp_hip_ichol0_create_batch_device(int32_t count, const double *const *d_data, const int32_t *const *d_indices,
+                                         const int32_t *const *d_indptr, const int32_t *n, const int64_t *nnz, int is_csr, ilupp_precond **out,
+                                         int32_t *status, int32_t *route)
+{
+    API_TRY_BUILD
+    return factor_create_batch_device(kIchol0Batch, count, d_data, d_indices, d_indptr, n, nnz, is_csr, out, status, route);
+    API_CATCH
+}
+
+int ilupp_hip_ichol0_create_batch(int32_t count, const double *const *data, const int32_t *const *indices, const int32_t *const *indptr,
+                                  const int32_t *n, int is_csr, ilupp_precond **out, int32_t *status, int32_t *route)
+{
+    API_TRY_BUILD
+    return factor_create_batch_host(kIchol0Batch, count, data, indices, indptr, n, is_csr, out, status, route);
     API_CATCH
 }
 
 }  // extern "C"
+

@@ -650,6 +650,21 @@ int ilu0_symbolic_batch_launch(hipStream_t st, int32_t count, const RefactorDesc
 // ilu0_refactor_batch_launch's (1: the matrix is no longer the one the symbolic launch read); lds_bytes: the largest fits()
 int ilu0_create_batch_launch(hipStream_t st, int32_t count, const RefactorDesc *d_table, int32_t *d_status, size_t lds_bytes);
 
+// ichol0_batch.hip: the same three launches for IChol(0), one workgroup per member.  The descriptor is RefactorDesc with other contents:
+// l* = the factor Lc (row-major lower triangle, strictly lower ascending, the diagonal LAST), u* = its transposed storage LcT (row c
+// ascending, the diagonal FIRST) or three null pointers for a member that has none; the re-factorisation and the create launch write the
+// new values into both.  Status words as above.  CreateInfo: nnz_l = entries of L, nnz_u = 0, max_row_len = the longest row of L.
+int64_t ichol0_refactor_batch_max_n();   // the largest n of a member on the current device (LDS: flags + working rows of 8 entries)
+// bytes of LDS a member asks of the launch (4 n bytes of flags + 5 120 bytes per entry of L's longest row), 0 = above the row cap
+size_t ichol0_refactor_batch_fits(int32_t n, int32_t max_row_len);
+int ichol0_refactor_batch_launch(hipStream_t st, int32_t count, const RefactorDesc *d_table, int32_t *d_status, size_t lds_bytes);
+int ichol0_symbolic_batch_launch(hipStream_t st, int32_t count, const RefactorDesc *d_table, CreateInfo *d_info);
+int ichol0_create_batch_launch(hipStream_t st, int32_t count, const RefactorDesc *d_table, int32_t *d_status, size_t lds_bytes);
+// the single re-factorisation's first step, over the chip: *d_bad = 1 unless, row by row, A's stored entries with column <= r are exactly
+// L's row (ichol0_refill_proof, writes nothing else); then L.val = those entries' values (ichol0_refill, behind a proof that passed)
+int ichol0_refill_proof(hipStream_t st, int32_t n, int64_t nnzA, const int32_t *aptr, const int32_t *aidx, const DevMat &L, int32_t *d_bad);
+int ichol0_refill(hipStream_t st, int32_t n, const int32_t *aptr, const int32_t *aidx, const double *aval, DevMat *L);
+
 // sptrsv_lvl.hip
 bool lvl_order(hipStream_t st, int mode, int32_t n, int64_t nnz, const int32_t *ptr, const int32_t *idx, const Schedule &sch,
                int32_t **perm_out, int32_t *nlevels, LevelNumbering *how = nullptr);

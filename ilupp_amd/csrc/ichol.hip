@@ -11,8 +11,9 @@
 //
 // Execution: first-generation persistent dataflow kernel (one launch, thread-per-row-block, rows of a lane in
 // order, finished rows published write-through + drained + flagged, consumers poll the flag; see ilu0.hip for
-// the protocol).  The working row lives in LDS.  This is the correctness-first kernel of this path; it does not
-// yet have the loader/consumer structure of the ILU(0) kernels.
+// the protocol).  The working row lives in LDS.  It spreads ONE matrix over the chip and waits for the host; for MANY
+// small members -- built at once, or re-factorised step after step in front of cg_batch -- see ichol0_batch.hip (one
+// workgroup per member, pivot rows fetched eight entries at a time, the transposed copy kept current by the same launch).
 #include <hipcub/hipcub.hpp>
 
 #include "common.h"

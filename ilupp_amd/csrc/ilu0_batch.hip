@@ -50,28 +50,9 @@
 #include <limits.h>
 
 #include "common.h"
+#include "refactor_batch.h"
 
 namespace ilupp {
-
-static constexpr int kRfThreads = 256;         // one wave per SIMD, as k_pivot_apply_batch
-static constexpr int kRG = 8;                  // entries of a row fetched together, their loads in flight at once
-static constexpr int kRfMaxRow = 31;            // the row cap where LDS allows it (see above)
-static constexpr size_t kRfRowBytes = (size_t)kRfThreads * (sizeof(double) + 3 * sizeof(int));      // LDS per entry of the longest row
-
-// bytes of LDS in front of the working rows: the flags, to a multiple of 8
-__host__ __device__ inline size_t rf_flag_bytes(int n) { return ((size_t)(n > 0 ? n : 1) * sizeof(int) + 7) & ~(size_t)7; }
-
-// The arrays come out of a descriptor in memory, so the compiler cannot tell their address space and would reach them with flat_
-// instructions, which count against the LDS counter as well: every wait for a working-row access would wait for the loads in flight.
-// Typed as global pointers they are reached with global_ instructions.
-#if defined(__HIP_DEVICE_COMPILE__)
-#define RF_HBM __attribute__((address_space(1)))
-#else
-#define RF_HBM
-#endif
-typedef const RF_HBM int32_t *rf_cint;
-typedef const RF_HBM double *rf_cdbl;
-typedef RF_HBM double *rf_dbl;
 
 // pass 2 for one member; the working rows in LDS (wv, wc, wk0, wkl: entry q of this lane at [q * 256 + tid])
 __device__ __forceinline__ void refactor_rows(const RefactorDesc &d, int *rf_done, double *wv, int *wc, int *wk0, int *wkl,
@@ -236,7 +217,6 @@ k_ilu0_refactor_batch(const RefactorDesc *__restrict__ table, int32_t *__restric
 }
 
 // ---- first construction: the symbolic launch ----
-typedef RF_HBM int32_t *rf_int;
 
 __global__ void __launch_bounds__(kRfThreads)
 k_ilu0_symbolic_batch(const RefactorDesc *__restrict__ table, CreateInfo *__restrict__ info)

@@ -154,7 +154,7 @@ class DevicePreconditioner:
         ``_native.ilu0_refactor_batch_max_n()``, a row of more than 31 entries), one with an unsorted row, and a batch of one are built
         by the single constructor inside the same call.  Ordered on torch's current stream; the call returns when every member is
         built.  A matrix without a diagonal entry in some row raises the constructor's RuntimeError, named by its number, and no object
-        is returned.  NotImplementedError for any other kind, TypeError for a member that is not a DeviceCSR -- before any native call;
+        is returned.  (IChol(0) has a batched construction under a name of its own: ``ichol0_batch``.)  NotImplementedError for any other kind, TypeError for a member that is not a DeviceCSR -- before any native call;
         an empty list gives ``[]``."""
         if kind != "ILU0":
             raise NotImplementedError("DevicePreconditioner.batch: only the \"ILU0\" kind has a batched construction, not %s" % (kind,))
@@ -206,7 +206,7 @@ class DevicePreconditioner:
         (ilupp_hip_ilu0_refactor_device); ordered on torch's current stream, the host waits for the new factor.  "ILU0" only:
         NotImplementedError for any other kind; ValueError for a matrix of another dimension -- before any native call.  A matrix whose
         number of stored entries differs from the analysed one's is refused by the library (RuntimeError).  Many small members at once:
-        ``refactor_batch_``."""
+        ``refactor_batch_``.  (IChol(0): ``ichol0_refactor_`` / ``ichol0_refactor_batch_``.)"""
         if self.kind != "ILU0":
             raise NotImplementedError("refactor_: only the \"ILU0\" kind has a numeric re-factorisation, not %s" % self.kind)
         if not isinstance(A, DeviceCSR):
@@ -522,17 +522,23 @@ def refactor_batch_(members, As, check=True):
     another kind or class, a pivoting member, the multilevel class or a matrix that is not a DeviceCSR; ValueError for lists of unequal
     length, a member named twice or a matrix and a member of different dimensions -- before any native call.  The batched FIRST
     construction of such members: ``DevicePreconditioner.batch("ILU0", As)`` / ``ilupp_amd.ILU0Preconditioner.batch`` (members built
-    that way always take route 0 here).  Out of scope: the other classes (no single re-factorisation to match), host (numpy) matrices."""
+    that way always take route 0 here).  IChol(0) members: ``ichol0_refactor_batch_``.  Out of scope: the other classes (no single
+    re-factorisation to match), host (numpy) matrices."""
+    return _refactor_batch("refactor_batch_", "ILU0", lambda *a, **k: _native.ilu0_refactor_batch_device(*a, **k), members, As, check)
+
+
+def _refactor_batch(who, want, entry, members, As, check):
+    """``refactor_batch_`` / ``ichol0_refactor_batch_`` for members of the kind ``want``: the argument checks, then ``entry``"""
     members, As = list(members), list(As)
     for A in As:
         if not isinstance(A, DeviceCSR):
-            raise TypeError("refactor_batch_ takes DeviceCSR matrices, got %s" % type(A).__name__)
+            raise TypeError("%s takes DeviceCSR matrices, got %s" % (who, type(A).__name__))
     natives = []
     for P in members:
-        pr, kind = _factor_native(P, "refactor_batch_")
-        if kind != "ILU0":
-            raise TypeError("refactor_batch_ takes members of the ILU0 kind only (DevicePreconditioner(\"ILU0\"), ILU0Preconditioner or a "
-                            "FactorOperator of one), got %s" % (kind if kind != "factor" else type(P).__name__))
+        pr, kind = _factor_native(P, who)
+        if kind != want:
+            raise TypeError("%s takes members of the %s kind only (DevicePreconditioner(\"%s\"), %sPreconditioner or a "
+                            "FactorOperator of one), got %s" % (who, want, want, want, kind if kind != "factor" else type(P).__name__))
         natives.append(pr)
     if len(members) != len(As):
         raise ValueError("%d preconditioners but %d matrices" % (len(members), len(As)))
@@ -545,7 +551,7 @@ def refactor_batch_(members, As, check=True):
         return [] if check else ([], torch.zeros(0, dtype=torch.int32))
     status = torch.zeros(len(natives), dtype=torch.int32, device=As[0].data.device)
     _on_current_stream()
-    route = _native.ilu0_refactor_batch_device(
+    route = entry(
         natives, [(A.data.data_ptr(), A.indices.data_ptr(), A.indptr.data_ptr(), A.nnz) for A in As], status.data_ptr(), sync=False)
     if not check:
         return route, status
@@ -553,8 +559,88 @@ def refactor_batch_(members, As, check=True):
         if v == 1:
             raise ValueError("member %d of the batch: the matrix does not have the analysed pattern (its factor is unchanged)" % k)
         if v != 0:
-            raise RuntimeError("member %d of the batch: ILU0: dependency wait timed out" % k)
+            raise RuntimeError("member %d of the batch: %s: dependency wait timed out" % (k, want))
     return route
+
+
+def ichol0_batch(As):
+    """``[DevicePreconditioner("IChol0", A) for A in As]`` from ONE native call, for MANY SMALL symmetric positive definite matrices: what
+    ``DevicePreconditioner.batch("ILU0", As)`` is for ILU(0).  Two kernel launches of one workgroup per matrix around one read-back
+    (ilupp_hip_ichol0_create_batch_device) where the loop pays the single constructor's five host waits and dozen launches per object;
+    the factor and every apply of a member have the bits of the singly built object.  The members go into ``apply_batch_`` / ``cg_batch``
+    / ``ichol0_refactor_batch_`` as they are: the first ``cg_batch`` (or ``apply_batch_``) builds a member's transposed copy of the
+    factor, and every ``ichol0_refactor_batch_`` after that keeps it current, so a loop of re-factorisation and ``cg_batch`` waits for
+    nothing on the host.  A matrix above the launches' caps (n above ``_native.ichol0_refactor_batch_max_n()``, a row of L of more than 31
+    entries -- 28 at n = 4 000), one with an unsorted row, and a batch of one are built by the single constructor inside the same call.
+    Ordered on torch's current stream; the call returns when every member is built.  A matrix without a diagonal entry in some row raises
+    the constructor's RuntimeError, named by its number, and no object is returned.  TypeError for a member that is not a DeviceCSR --
+    before any native call; an empty list gives ``[]``."""
+    As = list(As)
+    for A in As:
+        if not isinstance(A, DeviceCSR):
+            raise TypeError("ichol0_batch takes DeviceCSR matrices, got %s" % type(A).__name__)
+    if not As:
+        return []
+    _on_current_stream()
+    natives = _native.IChol0Preconditioner_batch_device(
+        [(A.data.data_ptr(), A.indices.data_ptr(), A.indptr.data_ptr(), A.n, A.nnz) for A in As], True)
+    out = []
+    for A, pr in zip(As, natives):
+        M = DevicePreconditioner.__new__(DevicePreconditioner)
+        M.pr, M.kind, M.n, M.shape = pr, "IChol0", A.n, A.shape
+        out.append(M)
+    return out
+
+
+def ichol0_refactor_(M, A):
+    """The numeric IChol(0) factorisation again on a DeviceCSR with the SAME pattern and (possibly) new values, the analysis kept
+    (ilupp_hip_ichol0_refactor_device); returns ``M``.  ``M``: a ``DevicePreconditioner("IChol0", ...)``, a host ``IChol0Preconditioner``
+    of the ctypes binding or a ``FactorOperator`` of one.  The factor has the bits of a fresh construction from ``A``.  The pattern is
+    PROVED equal to the analysed one (the lower triangle row by row; entries above the diagonal are ignored, as the constructor drops
+    them): a matrix that differs is refused by the library (RuntimeError) and the factor stays as it was.  Ordered on torch's current
+    stream, the host waits for the new factor; every copy of the old values (the transposed copy included) is rebuilt at its next use.
+    Many small members at once, with the transposed copy kept current for ``cg_batch``: ``ichol0_refactor_batch_``.
+    NotImplementedError naming the kind for any other member, TypeError for a matrix that is not a DeviceCSR, ValueError for a matrix
+    of another dimension -- before any native call."""
+    try:
+        pr, kind = _factor_native(M, "ichol0_refactor_")
+    except TypeError:
+        pr, kind = None, getattr(M, "kind", type(M).__name__)
+    if kind != "IChol0":
+        raise NotImplementedError("ichol0_refactor_: the numeric IChol(0) re-factorisation takes the \"IChol0\" kind, not %s"
+                                  % (kind if kind != "factor" else type(M).__name__))
+    if not isinstance(A, DeviceCSR):
+        raise TypeError("ichol0_refactor_ takes a DeviceCSR, got %s" % type(A).__name__)
+    if _factor_n(M, pr) != A.n:
+        raise ValueError("ichol0_refactor_: the matrix has dimension %d, the preconditioner %d" % (A.n, _factor_n(M, pr)))
+    _on_current_stream()
+    pr.ichol0_refactor_device(A.data.data_ptr(), A.indices.data_ptr(), A.indptr.data_ptr())
+    return M
+
+
+def ichol0_refactor_batch_(members, As, check=True):
+    """The numeric IChol(0) re-factorisation of MANY small SPD members in ONE kernel launch (ilupp_hip_ichol0_refactor_batch_device: one
+    workgroup per member, its rows side by side): what ``refactor_batch_`` is for ILU(0), in front of ``cg_batch``.  ``members``:
+    ``DevicePreconditioner("IChol0", ...)`` objects (``ichol0_batch`` builds many at once), host ``IChol0Preconditioner``s of the ctypes
+    binding or ``FactorOperator``s of them, each at most once; ``As[k]``: a DeviceCSR with member k's pattern and the new values.  Every
+    member's factor has the bits of a fresh construction from ``As[k]`` (and of ``ichol0_refactor_``), NaN / Inf behind a negative or
+    zero pivot included.
+    For ``cg_batch`` users: the members go into ``apply_batch_`` / ``cg_batch`` as they are; the first ``cg_batch`` builds a member's
+    transposed copy of the factor; every re-factorisation by this function after that writes the new values into that copy as well, so
+    the loop re-factorisation -> ``cg_batch`` -> re-factorisation with all members on route 0 and ``check=False`` waits for nothing on
+    the host and launches nothing per member.
+    Returns the routes: 0 = the launch; 1 = n above the launch's cap (``_native.ichol0_refactor_batch_max_n()``), a longest row of L above
+    the row cap (31 entries, fewer where 4 n + 5 120 bytes per entry do not fit into a workgroup's LDS: 28 at n = 4 000), or a member that
+    would have the launch to itself and is faster alone; 2 = an object built by the static form.  Members of routes 1 and 2 are
+    re-factorised by ``ichol0_refactor_``'s path inside the same call, with its host waits (their transposed copy is rebuilt at the next
+    use).  Inside the launch every member's pattern is PROVED equal to the analysed one (entries above the diagonal are ignored); a
+    member whose pattern differs keeps its factor and its transposed copy bitwise as they were (status 1), the others are re-factorised.
+    ``check=True`` reads the status words with one host wait and raises ValueError naming the first such member (RuntimeError for status
+    2); ``check=False`` returns ``(routes, status)``, status an int32 CUDA tensor.  A call whose launched members still hold packed or
+    level-ordered copies of the old values (single or block applies leave them) waits once before it frees them.  TypeError for a member
+    of another kind or class or a matrix that is not a DeviceCSR; ValueError for lists of unequal length, a member named twice or a
+    matrix and a member of different dimensions -- before any native call."""
+    return _refactor_batch("ichol0_refactor_batch_", "IChol0", lambda *a, **k: _native.ichol0_refactor_batch_device(*a, **k), members, As, check)
 
 
 def cg_batch(As, b, offsets, Ms, x0=None, maxiter=100, rtol=0.0, check_every=0, stats=None):

@@ -523,6 +523,38 @@ int ilupp_hip_ilu0_create_batch_device(int32_t count, const double *const *d_dat
                                        const int32_t *const *d_indptr, const int32_t *n, const int64_t *nnz, int is_csr, ilupp_precond **out,
                                        int32_t *status, int32_t *route);
 
+/* IChol(0) for MANY small SPD systems: what the five entries above are for ILU(0) (k_ichol0_refactor_batch, k_ichol0_symbolic_batch,
+ * k_ichol0_create_batch: ichol0_batch.hip; one workgroup per member, one lane per row).
+ * ilupp_hip_ichol0_refactor_device is the single numeric re-factorisation (same pattern, new values): the matrix's stored entries with
+ * column <= row must be, row by row and in stored order, the rows of the factor (entries above the diagonal are ignored, as the
+ * constructor drops them); a matrix that differs returns ILUPP_ERR_INVALID ("IChol0 refactor: the matrix does not have the analysed
+ * pattern") and leaves the factor bitwise unchanged.  The factor has the bits of ilupp_hip_ichol0_create on the same values; every copy
+ * of the old values (transposed storage, packed and level-ordered sweeps) goes and is rebuilt on first use.  A batch-built object runs
+ * the batched launch with that one member.
+ * ilupp_hip_ichol0_refactor_batch_device: arguments, ordering, sync, status words and refusals as for
+ * ilupp_hip_ilu0_refactor_batch_device ("not an IChol(0) object" for other members; nnz[i] is the matrix's number of stored entries,
+ * upper triangle included).  route: 0 = the launch; 1 = n above ilupp_hip_ichol0_refactor_batch_max_n(), a longest row of L above the
+ * row cap (at most 31 entries, and 4 n + 5 120 bytes per entry must fit into a workgroup's LDS: 28 entries at n = 4 000, 16 at
+ * n = 20 000), or a member that would have the launch to itself and has ILUPP_REFACTOR_ALONE_MIN rows or more; 2 = an object whose
+ * constructor ran the static form: routes 1 and 2 take ilupp_hip_ichol0_refactor_device's path inside the call.  The launch also writes
+ * the new values into a member's transposed storage when it has one (ilupp_hip_cg_batch_device and ilupp_hip_apply_batch_device read the
+ * factor and that copy): a route-0 member keeps both, and a steady state of re-factorisation -> ilupp_hip_cg_batch_device ->
+ * re-factorisation waits for nothing on the host and launches nothing per member.  With status 1 the factor and the transposed copy
+ * are bitwise as they were.
+ * ilupp_hip_ichol0_create_batch / _device: as ilupp_hip_ilu0_create_batch / _device (is_csr is ignored, as in ilupp_hip_ichol0_create).
+ * A route-0 object has the bits of ilupp_hip_ichol0_create's, ilupp_hip_path is "ichol0:batch"; a failing member fails as its single
+ * construction does ("matrix i of the batch: IChol0: structurally missing diagonal entry in row r"). */
+int ilupp_hip_ichol0_refactor_device(ilupp_precond *p, const double *d_data, const int32_t *d_indices, const int32_t *d_indptr);
+int ilupp_hip_ichol0_refactor_batch_device(int32_t count, ilupp_precond *const *members, const double *const *d_data,
+                                           const int32_t *const *d_indices, const int32_t *const *d_indptr, const int64_t *nnz,
+                                           int32_t *d_status, int sync, int32_t *route);
+int64_t ilupp_hip_ichol0_refactor_batch_max_n(void);
+int ilupp_hip_ichol0_create_batch(int32_t count, const double *const *data, const int32_t *const *indices, const int32_t *const *indptr,
+                                  const int32_t *n, int is_csr, ilupp_precond **out, int32_t *status, int32_t *route);
+int ilupp_hip_ichol0_create_batch_device(int32_t count, const double *const *d_data, const int32_t *const *d_indices,
+                                         const int32_t *const *d_indptr, const int32_t *n, const int64_t *nnz, int is_csr, ilupp_precond **out,
+                                         int32_t *status, int32_t *route);
+
 /* ---------------------------------------------------------------------------------------------
  * Measurement hooks used by bench.py (not part of the reference's surface).
  * Times are GPU milliseconds from hipEvents recorded on the object's stream.
@@ -537,7 +569,7 @@ typedef struct {
 } ilupp_timings;
 int ilupp_hip_get_timings(const ilupp_precond *p, ilupp_timings *t);
 /* which kernel family built this object ("ilu0:static-direct", "ilu0:static-level-major", "ilu0:level-order",
- * "ilu0:csr-program", "ilu0:csr", "ilu0:batch", "ilut", "ichol0", "icholt"): bench.py names the kernel its roofline line is about */
+ * "ilu0:csr-program", "ilu0:csr", "ilu0:batch", "ilut", "ichol0", "ichol0:batch", "icholt"): bench.py names the kernel its roofline line is about */
 const char *ilupp_hip_path(const ilupp_precond *p);
 /* how the row blocks of an ILU(0) object were found: "grid" (the pattern is a lexicographic box-grid stencil: guessed from row 0, proven
  * for every row by one streaming pass next to the lane-table kernels, grid.hip) or "general" (the pass over the pattern that finds the
