@@ -1,23 +1,9 @@
-// ilupp_amd/csrc/api.hip -- the C ABI (include/ilupp_hip.h): object lifetime, dispatch of apply()
-// to the sweep kernels, factor egress.  Mirrors the reference's binding layer (src/binding.cpp) and
-// L2 dispatch (preconditioner_implementation.h:103-111, :321-334, :381-394).
-#include <stdlib.h>
-#include <string.h>
-
-#include <algorithm>
-#include <atomic>
-#include <functional>
-#include <map>
-#include <chrono>
-#include <mutex>
-#include <set>
-#include <string>
-#include <thread>
-#include <unordered_map>
-#include <vector>
-
-#include "common.h"
-#include "pool.h"
+// ilupp_amd/csrc/api.hip -- the C ABI (include/ilupp_hip.h): object lifetime, dispatch of apply() to the sweep kernels, factor egress,
+// the constructions of an ilupp_precond, the multilevel preconditioner and the batched tables.  The pivoting preconditioners (ILUCP /
+// ILUTP) have a file of their own, api_pivot.hip; api_internal.h holds what the two files share (DESIGN_OTHER_PATHS.md section
+// 4h.13).  Mirrors the reference's binding layer (src/binding.cpp) and L2 dispatch (preconditioner_implementation.h:103-111,
+// :321-334, :381-394).
+#include "api_internal.h"
 
 namespace ilupp {
 std::mutex g_build_mu;
@@ -109,13 +95,13 @@ size_t pool_live_blocks() { return pool().live_blocks(); }
 // the vector), and an asynchronous apply makes that stream wait for the result.
 static thread_local hipStream_t g_caller_stream = nullptr;
 static thread_local bool g_caller_stream_set = false;
-static void order_after_caller(hipStream_t st, hipEvent_t ev)
+void order_after_caller(hipStream_t st, hipEvent_t ev)
 {
     if (!g_caller_stream_set) return;
     ILUPP_HIP(hipEventRecord(ev, g_caller_stream));
     ILUPP_HIP(hipStreamWaitEvent(st, ev, 0));
 }
-static void order_caller_after(hipStream_t st, hipEvent_t ev)
+void order_caller_after(hipStream_t st, hipEvent_t ev)
 {
     if (!g_caller_stream_set) return;
     ILUPP_HIP(hipEventRecord(ev, st));
@@ -124,7 +110,7 @@ static void order_caller_after(hipStream_t st, hipEvent_t ev)
 
 // indptr[n] of a device-resident matrix.  Ordered after the work the caller has submitted to its stream when one is set (the
 // producer of the arrays: a blocking copy on the null stream does not wait for a non-blocking stream)
-static int32_t read_device_nnz(const int32_t *d_indptr, int32_t n)
+int32_t read_device_nnz(const int32_t *d_indptr, int32_t n)
 {
     int32_t v = 0;
     if (g_caller_stream_set) {
@@ -166,7 +152,7 @@ static int32_t read_device_head(const int32_t *d_indptr, const int32_t *d_indice
     return stage[0];
 }
 
-static int report(const HipError &e)
+int report(const HipError &e)
 {
     char buf[512];
     snprintf(buf, sizeof(buf), "HIP error %d (%s) in %s at %s:%d", (int)e.code, hipGetErrorString(e.code), e.what, e.file, e.line);
@@ -175,97 +161,6 @@ static int report(const HipError &e)
 }
 
 }  // namespace ilupp
-
-using namespace ilupp;
-
-enum { KIND_LU = 0, KIND_LLT = 1, KIND_UTU = 2 };     // UTU (ILUC): two factors whose arrays both read as an upper CSR matrix, diagonal first
-enum { NNZ_GENERIC_LU = 0, NNZ_ILUT = 1, NNZ_LLT = 2 };
-
-namespace ilupp {
-// an object's queue: streams and events, recycled through a pool of their own (queue_take / queue_give)
-struct QueuePack {
-    hipStream_t stream = nullptr;
-    hipEvent_t ev[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};   // [4],[5]: around the factor kernel
-    hipEvent_t sev[2] = {nullptr, nullptr};           // ordering against the caller's stream
-    hipStream_t side = nullptr;                       // a second stream for work that runs NEXT to the analysis (grid.hip's proof)
-    hipEvent_t jev[2] = {nullptr, nullptr};           // fork / join of the side stream
-    int device = 0;
-};
-// what an object is, in its first three words whatever else it is made of: the CPU tests of the batched entries' refusals hand in zeroed
-// memory with n in its third word for a handle -- hence a base of its own, in front of the queue pack
-struct PrecondHead {
-    int kind = KIND_LU;
-    int nnz_mode = NNZ_GENERIC_LU;
-    int32_t n = 0;
-};
-}  // namespace ilupp
-
-struct ilupp_precond : ilupp::PrecondHead, ilupp::QueuePack {
-    bool input_csc = false;      // factors were computed on the row-major view M = A^T
-    // LU: row-major factors of M.  LLT: Lc = the factor in its stored major order, `llt_diag_last`
-    DevMat Lc, Uc;
-    bool llt_diag_last = true;
-    DevMat LcT, UcT;             // transposed storage, built on first use
-    bool haveT = false;
-    Schedule sA, sL, sU, sUT, sLT;   // factor sweep; fwd(Lc); bwd(Uc); fwd(UcT); bwd(LcT)
-    Ilu0Program prog;                // ILU(0) update program for sA (empty -> generic kernel)
-    int32_t *prog_f3 = nullptr;      // fixed-size program (short-row matrices): loader/consumer kernel
-    bool compact = false;            // descriptors/program usable (block size and grid within the encoding)
-    bool no_static_T = false;        // the static form's transposed records were tried and declined
-    bool pair_tried = false;         // static sweeps for the stored factor pair (LL^T objects) were tried
-    bool chol_static = false;        // IChol(0) was computed by the static-form kernel (st.hip)
-    int32_t *dL = nullptr, *dU = nullptr, *dUT = nullptr, *dLT = nullptr;   // solve descriptors
-    PackedSweep pkL, pkU;            // level-major packed sweeps of Lc / Uc (short-row factors)
-    PackedSweep pkUT, pkLT;          // ... of the transposed storages
-    bool pack_tried[4] = {false, false, false, false};   // Lc, Uc, UcT, LcT: packing from the descriptors was attempted
-    LevelSweep lvl[4];               // Lc, Uc, UcT, LcT in level order (long-row factors), built on first use
-    int32_t *fperm = nullptr;        // ILU(0) of a long-row matrix: its rows in level order (ilu0_lvl.hip), also the forward sweep's order
-    int32_t fperm_levels = 0;
-    LevelNumbering fperm_how;        // ... and how it was numbered (diagnostics: ilupp_hip_debug_level_order)
-    int8_t last_route[4] = {0, 0, 0, 0};   // per slot, the kernel family its last sweep ran on (SweepRoute; diagnostics)
-    FactorLM flm;                    // level-major factor kernel state (then Lc.val / Uc.val are filled on demand)
-    bool csr_vals = true;            // Lc.val / Uc.val hold the factor values
-    int64_t nnzA = 0;                // stored entries of the factored matrix (same pattern on a numeric re-factorisation; ILU(0), IChol(0))
-    int32_t max_row_len = 0;         // longest row of the factored matrix (LU objects) / of L (IChol(0)): what the batched launches route by
-    int32_t max_len_T = 0;       // longest major slice of the transposed storages
-    double *work = nullptr;      // n, all-sentinel between applies of the record-decoding / CSR sweeps (filled when the first of them runs)
-    bool work_clean = false;
-    double *xdev = nullptr;      // n, staging for host-vector apply
-    int32_t *done = nullptr;     // n
-    bool degenerate = false;     // a factor has a major slice without entries (NaN columns of an indefinite ICholT): guarded sweeps only
-    int32_t *ctrl = nullptr;     // 16 ints: [0] err, [1] ilu0 ticket (+ its err in [2]) , [4],[5] solve tickets
-    ilupp_timings tm = {0, 0, 0, 0, 0, 0};
-    bool apply_events_valid = false;
-    int max_lanes = 65536;
-    bool icholt_grid = false;    // ICholT(0, 0.0): built by the speculative static kernel for box grids (icholt_grid.hip)
-    GridDims llt_gd = {0, 0, 0};  // ... and the grid it was (the row-major copy for the sweeps follows from it)
-    bool grid_path = false;      // ILU(0): the row blocks came from grid.hip's guess (proven for every row)
-    bool no_general_retry = false;   // (ilupp_hip_ilu0_create_device_nnz) a grid guess that fails ends the attempt: the caller reads the head and starts over
-    bool verdict_clean = false;  // ctrl[8] (the verdict word of grid.hip's proof) is zero already
-    bool ctrl_armed = false;     // the control words are zero and both exchange buffers all-sentinel already (arm_apply): the next plain apply starts with its first sweep
-    bool borrowed_queue = false; // stream and events belong to another object (the levels of a multilevel preconditioner share one)
-    // block apply (ilupp_hip_apply_block*): buffers kept from one call to the next (grown, never shrunk), the route of the last one
-    double *bxp = nullptr, *by = nullptr;   // n x bkb each: the hand-over buffer and the intermediate chunk of the level route
-    int bkb = 0;
-    double *bcol = nullptr;                 // n: one column of the columns route
-    int32_t *btk = nullptr;                 // [0] a column's sweep timed out (columns route), [1 ..] two tickets per chunk (level route)
-    int64_t btk_cap = 0;
-    const char *block_path = "";
-    bool block_events = false;              // the last apply was a block apply: ev[3] .. ev[2] bracket all of it
-    hipEvent_t batch_ev = nullptr;          // a batched launch that was not waited for reads the factors (ilupp_hip_apply_batch_device, ilupp_hip_cg_batch_device): what a re-factorisation and the destruction wait for
-    // ILU(0) built by the launches of a batched first construction (ilupp_hip_ilu0_create_batch*): Lc, Uc, nnzA and max_row_len, and nothing of
-    // the single paths' analysis -- no sA / sU, no program, no packed sweeps, never the static form.  The batched launches take it as it
-    // is; the single sweeps' tables (sL, sU, dL, dU) are built from the factors' own patterns on first use (ensure_sweep_tables)
-    // IChol(0) built by ilupp_hip_ichol0_create_batch*: Lc, nnzA and max_row_len (the longest row of L) the same way; sL / dL on first use
-    bool batch_built = false;
-    bool sweeps_ready = false;
-};
-// (two bases with members: not a standard-layout type, so the order of the bases is the ABI's, not the language's -- checked here)
-#pragma clang diagnostic push
-#pragma clang diagnostic ignored "-Winvalid-offsetof"
-static_assert(offsetof(ilupp_precond, kind) == 0 && offsetof(ilupp_precond, nnz_mode) == 4 && offsetof(ilupp_precond, n) == 8,
-              "kind, nnz_mode and n are a handle's first three words");
-#pragma clang diagnostic pop
 
 namespace {
 
@@ -285,14 +180,17 @@ bool queue_take(int device, QueuePack *q)
     return false;
 }
 
+}  // namespace
+
+// (what api_pivot.hip and the templates of api_internal.h call, and what goes with it: declared ilupp:: names)
+namespace ilupp {
+
 // ... and a pack that nothing uses any more back into the pool
 void queue_give(const QueuePack &q)
 {
     std::lock_guard<std::mutex> lk(g_queues.mu);
     g_queues.free_list.push_back(q);
 }
-
-bool schedule_is_compact(const Schedule &s) { return s.B <= 32768 && s.nslots <= kGhostBase; }
 
 void destroy_obj(ilupp_precond *p)
 {
@@ -316,17 +214,6 @@ void destroy_obj(ilupp_precond *p)
     if (p->stream && !p->borrowed_queue && p->jev[1]) queue_give(*p);
     delete p;
 }
-
-// an object under construction: destroyed (its side stream synchronised, its pool blocks given back) when the construction unwinds --
-// a HIP error thrown from the middle of a factorisation or an analysis leaves nothing behind
-struct ObjGuard {
-    ilupp_precond *p;
-    explicit ObjGuard(ilupp_precond *q) : p(q) {}
-    ~ObjGuard() { if (p) { if (p->side) (void)stream_sync(p->side); destroy_obj(p); } }
-    ilupp_precond *release() { ilupp_precond *q = p; p = nullptr; return q; }
-    ObjGuard(const ObjGuard &) = delete;
-    ObjGuard &operator=(const ObjGuard &) = delete;
-};
 
 ilupp_precond *new_obj(int32_t n)
 {
@@ -354,20 +241,11 @@ ilupp_precond *new_obj(int32_t n)
     return g.release();
 }
 
-int validate(const int32_t *indptr, int32_t n)
+static int validate(const int32_t *indptr, int32_t n)
 {
     if (n <= 0 || indptr == nullptr) { set_error("matrix has size 0!"); return ILUPP_ERR_INVALID; }   // binding.cpp:80-81
     return ILUPP_OK;
 }
-
-// a device matrix this scope owns: released when it unwinds (or earlier, by whoever calls m.release())
-struct MatGuard {
-    DevMat m;
-    MatGuard() = default;
-    ~MatGuard() { m.release(); }
-    MatGuard(const MatGuard &) = delete;
-    MatGuard &operator=(const MatGuard &) = delete;
-};
 
 // a host CSR/CSC triple copied to pooled device memory, into *A (owned by the caller: a MatGuard, the solve's Guard)
 int upload(const double *data, const int32_t *indices, const int32_t *indptr, int32_t n, bool is_csr, DevMat *A)
@@ -401,9 +279,6 @@ void host_head(const int32_t *indptr, const int32_t *indices, int64_t nnz, int32
     for (int i = 0; i < 8; ++i) head[2 + i] = i < nnz ? indices[i] : -1;
 }
 
-// one sweep's lane tables: the factor it runs over, its direction, where its schedule and descriptors go
-struct SweepSpec { const DevMat *M; bool fwd; Schedule *s; int32_t **desc; };
-
 // the lane tables of one sweep, or of two (b.M != nullptr) stage by stage: cuts and schedules, tilings, slot tables, descriptors.
 // Descriptors need a compact schedule: joint = for both sweeps or for neither, else each sweep for itself.  *max_len = the longest
 // major slice of the factors; returns whether every schedule is compact.
@@ -425,7 +300,7 @@ bool sweep_tables(hipStream_t st, const ilupp_precond *p, const SweepSpec &a, co
 
 // the end of a construction: its last event, the wait for it, the times of its two phases -- [ev[0], ev[1]) is the numeric
 // factorisation and [ev[1], ev[2]) the analysis, or the other way round (IChol(0) analyses first)
-void finish_timing(ilupp_precond *p, float kernel_ms, bool analysis_first = false)
+void finish_timing(ilupp_precond *p, float kernel_ms, bool analysis_first)
 {
     ILUPP_HIP(hipEventRecord(p->ev[2], p->stream));
     ILUPP_HIP(stream_sync(p->stream));
@@ -433,6 +308,10 @@ void finish_timing(ilupp_precond *p, float kernel_ms, bool analysis_first = fals
     ILUPP_HIP(hipEventElapsedTime(analysis_first ? &p->tm.numeric_ms : &p->tm.analysis_ms, p->ev[1], p->ev[2]));
     p->tm.numeric_kernel_ms = kernel_ms;
 }
+
+}  // namespace ilupp
+
+namespace {
 
 // What a plain apply of a static ILU(0) object needs before its first sweep -- control words zero, both exchange buffers all-sentinel --
 // as ONE launch BEHIND the last wait of the call before (construction, apply): it runs while the host is on its way back to the caller,
@@ -790,8 +669,6 @@ static ApplyPlan apply_plan(int kind, bool transpose, bool input_csc, bool llt_d
 }
 static ApplyPlan apply_plan(const ilupp_precond *p, int transpose) { return apply_plan(p->kind, transpose != 0, p->input_csc, p->llt_diag_last); }
 
-#define OR_RETURN(call) do { const int rc_ = (call); if (rc_) return rc_; } while (0)
-
 // one sweep: the packed kernel when the factor has a verified level-major form, else the CSR kernels.  Either way
 // the right-hand side buffer is all-sentinel afterwards (the CSR kernels reset it row by row).
 // level-major records of a sweep straight from its CSR arrays and descriptors (any object whose rows are short enough:
@@ -917,6 +794,10 @@ static ApplyRoute prepare_apply(ilupp_precond *p, const ApplyPlan &plan, PackedS
     return ROUTE_SWEEPS;
 }
 
+}  // namespace
+
+namespace ilupp {
+
 // apply on a device vector; `transpose` as in apply_preconditioner_only(use, y)
 int apply_dev(ilupp_precond *p, double *x, int transpose)
 {
@@ -988,6 +869,10 @@ int finish_apply(ilupp_precond *p)
     if (!armed_here) arm_apply(p);
     return ILUPP_OK;
 }
+
+}  // namespace ilupp
+
+namespace {
 
 // ---- block apply: k right-hand sides, X row-major n x k, in place; every column as apply_dev gives it -----------------------------
 // Two routes.  "block:level": both sweeps of the apply are the level-order kernel (sptrsv_lvl.hip) -- the same records walked once per
@@ -1240,85 +1125,6 @@ int ilu0_refactor_single(ilupp_precond *p, const double *d_data, const int32_t *
 
 }  // namespace
 
-#define API_TRY try {
-// every construction / re-factorisation of the process, one after the other: the memory pool knows nothing of streams -- a block that
-// one construction gives back may still be in use on ITS stream when another thread's construction is handed it.  (Every
-// construction synchronises its stream before it returns, so the lock costs a concurrent caller what the construction costs.)
-#define API_TRY_BUILD try { std::lock_guard<std::mutex> build_lock_(ilupp::g_build_mu);
-#define API_CATCH                                                          \
-    } catch (const ilupp::HipError &e) { ilupp::d2h_cancel_all(); return ilupp::report(e); }        \
-    catch (const std::bad_alloc &) { ilupp::d2h_cancel_all(); ilupp::set_error("out of host memory"); return ILUPP_ERR_MEMORY; }
-
-// ---- what an entry of each shape is made of ----------------------------------------------------------------------------------------
-namespace {
-
-// A construction entry on host arrays: the triple copied to device memory this call owns, then `make(A)`.  args_ok / null_msg: what
-// else of the entry's arguments must not be null, and how the refusal reads (the multilevel entries: "null argument").
-template <class Handle, class Make>
-int create_from_host(const double *data, const int32_t *indices, const int32_t *indptr, int32_t n, bool is_csr, Handle **out, Make &&make,
-                     bool args_ok = true, const char *null_msg = "null output")
-{
-    API_TRY_BUILD
-    if (!out || !args_ok) { set_error(null_msg); return ILUPP_ERR_INVALID; }
-    *out = nullptr;
-    MatGuard A;
-    OR_RETURN(upload(data, indices, indptr, n, is_csr, &A.m));
-    return make(A.m);
-    API_CATCH
-}
-
-// ... on a matrix that already lives in HBM: the caller's arrays, borrowed for the call; indptr[n] is read back
-template <class Handle, class Make>
-int create_from_device(const double *d_data, const int32_t *d_indices, const int32_t *d_indptr, int32_t n, bool is_csr, Handle **out, Make &&make,
-                       bool args_ok = true, const char *null_msg = "null output")
-{
-    API_TRY_BUILD
-    if (!out || !args_ok) { set_error(null_msg); return ILUPP_ERR_INVALID; }
-    *out = nullptr;
-    if (n <= 0 || !d_indptr) { set_error("matrix has size 0!"); return ILUPP_ERR_INVALID; }
-    DevMat A = borrow_csr(d_data, d_indices, d_indptr, n, read_device_nnz(d_indptr, n), is_csr);
-    return make(A);
-    API_CATCH
-}
-
-// the handle and the length of the vector an apply entry is given (n: the handle's, 0 for none)
-int vector_args(const void *handle, int64_t len, int32_t n)
-{
-    if (!handle) { set_error("null preconditioner"); return ILUPP_ERR_INVALID; }
-    if (len != n) { set_error("vector has wrong size for preconditioner!"); return ILUPP_ERR_WRONG_SIZE; }   // binding.cpp:241-242
-    return ILUPP_OK;
-}
-
-// the end of a device apply queued on q: wait for it and say how it went (finish), or hand the result over to the caller's stream
-template <class Finish>
-int finish_or_hand_over(int sync, const QueuePack &q, Finish &&finish)
-{
-    if (sync) return finish();
-    order_caller_after(q.stream, q.sev[1]);
-    return ILUPP_OK;
-}
-
-// The apply of a host vector: staged in *slot (n doubles, allocated on first use), sent on the object's stream, apply(staged vector),
-// finish(), and a blocking copy back -- from `result` where the apply leaves its result elsewhere than in the staged vector.
-template <class Apply, class Finish>
-int apply_staged(hipStream_t st, double **slot, int32_t n, double *x, Apply &&apply, Finish &&finish, const double *result = nullptr)
-{
-    if (!*slot) ILUPP_HIP(pool_malloc(slot, sizeof(double) * (size_t)n));
-    ILUPP_HIP(hipMemcpyAsync(*slot, x, sizeof(double) * (size_t)n, hipMemcpyHostToDevice, st));
-    OR_RETURN(apply(*slot));
-    OR_RETURN(finish());
-    ILUPP_HIP(hipMemcpy(x, result ? result : *slot, sizeof(double) * (size_t)n, hipMemcpyDeviceToHost));
-    return ILUPP_OK;
-}
-
-// an optional host array of a handle's copy-out entry
-void get_host(void *dst, const void *src, size_t bytes)
-{
-    if (dst && bytes) ILUPP_HIP(hipMemcpy(dst, src, bytes, hipMemcpyDeviceToHost));
-}
-
-}  // namespace
-
 extern "C" {
 
 int ilupp_hip_index_size(void) { return (int)sizeof(int32_t); }
@@ -1398,13 +1204,17 @@ int ilupp_hip_ilu0_refactor_device(ilupp_precond *p, const double *d_data, const
 
 }  // extern "C"
 
+namespace ilupp {
+
 // ILUC: A = the major-order view (CSR arrays of the input, whatever its orientation: ILUC2 works on dim_along_orientation)
 // the sweeps of an object whose two factors both read as upper CSR matrices with the diagonal first (ILUC; a level of the multilevel
 // preconditioner): backward schedules and descriptors of the stored arrays (the forward sweeps run on transposed copies, built on first use)
-static void utu_analyse(ilupp_precond *p)
+void utu_analyse(ilupp_precond *p)
 {
     p->compact = sweep_tables(p->stream, p, {&p->Lc, false, &p->sL, &p->dL}, {&p->Uc, false, &p->sU, &p->dU}, true, &p->max_row_len);
 }
+
+}  // namespace ilupp
 
 static int iluc_create_common(DevMat &A, int32_t n, int is_csr, int32_t max_fill_in, double threshold, ilupp_precond **out)
 {
@@ -2015,7 +1825,6 @@ int ilupp_hip_get_timings(const ilupp_precond *p, ilupp_timings *t)
     return ILUPP_OK;
 }
 
-
 int ilupp_hip_release_cached_memory(void)
 {
     API_TRY
@@ -2227,6 +2036,10 @@ int ml_create_common(const DevMat &A, const ilupp_ml_params *ip, ilupp_ml **out)
     return ILUPP_OK;
 }
 
+}  // namespace
+
+namespace ilupp {
+
 // The workers of a batched construction (ilupp_hip_ml_create_batch, ilupp_hip_ilucp_create_batch, ilupp_hip_ilutp_create_batch): `build(i)`
 // constructs member i on the calling worker's thread and returns its code; `worst_bytes` is the device memory the largest member holds
 // while it is built.  At most 64 workers (ILUPP_BATCH_WORKERS, read per call) and as many as the memory takes: 0.6 of the free bytes, the
@@ -2297,7 +2110,7 @@ int batch_build(int32_t count, double worst_bytes, int32_t *status, const std::f
     return first;
 }
 
-}  // namespace
+}  // namespace ilupp
 
 extern "C" {
 
@@ -2508,305 +2321,8 @@ int ilupp_hip_ml_timings(const ilupp_ml *m, float *construct_ms, float *kernel_m
 
 }  // extern "C"
 
-// ===================================================================================================================
-// ILUCP: ILUCPPreconditioner, binding.cpp:343-356 -> preconditioner_implementation.h:1117-1147 -> ILUCP4 (ilucp.hip)
-// ===================================================================================================================
-// The factors come for the major-order view of the input ("Acol"): L by columns, U by rows with the pivot first and ORIGINAL column indices,
-// perm[k] = the column of step k.  With U's indices read through the inverse permutation the pair is an object of the ILUC kind (both
-// array triples upper CSR with the diagonal first), and the permuted solves of the reference (triangular_solve_perm,
-// sparse_implementation.h:4196-4218) are that object's sweeps between a gather and a scatter:
-//   COLUMN input, apply / ROW input, apply_trans:   t = (L U')^{-1} x;      x[perm[k]] = t[k]          (:4209-4218 after the plain solve with L)
-//   COLUMN input, apply_trans / ROW input, apply:   y[i] = x[perm[i]];      x = (L U')^{-T} y          (:4196-4206 before the plain solve with L^T)
-struct ilupp_ilucp {
-    int32_t n = 0;
-    bool input_csr = false;
-    bool row_kind = false;                 // ILUTP: the factors belong to the ROWS of the view (L by rows, 1 last), the plain solve comes first for ROW input
-    ilupp_precond *obj = nullptr;          // L and U' (permuted numbering), the sweeps
-    DevMat U;                              // U as the reference stores it (original column indices): what factors() hands out
-    int32_t *perm = nullptr;               // device
-    double *tmp = nullptr, *xdev = nullptr;
-    int32_t zero_pivots = 0;
-    float kernel_ms = 0.f;
-    hipEvent_t batch_ev = nullptr;         // a batched apply that was not waited for reads this member (and writes tmp): what the member's own stream waits for next
-};
-
-namespace {
-
-// the member's own stream behind the batched launch that last used it (apply_batch_run), before anything else touches tmp or the factors go
-void after_batch(ilupp_ilucp *m)
-{
-    if (!m->batch_ev) return;
-    ILUPP_HIP(hipStreamWaitEvent(m->obj->stream, m->batch_ev, 0));
-    m->batch_ev = nullptr;
-}
-
-// ILUCP: COLUMN input + apply, ROW input + apply_trans start with the plain factor; ILUTP: ROW input + apply, COLUMN input + apply_trans
-bool pivot_plain_first(const ilupp_ilucp *m, int transpose)
-{
-    return m->row_kind ? ((transpose == 0) == m->input_csr) : ((transpose != 0) == m->input_csr);
-}
-
-__global__ void k_cp_map_indices(int64_t nnz, const int32_t *__restrict__ idx, const int32_t *__restrict__ map, int32_t *__restrict__ out)
-{
-    const int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (j < nnz) out[j] = map[idx[j]];
-}
-__global__ void k_cp_invert(int32_t n, const int32_t *__restrict__ p, int32_t *__restrict__ inv)
-{
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n) inv[p[i]] = i;
-}
-__global__ void k_cp_gather(int32_t n, const double *__restrict__ x, const int32_t *__restrict__ perm, double *__restrict__ y)
-{
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n) y[i] = x[perm[i]];
-}
-__global__ void k_cp_scatter(int32_t n, const double *__restrict__ t, const int32_t *__restrict__ perm, double *__restrict__ x)
-{
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n) x[perm[i]] = t[i];
-}
-
-void ilucp_destroy(ilupp_ilucp *m)
-{
-    if (!m) return;
-    if (m->batch_ev && m->obj) (void)hipStreamWaitEvent(m->obj->stream, m->batch_ev, 0);      // (destroy_obj waits for the stream)
-    if (m->obj) destroy_obj(m->obj);
-    m->U.release();
-    for (void *q : {(void *)m->perm, (void *)m->tmp, (void *)m->xdev}) if (q) (void)pool_free(q);
-    delete m;
-}
-
-// What the constructions of the two kinds share: the handle and its object, perm and tmp, the event pair round `factor(m, p, st)`, the
-// matrix given back, `fill(m, p, st)` -- the ilupp_precond made from the factor call's result --, the times and the hand-over.
-template <class Factor, class Fill>
-int pivot_create_frame(DevMat &A, int32_t n, int is_csr, bool row_kind, ilupp_ilucp **out, Factor &&factor, Fill &&fill)
-{
-    struct Guard { ilupp_ilucp *m; ~Guard() { if (m) ilucp_destroy(m); } } g{new ilupp_ilucp};
-    ilupp_ilucp *m = g.m;
-    m->n = n; m->input_csr = is_csr != 0; m->row_kind = row_kind;
-    m->obj = new_obj(n);
-    ilupp_precond *p = m->obj;
-    hipStream_t st = p->stream;
-    ILUPP_HIP(pool_malloc(&m->perm, sizeof(int32_t) * (size_t)n));
-    ILUPP_HIP(pool_malloc(&m->tmp, sizeof(double) * (size_t)n));
-    ILUPP_HIP(hipEventRecord(p->ev[0], st));
-    const int rc = factor(m, p, st);
-    ILUPP_HIP(hipEventRecord(p->ev[1], st));
-    A.release();
-    if (rc) return rc;
-    fill(m, p, st);
-    finish_timing(p, m->kernel_ms);
-    *out = m;
-    g.m = nullptr;
-    return ILUPP_OK;
-}
-
-int ilucp_create_common(DevMat &A, int32_t n, int is_csr, int32_t max_fill_in, double threshold, double piv_tol, int32_t row_pos, double mem_factor,
-                        ilupp_ilucp **out)
-{
-    MatGuard gl;
-    return pivot_create_frame(A, n, is_csr, false, out,
-        [&](ilupp_ilucp *m, ilupp_precond *, hipStream_t st) {
-            return ilucp_factor(st, A, max_fill_in, threshold, piv_tol, row_pos, mem_factor, &gl.m, &m->U, m->perm, &m->zero_pivots, &m->kernel_ms);
-        },
-        [&](ilupp_ilucp *m, ilupp_precond *p, hipStream_t st) {
-            // U' = U with its column indices in the permuted numbering (values and pointers shared in content, own arrays)
-            DevMat Up;
-            Up.n = n; Up.nnz = m->U.nnz; Up.is_csr = true; Up.owns = true;
-            PoolBlock b_inv;
-            ILUPP_HIP(b_inv.alloc(sizeof(int32_t) * (size_t)n));
-            hipLaunchKernelGGL(k_cp_invert, dim3((n + 255) / 256), dim3(256), 0, st, n, m->perm, b_inv.as<int32_t>());
-            ILUPP_HIP(pool_malloc(&Up.ptr, sizeof(int32_t) * (size_t)(n + 1)));
-            ILUPP_HIP(pool_malloc(&Up.idx, sizeof(int32_t) * (size_t)(Up.nnz > 0 ? Up.nnz : 1)));
-            ILUPP_HIP(pool_malloc(&Up.val, sizeof(double) * (size_t)(Up.nnz > 0 ? Up.nnz : 1)));
-            ILUPP_HIP(hipMemcpyAsync(Up.ptr, m->U.ptr, sizeof(int32_t) * (size_t)(n + 1), hipMemcpyDeviceToDevice, st));
-            if (Up.nnz > 0) {
-                ILUPP_HIP(hipMemcpyAsync(Up.val, m->U.val, sizeof(double) * (size_t)Up.nnz, hipMemcpyDeviceToDevice, st));
-                hipLaunchKernelGGL(k_cp_map_indices, dim3((unsigned)((Up.nnz + 255) / 256)), dim3(256), 0, st, Up.nnz, m->U.idx, b_inv.as<int32_t>(), Up.idx);
-            }
-            ILUPP_HIP(stream_sync(st));
-            p->kind = KIND_UTU; p->nnz_mode = NNZ_GENERIC_LU; p->input_csc = false;
-            p->Lc = gl.m; p->Uc = Up;
-            gl.m = DevMat();                                            // (the object owns the arrays now)
-            utu_analyse(p);
-        });
-}
-
-// The pivoted solve of x (device, n doubles; overwritten), on the member's own stream: the plain solve then the scatter through perm, or
-// the gather then the transposed solve.  The result is in m->tmp.
-int pivot_solve(ilupp_ilucp *m, double *x, int transpose)
-{
-    const int32_t n = m->n;
-    ilupp_precond *p = m->obj;
-    hipStream_t st = p->stream;
-    if (pivot_plain_first(m, transpose)) {
-        OR_RETURN(apply_dev(p, x, 0));
-        hipLaunchKernelGGL(k_cp_scatter, dim3((n + 255) / 256), dim3(256), 0, st, n, x, m->perm, m->tmp);
-    } else {
-        hipLaunchKernelGGL(k_cp_gather, dim3((n + 255) / 256), dim3(256), 0, st, n, x, m->perm, m->tmp);
-        OR_RETURN(apply_dev(p, m->tmp, 1));
-    }
-    return ILUPP_OK;
-}
-
-}  // namespace
-
-extern "C" {
-
-int ilupp_hip_ilucp_create(const double *data, const int32_t *indices, const int32_t *indptr, int32_t n, int is_csr, int32_t max_fill_in,
-                           double threshold, double piv_tol, int32_t row_pos, double mem_factor, ilupp_ilucp **out)
-{
-    return create_from_host(data, indices, indptr, n, true, out,
-                            [&](DevMat &A) { return ilucp_create_common(A, n, is_csr, max_fill_in, threshold, piv_tol, row_pos, mem_factor, out); });
-}
-
-void ilupp_hip_ilucp_destroy(ilupp_ilucp *m) { ilucp_destroy(m); }
-
-int ilupp_hip_ilucp_apply(ilupp_ilucp *m, double *x, int64_t len, int transpose)
-{
-    API_TRY
-    OR_RETURN(vector_args(m, len, m ? m->n : 0));
-    after_batch(m);
-    return apply_staged(m->obj->stream, &m->xdev, m->n, x,
-                        [&](double *d) { return pivot_solve(m, d, transpose); },
-                        [&] { return finish_apply(m->obj); }, m->tmp);
-    API_CATCH
-}
-
-int64_t ilupp_hip_ilucp_total_nnz(const ilupp_ilucp *m) { return m ? m->obj->Lc.nnz + m->U.nnz : 0; }      /* preconditioner.h:208-209 */
-int32_t ilupp_hip_ilucp_zero_pivots(const ilupp_ilucp *m) { return m ? m->zero_pivots : 0; }
-
-/* sizes, then copies: L of the view by columns (the 1 first), U by rows (the pivot first, original column indices), the permutation */
-int ilupp_hip_ilucp_info(const ilupp_ilucp *m, int32_t *n, int64_t *nnz_l, int64_t *nnz_u, float *kernel_ms)
-{
-    if (!m) { set_error("null preconditioner"); return ILUPP_ERR_INVALID; }
-    if (n) *n = m->n;
-    if (nnz_l) *nnz_l = m->obj->Lc.nnz;
-    if (nnz_u) *nnz_u = m->U.nnz;
-    if (kernel_ms) *kernel_ms = m->kernel_ms;
-    return ILUPP_OK;
-}
-
-int ilupp_hip_ilucp_copy(const ilupp_ilucp *m, double *l_data, int32_t *l_indices, int32_t *l_indptr, double *u_data, int32_t *u_indices,
-                         int32_t *u_indptr, int32_t *perm)
-{
-    API_TRY
-    if (!m) { set_error("null preconditioner"); return ILUPP_ERR_INVALID; }
-    const ilupp_precond *p = m->obj;
-    ILUPP_HIP(stream_sync(p->stream));
-    const size_t n = (size_t)m->n;
-    get_host(l_data, p->Lc.val, sizeof(double) * (size_t)p->Lc.nnz); get_host(l_indices, p->Lc.idx, sizeof(int32_t) * (size_t)p->Lc.nnz); get_host(l_indptr, p->Lc.ptr, sizeof(int32_t) * (n + 1));
-    get_host(u_data, m->U.val, sizeof(double) * (size_t)m->U.nnz); get_host(u_indices, m->U.idx, sizeof(int32_t) * (size_t)m->U.nnz); get_host(u_indptr, m->U.ptr, sizeof(int32_t) * (n + 1));
-    get_host(perm, m->perm, sizeof(int32_t) * n);
-    return ILUPP_OK;
-    API_CATCH
-}
-
-}  // extern "C"
-
-namespace {
-
-int ilutp_create_common(DevMat &A, int32_t n, int is_csr, int32_t max_fill_in, double threshold, double piv_tol, int32_t row_pos, double mem_factor,
-                        ilupp_ilucp **out)
-{
-    return pivot_create_frame(A, n, is_csr, true, out,
-        [&](ilupp_ilucp *m, ilupp_precond *p, hipStream_t st) {
-            return ilutp_factor(st, A, max_fill_in, threshold, piv_tol, row_pos, mem_factor, &p->Lc, &p->Uc, &m->U, m->perm, &m->zero_pivots, &m->kernel_ms);
-        },
-        [&](ilupp_ilucp *, ilupp_precond *p, hipStream_t st) {
-            // an object of the ILUT kind: L by rows with its 1 last, U (permuted numbering) by rows with the pivot first
-            p->kind = KIND_LU; p->nnz_mode = NNZ_ILUT; p->input_csc = false;
-            p->compact = sweep_tables(st, p, {&p->Lc, true, &p->sL, &p->dL}, {&p->Uc, false, &p->sU, &p->dU}, true, &p->max_row_len);
-        });
-}
-
-}  // namespace
-
-extern "C" int ilupp_hip_ilutp_create(const double *data, const int32_t *indices, const int32_t *indptr, int32_t n, int is_csr, int32_t max_fill_in,
-                                      double threshold, double piv_tol, int32_t row_pos, double mem_factor, ilupp_ilucp **out)
-{
-    return create_from_host(data, indices, indptr, n, true, out,
-                            [&](DevMat &A) { return ilutp_create_common(A, n, is_csr, max_fill_in, threshold, piv_tol, row_pos, mem_factor, out); });
-}
-
-// ---- many matrices at once: the chains of the members side by side, one workgroup each (k_ilucp_batch / k_ilutp_batch) ----
-namespace {
-
-// The device memory one construction holds (ilucp_factor / ilutp_factor and the object built from their result), R = the reserved entries
-// = min(max_fill_in * n, (Integer) mem_factor * nnz), slot = n + 64:
-//   the stores of R + 1 entries             ILUCP 32 bytes per entry (U: index, link, row, value; L: index, value), ILUTP 24 (U and L: index, value)
-//   the slot tables                         ILUCP 16 int32 + 5 double tables of `slot` = 104 slot; ILUTP 5 int32 of slot + (5 int32 + 3 double) of 4 slot = 196 slot
-//   the sort buffers                        ILUCP: two key arrays of n and the in-kernel sort's of up to 2 n, 8 bytes each = 32 n;
-//                                           ILUTP: the segmented sorts of the compress step, keys and values twice over = 24 R
-//   the compressed factors                  L, U and U in the other numbering, 12 bytes per entry, each at most R entries = 36 R
-//   the uploaded matrix                     12 nnz + 4 (n + 1)
-// + 64 MiB for what does not scale with the matrix (the sorts' and scans' temporaries, the sweeps' tables, the pool's rounding).
-double pivot_member_bytes(bool tp, int32_t n, int64_t nnz, int32_t max_fill_in, double mem_factor)
-{
-    int64_t mf = max_fill_in < 1 ? 1 : max_fill_in;
-    if (mf > n) mf = n;
-    const double a = (double)mf * (double)n, b = (double)((int32_t)mem_factor) * (double)nnz;
-    const double R = a < b ? (a > 0.0 ? a : 0.0) : (b > 0.0 ? b : 0.0);
-    const double slot = (double)n + 64.0;
-    const double stores = (tp ? 24.0 : 32.0) * (R + 1.0), tables = (tp ? 196.0 : 104.0) * slot, sorts = tp ? 24.0 * R : 32.0 * (double)n;
-    return stores + tables + sorts + 36.0 * R + 12.0 * (double)nnz + 4.0 * ((double)n + 1.0) + (double)(64 << 20);
-}
-
-int pivot_create_batch(bool tp, int32_t count, const double *const *data, const int32_t *const *indices, const int32_t *const *indptr, const int32_t *n,
-                       int is_csr, int32_t max_fill_in, double threshold, double piv_tol, int32_t row_pos, double mem_factor, ilupp_ilucp **out,
-                       int32_t *status)
-{
-    if (count < 0 || !data || !indices || !indptr || !n || !out) { set_error("null argument"); return ILUPP_ERR_INVALID; }
-    for (int32_t i = 0; i < count; ++i) { out[i] = nullptr; if (status) status[i] = ILUPP_OK; }
-    if (count == 0) return ILUPP_OK;
-    double worst = 0.0;
-    for (int32_t i = 0; i < count; ++i)
-        if (indptr[i] && n[i] > 0) { const double e = pivot_member_bytes(tp, n[i], indptr[i][n[i]], max_fill_in, mem_factor); if (e > worst) worst = e; }
-    return batch_build(count, worst, status, [&](int32_t i) {
-        MatGuard A;
-        const int rc = upload(data[i], indices[i], indptr[i], n[i], true, &A.m);
-        if (rc) return rc;
-        return tp ? ilutp_create_common(A.m, n[i], is_csr, max_fill_in, threshold, piv_tol, row_pos, mem_factor, &out[i])
-                  : ilucp_create_common(A.m, n[i], is_csr, max_fill_in, threshold, piv_tol, row_pos, mem_factor, &out[i]);
-    });
-}
-
-}  // namespace
-
-extern "C" int ilupp_hip_ilucp_create_batch(int32_t count, const double *const *data, const int32_t *const *indices, const int32_t *const *indptr,
-                                            const int32_t *n, int is_csr, int32_t max_fill_in, double threshold, double piv_tol, int32_t row_pos,
-                                            double mem_factor, ilupp_ilucp **out, int32_t *status)
-{
-    API_TRY_BUILD
-    return pivot_create_batch(false, count, data, indices, indptr, n, is_csr, max_fill_in, threshold, piv_tol, row_pos, mem_factor, out, status);
-    API_CATCH
-}
-
-extern "C" int ilupp_hip_ilutp_create_batch(int32_t count, const double *const *data, const int32_t *const *indices, const int32_t *const *indptr,
-                                            const int32_t *n, int is_csr, int32_t max_fill_in, double threshold, double piv_tol, int32_t row_pos,
-                                            double mem_factor, ilupp_ilucp **out, int32_t *status)
-{
-    API_TRY_BUILD
-    return pivot_create_batch(true, count, data, indices, indptr, n, is_csr, max_fill_in, threshold, piv_tol, row_pos, mem_factor, out, status);
-    API_CATCH
-}
-
 // ---- many members applied at once: one launch, one workgroup per member (k_pivot_apply_batch, sptrsv_batch.hip) ----
 namespace {
-
-// the single apply in place on a device vector, on the member's own stream behind the caller's
-int pivot_apply_dev(ilupp_ilucp *m, double *x, int transpose)
-{
-    const int32_t n = m->n;
-    hipStream_t st = m->obj->stream;
-    after_batch(m);
-    order_after_caller(st, m->obj->sev[0]);
-    OR_RETURN(pivot_solve(m, x, transpose));
-    ILUPP_HIP(hipGetLastError());
-    ILUPP_HIP(hipMemcpyAsync(x, m->tmp, sizeof(double) * (size_t)n, hipMemcpyDeviceToDevice, st));
-    return ILUPP_OK;
-}
 
 // One array of the batched entries' scratch: `cap` elements on the device (d) and, where the instance is pinned, as many in page-locked
 // host memory (h), with the event that says the last upload from there is over (never recorded: over).  It only grows, and is never
@@ -3259,18 +2775,6 @@ int64_t ilupp_hip_cg_batch_max_n(void)
 {
     API_TRY
     return solve_batch_cap_n(BATCH_CG);
-    API_CATCH
-}
-
-int ilupp_hip_ilucp_apply_device(ilupp_ilucp *m, double *d_x, int64_t len, int transpose, int sync)
-{
-    API_TRY
-    if (!m) { set_error("null preconditioner"); return ILUPP_ERR_INVALID; }
-    if (!d_x) { set_error("null argument"); return ILUPP_ERR_INVALID; }
-    if (len != m->n) { set_error("vector has wrong size for preconditioner!"); return ILUPP_ERR_WRONG_SIZE; }
-    const int rc = pivot_apply_dev(m, d_x, transpose);
-    if (rc) return rc;
-    return finish_or_hand_over(sync, *m->obj, [&] { return finish_apply(m->obj); });
     API_CATCH
 }
 
@@ -3878,4 +3382,3 @@ int ilupp_hip_ichol0_create_batch(int32_t count, const double *const *data, cons
 }
 
 }  // extern "C"
-
