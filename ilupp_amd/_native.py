@@ -446,7 +446,8 @@ class Preconditioner:
     def level_order(self, which):
         """(perm, info) of ilupp_hip_debug_level_order: the level order of slot `which` (0 .. 3 the level-ordered copies of L, U, U^T, L^T,
         4 the factor order of an "ilu0:level-order" object) as perm[position] = row and the eight info words; perm is None where that order
-        does not exist.  Builds nothing: call an apply first (test hook)"""
+        does not exist.  info[6] is the kernel family of the last sweep over the slot, info[7] the kernel inside the descriptor family
+        (info[6] == 6: 1 k_sptrsv_lc, 2 k_sptrsv_desc; 0 for every other family).  Builds nothing: call an apply first (test hook)"""
         n = lib().ilupp_hip_dimension(self._h)
         perm = np.empty(n, dtype=np.int32)
         info = np.zeros(8, dtype=np.int32)

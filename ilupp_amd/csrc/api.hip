@@ -714,6 +714,7 @@ static int sweep(ilupp_precond *p, SweepOp op, const PackedSweep *ps, double *rh
 {
     const SweepParts s = sweep_parts(p, op);
     int8_t &route = p->last_route[op.slot];
+    p->last_desc_kernel[op.slot] = 0;
     // every sweep but the static ones hands its unknowns over through `out` (the data is the flag): all-sentinel before it runs.
     // The static sweeps never touch the work vector, so an object that only ever runs them never pays for the fill.
     if (!(ps && ps->valid && ps->stat && !p->degenerate) && !p->work_clean) {
@@ -742,7 +743,7 @@ static int sweep(ilupp_precond *p, SweepOp op, const PackedSweep *ps, double *rh
         return sptrsv_rows(p->stream, op.kind, s.M, rhs, out, ticket, err);
     }
     route = s.desc ? SWEPT_DESCRIPTORS : SWEPT_GENERIC;
-    return sptrsv(p->stream, op.kind, s.M, s.sch, s.desc, s.maxlen, rhs, out, ticket, err);
+    return sptrsv(p->stream, op.kind, s.M, s.sch, s.desc, s.maxlen, rhs, out, ticket, err, &p->last_desc_kernel[op.slot]);
 }
 // static form: records of U^T and L^T exist (built on first use; a pattern they cannot express is remembered)
 static bool static_transposed_ready(ilupp_precond *p)
@@ -814,6 +815,7 @@ int apply_dev(ilupp_precond *p, double *x, int transpose)
     if (route == ROUTE_STATIC_T) {
         // static form: the same two sweep kernels on records of U^T and L^T
         p->last_route[plan.first.slot] = p->last_route[plan.second.slot] = SWEPT_STATIC;
+        p->last_desc_kernel[plan.first.slot] = p->last_desc_kernel[plan.second.slot] = 0;
         ILUPP_HIP(hipEventRecord(p->ev[0], st));
         OR_RETURN(sptrsv_st_T(st, p->pkL, p->n, x, y, t1, err, p->pkL.ybuf, nullptr));
         ILUPP_HIP(hipEventRecord(p->ev[1], st));
@@ -821,6 +823,7 @@ int apply_dev(ilupp_precond *p, double *x, int transpose)
     } else if (route == ROUTE_STATIC_PAIR) {
         // stencil-like factors (IChol0, ICholT without fill on a mesh): the static sweep kernels on the factor's own values
         p->last_route[plan.first.slot] = p->last_route[plan.second.slot] = SWEPT_STATIC;
+        p->last_desc_kernel[plan.first.slot] = p->last_desc_kernel[plan.second.slot] = 0;
         ILUPP_HIP(hipEventRecord(p->ev[0], st));
         OR_RETURN(sptrsv_st(st, *pf, p->n, x, y, t1, err, pf->ybuf, nullptr, nullptr));
         ILUPP_HIP(hipEventRecord(p->ev[1], st));
@@ -908,6 +911,7 @@ static bool block_level_plan(ilupp_precond *p, int transpose, LevelSweep **first
     if (!(*first && *second) || p->degenerate) return false;
     // (the caller's chunks are level-order sweeps over these two slots, and they do not pass through sweep())
     p->last_route[plan.first.slot] = p->last_route[plan.second.slot] = SWEPT_LEVEL_ORDER;
+    p->last_desc_kernel[plan.first.slot] = p->last_desc_kernel[plan.second.slot] = 0;
     return true;
 }
 
@@ -1659,8 +1663,9 @@ long long ilupp_hip_debug_static_table(ilupp_precond *p, int which, int32_t *out
 
 /* diagnostics: the level order of slot `which` (0 .. 3: lvl[] = Lc, Uc, UcT, LcT; 4: the factor order of an "ilu0:level-order" object) as
  * perm[position] = row, and in info[] {levels, the sweep's w, its block, how it was numbered (0 given, 1 natural pass, 2 relaxation,
- * 3 relaxation given up then natural pass), relaxation batches, W of the natural pass, route of the last sweep over the slot (SweepRoute), 0}.
- * Builds nothing; -1 where that order does not exist (info[6] is still the slot's last route then, the rest zero) */
+ * 3 relaxation given up then natural pass), relaxation batches, W of the natural pass, route of the last sweep over the slot (SweepRoute), its kernel
+ * when that route is the descriptor kernels (1 k_sptrsv_lc, 2 k_sptrsv_desc; else 0)}.
+ * Builds nothing; -1 where that order does not exist (info[6] and [7] are still the slot's last route and kernel then, the rest zero) */
 long long ilupp_hip_debug_level_order(ilupp_precond *p, int which, int32_t *perm_out, long long cap, int32_t info[8])
 {
     try {
@@ -1675,6 +1680,7 @@ long long ilupp_hip_debug_level_order(ilupp_precond *p, int which, int32_t *perm
         } else {
             const LevelSweep &ls = p->lvl[which];
             info[6] = p->last_route[which];
+            info[7] = p->last_route[which] == SWEPT_DESCRIPTORS ? p->last_desc_kernel[which] : 0;
             if (!ls.valid || !ls.perm) return -1;
             src = ls.perm; how = ls.how;
             info[0] = ls.nlevels; info[1] = ls.w; info[2] = ls.block;

@@ -76,6 +76,7 @@ struct ilupp_precond : ilupp::PrecondHead, ilupp::QueuePack {
     int32_t fperm_levels = 0;
     LevelNumbering fperm_how;        // ... and how it was numbered (diagnostics: ilupp_hip_debug_level_order)
     int8_t last_route[4] = {0, 0, 0, 0};   // per slot, the kernel family its last sweep ran on (SweepRoute; diagnostics)
+    int8_t last_desc_kernel[4] = {0, 0, 0, 0};   // ... and, where that is SWEPT_DESCRIPTORS, the kernel: 1 k_sptrsv_lc, 2 k_sptrsv_desc (sptrsv())
     FactorLM flm;                    // level-major factor kernel state (then Lc.val / Uc.val are filled on demand)
     bool csr_vals = true;            // Lc.val / Uc.val hold the factor values
     int64_t nnzA = 0;                // stored entries of the factored matrix (same pattern on a numeric re-factorisation; ILU(0), IChol(0))

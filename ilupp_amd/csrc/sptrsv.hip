@@ -909,13 +909,15 @@ k_sptrsv_lc(const int32_t *__restrict__ ptr, const int32_t *__restrict__ desc, c
 }
 
 int sptrsv(hipStream_t st, SweepKind kind, const DevMat &M, const Schedule &sch, const int32_t *desc,
-           int32_t max_row_len, double *rhs_and_reset, double *out, int32_t *d_ticket, int32_t *d_err)
+           int32_t max_row_len, double *rhs_and_reset, double *out, int32_t *d_ticket, int32_t *d_err, int8_t *which)
 {
     // *d_ticket must be zero on entry (the caller zeroes the whole control block once per apply)
+    if (which) *which = 0;
     if (desc) {
         const unsigned grid = (unsigned)(sch.nslots / kThreads);
         // rows must fit the entry ring with room for the refill quantum; tiny systems keep the simple kernel
         if (max_row_len > 0 && max_row_len <= kEW - 2 * kEQ && M.nnz >= 16 && M.n >= 8) {
+            if (which) *which = 1;
 #define LAUNCHS(K)                                                                                           \
             do {                                                                                             \
                 ILUPP_HIP(hipFuncSetAttribute((const void *)k_sptrsv_lc<K>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLcLds)); \
@@ -949,6 +951,7 @@ int sptrsv(hipStream_t st, SweepKind kind, const DevMat &M, const Schedule &sch,
             ILUPP_HIP(hipGetLastError());
             return ILUPP_OK;
         }
+        if (which) *which = 2;
 #define LAUNCHD(K)                                                                                           \
         hipLaunchKernelGGL((k_sptrsv_desc<K>), dim3(grid), dim3(kThreads), 0, st, M.ptr, desc, M.val, rhs_and_reset, out, \
                            sch.nslots, sch.sfirst, sch.scount, sch.gtab, d_ticket, d_err)

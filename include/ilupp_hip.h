@@ -586,9 +586,10 @@ long long ilupp_hip_debug_static_table(ilupp_precond *p, int which, int32_t *out
  * (0 given: a copy of the factor order, 1 natural-order pass, 2 relaxation converged, 3 relaxation given up, then the natural-order pass),
  * [4] batches of relaxation passes run, [5] window of the natural-order pass (0: none ran), [6] kernel family of the LAST sweep over the slot
  * (0 none yet, 1 static, 2 level-major, 3 level order, 4 one lane per row in natural order, 5 the same because a factor is degenerate,
- * 6 descriptor kernels, 7 generic kernel; 0 for which = 4), [7] 0.  Builds nothing (call an apply first) and waits for the object's stream.
- * Returns the words copied (<= cap), -1 where that order does not exist (never tried, declined, dropped by a re-factorisation); info[6] is
- * valid either way.  No counterpart in binding.cpp. */
+ * 6 descriptor kernels, 7 generic kernel; 0 for which = 4), [7] the kernel inside family 6 (1 k_sptrsv_lc, 2 k_sptrsv_desc; 0 for every other
+ * family).  Builds nothing (call an apply first) and waits for the object's stream.
+ * Returns the words copied (<= cap), -1 where that order does not exist (never tried, declined, dropped by a re-factorisation); info[6] and
+ * info[7] are valid either way.  No counterpart in binding.cpp. */
 long long ilupp_hip_debug_level_order(ilupp_precond *p, int which, int32_t *perm_out, long long cap, int32_t info[8]);
 /* measurement hook: the kernels a static ILU(0) object runs, "factor;forward sweep;backward sweep"; for an LL^T object (IChol0, ICholT) its
  * factor kernel and, once an apply has built them, the sweeps of its factor pair; "" otherwise.  No counterpart in binding.cpp */

@@ -141,7 +141,7 @@ def test_ilu0(name, fmt):
 @pytest.mark.parametrize("name", ["below_floor", "nine3x700"])
 def test_objects_without_a_level_order(name):
     """n = 1 023 (below the floor of 1 024) and the 3 x 700 grid (deep, not wide): no order exists for any `which`, no sweep runs in level order
-    -- both applies ran on the descriptor kernels --, and the bits are the reference's all the same"""
+    -- both applies ran on the descriptor kernels, info[7] says on which of the two --, and the bits are the reference's all the same"""
     import ilupp_amd as ilupp
     O, ref = _oracle()
     A = R.matrix(name)
@@ -154,9 +154,12 @@ def test_objects_without_a_level_order(name):
     assert all(P.pr.level_order(s)[1][6] == 0 for s in range(4))                      # nothing swept yet
     b = G.rhs(n)
     _applies(P, ref.apply_lu(Lo, Uo, b, O.ID), ref.apply_lu(Lo, Uo, b, O.TRANSPOSE), b)
+    # (info[7], the kernel inside the descriptor family: rows and columns of up to 64 entries sweep on k_sptrsv_desc (2), of at most 9 on
+    # k_sptrsv_lc (1) -- sptrsv()'s rule, pinned at its edges by test_gpu_sweep_kernels.py)
+    kernel = 2 if name == "below_floor" else 1
     for which in range(5):
         perm, info = P.pr.level_order(which)
-        assert perm is None and not info[:6].any() and info[7] == 0, (which, info.tolist())
+        assert perm is None and not info[:6].any() and info[7] == (kernel if which < 4 else 0), (which, info.tolist())
         assert info[6] == (R.ROUTE_DESCRIPTORS if which < 4 else 0), (which, info.tolist())
 
 
