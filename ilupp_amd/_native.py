@@ -120,6 +120,7 @@ def lib():
     L.ilupp_hip_cached_bytes.restype = ctypes.c_ulonglong
     L.ilupp_hip_live_blocks.argtypes = []
     L.ilupp_hip_live_blocks.restype = ctypes.c_ulonglong
+    L.ilupp_hip_plan_cache_stats.argtypes = [_VP]
     L.ilupp_hip_total_nnz.argtypes = [_VP]
     L.ilupp_hip_total_nnz.restype = ctypes.c_int64
     for name in ("memory_used_calculations", "memory_allocated_calculations", "memory"):
@@ -228,7 +229,7 @@ ABI_SYMBOLS = [
     "ilupp_hip_exists", "ilupp_hip_special_info", "ilupp_hip_print_info", "ilupp_hip_dimension",
     "ilupp_hip_num_factors", "ilupp_hip_factor_info", "ilupp_hip_factor_copy",
     "ilupp_hip_factor_device_ptrs", "ilupp_hip_get_timings", "ilupp_hip_ilu0_refactor_device",
-    "ilupp_hip_sync", "ilupp_hip_release_cached_memory", "ilupp_hip_set_cache_limit", "ilupp_hip_cached_bytes", "ilupp_hip_live_blocks", "ilupp_hip_ilut_create_device", "ilupp_hip_ichol0_create_device",
+    "ilupp_hip_sync", "ilupp_hip_release_cached_memory", "ilupp_hip_set_cache_limit", "ilupp_hip_cached_bytes", "ilupp_hip_live_blocks", "ilupp_hip_plan_cache_stats", "ilupp_hip_ilut_create_device", "ilupp_hip_ichol0_create_device",
     "ilupp_hip_icholt_create_device", "ilupp_hip_set_caller_stream", "ilupp_hip_path", "ilupp_hip_analysis_path", "ilupp_hip_debug_static_table", "ilupp_hip_debug_level_order", "ilupp_hip_kernel_names", "ilupp_hip_spmv_device",
     "ilupp_hip_iluc_create", "ilupp_hip_iluc_create_device",
     "ilupp_hip_ml_default_params", "ilupp_hip_ml_create", "ilupp_hip_ml_create_device", "ilupp_hip_ml_destroy", "ilupp_hip_ml_apply",
@@ -775,8 +776,18 @@ def live_blocks():
     return int(lib().ilupp_hip_live_blocks())
 
 
+def plan_cache_stats():
+    """the parked analysis plans of box-grid ILU(0) objects (include/ilupp_hip.h: ilupp_hip_plan_cache_stats):
+    (plans parked now, constructions that adopted one, constructions that found none, plans that left unused)"""
+    out = (ctypes.c_ulonglong * 4)()
+    rc = lib().ilupp_hip_plan_cache_stats(out)
+    if rc:
+        _raise(rc)
+    return tuple(int(v) for v in out)
+
+
 def release_cached_memory():
-    """hand the device buffers the library keeps for the next construction back to the driver"""
+    """hand the device buffers the library keeps for the next construction back to the driver (parked plans included)"""
     rc = lib().ilupp_hip_release_cached_memory()
     if rc:
         _raise(rc)

@@ -180,6 +180,106 @@ bool queue_take(int device, QueuePack *q)
     return false;
 }
 
+// ---- parked plans (plan_cache.h) ----------------------------------------------------------------------------------------------------
+// Everything the analysis of a box-grid ILU(0) object makes from the three dimensions alone -- both schedules with their slot tables, the
+// lane, chunk, exchange and link tables of both sweeps, the factor kernel's lane records -- is MOVED out of such an object when it is
+// destroyed and into the next object of the same (device, n, nnz, nx, ny, nz): a caller that builds the preconditioner of one mesh anew
+// every time step runs k_grid_starts / k_grid_lanes / k_grid_scat and their read-back once.  The tables hold slots, offsets and counts,
+// no address of a value buffer: records, level-major vectors and exchange buffers go back to the pool as ever and come out of it again
+// by the sizes the plan keeps (st.hip: st_alloc_values).  What makes adopted tables valid for the matrix at hand is what makes built ones
+// valid: the proof of the pattern, which runs in every construction.
+struct GridPlan {
+    Schedule sA, sU;
+    PackedSweep pkL, pkU;           // (table members and sizes; no records, vectors, exchange buffers)
+    FactorLM flm;                   // (xbase, the flags, the predicted and the found sizes)
+    int32_t max_row_len = 0;
+    bool compact = false;
+    int64_t nnzL = 0, nnzU = 0;
+};
+typedef PlanCache<GridPlan> Plans;
+void plan_block_release(void *h) { (void)pool_free(h); }
+Plans &plans()
+{
+    (void)pool();                        // (made first, destroyed last: the plans that are parked when the process ends go back to it)
+    static Plans g(plan_block_release, 4);
+    return g;
+}
+// ILUPP_NO_PLAN_CACHE=1: nothing is parked or adopted; nor under a switch that selects an older piece of the analysis
+bool plan_cache_on()
+{
+    static const bool on = []() {
+        for (const char *name : {"ILUPP_NO_PLAN_CACHE", "ILUPP_NO_GRID", "ILUPP_NO_SPEC", "ILUPP_NO_WXF", "ILUPP_NO_WR", "ILUPP_SD_VERIFY", "ILUPP_CLASSIC_ANALYSIS"})
+            if (getenv(name) != nullptr) return false;
+        for (const char *name : {"ILUPP_GRID_TABLES", "ILUPP_GRID_LINK", "ILUPP_GRID_SCAT"}) {
+            const char *e = getenv(name);
+            if (e && atoi(e) == 0) return false;
+        }
+        return true;
+    }();
+    return on;
+}
+// every pointer of the five structures that is a table of the plan (f: called with a reference to each)
+template <class F>
+void plan_tables(Schedule &sa, Schedule &su, PackedSweep &pl, PackedSweep &pu, FactorLM &flm, F &&f)
+{
+    for (Schedule *s : {&sa, &su}) { f(s->start); f(s->slot2blk); f(s->blk2slot); f(s->sfirst); f(s->scount); f(s->exported); f(s->gtab); }
+    for (PackedSweep *k : {&pl, &pu}) { f(k->ltab); f(k->skew); f(k->wtab); f(k->flags); f(k->uslot); f(k->ysrc); f(k->xe); f(k->xw); f(k->dump); }
+    f(flm.xbase);
+}
+// An object on the headline path -- grid analysis, static direct feed, the wave-exchange factor kernel with predicted sizes -- whose
+// tables are what the analysis made: built (or adopted) by a construction that went well, and since then nothing but plain applies that
+// were waited for and went well, and factors() (which turns the records back and forth and makes CSR arrays of the object's own: values,
+// and they go to the pool; the record format is a flag the next factor kernel sets).  Everything else is excluded: a re-factorisation, a
+// transposed apply, an apply nobody waited for, a batched launch in flight, a call that ended in an error.
+bool plan_parkable(const ilupp_precond *p)
+{
+    if (!plan_cache_on() || !p->plan_ok || p->apply_open || p->batch_ev || p->batch_built || p->borrowed_queue || p->icholt_grid || p->degenerate) return false;
+    if (!(p->kind == KIND_LU && p->nnz_mode == NNZ_GENERIC_LU && p->grid_path && p->grid_gd.nx > 0 && p->stream)) return false;
+    const FactorLM &f = p->flm;
+    if (!(f.built && f.stat && f.direct && f.wxf && f.spec && f.xbase) || f.pkA || f.xch || f.xcount) return false;
+    if (!(p->pkL.valid && p->pkU.valid && p->pkL.stat && p->pkU.stat) || p->pkL.pkT || p->pkU.pkT || p->pkL.pair || p->pkU.pair) return false;
+    return ilu0_numeric_st_is_wx(p->pkL, f);
+}
+PlanKey plan_key(int device, int32_t n, int64_t nnz, const GridDims &g)
+{
+    PlanKey k;
+    k.device = device; k.n = n; k.nnz = nnz; k.nx = g.nx; k.ny = g.ny; k.nz = g.nz;
+    return k;
+}
+// destroy_obj, behind its wait for the stream: the tables leave the object (which releases the rest as ever) for the cache -- or for the
+// pool, where the cache refuses them: the plans' bytes count against the pool's limit, with what the pool keeps
+void plan_park(ilupp_precond *p)
+{
+    Plans::Plan plan;
+    plan.key = plan_key(p->device, p->n, p->nnzA, p->grid_gd);
+    GridPlan &g = plan.payload;
+    g.sA = p->sA; g.sU = p->sU; g.pkL = p->pkL; g.pkU = p->pkU; g.flm = p->flm;
+    g.max_row_len = p->max_row_len; g.compact = p->compact; g.nnzL = p->Lc.nnz; g.nnzU = p->Uc.nnz;
+    for (PackedSweep *k : {&g.pkL, &g.pkU}) {
+        k->pk = nullptr; k->ybuf = nullptr; k->xlm = nullptr; k->xch = nullptr; k->pkT = nullptr;
+        k->fmt = k->fmtT = 0; k->xch_armed = false;
+    }
+    plan_tables(g.sA, g.sU, g.pkL, g.pkU, g.flm, [&](auto *&t) { if (t) plan.blocks.push_back(PlanBlock{t, pool().live_bytes(t)}); });
+    plan_tables(p->sA, p->sU, p->pkL, p->pkU, p->flm, [](auto *&t) { t = nullptr; });
+    const size_t limit = pool().limit(), kept = pool_cached_bytes();
+    (void)plans().park(std::move(plan), limit > kept ? limit - kept : 0);
+}
+// ilu0_factor, with the dimensions guessed: the parked plan of that shape becomes this object's analysis (false: none is parked)
+bool plan_adopt(ilupp_precond *p, const DevMat &A, const GridDims &gd)
+{
+    if (!plan_cache_on() || p->batch_built || p->borrowed_queue) return false;
+    Plans::Plan plan;
+    if (!plans().take(plan_key(p->device, A.n, A.nnz, gd), &plan)) return false;
+    const GridPlan &g = plan.payload;
+    p->pkL.release(); p->pkU.release(); p->flm.release(); p->sA.release(); p->sU.release();
+    p->sA = g.sA; p->sU = g.sU; p->pkL = g.pkL; p->pkU = g.pkU; p->flm = g.flm;      // (the object owns the tables from here on, whatever follows)
+    p->max_row_len = g.max_row_len; p->compact = g.compact;
+    for (DevMat *M : {&p->Lc, &p->Uc}) { M->n = A.n; M->is_csr = true; M->owns = true; }
+    p->Lc.nnz = g.nnzL; p->Uc.nnz = g.nnzU;
+    st_alloc_values(&p->pkL, &p->pkU);
+    return true;
+}
+
 }  // namespace
 
 // (what api_pivot.hip and the templates of api_internal.h call, and what goes with it: declared ilupp:: names)
@@ -196,7 +296,8 @@ void destroy_obj(ilupp_precond *p)
 {
     if (!p) return;
     if (p->batch_ev && p->stream) (void)hipStreamWaitEvent(p->stream, p->batch_ev, 0);      // (a batched launch may still read the factors)
-    if (p->stream) (void)stream_sync(p->stream);   // pooled blocks may be handed out again at once
+    const bool idle = p->stream && stream_sync(p->stream) == hipSuccess;   // pooled blocks may be handed out again at once
+    if (idle && plan_parkable(p)) plan_park(p);       // (the dimension-derived tables: to the next object of this shape)
     p->Lc.release(); p->Uc.release(); p->LcT.release(); p->UcT.release();
     p->sA.release(); p->sL.release(); p->sU.release(); p->sUT.release(); p->sLT.release();
     p->prog.release();
@@ -350,6 +451,7 @@ static int ilu0_numeric_any(ilupp_precond *p, const DevMat &A, bool have_prog, f
 {
     hipStream_t st = p->stream;
     p->ctrl_armed = false; p->pkL.xch_armed = p->pkU.xch_armed = false;      // (the factor kernels use the control words and the forward exchange)
+    p->plan_ok = false;                  // (a construction that goes well sets it again: ilu0_factor; a re-factorisation never)
     int rc = ILUPP_ERR_UNSUPPORTED;
     if (p->flm.built) {
         // (flm.built means the static form: round 1's record-decoding level-major FACTOR kernel, which only matrices the static form takes
@@ -384,15 +486,20 @@ static int ilu0_numeric_any(ilupp_precond *p, const DevMat &A, bool have_prog, f
 // lives in LDS, so they lose little next to the 4.6 TB/s stream of the proof; DESIGN.md section 4.0.2 has the other placements.)
 // (a grid whose factor launch holds one workgroup per CU: that launch proves the pattern itself, on the CUs whose tile has ended --
 // st_wave.hip: wa_tail_proof --, and nothing runs on the side stream)
-static bool grid_attempt_begin(ilupp_precond *p, const DevMat &A, const int32_t *head, GridProof *gp, int max_wgs)
+// (*adopted: a plan of that shape was parked -- plan_adopt -- and is this object's analysis now: schedules, slot tables and lane tables are
+// there, no launch was made for them; where the factor launch will hold the proof, its preparing launch clears the verdict word as well --
+// st_wave.hip: k_wa_prepare --, and nothing at all is queued here)
+static bool grid_attempt_begin(ilupp_precond *p, const DevMat &A, const int32_t *head, GridProof *gp, int max_wgs, bool *adopted)
 {
+    *adopted = false;
     if (head == nullptr || p->side == nullptr || !grid_guess(A.n, A.nnz, head, &gp->g)) return false;
     gp->how = wx_tail_proof_wanted(gp->g.ny, gp->g.nz) ? GridProof::FACTOR_LAUNCH : GridProof::SIDE_STREAM;
     gp->side = p->side; gp->fork_ev = p->jev[0]; gp->join_ev = p->jev[1]; gp->d_verdict = p->ctrl + 8;
+    *adopted = plan_adopt(p, A, gp->g);
     if (p->verdict_clean) p->verdict_clean = false;
-    else ILUPP_HIP(hipMemsetAsync(gp->d_verdict, 0, sizeof(int32_t), p->stream));
+    else if (!(*adopted && gp->how == GridProof::FACTOR_LAUNCH)) ILUPP_HIP(hipMemsetAsync(gp->d_verdict, 0, sizeof(int32_t), p->stream));
     if (gp->how == GridProof::SIDE_STREAM) gp->queue(p->stream, A);
-    grid_schedules(p->stream, A, gp->g, &p->Lc, &p->Uc, &p->sA, &p->sU, &p->max_row_len, max_wgs);
+    if (!*adopted) grid_schedules(p->stream, A, gp->g, &p->Lc, &p->Uc, &p->sA, &p->sU, &p->max_row_len, max_wgs);
     return true;
 }
 // one pass over A's pattern: row counts of L and U, diagonal check, and the factor-sweep schedules (L shares A's
@@ -414,7 +521,7 @@ static void drop_grid_guess(ilupp_precond *p, const GridProof &gp, const char *w
     p->pkL.release(); p->pkU.release(); p->flm.release();
     p->sA.release(); p->sU.release();
     p->sA = Schedule(); p->sU = Schedule();
-    p->grid_path = false;
+    p->grid_path = false; p->plan_ok = false;
     if (forget) grid_shape_forget(forget->n, forget->nnz, forget->idx);
 }
 
@@ -507,8 +614,11 @@ int ilu0_factor(ilupp_precond *p, const DevMat &A, const int32_t *head)
     ILUPP_HIP(hipEventRecord(p->ev[0], st));
     const int max_wgs = p->max_lanes / kThreads;
     GridProof gp;
-    bool grid = grid_attempt_begin(p, A, head, &gp, max_wgs), lm = false;
+    bool adopted = false;
+    bool grid = grid_attempt_begin(p, A, head, &gp, max_wgs, &adopted), lm = false;
     for (;;) {
+        // (a parked plan of this shape: the three steps below ran for the object that left it)
+        if (adopted) { lm = true; break; }
         if (!grid) { const int rc = general_symbolic(p, A, max_wgs); if (rc) return rc; }
         // (a grid's slot tables are filled together with its lane templates: grid.hip, k_grid_lanes; ILUPP_GRID_TABLES=0: by the general kernels)
         static const bool grid_tables = []() { const char *e = getenv("ILUPP_GRID_TABLES"); return !(e && atoi(e) == 0); }();
@@ -552,10 +662,13 @@ int ilu0_factor(ilupp_precond *p, const DevMat &A, const int32_t *head)
     if (grid_bad != 0) {
         // the matrix only began like a grid (or a size was mispredicted): the general pass runs
         drop_grid_guess(p, gp, grid_bad == 2 ? "sizes mispredicted" : "pattern differs", &A);
+        if (adopted) plans().note_dropped();       // (the tables went to the pool with the guess: the plan is gone, not parked again)
         if (p->no_general_retry) return ILUPP_ERR_UNSUPPORTED;
         return ilu0_factor(p, A, nullptr);
     }
     if (grid && rc == ILUPP_OK) grid_shape_remember(A.n, A.nnz, gp.g, A.idx);
+    // (what destroy_obj may park: plan_parkable)
+    if (grid && wx_numeric && rc == ILUPP_OK) { p->grid_gd = gp.g; p->plan_ok = true; p->apply_open = false; }
     factor_timing(p, grid && wx_numeric && rc == ILUPP_OK, waited ? p->ev[5] : p->ev[2], kms);
     if (rc == ILUPP_ERR_TIMEOUT) set_error("ILU0: dependency wait timed out (invalid structure?)");
     if (rc == ILUPP_OK) settle_ctrl(p);
@@ -566,6 +679,8 @@ int ilu0_factor(ilupp_precond *p, const DevMat &A, const int32_t *head)
 void ensure_csr_values(ilupp_precond *p)
 {
     if (p->csr_vals) return;
+    // (an object its plan can still be parked from -- plan_parkable -- stays one: what follows rewrites records and makes CSR arrays of the
+    // object's own, and reads the tables)
     if (p->pkL.stat) {
         // (the passes below read records by template position: st_wave.hip's class-aligned ones are turned back for them)
         const int fmt = p->pkL.fmt;
@@ -786,6 +901,7 @@ static ApplyRoute prepare_apply(ilupp_precond *p, const ApplyPlan &plan, PackedS
 {
     ensure_sweep_tables(p);                          // (a batch-built ILU(0) object's first single sweep)
     if (!plan.transposed()) return ROUTE_SWEEPS;
+    p->plan_ok = false;                  // (transposed records or storages are made)
     if (p->kind == KIND_LU) {
         p->pkL.xch_armed = p->pkU.xch_armed = false;
         if (static_transposed_ready(p)) return ROUTE_STATIC_T;
@@ -803,6 +919,7 @@ namespace ilupp {
 int apply_dev(ilupp_precond *p, double *x, int transpose)
 {
     hipStream_t st = p->stream;
+    p->apply_open = true;                                // (until a finish_apply has waited for it and found no error)
     order_after_caller(st, p->sev[0]);
     if (p->ctrl_armed) p->ctrl_armed = false;            // (zero already: arm_apply)
     else ILUPP_HIP(hipMemsetAsync(p->ctrl, 0, 64, st));
@@ -870,6 +987,7 @@ int finish_apply(ilupp_precond *p)
         return ILUPP_ERR_TIMEOUT;
     }
     if (!armed_here) arm_apply(p);
+    p->apply_open = false;
     return ILUPP_OK;
 }
 
@@ -1834,6 +1952,7 @@ int ilupp_hip_get_timings(const ilupp_precond *p, ilupp_timings *t)
 int ilupp_hip_release_cached_memory(void)
 {
     API_TRY
+    plans().drop_all();                  // (first: the plans' blocks go to the pool, the pool's to the driver)
     pool_trim();
     { std::lock_guard<std::mutex> build_lock_(ilupp::g_build_mu); mwm_release_stage(); }
     return ILUPP_OK;
@@ -1843,12 +1962,27 @@ int ilupp_hip_release_cached_memory(void)
 int ilupp_hip_set_cache_limit(unsigned long long bytes)
 {
     API_TRY
+    // (the parked plans count against the limit with the pool's kept blocks; they leave first, the least recently parked first)
+    const size_t kept = pool_cached_bytes();
+    plans().shrink_to((size_t)bytes > kept ? (size_t)bytes - kept : 0);
     pool_set_limit((size_t)bytes);
     return ILUPP_OK;
     API_CATCH
 }
-unsigned long long ilupp_hip_cached_bytes(void) { return (unsigned long long)pool_cached_bytes(); }
-unsigned long long ilupp_hip_live_blocks(void) { return (unsigned long long)pool_live_blocks(); }
+// (a parked plan is cache: its bytes are cached bytes, its blocks -- which the pool has handed out -- are nobody's live blocks)
+unsigned long long ilupp_hip_cached_bytes(void) { return (unsigned long long)(pool_cached_bytes() + plans().bytes()); }
+unsigned long long ilupp_hip_live_blocks(void)
+{
+    const size_t live = pool_live_blocks(), parked = plans().blocks();
+    return (unsigned long long)(live > parked ? live - parked : 0);
+}
+int ilupp_hip_plan_cache_stats(unsigned long long out[4])
+{
+    if (!out) return ILUPP_ERR_INVALID;
+    const Plans::Stats s = plans().stats();
+    out[0] = s.parked; out[1] = s.taken; out[2] = s.missed; out[3] = s.dropped;
+    return ILUPP_OK;
+}
 
 int ilupp_hip_sync(ilupp_precond *p)
 {

@@ -24,6 +24,7 @@
 
 #include "common.h"
 #include "pool.h"
+#include "plan_cache.h"
 
 namespace ilupp {
 extern std::mutex g_build_mu;      // api.hip
@@ -94,6 +95,11 @@ struct ilupp_precond : ilupp::PrecondHead, ilupp::QueuePack {
     bool icholt_grid = false;    // ICholT(0, 0.0): built by the speculative static kernel for box grids (icholt_grid.hip)
     GridDims llt_gd = {0, 0, 0};  // ... and the grid it was (the row-major copy for the sweeps follows from it)
     bool grid_path = false;      // ILU(0): the row blocks came from grid.hip's guess (proven for every row)
+    // the plan cache (api.hip: plan_park): the grid this object's tables were made for; plan_ok: they are still what the analysis made and
+    // nothing but plain, waited-for applies has happened since (set by the construction, cleared by whatever else touches the object);
+    // apply_open: an apply was queued and no finish_apply has yet said that it went well
+    GridDims grid_gd = {0, 0, 0};
+    bool plan_ok = false, apply_open = false;
     bool no_general_retry = false;   // (ilupp_hip_ilu0_create_device_nnz) a grid guess that fails ends the attempt: the caller reads the head and starts over
     bool verdict_clean = false;  // ctrl[8] (the verdict word of grid.hip's proof) is zero already
     bool ctrl_armed = false;     // the control words are zero and both exchange buffers all-sentinel already (arm_apply): the next plain apply starts with its first sweep

@@ -693,6 +693,8 @@ void lm_link_y(hipStream_t st, const Schedule &fwd, PackedSweep *pl, PackedSweep
 // st.hip
 bool st_analyse_ilu0(hipStream_t st, const DevMat &A, const Schedule &fwd, const Schedule &bwd, PackedSweep *pl,
                      PackedSweep *pu, FactorLM *f, const GridDims *grid = nullptr);
+// records, level-major vectors and exchange buffers of two analysed sweeps, from the sizes pl and pu hold (what st_analyse_ilu0 ends with)
+void st_alloc_values(PackedSweep *pl, PackedSweep *pu);
 int ilu0_numeric_st(hipStream_t st, const DevMat &A, PackedSweep *pl, PackedSweep *pu, FactorLM *f, int32_t *d_ctrl, float *kernel_ms,
                     hipEvent_t e0, hipEvent_t e1, GridProof *gp);
 bool ilu0_numeric_st_is_wx(const PackedSweep &pl, const FactorLM &f);     // ... will launch the wave-exchange factor kernel (ilu0_numeric_wx)

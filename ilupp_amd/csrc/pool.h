@@ -179,6 +179,8 @@ public:
     size_t hits() const { return hits_; }
     size_t misses() const { return misses_; }
     bool is_live(void *p) const { std::lock_guard<std::mutex> lk(mu_); return live_.count(p) != 0; }
+    // the bytes a live block was served with (0: not a live block)
+    size_t live_bytes(void *p) const { std::lock_guard<std::mutex> lk(mu_); auto it = live_.find(p); return it == live_.end() ? 0 : it->second.bytes; }
 
 private:
     struct Key {                                             // (device, bytes, owner)

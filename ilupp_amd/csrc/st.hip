@@ -1592,13 +1592,20 @@ static bool st_accept(const char *what, int64_t n, int nwg, const int32_t *hl, c
 // workgroup).  One schedule: the records and the exchange buffer, which is all the factor kernel touches
 static void st_alloc(PackedSweep *pl, PackedSweep *pu, const int32_t *hl, const int32_t *hu, const int32_t *xtot)
 {
-    const size_t slots = (size_t)hl[1] + 4 * (size_t)pl->nwg;          // one spare chunk per wave: where waves / lanes without a row at a step store
     pl->nchunks = hl[1]; pl->max_chunks = hl[2];
     pl->xch_len = (int64_t)xtot[0] + xtot[1] + 64;
-    ILUPP_HIP(pool_malloc(&pl->pk, slots * 2048));
     if (pu) {
         pu->nchunks = hu[1]; pu->max_chunks = hu[2];
         pu->xch_len = (int64_t)xtot[2] + xtot[3] + 64;
+    }
+    st_alloc_values(pl, pu);
+}
+// ... the buffers themselves, from the sizes kept in pl and pu (api.hip: an object that adopts a parked plan has the sizes and no buffers)
+void st_alloc_values(PackedSweep *pl, PackedSweep *pu)
+{
+    const size_t slots = (size_t)pl->nchunks + 4 * (size_t)pl->nwg;    // one spare chunk per wave: where waves / lanes without a row at a step store
+    ILUPP_HIP(pool_malloc(&pl->pk, slots * 2048));
+    if (pu) {
         ILUPP_HIP(pool_malloc(&pu->pk, slots * 2048));                 // (the forward schedule's order: see k_sptrsv_st)
         // vectors travel level-major: the right-hand side and the intermediate vector in the L sweep's order (pl->ybuf, in place), the
         // result in the U sweep's (pu->xlm)

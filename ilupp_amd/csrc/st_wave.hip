@@ -1755,11 +1755,12 @@ const char *wx_factor_kernel_name()
 // proof beside it -- is what the analysis phase of a box grid lasts): the control words zero, the tiles' progress and claim words -1,
 // the exchange buffer all-sentinel
 __global__ void k_wa_prepare(int32_t *__restrict__ ctrl, int32_t *__restrict__ prog, const int nprog, unsigned long long *__restrict__ xch,
-                             const long long nx)
+                             const long long nx, const int clear_verdict)
 {
     const long long i0 = (long long)blockIdx.x * blockDim.x + threadIdx.x, stride = (long long)gridDim.x * blockDim.x;
     if (i0 < 4) ctrl[i0] = 0;
     if (i0 == 9) ctrl[9] = 0;                                          // (the tail proof's claim counter)
+    if (i0 == 8 && clear_verdict) ctrl[8] = 0;                         // (the proof's verdict word, when no proof is under way that may have written it)
     for (long long i = i0; i < nprog; i += stride) prog[i] = -1;
     for (long long i = i0; i < nx; i += stride) xch[i] = kSentinel;
 }
@@ -1822,8 +1823,10 @@ int ilu0_numeric_wx(hipStream_t st, const DevMat &A, PackedSweep *pl, PackedSwee
         long long blocks = ((long long)pl->xch_len + 255) / 256;
         if (blocks > 4096) blocks = 4096;
         if (blocks < 1) blocks = 1;
+        // (a proof that this launch or a launch behind it will hold: nothing queued so far writes the verdict word, it is cleared here)
+        const int clear_verdict = gp && gp->how == GridProof::FACTOR_LAUNCH && gp->queued == GridProof::NOBODY ? 1 : 0;
         hipLaunchKernelGGL(k_wa_prepare, dim3((unsigned)blocks), dim3(256), 0, st, d_ctrl, a.prog, 2 * (int)pl->nwg,
-                           reinterpret_cast<unsigned long long *>(pl->xch), (long long)pl->xch_len);
+                           reinterpret_cast<unsigned long long *>(pl->xch), (long long)pl->xch_len, clear_verdict);
     }
     {
         // does the chip hold every workgroup of the launch at once?  (Then the prefetchers stay behind their own tile's end, for the

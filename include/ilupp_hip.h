@@ -601,14 +601,25 @@ int ilupp_hip_ilu0_refactor_device(ilupp_precond *p, const double *d_data, const
 int ilupp_hip_sync(ilupp_precond *p);
 /* The library keeps freed device buffers (up to a limit, the oldest go first) for the next construction: a factorisation that is
  * repeated asks for the same sizes again and hipMalloc / hipFree of multi-GB buffers cost more than the kernels.  This hands them
- * back to the driver (no counterpart in binding.cpp: the reference's buffers are host memory). */
+ * back to the driver (no counterpart in binding.cpp: the reference's buffers are host memory).
+ * The cache also holds PARKED PLANS: when an ILU(0) object of a box-grid matrix is destroyed, the tables its analysis made from the grid's
+ * dimensions alone (schedules, lane tables: tens of MB at 256^3, none of the value records) are kept for the next ILU(0) object of the
+ * same device, size, entry count and dimensions, which then skips that part of the analysis (the proof of the pattern still runs every
+ * time).  A few plans per device, the least recently parked leaves first; only objects that saw nothing but their construction and
+ * plain, waited-for applies leave one.  ILUPP_NO_PLAN_CACHE=1 turns it off.  This call drops every parked plan as well. */
 int ilupp_hip_release_cached_memory(void);
 /* the limit of that cache in bytes (default 48 GiB, or ILUPP_CACHE_LIMIT_MB; 0 = keep nothing); blocks over the new limit are
- * handed back at once.  A process that shares the GPU with other allocators sets this before its first factorisation. */
+ * handed back at once.  A process that shares the GPU with other allocators sets this before its first factorisation.
+ * Parked plans count against the limit: one that would exceed it is not parked, and a lower limit drops plans first. */
 int ilupp_hip_set_cache_limit(unsigned long long bytes);
-/* bytes currently kept in the cache / blocks currently handed out (diagnostics; a leak shows as blocks that never come back) */
+/* bytes currently kept in the cache, parked plans included / blocks currently handed out, parked plans' blocks NOT included
+ * (diagnostics; a leak shows as blocks that never come back) */
 unsigned long long ilupp_hip_cached_bytes(void);
 unsigned long long ilupp_hip_live_blocks(void);
+/* diagnostics of the parked plans: out[0] = plans parked now, out[1] = constructions that adopted one, out[2] = constructions of a
+ * box-grid shape that found none, out[3] = plans that left unused (evicted, released with the cache, over the limit, or adopted for a
+ * matrix that then failed the proof).  No counterpart in binding.cpp. */
+int ilupp_hip_plan_cache_stats(unsigned long long out[4]);
 
 #ifdef __cplusplus
 }
