@@ -134,7 +134,6 @@ __device__ __forceinline__ void tp_chain(const TpArgs &A)
         int ns = 0;
         // ---- row i of the matrix with the positions of its columns (:46-52) ----
         const int r0 = A.Ap[i], r1 = A.Ap[i + 1];
-        if (r1 - r0 > A.cap) TP_FAIL(12);
         double acc = 0.0;
         for (int base = r0; base < r1; base += 64) {
             const int e = base + lane;
@@ -145,6 +144,7 @@ __device__ __forceinline__ void tp_chain(const TpArgs &A)
             const int pc = (act && e > r0) ? A.Ai[e - 1] : -1;
             const bool first = act && c != pc;                                      // (a column stored twice: one slot, the last value)
             const unsigned long long mask = __ballot(first);
+            if (ns + __popcll(mask) > A.cap) TP_FAIL(12);                           // (slots, not stored entries: the copies of a column share one)
             const int s = ns + __popcll(mask & lt) - (first ? 0 : 1);
             if (first) { A.sidx[s] = c; A.skey[s] = key; A.sstate[s] = 0; A.occ[c] = s; }
             if (act && (e + 1 >= r1 || A.Ai[e + 1] != c)) A.sval[s] = v;

@@ -1,4 +1,4 @@
-"""Recorded answers of the REAL reference for the live comparisons of tests/test_oracle_*.py (tests/ref_replay.py): runs those tests
+"""Recorded answers of the REAL reference for the live comparisons of tests/test_oracle_*.py and tests/test_pivot_ref.py (tests/ref_replay.py): runs those tests
 against oracle/_ref and keeps, for every call they make of it, a digest of the call and a digest of the reference's answer.
 
 Run where the reference's sources are present:   make -C oracle ref && python tests/golden/make_golden_live.py    -> tests/golden/ref_live.npz"""
@@ -18,7 +18,7 @@ TESTS = ["test_oracle_golden.py::test_oracle_vs_reference_live", "test_oracle_go
          "test_oracle_iluc.py::test_restatement_vs_reference_live", "test_oracle_ilucp.py::test_oracle_against_reference_live",
          "test_oracle_ilucp.py::test_mem_factor_is_truncated_before_the_product", "test_oracle_ilutp.py::test_oracle_against_reference_live",
          "test_oracle_ml.py::test_oracle_against_reference_live", "test_oracle_ml.py::test_oracle_against_reference_fuzz",
-         "test_oracle_mlp.py::test_oracle_against_reference_live"]
+         "test_oracle_mlp.py::test_oracle_against_reference_live", "test_pivot_ref.py::test_oracle_agrees_with_the_reference"]
 
 
 def main():

@@ -1,6 +1,6 @@
 """The real reference (oracle/_ref) where it is built, and its recorded answers where it is not.
 
-The live comparisons of the oracle's restatement with the reference's own C++ (tests/test_oracle_*.py) reach the reference through
+The live comparisons of the oracle's restatement with the reference's own C++ (tests/test_oracle_*.py, tests/test_pivot_ref.py) reach the reference through
 ref().  Where oracle/_ref is built (that needs the reference's sources) that is the library itself.  Elsewhere the restatement
 computes each call, and its answer is handed back only if it is the reference's: tests/golden/ref_live.npz
 (tests/golden/make_golden_live.py) holds, for every call the tests make of the reference, a digest of the call and a digest of

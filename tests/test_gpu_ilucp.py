@@ -61,8 +61,8 @@ def test_fuzz_against_the_oracle():
         try:
             Q = O.ILUCP(O.orc(), a, **kw)
         except O.OracleError as e:
-            assert e.code == O.ERR_MEMORY
-            with pytest.raises(RuntimeError, match="Insufficient memory reserved"):
+            message = {O.ERR_MEMORY: "ILUCP4: Insufficient memory reserved"}[e.code]          # (ILUCP4 has no other error)
+            with pytest.raises(RuntimeError, match=message):
                 _native_cp(a, kw["fill_in"], kw["threshold"], kw["piv_tol"], kw["rp"], kw["mem_factor"])
             failures += 1
             continue

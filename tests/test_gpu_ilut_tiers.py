@@ -14,7 +14,6 @@ import os
 import re
 import subprocess
 import sys
-import tempfile
 import time
 
 import numpy as np
@@ -24,6 +23,7 @@ import scipy.sparse as sp
 import golden_util as G
 import ilut_cases as C
 import ilut_ref as R
+from capture_util import Env as _Env, Stderr as _Stderr
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -34,41 +34,6 @@ _RE_BIG = re.compile(r"\[ilupp\] ilut_wp: largest capacity class, (\d+) waves, s
 _SWITCHES = ("ILUPP_ILUT_WAVES", "ILUPP_ILUT_NO_TIER2", "ILUPP_ILUT_CAP", "ILUPP_ILUT_BIG", "ILUPP_DEBUG")
 
 _dead = []          # the first child process that faulted, aborted or ran into its time limit: nothing is started after it
-
-
-class _Stderr:
-    """what the library writes to file descriptor 2 during the block (the child processes have no capfd)"""
-
-    def __enter__(self):
-        sys.stderr.flush()
-        self.tmp = tempfile.TemporaryFile()
-        self.saved = os.dup(2)
-        os.dup2(self.tmp.fileno(), 2)
-        return self
-
-    def __exit__(self, *a):
-        sys.stderr.flush()
-        os.dup2(self.saved, 2)
-        os.close(self.saved)
-        self.tmp.seek(0)
-        self.err = self.tmp.read().decode("utf-8", "replace")
-        self.tmp.close()
-
-
-class _Env:
-    def __init__(self, **kw):
-        self.kw = kw
-
-    def __enter__(self):
-        self.old = {k: os.environ.get(k) for k in self.kw}
-        os.environ.update(self.kw)
-
-    def __exit__(self, *a):
-        for k, v in self.old.items():
-            if v is None:
-                del os.environ[k]
-            else:
-                os.environ[k] = v
 
 
 def seen_route(err):

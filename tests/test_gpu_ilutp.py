@@ -61,8 +61,8 @@ def test_fuzz_against_the_oracle():
         try:
             Q = O.ILUTP(O.orc(), a, **kw)
         except O.OracleError as e:
-            assert e.code in (O.ERR_MEMORY, O.ERR_ZERO_PIVOT)
-            with pytest.raises(RuntimeError, match="memory reserved was insufficient|zero pivot"):
+            message = {O.ERR_MEMORY: "ILUTP2: memory reserved was insufficient", O.ERR_ZERO_PIVOT: "ILUTP2: encountered zero pivot in row"}[e.code]
+            with pytest.raises(RuntimeError, match=message):
                 _native_cp(a, kw["fill_in"], kw["threshold"], kw["piv_tol"], kw["rp"], kw["mem_factor"])
             failures += 1
             continue
@@ -77,7 +77,7 @@ def test_fuzz_against_the_oracle():
         assert np.array_equal(x, Q.apply(b), equal_nan=True), (it, kw)
         x = b.copy(); P.apply_trans(x)
         assert np.array_equal(x, Q.apply(b, O.TRANSPOSE), equal_nan=True), (it, kw)
-    assert failures >= 0
+    assert failures >= 1 or off            # (the default seed: four memory errors)
 
 
 def test_class_like_the_reference_tests():
