@@ -280,8 +280,8 @@ def apply_batch(preconditioners, vectors, transpose=False):
 
     TypeError for a member of any other class, ValueError for lists of unequal length or a vector of the wrong length -- all before any
     native call; an empty list gives ``[]``.  Out of scope: the device classes (``ilupp_amd.device.DevicePreconditioner`` has no "ILUTP" /
-    "ILUCP" kind; device vectors go through ``ilupp_amd.device.pivot_apply_batch_``) and a batched apply of
-    :class:`ILUppPreconditioner` objects.  Many systems SOLVED side by side, the whole preconditioned BiCGstab loop in one launch:
+    "ILUCP" kind; device vectors go through ``ilupp_amd.device.pivot_apply_batch_``).  :class:`ILUppPreconditioner` objects have a
+    batched apply of their own: :func:`ml_apply_batch`.  Many systems SOLVED side by side, the whole preconditioned BiCGstab loop in one launch:
     ``ilupp_amd.device.bicgstab_batch`` (these classes, the non-pivoting ones and members without a preconditioner, mixed at will)."""
     preconditioners, vectors = list(preconditioners), list(vectors)
     for P in preconditioners:
@@ -297,6 +297,35 @@ def apply_batch(preconditioners, vectors, transpose=False):
         out.append(y)
     if out:
         _backend.pivot_apply_batch([P.pr for P in preconditioners], out, bool(transpose))
+    return out
+
+
+def ml_apply_batch(preconditioners, vectors, transpose=False):
+    """``[P @ b for P, b in zip(preconditioners, vectors)]`` (with ``transpose=True``: ``P.T @ b``) for :class:`ILUppPreconditioner`
+    instances of the ctypes binding -- built one by one or by :meth:`ILUppPreconditioner.batch`, of either family -- as ONE native call:
+    one kernel launch applies all members side by side, one workgroup each walking its member's levels up and down with the unknowns of
+    a sweep in LDS (``ilupp_hip_ml_apply_batch``), where the loop pays six to eight small launches per level and member.  Returns a list
+    of new arrays, bit for bit what the loop gives; the inputs are not modified.  A member too large for the kernel
+    (``_native.ml_apply_batch_max_n()``; a member of n > 4 096 that would have the launch to itself), or with a level whose factors
+    have an empty row, is applied alone inside the same call.
+
+    TypeError for a member of any other class, ValueError for lists of unequal length or a vector of the wrong length -- all before any
+    native call; an empty list gives ``[]``.  Device vectors: ``ilupp_amd.device.ml_apply_batch_``; many systems SOLVED side by side
+    with multilevel members: ``ilupp_amd.device.bicgstab_batch`` with ``ilupp_amd.device.MultilevelOperator`` members."""
+    preconditioners, vectors = list(preconditioners), list(vectors)
+    for P in preconditioners:
+        if not isinstance(P, ILUppPreconditioner) or not isinstance(getattr(P, "pr", None), _native.MultilevelPreconditioner):
+            raise TypeError("ml_apply_batch takes ILUppPreconditioner instances of the ctypes binding, got %s" % type(P).__name__)
+    if len(preconditioners) != len(vectors):
+        raise ValueError("%d preconditioners but %d vectors" % (len(preconditioners), len(vectors)))
+    out = []
+    for P, b in zip(preconditioners, vectors):
+        y = np.array(b, dtype=np.float64, copy=True).ravel()
+        if y.shape[0] != P.shape[0]:
+            raise ValueError("vector of %d elements for a preconditioner of dimension %d" % (y.shape[0], P.shape[0]))
+        out.append(y)
+    if out:
+        _native.ml_apply_batch([P.pr for P in preconditioners], out, bool(transpose))
     return out
 
 

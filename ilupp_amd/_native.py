@@ -153,6 +153,12 @@ def lib():
     L.ilupp_hip_ml_apply_device.argtypes = [_VP, _VP, ctypes.c_int64, ctypes.c_int, ctypes.c_int]
     L.ilupp_hip_ml_apply_part_device.argtypes = [_VP, _VP, ctypes.c_int64, ctypes.c_int, ctypes.c_int, ctypes.c_int]
     L.ilupp_hip_ml_sync.argtypes = [_VP]
+    L.ilupp_hip_ml_apply_batch_device.argtypes = [ctypes.c_int32, ctypes.POINTER(_VP), _VP, ctypes.POINTER(ctypes.c_int64), ctypes.c_int,
+                                                  ctypes.c_int, _I32P]
+    L.ilupp_hip_ml_apply_batch.argtypes = [ctypes.c_int32, ctypes.POINTER(_VP), ctypes.POINTER(_VP), ctypes.POINTER(ctypes.c_int64),
+                                           ctypes.c_int, _I32P]
+    L.ilupp_hip_ml_apply_batch_max_n.argtypes = []
+    L.ilupp_hip_ml_apply_batch_max_n.restype = ctypes.c_int64
     L.ilupp_hip_ilucp_create.argtypes = [_VP, _VP, _VP, ctypes.c_int32, ctypes.c_int, ctypes.c_int32, ctypes.c_double, ctypes.c_double, ctypes.c_int32,
                                          ctypes.c_double, ctypes.POINTER(_VP)]
     L.ilupp_hip_ilutp_create.argtypes = L.ilupp_hip_ilucp_create.argtypes
@@ -187,6 +193,13 @@ def lib():
                                                   ctypes.c_double, ctypes.c_int32, _VP, _VP, _VP, _VP, ctypes.c_int, _I32P]
     L.ilupp_hip_bicgstab_batch_max_n.argtypes = []
     L.ilupp_hip_bicgstab_batch_max_n.restype = ctypes.c_int64
+    L.ilupp_hip_bicgstab_batch_ml_device.argtypes = [ctypes.c_int32, ctypes.POINTER(_VP), ctypes.POINTER(_VP), ctypes.POINTER(_VP),
+                                                     ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(_VP), ctypes.POINTER(_VP),
+                                                     ctypes.POINTER(_VP), ctypes.POINTER(ctypes.c_int64), _VP, _VP, _VP,
+                                                     ctypes.POINTER(ctypes.c_int64), _VP, ctypes.c_int64, ctypes.c_int32, ctypes.c_double,
+                                                     ctypes.c_int32, _VP, _VP, _VP, _VP, ctypes.c_int, _I32P]
+    L.ilupp_hip_bicgstab_batch_ml_max_n.argtypes = []
+    L.ilupp_hip_bicgstab_batch_ml_max_n.restype = ctypes.c_int64
     L.ilupp_hip_ilu0_refactor_batch_device.argtypes = [ctypes.c_int32, ctypes.POINTER(_VP), ctypes.POINTER(_VP), ctypes.POINTER(_VP),
                                                        ctypes.POINTER(_VP), ctypes.POINTER(ctypes.c_int64), _VP, ctypes.c_int, _I32P]
     L.ilupp_hip_ilu0_refactor_batch_max_n.argtypes = []
@@ -233,13 +246,15 @@ ABI_SYMBOLS = [
     "ilupp_hip_icholt_create_device", "ilupp_hip_set_caller_stream", "ilupp_hip_path", "ilupp_hip_analysis_path", "ilupp_hip_debug_static_table", "ilupp_hip_debug_level_order", "ilupp_hip_kernel_names", "ilupp_hip_spmv_device",
     "ilupp_hip_iluc_create", "ilupp_hip_iluc_create_device",
     "ilupp_hip_ml_default_params", "ilupp_hip_ml_create", "ilupp_hip_ml_create_device", "ilupp_hip_ml_destroy", "ilupp_hip_ml_apply",
-    "ilupp_hip_ml_apply_device", "ilupp_hip_ml_apply_part_device", "ilupp_hip_ml_sync", "ilupp_hip_ml_levels", "ilupp_hip_ml_total_nnz", "ilupp_hip_ml_level_info",
+    "ilupp_hip_ml_apply_device", "ilupp_hip_ml_apply_part_device", "ilupp_hip_ml_apply_batch_device", "ilupp_hip_ml_apply_batch",
+    "ilupp_hip_ml_apply_batch_max_n", "ilupp_hip_ml_sync", "ilupp_hip_ml_levels", "ilupp_hip_ml_total_nnz", "ilupp_hip_ml_level_info",
     "ilupp_hip_ml_level_copy", "ilupp_hip_ml_timings", "ilupp_hip_solve", "ilupp_hip_ml_create_batch",
     "ilupp_hip_ilucp_create", "ilupp_hip_ilucp_destroy", "ilupp_hip_ilucp_apply", "ilupp_hip_ilucp_total_nnz", "ilupp_hip_ilucp_zero_pivots",
     "ilupp_hip_ilucp_info", "ilupp_hip_ilucp_copy", "ilupp_hip_ilutp_create", "ilupp_hip_ilucp_create_batch", "ilupp_hip_ilutp_create_batch",
     "ilupp_hip_ilucp_apply_device", "ilupp_hip_pivot_apply_batch_device", "ilupp_hip_pivot_apply_batch", "ilupp_hip_pivot_apply_batch_max_n",
     "ilupp_hip_pivot_bicgstab_batch_device", "ilupp_hip_apply_batch_device", "ilupp_hip_cg_batch_device", "ilupp_hip_cg_batch_max_n",
-    "ilupp_hip_bicgstab_batch_device", "ilupp_hip_bicgstab_batch_max_n",
+    "ilupp_hip_bicgstab_batch_device", "ilupp_hip_bicgstab_batch_max_n", "ilupp_hip_bicgstab_batch_ml_device",
+    "ilupp_hip_bicgstab_batch_ml_max_n",
     "ilupp_hip_ilu0_refactor_batch_device", "ilupp_hip_ilu0_refactor_batch_max_n",
     "ilupp_hip_ilu0_create_batch", "ilupp_hip_ilu0_create_batch_device",
     "ilupp_hip_ichol0_refactor_device", "ilupp_hip_ichol0_refactor_batch_device", "ilupp_hip_ichol0_refactor_batch_max_n",
@@ -1004,16 +1019,15 @@ def _member_handles(members):
     return H
 
 
-def pivot_apply_batch(members, arrays, transpose):
-    """the applies of `members` (PivotedPreconditioner objects of either kind) on `arrays` (writable contiguous float64 vectors, one per
-    member), in place, with ONE launch for all members that fit (ilupp_hip_pivot_apply_batch); returns the route of every member
-    (0 = the launch, 1 = too large, 2 = a factor with an empty row: the single apply inside the same call)"""
+def _apply_batch_host(entry, handles, members, arrays, transpose):
+    """one call of a batched host apply's C entry (by name) with the handle array `handles(members)` on `arrays` (writable contiguous
+    float64 vectors, one per member), in place; returns the routes"""
     cnt = len(members)
     if len(arrays) != cnt:
         raise ValueError("%d preconditioners but %d vectors" % (cnt, len(arrays)))
     if cnt == 0:
         return []
-    H = _member_handles(members)
+    H = handles(members)
     X, N = (_VP * cnt)(), (ctypes.c_int64 * cnt)()
     keep = []
     for k, (m, x) in enumerate(zip(members, arrays)):
@@ -1026,10 +1040,17 @@ def pivot_apply_batch(members, arrays, transpose):
         keep.append(a)
         X[k], N[k] = a.ctypes.data, a.shape[0]
     route = (ctypes.c_int32 * cnt)()
-    rc = lib().ilupp_hip_pivot_apply_batch(cnt, H, X, N, 1 if transpose else 0, route)
+    rc = getattr(lib(), entry)(cnt, H, X, N, 1 if transpose else 0, route)
     if rc:
         _raise(rc)
     return list(route)
+
+
+def pivot_apply_batch(members, arrays, transpose):
+    """the applies of `members` (PivotedPreconditioner objects of either kind) on `arrays` (writable contiguous float64 vectors, one per
+    member), in place, with ONE launch for all members that fit (ilupp_hip_pivot_apply_batch); returns the route of every member
+    (0 = the launch, 1 = too large, 2 = a factor with an empty row: the single apply inside the same call)"""
+    return _apply_batch_host("ilupp_hip_pivot_apply_batch", _member_handles, members, arrays, transpose)
 
 
 def _apply_batch_device(entry, handles, members, dptr, offsets, transpose, sync):
@@ -1052,6 +1073,33 @@ def pivot_apply_batch_device(members, dptr, offsets, transpose=False, sync=True)
     """the same on device vectors: member k's vector starts `offsets[k]` doubles behind `dptr` (ilupp_hip_pivot_apply_batch_device),
     ordered on the caller's stream (set_caller_stream); returns the routes"""
     return _apply_batch_device("ilupp_hip_pivot_apply_batch_device", _member_handles, members, dptr, offsets, transpose, sync)
+
+
+def _ml_handles(members):
+    H = (_VP * len(members))()
+    for k, m in enumerate(members):
+        if not isinstance(m, MultilevelPreconditioner):
+            raise TypeError("a batched apply of the multilevel class takes multilevel ILU++ preconditioners, got %s" % type(m).__name__)
+        H[k] = m._h
+    return H
+
+
+def ml_apply_batch(members, arrays, transpose):
+    """the applies of `members` (MultilevelPreconditioner objects) on `arrays` (writable contiguous float64 vectors, one per member), in
+    place, with ONE launch for all members that fit (ilupp_hip_ml_apply_batch); returns the route of every member (0 = the launch,
+    1 = too large, 2 = a level's factor with an empty row: the single apply inside the same call)"""
+    return _apply_batch_host("ilupp_hip_ml_apply_batch", _ml_handles, members, arrays, transpose)
+
+
+def ml_apply_batch_device(members, dptr, offsets, transpose=False, sync=True):
+    """the same on device vectors: member k's vector starts `offsets[k]` doubles behind `dptr` (ilupp_hip_ml_apply_batch_device),
+    ordered on the caller's stream (set_caller_stream); returns the routes"""
+    return _apply_batch_device("ilupp_hip_ml_apply_batch_device", _ml_handles, members, dptr, offsets, transpose, sync)
+
+
+def ml_apply_batch_max_n():
+    """the largest n a multilevel member may have to take the batched launch on the current device (ILUPP_BATCH_APPLY_MAX_N applied)"""
+    return _batch_max_n("ilupp_hip_ml_apply_batch_max_n")
 
 
 def _matrix_arrays(matrices):
@@ -1217,3 +1265,36 @@ def bicgstab_batch_max_n():
     """the largest n a member may have to be solved in bicgstab_batch_device's launch on the current device (ILUPP_BATCH_APPLY_MAX_N
     applied)"""
     return _batch_max_n("ilupp_hip_bicgstab_batch_max_n")
+
+
+def bicgstab_batch_ml_device(members, ns, matrices, b_ptr, x0_ptr, x_ptr, offsets, work_ptr, work_doubles, maxiter, rtol, check_every,
+                             iterations_ptr, flags_ptr, rr_ptr, init_ptr, sync=True):
+    """bicgstab_batch_device for a batch that may hold MultilevelPreconditioner objects next to everything that function takes
+    (ilupp_hip_bicgstab_batch_ml_device: a launch with a multilevel member runs the kernel's second instantiation, in which a member's
+    apply is a choice on its descriptor).  Returns the routes: members of route 1 or 2 are NOT solved."""
+    cnt = len(members)
+    if len(matrices) != cnt or len(offsets) != cnt or len(ns) != cnt:
+        raise ValueError("%d preconditioners but %d dimensions, %d matrices and %d offsets" % (cnt, len(ns), len(matrices), len(offsets)))
+    if cnt == 0:
+        return []
+    HP, HV, HM = (_VP * cnt)(), (_VP * cnt)(), (_VP * cnt)()
+    for k, m in enumerate(members):
+        if m is None:
+            continue
+        if isinstance(m, PivotedPreconditioner):
+            HV[k] = m._h
+        elif isinstance(m, Preconditioner):
+            HP[k] = m._h
+        elif isinstance(m, MultilevelPreconditioner):
+            HM[k] = m._h
+        else:
+            raise TypeError("a batched solve takes ILUCP / ILUTP / ILU0 / ILUT / ILUC / IChol0 / ICholT / multilevel ILU++ preconditioners "
+                            "or None, got %s" % type(m).__name__)
+    return _solve_batch("ilupp_hip_bicgstab_batch_ml_device", (HP, HV, HM), ns, matrices, b_ptr, x0_ptr, x_ptr, offsets, work_ptr,
+                        work_doubles, maxiter, rtol, check_every, iterations_ptr, flags_ptr, rr_ptr, init_ptr, sync)
+
+
+def bicgstab_batch_ml_max_n():
+    """the largest n a member may have to be solved in a launch of bicgstab_batch_ml_device that holds a multilevel member, on the
+    current device (ILUPP_BATCH_APPLY_MAX_N applied)"""
+    return _batch_max_n("ilupp_hip_bicgstab_batch_ml_max_n")

@@ -2053,8 +2053,13 @@ int ml_apply_dev(ilupp_ml *m, double *x, int transpose, int part = 0)       // p
 {
     ilupp_precond *p0 = m->obj[0];
     hipStream_t st = p0->stream;
-    order_after_caller(st, p0->sev[0]);
     const int nl = (int)m->obj.size();
+    // (a batched launch that was not waited for still reads the levels and writes m->buf: ilupp_hip_ml_apply_batch_device)
+    if (p0->batch_ev) {
+        ILUPP_HIP(hipStreamWaitEvent(st, p0->batch_ev, 0));
+        for (int i = 0; i < nl; ++i) m->obj[(size_t)i]->batch_ev = nullptr;
+    }
+    order_after_caller(st, p0->sev[0]);
     for (int i = 0; i < nl; ++i) ILUPP_HIP(hipMemsetAsync(m->obj[(size_t)i]->ctrl, 0, 64, st));
     ILUPP_HIP(hipEventRecord(p0->ev[0], st));
     const bool tr = transpose != 0;
@@ -2531,16 +2536,26 @@ struct BatchScratch {
     BatchBuf<RefactorDesc> rtable{64, true};
     BatchBuf<CreateInfo> cinfo{64, true};         // a construction's symbolic records, read back through the pinned copy
     BatchBuf<int32_t> cstat{64, false};           // ... and the status words of its create launch
+    // the two tables of a batched multilevel apply (member records, and the level records of all of them), each cached on its own
+    BatchBuf<MlApplyDesc> mltable{64, true};
+    BatchBuf<MlLevelDesc> mllevels{64, true};
+    // a solve with multilevel members: their level records (one table, uploaded through mllevels) and, per workgroup of the launch, where
+    // its member's records start there (-1: not a multilevel member)
+    std::vector<MlLevelDesc> lfresh;
+    std::vector<int32_t> ml_first;
 };
 
 // One member as the batched kernels see it, whatever class it comes from: the object that holds the two triangles, the pivoting
 // permutation (or none) and the side it stands on, and the n doubles the one-array path hands its first sweep's result over in.  A
 // pivoting member brings its own tmp and is ordered through its owner's batch_ev; a non-pivoting one (owner == nullptr) gets a slice of
 // the scratch's block, which only launches on the scratch's stream ever touch, and is ordered through p->batch_ev.  p == nullptr: a
-// member without a preconditioner (the CG solve only).
+// member without a preconditioner (the CG solve only).  ml: a multilevel member of the BiCGstab solve (p stays null: its levels are objects
+// of their own, described by batch_describe from what the batched multilevel apply reads, ordered through every level's batch_ev, its
+// scratch the object's own buf).
 struct BatchMember {
     ilupp_precond *p = nullptr;
     ilupp_ilucp *owner = nullptr;
+    ilupp_ml *ml = nullptr;
     const int32_t *perm = nullptr;
     bool plain_first = true;
     double *tmp = nullptr;
@@ -2558,6 +2573,20 @@ BatchMember batch_member(ilupp_precond *p, int transpose)
     BatchMember v;
     v.p = p; v.plain_first = transpose == 0; v.n = p->n;
     return v;
+}
+BatchMember batch_member(ilupp_ml *m, int transpose)
+{
+    BatchMember v;
+    v.ml = m; v.plain_first = transpose == 0; v.n = m->n;
+    return v;
+}
+// the object whose stream a member's own work is queued on (a multilevel member: the first level's, which the others borrow)
+ilupp_precond *batch_stream_obj(const BatchMember &v) { return v.ml ? v.ml->obj[0] : v.p; }
+// a launch that reads the member is recorded in `ev` (nullptr: it has been waited for)
+void batch_mark(const BatchMember &v, hipEvent_t ev)
+{
+    if (v.ml) { for (ilupp_precond *p : v.ml->obj) p->batch_ev = ev; return; }
+    if (hipEvent_t *slot = v.batch_ev()) *slot = ev;
 }
 template <class Handle>
 std::vector<BatchMember> batch_members(int32_t count, Handle *const *members, int transpose)
@@ -2593,9 +2622,10 @@ int64_t batch_env_cap(int64_t cap_n)
 int64_t batch_apply_max_n() { return batch_env_cap((int64_t)(pivot_apply_batch_lds_cap() / 8)); }
 
 // ... to a solver's launch: the cap of the apply's launch, lowered by what the dot scratch takes
-int64_t solve_batch_cap_n(BatchSolver solver)
+// (ml: the launch of k_bicgstab_batch<true>, which a batch with a multilevel member runs: that instantiation's own cap)
+int64_t solve_batch_cap_n(BatchSolver solver, bool ml = false)
 {
-    const int64_t a = batch_apply_max_n(), b = solve_batch_max_n(solver);
+    const int64_t a = batch_apply_max_n(), b = solve_batch_max_n(solver, ml);
     return a < b ? a : b;
 }
 
@@ -2618,24 +2648,55 @@ void routes_out(const std::vector<int32_t> &from, int32_t *route)
     if (route) std::copy(from.begin(), from.end(), route);
 }
 
+// One record per level of a multilevel member, appended to `out`, from what ml_apply_dev reads: apply_plan(KIND_UTU, ...) and
+// sweep_parts on the level's object for the two halves (the caller has run ensure_transposed on every level, as utu_half does), the
+// level's diagonals and the two index arrays of the direction.
+void ml_level_records(ilupp_ml *m, bool tr, std::vector<MlLevelDesc> *out)
+{
+    const ApplyPlan plan = apply_plan(KIND_UTU, tr, false, false);
+    for (size_t k = 0; k < m->obj.size(); ++k) {
+        const MlLevelDev &l = m->dev[k];
+        const DevMat &M1 = sweep_parts(m->obj[k], plan.first).M, &M2 = sweep_parts(m->obj[k], plan.second).M;
+        MlLevelDesc e;
+        memset(&e, 0, sizeof(e));
+        e.n = l.n; e.kind1 = plan.first.kind; e.kind2 = plan.second.kind;
+        e.ptr1 = M1.ptr; e.idx1 = M1.idx; e.val1 = M1.val;
+        e.ptr2 = M2.ptr; e.idx2 = M2.idx; e.val2 = M2.val;
+        e.D = l.D; e.Dl = l.Dl; e.Dr = l.Dr;
+        e.gather = tr ? l.pc : l.pr; e.take = tr ? l.ipr : l.ipc;
+        out->push_back(e);
+    }
+}
+
 // Route and describe the members of a batched launch: route 0 = the launch (n <= cap_n, object not degenerate), 1 = too large, 2 = degenerate.
 // S.fresh / S.launched receive the descriptors and member numbers of route 0, from the tables the single apply uses (apply_plan,
 // sweep_parts); xoff = offsets[i].  A pivoting member is prepared as its single apply prepares it (prepare_apply).  A non-pivoting one
 // needs only the two CSR triangles with their values (ensure_csr_values: a static-form ILU(0) leaves them unwritten; ensure_transposed
 // when the plan reads slot 2 or 3): one whose single apply would take a static form goes to the launch all the same -- every route has
 // the reference's bits -- and no static analysis runs merely to describe it.  Its tmp is a slice of the scratch's block (batch_tmp).
-void batch_describe(BatchScratch &S, int32_t count, const BatchMember *members, const int64_t *offsets, int64_t cap_n)
+// take_ml == false: the launch is one without multilevel members -- they stay out of it whatever their n (route 1; the caller knows better).
+void batch_describe(BatchScratch &S, int32_t count, const BatchMember *members, const int64_t *offsets, int64_t cap_n, bool take_ml = true)
 {
     S.route.assign((size_t)count, 0); S.status.assign((size_t)count, ILUPP_OK); S.h_err.assign((size_t)count, 0);
-    S.launched.clear(); S.fresh.clear();
+    S.launched.clear(); S.fresh.clear(); S.lfresh.clear(); S.ml_first.clear();
     for (int32_t i = 0; i < count; ++i) {
         const BatchMember &v = members[i];
         ilupp_precond *p = v.p;
-        if (v.n > cap_n) { S.route[(size_t)i] = 1; continue; }
+        if (v.n > cap_n || (v.ml && !take_ml)) { S.route[(size_t)i] = 1; continue; }
         PivotApplyDesc d;
         memset(&d, 0, sizeof(d));
         d.n = v.n; d.xoff = offsets[i];
-        if (p) {
+        int32_t ml_first = -1;
+        if (v.ml) {
+            // a multilevel member (k_bicgstab_batch<true>): plain_first == 2, kind1 levels from ptr1 (set by batch_stage, when the level
+            // table's place on the device is known), kind2 the direction, tmp the object's own scratch
+            bool degenerate = false;
+            for (ilupp_precond *q : v.ml->obj) { ensure_transposed(q); degenerate = degenerate || q->degenerate; }
+            if (degenerate) { S.route[(size_t)i] = 2; continue; }
+            ml_first = (int32_t)S.lfresh.size();
+            ml_level_records(v.ml, !v.plain_first, &S.lfresh);
+            d.plain_first = 2; d.kind1 = (int32_t)v.ml->obj.size(); d.kind2 = v.plain_first ? 0 : 1; d.tmp = v.ml->buf;
+        } else if (p) {
             const ApplyPlan plan = apply_plan(p, v.plain_first ? 0 : 1);
             if (v.owner) {
                 PackedSweep *pf = nullptr, *pb = nullptr;
@@ -2653,6 +2714,7 @@ void batch_describe(BatchScratch &S, int32_t count, const BatchMember *members, 
         }
         S.fresh.push_back(d);
         S.launched.push_back(i);
+        S.ml_first.push_back(ml_first);
     }
 }
 
@@ -2686,8 +2748,15 @@ size_t batch_stage(BatchScratch &S, const BatchMember *members, int64_t cap_n)
     // (the kernel makes the same choice per member from the launch's size: 16 n <= lds exactly when 16 n <= the cap)
     S.err.reserve(bs, S.fresh.size());
     for (size_t k = 0; k < S.fresh.size(); ++k) S.fresh[k].err = S.err.d + k;
+    if (!S.lfresh.empty()) {
+        // (the level table first: a multilevel member's descriptor points into it)
+        if (S.mllevels.reserve(bs, S.lfresh.size())) S.mllevels.used = 0;
+        for (size_t k = 0; k < S.fresh.size(); ++k)
+            if (S.ml_first[k] >= 0) S.fresh[k].ptr1 = reinterpret_cast<const int32_t *>(S.mllevels.d + S.ml_first[k]);
+        batch_upload(bs, S.mllevels, S.lfresh);
+    }
     batch_upload(bs, S.table, S.fresh);
-    for (int32_t i : S.launched) batch_join(bs, members[i].p);
+    for (int32_t i : S.launched) batch_join(bs, batch_stream_obj(members[i]));
     return lds;
 }
 
@@ -2696,7 +2765,7 @@ size_t batch_stage(BatchScratch &S, const BatchMember *members, int64_t cap_n)
 void batch_launched(BatchScratch &S, const BatchMember *members)
 {
     ILUPP_HIP(hipEventRecord(S.done_ev, S.stream));
-    for (int32_t i : S.launched) if (hipEvent_t *ev = members[i].batch_ev()) *ev = S.done_ev;
+    for (int32_t i : S.launched) batch_mark(members[i], S.done_ev);
 }
 
 // The second table of a batched solve on the device: for every launched member (at least one) its matrix, its own words of the per-member
@@ -2767,7 +2836,7 @@ int apply_batch_finish(BatchScratch &S, int32_t count, const BatchMember *member
     ILUPP_HIP(stream_sync(S.stream));
     for (int32_t k = 0; k < nl; ++k) {
         const int32_t i = S.launched[(size_t)k];
-        if (hipEvent_t *ev = members[i].batch_ev()) *ev = nullptr;
+        batch_mark(members[i], nullptr);
         S.h_err[(size_t)i] = err[(size_t)k];
         if (err[(size_t)k]) { S.status[(size_t)i] = ILUPP_ERR_TIMEOUT; msgs[(size_t)i] = "triangular solve: dependency wait timed out (factor not triangular?)"; }
     }
@@ -2856,18 +2925,127 @@ int solve_batch_run(BatchSolver solver, int32_t count, const std::vector<BatchMe
     BatchScratch &S = batch_scratch();
     hipStream_t bs = S.stream;
     order_after_caller(bs, S.cev[0]);
-    const int64_t cap_n = solve_batch_cap_n(solver);
+    // The launch with a multilevel member is another instantiation of the kernel with a cap of its own: the members are routed by the
+    // cap of the instantiation that is launched -- and where no multilevel member takes route 0 after all, by the other one's again, for
+    // the launch they have always had.
+    bool ml = std::any_of(mv.begin(), mv.end(), [](const BatchMember &v) { return v.ml != nullptr; });
+    int64_t cap_n = solve_batch_cap_n(solver, ml);
     batch_describe(S, count, mv.data(), offsets, cap_n);
+    if (ml && S.lfresh.empty()) {
+        const std::vector<int32_t> routed = S.route;
+        ml = false;
+        cap_n = solve_batch_cap_n(solver, false);
+        batch_describe(S, count, mv.data(), offsets, cap_n, false);
+        for (int32_t i = 0; i < count; ++i) if (mv[(size_t)i].ml) S.route[(size_t)i] = routed[(size_t)i];
+    }
     routes_out(S.route, route);
     const int32_t nl = (int32_t)S.launched.size();
     if (nl == 0) return ILUPP_OK;
     const size_t lds = batch_stage(S, mv.data(), cap_n);
     batch_systems(S, count, mv.data(), solve_batch_work_factor(solver), d_data, d_indices, d_indptr);
     OR_RETURN(solve_batch_launch(solver, bs, nl, S.table.d, S.sys.d, d_b, d_x0, d_x, d_work, lds, maxiter, rtol, check_every, d_iterations,
-                                 d_flags, d_rr, d_last));
+                                 d_flags, d_rr, d_last, ml));
     batch_launched(S, mv.data());
     if (sync) return apply_batch_finish(S, count, mv.data(), false);
     order_caller_after(bs, S.cev[1]);
+    return ILUPP_OK;
+}
+
+// ---- many MULTILEVEL members applied at once: one launch, one workgroup per member (k_ml_apply_batch, sptrsv_batch.hip) ----
+// n up to which a multilevel member goes to the launch: the 8 n bytes of LDS its first level's sweeps take must fit
+int64_t ml_apply_batch_cap_n() { return batch_env_cap((int64_t)(ml_apply_batch_lds_cap() / 8)); }
+
+// null arguments, a negative count, a null member, a member named twice
+int ml_batch_args(int32_t count, ilupp_ml *const *members, const void *a, const void *b)
+{
+    if (count < 0 || !members || !a || !b) { set_error("null argument"); return ILUPP_ERR_INVALID; }
+    for (int32_t i = 0; i < count; ++i) {
+        if (!members[i]) { set_error("null preconditioner"); return ILUPP_ERR_INVALID; }
+        if (!is_live_ml(members[i])) { set_error("member " + std::to_string(i) + " of the batch is not a multilevel preconditioner"); return ILUPP_ERR_INVALID; }
+    }
+    std::vector<const void *> seen(members, members + count);
+    return batch_no_duplicates(seen);
+}
+
+// Queue the applies of all members, as apply_batch_run does for the other classes: route 0 = the launch (n within the LDS cap, no level
+// object degenerate), 1 = too large (for the LDS, or for a launch it would have to itself) and 2 = degenerate through ml_apply_dev on the
+// member's own stream.  A member's record and one record per level (ml_level_records, ensure_transposed first, as utu_half does) are
+// written from what ml_apply_dev reads; its scratch is the object's own m->buf.  Everything is joined on the scratch's stream when this
+// returns; nothing is waited for.  staged: the vectors were put there by work on the scratch's stream (the host entry).
+int ml_apply_batch_run(BatchScratch &S, int32_t count, ilupp_ml *const *members, double *d_x, const int64_t *offsets, int transpose, bool staged)
+{
+    hipStream_t bs = S.stream;
+    if (!staged) order_after_caller(bs, S.cev[0]);
+    else ILUPP_HIP(hipEventRecord(S.in_ev, bs));
+    const int64_t cap_n = ml_apply_batch_cap_n();
+    const bool tr = transpose != 0;
+    S.route.assign((size_t)count, 0); S.status.assign((size_t)count, ILUPP_OK); S.h_err.assign((size_t)count, 0);
+    S.launched.clear();
+    std::vector<MlApplyDesc> mfresh;
+    std::vector<MlLevelDesc> lfresh;
+    for (int32_t i = 0; i < count; ++i) {
+        ilupp_ml *m = members[i];
+        if (m->n > cap_n) { S.route[(size_t)i] = 1; continue; }
+        bool degenerate = false;
+        for (ilupp_precond *p : m->obj) { ensure_transposed(p); degenerate = degenerate || p->degenerate; }
+        if (degenerate) { S.route[(size_t)i] = 2; continue; }
+        MlApplyDesc d;
+        memset(&d, 0, sizeof(d));
+        d.n = m->n; d.levels = (int32_t)m->obj.size(); d.first = (int32_t)lfresh.size(); d.transpose = tr ? 1 : 0;
+        d.xoff = offsets[i]; d.tmp = m->buf;
+        ml_level_records(m, tr, &lfresh);
+        mfresh.push_back(d);
+        S.launched.push_back(i);
+    }
+    // (ONE member in the launch: the rule of apply_batch_run, past kSmallSweepMax rows it is faster on its single apply)
+    if (S.launched.size() == 1 && mfresh[0].n > kSmallSweepMax) { S.route[(size_t)S.launched[0]] = 1; S.launched.clear(); mfresh.clear(); lfresh.clear(); }
+    if (!S.launched.empty()) {
+        size_t lds = 0;
+        for (const MlApplyDesc &d : mfresh) if ((size_t)8 * (size_t)d.n > lds) lds = (size_t)8 * (size_t)d.n;
+        S.err.reserve(bs, mfresh.size());
+        for (size_t k = 0; k < mfresh.size(); ++k) mfresh[k].err = S.err.d + k;
+        batch_upload(bs, S.mltable, mfresh);
+        batch_upload(bs, S.mllevels, lfresh);
+        // (the levels of a member share the first one's stream: one join per member)
+        for (int32_t i : S.launched) batch_join(bs, members[i]->obj[0]);
+        OR_RETURN(ml_apply_batch_launch(bs, (int32_t)S.launched.size(), S.mltable.d, S.mllevels.d, d_x, lds));
+        // behind the launch: a later single apply of a member (ml_apply_dev) and the destruction of each of its level objects
+        ILUPP_HIP(hipEventRecord(S.done_ev, bs));
+        for (int32_t i : S.launched) for (ilupp_precond *p : members[i]->obj) p->batch_ev = S.done_ev;
+    }
+    for (int32_t i = 0; i < count; ++i) {
+        if (S.route[(size_t)i] == 0) continue;
+        ilupp_ml *m = members[i];
+        hipStream_t st = m->obj[0]->stream;
+        if (staged) ILUPP_HIP(hipStreamWaitEvent(st, S.in_ev, 0));
+        OR_RETURN(ml_apply_dev(m, d_x + offsets[i], transpose));
+        ILUPP_HIP(hipEventRecord(m->obj[0]->sev[1], st));
+        ILUPP_HIP(hipStreamWaitEvent(bs, m->obj[0]->sev[1], 0));
+    }
+    return ILUPP_OK;
+}
+
+// wait for a batch that ml_apply_batch_run queued and say how it went: status per member, the first failure returned and named by its number
+int ml_apply_batch_finish(BatchScratch &S, int32_t count, ilupp_ml *const *members)
+{
+    const int32_t nl = (int32_t)S.launched.size();
+    std::vector<std::string> msgs((size_t)count);
+    for (int32_t i = 0; i < count; ++i)
+        if (S.route[(size_t)i] != 0) {
+            S.status[(size_t)i] = ml_finish_apply(members[i]);
+            if (S.status[(size_t)i]) msgs[(size_t)i] = g_last_error;
+        }
+    std::vector<int32_t> err((size_t)(nl > 0 ? nl : 1), 0);
+    if (nl > 0) ILUPP_HIP(d2h_async(S.stream, err.data(), S.err.d, sizeof(int32_t) * (size_t)nl));
+    ILUPP_HIP(stream_sync(S.stream));
+    for (int32_t k = 0; k < nl; ++k) {
+        const int32_t i = S.launched[(size_t)k];
+        for (ilupp_precond *p : members[i]->obj) p->batch_ev = nullptr;
+        S.h_err[(size_t)i] = err[(size_t)k];
+        if (err[(size_t)k]) { S.status[(size_t)i] = ILUPP_ERR_TIMEOUT; msgs[(size_t)i] = "triangular solve: dependency wait timed out (factor not triangular?)"; }
+    }
+    for (int32_t i = 0; i < count; ++i)
+        if (S.status[(size_t)i]) { set_error("member " + std::to_string(i) + " of the batch: " + msgs[(size_t)i]); return S.status[(size_t)i]; }
     return ILUPP_OK;
 }
 
@@ -2981,6 +3159,52 @@ int ilupp_hip_pivot_bicgstab_batch_device(int32_t count, ilupp_ilucp *const *mem
     API_CATCH
 }
 
+// what ilupp_hip_bicgstab_batch_device and ilupp_hip_bicgstab_batch_ml_device do (the first without a list of multilevel members)
+static int bicgstab_batch_entry(int32_t count, ilupp_precond *const *plain, ilupp_ilucp *const *pivoted, ilupp_ml *const *multilevel, const int64_t *n,
+                                const double *const *d_data, const int32_t *const *d_indices, const int32_t *const *d_indptr,
+                                const int64_t *nnz, const double *d_b, const double *d_x0, double *d_x, const int64_t *offsets,
+                                double *d_work, int64_t work_doubles, int32_t maxiter, double rtol, int32_t check_every,
+                                int64_t *d_iterations, int32_t *d_flags, double *d_rr, double *d_init, int sync, int32_t *route)
+{
+    if (count < 0 || !d_x || !offsets || !n || !d_data || !d_indices || !d_indptr || !nnz || !d_b || !d_work || !d_iterations || !d_flags ||
+        !d_rr || !d_init) { set_error("null argument"); return ILUPP_ERR_INVALID; }
+    OR_RETURN(batch_iteration_args(maxiter, check_every));
+    // member i: pivoted[i], or plain[i], or multilevel[i], or none of them (no preconditioner); a multilevel object among `plain` is
+    // named before anything reads it as an ilupp_precond, and a member of `multilevel` must be a live one
+    std::vector<const void *> seen_plain, seen_pivoted, seen_ml;
+    int64_t total = 0;
+    for (int32_t i = 0; i < count; ++i) {
+        ilupp_precond *p = plain ? plain[i] : nullptr;
+        ilupp_ilucp *m = pivoted ? pivoted[i] : nullptr;
+        ilupp_ml *q = multilevel ? multilevel[i] : nullptr;
+        if (p && m) { set_error("member " + std::to_string(i) + " of the batch: both a pivoting and a non-pivoting preconditioner"); return ILUPP_ERR_INVALID; }
+        if (q && (p || m)) { set_error("member " + std::to_string(i) + " of the batch: both a multilevel and another preconditioner"); return ILUPP_ERR_INVALID; }
+        if (p && is_live_ml(p)) { set_error("a multilevel preconditioner cannot be a member of a batch"); return ILUPP_ERR_INVALID; }
+        if (q && !is_live_ml(q)) { set_error("member " + std::to_string(i) + " of the batch is not a multilevel preconditioner"); return ILUPP_ERR_INVALID; }
+        OR_RETURN(batch_matrix_arrays(d_data, d_indices, d_indptr, i));
+        if (n[i] <= 0 || n[i] > INT32_MAX) { set_error("matrix has size 0!"); return ILUPP_ERR_INVALID; }
+        if ((p && p->n != n[i]) || (m && m->n != n[i]) || (q && q->n != n[i])) { set_error("matrix has wrong size for preconditioner!"); return ILUPP_ERR_WRONG_SIZE; }
+        if (p) seen_plain.push_back(p);
+        if (m) seen_pivoted.push_back(m);
+        if (q) seen_ml.push_back(q);
+        total += n[i];
+    }
+    OR_RETURN(batch_no_duplicates(seen_plain));
+    OR_RETURN(batch_no_duplicates(seen_pivoted));
+    OR_RETURN(batch_no_duplicates(seen_ml));
+    OR_RETURN(batch_workspace(BATCH_BICGSTAB, work_doubles, total));
+    if (count == 0) return ILUPP_OK;
+    std::vector<BatchMember> mv((size_t)count);
+    for (int32_t i = 0; i < count; ++i) {
+        if (pivoted && pivoted[i]) mv[(size_t)i] = batch_member(pivoted[i], 0);
+        else if (plain && plain[i]) mv[(size_t)i] = batch_member(plain[i], 0);
+        else if (multilevel && multilevel[i]) mv[(size_t)i] = batch_member(multilevel[i], 0);
+        mv[(size_t)i].n = (int32_t)n[i];
+    }
+    return solve_batch_run(BATCH_BICGSTAB, count, mv, d_data, d_indices, d_indptr, d_b, d_x0, d_x, offsets, d_work, maxiter, rtol,
+                           check_every, d_iterations, d_flags, d_rr, d_init, sync, route);
+}
+
 int ilupp_hip_bicgstab_batch_device(int32_t count, ilupp_precond *const *plain, ilupp_ilucp *const *pivoted, const int64_t *n,
                                     const double *const *d_data, const int32_t *const *d_indices, const int32_t *const *d_indptr,
                                     const int64_t *nnz, const double *d_b, const double *d_x0, double *d_x, const int64_t *offsets,
@@ -2988,37 +3212,28 @@ int ilupp_hip_bicgstab_batch_device(int32_t count, ilupp_precond *const *plain, 
                                     int64_t *d_iterations, int32_t *d_flags, double *d_rr, double *d_init, int sync, int32_t *route)
 {
     API_TRY
-    if (count < 0 || !d_x || !offsets || !n || !d_data || !d_indices || !d_indptr || !nnz || !d_b || !d_work || !d_iterations || !d_flags ||
-        !d_rr || !d_init) { set_error("null argument"); return ILUPP_ERR_INVALID; }
-    OR_RETURN(batch_iteration_args(maxiter, check_every));
-    // member i: pivoted[i], or plain[i], or neither (no preconditioner); a multilevel object among `plain` is named before anything reads
-    // it as an ilupp_precond
-    std::vector<const void *> seen_plain, seen_pivoted;
-    int64_t total = 0;
-    for (int32_t i = 0; i < count; ++i) {
-        ilupp_precond *p = plain ? plain[i] : nullptr;
-        ilupp_ilucp *m = pivoted ? pivoted[i] : nullptr;
-        if (p && m) { set_error("member " + std::to_string(i) + " of the batch: both a pivoting and a non-pivoting preconditioner"); return ILUPP_ERR_INVALID; }
-        if (p && is_live_ml(p)) { set_error("a multilevel preconditioner cannot be a member of a batch"); return ILUPP_ERR_INVALID; }
-        OR_RETURN(batch_matrix_arrays(d_data, d_indices, d_indptr, i));
-        if (n[i] <= 0 || n[i] > INT32_MAX) { set_error("matrix has size 0!"); return ILUPP_ERR_INVALID; }
-        if ((p && p->n != n[i]) || (m && m->n != n[i])) { set_error("matrix has wrong size for preconditioner!"); return ILUPP_ERR_WRONG_SIZE; }
-        if (p) seen_plain.push_back(p);
-        if (m) seen_pivoted.push_back(m);
-        total += n[i];
-    }
-    OR_RETURN(batch_no_duplicates(seen_plain));
-    OR_RETURN(batch_no_duplicates(seen_pivoted));
-    OR_RETURN(batch_workspace(BATCH_BICGSTAB, work_doubles, total));
-    if (count == 0) return ILUPP_OK;
-    std::vector<BatchMember> mv((size_t)count);
-    for (int32_t i = 0; i < count; ++i) {
-        if (pivoted && pivoted[i]) mv[(size_t)i] = batch_member(pivoted[i], 0);
-        else if (plain && plain[i]) mv[(size_t)i] = batch_member(plain[i], 0);
-        mv[(size_t)i].n = (int32_t)n[i];
-    }
-    return solve_batch_run(BATCH_BICGSTAB, count, mv, d_data, d_indices, d_indptr, d_b, d_x0, d_x, offsets, d_work, maxiter, rtol,
-                           check_every, d_iterations, d_flags, d_rr, d_init, sync, route);
+    return bicgstab_batch_entry(count, plain, pivoted, nullptr, n, d_data, d_indices, d_indptr, nnz, d_b, d_x0, d_x, offsets, d_work, work_doubles,
+                                maxiter, rtol, check_every, d_iterations, d_flags, d_rr, d_init, sync, route);
+    API_CATCH
+}
+
+int ilupp_hip_bicgstab_batch_ml_device(int32_t count, ilupp_precond *const *plain, ilupp_ilucp *const *pivoted, ilupp_ml *const *multilevel,
+                                       const int64_t *n, const double *const *d_data, const int32_t *const *d_indices,
+                                       const int32_t *const *d_indptr, const int64_t *nnz, const double *d_b, const double *d_x0, double *d_x,
+                                       const int64_t *offsets, double *d_work, int64_t work_doubles, int32_t maxiter, double rtol,
+                                       int32_t check_every, int64_t *d_iterations, int32_t *d_flags, double *d_rr, double *d_init, int sync,
+                                       int32_t *route)
+{
+    API_TRY
+    return bicgstab_batch_entry(count, plain, pivoted, multilevel, n, d_data, d_indices, d_indptr, nnz, d_b, d_x0, d_x, offsets, d_work,
+                                work_doubles, maxiter, rtol, check_every, d_iterations, d_flags, d_rr, d_init, sync, route);
+    API_CATCH
+}
+
+int64_t ilupp_hip_bicgstab_batch_ml_max_n(void)
+{
+    API_TRY
+    return solve_batch_cap_n(BATCH_BICGSTAB, true);
     API_CATCH
 }
 
@@ -3033,6 +3248,60 @@ int64_t ilupp_hip_pivot_apply_batch_max_n(void)
 {
     API_TRY
     return batch_apply_max_n();
+    API_CATCH
+}
+
+int ilupp_hip_ml_apply_batch_device(int32_t count, ilupp_ml *const *members, double *d_x, const int64_t *offsets, int transpose, int sync,
+                                    int32_t *route)
+{
+    API_TRY
+    const int rc0 = ml_batch_args(count, members, d_x, offsets);
+    if (rc0 || count == 0) return rc0;
+    std::lock_guard<std::mutex> lk(g_batch_mu);
+    BatchScratch &S = batch_scratch();
+    const int rc = ml_apply_batch_run(S, count, members, d_x, offsets, transpose, false);
+    routes_out(S.route, route);
+    if (rc) return rc;
+    if (sync) return ml_apply_batch_finish(S, count, members);
+    order_caller_after(S.stream, S.cev[1]);
+    return ILUPP_OK;
+    API_CATCH
+}
+
+int ilupp_hip_ml_apply_batch(int32_t count, ilupp_ml *const *members, double *const *x, const int64_t *len, int transpose, int32_t *route)
+{
+    API_TRY
+    OR_RETURN(ml_batch_args(count, members, x, len));
+    for (int32_t i = 0; i < count; ++i) {
+        if (!x[i]) { set_error("null argument"); return ILUPP_ERR_INVALID; }
+        if (len[i] != members[i]->n) { set_error("vector has wrong size for preconditioner!"); return ILUPP_ERR_WRONG_SIZE; }
+    }
+    if (count == 0) return ILUPP_OK;
+    std::lock_guard<std::mutex> lk(g_batch_mu);
+    BatchScratch &S = batch_scratch();
+    // all vectors through ONE device buffer: one packed upload, one download
+    std::vector<int64_t> off((size_t)count);
+    size_t total = 0;
+    for (int32_t i = 0; i < count; ++i) { off[(size_t)i] = (int64_t)total; total += (size_t)len[i]; }
+    S.stage.reserve(S.stream, total);
+    for (int32_t i = 0; i < count; ++i) memcpy(S.stage.h + off[(size_t)i], x[i], sizeof(double) * (size_t)len[i]);
+    ILUPP_HIP(hipMemcpyAsync(S.stage.d, S.stage.h, sizeof(double) * total, hipMemcpyHostToDevice, S.stream));
+    int rc = ml_apply_batch_run(S, count, members, S.stage.d, off.data(), transpose, true);
+    routes_out(S.route, route);
+    if (rc) { (void)hipStreamSynchronize(S.stream); return rc; }
+    ILUPP_HIP(hipMemcpyAsync(S.stage.h, S.stage.d, sizeof(double) * total, hipMemcpyDeviceToHost, S.stream));
+    rc = ml_apply_batch_finish(S, count, members);
+    // (a member that failed keeps its vector as it was; the others have theirs)
+    for (int32_t i = 0; i < count; ++i)
+        if (S.status[(size_t)i] == ILUPP_OK) memcpy(x[i], S.stage.h + off[(size_t)i], sizeof(double) * (size_t)len[i]);
+    return rc;
+    API_CATCH
+}
+
+int64_t ilupp_hip_ml_apply_batch_max_n(void)
+{
+    API_TRY
+    return ml_apply_batch_cap_n();
     API_CATCH
 }
 

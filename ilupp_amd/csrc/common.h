@@ -580,7 +580,7 @@ struct PivotApplyDesc {
 };
 // Bytes of dynamic LDS one workgroup of Kernel may take on the current device: what the device gives a workgroup minus the kernel's
 // static words; the kernel is told once per device (and host thread) that it may ask for that much.  One-workgroup-per-member kernels:
-// k_pivot_apply_batch, k_cg_batch, k_bicgstab_batch, k_ilu0_refactor_batch.
+// k_pivot_apply_batch, k_ml_apply_batch, k_cg_batch, k_bicgstab_batch<false> and <true>, k_ilu0_refactor_batch.
 template <auto Kernel>
 size_t kernel_lds_cap()
 {
@@ -602,6 +602,28 @@ size_t kernel_lds_cap()
 }
 size_t pivot_apply_batch_lds_cap();      // bytes of dynamic LDS a workgroup of the kernel may take on the current device: n <= cap / 8
 int pivot_apply_batch_launch(hipStream_t st, int32_t count, const PivotApplyDesc *d_table, double *d_x, size_t lds_bytes);
+// the same file: the whole apply of many MULTILEVEL preconditioners in one launch, one workgroup per member (k_ml_apply_batch).  One
+// member: its n, how many levels it has and where their records start in the launch's level table, the direction, its vector (an offset
+// from the launch's base pointer), its n doubles of scratch (a level's right-hand sides) and its error word (1 = a dependency wait timed
+// out).  One level: its n_l (the level works on the LAST n_l entries of the vector), the triangles of its two halves with their sweep
+// kinds (triangle 1: the forward half of pass 0, triangle 2: the backward half of pass 1 -- apply_plan(KIND_UTU, ...) / sweep_parts on the
+// level's object), the three diagonals, and the two index arrays the direction needs: `gather` in front of pass 0's sweep (perm_rows; transposed:
+// perm_columns), `take` behind pass 1's (inverse_perm_columns; transposed: inverse_perm_rows).
+struct MlLevelDesc {
+    int32_t n, kind1, kind2, pad;
+    const int32_t *ptr1, *idx1; const double *val1;
+    const int32_t *ptr2, *idx2; const double *val2;
+    const double *D, *Dl, *Dr;
+    const int32_t *gather, *take;
+};
+struct MlApplyDesc {
+    int32_t n, levels, first, transpose;
+    int64_t xoff;
+    double *tmp;
+    int32_t *err;
+};
+size_t ml_apply_batch_lds_cap();         // bytes of dynamic LDS a workgroup of the kernel may take on the current device: n <= cap / 8
+int ml_apply_batch_launch(hipStream_t st, int32_t count, const MlApplyDesc *d_table, const MlLevelDesc *d_levels, double *d_x, size_t lds_bytes);
 // the same file: the whole preconditioned Krylov solve of many small systems in one launch, one workgroup per member: left-preconditioned
 // BiCGstab (k_bicgstab_batch) or CG (k_cg_batch).  Beside a member's PivotApplyDesc (xoff: its slice of the packed b / x0 / x; tmp; err;
 // perm != nullptr a pivoting member, perm == nullptr a non-pivoting one with its two CSR triangles from apply_plan / sweep_parts,
@@ -613,12 +635,14 @@ struct PivotSolveDesc {
     int32_t member, pad;
 };
 enum BatchSolver { BATCH_CG = 0, BATCH_BICGSTAB = 1 };
-int64_t solve_batch_max_n(BatchSolver s);        // the largest n of a member of that launch on the current device (LDS: dot scratch + 8 n bytes)
+// (ml: k_bicgstab_batch<true>, the instantiation a launch with a multilevel member runs: a PivotApplyDesc with plain_first == 2 is such a
+// member, ptr1 its MlLevelDesc records, kind1 their number, kind2 the direction, tmp its scratch; BATCH_BICGSTAB only)
+int64_t solve_batch_max_n(BatchSolver s, bool ml = false);        // the largest n of a member of that launch on the current device (LDS: dot scratch + 8 n bytes)
 int solve_batch_work_factor(BatchSolver s);      // doubles of workspace per unknown of the batch: CG 5 (x, r, z, p, Ap), BiCGstab 7 (y, r, r0*, p, s, Ap, As)
 // d_last: the per-member word behind rr -- CG's ||b||, BiCGstab's ||r_0||
 int solve_batch_launch(BatchSolver s, hipStream_t st, int32_t count, const PivotApplyDesc *d_table, const PivotSolveDesc *d_systems,
                        const double *d_b, const double *d_x0, double *d_x, double *d_work, size_t sweep_bytes, int32_t maxiter, double rtol,
-                       int32_t check_every, int64_t *d_iterations, int32_t *d_flags, double *d_rr, double *d_last);
+                       int32_t check_every, int64_t *d_iterations, int32_t *d_flags, double *d_rr, double *d_last, bool ml = false);
 
 // ilu0_batch.hip: the numeric ILU(0) re-factorisation of many small objects in one launch, one workgroup per member
 // (k_ilu0_refactor_batch).  One member: the matrix with the new values (device CSR arrays), the two triangles whose values are rewritten

@@ -29,6 +29,18 @@
 // left-preconditioned BiCGstab SOLVE of many small systems in one launch, and k_cg_batch, the whole preconditioned CG solve of many small
 // symmetric positive definite systems.  Both take members of every class above, pivoting or not, or without a preconditioner, mixed in
 // one launch.
+//
+// Between the apply's kernel and the two solvers: k_ml_apply_batch, the whole apply of MANY multilevel ILU++ preconditioners in one launch -- one workgroup per
+// member walks ml_apply_dev (api.hip) statement for statement: pass 0 upwards through the member's levels, pass 1 downwards, every level
+// on the LAST n_l entries of the member's vector, each step a scale / permute into right-hand sides, ONE sweep of the level's object
+// (batch_sweep above, the unknowns in the one LDS array of n_0), and a take / permute back into the tail.
+// In place without a hazard: a level's gather reads entries of the tail that its take overwrites later, so a step never writes the tail
+// while it is being read -- (1) EVERY right-hand side of the step is written to the member's scratch `tmp` in HBM (n doubles of the
+// object's own, and an object is a member at most once per call) before (2) a workgroup barrier, behind which nothing reads the tail until
+// (3) the sweep, which reads `tmp` and writes LDS only, has passed its closing barrier; (4) the take then reads LDS (through the
+// permutation) and writes the tail, every lane its own entries, and (5) a second barrier ends the step: the next step's gather reads the
+// finished tail, its sweep refills an LDS array nobody reads any more, and its right-hand sides overwrite a `tmp` whose readers have left
+// the sweep.  One CU and one L1 touch vector and scratch.  A member whose sweep gives up stops there: its vector is unspecified.
 #include "common.h"
 
 namespace ilupp {
@@ -181,6 +193,76 @@ int pivot_apply_batch_launch(hipStream_t st, int32_t count, const PivotApplyDesc
     return ILUPP_OK;
 }
 
+// ---- the whole apply of MANY multilevel ILU++ preconditioners in ONE launch: one workgroup per member ---------------------------------
+// The apply of one member by its workgroup, in place on x (n doubles): ml_apply_dev of api.hip with the element operations of ml.hip's
+// vector kernels in their exact form -- a division stays a division, a multiply a separate multiply -- and batch_sweep for the sweeps, so
+// the member has the bits of its single apply.  lv: the member's level records; arr: 8 n bytes of LDS.  The hazards: the file's header.
+// *s_fail != 0 afterwards: a sweep gave up and the member stopped there.
+__device__ __forceinline__ void ml_apply_member(const MlApplyDesc &d, const MlLevelDesc *__restrict__ lv, double *x, unsigned long long *arr,
+                                                unsigned *s_progress, int *s_fail)
+{
+    const int tid = threadIdx.x;
+    const bool tr = d.transpose != 0;
+    double *rhs = d.tmp;
+    for (int pass = 0; pass < 2; ++pass) {
+        for (int s = 0; s < d.levels; ++s) {
+            const MlLevelDesc l = lv[pass == 0 ? s : d.levels - 1 - s];
+            const int n = l.n;
+            double *xt = x + (d.n - n);
+            if (pass == 0) {                   // ID: x /= D_l, permute_first(perm_rows); TRANSPOSE: x /= D_r, permute_first(perm_columns)
+                const double *Dg = tr ? l.Dr : l.Dl;
+                for (int i = tid; i < n; i += kBatchThreads) { const int g = l.gather[i]; rhs[i] = xt[g] / Dg[g]; }
+            } else if (!tr) {                  // ID: x *= D
+                for (int i = tid; i < n; i += kBatchThreads) rhs[i] = xt[i] * l.D[i];
+            } else {
+                for (int i = tid; i < n; i += kBatchThreads) rhs[i] = xt[i];
+            }
+            __syncthreads();
+            // (one call for both passes: the inlined sweep stands in the code once)
+            batch_sweep(pass == 0 ? l.kind1 : l.kind2, n, pass == 0 ? l.ptr1 : l.ptr2, pass == 0 ? l.idx1 : l.idx2, pass == 0 ? l.val1 : l.val2,
+                        arr, nullptr, rhs, nullptr, nullptr, nullptr, s_progress, s_fail);
+            if (*s_fail != 0) return;          // (uniform: read behind the sweep's closing barrier, and nobody writes it outside a sweep)
+            if (pass == 0) {                   // ID: x = w; TRANSPOSE: x = w * D
+                for (int i = tid; i < n; i += kBatchThreads) {
+                    const double v = __longlong_as_double((long long)arr[i]);
+                    xt[i] = tr ? v * l.D[i] : v;
+                }
+            } else {                           // ID: permute_last(inverse_perm_columns), x /= D_r; TRANSPOSE: permute_last(inverse_perm_rows), x /= D_l
+                const double *Dt = tr ? l.Dl : l.Dr;
+                for (int i = tid; i < n; i += kBatchThreads) xt[i] = __longlong_as_double((long long)arr[l.take[i]]) / Dt[i];
+            }
+            __syncthreads();
+        }
+    }
+}
+
+__global__ void __launch_bounds__(kBatchThreads)
+k_ml_apply_batch(const MlApplyDesc *__restrict__ table, const MlLevelDesc *__restrict__ levels, double *xbase)
+{
+    extern __shared__ unsigned long long lds[];     // the unknowns of a sweep, sentinel = not yet: one array of n_0
+    __shared__ unsigned s_progress;
+    __shared__ int s_fail;
+    const MlApplyDesc d = table[blockIdx.x];
+    if (threadIdx.x == 0) { s_progress = 0; s_fail = 0; }
+    // (the barrier behind the first level's right-hand sides publishes the two words before any wave looks at them)
+    ml_apply_member(d, levels + d.first, xbase + d.xoff, lds, &s_progress, &s_fail);
+    if (threadIdx.x == 0) *d.err = s_fail;          // (one writer per member: its own word, whatever the other members do)
+}
+
+// bytes of dynamic LDS one workgroup of k_ml_apply_batch may take on the current device
+size_t ml_apply_batch_lds_cap() { return kernel_lds_cap<k_ml_apply_batch>(); }
+
+// `count` members, one workgroup each; member i's vector is d_x + table[i].xoff, its levels d_levels + table[i].first; lds_bytes for every
+// workgroup (<= the cap): 8 bytes per unknown of the launch's largest member
+int ml_apply_batch_launch(hipStream_t st, int32_t count, const MlApplyDesc *d_table, const MlLevelDesc *d_levels, double *d_x, size_t lds_bytes)
+{
+    if (count <= 0) return ILUPP_OK;
+    if (lds_bytes > ml_apply_batch_lds_cap()) return ILUPP_ERR_UNSUPPORTED;
+    hipLaunchKernelGGL(k_ml_apply_batch, dim3((unsigned)count), dim3(kBatchThreads), lds_bytes, st, d_table, d_levels, d_x);
+    ILUPP_HIP(hipGetLastError());
+    return ILUPP_OK;
+}
+
 
 // ---- the whole left-preconditioned BiCGstab solve of MANY small systems in ONE launch: one workgroup per member --------------------
 // k_bicgstab_batch runs _bicgstab_block of ilupp_amd/device.py with k = 1, statement for statement, for its member: the SpMV of
@@ -302,6 +384,25 @@ __device__ __forceinline__ void solve_member_exit(const PivotApplyDesc &d, const
     }
 }
 
+// A MULTILEVEL member of the solve (k_bicgstab_batch<true> only) travels in the same PivotApplyDesc: plain_first == kMlMember marks it,
+// ptr1 points at its level records (MlLevelDesc, the launch's level table), kind1 is their number, kind2 the direction, tmp its n doubles
+// of scratch.  Its apply is ml_apply_member in place on dst, behind a plain copy (which changes no bits) where dst is not src.
+static constexpr int kMlMember = 2;
+__device__ __forceinline__ void apply_member_or_ml(const PivotApplyDesc &d, const double *src, double *dst, unsigned long long *arr,
+                                                   const unsigned lds_bytes, unsigned *s_progress, int *s_fail)
+{
+    if (d.plain_first != kMlMember) { apply_member(d, src, dst, arr, lds_bytes, s_progress, s_fail); return; }      // (uniform over the workgroup)
+    if (dst != src) {
+        for (int i = threadIdx.x; i < d.n; i += kBatchThreads) dst[i] = src[i];
+        __syncthreads();
+    }
+    MlApplyDesc m;
+    m.n = d.n; m.levels = d.kind1; m.first = 0; m.transpose = d.kind2; m.xoff = 0; m.tmp = d.tmp; m.err = nullptr;
+    ml_apply_member(m, reinterpret_cast<const MlLevelDesc *>(d.ptr1), dst, arr, s_progress, s_fail);
+}
+
+// ML: the launch has a multilevel member (the apply is then a choice on the descriptor); false: the kernel as it always was
+template <bool ML>
 __global__ void __launch_bounds__(kBatchThreads)
 k_bicgstab_batch(const PivotApplyDesc *__restrict__ table, const PivotSolveDesc *__restrict__ systems, const double *bbase,
                  const double *x0base, double *xbase, double *work, const unsigned sweep_bytes, const int maxiter, const double rtol,
@@ -348,7 +449,8 @@ k_bicgstab_batch(const PivotApplyDesc *__restrict__ table, const PivotSolveDesc 
             __syncthreads();
         }
         if (has_m) {
-            apply_member(d, vec, vec, arr, sweep_bytes, &s_progress, &s_fail);
+            if constexpr (ML) apply_member_or_ml(d, vec, vec, arr, sweep_bytes, &s_progress, &s_fail);
+            else apply_member(d, vec, vec, arr, sweep_bytes, &s_progress, &s_fail);
             if (s_fail != 0) { failed = true; active = false; break; }
         }
         if (half == 0) {
@@ -515,12 +617,17 @@ k_cg_batch(const PivotApplyDesc *__restrict__ table, const PivotSolveDesc *__res
 }
 
 // ---- the host side of the two solver kernels ---------------------------------------------------------------------------------------
-static size_t solve_batch_lds_cap(BatchSolver s) { return s == BATCH_CG ? kernel_lds_cap<k_cg_batch>() : kernel_lds_cap<k_bicgstab_batch>(); }
+// (ml: the instantiation of the BiCGstab kernel that takes multilevel members -- a kernel of its own with a cap of its own)
+static size_t solve_batch_lds_cap(BatchSolver s, bool ml)
+{
+    if (s == BATCH_CG) return kernel_lds_cap<k_cg_batch>();
+    return ml ? kernel_lds_cap<k_bicgstab_batch<true>>() : kernel_lds_cap<k_bicgstab_batch<false>>();
+}
 
 // the largest n of a member of the solve's launch: the dot scratch and 8 n bytes for the sweeps fit, and the dot has at most kDotMaxNb chunks
-int64_t solve_batch_max_n(BatchSolver s)
+int64_t solve_batch_max_n(BatchSolver s, bool ml)
 {
-    const size_t cap = solve_batch_lds_cap(s), scratch = sizeof(double) * (size_t)kDotScratch;
+    const size_t cap = solve_batch_lds_cap(s, ml), scratch = sizeof(double) * (size_t)kDotScratch;
     const int64_t by_lds = cap > scratch ? (int64_t)((cap - scratch) / 8) : 0;
     return by_lds < 256 * kDotMaxNb ? by_lds : 256 * kDotMaxNb;
 }
@@ -530,12 +637,13 @@ int solve_batch_work_factor(BatchSolver s) { return s == BATCH_CG ? kCgBatchVect
 // `count` members, one workgroup each; sweep_bytes of LDS for the sweeps of every workgroup (the dot scratch comes on top)
 int solve_batch_launch(BatchSolver s, hipStream_t st, int32_t count, const PivotApplyDesc *d_table, const PivotSolveDesc *d_systems,
                        const double *d_b, const double *d_x0, double *d_x, double *d_work, size_t sweep_bytes, int32_t maxiter, double rtol,
-                       int32_t check_every, int64_t *d_iterations, int32_t *d_flags, double *d_rr, double *d_last)
+                       int32_t check_every, int64_t *d_iterations, int32_t *d_flags, double *d_rr, double *d_last, bool ml)
 {
     if (count <= 0) return ILUPP_OK;
+    if (ml && s == BATCH_CG) return ILUPP_ERR_UNSUPPORTED;      // (the multilevel preconditioner is not symmetric: no such instantiation)
     const size_t lds_bytes = sizeof(double) * (size_t)kDotScratch + sweep_bytes;
-    if (lds_bytes > solve_batch_lds_cap(s)) return ILUPP_ERR_UNSUPPORTED;
-    const auto kernel = s == BATCH_CG ? k_cg_batch : k_bicgstab_batch;
+    if (lds_bytes > solve_batch_lds_cap(s, ml)) return ILUPP_ERR_UNSUPPORTED;
+    const auto kernel = s == BATCH_CG ? k_cg_batch : ml ? k_bicgstab_batch<true> : k_bicgstab_batch<false>;
     hipLaunchKernelGGL(kernel, dim3((unsigned)count), dim3(kBatchThreads), lds_bytes, st, d_table, d_systems, d_b, d_x0, d_x, d_work,
                        (unsigned)sweep_bytes, (int)maxiter, rtol, (int)check_every, reinterpret_cast<long long *>(d_iterations), d_flags, d_rr,
                        d_last);

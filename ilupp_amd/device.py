@@ -228,7 +228,7 @@ def pivot_apply_batch_(members, x, offsets, transpose=False):
     synchronisation.  Returns the route of every member (0 = the launch, 1 = too large, 2 = a factor with an empty row: applied alone
     inside the same call).  ValueError for a wrong tensor, unequal lengths or a vector that does not lie inside ``x``; TypeError for a
     member of another class -- before any native call.  Out of scope: ``DevicePreconditioner("ILUTP" / "ILUCP")`` (construction from device
-    arrays) and a batched apply of the multilevel class.  The whole preconditioned BiCGstab solve of many systems in one launch:
+    arrays).  The multilevel class has a batched apply of its own: ``ml_apply_batch_``.  The whole preconditioned BiCGstab solve of many systems in one launch:
     ``bicgstab_batch``."""
     members, offsets = list(members), [int(o) for o in offsets]
     if not isinstance(x, torch.Tensor) or x.dim() != 1 or x.dtype != torch.float64 or not x.is_cuda or not x.is_contiguous():
@@ -290,15 +290,98 @@ class PivotedOperator:
         torch.cuda.current_stream().synchronize()
 
 
+def _ml_native(P):
+    """the native object of a multilevel member: an ``ilupp_amd.ILUppPreconditioner`` of the ctypes binding, a
+    ``DevicePreconditioner("ILUpp", ...)`` or a ``MultilevelOperator``; None for anything else -- no native call"""
+    if isinstance(P, DevicePreconditioner) and getattr(P, "kind", None) != "ILUpp":
+        return None
+    pr = getattr(P, "pr", P)
+    return pr if isinstance(pr, _native.MultilevelPreconditioner) else None
+
+
+class MultilevelOperator:
+    """A multilevel ILU++ preconditioner -- an ``ilupp_amd.ILUppPreconditioner`` (built on the host by the ctypes binding, alone or by
+    ``ILUppPreconditioner.batch``) or a ``DevicePreconditioner("ILUpp", ...)`` -- as the ``M`` of ``bicgstab`` with a 2-D right-hand side
+    and as a member of ``bicgstab_batch``: the sibling of ``PivotedOperator``.  ``apply_`` works in place on a device tensor through the
+    single device apply (ilupp_hip_ml_apply_device), ordered on torch's current stream.  One right-hand side at a time: shape (n,) or
+    (n, 1).  ``bicgstab(A, b[:, None], M=MultilevelOperator(P))`` is the solve every such member of ``bicgstab_batch`` has the bits of.
+    TypeError for any other class."""
+
+    kind = "ILUppOperator"       # (not "ILUpp": the block loops of cg / bicgstab take this wrapper, with k = 1)
+
+    def __init__(self, P):
+        pr = None if isinstance(P, MultilevelOperator) else _ml_native(P)
+        if pr is None:
+            raise TypeError("MultilevelOperator takes an ILUppPreconditioner instance of the ctypes binding or a "
+                            "DevicePreconditioner of the \"ILUpp\" kind, got %s" % type(P).__name__)
+        self.P, self.pr = P, pr
+        self.n = pr._n
+        self.shape = (self.n, self.n)
+
+    def apply_(self, x, transpose=False):
+        """in place on a contiguous fp64 CUDA tensor of shape (n,) or (n, 1); asynchronous, ordered on torch's current stream"""
+        if not isinstance(x, torch.Tensor) or x.dim() not in (1, 2) or x.shape[0] != self.n:
+            raise ValueError("x: expected a tensor of shape (%d,) or (%d, 1), got %s" % (self.n, self.n, tuple(getattr(x, "shape", ()))))
+        if x.dim() == 2 and x.shape[1] != 1:
+            raise NotImplementedError("k right-hand sides with the multilevel preconditioner: apply_ one column at a time")
+        if x.dtype != torch.float64 or not x.is_cuda or not x.is_contiguous():
+            raise ValueError("x: expected a contiguous torch.float64 CUDA tensor")
+        _on_current_stream()
+        self.pr.apply_device(x.data_ptr(), self.n, transpose=transpose, sync=False)
+        return x
+
+    def matvec(self, x):
+        return self.apply_(x.clone())
+
+    __matmul__ = matvec
+
+    def sync(self):
+        """wait for what was queued on torch's current stream (the applies are ordered on it)"""
+        torch.cuda.current_stream().synchronize()
+
+
+def ml_apply_batch_(members, x, offsets, transpose=False):
+    """The applies of many multilevel ILU++ preconditioners in place on ONE contiguous fp64 CUDA tensor: member k's vector is
+    ``x[offsets[k] : offsets[k] + n_k]``; what lies between the vectors is left untouched.  Members: ``ilupp_amd.ILUppPreconditioner``
+    objects of the ctypes binding, ``DevicePreconditioner("ILUpp", ...)`` objects or ``MultilevelOperator``s, mixed at will, each at
+    most once.  One kernel launch for all members that fit (``ilupp_hip_ml_apply_batch_device``: one workgroup per member walks its
+    levels up and down), ordered on torch's current stream, no host synchronisation.  Every member's vector has the bits of its single
+    ``apply_``.  Returns the route of every member (0 = the launch, 1 = too large, 2 = a level's factor with an empty row: applied alone
+    inside the same call).  ValueError for a wrong tensor, unequal lengths or a vector that does not lie inside ``x``; TypeError for a
+    member of another class -- before any native call.  The whole preconditioned BiCGstab solve of many systems in one launch:
+    ``bicgstab_batch`` with ``MultilevelOperator`` members."""
+    members, offsets = list(members), [int(o) for o in offsets]
+    if not isinstance(x, torch.Tensor) or x.dim() != 1 or x.dtype != torch.float64 or not x.is_cuda or not x.is_contiguous():
+        raise ValueError("x: expected a contiguous 1-D torch.float64 CUDA tensor")
+    if len(members) != len(offsets):
+        raise ValueError("%d preconditioners but %d offsets" % (len(members), len(offsets)))
+    natives = []
+    for P in members:
+        pr = _ml_native(P)
+        if pr is None:
+            raise TypeError("ml_apply_batch_ takes ILUppPreconditioner instances of the ctypes binding, DevicePreconditioners of the "
+                            "\"ILUpp\" kind or MultilevelOperators, got %s" % type(P).__name__)
+        natives.append(pr)
+    for pr, o in zip(natives, offsets):
+        if o < 0 or o + pr._n > x.numel():
+            raise ValueError("a vector of %d elements at offset %d does not lie inside x (%d elements)" % (pr._n, o, x.numel()))
+    if not natives:
+        return []
+    _on_current_stream()
+    return _native.ml_apply_batch_device(natives, x.data_ptr(), offsets, transpose=transpose, sync=False)
+
+
 def bicgstab_batch(As, b, offsets, Ms, x0=None, maxiter=100, rtol=0.0, check_every=0, stats=None):
     """Left-preconditioned BiCGstab for MANY small systems in ONE kernel launch (one workgroup per system runs the whole loop -- SpMV,
     apply, dot products, updates, convergence test -- with no host round trip).
 
     ``As``: a list of DeviceCSR; ``Ms``: as many members, each of them an ``ilupp_amd.ILUCPPreconditioner`` / ``ILUTPPreconditioner``
     object or a ``PivotedOperator``; or anything ``cg_batch`` takes (a ``DevicePreconditioner`` of the ILU0 / ILUT / ILUC / IChol0 /
-    ICholT kinds, a ``FactorOperator`` or a host class of the ctypes binding); or ``None`` (no preconditioner) -- mixed at will, each
-    object at most once.  Every batch goes through ilupp_hip_bicgstab_batch_device (k_bicgstab_batch, which takes all three kinds of
-    member in the same launch).  ``b``: ONE contiguous 1-D fp64 CUDA tensor, member k's right-hand side is
+    ICholT kinds, a ``FactorOperator`` or a host class of the ctypes binding); or a ``MultilevelOperator`` (a multilevel ILU++ object in
+    its wrapper); or ``None`` (no preconditioner) -- mixed at will, each object at most once.  A batch without a multilevel member goes
+    through ilupp_hip_bicgstab_batch_device (k_bicgstab_batch, which takes the other kinds of member in the same launch); one with a
+    multilevel member through ilupp_hip_bicgstab_batch_ml_device, whose launch is a second instantiation of that kernel with the
+    multilevel apply as a choice on the member's descriptor and an LDS cap of its own (``_native.bicgstab_batch_ml_max_n()``).  ``b``: ONE contiguous 1-D fp64 CUDA tensor, member k's right-hand side is
     ``b[offsets[k] : offsets[k] + n_k]``; ``x0``: the same layout.  Returns a new tensor of b's shape, a clone of ``x0`` or zeros, whose
     member slices hold the solutions; every other element is untouched.  Per member the loop of ``bicgstab`` for one column: ``maxiter``,
     ``rtol`` and ``check_every`` mean what they mean there, a member that converges or breaks down stops alone, and every member has the
@@ -309,8 +392,9 @@ def bicgstab_batch(As, b, offsets, Ms, x0=None, maxiter=100, rtol=0.0, check_eve
     call).  Ordered on torch's current stream; the host waits only when ``stats`` is asked for or a member takes route 1 or 2, so
     ``refactor_batch_(check=False)`` -> ``bicgstab_batch`` -> ``refactor_batch_`` runs without a host wait.  ValueError for a wrong
     tensor, lists of unequal length, a slice outside ``b`` or a matrix and a preconditioner of different dimensions; TypeError for a
-    member of another class or of the "ILUpp" kind -- before any native call.  Out of scope: a transposed solve, host (numpy) vectors,
-    the multilevel class, several right-hand sides per member."""
+    member of another class or a bare multilevel object (the "ILUpp" kind, ``ILUppPreconditioner``: wrap it in a
+    ``MultilevelOperator``) -- before any native call.  Out of scope: a transposed solve, host (numpy) vectors, several right-hand sides
+    per member."""
     As, Ms, offsets = list(As), list(Ms), [int(o) for o in offsets]
     natives, dims = [], []
     for A in As:
@@ -320,6 +404,9 @@ def bicgstab_batch(As, b, offsets, Ms, x0=None, maxiter=100, rtol=0.0, check_eve
         if M is None:
             natives.append(None)
             continue
+        if isinstance(M, MultilevelOperator):
+            natives.append(M.pr)
+            continue
         pr = M.pr if isinstance(M, PivotedOperator) else getattr(M, "pr", M)
         if not isinstance(pr, _native.PivotedPreconditioner):
             try:
@@ -327,7 +414,8 @@ def bicgstab_batch(As, b, offsets, Ms, x0=None, maxiter=100, rtol=0.0, check_eve
             except TypeError:
                 raise TypeError("bicgstab_batch takes ILUCPPreconditioner / ILUTPPreconditioner instances of the ctypes binding or "
                                 "PivotedOperators, ILU0 / ILUT / ILUC / IChol0 / ICholT preconditioners (DevicePreconditioners of those "
-                                "kinds, FactorOperators or the host classes) or None, got %s" % type(M).__name__) from None
+                                "kinds, FactorOperators or the host classes), MultilevelOperators or None, got %s"
+                                % type(M).__name__) from None
         natives.append(pr)
     if not (len(As) == len(Ms) == len(offsets)):
         raise ValueError("%d matrices, %d preconditioners and %d offsets" % (len(As), len(Ms), len(offsets)))
@@ -339,14 +427,16 @@ def bicgstab_batch(As, b, offsets, Ms, x0=None, maxiter=100, rtol=0.0, check_eve
     if x0 is not None and x0.shape != b.shape:
         raise ValueError("x0: expected shape %s, got %s" % (tuple(b.shape), tuple(x0.shape)))
     for k, (A, M, pr, o) in enumerate(zip(As, Ms, natives, offsets)):
-        n = A.n if pr is None else pr._n if isinstance(pr, _native.PivotedPreconditioner) else _factor_n(M, pr)
+        n = A.n if pr is None else pr._n if isinstance(pr, (_native.PivotedPreconditioner, _native.MultilevelPreconditioner)) else _factor_n(M, pr)
         if A.n != n:
             raise ValueError("member %d: the matrix has dimension %d, the preconditioner %d" % (k, A.n, n))
         if o < 0 or o + n > b.numel():
             raise ValueError("a vector of %d elements at offset %d does not lie inside b (%d elements)" % (n, o, b.numel()))
         dims.append(n)
-    return _solve_batch(bicgstab, _native.bicgstab_batch_device, 7, "init", As, Ms, natives, dims, b, offsets, x0, maxiter, rtol,
-                        check_every, stats)
+    # (a batch with a multilevel member: the entry with the third handle list, whose launch is the kernel's second instantiation)
+    has_ml = any(isinstance(pr, _native.MultilevelPreconditioner) for pr in natives)
+    return _solve_batch(bicgstab, _native.bicgstab_batch_ml_device if has_ml else _native.bicgstab_batch_device, 7, "init", As, Ms, natives,
+                        dims, b, offsets, x0, maxiter, rtol, check_every, stats)
 
 
 def _solve_batch(single, entry, work_factor, relres, As, Ms, natives, dims, b, offsets, x0, maxiter, rtol, check_every, stats):

@@ -305,6 +305,27 @@ int ilupp_hip_ml_apply_device(ilupp_ml *p, double *d_x, int64_t len, int transpo
 /* one half of the split preconditioner on a vector in HBM: apply_preconditioner_left / _right (preconditioner_implementation.h:441-453,
  * :468-486), what the reference's solver loop uses with SPLIT preconditioning (solving_routines_implementation.h:81); left != 0: the left part */
 int ilupp_hip_ml_apply_part_device(ilupp_ml *p, double *d_x, int64_t len, int transpose, int left, int sync);
+/* Many multilevel objects (each at most once) applied at once: member i's vector is d_x + offsets[i] (offsets: a host array of `count`
+ * entries, in doubles), of length n_i, in place; what lies between the vectors is left untouched.  ONE launch for all members whose n fits
+ * the kernel's LDS cap (one workgroup per member, which walks the member's levels up and down as the single apply does -- scale / permute,
+ * one sweep with the unknowns in LDS, take / permute, on the last n_level entries of the vector -- k_ml_apply_batch, sptrsv_batch.hip); a
+ * member that is too large (route 1: for the cap, or, with n > 4096, for a launch it would have to itself) or one of whose level objects
+ * has a factor with an empty row (route 2) goes through ilupp_hip_ml_apply_device's path inside the same call, so the call succeeds
+ * wherever the loop of single applies would.  route (may be NULL) receives 0, 1 or 2 per member.  Every result has the bits of
+ * ilupp_hip_ml_apply_device.  Ordered on the caller's stream; sync == 0 returns without waiting (and without reading the members' error
+ * words), sync != 0 waits and reports a member whose sweep gave up as ILUPP_ERR_TIMEOUT, "member i of the batch: triangular solve:
+ * dependency wait timed out ..." (that member's vector is unspecified, the other members' vectors are complete).  A later single apply or
+ * the destruction of a member is queued behind a launch that was not waited for.  ILUPP_BATCH_APPLY_MAX_N (read on every call) lowers the
+ * cap.  Refused with ILUPP_ERR_INVALID before any device call: null lists or members, a negative count, a member that is not a live
+ * multilevel object, a member named twice.  count == 0 returns ILUPP_OK without touching the device. */
+int ilupp_hip_ml_apply_batch_device(int32_t count, ilupp_ml *const *members, double *d_x, const int64_t *offsets, int transpose, int sync,
+                                    int32_t *route);
+/* The same on host vectors x[i] of len[i] == n_i doubles, in place: all vectors staged through one device buffer (one packed upload, one
+ * download); waits for the result.  A member that failed keeps its vector as it was. */
+int ilupp_hip_ml_apply_batch(int32_t count, ilupp_ml *const *members, double *const *x, const int64_t *len, int transpose, int32_t *route);
+/* the largest n that takes route 0 of the two entries above on the current device (what the device gives a workgroup of k_ml_apply_batch
+ * in LDS, ILUPP_BATCH_APPLY_MAX_N applied); negative: an error code */
+int64_t ilupp_hip_ml_apply_batch_max_n(void);
 int ilupp_hip_ml_sync(ilupp_ml *p);
 /* levels() (preconditioner.h:298), total_nnz (:312), dim(k) */
 int32_t ilupp_hip_ml_levels(const ilupp_ml *p);
@@ -473,6 +494,24 @@ int ilupp_hip_bicgstab_batch_device(int32_t count, ilupp_precond *const *plain, 
 /* the largest n that takes route 0 in ilupp_hip_bicgstab_batch_device on the current device (ILUPP_BATCH_APPLY_MAX_N applied);
  * negative: an error code */
 int64_t ilupp_hip_bicgstab_batch_max_n(void);
+/* ilupp_hip_bicgstab_batch_device with a third list: member i is plain[i], pivoted[i], multilevel[i] (each list may be NULL as a whole, at
+ * most one of the three non-NULL per member) or a member without a preconditioner.  A launch that holds a multilevel member runs a second
+ * instantiation of the kernel (k_bicgstab_batch<true>), in which a member's apply is a choice on its descriptor: a multilevel member walks
+ * its levels up and down inside its workgroup as in ilupp_hip_ml_apply_batch_device and has the bits of the same solve done alone with
+ * ilupp_hip_ml_apply_device; every other member has the bits it has in ilupp_hip_bicgstab_batch_device.  That instantiation has an LDS cap
+ * of its own (ilupp_hip_bicgstab_batch_ml_max_n), by which ALL members of such a launch are routed; where no multilevel member takes
+ * route 0 (none given, or all too large or degenerate) the call is ilupp_hip_bicgstab_batch_device's launch with its cap.  Route 2 for a
+ * multilevel member: a level object with an empty row.  Everything else -- arguments, outputs, ordering, sync, refusals -- as there; a
+ * member of `multilevel` that is not a live multilevel object, or a member named in two lists, is refused with ILUPP_ERR_INVALID. */
+int ilupp_hip_bicgstab_batch_ml_device(int32_t count, ilupp_precond *const *plain, ilupp_ilucp *const *pivoted, ilupp_ml *const *multilevel,
+                                       const int64_t *n, const double *const *d_data, const int32_t *const *d_indices,
+                                       const int32_t *const *d_indptr, const int64_t *nnz, const double *d_b, const double *d_x0, double *d_x,
+                                       const int64_t *offsets, double *d_work, int64_t work_doubles, int32_t maxiter, double rtol,
+                                       int32_t check_every, int64_t *d_iterations, int32_t *d_flags, double *d_rr, double *d_init, int sync,
+                                       int32_t *route);
+/* the largest n that takes route 0 in a launch of ilupp_hip_bicgstab_batch_ml_device that holds a multilevel member, on the current
+ * device (ILUPP_BATCH_APPLY_MAX_N applied); negative: an error code */
+int64_t ilupp_hip_bicgstab_batch_ml_max_n(void);
 /* The numeric re-factorisation of MANY small ILU(0) objects at once (same patterns, new values): ONE launch, one workgroup per member,
  * the member's rows side by side inside it (k_ilu0_refactor_batch, ilu0_batch.hip).  members: `count` distinct ILU(0) objects; d_data /
  * d_indices / d_indptr: host arrays of `count` DEVICE pointers, member i's matrix in CSR form as ilupp_hip_ilu0_refactor_device takes
