@@ -207,6 +207,17 @@ class ILUTPreconditioner(_BlockApply, _HipPreconditioner):
     def __init__(self, A, fill_in=100, threshold=0.1):
         super().__init__(A, lambda m: _backend.ILUTPreconditioner(*m, fill_in, threshold))
 
+    @classmethod
+    def batch(cls, matrices, fill_in=100, threshold=0.1):
+        """``[ILUTPreconditioner(A, fill_in, threshold) for A in matrices]`` from ONE native call, for MANY SMALL matrices (all CSR or
+        all CSC; one parameter set per batch): the rows of all members in one launch of the single constructor's wave kernel, claimed
+        round-robin so that the members' dependency chains advance side by side, then one read-back and one fill launch
+        (``ilupp_hip_ilut_create_batch``), where the loop pays five host waits and a nearly empty rows launch per object.  Factors,
+        ``total_nnz`` and every apply of a member have the bits of the singly built object.  A batch of one, a budget min(fill_in, n)
+        above 256 and a member with a row that outgrows the launch's 64 K pieces are built by the single constructor inside the same
+        call.  A zero pivot raises the constructor's RuntimeError, named by the member's number; no object is returned then."""
+        return _batch(cls, matrices, lambda ms, is_csr: _native.ILUTPreconditioner_batch(ms, is_csr, fill_in, threshold))
+
 
 class ILUCPreconditioner(_BlockApply, _HipPreconditioner):
     """ILUC, the Crout ILU of Li, Saad and Chow: at most `fill_in` entries per column of L and row of U, relative drop `threshold`."""

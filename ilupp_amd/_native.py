@@ -214,6 +214,11 @@ def lib():
     L.ilupp_hip_ichol0_refactor_batch_max_n.restype = ctypes.c_int64
     L.ilupp_hip_ichol0_create_batch.argtypes = L.ilupp_hip_ilu0_create_batch.argtypes
     L.ilupp_hip_ichol0_create_batch_device.argtypes = L.ilupp_hip_ilu0_create_batch_device.argtypes
+    L.ilupp_hip_ilut_create_batch.argtypes = [ctypes.c_int32, ctypes.POINTER(_VP), ctypes.POINTER(_VP), ctypes.POINTER(_VP), _I32P, ctypes.c_int,
+                                              ctypes.c_int32, ctypes.c_double, ctypes.POINTER(_VP), _I32P, _I32P]
+    L.ilupp_hip_ilut_create_batch_device.argtypes = [ctypes.c_int32, ctypes.POINTER(_VP), ctypes.POINTER(_VP), ctypes.POINTER(_VP), _I32P,
+                                                     ctypes.POINTER(ctypes.c_int64), ctypes.c_int, ctypes.c_int32, ctypes.c_double,
+                                                     ctypes.POINTER(_VP), _I32P, _I32P]
     L.ilupp_hip_ilucp_total_nnz.argtypes = [_VP]
     L.ilupp_hip_ilucp_total_nnz.restype = ctypes.c_int64
     L.ilupp_hip_ilucp_zero_pivots.argtypes = [_VP]
@@ -259,6 +264,7 @@ ABI_SYMBOLS = [
     "ilupp_hip_ilu0_create_batch", "ilupp_hip_ilu0_create_batch_device",
     "ilupp_hip_ichol0_refactor_device", "ilupp_hip_ichol0_refactor_batch_device", "ilupp_hip_ichol0_refactor_batch_max_n",
     "ilupp_hip_ichol0_create_batch", "ilupp_hip_ichol0_create_batch_device",
+    "ilupp_hip_ilut_create_batch", "ilupp_hip_ilut_create_batch_device",
     "ilupp_hip_apply_block", "ilupp_hip_apply_block_device", "ilupp_hip_block_path",
     "ilupp_hip_spmm_device", "ilupp_hip_block_dot_device", "ilupp_hip_cg_block_update_device", "ilupp_hip_bicgstab_block_update_device",
 ]
@@ -696,11 +702,12 @@ def _ilu0_batch_result(rc, cnt, out, status):
     return [Preconditioner(_VP(out[k])) for k in range(cnt)]
 
 
-def ILU0Preconditioner_batch(matrices, is_csr, routes=None, entry="ilupp_hip_ilu0_create_batch"):
+def ILU0Preconditioner_batch(matrices, is_csr, routes=None, entry="ilupp_hip_ilu0_create_batch", extra=()):
     """one ILU(0) preconditioner per matrix of `matrices` (a list of (data, indices, indptr)), built by two launches of one workgroup per
     matrix around one read-back (ilupp_hip_ilu0_create_batch): the factors and applies of the objects the constructor gives one at a
     time, bit for bit.  `routes`, when a list, receives every member's route (0 = the launches, 1 = the single constructor inside the
-    same call).  `entry`: the C entry (IChol0Preconditioner_batch names its own)"""
+    same call).  `entry`: the C entry (IChol0Preconditioner_batch names its own); `extra`: its arguments between is_csr and the outputs
+    (ILUTPreconditioner_batch: the fill budget and the threshold)"""
     cnt = len(matrices)
     if cnt == 0:
         return []
@@ -713,13 +720,13 @@ def ILU0Preconditioner_batch(matrices, is_csr, routes=None, entry="ilupp_hip_ilu
         ns.append(args[3])
     N = (ctypes.c_int32 * cnt)(*ns)
     out, status, route = (_VP * cnt)(), (ctypes.c_int32 * cnt)(), (ctypes.c_int32 * cnt)()
-    rc = getattr(lib(), entry)(cnt, D, I, P, N, 1 if is_csr else 0, out, status, route)
+    rc = getattr(lib(), entry)(cnt, D, I, P, N, 1 if is_csr else 0, *extra, out, status, route)
     if routes is not None:
         routes[:] = list(route)
     return _ilu0_batch_result(rc, cnt, out, status)
 
 
-def ILU0Preconditioner_batch_device(matrices, is_csr, routes=None, entry="ilupp_hip_ilu0_create_batch_device"):
+def ILU0Preconditioner_batch_device(matrices, is_csr, routes=None, entry="ilupp_hip_ilu0_create_batch_device", extra=()):
     """the same for matrices already resident in HBM: `matrices` is a list of (data_ptr, indices_ptr, indptr_ptr, n, nnz) of device CSR
     arrays (ilupp_hip_ilu0_create_batch_device).  Ordered on the caller's stream (set_caller_stream); the call returns when every member
     is built"""
@@ -731,7 +738,7 @@ def ILU0Preconditioner_batch_device(matrices, is_csr, routes=None, entry="ilupp_
     for k, (d, i, p, n, nnz) in enumerate(matrices):
         D[k], I[k], P[k], N[k], NNZ[k] = d, i, p, int(n), int(nnz)
     out, status, route = (_VP * cnt)(), (ctypes.c_int32 * cnt)(), (ctypes.c_int32 * cnt)()
-    rc = getattr(lib(), entry)(cnt, D, I, P, N, NNZ, 1 if is_csr else 0, out, status, route)
+    rc = getattr(lib(), entry)(cnt, D, I, P, N, NNZ, 1 if is_csr else 0, *extra, out, status, route)
     if routes is not None:
         routes[:] = list(route)
     return _ilu0_batch_result(rc, cnt, out, status)
@@ -747,6 +754,21 @@ def IChol0Preconditioner_batch(matrices, is_csr, routes=None):
 def IChol0Preconditioner_batch_device(matrices, is_csr, routes=None):
     """the same for matrices already resident in HBM, as ILU0Preconditioner_batch_device (ilupp_hip_ichol0_create_batch_device)"""
     return ILU0Preconditioner_batch_device(matrices, is_csr, routes, entry="ilupp_hip_ichol0_create_batch_device")
+
+
+def ILUTPreconditioner_batch(matrices, is_csr, fill_in, threshold, routes=None):
+    """one ILUT(fill_in, threshold) preconditioner per matrix of `matrices` (a list of (data, indices, indptr)): the rows of all members in
+    one launch, one read-back, one fill launch (ilupp_hip_ilut_create_batch).  The factors and applies of the objects the constructor
+    gives one at a time, bit for bit; `routes` as for ILU0Preconditioner_batch (1: a batch of one, a budget of the largest capacity
+    class, a member with a row that fits no tier of the launch)"""
+    return ILU0Preconditioner_batch(matrices, is_csr, routes, entry="ilupp_hip_ilut_create_batch",
+                                    extra=(ctypes.c_int32(int(fill_in)), ctypes.c_double(float(threshold))))
+
+
+def ILUTPreconditioner_batch_device(matrices, is_csr, fill_in, threshold, routes=None):
+    """the same for matrices already resident in HBM, as ILU0Preconditioner_batch_device (ilupp_hip_ilut_create_batch_device)"""
+    return ILU0Preconditioner_batch_device(matrices, is_csr, routes, entry="ilupp_hip_ilut_create_batch_device",
+                                           extra=(ctypes.c_int32(int(fill_in)), ctypes.c_double(float(threshold))))
 
 
 def _create_device(fn, d_data, d_indices, d_indptr, n, is_csr, *extra):

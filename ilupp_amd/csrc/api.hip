@@ -720,7 +720,8 @@ void ensure_transposed(ilupp_precond *p)
 
 // What the single sweeps of a batch-built ILU(0) object need -- cuts and schedules, tilings, slot tables, descriptors --, on first use and
 // from the factors' own patterns: L forward, U backward, as an ILUT object gets its own (ilut_create_common).  max_row_len stays A's
-// longest row (no row of L or U is longer): it is what the batched re-factorisation routes by.
+// longest row (no row of L or U is longer): it is what the batched re-factorisation routes by.  A batch-built ILUT object
+// (ilupp_hip_ilut_create_batch*) takes the same branch: its max_row_len is the longest row of L or U already, what sweep_tables finds.
 void ensure_sweep_tables(ilupp_precond *p)
 {
     if (!p->batch_built || p->sweeps_ready) return;
@@ -1371,9 +1372,10 @@ static int iluc_create_common(DevMat &A, int32_t n, int is_csr, int32_t max_fill
     return ILUPP_OK;
 }
 
-static int ilut_create_common(DevMat &A, int32_t n, int is_csr, int32_t max_fill_in, double threshold, ilupp_precond **out)
+static int ilut_create_common(DevMat &A, int32_t n, int is_csr, int32_t max_fill_in, double threshold, ilupp_precond **out,
+                              ilupp_precond *made = nullptr)
 {
-    ObjGuard g(new_obj(n));
+    ObjGuard g(made ? made : new_obj(n));
     ilupp_precond *p = g.p;
     p->kind = KIND_LU;
     p->nnz_mode = NNZ_ILUT;
@@ -1740,7 +1742,7 @@ const char *ilupp_hip_path(const ilupp_precond *p)
         if (p->fperm) return "ilu0:level-order";
         return p->prog_f3 ? "ilu0:csr-program" : "ilu0:csr";
     }
-    if (p->kind == KIND_LU) return "ilut";
+    if (p->kind == KIND_LU) return p->batch_built ? "ilut:batch" : "ilut";
     if (p->kind == KIND_UTU) return "iluc";
     if (p->llt_diag_last && p->batch_built) return "ichol0:batch";
     return p->llt_diag_last ? (p->chol_static ? "ichol0:static-level-major" : "ichol0") : (p->icholt_grid ? "icholt:grid-static" : "icholt");
@@ -2536,6 +2538,11 @@ struct BatchScratch {
     BatchBuf<RefactorDesc> rtable{64, true};
     BatchBuf<CreateInfo> cinfo{64, true};         // a construction's symbolic records, read back through the pinned copy
     BatchBuf<int32_t> cstat{64, false};           // ... and the status words of its create launch
+    // a batched ILUT construction: the members' descriptors, the ticket maps of its rows launches (segments, then the member order) and the
+    // members' records, read back through the pinned copy
+    BatchBuf<IlutBatchDesc> ttable{64, true};
+    BatchBuf<int32_t> ttick{512, true};
+    BatchBuf<IlutBatchInfo> tinfo{64, true};
     // the two tables of a batched multilevel apply (member records, and the level records of all of them), each cached on its own
     BatchBuf<MlApplyDesc> mltable{64, true};
     BatchBuf<MlLevelDesc> mllevels{64, true};
@@ -3688,8 +3695,9 @@ int ichol0_create_single(const CreateMember &m, int is_csr, bool staged, hipEven
     return ichol0_create_common(A, m.n, out, made);
 }
 
-// the arguments of the *_create_batch_device entries, then the run
-int factor_create_batch_device(const FactorBatchKind &K, int32_t count, const double *const *d_data, const int32_t *const *d_indices,
+// the arguments of the *_create_batch_device entries, then the run: run(scratch, count, members, is_csr, staged, out, status, route)
+template <class Run>
+int factor_create_batch_device(Run &&run, int32_t count, const double *const *d_data, const int32_t *const *d_indices,
                                const int32_t *const *d_indptr, const int32_t *n, const int64_t *nnz, int is_csr, ilupp_precond **out,
                                int32_t *status, int32_t *route)
 {
@@ -3703,11 +3711,12 @@ int factor_create_batch_device(const FactorBatchKind &K, int32_t count, const do
     }
     if (count == 0) return ILUPP_OK;
     std::lock_guard<std::mutex> lk(g_batch_mu);
-    return factor_create_batch_run(K, batch_scratch(), count, m.data(), is_csr, false, out, status, route);
+    return run(batch_scratch(), count, m.data(), is_csr, false, out, status, route);
 }
 
 // ... of the host-array entries: all members through ONE packed block, one upload
-int factor_create_batch_host(const FactorBatchKind &K, int32_t count, const double *const *data, const int32_t *const *indices,
+template <class Run>
+int factor_create_batch_host(Run &&run, int32_t count, const double *const *data, const int32_t *const *indices,
                              const int32_t *const *indptr, const int32_t *n, int is_csr, ilupp_precond **out, int32_t *status, int32_t *route)
 {
     if (count < 0 || !data || !indices || !indptr || !n || !out) { set_error("null argument"); return ILUPP_ERR_INVALID; }
@@ -3746,10 +3755,218 @@ int factor_create_batch_host(const FactorBatchKind &K, int32_t count, const doub
     }
     if (total > 0) ILUPP_HIP(hipMemcpyAsync(S.stage.d, S.stage.h, sizeof(double) * total, hipMemcpyHostToDevice, S.stream));
     ILUPP_HIP(hipEventRecord(S.in_ev, S.stream));
-    const int rc = factor_create_batch_run(K, S, count, m.data(), is_csr, true, out, status, route);
+    const int rc = run(S, count, m.data(), is_csr, true, out, status, route);
     // (the staged matrices are read by nothing once the call is over: every member's construction has been waited for)
     if (rc) (void)hipStreamSynchronize(S.stream);
     return rc;
+}
+
+// the run of an ILU(0) or IChol(0) construction, as the two entry shapes above take it
+auto factor_run(const FactorBatchKind &K)
+{
+    return [&K](BatchScratch &S, int32_t count, const CreateMember *m, int is_csr, bool staged, ilupp_precond **out, int32_t *status, int32_t *route) {
+        return factor_create_batch_run(K, S, count, m, is_csr, staged, out, status, route);
+    };
+}
+
+// ---- many ILUT objects built at once: the rows of all members in one launch per LDS class (k_ilut_rows_batch, ilut_wp.hip), one read-back,
+// one fill launch (ilut.hip) ----
+
+// the single constructor inside a batched ILUT construction (route 1)
+int ilut_create_single(const CreateMember &m, int is_csr, bool staged, hipEvent_t in_ev, int32_t max_fill_in, double threshold, ilupp_precond **out)
+{
+    if (!staged && (int64_t)read_device_nnz(m.indptr, m.n) != m.nnz) {
+        set_error("ILUT: the number of stored entries handed in is not indptr[n]");
+        return ILUPP_ERR_INVALID;
+    }
+    ilupp_precond *made = new_obj(m.n);
+    if (staged && hipStreamWaitEvent(made->stream, in_ev, 0) != hipSuccess) { destroy_obj(made); set_error("batched construction: no stream"); return ILUPP_ERR_HIP; }
+    DevMat A = borrow_csr(m.data, m.indices, m.indptr, m.n, m.nnz, true);
+    return ilut_create_common(A, m.n, is_csr, max_fill_in, threshold, out, made);
+}
+
+// the stream is idle when the scope ends, however it ends: the pool blocks declared before it go back only then
+struct StreamIdle {
+    hipStream_t s;
+    ~StreamIdle() { (void)hipStreamSynchronize(s); }
+};
+
+// What the two entries of the batched ILUT construction do once the matrices are in device memory (count > 0; the caller holds the
+// construction lock and the batch lock; staged as for factor_create_batch_run).  Steady state, on the scratch's stream: the descriptors and
+// the ticket maps (two small uploads), the record initialisation of all members, the rows launch (two when the members' clamped budgets
+// fall into both LDS classes), the count-and-scan launch, ONE read-back of the members' records, the index and value arrays from the pool,
+// the fill launch.  Routes: 0 = built by the launches; 1 = built by ilut_create_single inside this call -- a batch of one, a clamped budget
+// of the largest capacity class, a member whose record says status 3 (a row that fits no tier of the launch), or a call whose slabs would
+// not fit the memory budget.  Failures as factor_create_batch_run reports them.
+int ilut_create_batch_run(BatchScratch &S, int32_t count, const CreateMember *m, int is_csr, bool staged, int32_t max_fill_in, double threshold,
+                          ilupp_precond **out, int32_t *status, int32_t *route)
+{
+    hipStream_t bs = S.stream;
+    for (hipEvent_t &e : S.tev) if (!e) ILUPP_HIP(hipEventCreate(&e));
+    std::vector<int> rcs((size_t)count, ILUPP_OK);
+    std::vector<std::string> msgs((size_t)count);
+    std::vector<int32_t> rt((size_t)count, 0);
+    CreatedObjects objs;
+    objs.v.assign((size_t)count, nullptr);
+    std::vector<int32_t> cand;                       // the members of the launches
+    std::vector<int32_t> pm((size_t)count, 1);       // the clamped budgets (ILUT.hpp:211-212)
+    size_t slab_bytes = 0;
+    int64_t rows = 0;
+    auto rec_bytes = [](int32_t p) { return ((((size_t)4 + 4 * (size_t)p + 7) & ~(size_t)7) + 8 * (size_t)p + 127) & ~(size_t)127; };
+    for (int32_t i = 0; i < count; ++i) {
+        if (m[i].n <= 0 || !m[i].indptr) { rcs[(size_t)i] = ILUPP_ERR_INVALID; msgs[(size_t)i] = "matrix has size 0!"; continue; }
+        if (m[i].nnz < 0 || m[i].nnz + (int64_t)m[i].n > INT32_MAX) { rcs[(size_t)i] = ILUPP_ERR_INVALID; msgs[(size_t)i] = "ILUT: too many stored entries for 32-bit indices"; continue; }
+        const int32_t p = pm[(size_t)i] = std::min(std::max(max_fill_in, 1), m[i].n);
+        if (count == 1 || ilut_batch_class(p) < 0 || cand.size() >= 65535) { rt[(size_t)i] = 1; continue; }
+        cand.push_back(i);
+        slab_bytes += (size_t)m[i].n * ((size_t)p * 12 + 4 + rec_bytes(p));
+        rows += m[i].n;
+    }
+    // (the slabs of a call are held together: a call that asks for more than the single path's working arrays do takes the single path
+    // member by member; the tickets of a launch are counted in 32 bits)
+    if (slab_bytes > ((size_t)16 << 30) || rows > (int64_t)1 << 30) { for (int32_t i : cand) rt[(size_t)i] = 1; cand.clear(); }
+    if (!staged) order_after_caller(bs, S.cev[0]);
+    const int32_t nc = (int32_t)cand.size();
+    const bool debug = getenv("ILUPP_DEBUG") != nullptr;
+    bool failed = false;
+    for (int32_t i = 0; i < count; ++i) failed = failed || rcs[(size_t)i] != ILUPP_OK;
+    if (nc > 0 && !failed) {
+        PoolBlock b_Lri, b_Lrv, b_Llen, b_Urec, b_ctrl;
+        IlutBatchWork work;
+        StreamIdle idle{bs};                         // (declared last: the wait comes before the blocks above are given back)
+        // the slabs of all members, one block per array; the control blocks behind one block of the launches' own (its words 0 and 1: the ticket counters)
+        std::vector<size_t> oL((size_t)nc), oN((size_t)nc), oU((size_t)nc);
+        size_t tL = 0, tN = 0, tU = 0;
+        for (int32_t k = 0; k < nc; ++k) {
+            const int32_t i = cand[(size_t)k];
+            oL[(size_t)k] = tL; oN[(size_t)k] = tN; oU[(size_t)k] = tU;
+            tL += (size_t)m[i].n * (size_t)pm[(size_t)i]; tN += (size_t)m[i].n; tU += (size_t)m[i].n * rec_bytes(pm[(size_t)i]);
+        }
+        ILUPP_HIP(b_Lri.alloc(sizeof(int32_t) * tL));
+        ILUPP_HIP(b_Lrv.alloc(sizeof(double) * tL));
+        ILUPP_HIP(b_Llen.alloc(sizeof(int32_t) * tN));
+        ILUPP_HIP(b_Urec.alloc(tU));
+        ILUPP_HIP(b_ctrl.alloc(128 * ((size_t)nc + 1)));
+        std::vector<IlutBatchDesc> fresh((size_t)nc);
+        std::vector<int32_t> nk((size_t)nc), cls[2];
+        int64_t max_words = 0;
+        int32_t max_n = 0;
+        for (int32_t k = 0; k < nc; ++k) {
+            const int32_t i = cand[(size_t)k], n = m[i].n, p = pm[(size_t)i];
+            ilupp_precond *q = objs.v[(size_t)i] = new_obj(n);
+            q->kind = KIND_LU; q->nnz_mode = NNZ_ILUT; q->input_csc = !is_csr;
+            for (DevMat *M : {&q->Lc, &q->Uc}) {
+                M->n = n; M->is_csr = true; M->owns = true;
+                ILUPP_HIP(pool_malloc(&M->ptr, sizeof(int32_t) * (size_t)(n + 1)));
+            }
+            const size_t voff = ((size_t)4 + 4 * (size_t)p + 7) & ~(size_t)7, rec = rec_bytes(p);
+            unsigned char *urec = b_Urec.as<unsigned char>() + oU[(size_t)k];
+            IlutBatchDesc &d = fresh[(size_t)k];
+            memset(&d, 0, sizeof(d));
+            d.aptr = m[i].indptr; d.aidx = m[i].indices; d.aval = m[i].data;
+            d.Lri = b_Lri.as<int32_t>() + oL[(size_t)k]; d.Lrv = b_Lrv.as<double>() + oL[(size_t)k]; d.Llen = b_Llen.as<int32_t>() + oN[(size_t)k];
+            d.Ulen = reinterpret_cast<int32_t *>(urec); d.Uri = reinterpret_cast<int32_t *>(urec + 4); d.Urv = reinterpret_cast<double *>(urec + voff);
+            d.ctrl = b_ctrl.as<int32_t>() + 32 * ((size_t)k + 1);
+            d.lptr = q->Lc.ptr; d.uptr = q->Uc.ptr;
+            d.ul = {(int32_t)(rec / 4), (int32_t)(rec / 8), (int32_t)(rec / 4)};
+            d.n = n; d.p = p; d.vw = (int32_t)(voff / 8);
+            nk[(size_t)k] = n;
+            cls[ilut_batch_class(p)].push_back(k);
+            max_words = std::max(max_words, (int64_t)n * d.ul.sv);
+            max_n = std::max(max_n, n);
+        }
+        // the ticket maps of the (at most two) rows launches: round-robin over the members that still have rows.  ILUPP_ILUT_BATCH_ORDER=member
+        // is the measurement's other order (profiles/r26_ilut_batch.txt): one member after the other.
+        const char *order_env = getenv("ILUPP_ILUT_BATCH_ORDER");
+        const bool member_major = order_env && strcmp(order_env, "member") == 0;
+        std::vector<IlutBatchSeg> seg;
+        std::vector<int32_t> order;
+        int32_t seg0[3] = {0, 0, 0};
+        int64_t tickets[2] = {0, 0};
+        for (int c = 0; c < 2; ++c) {
+            if (!cls[c].empty()) tickets[c] = ilut_batch_tickets(cls[c], nk, member_major, &seg, &order);
+            seg0[c + 1] = (int32_t)seg.size();
+        }
+        std::vector<int32_t> tick(4 * seg.size() + order.size());
+        memcpy(tick.data(), seg.data(), sizeof(IlutBatchSeg) * seg.size());
+        memcpy(tick.data() + 4 * seg.size(), order.data(), sizeof(int32_t) * order.size());
+        batch_upload(bs, S.ttable, fresh, false);
+        batch_upload(bs, S.ttick, tick, false);
+        S.tinfo.reserve(bs, (size_t)nc);
+        int32_t *d_counters = b_ctrl.as<int32_t>();
+        OR_RETURN(ilut_batch_init_launch(bs, nc, S.ttable.d, max_words, d_counters));
+        OR_RETURN(ilut_batch_work(bs, tickets[0], tickets[1], &work));
+        ILUPP_HIP(hipEventRecord(S.tev[0], bs));
+        for (int c = 0; c < 2; ++c)
+            OR_RETURN(ilut_rows_batch_launch(bs, c, S.ttable.d, reinterpret_cast<const IlutBatchSeg *>(S.ttick.d) + seg0[c], seg0[c + 1] - seg0[c],
+                                             S.ttick.d + 4 * seg.size(), (int32_t)tickets[c], d_counters + c, threshold, work));
+        ILUPP_HIP(hipEventRecord(S.tev[1], bs));
+        // (queued unconditionally behind the rows: a member that failed has lengths within its slabs like every other)
+        OR_RETURN(ilut_batch_count_launch(bs, nc, S.ttable.d, S.tinfo.d));
+        // the call's one read-back
+        ILUPP_HIP(hipMemcpyAsync(S.tinfo.h, S.tinfo.d, sizeof(IlutBatchInfo) * (size_t)nc, hipMemcpyDeviceToHost, bs));
+        ILUPP_HIP(stream_sync(bs));
+        float rows_ms = 0.f;
+        ILUPP_HIP(hipEventElapsedTime(&rows_ms, S.tev[0], S.tev[1]));
+        std::vector<int32_t> launched;
+        for (int32_t k = 0; k < nc; ++k) {
+            const int32_t i = cand[(size_t)k];
+            const IlutBatchInfo &o = S.tinfo.h[k];
+            ilupp_precond *q = objs.v[(size_t)i];
+            if (debug)
+                fprintf(stderr, "[ilupp] ilut_batch: member %d: %d of %d rows outgrew LDS (pool %d, U slots %d, kept %d), %d of them the pool-in-LDS tier too, status %d, rows launches %.3f ms\n",
+                        i, o.outgrew, m[i].n, o.pool, o.uslots, o.kept, o.left_tier2, o.status, rows_ms);
+            if (o.status == 3) { rt[(size_t)i] = 1; continue; }
+            if (o.status != 0) { rcs[(size_t)i] = ILUPP_ERR_TIMEOUT; msgs[(size_t)i] = "ILUT: dependency wait timed out"; failed = true; continue; }
+            if (o.zero_row >= 0) {
+                rcs[(size_t)i] = ILUPP_ERR_ZERO_PIVOT; msgs[(size_t)i] = "ILUT_heap: encountered zero pivot in row " + std::to_string(o.zero_row);      // ILUT.hpp:269-270
+                failed = true;
+                continue;
+            }
+            q->Lc.nnz = o.nnz_l; q->Uc.nnz = o.nnz_u;
+            for (DevMat *M : {&q->Lc, &q->Uc}) {
+                ILUPP_HIP(pool_malloc(&M->idx, sizeof(int32_t) * (size_t)(M->nnz > 0 ? M->nnz : 1)));
+                ILUPP_HIP(pool_malloc(&M->val, sizeof(double) * (size_t)(M->nnz > 0 ? M->nnz : 1)));
+            }
+            q->max_row_len = o.max_row_len; q->csr_vals = true; q->batch_built = true;
+            q->tm.numeric_ms = rows_ms; q->tm.numeric_kernel_ms = rows_ms;      // (the rows launches' time, shared by the call's members)
+            IlutBatchDesc &d = fresh[(size_t)k];
+            d.lidx = q->Lc.idx; d.lval = q->Lc.val; d.uidx = q->Uc.idx; d.uval = q->Uc.val;
+            launched.push_back(i);
+        }
+        if (!failed && !launched.empty()) {
+            batch_upload(bs, S.ttable, fresh, false);
+            OR_RETURN(ilut_batch_fill_launch(bs, nc, S.ttable.d, max_n));
+            // whatever a member's own stream does next (an apply, factors(), ensure_*) comes after the launch that writes its factors
+            ILUPP_HIP(hipEventRecord(S.done_ev, bs));
+            for (int32_t i : launched) ILUPP_HIP(hipStreamWaitEvent(objs.v[(size_t)i]->stream, S.done_ev, 0));
+            // a construction synchronises: the launches are over when the call returns
+            ILUPP_HIP(stream_sync(bs));
+        }
+    }
+    // route 1: the single constructor, on the member's own stream (it waits for its stream itself)
+    for (int32_t i = 0; i < count && !failed; ++i) {
+        if (rt[(size_t)i] != 1) continue;
+        if (objs.v[(size_t)i]) { destroy_obj(objs.v[(size_t)i]); objs.v[(size_t)i] = nullptr; }      // (it only held the two row-pointer arrays)
+        const int rc = ilut_create_single(m[i], is_csr, staged, S.in_ev, max_fill_in, threshold, &objs.v[(size_t)i]);
+        if (rc) { rcs[(size_t)i] = rc; msgs[(size_t)i] = g_last_error; failed = true; }
+    }
+    routes_out(rt, route);
+    int first = ILUPP_OK;
+    for (int32_t i = 0; i < count; ++i) {
+        if (status) status[i] = rcs[(size_t)i];
+        if (rcs[(size_t)i] && !first) { first = rcs[(size_t)i]; set_error("matrix " + std::to_string(i) + " of the batch: " + msgs[(size_t)i]); }
+    }
+    if (first) return first;                         // (objs goes, and every object of the call with it)
+    for (int32_t i = 0; i < count; ++i) { out[i] = objs.v[(size_t)i]; objs.v[(size_t)i] = nullptr; }
+    return ILUPP_OK;
+}
+
+auto ilut_run(int32_t max_fill_in, double threshold)
+{
+    return [=](BatchScratch &S, int32_t count, const CreateMember *m, int is_csr, bool staged, ilupp_precond **out, int32_t *status, int32_t *route) {
+        return ilut_create_batch_run(S, count, m, is_csr, staged, max_fill_in, threshold, out, status, route);
+    };
 }
 
 }  // namespace
@@ -3761,7 +3978,7 @@ int ilupp_hip_ilu0_create_batch_device(int32_t count, const double *const *d_dat
                                        int32_t *status, int32_t *route)
 {
     API_TRY_BUILD
-    return factor_create_batch_device(kIlu0Batch, count, d_data, d_indices, d_indptr, n, nnz, is_csr, out, status, route);
+    return factor_create_batch_device(factor_run(kIlu0Batch), count, d_data, d_indices, d_indptr, n, nnz, is_csr, out, status, route);
     API_CATCH
 }
 
@@ -3769,7 +3986,7 @@ int ilupp_hip_ilu0_create_batch(int32_t count, const double *const *data, const 
                                 const int32_t *n, int is_csr, ilupp_precond **out, int32_t *status, int32_t *route)
 {
     API_TRY_BUILD
-    return factor_create_batch_host(kIlu0Batch, count, data, indices, indptr, n, is_csr, out, status, route);
+    return factor_create_batch_host(factor_run(kIlu0Batch), count, data, indices, indptr, n, is_csr, out, status, route);
     API_CATCH
 }
 
@@ -3778,7 +3995,7 @@ int ilupp_hip_ichol0_create_batch_device(int32_t count, const double *const *d_d
                                          int32_t *status, int32_t *route)
 {
     API_TRY_BUILD
-    return factor_create_batch_device(kIchol0Batch, count, d_data, d_indices, d_indptr, n, nnz, is_csr, out, status, route);
+    return factor_create_batch_device(factor_run(kIchol0Batch), count, d_data, d_indices, d_indptr, n, nnz, is_csr, out, status, route);
     API_CATCH
 }
 
@@ -3786,7 +4003,25 @@ int ilupp_hip_ichol0_create_batch(int32_t count, const double *const *data, cons
                                   const int32_t *n, int is_csr, ilupp_precond **out, int32_t *status, int32_t *route)
 {
     API_TRY_BUILD
-    return factor_create_batch_host(kIchol0Batch, count, data, indices, indptr, n, is_csr, out, status, route);
+    return factor_create_batch_host(factor_run(kIchol0Batch), count, data, indices, indptr, n, is_csr, out, status, route);
+    API_CATCH
+}
+
+int ilupp_hip_ilut_create_batch_device(int32_t count, const double *const *d_data, const int32_t *const *d_indices,
+                                       const int32_t *const *d_indptr, const int32_t *n, const int64_t *nnz, int is_csr, int32_t max_fill_in,
+                                       double threshold, ilupp_precond **out, int32_t *status, int32_t *route)
+{
+    API_TRY_BUILD
+    return factor_create_batch_device(ilut_run(max_fill_in, threshold), count, d_data, d_indices, d_indptr, n, nnz, is_csr, out, status, route);
+    API_CATCH
+}
+
+int ilupp_hip_ilut_create_batch(int32_t count, const double *const *data, const int32_t *const *indices, const int32_t *const *indptr,
+                                const int32_t *n, int is_csr, int32_t max_fill_in, double threshold, ilupp_precond **out, int32_t *status,
+                                int32_t *route)
+{
+    API_TRY_BUILD
+    return factor_create_batch_host(ilut_run(max_fill_in, threshold), count, data, indices, indptr, n, is_csr, out, status, route);
     API_CATCH
 }
 

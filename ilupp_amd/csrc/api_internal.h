@@ -117,6 +117,8 @@ struct ilupp_precond : ilupp::PrecondHead, ilupp::QueuePack {
     // the single paths' analysis -- no sA / sU, no program, no packed sweeps, never the static form.  The batched launches take it as it
     // is; the single sweeps' tables (sL, sU, dL, dU) are built from the factors' own patterns on first use (ensure_sweep_tables)
     // IChol(0) built by ilupp_hip_ichol0_create_batch*: Lc, nnzA and max_row_len (the longest row of L) the same way; sL / dL on first use
+    // ILUT built by ilupp_hip_ilut_create_batch* (KIND_LU / NNZ_ILUT): Lc and Uc with their values, max_row_len = the longest row of the two
+    // (what sweep_tables gives the singly built object), and nothing else; no numeric re-factorisation exists for it, batch-built or not
     bool batch_built = false;
     bool sweeps_ready = false;
 };

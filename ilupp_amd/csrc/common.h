@@ -555,6 +555,48 @@ struct UrowLayout { int32_t si, sv, sl; };
 int ilut_rows_wp(hipStream_t st, const DevMat &A, int32_t p, double threshold,
                  int32_t *Lri, double *Lrv, int32_t *Llen, int32_t *Uri, double *Urv, int32_t *Ulen, UrowLayout ul, int32_t *ctrl, float *kernel_ms);
 
+// ---- the first construction of MANY small ILUT members (ilupp_hip_ilut_create_batch*): ilut_wp.hip (rows), ilut.hip (compaction) ----
+// One member of the launches: the row-major view of its matrix, its clamped budget p = min(max(fill_in, 1), n), its two slabs (L: p entries
+// per row in plain arrays; U: one record per row, UrowLayout), its own control block of 32 words (the words of k_ilut_rows_wp's ctrl: [1]
+// status, [2] the first row with a zero pivot, [3..6] and [24] the tier counters, [7] rows finished) and the CSR arrays the compaction fills
+// (the row pointers are there from the start, the index and value arrays once the one read-back has said how long they are).
+struct IlutBatchDesc {
+    const int32_t *aptr, *aidx; const double *aval;
+    int32_t *Lri; double *Lrv; int32_t *Llen;
+    int32_t *Uri; double *Urv; int32_t *Ulen;
+    int32_t *ctrl;
+    int32_t *lptr, *lidx; double *lval;
+    int32_t *uptr, *uidx; double *uval;
+    UrowLayout ul;
+    int32_t n, p, vw, pad;                           // vw: 8-byte words of a record in front of its values (length word and columns)
+};
+// what the count launch leaves per member, all that the host reads back of a call: the member's status ([1] of its control block: 0, 1 = a
+// wait timed out, 3 = a row that fits no tier of the launch), its first row with a zero pivot or -1, the entries of L and U without the
+// exact zeros, the longest row of the two, and the tier counters (rows that outgrew tier 1, by pool / U slots / kept list; rows that left tier 2)
+struct IlutBatchInfo { int32_t status, zero_row, nnz_l, nnz_u, max_row_len, outgrew, pool, uslots, kept, left_tier2, pad[6]; };
+// The order in which the waves of a rows launch claim (member, row): ticket t lies in the segment s with seg[s].base <= t < seg[s + 1].base
+// and is row seg[s].r0 + (t - base) / cnt of member order[first + (t - base) % cnt].  Round-robin: the members sorted by n, one segment per
+// distinct n -- round r holds row r of every member that has one.  (Member-major, for the measurement: one segment per member, cnt = 1.)
+struct IlutBatchSeg { int32_t base, r0, first, cnt; };
+// ilut_wp.hip.  ilut_batch_class: 0 / 1 = the LDS class of k_ilut_rows_batch a member of budget p runs in, -1 = the largest capacity
+// class, which the launch does not have (the member goes to the single constructor).
+int ilut_batch_class(int32_t p);
+// the ticket map of `members` (indices into the descriptor table; n[k] rows each) appended to *seg / *order; returns the number of tickets
+int64_t ilut_batch_tickets(const std::vector<int32_t> &members, const std::vector<int32_t> &n, bool member_major,
+                           std::vector<IlutBatchSeg> *seg, std::vector<int32_t> *order);
+// every record of every member "not there", every control block as a rows kernel expects it, the launches' ticket counters (d_tickets[0..1]) zero
+int ilut_batch_init_launch(hipStream_t st, int32_t count, const IlutBatchDesc *d_table, int64_t max_words, int32_t *d_tickets);
+// the waves' private arrays of a call's rows launches (taken once, given back by the caller behind its wait for the launches)
+struct IlutBatchWork { PoolBlock b[10]; int workers = 0; };
+int ilut_batch_work(hipStream_t st, int64_t tickets_small, int64_t tickets_large, IlutBatchWork *work);
+// one rows launch: the members of LDS class `cls` in the order of their ticket map
+int ilut_rows_batch_launch(hipStream_t st, int cls, const IlutBatchDesc *d_table, const IlutBatchSeg *d_seg, int32_t nseg, const int32_t *d_order,
+                           int32_t tickets, int32_t *d_ticket, double threshold, const IlutBatchWork &work);
+// ilut.hip: the compaction of all members.  Count: exact zeros dropped (k_slab_count), the row pointers by a workgroup-wide scan per member,
+// the member's IlutBatchInfo.  Fill: k_slab_fill for all members at once.
+int ilut_batch_count_launch(hipStream_t st, int32_t count, const IlutBatchDesc *d_table, IlutBatchInfo *d_info);
+int ilut_batch_fill_launch(hipStream_t st, int32_t count, const IlutBatchDesc *d_table, int32_t max_n);
+
 // sptrsv.hip
 enum SweepKind { SWEEP_FWD_LAST_ASC = 0, SWEEP_BWD_FIRST_ASC = 1, SWEEP_BWD_FIRST_DESC = 2 };
 int sptrsv(hipStream_t st, SweepKind kind, const DevMat &M, const Schedule &sch, const int32_t *desc,

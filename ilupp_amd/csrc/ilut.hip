@@ -111,4 +111,102 @@ int ilut_factor(hipStream_t st, const DevMat &A, int32_t max_fill_in, double thr
     return rc;
 }
 
+// ---- the compaction of MANY members (ilupp_hip_ilut_create_batch*) -----------------------------------------------------------------------
+// One workgroup per member: k_slab_count's count of both slabs, row by row, and the two row-pointer arrays by a workgroup-wide running scan
+// over the rows (256 rows a round, the carry in registers: k_ilu0_symbolic_batch's scan), then the member's record for the call's one read-back.
+static constexpr int kIbThreads = 256;
+__global__ void __launch_bounds__(kIbThreads)
+k_ilut_count_batch(const IlutBatchDesc *__restrict__ table, IlutBatchInfo *__restrict__ info)
+{
+    __shared__ int s_wl[kIbThreads / 64], s_wu[kIbThreads / 64];
+    __shared__ int s_maxlen;
+    const IlutBatchDesc *d = table + blockIdx.x;
+    const int n = d->n, p = d->p, tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+    const UrowLayout ul = d->ul;
+    const int32_t *Llen = d->Llen, *Ulen = d->Ulen;
+    const double *Lrv = d->Lrv, *Urv = d->Urv;
+    int32_t *lptr = d->lptr, *uptr = d->uptr;
+    if (tid == 0) { s_maxlen = 0; lptr[0] = 0; uptr[0] = 0; }
+    int maxlen = 0, carry_l = 0, carry_u = 0;
+    for (int base = 0; base < n; base += kIbThreads) {
+        const int r = base + tid;
+        int nl = 0, nu = 0;
+        if (r < n) {
+            const int ll = Llen[r], lu = Ulen[(size_t)r * ul.sl];
+            const size_t bl = (size_t)r * p, bu = (size_t)r * ul.sv;
+            for (int q = 0; q < ll; ++q) nl += (fabs(Lrv[bl + q]) > 0.0) ? 1 : 0;
+            for (int q = 0; q < lu; ++q) nu += (fabs(Urv[bu + q]) > 0.0) ? 1 : 0;
+            maxlen = max(maxlen, max(nl, nu));
+        }
+        int xl = nl, xu = nu;                        // inclusive scan over the wave, then over the waves' totals
+#pragma unroll
+        for (int off = 1; off < 64; off <<= 1) {
+            const int tl = __shfl_up(xl, off), tu = __shfl_up(xu, off);
+            if (lane >= off) { xl += tl; xu += tu; }
+        }
+        if (lane == 63) { s_wl[w] = xl; s_wu[w] = xu; }
+        __syncthreads();
+        int before_l = 0, before_u = 0, all_l = 0, all_u = 0;
+#pragma unroll
+        for (int k = 0; k < kIbThreads / 64; ++k) {
+            if (k < w) { before_l += s_wl[k]; before_u += s_wu[k]; }
+            all_l += s_wl[k]; all_u += s_wu[k];
+        }
+        if (r < n) { lptr[r + 1] = carry_l + before_l + xl; uptr[r + 1] = carry_u + before_u + xu; }
+        carry_l += all_l; carry_u += all_u;
+        __syncthreads();                             // (the totals are read: the next round may write them)
+    }
+    atomicMax(&s_maxlen, maxlen);
+    __syncthreads();
+    if (tid == 0) {
+        const int32_t *ctrl = d->ctrl;
+        IlutBatchInfo o;
+        o.status = ctrl[1]; o.zero_row = ctrl[2] == 0x7fffffff ? -1 : ctrl[2];
+        o.nnz_l = carry_l; o.nnz_u = carry_u; o.max_row_len = s_maxlen;
+        o.outgrew = ctrl[3]; o.pool = ctrl[4]; o.uslots = ctrl[5]; o.kept = ctrl[6]; o.left_tier2 = ctrl[24];
+        for (int q = 0; q < 6; ++q) o.pad[q] = 0;
+        info[blockIdx.x] = o;
+    }
+}
+
+// k_slab_fill for both slabs of every member: blockIdx.y = the member, one thread per row
+__global__ void k_ilut_fill_batch(const IlutBatchDesc *__restrict__ table)
+{
+    const IlutBatchDesc *d = table + blockIdx.y;
+    const int r = blockIdx.x * blockDim.x + threadIdx.x;
+    if (r >= d->n || !d->lidx || !d->uidx) return;    // (a member that failed or takes the single path has no arrays to fill)
+    const int p = d->p;
+    const UrowLayout ul = d->ul;
+    {
+        int o = d->lptr[r];
+        const size_t b = (size_t)r * p;
+        const int len = d->Llen[r];
+        for (int q = 0; q < len; ++q)
+            if (fabs(d->Lrv[b + q]) > 0.0) { d->lidx[o] = d->Lri[b + q]; d->lval[o] = d->Lrv[b + q]; ++o; }
+    }
+    {
+        int o = d->uptr[r];
+        const size_t bi = (size_t)r * ul.si, bv = (size_t)r * ul.sv;
+        const int len = d->Ulen[(size_t)r * ul.sl];
+        for (int q = 0; q < len; ++q)
+            if (fabs(d->Urv[bv + q]) > 0.0) { d->uidx[o] = d->Uri[bi + q]; d->uval[o] = d->Urv[bv + q]; ++o; }
+    }
+}
+
+int ilut_batch_count_launch(hipStream_t st, int32_t count, const IlutBatchDesc *d_table, IlutBatchInfo *d_info)
+{
+    if (count <= 0) return ILUPP_OK;
+    hipLaunchKernelGGL(k_ilut_count_batch, dim3((unsigned)count), dim3(kIbThreads), 0, st, d_table, d_info);
+    ILUPP_HIP(hipGetLastError());
+    return ILUPP_OK;
+}
+
+int ilut_batch_fill_launch(hipStream_t st, int32_t count, const IlutBatchDesc *d_table, int32_t max_n)
+{
+    if (count <= 0) return ILUPP_OK;
+    hipLaunchKernelGGL(k_ilut_fill_batch, dim3((unsigned)((max_n + 255) / 256), (unsigned)count), dim3(256), 0, st, d_table);
+    ILUPP_HIP(hipGetLastError());
+    return ILUPP_OK;
+}
+
 }  // namespace ilupp

@@ -36,6 +36,8 @@
 // arrays between two eliminations and the row goes on (WpResume); a row that outgrows those, or a fill budget beyond the LDS
 // selection queue, makes the host run the whole factorisation in the largest capacity class (k_ilut_rows_wp_big: pieces as long
 // as the matrix is wide, on fewer waves).
+// Many small matrices at once (ilupp_hip_ilut_create_batch*): k_ilut_rows_batch, the same wave loop over TICKETS -- (member, row) pairs in
+// round-robin order -- on per-member descriptors; see there.
 #include <stdio.h>
 #include <algorithm>
 #include <vector>
@@ -922,6 +924,100 @@ k_ilut_rows_wp(int32_t n, const int32_t *__restrict__ Aptr, const int32_t *__res
 #endif
 }
 
+// The rows of MANY small members in one launch (ilupp_hip_ilut_create_batch*): k_ilut_rows_wp's wave loop over tickets instead of rows.  A
+// wave takes the next ticket from the launch's one counter, maps it to (member, row) and runs the tier ladder above on that member's
+// arrays, control block included (table: IlutBatchDesc, common.h); its LDS and its private global pieces go from one member's row to the
+// next member's as they go from row to row above.  The ticket order (seg, order: IlutBatchSeg) is round-robin over the members that still
+// have rows: within a member rows are claimed in ascending order, so a row waits only on rows claimed earlier -- by waves that are
+// resident and need nothing claimed later: no deadlock however few waves there are --, and the members advance side by side, so the launch
+// lasts as long as the longest dependency chain among them, not as long as their sum.
+// (The loop is written out a second time rather than shared: the two kernels above stay textually what they were.)
+#ifndef ILUT_PROFILE
+template <int kWpCapU, int kWpHashLds>
+__global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(ILUT_WPE, ILUT_WPE)))
+k_ilut_rows_batch(const IlutBatchDesc *__restrict__ table, const IlutBatchSeg *__restrict__ seg, int32_t nseg, const int32_t *__restrict__ order,
+                  int32_t tickets, int32_t *ticket, double tau, WpArrays gw, int *gscratch_all, int tier2)
+{
+    constexpr int kWpCapL = kWpCapU;
+    constexpr int kRaw = kWpCapU == 128 ? ILUT_RAW : 14336;
+    constexpr int kCap2 = kRaw / 14;
+    static_assert(kWpCapU * 26 + kWpHashLds * 2 <= kRaw, "tier 1 does not fit the block");
+    __shared__ __attribute__((aligned(16))) unsigned char s_raw[kRaw];
+    __shared__ int s_selq[kWpSel];
+    __shared__ int bcol[64], bfound[64], s_dlist[64];
+    __shared__ double bpr[64];
+    double *s_uval = reinterpret_cast<double *>(s_raw), *s_lval = s_uval + kWpCapU;
+    int *s_ucol = reinterpret_cast<int *>(s_lval + kWpCapL), *s_lcol = s_ucol + kWpCapU;
+    unsigned short *s_lseq = reinterpret_cast<unsigned short *>(s_lcol + kWpCapL), *s_uh = s_lseq + kWpCapL;
+    double *t_lval = reinterpret_cast<double *>(s_raw);
+    int *t_lcol = reinterpret_cast<int *>(t_lval + kCap2);
+    unsigned short *t_lseq = reinterpret_cast<unsigned short *>(t_lcol + kCap2);
+    const int lane = threadIdx.x;
+    const size_t wv = blockIdx.x;
+    WpArrays g = gw;
+    g.uh += wv * (size_t)kWpHashG;
+    g.ucol += wv * (size_t)gw.capU; g.uval += wv * (size_t)gw.capU;
+    g.lcol += wv * (size_t)gw.capL; g.lval += wv * (size_t)gw.capL; g.lseq += wv * (size_t)gw.capL;
+    g.kcol += wv * (size_t)gw.capK; g.kval += wv * (size_t)gw.capK; g.kseq += wv * (size_t)gw.capK;
+    int *gscratch = gscratch_all + wv * (size_t)gw.capU;
+    const WpArrays lw = {s_uh, kWpHashLds - 1, s_ucol, s_uval, kWpCapU, s_lcol, s_lval, s_lseq, kWpCapL, g.kcol, g.kval, g.kseq, gw.capK};
+    const WpArrays hw = {g.uh, kWpHashG - 1, g.ucol, g.uval, gw.capU, t_lcol, t_lval, t_lseq, kCap2, g.kcol, g.kval, g.kseq, gw.capK};
+    unsigned long long *prof = nullptr;
+    for (;;) {
+        int t = 0;
+        if (lane == 0) t = atomicAdd(ticket, 1);
+        t = __builtin_amdgcn_readfirstlane(t);
+        if (t >= tickets) break;
+        // the ticket's segment (the last one that starts at or before it), then its round and its member: the same for all lanes
+        int lo = 0, hi = nseg - 1;
+        while (lo < hi) { const int mid = (lo + hi + 1) >> 1; if (seg[mid].base <= t) lo = mid; else hi = mid - 1; }
+        const IlutBatchSeg sg = seg[lo];
+        const int off = t - sg.base;
+        const int i = __builtin_amdgcn_readfirstlane(sg.r0 + off / sg.cnt);
+        const int mem = __builtin_amdgcn_readfirstlane(order[sg.first + off % sg.cnt]);
+        const IlutBatchDesc *d = table + mem;
+        const int n = d->n, p = d->p;
+        const int32_t *Aptr = d->aptr, *Aidx = d->aidx;
+        const double *Aval = d->aval;
+        int32_t *Lrow_idx = d->Lri, *Llen = d->Llen, *Urow_idx = d->Uri, *Ulen = d->Ulen, *ctrl = d->ctrl;
+        double *Lrow_val = d->Lrv, *Urow_val = d->Urv;
+        const UrowLayout ul_ = d->ul;
+        WpResume rs;
+        rs.active = 0;
+        int rc = wp_row<false>(lane, i, n, p, tau, Aptr, Aidx, Aval, Lrow_idx, Lrow_val, Llen, Urow_idx, Urow_val, Ulen, ul_,
+                               lw, bcol, bpr, bfound, s_dlist, s_selq, gscratch, ctrl, prof);
+        rc = __builtin_amdgcn_readfirstlane(rc);
+        if (rc == 1 && tier2) {
+            if (lane == 0) atomicAdd(&ctrl[3], 1);          // the member's statistics: rows that outgrew tier 1
+            rc = wp_row<true>(lane, i, n, p, tau, Aptr, Aidx, Aval, Lrow_idx, Lrow_val, Llen, Urow_idx, Urow_val, Ulen, ul_,
+                              hw, bcol, bpr, bfound, s_dlist, s_selq, gscratch, ctrl, prof, &rs, g.lcol, g.lval, g.lseq, gw.capL);
+            rc = __builtin_amdgcn_readfirstlane(rc);
+            if ((rc == 1 || rc == 3) && lane == 0) atomicAdd(&ctrl[24], 1);      // ... and tier 2
+        } else if (rc == 1) {
+            if (lane == 0) atomicAdd(&ctrl[3], 1);
+        }
+        if (rc == 1 || rc == 3) {
+            if (rc == 1) rs.active = 0;
+            rc = wp_row<true>(lane, i, n, p, tau, Aptr, Aidx, Aval, Lrow_idx, Lrow_val, Llen, Urow_idx, Urow_val, Ulen, ul_,
+                              g, bcol, bpr, bfound, s_dlist, s_selq, gscratch, ctrl, prof, &rs);
+            rc = __builtin_amdgcn_readfirstlane(rc);
+        }
+        if (rc != 0) {
+            // give up: a poisoned row so that nobody of the member waits for it, and the member's status (the other members go on)
+            if (lane == 0) {
+                atomicMax(&ctrl[1], rc == 1 ? 3 : 1);
+                st_agent_f64(&Urow_val[(size_t)i * ul_.sv], 1.0);
+                st_agent_i32(&Urow_idx[(size_t)i * ul_.si], i);
+                st_agent_i32(&Ulen[(size_t)i * ul_.sl], 1);
+                Llen[i] = 0;
+            }
+            for (size_t q = lane; q < (size_t)kWpHashG * sizeof(unsigned short) / 8; q += 64) reinterpret_cast<unsigned long long *>(g.uh)[q] = 0ull;
+            __builtin_amdgcn_s_waitcnt(0);
+        }
+    }
+}
+#endif
+
 #pragma clang diagnostic pop
 
 // the largest capacity class: every piece as long as the matrix is wide, 32-bit slot ids and sequence numbers, the selection
@@ -1213,6 +1309,131 @@ int ilut_rows_wp(hipStream_t st, const DevMat &A, int32_t p, double threshold,
     if (h[1] == 3) return ilut_rows_wp_big(st, A, p, threshold, Lri, Lrv, Llen, Uri, Urv, Ulen, ul_, ctrl, kernel_ms);
     if (h[1] == 1) return ILUPP_ERR_TIMEOUT;
     return 0;
+}
+
+// ---- many small members in one launch (k_ilut_rows_batch) ------------------------------------------------------------------------------
+
+int ilut_batch_class(int32_t p)
+{
+#ifdef ILUT_PROFILE
+    (void)p;
+    return -1;                                       // (the profile build's per-row arrays belong to ONE matrix: every member takes the single path)
+#else
+    if (p - 1 >= kWpSel || getenv("ILUPP_ILUT_BIG") != nullptr) return -1;
+    const char *cap_env = getenv("ILUPP_ILUT_CAP");                             // (as ilut_rows_wp: 256 = the larger LDS class for every budget)
+    return p <= 32 && !(cap_env && atoi(cap_env) == 256) ? 0 : 1;
+#endif
+}
+
+int64_t ilut_batch_tickets(const std::vector<int32_t> &members, const std::vector<int32_t> &n, bool member_major,
+                           std::vector<IlutBatchSeg> *seg, std::vector<int32_t> *order)
+{
+    int64_t base = 0;
+    if (member_major) {
+        for (int32_t m : members) {
+            seg->push_back({(int32_t)base, 0, (int32_t)order->size(), 1});
+            order->push_back(m);
+            base += n[(size_t)m];
+        }
+        return base;
+    }
+    std::vector<int32_t> s = members;
+    std::stable_sort(s.begin(), s.end(), [&](int32_t a, int32_t b) { return n[(size_t)a] < n[(size_t)b]; });
+    const int32_t first = (int32_t)order->size(), M = (int32_t)s.size();
+    order->insert(order->end(), s.begin(), s.end());
+    int32_t r0 = 0;                                  // the first round the members from s[k] on are alone in
+    for (int32_t k = 0; k < M; ++k) {
+        const int32_t nk = n[(size_t)s[(size_t)k]];
+        if (nk <= r0) continue;                      // (as long as the member before it: it left with that one)
+        seg->push_back({(int32_t)base, r0, first + k, M - k});
+        base += (int64_t)(nk - r0) * (M - k);
+        r0 = nk;
+    }
+    return base;
+}
+
+// every record of every member starts as "not there" (k_urec_init), every control block as wp_init_slabs leaves it
+__global__ void k_urec_init_batch(const IlutBatchDesc *__restrict__ table, int32_t *__restrict__ tickets)
+{
+    const IlutBatchDesc *d = table + blockIdx.y;
+    if (blockIdx.x == 0 && threadIdx.x < 32) {
+        d->ctrl[threadIdx.x] = threadIdx.x == 2 ? 0x7fffffff : 0;
+        if (blockIdx.y == 0 && threadIdx.x < 2) tickets[threadIdx.x] = 0;
+    }
+    const int rw = d->ul.sv, vw = d->vw, p = d->p;
+    const long long words = (long long)d->n * rw;
+    const long long w = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (w >= words) return;
+    const int o = (int)(w % rw);
+    reinterpret_cast<unsigned long long *>(d->Ulen)[w] = o == 0 ? 0xffffffff00000000ull : o < vw ? ~0ull : o < vw + p ? kSentinel : 0ull;
+}
+
+int ilut_batch_init_launch(hipStream_t st, int32_t count, const IlutBatchDesc *d_table, int64_t max_words, int32_t *d_tickets)
+{
+    if (count <= 0) return ILUPP_OK;
+    hipLaunchKernelGGL(k_urec_init_batch, dim3((unsigned)((max_words + 255) / 256), (unsigned)count), dim3(256), 0, st, d_table, d_tickets);
+    ILUPP_HIP(hipGetLastError());
+    return ILUPP_OK;
+}
+
+// waves per CU of a launch's LDS class (ILUPP_ILUT_WAVES: experiments, as ilut_rows_wp)
+static int wp_batch_waves_per_cu(int cls)
+{
+    const char *e = getenv("ILUPP_ILUT_WAVES");
+    const int v = e ? atoi(e) : 0;
+    return v > 0 ? v : (cls == 0 ? 16 : 8);
+}
+
+int ilut_batch_work(hipStream_t st, int64_t tickets_small, int64_t tickets_large, IlutBatchWork *work)
+{
+    // what ilut_rows_wp takes for ONE matrix with as many rows as the launch has tickets, once for the call's launches
+    const int64_t cus = device_cu_count();
+    int64_t w = 1;
+    if (tickets_small > 0) w = std::max(w, std::min(cus * wp_batch_waves_per_cu(0), tickets_small));
+    if (tickets_large > 0) w = std::max(w, std::min(cus * wp_batch_waves_per_cu(1), tickets_large));
+    const size_t workers = (size_t)w;
+    PoolBlock *b = work->b;
+    ILUPP_HIP(b[0].alloc(sizeof(unsigned short) * workers * kWpHashG));
+    ILUPP_HIP(b[1].alloc(sizeof(int) * workers * kWpGCapU));
+    ILUPP_HIP(b[2].alloc(sizeof(double) * workers * kWpGCapU));
+    ILUPP_HIP(b[3].alloc(sizeof(int) * workers * kWpGCapL));
+    ILUPP_HIP(b[4].alloc(sizeof(double) * workers * kWpGCapL));
+    ILUPP_HIP(b[5].alloc(sizeof(unsigned short) * workers * kWpGCapL));
+    ILUPP_HIP(b[6].alloc(sizeof(int) * workers * kWpGCapK));
+    ILUPP_HIP(b[7].alloc(sizeof(double) * workers * kWpGCapK));
+    ILUPP_HIP(b[8].alloc(sizeof(unsigned short) * workers * kWpGCapK));
+    ILUPP_HIP(b[9].alloc(sizeof(int) * workers * kWpGCapU));
+    // (every wave leaves its table empty behind every row: the second launch of a call finds it as the first did)
+    ILUPP_HIP(hipMemsetAsync(b[0].p, 0, sizeof(unsigned short) * workers * kWpHashG, st));
+    work->workers = (int)workers;
+    return ILUPP_OK;
+}
+
+int ilut_rows_batch_launch(hipStream_t st, int cls, const IlutBatchDesc *d_table, const IlutBatchSeg *d_seg, int32_t nseg, const int32_t *d_order,
+                           int32_t tickets, int32_t *d_ticket, double threshold, const IlutBatchWork &work)
+{
+#ifdef ILUT_PROFILE
+    (void)st; (void)cls; (void)d_table; (void)d_seg; (void)nseg; (void)d_order; (void)tickets; (void)d_ticket; (void)threshold; (void)work;
+    return ILUPP_ERR_UNSUPPORTED;
+#else
+    if (tickets <= 0 || nseg <= 0) return ILUPP_OK;
+    int64_t workers = (int64_t)device_cu_count() * wp_batch_waves_per_cu(cls);
+    if (workers > tickets) workers = tickets;
+    if (workers > work.workers) workers = work.workers;
+    const PoolBlock *b = work.b;
+    const WpArrays g = {b[0].as<unsigned short>(), kWpHashG - 1, b[1].as<int>(), b[2].as<double>(), kWpGCapU,
+                        b[3].as<int>(), b[4].as<double>(), b[5].as<unsigned short>(), kWpGCapL,
+                        b[6].as<int>(), b[7].as<double>(), b[8].as<unsigned short>(), kWpGCapK};
+    const int tier2 = getenv("ILUPP_ILUT_NO_TIER2") ? 0 : 1;
+    if (cls == 0)
+        hipLaunchKernelGGL((k_ilut_rows_batch<128, 512>), dim3((unsigned)workers), dim3(64), 0, st, d_table, d_seg, nseg, d_order, tickets, d_ticket,
+                           threshold, g, b[9].as<int>(), tier2);
+    else
+        hipLaunchKernelGGL((k_ilut_rows_batch<256, 1024>), dim3((unsigned)workers), dim3(64), 0, st, d_table, d_seg, nseg, d_order, tickets, d_ticket,
+                           threshold, g, b[9].as<int>(), tier2);
+    ILUPP_HIP(hipGetLastError());
+    return ILUPP_OK;
+#endif
 }
 
 }  // namespace ilupp

@@ -682,6 +682,35 @@ def ichol0_batch(As):
     return out
 
 
+def ilut_batch(As, fill_in=100, threshold=0.1):
+    """``[DevicePreconditioner("ILUT", A, fill_in=fill_in, threshold=threshold) for A in As]`` from ONE native call, for MANY SMALL
+    matrices (one parameter set per batch).  ILUT's pattern depends on the values, so there is nothing to re-factor: a time-stepping
+    caller builds every member again at every step, and this is the call for that.  The rows of all members run in one launch of the
+    single constructor's wave kernel, claimed round-robin so that the members' dependency chains advance side by side; one read-back,
+    one fill launch (ilupp_hip_ilut_create_batch_device) where the loop pays five host waits, a nearly empty rows launch and the waves'
+    working arrays per object.  The factors and every apply of a member have the bits of the singly built object; the members go into
+    ``apply_batch_`` / ``cg_batch`` / ``bicgstab_batch`` as they are.  A batch of one, a budget min(fill_in, n) above 256 and a member
+    with a row that outgrows the launch's 64 K pieces are built by the single constructor inside the same call.  Ordered on torch's
+    current stream; the call returns when every member is built.  A zero pivot raises the constructor's RuntimeError, named by the
+    member's number, and no object is returned.  TypeError for a member that is not a DeviceCSR -- before any native call; an empty
+    list gives ``[]``."""
+    As = list(As)
+    for A in As:
+        if not isinstance(A, DeviceCSR):
+            raise TypeError("ilut_batch takes DeviceCSR matrices, got %s" % type(A).__name__)
+    if not As:
+        return []
+    _on_current_stream()
+    natives = _native.ILUTPreconditioner_batch_device(
+        [(A.data.data_ptr(), A.indices.data_ptr(), A.indptr.data_ptr(), A.n, A.nnz) for A in As], True, fill_in, threshold)
+    out = []
+    for A, pr in zip(As, natives):
+        M = DevicePreconditioner.__new__(DevicePreconditioner)
+        M.pr, M.kind, M.n, M.shape = pr, "ILUT", A.n, A.shape
+        out.append(M)
+    return out
+
+
 def ichol0_refactor_(M, A):
     """The numeric IChol(0) factorisation again on a DeviceCSR with the SAME pattern and (possibly) new values, the analysis kept
     (ilupp_hip_ichol0_refactor_device); returns ``M``.  ``M``: a ``DevicePreconditioner("IChol0", ...)``, a host ``IChol0Preconditioner``

@@ -594,6 +594,32 @@ int ilupp_hip_ichol0_create_batch_device(int32_t count, const double *const *d_d
                                          const int32_t *const *d_indptr, const int32_t *n, const int64_t *nnz, int is_csr, ilupp_precond **out,
                                          int32_t *status, int32_t *route);
 
+/* The FIRST construction of MANY small ILUT(max_fill_in, threshold) objects at once (one parameter set per batch).  ILUT's pattern depends
+ * on the values, so there is no numeric re-factorisation to fall back on: a time-stepping caller builds every member again at every step,
+ * and a loop of ilupp_hip_ilut_create* pays per member the record initialisation, the rows kernel running nearly empty, five host waits
+ * and the waves' working arrays.  Here all members share k_ilut_rows_batch (ilut_wp.hip): the single kernel's wave loop -- the same
+ * wp_row, the same three capacity tiers, the same bits -- over the rows of ALL members, claimed round-robin (round r holds row r of
+ * every member that has one: within a member rows are claimed in ascending order, so a row still waits only on rows claimed earlier, and
+ * the members' dependency chains run side by side), then one count-and-scan launch, ONE read-back (per member: status, first row with a
+ * zero pivot, nnz(L), nnz(U), longest row) and one fill launch that drops exact zeros as the single path's compaction does.
+ * Arguments as for ilupp_hip_ilu0_create_batch / _device, plus max_fill_in and threshold as for ilupp_hip_ilut_create.  route (may be
+ * NULL): 0 = built by the launches; 1 = built by ilupp_hip_ilut_create* inside the same call -- a batch of ONE member, a clamped budget
+ * min(max(max_fill_in, 1), n) - 1 >= 256 (the largest capacity class, which the launch does not have), or a member whose launch met a row
+ * that fits no tier of it.  A route-0 object holds L and U with their values, the longest row of the two, and nothing else: factors,
+ * total_nnz and every apply have the bits of ilupp_hip_ilut_create's object, ilupp_hip_path is "ilut:batch", the batched launches take it
+ * as it is, the tables of the single sweeps are built at its first single apply, and ilupp_hip_get_timings reports the rows launches as
+ * numeric_ms, shared by the call's members.  The re-factorisation entries refuse it as they refuse every ILUT object.
+ * A member with a zero pivot fails as its single construction does ("matrix i of the batch: ILUT_heap: encountered zero pivot in row N"), a
+ * dependency wait that timed out is ILUPP_ERR_TIMEOUT: the first failure is returned, status[i] says which members failed, every object
+ * of the call is destroyed and no handle is returned.  count == 0 returns ILUPP_OK without touching the device; null arguments are
+ * refused before any HIP call ("null argument"). */
+int ilupp_hip_ilut_create_batch(int32_t count, const double *const *data, const int32_t *const *indices, const int32_t *const *indptr,
+                                const int32_t *n, int is_csr, int32_t max_fill_in, double threshold, ilupp_precond **out, int32_t *status,
+                                int32_t *route);
+int ilupp_hip_ilut_create_batch_device(int32_t count, const double *const *d_data, const int32_t *const *d_indices,
+                                       const int32_t *const *d_indptr, const int32_t *n, const int64_t *nnz, int is_csr, int32_t max_fill_in,
+                                       double threshold, ilupp_precond **out, int32_t *status, int32_t *route);
+
 /* ---------------------------------------------------------------------------------------------
  * Measurement hooks used by bench.py (not part of the reference's surface).
  * Times are GPU milliseconds from hipEvents recorded on the object's stream.
@@ -608,7 +634,7 @@ typedef struct {
 } ilupp_timings;
 int ilupp_hip_get_timings(const ilupp_precond *p, ilupp_timings *t);
 /* which kernel family built this object ("ilu0:static-direct", "ilu0:static-level-major", "ilu0:level-order",
- * "ilu0:csr-program", "ilu0:csr", "ilu0:batch", "ilut", "ichol0", "ichol0:batch", "icholt"): bench.py names the kernel its roofline line is about */
+ * "ilu0:csr-program", "ilu0:csr", "ilu0:batch", "ilut", "ilut:batch", "ichol0", "ichol0:batch", "icholt"): bench.py names the kernel its roofline line is about */
 const char *ilupp_hip_path(const ilupp_precond *p);
 /* how the row blocks of an ILU(0) object were found: "grid" (the pattern is a lexicographic box-grid stencil: guessed from row 0, proven
  * for every row by one streaming pass next to the lane-table kernels, grid.hip) or "general" (the pass over the pattern that finds the
