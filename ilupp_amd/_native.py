@@ -1256,6 +1256,34 @@ def cg_batch_max_n():
     return _batch_max_n("ilupp_hip_cg_batch_max_n")
 
 
+def _bicgstab_batch(ml, members, ns, matrices, b_ptr, x0_ptr, x_ptr, offsets, *rest):
+    """what bicgstab_batch_device and bicgstab_batch_ml_device do (ml: a MultilevelPreconditioner is a member like the others, and the
+    entry takes a third handle list for them); rest: the arguments behind `offsets`, as they stand"""
+    cnt = len(members)
+    if len(matrices) != cnt or len(offsets) != cnt or len(ns) != cnt:
+        raise ValueError("%d preconditioners but %d dimensions, %d matrices and %d offsets" % (cnt, len(ns), len(matrices), len(offsets)))
+    if cnt == 0:
+        return []
+    handles = [(_VP * cnt)() for _ in range(3 if ml else 2)]        # plain, pivoted and, where the entry takes them, multilevel
+    for k, m in enumerate(members):
+        if m is None:
+            continue
+        if isinstance(m, PivotedPreconditioner):
+            handles[1][k] = m._h
+        elif isinstance(m, Preconditioner):
+            handles[0][k] = m._h
+        elif ml and isinstance(m, MultilevelPreconditioner):
+            handles[2][k] = m._h
+        elif ml:
+            raise TypeError("a batched solve takes ILUCP / ILUTP / ILU0 / ILUT / ILUC / IChol0 / ICholT / multilevel ILU++ preconditioners "
+                            "or None, got %s" % type(m).__name__)
+        else:
+            raise TypeError("a batched solve takes ILUCP / ILUTP / ILU0 / ILUT / ILUC / IChol0 / ICholT preconditioners or None, got %s"
+                            % type(m).__name__)
+    return _solve_batch("ilupp_hip_bicgstab_batch_ml_device" if ml else "ilupp_hip_bicgstab_batch_device", handles, ns, matrices, b_ptr,
+                        x0_ptr, x_ptr, offsets, *rest)
+
+
 def bicgstab_batch_device(members, ns, matrices, b_ptr, x0_ptr, x_ptr, offsets, work_ptr, work_doubles, maxiter, rtol, check_every,
                           iterations_ptr, flags_ptr, rr_ptr, init_ptr, sync=True):
     """left-preconditioned BiCGstab for many small systems in ONE launch with members of every batched class
@@ -1263,24 +1291,8 @@ def bicgstab_batch_device(members, ns, matrices, b_ptr, x0_ptr, x_ptr, offsets, 
     ILUC, IChol0, ICholT) or None (no preconditioner), mixed at will; `ns` the members' dimensions; everything else as in
     pivot_bicgstab_batch_device (7 doubles of workspace per unknown of the batch).  Ordered on the caller's stream (set_caller_stream).
     Returns the routes: members of route 1 or 2 are NOT solved."""
-    cnt = len(members)
-    if len(matrices) != cnt or len(offsets) != cnt or len(ns) != cnt:
-        raise ValueError("%d preconditioners but %d dimensions, %d matrices and %d offsets" % (cnt, len(ns), len(matrices), len(offsets)))
-    if cnt == 0:
-        return []
-    HP, HV = (_VP * cnt)(), (_VP * cnt)()
-    for k, m in enumerate(members):
-        if m is None:
-            continue
-        if isinstance(m, PivotedPreconditioner):
-            HV[k] = m._h
-        elif isinstance(m, Preconditioner):
-            HP[k] = m._h
-        else:
-            raise TypeError("a batched solve takes ILUCP / ILUTP / ILU0 / ILUT / ILUC / IChol0 / ICholT preconditioners or None, got %s"
-                            % type(m).__name__)
-    return _solve_batch("ilupp_hip_bicgstab_batch_device", (HP, HV), ns, matrices, b_ptr, x0_ptr, x_ptr, offsets, work_ptr, work_doubles,
-                        maxiter, rtol, check_every, iterations_ptr, flags_ptr, rr_ptr, init_ptr, sync)
+    return _bicgstab_batch(False, members, ns, matrices, b_ptr, x0_ptr, x_ptr, offsets, work_ptr, work_doubles, maxiter, rtol, check_every,
+                           iterations_ptr, flags_ptr, rr_ptr, init_ptr, sync)
 
 
 def bicgstab_batch_max_n():
@@ -1294,26 +1306,8 @@ def bicgstab_batch_ml_device(members, ns, matrices, b_ptr, x0_ptr, x_ptr, offset
     """bicgstab_batch_device for a batch that may hold MultilevelPreconditioner objects next to everything that function takes
     (ilupp_hip_bicgstab_batch_ml_device: a launch with a multilevel member runs the kernel's second instantiation, in which a member's
     apply is a choice on its descriptor).  Returns the routes: members of route 1 or 2 are NOT solved."""
-    cnt = len(members)
-    if len(matrices) != cnt or len(offsets) != cnt or len(ns) != cnt:
-        raise ValueError("%d preconditioners but %d dimensions, %d matrices and %d offsets" % (cnt, len(ns), len(matrices), len(offsets)))
-    if cnt == 0:
-        return []
-    HP, HV, HM = (_VP * cnt)(), (_VP * cnt)(), (_VP * cnt)()
-    for k, m in enumerate(members):
-        if m is None:
-            continue
-        if isinstance(m, PivotedPreconditioner):
-            HV[k] = m._h
-        elif isinstance(m, Preconditioner):
-            HP[k] = m._h
-        elif isinstance(m, MultilevelPreconditioner):
-            HM[k] = m._h
-        else:
-            raise TypeError("a batched solve takes ILUCP / ILUTP / ILU0 / ILUT / ILUC / IChol0 / ICholT / multilevel ILU++ preconditioners "
-                            "or None, got %s" % type(m).__name__)
-    return _solve_batch("ilupp_hip_bicgstab_batch_ml_device", (HP, HV, HM), ns, matrices, b_ptr, x0_ptr, x_ptr, offsets, work_ptr,
-                        work_doubles, maxiter, rtol, check_every, iterations_ptr, flags_ptr, rr_ptr, init_ptr, sync)
+    return _bicgstab_batch(True, members, ns, matrices, b_ptr, x0_ptr, x_ptr, offsets, work_ptr, work_doubles, maxiter, rtol, check_every,
+                           iterations_ptr, flags_ptr, rr_ptr, init_ptr, sync)
 
 
 def bicgstab_batch_ml_max_n():

@@ -2187,6 +2187,21 @@ int ml_create_common(const DevMat &A, const ilupp_ml_params *ip, ilupp_ml **out)
 
 namespace ilupp {
 
+// a batched construction that gets no stream to run on
+static int no_batch_stream() { set_error("batched construction: no stream"); return ILUPP_ERR_HIP; }
+
+// how a batched construction went, for every kind of batch: the members' codes into the caller's array, if it gave one, and the first
+// failure returned and named by its number
+static int batch_first_failure(int32_t count, const std::vector<int> &rcs, const std::vector<std::string> &msgs, int32_t *status)
+{
+    int first = ILUPP_OK;
+    for (int32_t i = 0; i < count; ++i) {
+        if (status) status[i] = rcs[(size_t)i];
+        if (rcs[(size_t)i] && !first) { first = rcs[(size_t)i]; set_error("matrix " + std::to_string(i) + " of the batch: " + msgs[(size_t)i]); }
+    }
+    return first;
+}
+
 // The workers of a batched construction (ilupp_hip_ml_create_batch, ilupp_hip_ilucp_create_batch, ilupp_hip_ilutp_create_batch): `build(i)`
 // constructs member i on the calling worker's thread and returns its code; `worst_bytes` is the device memory the largest member holds
 // while it is built.  At most 64 workers (ILUPP_BATCH_WORKERS, read per call) and as many as the memory takes: 0.6 of the free bytes, the
@@ -2207,7 +2222,7 @@ int batch_build(int32_t count, double worst_bytes, int32_t *status, const std::f
         if (worst_bytes > 0.0) { const double fit = 0.6 * (double)free_b / worst_bytes; if (fit < (double)workers) workers = fit < 1.0 ? 1 : (int)fit; }
     }
     ChainBatch *cb = chain_batch_create(workers);
-    if (!cb) { set_error("batched construction: no stream"); return ILUPP_ERR_HIP; }
+    if (!cb) return no_batch_stream();
     // (the batch and its stream go when this call unwinds, whatever throws below)
     struct BatchGuard { ChainBatch *b; ~BatchGuard() { if (b) chain_batch_destroy(b); } } cbg{cb};
     std::vector<int> rcs((size_t)count, ILUPP_OK);
@@ -2249,12 +2264,7 @@ int batch_build(int32_t count, double worst_bytes, int32_t *status, const std::f
         work(0);
     }
     chain_batch_destroy(cbg.b); cbg.b = nullptr;
-    int first = ILUPP_OK;
-    for (int32_t i = 0; i < count; ++i) {
-        if (status) status[i] = rcs[(size_t)i];
-        if (rcs[(size_t)i] && !first) { first = rcs[(size_t)i]; set_error("matrix " + std::to_string(i) + " of the batch: " + msgs[(size_t)i]); }
-    }
-    return first;
+    return batch_first_failure(count, rcs, msgs, status);
 }
 
 }  // namespace ilupp
@@ -2546,7 +2556,8 @@ struct BatchScratch {
     // the two tables of a batched multilevel apply (member records, and the level records of all of them), each cached on its own
     BatchBuf<MlApplyDesc> mltable{64, true};
     BatchBuf<MlLevelDesc> mllevels{64, true};
-    // a solve with multilevel members: their level records (one table, uploaded through mllevels) and, per workgroup of the launch, where
+    std::vector<MlApplyDesc> mfresh;              // the member records of a multilevel apply's launch (S.fresh stays empty there)
+    // the level records of a launch's multilevel members (one table, uploaded through mllevels) and, per workgroup of a solve's launch, where
     // its member's records start there (-1: not a multilevel member)
     std::vector<MlLevelDesc> lfresh;
     std::vector<int32_t> ml_first;
@@ -2556,9 +2567,9 @@ struct BatchScratch {
 // permutation (or none) and the side it stands on, and the n doubles the one-array path hands its first sweep's result over in.  A
 // pivoting member brings its own tmp and is ordered through its owner's batch_ev; a non-pivoting one (owner == nullptr) gets a slice of
 // the scratch's block, which only launches on the scratch's stream ever touch, and is ordered through p->batch_ev.  p == nullptr: a
-// member without a preconditioner (the CG solve only).  ml: a multilevel member of the BiCGstab solve (p stays null: its levels are objects
-// of their own, described by batch_describe from what the batched multilevel apply reads, ordered through every level's batch_ev, its
-// scratch the object's own buf).
+// member without a preconditioner (the CG solve only).  ml: a multilevel member, of the batched apply or the BiCGstab solve (p stays null:
+// its levels are objects of their own, described from what ml_apply_dev reads, ordered through every level's batch_ev, its scratch the
+// object's own buf).
 struct BatchMember {
     ilupp_precond *p = nullptr;
     ilupp_ilucp *owner = nullptr;
@@ -2628,6 +2639,9 @@ int64_t batch_env_cap(int64_t cap_n)
 // n up to which a member goes to the apply's launch: 8 n bytes of LDS must fit
 int64_t batch_apply_max_n() { return batch_env_cap((int64_t)(pivot_apply_batch_lds_cap() / 8)); }
 
+// ... a multilevel member to the apply's launch (k_ml_apply_batch): the 8 n bytes of LDS its first level's sweeps take must fit
+int64_t ml_apply_batch_cap_n() { return batch_env_cap((int64_t)(ml_apply_batch_lds_cap() / 8)); }
+
 // ... to a solver's launch: the cap of the apply's launch, lowered by what the dot scratch takes
 // (ml: the launch of k_bicgstab_batch<true>, which a batch with a multilevel member runs: that instantiation's own cap)
 int64_t solve_batch_cap_n(BatchSolver solver, bool ml = false)
@@ -2675,6 +2689,17 @@ void ml_level_records(ilupp_ml *m, bool tr, std::vector<MlLevelDesc> *out)
     }
 }
 
+// ... of a member whose levels are made ready first (ensure_transposed on every level, as utu_half does); false, and nothing appended,
+// when a level object is degenerate
+bool ml_member_records(ilupp_ml *m, bool tr, std::vector<MlLevelDesc> *out)
+{
+    bool degenerate = false;
+    for (ilupp_precond *p : m->obj) { ensure_transposed(p); degenerate = degenerate || p->degenerate; }
+    if (degenerate) return false;
+    ml_level_records(m, tr, out);
+    return true;
+}
+
 // Route and describe the members of a batched launch: route 0 = the launch (n <= cap_n, object not degenerate), 1 = too large, 2 = degenerate.
 // S.fresh / S.launched receive the descriptors and member numbers of route 0, from the tables the single apply uses (apply_plan,
 // sweep_parts); xoff = offsets[i].  A pivoting member is prepared as its single apply prepares it (prepare_apply).  A non-pivoting one
@@ -2697,11 +2722,8 @@ void batch_describe(BatchScratch &S, int32_t count, const BatchMember *members, 
         if (v.ml) {
             // a multilevel member (k_bicgstab_batch<true>): plain_first == 2, kind1 levels from ptr1 (set by batch_stage, when the level
             // table's place on the device is known), kind2 the direction, tmp the object's own scratch
-            bool degenerate = false;
-            for (ilupp_precond *q : v.ml->obj) { ensure_transposed(q); degenerate = degenerate || q->degenerate; }
-            if (degenerate) { S.route[(size_t)i] = 2; continue; }
             ml_first = (int32_t)S.lfresh.size();
-            ml_level_records(v.ml, !v.plain_first, &S.lfresh);
+            if (!ml_member_records(v.ml, !v.plain_first, &S.lfresh)) { S.route[(size_t)i] = 2; continue; }
             d.plain_first = 2; d.kind1 = (int32_t)v.ml->obj.size(); d.kind2 = v.plain_first ? 0 : 1; d.tmp = v.ml->buf;
         } else if (p) {
             const ApplyPlan plan = apply_plan(p, v.plain_first ? 0 : 1);
@@ -2794,35 +2816,90 @@ void batch_systems(BatchScratch &S, int32_t count, const BatchMember *members, i
     batch_upload(S.stream, S.sys, fresh, false);
 }
 
-// Queue the applies of all members: route 0 = the launch (n within the LDS cap, object not degenerate), 1 = too large (for the LDS, or for
-// a launch it would have to itself) and 2 = degenerate through the single apply on the member's own stream.  Everything is joined on the scratch's stream when this returns; nothing is waited for.
+// Route and describe the members of a batched MULTILEVEL apply (k_ml_apply_batch), as batch_describe does for the other classes: route 0 =
+// the launch (n <= cap_n, no level object degenerate), 1 = too large, 2 = degenerate.  S.mfresh / S.lfresh / S.launched receive a member's
+// record, one record per level (ml_member_records) and the member numbers of route 0; a member's scratch is the object's own buf.
+void ml_apply_describe(BatchScratch &S, int32_t count, const BatchMember *members, const int64_t *offsets, int64_t cap_n)
+{
+    S.route.assign((size_t)count, 0); S.status.assign((size_t)count, ILUPP_OK); S.h_err.assign((size_t)count, 0);
+    S.launched.clear(); S.fresh.clear(); S.mfresh.clear(); S.lfresh.clear();
+    for (int32_t i = 0; i < count; ++i) {
+        ilupp_ml *m = members[i].ml;
+        if (m->n > cap_n) { S.route[(size_t)i] = 1; continue; }
+        const bool tr = !members[i].plain_first;
+        MlApplyDesc d;
+        memset(&d, 0, sizeof(d));
+        d.n = m->n; d.levels = (int32_t)m->obj.size(); d.first = (int32_t)S.lfresh.size(); d.transpose = tr ? 1 : 0;
+        d.xoff = offsets[i]; d.tmp = m->buf;
+        if (!ml_member_records(m, tr, &S.lfresh)) { S.route[(size_t)i] = 2; continue; }
+        S.mfresh.push_back(d);
+        S.launched.push_back(i);
+    }
+}
+
+// ... made ready for their launch, as batch_stage does: the bytes of LDS (8 n of the largest member, returned), the error words, the two
+// tables (each uploaded again only when a record of it differs), and the stream behind whatever is still queued on a member's own stream
+size_t ml_apply_stage(BatchScratch &S, const BatchMember *members)
+{
+    hipStream_t bs = S.stream;
+    size_t lds = 0;
+    for (const MlApplyDesc &d : S.mfresh) if ((size_t)8 * (size_t)d.n > lds) lds = (size_t)8 * (size_t)d.n;
+    S.err.reserve(bs, S.mfresh.size());
+    for (size_t k = 0; k < S.mfresh.size(); ++k) S.mfresh[k].err = S.err.d + k;
+    batch_upload(bs, S.mltable, S.mfresh);
+    batch_upload(bs, S.mllevels, S.lfresh);
+    // (the levels of a member share the first one's stream: one join per member)
+    for (int32_t i : S.launched) batch_join(bs, batch_stream_obj(members[i]));
+    return lds;
+}
+
+// the single apply of a member on its own stream, and what waits for it
+int batch_single_apply(const BatchMember &v, double *x, int transpose)
+{
+    return v.ml ? ml_apply_dev(v.ml, x, transpose) : v.owner ? pivot_apply_dev(v.owner, x, transpose) : apply_dev(v.p, x, transpose);
+}
+int batch_single_finish(const BatchMember &v) { return v.ml ? ml_finish_apply(v.ml) : finish_apply(v.p); }
+
+// Queue the applies of all members (all of one class): route 0 = the launch (n within the LDS cap, object not degenerate), 1 = too large (for
+// the LDS, or for a launch it would have to itself) and 2 = degenerate through the single apply on the member's own stream.  Multilevel
+// members have a launch, a cap and tables of their own (ml_apply_describe); everything else is one path.  Everything is joined on the
+// scratch's stream when this returns; nothing is waited for.
 // staged: the vectors were put there by work on the scratch's stream (the host entry), not by the caller's stream.
 int apply_batch_run(BatchScratch &S, int32_t count, const BatchMember *members, double *d_x, const int64_t *offsets, int transpose, bool staged)
 {
     hipStream_t bs = S.stream;
     if (!staged) order_after_caller(bs, S.cev[0]);
     else ILUPP_HIP(hipEventRecord(S.in_ev, bs));
-    const int64_t cap_n = batch_apply_max_n();
-    batch_describe(S, count, members, offsets, cap_n);
+    const bool ml = members[0].ml != nullptr;
+    const int64_t cap_n = ml ? ml_apply_batch_cap_n() : batch_apply_max_n();
+    if (ml) ml_apply_describe(S, count, members, offsets, cap_n);
+    else batch_describe(S, count, members, offsets, cap_n);
     // ONE member in the launch is one workgroup of 256 lanes walking all its rows, 0.06 ms + 0.015 ms per 1 000 rows, where the general sweeps
     // of the single apply take 0.11 - 0.12 ms whatever n is: past n = 4 096 the member alone is faster on the single apply (n = 4 000: 0.92 -
     // 1.18 x, 6 000: 1.2 - 1.5 x, 12 000: 1.9 - 2.5 x; two members of n = 12 000 break even, four take half the loop's time:
     // profiles/r10_pivot_apply_batch.txt)
-    if (S.launched.size() == 1 && S.fresh[0].n > kSmallSweepMax) { S.route[(size_t)S.launched[0]] = 1; S.launched.clear(); S.fresh.clear(); }
+    if (S.launched.size() == 1 && members[S.launched[0]].n > kSmallSweepMax) {
+        S.route[(size_t)S.launched[0]] = 1;
+        S.launched.clear(); S.fresh.clear(); S.mfresh.clear(); S.lfresh.clear();
+    }
     if (!S.launched.empty()) {
-        const size_t lds = batch_stage(S, members, cap_n);
-        OR_RETURN(pivot_apply_batch_launch(bs, (int32_t)S.launched.size(), S.table.d, d_x, lds));
+        const int32_t nl = (int32_t)S.launched.size();
+        if (ml) {
+            const size_t lds = ml_apply_stage(S, members);
+            OR_RETURN(ml_apply_batch_launch(bs, nl, S.mltable.d, S.mllevels.d, d_x, lds));
+        } else {
+            const size_t lds = batch_stage(S, members, cap_n);
+            OR_RETURN(pivot_apply_batch_launch(bs, nl, S.table.d, d_x, lds));
+        }
         batch_launched(S, members);
     }
     for (int32_t i = 0; i < count; ++i) {
         if (S.route[(size_t)i] == 0) continue;
-        const BatchMember &v = members[i];
-        hipStream_t st = v.p->stream;
-        if (staged) ILUPP_HIP(hipStreamWaitEvent(st, S.in_ev, 0));
-        if (v.owner) OR_RETURN(pivot_apply_dev(v.owner, d_x + offsets[i], transpose));
-        else OR_RETURN(apply_dev(v.p, d_x + offsets[i], transpose));
-        ILUPP_HIP(hipEventRecord(v.p->sev[1], st));
-        ILUPP_HIP(hipStreamWaitEvent(bs, v.p->sev[1], 0));
+        ilupp_precond *q = batch_stream_obj(members[i]);
+        if (staged) ILUPP_HIP(hipStreamWaitEvent(q->stream, S.in_ev, 0));
+        OR_RETURN(batch_single_apply(members[i], d_x + offsets[i], transpose));
+        ILUPP_HIP(hipEventRecord(q->sev[1], q->stream));
+        ILUPP_HIP(hipStreamWaitEvent(bs, q->sev[1], 0));
     }
     return ILUPP_OK;
 }
@@ -2835,7 +2912,7 @@ int apply_batch_finish(BatchScratch &S, int32_t count, const BatchMember *member
     std::vector<std::string> msgs((size_t)count);
     for (int32_t i = 0; i < count; ++i)
         if (singles && S.route[(size_t)i] != 0) {
-            S.status[(size_t)i] = finish_apply(members[i].p);
+            S.status[(size_t)i] = batch_single_finish(members[i]);
             if (S.status[(size_t)i]) msgs[(size_t)i] = g_last_error;
         }
     std::vector<int32_t> err((size_t)(nl > 0 ? nl : 1), 0);
@@ -2867,7 +2944,43 @@ int apply_batch_device(int32_t count, const std::vector<BatchMember> &mv, double
     return ILUPP_OK;
 }
 
+// What both host entries of the batched apply do once their arguments are checked and their members named (at least one): x[i], len[i]
+// doubles, is member i's vector, replaced by its apply.  The call has waited for everything when it returns.
+int apply_batch_host(const std::vector<BatchMember> &mv, double *const *x, const int64_t *len, int transpose, int32_t *route)
+{
+    const int32_t count = (int32_t)mv.size();
+    std::lock_guard<std::mutex> lk(g_batch_mu);
+    BatchScratch &S = batch_scratch();
+    // all vectors through ONE device buffer: one packed upload, one download
+    std::vector<int64_t> off((size_t)count);
+    size_t total = 0;
+    for (int32_t i = 0; i < count; ++i) { off[(size_t)i] = (int64_t)total; total += (size_t)len[i]; }
+    S.stage.reserve(S.stream, total);
+    for (int32_t i = 0; i < count; ++i) memcpy(S.stage.h + off[(size_t)i], x[i], sizeof(double) * (size_t)len[i]);
+    ILUPP_HIP(hipMemcpyAsync(S.stage.d, S.stage.h, sizeof(double) * total, hipMemcpyHostToDevice, S.stream));
+    int rc = apply_batch_run(S, count, mv.data(), S.stage.d, off.data(), transpose, true);
+    routes_out(S.route, route);
+    if (rc) { (void)hipStreamSynchronize(S.stream); return rc; }
+    ILUPP_HIP(hipMemcpyAsync(S.stage.h, S.stage.d, sizeof(double) * total, hipMemcpyDeviceToHost, S.stream));
+    rc = apply_batch_finish(S, count, mv.data());
+    // (a member that failed keeps its vector as it was; the others have theirs)
+    for (int32_t i = 0; i < count; ++i)
+        if (S.status[(size_t)i] == ILUPP_OK) memcpy(x[i], S.stage.h + off[(size_t)i], sizeof(double) * (size_t)len[i]);
+    return rc;
+}
+
 // ---- the argument checks the entries share, each entry in its own order: all before any device call ----
+// the host vectors of a batched apply: every one there, and as long as its member
+template <class Handle>
+int batch_vector_args(int32_t count, Handle *const *members, double *const *x, const int64_t *len)
+{
+    for (int32_t i = 0; i < count; ++i) {
+        if (!x[i]) { set_error("null argument"); return ILUPP_ERR_INVALID; }
+        if (len[i] != members[i]->n) { set_error("vector has wrong size for preconditioner!"); return ILUPP_ERR_WRONG_SIZE; }
+    }
+    return ILUPP_OK;
+}
+
 // a handle that stands twice in `seen` (a member's scratch vector and its factors serve one launch at a time)
 int batch_no_duplicates(std::vector<const void *> &seen)
 {
@@ -2959,9 +3072,6 @@ int solve_batch_run(BatchSolver solver, int32_t count, const std::vector<BatchMe
 }
 
 // ---- many MULTILEVEL members applied at once: one launch, one workgroup per member (k_ml_apply_batch, sptrsv_batch.hip) ----
-// n up to which a multilevel member goes to the launch: the 8 n bytes of LDS its first level's sweeps take must fit
-int64_t ml_apply_batch_cap_n() { return batch_env_cap((int64_t)(ml_apply_batch_lds_cap() / 8)); }
-
 // null arguments, a negative count, a null member, a member named twice
 int ml_batch_args(int32_t count, ilupp_ml *const *members, const void *a, const void *b)
 {
@@ -2972,88 +3082,6 @@ int ml_batch_args(int32_t count, ilupp_ml *const *members, const void *a, const 
     }
     std::vector<const void *> seen(members, members + count);
     return batch_no_duplicates(seen);
-}
-
-// Queue the applies of all members, as apply_batch_run does for the other classes: route 0 = the launch (n within the LDS cap, no level
-// object degenerate), 1 = too large (for the LDS, or for a launch it would have to itself) and 2 = degenerate through ml_apply_dev on the
-// member's own stream.  A member's record and one record per level (ml_level_records, ensure_transposed first, as utu_half does) are
-// written from what ml_apply_dev reads; its scratch is the object's own m->buf.  Everything is joined on the scratch's stream when this
-// returns; nothing is waited for.  staged: the vectors were put there by work on the scratch's stream (the host entry).
-int ml_apply_batch_run(BatchScratch &S, int32_t count, ilupp_ml *const *members, double *d_x, const int64_t *offsets, int transpose, bool staged)
-{
-    hipStream_t bs = S.stream;
-    if (!staged) order_after_caller(bs, S.cev[0]);
-    else ILUPP_HIP(hipEventRecord(S.in_ev, bs));
-    const int64_t cap_n = ml_apply_batch_cap_n();
-    const bool tr = transpose != 0;
-    S.route.assign((size_t)count, 0); S.status.assign((size_t)count, ILUPP_OK); S.h_err.assign((size_t)count, 0);
-    S.launched.clear();
-    std::vector<MlApplyDesc> mfresh;
-    std::vector<MlLevelDesc> lfresh;
-    for (int32_t i = 0; i < count; ++i) {
-        ilupp_ml *m = members[i];
-        if (m->n > cap_n) { S.route[(size_t)i] = 1; continue; }
-        bool degenerate = false;
-        for (ilupp_precond *p : m->obj) { ensure_transposed(p); degenerate = degenerate || p->degenerate; }
-        if (degenerate) { S.route[(size_t)i] = 2; continue; }
-        MlApplyDesc d;
-        memset(&d, 0, sizeof(d));
-        d.n = m->n; d.levels = (int32_t)m->obj.size(); d.first = (int32_t)lfresh.size(); d.transpose = tr ? 1 : 0;
-        d.xoff = offsets[i]; d.tmp = m->buf;
-        ml_level_records(m, tr, &lfresh);
-        mfresh.push_back(d);
-        S.launched.push_back(i);
-    }
-    // (ONE member in the launch: the rule of apply_batch_run, past kSmallSweepMax rows it is faster on its single apply)
-    if (S.launched.size() == 1 && mfresh[0].n > kSmallSweepMax) { S.route[(size_t)S.launched[0]] = 1; S.launched.clear(); mfresh.clear(); lfresh.clear(); }
-    if (!S.launched.empty()) {
-        size_t lds = 0;
-        for (const MlApplyDesc &d : mfresh) if ((size_t)8 * (size_t)d.n > lds) lds = (size_t)8 * (size_t)d.n;
-        S.err.reserve(bs, mfresh.size());
-        for (size_t k = 0; k < mfresh.size(); ++k) mfresh[k].err = S.err.d + k;
-        batch_upload(bs, S.mltable, mfresh);
-        batch_upload(bs, S.mllevels, lfresh);
-        // (the levels of a member share the first one's stream: one join per member)
-        for (int32_t i : S.launched) batch_join(bs, members[i]->obj[0]);
-        OR_RETURN(ml_apply_batch_launch(bs, (int32_t)S.launched.size(), S.mltable.d, S.mllevels.d, d_x, lds));
-        // behind the launch: a later single apply of a member (ml_apply_dev) and the destruction of each of its level objects
-        ILUPP_HIP(hipEventRecord(S.done_ev, bs));
-        for (int32_t i : S.launched) for (ilupp_precond *p : members[i]->obj) p->batch_ev = S.done_ev;
-    }
-    for (int32_t i = 0; i < count; ++i) {
-        if (S.route[(size_t)i] == 0) continue;
-        ilupp_ml *m = members[i];
-        hipStream_t st = m->obj[0]->stream;
-        if (staged) ILUPP_HIP(hipStreamWaitEvent(st, S.in_ev, 0));
-        OR_RETURN(ml_apply_dev(m, d_x + offsets[i], transpose));
-        ILUPP_HIP(hipEventRecord(m->obj[0]->sev[1], st));
-        ILUPP_HIP(hipStreamWaitEvent(bs, m->obj[0]->sev[1], 0));
-    }
-    return ILUPP_OK;
-}
-
-// wait for a batch that ml_apply_batch_run queued and say how it went: status per member, the first failure returned and named by its number
-int ml_apply_batch_finish(BatchScratch &S, int32_t count, ilupp_ml *const *members)
-{
-    const int32_t nl = (int32_t)S.launched.size();
-    std::vector<std::string> msgs((size_t)count);
-    for (int32_t i = 0; i < count; ++i)
-        if (S.route[(size_t)i] != 0) {
-            S.status[(size_t)i] = ml_finish_apply(members[i]);
-            if (S.status[(size_t)i]) msgs[(size_t)i] = g_last_error;
-        }
-    std::vector<int32_t> err((size_t)(nl > 0 ? nl : 1), 0);
-    if (nl > 0) ILUPP_HIP(d2h_async(S.stream, err.data(), S.err.d, sizeof(int32_t) * (size_t)nl));
-    ILUPP_HIP(stream_sync(S.stream));
-    for (int32_t k = 0; k < nl; ++k) {
-        const int32_t i = S.launched[(size_t)k];
-        for (ilupp_precond *p : members[i]->obj) p->batch_ev = nullptr;
-        S.h_err[(size_t)i] = err[(size_t)k];
-        if (err[(size_t)k]) { S.status[(size_t)i] = ILUPP_ERR_TIMEOUT; msgs[(size_t)i] = "triangular solve: dependency wait timed out (factor not triangular?)"; }
-    }
-    for (int32_t i = 0; i < count; ++i)
-        if (S.status[(size_t)i]) { set_error("member " + std::to_string(i) + " of the batch: " + msgs[(size_t)i]); return S.status[(size_t)i]; }
-    return ILUPP_OK;
 }
 
 }  // namespace
@@ -3117,30 +3145,9 @@ int ilupp_hip_pivot_apply_batch(int32_t count, ilupp_ilucp *const *members, doub
 {
     API_TRY
     OR_RETURN(pivot_batch_args(count, members, x, len));
-    for (int32_t i = 0; i < count; ++i) {
-        if (!x[i]) { set_error("null argument"); return ILUPP_ERR_INVALID; }
-        if (len[i] != members[i]->n) { set_error("vector has wrong size for preconditioner!"); return ILUPP_ERR_WRONG_SIZE; }
-    }
+    OR_RETURN(batch_vector_args(count, members, x, len));
     if (count == 0) return ILUPP_OK;
-    std::lock_guard<std::mutex> lk(g_batch_mu);
-    BatchScratch &S = batch_scratch();
-    // all vectors through ONE device buffer: one packed upload, one download
-    std::vector<int64_t> off((size_t)count);
-    size_t total = 0;
-    for (int32_t i = 0; i < count; ++i) { off[(size_t)i] = (int64_t)total; total += (size_t)len[i]; }
-    S.stage.reserve(S.stream, total);
-    for (int32_t i = 0; i < count; ++i) memcpy(S.stage.h + off[(size_t)i], x[i], sizeof(double) * (size_t)len[i]);
-    ILUPP_HIP(hipMemcpyAsync(S.stage.d, S.stage.h, sizeof(double) * total, hipMemcpyHostToDevice, S.stream));
-    const std::vector<BatchMember> mv = batch_members(count, members, transpose);
-    int rc = apply_batch_run(S, count, mv.data(), S.stage.d, off.data(), transpose, true);
-    routes_out(S.route, route);
-    if (rc) { (void)hipStreamSynchronize(S.stream); return rc; }
-    ILUPP_HIP(hipMemcpyAsync(S.stage.h, S.stage.d, sizeof(double) * total, hipMemcpyDeviceToHost, S.stream));
-    rc = apply_batch_finish(S, count, mv.data());
-    // (a member that failed keeps its vector as it was; the others have theirs)
-    for (int32_t i = 0; i < count; ++i)
-        if (S.status[(size_t)i] == ILUPP_OK) memcpy(x[i], S.stage.h + off[(size_t)i], sizeof(double) * (size_t)len[i]);
-    return rc;
+    return apply_batch_host(batch_members(count, members, transpose), x, len, transpose, route);
     API_CATCH
 }
 
@@ -3264,14 +3271,7 @@ int ilupp_hip_ml_apply_batch_device(int32_t count, ilupp_ml *const *members, dou
     API_TRY
     const int rc0 = ml_batch_args(count, members, d_x, offsets);
     if (rc0 || count == 0) return rc0;
-    std::lock_guard<std::mutex> lk(g_batch_mu);
-    BatchScratch &S = batch_scratch();
-    const int rc = ml_apply_batch_run(S, count, members, d_x, offsets, transpose, false);
-    routes_out(S.route, route);
-    if (rc) return rc;
-    if (sync) return ml_apply_batch_finish(S, count, members);
-    order_caller_after(S.stream, S.cev[1]);
-    return ILUPP_OK;
+    return apply_batch_device(count, batch_members(count, members, transpose), d_x, offsets, transpose, sync, route);
     API_CATCH
 }
 
@@ -3279,29 +3279,9 @@ int ilupp_hip_ml_apply_batch(int32_t count, ilupp_ml *const *members, double *co
 {
     API_TRY
     OR_RETURN(ml_batch_args(count, members, x, len));
-    for (int32_t i = 0; i < count; ++i) {
-        if (!x[i]) { set_error("null argument"); return ILUPP_ERR_INVALID; }
-        if (len[i] != members[i]->n) { set_error("vector has wrong size for preconditioner!"); return ILUPP_ERR_WRONG_SIZE; }
-    }
+    OR_RETURN(batch_vector_args(count, members, x, len));
     if (count == 0) return ILUPP_OK;
-    std::lock_guard<std::mutex> lk(g_batch_mu);
-    BatchScratch &S = batch_scratch();
-    // all vectors through ONE device buffer: one packed upload, one download
-    std::vector<int64_t> off((size_t)count);
-    size_t total = 0;
-    for (int32_t i = 0; i < count; ++i) { off[(size_t)i] = (int64_t)total; total += (size_t)len[i]; }
-    S.stage.reserve(S.stream, total);
-    for (int32_t i = 0; i < count; ++i) memcpy(S.stage.h + off[(size_t)i], x[i], sizeof(double) * (size_t)len[i]);
-    ILUPP_HIP(hipMemcpyAsync(S.stage.d, S.stage.h, sizeof(double) * total, hipMemcpyHostToDevice, S.stream));
-    int rc = ml_apply_batch_run(S, count, members, S.stage.d, off.data(), transpose, true);
-    routes_out(S.route, route);
-    if (rc) { (void)hipStreamSynchronize(S.stream); return rc; }
-    ILUPP_HIP(hipMemcpyAsync(S.stage.h, S.stage.d, sizeof(double) * total, hipMemcpyDeviceToHost, S.stream));
-    rc = ml_apply_batch_finish(S, count, members);
-    // (a member that failed keeps its vector as it was; the others have theirs)
-    for (int32_t i = 0; i < count; ++i)
-        if (S.status[(size_t)i] == ILUPP_OK) memcpy(x[i], S.stage.h + off[(size_t)i], sizeof(double) * (size_t)len[i]);
-    return rc;
+    return apply_batch_host(batch_members(count, members, transpose), x, len, transpose, route);
     API_CATCH
 }
 
@@ -3536,28 +3516,70 @@ struct CreatedObjects {
     ~CreatedObjects() { for (ilupp_precond *p : v) if (p) { if (p->side) (void)stream_sync(p->side); destroy_obj(p); } }
 };
 
+// What the batched constructions share around their own launches, for one call: per member its code, its message, its route and its
+// object.  The first failing member is reported as "matrix i of the batch: ...", status[i] says which failed, and no object of the call
+// survives a failure (batch_build's convention).
+struct CreateShell {
+    const int32_t count;
+    const CreateMember *const m;
+    std::vector<int> rcs;
+    std::vector<std::string> msgs;
+    std::vector<int32_t> rt;
+    CreatedObjects objs;
+    bool failed = false;
+    CreateShell(BatchScratch &S, int32_t count_, const CreateMember *m_) : count(count_), m(m_), rcs((size_t)count_, ILUPP_OK), msgs((size_t)count_), rt((size_t)count_, 0)
+    {
+        for (hipEvent_t &e : S.tev) if (!e) ILUPP_HIP(hipEventCreate(&e));
+        objs.v.assign((size_t)count, nullptr);
+    }
+    void fail(int32_t i, int rc, const std::string &msg) { rcs[(size_t)i] = rc; msgs[(size_t)i] = msg; failed = true; }
+    // a member no construction of `name`'s kind takes
+    bool refused(int32_t i, const char *name)
+    {
+        if (m[i].n <= 0 || !m[i].indptr) { fail(i, ILUPP_ERR_INVALID, "matrix has size 0!"); return true; }
+        if (m[i].nnz < 0 || m[i].nnz + (int64_t)m[i].n > INT32_MAX) { fail(i, ILUPP_ERR_INVALID, std::string(name) + ": too many stored entries for 32-bit indices"); return true; }
+        return false;
+    }
+    // route 1: single(i, &object), the single constructor, on the member's own stream, next to the launches (it waits for its stream
+    // itself); nothing more is built once a member has failed
+    template <class Single>
+    void singles(Single &&single)
+    {
+        for (int32_t i = 0; i < count && !failed; ++i) {
+            if (rt[(size_t)i] != 1) continue;
+            if (objs.v[(size_t)i]) { destroy_obj(objs.v[(size_t)i]); objs.v[(size_t)i] = nullptr; }      // (it only held the two row-pointer arrays)
+            const int rc = single(i, &objs.v[(size_t)i]);
+            if (rc) fail(i, rc, g_last_error);
+        }
+    }
+    // the routes and the codes into the caller's arrays, then the first failure, or the objects handed out
+    int report(ilupp_precond **out, int32_t *status, int32_t *route)
+    {
+        routes_out(rt, route);
+        const int first = batch_first_failure(count, rcs, msgs, status);
+        if (first) return first;                     // (objs goes, and every object of the call with it)
+        for (int32_t i = 0; i < count; ++i) { out[i] = objs.v[(size_t)i]; objs.v[(size_t)i] = nullptr; }
+        return ILUPP_OK;
+    }
+};
+
 // What the entries of the batched ILU(0) and IChol(0) constructions do once the matrices are in device memory (count > 0; the caller holds the
 // construction lock and the batch lock).  staged: the matrices were uploaded on the scratch's stream (S.in_ev behind the upload), not
 // produced on the caller's.  Routes: 0 = built by the two launches; 1 = built by the single constructor inside this call (n above the cap
 // of the re-factorisation's launch, a longest row above its row cap, a matrix whose rows are not sorted or whose indices are out of
 // range -- whatever the single constructor does with it, it does here --, or a batch of one: a user who builds one object wants the
-// fully analysed one).  The first failing member is reported as "matrix i of the batch: ...", status[i] says which failed, and no
-// object of the call survives a failure (batch_build's convention).
+// fully analysed one).  Failures as CreateShell reports them.
 int factor_create_batch_run(const FactorBatchKind &K, BatchScratch &S, int32_t count, const CreateMember *m, int is_csr, bool staged, ilupp_precond **out, int32_t *status,
                           int32_t *route)
 {
     hipStream_t bs = S.stream;
-    for (hipEvent_t &e : S.tev) if (!e) ILUPP_HIP(hipEventCreate(&e));
-    std::vector<int> rcs((size_t)count, ILUPP_OK);
-    std::vector<std::string> msgs((size_t)count);
-    std::vector<int32_t> rt((size_t)count, 0);
-    CreatedObjects objs;
-    objs.v.assign((size_t)count, nullptr);
+    CreateShell C(S, count, m);
+    std::vector<int32_t> &rt = C.rt;
+    std::vector<ilupp_precond *> &objs = C.objs.v;
     const int64_t cap_n = batch_env_cap(K.max_n());
     std::vector<int32_t> cand;                       // the members of the symbolic launch
     for (int32_t i = 0; i < count; ++i) {
-        if (m[i].n <= 0 || !m[i].indptr) { rcs[(size_t)i] = ILUPP_ERR_INVALID; msgs[(size_t)i] = "matrix has size 0!"; continue; }
-        if (m[i].nnz < 0 || m[i].nnz + (int64_t)m[i].n > INT32_MAX) { rcs[(size_t)i] = ILUPP_ERR_INVALID; msgs[(size_t)i] = std::string(K.name) + ": too many stored entries for 32-bit indices"; continue; }
+        if (C.refused(i, K.name)) continue;
         if (count == 1 || m[i].n > cap_n) { rt[(size_t)i] = 1; continue; }
         cand.push_back(i);
     }
@@ -3571,7 +3593,7 @@ int factor_create_batch_run(const FactorBatchKind &K, BatchScratch &S, int32_t c
         S.cstat.reserve(bs, (size_t)count);
         // the objects, and the n + 1 row pointers of L and of U the symbolic launch writes
         for (int32_t i : cand) {
-            ilupp_precond *p = objs.v[(size_t)i] = new_obj(m[i].n);
+            ilupp_precond *p = objs[(size_t)i] = new_obj(m[i].n);
             if (K.llt) { p->kind = KIND_LLT; p->nnz_mode = NNZ_LLT; p->llt_diag_last = true; }
             else { p->kind = KIND_LU; p->nnz_mode = NNZ_GENERIC_LU; p->input_csc = !is_csr; }
             for (DevMat *M : {&p->Lc, &p->Uc}) {
@@ -3593,14 +3615,13 @@ int factor_create_batch_run(const FactorBatchKind &K, BatchScratch &S, int32_t c
         for (int32_t k = 0; k < nc; ++k) {
             const int32_t i = cand[(size_t)k];
             const CreateInfo &o = S.cinfo.h[k];
-            ilupp_precond *p = objs.v[(size_t)i];
+            ilupp_precond *p = objs[(size_t)i];
             if (o.flags & kCreateNnzDiffers) {
-                rcs[(size_t)i] = ILUPP_ERR_INVALID; msgs[(size_t)i] = std::string(K.name) + ": the number of stored entries handed in is not indptr[n]";
+                C.fail(i, ILUPP_ERR_INVALID, std::string(K.name) + ": the number of stored entries handed in is not indptr[n]");
             } else if (o.flags & kCreateUnsorted) {
                 rt[(size_t)i] = 1;
             } else if (o.missing >= 0) {
-                rcs[(size_t)i] = ILUPP_ERR_NO_DIAGONAL;
-                msgs[(size_t)i] = std::string(K.name) + ": structurally missing diagonal entry in row " + std::to_string(o.missing);
+                C.fail(i, ILUPP_ERR_NO_DIAGONAL, std::string(K.name) + ": structurally missing diagonal entry in row " + std::to_string(o.missing));
             } else {
                 if (K.fits(m[i].n, o.max_row_len) == 0) { rt[(size_t)i] = 1; continue; }
                 // exact index and value arrays, and what the object records of the factored matrix
@@ -3615,15 +3636,13 @@ int factor_create_batch_run(const FactorBatchKind &K, BatchScratch &S, int32_t c
             }
         }
     }
-    bool failed = false;
-    for (int32_t i = 0; i < count; ++i) failed = failed || rcs[(size_t)i] != ILUPP_OK;
-    const int32_t nl = failed ? 0 : (int32_t)launched.size();
+    const int32_t nl = C.failed ? 0 : (int32_t)launched.size();
     if (nl > 0) {
         // (this table is what the batched re-factorisation of the same members from the same buffers describes: its cache may hit)
         fresh.clear();
         size_t lds = 0;
         for (int32_t i : launched) {
-            const ilupp_precond *p = objs.v[(size_t)i];
+            const ilupp_precond *p = objs[(size_t)i];
             fresh.push_back(refactor_desc(K, p, m[i].data, m[i].indices, m[i].indptr, p->nnzA, i));
             const size_t want = K.fits(m[i].n, p->max_row_len);
             if (want > lds) lds = want;
@@ -3634,15 +3653,9 @@ int factor_create_batch_run(const FactorBatchKind &K, BatchScratch &S, int32_t c
         ILUPP_HIP(hipEventRecord(S.tev[3], bs));
         // whatever a member's own stream does next (an apply, factors(), ensure_*) comes after the launch that writes its factors
         ILUPP_HIP(hipEventRecord(S.done_ev, bs));
-        for (int32_t i : launched) ILUPP_HIP(hipStreamWaitEvent(objs.v[(size_t)i]->stream, S.done_ev, 0));
+        for (int32_t i : launched) ILUPP_HIP(hipStreamWaitEvent(objs[(size_t)i]->stream, S.done_ev, 0));
     }
-    // route 1: the single constructor, on the member's own stream, next to the launch (it waits for its stream itself)
-    for (int32_t i = 0; i < count && !failed; ++i) {
-        if (rt[(size_t)i] != 1) continue;
-        if (objs.v[(size_t)i]) { destroy_obj(objs.v[(size_t)i]); objs.v[(size_t)i] = nullptr; }      // (it only held the two row-pointer arrays)
-        const int rc = K.create_single(m[i], is_csr, staged, S.in_ev, &objs.v[(size_t)i]);
-        if (rc) { rcs[(size_t)i] = rc; msgs[(size_t)i] = g_last_error; failed = true; }
-    }
+    C.singles([&](int32_t i, ilupp_precond **made) { return K.create_single(m[i], is_csr, staged, S.in_ev, made); });
     if (nl > 0) {
         // a construction synchronises: the launch is over when the call returns
         std::vector<int32_t> st((size_t)count, 0);
@@ -3650,22 +3663,22 @@ int factor_create_batch_run(const FactorBatchKind &K, BatchScratch &S, int32_t c
         ILUPP_HIP(stream_sync(bs));
         ILUPP_HIP(hipEventElapsedTime(&create_ms, S.tev[2], S.tev[3]));
         for (int32_t i : launched) {
-            ilupp_precond *p = objs.v[(size_t)i];
-            if (st[(size_t)i] == 2) { rcs[(size_t)i] = ILUPP_ERR_TIMEOUT; msgs[(size_t)i] = std::string(K.name) + ": dependency wait timed out (invalid structure?)"; }
-            else if (st[(size_t)i] != 0) { rcs[(size_t)i] = ILUPP_ERR_INVALID; msgs[(size_t)i] = std::string(K.name) + ": the matrix changed while it was factored"; }
+            ilupp_precond *p = objs[(size_t)i];
+            if (st[(size_t)i] == 2) C.fail(i, ILUPP_ERR_TIMEOUT, std::string(K.name) + ": dependency wait timed out (invalid structure?)");
+            else if (st[(size_t)i] != 0) C.fail(i, ILUPP_ERR_INVALID, std::string(K.name) + ": the matrix changed while it was factored");
             // (the two launches' times, shared by the call's members)
             p->tm.analysis_ms = sym_ms; p->tm.numeric_ms = create_ms; p->tm.numeric_kernel_ms = create_ms;
         }
     }
-    routes_out(rt, route);
-    int first = ILUPP_OK;
-    for (int32_t i = 0; i < count; ++i) {
-        if (status) status[i] = rcs[(size_t)i];
-        if (rcs[(size_t)i] && !first) { first = rcs[(size_t)i]; set_error("matrix " + std::to_string(i) + " of the batch: " + msgs[(size_t)i]); }
-    }
-    if (first) return first;                         // (objs goes, and every object of the call with it)
-    for (int32_t i = 0; i < count; ++i) { out[i] = objs.v[(size_t)i]; objs.v[(size_t)i] = nullptr; }
-    return ILUPP_OK;
+    return C.report(out, status, route);
+}
+
+// the object a single constructor inside a batched construction fills, its stream behind the upload of a staged matrix (nullptr: no stream)
+ilupp_precond *single_obj(const CreateMember &m, bool staged, hipEvent_t in_ev)
+{
+    ilupp_precond *made = new_obj(m.n);
+    if (staged && hipStreamWaitEvent(made->stream, in_ev, 0) != hipSuccess) { destroy_obj(made); (void)no_batch_stream(); return nullptr; }
+    return made;
 }
 
 int ilu0_create_single(const CreateMember &m, int is_csr, bool staged, hipEvent_t in_ev, ilupp_precond **out)
@@ -3673,8 +3686,8 @@ int ilu0_create_single(const CreateMember &m, int is_csr, bool staged, hipEvent_
     if (staged) {
         int32_t head[10];
         host_head(m.h_indptr, m.h_indices, m.nnz, head);
-        ilupp_precond *made = new_obj(m.n);
-        if (hipStreamWaitEvent(made->stream, in_ev, 0) != hipSuccess) { destroy_obj(made); set_error("batched construction: no stream"); return ILUPP_ERR_HIP; }
+        ilupp_precond *made = single_obj(m, true, in_ev);
+        if (!made) return ILUPP_ERR_HIP;
         return ilu0_create_common(borrow_csr(m.data, m.indices, m.indptr, m.n, m.nnz, true), is_csr, head, out, made);
     }
     const int rc = ilu0_create_device_locked(m.data, m.indices, m.indptr, m.n, is_csr, out);
@@ -3682,17 +3695,25 @@ int ilu0_create_single(const CreateMember &m, int is_csr, bool staged, hipEvent_
     return rc;
 }
 
+// the single constructor of `name`'s kind on a borrowed matrix: the count of stored entries checked where nothing staged it, then
+// common(A, made)
+template <class Common>
+int borrowed_create_single(const char *name, const CreateMember &m, bool staged, hipEvent_t in_ev, Common &&common)
+{
+    if (!staged && (int64_t)read_device_nnz(m.indptr, m.n) != m.nnz) {
+        set_error(std::string(name) + ": the number of stored entries handed in is not indptr[n]");
+        return ILUPP_ERR_INVALID;
+    }
+    ilupp_precond *made = single_obj(m, staged, in_ev);
+    if (!made) return ILUPP_ERR_HIP;
+    DevMat A = borrow_csr(m.data, m.indices, m.indptr, m.n, m.nnz, true);
+    return common(A, made);
+}
+
 int ichol0_create_single(const CreateMember &m, int is_csr, bool staged, hipEvent_t in_ev, ilupp_precond **out)
 {
     (void)is_csr;                                    // (as ilupp_hip_ichol0_create)
-    if (!staged && (int64_t)read_device_nnz(m.indptr, m.n) != m.nnz) {
-        set_error("IChol0: the number of stored entries handed in is not indptr[n]");
-        return ILUPP_ERR_INVALID;
-    }
-    ilupp_precond *made = new_obj(m.n);
-    if (staged && hipStreamWaitEvent(made->stream, in_ev, 0) != hipSuccess) { destroy_obj(made); set_error("batched construction: no stream"); return ILUPP_ERR_HIP; }
-    DevMat A = borrow_csr(m.data, m.indices, m.indptr, m.n, m.nnz, true);
-    return ichol0_create_common(A, m.n, out, made);
+    return borrowed_create_single("IChol0", m, staged, in_ev, [&](DevMat &A, ilupp_precond *made) { return ichol0_create_common(A, m.n, out, made); });
 }
 
 // the arguments of the *_create_batch_device entries, then the run: run(scratch, count, members, is_csr, staged, out, status, route)
@@ -3775,14 +3796,8 @@ auto factor_run(const FactorBatchKind &K)
 // the single constructor inside a batched ILUT construction (route 1)
 int ilut_create_single(const CreateMember &m, int is_csr, bool staged, hipEvent_t in_ev, int32_t max_fill_in, double threshold, ilupp_precond **out)
 {
-    if (!staged && (int64_t)read_device_nnz(m.indptr, m.n) != m.nnz) {
-        set_error("ILUT: the number of stored entries handed in is not indptr[n]");
-        return ILUPP_ERR_INVALID;
-    }
-    ilupp_precond *made = new_obj(m.n);
-    if (staged && hipStreamWaitEvent(made->stream, in_ev, 0) != hipSuccess) { destroy_obj(made); set_error("batched construction: no stream"); return ILUPP_ERR_HIP; }
-    DevMat A = borrow_csr(m.data, m.indices, m.indptr, m.n, m.nnz, true);
-    return ilut_create_common(A, m.n, is_csr, max_fill_in, threshold, out, made);
+    return borrowed_create_single("ILUT", m, staged, in_ev,
+                                  [&](DevMat &A, ilupp_precond *made) { return ilut_create_common(A, m.n, is_csr, max_fill_in, threshold, out, made); });
 }
 
 // the stream is idle when the scope ends, however it ends: the pool blocks declared before it go back only then
@@ -3797,25 +3812,21 @@ struct StreamIdle {
 // fall into both LDS classes), the count-and-scan launch, ONE read-back of the members' records, the index and value arrays from the pool,
 // the fill launch.  Routes: 0 = built by the launches; 1 = built by ilut_create_single inside this call -- a batch of one, a clamped budget
 // of the largest capacity class, a member whose record says status 3 (a row that fits no tier of the launch), or a call whose slabs would
-// not fit the memory budget.  Failures as factor_create_batch_run reports them.
+// not fit the memory budget.  Failures as CreateShell reports them.
 int ilut_create_batch_run(BatchScratch &S, int32_t count, const CreateMember *m, int is_csr, bool staged, int32_t max_fill_in, double threshold,
                           ilupp_precond **out, int32_t *status, int32_t *route)
 {
     hipStream_t bs = S.stream;
-    for (hipEvent_t &e : S.tev) if (!e) ILUPP_HIP(hipEventCreate(&e));
-    std::vector<int> rcs((size_t)count, ILUPP_OK);
-    std::vector<std::string> msgs((size_t)count);
-    std::vector<int32_t> rt((size_t)count, 0);
-    CreatedObjects objs;
-    objs.v.assign((size_t)count, nullptr);
+    CreateShell C(S, count, m);
+    std::vector<int32_t> &rt = C.rt;
+    std::vector<ilupp_precond *> &objs = C.objs.v;
     std::vector<int32_t> cand;                       // the members of the launches
     std::vector<int32_t> pm((size_t)count, 1);       // the clamped budgets (ILUT.hpp:211-212)
     size_t slab_bytes = 0;
     int64_t rows = 0;
     auto rec_bytes = [](int32_t p) { return ((((size_t)4 + 4 * (size_t)p + 7) & ~(size_t)7) + 8 * (size_t)p + 127) & ~(size_t)127; };
     for (int32_t i = 0; i < count; ++i) {
-        if (m[i].n <= 0 || !m[i].indptr) { rcs[(size_t)i] = ILUPP_ERR_INVALID; msgs[(size_t)i] = "matrix has size 0!"; continue; }
-        if (m[i].nnz < 0 || m[i].nnz + (int64_t)m[i].n > INT32_MAX) { rcs[(size_t)i] = ILUPP_ERR_INVALID; msgs[(size_t)i] = "ILUT: too many stored entries for 32-bit indices"; continue; }
+        if (C.refused(i, "ILUT")) continue;
         const int32_t p = pm[(size_t)i] = std::min(std::max(max_fill_in, 1), m[i].n);
         if (count == 1 || ilut_batch_class(p) < 0 || cand.size() >= 65535) { rt[(size_t)i] = 1; continue; }
         cand.push_back(i);
@@ -3828,9 +3839,7 @@ int ilut_create_batch_run(BatchScratch &S, int32_t count, const CreateMember *m,
     if (!staged) order_after_caller(bs, S.cev[0]);
     const int32_t nc = (int32_t)cand.size();
     const bool debug = getenv("ILUPP_DEBUG") != nullptr;
-    bool failed = false;
-    for (int32_t i = 0; i < count; ++i) failed = failed || rcs[(size_t)i] != ILUPP_OK;
-    if (nc > 0 && !failed) {
+    if (nc > 0 && !C.failed) {
         PoolBlock b_Lri, b_Lrv, b_Llen, b_Urec, b_ctrl;
         IlutBatchWork work;
         StreamIdle idle{bs};                         // (declared last: the wait comes before the blocks above are given back)
@@ -3853,7 +3862,7 @@ int ilut_create_batch_run(BatchScratch &S, int32_t count, const CreateMember *m,
         int32_t max_n = 0;
         for (int32_t k = 0; k < nc; ++k) {
             const int32_t i = cand[(size_t)k], n = m[i].n, p = pm[(size_t)i];
-            ilupp_precond *q = objs.v[(size_t)i] = new_obj(n);
+            ilupp_precond *q = objs[(size_t)i] = new_obj(n);
             q->kind = KIND_LU; q->nnz_mode = NNZ_ILUT; q->input_csc = !is_csr;
             for (DevMat *M : {&q->Lc, &q->Uc}) {
                 M->n = n; M->is_csr = true; M->owns = true;
@@ -3912,17 +3921,13 @@ int ilut_create_batch_run(BatchScratch &S, int32_t count, const CreateMember *m,
         for (int32_t k = 0; k < nc; ++k) {
             const int32_t i = cand[(size_t)k];
             const IlutBatchInfo &o = S.tinfo.h[k];
-            ilupp_precond *q = objs.v[(size_t)i];
+            ilupp_precond *q = objs[(size_t)i];
             if (debug)
                 fprintf(stderr, "[ilupp] ilut_batch: member %d: %d of %d rows outgrew LDS (pool %d, U slots %d, kept %d), %d of them the pool-in-LDS tier too, status %d, rows launches %.3f ms\n",
                         i, o.outgrew, m[i].n, o.pool, o.uslots, o.kept, o.left_tier2, o.status, rows_ms);
             if (o.status == 3) { rt[(size_t)i] = 1; continue; }
-            if (o.status != 0) { rcs[(size_t)i] = ILUPP_ERR_TIMEOUT; msgs[(size_t)i] = "ILUT: dependency wait timed out"; failed = true; continue; }
-            if (o.zero_row >= 0) {
-                rcs[(size_t)i] = ILUPP_ERR_ZERO_PIVOT; msgs[(size_t)i] = "ILUT_heap: encountered zero pivot in row " + std::to_string(o.zero_row);      // ILUT.hpp:269-270
-                failed = true;
-                continue;
-            }
+            if (o.status != 0) { C.fail(i, ILUPP_ERR_TIMEOUT, "ILUT: dependency wait timed out"); continue; }
+            if (o.zero_row >= 0) { C.fail(i, ILUPP_ERR_ZERO_PIVOT, "ILUT_heap: encountered zero pivot in row " + std::to_string(o.zero_row)); continue; }      // ILUT.hpp:269-270
             q->Lc.nnz = o.nnz_l; q->Uc.nnz = o.nnz_u;
             for (DevMat *M : {&q->Lc, &q->Uc}) {
                 ILUPP_HIP(pool_malloc(&M->idx, sizeof(int32_t) * (size_t)(M->nnz > 0 ? M->nnz : 1)));
@@ -3934,32 +3939,18 @@ int ilut_create_batch_run(BatchScratch &S, int32_t count, const CreateMember *m,
             d.lidx = q->Lc.idx; d.lval = q->Lc.val; d.uidx = q->Uc.idx; d.uval = q->Uc.val;
             launched.push_back(i);
         }
-        if (!failed && !launched.empty()) {
+        if (!C.failed && !launched.empty()) {
             batch_upload(bs, S.ttable, fresh, false);
             OR_RETURN(ilut_batch_fill_launch(bs, nc, S.ttable.d, max_n));
             // whatever a member's own stream does next (an apply, factors(), ensure_*) comes after the launch that writes its factors
             ILUPP_HIP(hipEventRecord(S.done_ev, bs));
-            for (int32_t i : launched) ILUPP_HIP(hipStreamWaitEvent(objs.v[(size_t)i]->stream, S.done_ev, 0));
+            for (int32_t i : launched) ILUPP_HIP(hipStreamWaitEvent(objs[(size_t)i]->stream, S.done_ev, 0));
             // a construction synchronises: the launches are over when the call returns
             ILUPP_HIP(stream_sync(bs));
         }
     }
-    // route 1: the single constructor, on the member's own stream (it waits for its stream itself)
-    for (int32_t i = 0; i < count && !failed; ++i) {
-        if (rt[(size_t)i] != 1) continue;
-        if (objs.v[(size_t)i]) { destroy_obj(objs.v[(size_t)i]); objs.v[(size_t)i] = nullptr; }      // (it only held the two row-pointer arrays)
-        const int rc = ilut_create_single(m[i], is_csr, staged, S.in_ev, max_fill_in, threshold, &objs.v[(size_t)i]);
-        if (rc) { rcs[(size_t)i] = rc; msgs[(size_t)i] = g_last_error; failed = true; }
-    }
-    routes_out(rt, route);
-    int first = ILUPP_OK;
-    for (int32_t i = 0; i < count; ++i) {
-        if (status) status[i] = rcs[(size_t)i];
-        if (rcs[(size_t)i] && !first) { first = rcs[(size_t)i]; set_error("matrix " + std::to_string(i) + " of the batch: " + msgs[(size_t)i]); }
-    }
-    if (first) return first;                         // (objs goes, and every object of the call with it)
-    for (int32_t i = 0; i < count; ++i) { out[i] = objs.v[(size_t)i]; objs.v[(size_t)i] = nullptr; }
-    return ILUPP_OK;
+    C.singles([&](int32_t i, ilupp_precond **made) { return ilut_create_single(m[i], is_csr, staged, S.in_ev, max_fill_in, threshold, made); });
+    return C.report(out, status, route);
 }
 
 auto ilut_run(int32_t max_fill_in, double threshold)

@@ -230,33 +230,57 @@ def pivot_apply_batch_(members, x, offsets, transpose=False):
     member of another class -- before any native call.  Out of scope: ``DevicePreconditioner("ILUTP" / "ILUCP")`` (construction from device
     arrays).  The multilevel class has a batched apply of its own: ``ml_apply_batch_``.  The whole preconditioned BiCGstab solve of many systems in one launch:
     ``bicgstab_batch``."""
-    members, offsets = list(members), [int(o) for o in offsets]
-    if not isinstance(x, torch.Tensor) or x.dim() != 1 or x.dtype != torch.float64 or not x.is_cuda or not x.is_contiguous():
-        raise ValueError("x: expected a contiguous 1-D torch.float64 CUDA tensor")
-    if len(members) != len(offsets):
-        raise ValueError("%d preconditioners but %d offsets" % (len(members), len(offsets)))
-    natives = []
-    for P in members:
+    def native(P):
         pr = getattr(P, "pr", P)
         if not isinstance(pr, _native.PivotedPreconditioner):
             raise TypeError("pivot_apply_batch_ takes ILUCPPreconditioner / ILUTPPreconditioner instances of the ctypes binding, got %s"
                             % type(P).__name__)
-        natives.append(pr)
-    for pr, o in zip(natives, offsets):
-        if o < 0 or o + pr._n > x.numel():
-            raise ValueError("a vector of %d elements at offset %d does not lie inside x (%d elements)" % (pr._n, o, x.numel()))
-    if not natives:
-        return []
-    _on_current_stream()
-    return _native.pivot_apply_batch_device(natives, x.data_ptr(), offsets, transpose=transpose, sync=False)
+        return pr
+
+    return _apply_batch(members, x, offsets, transpose, entry=_native.pivot_apply_batch_device, native=native)
 
 
-class PivotedOperator:
+class _HostBuiltOperator:
+    """what PivotedOperator, MultilevelOperator and FactorOperator share: the apply of ``self.pr`` (dimension ``self.n``) on device tensors"""
+
+    _block = False          # k right-hand sides in one apply_ (FactorOperator); else one column at a time, and
+    _whose = ""             # ... the NotImplementedError names the class
+
+    def apply_(self, x, transpose=False):
+        """in place on a contiguous fp64 CUDA tensor of shape (n,) or (n, 1) -- (n, k) for a FactorOperator --; asynchronous, ordered on
+        torch's current stream"""
+        if not isinstance(x, torch.Tensor) or x.dim() not in (1, 2) or x.shape[0] != self.n:
+            raise ValueError("x: expected a tensor of shape (%d,) or (%d, %s), got %s"
+                             % (self.n, self.n, "k" if self._block else "1", tuple(getattr(x, "shape", ()))))
+        if x.dim() == 2 and x.shape[1] != 1 and not self._block:
+            raise NotImplementedError("k right-hand sides with %s preconditioner: apply_ one column at a time" % self._whose)
+        if x.dtype != torch.float64 or not x.is_cuda or not x.is_contiguous():
+            raise ValueError("x: expected a contiguous torch.float64 CUDA tensor")
+        _on_current_stream()
+        if x.dim() == 2 and self._block:
+            self.pr.apply_block_device(x.data_ptr(), self.n, x.shape[1], transpose=transpose, sync=False)
+        else:
+            self.pr.apply_device(x.data_ptr(), self.n, transpose=transpose, sync=False)
+        return x
+
+    def matvec(self, x):
+        return self.apply_(x.clone())
+
+    __matmul__ = matvec
+
+    def sync(self):
+        """wait for what was queued on torch's current stream (the applies are ordered on it)"""
+        torch.cuda.current_stream().synchronize()
+
+
+class PivotedOperator(_HostBuiltOperator):
     """An ``ilupp_amd.ILUCPPreconditioner`` / ``ILUTPPreconditioner`` (built on the host by the ctypes binding) as the ``M`` of ``cg`` /
     ``bicgstab``: ``apply_`` works in place on a device tensor through the single device apply (ilupp_hip_ilucp_apply_device), ordered on
     torch's current stream.  One right-hand side at a time: shape (n,) or (n, 1).  ``bicgstab(A, b[:, None], M=PivotedOperator(P))`` is
     the solve every member of ``bicgstab_batch`` has the bits of.  Not ``DevicePreconditioner("ILUCP")``: these classes are not constructed
     from device arrays."""
+
+    _whose = "a pivoting"
 
     def __init__(self, P):
         pr = getattr(P, "pr", P)
@@ -268,27 +292,6 @@ class PivotedOperator:
         self.n = pr._n
         self.shape = (self.n, self.n)
 
-    def apply_(self, x, transpose=False):
-        """in place on a contiguous fp64 CUDA tensor of shape (n,) or (n, 1); asynchronous, ordered on torch's current stream"""
-        if not isinstance(x, torch.Tensor) or x.dim() not in (1, 2) or x.shape[0] != self.n:
-            raise ValueError("x: expected a tensor of shape (%d,) or (%d, 1), got %s" % (self.n, self.n, tuple(getattr(x, "shape", ()))))
-        if x.dim() == 2 and x.shape[1] != 1:
-            raise NotImplementedError("k right-hand sides with a pivoting preconditioner: apply_ one column at a time")
-        if x.dtype != torch.float64 or not x.is_cuda or not x.is_contiguous():
-            raise ValueError("x: expected a contiguous torch.float64 CUDA tensor")
-        _on_current_stream()
-        self.pr.apply_device(x.data_ptr(), self.n, transpose=transpose, sync=False)
-        return x
-
-    def matvec(self, x):
-        return self.apply_(x.clone())
-
-    __matmul__ = matvec
-
-    def sync(self):
-        """wait for what was queued on torch's current stream (the applies are ordered on it)"""
-        torch.cuda.current_stream().synchronize()
-
 
 def _ml_native(P):
     """the native object of a multilevel member: an ``ilupp_amd.ILUppPreconditioner`` of the ctypes binding, a
@@ -299,7 +302,7 @@ def _ml_native(P):
     return pr if isinstance(pr, _native.MultilevelPreconditioner) else None
 
 
-class MultilevelOperator:
+class MultilevelOperator(_HostBuiltOperator):
     """A multilevel ILU++ preconditioner -- an ``ilupp_amd.ILUppPreconditioner`` (built on the host by the ctypes binding, alone or by
     ``ILUppPreconditioner.batch``) or a ``DevicePreconditioner("ILUpp", ...)`` -- as the ``M`` of ``bicgstab`` with a 2-D right-hand side
     and as a member of ``bicgstab_batch``: the sibling of ``PivotedOperator``.  ``apply_`` works in place on a device tensor through the
@@ -308,6 +311,7 @@ class MultilevelOperator:
     TypeError for any other class."""
 
     kind = "ILUppOperator"       # (not "ILUpp": the block loops of cg / bicgstab take this wrapper, with k = 1)
+    _whose = "the multilevel"
 
     def __init__(self, P):
         pr = None if isinstance(P, MultilevelOperator) else _ml_native(P)
@@ -317,27 +321,6 @@ class MultilevelOperator:
         self.P, self.pr = P, pr
         self.n = pr._n
         self.shape = (self.n, self.n)
-
-    def apply_(self, x, transpose=False):
-        """in place on a contiguous fp64 CUDA tensor of shape (n,) or (n, 1); asynchronous, ordered on torch's current stream"""
-        if not isinstance(x, torch.Tensor) or x.dim() not in (1, 2) or x.shape[0] != self.n:
-            raise ValueError("x: expected a tensor of shape (%d,) or (%d, 1), got %s" % (self.n, self.n, tuple(getattr(x, "shape", ()))))
-        if x.dim() == 2 and x.shape[1] != 1:
-            raise NotImplementedError("k right-hand sides with the multilevel preconditioner: apply_ one column at a time")
-        if x.dtype != torch.float64 or not x.is_cuda or not x.is_contiguous():
-            raise ValueError("x: expected a contiguous torch.float64 CUDA tensor")
-        _on_current_stream()
-        self.pr.apply_device(x.data_ptr(), self.n, transpose=transpose, sync=False)
-        return x
-
-    def matvec(self, x):
-        return self.apply_(x.clone())
-
-    __matmul__ = matvec
-
-    def sync(self):
-        """wait for what was queued on torch's current stream (the applies are ordered on it)"""
-        torch.cuda.current_stream().synchronize()
 
 
 def ml_apply_batch_(members, x, offsets, transpose=False):
@@ -350,25 +333,14 @@ def ml_apply_batch_(members, x, offsets, transpose=False):
     inside the same call).  ValueError for a wrong tensor, unequal lengths or a vector that does not lie inside ``x``; TypeError for a
     member of another class -- before any native call.  The whole preconditioned BiCGstab solve of many systems in one launch:
     ``bicgstab_batch`` with ``MultilevelOperator`` members."""
-    members, offsets = list(members), [int(o) for o in offsets]
-    if not isinstance(x, torch.Tensor) or x.dim() != 1 or x.dtype != torch.float64 or not x.is_cuda or not x.is_contiguous():
-        raise ValueError("x: expected a contiguous 1-D torch.float64 CUDA tensor")
-    if len(members) != len(offsets):
-        raise ValueError("%d preconditioners but %d offsets" % (len(members), len(offsets)))
-    natives = []
-    for P in members:
+    def native(P):
         pr = _ml_native(P)
         if pr is None:
             raise TypeError("ml_apply_batch_ takes ILUppPreconditioner instances of the ctypes binding, DevicePreconditioners of the "
                             "\"ILUpp\" kind or MultilevelOperators, got %s" % type(P).__name__)
-        natives.append(pr)
-    for pr, o in zip(natives, offsets):
-        if o < 0 or o + pr._n > x.numel():
-            raise ValueError("a vector of %d elements at offset %d does not lie inside x (%d elements)" % (pr._n, o, x.numel()))
-    if not natives:
-        return []
-    _on_current_stream()
-    return _native.ml_apply_batch_device(natives, x.data_ptr(), offsets, transpose=transpose, sync=False)
+        return pr
+
+    return _apply_batch(members, x, offsets, transpose, entry=_native.ml_apply_batch_device, native=native)
 
 
 def bicgstab_batch(As, b, offsets, Ms, x0=None, maxiter=100, rtol=0.0, check_every=0, stats=None):
@@ -518,13 +490,15 @@ def _factor_n(P, pr):
     return int(_native.lib().ilupp_hip_dimension(pr._h))
 
 
-class FactorOperator:
+class FactorOperator(_HostBuiltOperator):
     """An ``ilupp_amd.ILU0Preconditioner`` / ``ILUTPreconditioner`` / ``ILUCPreconditioner`` / ``IChol0Preconditioner`` /
     ``ICholTPreconditioner`` (built on the host by the ctypes binding) as the ``M`` of ``cg`` / ``bicgstab``: the counterpart of
     ``PivotedOperator`` for the non-pivoting classes.  ``apply_`` works in place on a device tensor of shape (n,) or (n, k) through
     ilupp_hip_apply_device / ilupp_hip_apply_block_device, ordered on torch's current stream.  ``cg(A, b[:, None], FactorOperator(P))``
     is the solve every member of ``cg_batch`` has the bits of, ``bicgstab(A, b[:, None], FactorOperator(P))`` the one every such member
     of ``bicgstab_batch`` has the bits of.  TypeError for any other class."""
+
+    _block = True
 
     def __init__(self, P):
         if isinstance(P, (FactorOperator, DevicePreconditioner)):
@@ -534,28 +508,6 @@ class FactorOperator:
         self.P, self.pr, self.kind = P, pr, kind
         self.n = _factor_n(P, pr)
         self.shape = (self.n, self.n)
-
-    def apply_(self, x, transpose=False):
-        """in place on a contiguous fp64 CUDA tensor of shape (n,) or (n, k); asynchronous, ordered on torch's current stream"""
-        if not isinstance(x, torch.Tensor) or x.dim() not in (1, 2) or x.shape[0] != self.n:
-            raise ValueError("x: expected a tensor of shape (%d,) or (%d, k), got %s" % (self.n, self.n, tuple(getattr(x, "shape", ()))))
-        if x.dtype != torch.float64 or not x.is_cuda or not x.is_contiguous():
-            raise ValueError("x: expected a contiguous torch.float64 CUDA tensor")
-        _on_current_stream()
-        if x.dim() == 2:
-            self.pr.apply_block_device(x.data_ptr(), self.n, x.shape[1], transpose=transpose, sync=False)
-        else:
-            self.pr.apply_device(x.data_ptr(), self.n, transpose=transpose, sync=False)
-        return x
-
-    def matvec(self, x):
-        return self.apply_(x.clone())
-
-    __matmul__ = matvec
-
-    def sync(self):
-        """wait for what was queued on torch's current stream (the applies are ordered on it)"""
-        torch.cuda.current_stream().synchronize()
 
 
 def _packed_vector(t, name):
@@ -568,6 +520,32 @@ def _on_device(t, name):
         raise ValueError("%s: expected a contiguous 1-D torch.float64 CUDA tensor" % name)
 
 
+def _apply_batch(members, x, offsets, transpose, *, entry, native, size=lambda P, pr: pr._n, members_first=False):
+    """what the three batched applies do through ``entry``: ``native(P)`` is a member's native object (TypeError for another class),
+    ``size(P, pr)`` its dimension.  The checks run in the caller's order.  members_first: the member classes before the tensor, and whether the tensor
+    lives on the device last of all -- else the tensor first, device and all, and the member classes behind the two lengths."""
+    members, offsets = list(members), [int(o) for o in offsets]
+    if members_first:
+        natives = [native(P) for P in members]
+    _packed_vector(x, "x")
+    if not members_first:
+        _on_device(x, "x")
+    if len(members) != len(offsets):
+        raise ValueError("%d preconditioners but %d offsets" % (len(members), len(offsets)))
+    if not members_first:
+        natives = [native(P) for P in members]
+    for P, pr, o in zip(members, natives, offsets):
+        n = size(P, pr)
+        if o < 0 or o + n > x.numel():
+            raise ValueError("a vector of %d elements at offset %d does not lie inside x (%d elements)" % (n, o, x.numel()))
+    if members_first:
+        _on_device(x, "x")
+    if not natives:
+        return []
+    _on_current_stream()
+    return entry(natives, x.data_ptr(), offsets, transpose=transpose, sync=False)
+
+
 def apply_batch_(members, x, offsets, transpose=False):
     """``pivot_apply_batch_`` for the NON-pivoting classes: the applies of many ILU0 / ILUT / ILUC / IChol0 / ICholT objects in place on
     ONE contiguous fp64 CUDA tensor, member k's vector being ``x[offsets[k] : offsets[k] + n_k]``, with one kernel launch for all members
@@ -576,20 +554,8 @@ def apply_batch_(members, x, offsets, transpose=False):
     member's vector has the bits of its single ``apply_``.  Returns the routes (0 = the launch, 1 = too large, 2 = a factor with an empty
     row: applied alone inside the same call).  ValueError for a wrong tensor, unequal lengths or a vector that does not lie inside ``x``;
     TypeError for the "ILUpp" kind, a pivoting member or any other class -- before any native call."""
-    members, offsets = list(members), [int(o) for o in offsets]
-    natives = [_factor_native(P, "apply_batch_")[0] for P in members]
-    _packed_vector(x, "x")
-    if len(members) != len(offsets):
-        raise ValueError("%d preconditioners but %d offsets" % (len(members), len(offsets)))
-    for P, pr, o in zip(members, natives, offsets):
-        n = _factor_n(P, pr)
-        if o < 0 or o + n > x.numel():
-            raise ValueError("a vector of %d elements at offset %d does not lie inside x (%d elements)" % (n, o, x.numel()))
-    _on_device(x, "x")
-    if not natives:
-        return []
-    _on_current_stream()
-    return _native.apply_batch_device(natives, x.data_ptr(), offsets, transpose=transpose, sync=False)
+    return _apply_batch(members, x, offsets, transpose, entry=_native.apply_batch_device,
+                        native=lambda P: _factor_native(P, "apply_batch_")[0], size=_factor_n, members_first=True)
 
 
 def refactor_batch_(members, As, check=True):

@@ -6,7 +6,8 @@ single constructors built, or, for the pivoting classes, by the member's own sin
 sizes): a member that took the single path inside the call would say nothing about the launch.
 
 Matrices: matgen.random_dd(n, 8, 25.0, seed) with n cycling over 3, 17, 40, 65 (one round of rows, a partial wave, one past a wave; every
-n > 2, which BiCGstab needs); the re-factorisations take every value scaled by 1 + 0.1 u.  Every solve runs 4 iterations with rtol = 0."""
+n > 2, which BiCGstab needs); the re-factorisations take every value scaled by 1 + 0.1 u.  Every solve runs 4 iterations with rtol = 0.
+The multilevel members (sections 4) are tiny objects of their own: see the `multilevel` fixture."""
 import numpy as np
 import pytest
 import scipy.sparse as sp
@@ -238,3 +239,107 @@ def test_host_construction_grows_its_staging_from_5_to_70_matrices(plain):
             assert _same_factors(_factors(M), want[k][0]), (count, k)
             assert M.pr.total_nnz == want[k][1], (count, k)
             assert np.array_equal(_bits(M @ _rhs(ns[k], 200 + k)), _bits(want[k][2])), (count, k)
+
+
+# ---- 4. multilevel members: the member table, the level table and the staging block of the batched multilevel apply grow ----
+@pytest.fixture(scope="module")
+def multilevel():
+    """70 multilevel members built the way tests/test_gpu_ml_apply_batch.py builds its smallest ones -- n = 1 and n = 2, the family without
+    pivoting under its "t0.1" set and default-constructed parameters, CSR and CSC --, every matrix scaled by a factor of its own so that no
+    two members apply alike; their right-hand sides and their single applies in both directions, computed once"""
+    import ilupp_amd as ilupp
+    import ml_cases
+    _, thr, pre, knobs = {p[0]: p for p in ml_cases.PARAMS}["t0.1"]
+    one, two = np.array([[2.0]]), np.array([[2.0, 1.0], [0.5, 3.0]])
+    t01 = ml_cases.engine_params(ilupp, thr, pre, knobs)
+    build = [lambda s: ilupp.ILUppPreconditioner(sp.csr_matrix(one * s), params=t01),
+             lambda s: ilupp.ILUppPreconditioner(sp.csr_matrix(two * s), params=t01),
+             lambda s: ilupp.ILUppPreconditioner(sp.csr_matrix(one * s)),
+             lambda s: ilupp.ILUppPreconditioner(sp.csc_matrix(two * s))]
+    members = [build[k % 4](1.0 + k / 8.0) for k in range(LARGE)]
+    ns = [P.shape[0] for P in members]
+    rhs = [_rhs(n, 300 + k) for k, n in enumerate(ns)]
+    want = dict(apply=[P @ b for P, b in zip(members, rhs)], apply_t=[P.T @ b for P, b in zip(members, rhs)])
+    return dict(members=members, ns=ns, rhs=rhs, want=want)
+
+
+def _ml_packed(ns, rhs):
+    """_packed with the multilevel members' own right-hand sides"""
+    offsets, host = _packed(ns)
+    for o, b in zip(offsets, rhs):
+        host[o:o + b.shape[0]] = b
+    return offsets, host
+
+
+def _check_ml_launch(ml, lo, hi, tag):
+    """ml_apply_batch_ in both directions over the members lo .. hi - 1: every member on route 0 with its single apply's bits, and nothing
+    written between the vectors"""
+    import torch
+    import ilupp_amd.device as ild
+    members, ns, rhs = ml["members"][lo:hi], ml["ns"][lo:hi], ml["rhs"][lo:hi]
+    offsets, host = _ml_packed(ns, rhs)
+    inside = np.zeros(host.shape[0], dtype=bool)
+    for o, n in zip(offsets, ns):
+        inside[o:o + n] = True
+    for key, transpose in (("apply", False), ("apply_t", True)):
+        x = torch.from_numpy(host).cuda()
+        assert ild.ml_apply_batch_(members, x, offsets, transpose=transpose) == [0] * len(members), (tag, key)
+        xh = x.cpu().numpy()
+        assert np.array_equal(xh[~inside], host[~inside]), (tag, key)
+        for k, (o, n) in enumerate(zip(offsets, ns)):
+            assert np.array_equal(_bits(xh[o:o + n]), _bits(ml["want"][key][lo + k])), (tag, key, k)
+
+
+def test_ml_apply_batch_device_grows_its_tables_from_5_to_70_members(multilevel):
+    s = SMALL
+    _check_ml_launch(multilevel, 0, s, "5")
+    _check_ml_launch(multilevel, 0, LARGE, "70")                 # (both tables grow with a cached upload in them)
+    for again in range(2):                                      # (an upload into the grown tables, then a cache hit)
+        _check_ml_launch(multilevel, 0, s, ("5 again", again))
+    _check_ml_launch(multilevel, 0, LARGE, "70 again")           # (a miss without growth)
+    _check_ml_launch(multilevel, 30, 41, "members 30 - 40")      # (other offsets, other places in the level table)
+
+
+def test_ml_apply_batch_host_grows_its_staging_from_5_to_70_vectors(multilevel):
+    """the host entry: the packed staging block it shares with the pivoting classes' host entry"""
+    from ilupp_amd import _native
+    members, rhs, want = multilevel["members"], multilevel["rhs"], multilevel["want"]
+    for tag, lo, hi in (("5", 0, SMALL), ("70", 0, LARGE), ("5 again", 0, SMALL), ("5 of the middle", 30, 35)):
+        for key, transpose in (("apply", False), ("apply_t", True)):
+            x = [b.copy() for b in rhs[lo:hi]]
+            assert _native.ml_apply_batch([P.pr for P in members[lo:hi]], x, transpose) == [0] * (hi - lo), (tag, key)
+            for k in range(hi - lo):
+                assert np.array_equal(_bits(x[k]), _bits(want[key][lo + k])), (tag, key, k)
+
+
+def test_plain_and_multilevel_applies_interleaved_on_one_scratch(plain, multilevel):
+    """a plain apply_batch_, an ml_apply_batch_, the same plain apply_batch_ again: the two descriptor paths of the one scaffold keep their
+    cached tables apart, and all three have the single applies' bits"""
+    import torch
+    import ilupp_amd.device as ild
+    s, ns, d1, want1 = 11, plain["ns"], plain["d1"], plain["want1"]
+    members = ild.DevicePreconditioner.batch("ILU0", d1[:s])
+    offsets, host = _packed(ns[:s])
+
+    def plain_apply(tag):
+        x = torch.from_numpy(host).cuda()
+        assert ild.apply_batch_(members, x, offsets) == [0] * s, tag
+        xh = x.cpu().numpy()
+        for k, (o, n) in enumerate(zip(offsets, ns[:s])):
+            assert np.array_equal(_bits(xh[o:o + n]), _bits(want1["apply"][k])), (tag, k)
+
+    plain_apply("before")
+    _check_ml_launch(multilevel, 0, s, "between")
+    plain_apply("after")
+
+
+# ---- 5. ILUT members: the descriptors, the ticket maps and the records of the batched ILUT construction grow ----
+def test_ilut_construction_grows_its_tables_from_5_to_70_matrices(plain):
+    import ilupp_amd as ilupp
+    mats = plain["mats"]
+    want = [_factors(ilupp.ILUTPreconditioner(A)) for A in mats]
+    for count in (SMALL, LARGE, SMALL):
+        members = ilupp.ILUTPreconditioner.batch(mats[:count])
+        assert [M.pr.path() for M in members] == ["ilut:batch"] * count      # (route 0: a member of route 1 has the single constructor's path)
+        for k, M in enumerate(members):
+            assert _same_factors(_factors(M), want[k]), (count, k)
