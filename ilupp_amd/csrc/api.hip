@@ -1,14 +1,14 @@
 // ilupp_amd/csrc/api.hip -- the C ABI (include/ilupp_hip.h): object lifetime, dispatch of apply() to the sweep kernels, factor egress,
-// the constructions of an ilupp_precond, the multilevel preconditioner and the batched tables.  The pivoting preconditioners (ILUCP /
-// ILUTP) have a file of their own, api_pivot.hip; api_internal.h holds what the two files share (DESIGN_OTHER_PATHS.md section
-// 4h.13).  Mirrors the reference's binding layer (src/binding.cpp) and L2 dispatch (preconditioner_implementation.h:103-111,
+// the constructions of an ilupp_precond, the entries of no handle.  The other handle families have files of their own: api_pivot.hip
+// (ILUCP / ILUTP), api_ml.hip (the multilevel preconditioner), api_batch.hip (batched apply and solves) and api_batch_build.hip (batched
+// re-factorisation and construction); api_internal.h holds what the files share (DESIGN_OTHER_PATHS.md section 4h.13).  Mirrors the reference's binding layer (src/binding.cpp) and L2 dispatch (preconditioner_implementation.h:103-111,
 // :321-334, :381-394).
 #include "api_internal.h"
 
 namespace ilupp {
 std::mutex g_build_mu;
 
-static thread_local std::string g_last_error;
+thread_local std::string g_last_error;
 void set_error(const std::string &msg) { g_last_error = msg; }
 
 void DevMat::release()
@@ -675,6 +675,12 @@ int ilu0_factor(ilupp_precond *p, const DevMat &A, const int32_t *head)
     return rc;
 }
 
+}  // namespace
+
+// (the sweeps of an apply and what makes an object ready for them: what api_ml.hip and the batched files call is declared in
+// api_internal.h, the rest is static)
+namespace ilupp {
+
 // the CSR value arrays of the factors, when the level-major factor kernel left them unwritten
 void ensure_csr_values(ilupp_precond *p)
 {
@@ -722,7 +728,7 @@ void ensure_transposed(ilupp_precond *p)
 // from the factors' own patterns: L forward, U backward, as an ILUT object gets its own (ilut_create_common).  max_row_len stays A's
 // longest row (no row of L or U is longer): it is what the batched re-factorisation routes by.  A batch-built ILUT object
 // (ilupp_hip_ilut_create_batch*) takes the same branch: its max_row_len is the longest row of L or U already, what sweep_tables finds.
-void ensure_sweep_tables(ilupp_precond *p)
+static void ensure_sweep_tables(ilupp_precond *p)
 {
     if (!p->batch_built || p->sweeps_ready) return;
     int32_t longest = 0;
@@ -733,15 +739,8 @@ void ensure_sweep_tables(ilupp_precond *p)
 }
 
 // ---- the sweeps of an apply -----------------------------------------------------------------------------------------------------------
-// One sweep of one object: the stored triangle it walks (slot 0 = Lc, 1 = Uc, 2 = UcT, 3 = LcT: the numbering of pack_tried[] and lvl[])
-// and the manner.  Whatever else a sweep needs follows from the slot: sweep_parts.
-struct SweepOp { int slot; SweepKind kind; };
-struct SweepParts {
-    const DevMat &M; const Schedule &sch; const int32_t *desc; int32_t maxlen;      // the triangle, its schedule, descriptors, longest major slice
-    PackedSweep *pk; bool *pack_tried;                                               // its level-major or static records
-    LevelSweep *lvl;                                                                 // its renumbered copy in level order
-};
-static SweepParts sweep_parts(ilupp_precond *p, SweepOp op)
+// (SweepOp, SweepParts, ApplyPlan: api_internal.h)
+SweepParts sweep_parts(ilupp_precond *p, SweepOp op)
 {
     switch (op.slot) {
     // (an LU object's L has A's strictly-lower pattern, hence A's forward cuts: the factor-sweep schedule serves it)
@@ -752,17 +751,7 @@ static SweepParts sweep_parts(ilupp_precond *p, SweepOp op)
     }
 }
 
-// The two sweeps of an apply, in the order they run: the one place that knows which factor and which loop of the reference
-// (sparse_implementation.h:4040-4087: T1 gather forward, T2 scatter forward, T3 gather backward, T4 scatter backward) every case takes.
-// A scatter loop is a gather sweep over the transposed storage, T4 with the off-diagonal entries last-to-first (BWD_FIRST_DESC).
-struct ApplyPlan {
-    SweepOp first, second;
-    // with the level-major factor path (every in-workgroup dependency one step back) the intermediate vector may travel level-major
-    // between the two sweeps (first's ybuf, second's ysrc); y then only carries the values other workgroups poll
-    bool ylm;
-    bool transposed() const { return first.slot >= 2 || second.slot >= 2; }      // reads UcT or LcT
-};
-static ApplyPlan apply_plan(int kind, bool transpose, bool input_csc, bool llt_diag_last)
+ApplyPlan apply_plan(int kind, bool transpose, bool input_csc, bool llt_diag_last)
 {
     const SweepKind fwd = SWEEP_FWD_LAST_ASC, bwd = SWEEP_BWD_FIRST_ASC, bwd_desc = SWEEP_BWD_FIRST_DESC;
     if (kind == KIND_LU) {
@@ -783,13 +772,13 @@ static ApplyPlan apply_plan(int kind, bool transpose, bool input_csc, bool llt_d
     if (llt_diag_last) return {{0, fwd}, {3, bwd_desc}, false};      // IChol0 (Lc row-major): T1(L) then T4(L)
     return {{3, fwd}, {0, bwd}, false};                               // ICholT (Lc column-major): T2(L) then T3(L)
 }
-static ApplyPlan apply_plan(const ilupp_precond *p, int transpose) { return apply_plan(p->kind, transpose != 0, p->input_csc, p->llt_diag_last); }
+ApplyPlan apply_plan(const ilupp_precond *p, int transpose) { return apply_plan(p->kind, transpose != 0, p->input_csc, p->llt_diag_last); }
 
 // one sweep: the packed kernel when the factor has a verified level-major form, else the CSR kernels.  Either way
 // the right-hand side buffer is all-sentinel afterwards (the CSR kernels reset it row by row).
 // level-major records of a sweep straight from its CSR arrays and descriptors (any object whose rows are short enough:
 // transposed ILU(0) factors, IChol(0)); tried once, on first use
-static const PackedSweep *packed(ilupp_precond *p, SweepOp op)
+const PackedSweep *packed(ilupp_precond *p, SweepOp op)
 {
     const SweepParts s = sweep_parts(p, op);
     if (!s.pk->valid && !*s.pack_tried && s.desc && !p->degenerate) {
@@ -825,8 +814,8 @@ static LevelSweep *level_sweep(ilupp_precond *p, SweepOp op)
 enum SweepRoute { SWEPT_NEVER = 0, SWEPT_STATIC = 1, SWEPT_LEVEL_MAJOR = 2, SWEPT_LEVEL_ORDER = 3, SWEPT_ROWS = 4, SWEPT_ROWS_DEGENERATE = 5,
                   SWEPT_DESCRIPTORS = 6, SWEPT_GENERIC = 7 };
 
-static int sweep(ilupp_precond *p, SweepOp op, const PackedSweep *ps, double *rhs, double *out, int32_t *ticket, int32_t *err,
-                 double *ypk_out = nullptr, const double *ypk_in = nullptr, const int32_t *ysrc = nullptr)
+int sweep(ilupp_precond *p, SweepOp op, const PackedSweep *ps, double *rhs, double *out, int32_t *ticket, int32_t *err,
+                 double *ypk_out, const double *ypk_in, const int32_t *ysrc)
 {
     const SweepParts s = sweep_parts(p, op);
     int8_t &route = p->last_route[op.slot];
@@ -897,8 +886,7 @@ static bool llt_static_pair(ilupp_precond *p, PackedSweep **pf_out, PackedSweep 
 
 // What an apply does before its sweeps, whichever route runs them then: the transposed storages when `plan` reads one, and the two static
 // forms that take the place of the plan's sweeps -- LU's transposed records (ROUTE_STATIC_T) and the LL^T pair (ROUTE_STATIC_PAIR: *pf, *pb).
-enum ApplyRoute { ROUTE_SWEEPS, ROUTE_STATIC_T, ROUTE_STATIC_PAIR };
-static ApplyRoute prepare_apply(ilupp_precond *p, const ApplyPlan &plan, PackedSweep **pf, PackedSweep **pb)
+ApplyRoute prepare_apply(ilupp_precond *p, const ApplyPlan &plan, PackedSweep **pf, PackedSweep **pb)
 {
     ensure_sweep_tables(p);                          // (a batch-built ILU(0) object's first single sweep)
     if (!plan.transposed()) return ROUTE_SWEEPS;
@@ -911,10 +899,6 @@ static ApplyRoute prepare_apply(ilupp_precond *p, const ApplyPlan &plan, PackedS
     if (p->kind == KIND_LLT && llt_static_pair(p, pf, pb)) return ROUTE_STATIC_PAIR;
     return ROUTE_SWEEPS;
 }
-
-}  // namespace
-
-namespace ilupp {
 
 // apply on a device vector; `transpose` as in apply_preconditioner_only(use, y)
 int apply_dev(ilupp_precond *p, double *x, int transpose)
@@ -1115,7 +1099,13 @@ int apply_block_dev(ilupp_precond *p, double *X, int64_t k, int transpose)
     return ILUPP_OK;
 }
 
-int ilu0_create_common(const DevMat &A, int is_csr, const int32_t *head, ilupp_precond **out, ilupp_precond *made = nullptr)
+}  // namespace
+
+// (the single ILU(0) / IChol(0) constructions and re-factorisations: api_batch_build.hip runs them for the members that stay out of its
+// launches)
+namespace ilupp {
+
+int ilu0_create_common(const DevMat &A, int is_csr, const int32_t *head, ilupp_precond **out, ilupp_precond *made)
 {
     ObjGuard g(made ? made : new_obj(A.n));
     ilupp_precond *p = g.p;
@@ -1147,10 +1137,6 @@ bool is_ilu0_object(const ilupp_precond *p)
 {
     return p && p->kind == KIND_LU && p->nnz_mode == NNZ_GENERIC_LU && (p->sA.nb > 0 || p->batch_built);
 }
-
-// the launch of the batched re-factorisation with this one member (defined with that launch's host code, below): the single
-// re-factorisation of a batch-built object, which has none of the single numeric paths' tables
-int refactor_in_launch(ilupp_precond *p, const double *d_data, const int32_t *d_indices, const int32_t *d_indptr);
 
 // behind a re-factorisation: every copy of the OLD values goes (the static forms' transposed records, the level-ordered sweeps, the
 // transposed storages with their schedules, descriptors and packed sweeps); each is built again on its first use.  The caller has
@@ -1246,7 +1232,7 @@ int ilu0_refactor_single(ilupp_precond *p, const double *d_data, const int32_t *
     return rc;
 }
 
-}  // namespace
+}  // namespace ilupp
 
 extern "C" {
 
@@ -1337,8 +1323,6 @@ void utu_analyse(ilupp_precond *p)
     p->compact = sweep_tables(p->stream, p, {&p->Lc, false, &p->sL, &p->dL}, {&p->Uc, false, &p->sU, &p->dU}, true, &p->max_row_len);
 }
 
-}  // namespace ilupp
-
 static int iluc_create_common(DevMat &A, int32_t n, int is_csr, int32_t max_fill_in, double threshold, ilupp_precond **out)
 {
     // (guards: an ILUPP_HIP that throws below must leave neither the object nor the factors behind)
@@ -1372,8 +1356,8 @@ static int iluc_create_common(DevMat &A, int32_t n, int is_csr, int32_t max_fill
     return ILUPP_OK;
 }
 
-static int ilut_create_common(DevMat &A, int32_t n, int is_csr, int32_t max_fill_in, double threshold, ilupp_precond **out,
-                              ilupp_precond *made = nullptr)
+int ilut_create_common(DevMat &A, int32_t n, int is_csr, int32_t max_fill_in, double threshold, ilupp_precond **out,
+                              ilupp_precond *made)
 {
     ObjGuard g(made ? made : new_obj(n));
     ilupp_precond *p = g.p;
@@ -1399,6 +1383,8 @@ static int ilut_create_common(DevMat &A, int32_t n, int is_csr, int32_t max_fill
     *out = g.release();
     return ILUPP_OK;
 }
+
+}  // namespace ilupp
 
 extern "C" {
 
@@ -1434,7 +1420,9 @@ int ilupp_hip_iluc_create_device(const double *d_data, const int32_t *d_indices,
 
 }  // extern "C"
 
-static int ichol0_create_common(DevMat &A, int32_t n, ilupp_precond **out, ilupp_precond *made = nullptr)
+namespace ilupp {
+
+int ichol0_create_common(DevMat &A, int32_t n, ilupp_precond **out, ilupp_precond *made)
 {
     ObjGuard g(made ? made : new_obj(n));
     ilupp_precond *p = g.p;
@@ -1468,6 +1456,8 @@ static int ichol0_create_common(DevMat &A, int32_t n, ilupp_precond **out, ilupp
     *out = g.release();
     return ILUPP_OK;
 }
+
+}  // namespace ilupp
 
 extern "C" {
 
@@ -1991,2028 +1981,6 @@ int ilupp_hip_sync(ilupp_precond *p)
     API_TRY
     if (!p) return ILUPP_ERR_INVALID;
     return finish_apply(p);
-    API_CATCH
-}
-
-}  // extern "C"
-
-// ================================================================================================================================
-// the multilevel ILU++ preconditioner without pivoting (include/ilupp_hip.h: ilupp_hip_ml_*).  Levels from ml.hip /
-// piluc_df.hip; every level's two factors are an object of the ILUC kind (left by columns, right by rows, both unit), whose sweep
-// kernels the apply borrows one half at a time: preconditioner_implementation.h:441-453 (left: all levels upwards) and :468-486
-// (right: all levels downwards), each on the LAST n_level entries of the vector (sparse_implementation.h:4096-4165).
-// ================================================================================================================================
-// the live multilevel objects: a batched entry that is handed one in place of an ilupp_precond says so instead of reading it as one
-static std::mutex g_ml_live_mu;
-static std::set<const void *> g_ml_live;
-static bool is_live_ml(const void *h) { std::lock_guard<std::mutex> lk(g_ml_live_mu); return g_ml_live.count(h) != 0; }
-
-struct ilupp_ml {
-    ilupp_ml() { std::lock_guard<std::mutex> lk(g_ml_live_mu); g_ml_live.insert(this); }
-    ~ilupp_ml() { std::lock_guard<std::mutex> lk(g_ml_live_mu); g_ml_live.erase(this); }
-    int32_t n = 0;
-    std::vector<MlLevelDev> dev;              // per level: scalings, permutations, the middle diagonal (the factors move into `obj`)
-    std::vector<ilupp_precond *> obj;         // per level: the sweeps of its two factors
-    double *buf = nullptr;                    // n: what a sweep reads
-    double *xdev = nullptr;                   // n: staging of host vectors
-    float construct_ms = 0.f, kernel_ms = 0.f, last_apply_ms = 0.f;
-};
-
-namespace {
-
-void ml_destroy(ilupp_ml *m)
-{
-    if (!m) return;
-    // (the first level owns the stream the others borrow: it goes last)
-    for (size_t k = m->obj.size(); k-- > 0;) if (m->obj[k]) destroy_obj(m->obj[k]);
-    for (auto &l : m->dev) l.release();
-    if (m->buf) (void)pool_free(m->buf);
-    if (m->xdev) (void)pool_free(m->xdev);
-    delete m;
-}
-
-static bool getenv_small_off() { static const bool off = getenv("ILUPP_NO_SMALL_SWEEPS") != nullptr; return off; }
-
-// one half of the ILUC-kind apply (apply_plan, KIND_UTU): forward = the T2 loop (left factor, or right^T), backward = the T3 loop
-int utu_half(ilupp_precond *p, bool forward, bool tr, double *rhs, double *out, int32_t *ticket)
-{
-    ensure_transposed(p);
-    int32_t *err = p->ctrl;
-    const ApplyPlan plan = apply_plan(KIND_UTU, tr, false, false);
-    const SweepOp op = forward ? plan.first : plan.second;
-    // small levels (the later, denser ones): one workgroup with the unknowns in LDS instead of a chain of hops through memory
-    // (not for a factor with an empty row: p->degenerate objects keep the row-by-row kernel, which reports what it meets)
-    // (up to 1 024 rows always; up to kSmallSweepMax = 4 096 when the rows are long -- more than 32 entries on average: there the general
-    //  kernels' hop through memory per link of the dependency chain costs most.  Measured, apply of a whole object: 26 levels from n = 2 000,
-    //  177 entries per row: 65 against 176 ms; 3 375 rows with 6 entries per row: 0.82 against 0.68 ms -- hence the second condition)
-    const DevMat &M = sweep_parts(p, op).M;
-    if ((p->n <= 1024 || (p->n <= kSmallSweepMax && M.nnz > 32 * (int64_t)p->n)) && !p->degenerate && !getenv_small_off())
-        return sptrsv_small(p->stream, op.kind, M, rhs, out, err);
-    return sweep(p, op, packed(p, op), rhs, out, ticket, err);
-}
-
-int ml_apply_dev(ilupp_ml *m, double *x, int transpose, int part = 0)       // part: 0 = both passes, 1 = the first only, 2 = the second only
-{
-    ilupp_precond *p0 = m->obj[0];
-    hipStream_t st = p0->stream;
-    const int nl = (int)m->obj.size();
-    // (a batched launch that was not waited for still reads the levels and writes m->buf: ilupp_hip_ml_apply_batch_device)
-    if (p0->batch_ev) {
-        ILUPP_HIP(hipStreamWaitEvent(st, p0->batch_ev, 0));
-        for (int i = 0; i < nl; ++i) m->obj[(size_t)i]->batch_ev = nullptr;
-    }
-    order_after_caller(st, p0->sev[0]);
-    for (int i = 0; i < nl; ++i) ILUPP_HIP(hipMemsetAsync(m->obj[(size_t)i]->ctrl, 0, 64, st));
-    ILUPP_HIP(hipEventRecord(p0->ev[0], st));
-    const bool tr = transpose != 0;
-    // first pass upwards through the levels, second pass downwards (:103-111 with :441-453, :468-486)
-    for (int pass = 0; pass < 2; ++pass) {
-        if (part != 0 && part != pass + 1) continue;
-        for (int s = 0; s < nl; ++s) {
-            const int i = pass == 0 ? s : nl - 1 - s;
-            ilupp_precond *p = m->obj[(size_t)i];
-            const MlLevelDev &l = m->dev[(size_t)i];
-            double *xt = x + (m->n - l.n);
-            int rc = ILUPP_OK;
-            if (!tr && pass == 0) {            // left, ID: x /= D_l; permute_first(perm_rows); T2(L)
-                ml_scale_perm(st, l.n, xt, l.Dl, l.pr, m->buf);
-                rc = utu_half(p, true, false, m->buf, p->work, p->ctrl + 4);
-                if (!rc) ml_take(st, l.n, p->work, nullptr, xt);
-            } else if (!tr) {                  // right, ID: x *= D; T3(U); permute_last(inverse_perm_columns); x /= D_r
-                ml_scale(st, l.n, xt, l.D, m->buf);
-                rc = utu_half(p, false, false, m->buf, p->work, p->ctrl + 5);
-                if (!rc) {
-                    ml_perm_scale(st, l.n, p->work, l.ipc, l.Dr, xt);
-                    fill_u64(st, reinterpret_cast<unsigned long long *>(p->work), l.n, kSentinel);
-                }
-            } else if (pass == 0) {            // right, TRANSPOSE: x /= D_r; permute_first(perm_columns); T2(U^T); x *= D
-                ml_scale_perm(st, l.n, xt, l.Dr, l.pc, m->buf);
-                rc = utu_half(p, true, true, m->buf, p->work, p->ctrl + 4);
-                if (!rc) ml_take(st, l.n, p->work, l.D, xt);
-            } else {                           // left, TRANSPOSE: T3(L^T); permute_last(inverse_perm_rows); x /= D_l
-                ILUPP_HIP(hipMemcpyAsync(m->buf, xt, sizeof(double) * (size_t)l.n, hipMemcpyDeviceToDevice, st));
-                rc = utu_half(p, false, true, m->buf, p->work, p->ctrl + 5);
-                if (!rc) {
-                    ml_perm_scale(st, l.n, p->work, l.ipr, l.Dl, xt);
-                    fill_u64(st, reinterpret_cast<unsigned long long *>(p->work), l.n, kSentinel);
-                }
-            }
-            if (rc) return rc;
-        }
-    }
-    ILUPP_HIP(hipEventRecord(p0->ev[2], st));
-    return ILUPP_OK;
-}
-
-int ml_finish_apply(ilupp_ml *m)
-{
-    ilupp_precond *p0 = m->obj[0];
-    const int nl = (int)m->obj.size();
-    std::vector<int32_t> err((size_t)nl, 0);
-    for (int i = 0; i < nl; ++i) ILUPP_HIP(hipMemcpyAsync(&err[(size_t)i], m->obj[(size_t)i]->ctrl, sizeof(int32_t), hipMemcpyDeviceToHost, p0->stream));
-    ILUPP_HIP(stream_sync(p0->stream));
-    ILUPP_HIP(hipEventElapsedTime(&m->last_apply_ms, p0->ev[0], p0->ev[2]));
-    for (int i = 0; i < nl; ++i)
-        if (err[(size_t)i]) {
-            for (int j = 0; j < nl; ++j) fill_u64(p0->stream, reinterpret_cast<unsigned long long *>(m->obj[(size_t)j]->work), m->obj[(size_t)j]->n, kSentinel);
-            ILUPP_HIP(stream_sync(p0->stream));
-            set_error("triangular solve: dependency wait timed out (factor not triangular?)");
-            return ILUPP_ERR_TIMEOUT;
-        }
-    return ILUPP_OK;
-}
-
-int ml_create_common(const DevMat &A, const ilupp_ml_params *ip, ilupp_ml **out)
-{
-    MlParams P;
-    P.threshold = ip->threshold;
-    P.n_pre = ip->n_preprocessing;
-    if (P.n_pre < 0 || P.n_pre > 8) { set_error("ILU++: at most 8 preprocessing steps"); return ILUPP_ERR_INVALID; }
-    for (int i = 0; i < P.n_pre; ++i) P.pre[i] = ip->preprocessing[i];
-    P.pq_threshold = ip->pq_threshold; P.max_levels = ip->max_levels; P.min_ml_size = ip->min_ml_size;
-    P.pil.small_pivot_terminates = ip->small_pivot_terminates != 0; P.pil.min_pivot = ip->min_pivot; P.pil.min_elim_factor = ip->min_elim_factor;
-    P.pil.threshold_shift_schur = ip->threshold_shift_schur; P.vary_threshold_factor = ip->vary_threshold_factor;
-    P.use_final_threshold = ip->use_final_threshold != 0; P.final_threshold = ip->final_threshold;
-    P.pil.max_fill_in = ip->max_fill_in > 0 ? ip->max_fill_in : 0;
-    P.pil.rules = ip->drop_rules; P.pil.combine = ip->combine_factor; P.pil.scale_invdiag = ip->scale_weight_invdiag != 0;
-    P.pil.wgt[0] = ip->weight_standard_drop; P.pil.wgt[1] = ip->weight_standard_drop2; P.pil.wgt[2] = ip->weight_err_prop_drop;
-    P.pil.wgt[3] = ip->weight_err_prop_drop2; P.pil.wgt[4] = ip->weight_pivot_drop; P.pil.wgt[5] = ip->weight_inverse_drop;
-    P.pil.wgt[6] = ip->weight_weighted_drop; P.pil.init_weights_lu = ip->init_weights_lu;
-    P.pil.neutral = ip->neutral_element; P.pil.min_weight = ip->min_weight;
-    P.pil.piv_tol = ip->piv_tol; P.pil.permute_rows = ip->permute_rows; P.pil.total_piv = ip->total_piv; P.pil.begin_total_piv = ip->begin_total_piv != 0;
-    P.pil.final_row_crit = ip->final_row_crit; P.pil.move_level_factor = ip->move_level_factor; P.pil.row_u_max = ip->row_u_max;
-    if (P.pil.permute_rows < 0 || P.pil.permute_rows > 3 || P.pil.total_piv < 0 || P.pil.total_piv > 2) { set_error("ILU++: PERMUTE_ROWS / TOTAL_PIV out of range"); return ILUPP_ERR_INVALID; }
-    if (P.pil.pivoting() && (P.pil.final_row_crit < -1 || P.pil.final_row_crit > 9)) {
-        set_error("ILU++: FINAL_ROW_CRIT " + std::to_string(P.pil.final_row_crit) + " (rows ordered by weights instead of counts) is not built");
-        return ILUPP_ERR_UNSUPPORTED;
-    }
-    if ((P.pil.rules & ~255) != 0) { set_error("ILU++: unknown dropping rule"); return ILUPP_ERR_INVALID; }
-    // (inverse-based and weighted dropping -- recurrences over all steps -- run as chains in both factorisations: pilucdp.hip)
-    struct MlGuard { ilupp_ml *m; ~MlGuard() { if (m) ml_destroy(m); } } g{new ilupp_ml()};
-    ilupp_ml *m = g.m;
-    m->n = A.n;
-    // the first level's object owns the stream everything runs on
-    ilupp_precond *p0 = new_obj(A.n);
-    m->obj.push_back(p0);
-    hipStream_t st = p0->stream;
-    ILUPP_HIP(hipEventRecord(p0->ev[0], st));
-    int rc = ml_build(st, A, P, &m->dev, &m->kernel_ms);
-    if (rc) return rc;
-    ILUPP_HIP(pool_malloc(&m->buf, sizeof(double) * (size_t)A.n));
-    for (size_t k = 0; k < m->dev.size(); ++k) {
-        MlLevelDev &l = m->dev[k];
-        ilupp_precond *p = p0;
-        if (k > 0) {
-            p = new_obj(l.n);
-            m->obj.push_back(p);
-            queue_give(*p);                                    // its own queue back to the pool: the level works on the first level's
-            static_cast<QueuePack &>(*p) = *p0;
-            p->side = nullptr; p->jev[0] = p->jev[1] = nullptr;
-            p->borrowed_queue = true;
-        }
-        p->kind = KIND_UTU; p->nnz_mode = NNZ_GENERIC_LU; p->input_csc = false;
-        p->Lc = l.L; p->Uc = l.U;
-        l.L = DevMat(); l.U = DevMat();                        // (the object owns the arrays now)
-        utu_analyse(p);
-    }
-    ILUPP_HIP(hipEventRecord(p0->ev[1], st));
-    ILUPP_HIP(stream_sync(st));
-    ILUPP_HIP(hipEventElapsedTime(&m->construct_ms, p0->ev[0], p0->ev[1]));
-    *out = m;
-    g.m = nullptr;
-    return ILUPP_OK;
-}
-
-}  // namespace
-
-namespace ilupp {
-
-// a batched construction that gets no stream to run on
-static int no_batch_stream() { set_error("batched construction: no stream"); return ILUPP_ERR_HIP; }
-
-// how a batched construction went, for every kind of batch: the members' codes into the caller's array, if it gave one, and the first
-// failure returned and named by its number
-static int batch_first_failure(int32_t count, const std::vector<int> &rcs, const std::vector<std::string> &msgs, int32_t *status)
-{
-    int first = ILUPP_OK;
-    for (int32_t i = 0; i < count; ++i) {
-        if (status) status[i] = rcs[(size_t)i];
-        if (rcs[(size_t)i] && !first) { first = rcs[(size_t)i]; set_error("matrix " + std::to_string(i) + " of the batch: " + msgs[(size_t)i]); }
-    }
-    return first;
-}
-
-// The workers of a batched construction (ilupp_hip_ml_create_batch, ilupp_hip_ilucp_create_batch, ilupp_hip_ilutp_create_batch): `build(i)`
-// constructs member i on the calling worker's thread and returns its code; `worst_bytes` is the device memory the largest member holds
-// while it is built.  At most 64 workers (ILUPP_BATCH_WORKERS, read per call) and as many as the memory takes: 0.6 of the free bytes, the
-// pool's kept blocks counted as free.  Every worker is a member of one ChainBatch, so the sequential chains of the members it builds are
-// launched together with the other workers' (pilucdp.hip).  Members are independent: status[i] per member (may be null), the first
-// failure is returned and reported as "matrix i of the batch: ...".  The caller holds the build lock.
-int batch_build(int32_t count, double worst_bytes, int32_t *status, const std::function<int(int32_t)> &build)
-{
-    int workers = 64;
-    if (const char *e = getenv("ILUPP_BATCH_WORKERS")) { const int v = atoi(e); if (v > 0) workers = v; }
-    if (workers > count) workers = count;
-    int device = 0;
-    ILUPP_HIP(hipGetDevice(&device));
-    {
-        size_t free_b = 0, total_b = 0;
-        ILUPP_HIP(hipMemGetInfo(&free_b, &total_b));
-        free_b += pool_cached_bytes();
-        if (worst_bytes > 0.0) { const double fit = 0.6 * (double)free_b / worst_bytes; if (fit < (double)workers) workers = fit < 1.0 ? 1 : (int)fit; }
-    }
-    ChainBatch *cb = chain_batch_create(workers);
-    if (!cb) return no_batch_stream();
-    // (the batch and its stream go when this call unwinds, whatever throws below)
-    struct BatchGuard { ChainBatch *b; ~BatchGuard() { if (b) chain_batch_destroy(b); } } cbg{cb};
-    std::vector<int> rcs((size_t)count, ILUPP_OK);
-    std::vector<std::string> msgs((size_t)count);
-    std::atomic<int32_t> next(0);
-    auto work = [&](int w) {
-        (void)hipSetDevice(device);
-        pool_set_owner(w + 1);
-        chain_batch_enter(cb);
-        for (;;) {
-            const int32_t i = next.fetch_add(1);
-            if (i >= count) break;
-            int rc;
-            try { rc = build(i); }
-            catch (const ilupp::HipError &e) { ilupp::d2h_cancel_all(); rc = ilupp::report(e); }
-            catch (const std::bad_alloc &) { ilupp::set_error("out of host memory"); rc = ILUPP_ERR_MEMORY; }
-            catch (...) { ilupp::set_error("unexpected exception in a batch worker"); rc = ILUPP_ERR_HIP; }     // (a worker must reach chain_batch_leave)
-            rcs[(size_t)i] = rc;
-            if (rc) msgs[(size_t)i] = ilupp::g_last_error;
-        }
-        chain_batch_leave(cb);
-        (void)hipDeviceSynchronize();                          // (everything this worker queued is done: its kept blocks are everybody's)
-        pool_disown(w + 1);
-        pool_set_owner(0);
-    };
-    // Kept blocks of owner 0 may have been given back by calls on other objects' streams (apply temporaries, destroy) without a wait for
-    // those streams: nothing of that may still be queued when up to 64 fresh streams start to take such blocks (pool.h).
-    ILUPP_HIP(hipDeviceSynchronize());
-    {
-        // (threads that were started are joined whatever happens -- a joinable std::thread that is destroyed ends the process --, and
-        // workers that could not be started are taken out of the batch's count, or the others would wait for their launches for good)
-        struct Joiner { std::vector<std::thread> v; ~Joiner() { for (std::thread &t : v) if (t.joinable()) t.join(); } } pool_threads;
-        int started = 1;
-        try {
-            for (int w = 1; w < workers; ++w) { pool_threads.v.emplace_back(work, w); ++started; }
-        } catch (...) {
-            for (int w = started; w < workers; ++w) { chain_batch_enter(cb); chain_batch_leave(cb); }
-        }
-        work(0);
-    }
-    chain_batch_destroy(cbg.b); cbg.b = nullptr;
-    return batch_first_failure(count, rcs, msgs, status);
-}
-
-}  // namespace ilupp
-
-extern "C" {
-
-void ilupp_hip_ml_default_params(ilupp_ml_params *p)
-{
-    if (!p) return;
-    memset(p, 0, sizeof(*p));
-    p->threshold = 0.0;
-    p->n_preprocessing = 3;
-    p->preprocessing[0] = ILUPP_PRE_NORMALIZE_COLUMNS; p->preprocessing[1] = ILUPP_PRE_NORMALIZE_ROWS; p->preprocessing[2] = ILUPP_PRE_PQ_ORDERING;
-    p->pq_threshold = 0.0; p->max_levels = 100; p->min_ml_size = 0;
-    p->small_pivot_terminates = 1; p->min_pivot = 1e-2; p->min_elim_factor = 0.0; p->threshold_shift_schur = 0.0;
-    p->vary_threshold_factor = 1.0; p->use_final_threshold = 0; p->final_threshold = 0.0;
-    p->max_fill_in = 0;
-    p->drop_rules = ILUPP_DROP_ERR_PROP;
-    p->weight_standard_drop = p->weight_standard_drop2 = p->weight_err_prop_drop = p->weight_err_prop_drop2 = p->weight_pivot_drop = 1.0;
-    p->weight_inverse_drop = 1.0; p->weight_weighted_drop = 1.0; p->init_weights_lu = 1.0;
-    p->combine_factor = 0; p->neutral_element = 0.0; p->min_weight = 1.0; p->scale_weight_invdiag = 0;
-    p->piv_tol = 0.0; p->permute_rows = 0; p->total_piv = 0; p->begin_total_piv = 1;        // (init case 10, :927-934)
-    p->final_row_crit = -1; p->move_level_factor = 2.0; p->row_u_max = 1.5;
-}
-
-int ilupp_hip_ml_create(const double *data, const int32_t *indices, const int32_t *indptr, int32_t n, int is_csr, const ilupp_ml_params *params,
-                        ilupp_ml **out)
-{
-    return create_from_host(data, indices, indptr, n, is_csr != 0, out, [&](DevMat &A) { return ml_create_common(A, params, out); },
-                            params != nullptr, "null argument");
-}
-
-int ilupp_hip_ml_create_batch(int32_t count, const double *const *data, const int32_t *const *indices, const int32_t *const *indptr, const int32_t *n,
-                              int is_csr, const ilupp_ml_params *params, ilupp_ml **out, int32_t *status)
-{
-    API_TRY_BUILD
-    if (count < 0 || !data || !indices || !indptr || !n || !params || !out) { set_error("null argument"); return ILUPP_ERR_INVALID; }
-    for (int32_t i = 0; i < count; ++i) { out[i] = nullptr; if (status) status[i] = ILUPP_OK; }
-    if (count == 0) return ILUPP_OK;
-    // a construction with pivoting holds ~116 bytes per entry + 450 per row (two stores with their link arrays, the Schur store, both
-    // orientations of the level's matrix, the tables)
-    double worst = 0.0;
-    for (int32_t i = 0; i < count; ++i)
-        if (indptr[i] && n[i] > 0) { const double e = 116.0 * (double)indptr[i][n[i]] + 450.0 * (double)n[i] + (double)(64 << 20); if (e > worst) worst = e; }
-    return batch_build(count, worst, status, [&](int32_t i) {
-        MatGuard A;
-        const int rc = upload(data[i], indices[i], indptr[i], n[i], is_csr != 0, &A.m);
-        return rc ? rc : ml_create_common(A.m, params, &out[i]);
-    });
-    API_CATCH
-}
-
-int ilupp_hip_ml_create_device(const double *d_data, const int32_t *d_indices, const int32_t *d_indptr, int32_t n, int is_csr,
-                               const ilupp_ml_params *params, ilupp_ml **out)
-{
-    return create_from_device(d_data, d_indices, d_indptr, n, is_csr != 0, out, [&](DevMat &A) { return ml_create_common(A, params, out); },
-                              params != nullptr, "null argument");
-}
-
-void ilupp_hip_ml_destroy(ilupp_ml *p)
-{
-    try { ml_destroy(p); } catch (...) {}
-}
-
-int ilupp_hip_ml_apply_device(ilupp_ml *m, double *d_x, int64_t len, int transpose, int sync)
-{
-    API_TRY
-    OR_RETURN(vector_args(m, len, m ? m->n : 0));
-    OR_RETURN(ml_apply_dev(m, d_x, transpose));
-    return finish_or_hand_over(sync, *m->obj[0], [&] { return ml_finish_apply(m); });
-    API_CATCH
-}
-
-int ilupp_hip_ml_apply_part_device(ilupp_ml *m, double *d_x, int64_t len, int transpose, int left, int sync)
-{
-    API_TRY
-    OR_RETURN(vector_args(m, len, m ? m->n : 0));
-    // ID: the left part is the first pass (upwards through the levels), the right part the second; TRANSPOSE: right^T first, then left^T
-    const int part = (left != 0) == (transpose == 0) ? 1 : 2;
-    OR_RETURN(ml_apply_dev(m, d_x, transpose, part));
-    return finish_or_hand_over(sync, *m->obj[0], [&] { return ml_finish_apply(m); });
-    API_CATCH
-}
-
-int ilupp_hip_ml_apply(ilupp_ml *m, double *x, int64_t len, int transpose)
-{
-    API_TRY
-    OR_RETURN(vector_args(m, len, m ? m->n : 0));
-    return apply_staged(m->obj[0]->stream, &m->xdev, m->n, x,
-                        [&](double *d) { return ml_apply_dev(m, d, transpose); },
-                        [&] { return ml_finish_apply(m); });
-    API_CATCH
-}
-
-namespace {
-// the matrix of a solve in HBM and its preconditioner (the caller holds the construction lock)
-int solve_build(const double *data, const int32_t *indices, const int32_t *indptr, int32_t n, int is_csr, const ilupp_ml_params *params, DevMat *A,
-                ilupp_ml **m)
-{
-    API_TRY
-    const int rc = upload(data, indices, indptr, n, is_csr != 0, A);
-    if (rc) return rc;
-    return ml_create_common(*A, params, m);
-    API_CATCH
-}
-}  // namespace
-
-int ilupp_hip_solve(const double *data, const int32_t *indices, const int32_t *indptr, int32_t n, int is_csr, const double *rhs, int64_t rhs_len,
-                    double rtol, double atol, int32_t max_iter, const ilupp_ml_params *params, double *x, int32_t *iterations, double *rel_reached,
-                    double *abs_reached)
-{
-    if (!data || !indices || !indptr || !rhs || !params || !x) { set_error("null argument"); return ILUPP_ERR_INVALID; }
-    if (n <= 0) { set_error("matrix has size 0!"); return ILUPP_ERR_INVALID; }
-    if (rhs_len != n) { set_error("right-hand side has wrong size!"); return ILUPP_ERR_WRONG_SIZE; }            // binding.cpp:209-210
-    // (the whole call under the construction lock: the iteration takes and returns pool blocks on its own stream, and the pool knows nothing
-    //  of streams -- see API_TRY_BUILD)
-    std::lock_guard<std::mutex> build_lock_(ilupp::g_build_mu);
-    struct Guard {
-        DevMat A, T; ilupp_ml *m = nullptr;
-        ~Guard() { try { if (m) { (void)hipStreamSynchronize(m->obj[0]->stream); ml_destroy(m); } } catch (...) {} A.release(); T.release(); }
-    } g;
-    { const int rc = solve_build(data, indices, indptr, n, is_csr, params, &g.A, &g.m); if (rc) return rc; }
-    API_TRY
-    ilupp_ml *m = g.m;
-    hipStream_t st = m->obj[0]->stream;
-    const DevMat *R = &g.A;                                    // the rows of A, for the products
-    if (!g.A.is_csr) { transpose_storage(st, g.A, &g.T); R = &g.T; }
-    PoolBlock b_r, b_y, b_t;
-    for (PoolBlock *b : {&b_r, &b_y, &b_t}) ILUPP_HIP(b->alloc(sizeof(double) * (size_t)n));
-    struct SyncOnExit { hipStream_t st; ~SyncOnExit() { (void)hipStreamSynchronize(st); } } quiesce{st};      // (before the blocks go back)
-    double *r = b_r.as<double>(), *y = b_y.as<double>(), *tmp = b_t.as<double>();
-    ILUPP_HIP(hipMemcpyAsync(r, rhs, sizeof(double) * (size_t)n, hipMemcpyHostToDevice, st));
-    { const int rc = ml_apply_dev(m, r, 0, 1); if (rc) return rc; }                                              // r = L' b (preconditioned_rhs)
-    auto op = [&](const double *in, double *out) -> int {       // out = L'(A(R' in))
-        ILUPP_HIP(hipMemcpyAsync(tmp, in, sizeof(double) * (size_t)n, hipMemcpyDeviceToDevice, st));
-        int rc = ml_apply_dev(m, tmp, 0, 2);
-        if (rc) return rc;
-        rc = ilupp_hip_spmv_device(R->val, R->idx, R->ptr, n, R->nnz, tmp, out, st);
-        if (rc) return rc;
-        return ml_apply_dev(m, out, 0, 1);
-    };
-    int32_t it = 0; double rel = 0.0, res = 0.0;
-    { const int rc = bicgstab_split(st, n, op, r, y, 1, max_iter, rtol, atol, &it, &rel, &res); if (rc) return rc; }
-    { const int rc = ml_apply_dev(m, y, 0, 2); if (rc) return rc; }                                              // x = R' y (adapt_solution)
-    { const int rc = ml_finish_apply(m); if (rc) return rc; }
-    ILUPP_HIP(hipMemcpy(x, y, sizeof(double) * (size_t)n, hipMemcpyDeviceToHost));
-    if (iterations) *iterations = it;
-    if (rel_reached) *rel_reached = rel;
-    if (abs_reached) *abs_reached = res;
-    if (!(rel < rtol && res < atol)) { set_error("did not converge"); return ILUPP_ERR_NOT_CONVERGED; }         // iterative_solvers_implementation.h:497
-    return ILUPP_OK;
-    API_CATCH
-}
-
-int ilupp_hip_ml_sync(ilupp_ml *m)
-{
-    API_TRY
-    if (!m) return ILUPP_ERR_INVALID;
-    return ml_finish_apply(m);
-    API_CATCH
-}
-
-int32_t ilupp_hip_ml_levels(const ilupp_ml *m) { return m ? (int32_t)m->obj.size() : 0; }
-
-int64_t ilupp_hip_ml_total_nnz(const ilupp_ml *m)          // preconditioner.h:312 with preconditioner_implementation.h:551-569
-{
-    if (!m) return 0;
-    int64_t sum = 0;
-    for (const ilupp_precond *p : m->obj) sum += (p->Lc.nnz - p->n) + (p->Uc.nnz - p->n) + p->n;
-    return sum;
-}
-
-int ilupp_hip_ml_level_info(const ilupp_ml *m, int32_t level, int32_t *n, int64_t *nnz_left, int64_t *nnz_right)
-{
-    if (!m || level < 0 || level >= (int32_t)m->obj.size()) { set_error("no such level"); return ILUPP_ERR_INVALID; }
-    const ilupp_precond *p = m->obj[(size_t)level];
-    if (n) *n = p->n;
-    if (nnz_left) *nnz_left = p->Lc.nnz;
-    if (nnz_right) *nnz_right = p->Uc.nnz;
-    return ILUPP_OK;
-}
-
-int ilupp_hip_ml_level_copy(const ilupp_ml *m, int32_t level, double *l_data, int32_t *l_indices, int32_t *l_indptr, double *u_data, int32_t *u_indices,
-                            int32_t *u_indptr, double *middle, int32_t *perm_rows, int32_t *perm_cols, int32_t *inv_perm_rows, int32_t *inv_perm_cols,
-                            double *d_left, double *d_right)
-{
-    API_TRY
-    if (!m || level < 0 || level >= (int32_t)m->obj.size()) { set_error("no such level"); return ILUPP_ERR_INVALID; }
-    const ilupp_precond *p = m->obj[(size_t)level];
-    const MlLevelDev &l = m->dev[(size_t)level];
-    ILUPP_HIP(stream_sync(p->stream));
-    const size_t n = (size_t)p->n;
-    get_host(l_data, p->Lc.val, sizeof(double) * (size_t)p->Lc.nnz); get_host(l_indices, p->Lc.idx, sizeof(int32_t) * (size_t)p->Lc.nnz); get_host(l_indptr, p->Lc.ptr, sizeof(int32_t) * (n + 1));
-    get_host(u_data, p->Uc.val, sizeof(double) * (size_t)p->Uc.nnz); get_host(u_indices, p->Uc.idx, sizeof(int32_t) * (size_t)p->Uc.nnz); get_host(u_indptr, p->Uc.ptr, sizeof(int32_t) * (n + 1));
-    get_host(middle, l.D, sizeof(double) * n);
-    get_host(perm_rows, l.pr, sizeof(int32_t) * n); get_host(perm_cols, l.pc, sizeof(int32_t) * n);
-    get_host(inv_perm_rows, l.ipr, sizeof(int32_t) * n); get_host(inv_perm_cols, l.ipc, sizeof(int32_t) * n);
-    get_host(d_left, l.Dl, sizeof(double) * n); get_host(d_right, l.Dr, sizeof(double) * n);
-    return ILUPP_OK;
-    API_CATCH
-}
-
-int ilupp_hip_ml_timings(const ilupp_ml *m, float *construct_ms, float *kernel_ms, float *last_apply_ms)
-{
-    if (!m) return ILUPP_ERR_INVALID;
-    if (construct_ms) *construct_ms = m->construct_ms;
-    if (kernel_ms) *kernel_ms = m->kernel_ms;
-    if (last_apply_ms) *last_apply_ms = m->last_apply_ms;
-    return ILUPP_OK;
-}
-
-}  // extern "C"
-
-// ---- many members applied at once: one launch, one workgroup per member (k_pivot_apply_batch, sptrsv_batch.hip) ----
-namespace {
-
-// One array of the batched entries' scratch: `cap` elements on the device (d) and, where the instance is pinned, as many in page-locked
-// host memory (h), with the event that says the last upload from there is over (never recorded: over).  It only grows, and is never
-// smaller than its floor: the descriptor tables start at 64 entries, the staging blocks take exactly what is asked for.
-template <class T>
-struct BatchBuf {
-    const size_t floor;
-    const bool pinned;
-    T *d = nullptr, *h = nullptr;
-    size_t cap = 0;
-    size_t used = 0;              // batch_upload's cache: so many entries of h are on the device as they stand there (0 = none)
-    hipEvent_t up = nullptr;
-    BatchBuf(size_t floor_, bool pinned_) : floor(floor_), pinned(pinned_) {}
-    // Room for `want` elements.  true: the arrays are new ones and what the old ones held is gone.  Work queued on `st` may still read
-    // the old ones, hence the wait before they are freed.  A growth that throws leaves cap == 0 and each pointer either null or
-    // allocated: nothing is reached through a buffer without capacity, and the next call frees what is there and starts over.
-    bool reserve(hipStream_t st, size_t want)
-    {
-        if (want <= cap) return false;
-        if (d) ILUPP_HIP(hipStreamSynchronize(st));
-        cap = 0;
-        if (d) (void)hipFree(d);
-        if (h) (void)hipHostFree(h);
-        d = h = nullptr;
-        if (pinned && !up) ILUPP_HIP(hipEventCreateWithFlags(&up, hipEventDisableTiming));
-        const size_t n = want < floor ? floor : want;
-        ILUPP_HIP(hipMalloc(reinterpret_cast<void **>(&d), sizeof(T) * n));
-        if (pinned) ILUPP_HIP(hipHostMalloc(reinterpret_cast<void **>(&h), sizeof(T) * n, hipHostMallocDefault));
-        cap = n;
-        return true;
-    }
-};
-
-// `fresh` (at least one entry) into B's pinned copy and from there to the device, on `st`.  cached: nothing is sent when the count and
-// the bytes are those the device holds already -- the same members with the same buffers, call after call -- and what is sent is
-// remembered.  Not cached: always sent and nothing remembered (a table nobody describes a second time).
-template <class T>
-void batch_upload(hipStream_t st, BatchBuf<T> &B, const std::vector<T> &fresh, bool cached = true)
-{
-    const size_t nl = fresh.size(), bytes = sizeof(T) * nl;
-    if (B.reserve(st, nl)) B.used = 0;
-    if (cached && nl == B.used && memcmp(B.h, fresh.data(), bytes) == 0) return;
-    ILUPP_HIP(hipEventSynchronize(B.up));                               // (the upload before this one has read the pinned copy: long over)
-    B.used = 0;
-    memcpy(B.h, fresh.data(), bytes);
-    ILUPP_HIP(hipMemcpyAsync(B.d, B.h, bytes, hipMemcpyHostToDevice, st));
-    ILUPP_HIP(hipEventRecord(B.up, st));
-    if (cached) B.used = nl;
-}
-
-// What the batched entries keep from call to call, one per device: a stream, the events that order it, what the last describing pass
-// left, and the arrays that grow with the largest call so far.
-struct BatchScratch {
-    hipStream_t stream = nullptr;
-    hipEvent_t cev[2] = {nullptr, nullptr};       // ordering against the caller's stream
-    hipEvent_t in_ev = nullptr, done_ev = nullptr;      // the staged vectors are there; the launch is over
-    hipEvent_t tev[4] = {nullptr, nullptr, nullptr, nullptr};      // around the two launches of a batched construction (timed; made there)
-    std::vector<PivotApplyDesc> fresh;            // the descriptors of the launch
-    std::vector<int32_t> launched, route, h_err, status;      // member of workgroup k; per member: route, error word, code
-    BatchBuf<PivotApplyDesc> table{64, true};     // the descriptors of an apply or a solve, cached: another member list, direction or vector layout uploads
-    BatchBuf<int32_t> err{64, false};             // ... and the error word of each
-    BatchBuf<PivotSolveDesc> sys{64, true};       // a solve's second table (the members' matrices), sent with every call
-    BatchBuf<double> tmp{0, false};               // the hand-over vectors (`tmp`) of a launch's non-pivoting members, one block: n doubles each
-    BatchBuf<double> stage{0, true};              // the host entries' packed block: the vectors of an apply, the matrices of a construction
-    // the descriptors of an ILU(0) re-factorisation or construction, cached apart from `table`: the apply's cache still hits after a re-factorisation
-    BatchBuf<RefactorDesc> rtable{64, true};
-    BatchBuf<CreateInfo> cinfo{64, true};         // a construction's symbolic records, read back through the pinned copy
-    BatchBuf<int32_t> cstat{64, false};           // ... and the status words of its create launch
-    // a batched ILUT construction: the members' descriptors, the ticket maps of its rows launches (segments, then the member order) and the
-    // members' records, read back through the pinned copy
-    BatchBuf<IlutBatchDesc> ttable{64, true};
-    BatchBuf<int32_t> ttick{512, true};
-    BatchBuf<IlutBatchInfo> tinfo{64, true};
-    // the two tables of a batched multilevel apply (member records, and the level records of all of them), each cached on its own
-    BatchBuf<MlApplyDesc> mltable{64, true};
-    BatchBuf<MlLevelDesc> mllevels{64, true};
-    std::vector<MlApplyDesc> mfresh;              // the member records of a multilevel apply's launch (S.fresh stays empty there)
-    // the level records of a launch's multilevel members (one table, uploaded through mllevels) and, per workgroup of a solve's launch, where
-    // its member's records start there (-1: not a multilevel member)
-    std::vector<MlLevelDesc> lfresh;
-    std::vector<int32_t> ml_first;
-};
-
-// One member as the batched kernels see it, whatever class it comes from: the object that holds the two triangles, the pivoting
-// permutation (or none) and the side it stands on, and the n doubles the one-array path hands its first sweep's result over in.  A
-// pivoting member brings its own tmp and is ordered through its owner's batch_ev; a non-pivoting one (owner == nullptr) gets a slice of
-// the scratch's block, which only launches on the scratch's stream ever touch, and is ordered through p->batch_ev.  p == nullptr: a
-// member without a preconditioner (the CG solve only).  ml: a multilevel member, of the batched apply or the BiCGstab solve (p stays null:
-// its levels are objects of their own, described from what ml_apply_dev reads, ordered through every level's batch_ev, its scratch the
-// object's own buf).
-struct BatchMember {
-    ilupp_precond *p = nullptr;
-    ilupp_ilucp *owner = nullptr;
-    ilupp_ml *ml = nullptr;
-    const int32_t *perm = nullptr;
-    bool plain_first = true;
-    double *tmp = nullptr;
-    int32_t n = 0;
-    hipEvent_t *batch_ev() const { return owner ? &owner->batch_ev : p ? &p->batch_ev : nullptr; }
-};
-BatchMember batch_member(ilupp_ilucp *m, int transpose)
-{
-    BatchMember v;
-    v.p = m->obj; v.owner = m; v.perm = m->perm; v.plain_first = pivot_plain_first(m, transpose); v.tmp = m->tmp; v.n = m->n;
-    return v;
-}
-BatchMember batch_member(ilupp_precond *p, int transpose)
-{
-    BatchMember v;
-    v.p = p; v.plain_first = transpose == 0; v.n = p->n;
-    return v;
-}
-BatchMember batch_member(ilupp_ml *m, int transpose)
-{
-    BatchMember v;
-    v.ml = m; v.plain_first = transpose == 0; v.n = m->n;
-    return v;
-}
-// the object whose stream a member's own work is queued on (a multilevel member: the first level's, which the others borrow)
-ilupp_precond *batch_stream_obj(const BatchMember &v) { return v.ml ? v.ml->obj[0] : v.p; }
-// a launch that reads the member is recorded in `ev` (nullptr: it has been waited for)
-void batch_mark(const BatchMember &v, hipEvent_t ev)
-{
-    if (v.ml) { for (ilupp_precond *p : v.ml->obj) p->batch_ev = ev; return; }
-    if (hipEvent_t *slot = v.batch_ev()) *slot = ev;
-}
-template <class Handle>
-std::vector<BatchMember> batch_members(int32_t count, Handle *const *members, int transpose)
-{
-    std::vector<BatchMember> v((size_t)count);
-    for (int32_t i = 0; i < count; ++i) v[(size_t)i] = batch_member(members[i], transpose);
-    return v;
-}
-std::mutex g_batch_mu;
-std::map<int, BatchScratch> g_batch_scratch;
-
-BatchScratch &batch_scratch()
-{
-    int dev = 0;
-    ILUPP_HIP(hipGetDevice(&dev));
-    BatchScratch &S = g_batch_scratch[dev];
-    if (!S.done_ev) {
-        if (!S.stream) ILUPP_HIP(hipStreamCreateWithFlags(&S.stream, hipStreamNonBlocking));
-        for (hipEvent_t *e : {&S.cev[0], &S.cev[1], &S.in_ev, &S.done_ev})       // (done_ev comes last: a scratch that has it is complete)
-            if (!*e) ILUPP_HIP(hipEventCreateWithFlags(e, hipEventDisableTiming));
-    }
-    return S;
-}
-
-// ILUPP_BATCH_APPLY_MAX_N lowers the n up to which a member goes to a launch (read per call)
-int64_t batch_env_cap(int64_t cap_n)
-{
-    if (const char *e = getenv("ILUPP_BATCH_APPLY_MAX_N")) { const long long v = atoll(e); if (v >= 0 && v < cap_n) cap_n = v; }
-    return cap_n;
-}
-
-// n up to which a member goes to the apply's launch: 8 n bytes of LDS must fit
-int64_t batch_apply_max_n() { return batch_env_cap((int64_t)(pivot_apply_batch_lds_cap() / 8)); }
-
-// ... a multilevel member to the apply's launch (k_ml_apply_batch): the 8 n bytes of LDS its first level's sweeps take must fit
-int64_t ml_apply_batch_cap_n() { return batch_env_cap((int64_t)(ml_apply_batch_lds_cap() / 8)); }
-
-// ... to a solver's launch: the cap of the apply's launch, lowered by what the dot scratch takes
-// (ml: the launch of k_bicgstab_batch<true>, which a batch with a multilevel member runs: that instantiation's own cap)
-int64_t solve_batch_cap_n(BatchSolver solver, bool ml = false)
-{
-    const int64_t a = batch_apply_max_n(), b = solve_batch_max_n(solver, ml);
-    return a < b ? a : b;
-}
-
-// ... to the re-factorisation's and the construction's launches: one flag word per row of LDS
-int64_t refactor_batch_max_n() { return batch_env_cap(ilu0_refactor_batch_max_n()); }
-
-// the scratch's stream behind whatever is still queued on a member's own stream (a single apply or factors() that was not waited for,
-// the transposed storages of a first use)
-void batch_join(hipStream_t bs, ilupp_precond *p)
-{
-    if (!p || hipStreamQuery(p->stream) == hipSuccess) return;
-    (void)hipGetLastError();
-    ILUPP_HIP(hipEventRecord(p->sev[1], p->stream));
-    ILUPP_HIP(hipStreamWaitEvent(bs, p->sev[1], 0));
-}
-
-// the routes of a call into the caller's array, if it gave one
-void routes_out(const std::vector<int32_t> &from, int32_t *route)
-{
-    if (route) std::copy(from.begin(), from.end(), route);
-}
-
-// One record per level of a multilevel member, appended to `out`, from what ml_apply_dev reads: apply_plan(KIND_UTU, ...) and
-// sweep_parts on the level's object for the two halves (the caller has run ensure_transposed on every level, as utu_half does), the
-// level's diagonals and the two index arrays of the direction.
-void ml_level_records(ilupp_ml *m, bool tr, std::vector<MlLevelDesc> *out)
-{
-    const ApplyPlan plan = apply_plan(KIND_UTU, tr, false, false);
-    for (size_t k = 0; k < m->obj.size(); ++k) {
-        const MlLevelDev &l = m->dev[k];
-        const DevMat &M1 = sweep_parts(m->obj[k], plan.first).M, &M2 = sweep_parts(m->obj[k], plan.second).M;
-        MlLevelDesc e;
-        memset(&e, 0, sizeof(e));
-        e.n = l.n; e.kind1 = plan.first.kind; e.kind2 = plan.second.kind;
-        e.ptr1 = M1.ptr; e.idx1 = M1.idx; e.val1 = M1.val;
-        e.ptr2 = M2.ptr; e.idx2 = M2.idx; e.val2 = M2.val;
-        e.D = l.D; e.Dl = l.Dl; e.Dr = l.Dr;
-        e.gather = tr ? l.pc : l.pr; e.take = tr ? l.ipr : l.ipc;
-        out->push_back(e);
-    }
-}
-
-// ... of a member whose levels are made ready first (ensure_transposed on every level, as utu_half does); false, and nothing appended,
-// when a level object is degenerate
-bool ml_member_records(ilupp_ml *m, bool tr, std::vector<MlLevelDesc> *out)
-{
-    bool degenerate = false;
-    for (ilupp_precond *p : m->obj) { ensure_transposed(p); degenerate = degenerate || p->degenerate; }
-    if (degenerate) return false;
-    ml_level_records(m, tr, out);
-    return true;
-}
-
-// Route and describe the members of a batched launch: route 0 = the launch (n <= cap_n, object not degenerate), 1 = too large, 2 = degenerate.
-// S.fresh / S.launched receive the descriptors and member numbers of route 0, from the tables the single apply uses (apply_plan,
-// sweep_parts); xoff = offsets[i].  A pivoting member is prepared as its single apply prepares it (prepare_apply).  A non-pivoting one
-// needs only the two CSR triangles with their values (ensure_csr_values: a static-form ILU(0) leaves them unwritten; ensure_transposed
-// when the plan reads slot 2 or 3): one whose single apply would take a static form goes to the launch all the same -- every route has
-// the reference's bits -- and no static analysis runs merely to describe it.  Its tmp is a slice of the scratch's block (batch_tmp).
-// take_ml == false: the launch is one without multilevel members -- they stay out of it whatever their n (route 1; the caller knows better).
-void batch_describe(BatchScratch &S, int32_t count, const BatchMember *members, const int64_t *offsets, int64_t cap_n, bool take_ml = true)
-{
-    S.route.assign((size_t)count, 0); S.status.assign((size_t)count, ILUPP_OK); S.h_err.assign((size_t)count, 0);
-    S.launched.clear(); S.fresh.clear(); S.lfresh.clear(); S.ml_first.clear();
-    for (int32_t i = 0; i < count; ++i) {
-        const BatchMember &v = members[i];
-        ilupp_precond *p = v.p;
-        if (v.n > cap_n || (v.ml && !take_ml)) { S.route[(size_t)i] = 1; continue; }
-        PivotApplyDesc d;
-        memset(&d, 0, sizeof(d));
-        d.n = v.n; d.xoff = offsets[i];
-        int32_t ml_first = -1;
-        if (v.ml) {
-            // a multilevel member (k_bicgstab_batch<true>): plain_first == 2, kind1 levels from ptr1 (set by batch_stage, when the level
-            // table's place on the device is known), kind2 the direction, tmp the object's own scratch
-            ml_first = (int32_t)S.lfresh.size();
-            if (!ml_member_records(v.ml, !v.plain_first, &S.lfresh)) { S.route[(size_t)i] = 2; continue; }
-            d.plain_first = 2; d.kind1 = (int32_t)v.ml->obj.size(); d.kind2 = v.plain_first ? 0 : 1; d.tmp = v.ml->buf;
-        } else if (p) {
-            const ApplyPlan plan = apply_plan(p, v.plain_first ? 0 : 1);
-            if (v.owner) {
-                PackedSweep *pf = nullptr, *pb = nullptr;
-                if (prepare_apply(p, plan, &pf, &pb) != ROUTE_SWEEPS || p->degenerate) { S.route[(size_t)i] = 2; continue; }
-            } else {
-                ensure_csr_values(p);
-                if (plan.transposed()) ensure_transposed(p);
-                if (p->degenerate) { S.route[(size_t)i] = 2; continue; }
-            }
-            const DevMat &M1 = sweep_parts(p, plan.first).M, &M2 = sweep_parts(p, plan.second).M;
-            d.kind1 = plan.first.kind; d.kind2 = plan.second.kind; d.plain_first = v.plain_first ? 1 : 0;
-            d.ptr1 = M1.ptr; d.idx1 = M1.idx; d.val1 = M1.val;
-            d.ptr2 = M2.ptr; d.idx2 = M2.idx; d.val2 = M2.val;
-            d.perm = v.perm; d.tmp = v.tmp;
-        }
-        S.fresh.push_back(d);
-        S.launched.push_back(i);
-        S.ml_first.push_back(ml_first);
-    }
-}
-
-// the hand-over vectors of the launch's non-pivoting members: slices of one block of the scratch, in the order of the launch
-void batch_tmp(BatchScratch &S, const BatchMember *members)
-{
-    size_t total = 0;
-    for (int32_t i : S.launched) if (members[i].p && !members[i].owner) total += (size_t)members[i].n;
-    S.tmp.reserve(S.stream, total);
-    size_t at = 0;
-    for (size_t k = 0; k < S.launched.size(); ++k) {
-        const BatchMember &v = members[S.launched[k]];
-        if (v.p && !v.owner) { S.fresh[k].tmp = S.tmp.d + at; at += (size_t)v.n; }
-    }
-}
-
-// The described members (at least one) made ready for their launch on the scratch's stream: the bytes of LDS the sweeps of the launch take
-// (returned), the error words, the descriptor table on the device (uploaded again only when a descriptor differs), and the stream behind
-// whatever is still queued on a member's own stream.
-size_t batch_stage(BatchScratch &S, const BatchMember *members, int64_t cap_n)
-{
-    hipStream_t bs = S.stream;
-    batch_tmp(S, members);
-    // both arrays in LDS where 16 n bytes fit under the cap, else one: the launch takes what its largest member needs
-    size_t lds = 0;
-    const size_t cap_bytes = (size_t)cap_n * 8;
-    for (const PivotApplyDesc &d : S.fresh) {
-        const size_t two = (size_t)16 * (size_t)d.n, want = two <= cap_bytes ? two : (size_t)8 * (size_t)d.n;
-        if (want > lds) lds = want;
-    }
-    // (the kernel makes the same choice per member from the launch's size: 16 n <= lds exactly when 16 n <= the cap)
-    S.err.reserve(bs, S.fresh.size());
-    for (size_t k = 0; k < S.fresh.size(); ++k) S.fresh[k].err = S.err.d + k;
-    if (!S.lfresh.empty()) {
-        // (the level table first: a multilevel member's descriptor points into it)
-        if (S.mllevels.reserve(bs, S.lfresh.size())) S.mllevels.used = 0;
-        for (size_t k = 0; k < S.fresh.size(); ++k)
-            if (S.ml_first[k] >= 0) S.fresh[k].ptr1 = reinterpret_cast<const int32_t *>(S.mllevels.d + S.ml_first[k]);
-        batch_upload(bs, S.mllevels, S.lfresh);
-    }
-    batch_upload(bs, S.table, S.fresh);
-    for (int32_t i : S.launched) batch_join(bs, batch_stream_obj(members[i]));
-    return lds;
-}
-
-// behind the launch: what touches a member's tmp or rewrites its factors comes after it (a pivoting member's later single apply, any
-// member's re-factorisation and destruction)
-void batch_launched(BatchScratch &S, const BatchMember *members)
-{
-    ILUPP_HIP(hipEventRecord(S.done_ev, S.stream));
-    for (int32_t i : S.launched) batch_mark(members[i], S.done_ev);
-}
-
-// The second table of a batched solve on the device: for every launched member (at least one) its matrix, its own words of the per-member
-// outputs and where its `wf` vectors of n start in the workspace -- member i's behind those of the members before it, launched or not.
-void batch_systems(BatchScratch &S, int32_t count, const BatchMember *members, int64_t wf, const double *const *d_data,
-                   const int32_t *const *d_indices, const int32_t *const *d_indptr)
-{
-    std::vector<int64_t> woff((size_t)count);
-    int64_t total = 0;
-    for (int32_t i = 0; i < count; ++i) { woff[(size_t)i] = wf * total; total += members[i].n; }
-    std::vector<PivotSolveDesc> fresh;
-    fresh.reserve(S.launched.size());
-    for (int32_t i : S.launched) {
-        PivotSolveDesc e;
-        e.aval = d_data[i]; e.aidx = d_indices[i]; e.aptr = d_indptr[i];
-        e.woff = woff[(size_t)i]; e.member = i; e.pad = 0;
-        fresh.push_back(e);
-    }
-    batch_upload(S.stream, S.sys, fresh, false);
-}
-
-// Route and describe the members of a batched MULTILEVEL apply (k_ml_apply_batch), as batch_describe does for the other classes: route 0 =
-// the launch (n <= cap_n, no level object degenerate), 1 = too large, 2 = degenerate.  S.mfresh / S.lfresh / S.launched receive a member's
-// record, one record per level (ml_member_records) and the member numbers of route 0; a member's scratch is the object's own buf.
-void ml_apply_describe(BatchScratch &S, int32_t count, const BatchMember *members, const int64_t *offsets, int64_t cap_n)
-{
-    S.route.assign((size_t)count, 0); S.status.assign((size_t)count, ILUPP_OK); S.h_err.assign((size_t)count, 0);
-    S.launched.clear(); S.fresh.clear(); S.mfresh.clear(); S.lfresh.clear();
-    for (int32_t i = 0; i < count; ++i) {
-        ilupp_ml *m = members[i].ml;
-        if (m->n > cap_n) { S.route[(size_t)i] = 1; continue; }
-        const bool tr = !members[i].plain_first;
-        MlApplyDesc d;
-        memset(&d, 0, sizeof(d));
-        d.n = m->n; d.levels = (int32_t)m->obj.size(); d.first = (int32_t)S.lfresh.size(); d.transpose = tr ? 1 : 0;
-        d.xoff = offsets[i]; d.tmp = m->buf;
-        if (!ml_member_records(m, tr, &S.lfresh)) { S.route[(size_t)i] = 2; continue; }
-        S.mfresh.push_back(d);
-        S.launched.push_back(i);
-    }
-}
-
-// ... made ready for their launch, as batch_stage does: the bytes of LDS (8 n of the largest member, returned), the error words, the two
-// tables (each uploaded again only when a record of it differs), and the stream behind whatever is still queued on a member's own stream
-size_t ml_apply_stage(BatchScratch &S, const BatchMember *members)
-{
-    hipStream_t bs = S.stream;
-    size_t lds = 0;
-    for (const MlApplyDesc &d : S.mfresh) if ((size_t)8 * (size_t)d.n > lds) lds = (size_t)8 * (size_t)d.n;
-    S.err.reserve(bs, S.mfresh.size());
-    for (size_t k = 0; k < S.mfresh.size(); ++k) S.mfresh[k].err = S.err.d + k;
-    batch_upload(bs, S.mltable, S.mfresh);
-    batch_upload(bs, S.mllevels, S.lfresh);
-    // (the levels of a member share the first one's stream: one join per member)
-    for (int32_t i : S.launched) batch_join(bs, batch_stream_obj(members[i]));
-    return lds;
-}
-
-// the single apply of a member on its own stream, and what waits for it
-int batch_single_apply(const BatchMember &v, double *x, int transpose)
-{
-    return v.ml ? ml_apply_dev(v.ml, x, transpose) : v.owner ? pivot_apply_dev(v.owner, x, transpose) : apply_dev(v.p, x, transpose);
-}
-int batch_single_finish(const BatchMember &v) { return v.ml ? ml_finish_apply(v.ml) : finish_apply(v.p); }
-
-// Queue the applies of all members (all of one class): route 0 = the launch (n within the LDS cap, object not degenerate), 1 = too large (for
-// the LDS, or for a launch it would have to itself) and 2 = degenerate through the single apply on the member's own stream.  Multilevel
-// members have a launch, a cap and tables of their own (ml_apply_describe); everything else is one path.  Everything is joined on the
-// scratch's stream when this returns; nothing is waited for.
-// staged: the vectors were put there by work on the scratch's stream (the host entry), not by the caller's stream.
-int apply_batch_run(BatchScratch &S, int32_t count, const BatchMember *members, double *d_x, const int64_t *offsets, int transpose, bool staged)
-{
-    hipStream_t bs = S.stream;
-    if (!staged) order_after_caller(bs, S.cev[0]);
-    else ILUPP_HIP(hipEventRecord(S.in_ev, bs));
-    const bool ml = members[0].ml != nullptr;
-    const int64_t cap_n = ml ? ml_apply_batch_cap_n() : batch_apply_max_n();
-    if (ml) ml_apply_describe(S, count, members, offsets, cap_n);
-    else batch_describe(S, count, members, offsets, cap_n);
-    // ONE member in the launch is one workgroup of 256 lanes walking all its rows, 0.06 ms + 0.015 ms per 1 000 rows, where the general sweeps
-    // of the single apply take 0.11 - 0.12 ms whatever n is: past n = 4 096 the member alone is faster on the single apply (n = 4 000: 0.92 -
-    // 1.18 x, 6 000: 1.2 - 1.5 x, 12 000: 1.9 - 2.5 x; two members of n = 12 000 break even, four take half the loop's time:
-    // profiles/r10_pivot_apply_batch.txt)
-    if (S.launched.size() == 1 && members[S.launched[0]].n > kSmallSweepMax) {
-        S.route[(size_t)S.launched[0]] = 1;
-        S.launched.clear(); S.fresh.clear(); S.mfresh.clear(); S.lfresh.clear();
-    }
-    if (!S.launched.empty()) {
-        const int32_t nl = (int32_t)S.launched.size();
-        if (ml) {
-            const size_t lds = ml_apply_stage(S, members);
-            OR_RETURN(ml_apply_batch_launch(bs, nl, S.mltable.d, S.mllevels.d, d_x, lds));
-        } else {
-            const size_t lds = batch_stage(S, members, cap_n);
-            OR_RETURN(pivot_apply_batch_launch(bs, nl, S.table.d, d_x, lds));
-        }
-        batch_launched(S, members);
-    }
-    for (int32_t i = 0; i < count; ++i) {
-        if (S.route[(size_t)i] == 0) continue;
-        ilupp_precond *q = batch_stream_obj(members[i]);
-        if (staged) ILUPP_HIP(hipStreamWaitEvent(q->stream, S.in_ev, 0));
-        OR_RETURN(batch_single_apply(members[i], d_x + offsets[i], transpose));
-        ILUPP_HIP(hipEventRecord(q->sev[1], q->stream));
-        ILUPP_HIP(hipStreamWaitEvent(bs, q->sev[1], 0));
-    }
-    return ILUPP_OK;
-}
-
-// wait for a batch that apply_batch_run queued and say how it went: status per member, the first failure returned and named by its number
-// (singles: the members of routes 1 and 2 went through their single applies -- not so behind the batched solve, which leaves them alone)
-int apply_batch_finish(BatchScratch &S, int32_t count, const BatchMember *members, bool singles = true)
-{
-    const int32_t nl = (int32_t)S.launched.size();
-    std::vector<std::string> msgs((size_t)count);
-    for (int32_t i = 0; i < count; ++i)
-        if (singles && S.route[(size_t)i] != 0) {
-            S.status[(size_t)i] = batch_single_finish(members[i]);
-            if (S.status[(size_t)i]) msgs[(size_t)i] = g_last_error;
-        }
-    std::vector<int32_t> err((size_t)(nl > 0 ? nl : 1), 0);
-    if (nl > 0) ILUPP_HIP(d2h_async(S.stream, err.data(), S.err.d, sizeof(int32_t) * (size_t)nl));
-    ILUPP_HIP(stream_sync(S.stream));
-    for (int32_t k = 0; k < nl; ++k) {
-        const int32_t i = S.launched[(size_t)k];
-        batch_mark(members[i], nullptr);
-        S.h_err[(size_t)i] = err[(size_t)k];
-        if (err[(size_t)k]) { S.status[(size_t)i] = ILUPP_ERR_TIMEOUT; msgs[(size_t)i] = "triangular solve: dependency wait timed out (factor not triangular?)"; }
-    }
-    for (int32_t i = 0; i < count; ++i)
-        if (S.status[(size_t)i]) { set_error("member " + std::to_string(i) + " of the batch: " + msgs[(size_t)i]); return S.status[(size_t)i]; }
-    return ILUPP_OK;
-}
-
-// What both device entries of the batched apply do once their arguments are checked and their members named (count > 0): queue the
-// applies, hand the routes out, and either wait for them (sync) or order the caller's stream behind them.
-int apply_batch_device(int32_t count, const std::vector<BatchMember> &mv, double *d_x, const int64_t *offsets, int transpose, int sync,
-                       int32_t *route)
-{
-    std::lock_guard<std::mutex> lk(g_batch_mu);
-    BatchScratch &S = batch_scratch();
-    const int rc = apply_batch_run(S, count, mv.data(), d_x, offsets, transpose, false);
-    routes_out(S.route, route);
-    if (rc) return rc;
-    if (sync) return apply_batch_finish(S, count, mv.data());
-    order_caller_after(S.stream, S.cev[1]);
-    return ILUPP_OK;
-}
-
-// What both host entries of the batched apply do once their arguments are checked and their members named (at least one): x[i], len[i]
-// doubles, is member i's vector, replaced by its apply.  The call has waited for everything when it returns.
-int apply_batch_host(const std::vector<BatchMember> &mv, double *const *x, const int64_t *len, int transpose, int32_t *route)
-{
-    const int32_t count = (int32_t)mv.size();
-    std::lock_guard<std::mutex> lk(g_batch_mu);
-    BatchScratch &S = batch_scratch();
-    // all vectors through ONE device buffer: one packed upload, one download
-    std::vector<int64_t> off((size_t)count);
-    size_t total = 0;
-    for (int32_t i = 0; i < count; ++i) { off[(size_t)i] = (int64_t)total; total += (size_t)len[i]; }
-    S.stage.reserve(S.stream, total);
-    for (int32_t i = 0; i < count; ++i) memcpy(S.stage.h + off[(size_t)i], x[i], sizeof(double) * (size_t)len[i]);
-    ILUPP_HIP(hipMemcpyAsync(S.stage.d, S.stage.h, sizeof(double) * total, hipMemcpyHostToDevice, S.stream));
-    int rc = apply_batch_run(S, count, mv.data(), S.stage.d, off.data(), transpose, true);
-    routes_out(S.route, route);
-    if (rc) { (void)hipStreamSynchronize(S.stream); return rc; }
-    ILUPP_HIP(hipMemcpyAsync(S.stage.h, S.stage.d, sizeof(double) * total, hipMemcpyDeviceToHost, S.stream));
-    rc = apply_batch_finish(S, count, mv.data());
-    // (a member that failed keeps its vector as it was; the others have theirs)
-    for (int32_t i = 0; i < count; ++i)
-        if (S.status[(size_t)i] == ILUPP_OK) memcpy(x[i], S.stage.h + off[(size_t)i], sizeof(double) * (size_t)len[i]);
-    return rc;
-}
-
-// ---- the argument checks the entries share, each entry in its own order: all before any device call ----
-// the host vectors of a batched apply: every one there, and as long as its member
-template <class Handle>
-int batch_vector_args(int32_t count, Handle *const *members, double *const *x, const int64_t *len)
-{
-    for (int32_t i = 0; i < count; ++i) {
-        if (!x[i]) { set_error("null argument"); return ILUPP_ERR_INVALID; }
-        if (len[i] != members[i]->n) { set_error("vector has wrong size for preconditioner!"); return ILUPP_ERR_WRONG_SIZE; }
-    }
-    return ILUPP_OK;
-}
-
-// a handle that stands twice in `seen` (a member's scratch vector and its factors serve one launch at a time)
-int batch_no_duplicates(std::vector<const void *> &seen)
-{
-    std::sort(seen.begin(), seen.end());
-    if (std::adjacent_find(seen.begin(), seen.end()) != seen.end()) { set_error("a preconditioner appears twice in the batch"); return ILUPP_ERR_INVALID; }
-    return ILUPP_OK;
-}
-
-// the three arrays of member i's matrix
-int batch_matrix_arrays(const double *const *d_data, const int32_t *const *d_indices, const int32_t *const *d_indptr, int32_t i)
-{
-    if (!d_data[i] || !d_indices[i] || !d_indptr[i]) { set_error("null argument"); return ILUPP_ERR_INVALID; }
-    return ILUPP_OK;
-}
-
-int batch_iteration_args(int32_t maxiter, int32_t check_every)
-{
-    if (maxiter < 0 || check_every < 0) { set_error("maxiter and check_every must not be negative"); return ILUPP_ERR_INVALID; }
-    return ILUPP_OK;
-}
-
-// the workspace of a solve over `total` unknowns
-int batch_workspace(BatchSolver solver, int64_t work_doubles, int64_t total)
-{
-    const int64_t wf = solve_batch_work_factor(solver);
-    if (work_doubles < wf * total) { set_error("workspace too small: " + std::to_string(wf) + " doubles per unknown of the batch"); return ILUPP_ERR_INVALID; }
-    return ILUPP_OK;
-}
-
-// null arguments, a negative count, a null member, a member named twice
-int pivot_batch_args(int32_t count, ilupp_ilucp *const *members, const void *a, const void *b)
-{
-    if (count < 0 || !members || !a || !b) { set_error("null argument"); return ILUPP_ERR_INVALID; }
-    for (int32_t i = 0; i < count; ++i) if (!members[i]) { set_error("null preconditioner"); return ILUPP_ERR_INVALID; }
-    std::vector<const void *> seen(members, members + count);
-    return batch_no_duplicates(seen);
-}
-
-// the same for a list of non-pivoting objects; null_ok: a null handle is a member without a preconditioner (the CG solve), any number of them.
-// A multilevel object handed in as a member is named before anything reads it as an ilupp_precond.
-int plain_batch_args(int32_t count, ilupp_precond *const *members, bool null_ok, const void *a, const void *b)
-{
-    if (count < 0 || !members || !a || !b) { set_error("null argument"); return ILUPP_ERR_INVALID; }
-    std::vector<const void *> seen;
-    for (int32_t i = 0; i < count; ++i) {
-        if (!members[i]) { if (null_ok) continue; set_error("null preconditioner"); return ILUPP_ERR_INVALID; }
-        if (is_live_ml(members[i])) { set_error("a multilevel preconditioner cannot be a member of a batch"); return ILUPP_ERR_INVALID; }
-        seen.push_back(members[i]);
-    }
-    return batch_no_duplicates(seen);
-}
-
-// What the three batched solves do once their arguments are checked and their members named (count > 0): the members routed and
-// described, those of route 0 solved in ONE launch of `solver`'s kernel on the scratch's stream behind the caller's, and either waited
-// for (sync) or the caller's stream ordered behind them.  Members of routes 1 and 2 are left alone.
-int solve_batch_run(BatchSolver solver, int32_t count, const std::vector<BatchMember> &mv, const double *const *d_data,
-                    const int32_t *const *d_indices, const int32_t *const *d_indptr, const double *d_b, const double *d_x0, double *d_x,
-                    const int64_t *offsets, double *d_work, int32_t maxiter, double rtol, int32_t check_every, int64_t *d_iterations,
-                    int32_t *d_flags, double *d_rr, double *d_last, int sync, int32_t *route)
-{
-    std::lock_guard<std::mutex> lk(g_batch_mu);
-    BatchScratch &S = batch_scratch();
-    hipStream_t bs = S.stream;
-    order_after_caller(bs, S.cev[0]);
-    // The launch with a multilevel member is another instantiation of the kernel with a cap of its own: the members are routed by the
-    // cap of the instantiation that is launched -- and where no multilevel member takes route 0 after all, by the other one's again, for
-    // the launch they have always had.
-    bool ml = std::any_of(mv.begin(), mv.end(), [](const BatchMember &v) { return v.ml != nullptr; });
-    int64_t cap_n = solve_batch_cap_n(solver, ml);
-    batch_describe(S, count, mv.data(), offsets, cap_n);
-    if (ml && S.lfresh.empty()) {
-        const std::vector<int32_t> routed = S.route;
-        ml = false;
-        cap_n = solve_batch_cap_n(solver, false);
-        batch_describe(S, count, mv.data(), offsets, cap_n, false);
-        for (int32_t i = 0; i < count; ++i) if (mv[(size_t)i].ml) S.route[(size_t)i] = routed[(size_t)i];
-    }
-    routes_out(S.route, route);
-    const int32_t nl = (int32_t)S.launched.size();
-    if (nl == 0) return ILUPP_OK;
-    const size_t lds = batch_stage(S, mv.data(), cap_n);
-    batch_systems(S, count, mv.data(), solve_batch_work_factor(solver), d_data, d_indices, d_indptr);
-    OR_RETURN(solve_batch_launch(solver, bs, nl, S.table.d, S.sys.d, d_b, d_x0, d_x, d_work, lds, maxiter, rtol, check_every, d_iterations,
-                                 d_flags, d_rr, d_last, ml));
-    batch_launched(S, mv.data());
-    if (sync) return apply_batch_finish(S, count, mv.data(), false);
-    order_caller_after(bs, S.cev[1]);
-    return ILUPP_OK;
-}
-
-// ---- many MULTILEVEL members applied at once: one launch, one workgroup per member (k_ml_apply_batch, sptrsv_batch.hip) ----
-// null arguments, a negative count, a null member, a member named twice
-int ml_batch_args(int32_t count, ilupp_ml *const *members, const void *a, const void *b)
-{
-    if (count < 0 || !members || !a || !b) { set_error("null argument"); return ILUPP_ERR_INVALID; }
-    for (int32_t i = 0; i < count; ++i) {
-        if (!members[i]) { set_error("null preconditioner"); return ILUPP_ERR_INVALID; }
-        if (!is_live_ml(members[i])) { set_error("member " + std::to_string(i) + " of the batch is not a multilevel preconditioner"); return ILUPP_ERR_INVALID; }
-    }
-    std::vector<const void *> seen(members, members + count);
-    return batch_no_duplicates(seen);
-}
-
-}  // namespace
-
-extern "C" {
-
-int ilupp_hip_apply_batch_device(int32_t count, ilupp_precond *const *members, double *d_x, const int64_t *offsets, int transpose, int sync,
-                                 int32_t *route)
-{
-    API_TRY
-    const int rc0 = plain_batch_args(count, members, false, d_x, offsets);
-    if (rc0 || count == 0) return rc0;
-    return apply_batch_device(count, batch_members(count, members, transpose), d_x, offsets, transpose, sync, route);
-    API_CATCH
-}
-
-int ilupp_hip_cg_batch_device(int32_t count, ilupp_precond *const *members, const int64_t *n, const double *const *d_data,
-                              const int32_t *const *d_indices, const int32_t *const *d_indptr, const int64_t *nnz, const double *d_b,
-                              const double *d_x0, double *d_x, const int64_t *offsets, double *d_work, int64_t work_doubles, int32_t maxiter,
-                              double rtol, int32_t check_every, int64_t *d_iterations, int32_t *d_flags, double *d_rr, double *d_bnorm, int sync,
-                              int32_t *route)
-{
-    API_TRY
-    OR_RETURN(plain_batch_args(count, members, true, d_x, offsets));
-    if (!n || !d_data || !d_indices || !d_indptr || !nnz || !d_b || !d_work || !d_iterations || !d_flags || !d_rr || !d_bnorm) { set_error("null argument"); return ILUPP_ERR_INVALID; }
-    OR_RETURN(batch_iteration_args(maxiter, check_every));
-    int64_t total = 0;
-    for (int32_t i = 0; i < count; ++i) {
-        OR_RETURN(batch_matrix_arrays(d_data, d_indices, d_indptr, i));
-        if (n[i] <= 0 || n[i] > INT32_MAX) { set_error("matrix has size 0!"); return ILUPP_ERR_INVALID; }
-        if (members[i] && members[i]->n != n[i]) { set_error("matrix has wrong size for preconditioner!"); return ILUPP_ERR_WRONG_SIZE; }
-        total += n[i];
-    }
-    OR_RETURN(batch_workspace(BATCH_CG, work_doubles, total));
-    if (count == 0) return ILUPP_OK;
-    std::vector<BatchMember> mv((size_t)count);
-    for (int32_t i = 0; i < count; ++i) { if (members[i]) mv[(size_t)i] = batch_member(members[i], 0); mv[(size_t)i].n = (int32_t)n[i]; }
-    return solve_batch_run(BATCH_CG, count, mv, d_data, d_indices, d_indptr, d_b, d_x0, d_x, offsets, d_work, maxiter, rtol, check_every,
-                           d_iterations, d_flags, d_rr, d_bnorm, sync, route);
-    API_CATCH
-}
-
-int64_t ilupp_hip_cg_batch_max_n(void)
-{
-    API_TRY
-    return solve_batch_cap_n(BATCH_CG);
-    API_CATCH
-}
-
-int ilupp_hip_pivot_apply_batch_device(int32_t count, ilupp_ilucp *const *members, double *d_x, const int64_t *offsets, int transpose, int sync,
-                                       int32_t *route)
-{
-    API_TRY
-    const int rc0 = pivot_batch_args(count, members, d_x, offsets);
-    if (rc0 || count == 0) return rc0;
-    return apply_batch_device(count, batch_members(count, members, transpose), d_x, offsets, transpose, sync, route);
-    API_CATCH
-}
-
-int ilupp_hip_pivot_apply_batch(int32_t count, ilupp_ilucp *const *members, double *const *x, const int64_t *len, int transpose, int32_t *route)
-{
-    API_TRY
-    OR_RETURN(pivot_batch_args(count, members, x, len));
-    OR_RETURN(batch_vector_args(count, members, x, len));
-    if (count == 0) return ILUPP_OK;
-    return apply_batch_host(batch_members(count, members, transpose), x, len, transpose, route);
-    API_CATCH
-}
-
-int ilupp_hip_pivot_bicgstab_batch_device(int32_t count, ilupp_ilucp *const *members, const double *const *d_data, const int32_t *const *d_indices,
-                                          const int32_t *const *d_indptr, const int64_t *nnz, const double *d_b, const double *d_x0, double *d_x,
-                                          const int64_t *offsets, double *d_work, int64_t work_doubles, int32_t maxiter, double rtol,
-                                          int32_t check_every, int64_t *d_iterations, int32_t *d_flags, double *d_rr, double *d_init, int sync,
-                                          int32_t *route)
-{
-    API_TRY
-    OR_RETURN(pivot_batch_args(count, members, d_x, offsets));
-    if (!d_data || !d_indices || !d_indptr || !nnz || !d_b || !d_work || !d_iterations || !d_flags || !d_rr || !d_init) { set_error("null argument"); return ILUPP_ERR_INVALID; }
-    OR_RETURN(batch_iteration_args(maxiter, check_every));
-    int64_t total = 0;
-    for (int32_t i = 0; i < count; ++i) {
-        OR_RETURN(batch_matrix_arrays(d_data, d_indices, d_indptr, i));
-        total += members[i]->n;
-    }
-    OR_RETURN(batch_workspace(BATCH_BICGSTAB, work_doubles, total));
-    if (count == 0) return ILUPP_OK;
-    return solve_batch_run(BATCH_BICGSTAB, count, batch_members(count, members, 0), d_data, d_indices, d_indptr, d_b, d_x0, d_x, offsets,
-                           d_work, maxiter, rtol, check_every, d_iterations, d_flags, d_rr, d_init, sync, route);
-    API_CATCH
-}
-
-// what ilupp_hip_bicgstab_batch_device and ilupp_hip_bicgstab_batch_ml_device do (the first without a list of multilevel members)
-static int bicgstab_batch_entry(int32_t count, ilupp_precond *const *plain, ilupp_ilucp *const *pivoted, ilupp_ml *const *multilevel, const int64_t *n,
-                                const double *const *d_data, const int32_t *const *d_indices, const int32_t *const *d_indptr,
-                                const int64_t *nnz, const double *d_b, const double *d_x0, double *d_x, const int64_t *offsets,
-                                double *d_work, int64_t work_doubles, int32_t maxiter, double rtol, int32_t check_every,
-                                int64_t *d_iterations, int32_t *d_flags, double *d_rr, double *d_init, int sync, int32_t *route)
-{
-    if (count < 0 || !d_x || !offsets || !n || !d_data || !d_indices || !d_indptr || !nnz || !d_b || !d_work || !d_iterations || !d_flags ||
-        !d_rr || !d_init) { set_error("null argument"); return ILUPP_ERR_INVALID; }
-    OR_RETURN(batch_iteration_args(maxiter, check_every));
-    // member i: pivoted[i], or plain[i], or multilevel[i], or none of them (no preconditioner); a multilevel object among `plain` is
-    // named before anything reads it as an ilupp_precond, and a member of `multilevel` must be a live one
-    std::vector<const void *> seen_plain, seen_pivoted, seen_ml;
-    int64_t total = 0;
-    for (int32_t i = 0; i < count; ++i) {
-        ilupp_precond *p = plain ? plain[i] : nullptr;
-        ilupp_ilucp *m = pivoted ? pivoted[i] : nullptr;
-        ilupp_ml *q = multilevel ? multilevel[i] : nullptr;
-        if (p && m) { set_error("member " + std::to_string(i) + " of the batch: both a pivoting and a non-pivoting preconditioner"); return ILUPP_ERR_INVALID; }
-        if (q && (p || m)) { set_error("member " + std::to_string(i) + " of the batch: both a multilevel and another preconditioner"); return ILUPP_ERR_INVALID; }
-        if (p && is_live_ml(p)) { set_error("a multilevel preconditioner cannot be a member of a batch"); return ILUPP_ERR_INVALID; }
-        if (q && !is_live_ml(q)) { set_error("member " + std::to_string(i) + " of the batch is not a multilevel preconditioner"); return ILUPP_ERR_INVALID; }
-        OR_RETURN(batch_matrix_arrays(d_data, d_indices, d_indptr, i));
-        if (n[i] <= 0 || n[i] > INT32_MAX) { set_error("matrix has size 0!"); return ILUPP_ERR_INVALID; }
-        if ((p && p->n != n[i]) || (m && m->n != n[i]) || (q && q->n != n[i])) { set_error("matrix has wrong size for preconditioner!"); return ILUPP_ERR_WRONG_SIZE; }
-        if (p) seen_plain.push_back(p);
-        if (m) seen_pivoted.push_back(m);
-        if (q) seen_ml.push_back(q);
-        total += n[i];
-    }
-    OR_RETURN(batch_no_duplicates(seen_plain));
-    OR_RETURN(batch_no_duplicates(seen_pivoted));
-    OR_RETURN(batch_no_duplicates(seen_ml));
-    OR_RETURN(batch_workspace(BATCH_BICGSTAB, work_doubles, total));
-    if (count == 0) return ILUPP_OK;
-    std::vector<BatchMember> mv((size_t)count);
-    for (int32_t i = 0; i < count; ++i) {
-        if (pivoted && pivoted[i]) mv[(size_t)i] = batch_member(pivoted[i], 0);
-        else if (plain && plain[i]) mv[(size_t)i] = batch_member(plain[i], 0);
-        else if (multilevel && multilevel[i]) mv[(size_t)i] = batch_member(multilevel[i], 0);
-        mv[(size_t)i].n = (int32_t)n[i];
-    }
-    return solve_batch_run(BATCH_BICGSTAB, count, mv, d_data, d_indices, d_indptr, d_b, d_x0, d_x, offsets, d_work, maxiter, rtol,
-                           check_every, d_iterations, d_flags, d_rr, d_init, sync, route);
-}
-
-int ilupp_hip_bicgstab_batch_device(int32_t count, ilupp_precond *const *plain, ilupp_ilucp *const *pivoted, const int64_t *n,
-                                    const double *const *d_data, const int32_t *const *d_indices, const int32_t *const *d_indptr,
-                                    const int64_t *nnz, const double *d_b, const double *d_x0, double *d_x, const int64_t *offsets,
-                                    double *d_work, int64_t work_doubles, int32_t maxiter, double rtol, int32_t check_every,
-                                    int64_t *d_iterations, int32_t *d_flags, double *d_rr, double *d_init, int sync, int32_t *route)
-{
-    API_TRY
-    return bicgstab_batch_entry(count, plain, pivoted, nullptr, n, d_data, d_indices, d_indptr, nnz, d_b, d_x0, d_x, offsets, d_work, work_doubles,
-                                maxiter, rtol, check_every, d_iterations, d_flags, d_rr, d_init, sync, route);
-    API_CATCH
-}
-
-int ilupp_hip_bicgstab_batch_ml_device(int32_t count, ilupp_precond *const *plain, ilupp_ilucp *const *pivoted, ilupp_ml *const *multilevel,
-                                       const int64_t *n, const double *const *d_data, const int32_t *const *d_indices,
-                                       const int32_t *const *d_indptr, const int64_t *nnz, const double *d_b, const double *d_x0, double *d_x,
-                                       const int64_t *offsets, double *d_work, int64_t work_doubles, int32_t maxiter, double rtol,
-                                       int32_t check_every, int64_t *d_iterations, int32_t *d_flags, double *d_rr, double *d_init, int sync,
-                                       int32_t *route)
-{
-    API_TRY
-    return bicgstab_batch_entry(count, plain, pivoted, multilevel, n, d_data, d_indices, d_indptr, nnz, d_b, d_x0, d_x, offsets, d_work,
-                                work_doubles, maxiter, rtol, check_every, d_iterations, d_flags, d_rr, d_init, sync, route);
-    API_CATCH
-}
-
-int64_t ilupp_hip_bicgstab_batch_ml_max_n(void)
-{
-    API_TRY
-    return solve_batch_cap_n(BATCH_BICGSTAB, true);
-    API_CATCH
-}
-
-int64_t ilupp_hip_bicgstab_batch_max_n(void)
-{
-    API_TRY
-    return solve_batch_cap_n(BATCH_BICGSTAB);
-    API_CATCH
-}
-
-int64_t ilupp_hip_pivot_apply_batch_max_n(void)
-{
-    API_TRY
-    return batch_apply_max_n();
-    API_CATCH
-}
-
-int ilupp_hip_ml_apply_batch_device(int32_t count, ilupp_ml *const *members, double *d_x, const int64_t *offsets, int transpose, int sync,
-                                    int32_t *route)
-{
-    API_TRY
-    const int rc0 = ml_batch_args(count, members, d_x, offsets);
-    if (rc0 || count == 0) return rc0;
-    return apply_batch_device(count, batch_members(count, members, transpose), d_x, offsets, transpose, sync, route);
-    API_CATCH
-}
-
-int ilupp_hip_ml_apply_batch(int32_t count, ilupp_ml *const *members, double *const *x, const int64_t *len, int transpose, int32_t *route)
-{
-    API_TRY
-    OR_RETURN(ml_batch_args(count, members, x, len));
-    OR_RETURN(batch_vector_args(count, members, x, len));
-    if (count == 0) return ILUPP_OK;
-    return apply_batch_host(batch_members(count, members, transpose), x, len, transpose, route);
-    API_CATCH
-}
-
-int64_t ilupp_hip_ml_apply_batch_max_n(void)
-{
-    API_TRY
-    return ml_apply_batch_cap_n();
-    API_CATCH
-}
-
-}  // extern "C"
-
-namespace {
-
-// What the batched re-factorisation and the batched first construction of ILU(0) and of IChol(0) differ in; everything else of the two
-// host scaffolds below is one copy.
-struct CreateMember;
-struct FactorBatchKind {
-    const char *name, *object;                       // in messages: "ILU0", "an ILU(0) object"
-    bool llt;                                        // one factor Lc (and its transposed copy, kept current) instead of Lc and Uc
-    int32_t alone_min;                               // rows from which a member that would have the launch to itself takes the single path
-    bool (*is_object)(const ilupp_precond *);
-    bool (*is_static)(const ilupp_precond *);        // the values live elsewhere than in the CSR factor(s), or the single path is the static form's
-    size_t (*fits)(int32_t n, int32_t max_row_len);
-    int64_t (*max_n)();
-    int (*refactor_launch)(hipStream_t, int32_t, const RefactorDesc *, int32_t *, size_t);
-    int (*symbolic_launch)(hipStream_t, int32_t, const RefactorDesc *, CreateInfo *);
-    int (*create_launch)(hipStream_t, int32_t, const RefactorDesc *, int32_t *, size_t);
-    int (*refactor_single)(ilupp_precond *, const double *, const int32_t *, const int32_t *);
-    // the single constructor inside a batched construction (staged: the matrix was uploaded on the scratch's stream, in_ev behind it)
-    int (*create_single)(const CreateMember &, int is_csr, bool staged, hipEvent_t in_ev, ilupp_precond **out);
-};
-int ilu0_create_single(const CreateMember &m, int is_csr, bool staged, hipEvent_t in_ev, ilupp_precond **out);
-int ichol0_create_single(const CreateMember &m, int is_csr, bool staged, hipEvent_t in_ev, ilupp_precond **out);
-// ONE member in the launch is one workgroup walking all its rows where the single path's factor kernels spread them over the chip, and
-// the launch then saves no host wait that matters.  ILU(0) alone: n = 1 000 takes 0.447 ms in the launch against 0.202 ms on the single
-// path, n = 4 000 0.858 against 0.167 ms (profiles/r13_refactor_batch.txt, "alone in the launch"; smaller n not measured: it stays in
-// the launch).  IChol(0) alone: n = 250 0.461 ms in the launch against 0.636 ms, n = 1 000 1.423 against 0.738 ms, n = 4 000 3.354 against
-// 0.843 ms (profiles/r16_ichol0_batch.txt, "alone in the launch"): the single path wins from the same 1 000 rows on.
-const FactorBatchKind kIlu0Batch = {"ILU0", "an ILU(0) object", false, 1000, is_ilu0_object,
-                                    [](const ilupp_precond *p) { return p->flm.built; }, ilu0_refactor_batch_fits, ilu0_refactor_batch_max_n,
-                                    ilu0_refactor_batch_launch, ilu0_symbolic_batch_launch, ilu0_create_batch_launch, ilu0_refactor_single,
-                                    ilu0_create_single};
-const FactorBatchKind kIchol0Batch = {"IChol0", "an IChol(0) object", true, 1000, is_ichol0_object,
-                                      [](const ilupp_precond *p) { return p->chol_static; }, ichol0_refactor_batch_fits, ichol0_refactor_batch_max_n,
-                                      ichol0_refactor_batch_launch, ichol0_symbolic_batch_launch, ichol0_create_batch_launch, ichol0_refactor_single,
-                                      ichol0_create_single};
-
-}  // namespace
-
-extern "C" {
-
-// one member of the launches: the matrix and the two triangles of p -- Lc and Uc, for IChol(0) Lc and its transposed copy LcT when the
-// object has one (at the symbolic launch the index and value arrays are not there yet: null) --, the number of stored entries the matrix
-// is to have, and the member's number in the call
-static RefactorDesc refactor_desc(const FactorBatchKind &K, const ilupp_precond *p, const double *aval, const int32_t *aidx, const int32_t *aptr,
-                                  int64_t nnzA, int32_t member)
-{
-    RefactorDesc d;
-    memset(&d, 0, sizeof(d));
-    d.aptr = aptr; d.aidx = aidx; d.aval = aval;
-    d.lptr = p->Lc.ptr; d.lidx = p->Lc.idx; d.lval = p->Lc.val;
-    if (!K.llt) { d.uptr = p->Uc.ptr; d.uidx = p->Uc.idx; d.uval = p->Uc.val; }
-    else if (p->haveT) { d.uptr = p->LcT.ptr; d.uidx = p->LcT.idx; d.uval = p->LcT.val; }
-    d.nnzA = nnzA; d.n = p->n; d.member = member;
-    return d;
-}
-
-// what ilupp_hip_ilu0_refactor_batch_device and ilupp_hip_ichol0_refactor_batch_device do, under the construction lock its caller holds (the construction lock first, then the
-// batch lock: pool blocks are freed below; no path takes the two in the other order)
-static int refactor_batch_locked(const FactorBatchKind &K, int32_t count, ilupp_precond *const *members, const double *const *d_data,
-                                 const int32_t *const *d_indices, const int32_t *const *d_indptr, const int64_t *nnz,
-                                 int32_t *d_status, int sync, int32_t *route)
-{
-    OR_RETURN(plain_batch_args(count, members, false, d_data, nnz));
-    if (!d_indices || !d_indptr || !d_status) { set_error("null argument"); return ILUPP_ERR_INVALID; }
-    for (int32_t i = 0; i < count; ++i) {
-        OR_RETURN(batch_matrix_arrays(d_data, d_indices, d_indptr, i));
-        if (!K.is_object(members[i])) { set_error("member " + std::to_string(i) + " of the batch: not " + K.object); return ILUPP_ERR_INVALID; }
-        if (nnz[i] != members[i]->nnzA) {
-            set_error("member " + std::to_string(i) + " of the batch: the matrix does not have the analysed pattern");
-            return ILUPP_ERR_INVALID;
-        }
-    }
-    if (count == 0) return ILUPP_OK;
-    std::lock_guard<std::mutex> lk(g_batch_mu);
-    BatchScratch &S = batch_scratch();
-    hipStream_t bs = S.stream;
-    order_after_caller(bs, S.cev[0]);
-    // routes: 0 = the launch, 1 = n above the cap or a row above the row cap (K.fits), 2 = static form (ILU(0): its values live in
-    // lane-table records; IChol(0): its single path is the static kernel)
-    const int64_t cap_n = batch_env_cap(K.max_n());
-    S.route.assign((size_t)count, 0); S.launched.clear();
-    size_t lds = 0;                                                     // what the launch's most demanding member asks for
-    for (int32_t i = 0; i < count; ++i) {
-        const ilupp_precond *p = members[i];
-        if (K.is_static(p)) { S.route[(size_t)i] = 2; continue; }
-        // (a member the batched construction built has no single numeric path, and fits by construction: the launch, whatever the cap says)
-        if (p->n > cap_n && !p->batch_built) { S.route[(size_t)i] = 1; continue; }
-        const size_t want = K.fits(p->n, p->max_row_len);
-        if (want == 0) { S.route[(size_t)i] = 1; continue; }
-        S.launched.push_back(i);
-        if (want > lds) lds = want;
-    }
-    // From K.alone_min rows on, a member that would have the launch to itself takes the single path (the measurements: at the kinds' table).
-    // ILUPP_REFACTOR_ALONE_MIN moves the threshold (read per call; the measurement sets it above n to time the launch of one member).
-    long long alone_min = K.alone_min;
-    if (const char *e = getenv("ILUPP_REFACTOR_ALONE_MIN")) { const long long v = atoll(e); if (v > 0) alone_min = v; }
-    if (S.launched.size() == 1 && members[S.launched[0]]->n >= alone_min && !members[S.launched[0]]->batch_built) { S.route[(size_t)S.launched[0]] = 1; S.launched.clear(); }
-    routes_out(S.route, route);
-    const int32_t nl = (int32_t)S.launched.size();
-    if (nl > 0) {
-        // (uploaded again only when a descriptor differs: the same members with their matrices in the same buffers, step after step, upload nothing)
-        std::vector<RefactorDesc> fresh;
-        fresh.reserve((size_t)nl);
-        for (int32_t i : S.launched) fresh.push_back(refactor_desc(K, members[i], d_data[i], d_indices[i], d_indptr[i], members[i]->nnzA, i));
-        batch_upload(bs, S.rtable, fresh);
-        // the launch behind whatever is still queued on a member's own stream; what earlier batched launches read of the factors lies on
-        // the scratch's stream itself
-        bool stale = false;
-        for (int32_t i : S.launched) {
-            ilupp_precond *p = members[i];
-            // (IChol(0): the launch writes the transposed copy too, which therefore stays; what goes are the packed sweeps of the two)
-            if (K.llt) stale = stale || p->pkL.built || p->pkL.valid || p->pkLT.built || p->pkLT.valid;
-            else stale = stale || p->pkL.valid || p->pkU.valid || p->pkL.pkT || p->pkU.pkT || p->haveT;
-            for (const auto &l : p->lvl) stale = stale || l.tried;
-            batch_join(bs, p);
-        }
-        OR_RETURN(K.refactor_launch(bs, nl, S.rtable.d, d_status, lds));
-        const std::vector<BatchMember> mv = batch_members(count, members, 0);
-        batch_launched(S, mv.data());
-        // this launch WRITES the factors: whatever a member's own stream does next (a single apply, factors(), ensure_*) comes after it
-        for (int32_t i : S.launched) ILUPP_HIP(hipStreamWaitEvent(members[i]->stream, S.done_ev, 0));
-        // copies of the old values go (as in the single path; the non-static packed sweeps too: they are rebuilt at the next single apply,
-        // not re-packed per member here).  The pool knows nothing of streams: ONE wait for the whole call before the first free, and none
-        // when no member holds such a copy -- the steady state of refactor -> cg_batch -> refactor.
-        if (stale) ILUPP_HIP(hipStreamSynchronize(bs));
-        for (int32_t i : S.launched) {
-            ilupp_precond *p = members[i];
-            p->csr_vals = true;
-            if (K.llt) { drop_llt_sweep_copies(p); continue; }      // (Lc and LcT, with LcT's schedule and descriptors, hold the new values)
-            drop_old_value_copies(p);
-            if (p->pkL.valid) { p->pkL.release(); p->pack_tried[0] = false; }
-            if (p->pkU.valid) { p->pkU.release(); p->pack_tried[1] = false; }
-        }
-    }
-    // routes 1 and 2: the single path on the member's own stream (it waits for its stream itself); the status word by the host afterwards
-    for (int32_t i = 0; i < count; ++i) {
-        if (S.route[(size_t)i] == 0) continue;
-        const int rc = K.refactor_single(members[i], d_data[i], d_indices[i], d_indptr[i]);
-        if (rc != ILUPP_OK && rc != ILUPP_ERR_INVALID && rc != ILUPP_ERR_TIMEOUT) return rc;
-        ILUPP_HIP(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(d_status + i), rc == ILUPP_OK ? 0 : rc == ILUPP_ERR_INVALID ? 1 : 2, 1, bs));
-    }
-    if (sync) {
-        std::vector<int32_t> st((size_t)count, 0);
-        ILUPP_HIP(d2h_async(bs, st.data(), d_status, sizeof(int32_t) * (size_t)count));
-        ILUPP_HIP(stream_sync(bs));
-        for (int32_t i : S.launched) members[i]->batch_ev = nullptr;
-        for (int32_t i = 0; i < count; ++i) {
-            if (st[(size_t)i] == 1) { set_error("member " + std::to_string(i) + " of the batch: the matrix does not have the analysed pattern"); return ILUPP_ERR_INVALID; }
-            if (st[(size_t)i] != 0) { set_error("member " + std::to_string(i) + " of the batch: " + K.name + ": dependency wait timed out"); return ILUPP_ERR_TIMEOUT; }
-        }
-        return ILUPP_OK;
-    }
-    order_caller_after(bs, S.cev[1]);
-    return ILUPP_OK;
-}
-
-int ilupp_hip_ilu0_refactor_batch_device(int32_t count, ilupp_precond *const *members, const double *const *d_data,
-                                         const int32_t *const *d_indices, const int32_t *const *d_indptr, const int64_t *nnz,
-                                         int32_t *d_status, int sync, int32_t *route)
-{
-    API_TRY_BUILD
-    return refactor_batch_locked(kIlu0Batch, count, members, d_data, d_indices, d_indptr, nnz, d_status, sync, route);
-    API_CATCH
-}
-
-int64_t ilupp_hip_ilu0_refactor_batch_max_n(void)
-{
-    API_TRY
-    return refactor_batch_max_n();
-    API_CATCH
-}
-
-int ilupp_hip_ichol0_refactor_batch_device(int32_t count, ilupp_precond *const *members, const double *const *d_data,
-                                           const int32_t *const *d_indices, const int32_t *const *d_indptr, const int64_t *nnz,
-                                           int32_t *d_status, int sync, int32_t *route)
-{
-    API_TRY_BUILD
-    return refactor_batch_locked(kIchol0Batch, count, members, d_data, d_indices, d_indptr, nnz, d_status, sync, route);
-    API_CATCH
-}
-
-int64_t ilupp_hip_ichol0_refactor_batch_max_n(void)
-{
-    API_TRY
-    return batch_env_cap(ichol0_refactor_batch_max_n());
-    API_CATCH
-}
-
-}  // extern "C"
-
-// ---- many ILU(0) or IChol(0) objects built at once: a symbolic launch, one read-back, a create launch (ilu0_batch.hip, ichol0_batch.hip) ----
-namespace {
-
-int refactor_in_launch(ilupp_precond *p, const double *d_data, const int32_t *d_indices, const int32_t *d_indptr)
-{
-    // (never reached from the batched re-factorisation, which holds the batch lock and sends such a member to its launch)
-    ilupp_precond *const one[1] = {p};
-    const double *const dd[1] = {d_data};
-    const int32_t *const di[1] = {d_indices}, *const dp[1] = {d_indptr};
-    const int64_t nz[1] = {p->nnzA};
-    const int rc = refactor_batch_locked(p->kind == KIND_LLT ? kIchol0Batch : kIlu0Batch, 1, one, dd, di, dp, nz, p->ctrl + 2, 1, nullptr);      // (ctrl[2]: a word no sweep of such an object uses)
-    if (rc) {
-        const std::string prefix = "member 0 of the batch: ", msg = g_last_error;
-        if (msg.compare(0, prefix.size(), prefix) == 0) set_error(msg.substr(prefix.size()));
-    }
-    return rc;
-}
-
-// one matrix of a batched construction: device CSR arrays (the caller's, or slices of the scratch's staging block), and for the host
-// entry the host arrays they were copied from
-struct CreateMember {
-    const double *data = nullptr; const int32_t *indices = nullptr, *indptr = nullptr;
-    int32_t n = 0; int64_t nnz = 0;
-    const int32_t *h_indices = nullptr, *h_indptr = nullptr;
-};
-
-// the objects of a call until it has succeeded: whatever makes it unwind destroys them all
-struct CreatedObjects {
-    std::vector<ilupp_precond *> v;
-    ~CreatedObjects() { for (ilupp_precond *p : v) if (p) { if (p->side) (void)stream_sync(p->side); destroy_obj(p); } }
-};
-
-// What the batched constructions share around their own launches, for one call: per member its code, its message, its route and its
-// object.  The first failing member is reported as "matrix i of the batch: ...", status[i] says which failed, and no object of the call
-// survives a failure (batch_build's convention).
-struct CreateShell {
-    const int32_t count;
-    const CreateMember *const m;
-    std::vector<int> rcs;
-    std::vector<std::string> msgs;
-    std::vector<int32_t> rt;
-    CreatedObjects objs;
-    bool failed = false;
-    CreateShell(BatchScratch &S, int32_t count_, const CreateMember *m_) : count(count_), m(m_), rcs((size_t)count_, ILUPP_OK), msgs((size_t)count_), rt((size_t)count_, 0)
-    {
-        for (hipEvent_t &e : S.tev) if (!e) ILUPP_HIP(hipEventCreate(&e));
-        objs.v.assign((size_t)count, nullptr);
-    }
-    void fail(int32_t i, int rc, const std::string &msg) { rcs[(size_t)i] = rc; msgs[(size_t)i] = msg; failed = true; }
-    // a member no construction of `name`'s kind takes
-    bool refused(int32_t i, const char *name)
-    {
-        if (m[i].n <= 0 || !m[i].indptr) { fail(i, ILUPP_ERR_INVALID, "matrix has size 0!"); return true; }
-        if (m[i].nnz < 0 || m[i].nnz + (int64_t)m[i].n > INT32_MAX) { fail(i, ILUPP_ERR_INVALID, std::string(name) + ": too many stored entries for 32-bit indices"); return true; }
-        return false;
-    }
-    // route 1: single(i, &object), the single constructor, on the member's own stream, next to the launches (it waits for its stream
-    // itself); nothing more is built once a member has failed
-    template <class Single>
-    void singles(Single &&single)
-    {
-        for (int32_t i = 0; i < count && !failed; ++i) {
-            if (rt[(size_t)i] != 1) continue;
-            if (objs.v[(size_t)i]) { destroy_obj(objs.v[(size_t)i]); objs.v[(size_t)i] = nullptr; }      // (it only held the two row-pointer arrays)
-            const int rc = single(i, &objs.v[(size_t)i]);
-            if (rc) fail(i, rc, g_last_error);
-        }
-    }
-    // the routes and the codes into the caller's arrays, then the first failure, or the objects handed out
-    int report(ilupp_precond **out, int32_t *status, int32_t *route)
-    {
-        routes_out(rt, route);
-        const int first = batch_first_failure(count, rcs, msgs, status);
-        if (first) return first;                     // (objs goes, and every object of the call with it)
-        for (int32_t i = 0; i < count; ++i) { out[i] = objs.v[(size_t)i]; objs.v[(size_t)i] = nullptr; }
-        return ILUPP_OK;
-    }
-};
-
-// What the entries of the batched ILU(0) and IChol(0) constructions do once the matrices are in device memory (count > 0; the caller holds the
-// construction lock and the batch lock).  staged: the matrices were uploaded on the scratch's stream (S.in_ev behind the upload), not
-// produced on the caller's.  Routes: 0 = built by the two launches; 1 = built by the single constructor inside this call (n above the cap
-// of the re-factorisation's launch, a longest row above its row cap, a matrix whose rows are not sorted or whose indices are out of
-// range -- whatever the single constructor does with it, it does here --, or a batch of one: a user who builds one object wants the
-// fully analysed one).  Failures as CreateShell reports them.
-int factor_create_batch_run(const FactorBatchKind &K, BatchScratch &S, int32_t count, const CreateMember *m, int is_csr, bool staged, ilupp_precond **out, int32_t *status,
-                          int32_t *route)
-{
-    hipStream_t bs = S.stream;
-    CreateShell C(S, count, m);
-    std::vector<int32_t> &rt = C.rt;
-    std::vector<ilupp_precond *> &objs = C.objs.v;
-    const int64_t cap_n = batch_env_cap(K.max_n());
-    std::vector<int32_t> cand;                       // the members of the symbolic launch
-    for (int32_t i = 0; i < count; ++i) {
-        if (C.refused(i, K.name)) continue;
-        if (count == 1 || m[i].n > cap_n) { rt[(size_t)i] = 1; continue; }
-        cand.push_back(i);
-    }
-    if (!staged) order_after_caller(bs, S.cev[0]);
-    const int32_t nc = (int32_t)cand.size();
-    std::vector<int32_t> launched;                   // the members of the create launch
-    std::vector<RefactorDesc> fresh;
-    float sym_ms = 0.f, create_ms = 0.f;
-    if (nc > 0) {
-        S.cinfo.reserve(bs, (size_t)count);
-        S.cstat.reserve(bs, (size_t)count);
-        // the objects, and the n + 1 row pointers of L and of U the symbolic launch writes
-        for (int32_t i : cand) {
-            ilupp_precond *p = objs[(size_t)i] = new_obj(m[i].n);
-            if (K.llt) { p->kind = KIND_LLT; p->nnz_mode = NNZ_LLT; p->llt_diag_last = true; }
-            else { p->kind = KIND_LU; p->nnz_mode = NNZ_GENERIC_LU; p->input_csc = !is_csr; }
-            for (DevMat *M : {&p->Lc, &p->Uc}) {
-                if (K.llt && M == &p->Uc) continue;
-                M->n = m[i].n; M->is_csr = true; M->owns = true;
-                ILUPP_HIP(pool_malloc(&M->ptr, sizeof(int32_t) * (size_t)(m[i].n + 1)));
-            }
-            fresh.push_back(refactor_desc(K, p, m[i].data, m[i].indices, m[i].indptr, m[i].nnz, i));
-        }
-        // (sent whatever the table holds, and the re-factorisation's cached table is gone: these descriptors are half filled)
-        batch_upload(bs, S.rtable, fresh, false);
-        ILUPP_HIP(hipEventRecord(S.tev[0], bs));
-        OR_RETURN(K.symbolic_launch(bs, nc, S.rtable.d, S.cinfo.d));
-        ILUPP_HIP(hipEventRecord(S.tev[1], bs));
-        // the call's one host wait in front of the numeric launch: all result records with one read-back
-        ILUPP_HIP(hipMemcpyAsync(S.cinfo.h, S.cinfo.d, sizeof(CreateInfo) * (size_t)nc, hipMemcpyDeviceToHost, bs));
-        ILUPP_HIP(stream_sync(bs));
-        ILUPP_HIP(hipEventElapsedTime(&sym_ms, S.tev[0], S.tev[1]));
-        for (int32_t k = 0; k < nc; ++k) {
-            const int32_t i = cand[(size_t)k];
-            const CreateInfo &o = S.cinfo.h[k];
-            ilupp_precond *p = objs[(size_t)i];
-            if (o.flags & kCreateNnzDiffers) {
-                C.fail(i, ILUPP_ERR_INVALID, std::string(K.name) + ": the number of stored entries handed in is not indptr[n]");
-            } else if (o.flags & kCreateUnsorted) {
-                rt[(size_t)i] = 1;
-            } else if (o.missing >= 0) {
-                C.fail(i, ILUPP_ERR_NO_DIAGONAL, std::string(K.name) + ": structurally missing diagonal entry in row " + std::to_string(o.missing));
-            } else {
-                if (K.fits(m[i].n, o.max_row_len) == 0) { rt[(size_t)i] = 1; continue; }
-                // exact index and value arrays, and what the object records of the factored matrix
-                p->Lc.nnz = o.nnz_l; p->Uc.nnz = o.nnz_u;
-                for (DevMat *M : {&p->Lc, &p->Uc}) {
-                    if (K.llt && M == &p->Uc) continue;
-                    ILUPP_HIP(pool_malloc(&M->idx, sizeof(int32_t) * (size_t)M->nnz));
-                    ILUPP_HIP(pool_malloc(&M->val, sizeof(double) * (size_t)M->nnz));
-                }
-                p->nnzA = m[i].nnz; p->max_row_len = o.max_row_len; p->csr_vals = true; p->batch_built = true;
-                launched.push_back(i);
-            }
-        }
-    }
-    const int32_t nl = C.failed ? 0 : (int32_t)launched.size();
-    if (nl > 0) {
-        // (this table is what the batched re-factorisation of the same members from the same buffers describes: its cache may hit)
-        fresh.clear();
-        size_t lds = 0;
-        for (int32_t i : launched) {
-            const ilupp_precond *p = objs[(size_t)i];
-            fresh.push_back(refactor_desc(K, p, m[i].data, m[i].indices, m[i].indptr, p->nnzA, i));
-            const size_t want = K.fits(m[i].n, p->max_row_len);
-            if (want > lds) lds = want;
-        }
-        batch_upload(bs, S.rtable, fresh);
-        ILUPP_HIP(hipEventRecord(S.tev[2], bs));
-        OR_RETURN(K.create_launch(bs, nl, S.rtable.d, S.cstat.d, lds));
-        ILUPP_HIP(hipEventRecord(S.tev[3], bs));
-        // whatever a member's own stream does next (an apply, factors(), ensure_*) comes after the launch that writes its factors
-        ILUPP_HIP(hipEventRecord(S.done_ev, bs));
-        for (int32_t i : launched) ILUPP_HIP(hipStreamWaitEvent(objs[(size_t)i]->stream, S.done_ev, 0));
-    }
-    C.singles([&](int32_t i, ilupp_precond **made) { return K.create_single(m[i], is_csr, staged, S.in_ev, made); });
-    if (nl > 0) {
-        // a construction synchronises: the launch is over when the call returns
-        std::vector<int32_t> st((size_t)count, 0);
-        ILUPP_HIP(d2h_async(bs, st.data(), S.cstat.d, sizeof(int32_t) * (size_t)count));
-        ILUPP_HIP(stream_sync(bs));
-        ILUPP_HIP(hipEventElapsedTime(&create_ms, S.tev[2], S.tev[3]));
-        for (int32_t i : launched) {
-            ilupp_precond *p = objs[(size_t)i];
-            if (st[(size_t)i] == 2) C.fail(i, ILUPP_ERR_TIMEOUT, std::string(K.name) + ": dependency wait timed out (invalid structure?)");
-            else if (st[(size_t)i] != 0) C.fail(i, ILUPP_ERR_INVALID, std::string(K.name) + ": the matrix changed while it was factored");
-            // (the two launches' times, shared by the call's members)
-            p->tm.analysis_ms = sym_ms; p->tm.numeric_ms = create_ms; p->tm.numeric_kernel_ms = create_ms;
-        }
-    }
-    return C.report(out, status, route);
-}
-
-// the object a single constructor inside a batched construction fills, its stream behind the upload of a staged matrix (nullptr: no stream)
-ilupp_precond *single_obj(const CreateMember &m, bool staged, hipEvent_t in_ev)
-{
-    ilupp_precond *made = new_obj(m.n);
-    if (staged && hipStreamWaitEvent(made->stream, in_ev, 0) != hipSuccess) { destroy_obj(made); (void)no_batch_stream(); return nullptr; }
-    return made;
-}
-
-int ilu0_create_single(const CreateMember &m, int is_csr, bool staged, hipEvent_t in_ev, ilupp_precond **out)
-{
-    if (staged) {
-        int32_t head[10];
-        host_head(m.h_indptr, m.h_indices, m.nnz, head);
-        ilupp_precond *made = single_obj(m, true, in_ev);
-        if (!made) return ILUPP_ERR_HIP;
-        return ilu0_create_common(borrow_csr(m.data, m.indices, m.indptr, m.n, m.nnz, true), is_csr, head, out, made);
-    }
-    const int rc = ilu0_create_device_locked(m.data, m.indices, m.indptr, m.n, is_csr, out);
-    if (rc == ILUPP_OK && (*out)->nnzA != m.nnz) { set_error("ILU0: the number of stored entries handed in is not indptr[n]"); return ILUPP_ERR_INVALID; }
-    return rc;
-}
-
-// the single constructor of `name`'s kind on a borrowed matrix: the count of stored entries checked where nothing staged it, then
-// common(A, made)
-template <class Common>
-int borrowed_create_single(const char *name, const CreateMember &m, bool staged, hipEvent_t in_ev, Common &&common)
-{
-    if (!staged && (int64_t)read_device_nnz(m.indptr, m.n) != m.nnz) {
-        set_error(std::string(name) + ": the number of stored entries handed in is not indptr[n]");
-        return ILUPP_ERR_INVALID;
-    }
-    ilupp_precond *made = single_obj(m, staged, in_ev);
-    if (!made) return ILUPP_ERR_HIP;
-    DevMat A = borrow_csr(m.data, m.indices, m.indptr, m.n, m.nnz, true);
-    return common(A, made);
-}
-
-int ichol0_create_single(const CreateMember &m, int is_csr, bool staged, hipEvent_t in_ev, ilupp_precond **out)
-{
-    (void)is_csr;                                    // (as ilupp_hip_ichol0_create)
-    return borrowed_create_single("IChol0", m, staged, in_ev, [&](DevMat &A, ilupp_precond *made) { return ichol0_create_common(A, m.n, out, made); });
-}
-
-// the arguments of the *_create_batch_device entries, then the run: run(scratch, count, members, is_csr, staged, out, status, route)
-template <class Run>
-int factor_create_batch_device(Run &&run, int32_t count, const double *const *d_data, const int32_t *const *d_indices,
-                               const int32_t *const *d_indptr, const int32_t *n, const int64_t *nnz, int is_csr, ilupp_precond **out,
-                               int32_t *status, int32_t *route)
-{
-    if (count < 0 || !d_data || !d_indices || !d_indptr || !n || !nnz || !out) { set_error("null argument"); return ILUPP_ERR_INVALID; }
-    for (int32_t i = 0; i < count; ++i) { out[i] = nullptr; if (status) status[i] = ILUPP_OK; if (route) route[i] = 0; }
-    std::vector<CreateMember> m((size_t)count);
-    for (int32_t i = 0; i < count; ++i) {
-        if (n[i] > 0) OR_RETURN(batch_matrix_arrays(d_data, d_indices, d_indptr, i));
-        m[(size_t)i].data = d_data[i]; m[(size_t)i].indices = d_indices[i]; m[(size_t)i].indptr = d_indptr[i];
-        m[(size_t)i].n = n[i]; m[(size_t)i].nnz = nnz[i];
-    }
-    if (count == 0) return ILUPP_OK;
-    std::lock_guard<std::mutex> lk(g_batch_mu);
-    return run(batch_scratch(), count, m.data(), is_csr, false, out, status, route);
-}
-
-// ... of the host-array entries: all members through ONE packed block, one upload
-template <class Run>
-int factor_create_batch_host(Run &&run, int32_t count, const double *const *data, const int32_t *const *indices,
-                             const int32_t *const *indptr, const int32_t *n, int is_csr, ilupp_precond **out, int32_t *status, int32_t *route)
-{
-    if (count < 0 || !data || !indices || !indptr || !n || !out) { set_error("null argument"); return ILUPP_ERR_INVALID; }
-    for (int32_t i = 0; i < count; ++i) { out[i] = nullptr; if (status) status[i] = ILUPP_OK; if (route) route[i] = 0; }
-    for (int32_t i = 0; i < count; ++i)
-        if (n[i] > 0) OR_RETURN(batch_matrix_arrays(data, indices, indptr, i));
-    if (count == 0) return ILUPP_OK;
-    std::lock_guard<std::mutex> lk(g_batch_mu);
-    BatchScratch &S = batch_scratch();
-    // all members through ONE packed block, one upload: per member its values, then its indices and its row pointers (each padded to 8 bytes)
-    std::vector<CreateMember> m((size_t)count);
-    std::vector<size_t> at((size_t)count);
-    size_t total = 0;
-    auto words = [](int64_t ints) { return (size_t)((ints + 1) / 2); };
-    for (int32_t i = 0; i < count; ++i) {
-        m[(size_t)i].n = n[i];
-        if (n[i] <= 0) continue;
-        const int64_t nz = indptr[i][n[i]];
-        m[(size_t)i].nnz = nz;
-        if (nz < 0 || nz + (int64_t)n[i] > INT32_MAX) continue;      // (refused per member below; nothing of it is staged)
-        at[(size_t)i] = total;
-        total += (size_t)nz + words(nz) + words((int64_t)n[i] + 1);
-    }
-    S.stage.reserve(S.stream, total > 0 ? total : 1);
-    for (int32_t i = 0; i < count; ++i) {
-        CreateMember &c = m[(size_t)i];
-        if (c.n <= 0 || c.nnz < 0 || c.nnz + (int64_t)c.n > INT32_MAX) continue;
-        const size_t nz = (size_t)c.nnz, o_idx = at[(size_t)i] + nz, o_ptr = o_idx + words(c.nnz);
-        memcpy(S.stage.h + at[(size_t)i], data[i], sizeof(double) * nz);
-        memcpy(S.stage.h + o_idx, indices[i], sizeof(int32_t) * nz);
-        memcpy(S.stage.h + o_ptr, indptr[i], sizeof(int32_t) * ((size_t)c.n + 1));
-        c.data = S.stage.d + at[(size_t)i];
-        c.indices = reinterpret_cast<const int32_t *>(S.stage.d + o_idx);
-        c.indptr = reinterpret_cast<const int32_t *>(S.stage.d + o_ptr);
-        c.h_indices = indices[i]; c.h_indptr = indptr[i];
-    }
-    if (total > 0) ILUPP_HIP(hipMemcpyAsync(S.stage.d, S.stage.h, sizeof(double) * total, hipMemcpyHostToDevice, S.stream));
-    ILUPP_HIP(hipEventRecord(S.in_ev, S.stream));
-    const int rc = run(S, count, m.data(), is_csr, true, out, status, route);
-    // (the staged matrices are read by nothing once the call is over: every member's construction has been waited for)
-    if (rc) (void)hipStreamSynchronize(S.stream);
-    return rc;
-}
-
-// the run of an ILU(0) or IChol(0) construction, as the two entry shapes above take it
-auto factor_run(const FactorBatchKind &K)
-{
-    return [&K](BatchScratch &S, int32_t count, const CreateMember *m, int is_csr, bool staged, ilupp_precond **out, int32_t *status, int32_t *route) {
-        return factor_create_batch_run(K, S, count, m, is_csr, staged, out, status, route);
-    };
-}
-
-// ---- many ILUT objects built at once: the rows of all members in one launch per LDS class (k_ilut_rows_batch, ilut_wp.hip), one read-back,
-// one fill launch (ilut.hip) ----
-
-// the single constructor inside a batched ILUT construction (route 1)
-int ilut_create_single(const CreateMember &m, int is_csr, bool staged, hipEvent_t in_ev, int32_t max_fill_in, double threshold, ilupp_precond **out)
-{
-    return borrowed_create_single("ILUT", m, staged, in_ev,
-                                  [&](DevMat &A, ilupp_precond *made) { return ilut_create_common(A, m.n, is_csr, max_fill_in, threshold, out, made); });
-}
-
-// the stream is idle when the scope ends, however it ends: the pool blocks declared before it go back only then
-struct StreamIdle {
-    hipStream_t s;
-    ~StreamIdle() { (void)hipStreamSynchronize(s); }
-};
-
-// What the two entries of the batched ILUT construction do once the matrices are in device memory (count > 0; the caller holds the
-// construction lock and the batch lock; staged as for factor_create_batch_run).  Steady state, on the scratch's stream: the descriptors and
-// the ticket maps (two small uploads), the record initialisation of all members, the rows launch (two when the members' clamped budgets
-// fall into both LDS classes), the count-and-scan launch, ONE read-back of the members' records, the index and value arrays from the pool,
-// the fill launch.  Routes: 0 = built by the launches; 1 = built by ilut_create_single inside this call -- a batch of one, a clamped budget
-// of the largest capacity class, a member whose record says status 3 (a row that fits no tier of the launch), or a call whose slabs would
-// not fit the memory budget.  Failures as CreateShell reports them.
-int ilut_create_batch_run(BatchScratch &S, int32_t count, const CreateMember *m, int is_csr, bool staged, int32_t max_fill_in, double threshold,
-                          ilupp_precond **out, int32_t *status, int32_t *route)
-{
-    hipStream_t bs = S.stream;
-    CreateShell C(S, count, m);
-    std::vector<int32_t> &rt = C.rt;
-    std::vector<ilupp_precond *> &objs = C.objs.v;
-    std::vector<int32_t> cand;                       // the members of the launches
-    std::vector<int32_t> pm((size_t)count, 1);       // the clamped budgets (ILUT.hpp:211-212)
-    size_t slab_bytes = 0;
-    int64_t rows = 0;
-    auto rec_bytes = [](int32_t p) { return ((((size_t)4 + 4 * (size_t)p + 7) & ~(size_t)7) + 8 * (size_t)p + 127) & ~(size_t)127; };
-    for (int32_t i = 0; i < count; ++i) {
-        if (C.refused(i, "ILUT")) continue;
-        const int32_t p = pm[(size_t)i] = std::min(std::max(max_fill_in, 1), m[i].n);
-        if (count == 1 || ilut_batch_class(p) < 0 || cand.size() >= 65535) { rt[(size_t)i] = 1; continue; }
-        cand.push_back(i);
-        slab_bytes += (size_t)m[i].n * ((size_t)p * 12 + 4 + rec_bytes(p));
-        rows += m[i].n;
-    }
-    // (the slabs of a call are held together: a call that asks for more than the single path's working arrays do takes the single path
-    // member by member; the tickets of a launch are counted in 32 bits)
-    if (slab_bytes > ((size_t)16 << 30) || rows > (int64_t)1 << 30) { for (int32_t i : cand) rt[(size_t)i] = 1; cand.clear(); }
-    if (!staged) order_after_caller(bs, S.cev[0]);
-    const int32_t nc = (int32_t)cand.size();
-    const bool debug = getenv("ILUPP_DEBUG") != nullptr;
-    if (nc > 0 && !C.failed) {
-        PoolBlock b_Lri, b_Lrv, b_Llen, b_Urec, b_ctrl;
-        IlutBatchWork work;
-        StreamIdle idle{bs};                         // (declared last: the wait comes before the blocks above are given back)
-        // the slabs of all members, one block per array; the control blocks behind one block of the launches' own (its words 0 and 1: the ticket counters)
-        std::vector<size_t> oL((size_t)nc), oN((size_t)nc), oU((size_t)nc);
-        size_t tL = 0, tN = 0, tU = 0;
-        for (int32_t k = 0; k < nc; ++k) {
-            const int32_t i = cand[(size_t)k];
-            oL[(size_t)k] = tL; oN[(size_t)k] = tN; oU[(size_t)k] = tU;
-            tL += (size_t)m[i].n * (size_t)pm[(size_t)i]; tN += (size_t)m[i].n; tU += (size_t)m[i].n * rec_bytes(pm[(size_t)i]);
-        }
-        ILUPP_HIP(b_Lri.alloc(sizeof(int32_t) * tL));
-        ILUPP_HIP(b_Lrv.alloc(sizeof(double) * tL));
-        ILUPP_HIP(b_Llen.alloc(sizeof(int32_t) * tN));
-        ILUPP_HIP(b_Urec.alloc(tU));
-        ILUPP_HIP(b_ctrl.alloc(128 * ((size_t)nc + 1)));
-        std::vector<IlutBatchDesc> fresh((size_t)nc);
-        std::vector<int32_t> nk((size_t)nc), cls[2];
-        int64_t max_words = 0;
-        int32_t max_n = 0;
-        for (int32_t k = 0; k < nc; ++k) {
-            const int32_t i = cand[(size_t)k], n = m[i].n, p = pm[(size_t)i];
-            ilupp_precond *q = objs[(size_t)i] = new_obj(n);
-            q->kind = KIND_LU; q->nnz_mode = NNZ_ILUT; q->input_csc = !is_csr;
-            for (DevMat *M : {&q->Lc, &q->Uc}) {
-                M->n = n; M->is_csr = true; M->owns = true;
-                ILUPP_HIP(pool_malloc(&M->ptr, sizeof(int32_t) * (size_t)(n + 1)));
-            }
-            const size_t voff = ((size_t)4 + 4 * (size_t)p + 7) & ~(size_t)7, rec = rec_bytes(p);
-            unsigned char *urec = b_Urec.as<unsigned char>() + oU[(size_t)k];
-            IlutBatchDesc &d = fresh[(size_t)k];
-            memset(&d, 0, sizeof(d));
-            d.aptr = m[i].indptr; d.aidx = m[i].indices; d.aval = m[i].data;
-            d.Lri = b_Lri.as<int32_t>() + oL[(size_t)k]; d.Lrv = b_Lrv.as<double>() + oL[(size_t)k]; d.Llen = b_Llen.as<int32_t>() + oN[(size_t)k];
-            d.Ulen = reinterpret_cast<int32_t *>(urec); d.Uri = reinterpret_cast<int32_t *>(urec + 4); d.Urv = reinterpret_cast<double *>(urec + voff);
-            d.ctrl = b_ctrl.as<int32_t>() + 32 * ((size_t)k + 1);
-            d.lptr = q->Lc.ptr; d.uptr = q->Uc.ptr;
-            d.ul = {(int32_t)(rec / 4), (int32_t)(rec / 8), (int32_t)(rec / 4)};
-            d.n = n; d.p = p; d.vw = (int32_t)(voff / 8);
-            nk[(size_t)k] = n;
-            cls[ilut_batch_class(p)].push_back(k);
-            max_words = std::max(max_words, (int64_t)n * d.ul.sv);
-            max_n = std::max(max_n, n);
-        }
-        // the ticket maps of the (at most two) rows launches: round-robin over the members that still have rows.  ILUPP_ILUT_BATCH_ORDER=member
-        // is the measurement's other order (profiles/r26_ilut_batch.txt): one member after the other.
-        const char *order_env = getenv("ILUPP_ILUT_BATCH_ORDER");
-        const bool member_major = order_env && strcmp(order_env, "member") == 0;
-        std::vector<IlutBatchSeg> seg;
-        std::vector<int32_t> order;
-        int32_t seg0[3] = {0, 0, 0};
-        int64_t tickets[2] = {0, 0};
-        for (int c = 0; c < 2; ++c) {
-            if (!cls[c].empty()) tickets[c] = ilut_batch_tickets(cls[c], nk, member_major, &seg, &order);
-            seg0[c + 1] = (int32_t)seg.size();
-        }
-        std::vector<int32_t> tick(4 * seg.size() + order.size());
-        memcpy(tick.data(), seg.data(), sizeof(IlutBatchSeg) * seg.size());
-        memcpy(tick.data() + 4 * seg.size(), order.data(), sizeof(int32_t) * order.size());
-        batch_upload(bs, S.ttable, fresh, false);
-        batch_upload(bs, S.ttick, tick, false);
-        S.tinfo.reserve(bs, (size_t)nc);
-        int32_t *d_counters = b_ctrl.as<int32_t>();
-        OR_RETURN(ilut_batch_init_launch(bs, nc, S.ttable.d, max_words, d_counters));
-        OR_RETURN(ilut_batch_work(bs, tickets[0], tickets[1], &work));
-        ILUPP_HIP(hipEventRecord(S.tev[0], bs));
-        for (int c = 0; c < 2; ++c)
-            OR_RETURN(ilut_rows_batch_launch(bs, c, S.ttable.d, reinterpret_cast<const IlutBatchSeg *>(S.ttick.d) + seg0[c], seg0[c + 1] - seg0[c],
-                                             S.ttick.d + 4 * seg.size(), (int32_t)tickets[c], d_counters + c, threshold, work));
-        ILUPP_HIP(hipEventRecord(S.tev[1], bs));
-        // (queued unconditionally behind the rows: a member that failed has lengths within its slabs like every other)
-        OR_RETURN(ilut_batch_count_launch(bs, nc, S.ttable.d, S.tinfo.d));
-        // the call's one read-back
-        ILUPP_HIP(hipMemcpyAsync(S.tinfo.h, S.tinfo.d, sizeof(IlutBatchInfo) * (size_t)nc, hipMemcpyDeviceToHost, bs));
-        ILUPP_HIP(stream_sync(bs));
-        float rows_ms = 0.f;
-        ILUPP_HIP(hipEventElapsedTime(&rows_ms, S.tev[0], S.tev[1]));
-        std::vector<int32_t> launched;
-        for (int32_t k = 0; k < nc; ++k) {
-            const int32_t i = cand[(size_t)k];
-            const IlutBatchInfo &o = S.tinfo.h[k];
-            ilupp_precond *q = objs[(size_t)i];
-            if (debug)
-                fprintf(stderr, "[ilupp] ilut_batch: member %d: %d of %d rows outgrew LDS (pool %d, U slots %d, kept %d), %d of them the pool-in-LDS tier too, status %d, rows launches %.3f ms\n",
-                        i, o.outgrew, m[i].n, o.pool, o.uslots, o.kept, o.left_tier2, o.status, rows_ms);
-            if (o.status == 3) { rt[(size_t)i] = 1; continue; }
-            if (o.status != 0) { C.fail(i, ILUPP_ERR_TIMEOUT, "ILUT: dependency wait timed out"); continue; }
-            if (o.zero_row >= 0) { C.fail(i, ILUPP_ERR_ZERO_PIVOT, "ILUT_heap: encountered zero pivot in row " + std::to_string(o.zero_row)); continue; }      // ILUT.hpp:269-270
-            q->Lc.nnz = o.nnz_l; q->Uc.nnz = o.nnz_u;
-            for (DevMat *M : {&q->Lc, &q->Uc}) {
-                ILUPP_HIP(pool_malloc(&M->idx, sizeof(int32_t) * (size_t)(M->nnz > 0 ? M->nnz : 1)));
-                ILUPP_HIP(pool_malloc(&M->val, sizeof(double) * (size_t)(M->nnz > 0 ? M->nnz : 1)));
-            }
-            q->max_row_len = o.max_row_len; q->csr_vals = true; q->batch_built = true;
-            q->tm.numeric_ms = rows_ms; q->tm.numeric_kernel_ms = rows_ms;      // (the rows launches' time, shared by the call's members)
-            IlutBatchDesc &d = fresh[(size_t)k];
-            d.lidx = q->Lc.idx; d.lval = q->Lc.val; d.uidx = q->Uc.idx; d.uval = q->Uc.val;
-            launched.push_back(i);
-        }
-        if (!C.failed && !launched.empty()) {
-            batch_upload(bs, S.ttable, fresh, false);
-            OR_RETURN(ilut_batch_fill_launch(bs, nc, S.ttable.d, max_n));
-            // whatever a member's own stream does next (an apply, factors(), ensure_*) comes after the launch that writes its factors
-            ILUPP_HIP(hipEventRecord(S.done_ev, bs));
-            for (int32_t i : launched) ILUPP_HIP(hipStreamWaitEvent(objs[(size_t)i]->stream, S.done_ev, 0));
-            // a construction synchronises: the launches are over when the call returns
-            ILUPP_HIP(stream_sync(bs));
-        }
-    }
-    C.singles([&](int32_t i, ilupp_precond **made) { return ilut_create_single(m[i], is_csr, staged, S.in_ev, max_fill_in, threshold, made); });
-    return C.report(out, status, route);
-}
-
-auto ilut_run(int32_t max_fill_in, double threshold)
-{
-    return [=](BatchScratch &S, int32_t count, const CreateMember *m, int is_csr, bool staged, ilupp_precond **out, int32_t *status, int32_t *route) {
-        return ilut_create_batch_run(S, count, m, is_csr, staged, max_fill_in, threshold, out, status, route);
-    };
-}
-
-}  // namespace
-
-extern "C" {
-
-int ilupp_hip_ilu0_create_batch_device(int32_t count, const double *const *d_data, const int32_t *const *d_indices,
-                                       const int32_t *const *d_indptr, const int32_t *n, const int64_t *nnz, int is_csr, ilupp_precond **out,
-                                       int32_t *status, int32_t *route)
-{
-    API_TRY_BUILD
-    return factor_create_batch_device(factor_run(kIlu0Batch), count, d_data, d_indices, d_indptr, n, nnz, is_csr, out, status, route);
-    API_CATCH
-}
-
-int ilupp_hip_ilu0_create_batch(int32_t count, const double *const *data, const int32_t *const *indices, const int32_t *const *indptr,
-                                const int32_t *n, int is_csr, ilupp_precond **out, int32_t *status, int32_t *route)
-{
-    API_TRY_BUILD
-    return factor_create_batch_host(factor_run(kIlu0Batch), count, data, indices, indptr, n, is_csr, out, status, route);
-    API_CATCH
-}
-
-int ilupp_hip_ichol0_create_batch_device(int32_t count, const double *const *d_data, const int32_t *const *d_indices,
-                                         const int32_t *const *d_indptr, const int32_t *n, const int64_t *nnz, int is_csr, ilupp_precond **out,
-                                         int32_t *status, int32_t *route)
-{
-    API_TRY_BUILD
-    return factor_create_batch_device(factor_run(kIchol0Batch), count, d_data, d_indices, d_indptr, n, nnz, is_csr, out, status, route);
-    API_CATCH
-}
-
-int ilupp_hip_ichol0_create_batch(int32_t count, const double *const *data, const int32_t *const *indices, const int32_t *const *indptr,
-                                  const int32_t *n, int is_csr, ilupp_precond **out, int32_t *status, int32_t *route)
-{
-    API_TRY_BUILD
-    return factor_create_batch_host(factor_run(kIchol0Batch), count, data, indices, indptr, n, is_csr, out, status, route);
-    API_CATCH
-}
-
-int ilupp_hip_ilut_create_batch_device(int32_t count, const double *const *d_data, const int32_t *const *d_indices,
-                                       const int32_t *const *d_indptr, const int32_t *n, const int64_t *nnz, int is_csr, int32_t max_fill_in,
-                                       double threshold, ilupp_precond **out, int32_t *status, int32_t *route)
-{
-    API_TRY_BUILD
-    return factor_create_batch_device(ilut_run(max_fill_in, threshold), count, d_data, d_indices, d_indptr, n, nnz, is_csr, out, status, route);
-    API_CATCH
-}
-
-int ilupp_hip_ilut_create_batch(int32_t count, const double *const *data, const int32_t *const *indices, const int32_t *const *indptr,
-                                const int32_t *n, int is_csr, int32_t max_fill_in, double threshold, ilupp_precond **out, int32_t *status,
-                                int32_t *route)
-{
-    API_TRY_BUILD
-    return factor_create_batch_host(ilut_run(max_fill_in, threshold), count, data, indices, indptr, n, is_csr, out, status, route);
     API_CATCH
 }
 

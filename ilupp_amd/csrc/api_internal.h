@@ -3,8 +3,9 @@
 // plain function that one of them defines and another calls.  Whatever one file alone uses stays in that file, static or in an
 // anonymous namespace.  Everything behind the handle types is hidden from the dynamic symbol table (the Makefile sets no
 // -fvisibility, so a non-static host function is exported otherwise): the library exports what it exported as one translation unit.
-// g_build_mu, which api.hip has always exported, stays exported.  The thread-local state (last error, pool owner, caller stream) is
-// static in api.hip and reached through set_error, order_after_caller, order_caller_after and read_device_nnz.
+// g_build_mu, which api.hip has always exported, stays exported.  The thread-local state (pool owner, caller stream) is static in
+// api.hip and reached through order_after_caller, order_caller_after and read_device_nnz; the last error's text is written through
+// set_error alone and read as g_last_error.  What only the two batched files share has a header of its own, api_batch.h.
 #pragma once
 
 #include <stdlib.h>
@@ -129,7 +130,7 @@ static_assert(offsetof(ilupp_precond, kind) == 0 && offsetof(ilupp_precond, nnz_
               "kind, nnz_mode and n are a handle's first three words");
 #pragma clang diagnostic pop
 
-// (api_pivot.hip's handle, here because the batched code reads its fields: BatchMember in api.hip takes obj, perm, tmp, n and batch_ev
+// (api_pivot.hip's handle, here because the batched code reads its fields: BatchMember in api_batch.h takes obj, perm, tmp, n and batch_ev
 // from it)
 struct ilupp_ilucp {
     int32_t n = 0;
@@ -144,6 +145,25 @@ struct ilupp_ilucp {
     hipEvent_t batch_ev = nullptr;         // a batched apply that was not waited for reads this member (and writes tmp): what the member's own stream waits for next
 };
 
+// (api_ml.hip's handle, here for the same reason: BatchMember takes n, obj, dev and buf from it.  The set of live ones, which its
+// constructor keeps, is api_ml.hip's and hidden; is_live_ml asks it)
+#pragma GCC visibility push(hidden)
+namespace ilupp {
+extern std::mutex g_ml_live_mu;
+extern std::set<const void *> g_ml_live;
+}  // namespace ilupp
+#pragma GCC visibility pop
+struct ilupp_ml {
+    ilupp_ml() { std::lock_guard<std::mutex> lk(g_ml_live_mu); g_ml_live.insert(this); }
+    ~ilupp_ml() { std::lock_guard<std::mutex> lk(g_ml_live_mu); g_ml_live.erase(this); }
+    int32_t n = 0;
+    std::vector<MlLevelDev> dev;              // per level: scalings, permutations, the middle diagonal (the factors move into `obj`)
+    std::vector<ilupp_precond *> obj;         // per level: the sweeps of its two factors
+    double *buf = nullptr;                    // n: what a sweep reads
+    double *xdev = nullptr;                   // n: staging of host vectors
+    float construct_ms = 0.f, kernel_ms = 0.f, last_apply_ms = 0.f;
+};
+
 // (from here on hidden: the handle types above keep the visibility they had, and with it their implicit constructors' weak symbols)
 #pragma GCC visibility push(hidden)
 namespace ilupp {
@@ -151,7 +171,31 @@ namespace ilupp {
 // one sweep's lane tables: the factor it runs over, its direction, where its schedule and descriptors go
 struct SweepSpec { const DevMat *M; bool fwd; Schedule *s; int32_t **desc; };
 
+// One sweep of one object: the stored triangle it walks (slot 0 = Lc, 1 = Uc, 2 = UcT, 3 = LcT: the numbering of pack_tried[] and lvl[])
+// and the manner.  Whatever else a sweep needs follows from the slot: sweep_parts.
+struct SweepOp { int slot; SweepKind kind; };
+struct SweepParts {
+    const DevMat &M; const Schedule &sch; const int32_t *desc; int32_t maxlen;      // the triangle, its schedule, descriptors, longest major slice
+    PackedSweep *pk; bool *pack_tried;                                               // its level-major or static records
+    LevelSweep *lvl;                                                                 // its renumbered copy in level order
+};
+
+// The two sweeps of an apply, in the order they run: the one place that knows which factor and which loop of the reference
+// (sparse_implementation.h:4040-4087: T1 gather forward, T2 scatter forward, T3 gather backward, T4 scatter backward) every case takes.
+// A scatter loop is a gather sweep over the transposed storage, T4 with the off-diagonal entries last-to-first (BWD_FIRST_DESC).
+struct ApplyPlan {
+    SweepOp first, second;
+    // with the level-major factor path (every in-workgroup dependency one step back) the intermediate vector may travel level-major
+    // between the two sweeps (first's ybuf, second's ysrc); y then only carries the values other workgroups poll
+    bool ylm;
+    bool transposed() const { return first.slot >= 2 || second.slot >= 2; }      // reads UcT or LcT
+};
+
+// what prepare_apply finds: the plan's sweeps, or one of the two static forms that take their place
+enum ApplyRoute { ROUTE_SWEEPS, ROUTE_STATIC_T, ROUTE_STATIC_PAIR };
+
 // ---- api.hip ----
+extern thread_local std::string g_last_error;      // (read where a member's message is kept for the batch's report; written by set_error alone)
 void order_after_caller(hipStream_t st, hipEvent_t ev);
 void order_caller_after(hipStream_t st, hipEvent_t ev);
 int32_t read_device_nnz(const int32_t *d_indptr, int32_t n);
@@ -167,8 +211,37 @@ void finish_timing(ilupp_precond *p, float kernel_ms, bool analysis_first = fals
 void utu_analyse(ilupp_precond *p);
 int apply_dev(ilupp_precond *p, double *x, int transpose);
 int finish_apply(ilupp_precond *p);
-// (the workers of a batched construction: of the multilevel batch first, of the pivoting batches since)
+// (what makes an object ready for its sweeps and the tables an apply reads them from: the multilevel apply and the batched launches'
+// describing passes ask what the single apply asks)
+void ensure_csr_values(ilupp_precond *p);
+void ensure_transposed(ilupp_precond *p);
+SweepParts sweep_parts(ilupp_precond *p, SweepOp op);
+ApplyPlan apply_plan(int kind, bool transpose, bool input_csc, bool llt_diag_last);
+ApplyPlan apply_plan(const ilupp_precond *p, int transpose);
+const PackedSweep *packed(ilupp_precond *p, SweepOp op);
+int sweep(ilupp_precond *p, SweepOp op, const PackedSweep *ps, double *rhs, double *out, int32_t *ticket, int32_t *err, double *ypk_out = nullptr, const double *ypk_in = nullptr, const int32_t *ysrc = nullptr);
+ApplyRoute prepare_apply(ilupp_precond *p, const ApplyPlan &plan, PackedSweep **pf, PackedSweep **pb);
+// (the single constructions and re-factorisations that the batched ones run for the members that stay out of their launches)
+int ilu0_create_common(const DevMat &A, int is_csr, const int32_t *head, ilupp_precond **out, ilupp_precond *made = nullptr);
+int ilu0_create_device_locked(const double *d_data, const int32_t *d_indices, const int32_t *d_indptr, int32_t n, int is_csr, ilupp_precond **out);
+int ilut_create_common(DevMat &A, int32_t n, int is_csr, int32_t max_fill_in, double threshold, ilupp_precond **out, ilupp_precond *made = nullptr);
+int ichol0_create_common(DevMat &A, int32_t n, ilupp_precond **out, ilupp_precond *made = nullptr);
+bool is_ilu0_object(const ilupp_precond *p);
+bool is_ichol0_object(const ilupp_precond *p);
+int ilu0_refactor_single(ilupp_precond *p, const double *d_data, const int32_t *d_indices, const int32_t *d_indptr);
+int ichol0_refactor_single(ilupp_precond *p, const double *d_data, const int32_t *d_indices, const int32_t *d_indptr);
+void drop_old_value_copies(ilupp_precond *p);
+void drop_llt_sweep_copies(ilupp_precond *p);
+// ---- api_ml.hip (batch_build: the workers of a batched construction, of the multilevel batch first, of the pivoting batches since) ----
+bool is_live_ml(const void *h);
+int ml_apply_dev(ilupp_ml *m, double *x, int transpose, int part = 0);
+int ml_finish_apply(ilupp_ml *m);
+int no_batch_stream();
+int batch_first_failure(int32_t count, const std::vector<int> &rcs, const std::vector<std::string> &msgs, int32_t *status);
 int batch_build(int32_t count, double worst_bytes, int32_t *status, const std::function<int(int32_t)> &build);
+// ---- api_batch_build.hip (the launch of the batched re-factorisation with this one member: the single re-factorisation of a batch-built
+// object, which has none of the single numeric paths' tables) ----
+int refactor_in_launch(ilupp_precond *p, const double *d_data, const int32_t *d_indices, const int32_t *d_indptr);
 // ---- api_pivot.hip (pivot_apply_dev: the single device apply of a pivoting member, which the batched apply runs for the members it
 // does not launch) ----
 bool pivot_plain_first(const ilupp_ilucp *m, int transpose);

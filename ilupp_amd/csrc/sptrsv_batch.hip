@@ -23,7 +23,7 @@
 // reads its right-hand sides from `tmp`.
 //
 // The non-pivoting classes (ILU0, ILUT, ILUC, IChol0, ICholT) take the same launch: a descriptor with perm == nullptr is an apply without a
-// permutation, its two triangles those of apply_plan / sweep_parts (api.hip: batch_describe).
+// permutation, its two triangles those of apply_plan / sweep_parts (api_batch.hip: batch_describe).
 //
 // Two more kernels further down, each one workgroup per system with this apply (apply_member) inside its loop: k_bicgstab_batch, the whole
 // left-preconditioned BiCGstab SOLVE of many small systems in one launch, and k_cg_batch, the whole preconditioned CG solve of many small
@@ -31,7 +31,7 @@
 // one launch.
 //
 // Between the apply's kernel and the two solvers: k_ml_apply_batch, the whole apply of MANY multilevel ILU++ preconditioners in one launch -- one workgroup per
-// member walks ml_apply_dev (api.hip) statement for statement: pass 0 upwards through the member's levels, pass 1 downwards, every level
+// member walks ml_apply_dev (api_ml.hip) statement for statement: pass 0 upwards through the member's levels, pass 1 downwards, every level
 // on the LAST n_l entries of the member's vector, each step a scale / permute into right-hand sides, ONE sweep of the level's object
 // (batch_sweep above, the unknowns in the one LDS array of n_0), and a take / permute back into the tail.
 // In place without a hazard: a level's gather reads entries of the tail that its take overwrites later, so a step never writes the tail
@@ -194,7 +194,7 @@ int pivot_apply_batch_launch(hipStream_t st, int32_t count, const PivotApplyDesc
 }
 
 // ---- the whole apply of MANY multilevel ILU++ preconditioners in ONE launch: one workgroup per member ---------------------------------
-// The apply of one member by its workgroup, in place on x (n doubles): ml_apply_dev of api.hip with the element operations of ml.hip's
+// The apply of one member by its workgroup, in place on x (n doubles): ml_apply_dev of api_ml.hip with the element operations of ml.hip's
 // vector kernels in their exact form -- a division stays a division, a multiply a separate multiply -- and batch_sweep for the sweeps, so
 // the member has the bits of its single apply.  lv: the member's level records; arr: 8 n bytes of LDS.  The hazards: the file's header.
 // *s_fail != 0 afterwards: a sweep gave up and the member stopped there.

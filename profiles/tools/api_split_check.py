@@ -1,16 +1,19 @@
 #!/usr/bin/env python3
-"""Is a cut of api.hip into api_internal.h + api.hip + api_*.hip a pure move?  (DESIGN_OTHER_PATHS.md section 4h.13)
+"""Is a cut of the C ABI's host layer into api_internal.h + api_batch.h + api.hip + api_*.hip a pure move?  (DESIGN_OTHER_PATHS.md
+section 4h.13)
 
-    python profiles/tools/api_split_check.py PARENT_API_HIP [--asm]
+    python profiles/tools/api_split_check.py PARENT [--asm]
 
-PARENT_API_HIP: the file before the cut (git show REV:ilupp_amd/csrc/api.hip > FILE).
+PARENT: the host layer before the cut -- one file where it was api.hip alone (git show REV:ilupp_amd/csrc/api.hip > FILE), else a
+directory that holds its files under their own names (git show REV:ilupp_amd/csrc/F > DIR/F for api.hip, every api_*.hip and every
+api_*.h of REV: the units of the parent then include the parent's headers, not this tree's).
 
-1. Lines.  The non-blank lines of the parent against those of api_internal.h, api.hip and the api_*.hip files of this tree, as
+1. Lines.  The non-blank lines of the parent's files against those of the two headers, api.hip and the api_*.hip files of this tree, as
    multisets.  Every line that stands on one side only is put into a class; a '-' line and a '+' line that differ in nothing but a
    linkage keyword or a default argument are paired and printed side by side.  Lines no class takes are printed under UNCLASSIFIED:
    there must be none.
-2. --asm: device code (needs hipcc).  The Makefile's flags plus --cuda-device-only -S -fuse-cuid=none on the parent and on every
-   translation unit of the cut; each kernel's instruction stream, its .amdhsa_kernel block and its metadata entry are compared.
+2. --asm: device code (needs hipcc).  The Makefile's flags plus --cuda-device-only -S -fuse-cuid=none on every translation unit of the parent
+   and of the cut; each kernel's instruction stream, its .amdhsa_kernel block and its metadata entry are compared.
 """
 import collections
 import glob
@@ -22,7 +25,8 @@ import tempfile
 
 CSRC = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "..", "ilupp_amd", "csrc")
 UNITS = ["api.hip"] + sorted(os.path.basename(p) for p in glob.glob(os.path.join(CSRC, "api_*.hip")))
-FILES = ["api_internal.h"] + UNITS
+HEADERS = ["api_internal.h", "api_batch.h"]
+FILES = HEADERS + UNITS
 
 
 def body(path):
@@ -45,13 +49,22 @@ def classify(sign, line, where):
         return 'namespace / extern "C" brace'
     if s.startswith("//"):
         return "file header / header comment"
-    if sign == "+" and where == "api_internal.h" and s.split("//")[0].rstrip().endswith(";"):
+    if sign == "+" and where in HEADERS and s.split("//")[0].rstrip().endswith(";"):
         return "declaration"
     return None
 
 
+def parent_files(parent, pattern):
+    """the parent's files that match `pattern` (a single file is api.hip)"""
+    if os.path.isdir(parent):
+        return sorted(glob.glob(os.path.join(parent, pattern)))
+    return [parent] if pattern == "api*.hip" else []
+
+
 def check_lines(parent):
-    old = collections.Counter(body(parent))
+    old = collections.Counter()
+    for f in parent_files(parent, "api*.hip") + parent_files(parent, "api*.h"):
+        old.update(body(f))
     new = collections.Counter()
     where = {}
     for f in FILES:
@@ -115,9 +128,12 @@ def check_asm(parent):
     flags += ["-I" + os.path.join(CSRC, "..", "..", "include"), "-I" + CSRC]
     hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
     with tempfile.TemporaryDirectory() as d:
-        subprocess.check_call([hipcc] + flags + ["-x", "hip", parent, "-o", os.path.join(d, "parent.s")])
-        old = kernels(os.path.join(d, "parent.s"))
-        new, home = {}, {}
+        old, new, home = {}, {}, {}
+        for i, u in enumerate(parent_files(parent, "api*.hip")):
+            subprocess.check_call([hipcc] + flags + ["-x", "hip", u, "-o", os.path.join(d, "parent%d.s" % i)])
+            for k, v in kernels(os.path.join(d, "parent%d.s" % i)).items():
+                assert k not in old, k
+                old[k] = v
         for u in UNITS:
             subprocess.check_call([hipcc] + flags + [os.path.join(CSRC, u), "-o", os.path.join(d, u + ".s")])
             for k, v in kernels(os.path.join(d, u + ".s")).items():

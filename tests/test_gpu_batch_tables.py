@@ -1,4 +1,4 @@
-"""GPU tests of the tables the batched entries keep from call to call (BatchScratch in api.hip: descriptor tables, error and status
+"""GPU tests of the tables the batched entries keep from call to call (BatchScratch in api_batch.h: descriptor tables, error and status
 words, the hand-over block, the packed staging block): a table that exists and holds a cached upload is freed and allocated again when a
 call brings more members than any call before it.  Every test goes from 5 members to 70 (the descriptor tables start at 64 entries) and
 back, and compares every operation bitwise on int64 views with the same operation done one member at a time -- on twin objects the
