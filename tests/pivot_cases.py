@@ -43,7 +43,8 @@ NOT pinned, with the reason:
   * a NaN among the KEYS of a selection (wv_argmax_first's shuffle form): a NaN never is a candidate (NaN > norm * tau is false, and a NaN
     in the row makes the norm a NaN), so no input reaches it from these two kernels.  The nonfinite cases show inf keys and NaN values.
   * select_largest on more than a few hundred candidates, n beyond 300, the 2^31 reservation refusal: sizes, not boundaries of the chain.
-  * pilucdp.hip: out of scope.  Of the helpers it shares, these cases run dp_subtract (both the prefetched first pass and the later ones),
+  * pilucdp.hip: not here.  Its two chain kernels and their hand-over have a model, cases and tests of their own: tests/dp_ref.py,
+    tests/dp_cases.py, tests/test_dp_ref.py, tests/test_gpu_dp_chains.py.  Of the helpers it shares, these cases run dp_subtract (both the prefetched first pass and the later ones),
     dp_seq_sum (mode 1), dp_sort_n, dp_touch, wv_argmax_first (integer form), wv_max_f64, wv_min_i32, select_largest and
     wave_sort_u64<true>; not dp_sort64, dp_node / dp_row / dp_ent, dp_seq_sum mode 0."""
 import collections
